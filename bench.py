@@ -9,6 +9,9 @@ headline number: verify_batch (src/batch.rs: no torsion check, R decompressed wi
 sig.x -- flags = SSA_FLAG_SIG_FLAG_BYTE, exactly what ssa_verify_batch sets); the Signature::verify
 number (flags = SSA_FLAG_CHECK_TORSION: the [q]P subgroup check, src/signature.rs:182, flag byte
 ignored) is reported beside it.  The CPU leg runs the headline's flags.
+One lane in 1024 (--forged) holds a seeded forgery -- a flipped bit of e or of the message, someone else's key or R --
+that costs a verification exactly what an honest signature costs and must be rejected: the status vector of a step is
+then a fingerprint of the run, checked lane by lane (all_verdicts_as_expected) and written by --dump-outputs.
 
 Multi-GPU: one process per GPU over RCCL.  The batch shards by signature, no data-path
 collective; the only exchange is one 8-byte all-reduce of the rejection counts per step.
@@ -28,6 +31,14 @@ invocation records both.
                    `nccl` group is initialised and every collective of the N > 1 run (scatter, broadcast, all-reduce,
                    all-gather of the MSM records, max-over-ranks, the config-4 leg) executes through RCCL on device
                    tensors -- the rehearsal of the multi-GPU code on a one-GPU box (tests/test_gpu_round3.py)
+A plain run sets up, warms up, times the steps and prints the line (metric, value, ms_per_step and what the timed steps
+themselves yield: kernel times, roofline fractions).  Everything measured beside the headline -- the torsion, MSM,
+host-path, keyed, signing, pipelined and config-4 legs, the broadcast of the strong mode, the measured multiplier peak
+and the CPU baseline -- runs only with --full (and there as before: --skip-torsion-leg / --no-cpu-baseline still drop
+their parts).
+  --dump-outputs DIR  after the timed steps, write what the last step computed (the per-signature status vector and the
+                   all-reduced rejection count) as DIR/<name>.npy in float32 / float64; the inputs are seeded, so two
+                   builds can be compared output for output
 """
 import argparse
 import hashlib
@@ -86,6 +97,9 @@ def parse_args(argv=None):
                     help="strong scaling: ONE batch of this many signatures sharded over the GPUs "
                          "(config 4: 4194304); overrides --batch")
     ap.add_argument("--corrupt", type=float, default=0.0, help="fraction of corrupted signatures (config 5)")
+    ap.add_argument("--forged", type=int, default=None,
+                    help="signatures per GPU replaced by seeded forgeries that cost a full verification (default: one "
+                         "in 1024 without --corrupt, none with it); they make the status vector a fingerprint of the run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample", type=int, default=65536)
     ap.add_argument("--skip-torsion-leg", action="store_true",
@@ -98,7 +112,35 @@ def parse_args(argv=None):
     ap.add_argument("--plumbing-only", action="store_true",
                     help="rank/launch/collective plumbing with NO GPU work (CPU test of the N>1 launch path; "
                          "prints value 0 and \"plumbing_only\": true -- never a measurement)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline (torsion, MSM, host path, keyed, signing, pipelined, "
+                         "config 4, broadcast, multiplier peak, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32/float64)")
     return ap.parse_args(argv)
+
+
+DUMP_BYTES_MAX = 48 << 20       # all ranks' dumps together stay well under 64 MB
+DUMP_SAMPLE_SEED = 0x5C4E0D0D
+
+
+def dump_outputs(dirname, status, rejected, rank, world):
+    """What a caller of the timed path receives from its last step: status.npy (one code per signature, 0 = accepted;
+    float32) and rejected.npy (the all-reduced rejection count; float64).  With several ranks every rank writes its own
+    shard as status_rank<r>.npy.  A shard larger than its share of DUMP_BYTES_MAX is written as a fixed seeded sample of
+    lanes, their indices in status_index[_rank<r>].npy (float64: 4 + 8 bytes per sampled lane)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    suffix = "" if world == 1 else "_rank%d" % rank
+    st = status.cpu().numpy()
+    if st.shape[0] * 4 > DUMP_BYTES_MAX // world:
+        cap = DUMP_BYTES_MAX // world // 12
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED + rank).choice(st.shape[0], cap, replace=False))
+        st = st[idx]
+        np.save(os.path.join(dirname, "status_index%s.npy" % suffix), idx.astype(np.float64))
+    np.save(os.path.join(dirname, "status%s.npy" % suffix), st.astype(np.float32))
+    if rank == 0:
+        np.save(os.path.join(dirname, "rejected.npy"), np.array([rejected], dtype=np.float64))
 
 
 def pow2_label(n):
@@ -346,6 +388,24 @@ def gen_batch(torch, eng, dev, n, seed, chunk=1 << 20):
     return sigs, pks, msgs, g
 
 
+FORGE_SEED = 0x5C4E0F06
+
+
+def forge(torch, sigs, pks, msgs, n, count, seed):
+    """Replace `count` seeded lanes of the batch by forgeries a verifier must reject with SSA_INVALID_SIGNATURE, each as
+    costly as an honest signature (canonical e, R and key on the curve: hash, ladder, comb and compare all run): a
+    flipped bit of e, a flipped bit of the message, someone else's key, someone else's R.  Returns the lanes."""
+    g = torch.Generator(device=sigs.device)
+    g.manual_seed(seed)
+    idx = torch.randperm(n, device=sigs.device, generator=g)[:count]
+    kinds = [idx[k * count // 4:(k + 1) * count // 4] for k in range(4)]
+    sigs[kinds[0], 50] ^= 0x02                                  # e + or - 512: still < q
+    msgs[kinds[1], 7] ^= 0x01
+    pks[kinds[2]] = pks[(kinds[2] + 1) % n]
+    sigs[kinds[3], :49] = sigs[(kinds[3] + 1) % n, :49]
+    return idx
+
+
 def distribute(rk, full, total, how):
     """rank-0-resident (sigs, pks, msgs) -> this rank's contiguous shard; returns (shard tensors, milliseconds).
     how = "scatter": every shard crosses one link once; "broadcast": the whole arrays go to every rank."""
@@ -396,6 +456,8 @@ def main():
     args = parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args))      # (the ranks inherit the real stdout)
     quiet_stdout()
@@ -427,8 +489,9 @@ def main():
             s_, p_, m_, g = gen_batch(torch, eng, dev, total, 0x5C4E0224)
             full = (s_, p_, m_)
         if world > 1:
-            (sigs_b, pks_b, msgs_b), broadcast_ms = distribute(rk, full, total, "broadcast")
-            del sigs_b, pks_b, msgs_b
+            if args.full:
+                (sigs_b, pks_b, msgs_b), broadcast_ms = distribute(rk, full, total, "broadcast")
+                del sigs_b, pks_b, msgs_b
             (sigs, pks, msgs), scatter_ms = distribute(rk, full, total, "scatter")
             sigs, pks, msgs = sigs.contiguous(), pks.contiguous(), msgs.contiguous()
         else:
@@ -444,15 +507,22 @@ def main():
         sigs, pks, msgs, g = gen_batch(torch, eng, dev, n, 0x5C4E0222 + rank)
         n_all = n * world
 
-    n_bad_expected = 0
+    bad = torch.zeros(max(n, 1), dtype=torch.bool, device=dev)      # the lanes that must be rejected
     if args.corrupt > 0:
-        n_bad_expected = int(n * args.corrupt)
-        idx = torch.randperm(n, device=dev, generator=g)[:n_bad_expected]
-        third = n_bad_expected // 3
+        n_corrupt = int(n * args.corrupt)
+        idx = torch.randperm(n, device=dev, generator=g)[:n_corrupt]
+        third = n_corrupt // 3
         sigs[idx[:third], 49] ^= 1                       # e bit flip
         msgs[idx[third:2 * third], 40] ^= 0x10           # message bit flip
         rest = idx[2 * third:]
         sigs[rest, :49] = sigs[(rest + 1) % n, :49]      # someone else's R (canonical, on curve)
+        bad[idx] = True
+    # forgeries change other bytes than the corruptions: a lane hit by both is still rejected
+    n_forged = args.forged if args.forged is not None else (0 if args.corrupt > 0 else n >> 10)
+    n_forged = min(max(n_forged, 0), n) if n >= 2 else 0
+    if n_forged:
+        bad[forge(torch, sigs, pks, msgs, n, n_forged, FORGE_SEED + rank)] = True
+    n_bad_expected = int(bad[:n].sum().item())
     status = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
     nfail = torch.zeros(1, dtype=torch.int64, device=dev)
 
@@ -478,13 +548,20 @@ def main():
     k_verify_ms, k_cnt = eng.read_timing("ssa_k_verify")
     k_hash_ms, _ = eng.read_timing("ssa_k_hash")
     total_fail = int(nfail.item())
-    status_batch_semantics = status[:min(n, args.cpu_sample)].clone()   # what the CPU leg is compared with
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, status[:n], total_fail, rank, world)
+    cpu_leg = args.full and not args.no_cpu_baseline and world == 1
+    if cpu_leg:
+        status_batch_semantics = status[:min(n, args.cpu_sample)].clone()   # what the CPU leg is compared with
     bad_total = torch.tensor([n_bad_expected], dtype=torch.int64, device=dev)
     rk.all_reduce_sum(bad_total)
-    ok = total_fail == int(bad_total.item())
+    wrong_lanes = ((status[:n] != 0) != bad[:n]).sum().view(1)        # rejected exactly where expected, lane by lane
+    rk.all_reduce_sum(wrong_lanes)
+    bad_total = int(bad_total.item())
+    ok = total_fail == bad_total and int(wrong_lanes.item()) == 0
     elapsed = rk.max_over_ranks(elapsed)
     devices = rk.device_report()
-    legs = not args.skip_torsion_leg
+    legs = args.full and not args.skip_torsion_leg
 
     # ---- Signature::verify semantics (torsion check on), 2 steps ----
     torsion_rate, total_fail_t = None, None
@@ -533,7 +610,7 @@ def main():
         stages = {k: eng.read_timing(k)[0] for k in ("ssa_k_hash", "msm_k_prepare", "msm_sort", "msm_k_buckets",
                                                      "msm_reduce", "msm_combine")}
         msm = {"verifications_per_sec": n_all * 3 / dt, "ms_per_batch": dt / 3 * 1e3,
-               "verdict": int(verdict.item()), "expected_verdict": 2 if args.corrupt > 0 else 0, "stages_ms": stages,
+               "verdict": int(verdict.item()), "expected_verdict": 2 if bad_total > 0 else 0, "stages_ms": stages,
                "combined_over_ranks": rk.dist is not None,
                "note": ("ONE verdict for the %d signatures of all %d rank(s): per-rank shard records all-gathered "
                         "(24 words each) and combined on every rank" % (n_all, world)) if rk.dist is not None else
@@ -591,6 +668,7 @@ def main():
                     if strong else "%s: %s random-keypair signatures per GPU%s"
                     % ("config5" if args.corrupt > 0 else "config3", pow2_label(n),
                        ", %g %% corrupted" % (100 * args.corrupt) if args.corrupt > 0 else "")) + \
+            (", %d forged per GPU (seeded: wrong e, message, key or R)" % n_forged if n_forged else "") + \
             ", 80-byte distinct messages, full verify (Rescue hash + [h]P+[e]G + x-compare), verify_batch semantics"
         out = {
             "metric": metric,
@@ -605,11 +683,13 @@ def main():
             "vs_baseline": None,
             "dtype": "u64",
             "data": "synthetic",
+            "full": bool(args.full),
             "config": {"workload": workload, "signatures_per_gpu": n, "signatures_total": n_all, "message_bytes": 80,
                        "flags": {"word": ssa.FLAG_SIG_FLAG_BYTE, "names": ["SSA_FLAG_SIG_FLAG_BYTE"],
                                  "meaning": "what ssa_verify_batch sets: no subgroup check, byte 48 of the signature "
                                             "honoured (src/batch.rs:104); the CPU leg runs the same flags"},
                        "parallelism": "shard%d" % world, "corrupt_fraction": args.corrupt,
+                       "forged_per_gpu": n_forged,
                        # what the context holds on the device (ssa_ctx_info, read AFTER the run): the comb for G is a
                        # speed-for-memory choice of the context (ssa_ctx_create_ex), the workspaces are per slice
                        "device_memory": (lambda i: {"gtab_window_bits": i["gtab_bits"], "gtab_windows": i["gtab_windows"],
@@ -682,13 +762,14 @@ def main():
                 "traffic": None,
             },
         }
-        try:
-            out["measured_fpmul_peak"] = {"fp_mul": eng.bench_fpmul(1), "f6_lazy": eng.bench_fpmul(3),
-                                          "unit": "Fp-mul/s"}
-        except Exception as exc:  # pragma: no cover
-            out["measured_fpmul_peak"] = str(exc)
+        if args.full:
+            try:
+                out["measured_fpmul_peak"] = {"fp_mul": eng.bench_fpmul(1), "f6_lazy": eng.bench_fpmul(3),
+                                              "unit": "Fp-mul/s"}
+            except Exception as exc:  # pragma: no cover
+                out["measured_fpmul_peak"] = str(exc)
 
-        if not args.no_cpu_baseline and world == 1:
+        if cpu_leg:
             out["cpu_baseline"] = cpu_baseline(np, sigs, pks, msgs, status_batch_semantics, min(args.cpu_sample, n))
         elif world > 1:
             out["cpu_baseline"] = None

@@ -56,7 +56,7 @@ def _bench(args, timeout=900):
 
 def test_bench_collectives_run_through_rccl_on_one_rank():
     """`--force-dist`: a world-size-1 nccl group; every collective of the N > 1 run executes on device tensors."""
-    out = _bench(["--gpus", "1", "--force-dist", "--batch", "65536", "--steps", "2", "--warmup", "1",
+    out = _bench(["--gpus", "1", "--full", "--force-dist", "--batch", "65536", "--steps", "2", "--warmup", "1",
                   "--strong-total", "131072", "--cpu-sample", "256", "--corrupt", "0.01"])
     assert out["n_gpus"] == 1 and out["config"]["backend"] == "nccl"
     assert out["config"]["process_group"].startswith("forced one-rank")

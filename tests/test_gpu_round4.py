@@ -50,7 +50,7 @@ def _bench(args, env_extra=None, timeout=900):
 def test_bench_two_ranks_real_kernels_corrupted_and_ragged():
     """Two ranks (gloo: the box has one GPU, both ranks run their kernels on it), 1 % corrupted shards, a config-4 leg
     whose total does not divide by two (rank 1 gets the short shard), MSM records of both shards combined."""
-    out = _bench(["--gpus", "2", "--batch", "65536", "--strong-total", "262145", "--corrupt", "0.01", "--steps", "2",
+    out = _bench(["--gpus", "2", "--full", "--batch", "65536", "--strong-total", "262145", "--corrupt", "0.01", "--steps", "2",
                   "--warmup", "1"], env_extra={"SSA_BENCH_BACKEND": "gloo"})
     assert out["n_gpus"] == 2 and out["config"]["backend"] == "gloo"
     assert len(out["ranks"]) == 2 and sorted(r[0] for r in out["ranks"]) == [0, 1]
@@ -77,7 +77,8 @@ def test_bench_two_ranks_real_kernels_corrupted_and_ragged():
 
 
 def test_bench_two_ranks_honest_msm_verdict_is_ok():
-    out = _bench(["--gpus", "2", "--batch", "16384", "--steps", "1", "--warmup", "1", "--no-strong-leg"],
+    out = _bench(["--gpus", "2", "--full", "--batch", "16384", "--forged", "0", "--steps", "1", "--warmup", "1",
+                  "--no-strong-leg"],
                  env_extra={"SSA_BENCH_BACKEND": "gloo"})
     assert out["n_gpus"] == 2 and out["rejected"] == 0 and out["all_verdicts_as_expected"] is True
     msm = out["verify_batch_msm_form"]
@@ -87,7 +88,8 @@ def test_bench_two_ranks_honest_msm_verdict_is_ok():
 
 def test_bench_strong_mode_two_ranks_ragged_total():
     """`--total` (config 4 as the main mode): rank 0 generates, both distributions run, rank 1's shard is one short"""
-    out = _bench(["--gpus", "2", "--total", "100001", "--steps", "1", "--warmup", "1", "--skip-torsion-leg"],
+    out = _bench(["--gpus", "2", "--full", "--total", "100001", "--forged", "0", "--steps", "1", "--warmup", "1",
+                  "--skip-torsion-leg"],
                  env_extra={"SSA_BENCH_BACKEND": "gloo"})
     assert out["scaling"] == "strong" and out["config"]["signatures_total"] == 100001
     assert out["config"]["signatures_per_gpu"] == 50001          # rank 0's shard (earlier ranks take the remainder)
@@ -96,7 +98,7 @@ def test_bench_strong_mode_two_ranks_ragged_total():
 
 
 def test_bench_line_names_its_flags_and_cpu_leg_runs_them():
-    out = _bench(["--gpus", "1", "--batch", "8192", "--steps", "1", "--warmup", "1", "--skip-torsion-leg",
+    out = _bench(["--gpus", "1", "--full", "--batch", "8192", "--steps", "1", "--warmup", "1", "--skip-torsion-leg",
                   "--cpu-sample", "512", "--corrupt", "0.01"])
     assert out["config"]["flags"] == {"word": 8, "names": ["SSA_FLAG_SIG_FLAG_BYTE"],
                                      "meaning": out["config"]["flags"]["meaning"]}
@@ -108,7 +110,8 @@ def test_bench_line_names_its_flags_and_cpu_leg_runs_them():
 def test_bench_pipelined_leg_verifies_what_the_metric_verifies():
     """`pipelined_two_contexts` (two contexts of the device over the halves of every batch: what a caller that pipelines batches
     gets) rejects exactly the corrupted signatures of the batch the timed steps ran on, and is reported beside the metric"""
-    out = _bench(["--gpus", "1", "--batch", "65536", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--corrupt", "0.01"])
+    out = _bench(["--gpus", "1", "--full", "--batch", "65536", "--steps", "1", "--warmup", "1", "--no-cpu-baseline",
+                  "--corrupt", "0.01"])
     leg = out["pipelined_two_contexts"]
     assert "error" not in leg, leg
     assert leg["rejected"] == out["rejected"] == 655

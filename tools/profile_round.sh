@@ -13,7 +13,7 @@ BENCH="python3 $REPO/bench.py --steps 5 --warmup 1 --no-cpu-baseline --skip-tors
 PMCB="python3 $REPO/bench.py --steps 2 --warmup 1 --no-cpu-baseline --skip-torsion-leg"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- $BENCH > $OUT/bench_stats_run.json 2> $OUT/stats.err
 echo "stats pass done"
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_full -- python3 $REPO/bench.py --steps 5 --warmup 1 --no-cpu-baseline > $OUT/bench_full_run.json 2> $OUT/stats_full.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_full -- python3 $REPO/bench.py --full --steps 5 --warmup 1 --no-cpu-baseline > $OUT/bench_full_run.json 2> $OUT/stats_full.err
 echo "full-bench stats pass done"
 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_INSTS_SALU SQ_BUSY_CYCLES --output-format csv -d $OUT/pmc_sq -- $PMCB > /dev/null 2> $OUT/pmc_sq.err
 echo "sq pass done"
