@@ -24,6 +24,10 @@
  *                              (sign_and_bind_pkey + KeyedSignature::to_bytes, src/signature.rs:132-156,237-245)
  *   ssa_pubkey_many         <- PublicKey::from(&PrivateKey) src/public.rs:26-32
  *   ssa_compress_many       <- PublicKey::to_bytes          src/public.rs:49-51
+ *   ssa_xprv_master_many    <- ExtendedPrivateKey::generate_master_key   src/derivation.rs:66-82
+ *   ssa_xprv_derive_many    <- ExtendedPrivateKey::derive_private / derive_public
+ *                                                           src/derivation.rs:88-174
+ *   ssa_xpub_derive_many    <- ExtendedPublicKey::derive_normal_public   src/derivation.rs:235-260
  *   status codes            <- SignatureError               src/error.rs:13-18
  *   record sizes            <- src/constants.rs:12-30
  *
@@ -238,6 +242,51 @@ int ssa_pubkey_many(ssa_ctx *ctx, const uint8_t *sks, size_t n, uint8_t *pks_out
 int ssa_compress_many(ssa_ctx *ctx, const uint8_t *pks, const uint8_t *pk_inf, size_t n, uint8_t *out,
                       uint8_t *status_out);
 
+/* ---- hierarchical deterministic key derivation (src/derivation.rs) ---------------------------------------------
+ * An extended private key is sk(32, little-endian, canonical, non-zero) || chain code(32); an extended public key is
+ * the compressed key(49) || chain code(32).  An index is a uint32_t whose little-endian bytes are the reference's
+ * &[u8; 4]; it is hardened when bit 31 is set.  Every child is one HMAC-SHA512 keyed by its parent's chain code (the
+ * key's ipad / opad states are computed once per parent: two SHA-512 compressions per child) and one base
+ * multiplication.  parse(I_L) = Scalar::from_bytes_non_canonical is read as the full reduction mod q of the 256-bit
+ * little-endian value.
+ * Parents: when parent_idx is NULL, m is 1 (every child of one parent) or n (child i of parent i); otherwise child i
+ * derives from parent parent_idx[i], and an index >= m gives SSA_MALFORMED on that lane.
+ * status_out[i]: 0 ok, 1 the reference's CtOption is none (child key 0, hardened index on an xpub, T = O),
+ * SSA_MALFORMED the parent does not decode (ExtendedPrivateKey::from_bytes / ExtendedPublicKey::from_bytes is none).
+ * Lanes whose status is not 0 get all-zero outputs.  n <= SSA_MAX_BATCH (n == 0 is a no-op). */
+#define SSA_CHAIN_CODE_LENGTH 32
+#define SSA_EXTENDED_PRIVATE_KEY_LENGTH 64
+#define SSA_EXTENDED_PUBLIC_KEY_LENGTH 81
+#define SSA_FLAG_DERIVE_PUBLIC 64u   /* xprv -> xpub children (derive_public) */
+
+/* ExtendedPrivateKey::generate_master_key (src/derivation.rs:66-82): HMAC-SHA512(b"Cheetah - Master extended key
+ * seed", seed) for n 32-byte seeds -> n x 64-byte xprvs; status 1 when the key reduces to 0.  Constant-time in the
+ * seeds; the host form wipes its device copies of seeds and keys before it returns. */
+int ssa_xprv_master_many(ssa_ctx *ctx, const uint8_t *seeds, size_t n, uint8_t *xprvs_out, uint8_t *status_out);
+
+/* ExtendedPrivateKey::derive_private (src/derivation.rs:88-154) and, with SSA_FLAG_DERIVE_PUBLIC, derive_public
+ * (:160-174): m parents (m x 64) -> n children, n x 64 bytes (sk || cc') or n x 81 (compress([sk]G) || cc').
+ * Constant-time in every secret (keys, chain codes, the hardened bit selects the message without a branch); the
+ * host form wipes its device copies of parents and children, and every call its per-parent records, before it
+ * returns. */
+int ssa_xprv_derive_many(ssa_ctx *ctx, const uint8_t *parents, size_t m, const uint32_t *parent_idx,
+                         const uint32_t *indices, size_t n, uint32_t flags, uint8_t *children_out,
+                         uint8_t *status_out);
+
+/* ExtendedPublicKey::derive_normal_public (src/derivation.rs:235-260): m parents (m x 81) -> n x 81 children and,
+ * optionally, the children's 96-byte affine keys (pks_out: what ssa_verify_many and key sets take; zero for the
+ * identity) and identity flags (pk_inf_out: a child equal to the identity is valid and encodes as [0; 48] || 0x80).
+ * Variable-time: everything here is public. */
+int ssa_xpub_derive_many(ssa_ctx *ctx, const uint8_t *parents, size_t m, const uint32_t *parent_idx,
+                         const uint32_t *indices, size_t n, uint8_t *children_out, uint8_t *pks_out,
+                         uint8_t *pk_inf_out, uint8_t *status_out);
+
+/* the SHA-512 / HMAC code of the derivation kernels on its own (not part of the reference API): n MACs
+ * HMAC-SHA512(key, msgs[i]) -> n x 64 bytes.  key_len <= 256 (keys longer than 128 bytes are hashed first, RFC 2104),
+ * msg_len <= 239 (messages of i * msg_len .. (i + 1) * msg_len). */
+int ssa_debug_hmac_sha512(ssa_ctx *ctx, const uint8_t *key, size_t key_len, const uint8_t *msgs, size_t msg_len,
+                          size_t n, uint8_t *out);
+
 #define SSA_KEYED_SIGNATURE_LENGTH 130  /* src/constants.rs:30 */
 /* n x KeyedSignature::verify on the 130-byte wire form pk(49, compressed) || sig(81)
  * (src/signature.rs:232-271): the key is decompressed on the GPU, then verified as ssa_verify_many.
@@ -280,6 +329,15 @@ int ssa_keygen_sign_many_ex_device(ssa_ctx *ctx, const uint8_t *d_sks, const uin
 int ssa_pubkey_many_device(ssa_ctx *ctx, const uint8_t *d_sks, size_t n, uint8_t *d_pks_out);
 int ssa_compress_many_device(ssa_ctx *ctx, const uint8_t *d_pks, const uint8_t *d_pk_inf, size_t n, uint8_t *d_out,
                              uint8_t *d_status_out);
+/* key derivation (src/derivation.rs): the device forms wipe the per-parent records, not the caller's buffers */
+int ssa_xprv_master_many_device(ssa_ctx *ctx, const uint8_t *d_seeds, size_t n, uint8_t *d_xprvs_out,
+                                uint8_t *d_status_out);
+int ssa_xprv_derive_many_device(ssa_ctx *ctx, const uint8_t *d_parents, size_t m, const uint32_t *d_parent_idx,
+                                const uint32_t *d_indices, size_t n, uint32_t flags, uint8_t *d_children_out,
+                                uint8_t *d_status_out);
+int ssa_xpub_derive_many_device(ssa_ctx *ctx, const uint8_t *d_parents, size_t m, const uint32_t *d_parent_idx,
+                                const uint32_t *d_indices, size_t n, uint8_t *d_children_out, uint8_t *d_pks_out,
+                                uint8_t *d_pk_inf_out, uint8_t *d_status_out);
 /* coeff_bytes in 1..32: little-endian coefficient width (d_coeffs == NULL: the library draws 128-bit
  * coefficients as above); *d_verdict_out receives the status.  A 32-byte coefficient is taken mod q (Scalar::random,
  * src/batch.rs:75-78).  A narrower one is recoded into signed digits over its own windows only, so a value that fills

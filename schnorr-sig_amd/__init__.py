@@ -13,6 +13,8 @@ Reference API mirrored (names and semantics, reference file:line):
   verify_batch(signatures, public_keys, messages, rng)    src/batch.rs:31-50
   SignatureError.{InvalidPublicKey, InvalidSignature}     src/error.rs:13-31
   *_LENGTH constants                         src/constants.rs:12-30
+  ChainCode / ExtendedPrivateKey / ExtendedPublicKey, PrivateKey.derive_private, PublicKey.derive_public
+                                             src/derivation.rs:30-317
 
 The directory is named `schnorr-sig_amd`; import it as `schnorr_sig_amd` (repo-root shim).
 """
@@ -42,6 +44,13 @@ FLAG_FORCE_COOP = 4   # low-latency kernel (one wave per signature) whatever the
 FLAG_SIG_FLAG_BYTE = 8  # verify_batch's semantics for byte 48 of the signature (src/batch.rs:104)
 FLAG_SIGN_CT = 16       # constant-time signing (the reference's `&BASEPOINT_TABLE * r`, src/signature.rs:67,116)
 FLAG_SIGN_KEYED = 32    # 130-byte KeyedSignature records out (src/signature.rs:237-245)
+FLAG_DERIVE_PUBLIC = 64  # xprv -> xpub children (ExtendedPrivateKey::derive_public, src/derivation.rs:160-174)
+# src/derivation.rs, src/constants.rs
+CHAIN_CODE_LENGTH = 32
+EXTENDED_PRIVATE_KEY_LENGTH = 64
+EXTENDED_PUBLIC_KEY_LENGTH = 81
+PRIVATE_KEY_SEED_LENGTH = 32
+DERIVE_NONE = 1          # status of a derivation lane whose CtOption is none
 KEYSET_KINDS = {"auto": 0, "comb": 1, "ladder": 2}
 _MODE_FLAGS = {None: 0, "auto": 0, "lane": FLAG_FORCE_LANE, "coop": FLAG_FORCE_COOP}
 
@@ -173,6 +182,13 @@ def _load():
         "ssa_ctx_stream_acquire": (i32, [vp, vp]),
         "ssa_debug_fault_after_chunk": (i32, [vp, i32]),
         "ssa_debug_tail_plan": (i32, [u32, u32, u32, i32, u32, sz, u32, vp]),
+        "ssa_xprv_master_many": (i32, [vp, vp, sz, vp, vp]),
+        "ssa_xprv_master_many_device": (i32, [vp, vp, sz, vp, vp]),
+        "ssa_xprv_derive_many": (i32, [vp, vp, sz, vp, vp, sz, u32, vp, vp]),
+        "ssa_xprv_derive_many_device": (i32, [vp, vp, sz, vp, vp, sz, u32, vp, vp]),
+        "ssa_xpub_derive_many": (i32, [vp, vp, sz, vp, vp, sz, vp, vp, vp, vp]),
+        "ssa_xpub_derive_many_device": (i32, [vp, vp, sz, vp, vp, sz, vp, vp, vp, vp]),
+        "ssa_debug_hmac_sha512": (i32, [vp, vp, sz, vp, sz, sz, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)      # AttributeError here == ABI symbol missing: fail loudly
@@ -444,6 +460,80 @@ class Engine:
         _check(_lib.ssa_decompress_many(self._ctx, _ptr(c), n, _ptr(pks), _ptr(inf), _ptr(st)),
                "ssa_decompress_many")
         return pks, inf, st
+
+    # ---- hierarchical key derivation (src/derivation.rs) ------------------------------------
+    @staticmethod
+    def _derive_idx(indices, parent_idx, m):
+        idx = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
+        pidx = None if parent_idx is None else np.ascontiguousarray(parent_idx, dtype=np.uint32).reshape(-1)
+        if pidx is not None and pidx.shape[0] != idx.shape[0]:
+            raise ValueError("parent_idx needs one entry per index")
+        return idx, pidx
+
+    def xprv_master_many(self, seeds):
+        """ExtendedPrivateKey::generate_master_key for n 32-byte seeds -> (xprvs uint8[n, 64], status uint8[n])"""
+        sd = _np_u8(seeds, 32)
+        n = sd.shape[0]
+        out = np.zeros((n, 64), dtype=np.uint8)
+        st = np.full(n, 255, dtype=np.uint8)
+        _check(_lib.ssa_xprv_master_many(self._ctx, _ptr(sd), n, _ptr(out), _ptr(st)), "ssa_xprv_master_many")
+        return out, st
+
+    def xprv_master_many_device(self, d_seeds, n, d_out, d_status):
+        _check(_lib.ssa_xprv_master_many_device(self._ctx, d_seeds, n, d_out, d_status), "ssa_xprv_master_many_device")
+
+    def xprv_derive_many(self, parents, indices, parent_idx=None, derive_public=False):
+        """derive_private (or derive_public) of m 64-byte xprvs -> (children uint8[n, 64] (or [n, 81]), status uint8[n]).
+        parent_idx None: one parent for every child (m == 1) or one per child (m == n)."""
+        par = _np_u8(parents, 64)
+        idx, pidx = self._derive_idx(indices, parent_idx, par.shape[0])
+        n = idx.shape[0]
+        out = np.zeros((n, 81 if derive_public else 64), dtype=np.uint8)
+        st = np.full(n, 255, dtype=np.uint8)
+        _check(_lib.ssa_xprv_derive_many(self._ctx, _ptr(par), par.shape[0], _ptr(pidx), _ptr(idx), n,
+                                         FLAG_DERIVE_PUBLIC if derive_public else 0, _ptr(out), _ptr(st)),
+               "ssa_xprv_derive_many")
+        return out, st
+
+    def xprv_derive_many_device(self, d_parents, m, d_indices, n, d_children, d_status, d_parent_idx=0,
+                                derive_public=False):
+        _check(_lib.ssa_xprv_derive_many_device(self._ctx, d_parents, m, d_parent_idx or None, d_indices, n,
+                                                FLAG_DERIVE_PUBLIC if derive_public else 0, d_children, d_status),
+               "ssa_xprv_derive_many_device")
+
+    def xpub_derive_many(self, parents, indices, parent_idx=None):
+        """derive_normal_public of m 81-byte xpubs -> (children uint8[n, 81], pks uint8[n, 96] (affine, zero for the
+        identity), is_identity uint8[n], status uint8[n])"""
+        par = _np_u8(parents, 81)
+        idx, pidx = self._derive_idx(indices, parent_idx, par.shape[0])
+        n = idx.shape[0]
+        out = np.zeros((n, 81), dtype=np.uint8)
+        pks = np.zeros((n, 96), dtype=np.uint8)
+        inf = np.zeros(n, dtype=np.uint8)
+        st = np.full(n, 255, dtype=np.uint8)
+        _check(_lib.ssa_xpub_derive_many(self._ctx, _ptr(par), par.shape[0], _ptr(pidx), _ptr(idx), n, _ptr(out),
+                                         _ptr(pks), _ptr(inf), _ptr(st)), "ssa_xpub_derive_many")
+        return out, pks, inf, st
+
+    def xpub_derive_many_device(self, d_parents, m, d_indices, n, d_children, d_status, d_parent_idx=0, d_pks=0,
+                                d_pk_inf=0):
+        _check(_lib.ssa_xpub_derive_many_device(self._ctx, d_parents, m, d_parent_idx or None, d_indices, n, d_children,
+                                                d_pks or None, d_pk_inf or None, d_status),
+               "ssa_xpub_derive_many_device")
+
+    def debug_hmac_sha512(self, key, msgs):
+        """HMAC-SHA512(key, msgs[i]) on the GPU for n messages of one length (<= 239 bytes; key <= 256 bytes)
+        -> uint8[n, 64]"""
+        k = np.frombuffer(bytes(key) + b"\0", np.uint8).copy()
+        m = np.ascontiguousarray(msgs, dtype=np.uint8)
+        if m.ndim == 1:
+            m = m.reshape(1, -1)
+        n, ml = m.shape
+        flat = np.concatenate([m.reshape(-1), np.zeros(1, np.uint8)])
+        out = np.zeros((n, 64), dtype=np.uint8)
+        _check(_lib.ssa_debug_hmac_sha512(self._ctx, _ptr(k), len(bytes(key)), _ptr(flat), ml, n, _ptr(out)),
+               "ssa_debug_hmac_sha512")
+        return out
 
     # ---- keyed context (many signatures by few signers) ---------------------------------
     def keyset_create(self, pks, pk_inf=None, kind="auto"):
@@ -729,6 +819,14 @@ class PublicKey:
     def __eq__(self, o):
         return isinstance(o, PublicKey) and o.affine == self.affine and o.is_identity == self.is_identity
 
+    def derive_public(self, chaincode, i, engine=None):
+        """PublicKey::derive_public (src/derivation.rs:305-316) -> (PublicKey, ChainCode); a hardened index (the
+        reference unwraps a none CtOption and panics) raises MalformedInput"""
+        child = ExtendedPublicKey(self, chaincode).derive_normal_public(i, engine)
+        if child is None:
+            raise MalformedInput("derive_normal_public is none (hardened index or T = O): the reference panics here")
+        return child.key, child.chaincode
+
 
 class PrivateKey:
     """PrivateKey(Scalar) (src/private.rs:25): 32 bytes LE, canonical, non-zero."""
@@ -773,6 +871,14 @@ class PrivateKey:
 
     def sign_and_bind_pkey(self, message, rng, engine=None):
         return KeyPair.from_private(self, engine).sign_and_bind_pkey(message, rng, engine)
+
+    def derive_private(self, chaincode, i, engine=None):
+        """PrivateKey::derive_private (src/derivation.rs:291-302) -> (PrivateKey, ChainCode); raises MalformedInput
+        where the reference's unwrap would panic (a child key of 0)"""
+        child = ExtendedPrivateKey(self, chaincode).derive_private(i, engine)
+        if child is None:
+            raise MalformedInput("derive_private is none (child key 0): the reference panics here")
+        return child.key, child.chaincode
 
     def __eq__(self, o):
         return isinstance(o, PrivateKey) and o.bytes == self.bytes
@@ -902,6 +1008,120 @@ class KeyPair:
                                        np.frombuffer(self._nonce(rng), np.uint8), msg, offsets=off, constant_time=True,
                                        keyed=True)
         return KeyedSignature(self.public_key, Signature(recs[0, 49:].tobytes()))
+
+
+def _index_bytes(i):
+    """an index as the reference's &[u8; 4] (little-endian) from an int or 4 bytes -> uint32"""
+    if isinstance(i, (bytes, bytearray, memoryview)):
+        b = bytes(i)
+        if len(b) != 4:
+            raise ValueError("an index is 4 bytes")
+        return int.from_bytes(b, "little")
+    v = int(i)
+    if not 0 <= v < 1 << 32:
+        raise ValueError("an index is a 32-bit unsigned value")
+    return v
+
+
+class ChainCode:
+    """ChainCode([u8; 32]) (src/derivation.rs:30-31)"""
+
+    def __init__(self, b32):
+        b = bytes(b32)
+        if len(b) != CHAIN_CODE_LENGTH:
+            raise ValueError("ChainCode needs 32 bytes")
+        self.bytes = b
+
+    def __eq__(self, o):
+        return isinstance(o, ChainCode) and o.bytes == self.bytes
+
+    def __hash__(self):
+        return hash(self.bytes)
+
+    def __repr__(self):
+        return "ChainCode(%s)" % self.bytes.hex()
+
+
+class ExtendedPrivateKey:
+    """ExtendedPrivateKey{key, chaincode} (src/derivation.rs:46-52); wire form sk(32) || cc(32).  Derivation runs on the
+    GPU (ssa_xprv_master_many / ssa_xprv_derive_many); the codecs stay on the host."""
+
+    def __init__(self, key, chaincode):
+        self.key = key
+        self.chaincode = chaincode if isinstance(chaincode, ChainCode) else ChainCode(chaincode)
+
+    @classmethod
+    def generate_master_key(cls, seed, engine=None):  # src/derivation.rs:66-82: None when the key is 0
+        b = bytes(seed)
+        if len(b) != PRIVATE_KEY_SEED_LENGTH:
+            raise ValueError("seed needs 32 bytes")
+        out, st = (engine or default_engine()).xprv_master_many(np.frombuffer(b, np.uint8))
+        return None if st[0] != OK else cls.from_bytes(out[0].tobytes())
+
+    def derive_private(self, i, engine=None):  # src/derivation.rs:88-92: None when the child key is 0
+        out, st = (engine or default_engine()).xprv_derive_many(np.frombuffer(self.to_bytes(), np.uint8),
+                                                                [_index_bytes(i)])
+        return None if st[0] != OK else ExtendedPrivateKey.from_bytes(out[0].tobytes())
+
+    def derive_public(self, i, engine=None):  # src/derivation.rs:160-174
+        out, st = (engine or default_engine()).xprv_derive_many(np.frombuffer(self.to_bytes(), np.uint8),
+                                                                [_index_bytes(i)], derive_public=True)
+        return None if st[0] != OK else ExtendedPublicKey.from_bytes(out[0].tobytes(), engine)
+
+    def to_bytes(self):  # src/derivation.rs:177-184
+        return self.key.to_bytes() + self.chaincode.bytes
+
+    @classmethod
+    def from_bytes(cls, b64):  # src/derivation.rs:187-203: None for a non-canonical or zero key
+        b = bytes(b64)
+        if len(b) != EXTENDED_PRIVATE_KEY_LENGTH:
+            raise ValueError("ExtendedPrivateKey needs 64 bytes")
+        sk = PrivateKey.from_bytes(b[:32])
+        return None if sk is None else cls(sk, ChainCode(b[32:]))
+
+    def __eq__(self, o):
+        return isinstance(o, ExtendedPrivateKey) and o.key == self.key and o.chaincode == self.chaincode
+
+    def __hash__(self):
+        return hash((self.key.bytes, self.chaincode.bytes))
+
+
+class ExtendedPublicKey:
+    """ExtendedPublicKey{key, chaincode} (src/derivation.rs:207-213); wire form compressed key(49) || cc(32)."""
+
+    def __init__(self, key, chaincode):
+        self.key = key
+        self.chaincode = chaincode if isinstance(chaincode, ChainCode) else ChainCode(chaincode)
+
+    @classmethod
+    def from_extended_private_key(cls, xprv, engine=None):  # src/derivation.rs:225-230
+        return cls(PublicKey.from_private(xprv.key, engine), xprv.chaincode)
+
+    def derive_normal_public(self, i, engine=None):
+        """src/derivation.rs:235-260: None for a hardened index or T = O; the child may be the identity"""
+        out, pks, inf, st = (engine or default_engine()).xpub_derive_many(
+            np.frombuffer(self.to_bytes(engine), np.uint8), [_index_bytes(i)])
+        if st[0] == MALFORMED:
+            raise MalformedInput("ExtendedPublicKey does not encode")
+        if st[0] != OK:
+            return None
+        return ExtendedPublicKey(PublicKey(pks[0].tobytes(), is_identity=bool(inf[0])), ChainCode(out[0, 49:].tobytes()))
+
+    def to_bytes(self, engine=None):  # src/derivation.rs:263-270
+        return self.key.to_bytes(engine) + self.chaincode.bytes
+
+    @classmethod
+    def from_bytes(cls, b81, engine=None):  # src/derivation.rs:273-290: None when decompression fails or for the identity
+        b = bytes(b81)
+        if len(b) != EXTENDED_PUBLIC_KEY_LENGTH:
+            raise ValueError("ExtendedPublicKey needs 81 bytes")
+        pk = PublicKey.from_bytes(b[:49], engine)
+        if pk is None or pk.is_identity:
+            return None
+        return cls(pk, ChainCode(b[49:]))
+
+    def __eq__(self, o):
+        return isinstance(o, ExtendedPublicKey) and o.key == self.key and o.chaincode == self.chaincode
 
 
 def verify_batch(signatures, public_keys, messages, rng=None, engine=None, msm=False):

@@ -131,6 +131,7 @@ struct ssa_ctx {
     // intermediates of the keyed (130-byte) output
     DevBuf ctab, sg_sigs, sg_pks;
     bool ctab_ready = false;
+    DevBuf dv_recs;               // key derivation (ssa_derive.hpp): one record per parent, wiped after each call
     unsigned verify_block = 256;  // threads per block of ssa_k_verify (SSA_VERIFY_BLOCK overrides: 64/128/256)
     // the end game of ssa_k_verify (ssa_kernels.hpp "The end game of a launch"): the last generation of lanes runs in
     // tail_pieces pieces per ladder pass, only the last of which stand at the end of the grid

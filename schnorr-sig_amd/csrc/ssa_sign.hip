@@ -533,3 +533,6 @@ extern "C" int ssa_keygen_sign_many_ex(ssa_ctx *ctx, const uint8_t *sks, const u
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return 0;
 }
+
+// hierarchical key derivation (reference src/derivation.rs): SHA-512 / HMAC and the derivation kernels and entry points
+#include "ssa_derive.hpp"

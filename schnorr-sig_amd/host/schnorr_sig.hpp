@@ -12,6 +12,8 @@
 //   schnorr_sig::PublicKey::verify_signature <- src/signature.rs:170-176
 //   schnorr_sig::verify_batch               <- src/batch.rs:31-50
 //   schnorr_sig::SignatureError             <- src/error.rs:13-31
+//   schnorr_sig::{ChainCode, ExtendedPrivateKey, ExtendedPublicKey}, PrivateKey / PublicKey derivation
+//                                           <- src/derivation.rs:30-317 (Context::xprv_derive_many & co. batched)
 //
 // All compute happens on the GPU behind ssa_*; nothing here does field or curve arithmetic.
 #pragma once
@@ -22,6 +24,7 @@
 #include <optional>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/schnorr_sig_amd.h"
@@ -389,6 +392,133 @@ inline Result verify_batch(Context &cx, const std::vector<Signature> &signatures
     }
     return status_to_result(
         ssa_verify_batch(cx.get(), sigs.data(), pks.data(), inf.data(), flat.data(), off.data(), 0, 0, n, 0));
+}
+
+// ---- hierarchical deterministic key derivation (src/derivation.rs) ---------------------------------------------------
+constexpr size_t CHAIN_CODE_LENGTH = SSA_CHAIN_CODE_LENGTH, EXTENDED_PRIVATE_KEY_LENGTH = SSA_EXTENDED_PRIVATE_KEY_LENGTH,
+                 EXTENDED_PUBLIC_KEY_LENGTH = SSA_EXTENDED_PUBLIC_KEY_LENGTH;
+using Index = std::array<uint8_t, 4>;   // the reference's &[u8; 4], little-endian; hardened when bit 7 of i[3] is set
+inline uint32_t index_value(const Index &i) {
+    return (uint32_t)i[0] | (uint32_t)i[1] << 8 | (uint32_t)i[2] << 16 | (uint32_t)i[3] << 24;
+}
+inline void derive_check(int rc, const char *what) {
+    if (rc != 0) throw std::runtime_error(std::string(what) + ": " + ssa_strerror(rc));
+}
+
+struct ChainCode {  // src/derivation.rs:30-31
+    std::array<uint8_t, CHAIN_CODE_LENGTH> bytes{};
+    bool operator==(const ChainCode &o) const { return bytes == o.bytes; }
+};
+
+struct ExtendedPublicKey;
+
+struct ExtendedPrivateKey {  // src/derivation.rs:46-52; wire form sk(32) || cc(32)
+    PrivateKey key;
+    ChainCode chaincode;
+    bool operator==(const ExtendedPrivateKey &o) const { return key == o.key && chaincode == o.chaincode; }
+    std::array<uint8_t, EXTENDED_PRIVATE_KEY_LENGTH> to_bytes() const {  // :177-184
+        std::array<uint8_t, EXTENDED_PRIVATE_KEY_LENGTH> b{};
+        std::memcpy(b.data(), key.bytes.data(), 32);
+        std::memcpy(b.data() + 32, chaincode.bytes.data(), 32);
+        return b;
+    }
+    // :187-203: nullopt for a non-canonical or zero key
+    static std::optional<ExtendedPrivateKey> from_bytes(const std::array<uint8_t, EXTENDED_PRIVATE_KEY_LENGTH> &b) {
+        std::array<uint8_t, PRIVATE_KEY_LENGTH> k{};
+        std::memcpy(k.data(), b.data(), 32);
+        auto sk = PrivateKey::from_bytes(k);
+        if (!sk) return std::nullopt;
+        ExtendedPrivateKey x{*sk, {}};
+        std::memcpy(x.chaincode.bytes.data(), b.data() + 32, 32);
+        return x;
+    }
+    // :66-82 (ssa_xprv_master_many)
+    static std::optional<ExtendedPrivateKey> generate_master_key(Context &cx, const std::array<uint8_t, 32> &seed) {
+        std::array<uint8_t, EXTENDED_PRIVATE_KEY_LENGTH> out{};
+        uint8_t st = 0xff;
+        derive_check(ssa_xprv_master_many(cx.get(), seed.data(), 1, out.data(), &st), "ssa_xprv_master_many");
+        if (st != SSA_OK) return std::nullopt;
+        return from_bytes(out);
+    }
+    // :88-154 (ssa_xprv_derive_many): nullopt when the child key is 0
+    std::optional<ExtendedPrivateKey> derive_private(Context &cx, const Index &i) const {
+        const auto par = to_bytes();
+        const uint32_t idx = index_value(i);
+        std::array<uint8_t, EXTENDED_PRIVATE_KEY_LENGTH> out{};
+        uint8_t st = 0xff;
+        derive_check(ssa_xprv_derive_many(cx.get(), par.data(), 1, nullptr, &idx, 1, 0, out.data(), &st),
+                     "ssa_xprv_derive_many");
+        if (st != SSA_OK) return std::nullopt;
+        return from_bytes(out);
+    }
+    // :160-174 (SSA_FLAG_DERIVE_PUBLIC)
+    std::optional<ExtendedPublicKey> derive_public(Context &cx, const Index &i) const;
+};
+
+struct ExtendedPublicKey {  // src/derivation.rs:207-213; wire form compressed key(49) || cc(32)
+    PublicKey key;
+    ChainCode chaincode;
+    bool operator==(const ExtendedPublicKey &o) const { return key == o.key && chaincode == o.chaincode; }
+    static ExtendedPublicKey from_extended_private_key(Context &cx, const ExtendedPrivateKey &x) {  // :225-230
+        return ExtendedPublicKey{PublicKey::from_private(cx, x.key), x.chaincode};
+    }
+    std::array<uint8_t, EXTENDED_PUBLIC_KEY_LENGTH> to_bytes(Context &cx) const {  // :263-270
+        std::array<uint8_t, EXTENDED_PUBLIC_KEY_LENGTH> b{};
+        const auto k = key.to_bytes(cx);
+        std::memcpy(b.data(), k.data(), PUBLIC_KEY_LENGTH);
+        std::memcpy(b.data() + PUBLIC_KEY_LENGTH, chaincode.bytes.data(), 32);
+        return b;
+    }
+    // :273-290: nullopt when decompression fails or for the identity
+    static std::optional<ExtendedPublicKey> from_bytes(Context &cx, const std::array<uint8_t, EXTENDED_PUBLIC_KEY_LENGTH> &b) {
+        std::array<uint8_t, PUBLIC_KEY_LENGTH> k{};
+        std::memcpy(k.data(), b.data(), PUBLIC_KEY_LENGTH);
+        auto pk = PublicKey::from_bytes(cx, k);
+        if (!pk || pk->is_identity) return std::nullopt;
+        ExtendedPublicKey x{*pk, {}};
+        std::memcpy(x.chaincode.bytes.data(), b.data() + PUBLIC_KEY_LENGTH, 32);
+        return x;
+    }
+    // :235-260 (ssa_xpub_derive_many): nullopt for a hardened index or T = O; the child may be the identity
+    std::optional<ExtendedPublicKey> derive_normal_public(Context &cx, const Index &i) const {
+        const auto par = to_bytes(cx);
+        const uint32_t idx = index_value(i);
+        std::array<uint8_t, EXTENDED_PUBLIC_KEY_LENGTH> out{};
+        ExtendedPublicKey child;
+        uint8_t inf = 0, st = 0xff;
+        derive_check(ssa_xpub_derive_many(cx.get(), par.data(), 1, nullptr, &idx, 1, out.data(), child.key.affine.data(),
+                                          &inf, &st), "ssa_xpub_derive_many");
+        if (st == SSA_MALFORMED) throw Panic("ExtendedPublicKey does not encode");
+        if (st != SSA_OK) return std::nullopt;
+        child.key.is_identity = inf != 0;
+        std::memcpy(child.chaincode.bytes.data(), out.data() + PUBLIC_KEY_LENGTH, 32);
+        return child;
+    }
+};
+
+inline std::optional<ExtendedPublicKey> ExtendedPrivateKey::derive_public(Context &cx, const Index &i) const {
+    const auto par = to_bytes();
+    const uint32_t idx = index_value(i);
+    std::array<uint8_t, EXTENDED_PUBLIC_KEY_LENGTH> out{};
+    uint8_t st = 0xff;
+    derive_check(ssa_xprv_derive_many(cx.get(), par.data(), 1, nullptr, &idx, 1, SSA_FLAG_DERIVE_PUBLIC, out.data(), &st),
+                 "ssa_xprv_derive_many");
+    if (st != SSA_OK) return std::nullopt;
+    return ExtendedPublicKey::from_bytes(cx, out);
+}
+
+// PrivateKey::derive_private (src/derivation.rs:291-302): the reference unwraps -- Panic on a none child
+inline std::pair<PrivateKey, ChainCode> derive_private(Context &cx, const PrivateKey &sk, const ChainCode &cc,
+                                                       const Index &i) {
+    auto c = ExtendedPrivateKey{sk, cc}.derive_private(cx, i);
+    if (!c) throw Panic("derive_private is none (child key 0)");
+    return {c->key, c->chaincode};
+}
+// PublicKey::derive_public (src/derivation.rs:305-316): Panic on a hardened index (the reference's unwrap)
+inline std::pair<PublicKey, ChainCode> derive_public(Context &cx, const PublicKey &pk, const ChainCode &cc, const Index &i) {
+    auto c = ExtendedPublicKey{pk, cc}.derive_normal_public(cx, i);
+    if (!c) throw Panic("derive_normal_public is none (hardened index or T = O)");
+    return {c->key, c->chaincode};
 }
 
 }  // namespace schnorr_sig
