@@ -28,6 +28,8 @@
  *   ssa_xprv_derive_many    <- ExtendedPrivateKey::derive_private / derive_public
  *                                                           src/derivation.rs:88-174
  *   ssa_xpub_derive_many    <- ExtendedPublicKey::derive_normal_public   src/derivation.rs:235-260
+ *   ssa_sign_many_indexed   <- KeyPair::sign / sign_and_bind_pkey over a signer set (key pairs held on the device)
+ *                                                           src/signature.rs:114-156
  *   status codes            <- SignatureError               src/error.rs:13-18
  *   record sizes            <- src/constants.rs:12-30
  *
@@ -379,6 +381,47 @@ int ssa_verify_many_indexed_device(ssa_ctx *ctx, ssa_keyset *ks, const uint32_t 
                                    const uint8_t *d_msgs, const uint64_t *d_msg_off, size_t msg_stride,
                                    size_t msg_len, size_t n, uint32_t flags, uint8_t *d_status_out,
                                    uint64_t *d_n_fail_out);
+
+/* ---- signer sets: many signatures by few signers (the signing twin of the key set) ---------------------------
+ * A signer set holds m key pairs on the device: the secret key, the 96-byte affine public key, the 49-byte compressed
+ * key and a per-key status.  Signature i is then KeyPair::sign (src/signature.rs:114-129) -- or, with
+ * SSA_FLAG_SIGN_KEYED, KeyPair::sign_and_bind_pkey (:132-156) -- by key pair key_idx[i]: the public key the key pair
+ * holds is hashed, so each signature costs ONE base multiplication, [r]G, where ssa_keygen_sign_many_ex (which is
+ * PrivateKey::sign) computes [sk]G as well.  For every valid lane the output is byte-identical to
+ * ssa_keygen_sign_many_ex with the same flags on the gathered rows sks[key_idx[i]].  Lifetime as for key sets: a set
+ * belongs to its context; one that outlives it is orphaned by ssa_ctx_destroy (its secret keys are zeroed and its
+ * memory freed there, every call on it but ssa_signer_set_destroy returns SSA_ERR_ARG).  ssa_signer_set_destroy zeroes
+ * the secret keys on the device before it frees them. */
+typedef struct ssa_signer_set ssa_signer_set;
+/* KeyPair::from_bytes (src/keypair.rs:78-89) for m keys (m x 32): a zero or non-canonical key gives SSA_ERR_ARG (the
+ * check takes the same time whatever the keys are); the staged copy of the keys is wiped before the call returns. */
+int ssa_signer_set_create(ssa_ctx *ctx, const uint8_t *sks, size_t m, ssa_signer_set **out);
+/* the same from device memory: key k is the first 32 bytes of d_sks + k * sk_stride (sk_stride >= 32; 64 takes the
+ * key half of the ExtendedPrivateKey records key || chaincode, src/derivation.rs:177-184, that
+ * ssa_xprv_derive_many_device writes).  Each key is checked on the device without a branch on its value: a zero or
+ * non-canonical key gets status SSA_MALFORMED and signs nothing. */
+int ssa_signer_set_create_device(ssa_ctx *ctx, const uint8_t *d_sks, size_t sk_stride, size_t m,
+                                 ssa_signer_set **out);
+void ssa_signer_set_destroy(ssa_signer_set *ss);
+/* per-key status (m bytes): 0 usable, 3 malformed */
+int ssa_signer_set_status(ssa_signer_set *ss, uint8_t *status_out);
+/* PublicKey::from(&PrivateKey) (src/public.rs:26-32) as m x 96 affine bytes and PublicKey::to_bytes (:49-51) as m x 49,
+ * byte for byte what ssa_pubkey_many and ssa_compress_many give (zero for a malformed key); either may be NULL */
+int ssa_signer_set_public_keys(ssa_signer_set *ss, uint8_t *pks96_out, uint8_t *pks49_out);
+/* KeyPair::sign / sign_and_bind_pkey for n messages: signature i by key pair key_idx[i] with nonce i.  flags:
+ * SSA_FLAG_SIGN_CT and SSA_FLAG_SIGN_KEYED as for ssa_keygen_sign_many_ex, any other bit is SSA_ERR_ARG.  Messages,
+ * limits and output layout (n x 81, or n x 130 keyed) are those of ssa_keygen_sign_many_ex.  SSA_ERR_ARG for an index
+ * >= m, a key whose status is not 0, or a zero or non-canonical nonce; the device copy of the nonces is wiped. */
+int ssa_sign_many_indexed(ssa_ctx *ctx, ssa_signer_set *ss, const uint32_t *key_idx, const uint8_t *nonces,
+                          const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len,
+                          size_t n, uint32_t flags, uint8_t *sigs_out);
+/* the same on device buffers, on the context's stream: nonces are reduced mod q; a lane whose index is >= m or whose
+ * key is unusable gets an all-zero record and, when d_status_out is given, SSA_MALFORMED there (0 for the others).
+ * PRECONDITION of SSA_FLAG_SIGN_CT: every nonce is canonical and non-zero, as for ssa_keygen_sign_many_ex_device. */
+int ssa_sign_many_indexed_device(ssa_ctx *ctx, ssa_signer_set *ss, const uint32_t *d_key_idx,
+                                 const uint8_t *d_nonces, const uint8_t *d_msgs, const uint64_t *d_msg_off,
+                                 size_t msg_stride, size_t msg_len, size_t n, uint32_t flags,
+                                 uint8_t *d_sigs_out, uint8_t *d_status_out);
 
 /* ---- several GPUs of one node from a single process --------------------------------------------
  * The batch shards by signature (contiguous ranges, sizes differ by at most one) over the listed

@@ -189,6 +189,13 @@ def _load():
         "ssa_xpub_derive_many": (i32, [vp, vp, sz, vp, vp, sz, vp, vp, vp, vp]),
         "ssa_xpub_derive_many_device": (i32, [vp, vp, sz, vp, vp, sz, vp, vp, vp, vp]),
         "ssa_debug_hmac_sha512": (i32, [vp, vp, sz, vp, sz, sz, vp]),
+        "ssa_signer_set_create": (i32, [vp, vp, sz, C.POINTER(vp)]),
+        "ssa_signer_set_create_device": (i32, [vp, vp, sz, sz, C.POINTER(vp)]),
+        "ssa_signer_set_destroy": (None, [vp]),
+        "ssa_signer_set_status": (i32, [vp, vp]),
+        "ssa_signer_set_public_keys": (i32, [vp, vp, vp]),
+        "ssa_sign_many_indexed": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz, u32, vp]),
+        "ssa_sign_many_indexed_device": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz, u32, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)      # AttributeError here == ABI symbol missing: fail loudly
@@ -582,6 +589,55 @@ class Engine:
                                                    FLAG_CHECK_TORSION if check_torsion else 0, d_status, d_nfail),
                "ssa_verify_many_indexed_device")
 
+    # ---- signer sets (KeyPair::sign for many messages by few key pairs) ---------------------
+    def signer_set_create(self, sks):
+        """-> SignerSet holding the key pairs of m canonical non-zero secret keys (uint8[m, 32]) on the device"""
+        sks = _np_u8(sks, 32)
+        ss = C.c_void_p()
+        _check(_lib.ssa_signer_set_create(self._ctx, _ptr(sks), sks.shape[0], C.byref(ss)), "ssa_signer_set_create")
+        return SignerSet(self, ss, sks.shape[0])
+
+    def signer_set_create_device(self, d_sks, m, sk_stride=32):
+        """key k at d_sks + k * sk_stride (64: the key half of ExtendedPrivateKey records); a zero or non-canonical
+        key gets status 3 (signer_set_status)"""
+        ss = C.c_void_p()
+        _check(_lib.ssa_signer_set_create_device(self._ctx, C.c_void_p(d_sks), sk_stride, m, C.byref(ss)),
+               "ssa_signer_set_create_device")
+        return SignerSet(self, ss, m)
+
+    def signer_set_status(self, ss):
+        st = np.full(ss.m, 255, dtype=np.uint8)
+        _check(_lib.ssa_signer_set_status(ss.handle, _ptr(st)), "ssa_signer_set_status")
+        return st
+
+    def signer_set_public_keys(self, ss):
+        """-> (uint8[m, 96] affine keys, uint8[m, 49] compressed keys)"""
+        pks = np.zeros((ss.m, 96), dtype=np.uint8)
+        cpks = np.zeros((ss.m, 49), dtype=np.uint8)
+        _check(_lib.ssa_signer_set_public_keys(ss.handle, _ptr(pks), _ptr(cpks)), "ssa_signer_set_public_keys")
+        return pks, cpks
+
+    def sign_many_indexed(self, ss, key_idx, nonces, msgs, offsets=None, constant_time=False, keyed=False):
+        """signature i by key pair key_idx[i] of the signer set with nonce i -> uint8[n, 81] (uint8[n, 130] keyed);
+        byte for byte keygen_sign_many(sks[key_idx], nonces, msgs, ...)[1]"""
+        idx = np.ascontiguousarray(key_idx, dtype=np.uint32).reshape(-1)
+        nonces = _np_u8(nonces, 32)
+        n = idx.shape[0]
+        assert nonces.shape[0] == n
+        m, off, stride, mlen = self._msg_args(msgs, offsets, n)
+        sigs = np.zeros((n, 130 if keyed else 81), dtype=np.uint8)
+        flags = (FLAG_SIGN_CT if constant_time else 0) | (FLAG_SIGN_KEYED if keyed else 0)
+        _check(_lib.ssa_sign_many_indexed(self._ctx, ss.handle, _ptr(idx), _ptr(nonces), _ptr(m), _ptr(off), stride,
+                                          mlen, n, flags, _ptr(sigs)), "ssa_sign_many_indexed")
+        return sigs
+
+    def sign_many_indexed_device(self, ss, d_key_idx, d_nonces, d_msgs, n, msg_len, d_sigs, d_status=0,
+                                 msg_stride=None, d_offsets=0, constant_time=False, keyed=False):
+        flags = (FLAG_SIGN_CT if constant_time else 0) | (FLAG_SIGN_KEYED if keyed else 0)
+        _check(_lib.ssa_sign_many_indexed_device(self._ctx, ss.handle, d_key_idx, d_nonces, d_msgs, d_offsets or None,
+                                                 msg_stride if msg_stride is not None else msg_len, msg_len, n, flags,
+                                                 d_sigs, d_status or None), "ssa_sign_many_indexed_device")
+
     # ---- device-buffer entry points (raw device addresses, e.g. torch.Tensor.data_ptr()) ----
     def set_stream(self, hip_stream):
         _check(_lib.ssa_ctx_set_stream(self._ctx, C.c_void_p(hip_stream or 0)), "ssa_ctx_set_stream")
@@ -692,6 +748,55 @@ class KeySet:
     def close(self):
         if self.handle:
             _lib.ssa_keyset_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SignerSet:
+    """ssa_signer_set handle: m key pairs held on the device, signing by index (KeyPair::sign for many messages).  Tied
+    to its Engine like KeySet; destroyed exactly once (close(), or when the object goes away), which zeroes the secret
+    keys on the device."""
+
+    def __init__(self, engine, handle, m, public_keys=None):
+        self.engine = engine      # keeps the context alive
+        self.handle = handle
+        self.m = int(m)
+        self.public_keys = public_keys
+
+    @classmethod
+    def from_key_pairs(cls, key_pairs, engine=None):
+        eng = engine or default_engine()
+        sks = np.frombuffer(b"".join(kp.private_key.bytes for kp in key_pairs), np.uint8).reshape(-1, 32)
+        ss = eng.signer_set_create(sks)
+        ss.public_keys = [kp.public_key for kp in key_pairs]
+        return ss
+
+    def sign(self, key_idx, messages, rng, constant_time=True, keyed=False):
+        """KeyPair::sign (src/signature.rs:114-129) of messages[i] by key pair key_idx[i], nonces drawn as KeyPair
+        draws them -> [Signature], or [KeyedSignature] (sign_and_bind_pkey, :132-156) with keyed=True"""
+        idx = [int(k) for k in key_idx]
+        if len(idx) != len(messages):
+            raise ValueError("one key index per message")
+        nonces = np.frombuffer(b"".join(KeyPair._nonce(None, rng) for _ in idx), np.uint8).reshape(-1, 32)
+        flat, off = pack_messages(messages)
+        out = self.engine.sign_many_indexed(self, np.array(idx, dtype=np.uint32), nonces, flat, offsets=off,
+                                            constant_time=constant_time, keyed=keyed)
+        if not keyed:
+            return [Signature(r.tobytes()) for r in out]
+        pub = self.public_keys
+        if pub is None:
+            pks, _ = self.engine.signer_set_public_keys(self)
+            pub = self.public_keys = [PublicKey(p.tobytes()) for p in pks]
+        return [KeyedSignature(pub[k], Signature(r[49:].tobytes())) for k, r in zip(idx, out)]
+
+    def close(self):
+        if self.handle:
+            _lib.ssa_signer_set_destroy(self.handle)
             self.handle = C.c_void_p()
 
     def __del__(self):

@@ -345,6 +345,11 @@ extern "C" void ssa_ctx_destroy(ssa_ctx *ctx) {
         ks->ctx = nullptr;
     }
     ctx->keysets.clear();
+    for (ssa_signer_set *ss : ctx->signer_sets) {
+        ss->wipe_release();
+        ss->ctx = nullptr;
+    }
+    ctx->signer_sets.clear();
     for (auto &kv : ctx->timed)
         for (auto &t : kv.second) {
             (void)hipEventDestroy(t.start);
@@ -730,6 +735,19 @@ int ssa_internal_sign_vartime(ssa_ctx *ctx, const uint8_t *d_sks, const uint8_t 
     return timed_launch(ctx, "ssa_k_sign", [&] {
         hipLaunchKernelGGL(ssa_k_sign, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, ctx->d_params,
                            (const u64 *)ctx->d_gtab, d_sks, d_nonces, mv, n, d_pks_out, d_sigs_out);
+    });
+}
+
+// the throughput signer of a signer set (ssa_sign_many_indexed_device); arguments checked by the caller (ssa_sign.hip)
+int ssa_internal_sign_indexed_vartime(ssa_ctx *ctx, const ssa_signer_set *ss, const uint32_t *d_key_idx,
+                                      const uint8_t *d_nonces, const uint8_t *d_msgs, const uint64_t *d_msg_off,
+                                      size_t msg_stride, size_t msg_len, size_t n, bool keyed, uint8_t *d_out,
+                                      uint8_t *d_status_out) {
+    MsgView mv{d_msgs, d_msg_off, msg_stride, msg_len};
+    return timed_launch(ctx, "ssa_k_sign_indexed", [&] {
+        hipLaunchKernelGGL(ssa_k_sign_indexed, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, ctx->d_params,
+                           (const u64 *)ctx->d_gtab, ss->view(), d_key_idx, d_nonces, mv, n, keyed ? 1u : 0u, d_out,
+                           d_status_out);
     });
 }
 

@@ -148,6 +148,27 @@ struct ssa_ctx {
     HostBuf pin_in, pin_coeffs, pin_out;
     std::map<std::string, std::vector<TimedLaunch>> timed;
     std::vector<struct ssa_keyset *> keysets;   // live key sets of this context (orphaned, not leaked, by ssa_ctx_destroy)
+    std::vector<struct ssa_signer_set *> signer_sets;   // live signer sets (ssa_sign.hip), orphaned the same way
+};
+
+// signer set (the signing twin of ssa_keyset; entry points in ssa_sign.hip): m key pairs resident on the device
+struct ssa_signer_set {
+    ssa_ctx *ctx = nullptr;   // nullptr: the context is gone, the device memory went with it
+    size_t m = 0;
+    DevBuf sks, pks, cpks, status;        // m x 32 secret keys, m x 96 affine keys, m x 49 compressed keys, m statuses
+    std::vector<uint8_t> host_status;     // a copy of `status`: what the host form refuses without a device round trip
+    SignerView view() const { return {(const u8 *)sks.p, (const u8 *)pks.p, (const u8 *)cpks.p, (const u8 *)status.p, (u32)m}; }
+    // the secret keys are zeroed on the device before their memory goes back to the allocator
+    void wipe_release() {
+        if (sks.p) {
+            (void)hipMemsetAsync(sks.p, 0, sks.cap, ctx->stream);
+            (void)hipStreamSynchronize(ctx->stream);
+        }
+        sks.release();
+        pks.release();
+        cpks.release();
+        status.release();
+    }
 };
 
 static inline unsigned grid_for(size_t n, unsigned block) { return (unsigned)((n + block - 1) / block); }

@@ -145,6 +145,31 @@ SSA_DEV void hash_message_lane(u64 *A, u64 *B, const DevParams *__restrict__ prm
     sponge_hash(A, B, prm, n_felts, src, digest);
 }
 
+// signer sets (ssa_sign_many_indexed): the key pairs of a set, as the signing kernels read them
+struct SignerView {
+    const u8 *sks, *pks, *cpks, *status;   // m x 32 secret keys, m x 96 affine keys, m x 49 compressed keys, m statuses
+    u32 m;
+};
+// the key row of signing lane i, or -1 when key_idx[i] >= m or the key is unusable: the lane's record (81 bytes, 130
+// keyed) is zeroed and its status is SSA_MALFORMED.  (the index and the key's status are public: the status says both)
+SSA_DEV long signer_row(const SignerView &sv, const u32 *__restrict__ key_idx, size_t i, u32 keyed, u8 *__restrict__ rec,
+                        u8 *__restrict__ lane_status) {
+    const u32 k = key_idx[i];
+    const bool usable = k < sv.m && sv.status[k] == ST_OK;
+    if (lane_status) lane_status[i] = (u8)(usable ? ST_OK : ST_MALFORMED);
+    if (usable) return (long)k;
+    const int len = keyed ? 130 : 81;
+    for (int j = 0; j < len; j++) rec[j] = 0;
+    return -1;
+}
+// KeyedSignature::to_bytes: the stored compressed key in front of the signature
+SSA_DEV u8 *signer_record(const SignerView &sv, long k, u32 keyed, u8 *__restrict__ rec) {
+    if (!keyed) return rec;
+#pragma unroll
+    for (int j = 0; j < 49; j++) rec[j] = sv.cpks[49 * k + j];
+    return rec + 49;
+}
+
 // ------------------------------------------------------------------------------------------
 #ifndef SSA_NO_KERNELS
 __global__ void __launch_bounds__(256, 4)    // four waves per SIMD: 128 VGPRs (the S-box blocks own v72..v127)
@@ -1316,6 +1341,43 @@ ssa_k_sign(const DevParams *__restrict__ prm, const u64 *__restrict__ gtab,
     sig[48] = jac_is_identity(rj) ? 0x80 : (f6_lex_largest(rp.y) ? 0x40 : 0x00);
 #pragma unroll
     for (int k = 0; k < 4; k++) st_u64_le(sig + 49 + 8 * k, e.w[k]);
+}
+
+// KeyPair::sign / sign_and_bind_pkey (src/signature.rs:114-156) for a signer set: the key pair is row key_idx[i] of the
+// set, so its public key is read, not computed -- ONE comb walk per signature, [r]G.  Same bytes as ssa_k_sign on the
+// gathered rows (the set's keys are canonical and non-zero, sc_reduce256 leaves them as they are).
+__global__ void __launch_bounds__(256, 2)
+ssa_k_sign_indexed(const DevParams *__restrict__ prm, const u64 *__restrict__ gtab, SignerView sv,
+                   const u32 *__restrict__ key_idx, const u8 *__restrict__ nonces, MsgView mv, size_t n, u32 keyed,
+                   u8 *__restrict__ out, u8 *__restrict__ lane_status) {
+    __shared__ u64 lds[RS_LDS_U64];
+    u64 *A = lds + threadIdx.x, *B = A;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    u8 *rec = out + (size_t)(keyed ? 130 : 81) * i;
+    const long k = signer_row(sv, key_idx, i, keyed, rec, lane_status);
+    if (k < 0) return;
+    const sc256 r = sc_reduce256(ld_sc(nonces + 32 * i));
+    const jac rj = add_base_mul(jac_identity(), gtab, r);                // src/signature.rs:116
+    const aff rp = jac_to_aff(rj);
+    bool ok = true;
+    const fp6 px = ld_fp6(sv.pks + 96 * k, ok);
+    const u64 py0 = ld_u64_le(sv.pks + 96 * k + 48);
+    u32 len;
+    const u8 *m = msg_ptr(mv, i, len);
+    u64 d[4];
+    hash_message_lane(A, B, prm, rp.x, px, py0, m, len, d);              // :118
+    sc256 h;
+#pragma unroll
+    for (int j = 0; j < 4; j++) h.w[j] = d[j];
+    h = sc_reduce256(h);                                                 // :122
+    const sc256 sk = sc_reduce256(ld_sc(sv.sks + 32 * k));
+    const sc256 e = sc_add_mod(r, sc_neg_mod(sc_mul_mod(sk, h)));        // :124
+    u8 *sig = signer_record(sv, k, keyed, rec);
+    st_fp6(sig, rp.x);
+    sig[48] = jac_is_identity(rj) ? 0x80 : (f6_lex_largest(rp.y) ? 0x40 : 0x00);
+#pragma unroll
+    for (int j = 0; j < 4; j++) st_u64_le(sig + 49 + 8 * j, e.w[j]);
 }
 #endif  // SSA_NO_KERNELS
 

@@ -22,6 +22,8 @@
 //                       * scalar arithmetic mod q (e = r - sk h, src/signature.rs:124) by masked subtractions.
 //                     What is NOT secret and therefore not treated: the message, the public key, R and the challenge
 //                     hash (the S-box blocks keep their flagged-lane fallback: their inputs are public).
+//   ssa_k_sign_indexed_ct  the same signer for a signer set (KeyPair::sign): the key pair is read by index, one base
+//                     multiplication per signature
 //   ssa_k_ctab        the 4-bit comb table and +-B, built once per context from the 16-bit comb table
 //   ssa_k_compress    AffinePoint::to_compressed: 96-byte affine -> 49-byte wire form
 //   ssa_k_pack_keyed  (pk, sig) -> the 130-byte KeyedSignature record pk(49) || sig(81)
@@ -241,6 +243,22 @@ SSA_FN void ct_response(sc256 *__restrict__ e, const sc256 *__restrict__ r, cons
 // secret scalar bytes -> value mod q
 SSA_FN void ct_load_scalar(sc256 *__restrict__ out, const u8 *__restrict__ p) { *out = sc_reduce256_ct(ld_sc(p)); }
 
+// the flag byte of R (CompressedPoint: bit 7 infinity, bit 6 the sort flag of y; rp canonical, from ct_to_aff).
+// (R is public, but its flag is formed without branches as well: whether the 64 sort bits of a wave agree would
+//  otherwise show in the kernel's instruction counts and blur the PMC comparison of secret sets)
+SSA_DEV u8 ct_r_flag(const aff &rp, const jac &rj) {
+    u32 lex = 0u, decided = 0u;
+#pragma unroll
+    for (int k = 5; k >= 0; k--) {
+        const u64 c = rp.y.c[k];
+        const u32 nz = (u32)(c != 0ull), take = nz & ~decided & 1u;
+        lex = take ? (u32)(c > (FP_P - 1) / 2) : lex;
+        decided |= nz;
+    }
+    const u32 r_inf = (u32)f6_is_zero_ct(rj.Z);
+    return (u8)(r_inf ? 0x80u : (lex << 6));
+}
+
 __global__ void __launch_bounds__(256, 2)      // two waves per SIMD: 256 registers (the default allocation took 266 and ran one)
 ssa_k_sign_ct(const DevParams *__restrict__ prm, const u64 *__restrict__ ctab, const u64 *__restrict__ gtab,
               const u8 *__restrict__ sks, const u8 *__restrict__ nonces, MsgView mv, size_t n,
@@ -279,18 +297,7 @@ ssa_k_sign_ct(const DevParams *__restrict__ prm, const u64 *__restrict__ ctab, c
     ct_response(&e, &r, &sk, &h);                                          // :124
     u8 *sig = sigs_out + 81 * i;
     st_fp6(sig, rp.x);
-    // (R is public, but its flag is formed without branches as well: whether the 64 sort bits of a wave agree would
-    //  otherwise show in the kernel's instruction counts and blur the PMC comparison of secret sets)
-    u32 lex = 0u, decided = 0u;
-#pragma unroll
-    for (int k = 5; k >= 0; k--) {
-        const u64 c = rp.y.c[k];                       // canonical (ct_to_aff)
-        const u32 nz = (u32)(c != 0ull), take = nz & ~decided & 1u;
-        lex = take ? (u32)(c > (FP_P - 1) / 2) : lex;
-        decided |= nz;
-    }
-    const u32 r_inf = (u32)f6_is_zero_ct(rj.Z);
-    sig[48] = (u8)(r_inf ? 0x80u : (lex << 6));
+    sig[48] = ct_r_flag(rp, rj);
 #pragma unroll
     for (int k = 0; k < 4; k++) st_u64_le(sig + 49 + 8 * k, e.w[k]);
 }
@@ -357,12 +364,62 @@ ssa_k_pack_keyed(const u8 *__restrict__ pks, const u8 *__restrict__ sigs, size_t
     for (int k = 0; k < 81; k++) rec[49 + k] = sigs[81 * i + k];
 }
 
+// KeyPair::sign / sign_and_bind_pkey (src/signature.rs:114-156), constant-time, for a signer set: the key pair is row
+// key_idx[i] of the set and its public key is read, not computed -- ONE ct_base_mul per signature, [r]G, where
+// ssa_k_sign_ct runs two.  The index, the row address it forms and the key's status are public; sk, r and e are
+// touched by the same out-of-line functions as in ssa_k_sign_ct (tests/test_signer_set_ct_static.py).  sk is loaded
+// after the product, so it does not stay live across it.
+__global__ void __launch_bounds__(256, 2)
+ssa_k_sign_indexed_ct(const DevParams *__restrict__ prm, const u64 *__restrict__ ctab, const u64 *__restrict__ gtab,
+                      SignerView sv, const u32 *__restrict__ key_idx, const u8 *__restrict__ nonces, MsgView mv,
+                      size_t n, u32 keyed, u8 *__restrict__ out, u8 *__restrict__ lane_status) {
+    __shared__ u64 lds[RS_LDS_U64];
+    u64 *A = lds + threadIdx.x, *B = A;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    u8 *rec = out + (size_t)(keyed ? 130 : 81) * i;
+    const long k = signer_row(sv, key_idx, i, keyed, rec, lane_status);
+    if (k < 0) return;
+    sc256 r;
+    ct_load_scalar(&r, nonces + 32 * i);
+    jac rj;
+    bool bad_r;
+    ct_base_mul(&rj, &bad_r, ctab, &r);                                    // src/signature.rs:116
+    if (bad_r) rj = add_base_mul(jac_identity(), gtab, r);                 // as in ssa_k_sign_ct: r = 0 or a 2^-250 event
+    aff rp;
+    ct_to_aff(&rp, &rj);
+    // from here on everything but sk, r and e is public
+    bool ok = true;
+    const fp6 px = ld_fp6(sv.pks + 96 * k, ok);
+    const u64 py0 = ld_u64_le(sv.pks + 96 * k + 48);
+    u32 len;
+    const u8 *m = msg_ptr(mv, i, len);
+    u64 d[4];
+    hash_message_lane(A, B, prm, rp.x, px, py0, m, len, d);                // :118
+    sc256 h;
+#pragma unroll
+    for (int j = 0; j < 4; j++) h.w[j] = d[j];
+    h = sc_reduce256_ct(h);                                                // :122
+    sc256 sk, e;
+    ct_load_scalar(&sk, sv.sks + 32 * k);
+    ct_response(&e, &r, &sk, &h);                                          // :124
+    u8 *sig = signer_record(sv, k, keyed, rec);
+    st_fp6(sig, rp.x);
+    sig[48] = ct_r_flag(rp, rj);
+#pragma unroll
+    for (int j = 0; j < 4; j++) st_u64_le(sig + 49 + 8 * j, e.w[j]);
+}
+
 }  // namespace ssa
 
 // ------------------------------------------------------------------------------------------------------------------
 int ssa_internal_sign_vartime(ssa_ctx *ctx, const uint8_t *d_sks, const uint8_t *d_nonces, const uint8_t *d_msgs,
                               const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len, size_t n, uint8_t *d_pks_out,
                               uint8_t *d_sigs_out);     // ssa_api.hip: the throughput signer's launch
+int ssa_internal_sign_indexed_vartime(ssa_ctx *ctx, const ssa_signer_set *ss, const uint32_t *d_key_idx,
+                                      const uint8_t *d_nonces, const uint8_t *d_msgs, const uint64_t *d_msg_off,
+                                      size_t msg_stride, size_t msg_len, size_t n, bool keyed, uint8_t *d_out,
+                                      uint8_t *d_status_out);    // ssa_api.hip: the same for a signer set
 
 // the 98 KB table of the constant-time signer, built once per context -- and COMPLETE before the call returns: a later
 // call may run on another stream (ssa_ctx_set_stream), and a failed build must not leave a table marked ready
@@ -536,3 +593,165 @@ extern "C" int ssa_keygen_sign_many_ex(ssa_ctx *ctx, const uint8_t *sks, const u
 
 // hierarchical key derivation (reference src/derivation.rs): SHA-512 / HMAC and the derivation kernels and entry points
 #include "ssa_derive.hpp"
+
+// ------------------------------------------------------------------------------------------------------------------
+// signer sets: m key pairs resident on the device, signatures name their key by index (KeyPair::sign for many messages)
+namespace ssa {
+
+// a key of a signer set from its record: status SSA_MALFORMED for a key that is zero or >= q (PrivateKey::from_bytes is
+// none, src/private.rs:74-76), by a masked borrow as in ct_xprv_prep; the stored key is the key itself, or 0 for a
+// malformed one (its public key is then the identity, (0, 0), and no signature uses it)
+SSA_FN void ct_signer_key(u8 *__restrict__ dst, u32 *__restrict__ status, const u8 *__restrict__ src) {
+    const sc256 sk = ld_sc(src);
+    u64 bw = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {                  // sk - q: the final borrow says sk < q
+        const u64 t = sk.w[i] - SC_Q(i);
+        const u64 b1 = sk.w[i] < SC_Q(i);
+        const u64 b2 = t < bw;
+        bw = b1 | b2;
+    }
+    const u64 ok = (u64)0 - (bw & ~sc_is_zero_mask(sk) & 1ull);
+#pragma unroll
+    for (int i = 0; i < 4; i++) st_u64_le(dst + 8 * i, sk.w[i] & ok);
+    *status = ST_MALFORMED & ~(u32)ok;
+}
+
+__global__ void __launch_bounds__(256)
+ssa_k_signer_keys(const u8 *__restrict__ src, size_t stride, size_t m, u8 *__restrict__ sks, u8 *__restrict__ status) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    u32 st;
+    ct_signer_key(sks + 32 * i, &st, src + stride * i);
+    status[i] = (u8)st;
+}
+
+}  // namespace ssa
+
+extern "C" void ssa_signer_set_destroy(ssa_signer_set *ss) {
+    if (!ss) return;
+    if (ss->ctx) {
+        (void)hipSetDevice(ss->ctx->device);
+        (void)hipStreamSynchronize(ss->ctx->stream);
+        auto &v = ss->ctx->signer_sets;
+        for (size_t i = 0; i < v.size(); i++)
+            if (v[i] == ss) {
+                v.erase(v.begin() + (long)i);
+                break;
+            }
+        ss->wipe_release();
+    }
+    delete ss;
+}
+
+// the keys (checked and copied), then PublicKey::from(&PrivateKey) and PublicKey::to_bytes once per key -- the kernels
+// of ssa_pubkey_many and ssa_compress_many, so the set's keys are theirs byte for byte
+static int signer_set_fill(ssa_ctx *ctx, ssa_signer_set *ss, const uint8_t *d_sks, size_t stride) {
+    const size_t m = ss->m;
+    if (ss->sks.reserve(m * 32) || ss->pks.reserve(m * 96) || ss->cpks.reserve(m * 49) || ss->status.reserve(m + 16))
+        return SSA_ERR_HIP;
+    if (int rc = timed_launch(ctx, "ssa_k_signer_keys", [&] {
+            hipLaunchKernelGGL(ssa_k_signer_keys, dim3(grid_for(m, 256)), dim3(256), 0, ctx->stream, d_sks, stride, m,
+                               (u8 *)ss->sks.p, (u8 *)ss->status.p);
+        }))
+        return rc;
+    if (int rc = ssa_pubkey_many_device(ctx, (const u8 *)ss->sks.p, m, (u8 *)ss->pks.p)) return rc;
+    if (int rc = ssa_compress_many_device(ctx, (const u8 *)ss->pks.p, nullptr, m, (u8 *)ss->cpks.p, nullptr)) return rc;
+    ss->host_status.assign(m, 0xff);
+    HIP_TRY(hipMemcpyAsync(ss->host_status.data(), ss->status.p, m, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+extern "C" int ssa_signer_set_create_device(ssa_ctx *ctx, const uint8_t *d_sks, size_t sk_stride, size_t m,
+                                            ssa_signer_set **out) {
+    if (!ctx || !out || !d_sks || m == 0 || m > SSA_MAX_BATCH || sk_stride < 32) return SSA_ERR_ARG;
+    *out = nullptr;
+    HIP_TRY(hipSetDevice(ctx->device));
+    ssa_signer_set *ss = new ssa_signer_set();
+    ss->ctx = ctx;
+    ss->m = m;
+    if (int rc = signer_set_fill(ctx, ss, d_sks, sk_stride)) {
+        ssa_signer_set_destroy(ss);
+        return rc;
+    }
+    ctx->signer_sets.push_back(ss);
+    *out = ss;
+    return 0;
+}
+
+extern "C" int ssa_signer_set_create(ssa_ctx *ctx, const uint8_t *sks, size_t m, ssa_signer_set **out) {
+    if (!ctx || !out || !sks || m == 0 || m > SSA_MAX_BATCH) return SSA_ERR_ARG;
+    *out = nullptr;
+    if (!scalars_canonical_nonzero(sks, m)) return SSA_ERR_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    DeriveWipe wipe{ctx, {&ctx->st_sigs, nullptr, nullptr}, {m * 32, 0, 0}, true};   // the staged keys do not outlive the call
+    const void *p;
+    if (int rc = stage_up(ctx, ctx->st_sigs, sks, m * 32, &p)) return rc;
+    return ssa_signer_set_create_device(ctx, (const u8 *)p, 32, m, out);
+}
+
+extern "C" int ssa_signer_set_status(ssa_signer_set *ss, uint8_t *status_out) {
+    if (!ss || !ss->ctx || !status_out) return SSA_ERR_ARG;
+    std::memcpy(status_out, ss->host_status.data(), ss->m);
+    return 0;
+}
+
+extern "C" int ssa_signer_set_public_keys(ssa_signer_set *ss, uint8_t *pks96_out, uint8_t *pks49_out) {
+    if (!ss || !ss->ctx) return SSA_ERR_ARG;
+    ssa_ctx *ctx = ss->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (pks96_out) HIP_TRY(hipMemcpyAsync(pks96_out, ss->pks.p, ss->m * 96, hipMemcpyDeviceToHost, ctx->stream));
+    if (pks49_out) HIP_TRY(hipMemcpyAsync(pks49_out, ss->cpks.p, ss->m * 49, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+extern "C" int ssa_sign_many_indexed_device(ssa_ctx *ctx, ssa_signer_set *ss, const uint32_t *d_key_idx,
+                                            const uint8_t *d_nonces, const uint8_t *d_msgs, const uint64_t *d_msg_off,
+                                            size_t msg_stride, size_t msg_len, size_t n, uint32_t flags,
+                                            uint8_t *d_sigs_out, uint8_t *d_status_out) {
+    if (!ctx || !ss || ss->ctx != ctx || (flags & ~(SSA_FLAG_SIGN_CT | SSA_FLAG_SIGN_KEYED))) return SSA_ERR_ARG;
+    if (n && (!d_key_idx || !d_nonces || !d_sigs_out)) return SSA_ERR_ARG;
+    if (int rc = check_msgs(d_msgs, d_msg_off, msg_stride, msg_len, n)) return rc;
+    if (n == 0) return 0;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const bool keyed = (flags & SSA_FLAG_SIGN_KEYED) != 0;
+    if (!(flags & SSA_FLAG_SIGN_CT))
+        return ssa_internal_sign_indexed_vartime(ctx, ss, d_key_idx, d_nonces, d_msgs, d_msg_off, msg_stride, msg_len, n,
+                                                 keyed, d_sigs_out, d_status_out);
+    if (int rc = ensure_ctab(ctx)) return rc;
+    MsgView mv{d_msgs, d_msg_off, msg_stride, msg_len};
+    return timed_launch(ctx, "ssa_k_sign_indexed_ct", [&] {
+        hipLaunchKernelGGL(ssa_k_sign_indexed_ct, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, ctx->d_params,
+                           (const u64 *)ctx->ctab.p, (const u64 *)ctx->d_gtab, ss->view(), d_key_idx, d_nonces, mv, n,
+                           keyed ? 1u : 0u, d_sigs_out, d_status_out);
+    });
+}
+
+extern "C" int ssa_sign_many_indexed(ssa_ctx *ctx, ssa_signer_set *ss, const uint32_t *key_idx, const uint8_t *nonces,
+                                     const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len,
+                                     size_t n, uint32_t flags, uint8_t *sigs_out) {
+    if (!ctx || !ss || ss->ctx != ctx || (flags & ~(SSA_FLAG_SIGN_CT | SSA_FLAG_SIGN_KEYED))) return SSA_ERR_ARG;
+    if (n && (!key_idx || !nonces || !sigs_out)) return SSA_ERR_ARG;
+    if (int rc = check_msgs(msgs, msg_off, msg_stride, msg_len, n)) return rc;
+    if (n == 0) return 0;
+    for (size_t i = 0; i < n; i++)                 // (indices are public)
+        if (key_idx[i] >= ss->m || ss->host_status[key_idx[i]] != ST_OK) return SSA_ERR_ARG;
+    if (!scalars_canonical_nonzero(nonces, n)) return SSA_ERR_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    DeriveWipe wipe{ctx, {&ctx->st_pks, nullptr, nullptr}, {n * 32, 0, 0}, true};     // the staged nonces
+    StagedInputs s;
+    const void *p_nonce, *p_idx;
+    if (int rc = stage_up(ctx, ctx->st_pks, nonces, n * 32, &p_nonce)) return rc;
+    if (int rc = stage_up(ctx, ctx->st_inf, key_idx, n * sizeof(uint32_t), &p_idx)) return rc;
+    if (int rc = stage_msgs(ctx, msgs, msg_off, msg_stride, msg_len, n, s)) return rc;
+    const size_t sig_bytes = (flags & SSA_FLAG_SIGN_KEYED) ? 130 : 81;
+    if (ctx->st_aux2.reserve(n * sig_bytes)) return SSA_ERR_HIP;
+    if (int rc = ssa_sign_many_indexed_device(ctx, ss, (const uint32_t *)p_idx, (const u8 *)p_nonce, s.msgs, s.off,
+                                              msg_stride, msg_len, n, flags, (u8 *)ctx->st_aux2.p, nullptr))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(sigs_out, ctx->st_aux2.p, n * sig_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}

@@ -12,11 +12,14 @@
 //   schnorr_sig::PublicKey::verify_signature <- src/signature.rs:170-176
 //   schnorr_sig::verify_batch               <- src/batch.rs:31-50
 //   schnorr_sig::SignatureError             <- src/error.rs:13-31
+//   schnorr_sig::SignerSet::{sign, sign_and_bind_pkey}  <- KeyPair::sign / sign_and_bind_pkey over many messages by few
+//                                              key pairs held on the device, src/signature.rs:114-156
 //   schnorr_sig::{ChainCode, ExtendedPrivateKey, ExtendedPublicKey}, PrivateKey / PublicKey derivation
 //                                           <- src/derivation.rs:30-317 (Context::xprv_derive_many & co. batched)
 //
 // All compute happens on the GPU behind ssa_*; nothing here does field or curve arithmetic.
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <cstring>
@@ -354,6 +357,81 @@ class KeySet {
     Context &cx_;
     size_t m_;
     ssa_keyset *ks_ = nullptr;
+};
+
+// Many signatures by few key pairs (a service's keys, derived deposit addresses): the key pairs stay on the device
+// (ssa_signer_set_create) and sign() is KeyPair::sign (src/signature.rs:114-129) -- constant-time, one base
+// multiplication per signature -- of message i by key pair key_idx[i]; sign_and_bind_pkey() gives the KeyedSignature
+// records (:132-156).  The destructor zeroes the secret keys on the device.
+class SignerSet {
+  public:
+    SignerSet(Context &cx, const std::vector<KeyPair> &pairs) : cx_(cx), pairs_(pairs) {
+        std::vector<uint8_t> sks(pairs.size() * PRIVATE_KEY_LENGTH);
+        for (size_t i = 0; i < pairs.size(); i++)
+            std::memcpy(&sks[i * PRIVATE_KEY_LENGTH], pairs[i].private_key.bytes.data(), PRIVATE_KEY_LENGTH);
+        int rc = ssa_signer_set_create(cx.get(), sks.data(), pairs.size(), &ss_);
+        std::fill(sks.begin(), sks.end(), 0);
+        if (rc != 0) throw std::runtime_error(std::string("ssa_signer_set_create: ") + ssa_strerror(rc));
+    }
+    ~SignerSet() { ssa_signer_set_destroy(ss_); }
+    SignerSet(const SignerSet &) = delete;
+    SignerSet &operator=(const SignerSet &) = delete;
+    size_t size() const { return pairs_.size(); }
+    // the public keys as the set computed them: 96-byte affine and 49-byte compressed
+    std::vector<PublicKey> public_keys() const {
+        std::vector<uint8_t> pks(size() * AFFINE_PUBLIC_KEY_LENGTH);
+        int rc = ssa_signer_set_public_keys(ss_, pks.data(), nullptr);
+        if (rc != 0) throw std::runtime_error(std::string("ssa_signer_set_public_keys: ") + ssa_strerror(rc));
+        std::vector<PublicKey> out(size());
+        for (size_t i = 0; i < size(); i++) std::memcpy(out[i].affine.data(), &pks[i * AFFINE_PUBLIC_KEY_LENGTH], AFFINE_PUBLIC_KEY_LENGTH);
+        return out;
+    }
+    std::vector<Signature> sign(const std::vector<uint32_t> &key_idx,
+                                const std::vector<std::pair<const uint8_t *, size_t>> &messages, Rng rng) const {
+        std::vector<Signature> out(key_idx.size());
+        const auto recs = run(key_idx, messages, rng, SSA_FLAG_SIGN_CT, SIGNATURE_LENGTH);
+        for (size_t i = 0; i < out.size(); i++)
+            std::memcpy(out[i].bytes.data(), &recs[i * SIGNATURE_LENGTH], SIGNATURE_LENGTH);
+        return out;
+    }
+    std::vector<KeyedSignature> sign_and_bind_pkey(const std::vector<uint32_t> &key_idx,
+                                                   const std::vector<std::pair<const uint8_t *, size_t>> &messages,
+                                                   Rng rng) const {
+        std::vector<KeyedSignature> out(key_idx.size());
+        const auto recs = run(key_idx, messages, rng, SSA_FLAG_SIGN_CT | SSA_FLAG_SIGN_KEYED, KEYED_SIGNATURE_LENGTH);
+        for (size_t i = 0; i < out.size(); i++) {
+            out[i].public_key = pairs_[key_idx[i]].public_key;
+            std::memcpy(out[i].signature.bytes.data(), &recs[i * KEYED_SIGNATURE_LENGTH + PUBLIC_KEY_LENGTH],
+                        SIGNATURE_LENGTH);
+        }
+        return out;
+    }
+
+  private:
+    std::vector<uint8_t> run(const std::vector<uint32_t> &key_idx,
+                             const std::vector<std::pair<const uint8_t *, size_t>> &messages, Rng &rng, uint32_t flags,
+                             size_t rec_len) const {
+        const size_t n = key_idx.size();
+        if (messages.size() != n) throw Panic("one key index per message");
+        for (uint32_t k : key_idx)
+            if (k >= size()) throw Panic("key index out of range");
+        std::vector<uint8_t> nonces(n * SCALAR_LENGTH), flat, recs(n * rec_len);
+        std::vector<uint64_t> off(n + 1, 0);
+        for (size_t i = 0; i < n; i++) {
+            KeyPair::random_scalar(rng, &nonces[i * SCALAR_LENGTH]);
+            flat.insert(flat.end(), messages[i].first, messages[i].first + messages[i].second);
+            off[i + 1] = flat.size();
+        }
+        flat.push_back(0);
+        int rc = ssa_sign_many_indexed(cx_.get(), ss_, key_idx.data(), nonces.data(), flat.data(), off.data(), 0, 0, n,
+                                       flags, recs.data());
+        std::fill(nonces.begin(), nonces.end(), 0);
+        if (rc != 0) throw std::runtime_error(std::string("ssa_sign_many_indexed: ") + ssa_strerror(rc));
+        return recs;
+    }
+    Context &cx_;
+    std::vector<KeyPair> pairs_;
+    ssa_signer_set *ss_ = nullptr;
 };
 
 // verify_batch, src/batch.rs:31-50.
