@@ -76,6 +76,7 @@ extern "C" {
 #define SSA_ERR_HIP (-2)
 #define SSA_ERR_PARAMS (-3)
 #define SSA_ERR_NO_DEVICE (-4)
+#define SSA_ERR_TABLE (-5)        /* a precomputed table failed its self-check (ssa_ctx_selfcheck) */
 
 /* flags */
 #define SSA_MAX_BATCH ((size_t)1 << 30)   /* signatures per call; larger n returns SSA_ERR_ARG.  Device memory does not grow
@@ -128,6 +129,24 @@ int ssa_ctx_create_ex(ssa_ctx **out, int device, const void *params, size_t para
  * per-lane kernels, out[5] signatures per slice of the MSM form, out[6] the HBM budget, out[7] 1 when calls of more than
  * one slice alternate their slices between two internal streams (SSA_TWO_STREAMS=0 turns that off). */
 int ssa_ctx_info(const ssa_ctx *ctx, uint64_t out[8]);
+/* Exact self-check of the context's precomputed tables, on the context's stream; returns when it is done.  Every row of
+ * the comb for G (the table every verification, the throughput signer and xpub derivation walk) and, once the first
+ * constant-time signature has built it, every row of the constant-time signer's table is checked against the rows
+ * before it: a clean result proves each row equal to its multiple of G.  flags must be 0.
+ * Returns SSA_OK when both are clean, SSA_ERR_TABLE when a row is wrong, SSA_ERR_ARG / SSA_ERR_HIP as usual.
+ *   out[0] comb rows checked (windows x 2^bits)      out[4] constant-time rows that fail
+ *   out[1] comb rows that fail                       out[5] first failing constant-time row (UINT64_MAX: none)
+ *   out[2] first failing comb row (UINT64_MAX: none) out[6] builds the comb took (1; 2 after a rebuild at creation)
+ *   out[3] constant-time rows checked (0 before it is built, or while the comb fails; else 1026)
+ *                                                    out[7] window bits of the comb
+ * Tables are checked when they are built, too: ssa_ctx_create_ex rebuilds a comb that fails once, falls back to the
+ * next smaller width when it fails again and returns SSA_ERR_TABLE when no width gives a clean table; a constant-time
+ * table that fails twice makes the signing call return SSA_ERR_TABLE.  A comb that fails here is RETIRED: contexts
+ * created afterwards build and check a new one.  Contexts that hold the failed comb (this one and any other of the
+ * process on the same device and geometry) keep computing with it -- destroy them.  A constant-time table that fails
+ * here is rebuilt (and checked) by the next constant-time call.  Long-lived services should run this periodically
+ * (INTEGRATION.md gives its cost per width). */
+int ssa_ctx_selfcheck(ssa_ctx *ctx, uint32_t flags, uint64_t out[8]);
 /* 1 when the context was created from the built-in blob (parity with upstream unpinned), 0 for a caller-supplied one */
 int ssa_ctx_uses_default_params(const ssa_ctx *ctx);
 void ssa_ctx_destroy(ssa_ctx *ctx);
@@ -504,6 +523,18 @@ int ssa_debug_arith(ssa_ctx *ctx, int op, const uint64_t *a, const uint64_t *b, 
  * has been enqueued (one shot; chunk < 0 disarms).  Replaces round 3's SSA_FAULT_AFTER_CHUNK environment variable: the
  * production path reads no environment per call. */
 int ssa_debug_fault_after_chunk(ssa_ctx *ctx, int chunk);
+/* self-check tests.  which: 0 the comb for G, 1 the constant-time table (SSA_ERR_ARG before it is built).  Rows are 12
+ * words (x[6], y[6]); rows and words outside the table are SSA_ERR_ARG, nothing is read or written out of bounds.
+ *   ssa_debug_table_read  copies rows [first_row, first_row + n) to rows_out (n x 12 words)
+ *   ssa_debug_table_xor   XORs `mask` into word `word` of row `row` ON THE DEVICE.  The comb is shared by every context of
+ *                         the process on this device and geometry: this corrupts all of them.  Run no verification,
+ *                         signing or derivation on any of them afterwards -- a poked header word (row 0, word 0)
+ *                         misdirects the comb walk itself; ssa_ctx_selfcheck and ssa_ctx_destroy are what is left.
+ *   ssa_debug_corrupt_table_builds  the next n comb builds of this process (any context, any width) get one fixed word
+ *                         of a mid-table row flipped after the build and before its check (n = 0 disarms). */
+int ssa_debug_table_read(ssa_ctx *ctx, int which, uint64_t first_row, uint64_t n, uint64_t *rows_out);
+int ssa_debug_table_xor(ssa_ctx *ctx, int which, uint64_t row, uint32_t word, uint64_t mask);
+int ssa_debug_corrupt_table_builds(int n);
 /* host logic of ssa_k_verify's end game, no context and no device needed: the launch plan for n lanes when `waves`
  * waves are resident (pieces / gens / uniform / min_main: what SSA_TAIL_PIECES, _GENS, _UNIFORM, _MIN_MAIN set).
  * out: number of pieces (0: no end game), 64-lane tail groups, ordinary workgroups, workgroups of the grid, the eight

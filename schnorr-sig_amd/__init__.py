@@ -38,6 +38,9 @@ SIGNATURE_LENGTH = 81
 KEYED_SIGNATURE_LENGTH = 130
 
 OK, INVALID_PUBLIC_KEY, INVALID_SIGNATURE, MALFORMED = 0, 1, 2, 3
+ERR_ARG, ERR_HIP, ERR_PARAMS, ERR_NO_DEVICE, ERR_TABLE = -1, -2, -3, -4, -5
+TABLE_COMB, TABLE_CT = 0, 1        # ssa_debug_table_read / _xor: the comb for G, the constant-time signer's table
+SELFCHECK_FIELDS = ("rows", "bad", "first_bad", "ctab_rows", "ctab_bad", "ctab_first_bad", "builds", "bits")
 FLAG_CHECK_TORSION = 1
 FLAG_FORCE_LANE = 2   # throughput kernels (one signature per lane) whatever the batch size
 FLAG_FORCE_COOP = 4   # low-latency kernel (one wave per signature) whatever the batch size
@@ -196,6 +199,10 @@ def _load():
         "ssa_signer_set_public_keys": (i32, [vp, vp, vp]),
         "ssa_sign_many_indexed": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz, u32, vp]),
         "ssa_sign_many_indexed_device": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz, u32, vp, vp]),
+        "ssa_ctx_selfcheck": (i32, [vp, u32, u64p]),
+        "ssa_debug_table_read": (i32, [vp, i32, C.c_uint64, C.c_uint64, vp]),
+        "ssa_debug_table_xor": (i32, [vp, i32, C.c_uint64, u32, C.c_uint64]),
+        "ssa_debug_corrupt_table_builds": (i32, [i32]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)      # AttributeError here == ABI symbol missing: fail loudly
@@ -655,6 +662,30 @@ class Engine:
         by a collective, are visible to the next call on the engine)"""
         _check(_lib.ssa_ctx_stream_acquire(self._ctx, C.c_void_p(producer_stream or 0)), "ssa_ctx_stream_acquire")
 
+    def selfcheck(self):
+        """ssa_ctx_selfcheck: the exact check of the comb for G and (once built) the constant-time table.  Returns the
+        eight out[] fields by name (SELFCHECK_FIELDS) plus ok; a failing table is a result (ok False), not an exception.
+        A comb that fails is retired: engines created afterwards build a new one, this one should be closed."""
+        out = (C.c_uint64 * 8)()
+        rc = _lib.ssa_ctx_selfcheck(self._ctx, 0, out)
+        if rc != ERR_TABLE:
+            _check(rc, "ssa_ctx_selfcheck")
+        res = dict(zip(SELFCHECK_FIELDS, (int(v) for v in out)))
+        res["ok"] = rc == OK
+        return res
+
+    def debug_table_read(self, which, first_row, n):
+        """tests: rows [first_row, first_row + n) of a table (TABLE_COMB / TABLE_CT) as an (n, 12) uint64 array"""
+        out = np.zeros((n, 12), dtype=np.uint64)
+        _check(_lib.ssa_debug_table_read(self._ctx, int(which), int(first_row), int(n), _ptr(out)), "ssa_debug_table_read")
+        return out
+
+    def debug_table_xor(self, which, row, word, mask):
+        """tests: XOR `mask` into one word of a table ON THE DEVICE.  The comb is shared by every engine of the process on
+        this device and geometry; run no verification, signing or derivation on any of them afterwards."""
+        _check(_lib.ssa_debug_table_xor(self._ctx, int(which), int(row), int(word), C.c_uint64(int(mask))),
+               "ssa_debug_table_xor")
+
     def debug_fault_after_chunk(self, chunk):
         """tests: the NEXT pipelined host-buffer upload fails after chunk `chunk` (one shot; < 0 disarms)"""
         _check(_lib.ssa_debug_fault_after_chunk(self._ctx, int(chunk)), "ssa_debug_fault_after_chunk")
@@ -734,6 +765,11 @@ class Engine:
         v = C.c_double(0)
         _check(_lib.ssa_bench_fpmul(self._ctx, variant, C.byref(v)), "ssa_bench_fpmul")
         return v.value
+
+
+def debug_corrupt_table_builds(n):
+    """tests: the next n comb builds of this process get one word flipped before their check (0 disarms)"""
+    _check(_lib.ssa_debug_corrupt_table_builds(int(n)), "ssa_debug_corrupt_table_builds")
 
 
 class KeySet:

@@ -4,6 +4,7 @@
 #define SSA_KERNELS_DEFINE 1
 #include "ssa_ctx.hpp"
 
+#include <atomic>
 #include <mutex>
 #include <thread>
 
@@ -21,6 +22,7 @@ extern "C" const char *ssa_strerror(int rc) {
         case SSA_ERR_HIP: return "HIP runtime error";
         case SSA_ERR_PARAMS: return "invalid parameter blob";
         case SSA_ERR_NO_DEVICE: return "no HIP device";
+        case SSA_ERR_TABLE: return "a precomputed table failed its self-check";
         default: return "unknown";
     }
 }
@@ -46,21 +48,44 @@ struct ssa_keyset {
 // The comb table depends on the device, the generator and its geometry only, and it is up to 17.7 GB: contexts of one
 // process share it (reference-counted; ssa_multi_create with several contexts per device, the tests' many engines, a
 // binding that makes a context per thread).  Built at the first acquisition on the acquiring context's stream,
-// synchronously, under the registry's lock; read-only afterwards.
+// synchronously, under the registry's lock, and checked row by row before it is handed out (ssa_selfcheck.hpp);
+// read-only afterwards.  A table that fails an on-demand check (ssa_ctx_selfcheck) is RETIRED: out of the registry, so
+// that no later context gets it, and freed with the last reference of the contexts that still hold it.
 struct SharedGtab {
     int device = 0;
     u32 bits = 0;
     u64 gen[12] = {};
     u64 *d_gtab = nullptr;
     int refs = 0;
+    int builds = 0;           // builds this table took (1; 2 when the first one failed its check)
+    bool retired = false;
 };
 static std::mutex g_gtab_mu;
 static std::vector<SharedGtab *> g_gtabs;
 
 static inline size_t gtab_bytes(u32 bits) { return gtab_entries(bits) * 12 * sizeof(u64); }
 
-// the table of `bits`-bit windows for this generator on this device: an existing one, or a new one (nullptr: no memory)
-static SharedGtab *gtab_acquire(ssa_ctx *ctx, const DevParams &hp, u32 bits) {
+// ssa_debug_corrupt_table_builds: the next n comb builds of the process get one word flipped before their check
+static std::atomic<int> g_corrupt_builds{0};
+
+static int debug_corrupt_build(ssa_ctx *ctx, SharedGtab *g) {
+    int n = g_corrupt_builds.load();
+    while (n > 0 && !g_corrupt_builds.compare_exchange_weak(n, n - 1)) {
+    }
+    if (n <= 0) return 0;
+    // a mid-table row (window count / 2, digit 12345 -- never the header row), word 7 (y, limb 1)
+    u64 *p = g->d_gtab + 12 * (((size_t)(gtab_windows(g->bits) / 2) << g->bits) + 12345) + 7, v = 0;
+    HIP_TRY(hipMemcpyAsync(&v, p, sizeof v, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    v ^= 1ull << 17;
+    HIP_TRY(hipMemcpyAsync(p, &v, sizeof v, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+// the table of `bits`-bit windows for this generator on this device: an existing one, or a new one (nullptr: no memory,
+// or -- *bad_table set -- a table that failed its check twice)
+static SharedGtab *gtab_acquire(ssa_ctx *ctx, const DevParams &hp, u32 bits, bool *bad_table) {
     std::lock_guard<std::mutex> lock(g_gtab_mu);
     u64 gen[12];
     for (int i = 0; i < 6; i++) {
@@ -82,11 +107,25 @@ static SharedGtab *gtab_acquire(ssa_ctx *ctx, const DevParams &hp, u32 bits) {
     bool ok = hipMalloc((void **)&g->d_gtab, gtab_bytes(bits)) == hipSuccess &&
               hipMalloc(&gbase, gbase_entries(bits) * 12 * sizeof(u64)) == hipSuccess;
     if (ok) {
-        hipLaunchKernelGGL(ssa_k_gbase, dim3(grid_for(gbase_entries(bits), 256)), dim3(256), 0, ctx->stream, ctx->d_params,
-                           (u64 *)gbase, bits);
-        hipLaunchKernelGGL(ssa_k_gtable, dim3(grid_for(gtab_entries(bits) / 8, 256)), dim3(256), 0, ctx->stream,
-                           (const u64 *)gbase, g->d_gtab, bits);
-        ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(ctx->stream) == hipSuccess;
+        // every row is checked before the table is handed out: a table that fails is rebuilt once in the same
+        // allocation, then given up (the caller moves on to the next smaller width)
+        bool clean = false;
+        for (int b = 0; b < 2 && ok && !clean; b++) {
+            hipLaunchKernelGGL(ssa_k_gbase, dim3(grid_for(gbase_entries(bits), 256)), dim3(256), 0, ctx->stream,
+                               ctx->d_params, (u64 *)gbase, bits);
+            hipLaunchKernelGGL(ssa_k_gtable, dim3(grid_for(gtab_entries(bits) / 8, 256)), dim3(256), 0, ctx->stream,
+                               (const u64 *)gbase, g->d_gtab, bits);
+            g->builds++;
+            ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(ctx->stream) == hipSuccess &&
+                 debug_corrupt_build(ctx, g) == 0;
+            uint64_t res[2] = {0, 0};
+            ok = ok && ssa_internal_gtab_check(ctx, g->d_gtab, bits, res) == 0;
+            clean = ok && res[0] == 0;
+        }
+        if (ok && !clean) {
+            *bad_table = true;
+            ok = false;
+        }
     } else {
         (void)hipGetLastError();      // an allocation that did not fit is not a sticky error: the caller tries a smaller table
     }
@@ -101,6 +140,7 @@ static SharedGtab *gtab_acquire(ssa_ctx *ctx, const DevParams &hp, u32 bits) {
     return g;
 }
 
+// (a retired table is no longer in the registry: the search finds nothing, the table is freed all the same)
 static void gtab_release(SharedGtab *g) {
     if (!g) return;
     std::lock_guard<std::mutex> lock(g_gtab_mu);
@@ -265,15 +305,18 @@ extern "C" int ssa_ctx_create_ex(ssa_ctx **out, int device, const void *params, 
     // the comb table of this generator on this device: shared by every context that asks for the same geometry.
     // Forced width: that one first; automatic: the widest within the budget.  Either way a failed allocation moves on
     // to the next smaller table.
+    // A table that fails its check twice counts as one that did not fit; no clean table at all is SSA_ERR_TABLE.
     static const u32 k_widths[4] = {24, 22, 20, 16};
+    bool bad_table = false;
     for (u32 wbits : k_widths) {
         if (gtab_bits ? wbits > gtab_bits : (wbits > 16 && gtab_bytes(wbits) > hbm_budget_bytes)) continue;
-        ctx->gtab_share = gtab_acquire(ctx, hp, wbits);
+        ctx->gtab_share = gtab_acquire(ctx, hp, wbits, &bad_table);
         if (ctx->gtab_share) break;
     }
     if (!ctx->gtab_share || ctx->ws_fail.reserve(64)) {
+        const int rc = !ctx->gtab_share && bad_table ? SSA_ERR_TABLE : SSA_ERR_HIP;
         ssa_ctx_destroy(ctx);
-        return SSA_ERR_HIP;
+        return rc;
     }
     ctx->d_gtab = ctx->gtab_share->d_gtab;
     ctx->gtab_bits = ctx->gtab_share->bits;
@@ -360,7 +403,7 @@ extern "C" void ssa_ctx_destroy(ssa_ctx *ctx) {
                       &ctx->msm_scalars, &ctx->msm_keys, &ctx->msm_vals, &ctx->msm_keys2, &ctx->msm_vals2,
                       &ctx->msm_sort_tmp, &ctx->msm_bounds, &ctx->msm_buckets, &ctx->msm_chunks, &ctx->msm_windows,
                       &ctx->msm_partials, &ctx->msm_flags, &ctx->st_coeffs, &ctx->msm_cnt, &ctx->msm_cnt2,
-                      &ctx->msm_ids, &ctx->msm_ids2, &ctx->msm_comb_pts, &ctx->msm_comb_lins, &ctx->msm_slice_recs, &ctx->msm_sbuf, &ctx->tail_done, &ctx->tail_park, &ctx->ctab, &ctx->sg_sigs, &ctx->sg_pks, &ctx->dv_recs})
+                      &ctx->msm_ids, &ctx->msm_ids2, &ctx->msm_comb_pts, &ctx->msm_comb_lins, &ctx->msm_slice_recs, &ctx->msm_sbuf, &ctx->tail_done, &ctx->tail_park, &ctx->ctab, &ctx->sg_sigs, &ctx->sg_pks, &ctx->dv_recs, &ctx->tc_out})
         b->release();
     for (HostBuf *b : {&ctx->pin_in, &ctx->pin_coeffs, &ctx->pin_out}) b->release();
     if (ctx->d_params) (void)hipFree(ctx->d_params);
@@ -406,6 +449,41 @@ extern "C" int ssa_ctx_info(const ssa_ctx *ctx, uint64_t out[8]) {
     out[6] = ctx->hbm_budget;
     out[7] = ctx->two_streams && !ctx->is_twin ? 1 : 0;
     return 0;
+}
+
+// The exact check of the context's tables on demand: the comb for G and, once built, the
+// constant-time table.  A comb that fails is retired from the registry (contexts created afterwards build a new one;
+// this one keeps its reference until it is destroyed).
+extern "C" int ssa_ctx_selfcheck(ssa_ctx *ctx, uint32_t flags, uint64_t out[8]) {
+    if (!ctx || !out || flags != 0) return SSA_ERR_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    uint64_t g[2], c[3] = {0, 0, ~0ull};
+    if (int rc = ssa_internal_gtab_check(ctx, ctx->d_gtab, ctx->gtab_bits, g)) return rc;
+    // the constant-time table only behind a clean comb: its offset rows are checked by a walk of the comb, and a wrong
+    // header word would misdirect that walk
+    if (g[0] == 0)
+        if (int rc = ssa_internal_ctab_selfcheck(ctx, c)) return rc;
+    out[0] = gtab_entries(ctx->gtab_bits);
+    out[1] = g[0];
+    out[2] = g[1];
+    out[3] = c[0];
+    out[4] = c[1];
+    out[5] = c[2];
+    out[6] = (uint64_t)ctx->gtab_share->builds;
+    out[7] = ctx->gtab_bits;
+    if (g[0]) {
+        std::lock_guard<std::mutex> lock(g_gtab_mu);
+        SharedGtab *sg = ctx->gtab_share;
+        if (!sg->retired) {
+            sg->retired = true;
+            for (size_t i = 0; i < g_gtabs.size(); i++)
+                if (g_gtabs[i] == sg) {
+                    g_gtabs.erase(g_gtabs.begin() + (long)i);
+                    break;
+                }
+        }
+    }
+    return g[0] || c[1] ? SSA_ERR_TABLE : SSA_OK;
 }
 
 extern "C" int ssa_ctx_uses_default_params(const ssa_ctx *ctx) { return ctx ? (ctx->default_params ? 1 : 0) : SSA_ERR_ARG; }
@@ -1305,6 +1383,12 @@ extern "C" int ssa_multi_verify_batch_msm(ssa_multi *m, const uint8_t *sigs, con
 }
 
 // ------------------------------------------------------------------ probes
+extern "C" int ssa_debug_corrupt_table_builds(int n) {
+    if (n < 0) return SSA_ERR_ARG;
+    g_corrupt_builds.store(n);
+    return 0;
+}
+
 extern "C" int ssa_debug_fault_after_chunk(ssa_ctx *ctx, int chunk) {
     if (!ctx) return SSA_ERR_ARG;
     ctx->fault_after_chunk = chunk;

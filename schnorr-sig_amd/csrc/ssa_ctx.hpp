@@ -131,6 +131,7 @@ struct ssa_ctx {
     // intermediates of the keyed (130-byte) output
     DevBuf ctab, sg_sigs, sg_pks;
     bool ctab_ready = false;
+    DevBuf tc_out;                // table self-check (ssa_selfcheck.hpp): failing rows, first failing row
     DevBuf dv_recs;               // key derivation (ssa_derive.hpp): one record per parent, wiped after each call
     unsigned verify_block = 256;  // threads per block of ssa_k_verify (SSA_VERIFY_BLOCK overrides: 64/128/256)
     // the end game of ssa_k_verify (ssa_kernels.hpp "The end game of a launch"): the last generation of lanes runs in
@@ -387,6 +388,11 @@ static inline int pipelined_upload_hash(ssa_ctx *ctx, const uint8_t *sigs, const
 // defined in ssa_api.hip: hash_message + Scalar::from_bits_vartime for n signatures into ctx->ws_h
 int ssa_internal_hash_scalars(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_msgs,
                               const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len, size_t n);
+
+// defined in ssa_sign.hip (ssa_selfcheck.hpp): the exact check of a comb table for G (res[0] failing rows, res[1] the
+// first failing row or ~0) and of the context's constant-time table (out[0] rows checked, out[1], out[2] as res)
+int ssa_internal_gtab_check(ssa_ctx *ctx, const uint64_t *d_gtab, uint32_t bits, uint64_t res[2]);
+int ssa_internal_ctab_selfcheck(ssa_ctx *ctx, uint64_t out[3]);
 
 // defined in ssa_api.hip: the context's second set of streams and workspaces (nullptr: none -- a twin itself, turned
 // off, or no memory for it)

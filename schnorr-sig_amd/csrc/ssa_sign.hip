@@ -421,17 +421,27 @@ int ssa_internal_sign_indexed_vartime(ssa_ctx *ctx, const ssa_signer_set *ss, co
                                       size_t msg_stride, size_t msg_len, size_t n, bool keyed, uint8_t *d_out,
                                       uint8_t *d_status_out);    // ssa_api.hip: the same for a signer set
 
+// the exact check of the tables (ssa_k_gtab_check, ssa_k_ctab_check_b) and its test hooks
+#include "ssa_selfcheck.hpp"
+
 // the 98 KB table of the constant-time signer, built once per context -- and COMPLETE before the call returns: a later
-// call may run on another stream (ssa_ctx_set_stream), and a failed build must not leave a table marked ready
+// call may run on another stream (ssa_ctx_set_stream), and a failed build must not leave a table marked ready.  It is
+// checked before it is marked ready: a table that fails is rebuilt once, then SSA_ERR_TABLE.
 static int ensure_ctab(ssa_ctx *ctx) {
     if (ctx->ctab_ready) return 0;
     if (ctx->ctab.reserve(CTAB_ROWS * 12 * sizeof(u64))) return SSA_ERR_HIP;
-    hipLaunchKernelGGL(ssa_k_ctab, dim3(grid_for(CTAB_ROWS, 64)), dim3(64), 0, ctx->stream, (const u64 *)ctx->d_gtab,
-                       (u64 *)ctx->ctab.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    ctx->ctab_ready = true;
-    return 0;
+    for (int build = 0; build < 2; build++) {
+        hipLaunchKernelGGL(ssa_k_ctab, dim3(grid_for(CTAB_ROWS, 64)), dim3(64), 0, ctx->stream, (const u64 *)ctx->d_gtab,
+                           (u64 *)ctx->ctab.p);
+        HIP_TRY(hipGetLastError());
+        uint64_t res[2];
+        if (int rc = ctab_check(ctx, res)) return rc;      // (synchronises the stream)
+        if (res[0] == 0) {
+            ctx->ctab_ready = true;
+            return 0;
+        }
+    }
+    return SSA_ERR_TABLE;
 }
 
 // PublicKey::from(&PrivateKey) for n secret keys (device buffers; the caller guarantees canonical non-zero scalars --

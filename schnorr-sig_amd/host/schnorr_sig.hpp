@@ -53,6 +53,12 @@ struct Panic : std::runtime_error {
 
 using Rng = std::function<void(uint8_t *, size_t)>;  // fills a buffer with random bytes
 
+// ssa_ctx_selfcheck's out[8] by name; ok == false is a failing table (SSA_ERR_TABLE), not an exception
+struct SelfCheck {
+    uint64_t rows, bad, first_bad, ctab_rows, ctab_bad, ctab_first_bad, builds, bits;
+    bool ok;
+};
+
 class Context {
   public:
     // gtab_bits / hbm_budget_bytes: the comb for G (the reference's const BASEPOINT_TABLE) as a speed-for-memory choice of
@@ -70,6 +76,14 @@ class Context {
     Context(const Context &) = delete;
     Context &operator=(const Context &) = delete;
     ssa_ctx *get() const { return ctx_; }
+    // the exact check of the comb for G and (once built) the constant-time table; a comb that fails is retired: destroy
+    // this context and create a new one
+    SelfCheck selfcheck() {
+        uint64_t o[8] = {};
+        const int rc = ssa_ctx_selfcheck(ctx_, 0, o);
+        if (rc != SSA_OK && rc != SSA_ERR_TABLE) throw std::runtime_error(std::string("ssa_ctx_selfcheck: ") + ssa_strerror(rc));
+        return SelfCheck{o[0], o[1], o[2], o[3], o[4], o[5], o[6], o[7], rc == SSA_OK};
+    }
 
   private:
     ssa_ctx *ctx_ = nullptr;
