@@ -442,6 +442,46 @@ int ssa_sign_many_indexed_device(ssa_ctx *ctx, ssa_signer_set *ss, const uint32_
                                  size_t msg_stride, size_t msg_len, size_t n, uint32_t flags,
                                  uint8_t *d_sigs_out, uint8_t *d_status_out);
 
+/* ---- nonces and keys drawn on the device (Scalar::random(rng)) --------------------------
+ * sign(message, rng) and sign_and_bind_pkey(message, rng) (src/signature.rs:65-156) with the nonces drawn by the GPU
+ * itself, and KeyPair::new(rng) (src/keypair.rs:57-65) for a whole signer set.  Each call takes a fresh 44-byte seed from
+ * getrandom(2) -- ChaCha20 key = seed[0:32], nonce = seed[32:44], RFC 8439 blocks with a 32-bit counter -- and lane i of
+ * the call (counted over the whole call) gets Scalar::from_bytes_wide(block 2i), or from_bytes_wide(block 2i + 1) where
+ * the first is 0, chosen by a constant-time select.  Neither the nonces nor the seed ever reach the host: the seed passes
+ * through the library's page-locked buffer (wiped before the call returns) into device memory, and the device seed and
+ * the drawn scalars are zeroed on the context's stream after the signing kernels.  Device memory for the draw is one
+ * slice (SSA_LANE_SLICE lanes, 32 B each), whatever n is.  The _device forms wait for the seed upload (and so for the work
+ * queued before it on the stream) before they enqueue the rest. */
+/* ssa_keygen_sign_many_ex with nonces drawn on the device: flags, checks, limits and output layout are those of
+ * ssa_keygen_sign_many_ex (SSA_FLAG_SIGN_CT, SSA_FLAG_SIGN_KEYED; any other bit is SSA_ERR_ARG), and the output is
+ * byte-identical to it given the drawn nonces. */
+int ssa_keygen_sign_many_rng(ssa_ctx *ctx, const uint8_t *sks, const uint8_t *msgs, const uint64_t *msg_off,
+                             size_t msg_stride, size_t msg_len, size_t n, uint32_t flags, uint8_t *pks_out,
+                             uint8_t *sigs_out);
+int ssa_keygen_sign_many_rng_device(ssa_ctx *ctx, const uint8_t *d_sks, const uint8_t *d_msgs,
+                                    const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len, size_t n,
+                                    uint32_t flags, uint8_t *d_pks_out, uint8_t *d_sigs_out);
+/* ssa_sign_many_indexed[_device] with nonces drawn on the device: statuses, errors and orphan behaviour are theirs */
+int ssa_sign_many_indexed_rng(ssa_ctx *ctx, ssa_signer_set *ss, const uint32_t *key_idx, const uint8_t *msgs,
+                              const uint64_t *msg_off, size_t msg_stride, size_t msg_len, size_t n, uint32_t flags,
+                              uint8_t *sigs_out);
+int ssa_sign_many_indexed_rng_device(ssa_ctx *ctx, ssa_signer_set *ss, const uint32_t *d_key_idx,
+                                     const uint8_t *d_msgs, const uint64_t *d_msg_off, size_t msg_stride,
+                                     size_t msg_len, size_t n, uint32_t flags, uint8_t *d_sigs_out,
+                                     uint8_t *d_status_out);
+/* KeyPair::new(rng) for m key pairs (1 <= m <= SSA_MAX_BATCH): key j is the draw of lane j under a fresh seed; public
+ * keys and statuses come from the path of ssa_signer_set_create_device */
+int ssa_signer_set_generate(ssa_ctx *ctx, size_t m, ssa_signer_set **out);
+/* KeyPair::to_bytes (src/keypair.rs:73-75) for the whole set: m x 32 bytes, zeros for a malformed key.  What makes a
+ * generated set persistable -- and the one call that brings its secret keys to the host. */
+int ssa_signer_set_secret_keys(ssa_signer_set *ss, uint8_t *sks_out);
+/* TEST HOOKS.  ssa_debug_pin_rng makes every later draw on ctx use `seed` (44 bytes) instead of getrandom(2); NULL
+ * unpins.  A PINNED CONTEXT REUSES ITS NONCES ON EVERY CALL, AND TWO SIGNATURES BY ONE KEY WITH ONE NONCE GIVE THE KEY
+ * AWAY: for tests only, never in production.  ssa_debug_draw_scalars runs the device's draw rule on n caller-supplied
+ * block pairs (B0 || B1, 128 bytes each) and writes n x 32 bytes. */
+int ssa_debug_pin_rng(ssa_ctx *ctx, const uint8_t seed[44]);
+int ssa_debug_draw_scalars(ssa_ctx *ctx, const uint8_t *blocks, size_t n, uint8_t *out);
+
 /* ---- several GPUs of one node from a single process --------------------------------------------
  * The batch shards by signature (contiguous ranges, sizes differ by at most one) over the listed
  * devices -- one context and one host thread per device, no collective: every verification reads

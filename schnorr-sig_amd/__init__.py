@@ -60,6 +60,20 @@ _MODE_FLAGS = {None: 0, "auto": 0, "lane": FLAG_FORCE_LANE, "coop": FLAG_FORCE_C
 Q = 0x7AF2599B3B3F22D0563FBF0F990A37B5327AA72330157722D443623EAED4ACCF
 
 
+class _DeviceRng:
+    """the `rng` that has the GPU draw the nonces itself (ssa_*_rng): no nonce exists on the
+    host.  Accepted by KeyPair.sign / sign_and_bind_pkey, PrivateKey.sign / sign_and_bind_pkey and SignerSet.sign."""
+
+    def __repr__(self):
+        return "DEVICE_RNG"
+
+    def __call__(self, n):
+        raise TypeError("DEVICE_RNG draws on the device only; it yields no bytes on the host")
+
+
+DEVICE_RNG = _DeviceRng()
+
+
 class SignatureError(Exception):
     """src/error.rs:13-31 (Display strings kept verbatim)."""
     InvalidPublicKey = "InvalidPublicKey"
@@ -203,6 +217,14 @@ def _load():
         "ssa_debug_table_read": (i32, [vp, i32, C.c_uint64, C.c_uint64, vp]),
         "ssa_debug_table_xor": (i32, [vp, i32, C.c_uint64, u32, C.c_uint64]),
         "ssa_debug_corrupt_table_builds": (i32, [i32]),
+        "ssa_keygen_sign_many_rng": (i32, [vp, vp, vp, vp, sz, sz, sz, u32, vp, vp]),
+        "ssa_keygen_sign_many_rng_device": (i32, [vp, vp, vp, vp, sz, sz, sz, u32, vp, vp]),
+        "ssa_sign_many_indexed_rng": (i32, [vp, vp, vp, vp, vp, sz, sz, sz, u32, vp]),
+        "ssa_sign_many_indexed_rng_device": (i32, [vp, vp, vp, vp, vp, sz, sz, sz, u32, vp, vp]),
+        "ssa_signer_set_generate": (i32, [vp, sz, C.POINTER(vp)]),
+        "ssa_signer_set_secret_keys": (i32, [vp, vp]),
+        "ssa_debug_pin_rng": (i32, [vp, vp]),
+        "ssa_debug_draw_scalars": (i32, [vp, vp, sz, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)      # AttributeError here == ABI symbol missing: fail loudly
@@ -645,6 +667,74 @@ class Engine:
                                                  msg_stride if msg_stride is not None else msg_len, msg_len, n, flags,
                                                  d_sigs, d_status or None), "ssa_sign_many_indexed_device")
 
+    # ---- nonces and keys drawn on the device (Scalar::random(rng) on the GPU: no nonce exists on the host) ------
+    def keygen_sign_many_rng(self, sks, msgs, offsets=None, constant_time=False, keyed=False):
+        """keygen_sign_many with the nonces drawn on the device -> (pks uint8[n, 96], sigs uint8[n, 81] or [n, 130])"""
+        sks = _np_u8(sks, 32)
+        n = sks.shape[0]
+        m, off, stride, mlen = self._msg_args(msgs, offsets, n)
+        pks = np.zeros((n, 96), dtype=np.uint8)
+        sigs = np.zeros((n, 130 if keyed else 81), dtype=np.uint8)
+        flags = (FLAG_SIGN_CT if constant_time else 0) | (FLAG_SIGN_KEYED if keyed else 0)
+        _check(_lib.ssa_keygen_sign_many_rng(self._ctx, _ptr(sks), _ptr(m), _ptr(off), stride, mlen, n, flags, _ptr(pks),
+                                             _ptr(sigs)), "ssa_keygen_sign_many_rng")
+        return pks, sigs
+
+    def keygen_sign_many_rng_device(self, d_sks, d_msgs, n, msg_len, d_pks, d_sigs, msg_stride=None, d_offsets=0,
+                                    constant_time=False, keyed=False):
+        flags = (FLAG_SIGN_CT if constant_time else 0) | (FLAG_SIGN_KEYED if keyed else 0)
+        _check(_lib.ssa_keygen_sign_many_rng_device(self._ctx, d_sks, d_msgs, d_offsets or None,
+                                                    msg_stride if msg_stride is not None else msg_len, msg_len, n, flags,
+                                                    d_pks or None, d_sigs), "ssa_keygen_sign_many_rng_device")
+
+    def sign_many_indexed_rng(self, ss, key_idx, msgs, offsets=None, constant_time=False, keyed=False):
+        """sign_many_indexed with the nonces drawn on the device -> uint8[n, 81] (uint8[n, 130] keyed)"""
+        idx = np.ascontiguousarray(key_idx, dtype=np.uint32).reshape(-1)
+        n = idx.shape[0]
+        m, off, stride, mlen = self._msg_args(msgs, offsets, n)
+        sigs = np.zeros((n, 130 if keyed else 81), dtype=np.uint8)
+        flags = (FLAG_SIGN_CT if constant_time else 0) | (FLAG_SIGN_KEYED if keyed else 0)
+        _check(_lib.ssa_sign_many_indexed_rng(self._ctx, ss.handle, _ptr(idx), _ptr(m), _ptr(off), stride, mlen, n, flags,
+                                              _ptr(sigs)), "ssa_sign_many_indexed_rng")
+        return sigs
+
+    def sign_many_indexed_rng_device(self, ss, d_key_idx, d_msgs, n, msg_len, d_sigs, d_status=0, msg_stride=None,
+                                     d_offsets=0, constant_time=False, keyed=False):
+        flags = (FLAG_SIGN_CT if constant_time else 0) | (FLAG_SIGN_KEYED if keyed else 0)
+        _check(_lib.ssa_sign_many_indexed_rng_device(self._ctx, ss.handle, d_key_idx, d_msgs, d_offsets or None,
+                                                     msg_stride if msg_stride is not None else msg_len, msg_len, n,
+                                                     flags, d_sigs, d_status or None), "ssa_sign_many_indexed_rng_device")
+
+    def signer_set_generate(self, m):
+        """KeyPair::new(rng) for m key pairs whose secret keys are drawn on the device -> SignerSet"""
+        ss = C.c_void_p()
+        _check(_lib.ssa_signer_set_generate(self._ctx, int(m), C.byref(ss)), "ssa_signer_set_generate")
+        return SignerSet(self, ss, m)
+
+    def signer_set_secret_keys(self, ss):
+        """KeyPair::to_bytes for the whole set -> uint8[m, 32] (zeros for a malformed key)"""
+        sks = np.zeros((ss.m, 32), dtype=np.uint8)
+        _check(_lib.ssa_signer_set_secret_keys(ss.handle, _ptr(sks)), "ssa_signer_set_secret_keys")
+        return sks
+
+    def debug_pin_rng(self, seed44):
+        """TESTS ONLY: every later draw on this engine uses seed44 (None unpins).  A pinned engine reuses its nonces,
+        which gives the signing keys away."""
+        if seed44 is None:
+            _check(_lib.ssa_debug_pin_rng(self._ctx, None), "ssa_debug_pin_rng")
+            return
+        seed = _np_u8(bytearray(seed44))
+        if seed.size != 44:
+            raise ValueError("the seed is 44 bytes")
+        _check(_lib.ssa_debug_pin_rng(self._ctx, _ptr(seed)), "ssa_debug_pin_rng")
+
+    def debug_draw_scalars(self, blocks):
+        """the device's draw rule on n block pairs B0 || B1 (uint8[n, 128]) -> uint8[n, 32]"""
+        b = _np_u8(blocks, 128)
+        out = np.zeros((b.shape[0], 32), dtype=np.uint8)
+        _check(_lib.ssa_debug_draw_scalars(self._ctx, _ptr(b), b.shape[0], _ptr(out)), "ssa_debug_draw_scalars")
+        return out
+
     # ---- device-buffer entry points (raw device addresses, e.g. torch.Tensor.data_ptr()) ----
     def set_stream(self, hip_stream):
         _check(_lib.ssa_ctx_set_stream(self._ctx, C.c_void_p(hip_stream or 0)), "ssa_ctx_set_stream")
@@ -812,16 +902,30 @@ class SignerSet:
         ss.public_keys = [kp.public_key for kp in key_pairs]
         return ss
 
+    @classmethod
+    def generate(cls, m, engine=None):
+        """KeyPair::new(rng) (src/keypair.rs:57-65) for m key pairs, the secret keys drawn on the device"""
+        return (engine or default_engine()).signer_set_generate(m)
+
+    def secret_keys(self):
+        """KeyPair::to_bytes for every key pair -> uint8[m, 32]: the one call that brings the keys to the host"""
+        return self.engine.signer_set_secret_keys(self)
+
     def sign(self, key_idx, messages, rng, constant_time=True, keyed=False):
         """KeyPair::sign (src/signature.rs:114-129) of messages[i] by key pair key_idx[i], nonces drawn as KeyPair
-        draws them -> [Signature], or [KeyedSignature] (sign_and_bind_pkey, :132-156) with keyed=True"""
+        draws them -> [Signature], or [KeyedSignature] (sign_and_bind_pkey, :132-156) with keyed=True.
+        rng=DEVICE_RNG draws the nonces on the device."""
         idx = [int(k) for k in key_idx]
         if len(idx) != len(messages):
             raise ValueError("one key index per message")
-        nonces = np.frombuffer(b"".join(KeyPair._nonce(None, rng) for _ in idx), np.uint8).reshape(-1, 32)
         flat, off = pack_messages(messages)
-        out = self.engine.sign_many_indexed(self, np.array(idx, dtype=np.uint32), nonces, flat, offsets=off,
-                                            constant_time=constant_time, keyed=keyed)
+        if rng is DEVICE_RNG:
+            out = self.engine.sign_many_indexed_rng(self, np.array(idx, dtype=np.uint32), flat, offsets=off,
+                                                    constant_time=constant_time, keyed=keyed)
+        else:
+            nonces = np.frombuffer(b"".join(KeyPair._nonce(None, rng) for _ in idx), np.uint8).reshape(-1, 32)
+            out = self.engine.sign_many_indexed(self, np.array(idx, dtype=np.uint32), nonces, flat, offsets=off,
+                                                constant_time=constant_time, keyed=keyed)
         if not keyed:
             return [Signature(r.tobytes()) for r in out]
         pub = self.public_keys
@@ -1133,8 +1237,12 @@ class KeyPair:
         eng = engine or default_engine()
         msg = np.frombuffer(bytes(message) + b"\0", np.uint8).copy()
         off = np.array([0, len(message)], dtype=np.uint64)
-        _, sigs = eng.keygen_sign_many(np.frombuffer(self.private_key.bytes, np.uint8),
-                                       np.frombuffer(self._nonce(rng), np.uint8), msg, offsets=off, constant_time=True)
+        sk = np.frombuffer(self.private_key.bytes, np.uint8)
+        if rng is DEVICE_RNG:
+            _, sigs = eng.keygen_sign_many_rng(sk, msg, offsets=off, constant_time=True)
+        else:
+            _, sigs = eng.keygen_sign_many(sk, np.frombuffer(self._nonce(rng), np.uint8), msg, offsets=off,
+                                           constant_time=True)
         return Signature(sigs[0].tobytes())
 
     def verify_signature(self, signature, message):  # src/signature.rs:159-165
@@ -1145,9 +1253,12 @@ class KeyPair:
         eng = engine or default_engine()
         msg = np.frombuffer(bytes(message) + b"\0", np.uint8).copy()
         off = np.array([0, len(message)], dtype=np.uint64)
-        _, recs = eng.keygen_sign_many(np.frombuffer(self.private_key.bytes, np.uint8),
-                                       np.frombuffer(self._nonce(rng), np.uint8), msg, offsets=off, constant_time=True,
-                                       keyed=True)
+        sk = np.frombuffer(self.private_key.bytes, np.uint8)
+        if rng is DEVICE_RNG:
+            _, recs = eng.keygen_sign_many_rng(sk, msg, offsets=off, constant_time=True, keyed=True)
+        else:
+            _, recs = eng.keygen_sign_many(sk, np.frombuffer(self._nonce(rng), np.uint8), msg, offsets=off,
+                                           constant_time=True, keyed=True)
         return KeyedSignature(self.public_key, Signature(recs[0, 49:].tobytes()))
 
 

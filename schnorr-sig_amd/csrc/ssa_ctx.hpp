@@ -133,6 +133,12 @@ struct ssa_ctx {
     bool ctab_ready = false;
     DevBuf tc_out;                // table self-check (ssa_selfcheck.hpp): failing rows, first failing row
     DevBuf dv_recs;               // key derivation (ssa_derive.hpp): one record per parent, wiped after each call
+    // device-drawn scalars (ssa_rng.hpp): the call's 44-byte seed, one slice of drawn scalars (both zeroed on the stream
+    // after each call), the page-locked host copy of the seed (wiped before the call returns) and the test pin
+    DevBuf rng_seed, rng_scratch;
+    HostBuf pin_seed;
+    bool rng_pinned = false;
+    uint8_t rng_pin[44] = {};
     unsigned verify_block = 256;  // threads per block of ssa_k_verify (SSA_VERIFY_BLOCK overrides: 64/128/256)
     // the end game of ssa_k_verify (ssa_kernels.hpp "The end game of a launch"): the last generation of lanes runs in
     // tail_pieces pieces per ladder pass, only the last of which stand at the end of the grid

@@ -656,21 +656,32 @@ extern "C" void ssa_signer_set_destroy(ssa_signer_set *ss) {
 
 // the keys (checked and copied), then PublicKey::from(&PrivateKey) and PublicKey::to_bytes once per key -- the kernels
 // of ssa_pubkey_many and ssa_compress_many, so the set's keys are theirs byte for byte
-static int signer_set_fill(ssa_ctx *ctx, ssa_signer_set *ss, const uint8_t *d_sks, size_t stride) {
+static int signer_set_reserve(ssa_signer_set *ss) {
     const size_t m = ss->m;
     if (ss->sks.reserve(m * 32) || ss->pks.reserve(m * 96) || ss->cpks.reserve(m * 49) || ss->status.reserve(m + 16))
         return SSA_ERR_HIP;
-    if (int rc = timed_launch(ctx, "ssa_k_signer_keys", [&] {
-            hipLaunchKernelGGL(ssa_k_signer_keys, dim3(grid_for(m, 256)), dim3(256), 0, ctx->stream, d_sks, stride, m,
-                               (u8 *)ss->sks.p, (u8 *)ss->status.p);
-        }))
-        return rc;
+    return 0;
+}
+// keys lo .. lo + cnt - 1 of the set from d_sks (key k - lo at d_sks + (k - lo) * stride)
+static int signer_set_keys(ssa_ctx *ctx, ssa_signer_set *ss, const uint8_t *d_sks, size_t stride, size_t lo, size_t cnt) {
+    return timed_launch(ctx, "ssa_k_signer_keys", [&] {
+        hipLaunchKernelGGL(ssa_k_signer_keys, dim3(grid_for(cnt, 256)), dim3(256), 0, ctx->stream, d_sks, stride, cnt,
+                           (u8 *)ss->sks.p + 32 * lo, (u8 *)ss->status.p + lo);
+    });
+}
+static int signer_set_publish(ssa_ctx *ctx, ssa_signer_set *ss) {
+    const size_t m = ss->m;
     if (int rc = ssa_pubkey_many_device(ctx, (const u8 *)ss->sks.p, m, (u8 *)ss->pks.p)) return rc;
     if (int rc = ssa_compress_many_device(ctx, (const u8 *)ss->pks.p, nullptr, m, (u8 *)ss->cpks.p, nullptr)) return rc;
     ss->host_status.assign(m, 0xff);
     HIP_TRY(hipMemcpyAsync(ss->host_status.data(), ss->status.p, m, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return 0;
+}
+static int signer_set_fill(ssa_ctx *ctx, ssa_signer_set *ss, const uint8_t *d_sks, size_t stride) {
+    if (int rc = signer_set_reserve(ss)) return rc;
+    if (int rc = signer_set_keys(ctx, ss, d_sks, stride, 0, ss->m)) return rc;
+    return signer_set_publish(ctx, ss);
 }
 
 extern "C" int ssa_signer_set_create_device(ssa_ctx *ctx, const uint8_t *d_sks, size_t sk_stride, size_t m,
@@ -765,3 +776,6 @@ extern "C" int ssa_sign_many_indexed(ssa_ctx *ctx, ssa_signer_set *ss, const uin
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return 0;
 }
+
+// Scalar::random(rng) on the device: the _rng signers, ssa_signer_set_generate and their test hooks
+#include "ssa_rng.hpp"

@@ -52,6 +52,10 @@ struct Panic : std::runtime_error {
 };
 
 using Rng = std::function<void(uint8_t *, size_t)>;  // fills a buffer with random bytes
+// the `rng` that has the GPU draw the nonces (and the keys of SignerSet::generate) itself: no nonce exists on the host
+// (ssa_*_rng)
+struct DeviceRng {};
+inline constexpr DeviceRng device_rng{};
 
 // ssa_ctx_selfcheck's out[8] by name; ok == false is a failing table (SSA_ERR_TABLE), not an exception
 struct SelfCheck {
@@ -166,6 +170,8 @@ struct PrivateKey {  // src/private.rs:25
     // is recomputed first, PublicKey::from(self)) -- defined after KeyPair
     Signature sign(Context &cx, const uint8_t *msg, size_t len, Rng rng) const;
     KeyedSignature sign_and_bind_pkey(Context &cx, const uint8_t *msg, size_t len, Rng rng) const;
+    Signature sign(Context &cx, const uint8_t *msg, size_t len, DeviceRng) const;
+    KeyedSignature sign_and_bind_pkey(Context &cx, const uint8_t *msg, size_t len, DeviceRng) const;
 };
 
 struct PublicKey {  // src/public.rs:24 -- the in-memory AffinePoint (x, y), canonical LE limbs
@@ -313,6 +319,25 @@ struct KeyPair {  // src/keypair.rs:48-53
         std::memcpy(ks.signature.bytes.data(), rec + PUBLIC_KEY_LENGTH, SIGNATURE_LENGTH);
         return ks;
     }
+    // the same two with the nonce drawn on the device (ssa_keygen_sign_many_rng)
+    Signature sign(Context &cx, const uint8_t *msg, size_t len, DeviceRng) const {
+        uint8_t pk[AFFINE_PUBLIC_KEY_LENGTH], dummy = 0;
+        Signature s;
+        int rc = ssa_keygen_sign_many_rng(cx.get(), private_key.bytes.data(), len ? msg : &dummy, nullptr, len, len, 1,
+                                          SSA_FLAG_SIGN_CT, pk, s.bytes.data());
+        if (rc != 0) throw std::runtime_error(std::string("ssa_keygen_sign_many_rng: ") + ssa_strerror(rc));
+        return s;
+    }
+    KeyedSignature sign_and_bind_pkey(Context &cx, const uint8_t *msg, size_t len, DeviceRng) const {
+        uint8_t rec[KEYED_SIGNATURE_LENGTH], dummy = 0;
+        int rc = ssa_keygen_sign_many_rng(cx.get(), private_key.bytes.data(), len ? msg : &dummy, nullptr, len, len, 1,
+                                          SSA_FLAG_SIGN_CT | SSA_FLAG_SIGN_KEYED, nullptr, rec);
+        if (rc != 0) throw std::runtime_error(std::string("ssa_keygen_sign_many_rng: ") + ssa_strerror(rc));
+        KeyedSignature ks;
+        ks.public_key = public_key;
+        std::memcpy(ks.signature.bytes.data(), rec + PUBLIC_KEY_LENGTH, SIGNATURE_LENGTH);
+        return ks;
+    }
     Result verify_signature(Context &cx, const Signature &sig, const uint8_t *msg, size_t len) const {
         return sig.verify(cx, msg, len, public_key);  // src/signature.rs:159-165
     }
@@ -324,6 +349,12 @@ inline Signature PrivateKey::sign(Context &cx, const uint8_t *msg, size_t len, R
 }
 inline KeyedSignature PrivateKey::sign_and_bind_pkey(Context &cx, const uint8_t *msg, size_t len, Rng rng) const {
     return KeyPair::from_private(cx, *this).sign_and_bind_pkey(cx, msg, len, rng);
+}
+inline Signature PrivateKey::sign(Context &cx, const uint8_t *msg, size_t len, DeviceRng r) const {
+    return KeyPair::from_private(cx, *this).sign(cx, msg, len, r);
+}
+inline KeyedSignature PrivateKey::sign_and_bind_pkey(Context &cx, const uint8_t *msg, size_t len, DeviceRng r) const {
+    return KeyPair::from_private(cx, *this).sign_and_bind_pkey(cx, msg, len, r);
 }
 
 // Many signatures by few signers (validator sets; the reference's own batch test reuses keys, src/batch.rs:152-175):
@@ -376,21 +407,36 @@ class KeySet {
 // Many signatures by few key pairs (a service's keys, derived deposit addresses): the key pairs stay on the device
 // (ssa_signer_set_create) and sign() is KeyPair::sign (src/signature.rs:114-129) -- constant-time, one base
 // multiplication per signature -- of message i by key pair key_idx[i]; sign_and_bind_pkey() gives the KeyedSignature
-// records (:132-156).  The destructor zeroes the secret keys on the device.
+// records (:132-156).  The destructor zeroes the secret keys on the device.  SignerSet(cx, m, device_rng) is
+// KeyPair::new(rng) for m key pairs drawn on the device (ssa_signer_set_generate); secret_keys() exports them.
 class SignerSet {
   public:
-    SignerSet(Context &cx, const std::vector<KeyPair> &pairs) : cx_(cx), pairs_(pairs) {
+    SignerSet(Context &cx, const std::vector<KeyPair> &pairs) : cx_(cx), m_(pairs.size()) {
         std::vector<uint8_t> sks(pairs.size() * PRIVATE_KEY_LENGTH);
-        for (size_t i = 0; i < pairs.size(); i++)
+        for (size_t i = 0; i < pairs.size(); i++) {
             std::memcpy(&sks[i * PRIVATE_KEY_LENGTH], pairs[i].private_key.bytes.data(), PRIVATE_KEY_LENGTH);
+            pks_.push_back(pairs[i].public_key);
+        }
         int rc = ssa_signer_set_create(cx.get(), sks.data(), pairs.size(), &ss_);
         std::fill(sks.begin(), sks.end(), 0);
         if (rc != 0) throw std::runtime_error(std::string("ssa_signer_set_create: ") + ssa_strerror(rc));
     }
+    SignerSet(Context &cx, size_t m, DeviceRng) : cx_(cx), m_(m) {
+        int rc = ssa_signer_set_generate(cx.get(), m, &ss_);
+        if (rc != 0) throw std::runtime_error(std::string("ssa_signer_set_generate: ") + ssa_strerror(rc));
+        pks_ = public_keys();
+    }
     ~SignerSet() { ssa_signer_set_destroy(ss_); }
     SignerSet(const SignerSet &) = delete;
     SignerSet &operator=(const SignerSet &) = delete;
-    size_t size() const { return pairs_.size(); }
+    size_t size() const { return m_; }
+    // KeyPair::to_bytes of every key pair (src/keypair.rs:73-75): the one call that brings the keys to the host
+    std::vector<std::array<uint8_t, KEY_PAIR_LENGTH>> secret_keys() const {
+        std::vector<std::array<uint8_t, KEY_PAIR_LENGTH>> out(size());
+        int rc = ssa_signer_set_secret_keys(ss_, size() ? out[0].data() : nullptr);
+        if (rc != 0) throw std::runtime_error(std::string("ssa_signer_set_secret_keys: ") + ssa_strerror(rc));
+        return out;
+    }
     // the public keys as the set computed them: 96-byte affine and 49-byte compressed
     std::vector<PublicKey> public_keys() const {
         std::vector<uint8_t> pks(size() * AFFINE_PUBLIC_KEY_LENGTH);
@@ -402,41 +448,62 @@ class SignerSet {
     }
     std::vector<Signature> sign(const std::vector<uint32_t> &key_idx,
                                 const std::vector<std::pair<const uint8_t *, size_t>> &messages, Rng rng) const {
-        std::vector<Signature> out(key_idx.size());
-        const auto recs = run(key_idx, messages, rng, SSA_FLAG_SIGN_CT, SIGNATURE_LENGTH);
-        for (size_t i = 0; i < out.size(); i++)
-            std::memcpy(out[i].bytes.data(), &recs[i * SIGNATURE_LENGTH], SIGNATURE_LENGTH);
-        return out;
+        return sigs(run(key_idx, messages, &rng, SSA_FLAG_SIGN_CT, SIGNATURE_LENGTH));
     }
     std::vector<KeyedSignature> sign_and_bind_pkey(const std::vector<uint32_t> &key_idx,
                                                    const std::vector<std::pair<const uint8_t *, size_t>> &messages,
                                                    Rng rng) const {
+        return keyed(key_idx, run(key_idx, messages, &rng, SSA_FLAG_SIGN_CT | SSA_FLAG_SIGN_KEYED, KEYED_SIGNATURE_LENGTH));
+    }
+    // the same two with the nonces drawn on the device (ssa_sign_many_indexed_rng)
+    std::vector<Signature> sign(const std::vector<uint32_t> &key_idx,
+                                const std::vector<std::pair<const uint8_t *, size_t>> &messages, DeviceRng) const {
+        return sigs(run(key_idx, messages, nullptr, SSA_FLAG_SIGN_CT, SIGNATURE_LENGTH));
+    }
+    std::vector<KeyedSignature> sign_and_bind_pkey(const std::vector<uint32_t> &key_idx,
+                                                   const std::vector<std::pair<const uint8_t *, size_t>> &messages,
+                                                   DeviceRng) const {
+        return keyed(key_idx, run(key_idx, messages, nullptr, SSA_FLAG_SIGN_CT | SSA_FLAG_SIGN_KEYED, KEYED_SIGNATURE_LENGTH));
+    }
+
+  private:
+    static std::vector<Signature> sigs(const std::vector<uint8_t> &recs) {
+        std::vector<Signature> out(recs.size() / SIGNATURE_LENGTH);
+        for (size_t i = 0; i < out.size(); i++)
+            std::memcpy(out[i].bytes.data(), &recs[i * SIGNATURE_LENGTH], SIGNATURE_LENGTH);
+        return out;
+    }
+    std::vector<KeyedSignature> keyed(const std::vector<uint32_t> &key_idx, const std::vector<uint8_t> &recs) const {
         std::vector<KeyedSignature> out(key_idx.size());
-        const auto recs = run(key_idx, messages, rng, SSA_FLAG_SIGN_CT | SSA_FLAG_SIGN_KEYED, KEYED_SIGNATURE_LENGTH);
         for (size_t i = 0; i < out.size(); i++) {
-            out[i].public_key = pairs_[key_idx[i]].public_key;
+            out[i].public_key = pks_[key_idx[i]];
             std::memcpy(out[i].signature.bytes.data(), &recs[i * KEYED_SIGNATURE_LENGTH + PUBLIC_KEY_LENGTH],
                         SIGNATURE_LENGTH);
         }
         return out;
     }
-
-  private:
+    // rng == nullptr: the nonces are drawn on the device
     std::vector<uint8_t> run(const std::vector<uint32_t> &key_idx,
-                             const std::vector<std::pair<const uint8_t *, size_t>> &messages, Rng &rng, uint32_t flags,
+                             const std::vector<std::pair<const uint8_t *, size_t>> &messages, Rng *rng, uint32_t flags,
                              size_t rec_len) const {
         const size_t n = key_idx.size();
         if (messages.size() != n) throw Panic("one key index per message");
         for (uint32_t k : key_idx)
             if (k >= size()) throw Panic("key index out of range");
-        std::vector<uint8_t> nonces(n * SCALAR_LENGTH), flat, recs(n * rec_len);
+        std::vector<uint8_t> nonces(rng ? n * SCALAR_LENGTH : 0), flat, recs(n * rec_len);
         std::vector<uint64_t> off(n + 1, 0);
         for (size_t i = 0; i < n; i++) {
-            KeyPair::random_scalar(rng, &nonces[i * SCALAR_LENGTH]);
+            if (rng) KeyPair::random_scalar(*rng, &nonces[i * SCALAR_LENGTH]);
             flat.insert(flat.end(), messages[i].first, messages[i].first + messages[i].second);
             off[i + 1] = flat.size();
         }
         flat.push_back(0);
+        if (!rng) {
+            int rc = ssa_sign_many_indexed_rng(cx_.get(), ss_, key_idx.data(), flat.data(), off.data(), 0, 0, n, flags,
+                                               recs.data());
+            if (rc != 0) throw std::runtime_error(std::string("ssa_sign_many_indexed_rng: ") + ssa_strerror(rc));
+            return recs;
+        }
         int rc = ssa_sign_many_indexed(cx_.get(), ss_, key_idx.data(), nonces.data(), flat.data(), off.data(), 0, 0, n,
                                        flags, recs.data());
         std::fill(nonces.begin(), nonces.end(), 0);
@@ -444,7 +511,8 @@ class SignerSet {
         return recs;
     }
     Context &cx_;
-    std::vector<KeyPair> pairs_;
+    size_t m_;
+    std::vector<PublicKey> pks_;
     ssa_signer_set *ss_ = nullptr;
 };
 
