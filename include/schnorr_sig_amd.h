@@ -208,6 +208,35 @@ int ssa_verify_batch_msm(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t *pks, 
                          const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len,
                          size_t n, const uint8_t *coeffs);
 
+/* Screened batch verification: a per-signature status vector at close to the price of one MSM verdict (DESIGN.md
+ * section 13).  The MSM of ssa_verify_batch_msm, with its buckets keyed by (window, segment, digit), gives one sum per
+ * contiguous segment of the batch in one pass.  A segment whose sum is the identity is accepted as a whole; only the
+ * lanes of failing segments run the exact per-lane check, on the challenge scalars the MSM already computed.
+ * status_out[i] is 0, 2 or 3 with verify_batch semantics: the flag byte is honoured (SSA_FLAG_SIG_FLAG_BYTE), there is
+ * no subgroup check, and pk_inf marks identity keys, exactly as ssa_verify_batch.
+ *   - 3 (SSA_MALFORMED) exactly on the lanes where ssa_verify_many(..., SSA_FLAG_SIG_FLAG_BYTE) says 3: non-canonical
+ *     limbs, e >= q, a key off the curve, an undecodable sig.x or flag byte.  Such lanes add nothing to any segment.
+ *   - A lane the per-lane check accepts is never rejected: its E_i = R_i - [h_i]P_i - [e_i]G is exactly O, so a segment
+ *     of valid lanes always passes, and a lane in a failing segment gets its per-lane status.
+ *   - A lane the per-lane check rejects gets that status (2, or 3 as above) UNLESS its segment's random combination
+ *     vanishes, sum s_i E_i = O over the segment: the soundness of the reference's verify_batch (DESIGN.md section 1,
+ *     divergence class 1) -- about 2^-128 for an error with a prime-order component, but 1/l for an error of pure small
+ *     order l (2, 5, ...: reachable only with keys or R outside the prime-order subgroup).  A small-order part of P_i
+ *     enters the sum through the reduced scalar s_i h_i mod q, as in the reference (src/batch.rs:109-111): with a key
+ *     P + T2 (T2 of order 2) the lane is reported exactly when s_i h_i mod q is odd.  A segment is checked as the
+ *     point equation sum s_i R_i - sum s_i h_i P_i == [sum s_i e_i] G, not x-only: the global-sign divergence of the
+ *     MSM form (class 2) does not occur, a segment in which every e is replaced by q - e fails.
+ * coeffs: n x 32-byte coefficients (mod q, as ssa_verify_batch_msm), or NULL for 128-bit coefficients drawn on the
+ * device (ChaCha20 keyed with getrandom(2)).  For given inputs and coefficients the result does not depend on the
+ * number of segments.  n <= the context's small-batch bound (SSA_MSM_SMALL_MAX, 3072 by default): the exact per-lane
+ * path, as ssa_verify_many with SSA_FLAG_SIG_FLAG_BYTE.  Above SSA_MSM_SLICE signatures the batch is screened slice by
+ * slice; segments never straddle two slices.  n == 0 returns SSA_OK.  Return code and *n_fail_out (the number of
+ * nonzero statuses) as ssa_verify_many.  Host buffers go through the library's staging, caller memory is not
+ * registered. */
+int ssa_verify_batch_screened(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_inf,
+                              const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len,
+                              size_t n, const uint8_t *coeffs, uint8_t *status_out, uint64_t *n_fail_out);
+
 /* hash_message for n (R.x, pk, message) triples -> n x 32-byte digests */
 int ssa_hash_message_many(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t *pks,
                           const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride,
@@ -369,6 +398,15 @@ int ssa_verify_batch_msm_device(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8
                                 const uint8_t *d_pk_inf, const uint8_t *d_msgs, const uint64_t *d_msg_off, size_t msg_stride,
                                 size_t msg_len, size_t n, const uint8_t *d_coeffs, uint32_t coeff_bytes,
                                 uint32_t *d_verdict_out);
+/* The device form of ssa_verify_batch_screened.  d_coeffs: n x coeff_bytes (1..32) as ssa_verify_batch_msm_device, or
+ * NULL (library-drawn).  *d_n_fail_out (device, may be NULL) receives the number of nonzero statuses.  Unlike the other
+ * _device forms this one SYNCHRONISES the context's stream once per slice of SSA_MSM_SLICE signatures (once for any
+ * batch of up to 2^23), to read back the segment verdicts (at most 256 bytes) and size the re-check of the failing
+ * segments; the statuses and the count are ordered on the context's stream like any other _device result. */
+int ssa_verify_batch_screened_device(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_pk_inf,
+                                     const uint8_t *d_msgs, const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len,
+                                     size_t n, const uint8_t *d_coeffs, uint32_t coeff_bytes, uint8_t *d_status_out,
+                                     uint64_t *d_n_fail_out);
 int ssa_ctx_sync(ssa_ctx *ctx);
 
 /* ---- keyed context: many signatures by few signers (validator sets) ---------------------------------
@@ -582,6 +620,15 @@ int ssa_debug_corrupt_table_builds(int n);
  * whole-pass descriptors ([q]P of the subgroup check, [h]P). */
 int ssa_debug_tail_plan(unsigned waves, unsigned pieces, unsigned gens, int uniform, unsigned min_main, size_t n,
                         uint32_t flags, uint32_t out[14]);
+/* host logic of the screened form, no context and no device needed: the plan for n signatures with coeff_bytes-wide
+ * coefficients (0: library-drawn, 128-bit) at the default SSA_MSM_SLICE.  out: segments K of the first slice, lanes per
+ * segment (a multiple of 256; only the last segment of a slice is ragged), window bits c, windows, windows that carry
+ * R (the coefficient's), buckets per window (K * 2^(c-1)), slices, segments over all slices.  A context runs the exact
+ * per-lane path instead for batches up to its small-batch bound. */
+int ssa_debug_screen_plan(size_t n, uint32_t coeff_bytes, uint64_t out[8]);
+/* tests: the screened form on this context uses k segments per slice (k in 1..256, fewer where the slice has fewer
+ * 256-lane blocks; 0 = automatic).  The statuses do not depend on k. */
+int ssa_debug_screen_segments(ssa_ctx *ctx, uint32_t k);
 /* n_blocks 64-byte blocks of the ChaCha20 keystream the MSM coefficients come from (RFC 8439 known answers) */
 int ssa_debug_chacha20(ssa_ctx *ctx, const uint8_t key[32], const uint8_t nonce[12], uint32_t counter0,
                        size_t n_blocks, uint8_t *out);

@@ -199,6 +199,10 @@ def _load():
         "ssa_ctx_stream_acquire": (i32, [vp, vp]),
         "ssa_debug_fault_after_chunk": (i32, [vp, i32]),
         "ssa_debug_tail_plan": (i32, [u32, u32, u32, i32, u32, sz, u32, vp]),
+        "ssa_verify_batch_screened": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz, vp, vp, u64p]),
+        "ssa_verify_batch_screened_device": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz, vp, u32, vp, vp]),
+        "ssa_debug_screen_plan": (i32, [sz, u32, vp]),
+        "ssa_debug_screen_segments": (i32, [vp, u32]),
         "ssa_xprv_master_many": (i32, [vp, vp, sz, vp, vp]),
         "ssa_xprv_master_many_device": (i32, [vp, vp, sz, vp, vp]),
         "ssa_xprv_derive_many": (i32, [vp, vp, sz, vp, vp, sz, u32, vp, vp]),
@@ -368,6 +372,42 @@ class Engine:
         _check(_lib.ssa_verify_batch_msm_device(self._ctx, d_sigs, d_pks, d_pk_inf or None, d_msgs, d_offsets or None,
                                                 msg_stride if msg_stride is not None else msg_len, msg_len, n,
                                                 d_coeffs, coeff_bytes, d_verdict), "ssa_verify_batch_msm_device")
+
+    def verify_batch_screened(self, sigs, pks, msgs, offsets=None, coeffs=None, pk_inf=None):
+        """verify_batch semantics per signature at about the price of the MSM verdict -> (status uint8[n], n_fail).
+        Segments of the batch are screened by the MSM; only lanes of failing segments run the per-lane check
+        (include/schnorr_sig_amd.h).  coeffs: n x 32-byte scalars, or None (drawn on the device)."""
+        sigs, pks = _np_u8(sigs, 81), _np_u8(pks, 96)
+        n = sigs.shape[0]
+        if pks.shape[0] != n:
+            raise MalformedInput("We should have the same number of signatures than public keys")
+        if n:
+            m, off, stride, mlen = self._msg_args(msgs, offsets, n)
+        else:
+            m, off, stride, mlen = None, None, 0, 0
+        c = _np_u8(coeffs, 32) if coeffs is not None else None
+        if c is not None:
+            assert c.shape[0] == n
+        inf = _np_u8(pk_inf) if pk_inf is not None else None
+        status = np.full(n, 255, dtype=np.uint8)
+        nfail = C.c_uint64(0)
+        _check(_lib.ssa_verify_batch_screened(self._ctx, _ptr(sigs) if n else None, _ptr(pks) if n else None, _ptr(inf),
+                                              _ptr(m), _ptr(off), stride, mlen, n, _ptr(c),
+                                              _ptr(status) if n else None, C.byref(nfail)),
+               "ssa_verify_batch_screened")
+        return status, int(nfail.value)
+
+    def verify_batch_screened_device(self, d_sigs, d_pks, d_msgs, n, msg_len, d_coeffs, coeff_bytes, d_status, d_nfail,
+                                     msg_stride=None, d_offsets=0, d_pk_inf=0):
+        """device form (synchronises the stream once per slice to read the segment verdicts)"""
+        _check(_lib.ssa_verify_batch_screened_device(
+            self._ctx, d_sigs, d_pks, d_pk_inf or None, d_msgs, d_offsets or None,
+            msg_stride if msg_stride is not None else msg_len, msg_len, n, d_coeffs or None, coeff_bytes, d_status,
+            d_nfail or None), "ssa_verify_batch_screened_device")
+
+    def debug_screen_segments(self, k):
+        """tests: k segments per slice in the screened form on this engine (0 = automatic)"""
+        _check(_lib.ssa_debug_screen_segments(self._ctx, int(k)), "ssa_debug_screen_segments")
 
     # ---- MSM-form verdict across processes: per-shard records + combination (include/schnorr_sig_amd.h) ----
     def verify_batch_msm_partial_device(self, d_sigs, d_pks, d_msgs, n, msg_len, d_coeffs, coeff_bytes, d_partial24,
@@ -1014,6 +1054,15 @@ def debug_tail_plan(waves, n, check_torsion=False, pieces=5, gens=1, uniform=Fal
             "pieces": [dec(out[4 + k]) for k in range(int(out[0]))], "whole": [dec(out[12]), dec(out[13])]}
 
 
+def debug_screen_plan(n, coeff_bytes=0):
+    """host logic of the screened form (no device needed): its plan for n signatures at the default slice size"""
+    out = np.zeros(8, dtype=np.uint64)
+    _check(_lib.ssa_debug_screen_plan(int(n), int(coeff_bytes), out.ctypes.data), "ssa_debug_screen_plan")
+    keys = ("segments", "segment_lanes", "window_bits", "windows", "r_windows", "buckets_per_window", "slices",
+            "total_segments")
+    return {k: int(v) for k, v in zip(keys, out)}
+
+
 def default_engine():
     global _default_engine
     if _default_engine is None:
@@ -1374,6 +1423,30 @@ class ExtendedPublicKey:
 
     def __eq__(self, o):
         return isinstance(o, ExtendedPublicKey) and o.key == self.key and o.chaincode == self.chaincode
+
+
+def verify_batch_statuses(signatures, public_keys, messages, rng=None, engine=None):
+    """verify_batch semantics per signature (screened on the GPU): a uint8 array of statuses, 0 = OK,
+    2 = INVALID_SIGNATURE, 3 = MALFORMED (the reference would panic on this input).  Coefficients from `rng(64)` per
+    signature reduced mod q, or drawn on the device when rng is None.  A rejected lane is reported except with the
+    probability stated in DESIGN.md section 13."""
+    if len(signatures) != len(public_keys):
+        raise MalformedInput("We should have the same number of signatures than public keys")
+    if len(messages) != len(public_keys):
+        raise MalformedInput("We should have the same number of messages than public keys")
+    if not signatures:
+        return np.zeros(0, dtype=np.uint8)
+    eng = engine or default_engine()
+    sigs = np.frombuffer(b"".join(s.bytes for s in signatures), np.uint8)
+    pks = np.frombuffer(b"".join(p.affine for p in public_keys), np.uint8)
+    inf = np.array([1 if p.is_identity else 0 for p in public_keys], np.uint8)
+    flat, off = pack_messages(messages)
+    coeffs = None
+    if rng is not None:
+        coeffs = np.frombuffer(b"".join((int.from_bytes(rng(64), "little") % Q).to_bytes(32, "little")
+                                        for _ in signatures), np.uint8)
+    status, _ = eng.verify_batch_screened(sigs, pks, flat, offsets=off, coeffs=coeffs, pk_inf=inf)
+    return status
 
 
 def verify_batch(signatures, public_keys, messages, rng=None, engine=None, msm=False):

@@ -370,6 +370,7 @@ ssa_ctx *ssa_internal_twin(ssa_ctx *ctx) {
         ctx->twin = t;
     }
     ctx->twin->timing = ctx->timing;
+    ctx->twin->screen_segs = ctx->screen_segs;
     return ctx->twin;
 }
 
@@ -403,7 +404,7 @@ extern "C" void ssa_ctx_destroy(ssa_ctx *ctx) {
                       &ctx->msm_scalars, &ctx->msm_keys, &ctx->msm_vals, &ctx->msm_keys2, &ctx->msm_vals2,
                       &ctx->msm_sort_tmp, &ctx->msm_bounds, &ctx->msm_buckets, &ctx->msm_chunks, &ctx->msm_windows,
                       &ctx->msm_partials, &ctx->msm_flags, &ctx->st_coeffs, &ctx->msm_cnt, &ctx->msm_cnt2,
-                      &ctx->msm_ids, &ctx->msm_ids2, &ctx->msm_comb_pts, &ctx->msm_comb_lins, &ctx->msm_slice_recs, &ctx->msm_sbuf, &ctx->tail_done, &ctx->tail_park, &ctx->ctab, &ctx->sg_sigs, &ctx->sg_pks, &ctx->dv_recs, &ctx->tc_out,
+                      &ctx->msm_ids, &ctx->msm_ids2, &ctx->msm_comb_pts, &ctx->msm_comb_lins, &ctx->msm_slice_recs, &ctx->msm_sbuf, &ctx->scr_ok, &ctx->scr_in, &ctx->scr_status, &ctx->scr_fail, &ctx->tail_done, &ctx->tail_park, &ctx->ctab, &ctx->sg_sigs, &ctx->sg_pks, &ctx->dv_recs, &ctx->tc_out,
                       &ctx->rng_seed, &ctx->rng_scratch})
         b->release();
     for (HostBuf *b : {&ctx->pin_in, &ctx->pin_coeffs, &ctx->pin_out, &ctx->pin_seed}) b->release();
@@ -437,7 +438,7 @@ extern "C" int ssa_ctx_info(const ssa_ctx *ctx, uint64_t out[8]) {
                                 &c->msm_keys, &c->msm_vals, &c->msm_keys2, &c->msm_vals2, &c->msm_sort_tmp, &c->msm_bounds,
                                 &c->msm_buckets, &c->msm_chunks, &c->msm_windows, &c->msm_partials, &c->msm_flags,
                                 &c->st_coeffs, &c->msm_cnt, &c->msm_cnt2, &c->msm_ids, &c->msm_ids2, &c->msm_comb_pts,
-                                &c->msm_comb_lins, &c->msm_slice_recs, &c->msm_sbuf, &c->tail_done, &c->tail_park, &c->ctab, &c->sg_sigs, &c->sg_pks})
+                                &c->msm_comb_lins, &c->msm_slice_recs, &c->msm_sbuf, &c->scr_ok, &c->scr_in, &c->scr_status, &c->scr_fail, &c->tail_done, &c->tail_park, &c->ctab, &c->sg_sigs, &c->sg_pks})
             sum += b->cap;
         return sum;
     };
@@ -746,6 +747,14 @@ static int verify_slices(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_p
         if (rc) return rc;
     }
     return 0;
+}
+
+int ssa_internal_verify_hashed(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_pk_inf,
+                               const uint64_t *d_h, size_t n, uint32_t flags, uint8_t *d_status_out,
+                               unsigned long long *d_fail) {
+    const size_t slice = ctx->lane_slice < n ? ctx->lane_slice : n;
+    if (ctx->ws_tab.reserve(slice * (size_t)(PTAB_ENTRIES * PTAB_ENTRY_U64) * sizeof(u64))) return SSA_ERR_HIP;
+    return verify_slices(ctx, d_sigs, d_pks, d_pk_inf, (const u64 *)d_h, n, flags, d_status_out, d_fail);
 }
 
 // hash + verification of ONE slice (cnt <= c->lane_slice lanes) on c->stream with c's workspaces; *d_fail is added to

@@ -127,6 +127,11 @@ struct ssa_ctx {
     DevBuf msm_sbuf;              // the coefficients s_i between the two halves of the preparation (32 B per signature)
     bool msm_overlap = true;      // the h-independent half of msm_k_prepare runs under ssa_k_hash (SSA_MSM_OVERLAP=0: off)
     unsigned msm_tree_group = 16; // chunk sums added per cooperating wave and tree level (SSA_MSM_TREE_GROUP: 2..64)
+    // screened batch verification (ssa_msm.hip): segments per slice forced by
+    // ssa_debug_screen_segments (0 = automatic), the segment verdicts, the gathered lanes of failing segments (inputs and
+    // challenge scalars), their statuses, and a scratch rejection counter
+    unsigned screen_segs = 0;
+    DevBuf scr_ok, scr_in, scr_status, scr_fail;
     // signing (ssa_sign.hip): the 4-bit comb table of the constant-time signer (98 KB, built at the first use) and the
     // intermediates of the keyed (130-byte) output
     DevBuf ctab, sg_sigs, sg_pks;
@@ -394,6 +399,12 @@ static inline int pipelined_upload_hash(ssa_ctx *ctx, const uint8_t *sigs, const
 // defined in ssa_api.hip: hash_message + Scalar::from_bits_vartime for n signatures into ctx->ws_h
 int ssa_internal_hash_scalars(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_msgs,
                               const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len, size_t n);
+
+// defined in ssa_api.hip: ssa_k_verify over n lanes whose challenge scalars are already in d_h (the per-lane workspace
+// reserved for one slice of lanes); *d_fail is added to
+int ssa_internal_verify_hashed(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_pk_inf,
+                               const uint64_t *d_h, size_t n, uint32_t flags, uint8_t *d_status_out,
+                               unsigned long long *d_fail);
 
 // defined in ssa_sign.hip (ssa_selfcheck.hpp): the exact check of a comb table for G (res[0] failing rows, res[1] the
 // first failing row or ~0) and of the context's constant-time table (out[0] rows checked, out[1], out[2] as res)

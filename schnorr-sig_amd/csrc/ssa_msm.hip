@@ -57,6 +57,7 @@ constexpr u32 MSM_MAX_WINDOWS = 32;
 // (0 .. n-1) while j < wa (a coefficient of `coeff_bytes` bytes reaches only its lowest wa windows)
 struct MsmItems {
     u32 n, wa, windows;
+    u32 seg_blocks, cm1;                // screened form: 256-lane blocks per segment, c - 1
     u32 tile0[MSM_MAX_WINDOWS + 1];     // first tile of window j (tiles never straddle two windows)
     u32 base[MSM_MAX_WINDOWS + 1];      // first position of window j's region in the item arrays
 };
@@ -105,7 +106,7 @@ msm_k_prepare(const u8 *__restrict__ sigs, const u8 *__restrict__ pks, const u8 
               const u64 *__restrict__ h_in,
               const u8 *__restrict__ coeffs, u32 coeff_bytes, size_t n, MsmShape shp, u32 wa, u64 *__restrict__ points,
               short *__restrict__ digits, u64 *__restrict__ partials, u32 *__restrict__ malformed,
-              u64 *__restrict__ s_out) {
+              u64 *__restrict__ s_out, u8 *__restrict__ status) {
     // h_in == nullptr (round 5): everything that does not need the challenge scalars -- the checks, R's square root,
     // the coefficient's digits, s_i e_i -- so that this kernel can run on a second stream UNDER ssa_k_hash (it fills the
     // hash kernel's tail and its own); the coefficient s_i is left in s_out for msm_k_prepare_h, which writes the digits
@@ -134,6 +135,9 @@ msm_k_prepare(const u8 *__restrict__ sigs, const u8 *__restrict__ pks, const u8 
             R.x = f6_zero(); R.y = f6_zero();
             P.x = f6_zero(); P.y = f6_zero();
         }
+        // the screened form's per-lane status: 3 exactly where the per-lane check with the flag byte says 3 (the same
+        // limb, range, curve and decompression checks); 0 stands until the lane's segment fails
+        if (status) status[i] = (u8)(ok ? ST_OK : ST_MALFORMED);
         if (r_inf) {  // identity R: the (0, 0) sentinel jac_madd skips
             R.x = f6_zero();
             R.y = f6_zero();
@@ -240,9 +244,20 @@ SSA_DEV bool tile_of_block(const MsmItems &it, u32 blk, u32 &j, u32 &k0, u32 &cn
     return true;
 }
 
+// Bucket number of a nonzero digit of point `pt`: |d| - 1 in [0, 2^(c-1)); the screened form (SEG) keys the buckets by
+// (window, segment, digit) instead: b = segment << (c - 1) | (|d| - 1), where the segment is that of the point's lane
+// for R_i and -P_i alike.  hi = the bits above the low 7 (the group), lo = the low 7.
+template <bool SEG>
+SSA_DEV u32 bucket_of(const MsmItems &it, u32 pt, int d) {
+    const u32 b = (u32)((d < 0 ? -d : d) - 1);
+    if (!SEG) return b;
+    const u32 lane = pt < it.n ? pt : pt - it.n;
+    return (((lane >> 8) / it.seg_blocks) << it.cm1) | b;
+}
+
 // tile_hist[(j * 256 + bin) * tmax + tile] = items of this tile whose bucket lies in group `bin`
-__global__ void __launch_bounds__(256)
-msm_k_hist(const short *__restrict__ digits, MsmItems it, u32 tmax, u32 *__restrict__ tile_hist) {
+template <bool SEG>
+SSA_DEV void hist_tile(const short *__restrict__ digits, const MsmItems &it, u32 tmax, u32 *__restrict__ tile_hist) {
     __shared__ u32 h[MSM_HI_BINS];
     h[threadIdx.x] = 0u;
     __syncthreads();
@@ -250,11 +265,20 @@ msm_k_hist(const short *__restrict__ digits, MsmItems it, u32 tmax, u32 *__restr
     if (!tile_of_block(it, blockIdx.x, j, k0, cnt)) return;        // (block-uniform)
     const short *dj = digits + (size_t)j * (2u * (size_t)it.n);
     for (u32 k = threadIdx.x; k < cnt; k += 256u) {
-        const int d = dj[item_point(it, j, k0 + k)];
-        if (d != 0) atomicAdd(&h[(u32)((d < 0 ? -d : d) - 1) >> MSM_LO_BITS], 1u);
+        const u32 pt = item_point(it, j, k0 + k);
+        const int d = dj[pt];
+        if (d != 0) atomicAdd(&h[bucket_of<SEG>(it, pt, d) >> MSM_LO_BITS], 1u);
     }
     __syncthreads();
     tile_hist[((size_t)j * MSM_HI_BINS + threadIdx.x) * tmax + (blockIdx.x - it.tile0[j])] = h[threadIdx.x];
+}
+__global__ void __launch_bounds__(256)
+msm_k_hist(const short *__restrict__ digits, MsmItems it, u32 tmax, u32 *__restrict__ tile_hist) {
+    hist_tile<false>(digits, it, tmax, tile_hist);
+}
+__global__ void __launch_bounds__(256)
+msm_k_hist_seg(const short *__restrict__ digits, MsmItems it, u32 tmax, u32 *__restrict__ tile_hist) {
+    hist_tile<true>(digits, it, tmax, tile_hist);
 }
 
 // Exclusive scan of a window's (bin, tile) counts in bin-major order, in place, in two steps:
@@ -318,9 +342,9 @@ msm_k_rowscan(MsmItems it, u32 tmax, const u32 *__restrict__ rowsum, u32 *__rest
 
 // items -> their group, ONE word per item: v1[pos] = point index (24 bits: 2n <= 2^24 per slice) | low 7 bits of the
 // bucket number << 24 | sign << 31
-__global__ void __launch_bounds__(256)
-msm_k_scatter(const short *__restrict__ digits, MsmItems it, u32 tmax, const u32 *__restrict__ tile_hist,
-              u32 *__restrict__ v1) {
+template <bool SEG>
+SSA_DEV void scatter_tile(const short *__restrict__ digits, const MsmItems &it, u32 tmax, const u32 *__restrict__ tile_hist,
+                          u32 *__restrict__ v1) {
     __shared__ u32 cur[MSM_HI_BINS];
     u32 j, k0, cnt;
     if (!tile_of_block(it, blockIdx.x, j, k0, cnt)) return;
@@ -331,11 +355,21 @@ msm_k_scatter(const short *__restrict__ digits, MsmItems it, u32 tmax, const u32
         const u32 pt = item_point(it, j, k0 + k);
         const int d = dj[pt];
         if (d != 0) {
-            const u32 b = (u32)((d < 0 ? -d : d) - 1);
+            const u32 b = bucket_of<SEG>(it, pt, d);
             const u32 pos = atomicAdd(&cur[b >> MSM_LO_BITS], 1u);
             v1[pos] = pt | ((b & (MSM_LO_BINS - 1u)) << 24) | (d < 0 ? 0x80000000u : 0u);
         }
     }
+}
+__global__ void __launch_bounds__(256)
+msm_k_scatter(const short *__restrict__ digits, MsmItems it, u32 tmax, const u32 *__restrict__ tile_hist,
+              u32 *__restrict__ v1) {
+    scatter_tile<false>(digits, it, tmax, tile_hist, v1);
+}
+__global__ void __launch_bounds__(256)
+msm_k_scatter_seg(const short *__restrict__ digits, MsmItems it, u32 tmax, const u32 *__restrict__ tile_hist,
+                  u32 *__restrict__ v1) {
+    scatter_tile<true>(digits, it, tmax, tile_hist, v1);
 }
 
 // one block per (window, group): counting sort of the group's items by the low 7 bits of their bucket number; the
@@ -446,8 +480,10 @@ msm_k_buckets(const u64 *__restrict__ points, const u32 *__restrict__ vals, cons
 //   sum_k (k + 1) B_k = sum_k (k - k0 + 1) B_k + k0 sum_k B_k
 // (2^16 lanes are one wave per SIMD anyway: with one wave per SIMD allowed the general addition keeps its values in
 //  registers -- 256 VGPRs + 384 B of scratch before)
-__global__ void __launch_bounds__(256, 1)
-msm_k_chunks(const u64 *__restrict__ bsum, MsmShape sh, u64 *__restrict__ chunk_out) {
+// (SEG: a window holds one run of 2^(c-1) buckets per segment, and a chunk's weights count from its segment's first
+//  bucket: k0 mod 2^(c-1))
+template <bool SEG>
+SSA_DEV void chunk_sum(const u64 *__restrict__ bsum, const MsmShape &sh, u64 *__restrict__ chunk_out) {
     const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= (size_t)sh.windows * sh.chunks) return;
     const u32 j = (u32)(t / sh.chunks), ch = (u32)(t % sh.chunks);
@@ -463,8 +499,8 @@ msm_k_chunks(const u64 *__restrict__ bsum, MsmShape sh, u64 *__restrict__ chunk_
     }
     // + [k0] running: double-and-add from the top set bit of the weight, the doublings through the ladder's
     // generated statement
-    if (k0 > 0) {
-        const u32 m = k0;
+    const u32 m = SEG ? k0 & ((1u << (sh.c - 1)) - 1u) : k0;
+    if (m > 0) {
         jac acc = running;
 #pragma unroll 1
         for (int bit = 30 - __builtin_clz(m); bit >= 0; bit--) {
@@ -474,6 +510,14 @@ msm_k_chunks(const u64 *__restrict__ bsum, MsmShape sh, u64 *__restrict__ chunk_
         total = jac_add(total, acc);
     }
     st_jac(chunk_out + 18 * t, total);
+}
+__global__ void __launch_bounds__(256, 1)
+msm_k_chunks(const u64 *__restrict__ bsum, MsmShape sh, u64 *__restrict__ chunk_out) {
+    chunk_sum<false>(bsum, sh, chunk_out);
+}
+__global__ void __launch_bounds__(256, 1)
+msm_k_chunks_seg(const u64 *__restrict__ bsum, MsmShape sh, u64 *__restrict__ chunk_out) {
+    chunk_sum<true>(bsum, sh, chunk_out);
 }
 
 // tree step: out[j][g] = sum of `group` consecutive points of window j's `count` inputs.  ONE WAVE per output, the
@@ -694,6 +738,172 @@ msm_k_finish(const u64 *__restrict__ win_in, MsmShape sh, const u64 *__restrict_
         }
         if (lane == 0) *verdict = eq ? ST_OK : ST_INVALID_SIG;
     }
+}
+
+// ---- the screened form: one verdict per segment ---------------------------
+// Block s per segment s (the same split as msm_k_finish): wave 0 runs Horner over the segment's window sums
+// win_in[j * segs + s], wave 1 adds up the segment's block partials of s_i e_i (segments are whole 256-lane blocks,
+// the last one ragged) and computes [lin_s] G from the comb table.  Then the EXACT point comparison
+//     sum s_i R_i - sum s_i h_i P_i  ==  [sum s_i e_i] G       (identity = Z 0 on both sides)
+// -- not x-only: a segment whose equation holds only up to the sign of both sides fails.  Malformed lanes entered
+// the sums as the identity with s_i e_i = 0 (msm_k_prepare); the global flag is not read.
+__global__ void __launch_bounds__(128)
+msm_k_finish_seg(const u64 *__restrict__ win_in, MsmShape sh, u32 segs, u32 seg_blocks, const u64 *__restrict__ partials,
+                 u32 n_partials, const u64 *__restrict__ gtab, u8 *__restrict__ seg_ok) {
+    __shared__ CoopLds L;
+    __shared__ u64 lin_sh[64][4];
+    const u32 lane = threadIdx.x & 63u, s = blockIdx.x;
+    const int ws = (int)(threadIdx.x >> 6);
+    // slots as msm_k_finish: wave 0 accumulator 0..3, addend 4..6, scratch 7..15; wave 1 accumulator 20..23,
+    // addend 24..25, scratch 26..34
+    int t[9];
+#pragma unroll
+    for (int k = 0; k < 9; k++) t[k] = (ws ? 26 : 7) + k;
+    if (ws == 0) {
+        auto load = [&](int s0, u32 j) {   // X, Y, Z of window j of this segment with their 7x halves
+            if (lane < 36) {
+                const u32 v = lane / 12u, c = lane % 12u;
+                const u64 w = win_in[18 * ((size_t)j * segs + s) + 6u * v + c % 6u];
+                L.slot[s0 + (int)v][c] = c < 6 ? w : fp_mul_small(w, 7u);
+            }
+            coop_sync();
+        };
+        load(0, sh.windows - 1);
+        coop_mul(L, 3, 2, 2, lane, ws);    // W = Z^4 of the accumulator
+        coop_mul(L, 3, 3, 3, lane, ws);
+#pragma unroll 1
+        for (int j = (int)sh.windows - 2; j >= 0; j--) {
+#pragma unroll 1
+            for (u32 d = 0; d < sh.c; d++) coop_jac_dbl(L, 0, t, lane, ws);
+            load(4, (u32)j);
+            coop_jac_add(L, 0, 4, t, lane, ws);
+        }
+    } else {
+        const u32 b_lo = s * seg_blocks, b_hi = b_lo + seg_blocks < n_partials ? b_lo + seg_blocks : n_partials;
+        sc256 acc;
+#pragma unroll
+        for (int k = 0; k < 4; k++) acc.w[k] = 0;
+#pragma unroll 1
+        for (u32 b = b_lo + lane; b < b_hi; b += 64) {
+            sc256 p;
+#pragma unroll
+            for (int k = 0; k < 4; k++) p.w[k] = partials[4 * (size_t)b + k];
+            acc = sc_add_mod(acc, p);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++) lin_sh[lane][k] = acc.w[k];
+        coop_sync();
+#pragma unroll 1
+        for (u32 stride = 32; stride >= 1; stride >>= 1) {
+            if (lane < stride) {
+                sc256 a, b;
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    a.w[k] = lin_sh[lane][k];
+                    b.w[k] = lin_sh[lane + stride][k];
+                }
+                a = sc_add_mod(a, b);
+#pragma unroll
+                for (int k = 0; k < 4; k++) lin_sh[lane][k] = a.w[k];
+            }
+            coop_sync();
+        }
+        sc256 lin;
+#pragma unroll
+        for (int k = 0; k < 4; k++) lin.w[k] = lin_sh[0][k];
+        coop_set(L, 20, 1ull, lane, ws);
+        coop_set(L, 21, 1ull, lane, ws);
+        coop_set(L, 22, 0ull, lane, ws);
+        coop_set(L, 23, 0ull, lane, ws);
+        const GtabGeom gg = gtab_geom(gtab);
+#pragma unroll 1
+        for (u32 w = 0; w < gg.count; w++) {
+            const u32 d = sc_bits(lin, w * gg.bits, gg.bits);
+            if (d != 0) {
+                const u64 *rowp = gtab + (((size_t)w << gg.bits) + d) * 12;
+                if (lane < 24) {
+                    const u32 half = lane / 12u, c = lane % 12u;
+                    const u64 v = rowp[6u * half + c % 6u];
+                    L.slot[half ? 25 : 24][c] = c < 6 ? v : fp_mul_small(v, 7u);
+                }
+                coop_sync();
+                coop_jac_madd(L, 20, 24, 25, t, lane, ws);
+            }
+        }
+    }
+    __syncthreads();
+    if (ws == 0) {
+        // X_l Z_r^2 == X_r Z_l^2 and Y_l Z_r^3 == Y_r Z_l^3 (X and Y only as first operands: their 7x halves may be stale)
+        const bool li = coop_is_zero(L, 2, lane, ws), ri = coop_is_zero(L, 22, lane, ws);
+        bool eq;
+        if (li || ri) {
+            eq = li && ri;
+        } else {
+            coop_mul(L, 7, 22, 22, lane, ws);      // Z_r^2
+            coop_mul(L, 8, 0, 7, lane, ws);        // X_l Z_r^2
+            coop_mul(L, 9, 2, 2, lane, ws);        // Z_l^2
+            coop_mul(L, 10, 20, 9, lane, ws);      // X_r Z_l^2
+            eq = coop_eq(L, 8, 10, lane, ws);
+            coop_mul(L, 7, 7, 22, lane, ws);       // Z_r^3
+            coop_mul(L, 8, 1, 7, lane, ws);        // Y_l Z_r^3
+            coop_mul(L, 9, 9, 2, lane, ws);        // Z_l^3
+            coop_mul(L, 10, 21, 9, lane, ws);      // Y_r Z_l^3
+            eq = eq && coop_eq(L, 8, 10, lane, ws);
+        }
+        if (lane == 0) seg_ok[s] = eq ? 1u : 0u;
+    }
+}
+
+// the failing segments of a slice (ascending; only the last segment of a slice can be ragged, so failing segment f
+// lands at compact lane f * seg_lanes)
+struct ScreenList {
+    u32 count, seg_lanes, n;
+    uint16_t id[256];
+};
+
+SSA_DEV void copy_run(u8 *__restrict__ dst, const u8 *__restrict__ src, size_t bytes, size_t tid, size_t nth) {
+    if (((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src)) & 15u) == 0) {
+        const size_t v = bytes / 16;
+        for (size_t k = tid; k < v; k += nth) reinterpret_cast<uint4 *>(dst)[k] = reinterpret_cast<const uint4 *>(src)[k];
+        for (size_t k = v * 16 + tid; k < bytes; k += nth) dst[k] = src[k];
+    } else {
+        for (size_t k = tid; k < bytes; k += nth) dst[k] = src[k];
+    }
+}
+
+// the lanes of the failing segments -> compact buffers (signature 81 B, key 96 B, pk_inf 1 B, challenge scalar 32 B):
+// blockIdx.y = failing segment, the x blocks share its bytes
+__global__ void __launch_bounds__(256)
+msm_k_screen_gather(ScreenList sl, const u8 *__restrict__ sigs, const u8 *__restrict__ pks, const u8 *__restrict__ pk_inf,
+                    const u64 *__restrict__ h, u8 *__restrict__ g_sigs, u8 *__restrict__ g_pks, u8 *__restrict__ g_inf,
+                    u64 *__restrict__ g_h) {
+    const u32 f = blockIdx.y;
+    if (f >= sl.count) return;
+    const size_t lo = (size_t)sl.id[f] * sl.seg_lanes, dlo = (size_t)f * sl.seg_lanes;
+    if (lo >= sl.n) return;
+    const size_t cnt = sl.n - lo < sl.seg_lanes ? sl.n - lo : sl.seg_lanes;
+    const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (size_t)gridDim.x * blockDim.x;
+    copy_run(g_sigs + 81 * dlo, sigs + 81 * lo, 81 * cnt, tid, nth);
+    copy_run(g_pks + 96 * dlo, pks + 96 * lo, 96 * cnt, tid, nth);
+    copy_run(reinterpret_cast<u8 *>(g_h + 4 * dlo), reinterpret_cast<const u8 *>(h + 4 * lo), 32 * cnt, tid, nth);
+    if (pk_inf) copy_run(g_inf + dlo, pk_inf + lo, cnt, tid, nth);
+}
+
+// compact statuses -> their lanes
+__global__ void __launch_bounds__(256)
+msm_k_screen_scatter(ScreenList sl, size_t m, const u8 *__restrict__ g_status, u8 *__restrict__ status) {
+    const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= m) return;
+    const u32 f = (u32)(c / sl.seg_lanes);
+    status[(size_t)sl.id[f] * sl.seg_lanes + c % sl.seg_lanes] = g_status[c];
+}
+
+// *n_fail += number of nonzero statuses (one ballot and one atomic per wave)
+__global__ void __launch_bounds__(256)
+msm_k_screen_count(const u8 *__restrict__ status, size_t n, unsigned long long *__restrict__ n_fail) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const unsigned long long bad = __ballot(i < n && status[i] != 0);
+    if ((threadIdx.x & 63u) == 0 && bad) atomicAdd(n_fail, (unsigned long long)__popcll(bad));
 }
 
 // ---- small batches: Straus on cooperating waves ---------------------------------------------------
@@ -964,10 +1174,15 @@ static int msm_run(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks, co
                    const uint8_t *d_msgs, const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len, size_t n,
                    const uint8_t *d_coeffs, uint32_t coeff_bytes, uint32_t *d_verdict_out, u64 *d_partial_out,
                    bool hashed = false);
+// the screened form: segments of the slice, per-lane status out, one verdict byte per segment
+struct ScreenArgs {
+    u32 segs, seg_blocks;
+    u8 *status, *seg_ok;
+};
 static int msm_run_one(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_pk_inf,
                        const uint8_t *d_msgs, const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len, size_t n,
                        const uint8_t *d_coeffs, uint32_t coeff_bytes, uint32_t *d_verdict_out, u64 *d_partial_out,
-                       const u64 *d_h);
+                       const u64 *d_h, const ScreenArgs *scr = nullptr);
 static int msm_run_small(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_pk_inf,
                          const uint8_t *d_msgs, const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len, size_t n,
                          const uint8_t *d_coeffs, uint32_t coeff_bytes, uint32_t *d_verdict_out, u64 *d_partial_out);
@@ -1052,10 +1267,13 @@ static int msm_run(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks, co
 
 // the kernels of one MSM-form slice on ctx->stream: a verdict (d_partial_out == nullptr) or the slice's / shard's record
 // d_h: the challenge scalars if they exist already, else nullptr (they are computed into ctx->ws_h)
+static MsmShape screen_shape(u32 segs);
+// scr != nullptr: the screened form -- (window, segment, digit) buckets, a per-lane status, one verdict per segment in
+// scr->seg_ok (no verdict, no record)
 static int msm_run_one(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_pk_inf,
                        const uint8_t *d_msgs, const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len, size_t n,
                        const uint8_t *d_coeffs, uint32_t coeff_bytes, uint32_t *d_verdict_out, u64 *d_partial_out,
-                       const u64 *d_h) {
+                       const u64 *d_h, const ScreenArgs *scr) {
     if (n > (1ull << 23)) return SSA_ERR_ARG;   // an item carries its point index in 24 bits: 2n <= 2^24 (msm_run slices)
     if (n == 0) {   // empty batch: Ok (src/batch.rs); an empty shard adds the identity and 0
         if (d_partial_out) {
@@ -1072,9 +1290,10 @@ static int msm_run_one(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks
         d_coeffs = (const uint8_t *)p;
         coeff_bytes = 16;
     }
-    if (n <= ctx->msm_small_max) return msm_run_small(ctx, d_sigs, d_pks, d_pk_inf, d_msgs, d_msg_off, msg_stride, msg_len, n,
-                                                      d_coeffs, coeff_bytes, d_verdict_out, d_partial_out);
-    const MsmShape sh = msm_shape(n);
+    if (!scr && n <= ctx->msm_small_max)
+        return msm_run_small(ctx, d_sigs, d_pks, d_pk_inf, d_msgs, d_msg_off, msg_stride, msg_len, n, d_coeffs, coeff_bytes,
+                             d_verdict_out, d_partial_out);
+    const MsmShape sh = scr ? screen_shape(scr->segs) : msm_shape(n);
     // windows the coefficients themselves can reach (32-byte ones are reduced mod q: all of them).  A narrower coefficient
     // whose width is a whole number of windows is read as a TWO'S-COMPLEMENT integer (msm_k_prepare): its signed digits
     // then need no carry window -- which would hold the digit 1 for half of the points, one enormous bucket -- and a
@@ -1084,6 +1303,8 @@ static int msm_run_one(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks
     it.n = (u32)n;
     it.wa = wa;
     it.windows = sh.windows;
+    it.seg_blocks = scr ? scr->seg_blocks : 0u;
+    it.cm1 = sh.c - 1;
     it.tile0[0] = it.base[0] = 0;
     for (u32 j = 0; j < sh.windows; j++) {
         const size_t items = j < wa ? 2 * n : n;
@@ -1122,7 +1343,7 @@ static int msm_run_one(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks
         hipLaunchKernelGGL(msm_k_prepare, dim3(n_blocks), dim3(256), 0, side, d_sigs, d_pks, d_pk_inf,
                            (const u64 *)nullptr, d_coeffs, coeff_bytes, n, sh, wa, (u64 *)ctx->msm_points.p,
                            (short *)ctx->msm_scalars.p, (u64 *)ctx->msm_partials.p, (u32 *)ctx->msm_flags.p,
-                           (u64 *)ctx->msm_sbuf.p);
+                           (u64 *)ctx->msm_sbuf.p, scr ? scr->status : (u8 *)nullptr);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(ctx->hash_done[0], side));
         if (int hrc = ssa_internal_hash_scalars(ctx, d_sigs, d_pks, d_msgs, d_msg_off, msg_stride, msg_len, n)) {
@@ -1146,19 +1367,19 @@ static int msm_run_one(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks
             hipLaunchKernelGGL(msm_k_prepare, dim3(n_blocks), dim3(256), 0, ctx->stream, d_sigs, d_pks, d_pk_inf,
                                d_h, d_coeffs, coeff_bytes, n, sh, wa, (u64 *)ctx->msm_points.p,
                                (short *)ctx->msm_scalars.p, (u64 *)ctx->msm_partials.p, (u32 *)ctx->msm_flags.p,
-                               (u64 *)nullptr);
+                               (u64 *)nullptr, scr ? scr->status : (u8 *)nullptr);
         });
         if (rc) return rc;
     }
     rc = timed_launch(ctx, "msm_sort", [&] {
-        hipLaunchKernelGGL(msm_k_hist, dim3(n_tiles), dim3(256), 0, ctx->stream, (const short *)ctx->msm_scalars.p, it, tmax,
-                           (u32 *)ctx->msm_keys.p);
+        hipLaunchKernelGGL(scr ? msm_k_hist_seg : msm_k_hist, dim3(n_tiles), dim3(256), 0, ctx->stream,
+                           (const short *)ctx->msm_scalars.p, it, tmax, (u32 *)ctx->msm_keys.p);
         hipLaunchKernelGGL(msm_k_rowsum, dim3(sh.windows * MSM_HI_BINS), dim3(64), 0, ctx->stream, it, tmax,
                            (const u32 *)ctx->msm_keys.p, (u32 *)ctx->msm_keys2.p);
         hipLaunchKernelGGL(msm_k_rowscan, dim3(sh.windows * MSM_HI_BINS), dim3(256), 0, ctx->stream, it, tmax,
                            (const u32 *)ctx->msm_keys2.p, (u32 *)ctx->msm_keys.p, (u32 *)ctx->msm_cnt2.p);
-        hipLaunchKernelGGL(msm_k_scatter, dim3(n_tiles), dim3(256), 0, ctx->stream, (const short *)ctx->msm_scalars.p, it,
-                           tmax, (const u32 *)ctx->msm_keys.p, (u32 *)ctx->msm_vals.p);
+        hipLaunchKernelGGL(scr ? msm_k_scatter_seg : msm_k_scatter, dim3(n_tiles), dim3(256), 0, ctx->stream,
+                           (const short *)ctx->msm_scalars.p, it, tmax, (const u32 *)ctx->msm_keys.p, (u32 *)ctx->msm_vals.p);
         hipLaunchKernelGGL(msm_k_group, dim3(sh.windows * MSM_HI_BINS), dim3(256), 0, ctx->stream,
                            (const u32 *)ctx->msm_cnt2.p, (const u32 *)ctx->msm_vals.p, sh, (u32 *)ctx->msm_vals2.p,
                            (u32 *)ctx->msm_bounds.p, (u32 *)ctx->msm_cnt.p);
@@ -1178,25 +1399,34 @@ static int msm_run_one(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks
                            (u64 *)ctx->msm_buckets.p);
     });
     if (rc) return rc;
-    return timed_launch(ctx, "msm_reduce", [&] {
-        // per window: running sums on chunks of MSM_CHUNK buckets, a tree over the chunk sums, then one
-        // cooperative block: Horner over the windows || [lin]G, and the comparison
-        hipLaunchKernelGGL(msm_k_chunks, dim3(grid_for((size_t)sh.windows * sh.chunks, 256)), dim3(256), 0,
-                           ctx->stream, (const u64 *)ctx->msm_buckets.p, sh, (u64 *)ctx->msm_chunks.p);
-        u64 *ping = (u64 *)ctx->msm_chunks.p, *pong = (u64 *)ctx->msm_windows.p;
-        u32 count = sh.chunks;
+    // per window (and segment): running sums on chunks of MSM_CHUNK buckets, a tree over the chunk sums, then one
+    // cooperative block (per segment): Horner over the windows || [lin]G, and the comparison
+    // (screened: a window's chunks are `segs` runs of 2^(c-1) / MSM_CHUNK, the tree reduces each run on its own)
+    const u32 runs = scr ? scr->segs : 1u;
+    u64 *ping = (u64 *)ctx->msm_chunks.p, *pong = (u64 *)ctx->msm_windows.p;
+    rc = timed_launch(ctx, "msm_reduce", [&] {
+        hipLaunchKernelGGL(scr ? msm_k_chunks_seg : msm_k_chunks, dim3(grid_for((size_t)sh.windows * sh.chunks, 256)),
+                           dim3(256), 0, ctx->stream, (const u64 *)ctx->msm_buckets.p, sh, (u64 *)ctx->msm_chunks.p);
+        u32 count = sh.chunks / runs;
         while (count > 1) {
             const u32 groups = (count + ctx->msm_tree_group - 1) / ctx->msm_tree_group;
-            hipLaunchKernelGGL(msm_k_tree, dim3(sh.windows * groups), dim3(64), 0, ctx->stream,
-                               (const u64 *)ping, sh.windows, count, ctx->msm_tree_group, pong);
+            hipLaunchKernelGGL(msm_k_tree, dim3(sh.windows * runs * groups), dim3(64), 0, ctx->stream,
+                               (const u64 *)ping, sh.windows * runs, count, ctx->msm_tree_group, pong);
             u64 *tmp = ping;
             ping = pong;
             pong = tmp;
             count = groups;
         }
-        hipLaunchKernelGGL(msm_k_finish, dim3(1), dim3(128), 0, ctx->stream, (const u64 *)ping, sh,
-                           (const u64 *)ctx->msm_partials.p, n_blocks, (const u64 *)ctx->d_gtab,
-                           (const u32 *)ctx->msm_flags.p, d_verdict_out, d_partial_out);
+        if (!scr)
+            hipLaunchKernelGGL(msm_k_finish, dim3(1), dim3(128), 0, ctx->stream, (const u64 *)ping, sh,
+                               (const u64 *)ctx->msm_partials.p, n_blocks, (const u64 *)ctx->d_gtab,
+                               (const u32 *)ctx->msm_flags.p, d_verdict_out, d_partial_out);
+    });
+    if (rc || !scr) return rc;
+    return timed_launch(ctx, "msm_k_finish_seg", [&] {
+        hipLaunchKernelGGL(msm_k_finish_seg, dim3(scr->segs), dim3(128), 0, ctx->stream, (const u64 *)ping, sh, scr->segs,
+                           scr->seg_blocks, (const u64 *)ctx->msm_partials.p, n_blocks, (const u64 *)ctx->d_gtab,
+                           scr->seg_ok);
     });
 }
 
@@ -1460,4 +1690,244 @@ static int msm_host_one(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t *pks, c
                          d_rec, false))
         return rc;
     return fetch();
+}
+
+// ------------------------------------------------------------------------------------------------
+// Screened batch verification: the MSM above with its buckets keyed by (window, segment, digit)
+// gives one sum per contiguous segment of the slice in one pass; a segment whose equation holds exactly is accepted as a
+// whole, and only the lanes of failing segments run the exact per-lane kernel, on the challenge scalars the MSM hashed.
+constexpr u32 SCREEN_C = 8;                 // window bits: K * 2^(c-1) <= 256 * 128 stays within the grouping grid
+constexpr u32 SCREEN_MAX_SEGS = 256;
+constexpr u32 SCREEN_MIN_SEG_LANES = 1024;  // automatic K: the largest power of two <= 256 whose segments hold this many
+
+struct ScreenPlan {
+    u32 segs, seg_lanes;
+};
+// segments of a slice of n lanes: k requested (0 = automatic), segment size rounded up to whole 256-lane blocks, so the
+// per-block partial sums of s_i e_i add up per segment; only the last segment can be ragged
+static ScreenPlan screen_plan(size_t n, unsigned forced) {
+    size_t k = forced;
+    if (k == 0) {
+        k = SCREEN_MAX_SEGS;
+        while (k > 1 && n / k < SCREEN_MIN_SEG_LANES) k >>= 1;
+    }
+    size_t per = (n + k - 1) / k;
+    per = (per + 255) & ~(size_t)255;
+    return {(u32)((n + per - 1) / per), (u32)per};
+}
+
+static MsmShape screen_shape(u32 segs) {
+    MsmShape sh;
+    sh.c = SCREEN_C;
+    sh.windows = (255 + sh.c - 1) / sh.c;
+    sh.buckets = segs << (sh.c - 1);
+    sh.chunks = sh.buckets / (u32)MSM_CHUNK;
+    return sh;
+}
+
+extern "C" int ssa_debug_screen_plan(size_t n, uint32_t coeff_bytes, uint64_t out[8]) {
+    if (!out || n == 0 || n > SSA_MAX_BATCH || coeff_bytes > 32) return SSA_ERR_ARG;
+    const size_t slice = (size_t)1 << 23;           // the default SSA_MSM_SLICE
+    const size_t first = n < slice ? n : slice, slices = (n + slice - 1) / slice, last = n - (slices - 1) * slice;
+    const ScreenPlan pl = screen_plan(first, 0);
+    const MsmShape sh = screen_shape(pl.segs);
+    const u32 cb = coeff_bytes ? coeff_bytes : 16u;   // 0: the library draws 128-bit coefficients
+    out[0] = pl.segs;
+    out[1] = pl.seg_lanes;
+    out[2] = sh.c;
+    out[3] = sh.windows;
+    out[4] = cb >= 32 ? sh.windows : (8u * cb + sh.c - 1) / sh.c;
+    out[5] = sh.buckets;
+    out[6] = slices;
+    out[7] = (uint64_t)(slices - 1) * pl.segs + screen_plan(last, 0).segs;
+    return 0;
+}
+
+extern "C" int ssa_debug_screen_segments(ssa_ctx *ctx, uint32_t k) {
+    if (!ctx || k > SCREEN_MAX_SEGS) return SSA_ERR_ARG;
+    ctx->screen_segs = k;
+    return 0;
+}
+
+// ONE slice (n <= ctx->msm_slice) on ctx->stream into d_status[0, n): d_h = the slice's challenge scalars if they exist
+// (else they are computed into ctx->ws_h).  Synchronises the stream once, to read the segment verdicts.
+static int screen_slice(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_pk_inf,
+                        const uint8_t *d_msgs, const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len, size_t n,
+                        const uint8_t *d_coeffs, uint32_t coeff_bytes, const u64 *d_h, uint8_t *d_status) {
+    if (ctx->scr_fail.reserve(16)) return SSA_ERR_HIP;
+    unsigned long long *scratch_fail = (unsigned long long *)ctx->scr_fail.p;    // (the caller counts the statuses)
+    if (n <= ctx->msm_small_max) {      // the exact per-lane path
+        if (d_h) return ssa_internal_verify_hashed(ctx, d_sigs, d_pks, d_pk_inf, d_h, n, SSA_FLAG_SIG_FLAG_BYTE, d_status,
+                                                   scratch_fail);
+        return ssa_verify_many_device(ctx, d_sigs, d_pks, d_pk_inf, d_msgs, d_msg_off, msg_stride, msg_len, n,
+                                      SSA_FLAG_SIG_FLAG_BYTE, d_status, (uint64_t *)scratch_fail);
+    }
+    const ScreenPlan pl = screen_plan(n, ctx->screen_segs);
+    if (ctx->scr_ok.reserve(SCREEN_MAX_SEGS)) return SSA_ERR_HIP;
+    const ScreenArgs sa{pl.segs, pl.seg_lanes / 256u, d_status, (u8 *)ctx->scr_ok.p};
+    if (int rc = msm_run_one(ctx, d_sigs, d_pks, d_pk_inf, d_msgs, d_msg_off, msg_stride, msg_len, n, d_coeffs, coeff_bytes,
+                             nullptr, nullptr, d_h, &sa))
+        return rc;
+    const u64 *h = d_h ? d_h : (const u64 *)ctx->ws_h.p;     // (msm_run_one hashed into ws_h)
+    uint8_t ok[SCREEN_MAX_SEGS];
+    HIP_TRY(hipMemcpyAsync(ok, ctx->scr_ok.p, pl.segs, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    ScreenList sl{};
+    sl.seg_lanes = pl.seg_lanes;
+    sl.n = (u32)n;
+    size_t m = 0;
+    for (u32 s = 0; s < pl.segs; s++) {
+        if (ok[s]) continue;
+        sl.id[sl.count++] = (uint16_t)s;
+        const size_t lo = (size_t)s * pl.seg_lanes;
+        m += n - lo < pl.seg_lanes ? n - lo : pl.seg_lanes;
+    }
+    if (m == 0) return 0;
+    // Most of the slice fails (e.g. one bad lane in every segment): no gather, the per-lane kernel over all of it.
+    if (2 * m > n)
+        return ssa_internal_verify_hashed(ctx, d_sigs, d_pks, d_pk_inf, h, n, SSA_FLAG_SIG_FLAG_BYTE, d_status, scratch_fail);
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t o_pks = al(m * 81), o_h = o_pks + al(m * 96), o_inf = o_h + al(m * 32), total = o_inf + al(m);
+    if (ctx->scr_in.reserve(total) || ctx->scr_status.reserve(m + 16)) return SSA_ERR_HIP;
+    u8 *g = (u8 *)ctx->scr_in.p;
+    int rc = timed_launch(ctx, "screen_gather", [&] {
+        const unsigned gx = grid_for((size_t)pl.seg_lanes * 210u / 16u, 256u * 4u);   // ~4 vectors per thread
+        hipLaunchKernelGGL(msm_k_screen_gather, dim3(gx, sl.count), dim3(256), 0, ctx->stream, sl, d_sigs, d_pks, d_pk_inf,
+                           h, g, g + o_pks, g + o_inf, (u64 *)(g + o_h));
+    });
+    if (rc) return rc;
+    if ((rc = ssa_internal_verify_hashed(ctx, g, g + o_pks, d_pk_inf ? g + o_inf : nullptr, (const u64 *)(g + o_h), m,
+                                         SSA_FLAG_SIG_FLAG_BYTE, (u8 *)ctx->scr_status.p, scratch_fail)))
+        return rc;
+    return timed_launch(ctx, "screen_scatter", [&] {
+        hipLaunchKernelGGL(msm_k_screen_scatter, dim3(grid_for(m, 256)), dim3(256), 0, ctx->stream, sl, m,
+                           (const u8 *)ctx->scr_status.p, d_status);
+    });
+}
+
+static int screen_count(ssa_ctx *ctx, const uint8_t *d_status, size_t n, unsigned long long *d_fail) {
+    HIP_TRY(hipMemsetAsync(d_fail, 0, sizeof(unsigned long long), ctx->stream));
+    hipLaunchKernelGGL(msm_k_screen_count, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, d_status, n, d_fail);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int ssa_verify_batch_screened_device(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks,
+                                                const uint8_t *d_pk_inf, const uint8_t *d_msgs, const uint64_t *d_msg_off,
+                                                size_t msg_stride, size_t msg_len, size_t n, const uint8_t *d_coeffs,
+                                                uint32_t coeff_bytes, uint8_t *d_status_out, uint64_t *d_n_fail_out) {
+    if (!ctx || (n && (!d_sigs || !d_pks || !d_status_out))) return SSA_ERR_ARG;
+    if (d_coeffs && (coeff_bytes == 0 || coeff_bytes > 32)) return SSA_ERR_ARG;
+    if (int rc = check_msgs(d_msgs, d_msg_off, msg_stride, msg_len, n)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    unsigned long long *d_fail = d_n_fail_out ? (unsigned long long *)d_n_fail_out : (unsigned long long *)ctx->ws_fail.p;
+    HIP_TRY(hipMemsetAsync(d_fail, 0, sizeof(unsigned long long), ctx->stream));
+    if (n == 0) return 0;
+    if (n <= ctx->msm_small_max)
+        return ssa_verify_many_device(ctx, d_sigs, d_pks, d_pk_inf, d_msgs, d_msg_off, msg_stride, msg_len, n,
+                                      SSA_FLAG_SIG_FLAG_BYTE, d_status_out, (uint64_t *)d_fail);
+    const size_t slice = ctx->msm_slice;
+    for (size_t lo = 0; lo < n; lo += slice) {      // segments never straddle two slices
+        const size_t cnt = n - lo < slice ? n - lo : slice;
+        if (int rc = screen_slice(ctx, d_sigs + 81 * lo, d_pks + 96 * lo, d_pk_inf ? d_pk_inf + lo : nullptr,
+                                  d_msg_off ? d_msgs : (d_msgs ? d_msgs + lo * msg_stride : nullptr),
+                                  d_msg_off ? d_msg_off + lo : nullptr, msg_stride, msg_len, cnt,
+                                  d_coeffs ? d_coeffs + (size_t)coeff_bytes * lo : nullptr, coeff_bytes, nullptr,
+                                  d_status_out + lo))
+            return rc;
+    }
+    return screen_count(ctx, d_status_out, n, d_fail);
+}
+
+// ONE slice from host buffers (the staging of msm_host_one): statuses into status_out[0, n), *nf the count
+static int screen_host_one(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_inf, const uint8_t *msgs,
+                           const uint64_t *msg_off, size_t msg_stride, size_t msg_len, size_t n, const uint8_t *coeffs,
+                           uint8_t *status_out, uint64_t *nf) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (ctx->st_status.reserve(n + 16)) return SSA_ERR_HIP;
+    unsigned long long *d_fail = (unsigned long long *)ctx->ws_fail.p;
+    auto fetch = [&]() -> int {
+        if (int rc = screen_count(ctx, (const u8 *)ctx->st_status.p, n, d_fail)) return rc;
+        HIP_TRY(hipMemcpyAsync(status_out, ctx->st_status.p, n, hipMemcpyDeviceToHost, ctx->stream));
+        unsigned long long v = 0;
+        HIP_TRY(hipMemcpyAsync(&v, d_fail, sizeof v, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        *nf = v;
+        return 0;
+    };
+    if (n >= ctx->pipeline_min_n && ctx->pipeline_chunks > 1) {
+        // large slice: uploads in chunks with the hashes behind them (msm_host_one)
+        PipelinedInputs pin;      // its destructor drains the side streams on every error return below
+        bool used = false;
+        if (!coeffs || ctx->pin_coeffs.reserve(n * 32) == 0) {
+            if (coeffs && ctx->st_coeffs.reserve(n * 32)) return SSA_ERR_HIP;
+            if (int rc = pipelined_upload_hash(ctx, sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len, n, pin, &used))
+                return rc;
+            if (used) {
+                const void *pc = nullptr;
+                if (coeffs) {
+                    host_copy(ctx->pin_coeffs.p, coeffs, n * 32);
+                    HIP_TRY(hipMemcpyAsync(ctx->st_coeffs.p, ctx->pin_coeffs.p, n * 32, hipMemcpyHostToDevice, ctx->copy_stream));
+                    HIP_TRY(hipEventRecord(ctx->pipe_start, ctx->copy_stream));
+                    HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->pipe_start, 0));
+                    pc = ctx->st_coeffs.p;
+                }
+                if (int rc = screen_slice(ctx, pin.s.sigs, pin.s.pks, pin.s.inf, pin.s.msgs, pin.s.off, msg_stride, msg_len, n,
+                                          (const u8 *)pc, 32, (const u64 *)ctx->ws_h.p, (u8 *)ctx->st_status.p))
+                    return rc;
+                if (int rc = fetch()) return rc;
+                pin.done();
+                return 0;
+            }
+        }
+    }
+    StagedInputs s;
+    const void *p;
+    if (int rc = stage_up(ctx, ctx->st_sigs, sigs, n * 81, &p)) return rc;
+    s.sigs = (const u8 *)p;
+    if (int rc = stage_up(ctx, ctx->st_pks, pks, n * 96, &p)) return rc;
+    s.pks = (const u8 *)p;
+    if (pk_inf) {
+        if (int rc = stage_up(ctx, ctx->st_inf, pk_inf, n, &p)) return rc;
+        s.inf = (const u8 *)p;
+    }
+    if (int rc = stage_msgs(ctx, msgs, msg_off, msg_stride, msg_len, n, s)) return rc;
+    p = nullptr;
+    if (coeffs) {
+        if (int rc = stage_up(ctx, ctx->st_coeffs, coeffs, n * 32, &p)) return rc;
+    }
+    if (int rc = screen_slice(ctx, s.sigs, s.pks, s.inf, s.msgs, s.off, msg_stride, msg_len, n, (const u8 *)p, 32, nullptr,
+                              (u8 *)ctx->st_status.p))
+        return rc;
+    return fetch();
+}
+
+extern "C" int ssa_verify_batch_screened(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_inf,
+                                         const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len,
+                                         size_t n, const uint8_t *coeffs, uint8_t *status_out, uint64_t *n_fail_out) {
+    if (!ctx || (n && (!sigs || !pks || !status_out))) return SSA_ERR_ARG;
+    if (int rc = check_msgs(msgs, msg_off, msg_stride, msg_len, n)) return rc;
+    if (msg_off)
+        for (size_t i = 0; i < n; i++)
+            if (msg_off[i + 1] < msg_off[i] || msg_off[i + 1] - msg_off[i] > 0xffffffffull) return SSA_ERR_ARG;
+    if (n_fail_out) *n_fail_out = 0;
+    if (n == 0) return 0;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (n <= ctx->msm_small_max)
+        return ssa_verify_many(ctx, sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len, n, SSA_FLAG_SIG_FLAG_BYTE,
+                               status_out, n_fail_out);
+    std::mutex mu;
+    uint64_t total = 0;
+    const int rc = run_host_slices(ctx, n, ctx->msm_slice, [&](ssa_ctx *c, size_t lo, size_t cnt) {
+        const HostMsgSlice ms(msgs, msg_off, msg_stride, lo, cnt);
+        uint64_t nf = 0;
+        const int r = screen_host_one(c, sigs + 81 * lo, pks + 96 * lo, pk_inf ? pk_inf + lo : nullptr, ms.msgs, ms.offp,
+                                      msg_stride, msg_len, cnt, coeffs ? coeffs + 32 * lo : nullptr, status_out + lo, &nf);
+        std::lock_guard<std::mutex> lock(mu);
+        total += nf;
+        return r;
+    });
+    if (rc) return rc;
+    if (n_fail_out) *n_fail_out = total;
+    return 0;
 }
