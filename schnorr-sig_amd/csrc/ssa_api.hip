@@ -399,14 +399,7 @@ extern "C" void ssa_ctx_destroy(ssa_ctx *ctx) {
             (void)hipEventDestroy(t.start);
             (void)hipEventDestroy(t.stop);
         }
-    for (DevBuf *b : {&ctx->ws_h, &ctx->ws_tab, &ctx->ws_fail, &ctx->st_sigs, &ctx->st_pks, &ctx->st_inf,
-                      &ctx->st_msgs, &ctx->st_off, &ctx->st_status, &ctx->st_aux, &ctx->st_aux2, &ctx->msm_points,
-                      &ctx->msm_scalars, &ctx->msm_keys, &ctx->msm_vals, &ctx->msm_keys2, &ctx->msm_vals2,
-                      &ctx->msm_sort_tmp, &ctx->msm_bounds, &ctx->msm_buckets, &ctx->msm_chunks, &ctx->msm_windows,
-                      &ctx->msm_partials, &ctx->msm_flags, &ctx->st_coeffs, &ctx->msm_cnt, &ctx->msm_cnt2,
-                      &ctx->msm_ids, &ctx->msm_ids2, &ctx->msm_comb_pts, &ctx->msm_comb_lins, &ctx->msm_slice_recs, &ctx->msm_sbuf, &ctx->scr_ok, &ctx->scr_in, &ctx->scr_status, &ctx->scr_fail, &ctx->tail_done, &ctx->tail_park, &ctx->ctab, &ctx->sg_sigs, &ctx->sg_pks, &ctx->dv_recs, &ctx->tc_out,
-                      &ctx->rng_seed, &ctx->rng_scratch})
-        b->release();
+    for_each_devbuf(ctx, [](DevBuf &b) { b.release(); });
     for (HostBuf *b : {&ctx->pin_in, &ctx->pin_coeffs, &ctx->pin_out, &ctx->pin_seed}) b->release();
     if (ctx->d_params) (void)hipFree(ctx->d_params);
     gtab_release(ctx->gtab_share);
@@ -433,13 +426,7 @@ extern "C" int ssa_ctx_info(const ssa_ctx *ctx, uint64_t out[8]) {
     if (!ctx || !out) return SSA_ERR_ARG;
     auto reserved = [](const ssa_ctx *c) {
         uint64_t sum = 0;
-        for (const DevBuf *b : {&c->ws_h, &c->ws_tab, &c->ws_fail, &c->st_sigs, &c->st_pks, &c->st_inf, &c->st_msgs,
-                                &c->st_off, &c->st_status, &c->st_aux, &c->st_aux2, &c->msm_points, &c->msm_scalars,
-                                &c->msm_keys, &c->msm_vals, &c->msm_keys2, &c->msm_vals2, &c->msm_sort_tmp, &c->msm_bounds,
-                                &c->msm_buckets, &c->msm_chunks, &c->msm_windows, &c->msm_partials, &c->msm_flags,
-                                &c->st_coeffs, &c->msm_cnt, &c->msm_cnt2, &c->msm_ids, &c->msm_ids2, &c->msm_comb_pts,
-                                &c->msm_comb_lins, &c->msm_slice_recs, &c->msm_sbuf, &c->scr_ok, &c->scr_in, &c->scr_status, &c->scr_fail, &c->tail_done, &c->tail_park, &c->ctab, &c->sg_sigs, &c->sg_pks})
-            sum += b->cap;
+        for_each_devbuf(c, [&](const DevBuf &b) { sum += b.cap; });
         return sum;
     };
     out[0] = ctx->gtab_bits;
@@ -859,40 +846,35 @@ extern "C" int ssa_decompress_many_device(ssa_ctx *ctx, const uint8_t *d_compres
 }
 
 // ------------------------------------------------------------------ host entry points
-// Large host-buffer batch: the shared upload + hash pipeline (ssa_ctx.hpp: pipelined_upload_hash), then ONE
-// verification launch over the whole batch: the ladder kernel keeps its full-size grid, only the first chunk's
-// upload is exposed.
-static int verify_many_pipelined(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_inf,
-                                 const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len,
-                                 size_t n, uint32_t flags, uint8_t *status_out, uint64_t *n_fail_out, bool *used) {
-    PipelinedInputs pin;      // its destructor drains the side streams on every error return below
-    *used = false;
-    if (ctx->pin_out.reserve(n)) return 0;          // (no page-locked memory: the staged path)
-    if (int rc = pipelined_upload_hash(ctx, sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len, n, pin, used)) return rc;
-    if (!*used) return 0;
-    const size_t slice = ctx->lane_slice < n ? ctx->lane_slice : n;
-    if (ctx->st_status.reserve(n + 16) ||
-        ctx->ws_tab.reserve(slice * (size_t)(PTAB_ENTRIES * PTAB_ENTRY_U64) * sizeof(u64)))
-        return SSA_ERR_HIP;
-    unsigned long long *d_fail = (unsigned long long *)ctx->ws_fail.p;
-    HIP_TRY(hipMemsetAsync(d_fail, 0, sizeof(unsigned long long), ctx->stream));
-    // (the pipeline hashed the whole batch into ws_h, 32 B per lane, while it was uploading)
-    if (int rc = verify_slices(ctx, pin.s.sigs, pin.s.pks, pin.s.inf, (const u64 *)ctx->ws_h.p, n, flags,
-                               (u8 *)ctx->st_status.p, d_fail))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->pin_out.p, ctx->st_status.p, n, hipMemcpyDeviceToHost, ctx->stream));
-    unsigned long long nf = 0;
-    HIP_TRY(hipMemcpyAsync(&nf, d_fail, sizeof nf, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+// ONE slice (n <= ctx->lane_slice, or a batch for the cooperative kernel) from host buffers.  A large one takes the shared
+// upload + hash pipeline (ssa_ctx.hpp: pipelined_upload_hash), then ONE verification launch over the whole slice: the
+// ladder kernel keeps its full-size grid, only the first chunk's upload is exposed, and the statuses come back through
+// page-locked memory.
+static int verify_many_host_one(ssa_ctx *ctx, const HostBatch &b, size_t n, uint32_t flags, uint8_t *status_out,
+                                uint64_t *n_fail_out) {
+    const size_t coop_lim = (flags & SSA_FLAG_CHECK_TORSION) ? ctx->coop_max_n_torsion : ctx->coop_max_n;
+    const bool lane_kernels = !(flags & SSA_FLAG_FORCE_COOP) && ((flags & SSA_FLAG_FORCE_LANE) || n > coop_lim);
+    HostCall hc(ctx);
+    PipelinedInputs pin;      // its destructor drains the side streams on every error return
+    const StagedInputs s = slice_inputs(hc, pin, b, n, nullptr, lane_kernels, true);
+    u8 *d_status = hc.out(ctx->st_status, s.hashed ? ctx->pin_out.p : status_out, n, 16);
+    unsigned long long nf = 0, *d_fail = (unsigned long long *)ctx->ws_fail.p;
+    hc.copy_back(&nf, d_fail, sizeof nf);
+    const int rc = hc.finish([&] {
+        if (!s.hashed)
+            return ssa_verify_many_device(ctx, s.sigs, s.pks, s.inf, s.msgs, s.off, b.msg_stride, b.msg_len, n, flags,
+                                          d_status, (uint64_t *)d_fail);
+        // (the pipeline hashed the whole slice into ws_h, 32 B per lane, while it was uploading)
+        HIP_TRY(hipMemsetAsync(d_fail, 0, sizeof(unsigned long long), ctx->stream));
+        return ssa_internal_verify_hashed(ctx, s.sigs, s.pks, s.inf, (const uint64_t *)ctx->ws_h.p, n, flags, d_status,
+                                          d_fail);
+    });
+    if (rc) return rc;
     pin.done();
-    std::memcpy(status_out, ctx->pin_out.p, n);
+    if (s.hashed) std::memcpy(status_out, ctx->pin_out.p, n);
     if (n_fail_out) *n_fail_out = nf;
     return 0;
 }
-
-static int verify_many_host_one(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_inf,
-                                const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len, size_t n,
-                                uint32_t flags, uint8_t *status_out, uint64_t *n_fail_out);
 
 extern "C" int ssa_verify_many(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_inf,
                                const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride,
@@ -900,66 +882,15 @@ extern "C" int ssa_verify_many(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t 
                                uint64_t *n_fail_out) {
     if (!ctx || (n && (!sigs || !pks || !status_out))) return SSA_ERR_ARG;
     if (int rc = check_msgs(msgs, msg_off, msg_stride, msg_len, n)) return rc;
-    if (msg_off)
-        for (size_t i = 0; i < n; i++)
-            if (msg_off[i + 1] < msg_off[i] || msg_off[i + 1] - msg_off[i] > 0xffffffffull) return SSA_ERR_ARG;
+    if (int rc = check_host_offsets(msg_off, n)) return rc;
     if (n_fail_out) *n_fail_out = 0;
     if (n == 0) return 0;
     HIP_TRY(hipSetDevice(ctx->device));
-    if (n <= ctx->lane_slice)
-        return verify_many_host_one(ctx, sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len, n, flags, status_out,
-                                    n_fail_out);
-    std::mutex mu;
-    uint64_t total = 0;
-    const int rc = run_host_slices(ctx, n, ctx->lane_slice, [&](ssa_ctx *c, size_t lo, size_t cnt) {
-        const HostMsgSlice ms(msgs, msg_off, msg_stride, lo, cnt);
-        uint64_t nf = 0;
-        const int r = verify_many_host_one(c, sigs + 81 * lo, pks + 96 * lo, pk_inf ? pk_inf + lo : nullptr, ms.msgs, ms.offp,
-                                           msg_stride, msg_len, cnt, flags, status_out + lo, &nf);
-        std::lock_guard<std::mutex> lock(mu);
-        total += nf;
-        return r;
-    });
-    if (rc) return rc;
-    if (n_fail_out) *n_fail_out = total;
-    return 0;
-}
-
-// one slice (n <= ctx->lane_slice, or a batch for the cooperative kernel) from host buffers
-static int verify_many_host_one(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_inf,
-                                const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len, size_t n,
-                                uint32_t flags, uint8_t *status_out, uint64_t *n_fail_out) {
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t coop_lim = (flags & SSA_FLAG_CHECK_TORSION) ? ctx->coop_max_n_torsion : ctx->coop_max_n;
-    const bool lane_kernels = !(flags & SSA_FLAG_FORCE_COOP) && ((flags & SSA_FLAG_FORCE_LANE) || n > coop_lim);
-    if (lane_kernels && n >= ctx->pipeline_min_n && ctx->pipeline_chunks > 1) {
-        bool used = false;
-        const int rc = verify_many_pipelined(ctx, sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len, n, flags,
-                                             status_out, n_fail_out, &used);
-        if (used) return rc;
-    }
-    StagedInputs s;
-    const void *p;
-    if (int rc = stage_up(ctx, ctx->st_sigs, sigs, n * 81, &p)) return rc;
-    s.sigs = (const u8 *)p;
-    if (int rc = stage_up(ctx, ctx->st_pks, pks, n * 96, &p)) return rc;
-    s.pks = (const u8 *)p;
-    if (pk_inf) {
-        if (int rc = stage_up(ctx, ctx->st_inf, pk_inf, n, &p)) return rc;
-        s.inf = (const u8 *)p;
-    }
-    if (int rc = stage_msgs(ctx, msgs, msg_off, msg_stride, msg_len, n, s)) return rc;
-    if (ctx->st_status.reserve(n + 16)) return SSA_ERR_HIP;
-    unsigned long long *d_fail = (unsigned long long *)ctx->ws_fail.p;
-    if (int rc = ssa_verify_many_device(ctx, s.sigs, s.pks, s.inf, s.msgs, s.off, msg_stride, msg_len, n,
-                                        flags, (u8 *)ctx->st_status.p, (uint64_t *)d_fail))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(status_out, ctx->st_status.p, n, hipMemcpyDeviceToHost, ctx->stream));
-    unsigned long long nf = 0;
-    HIP_TRY(hipMemcpyAsync(&nf, d_fail, sizeof nf, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (n_fail_out) *n_fail_out = nf;
-    return 0;
+    const HostBatch b{sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len};
+    return run_host_slices_counted(ctx, b, n, ctx->lane_slice, n_fail_out,
+                                   [&](ssa_ctx *c, size_t lo, size_t cnt, const HostBatch &s, uint64_t *nf) {
+                                       return verify_many_host_one(c, s, cnt, flags, status_out + lo, nf);
+                                   });
 }
 
 extern "C" int ssa_verify_batch(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_inf,
@@ -997,38 +928,25 @@ extern "C" int ssa_hash_message_many(ssa_ctx *ctx, const uint8_t *sigs, const ui
                                      uint8_t *digests_out) {
     if (!ctx || (n && (!sigs || !pks || !digests_out))) return SSA_ERR_ARG;
     if (int rc = check_msgs(msgs, msg_off, msg_stride, msg_len, n)) return rc;
+    if (int rc = check_host_offsets(msg_off, n)) return rc;
     if (n == 0) return 0;
-    HIP_TRY(hipSetDevice(ctx->device));
-    StagedInputs s;
-    const void *p;
-    if (int rc = stage_up(ctx, ctx->st_sigs, sigs, n * 81, &p)) return rc;
-    s.sigs = (const u8 *)p;
-    if (int rc = stage_up(ctx, ctx->st_pks, pks, n * 96, &p)) return rc;
-    s.pks = (const u8 *)p;
-    if (int rc = stage_msgs(ctx, msgs, msg_off, msg_stride, msg_len, n, s)) return rc;
-    if (ctx->st_aux.reserve(n * 32)) return SSA_ERR_HIP;
-    if (int rc = ssa_hash_message_many_device(ctx, s.sigs, s.pks, s.msgs, s.off, msg_stride, msg_len, n,
-                                              (u8 *)ctx->st_aux.p))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(digests_out, ctx->st_aux.p, n * 32, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return 0;
+    HostCall hc(ctx);
+    const u8 *d_sigs = hc.in(ctx->st_sigs, sigs, n * 81), *d_pks = hc.in(ctx->st_pks, pks, n * 96);
+    const MsgView mv = hc.msgs(msgs, msg_off, msg_stride, msg_len, n);
+    u8 *d_out = hc.out(ctx->st_aux, digests_out, n * 32);
+    return hc.finish([&] {
+        return ssa_hash_message_many_device(ctx, d_sigs, d_pks, mv.msgs, mv.off, msg_stride, msg_len, n, d_out);
+    });
 }
 
 extern "C" int ssa_rescue_hash_many(ssa_ctx *ctx, const uint64_t *felts, uint32_t felts_per_row, size_t n,
                                     uint64_t *digests_out) {
     if (!ctx || (n && (!digests_out || (felts_per_row && !felts)))) return SSA_ERR_ARG;
     if (n == 0) return 0;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const void *p;
-    if (int rc = stage_up(ctx, ctx->st_aux, felts, n * (size_t)felts_per_row * 8, &p)) return rc;
-    if (ctx->st_aux2.reserve(n * 32)) return SSA_ERR_HIP;
-    if (int rc = ssa_rescue_hash_many_device(ctx, (const uint64_t *)p, felts_per_row, n,
-                                             (uint64_t *)ctx->st_aux2.p))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(digests_out, ctx->st_aux2.p, n * 32, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return 0;
+    HostCall hc(ctx);
+    const uint64_t *d_felts = hc.in<uint64_t>(ctx->st_aux, felts, n * (size_t)felts_per_row * 8);
+    u8 *d_out = hc.out(ctx->st_aux2, digests_out, n * 32);
+    return hc.finish([&] { return ssa_rescue_hash_many_device(ctx, d_felts, felts_per_row, n, (uint64_t *)d_out); });
 }
 
 extern "C" int ssa_keygen_sign_many(ssa_ctx *ctx, const uint8_t *sks, const uint8_t *nonces,
@@ -1042,80 +960,52 @@ extern "C" int ssa_decompress_many(ssa_ctx *ctx, const uint8_t *compressed, size
                                    uint8_t *pk_inf_out, uint8_t *status_out) {
     if (!ctx || (n && (!compressed || !pks_out || !status_out))) return SSA_ERR_ARG;
     if (n == 0) return 0;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const void *p;
-    if (int rc = stage_up(ctx, ctx->st_sigs, compressed, n * 49, &p)) return rc;
-    if (ctx->st_aux.reserve(n * 96) || ctx->st_aux2.reserve(n + 16) || ctx->st_status.reserve(n + 16))
-        return SSA_ERR_HIP;
-    if (int rc = ssa_decompress_many_device(ctx, (const u8 *)p, n, (u8 *)ctx->st_aux.p, (u8 *)ctx->st_aux2.p,
-                                            (u8 *)ctx->st_status.p))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(pks_out, ctx->st_aux.p, n * 96, hipMemcpyDeviceToHost, ctx->stream));
-    if (pk_inf_out) HIP_TRY(hipMemcpyAsync(pk_inf_out, ctx->st_aux2.p, n, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(status_out, ctx->st_status.p, n, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return 0;
+    HostCall hc(ctx);
+    const u8 *d_in = hc.in(ctx->st_sigs, compressed, n * 49);
+    u8 *d_pks = hc.out(ctx->st_aux, pks_out, n * 96), *d_inf = hc.out(ctx->st_aux2, pk_inf_out, n, 16),
+       *d_status = hc.out(ctx->st_status, status_out, n, 16);
+    return hc.finish([&] { return ssa_decompress_many_device(ctx, d_in, n, d_pks, d_inf, d_status); });
 }
 
-static int verify_keyed_host_one(ssa_ctx *ctx, const uint8_t *keyed, const uint8_t *msgs, const uint64_t *msg_off,
-                                 size_t msg_stride, size_t msg_len, size_t n, uint32_t flags, uint8_t *status_out,
-                                 uint64_t *n_fail_out);
+// one slice of KeyedSignature records (n <= ctx->lane_slice) from host buffers (b: the messages only)
+static int verify_keyed_host_one(ssa_ctx *ctx, const uint8_t *keyed, const HostBatch &b, size_t n, uint32_t flags,
+                                 uint8_t *status_out, uint64_t *n_fail_out) {
+    HostCall hc(ctx);
+    const u8 *d_keyed = hc.in(ctx->st_coeffs, keyed, n * 130);
+    u8 *d_sigs = hc.out(ctx->st_sigs, nullptr, n * 81), *d_pks = hc.out(ctx->st_pks, nullptr, n * 96),
+       *d_inf = hc.out(ctx->st_inf, nullptr, n, 16), *d_status = hc.out(ctx->st_status, status_out, n, 16);
+    hc.step([&] {
+        hipLaunchKernelGGL(ssa_k_unpack_keyed, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, d_keyed, n, d_pks, d_inf,
+                           d_sigs);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    });
+    const MsgView mv = hc.msgs(b.msgs, b.msg_off, b.msg_stride, b.msg_len, n);
+    unsigned long long nf = 0, *d_fail = (unsigned long long *)ctx->ws_fail.p;
+    hc.copy_back(&nf, d_fail, sizeof nf);
+    if (int rc = hc.finish([&] {
+            return ssa_verify_many_device(ctx, d_sigs, d_pks, d_inf, mv.msgs, mv.off, b.msg_stride, b.msg_len, n, flags,
+                                          d_status, (uint64_t *)d_fail);
+        }))
+        return rc;
+    if (n_fail_out) *n_fail_out = nf;
+    return 0;
+}
 
 extern "C" int ssa_verify_keyed_many(ssa_ctx *ctx, const uint8_t *keyed, const uint8_t *msgs,
                                      const uint64_t *msg_off, size_t msg_stride, size_t msg_len, size_t n,
                                      uint32_t flags, uint8_t *status_out, uint64_t *n_fail_out) {
     if (!ctx || (n && (!keyed || !status_out))) return SSA_ERR_ARG;
     if (int rc = check_msgs(msgs, msg_off, msg_stride, msg_len, n)) return rc;
-    if (msg_off)
-        for (size_t i = 0; i < n; i++)
-            if (msg_off[i + 1] < msg_off[i] || msg_off[i + 1] - msg_off[i] > 0xffffffffull) return SSA_ERR_ARG;
+    if (int rc = check_host_offsets(msg_off, n)) return rc;
     if (n_fail_out) *n_fail_out = 0;
     if (n == 0) return 0;
     HIP_TRY(hipSetDevice(ctx->device));
-    if (n <= ctx->lane_slice)
-        return verify_keyed_host_one(ctx, keyed, msgs, msg_off, msg_stride, msg_len, n, flags, status_out, n_fail_out);
-    std::mutex mu;
-    uint64_t total = 0;
-    const int rc = run_host_slices(ctx, n, ctx->lane_slice, [&](ssa_ctx *c, size_t lo, size_t cnt) {
-        const HostMsgSlice ms(msgs, msg_off, msg_stride, lo, cnt);
-        uint64_t nf = 0;
-        const int r = verify_keyed_host_one(c, keyed + 130 * lo, ms.msgs, ms.offp, msg_stride, msg_len, cnt, flags,
-                                            status_out + lo, &nf);
-        std::lock_guard<std::mutex> lock(mu);
-        total += nf;
-        return r;
-    });
-    if (rc) return rc;
-    if (n_fail_out) *n_fail_out = total;
-    return 0;
-}
-
-// one slice of KeyedSignature records (n <= ctx->lane_slice) from host buffers
-static int verify_keyed_host_one(ssa_ctx *ctx, const uint8_t *keyed, const uint8_t *msgs, const uint64_t *msg_off,
-                                 size_t msg_stride, size_t msg_len, size_t n, uint32_t flags, uint8_t *status_out,
-                                 uint64_t *n_fail_out) {
-    HIP_TRY(hipSetDevice(ctx->device));
-    StagedInputs s;
-    const void *p;
-    if (int rc = stage_up(ctx, ctx->st_coeffs, keyed, n * 130, &p)) return rc;
-    if (ctx->st_sigs.reserve(n * 81) || ctx->st_pks.reserve(n * 96) || ctx->st_inf.reserve(n + 16) ||
-        ctx->st_status.reserve(n + 16))
-        return SSA_ERR_HIP;
-    hipLaunchKernelGGL(ssa_k_unpack_keyed, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, (const u8 *)p, n,
-                       (u8 *)ctx->st_pks.p, (u8 *)ctx->st_inf.p, (u8 *)ctx->st_sigs.p);
-    HIP_TRY(hipGetLastError());
-    if (int rc = stage_msgs(ctx, msgs, msg_off, msg_stride, msg_len, n, s)) return rc;
-    unsigned long long *d_fail = (unsigned long long *)ctx->ws_fail.p;
-    if (int rc = ssa_verify_many_device(ctx, (const u8 *)ctx->st_sigs.p, (const u8 *)ctx->st_pks.p,
-                                        (const u8 *)ctx->st_inf.p, s.msgs, s.off, msg_stride, msg_len, n, flags,
-                                        (u8 *)ctx->st_status.p, (uint64_t *)d_fail))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(status_out, ctx->st_status.p, n, hipMemcpyDeviceToHost, ctx->stream));
-    unsigned long long nf = 0;
-    HIP_TRY(hipMemcpyAsync(&nf, d_fail, sizeof nf, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (n_fail_out) *n_fail_out = nf;
-    return 0;
+    const HostBatch b{nullptr, nullptr, nullptr, msgs, msg_off, msg_stride, msg_len};
+    return run_host_slices_counted(ctx, b, n, ctx->lane_slice, n_fail_out,
+                                   [&](ssa_ctx *c, size_t lo, size_t cnt, const HostBatch &s, uint64_t *nf) {
+                                       return verify_keyed_host_one(c, keyed + 130 * lo, s, cnt, flags, status_out + lo, nf);
+                                   });
 }
 
 // ------------------------------------------------------------------ keyed context
@@ -1186,12 +1076,9 @@ extern "C" int ssa_keyset_create_device(ssa_ctx *ctx, const uint8_t *d_pks, cons
 extern "C" int ssa_keyset_create(ssa_ctx *ctx, const uint8_t *pks, const uint8_t *pk_inf, size_t m, uint32_t flags,
                                  ssa_keyset **out) {
     if (!ctx || !out || !pks || m == 0) return SSA_ERR_ARG;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const void *p_pks, *p_inf = nullptr;
-    if (int rc = stage_up(ctx, ctx->st_pks, pks, m * 96, &p_pks)) return rc;
-    if (pk_inf)
-        if (int rc = stage_up(ctx, ctx->st_inf, pk_inf, m, &p_inf)) return rc;
-    return ssa_keyset_create_device(ctx, (const u8 *)p_pks, (const u8 *)p_inf, m, flags, out);
+    HostCall hc(ctx);
+    const u8 *d_pks = hc.in(ctx->st_pks, pks, m * 96), *d_inf = pk_inf ? hc.in(ctx->st_inf, pk_inf, m) : nullptr;
+    return hc.finish([&] { return ssa_keyset_create_device(ctx, d_pks, d_inf, m, flags, out); });
 }
 
 extern "C" void ssa_keyset_destroy(ssa_keyset *ks) {
@@ -1212,10 +1099,9 @@ extern "C" void ssa_keyset_destroy(ssa_keyset *ks) {
 
 extern "C" int ssa_keyset_status(ssa_keyset *ks, uint8_t *status_out) {
     if (!ks || !ks->ctx || !status_out) return SSA_ERR_ARG;
-    HIP_TRY(hipSetDevice(ks->ctx->device));
-    HIP_TRY(hipMemcpyAsync(status_out, ks->status.p, ks->m, hipMemcpyDeviceToHost, ks->ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ks->ctx->stream));
-    return 0;
+    HostCall hc(ks->ctx);
+    hc.copy_back(status_out, ks->status.p, ks->m);
+    return hc.finish([] { return 0; });
 }
 
 extern "C" int ssa_verify_many_indexed_device(ssa_ctx *ctx, ssa_keyset *ks, const uint32_t *d_key_idx,
@@ -1254,24 +1140,21 @@ extern "C" int ssa_verify_many_indexed(ssa_ctx *ctx, ssa_keyset *ks, const uint3
                                        size_t n, uint32_t flags, uint8_t *status_out, uint64_t *n_fail_out) {
     if (!ctx || !ks || ks->ctx != ctx || (n && (!key_idx || !sigs || !status_out))) return SSA_ERR_ARG;
     if (int rc = check_msgs(msgs, msg_off, msg_stride, msg_len, n)) return rc;
+    if (int rc = check_host_offsets(msg_off, n)) return rc;
     if (n_fail_out) *n_fail_out = 0;
     if (n == 0) return 0;
-    HIP_TRY(hipSetDevice(ctx->device));
-    StagedInputs s;
-    const void *p, *p_idx;
-    if (int rc = stage_up(ctx, ctx->st_sigs, sigs, n * 81, &p)) return rc;
-    s.sigs = (const u8 *)p;
-    if (int rc = stage_up(ctx, ctx->st_aux, key_idx, n * sizeof(uint32_t), &p_idx)) return rc;
-    if (int rc = stage_msgs(ctx, msgs, msg_off, msg_stride, msg_len, n, s)) return rc;
-    if (ctx->st_status.reserve(n + 16)) return SSA_ERR_HIP;
-    unsigned long long *d_fail = (unsigned long long *)ctx->ws_fail.p;
-    if (int rc = ssa_verify_many_indexed_device(ctx, ks, (const uint32_t *)p_idx, s.sigs, s.msgs, s.off, msg_stride,
-                                                msg_len, n, flags, (u8 *)ctx->st_status.p, (uint64_t *)d_fail))
+    HostCall hc(ctx);
+    const u8 *d_sigs = hc.in(ctx->st_sigs, sigs, n * 81);
+    const uint32_t *d_idx = hc.in<uint32_t>(ctx->st_aux, key_idx, n * sizeof(uint32_t));
+    const MsgView mv = hc.msgs(msgs, msg_off, msg_stride, msg_len, n);
+    u8 *d_status = hc.out(ctx->st_status, status_out, n, 16);
+    unsigned long long nf = 0, *d_fail = (unsigned long long *)ctx->ws_fail.p;
+    hc.copy_back(&nf, d_fail, sizeof nf);
+    if (int rc = hc.finish([&] {
+            return ssa_verify_many_indexed_device(ctx, ks, d_idx, d_sigs, mv.msgs, mv.off, msg_stride, msg_len, n, flags,
+                                                  d_status, (uint64_t *)d_fail);
+        }))
         return rc;
-    HIP_TRY(hipMemcpyAsync(status_out, ctx->st_status.p, n, hipMemcpyDeviceToHost, ctx->stream));
-    unsigned long long nf = 0;
-    HIP_TRY(hipMemcpyAsync(&nf, d_fail, sizeof nf, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
     if (n_fail_out) *n_fail_out = nf;
     return 0;
 }
@@ -1317,6 +1200,7 @@ extern "C" int ssa_multi_verify_many(ssa_multi *m, const uint8_t *sigs, const ui
     if (n_fail_out) *n_fail_out = 0;
     if (n == 0) return 0;
     const size_t world = m->ctxs.size();
+    const HostBatch b{sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len};
     std::vector<int> rcs(world, 0);
     std::vector<uint64_t> fails(world, 0);
     std::vector<std::thread> threads;
@@ -1325,20 +1209,10 @@ extern "C" int ssa_multi_verify_many(ssa_multi *m, const uint8_t *sigs, const ui
         const size_t lo = r * base + (r < rem ? r : rem), cnt = base + (r < rem ? 1 : 0);
         threads.emplace_back([&, r, lo, cnt] {
             if (cnt == 0) return;
-            // shard-local message view: offsets are rebased by pointing at msgs + off[lo]
             std::vector<uint64_t> off;
-            const uint8_t *mbase = msgs;
-            const uint64_t *offp = nullptr;
-            if (msg_off) {
-                off.resize(cnt + 1);
-                for (size_t k = 0; k <= cnt; k++) off[k] = msg_off[lo + k] - msg_off[lo];
-                mbase = msgs + msg_off[lo];
-                offp = off.data();
-            } else {
-                mbase = msgs ? msgs + lo * msg_stride : nullptr;
-            }
-            rcs[r] = ssa_verify_many(m->ctxs[r], sigs + 81 * lo, pks + 96 * lo, pk_inf ? pk_inf + lo : nullptr, mbase,
-                                     offp, msg_stride, msg_len, cnt, flags, status_out + lo, &fails[r]);
+            const HostBatch s = b.slice(lo, cnt, off);
+            rcs[r] = ssa_verify_many(m->ctxs[r], s.sigs, s.pks, s.pk_inf, s.msgs, s.msg_off, msg_stride, msg_len, cnt, flags,
+                                     status_out + lo, &fails[r]);
         });
     }
     for (auto &t : threads) t.join();
@@ -1362,6 +1236,7 @@ extern "C" int ssa_multi_verify_batch_msm(ssa_multi *m, const uint8_t *sigs, con
     if (int rc = check_msgs(msgs, msg_off, msg_stride, msg_len, n)) return rc;
     if (n == 0) return SSA_OK;
     const size_t world = m->ctxs.size();
+    const HostBatch b{sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len};
     std::vector<int> rcs(world, 0);
     std::vector<uint64_t> parts(24 * world, 0);
     std::vector<std::thread> threads;
@@ -1371,19 +1246,9 @@ extern "C" int ssa_multi_verify_batch_msm(ssa_multi *m, const uint8_t *sigs, con
         threads.emplace_back([&, r, lo, cnt] {
             // (an empty shard still produces its record -- the identity, 0 and the magic word: an unwritten slot is not one)
             std::vector<uint64_t> off;
-            const uint8_t *mbase = msgs;
-            const uint64_t *offp = nullptr;
-            if (msg_off) {
-                off.resize(cnt + 1);
-                for (size_t k = 0; k <= cnt; k++) off[k] = msg_off[lo + k] - msg_off[lo];
-                mbase = msgs + msg_off[lo];
-                offp = off.data();
-            } else {
-                mbase = msgs ? msgs + lo * msg_stride : nullptr;
-            }
-            rcs[r] = ssa_verify_batch_msm_partial(m->ctxs[r], sigs + 81 * lo, pks + 96 * lo, pk_inf ? pk_inf + lo : nullptr,
-                                              mbase, offp, msg_stride, msg_len, cnt, coeffs ? coeffs + 32 * lo : nullptr,
-                                              &parts[24 * r]);
+            const HostBatch s = b.slice(lo, cnt, off);
+            rcs[r] = ssa_verify_batch_msm_partial(m->ctxs[r], s.sigs, s.pks, s.pk_inf, s.msgs, s.msg_off, msg_stride, msg_len,
+                                                  cnt, coeffs ? coeffs + 32 * lo : nullptr, &parts[24 * r]);
         });
     }
     for (auto &t : threads) t.join();
@@ -1419,29 +1284,25 @@ extern "C" int ssa_debug_arith(ssa_ctx *ctx, int op, const uint64_t *a, const ui
                 if (a[i * a_stride + 19] == 0 || a[i * a_stride + 19] > 64 || a[i * a_stride + 19] != a[19])
                     return SSA_ERR_ARG;
     }
-    HIP_TRY(hipSetDevice(ctx->device));
-    const void *da, *db = nullptr;
-    if (int rc = stage_up(ctx, ctx->st_aux, a, n * a_stride * 8, &da)) return rc;
-    if (b)
-        if (int rc = stage_up(ctx, ctx->st_aux2, b, n * b_stride * 8, &db)) return rc;
-    if (ctx->st_status.reserve(n * out_stride * 8)) return SSA_ERR_HIP;
-    HIP_TRY(hipMemsetAsync(ctx->st_status.p, 0, n * out_stride * 8, ctx->stream));
-    if (op == 7) {
-        hipLaunchKernelGGL(ssa_k_debug_coop, dim3((unsigned)n), dim3(64), 0, ctx->stream, (const u64 *)da,
-                           (const u64 *)db, n, a_stride, b_stride, (u64 *)ctx->st_status.p, out_stride);
-    } else if (op == 4 || (op >= 15 && op <= 17)) {
-        if (ctx->ws_tab.reserve(n * (size_t)(PTAB_ENTRIES * PTAB_ENTRY_U64) * sizeof(u64))) return SSA_ERR_HIP;
-        hipLaunchKernelGGL(ssa_k_debug_mul, dim3(grid_for(n, 64)), dim3(64), 0, ctx->stream, op, (const u64 *)da,
-                           (const u64 *)db, n, a_stride, b_stride, (u64 *)ctx->ws_tab.p,
-                           (u64 *)ctx->st_status.p, out_stride);
-    } else {
-        hipLaunchKernelGGL(ssa_k_debug, dim3(grid_for(n, 64)), dim3(64), 0, ctx->stream, op, (const u64 *)da,
-                           (const u64 *)db, n, a_stride, b_stride, (u64 *)ctx->st_status.p, out_stride);
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, ctx->st_status.p, n * out_stride * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return 0;
+    HostCall hc(ctx);
+    const u64 *da = hc.in<u64>(ctx->st_aux, a, n * a_stride * 8), *db = b ? hc.in<u64>(ctx->st_aux2, b, n * b_stride * 8) : nullptr;
+    u64 *d_out = (u64 *)hc.out(ctx->st_status, out, n * out_stride * 8);
+    return hc.finish([&] {
+        HIP_TRY(hipMemsetAsync(d_out, 0, n * out_stride * 8, ctx->stream));
+        if (op == 7) {
+            hipLaunchKernelGGL(ssa_k_debug_coop, dim3((unsigned)n), dim3(64), 0, ctx->stream, da, db, n, a_stride, b_stride,
+                               d_out, out_stride);
+        } else if (op == 4 || (op >= 15 && op <= 17)) {
+            if (ctx->ws_tab.reserve(n * (size_t)(PTAB_ENTRIES * PTAB_ENTRY_U64) * sizeof(u64))) return SSA_ERR_HIP;
+            hipLaunchKernelGGL(ssa_k_debug_mul, dim3(grid_for(n, 64)), dim3(64), 0, ctx->stream, op, da, db, n, a_stride,
+                               b_stride, (u64 *)ctx->ws_tab.p, d_out, out_stride);
+        } else {
+            hipLaunchKernelGGL(ssa_k_debug, dim3(grid_for(n, 64)), dim3(64), 0, ctx->stream, op, da, db, n, a_stride,
+                               b_stride, d_out, out_stride);
+        }
+        HIP_TRY(hipGetLastError());
+        return 0;
+    });
 }
 
 extern "C" int ssa_bench_fpmul(ssa_ctx *ctx, int variant, double *fpmul_per_s) {

@@ -6,13 +6,15 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
 #include <mutex>
-#include <thread>
 #include <string>
+#include <thread>
+#include <utility>
 #include <vector>
 
 using namespace ssa;
@@ -163,6 +165,19 @@ struct ssa_ctx {
     std::vector<struct ssa_signer_set *> signer_sets;   // live signer sets (ssa_sign.hip), orphaned the same way
 };
 
+// every DevBuf of a context, once: ssa_ctx_destroy releases them, ssa_ctx_info sums their capacities
+template <class Ctx, class F>
+static inline void for_each_devbuf(Ctx *c, F &&f) {
+    for (auto *b : {&c->ws_h, &c->ws_tab, &c->ws_fail, &c->st_sigs, &c->st_pks, &c->st_inf, &c->st_msgs, &c->st_off,
+                    &c->st_status, &c->st_aux, &c->st_aux2, &c->msm_points, &c->msm_scalars, &c->msm_keys, &c->msm_vals,
+                    &c->msm_keys2, &c->msm_vals2, &c->msm_sort_tmp, &c->msm_bounds, &c->msm_buckets, &c->msm_chunks,
+                    &c->msm_windows, &c->msm_partials, &c->msm_flags, &c->st_coeffs, &c->msm_cnt, &c->msm_cnt2,
+                    &c->msm_ids, &c->msm_ids2, &c->msm_comb_pts, &c->msm_comb_lins, &c->msm_slice_recs, &c->msm_sbuf,
+                    &c->scr_ok, &c->scr_in, &c->scr_status, &c->scr_fail, &c->ctab, &c->sg_sigs, &c->sg_pks, &c->tc_out,
+                    &c->dv_recs, &c->rng_seed, &c->rng_scratch, &c->tail_done, &c->tail_park})
+        f(*b);
+}
+
 // signer set (the signing twin of ssa_keyset; entry points in ssa_sign.hip): m key pairs resident on the device
 struct ssa_signer_set {
     ssa_ctx *ctx = nullptr;   // nullptr: the context is gone, the device memory went with it
@@ -214,46 +229,151 @@ static inline int check_msgs(const uint8_t *msgs, const uint64_t *off, size_t st
     return 0;
 }
 
+// the offset table of a host batch (read here, so once per host entry point and before anything is enqueued): offsets
+// never decrease and no message is longer than 2^32 - 1 bytes.  check_msgs also runs on device pointers: it reads no offset.
+static inline int check_host_offsets(const uint64_t *off, size_t n) {
+    if (off)
+        for (size_t i = 0; i < n; i++)
+            if (off[i + 1] < off[i] || off[i + 1] - off[i] > 0xffffffffull) return SSA_ERR_ARG;
+    return 0;
+}
+
 static inline size_t msgs_bytes(const uint64_t *off, size_t stride, size_t len, size_t n) {
     if (n == 0) return 0;
     if (off) return (size_t)off[n];
     return (n - 1) * stride + len;
 }
 
-struct StagedInputs {
-    const u8 *sigs = nullptr, *pks = nullptr, *inf = nullptr, *msgs = nullptr;
-    const u64 *off = nullptr;
+// a batch in host memory as the verification entry points take it: 81-byte signatures, 96-byte keys, optional identity
+// flags, and the messages by offset table or by stride
+struct HostBatch {
+    const uint8_t *sigs, *pks, *pk_inf, *msgs;
+    const uint64_t *msg_off;
+    size_t msg_stride, msg_len;
+    // lanes [lo, lo + cnt) as a batch of their own (an offset table is rebased into `off`, which must outlive the result)
+    HostBatch slice(size_t lo, size_t cnt, std::vector<uint64_t> &off) const {
+        HostBatch s = *this;
+        s.sigs = sigs ? sigs + 81 * lo : nullptr;
+        s.pks = pks ? pks + 96 * lo : nullptr;
+        s.pk_inf = pk_inf ? pk_inf + lo : nullptr;
+        if (msg_off) {
+            off.resize(cnt + 1);
+            for (size_t k = 0; k <= cnt; k++) off[k] = msg_off[lo + k] - msg_off[lo];
+            s.msgs = msgs ? msgs + msg_off[lo] : nullptr;
+            s.msg_off = off.data();
+        } else {
+            s.msgs = msgs ? msgs + lo * msg_stride : nullptr;
+        }
+        return s;
+    }
 };
 
-static inline int stage_up(ssa_ctx *ctx, DevBuf &buf, const void *src, size_t bytes, const void **dst) {
-    *dst = nullptr;
-    if (!src || bytes == 0) {
-        if (buf.reserve(16)) return SSA_ERR_HIP;  // non-null dummy for zero-length messages
-        *dst = src ? buf.p : nullptr;
-        return 0;
-    }
-    if (buf.reserve(bytes)) return SSA_ERR_HIP;
-    HIP_TRY(hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-    *dst = buf.p;
-    return 0;
-}
+// device copies of one slice of a batch; hashed: ctx->ws_h already holds the challenge scalars (pipelined_upload_hash)
+struct StagedInputs {
+    const u8 *sigs = nullptr, *pks = nullptr, *inf = nullptr, *msgs = nullptr, *coeffs = nullptr;
+    const u64 *off = nullptr;
+    bool hashed = false;
+};
 
-static inline int stage_msgs(ssa_ctx *ctx, const uint8_t *msgs, const uint64_t *off, size_t stride, size_t len,
-                      size_t n, StagedInputs &s) {
-    const void *p;
-    if (off) {
-        for (size_t i = 0; i < n; i++)
-            if (off[i + 1] < off[i] || off[i + 1] - off[i] > 0xffffffffull) return SSA_ERR_ARG;
-        if (int rc = stage_up(ctx, ctx->st_off, off, (n + 1) * sizeof(uint64_t), &p)) return rc;
-        s.off = (const u64 *)p;
+// Device copies of secrets (keys, nonces, seeds, parent and master xprvs) do not outlive the call that made them,
+// whichever way it returns: the named buffers are zeroed on the context's stream, each clamped to its capacity, when
+// this goes out of scope.  Whoever owns it synchronises where the call must not return before the zeroing.
+struct SecretWipe {
+    ssa_ctx *ctx;
+    std::vector<std::pair<DevBuf *, size_t>> bufs;     // buffer, bytes of secrets in it
+    void add(DevBuf &b, size_t bytes) { bufs.emplace_back(&b, bytes); }
+    bool zero() {             // true when something was zeroed
+        bool any = false;
+        for (auto &b : bufs)
+            if (b.first->p && b.second) {
+                (void)hipMemsetAsync(b.first->p, 0, std::min(b.second, b.first->cap), ctx->stream);
+                any = true;
+            }
+        bufs.clear();
+        return any;
     }
-    const size_t mb = msgs_bytes(off, stride, len, n);
-    if (mb && !msgs) return SSA_ERR_ARG;
-    if (ctx->st_msgs.reserve(mb + 16)) return SSA_ERR_HIP;
-    if (mb) HIP_TRY(hipMemcpyAsync(ctx->st_msgs.p, msgs, mb, hipMemcpyHostToDevice, ctx->stream));
-    s.msgs = (const u8 *)ctx->st_msgs.p;
-    return 0;
-}
+    ~SecretWipe() { zero(); }
+};
+
+constexpr bool SECRET = true;
+
+// One call of a host-buffer entry point that stages its inputs, runs the device form and copies the results back.
+// Built after the argument checks, it selects the device; in() stages an input into the named context buffer, out()
+// reserves an output there and remembers where it goes (a null destination: no copy), msgs() stages a message batch.
+// The first error sticks and every later step is skipped, so a call site needs no check per line.  finish() runs the
+// device form, queues the copies back in order and synchronises once.  On destruction the secret buffers are zeroed on
+// the stream, and the stream is drained if anything was zeroed or if an error return left work in flight: the caller
+// may free or reuse its buffers as soon as the entry point returns.
+struct HostCall {
+    ssa_ctx *ctx;
+    int rc = 0;
+    bool enqueued = false, settled = false;
+    SecretWipe wipe{ctx};
+    struct Back { void *dst; const void *src; size_t bytes; };
+    std::vector<Back> back;       // the copies of finish(), in order
+
+    explicit HostCall(ssa_ctx *c) : ctx(c) { hip(hipSetDevice(ctx->device)); }
+    ~HostCall() {
+        const bool zeroed = wipe.zero();
+        if (zeroed || (enqueued && !settled)) (void)hipStreamSynchronize(ctx->stream);
+    }
+    bool ok() const { return rc == 0; }
+    void hip(hipError_t err) {
+        if (err == hipSuccess || rc) return;
+        if (ssa_debug_enabled()) std::fprintf(stderr, "[schnorr_sig_amd] host call: %s\n", hipGetErrorString(err));
+        rc = SSA_ERR_HIP;
+    }
+    // one step on the stream (a launch, a device form), unless an earlier one failed
+    template <class F>
+    void step(F &&f) {
+        if (rc) return;
+        enqueued = true;
+        rc = f();
+    }
+    // bytes of host memory into buf: its device copy (a non-null dummy for zero bytes), or nullptr for a null source
+    template <class T = u8>
+    const T *in(DevBuf &buf, const void *src, size_t bytes, bool secret = false) {
+        if (rc) return nullptr;
+        if (secret) wipe.add(buf, bytes);
+        enqueued = true;
+        if (buf.reserve(src && bytes ? bytes : 16)) rc = SSA_ERR_HIP;
+        else if (src && bytes) hip(hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+        return rc || !src ? nullptr : (const T *)buf.p;
+    }
+    // `bytes` of results in buf (reserved with `pad` bytes to spare), copied to dst by finish()
+    u8 *out(DevBuf &buf, void *dst, size_t bytes, size_t pad = 0, bool secret = false) {
+        if (rc) return nullptr;
+        if (buf.reserve(bytes + pad)) {
+            rc = SSA_ERR_HIP;
+            return nullptr;
+        }
+        if (secret) wipe.add(buf, bytes);
+        if (dst) copy_back(dst, buf.p, bytes);
+        return (u8 *)buf.p;
+    }
+    void copy_back(void *dst, const void *src, size_t bytes) { back.push_back({dst, src, bytes}); }
+    // the messages of n lanes into ctx->st_msgs (and the offset table into ctx->st_off)
+    MsgView msgs(const uint8_t *msgs, const uint64_t *off, size_t stride, size_t len, size_t n) {
+        MsgView mv{nullptr, nullptr, stride, len};
+        if (off) mv.off = in<u64>(ctx->st_off, off, (n + 1) * sizeof(uint64_t));
+        if (rc) return mv;
+        const size_t mb = msgs_bytes(off, stride, len, n);
+        if (mb && !msgs) rc = SSA_ERR_ARG;
+        else if (ctx->st_msgs.reserve(mb + 16)) rc = SSA_ERR_HIP;
+        else if (mb) hip(hipMemcpyAsync(ctx->st_msgs.p, msgs, mb, hipMemcpyHostToDevice, ctx->stream));
+        mv.msgs = rc ? nullptr : (const u8 *)ctx->st_msgs.p;
+        return mv;
+    }
+    template <class F>
+    int finish(F &&device_form) {
+        step(device_form);
+        for (const Back &c : back)
+            if (rc == 0) hip(hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, ctx->stream));
+        if (rc == 0 && !back.empty()) hip(hipStreamSynchronize(ctx->stream));
+        settled = rc == 0;
+        return rc;
+    }
+};
 
 
 // defined in ssa_api.hip
@@ -325,16 +445,15 @@ static inline int pipeline_fault_chunk(ssa_ctx *ctx) {
 // *_device call may still read ws_h or the staging buffers this call overwrites), and on return ctx->stream waits for
 // all of it: whatever the caller enqueues next sees the inputs and ctx->ws_h.
 // *used == false: the ranges could not be pinned (e.g. a read-only mapping) and nothing was enqueued.
-static inline int pipelined_upload_hash(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_inf,
-                                        const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len,
-                                        size_t n, PipelinedInputs &pin, bool *used) {
+static inline int pipelined_upload_hash(ssa_ctx *ctx, const HostBatch &b, size_t n, PipelinedInputs &pin, bool *used) {
+    const uint8_t *sigs = b.sigs, *pks = b.pks, *pk_inf = b.pk_inf, *msgs = b.msgs;
+    const uint64_t *msg_off = b.msg_off;
+    const size_t msg_stride = b.msg_stride, msg_len = b.msg_len;
     *used = false;
-    // arguments first: nothing is pinned or enqueued for a call that is going to be refused
+    // arguments first: nothing is pinned or enqueued for a call that is going to be refused (the offset table was
+    // checked by the entry point)
     const size_t mb = msgs_bytes(msg_off, msg_stride, msg_len, n);
     if (mb && !msgs) return SSA_ERR_ARG;
-    if (msg_off)
-        for (size_t i = 0; i < n; i++)
-            if (msg_off[i + 1] < msg_off[i] || msg_off[i + 1] - msg_off[i] > 0xffffffffull) return SSA_ERR_ARG;
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t o_pks = al(n * 81), o_msgs = o_pks + al(n * 96), o_inf = o_msgs + al(mb),
                  o_off = o_inf + al(pk_inf ? n : 0), total = o_off + al(msg_off ? (n + 1) * sizeof(uint64_t) : 0);
@@ -396,6 +515,46 @@ static inline int pipelined_upload_hash(ssa_ctx *ctx, const uint8_t *sigs, const
     return 0;
 }
 
+// The inputs of ONE host slice on the device, for verify_many_host_one, msm_host_one and screen_host_one: a large slice
+// (with `pipeline`, from ctx->pipeline_min_n lanes on) goes through pipelined_upload_hash, which leaves the challenge
+// hashes in ctx->ws_h (hashed) and arms `pin`; any other slice, or one that finds no page-locked memory for its
+// statuses (pin_out) or for the caller's 32-byte coefficients, is staged by `hc`.  Errors are left in hc.rc.
+static inline StagedInputs slice_inputs(HostCall &hc, PipelinedInputs &pin, const HostBatch &b, size_t n,
+                                        const uint8_t *coeffs, bool pipeline, bool pin_out) {
+    ssa_ctx *ctx = hc.ctx;
+    if (hc.ok() && pipeline && n >= ctx->pipeline_min_n && ctx->pipeline_chunks > 1 && !(pin_out && ctx->pin_out.reserve(n)) &&
+        (!coeffs || ctx->pin_coeffs.reserve(n * 32) == 0)) {
+        bool used = false;
+        if (coeffs && ctx->st_coeffs.reserve(n * 32)) hc.rc = SSA_ERR_HIP;
+        else hc.rc = pipelined_upload_hash(ctx, b, n, pin, &used);
+        if (!hc.ok() || used) {
+            StagedInputs s = pin.s;
+            s.hashed = true;
+            if (coeffs && hc.ok()) {
+                // behind the chunk copies on the copy stream; ctx->stream waits for this copy explicitly
+                host_copy(ctx->pin_coeffs.p, coeffs, n * 32);
+                hc.step([&] {
+                    HIP_TRY(hipMemcpyAsync(ctx->st_coeffs.p, ctx->pin_coeffs.p, n * 32, hipMemcpyHostToDevice, ctx->copy_stream));
+                    HIP_TRY(hipEventRecord(ctx->pipe_start, ctx->copy_stream));
+                    HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->pipe_start, 0));
+                    return 0;
+                });
+                s.coeffs = (const u8 *)ctx->st_coeffs.p;
+            }
+            return s;
+        }
+    }
+    StagedInputs s;
+    s.sigs = hc.in(ctx->st_sigs, b.sigs, n * 81);
+    s.pks = hc.in(ctx->st_pks, b.pks, n * 96);
+    if (b.pk_inf) s.inf = hc.in(ctx->st_inf, b.pk_inf, n);
+    const MsgView mv = hc.msgs(b.msgs, b.msg_off, b.msg_stride, b.msg_len, n);
+    s.msgs = mv.msgs;
+    s.off = mv.off;
+    if (coeffs) s.coeffs = hc.in(ctx->st_coeffs, coeffs, n * 32);
+    return s;
+}
+
 // defined in ssa_api.hip: hash_message + Scalar::from_bits_vartime for n signatures into ctx->ws_h
 int ssa_internal_hash_scalars(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_msgs,
                               const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len, size_t n);
@@ -449,20 +608,23 @@ static int run_host_slices(ssa_ctx *ctx, size_t n, size_t slice, F &&fn) {
     return rcs[0] ? rcs[0] : rcs[1];
 }
 
-// the messages of lanes [lo, lo + cnt) of a host batch as a batch of their own (an offset table is rebased)
-struct HostMsgSlice {
-    std::vector<uint64_t> off;
-    const uint8_t *msgs = nullptr;
-    const uint64_t *offp = nullptr;
-    HostMsgSlice(const uint8_t *all, const uint64_t *msg_off, size_t msg_stride, size_t lo, size_t cnt) {
-        if (msg_off) {
-            off.resize(cnt + 1);
-            for (size_t k = 0; k <= cnt; k++) off[k] = msg_off[lo + k] - msg_off[lo];
-            msgs = all ? all + msg_off[lo] : nullptr;
-            offp = off.data();
-        } else {
-            msgs = all ? all + lo * msg_stride : nullptr;
-        }
-    }
-};
-
+// run_host_slices for the counted forms: fn(c, lo, cnt, slice, nf) is the one-slice form on context c for the lanes
+// [lo, lo + cnt) of b (their own batch, slice), which writes its rejection count to *nf; the counts add up into
+// *n_fail_out.  A batch of one slice is handed over whole.
+template <class F>
+static int run_host_slices_counted(ssa_ctx *ctx, const HostBatch &b, size_t n, size_t slice, uint64_t *n_fail_out, F &&fn) {
+    if (n <= slice) return fn(ctx, (size_t)0, n, b, n_fail_out);
+    std::mutex mu;
+    uint64_t total = 0;
+    const int rc = run_host_slices(ctx, n, slice, [&](ssa_ctx *c, size_t lo, size_t cnt) {
+        std::vector<uint64_t> off;
+        uint64_t nf = 0;
+        const int r = fn(c, lo, cnt, b.slice(lo, cnt, off), &nf);
+        std::lock_guard<std::mutex> lock(mu);
+        total += nf;
+        return r;
+    });
+    if (rc) return rc;
+    if (n_fail_out) *n_fail_out = total;
+    return 0;
+}

@@ -404,18 +404,6 @@ static int derive_prep(ssa_ctx *ctx, const uint8_t *d_parents, size_t m, bool xp
     });
 }
 
-struct DeriveWipe {      // device copies of secrets do not outlive the call, whichever way it returns
-    ssa_ctx *ctx;
-    DevBuf *bufs[3];
-    size_t bytes[3];
-    bool sync;
-    ~DeriveWipe() {
-        for (int k = 0; k < 3; k++)
-            if (bufs[k] && bufs[k]->p && bytes[k]) (void)hipMemsetAsync(bufs[k]->p, 0, bytes[k] < bufs[k]->cap ? bytes[k] : bufs[k]->cap, ctx->stream);
-        if (sync) (void)hipStreamSynchronize(ctx->stream);
-    }
-};
-
 extern "C" int ssa_xprv_master_many_device(ssa_ctx *ctx, const uint8_t *d_seeds, size_t n, uint8_t *d_xprvs_out,
                                            uint8_t *d_status_out) {
     if (!ctx || n > SSA_MAX_BATCH || (n && (!d_seeds || !d_xprvs_out || !d_status_out))) return SSA_ERR_ARG;
@@ -431,16 +419,10 @@ extern "C" int ssa_xprv_master_many(ssa_ctx *ctx, const uint8_t *seeds, size_t n
                                     uint8_t *status_out) {
     if (!ctx || n > SSA_MAX_BATCH || (n && (!seeds || !xprvs_out || !status_out))) return SSA_ERR_ARG;
     if (n == 0) return 0;
-    HIP_TRY(hipSetDevice(ctx->device));
-    DeriveWipe wipe{ctx, {&ctx->st_sigs, &ctx->st_aux, nullptr}, {n * 32, n * 64, 0}, true};
-    const void *p;
-    if (int rc = stage_up(ctx, ctx->st_sigs, seeds, n * 32, &p)) return rc;
-    if (ctx->st_aux.reserve(n * 64) || ctx->st_status.reserve(n + 16)) return SSA_ERR_HIP;
-    if (int rc = ssa_xprv_master_many_device(ctx, (const u8 *)p, n, (u8 *)ctx->st_aux.p, (u8 *)ctx->st_status.p)) return rc;
-    HIP_TRY(hipMemcpyAsync(xprvs_out, ctx->st_aux.p, n * 64, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(status_out, ctx->st_status.p, n, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return 0;
+    HostCall hc(ctx);
+    const u8 *d_seeds = hc.in(ctx->st_sigs, seeds, n * 32, SECRET);
+    u8 *d_xprvs = hc.out(ctx->st_aux, xprvs_out, n * 64, 0, SECRET), *d_status = hc.out(ctx->st_status, status_out, n, 16);
+    return hc.finish([&] { return ssa_xprv_master_many_device(ctx, d_seeds, n, d_xprvs, d_status); });
 }
 
 extern "C" int ssa_xprv_derive_many_device(ssa_ctx *ctx, const uint8_t *d_parents, size_t m, const uint32_t *d_parent_idx,
@@ -450,7 +432,7 @@ extern "C" int ssa_xprv_derive_many_device(ssa_ctx *ctx, const uint8_t *d_parent
     if (int rc = derive_args(m, d_parents, d_indices, n, d_parent_idx, d_children_out, d_status_out)) return rc;
     if (n == 0) return 0;
     HIP_TRY(hipSetDevice(ctx->device));
-    DeriveWipe wipe{ctx, {&ctx->dv_recs, nullptr, nullptr}, {m * DRV_REC_WORDS * sizeof(u64), 0, 0}, false};
+    SecretWipe wipe{ctx, {{&ctx->dv_recs, m * DRV_REC_WORDS * sizeof(u64)}}};    // behind the launches that read them
     if (int rc = derive_prep(ctx, d_parents, m, false)) return rc;
     const int pub = (flags & SSA_FLAG_DERIVE_PUBLIC) ? 1 : 0;
     return timed_launch(ctx, "ssa_k_xprv_derive", [&] {
@@ -466,22 +448,15 @@ extern "C" int ssa_xprv_derive_many(ssa_ctx *ctx, const uint8_t *parents, size_t
     if (!ctx || (flags & ~SSA_FLAG_DERIVE_PUBLIC)) return SSA_ERR_ARG;
     if (int rc = derive_args(m, parents, indices, n, parent_idx, children_out, status_out)) return rc;
     if (n == 0) return 0;
-    HIP_TRY(hipSetDevice(ctx->device));
     const size_t len = (flags & SSA_FLAG_DERIVE_PUBLIC) ? 81 : 64;
-    DeriveWipe wipe{ctx, {&ctx->st_sigs, &ctx->st_aux, nullptr}, {m * 64, n * len, 0}, true};
-    const void *p_par, *p_idx, *p_pidx = nullptr;
-    if (int rc = stage_up(ctx, ctx->st_sigs, parents, m * 64, &p_par)) return rc;
-    if (int rc = stage_up(ctx, ctx->st_off, indices, n * 4, &p_idx)) return rc;
-    if (parent_idx)
-        if (int rc = stage_up(ctx, ctx->st_inf, parent_idx, n * 4, &p_pidx)) return rc;
-    if (ctx->st_aux.reserve(n * len) || ctx->st_status.reserve(n + 16)) return SSA_ERR_HIP;
-    if (int rc = ssa_xprv_derive_many_device(ctx, (const u8 *)p_par, m, (const uint32_t *)p_pidx, (const uint32_t *)p_idx,
-                                             n, flags, (u8 *)ctx->st_aux.p, (u8 *)ctx->st_status.p))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(children_out, ctx->st_aux.p, n * len, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(status_out, ctx->st_status.p, n, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return 0;
+    HostCall hc(ctx);
+    const u8 *d_par = hc.in(ctx->st_sigs, parents, m * 64, SECRET);
+    const uint32_t *d_idx = hc.in<uint32_t>(ctx->st_off, indices, n * 4),
+                   *d_pidx = parent_idx ? hc.in<uint32_t>(ctx->st_inf, parent_idx, n * 4) : nullptr;
+    u8 *d_children = hc.out(ctx->st_aux, children_out, n * len, 0, SECRET), *d_status = hc.out(ctx->st_status, status_out, n, 16);
+    return hc.finish([&] {
+        return ssa_xprv_derive_many_device(ctx, d_par, m, d_pidx, d_idx, n, flags, d_children, d_status);
+    });
 }
 
 extern "C" int ssa_xpub_derive_many_device(ssa_ctx *ctx, const uint8_t *d_parents, size_t m, const uint32_t *d_parent_idx,
@@ -505,25 +480,17 @@ extern "C" int ssa_xpub_derive_many(ssa_ctx *ctx, const uint8_t *parents, size_t
     if (!ctx) return SSA_ERR_ARG;
     if (int rc = derive_args(m, parents, indices, n, parent_idx, children_out, status_out)) return rc;
     if (n == 0) return 0;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const void *p_par, *p_idx, *p_pidx = nullptr;
-    if (int rc = stage_up(ctx, ctx->st_pks, parents, m * 81, &p_par)) return rc;
-    if (int rc = stage_up(ctx, ctx->st_off, indices, n * 4, &p_idx)) return rc;
-    if (parent_idx)
-        if (int rc = stage_up(ctx, ctx->st_inf, parent_idx, n * 4, &p_pidx)) return rc;
-    if (ctx->st_aux.reserve(n * 81) || ctx->st_status.reserve(n + 16) || (pks_out && ctx->st_aux2.reserve(n * 96)) ||
-        (pk_inf_out && ctx->st_msgs.reserve(n + 16)))
-        return SSA_ERR_HIP;
-    u8 *d_pks = pks_out ? (u8 *)ctx->st_aux2.p : nullptr, *d_inf = pk_inf_out ? (u8 *)ctx->st_msgs.p : nullptr;
-    if (int rc = ssa_xpub_derive_many_device(ctx, (const u8 *)p_par, m, (const uint32_t *)p_pidx, (const uint32_t *)p_idx, n,
-                                             (u8 *)ctx->st_aux.p, d_pks, d_inf, (u8 *)ctx->st_status.p))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(children_out, ctx->st_aux.p, n * 81, hipMemcpyDeviceToHost, ctx->stream));
-    if (pks_out) HIP_TRY(hipMemcpyAsync(pks_out, d_pks, n * 96, hipMemcpyDeviceToHost, ctx->stream));
-    if (pk_inf_out) HIP_TRY(hipMemcpyAsync(pk_inf_out, d_inf, n, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(status_out, ctx->st_status.p, n, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return 0;
+    HostCall hc(ctx);
+    const u8 *d_par = hc.in(ctx->st_pks, parents, m * 81);
+    const uint32_t *d_idx = hc.in<uint32_t>(ctx->st_off, indices, n * 4),
+                   *d_pidx = parent_idx ? hc.in<uint32_t>(ctx->st_inf, parent_idx, n * 4) : nullptr;
+    u8 *d_children = hc.out(ctx->st_aux, children_out, n * 81),
+       *d_pks = pks_out ? hc.out(ctx->st_aux2, pks_out, n * 96) : nullptr,
+       *d_inf = pk_inf_out ? hc.out(ctx->st_msgs, pk_inf_out, n, 16) : nullptr,
+       *d_status = hc.out(ctx->st_status, status_out, n, 16);
+    return hc.finish([&] {
+        return ssa_xpub_derive_many_device(ctx, d_par, m, d_pidx, d_idx, n, d_children, d_pks, d_inf, d_status);
+    });
 }
 
 extern "C" int ssa_debug_hmac_sha512(ssa_ctx *ctx, const uint8_t *key, size_t key_len, const uint8_t *msgs,
@@ -531,17 +498,14 @@ extern "C" int ssa_debug_hmac_sha512(ssa_ctx *ctx, const uint8_t *key, size_t ke
     if (!ctx || key_len > 256 || msg_len > 239 || n > SSA_MAX_BATCH) return SSA_ERR_ARG;
     if (n && (!out || (key_len && !key) || (msg_len && !msgs))) return SSA_ERR_ARG;
     if (n == 0) return 0;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const void *p_key, *p_msgs;
-    if (int rc = stage_up(ctx, ctx->st_pks, key_len ? key : nullptr, key_len, &p_key)) return rc;
-    if (int rc = stage_up(ctx, ctx->st_msgs, msg_len ? msgs : nullptr, n * msg_len, &p_msgs)) return rc;
-    if (ctx->st_aux.reserve(n * 64)) return SSA_ERR_HIP;
-    if (int rc = timed_launch(ctx, "ssa_k_hmac_sha512", [&] {
-            hipLaunchKernelGGL(ssa_k_hmac_sha512, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, (const u8 *)p_key,
-                               (u32)key_len, (const u8 *)p_msgs, (u32)msg_len, n, (u8 *)ctx->st_aux.p);
-        }))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(out, ctx->st_aux.p, n * 64, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return 0;
+    HostCall hc(ctx);
+    const u8 *d_key = hc.in(ctx->st_pks, key_len ? key : nullptr, key_len),
+             *d_msgs = hc.in(ctx->st_msgs, msg_len ? msgs : nullptr, n * msg_len);
+    u8 *d_out = hc.out(ctx->st_aux, out, n * 64);
+    return hc.finish([&] {
+        return timed_launch(ctx, "ssa_k_hmac_sha512", [&] {
+            hipLaunchKernelGGL(ssa_k_hmac_sha512, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, d_key, (u32)key_len,
+                               d_msgs, (u32)msg_len, n, d_out);
+        });
+    });
 }

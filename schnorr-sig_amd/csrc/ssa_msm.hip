@@ -1162,12 +1162,9 @@ static int msm_draw_coefficients(ssa_ctx *ctx, size_t n, const void **d_out) {
 extern "C" int ssa_debug_chacha20(ssa_ctx *ctx, const uint8_t key[32], const uint8_t nonce[12], uint32_t counter0,
                                   size_t n_blocks, uint8_t *out) {
     if (!ctx || !key || !nonce || (n_blocks && !out)) return SSA_ERR_ARG;
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (ctx->st_coeffs.reserve(n_blocks * 64 + 64)) return SSA_ERR_HIP;
-    if (int rc = msm_chacha20(ctx, key, nonce, counter0, n_blocks, ctx->st_coeffs.p)) return rc;
-    HIP_TRY(hipMemcpyAsync(out, ctx->st_coeffs.p, n_blocks * 64, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return 0;
+    HostCall hc(ctx);
+    u8 *d_out = hc.out(ctx->st_coeffs, out, n_blocks * 64, 64);
+    return hc.finish([&] { return msm_chacha20(ctx, key, nonce, counter0, n_blocks, d_out); });
 }
 
 static int msm_run(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_pk_inf,
@@ -1430,12 +1427,10 @@ static int msm_run_one(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks
     });
 }
 
-static int msm_host_one(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_inf, const uint8_t *msgs,
-                        const uint64_t *msg_off, size_t msg_stride, size_t msg_len, size_t n, const uint8_t *coeffs,
-                        int *verdict_out, uint64_t *out24);
-static int msm_host_sliced(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_inf, const uint8_t *msgs,
-                           const uint64_t *msg_off, size_t msg_stride, size_t msg_len, size_t n, const uint8_t *coeffs,
-                           int *verdict_out, uint64_t *out24);
+static int msm_host_one(ssa_ctx *ctx, const HostBatch &b, size_t n, const uint8_t *coeffs, int *verdict_out,
+                        uint64_t *out24);
+static int msm_host_sliced(ssa_ctx *ctx, const HostBatch &b, size_t n, const uint8_t *coeffs, int *verdict_out,
+                           uint64_t *out24);
 
 // One shard of a batch that spans several devices: stage the host buffers, run the MSM pipeline, return the shard's
 // 24-word partial record (left-hand point, sum s_i e_i, malformed flag) in host memory.
@@ -1451,9 +1446,10 @@ extern "C" int ssa_verify_batch_msm_partial(ssa_ctx *ctx, const uint8_t *sigs, c
         out24[23] = SSA_MSM_RECORD_MAGIC;    // the empty shard's record: identity, 0
         return 0;
     }
-    if (n > ctx->msm_slice)
-        return msm_host_sliced(ctx, sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len, n, coeffs, nullptr, out24);
-    return msm_host_one(ctx, sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len, n, coeffs, nullptr, out24);
+    if (int rc = check_host_offsets(msg_off, n)) return rc;
+    const HostBatch b{sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len};
+    return n > ctx->msm_slice ? msm_host_sliced(ctx, b, n, coeffs, nullptr, out24)
+                              : msm_host_one(ctx, b, n, coeffs, nullptr, out24);
 }
 
 // the device-buffer form: what one rank of a process-per-GPU job calls on its shard (the records then travel by
@@ -1558,15 +1554,12 @@ extern "C" int ssa_msm_combine_device(ssa_ctx *ctx, const uint64_t *d_parts24, s
 
 extern "C" int ssa_msm_combine(ssa_ctx *ctx, const uint64_t *parts24, size_t k) {
     if (!ctx || !parts24 || k == 0 || k > 4096) return SSA_ERR_ARG;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const void *d_parts;
-    if (int rc = stage_up(ctx, ctx->st_aux, parts24, k * SSA_MSM_PARTIAL_WORDS * sizeof(uint64_t), &d_parts)) return rc;
-    uint32_t *d_verdict = (uint32_t *)((char *)ctx->ws_fail.p + 32);
-    if (int rc = ssa_msm_combine_device(ctx, (const uint64_t *)d_parts, k, d_verdict)) return rc;
-    uint32_t v = SSA_MALFORMED;
-    HIP_TRY(hipMemcpyAsync(&v, d_verdict, sizeof v, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return (int)v;
+    HostCall hc(ctx);
+    const uint64_t *d_parts = hc.in<uint64_t>(ctx->st_aux, parts24, k * SSA_MSM_PARTIAL_WORDS * sizeof(uint64_t));
+    uint32_t v = SSA_MALFORMED, *d_verdict = (uint32_t *)((char *)ctx->ws_fail.p + 32);
+    hc.copy_back(&v, d_verdict, sizeof v);
+    const int rc = hc.finish([&] { return ssa_msm_combine_device(ctx, d_parts, k, d_verdict); });
+    return rc ? rc : (int)v;
 }
 
 extern "C" int ssa_verify_batch_msm(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_inf,
@@ -1574,12 +1567,13 @@ extern "C" int ssa_verify_batch_msm(ssa_ctx *ctx, const uint8_t *sigs, const uin
                                     size_t n, const uint8_t *coeffs) {
     if (!ctx || (n && (!sigs || !pks))) return SSA_ERR_ARG;
     if (int rc = check_msgs(msgs, msg_off, msg_stride, msg_len, n)) return rc;
+    if (int rc = check_host_offsets(msg_off, n)) return rc;
     if (n == 0) return SSA_OK;
     HIP_TRY(hipSetDevice(ctx->device));
+    const HostBatch b{sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len};
     int verdict = SSA_MALFORMED;
-    const int rc = n > ctx->msm_slice
-                       ? msm_host_sliced(ctx, sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len, n, coeffs, &verdict, nullptr)
-                       : msm_host_one(ctx, sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len, n, coeffs, &verdict, nullptr);
+    const int rc = n > ctx->msm_slice ? msm_host_sliced(ctx, b, n, coeffs, &verdict, nullptr)
+                                      : msm_host_one(ctx, b, n, coeffs, &verdict, nullptr);
     return rc ? rc : verdict;
 }
 
@@ -1587,109 +1581,49 @@ extern "C" int ssa_verify_batch_msm(ssa_ctx *ctx, const uint8_t *sigs, const uin
 // form -- staging sized for a slice, only the slice in flight pinned, on the context and its twin alternately -- each
 // reduced to its 24-word record in HOST memory, and the records combined like the shards of a multi-GPU batch
 // (src/batch.rs:98-129: one point and one scalar per part): a verdict, or the whole batch's own record.
-static int msm_host_sliced(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_inf, const uint8_t *msgs,
-                           const uint64_t *msg_off, size_t msg_stride, size_t msg_len, size_t n, const uint8_t *coeffs,
-                           int *verdict_out, uint64_t *out24) {
-    if (msg_off)
-        for (size_t i = 0; i < n; i++)
-            if (msg_off[i + 1] < msg_off[i] || msg_off[i + 1] - msg_off[i] > 0xffffffffull) return SSA_ERR_ARG;
+static int msm_host_sliced(ssa_ctx *ctx, const HostBatch &b, size_t n, const uint8_t *coeffs, int *verdict_out,
+                           uint64_t *out24) {
     const size_t slice = ctx->msm_slice, k = (n + slice - 1) / slice;
     if (k > 4096) return SSA_ERR_ARG;
     std::vector<uint64_t> recs(k * SSA_MSM_PARTIAL_WORDS, 0);
     int rc = run_host_slices(ctx, n, slice, [&](ssa_ctx *c, size_t lo, size_t cnt) {
-        const HostMsgSlice ms(msgs, msg_off, msg_stride, lo, cnt);
-        return msm_host_one(c, sigs + 81 * lo, pks + 96 * lo, pk_inf ? pk_inf + lo : nullptr, ms.msgs, ms.offp, msg_stride,
-                            msg_len, cnt, coeffs ? coeffs + 32 * lo : nullptr, nullptr,
+        std::vector<uint64_t> off;
+        return msm_host_one(c, b.slice(lo, cnt, off), cnt, coeffs ? coeffs + 32 * lo : nullptr, nullptr,
                             recs.data() + (lo / slice) * SSA_MSM_PARTIAL_WORDS);
     });
     if (rc) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const void *d_parts;
-    if (int r = stage_up(ctx, ctx->st_aux, recs.data(), recs.size() * sizeof(uint64_t), &d_parts)) return r;
-    uint32_t *d_verdict = (uint32_t *)((char *)ctx->ws_fail.p + 32);
-    if (out24 && ctx->st_aux2.reserve(SSA_MSM_PARTIAL_WORDS * sizeof(u64))) return SSA_ERR_HIP;
-    if (int r = msm_combine_records(ctx, (const u64 *)d_parts, k, out24 ? nullptr : d_verdict,
-                                    out24 ? (u64 *)ctx->st_aux2.p : nullptr, true))
+    HostCall hc(ctx);
+    const u64 *d_parts = hc.in<u64>(ctx->st_aux, recs.data(), recs.size() * sizeof(uint64_t));
+    uint32_t v = SSA_MALFORMED, *d_verdict = (uint32_t *)((char *)ctx->ws_fail.p + 32);
+    u64 *d_rec = out24 ? (u64 *)hc.out(ctx->st_aux2, out24, SSA_MSM_PARTIAL_WORDS * sizeof(u64)) : nullptr;
+    if (!out24) hc.copy_back(&v, d_verdict, sizeof v);
+    if (int r = hc.finish([&] { return msm_combine_records(ctx, d_parts, k, out24 ? nullptr : d_verdict, d_rec, true); }))
         return r;
-    uint32_t v = SSA_MALFORMED;
-    if (out24)
-        HIP_TRY(hipMemcpyAsync(out24, ctx->st_aux2.p, SSA_MSM_PARTIAL_WORDS * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
-    else
-        HIP_TRY(hipMemcpyAsync(&v, d_verdict, sizeof v, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
     if (verdict_out) *verdict_out = (int)v;
     return 0;
 }
 
 // ONE slice (n <= ctx->msm_slice) from host buffers: the verdict (out24 == nullptr) or the slice's 24-word record
-static int msm_host_one(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_inf, const uint8_t *msgs,
-                        const uint64_t *msg_off, size_t msg_stride, size_t msg_len, size_t n, const uint8_t *coeffs,
-                        int *verdict_out, uint64_t *out24) {
-    HIP_TRY(hipSetDevice(ctx->device));
-    uint32_t *d_verdict = out24 ? nullptr : (uint32_t *)((char *)ctx->ws_fail.p + 32);
-    u64 *d_rec = nullptr;
-    if (out24) {
-        if (ctx->st_aux2.reserve(SSA_MSM_PARTIAL_WORDS * sizeof(u64))) return SSA_ERR_HIP;
-        d_rec = (u64 *)ctx->st_aux2.p;
-    }
-    auto fetch = [&]() -> int {       // the result of the launches queued on ctx->stream
-        uint32_t v = SSA_MALFORMED;
-        if (out24)
-            HIP_TRY(hipMemcpyAsync(out24, d_rec, SSA_MSM_PARTIAL_WORDS * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
-        else
-            HIP_TRY(hipMemcpyAsync(&v, d_verdict, sizeof v, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (verdict_out) *verdict_out = (int)v;
-        return 0;
-    };
+static int msm_host_one(ssa_ctx *ctx, const HostBatch &b, size_t n, const uint8_t *coeffs, int *verdict_out,
+                        uint64_t *out24) {
+    HostCall hc(ctx);
+    uint32_t v = SSA_MALFORMED, *d_verdict = out24 ? nullptr : (uint32_t *)((char *)ctx->ws_fail.p + 32);
+    u64 *d_rec = out24 ? (u64 *)hc.out(ctx->st_aux2, nullptr, SSA_MSM_PARTIAL_WORDS * sizeof(u64)) : nullptr;
     // Scalar::random(rng) (src/batch.rs:75-78): caller-supplied 32-byte scalars, or (coeffs == NULL) 128-bit
-    // coefficients drawn on the device from a ChaCha20 stream keyed with getrandom(2)
-    if (n >= ctx->pipeline_min_n && ctx->pipeline_chunks > 1) {
-        // large batch: uploads pinned in place and chunked, the hashes (62 % of this form) run behind them
-        PipelinedInputs pin;      // its destructor drains the side streams on every error return below
-        bool used = false;
-        if (!coeffs || ctx->pin_coeffs.reserve(n * 32) == 0) {
-            if (coeffs && ctx->st_coeffs.reserve(n * 32)) return SSA_ERR_HIP;
-            if (int rc = pipelined_upload_hash(ctx, sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len, n, pin, &used))
-                return rc;
-            if (used) {
-                const void *pc = nullptr;
-                if (coeffs) {
-                    // behind the chunk copies on the copy stream; ctx->stream waits for this copy explicitly
-                    host_copy(ctx->pin_coeffs.p, coeffs, n * 32);
-                    HIP_TRY(hipMemcpyAsync(ctx->st_coeffs.p, ctx->pin_coeffs.p, n * 32, hipMemcpyHostToDevice, ctx->copy_stream));
-                    HIP_TRY(hipEventRecord(ctx->pipe_start, ctx->copy_stream));
-                    HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->pipe_start, 0));
-                    pc = ctx->st_coeffs.p;
-                }
-                if (int rc = msm_run(ctx, pin.s.sigs, pin.s.pks, pin.s.inf, pin.s.msgs, pin.s.off, msg_stride, msg_len, n,
-                                     (const u8 *)pc, 32, d_verdict, d_rec, true))
-                    return rc;
-                if (int rc = fetch()) return rc;
-                pin.done();
-                return 0;
-            }
-        }
-    }
-    StagedInputs s;
-    const void *p;
-    if (int rc = stage_up(ctx, ctx->st_sigs, sigs, n * 81, &p)) return rc;
-    s.sigs = (const u8 *)p;
-    if (int rc = stage_up(ctx, ctx->st_pks, pks, n * 96, &p)) return rc;
-    s.pks = (const u8 *)p;
-    if (pk_inf) {
-        if (int rc = stage_up(ctx, ctx->st_inf, pk_inf, n, &p)) return rc;
-        s.inf = (const u8 *)p;
-    }
-    if (int rc = stage_msgs(ctx, msgs, msg_off, msg_stride, msg_len, n, s)) return rc;
-    p = nullptr;
-    if (coeffs) {
-        if (int rc = stage_up(ctx, ctx->st_coeffs, coeffs, n * 32, &p)) return rc;
-    }
-    if (int rc = msm_run(ctx, s.sigs, s.pks, s.inf, s.msgs, s.off, msg_stride, msg_len, n, (const u8 *)p, 32, d_verdict,
-                         d_rec, false))
+    // coefficients drawn on the device from a ChaCha20 stream keyed with getrandom(2).  A large batch: uploads in
+    // chunks, the hashes (62 % of this form) behind them.
+    PipelinedInputs pin;      // its destructor drains the side streams on every error return
+    const StagedInputs s = slice_inputs(hc, pin, b, n, coeffs, true, false);
+    if (out24) hc.copy_back(out24, d_rec, SSA_MSM_PARTIAL_WORDS * sizeof(u64));
+    else hc.copy_back(&v, d_verdict, sizeof v);
+    if (int rc = hc.finish([&] {
+            return msm_run(ctx, s.sigs, s.pks, s.inf, s.msgs, s.off, b.msg_stride, b.msg_len, n, s.coeffs, 32, d_verdict, d_rec,
+                           s.hashed);
+        }))
         return rc;
-    return fetch();
+    pin.done();
+    if (verdict_out) *verdict_out = (int)v;
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1840,66 +1774,24 @@ extern "C" int ssa_verify_batch_screened_device(ssa_ctx *ctx, const uint8_t *d_s
 }
 
 // ONE slice from host buffers (the staging of msm_host_one): statuses into status_out[0, n), *nf the count
-static int screen_host_one(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_inf, const uint8_t *msgs,
-                           const uint64_t *msg_off, size_t msg_stride, size_t msg_len, size_t n, const uint8_t *coeffs,
-                           uint8_t *status_out, uint64_t *nf) {
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (ctx->st_status.reserve(n + 16)) return SSA_ERR_HIP;
-    unsigned long long *d_fail = (unsigned long long *)ctx->ws_fail.p;
-    auto fetch = [&]() -> int {
-        if (int rc = screen_count(ctx, (const u8 *)ctx->st_status.p, n, d_fail)) return rc;
-        HIP_TRY(hipMemcpyAsync(status_out, ctx->st_status.p, n, hipMemcpyDeviceToHost, ctx->stream));
-        unsigned long long v = 0;
-        HIP_TRY(hipMemcpyAsync(&v, d_fail, sizeof v, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        *nf = v;
-        return 0;
-    };
-    if (n >= ctx->pipeline_min_n && ctx->pipeline_chunks > 1) {
-        // large slice: uploads in chunks with the hashes behind them (msm_host_one)
-        PipelinedInputs pin;      // its destructor drains the side streams on every error return below
-        bool used = false;
-        if (!coeffs || ctx->pin_coeffs.reserve(n * 32) == 0) {
-            if (coeffs && ctx->st_coeffs.reserve(n * 32)) return SSA_ERR_HIP;
-            if (int rc = pipelined_upload_hash(ctx, sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len, n, pin, &used))
-                return rc;
-            if (used) {
-                const void *pc = nullptr;
-                if (coeffs) {
-                    host_copy(ctx->pin_coeffs.p, coeffs, n * 32);
-                    HIP_TRY(hipMemcpyAsync(ctx->st_coeffs.p, ctx->pin_coeffs.p, n * 32, hipMemcpyHostToDevice, ctx->copy_stream));
-                    HIP_TRY(hipEventRecord(ctx->pipe_start, ctx->copy_stream));
-                    HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->pipe_start, 0));
-                    pc = ctx->st_coeffs.p;
-                }
-                if (int rc = screen_slice(ctx, pin.s.sigs, pin.s.pks, pin.s.inf, pin.s.msgs, pin.s.off, msg_stride, msg_len, n,
-                                          (const u8 *)pc, 32, (const u64 *)ctx->ws_h.p, (u8 *)ctx->st_status.p))
-                    return rc;
-                if (int rc = fetch()) return rc;
-                pin.done();
-                return 0;
-            }
-        }
-    }
-    StagedInputs s;
-    const void *p;
-    if (int rc = stage_up(ctx, ctx->st_sigs, sigs, n * 81, &p)) return rc;
-    s.sigs = (const u8 *)p;
-    if (int rc = stage_up(ctx, ctx->st_pks, pks, n * 96, &p)) return rc;
-    s.pks = (const u8 *)p;
-    if (pk_inf) {
-        if (int rc = stage_up(ctx, ctx->st_inf, pk_inf, n, &p)) return rc;
-        s.inf = (const u8 *)p;
-    }
-    if (int rc = stage_msgs(ctx, msgs, msg_off, msg_stride, msg_len, n, s)) return rc;
-    p = nullptr;
-    if (coeffs) {
-        if (int rc = stage_up(ctx, ctx->st_coeffs, coeffs, n * 32, &p)) return rc;
-    }
-    if (int rc = screen_slice(ctx, s.sigs, s.pks, s.inf, s.msgs, s.off, msg_stride, msg_len, n, (const u8 *)p, 32, nullptr,
-                              (u8 *)ctx->st_status.p))
+static int screen_host_one(ssa_ctx *ctx, const HostBatch &b, size_t n, const uint8_t *coeffs, uint8_t *status_out,
+                           uint64_t *nf) {
+    HostCall hc(ctx);
+    PipelinedInputs pin;      // its destructor drains the side streams on every error return
+    const StagedInputs s = slice_inputs(hc, pin, b, n, coeffs, true, false);
+    u8 *d_status = hc.out(ctx->st_status, status_out, n, 16);
+    unsigned long long v = 0, *d_fail = (unsigned long long *)ctx->ws_fail.p;
+    hc.copy_back(&v, d_fail, sizeof v);
+    if (int rc = hc.finish([&] {
+            if (int r = screen_slice(ctx, s.sigs, s.pks, s.inf, s.msgs, s.off, b.msg_stride, b.msg_len, n, s.coeffs, 32,
+                                     s.hashed ? (const u64 *)ctx->ws_h.p : nullptr, d_status))
+                return r;
+            return screen_count(ctx, d_status, n, d_fail);
+        }))
         return rc;
-    return fetch();
+    pin.done();
+    if (nf) *nf = v;
+    return 0;
 }
 
 extern "C" int ssa_verify_batch_screened(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_inf,
@@ -1907,27 +1799,17 @@ extern "C" int ssa_verify_batch_screened(ssa_ctx *ctx, const uint8_t *sigs, cons
                                          size_t n, const uint8_t *coeffs, uint8_t *status_out, uint64_t *n_fail_out) {
     if (!ctx || (n && (!sigs || !pks || !status_out))) return SSA_ERR_ARG;
     if (int rc = check_msgs(msgs, msg_off, msg_stride, msg_len, n)) return rc;
-    if (msg_off)
-        for (size_t i = 0; i < n; i++)
-            if (msg_off[i + 1] < msg_off[i] || msg_off[i + 1] - msg_off[i] > 0xffffffffull) return SSA_ERR_ARG;
+    if (int rc = check_host_offsets(msg_off, n)) return rc;
     if (n_fail_out) *n_fail_out = 0;
     if (n == 0) return 0;
     HIP_TRY(hipSetDevice(ctx->device));
     if (n <= ctx->msm_small_max)
         return ssa_verify_many(ctx, sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len, n, SSA_FLAG_SIG_FLAG_BYTE,
                                status_out, n_fail_out);
-    std::mutex mu;
-    uint64_t total = 0;
-    const int rc = run_host_slices(ctx, n, ctx->msm_slice, [&](ssa_ctx *c, size_t lo, size_t cnt) {
-        const HostMsgSlice ms(msgs, msg_off, msg_stride, lo, cnt);
-        uint64_t nf = 0;
-        const int r = screen_host_one(c, sigs + 81 * lo, pks + 96 * lo, pk_inf ? pk_inf + lo : nullptr, ms.msgs, ms.offp,
-                                      msg_stride, msg_len, cnt, coeffs ? coeffs + 32 * lo : nullptr, status_out + lo, &nf);
-        std::lock_guard<std::mutex> lock(mu);
-        total += nf;
-        return r;
-    });
-    if (rc) return rc;
-    if (n_fail_out) *n_fail_out = total;
-    return 0;
+    const HostBatch b{sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len};
+    return run_host_slices_counted(ctx, b, n, ctx->msm_slice, n_fail_out,
+                                   [&](ssa_ctx *c, size_t lo, size_t cnt, const HostBatch &s, uint64_t *nf) {
+                                       return screen_host_one(c, s, cnt, coeffs ? coeffs + 32 * lo : nullptr,
+                                                              status_out + lo, nf);
+                                   });
 }

@@ -153,7 +153,7 @@ template <class F>
 static int rng_draw_slices(ssa_ctx *ctx, size_t n, F &&consume) {
     const size_t slice = ctx->lane_slice < n ? ctx->lane_slice : n;
     if (ctx->rng_scratch.reserve(slice * 32)) return SSA_ERR_HIP;
-    DeriveWipe wipe{ctx, {&ctx->rng_scratch, &ctx->rng_seed, nullptr}, {slice * 32, 64, 0}, false};
+    SecretWipe wipe{ctx, {{&ctx->rng_scratch, slice * 32}, {&ctx->rng_seed, 64}}};
     if (int rc = rng_stage_seed(ctx)) return rc;
     for (size_t lo = 0; lo < n; lo += slice) {
         const size_t cnt = n - lo < slice ? n - lo : slice;
@@ -196,23 +196,16 @@ extern "C" int ssa_keygen_sign_many_rng(ssa_ctx *ctx, const uint8_t *sks, const 
     const bool keyed = (flags & SSA_FLAG_SIGN_KEYED) != 0;
     if (n && (!sks || !sigs_out || (!keyed && !pks_out))) return SSA_ERR_ARG;
     if (int rc = check_msgs(msgs, msg_off, msg_stride, msg_len, n)) return rc;
+    if (int rc = check_host_offsets(msg_off, n)) return rc;
     if (n == 0) return 0;
     if (!scalars_canonical_nonzero(sks, n)) return SSA_ERR_ARG;
-    HIP_TRY(hipSetDevice(ctx->device));
-    DeriveWipe wipe{ctx, {&ctx->st_sigs, nullptr, nullptr}, {n * 32, 0, 0}, true};     // the staged keys
-    StagedInputs s;
-    const void *p_sk;
-    if (int rc = stage_up(ctx, ctx->st_sigs, sks, n * 32, &p_sk)) return rc;
-    if (int rc = stage_msgs(ctx, msgs, msg_off, msg_stride, msg_len, n, s)) return rc;
-    const size_t sig_bytes = keyed ? 130 : 81;
-    if (ctx->st_aux.reserve(n * 96) || ctx->st_aux2.reserve(n * sig_bytes)) return SSA_ERR_HIP;
-    if (int rc = ssa_keygen_sign_many_rng_device(ctx, (const u8 *)p_sk, s.msgs, s.off, msg_stride, msg_len, n, flags,
-                                                 (u8 *)ctx->st_aux.p, (u8 *)ctx->st_aux2.p))
-        return rc;
-    if (pks_out) HIP_TRY(hipMemcpyAsync(pks_out, ctx->st_aux.p, n * 96, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(sigs_out, ctx->st_aux2.p, n * sig_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return 0;
+    HostCall hc(ctx);
+    const u8 *d_sks = hc.in(ctx->st_sigs, sks, n * 32, SECRET);
+    const MsgView mv = hc.msgs(msgs, msg_off, msg_stride, msg_len, n);
+    u8 *d_pks = hc.out(ctx->st_aux, pks_out, n * 96), *d_sigs = hc.out(ctx->st_aux2, sigs_out, n * (keyed ? 130 : 81));
+    return hc.finish([&] {
+        return ssa_keygen_sign_many_rng_device(ctx, d_sks, mv.msgs, mv.off, msg_stride, msg_len, n, flags, d_pks, d_sigs);
+    });
 }
 
 extern "C" int ssa_sign_many_indexed_rng_device(ssa_ctx *ctx, ssa_signer_set *ss, const uint32_t *d_key_idx,
@@ -239,24 +232,18 @@ extern "C" int ssa_sign_many_indexed_rng(ssa_ctx *ctx, ssa_signer_set *ss, const
     if (!ctx || !ss || ss->ctx != ctx || (flags & ~(SSA_FLAG_SIGN_CT | SSA_FLAG_SIGN_KEYED))) return SSA_ERR_ARG;
     if (n && (!key_idx || !sigs_out)) return SSA_ERR_ARG;
     if (int rc = check_msgs(msgs, msg_off, msg_stride, msg_len, n)) return rc;
+    if (int rc = check_host_offsets(msg_off, n)) return rc;
     if (n == 0) return 0;
     for (size_t i = 0; i < n; i++)                 // (indices are public)
         if (key_idx[i] >= ss->m || ss->host_status[key_idx[i]] != ST_OK) return SSA_ERR_ARG;
-    HIP_TRY(hipSetDevice(ctx->device));
-    StagedInputs s;
-    const void *p_idx;
-    if (int rc = stage_up(ctx, ctx->st_inf, key_idx, n * sizeof(uint32_t), &p_idx)) return rc;
-    if (int rc = stage_msgs(ctx, msgs, msg_off, msg_stride, msg_len, n, s)) return rc;
-    const size_t sig_bytes = (flags & SSA_FLAG_SIGN_KEYED) ? 130 : 81;
-    if (ctx->st_aux2.reserve(n * sig_bytes)) return SSA_ERR_HIP;
-    if (int rc = ssa_sign_many_indexed_rng_device(ctx, ss, (const uint32_t *)p_idx, s.msgs, s.off, msg_stride, msg_len, n,
-                                                  flags, (u8 *)ctx->st_aux2.p, nullptr)) {
-        (void)hipStreamSynchronize(ctx->stream);
-        return rc;
-    }
-    HIP_TRY(hipMemcpyAsync(sigs_out, ctx->st_aux2.p, n * sig_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return 0;
+    HostCall hc(ctx);
+    const uint32_t *d_idx = hc.in<uint32_t>(ctx->st_inf, key_idx, n * sizeof(uint32_t));
+    const MsgView mv = hc.msgs(msgs, msg_off, msg_stride, msg_len, n);
+    u8 *d_sigs = hc.out(ctx->st_aux2, sigs_out, n * ((flags & SSA_FLAG_SIGN_KEYED) ? 130 : 81));
+    return hc.finish([&] {
+        return ssa_sign_many_indexed_rng_device(ctx, ss, d_idx, mv.msgs, mv.off, msg_stride, msg_len, n, flags, d_sigs,
+                                                nullptr);
+    });
 }
 
 // KeyPair::new(rng) for m key pairs: the keys are drawn straight into the set (slice by slice through the scratch),
@@ -285,11 +272,9 @@ extern "C" int ssa_signer_set_generate(ssa_ctx *ctx, size_t m, ssa_signer_set **
 
 extern "C" int ssa_signer_set_secret_keys(ssa_signer_set *ss, uint8_t *sks_out) {
     if (!ss || !ss->ctx || !sks_out) return SSA_ERR_ARG;
-    ssa_ctx *ctx = ss->ctx;
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipMemcpyAsync(sks_out, ss->sks.p, ss->m * 32, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return 0;
+    HostCall hc(ss->ctx);
+    hc.copy_back(sks_out, ss->sks.p, ss->m * 32);
+    return hc.finish([] { return 0; });
 }
 
 extern "C" int ssa_debug_pin_rng(ssa_ctx *ctx, const uint8_t *seed) {
@@ -303,16 +288,12 @@ extern "C" int ssa_debug_pin_rng(ssa_ctx *ctx, const uint8_t *seed) {
 extern "C" int ssa_debug_draw_scalars(ssa_ctx *ctx, const uint8_t *blocks, size_t n, uint8_t *out) {
     if (!ctx || (n && (!blocks || !out)) || n > SSA_MAX_BATCH) return SSA_ERR_ARG;
     if (n == 0) return 0;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const void *p;
-    if (int rc = stage_up(ctx, ctx->st_aux, blocks, n * 128, &p)) return rc;
-    if (ctx->st_aux2.reserve(n * 32)) return SSA_ERR_HIP;
-    if (int rc = timed_launch(ctx, "ssa_k_draw_wide", [&] {
-            hipLaunchKernelGGL(ssa_k_draw_wide, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, (const u8 *)p, n,
-                               (u8 *)ctx->st_aux2.p);
-        }))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(out, ctx->st_aux2.p, n * 32, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return 0;
+    HostCall hc(ctx);
+    const u8 *d_blocks = hc.in(ctx->st_aux, blocks, n * 128);
+    u8 *d_out = hc.out(ctx->st_aux2, out, n * 32);
+    return hc.finish([&] {
+        return timed_launch(ctx, "ssa_k_draw_wide", [&] {
+            hipLaunchKernelGGL(ssa_k_draw_wide, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, d_blocks, n, d_out);
+        });
+    });
 }

@@ -509,18 +509,10 @@ extern "C" int ssa_compress_many(ssa_ctx *ctx, const uint8_t *pks, const uint8_t
                                  uint8_t *status_out) {
     if (!ctx || (n && (!pks || !out))) return SSA_ERR_ARG;
     if (n == 0) return 0;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const void *p, *pi = nullptr;
-    if (int rc = stage_up(ctx, ctx->st_pks, pks, n * 96, &p)) return rc;
-    if (pk_inf)
-        if (int rc = stage_up(ctx, ctx->st_inf, pk_inf, n, &pi)) return rc;
-    if (ctx->st_aux.reserve(n * 49) || ctx->st_status.reserve(n + 16)) return SSA_ERR_HIP;
-    if (int rc = ssa_compress_many_device(ctx, (const u8 *)p, (const u8 *)pi, n, (u8 *)ctx->st_aux.p, (u8 *)ctx->st_status.p))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(out, ctx->st_aux.p, n * 49, hipMemcpyDeviceToHost, ctx->stream));
-    if (status_out) HIP_TRY(hipMemcpyAsync(status_out, ctx->st_status.p, n, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return 0;
+    HostCall hc(ctx);
+    const u8 *d_pks = hc.in(ctx->st_pks, pks, n * 96), *d_inf = pk_inf ? hc.in(ctx->st_inf, pk_inf, n) : nullptr;
+    u8 *d_out = hc.out(ctx->st_aux, out, n * 49), *d_status = hc.out(ctx->st_status, status_out, n, 16);
+    return hc.finish([&] { return ssa_compress_many_device(ctx, d_pks, d_inf, n, d_out, d_status); });
 }
 
 // secret keys and nonces are canonical non-zero scalars: PrivateKey::new / Scalar::random never yield 0 or a value >= q
@@ -547,22 +539,10 @@ extern "C" int ssa_pubkey_many(ssa_ctx *ctx, const uint8_t *sks, size_t n, uint8
     if (!ctx || (n && (!sks || !pks_out)) || n > SSA_MAX_BATCH) return SSA_ERR_ARG;
     if (n == 0) return 0;
     if (!scalars_canonical_nonzero(sks, n)) return SSA_ERR_ARG;
-    HIP_TRY(hipSetDevice(ctx->device));
-    struct Wipe {      // the staged secrets do not outlive the call, whichever way it returns
-        ssa_ctx *ctx;
-        size_t bytes;
-        ~Wipe() {
-            if (ctx->st_sigs.p && ctx->st_sigs.cap >= bytes) (void)hipMemsetAsync(ctx->st_sigs.p, 0, bytes, ctx->stream);
-            (void)hipStreamSynchronize(ctx->stream);
-        }
-    } wipe{ctx, n * 32};
-    const void *p_sk;
-    if (int rc = stage_up(ctx, ctx->st_sigs, sks, n * 32, &p_sk)) return rc;
-    if (ctx->st_aux.reserve(n * 96)) return SSA_ERR_HIP;
-    if (int rc = ssa_pubkey_many_device(ctx, (const u8 *)p_sk, n, (u8 *)ctx->st_aux.p)) return rc;
-    HIP_TRY(hipMemcpyAsync(pks_out, ctx->st_aux.p, n * 96, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return 0;
+    HostCall hc(ctx);
+    const u8 *d_sks = hc.in(ctx->st_sigs, sks, n * 32, SECRET);
+    u8 *d_pks = hc.out(ctx->st_aux, pks_out, n * 96);
+    return hc.finish([&] { return ssa_pubkey_many_device(ctx, d_sks, n, d_pks); });
 }
 
 extern "C" int ssa_keygen_sign_many_ex(ssa_ctx *ctx, const uint8_t *sks, const uint8_t *nonces, const uint8_t *msgs,
@@ -572,33 +552,17 @@ extern "C" int ssa_keygen_sign_many_ex(ssa_ctx *ctx, const uint8_t *sks, const u
     const bool keyed = (flags & SSA_FLAG_SIGN_KEYED) != 0;
     if (n && (!sks || !nonces || !sigs_out || (!keyed && !pks_out))) return SSA_ERR_ARG;
     if (int rc = check_msgs(msgs, msg_off, msg_stride, msg_len, n)) return rc;
+    if (int rc = check_host_offsets(msg_off, n)) return rc;
     if (n == 0) return 0;
     if (!scalars_canonical_nonzero(sks, n) || !scalars_canonical_nonzero(nonces, n)) return SSA_ERR_ARG;
-    HIP_TRY(hipSetDevice(ctx->device));
-    // the staged secrets do not outlive the call, whichever way it returns
-    struct Wipe {
-        ssa_ctx *ctx;
-        size_t bytes;
-        ~Wipe() {
-            if (ctx->st_sigs.p && ctx->st_sigs.cap >= bytes) (void)hipMemsetAsync(ctx->st_sigs.p, 0, bytes, ctx->stream);
-            if (ctx->st_pks.p && ctx->st_pks.cap >= bytes) (void)hipMemsetAsync(ctx->st_pks.p, 0, bytes, ctx->stream);
-            (void)hipStreamSynchronize(ctx->stream);
-        }
-    } wipe{ctx, n * 32};
-    StagedInputs s;
-    const void *p_sk, *p_nonce;
-    if (int rc = stage_up(ctx, ctx->st_sigs, sks, n * 32, &p_sk)) return rc;
-    if (int rc = stage_up(ctx, ctx->st_pks, nonces, n * 32, &p_nonce)) return rc;
-    if (int rc = stage_msgs(ctx, msgs, msg_off, msg_stride, msg_len, n, s)) return rc;
-    const size_t sig_bytes = keyed ? 130 : 81;
-    if (ctx->st_aux.reserve(n * 96) || ctx->st_aux2.reserve(n * sig_bytes)) return SSA_ERR_HIP;
-    if (int rc = ssa_keygen_sign_many_ex_device(ctx, (const u8 *)p_sk, (const u8 *)p_nonce, s.msgs, s.off, msg_stride,
-                                                msg_len, n, flags, (u8 *)ctx->st_aux.p, (u8 *)ctx->st_aux2.p))
-        return rc;
-    if (pks_out) HIP_TRY(hipMemcpyAsync(pks_out, ctx->st_aux.p, n * 96, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(sigs_out, ctx->st_aux2.p, n * sig_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return 0;
+    HostCall hc(ctx);
+    const u8 *d_sks = hc.in(ctx->st_sigs, sks, n * 32, SECRET), *d_nonces = hc.in(ctx->st_pks, nonces, n * 32, SECRET);
+    const MsgView mv = hc.msgs(msgs, msg_off, msg_stride, msg_len, n);
+    u8 *d_pks = hc.out(ctx->st_aux, pks_out, n * 96), *d_sigs = hc.out(ctx->st_aux2, sigs_out, n * (keyed ? 130 : 81));
+    return hc.finish([&] {
+        return ssa_keygen_sign_many_ex_device(ctx, d_sks, d_nonces, mv.msgs, mv.off, msg_stride, msg_len, n, flags, d_pks,
+                                              d_sigs);
+    });
 }
 
 // hierarchical key derivation (reference src/derivation.rs): SHA-512 / HMAC and the derivation kernels and entry points
@@ -705,11 +669,9 @@ extern "C" int ssa_signer_set_create(ssa_ctx *ctx, const uint8_t *sks, size_t m,
     if (!ctx || !out || !sks || m == 0 || m > SSA_MAX_BATCH) return SSA_ERR_ARG;
     *out = nullptr;
     if (!scalars_canonical_nonzero(sks, m)) return SSA_ERR_ARG;
-    HIP_TRY(hipSetDevice(ctx->device));
-    DeriveWipe wipe{ctx, {&ctx->st_sigs, nullptr, nullptr}, {m * 32, 0, 0}, true};   // the staged keys do not outlive the call
-    const void *p;
-    if (int rc = stage_up(ctx, ctx->st_sigs, sks, m * 32, &p)) return rc;
-    return ssa_signer_set_create_device(ctx, (const u8 *)p, 32, m, out);
+    HostCall hc(ctx);
+    const u8 *d_sks = hc.in(ctx->st_sigs, sks, m * 32, SECRET);
+    return hc.finish([&] { return ssa_signer_set_create_device(ctx, d_sks, 32, m, out); });
 }
 
 extern "C" int ssa_signer_set_status(ssa_signer_set *ss, uint8_t *status_out) {
@@ -720,12 +682,10 @@ extern "C" int ssa_signer_set_status(ssa_signer_set *ss, uint8_t *status_out) {
 
 extern "C" int ssa_signer_set_public_keys(ssa_signer_set *ss, uint8_t *pks96_out, uint8_t *pks49_out) {
     if (!ss || !ss->ctx) return SSA_ERR_ARG;
-    ssa_ctx *ctx = ss->ctx;
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (pks96_out) HIP_TRY(hipMemcpyAsync(pks96_out, ss->pks.p, ss->m * 96, hipMemcpyDeviceToHost, ctx->stream));
-    if (pks49_out) HIP_TRY(hipMemcpyAsync(pks49_out, ss->cpks.p, ss->m * 49, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return 0;
+    HostCall hc(ss->ctx);
+    if (pks96_out) hc.copy_back(pks96_out, ss->pks.p, ss->m * 96);
+    if (pks49_out) hc.copy_back(pks49_out, ss->cpks.p, ss->m * 49);
+    return hc.finish([] { return 0; });
 }
 
 extern "C" int ssa_sign_many_indexed_device(ssa_ctx *ctx, ssa_signer_set *ss, const uint32_t *d_key_idx,
@@ -756,25 +716,20 @@ extern "C" int ssa_sign_many_indexed(ssa_ctx *ctx, ssa_signer_set *ss, const uin
     if (!ctx || !ss || ss->ctx != ctx || (flags & ~(SSA_FLAG_SIGN_CT | SSA_FLAG_SIGN_KEYED))) return SSA_ERR_ARG;
     if (n && (!key_idx || !nonces || !sigs_out)) return SSA_ERR_ARG;
     if (int rc = check_msgs(msgs, msg_off, msg_stride, msg_len, n)) return rc;
+    if (int rc = check_host_offsets(msg_off, n)) return rc;
     if (n == 0) return 0;
     for (size_t i = 0; i < n; i++)                 // (indices are public)
         if (key_idx[i] >= ss->m || ss->host_status[key_idx[i]] != ST_OK) return SSA_ERR_ARG;
     if (!scalars_canonical_nonzero(nonces, n)) return SSA_ERR_ARG;
-    HIP_TRY(hipSetDevice(ctx->device));
-    DeriveWipe wipe{ctx, {&ctx->st_pks, nullptr, nullptr}, {n * 32, 0, 0}, true};     // the staged nonces
-    StagedInputs s;
-    const void *p_nonce, *p_idx;
-    if (int rc = stage_up(ctx, ctx->st_pks, nonces, n * 32, &p_nonce)) return rc;
-    if (int rc = stage_up(ctx, ctx->st_inf, key_idx, n * sizeof(uint32_t), &p_idx)) return rc;
-    if (int rc = stage_msgs(ctx, msgs, msg_off, msg_stride, msg_len, n, s)) return rc;
-    const size_t sig_bytes = (flags & SSA_FLAG_SIGN_KEYED) ? 130 : 81;
-    if (ctx->st_aux2.reserve(n * sig_bytes)) return SSA_ERR_HIP;
-    if (int rc = ssa_sign_many_indexed_device(ctx, ss, (const uint32_t *)p_idx, (const u8 *)p_nonce, s.msgs, s.off,
-                                              msg_stride, msg_len, n, flags, (u8 *)ctx->st_aux2.p, nullptr))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(sigs_out, ctx->st_aux2.p, n * sig_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return 0;
+    HostCall hc(ctx);
+    const u8 *d_nonces = hc.in(ctx->st_pks, nonces, n * 32, SECRET);
+    const uint32_t *d_idx = hc.in<uint32_t>(ctx->st_inf, key_idx, n * sizeof(uint32_t));
+    const MsgView mv = hc.msgs(msgs, msg_off, msg_stride, msg_len, n);
+    u8 *d_sigs = hc.out(ctx->st_aux2, sigs_out, n * ((flags & SSA_FLAG_SIGN_KEYED) ? 130 : 81));
+    return hc.finish([&] {
+        return ssa_sign_many_indexed_device(ctx, ss, d_idx, d_nonces, mv.msgs, mv.off, msg_stride, msg_len, n, flags, d_sigs,
+                                            nullptr);
+    });
 }
 
 // Scalar::random(rng) on the device: the _rng signers, ssa_signer_set_generate and their test hooks

@@ -157,6 +157,22 @@ def test_xpub_children(engine, one_parent):
     for k in list(soft[:3]) + random.Random(2).sample(list(soft[3:]), 9):
         p, c = dm.derive_normal_public(pk, cc, int(idx[k]))
         assert got[k].tobytes() == dm.xpub_bytes(p, c), k
+    # the context's workspace count includes the per-parent records (384 B each), the one context buffer the device
+    # form reserves (no constant-time table on the public side, no staging)
+    import torch
+    dev = torch.device("cuda", 0)
+    m = 2 ** 16
+    eng = ssa.Engine(0)
+    try:
+        d_par = torch.from_numpy(np.tile(xpub, (m, 1))).to(dev)
+        d_idx = torch.arange(m, dtype=torch.int32, device=dev)
+        d_out, d_st = (torch.empty(shape, dtype=torch.uint8, device=dev) for shape in ((m, 81), (m,)))
+        before = eng.info()["workspace_bytes"]
+        eng.xpub_derive_many_device(d_par.data_ptr(), m, d_idx.data_ptr(), m, d_out.data_ptr(), d_st.data_ptr())
+        eng.sync()
+        assert eng.info()["workspace_bytes"] - before >= m * 384
+    finally:
+        eng.close()
 
 
 # ---- 5. the pinned case ---------------------------------------------------------------------------------------------
