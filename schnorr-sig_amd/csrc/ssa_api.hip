@@ -548,11 +548,11 @@ extern "C" int ssa_hash_message_many_device(ssa_ctx *ctx, const uint8_t *d_sigs,
                                             const uint8_t *d_msgs, const uint64_t *d_msg_off,
                                             size_t msg_stride, size_t msg_len, size_t n,
                                             uint8_t *d_digests_out) {
+    const MsgView mv{d_msgs, d_msg_off, msg_stride, msg_len};
     if (!ctx || (n && (!d_sigs || !d_pks || !d_digests_out))) return SSA_ERR_ARG;
-    if (int rc = check_msgs(d_msgs, d_msg_off, msg_stride, msg_len, n)) return rc;
+    if (int rc = check_msgs(mv, n)) return rc;
     if (n == 0) return 0;
     HIP_TRY(hipSetDevice(ctx->device));
-    MsgView mv{d_msgs, d_msg_off, msg_stride, msg_len};
     return timed_launch(ctx, "ssa_k_hash", [&] {
         hipLaunchKernelGGL(ssa_k_hash, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, ctx->d_params,
                            d_sigs, d_pks, mv, n, (u64 *)nullptr, d_digests_out, (const u32 *)nullptr, 0u);
@@ -571,51 +571,19 @@ extern "C" int ssa_rescue_hash_many_device(ssa_ctx *ctx, const uint64_t *d_felts
 }
 
 // one chunk of challenge hashes on `hs` (the shared upload pipeline of the host-buffer entry points)
-int ssa_internal_hash_chunk(ssa_ctx *ctx, hipStream_t hs, const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_msgs,
-                            const uint64_t *d_off, size_t msg_stride, size_t msg_len, size_t cnt, uint64_t *d_h) {
-    MsgView mv{d_msgs, d_off, msg_stride, msg_len};
-    hipLaunchKernelGGL(ssa_k_hash, dim3(grid_for(cnt, 256)), dim3(256), 0, hs, ctx->d_params, d_sigs, d_pks, mv, cnt,
+int ssa_internal_hash_chunk(ssa_ctx *ctx, hipStream_t hs, const DevBatch &b, size_t cnt, uint64_t *d_h) {
+    hipLaunchKernelGGL(ssa_k_hash, dim3(grid_for(cnt, 256)), dim3(256), 0, hs, ctx->d_params, b.sigs, b.pks, b.msgs, cnt,
                        (u64 *)d_h, (u8 *)nullptr, (const u32 *)nullptr, 0u);
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
-int ssa_internal_hash_scalars(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_msgs,
-                              const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len, size_t n) {
+int ssa_internal_hash_scalars(ssa_ctx *ctx, const DevBatch &b, size_t n) {
     if (ctx->ws_h.reserve(n * 4 * sizeof(u64))) return SSA_ERR_HIP;
-    MsgView mv{d_msgs, d_msg_off, msg_stride, msg_len};
     return timed_launch(ctx, "ssa_k_hash", [&] {
         hipLaunchKernelGGL(ssa_k_hash, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, ctx->d_params,
-                           d_sigs, d_pks, mv, n, (u64 *)ctx->ws_h.p, (u8 *)nullptr, (const u32 *)nullptr, 0u);
+                           b.sigs, b.pks, b.msgs, n, (u64 *)ctx->ws_h.p, (u8 *)nullptr, (const u32 *)nullptr, 0u);
     });
-}
-
-static int verify_launch(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_pk_inf,
-                         const uint8_t *d_msgs, const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len, size_t n,
-                         uint32_t flags, uint8_t *d_status_out, unsigned long long *d_fail);
-
-extern "C" int ssa_verify_many_device(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks,
-                                      const uint8_t *d_pk_inf, const uint8_t *d_msgs,
-                                      const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len,
-                                      size_t n, uint32_t flags, uint8_t *d_status_out,
-                                      uint64_t *d_n_fail_out) {
-    if (!ctx || (n && (!d_sigs || !d_pks || !d_status_out))) return SSA_ERR_ARG;
-    if (int rc = check_msgs(d_msgs, d_msg_off, msg_stride, msg_len, n)) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    unsigned long long *d_fail = d_n_fail_out ? (unsigned long long *)d_n_fail_out
-                                              : (unsigned long long *)ctx->ws_fail.p;
-    HIP_TRY(hipMemsetAsync(d_fail, 0, sizeof(unsigned long long), ctx->stream));
-    if (n == 0) return 0;
-    return verify_launch(ctx, d_sigs, d_pks, d_pk_inf, d_msgs, d_msg_off, msg_stride, msg_len, n, flags, d_status_out,
-                         d_fail);
-}
-
-// message view of the lanes from `lo` on (offsets are absolute into msgs: only the offset table moves)
-static inline MsgView msg_slice(const MsgView &mv, size_t lo) {
-    MsgView s = mv;
-    if (mv.off) s.off = mv.off + lo;
-    else if (mv.msgs) s.msgs = mv.msgs + lo * mv.stride;
-    return s;
 }
 
 // The end game of an ssa_k_verify launch over cnt lanes: which groups run in pieces, where their work is cut.  The cuts
@@ -627,11 +595,6 @@ struct TailKnobs {
     unsigned pieces, gens, waves, block, min_main;
     bool uniform, reversed;
 };
-static TailPlan tail_plan_of(const TailKnobs &kn, size_t cnt, uint32_t flags);
-static TailPlan tail_plan(const ssa_ctx *ctx, size_t cnt, uint32_t flags) {
-    return tail_plan_of({ctx->tail_pieces, ctx->tail_gens, ctx->verify_waves, ctx->verify_block, ctx->tail_min_main,
-                         ctx->tail_uniform, ctx->tail_reversed}, cnt, flags);
-}
 static TailPlan tail_plan_of(const TailKnobs &kn, size_t cnt, uint32_t flags) {
     const TailKnobs *ctx = &kn;
     TailPlan tp{};
@@ -691,6 +654,10 @@ static TailPlan tail_plan_of(const TailKnobs &kn, size_t cnt, uint32_t flags) {
     tp.reversed = ctx->reversed ? 1u : 0u;
     return tp;
 }
+static TailPlan tail_plan(const ssa_ctx *ctx, size_t cnt, uint32_t flags) {
+    return tail_plan_of({ctx->tail_pieces, ctx->tail_gens, ctx->verify_waves, ctx->verify_block, ctx->tail_min_main,
+                         ctx->tail_uniform, ctx->tail_reversed}, cnt, flags);
+}
 
 // the plan for explicit knobs: no context and no device needed, so the host logic is tested on the CPU
 // (tests/test_tail_plan.py: the pieces cover every window of every pass exactly once and never span two passes, the
@@ -711,11 +678,12 @@ extern "C" int ssa_debug_tail_plan(unsigned waves, unsigned pieces, unsigned gen
 
 // ssa_k_verify over n lanes whose challenge scalars are in d_h, in slices of at most ctx->lane_slice lanes: the 4 KB
 // per-lane table workspace never exceeds one slice (the caller has reserved it).  *d_fail is added to.
-static int verify_slices(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_pk_inf,
-                         const u64 *d_h, size_t n, uint32_t flags, uint8_t *d_status_out, unsigned long long *d_fail) {
+static int verify_slices(ssa_ctx *ctx, const DevBatch &b, const u64 *d_h, size_t n, uint32_t flags, uint8_t *d_status_out,
+                         unsigned long long *d_fail) {
     const size_t slice = ctx->lane_slice < n ? ctx->lane_slice : n;
     for (size_t lo = 0; lo < n; lo += slice) {
         const size_t cnt = n - lo < slice ? n - lo : slice;
+        const DevBatch s = b.slice(lo);
         const TailPlan tp = tail_plan(ctx, cnt, flags);
         unsigned blocks = grid_for(cnt, ctx->verify_block);
         if (tp.n_pieces) {
@@ -727,49 +695,45 @@ static int verify_slices(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_p
         }
         int rc = timed_launch(ctx, "ssa_k_verify", [&] {
             hipLaunchKernelGGL(ssa_k_verify, dim3(blocks), dim3(ctx->verify_block), 0,
-                               ctx->stream, d_sigs + 81 * lo, d_pks + 96 * lo, d_pk_inf ? d_pk_inf + lo : nullptr,
-                               d_h + 4 * lo, (const u64 *)ctx->d_gtab, (u64 *)ctx->ws_tab.p, cnt, flags,
-                               d_status_out + lo, d_fail, tp, (u32 *)ctx->tail_done.p, (u64 *)ctx->tail_park.p);
+                               ctx->stream, s.sigs, s.pks, s.pk_inf, d_h + 4 * lo, (const u64 *)ctx->d_gtab,
+                               (u64 *)ctx->ws_tab.p, cnt, flags, d_status_out + lo, d_fail, tp, (u32 *)ctx->tail_done.p,
+                               (u64 *)ctx->tail_park.p);
         });
         if (rc) return rc;
     }
     return 0;
 }
 
-int ssa_internal_verify_hashed(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_pk_inf,
-                               const uint64_t *d_h, size_t n, uint32_t flags, uint8_t *d_status_out,
-                               unsigned long long *d_fail) {
+int ssa_internal_verify_hashed(ssa_ctx *ctx, const DevBatch &b, const uint64_t *d_h, size_t n, uint32_t flags,
+                               uint8_t *d_status_out, unsigned long long *d_fail) {
     const size_t slice = ctx->lane_slice < n ? ctx->lane_slice : n;
     if (ctx->ws_tab.reserve(slice * (size_t)(PTAB_ENTRIES * PTAB_ENTRY_U64) * sizeof(u64))) return SSA_ERR_HIP;
-    return verify_slices(ctx, d_sigs, d_pks, d_pk_inf, (const u64 *)d_h, n, flags, d_status_out, d_fail);
+    return verify_slices(ctx, b, (const u64 *)d_h, n, flags, d_status_out, d_fail);
 }
 
 // hash + verification of ONE slice (cnt <= c->lane_slice lanes) on c->stream with c's workspaces; *d_fail is added to
-static int verify_one_slice(ssa_ctx *c, const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_pk_inf,
-                            const MsgView &mv, size_t cnt, uint32_t flags, uint8_t *d_status_out,
+static int verify_one_slice(ssa_ctx *c, const DevBatch &b, size_t cnt, uint32_t flags, uint8_t *d_status_out,
                             unsigned long long *d_fail) {
     if (c->ws_h.reserve(cnt * 4 * sizeof(u64))) return SSA_ERR_HIP;
     if (c->ws_tab.reserve(cnt * (size_t)(PTAB_ENTRIES * PTAB_ENTRY_U64) * sizeof(u64))) return SSA_ERR_HIP;
     int rc = timed_launch(c, "ssa_k_hash", [&] {
-        hipLaunchKernelGGL(ssa_k_hash, dim3(grid_for(cnt, 256)), dim3(256), 0, c->stream, c->d_params, d_sigs, d_pks, mv,
-                           cnt, (u64 *)c->ws_h.p, (u8 *)nullptr, (const u32 *)nullptr, 0u);
+        hipLaunchKernelGGL(ssa_k_hash, dim3(grid_for(cnt, 256)), dim3(256), 0, c->stream, c->d_params, b.sigs, b.pks,
+                           b.msgs, cnt, (u64 *)c->ws_h.p, (u8 *)nullptr, (const u32 *)nullptr, 0u);
     });
     if (rc) return rc;
-    return verify_slices(c, d_sigs, d_pks, d_pk_inf, (const u64 *)c->ws_h.p, cnt, flags, d_status_out, d_fail);
+    return verify_slices(c, b, (const u64 *)c->ws_h.p, cnt, flags, d_status_out, d_fail);
 }
 
 // the kernels of one verification batch on ctx->stream; *d_fail is added to, not reset
-static int verify_launch(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_pk_inf,
-                         const uint8_t *d_msgs, const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len, size_t n,
-                         uint32_t flags, uint8_t *d_status_out, unsigned long long *d_fail) {
-    MsgView mv{d_msgs, d_msg_off, msg_stride, msg_len};
+static int verify_launch(ssa_ctx *ctx, const DevBatch &b, size_t n, uint32_t flags, uint8_t *d_status_out,
+                         unsigned long long *d_fail) {
     // small batches: one wave per signature (low latency); large ones: one lane per signature (throughput)
     const size_t coop_lim = (flags & SSA_FLAG_CHECK_TORSION) ? ctx->coop_max_n_torsion : ctx->coop_max_n;
     const bool coop = (flags & SSA_FLAG_FORCE_COOP) || (!(flags & SSA_FLAG_FORCE_LANE) && n <= coop_lim);
     if (coop) {
         return timed_launch(ctx, "ssa_k_verify_coop", [&] {
-            hipLaunchKernelGGL(ssa_k_verify_coop, dim3((unsigned)n), dim3(128), 0, ctx->stream, ctx->d_params, d_sigs,
-                               d_pks, d_pk_inf, mv, (const u64 *)ctx->d_gtab, n, flags, d_status_out, d_fail);
+            hipLaunchKernelGGL(ssa_k_verify_coop, dim3((unsigned)n), dim3(128), 0, ctx->stream, ctx->d_params, b.sigs,
+                               b.pks, b.pk_inf, b.msgs, (const u64 *)ctx->d_gtab, n, flags, d_status_out, d_fail);
         });
     }
     // The per-lane workspaces (32 B of challenge scalar, 4 KB of table) are sized for ONE slice of at most
@@ -777,7 +741,7 @@ static int verify_launch(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_p
     // length, src/batch.rs:31-50): a larger batch runs slice after slice, into the caller's one status array and the one
     // rejection counter.  At n <= lane_slice this is the single pair of launches it always was.
     const size_t slice = ctx->lane_slice < n ? ctx->lane_slice : n;
-    if (n <= slice) return verify_one_slice(ctx, d_sigs, d_pks, d_pk_inf, mv, n, flags, d_status_out, d_fail);
+    if (n <= slice) return verify_one_slice(ctx, b, n, flags, d_status_out, d_fail);
     // More than one slice: the slices alternate between the context's stream and its twin's (a second set of
     // workspaces), so that one slice's kernels fill the tails of the other's -- ordered after everything queued on
     // ctx->stream before the call, and ctx->stream continues after both.
@@ -791,8 +755,7 @@ static int verify_launch(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_p
     for (size_t lo = 0; lo < n && rc == 0; lo += slice, j++) {
         const size_t cnt = n - lo < slice ? n - lo : slice;
         ssa_ctx *c = (tw && (j & 1u)) ? tw : ctx;
-        rc = verify_one_slice(c, d_sigs + 81 * lo, d_pks + 96 * lo, d_pk_inf ? d_pk_inf + lo : nullptr, msg_slice(mv, lo), cnt,
-                              flags, d_status_out + lo, d_fail);
+        rc = verify_one_slice(c, b.slice(lo), cnt, flags, d_status_out + lo, d_fail);
     }
     if (tw) {     // (also on an error: whatever was queued on the twin's stream is still ordered before the caller's next step)
         if (hipEventRecord(tw->order_ev, tw->stream) != hipSuccess ||
@@ -802,11 +765,24 @@ static int verify_launch(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_p
     return rc;
 }
 
+extern "C" int ssa_verify_many_device(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks,
+                                      const uint8_t *d_pk_inf, const uint8_t *d_msgs,
+                                      const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len,
+                                      size_t n, uint32_t flags, uint8_t *d_status_out,
+                                      uint64_t *d_n_fail_out) {
+    const DevBatch b{d_sigs, d_pks, d_pk_inf, {d_msgs, d_msg_off, msg_stride, msg_len}};
+    if (!ctx || (n && (!d_sigs || !d_pks || !d_status_out))) return SSA_ERR_ARG;
+    if (int rc = check_msgs(b.msgs, n)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    unsigned long long *d_fail;
+    if (int rc = reset_fail_counter(ctx, d_n_fail_out, &d_fail)) return rc;
+    if (n == 0) return 0;
+    return verify_launch(ctx, b, n, flags, d_status_out, d_fail);
+}
+
 // the throughput (variable-time) signer's launch; arguments checked by the caller (ssa_sign.hip)
-int ssa_internal_sign_vartime(ssa_ctx *ctx, const uint8_t *d_sks, const uint8_t *d_nonces, const uint8_t *d_msgs,
-                              const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len, size_t n, uint8_t *d_pks_out,
-                              uint8_t *d_sigs_out) {
-    MsgView mv{d_msgs, d_msg_off, msg_stride, msg_len};
+int ssa_internal_sign_vartime(ssa_ctx *ctx, const uint8_t *d_sks, const uint8_t *d_nonces, const MsgView &mv, size_t n,
+                              uint8_t *d_pks_out, uint8_t *d_sigs_out) {
     return timed_launch(ctx, "ssa_k_sign", [&] {
         hipLaunchKernelGGL(ssa_k_sign, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, ctx->d_params,
                            (const u64 *)ctx->d_gtab, d_sks, d_nonces, mv, n, d_pks_out, d_sigs_out);
@@ -815,10 +791,8 @@ int ssa_internal_sign_vartime(ssa_ctx *ctx, const uint8_t *d_sks, const uint8_t 
 
 // the throughput signer of a signer set (ssa_sign_many_indexed_device); arguments checked by the caller (ssa_sign.hip)
 int ssa_internal_sign_indexed_vartime(ssa_ctx *ctx, const ssa_signer_set *ss, const uint32_t *d_key_idx,
-                                      const uint8_t *d_nonces, const uint8_t *d_msgs, const uint64_t *d_msg_off,
-                                      size_t msg_stride, size_t msg_len, size_t n, bool keyed, uint8_t *d_out,
+                                      const uint8_t *d_nonces, const MsgView &mv, size_t n, bool keyed, uint8_t *d_out,
                                       uint8_t *d_status_out) {
-    MsgView mv{d_msgs, d_msg_off, msg_stride, msg_len};
     return timed_launch(ctx, "ssa_k_sign_indexed", [&] {
         hipLaunchKernelGGL(ssa_k_sign_indexed, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, ctx->d_params,
                            (const u64 *)ctx->d_gtab, ss->view(), d_key_idx, d_nonces, mv, n, keyed ? 1u : 0u, d_out,
@@ -861,13 +835,10 @@ static int verify_many_host_one(ssa_ctx *ctx, const HostBatch &b, size_t n, uint
     unsigned long long nf = 0, *d_fail = (unsigned long long *)ctx->ws_fail.p;
     hc.copy_back(&nf, d_fail, sizeof nf);
     const int rc = hc.finish([&] {
-        if (!s.hashed)
-            return ssa_verify_many_device(ctx, s.sigs, s.pks, s.inf, s.msgs, s.off, b.msg_stride, b.msg_len, n, flags,
-                                          d_status, (uint64_t *)d_fail);
-        // (the pipeline hashed the whole slice into ws_h, 32 B per lane, while it was uploading)
         HIP_TRY(hipMemsetAsync(d_fail, 0, sizeof(unsigned long long), ctx->stream));
-        return ssa_internal_verify_hashed(ctx, s.sigs, s.pks, s.inf, (const uint64_t *)ctx->ws_h.p, n, flags, d_status,
-                                          d_fail);
+        if (!s.hashed) return verify_launch(ctx, s.batch, n, flags, d_status, d_fail);
+        // (the pipeline hashed the whole slice into ws_h, 32 B per lane, while it was uploading)
+        return ssa_internal_verify_hashed(ctx, s.batch, (const uint64_t *)ctx->ws_h.p, n, flags, d_status, d_fail);
     });
     if (rc) return rc;
     pin.done();
@@ -881,7 +852,7 @@ extern "C" int ssa_verify_many(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t 
                                size_t msg_len, size_t n, uint32_t flags, uint8_t *status_out,
                                uint64_t *n_fail_out) {
     if (!ctx || (n && (!sigs || !pks || !status_out))) return SSA_ERR_ARG;
-    if (int rc = check_msgs(msgs, msg_off, msg_stride, msg_len, n)) return rc;
+    if (int rc = check_msgs({msgs, msg_off, msg_stride, msg_len}, n)) return rc;
     if (int rc = check_host_offsets(msg_off, n)) return rc;
     if (n_fail_out) *n_fail_out = 0;
     if (n == 0) return 0;
@@ -927,7 +898,7 @@ extern "C" int ssa_hash_message_many(ssa_ctx *ctx, const uint8_t *sigs, const ui
                                      const uint64_t *msg_off, size_t msg_stride, size_t msg_len, size_t n,
                                      uint8_t *digests_out) {
     if (!ctx || (n && (!sigs || !pks || !digests_out))) return SSA_ERR_ARG;
-    if (int rc = check_msgs(msgs, msg_off, msg_stride, msg_len, n)) return rc;
+    if (int rc = check_msgs({msgs, msg_off, msg_stride, msg_len}, n)) return rc;
     if (int rc = check_host_offsets(msg_off, n)) return rc;
     if (n == 0) return 0;
     HostCall hc(ctx);
@@ -996,7 +967,7 @@ extern "C" int ssa_verify_keyed_many(ssa_ctx *ctx, const uint8_t *keyed, const u
                                      const uint64_t *msg_off, size_t msg_stride, size_t msg_len, size_t n,
                                      uint32_t flags, uint8_t *status_out, uint64_t *n_fail_out) {
     if (!ctx || (n && (!keyed || !status_out))) return SSA_ERR_ARG;
-    if (int rc = check_msgs(msgs, msg_off, msg_stride, msg_len, n)) return rc;
+    if (int rc = check_msgs({msgs, msg_off, msg_stride, msg_len}, n)) return rc;
     if (int rc = check_host_offsets(msg_off, n)) return rc;
     if (n_fail_out) *n_fail_out = 0;
     if (n == 0) return 0;
@@ -1108,15 +1079,14 @@ extern "C" int ssa_verify_many_indexed_device(ssa_ctx *ctx, ssa_keyset *ks, cons
                                               const uint8_t *d_sigs, const uint8_t *d_msgs, const uint64_t *d_msg_off,
                                               size_t msg_stride, size_t msg_len, size_t n, uint32_t flags,
                                               uint8_t *d_status_out, uint64_t *d_n_fail_out) {
+    const MsgView mv{d_msgs, d_msg_off, msg_stride, msg_len};
     if (!ctx || !ks || ks->ctx != ctx || (n && (!d_key_idx || !d_sigs || !d_status_out))) return SSA_ERR_ARG;
-    if (int rc = check_msgs(d_msgs, d_msg_off, msg_stride, msg_len, n)) return rc;
+    if (int rc = check_msgs(mv, n)) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
-    unsigned long long *d_fail = d_n_fail_out ? (unsigned long long *)d_n_fail_out
-                                              : (unsigned long long *)ctx->ws_fail.p;
-    HIP_TRY(hipMemsetAsync(d_fail, 0, sizeof(unsigned long long), ctx->stream));
+    unsigned long long *d_fail;
+    if (int rc = reset_fail_counter(ctx, d_n_fail_out, &d_fail)) return rc;
     if (n == 0) return 0;
     if (ctx->ws_h.reserve(n * 4 * sizeof(u64))) return SSA_ERR_HIP;
-    MsgView mv{d_msgs, d_msg_off, msg_stride, msg_len};
     int rc = timed_launch(ctx, "ssa_k_hash", [&] {
         hipLaunchKernelGGL(ssa_k_hash, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, ctx->d_params, d_sigs,
                            (const u8 *)ks->pks.p, mv, n, (u64 *)ctx->ws_h.p, (u8 *)nullptr, d_key_idx, (u32)ks->m);
@@ -1139,7 +1109,7 @@ extern "C" int ssa_verify_many_indexed(ssa_ctx *ctx, ssa_keyset *ks, const uint3
                                        const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len,
                                        size_t n, uint32_t flags, uint8_t *status_out, uint64_t *n_fail_out) {
     if (!ctx || !ks || ks->ctx != ctx || (n && (!key_idx || !sigs || !status_out))) return SSA_ERR_ARG;
-    if (int rc = check_msgs(msgs, msg_off, msg_stride, msg_len, n)) return rc;
+    if (int rc = check_msgs({msgs, msg_off, msg_stride, msg_len}, n)) return rc;
     if (int rc = check_host_offsets(msg_off, n)) return rc;
     if (n_fail_out) *n_fail_out = 0;
     if (n == 0) return 0;
@@ -1233,7 +1203,7 @@ extern "C" int ssa_multi_verify_batch_msm(ssa_multi *m, const uint8_t *sigs, con
                                           const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride,
                                           size_t msg_len, size_t n, const uint8_t *coeffs) {
     if (!m || m->ctxs.empty() || (n && (!sigs || !pks))) return SSA_ERR_ARG;
-    if (int rc = check_msgs(msgs, msg_off, msg_stride, msg_len, n)) return rc;
+    if (int rc = check_msgs({msgs, msg_off, msg_stride, msg_len}, n)) return rc;
     if (n == 0) return SSA_OK;
     const size_t world = m->ctxs.size();
     const HostBatch b{sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len};

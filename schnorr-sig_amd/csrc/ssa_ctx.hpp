@@ -220,12 +220,12 @@ static inline int timed_launch(ssa_ctx *ctx, const char *name, F &&launch) {
 
 
 // ---- argument checks and host->device staging shared by the entry points ----
-static inline int check_msgs(const uint8_t *msgs, const uint64_t *off, size_t stride, size_t len, size_t n) {
+static inline int check_msgs(const MsgView &mv, size_t n) {
     if (n == 0) return 0;
     if (n > SSA_MAX_BATCH) return SSA_ERR_ARG;   // grid sizes and workspace offsets are computed for n <= 2^30
-    if (!off && len > 0 && !msgs) return SSA_ERR_ARG;
-    if (!off && stride < len) return SSA_ERR_ARG;
-    if (len > 0xffffffffull) return SSA_ERR_ARG;
+    if (!mv.off && mv.len > 0 && !mv.msgs) return SSA_ERR_ARG;
+    if (!mv.off && mv.stride < mv.len) return SSA_ERR_ARG;
+    if (mv.len > 0xffffffffull) return SSA_ERR_ARG;
     return 0;
 }
 
@@ -268,12 +268,37 @@ struct HostBatch {
     }
 };
 
+// a batch in device memory as the internal device paths take it (host code only: kernels take the pointers and the
+// MsgView).  Message offsets are absolute into msgs.msgs.
+struct DevBatch {
+    const uint8_t *sigs, *pks, *pk_inf;
+    MsgView msgs;
+    // lanes from lo on: signatures, keys and flags move by lo, strided messages by lo * stride, an offset table by lo
+    // (the message bytes stay put)
+    DevBatch slice(size_t lo) const {
+        DevBatch s = *this;
+        s.sigs = sigs ? sigs + 81 * lo : nullptr;
+        s.pks = pks ? pks + 96 * lo : nullptr;
+        s.pk_inf = pk_inf ? pk_inf + lo : nullptr;
+        if (msgs.off) s.msgs.off = msgs.off + lo;
+        else if (msgs.msgs) s.msgs.msgs = msgs.msgs + lo * msgs.stride;
+        return s;
+    }
+};
+
 // device copies of one slice of a batch; hashed: ctx->ws_h already holds the challenge scalars (pipelined_upload_hash)
 struct StagedInputs {
-    const u8 *sigs = nullptr, *pks = nullptr, *inf = nullptr, *msgs = nullptr, *coeffs = nullptr;
-    const u64 *off = nullptr;
+    DevBatch batch{};
+    const u8 *coeffs = nullptr;
     bool hashed = false;
 };
+
+// the rejection counter of a counted device form: the caller's, or the context's own; zeroed on ctx->stream
+static inline int reset_fail_counter(ssa_ctx *ctx, uint64_t *d_n_fail_out, unsigned long long **d_fail) {
+    *d_fail = (unsigned long long *)(d_n_fail_out ? (void *)d_n_fail_out : ctx->ws_fail.p);
+    HIP_TRY(hipMemsetAsync(*d_fail, 0, sizeof(unsigned long long), ctx->stream));
+    return 0;
+}
 
 // Device copies of secrets (keys, nonces, seeds, parent and master xprvs) do not outlive the call that made them,
 // whichever way it returns: the named buffers are zeroed on the context's stream, each clamped to its capacity, when
@@ -377,8 +402,20 @@ struct HostCall {
 
 
 // defined in ssa_api.hip
-int ssa_internal_hash_chunk(ssa_ctx *ctx, hipStream_t hs, const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_msgs,
-                            const uint64_t *d_off, size_t msg_stride, size_t msg_len, size_t cnt, uint64_t *d_h);
+int ssa_internal_hash_chunk(ssa_ctx *ctx, hipStream_t hs, const DevBatch &b, size_t cnt, uint64_t *d_h);
+
+// An error return after work was queued on the context's side streams (copies out of the bounce buffers, hash launches
+// that write ctx->ws_h, msm_k_prepare): wait for all of it before the next call reuses the buffers it reads or writes.
+struct SideStreamDrain {
+    ssa_ctx *armed = nullptr;   // set with the first enqueue; done(): no error return from here on needs the wait
+    void done() { armed = nullptr; }
+    ~SideStreamDrain() {
+        if (!armed) return;
+        (void)hipStreamSynchronize(armed->copy_stream);
+        for (auto &hs : armed->hash_stream) (void)hipStreamSynchronize(hs);
+        (void)hipStreamSynchronize(armed->stream);
+    }
+};
 
 // Host-buffer uploads go through page-locked memory of the LIBRARY's (ctx->pin_in): the caller's bytes are copied into it
 // by host threads, chunk by chunk, and the DMA engines read it asynchronously, under the kernels of the chunk before.
@@ -389,18 +426,8 @@ int ssa_internal_hash_chunk(ssa_ctx *ctx, hipStream_t hs, const uint8_t *d_sigs,
 // tools/soak_large.py found it within ten iterations, never with the in-place registration off, never with the arrays in
 // their own mappings).  Whatever the runtime keeps of a registration, a library has no business changing the mapping state
 // of memory it does not own.
-struct PipelinedInputs {
+struct PipelinedInputs : SideStreamDrain {
     StagedInputs s;     // device copies (context staging buffers)
-    ssa_ctx *armed = nullptr;   // set with the first enqueue; cleared by done() once the call has synchronised
-    void done() { armed = nullptr; }
-    ~PipelinedInputs() {
-        // an error return after the first enqueue: copies out of the bounce buffers and hash launches that write
-        // ctx->ws_h may still be in flight -- wait for them before the next call reuses the buffers
-        if (!armed) return;
-        (void)hipStreamSynchronize(armed->copy_stream);
-        for (auto &hs : armed->hash_stream) (void)hipStreamSynchronize(hs);
-        (void)hipStreamSynchronize(armed->stream);
-    }
 };
 
 // caller memory -> page-locked memory on up to SSA_COPY_THREADS (default 8) host threads (one thread moves ~10 GB/s; a
@@ -470,19 +497,20 @@ static inline int pipelined_upload_hash(ssa_ctx *ctx, const HostBatch &b, size_t
     for (auto &hs : ctx->hash_stream) HIP_TRY(hipStreamWaitEvent(hs, ctx->pipe_start, 0));
     pin.armed = ctx;
     const int fault_chunk = pipeline_fault_chunk(ctx);
-    const u64 *d_off = nullptr;
+    u8 *d_sigs = (u8 *)ctx->st_sigs.p, *d_pks = (u8 *)ctx->st_pks.p, *d_msgs = (u8 *)ctx->st_msgs.p;
+    DevBatch &d = pin.s.batch;
+    d = {d_sigs, d_pks, nullptr, {d_msgs, nullptr, msg_stride, msg_len}};
     if (msg_off) {
         host_copy(h_off, msg_off, (n + 1) * sizeof(uint64_t));
         HIP_TRY(hipMemcpyAsync(ctx->st_off.p, h_off, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->copy_stream));
-        d_off = (const u64 *)ctx->st_off.p;
+        d.msgs.off = (const u64 *)ctx->st_off.p;
     }
     if (pk_inf) {
         host_copy(h_inf, pk_inf, n);
         HIP_TRY(hipMemcpyAsync(ctx->st_inf.p, h_inf, n, hipMemcpyHostToDevice, ctx->copy_stream));
-        pin.s.inf = (const u8 *)ctx->st_inf.p;
+        d.pk_inf = (const u8 *)ctx->st_inf.p;
     }
     const unsigned chunks = ctx->pipeline_chunks;
-    u8 *d_sigs = (u8 *)ctx->st_sigs.p, *d_pks = (u8 *)ctx->st_pks.p, *d_msgs = (u8 *)ctx->st_msgs.p;
     for (unsigned c = 0; c < chunks; c++) {
         const size_t lo = n * c / chunks, hi = n * (c + 1) / chunks, cnt = hi - lo;
         if (cnt == 0) continue;
@@ -500,18 +528,11 @@ static inline int pipelined_upload_hash(ssa_ctx *ctx, const HostBatch &b, size_t
         HIP_TRY(hipEventRecord(ctx->copy_done[c], ctx->copy_stream));
         hipStream_t hs = ctx->hash_stream[c & 1u];
         HIP_TRY(hipStreamWaitEvent(hs, ctx->copy_done[c], 0));
-        if (int rc = ssa_internal_hash_chunk(ctx, hs, d_sigs + 81 * lo, d_pks + 96 * lo,
-                                             msg_off ? d_msgs : d_msgs + lo * msg_stride, msg_off ? d_off + lo : nullptr,
-                                             msg_stride, msg_len, cnt, (uint64_t *)ctx->ws_h.p + 4 * lo))
-            return rc;
+        if (int rc = ssa_internal_hash_chunk(ctx, hs, d.slice(lo), cnt, (uint64_t *)ctx->ws_h.p + 4 * lo)) return rc;
         HIP_TRY(hipEventRecord(ctx->hash_done[c], hs));
         HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->hash_done[c], 0));
         if ((int)c == fault_chunk) return SSA_ERR_HIP;   // injected (tests)
     }
-    pin.s.sigs = d_sigs;
-    pin.s.pks = d_pks;
-    pin.s.msgs = d_msgs;
-    pin.s.off = d_off;
     return 0;
 }
 
@@ -545,25 +566,21 @@ static inline StagedInputs slice_inputs(HostCall &hc, PipelinedInputs &pin, cons
         }
     }
     StagedInputs s;
-    s.sigs = hc.in(ctx->st_sigs, b.sigs, n * 81);
-    s.pks = hc.in(ctx->st_pks, b.pks, n * 96);
-    if (b.pk_inf) s.inf = hc.in(ctx->st_inf, b.pk_inf, n);
-    const MsgView mv = hc.msgs(b.msgs, b.msg_off, b.msg_stride, b.msg_len, n);
-    s.msgs = mv.msgs;
-    s.off = mv.off;
+    s.batch.sigs = hc.in(ctx->st_sigs, b.sigs, n * 81);
+    s.batch.pks = hc.in(ctx->st_pks, b.pks, n * 96);
+    if (b.pk_inf) s.batch.pk_inf = hc.in(ctx->st_inf, b.pk_inf, n);
+    s.batch.msgs = hc.msgs(b.msgs, b.msg_off, b.msg_stride, b.msg_len, n);
     if (coeffs) s.coeffs = hc.in(ctx->st_coeffs, coeffs, n * 32);
     return s;
 }
 
 // defined in ssa_api.hip: hash_message + Scalar::from_bits_vartime for n signatures into ctx->ws_h
-int ssa_internal_hash_scalars(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_msgs,
-                              const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len, size_t n);
+int ssa_internal_hash_scalars(ssa_ctx *ctx, const DevBatch &b, size_t n);
 
-// defined in ssa_api.hip: ssa_k_verify over n lanes whose challenge scalars are already in d_h (the per-lane workspace
-// reserved for one slice of lanes); *d_fail is added to
-int ssa_internal_verify_hashed(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_pk_inf,
-                               const uint64_t *d_h, size_t n, uint32_t flags, uint8_t *d_status_out,
-                               unsigned long long *d_fail);
+// defined in ssa_api.hip: ssa_k_verify over n lanes of b (its messages unused) whose challenge scalars are already in
+// d_h (the per-lane workspace reserved for one slice of lanes); *d_fail is added to
+int ssa_internal_verify_hashed(ssa_ctx *ctx, const DevBatch &b, const uint64_t *d_h, size_t n, uint32_t flags,
+                               uint8_t *d_status_out, unsigned long long *d_fail);
 
 // defined in ssa_sign.hip (ssa_selfcheck.hpp): the exact check of a comb table for G (res[0] failing rows, res[1] the
 // first failing row or ~0) and of the context's constant-time table (out[0] rows checked, out[1], out[2] as res)

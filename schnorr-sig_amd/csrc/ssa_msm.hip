@@ -1167,51 +1167,132 @@ extern "C" int ssa_debug_chacha20(ssa_ctx *ctx, const uint8_t key[32], const uin
     return hc.finish([&] { return msm_chacha20(ctx, key, nonce, counter0, n_blocks, d_out); });
 }
 
-static int msm_run(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_pk_inf,
-                   const uint8_t *d_msgs, const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len, size_t n,
-                   const uint8_t *d_coeffs, uint32_t coeff_bytes, uint32_t *d_verdict_out, u64 *d_partial_out,
-                   bool hashed = false);
+namespace ssa {
+// k partial records (24-word stride) -> the layout msm_k_finish reads: k points of 18 words, k scalars of 4 words, and
+// the OR of the malformed flags
+__global__ void msm_k_unpack_parts(const u64 *__restrict__ parts, u32 k, u64 *__restrict__ pts, u64 *__restrict__ lins,
+                                   u32 *__restrict__ malformed) {
+    const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= k * 24u) return;
+    const u32 j = t / 24u, w = t % 24u;
+    const u64 v = parts[t];
+    if (w < 18) {
+        pts[18u * j + w] = v;
+        if (v >= FP_P) atomicOr(malformed, 1u);                 // limbs of a record are canonical
+    } else if (w < 22) {
+        lins[4u * j + (w - 18u)] = v;
+    } else if (w == 22) {
+        if (v != 0) atomicOr(malformed, 1u);
+    } else if (v != SSA_MSM_RECORD_MAGIC) {
+        atomicOr(malformed, 1u);   // not a record of this format: never written (all zero), foreign version, garbled
+    }
+}
+
+// One lane per record: the scalar is canonical (< q) and the point is the identity (Z = 0) or satisfies the Jacobian
+// curve equation Y^2 = X^3 + X Z^4 + (u + 395) Z^6.  Records cross process boundaries (all-gather): a corrupted or
+// foreign one gives SSA_MALFORMED, never an arbitrary verdict.  k <= 4096: the cost is one short launch.
+__global__ void __launch_bounds__(64)
+msm_k_check_parts(const u64 *__restrict__ parts, u32 k, u32 *__restrict__ malformed) {
+    const u32 j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= k) return;
+    const u64 *r = parts + 24u * (size_t)j;
+    bool ok = true;
+    fp6 X, Y, Z;
+#pragma unroll
+    for (int c = 0; c < 6; c++) {
+        X.c[c] = r[c];
+        Y.c[c] = r[6 + c];
+        Z.c[c] = r[12 + c];
+        ok = ok && X.c[c] < FP_P && Y.c[c] < FP_P && Z.c[c] < FP_P;
+    }
+    sc256 lin;
+#pragma unroll
+    for (int c = 0; c < 4; c++) lin.w[c] = r[18 + c];
+    ok = ok && !sc_geq_q(lin);
+    if (ok && !f6_is_zero(Z)) {
+        const fp6 z2 = f6_sqr(Z), z4 = f6_sqr(z2), z6 = f6_mul(z4, z2);
+        fp6 b = f6_zero();
+        b.c[0] = 395ull;
+        b.c[1] = 1ull;
+        const fp6 rhs = f6_add(f6_add(f6_mul(f6_sqr(X), X), f6_mul(X, z4)), f6_mul(b, z6));
+        ok = f6_eq(f6_sqr(Y), rhs);
+    }
+    if (!ok) atomicOr(malformed, 1u);
+}
+}  // namespace ssa
+
+// The shards added up on one device: one Jacobian addition per shard, the scalars mod q, [lin]G from the comb table and
+// the x-only comparison (src/batch.rs:98-100,123-129) -- msm_k_finish with no doublings between its "windows".
+// check_points: the records come from outside this call (ssa_msm_combine*): scalars and points are validated too
+static int msm_combine_records(ssa_ctx *ctx, const u64 *d_records, size_t k, uint32_t *d_verdict_out, u64 *d_partial_out,
+                               bool check_points = false) {
+    if (ctx->msm_comb_pts.reserve(18 * k * sizeof(u64)) || ctx->msm_comb_lins.reserve(4 * k * sizeof(u64)) ||
+        ctx->msm_flags.reserve(64))
+        return SSA_ERR_HIP;
+    HIP_TRY(hipMemsetAsync(ctx->msm_flags.p, 0, 64, ctx->stream));
+    hipLaunchKernelGGL(msm_k_unpack_parts, dim3(grid_for(k * 24, 256)), dim3(256), 0, ctx->stream, d_records, (u32)k,
+                       (u64 *)ctx->msm_comb_pts.p, (u64 *)ctx->msm_comb_lins.p, (u32 *)ctx->msm_flags.p);
+    HIP_TRY(hipGetLastError());
+    if (check_points) {
+        hipLaunchKernelGGL(msm_k_check_parts, dim3(grid_for(k, 64)), dim3(64), 0, ctx->stream, d_records, (u32)k,
+                           (u32 *)ctx->msm_flags.p);
+        HIP_TRY(hipGetLastError());
+    }
+    MsmShape sh;
+    sh.c = 0;
+    sh.windows = (u32)k;
+    sh.buckets = 1;
+    sh.chunks = 1;
+    return timed_launch(ctx, "msm_combine", [&] {
+        hipLaunchKernelGGL(msm_k_finish, dim3(1), dim3(128), 0, ctx->stream, (const u64 *)ctx->msm_comb_pts.p, sh,
+                           (const u64 *)ctx->msm_comb_lins.p, (u32)k, (const u64 *)ctx->d_gtab,
+                           (const u32 *)ctx->msm_flags.p, d_verdict_out, d_partial_out);
+    });
+}
+
+extern "C" int ssa_msm_combine_device(ssa_ctx *ctx, const uint64_t *d_parts24, size_t k, uint32_t *d_verdict_out) {
+    if (!ctx || !d_parts24 || !d_verdict_out || k == 0 || k > 4096) return SSA_ERR_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    return msm_combine_records(ctx, (const u64 *)d_parts24, k, d_verdict_out, nullptr, true);
+}
+
+extern "C" int ssa_msm_combine(ssa_ctx *ctx, const uint64_t *parts24, size_t k) {
+    if (!ctx || !parts24 || k == 0 || k > 4096) return SSA_ERR_ARG;
+    HostCall hc(ctx);
+    const uint64_t *d_parts = hc.in<uint64_t>(ctx->st_aux, parts24, k * SSA_MSM_PARTIAL_WORDS * sizeof(uint64_t));
+    uint32_t v = SSA_MALFORMED, *d_verdict = (uint32_t *)((char *)ctx->ws_fail.p + 32);
+    hc.copy_back(&v, d_verdict, sizeof v);
+    const int rc = hc.finish([&] { return ssa_msm_combine_device(ctx, d_parts, k, d_verdict); });
+    return rc ? rc : (int)v;
+}
+
 // the screened form: segments of the slice, per-lane status out, one verdict byte per segment
 struct ScreenArgs {
     u32 segs, seg_blocks;
     u8 *status, *seg_ok;
 };
-static int msm_run_one(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_pk_inf,
-                       const uint8_t *d_msgs, const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len, size_t n,
-                       const uint8_t *d_coeffs, uint32_t coeff_bytes, uint32_t *d_verdict_out, u64 *d_partial_out,
-                       const u64 *d_h, const ScreenArgs *scr = nullptr);
-static int msm_run_small(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_pk_inf,
-                         const uint8_t *d_msgs, const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len, size_t n,
-                         const uint8_t *d_coeffs, uint32_t coeff_bytes, uint32_t *d_verdict_out, u64 *d_partial_out);
-
-extern "C" int ssa_verify_batch_msm_device(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks,
-                                           const uint8_t *d_pk_inf, const uint8_t *d_msgs,
-                                           const uint64_t *d_msg_off, size_t msg_stride,
-                                           size_t msg_len, size_t n, const uint8_t *d_coeffs, uint32_t coeff_bytes,
-                                           uint32_t *d_verdict_out) {
-    if (!d_verdict_out) return SSA_ERR_ARG;
-    return msm_run(ctx, d_sigs, d_pks, d_pk_inf, d_msgs, d_msg_off, msg_stride, msg_len, n, d_coeffs, coeff_bytes,
-                   d_verdict_out, nullptr);
+constexpr u32 SCREEN_C = 8;                 // window bits: K * 2^(c-1) <= 256 * 128 stays within the grouping grid
+static MsmShape screen_shape(u32 segs) {
+    MsmShape sh;
+    sh.c = SCREEN_C;
+    sh.windows = (255 + sh.c - 1) / sh.c;
+    sh.buckets = segs << (sh.c - 1);
+    sh.chunks = sh.buckets / (u32)MSM_CHUNK;
+    return sh;
 }
-
-// check_points: the records come from outside this call (ssa_msm_combine*): scalars and points are validated too
-static int msm_combine_records(ssa_ctx *ctx, const u64 *d_records, size_t k, uint32_t *d_verdict_out, u64 *d_partial_out,
-                               bool check_points = false);
 
 // Small batch (n <= ctx->msm_small_max): one cooperative block per signature, then the records are summed -- in
 // groups of 16 by one wave each while there are more than 16 of them, the rest by the combination kernel, which also
 // computes [sum s_i e_i] G and compares (or emits the shard's record).
-static int msm_run_small(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_pk_inf,
-                         const uint8_t *d_msgs, const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len, size_t n,
-                         const uint8_t *d_coeffs, uint32_t coeff_bytes, uint32_t *d_verdict_out, u64 *d_partial_out) {
+static int msm_run_small(ssa_ctx *ctx, const DevBatch &b, size_t n, const uint8_t *d_coeffs, uint32_t coeff_bytes,
+                         uint32_t *d_verdict_out, u64 *d_partial_out) {
     const size_t groups = (n + 15) / 16;
     if (ctx->msm_buckets.reserve(n * 24 * sizeof(u64)) || ctx->msm_chunks.reserve(groups * 24 * sizeof(u64)) ||
         ctx->msm_windows.reserve(groups * 24 * sizeof(u64)))
         return SSA_ERR_HIP;
-    MsgView mv{d_msgs, d_msg_off, msg_stride, msg_len};
     int rc = timed_launch(ctx, "msm_k_small", [&] {
-        hipLaunchKernelGGL(msm_k_small, dim3((unsigned)n), dim3(128), 0, ctx->stream, ctx->d_params, d_sigs, d_pks, d_pk_inf,
-                           mv, d_coeffs, coeff_bytes, n, (u64 *)ctx->msm_buckets.p);
+        hipLaunchKernelGGL(msm_k_small, dim3((unsigned)n), dim3(128), 0, ctx->stream, ctx->d_params, b.sigs, b.pks, b.pk_inf,
+                           b.msgs, d_coeffs, coeff_bytes, n, (u64 *)ctx->msm_buckets.p);
     });
     if (rc) return rc;
     const u64 *recs = (const u64 *)ctx->msm_buckets.p;
@@ -1230,47 +1311,12 @@ static int msm_run_small(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_p
     return msm_combine_records(ctx, recs, count, d_verdict_out, d_partial_out);
 }
 
-// A batch of any size (n <= SSA_MAX_BATCH) in bounded memory: more than ctx->msm_slice signatures run slice after slice,
-// every slice reduced to its 24-word record exactly as a shard of a multi-GPU batch is (src/batch.rs:98-129: one point
-// and one scalar per part), and the records are added up by the combination kernel -- one point addition per slice.
-// hashed: ctx->ws_h already holds the challenge scalars of the WHOLE batch (the host-buffer pipeline computed them).
-static int msm_run(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_pk_inf,
-                   const uint8_t *d_msgs, const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len, size_t n,
-                   const uint8_t *d_coeffs, uint32_t coeff_bytes, uint32_t *d_verdict_out, u64 *d_partial_out,
-                   bool hashed) {
-    if (!ctx || (!d_verdict_out && !d_partial_out)) return SSA_ERR_ARG;
-    if (n && (!d_sigs || !d_pks)) return SSA_ERR_ARG;
-    if (d_coeffs && (coeff_bytes == 0 || coeff_bytes > 32)) return SSA_ERR_ARG;
-    if (int rc = check_msgs(d_msgs, d_msg_off, msg_stride, msg_len, n)) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const u64 *d_h = hashed ? (const u64 *)ctx->ws_h.p : nullptr;
-    if (n <= ctx->msm_slice)
-        return msm_run_one(ctx, d_sigs, d_pks, d_pk_inf, d_msgs, d_msg_off, msg_stride, msg_len, n, d_coeffs, coeff_bytes,
-                           d_verdict_out, d_partial_out, d_h);
-    const size_t slice = ctx->msm_slice, k = (n + slice - 1) / slice;
-    if (ctx->msm_slice_recs.reserve(k * 24 * sizeof(u64))) return SSA_ERR_HIP;
-    u64 *recs = (u64 *)ctx->msm_slice_recs.p;
-    for (size_t j = 0; j < k; j++) {
-        const size_t lo = j * slice, cnt = n - lo < slice ? n - lo : slice;
-        if (int rc = msm_run_one(ctx, d_sigs + 81 * lo, d_pks + 96 * lo, d_pk_inf ? d_pk_inf + lo : nullptr,
-                                 d_msg_off ? d_msgs : (d_msgs ? d_msgs + lo * msg_stride : nullptr),
-                                 d_msg_off ? d_msg_off + lo : nullptr, msg_stride, msg_len, cnt,
-                                 d_coeffs ? d_coeffs + (size_t)coeff_bytes * lo : nullptr, coeff_bytes, nullptr,
-                                 recs + 24 * j, d_h ? d_h + 4 * lo : nullptr))
-            return rc;
-    }
-    return msm_combine_records(ctx, recs, k, d_verdict_out, d_partial_out);
-}
-
 // the kernels of one MSM-form slice on ctx->stream: a verdict (d_partial_out == nullptr) or the slice's / shard's record
 // d_h: the challenge scalars if they exist already, else nullptr (they are computed into ctx->ws_h)
-static MsmShape screen_shape(u32 segs);
 // scr != nullptr: the screened form -- (window, segment, digit) buckets, a per-lane status, one verdict per segment in
 // scr->seg_ok (no verdict, no record)
-static int msm_run_one(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_pk_inf,
-                       const uint8_t *d_msgs, const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len, size_t n,
-                       const uint8_t *d_coeffs, uint32_t coeff_bytes, uint32_t *d_verdict_out, u64 *d_partial_out,
-                       const u64 *d_h, const ScreenArgs *scr) {
+static int msm_run_one(ssa_ctx *ctx, const DevBatch &b, size_t n, const uint8_t *d_coeffs, uint32_t coeff_bytes,
+                       uint32_t *d_verdict_out, u64 *d_partial_out, const u64 *d_h, const ScreenArgs *scr = nullptr) {
     if (n > (1ull << 23)) return SSA_ERR_ARG;   // an item carries its point index in 24 bits: 2n <= 2^24 (msm_run slices)
     if (n == 0) {   // empty batch: Ok (src/batch.rs); an empty shard adds the identity and 0
         if (d_partial_out) {
@@ -1288,8 +1334,7 @@ static int msm_run_one(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks
         coeff_bytes = 16;
     }
     if (!scr && n <= ctx->msm_small_max)
-        return msm_run_small(ctx, d_sigs, d_pks, d_pk_inf, d_msgs, d_msg_off, msg_stride, msg_len, n, d_coeffs, coeff_bytes,
-                             d_verdict_out, d_partial_out);
+        return msm_run_small(ctx, b, n, d_coeffs, coeff_bytes, d_verdict_out, d_partial_out);
     const MsmShape sh = scr ? screen_shape(scr->segs) : msm_shape(n);
     // windows the coefficients themselves can reach (32-byte ones are reduced mod q: all of them).  A narrower coefficient
     // whose width is a whole number of windows is read as a TWO'S-COMPLEMENT integer (msm_k_prepare): its signed digits
@@ -1333,20 +1378,20 @@ static int msm_run_one(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks
         // preparation (R's square roots above all) runs on a second stream UNDER ssa_k_hash -- its waves fill the hash
         // kernel's tail (the last wave of every SIMD alone, 0.35 ms) and the hash fills theirs --, ctx->stream joins it
         // after the hash and writes the digits that were missing.
+        // Until msm_k_prepare_h is queued behind it, an error return waits for msm_k_prepare: it writes msm_points,
+        // msm_scalars, msm_sbuf and msm_flags.
         if (ctx->msm_sbuf.reserve(n * 32)) return SSA_ERR_HIP;
         hipStream_t side = ctx->hash_stream[0];
         HIP_TRY(hipEventRecord(ctx->pipe_start, ctx->stream));
         HIP_TRY(hipStreamWaitEvent(side, ctx->pipe_start, 0));
-        hipLaunchKernelGGL(msm_k_prepare, dim3(n_blocks), dim3(256), 0, side, d_sigs, d_pks, d_pk_inf,
+        SideStreamDrain drain{ctx};
+        hipLaunchKernelGGL(msm_k_prepare, dim3(n_blocks), dim3(256), 0, side, b.sigs, b.pks, b.pk_inf,
                            (const u64 *)nullptr, d_coeffs, coeff_bytes, n, sh, wa, (u64 *)ctx->msm_points.p,
                            (short *)ctx->msm_scalars.p, (u64 *)ctx->msm_partials.p, (u32 *)ctx->msm_flags.p,
                            (u64 *)ctx->msm_sbuf.p, scr ? scr->status : (u8 *)nullptr);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(ctx->hash_done[0], side));
-        if (int hrc = ssa_internal_hash_scalars(ctx, d_sigs, d_pks, d_msgs, d_msg_off, msg_stride, msg_len, n)) {
-            (void)hipStreamSynchronize(side);
-            return hrc;
-        }
+        if (int hrc = ssa_internal_hash_scalars(ctx, b, n)) return hrc;
         d_h = (const u64 *)ctx->ws_h.p;
         HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->hash_done[0], 0));
         rc = timed_launch(ctx, "msm_k_prepare", [&] {
@@ -1354,14 +1399,15 @@ static int msm_run_one(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks
                                n, sh, (short *)ctx->msm_scalars.p);
         });
         if (rc) return rc;
+        drain.done();
     } else {
         // challenge scalars h_i with the kernel of the per-lane path
         if (!d_h) {
-            if (int hrc = ssa_internal_hash_scalars(ctx, d_sigs, d_pks, d_msgs, d_msg_off, msg_stride, msg_len, n)) return hrc;
+            if (int hrc = ssa_internal_hash_scalars(ctx, b, n)) return hrc;
             d_h = (const u64 *)ctx->ws_h.p;
         }
         rc = timed_launch(ctx, "msm_k_prepare", [&] {
-            hipLaunchKernelGGL(msm_k_prepare, dim3(n_blocks), dim3(256), 0, ctx->stream, d_sigs, d_pks, d_pk_inf,
+            hipLaunchKernelGGL(msm_k_prepare, dim3(n_blocks), dim3(256), 0, ctx->stream, b.sigs, b.pks, b.pk_inf,
                                d_h, d_coeffs, coeff_bytes, n, sh, wa, (u64 *)ctx->msm_points.p,
                                (short *)ctx->msm_scalars.p, (u64 *)ctx->msm_partials.p, (u32 *)ctx->msm_flags.p,
                                (u64 *)nullptr, scr ? scr->status : (u8 *)nullptr);
@@ -1427,29 +1473,39 @@ static int msm_run_one(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks
     });
 }
 
-static int msm_host_one(ssa_ctx *ctx, const HostBatch &b, size_t n, const uint8_t *coeffs, int *verdict_out,
-                        uint64_t *out24);
-static int msm_host_sliced(ssa_ctx *ctx, const HostBatch &b, size_t n, const uint8_t *coeffs, int *verdict_out,
-                           uint64_t *out24);
-
-// One shard of a batch that spans several devices: stage the host buffers, run the MSM pipeline, return the shard's
-// 24-word partial record (left-hand point, sum s_i e_i, malformed flag) in host memory.
-extern "C" int ssa_verify_batch_msm_partial(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_inf,
-                                            const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride,
-                                            size_t msg_len, size_t n, const uint8_t *coeffs,
-                                            uint64_t out24[SSA_MSM_PARTIAL_WORDS]) {
-    if (!ctx || !out24 || (n && (!sigs || !pks))) return SSA_ERR_ARG;
-    if (int rc = check_msgs(msgs, msg_off, msg_stride, msg_len, n)) return rc;
+// A batch of any size (n <= SSA_MAX_BATCH) in bounded memory: more than ctx->msm_slice signatures run slice after slice,
+// every slice reduced to its 24-word record exactly as a shard of a multi-GPU batch is (src/batch.rs:98-129: one point
+// and one scalar per part), and the records are added up by the combination kernel -- one point addition per slice.
+// hashed: ctx->ws_h already holds the challenge scalars of the WHOLE batch (the host-buffer pipeline computed them).
+static int msm_run(ssa_ctx *ctx, const DevBatch &b, size_t n, const uint8_t *d_coeffs, uint32_t coeff_bytes,
+                   uint32_t *d_verdict_out, u64 *d_partial_out, bool hashed = false) {
+    if (!ctx || (!d_verdict_out && !d_partial_out)) return SSA_ERR_ARG;
+    if (n && (!b.sigs || !b.pks)) return SSA_ERR_ARG;
+    if (d_coeffs && (coeff_bytes == 0 || coeff_bytes > 32)) return SSA_ERR_ARG;
+    if (int rc = check_msgs(b.msgs, n)) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
-    std::memset(out24, 0, SSA_MSM_PARTIAL_WORDS * sizeof(uint64_t));
-    if (n == 0) {
-        out24[23] = SSA_MSM_RECORD_MAGIC;    // the empty shard's record: identity, 0
-        return 0;
+    const u64 *d_h = hashed ? (const u64 *)ctx->ws_h.p : nullptr;
+    if (n <= ctx->msm_slice) return msm_run_one(ctx, b, n, d_coeffs, coeff_bytes, d_verdict_out, d_partial_out, d_h);
+    const size_t slice = ctx->msm_slice, k = (n + slice - 1) / slice;
+    if (ctx->msm_slice_recs.reserve(k * 24 * sizeof(u64))) return SSA_ERR_HIP;
+    u64 *recs = (u64 *)ctx->msm_slice_recs.p;
+    for (size_t j = 0; j < k; j++) {
+        const size_t lo = j * slice, cnt = n - lo < slice ? n - lo : slice;
+        if (int rc = msm_run_one(ctx, b.slice(lo), cnt, d_coeffs ? d_coeffs + (size_t)coeff_bytes * lo : nullptr, coeff_bytes,
+                                 nullptr, recs + 24 * j, d_h ? d_h + 4 * lo : nullptr))
+            return rc;
     }
-    if (int rc = check_host_offsets(msg_off, n)) return rc;
-    const HostBatch b{sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len};
-    return n > ctx->msm_slice ? msm_host_sliced(ctx, b, n, coeffs, nullptr, out24)
-                              : msm_host_one(ctx, b, n, coeffs, nullptr, out24);
+    return msm_combine_records(ctx, recs, k, d_verdict_out, d_partial_out);
+}
+
+extern "C" int ssa_verify_batch_msm_device(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks,
+                                           const uint8_t *d_pk_inf, const uint8_t *d_msgs,
+                                           const uint64_t *d_msg_off, size_t msg_stride,
+                                           size_t msg_len, size_t n, const uint8_t *d_coeffs, uint32_t coeff_bytes,
+                                           uint32_t *d_verdict_out) {
+    if (!d_verdict_out) return SSA_ERR_ARG;
+    return msm_run(ctx, {d_sigs, d_pks, d_pk_inf, {d_msgs, d_msg_off, msg_stride, msg_len}}, n, d_coeffs, coeff_bytes,
+                   d_verdict_out, nullptr);
 }
 
 // the device-buffer form: what one rank of a process-per-GPU job calls on its shard (the records then travel by
@@ -1460,121 +1516,27 @@ extern "C" int ssa_verify_batch_msm_partial_device(ssa_ctx *ctx, const uint8_t *
                                                    const uint8_t *d_coeffs, uint32_t coeff_bytes,
                                                    uint64_t *d_partial_out) {
     if (!d_partial_out) return SSA_ERR_ARG;
-    return msm_run(ctx, d_sigs, d_pks, d_pk_inf, d_msgs, d_msg_off, msg_stride, msg_len, n, d_coeffs, coeff_bytes, nullptr,
-                   (u64 *)d_partial_out);
+    return msm_run(ctx, {d_sigs, d_pks, d_pk_inf, {d_msgs, d_msg_off, msg_stride, msg_len}}, n, d_coeffs, coeff_bytes,
+                   nullptr, (u64 *)d_partial_out);
 }
 
-namespace ssa {
-// k partial records (24-word stride) -> the layout msm_k_finish reads: k points of 18 words, k scalars of 4 words, and
-// the OR of the malformed flags
-__global__ void msm_k_unpack_parts(const u64 *__restrict__ parts, u32 k, u64 *__restrict__ pts, u64 *__restrict__ lins,
-                                   u32 *__restrict__ malformed) {
-    const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= k * 24u) return;
-    const u32 j = t / 24u, w = t % 24u;
-    const u64 v = parts[t];
-    if (w < 18) {
-        pts[18u * j + w] = v;
-        if (v >= FP_P) atomicOr(malformed, 1u);                 // limbs of a record are canonical
-    } else if (w < 22) {
-        lins[4u * j + (w - 18u)] = v;
-    } else if (w == 22) {
-        if (v != 0) atomicOr(malformed, 1u);
-    } else if (v != SSA_MSM_RECORD_MAGIC) {
-        atomicOr(malformed, 1u);   // not a record of this format: never written (all zero), foreign version, garbled
-    }
-}
-
-// One lane per record: the scalar is canonical (< q) and the point is the identity (Z = 0) or satisfies the Jacobian
-// curve equation Y^2 = X^3 + X Z^4 + (u + 395) Z^6.  Records cross process boundaries (all-gather): a corrupted or
-// foreign one gives SSA_MALFORMED, never an arbitrary verdict.  k <= 4096: the cost is one short launch.
-__global__ void __launch_bounds__(64)
-msm_k_check_parts(const u64 *__restrict__ parts, u32 k, u32 *__restrict__ malformed) {
-    const u32 j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= k) return;
-    const u64 *r = parts + 24u * (size_t)j;
-    bool ok = true;
-    fp6 X, Y, Z;
-#pragma unroll
-    for (int c = 0; c < 6; c++) {
-        X.c[c] = r[c];
-        Y.c[c] = r[6 + c];
-        Z.c[c] = r[12 + c];
-        ok = ok && X.c[c] < FP_P && Y.c[c] < FP_P && Z.c[c] < FP_P;
-    }
-    sc256 lin;
-#pragma unroll
-    for (int c = 0; c < 4; c++) lin.w[c] = r[18 + c];
-    ok = ok && !sc_geq_q(lin);
-    if (ok && !f6_is_zero(Z)) {
-        const fp6 z2 = f6_sqr(Z), z4 = f6_sqr(z2), z6 = f6_mul(z4, z2);
-        fp6 b = f6_zero();
-        b.c[0] = 395ull;
-        b.c[1] = 1ull;
-        const fp6 rhs = f6_add(f6_add(f6_mul(f6_sqr(X), X), f6_mul(X, z4)), f6_mul(b, z6));
-        ok = f6_eq(f6_sqr(Y), rhs);
-    }
-    if (!ok) atomicOr(malformed, 1u);
-}
-}  // namespace ssa
-
-// The shards added up on one device: one Jacobian addition per shard, the scalars mod q, [lin]G from the comb table and
-// the x-only comparison (src/batch.rs:98-100,123-129) -- msm_k_finish with no doublings between its "windows".
-static int msm_combine_records(ssa_ctx *ctx, const u64 *d_records, size_t k, uint32_t *d_verdict_out, u64 *d_partial_out,
-                               bool check_points) {
-    if (ctx->msm_comb_pts.reserve(18 * k * sizeof(u64)) || ctx->msm_comb_lins.reserve(4 * k * sizeof(u64)) ||
-        ctx->msm_flags.reserve(64))
-        return SSA_ERR_HIP;
-    HIP_TRY(hipMemsetAsync(ctx->msm_flags.p, 0, 64, ctx->stream));
-    hipLaunchKernelGGL(msm_k_unpack_parts, dim3(grid_for(k * 24, 256)), dim3(256), 0, ctx->stream, d_records, (u32)k,
-                       (u64 *)ctx->msm_comb_pts.p, (u64 *)ctx->msm_comb_lins.p, (u32 *)ctx->msm_flags.p);
-    HIP_TRY(hipGetLastError());
-    if (check_points) {
-        hipLaunchKernelGGL(msm_k_check_parts, dim3(grid_for(k, 64)), dim3(64), 0, ctx->stream, d_records, (u32)k,
-                           (u32 *)ctx->msm_flags.p);
-        HIP_TRY(hipGetLastError());
-    }
-    MsmShape sh;
-    sh.c = 0;
-    sh.windows = (u32)k;
-    sh.buckets = 1;
-    sh.chunks = 1;
-    return timed_launch(ctx, "msm_combine", [&] {
-        hipLaunchKernelGGL(msm_k_finish, dim3(1), dim3(128), 0, ctx->stream, (const u64 *)ctx->msm_comb_pts.p, sh,
-                           (const u64 *)ctx->msm_comb_lins.p, (u32)k, (const u64 *)ctx->d_gtab,
-                           (const u32 *)ctx->msm_flags.p, d_verdict_out, d_partial_out);
-    });
-}
-
-extern "C" int ssa_msm_combine_device(ssa_ctx *ctx, const uint64_t *d_parts24, size_t k, uint32_t *d_verdict_out) {
-    if (!ctx || !d_parts24 || !d_verdict_out || k == 0 || k > 4096) return SSA_ERR_ARG;
-    HIP_TRY(hipSetDevice(ctx->device));
-    return msm_combine_records(ctx, (const u64 *)d_parts24, k, d_verdict_out, nullptr, true);
-}
-
-extern "C" int ssa_msm_combine(ssa_ctx *ctx, const uint64_t *parts24, size_t k) {
-    if (!ctx || !parts24 || k == 0 || k > 4096) return SSA_ERR_ARG;
+// ONE slice (n <= ctx->msm_slice) from host buffers: the verdict (out24 == nullptr) or the slice's 24-word record
+static int msm_host_one(ssa_ctx *ctx, const HostBatch &b, size_t n, const uint8_t *coeffs, int *verdict_out,
+                        uint64_t *out24) {
     HostCall hc(ctx);
-    const uint64_t *d_parts = hc.in<uint64_t>(ctx->st_aux, parts24, k * SSA_MSM_PARTIAL_WORDS * sizeof(uint64_t));
-    uint32_t v = SSA_MALFORMED, *d_verdict = (uint32_t *)((char *)ctx->ws_fail.p + 32);
-    hc.copy_back(&v, d_verdict, sizeof v);
-    const int rc = hc.finish([&] { return ssa_msm_combine_device(ctx, d_parts, k, d_verdict); });
-    return rc ? rc : (int)v;
-}
-
-extern "C" int ssa_verify_batch_msm(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_inf,
-                                    const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len,
-                                    size_t n, const uint8_t *coeffs) {
-    if (!ctx || (n && (!sigs || !pks))) return SSA_ERR_ARG;
-    if (int rc = check_msgs(msgs, msg_off, msg_stride, msg_len, n)) return rc;
-    if (int rc = check_host_offsets(msg_off, n)) return rc;
-    if (n == 0) return SSA_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const HostBatch b{sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len};
-    int verdict = SSA_MALFORMED;
-    const int rc = n > ctx->msm_slice ? msm_host_sliced(ctx, b, n, coeffs, &verdict, nullptr)
-                                      : msm_host_one(ctx, b, n, coeffs, &verdict, nullptr);
-    return rc ? rc : verdict;
+    uint32_t v = SSA_MALFORMED, *d_verdict = out24 ? nullptr : (uint32_t *)((char *)ctx->ws_fail.p + 32);
+    u64 *d_rec = out24 ? (u64 *)hc.out(ctx->st_aux2, nullptr, SSA_MSM_PARTIAL_WORDS * sizeof(u64)) : nullptr;
+    // Scalar::random(rng) (src/batch.rs:75-78): caller-supplied 32-byte scalars, or (coeffs == NULL) 128-bit
+    // coefficients drawn on the device from a ChaCha20 stream keyed with getrandom(2).  A large batch: uploads in
+    // chunks, the hashes (62 % of this form) behind them.
+    PipelinedInputs pin;      // its destructor drains the side streams on every error return
+    const StagedInputs s = slice_inputs(hc, pin, b, n, coeffs, true, false);
+    if (out24) hc.copy_back(out24, d_rec, SSA_MSM_PARTIAL_WORDS * sizeof(u64));
+    else hc.copy_back(&v, d_verdict, sizeof v);
+    if (int rc = hc.finish([&] { return msm_run(ctx, s.batch, n, s.coeffs, 32, d_verdict, d_rec, s.hashed); })) return rc;
+    pin.done();
+    if (verdict_out) *verdict_out = (int)v;
+    return 0;
 }
 
 // A host batch of more than one MSM slice in bounded device memory (round 5): slice after slice through the one-slice
@@ -1603,34 +1565,45 @@ static int msm_host_sliced(ssa_ctx *ctx, const HostBatch &b, size_t n, const uin
     return 0;
 }
 
-// ONE slice (n <= ctx->msm_slice) from host buffers: the verdict (out24 == nullptr) or the slice's 24-word record
-static int msm_host_one(ssa_ctx *ctx, const HostBatch &b, size_t n, const uint8_t *coeffs, int *verdict_out,
-                        uint64_t *out24) {
-    HostCall hc(ctx);
-    uint32_t v = SSA_MALFORMED, *d_verdict = out24 ? nullptr : (uint32_t *)((char *)ctx->ws_fail.p + 32);
-    u64 *d_rec = out24 ? (u64 *)hc.out(ctx->st_aux2, nullptr, SSA_MSM_PARTIAL_WORDS * sizeof(u64)) : nullptr;
-    // Scalar::random(rng) (src/batch.rs:75-78): caller-supplied 32-byte scalars, or (coeffs == NULL) 128-bit
-    // coefficients drawn on the device from a ChaCha20 stream keyed with getrandom(2).  A large batch: uploads in
-    // chunks, the hashes (62 % of this form) behind them.
-    PipelinedInputs pin;      // its destructor drains the side streams on every error return
-    const StagedInputs s = slice_inputs(hc, pin, b, n, coeffs, true, false);
-    if (out24) hc.copy_back(out24, d_rec, SSA_MSM_PARTIAL_WORDS * sizeof(u64));
-    else hc.copy_back(&v, d_verdict, sizeof v);
-    if (int rc = hc.finish([&] {
-            return msm_run(ctx, s.sigs, s.pks, s.inf, s.msgs, s.off, b.msg_stride, b.msg_len, n, s.coeffs, 32, d_verdict, d_rec,
-                           s.hashed);
-        }))
-        return rc;
-    pin.done();
-    if (verdict_out) *verdict_out = (int)v;
-    return 0;
+// One shard of a batch that spans several devices: stage the host buffers, run the MSM pipeline, return the shard's
+// 24-word partial record (left-hand point, sum s_i e_i, malformed flag) in host memory.
+extern "C" int ssa_verify_batch_msm_partial(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_inf,
+                                            const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride,
+                                            size_t msg_len, size_t n, const uint8_t *coeffs,
+                                            uint64_t out24[SSA_MSM_PARTIAL_WORDS]) {
+    if (!ctx || !out24 || (n && (!sigs || !pks))) return SSA_ERR_ARG;
+    if (int rc = check_msgs({msgs, msg_off, msg_stride, msg_len}, n)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    std::memset(out24, 0, SSA_MSM_PARTIAL_WORDS * sizeof(uint64_t));
+    if (n == 0) {
+        out24[23] = SSA_MSM_RECORD_MAGIC;    // the empty shard's record: identity, 0
+        return 0;
+    }
+    if (int rc = check_host_offsets(msg_off, n)) return rc;
+    const HostBatch b{sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len};
+    return n > ctx->msm_slice ? msm_host_sliced(ctx, b, n, coeffs, nullptr, out24)
+                              : msm_host_one(ctx, b, n, coeffs, nullptr, out24);
+}
+
+extern "C" int ssa_verify_batch_msm(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_inf,
+                                    const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len,
+                                    size_t n, const uint8_t *coeffs) {
+    if (!ctx || (n && (!sigs || !pks))) return SSA_ERR_ARG;
+    if (int rc = check_msgs({msgs, msg_off, msg_stride, msg_len}, n)) return rc;
+    if (int rc = check_host_offsets(msg_off, n)) return rc;
+    if (n == 0) return SSA_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const HostBatch b{sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len};
+    int verdict = SSA_MALFORMED;
+    const int rc = n > ctx->msm_slice ? msm_host_sliced(ctx, b, n, coeffs, &verdict, nullptr)
+                                      : msm_host_one(ctx, b, n, coeffs, &verdict, nullptr);
+    return rc ? rc : verdict;
 }
 
 // ------------------------------------------------------------------------------------------------
 // Screened batch verification: the MSM above with its buckets keyed by (window, segment, digit)
 // gives one sum per contiguous segment of the slice in one pass; a segment whose equation holds exactly is accepted as a
 // whole, and only the lanes of failing segments run the exact per-lane kernel, on the challenge scalars the MSM hashed.
-constexpr u32 SCREEN_C = 8;                 // window bits: K * 2^(c-1) <= 256 * 128 stays within the grouping grid
 constexpr u32 SCREEN_MAX_SEGS = 256;
 constexpr u32 SCREEN_MIN_SEG_LANES = 1024;  // automatic K: the largest power of two <= 256 whose segments hold this many
 
@@ -1648,15 +1621,6 @@ static ScreenPlan screen_plan(size_t n, unsigned forced) {
     size_t per = (n + k - 1) / k;
     per = (per + 255) & ~(size_t)255;
     return {(u32)((n + per - 1) / per), (u32)per};
-}
-
-static MsmShape screen_shape(u32 segs) {
-    MsmShape sh;
-    sh.c = SCREEN_C;
-    sh.windows = (255 + sh.c - 1) / sh.c;
-    sh.buckets = segs << (sh.c - 1);
-    sh.chunks = sh.buckets / (u32)MSM_CHUNK;
-    return sh;
 }
 
 extern "C" int ssa_debug_screen_plan(size_t n, uint32_t coeff_bytes, uint64_t out[8]) {
@@ -1685,23 +1649,19 @@ extern "C" int ssa_debug_screen_segments(ssa_ctx *ctx, uint32_t k) {
 
 // ONE slice (n <= ctx->msm_slice) on ctx->stream into d_status[0, n): d_h = the slice's challenge scalars if they exist
 // (else they are computed into ctx->ws_h).  Synchronises the stream once, to read the segment verdicts.
-static int screen_slice(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_pk_inf,
-                        const uint8_t *d_msgs, const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len, size_t n,
-                        const uint8_t *d_coeffs, uint32_t coeff_bytes, const u64 *d_h, uint8_t *d_status) {
+static int screen_slice(ssa_ctx *ctx, const DevBatch &b, size_t n, const uint8_t *d_coeffs, uint32_t coeff_bytes,
+                        const u64 *d_h, uint8_t *d_status) {
     if (ctx->scr_fail.reserve(16)) return SSA_ERR_HIP;
     unsigned long long *scratch_fail = (unsigned long long *)ctx->scr_fail.p;    // (the caller counts the statuses)
     if (n <= ctx->msm_small_max) {      // the exact per-lane path
-        if (d_h) return ssa_internal_verify_hashed(ctx, d_sigs, d_pks, d_pk_inf, d_h, n, SSA_FLAG_SIG_FLAG_BYTE, d_status,
-                                                   scratch_fail);
-        return ssa_verify_many_device(ctx, d_sigs, d_pks, d_pk_inf, d_msgs, d_msg_off, msg_stride, msg_len, n,
+        if (d_h) return ssa_internal_verify_hashed(ctx, b, d_h, n, SSA_FLAG_SIG_FLAG_BYTE, d_status, scratch_fail);
+        return ssa_verify_many_device(ctx, b.sigs, b.pks, b.pk_inf, b.msgs.msgs, b.msgs.off, b.msgs.stride, b.msgs.len, n,
                                       SSA_FLAG_SIG_FLAG_BYTE, d_status, (uint64_t *)scratch_fail);
     }
     const ScreenPlan pl = screen_plan(n, ctx->screen_segs);
     if (ctx->scr_ok.reserve(SCREEN_MAX_SEGS)) return SSA_ERR_HIP;
     const ScreenArgs sa{pl.segs, pl.seg_lanes / 256u, d_status, (u8 *)ctx->scr_ok.p};
-    if (int rc = msm_run_one(ctx, d_sigs, d_pks, d_pk_inf, d_msgs, d_msg_off, msg_stride, msg_len, n, d_coeffs, coeff_bytes,
-                             nullptr, nullptr, d_h, &sa))
-        return rc;
+    if (int rc = msm_run_one(ctx, b, n, d_coeffs, coeff_bytes, nullptr, nullptr, d_h, &sa)) return rc;
     const u64 *h = d_h ? d_h : (const u64 *)ctx->ws_h.p;     // (msm_run_one hashed into ws_h)
     uint8_t ok[SCREEN_MAX_SEGS];
     HIP_TRY(hipMemcpyAsync(ok, ctx->scr_ok.p, pl.segs, hipMemcpyDeviceToHost, ctx->stream));
@@ -1719,19 +1679,20 @@ static int screen_slice(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pk
     if (m == 0) return 0;
     // Most of the slice fails (e.g. one bad lane in every segment): no gather, the per-lane kernel over all of it.
     if (2 * m > n)
-        return ssa_internal_verify_hashed(ctx, d_sigs, d_pks, d_pk_inf, h, n, SSA_FLAG_SIG_FLAG_BYTE, d_status, scratch_fail);
+        return ssa_internal_verify_hashed(ctx, b, h, n, SSA_FLAG_SIG_FLAG_BYTE, d_status, scratch_fail);
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t o_pks = al(m * 81), o_h = o_pks + al(m * 96), o_inf = o_h + al(m * 32), total = o_inf + al(m);
     if (ctx->scr_in.reserve(total) || ctx->scr_status.reserve(m + 16)) return SSA_ERR_HIP;
     u8 *g = (u8 *)ctx->scr_in.p;
     int rc = timed_launch(ctx, "screen_gather", [&] {
         const unsigned gx = grid_for((size_t)pl.seg_lanes * 210u / 16u, 256u * 4u);   // ~4 vectors per thread
-        hipLaunchKernelGGL(msm_k_screen_gather, dim3(gx, sl.count), dim3(256), 0, ctx->stream, sl, d_sigs, d_pks, d_pk_inf,
+        hipLaunchKernelGGL(msm_k_screen_gather, dim3(gx, sl.count), dim3(256), 0, ctx->stream, sl, b.sigs, b.pks, b.pk_inf,
                            h, g, g + o_pks, g + o_inf, (u64 *)(g + o_h));
     });
     if (rc) return rc;
-    if ((rc = ssa_internal_verify_hashed(ctx, g, g + o_pks, d_pk_inf ? g + o_inf : nullptr, (const u64 *)(g + o_h), m,
-                                         SSA_FLAG_SIG_FLAG_BYTE, (u8 *)ctx->scr_status.p, scratch_fail)))
+    const DevBatch gathered{g, g + o_pks, b.pk_inf ? g + o_inf : nullptr, {}};
+    if ((rc = ssa_internal_verify_hashed(ctx, gathered, (const u64 *)(g + o_h), m, SSA_FLAG_SIG_FLAG_BYTE,
+                                         (u8 *)ctx->scr_status.p, scratch_fail)))
         return rc;
     return timed_launch(ctx, "screen_scatter", [&] {
         hipLaunchKernelGGL(msm_k_screen_scatter, dim3(grid_for(m, 256)), dim3(256), 0, ctx->stream, sl, m,
@@ -1750,12 +1711,13 @@ extern "C" int ssa_verify_batch_screened_device(ssa_ctx *ctx, const uint8_t *d_s
                                                 const uint8_t *d_pk_inf, const uint8_t *d_msgs, const uint64_t *d_msg_off,
                                                 size_t msg_stride, size_t msg_len, size_t n, const uint8_t *d_coeffs,
                                                 uint32_t coeff_bytes, uint8_t *d_status_out, uint64_t *d_n_fail_out) {
+    const DevBatch b{d_sigs, d_pks, d_pk_inf, {d_msgs, d_msg_off, msg_stride, msg_len}};
     if (!ctx || (n && (!d_sigs || !d_pks || !d_status_out))) return SSA_ERR_ARG;
     if (d_coeffs && (coeff_bytes == 0 || coeff_bytes > 32)) return SSA_ERR_ARG;
-    if (int rc = check_msgs(d_msgs, d_msg_off, msg_stride, msg_len, n)) return rc;
+    if (int rc = check_msgs(b.msgs, n)) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
-    unsigned long long *d_fail = d_n_fail_out ? (unsigned long long *)d_n_fail_out : (unsigned long long *)ctx->ws_fail.p;
-    HIP_TRY(hipMemsetAsync(d_fail, 0, sizeof(unsigned long long), ctx->stream));
+    unsigned long long *d_fail;
+    if (int rc = reset_fail_counter(ctx, d_n_fail_out, &d_fail)) return rc;
     if (n == 0) return 0;
     if (n <= ctx->msm_small_max)
         return ssa_verify_many_device(ctx, d_sigs, d_pks, d_pk_inf, d_msgs, d_msg_off, msg_stride, msg_len, n,
@@ -1763,11 +1725,8 @@ extern "C" int ssa_verify_batch_screened_device(ssa_ctx *ctx, const uint8_t *d_s
     const size_t slice = ctx->msm_slice;
     for (size_t lo = 0; lo < n; lo += slice) {      // segments never straddle two slices
         const size_t cnt = n - lo < slice ? n - lo : slice;
-        if (int rc = screen_slice(ctx, d_sigs + 81 * lo, d_pks + 96 * lo, d_pk_inf ? d_pk_inf + lo : nullptr,
-                                  d_msg_off ? d_msgs : (d_msgs ? d_msgs + lo * msg_stride : nullptr),
-                                  d_msg_off ? d_msg_off + lo : nullptr, msg_stride, msg_len, cnt,
-                                  d_coeffs ? d_coeffs + (size_t)coeff_bytes * lo : nullptr, coeff_bytes, nullptr,
-                                  d_status_out + lo))
+        if (int rc = screen_slice(ctx, b.slice(lo), cnt, d_coeffs ? d_coeffs + (size_t)coeff_bytes * lo : nullptr, coeff_bytes,
+                                  nullptr, d_status_out + lo))
             return rc;
     }
     return screen_count(ctx, d_status_out, n, d_fail);
@@ -1783,8 +1742,7 @@ static int screen_host_one(ssa_ctx *ctx, const HostBatch &b, size_t n, const uin
     unsigned long long v = 0, *d_fail = (unsigned long long *)ctx->ws_fail.p;
     hc.copy_back(&v, d_fail, sizeof v);
     if (int rc = hc.finish([&] {
-            if (int r = screen_slice(ctx, s.sigs, s.pks, s.inf, s.msgs, s.off, b.msg_stride, b.msg_len, n, s.coeffs, 32,
-                                     s.hashed ? (const u64 *)ctx->ws_h.p : nullptr, d_status))
+            if (int r = screen_slice(ctx, s.batch, n, s.coeffs, 32, s.hashed ? (const u64 *)ctx->ws_h.p : nullptr, d_status))
                 return r;
             return screen_count(ctx, d_status, n, d_fail);
         }))
@@ -1798,7 +1756,7 @@ extern "C" int ssa_verify_batch_screened(ssa_ctx *ctx, const uint8_t *sigs, cons
                                          const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len,
                                          size_t n, const uint8_t *coeffs, uint8_t *status_out, uint64_t *n_fail_out) {
     if (!ctx || (n && (!sigs || !pks || !status_out))) return SSA_ERR_ARG;
-    if (int rc = check_msgs(msgs, msg_off, msg_stride, msg_len, n)) return rc;
+    if (int rc = check_msgs({msgs, msg_off, msg_stride, msg_len}, n)) return rc;
     if (int rc = check_host_offsets(msg_off, n)) return rc;
     if (n_fail_out) *n_fail_out = 0;
     if (n == 0) return 0;

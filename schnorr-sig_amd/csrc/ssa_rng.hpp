@@ -167,24 +167,20 @@ static int rng_draw_slices(ssa_ctx *ctx, size_t n, F &&consume) {
     return 0;
 }
 
-// the messages of lanes lo.. of a call: offsets are absolute into d_msgs, dense messages move by the stride
-static inline const uint8_t *rng_msgs_at(const uint8_t *d_msgs, const uint64_t *d_off, size_t stride, size_t lo) {
-    return d_off || !d_msgs ? d_msgs : d_msgs + lo * stride;
-}
-
 extern "C" int ssa_keygen_sign_many_rng_device(ssa_ctx *ctx, const uint8_t *d_sks, const uint8_t *d_msgs,
                                                const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len, size_t n,
                                                uint32_t flags, uint8_t *d_pks_out, uint8_t *d_sigs_out) {
     if (!ctx || (flags & ~(SSA_FLAG_SIGN_CT | SSA_FLAG_SIGN_KEYED))) return SSA_ERR_ARG;
     const bool keyed = (flags & SSA_FLAG_SIGN_KEYED) != 0;
     if (n && (!d_sks || !d_sigs_out || (!keyed && !d_pks_out))) return SSA_ERR_ARG;
-    if (int rc = check_msgs(d_msgs, d_msg_off, msg_stride, msg_len, n)) return rc;
+    const DevBatch b{nullptr, nullptr, nullptr, {d_msgs, d_msg_off, msg_stride, msg_len}};     // (the messages only)
+    if (int rc = check_msgs(b.msgs, n)) return rc;
     if (n == 0) return 0;
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t rec = keyed ? 130 : 81;
     return rng_draw_slices(ctx, n, [&](size_t lo, size_t cnt, const u8 *d_nonces) {
-        return ssa_keygen_sign_many_ex_device(ctx, d_sks + 32 * lo, d_nonces, rng_msgs_at(d_msgs, d_msg_off, msg_stride, lo),
-                                              d_msg_off ? d_msg_off + lo : nullptr, msg_stride, msg_len, cnt, flags,
+        const MsgView mv = b.slice(lo).msgs;
+        return ssa_keygen_sign_many_ex_device(ctx, d_sks + 32 * lo, d_nonces, mv.msgs, mv.off, mv.stride, mv.len, cnt, flags,
                                               d_pks_out ? d_pks_out + 96 * lo : nullptr, d_sigs_out + rec * lo);
     });
 }
@@ -195,7 +191,7 @@ extern "C" int ssa_keygen_sign_many_rng(ssa_ctx *ctx, const uint8_t *sks, const 
     if (!ctx || (flags & ~(SSA_FLAG_SIGN_CT | SSA_FLAG_SIGN_KEYED))) return SSA_ERR_ARG;
     const bool keyed = (flags & SSA_FLAG_SIGN_KEYED) != 0;
     if (n && (!sks || !sigs_out || (!keyed && !pks_out))) return SSA_ERR_ARG;
-    if (int rc = check_msgs(msgs, msg_off, msg_stride, msg_len, n)) return rc;
+    if (int rc = check_msgs({msgs, msg_off, msg_stride, msg_len}, n)) return rc;
     if (int rc = check_host_offsets(msg_off, n)) return rc;
     if (n == 0) return 0;
     if (!scalars_canonical_nonzero(sks, n)) return SSA_ERR_ARG;
@@ -214,14 +210,14 @@ extern "C" int ssa_sign_many_indexed_rng_device(ssa_ctx *ctx, ssa_signer_set *ss
                                                 uint8_t *d_status_out) {
     if (!ctx || !ss || ss->ctx != ctx || (flags & ~(SSA_FLAG_SIGN_CT | SSA_FLAG_SIGN_KEYED))) return SSA_ERR_ARG;
     if (n && (!d_key_idx || !d_sigs_out)) return SSA_ERR_ARG;
-    if (int rc = check_msgs(d_msgs, d_msg_off, msg_stride, msg_len, n)) return rc;
+    const DevBatch b{nullptr, nullptr, nullptr, {d_msgs, d_msg_off, msg_stride, msg_len}};     // (the messages only)
+    if (int rc = check_msgs(b.msgs, n)) return rc;
     if (n == 0) return 0;
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t rec = (flags & SSA_FLAG_SIGN_KEYED) ? 130 : 81;
     return rng_draw_slices(ctx, n, [&](size_t lo, size_t cnt, const u8 *d_nonces) {
-        return ssa_sign_many_indexed_device(ctx, ss, d_key_idx + lo, d_nonces,
-                                            rng_msgs_at(d_msgs, d_msg_off, msg_stride, lo),
-                                            d_msg_off ? d_msg_off + lo : nullptr, msg_stride, msg_len, cnt, flags,
+        const MsgView mv = b.slice(lo).msgs;
+        return ssa_sign_many_indexed_device(ctx, ss, d_key_idx + lo, d_nonces, mv.msgs, mv.off, mv.stride, mv.len, cnt, flags,
                                             d_sigs_out + rec * lo, d_status_out ? d_status_out + lo : nullptr);
     });
 }
@@ -231,7 +227,7 @@ extern "C" int ssa_sign_many_indexed_rng(ssa_ctx *ctx, ssa_signer_set *ss, const
                                          uint32_t flags, uint8_t *sigs_out) {
     if (!ctx || !ss || ss->ctx != ctx || (flags & ~(SSA_FLAG_SIGN_CT | SSA_FLAG_SIGN_KEYED))) return SSA_ERR_ARG;
     if (n && (!key_idx || !sigs_out)) return SSA_ERR_ARG;
-    if (int rc = check_msgs(msgs, msg_off, msg_stride, msg_len, n)) return rc;
+    if (int rc = check_msgs({msgs, msg_off, msg_stride, msg_len}, n)) return rc;
     if (int rc = check_host_offsets(msg_off, n)) return rc;
     if (n == 0) return 0;
     for (size_t i = 0; i < n; i++)                 // (indices are public)

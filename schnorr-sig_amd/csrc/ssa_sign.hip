@@ -413,12 +413,10 @@ ssa_k_sign_indexed_ct(const DevParams *__restrict__ prm, const u64 *__restrict__
 }  // namespace ssa
 
 // ------------------------------------------------------------------------------------------------------------------
-int ssa_internal_sign_vartime(ssa_ctx *ctx, const uint8_t *d_sks, const uint8_t *d_nonces, const uint8_t *d_msgs,
-                              const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len, size_t n, uint8_t *d_pks_out,
-                              uint8_t *d_sigs_out);     // ssa_api.hip: the throughput signer's launch
+int ssa_internal_sign_vartime(ssa_ctx *ctx, const uint8_t *d_sks, const uint8_t *d_nonces, const MsgView &mv, size_t n,
+                              uint8_t *d_pks_out, uint8_t *d_sigs_out);     // ssa_api.hip: the throughput signer's launch
 int ssa_internal_sign_indexed_vartime(ssa_ctx *ctx, const ssa_signer_set *ss, const uint32_t *d_key_idx,
-                                      const uint8_t *d_nonces, const uint8_t *d_msgs, const uint64_t *d_msg_off,
-                                      size_t msg_stride, size_t msg_len, size_t n, bool keyed, uint8_t *d_out,
+                                      const uint8_t *d_nonces, const MsgView &mv, size_t n, bool keyed, uint8_t *d_out,
                                       uint8_t *d_status_out);    // ssa_api.hip: the same for a signer set
 
 // the exact check of the tables (ssa_k_gtab_check, ssa_k_ctab_check_b) and its test hooks
@@ -465,7 +463,8 @@ extern "C" int ssa_keygen_sign_many_ex_device(ssa_ctx *ctx, const uint8_t *d_sks
     if (!ctx || (flags & ~(SSA_FLAG_SIGN_CT | SSA_FLAG_SIGN_KEYED))) return SSA_ERR_ARG;
     const bool keyed = (flags & SSA_FLAG_SIGN_KEYED) != 0;
     if (n && (!d_sks || !d_nonces || !d_sigs_out || (!keyed && !d_pks_out))) return SSA_ERR_ARG;
-    if (int rc = check_msgs(d_msgs, d_msg_off, msg_stride, msg_len, n)) return rc;
+    const MsgView mv{d_msgs, d_msg_off, msg_stride, msg_len};
+    if (int rc = check_msgs(mv, n)) return rc;
     if (n == 0) return 0;
     HIP_TRY(hipSetDevice(ctx->device));
     // keyed output: the 81-byte signatures (and the keys, when the caller does not want them) pass through the context
@@ -477,13 +476,12 @@ extern "C" int ssa_keygen_sign_many_ex_device(ssa_ctx *ctx, const uint8_t *d_sks
     }
     if (flags & SSA_FLAG_SIGN_CT) {
         if (int rc = ensure_ctab(ctx)) return rc;
-        MsgView mv{d_msgs, d_msg_off, msg_stride, msg_len};
         int rc = timed_launch(ctx, "ssa_k_sign_ct", [&] {
             hipLaunchKernelGGL(ssa_k_sign_ct, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, ctx->d_params,
                                (const u64 *)ctx->ctab.p, (const u64 *)ctx->d_gtab, d_sks, d_nonces, mv, n, pks, sigs);
         });
         if (rc) return rc;
-    } else if (int rc = ssa_internal_sign_vartime(ctx, d_sks, d_nonces, d_msgs, d_msg_off, msg_stride, msg_len, n, pks, sigs)) {
+    } else if (int rc = ssa_internal_sign_vartime(ctx, d_sks, d_nonces, mv, n, pks, sigs)) {
         return rc;
     }
     if (keyed) {
@@ -551,7 +549,7 @@ extern "C" int ssa_keygen_sign_many_ex(ssa_ctx *ctx, const uint8_t *sks, const u
     if (!ctx || (flags & ~(SSA_FLAG_SIGN_CT | SSA_FLAG_SIGN_KEYED))) return SSA_ERR_ARG;
     const bool keyed = (flags & SSA_FLAG_SIGN_KEYED) != 0;
     if (n && (!sks || !nonces || !sigs_out || (!keyed && !pks_out))) return SSA_ERR_ARG;
-    if (int rc = check_msgs(msgs, msg_off, msg_stride, msg_len, n)) return rc;
+    if (int rc = check_msgs({msgs, msg_off, msg_stride, msg_len}, n)) return rc;
     if (int rc = check_host_offsets(msg_off, n)) return rc;
     if (n == 0) return 0;
     if (!scalars_canonical_nonzero(sks, n) || !scalars_canonical_nonzero(nonces, n)) return SSA_ERR_ARG;
@@ -694,15 +692,14 @@ extern "C" int ssa_sign_many_indexed_device(ssa_ctx *ctx, ssa_signer_set *ss, co
                                             uint8_t *d_sigs_out, uint8_t *d_status_out) {
     if (!ctx || !ss || ss->ctx != ctx || (flags & ~(SSA_FLAG_SIGN_CT | SSA_FLAG_SIGN_KEYED))) return SSA_ERR_ARG;
     if (n && (!d_key_idx || !d_nonces || !d_sigs_out)) return SSA_ERR_ARG;
-    if (int rc = check_msgs(d_msgs, d_msg_off, msg_stride, msg_len, n)) return rc;
+    const MsgView mv{d_msgs, d_msg_off, msg_stride, msg_len};
+    if (int rc = check_msgs(mv, n)) return rc;
     if (n == 0) return 0;
     HIP_TRY(hipSetDevice(ctx->device));
     const bool keyed = (flags & SSA_FLAG_SIGN_KEYED) != 0;
     if (!(flags & SSA_FLAG_SIGN_CT))
-        return ssa_internal_sign_indexed_vartime(ctx, ss, d_key_idx, d_nonces, d_msgs, d_msg_off, msg_stride, msg_len, n,
-                                                 keyed, d_sigs_out, d_status_out);
+        return ssa_internal_sign_indexed_vartime(ctx, ss, d_key_idx, d_nonces, mv, n, keyed, d_sigs_out, d_status_out);
     if (int rc = ensure_ctab(ctx)) return rc;
-    MsgView mv{d_msgs, d_msg_off, msg_stride, msg_len};
     return timed_launch(ctx, "ssa_k_sign_indexed_ct", [&] {
         hipLaunchKernelGGL(ssa_k_sign_indexed_ct, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, ctx->d_params,
                            (const u64 *)ctx->ctab.p, (const u64 *)ctx->d_gtab, ss->view(), d_key_idx, d_nonces, mv, n,
@@ -715,7 +712,7 @@ extern "C" int ssa_sign_many_indexed(ssa_ctx *ctx, ssa_signer_set *ss, const uin
                                      size_t n, uint32_t flags, uint8_t *sigs_out) {
     if (!ctx || !ss || ss->ctx != ctx || (flags & ~(SSA_FLAG_SIGN_CT | SSA_FLAG_SIGN_KEYED))) return SSA_ERR_ARG;
     if (n && (!key_idx || !nonces || !sigs_out)) return SSA_ERR_ARG;
-    if (int rc = check_msgs(msgs, msg_off, msg_stride, msg_len, n)) return rc;
+    if (int rc = check_msgs({msgs, msg_off, msg_stride, msg_len}, n)) return rc;
     if (int rc = check_host_offsets(msg_off, n)) return rc;
     if (n == 0) return 0;
     for (size_t i = 0; i < n; i++)                 // (indices are public)
