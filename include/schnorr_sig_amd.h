@@ -13,6 +13,7 @@
  *                              combination + 2n-point MSM)     src/batch.rs:56-130
  *   ssa_verify_many         <- n x Signature::verify (the per-signature accept/reject vector
  *                              BASELINE.json's north_star asks for)
+ *   ssa_verify_many_dedup   <- the same over a slice in which keys repeat: each distinct key is checked once
  *   ssa_hash_message_many   <- hash_message                 src/signature.rs:274-306
  *   ssa_rescue_hash_many    <- RescueHash::hash_field       src/signature.rs:303
  *   ssa_verify_keyed_many   <- KeyedSignature::{from_bytes, verify}  src/signature.rs:232-271
@@ -439,6 +440,39 @@ int ssa_verify_many_indexed_device(ssa_ctx *ctx, ssa_keyset *ks, const uint32_t 
                                    size_t msg_len, size_t n, uint32_t flags, uint8_t *d_status_out,
                                    uint64_t *d_n_fail_out);
 
+/* ---- ssa_verify_many with each DISTINCT public key of a slice checked once --------------
+ * Real batches repeat keys (a block or a mempool holds many signatures by far fewer accounts; the reference's own batch
+ * test reuses keys, src/batch.rs:152-175), and the subgroup check [q]P == O of SSA_FLAG_CHECK_TORSION -- about 40 % of
+ * that mode's time -- depends on the key alone.  These calls take the arguments of ssa_verify_many[_device] and return
+ * the same status vector, lane for lane, and the same *n_fail_out, for any flags: no key set, no handle, no index from
+ * the caller, no allocation per call.  Per slice of at most SSA_LANE_SLICE lanes the device finds the distinct keys
+ * (two lanes share a key only when their 96 key bytes are equal AND their pk_inf flags agree as booleans: equality is
+ * decided on the bytes; a keyed 64-bit fingerprint only picks the candidates), runs the limb, curve and subgroup
+ * checks and the table of sixteen multiples once per distinct key, and starts every lane at the ladder.
+ * Non-canonical and off-curve keys take part like any other bytes: they are found malformed once, and every lane
+ * that holds them is SSA_MALFORMED.
+ *   - Policy per slice (u: its distinct keys), from the measured table of DESIGN.md section 14.  With
+ *     SSA_FLAG_CHECK_TORSION the keyed route is taken whenever u < lanes: it was faster at every u measured below all-
+ *     distinct (2^20 lanes: 34.7 ms against 56.7 at u = lanes / 16, 45.3 at lanes / 2); a slice of all-distinct keys
+ *     takes the path of ssa_verify_many, having paid for the dedup (+0.2 ms per 2^20 lanes: why these calls are
+ *     opt-in).  Without the flag there is no subgroup check to save and the keyed route measured slower at every u:
+ *     every slice takes the path of ssa_verify_many, and the dedup runs only when stats_out asks for the count.
+ *   - SSA_FLAG_FORCE_COOP, and batches that ssa_verify_many would hand to the cooperative kernel (n <= 7680, or
+ *     n <= 10496 with SSA_FLAG_CHECK_TORSION, unless SSA_FLAG_FORCE_LANE is set), take the path of ssa_verify_many
+ *     unchanged; their keys are counted only when stats_out is given.
+ *   - Both forms read u back once per slice: the _device form synchronises the context's stream once per slice (as the
+ *     screened form does) and runs the slices of a larger batch one after the other on that stream.
+ * stats_out (optional, HOST memory in both forms): [0] distinct keys summed over the slices, [1] slices that took the
+ * keyed route, [2] slices that fell back (or went to the cooperative kernel), [3] lanes that hit the probe bound of the
+ * dedup table and became keys of their own -- always correct, it only costs time (0 on honest inputs). */
+int ssa_verify_many_dedup(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_inf,
+                          const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len, size_t n,
+                          uint32_t flags, uint8_t *status_out, uint64_t *n_fail_out, uint64_t stats_out[4]);
+int ssa_verify_many_dedup_device(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_pk_inf,
+                                 const uint8_t *d_msgs, const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len,
+                                 size_t n, uint32_t flags, uint8_t *d_status_out, uint64_t *d_n_fail_out,
+                                 uint64_t stats_out[4]);
+
 /* ---- signer sets: many signatures by few signers (the signing twin of the key set) ---------------------------
  * A signer set holds m key pairs on the device: the secret key, the 96-byte affine public key, the 49-byte compressed
  * key and a per-key status.  Signature i is then KeyPair::sign (src/signature.rs:114-129) -- or, with
@@ -629,6 +663,16 @@ int ssa_debug_screen_plan(size_t n, uint32_t coeff_bytes, uint64_t out[8]);
 /* tests: the screened form on this context uses k segments per slice (k in 1..256, fewer where the slice has fewer
  * 256-lane blocks; 0 = automatic).  The statuses do not depend on k. */
 int ssa_debug_screen_segments(ssa_ctx *ctx, uint32_t k);
+/* tests of the key dedup.  ssa_debug_dedup_device runs the dedup alone over ONE slice (1 <= n <= SSA_LANE_SLICE) of
+ * device keys and optional flags: out[0] = u, out[1] = lanes that hit the probe bound; d_key_idx_out (optional, device,
+ * n words) receives each lane's key index (< u; equal for two lanes only if their 97 bytes are equal).  Returns when it is
+ * done.  ssa_debug_dedup_config sets the policy of ssa_verify_many_dedup on this context, for both flag settings: a
+ * slice takes the keyed route when u < max_distinct_ratio * lanes (0 forces the fallback, anything above 1 the keyed
+ * route; negative: the measured defaults), a lane probes at most probe_bound slots (0: the default, 128).  The statuses
+ * depend on neither. */
+int ssa_debug_dedup_device(ssa_ctx *ctx, const uint8_t *d_pks, const uint8_t *d_pk_inf, size_t n,
+                           uint32_t *d_key_idx_out, uint64_t out[2]);
+int ssa_debug_dedup_config(ssa_ctx *ctx, double max_distinct_ratio, uint32_t probe_bound);
 /* n_blocks 64-byte blocks of the ChaCha20 keystream the MSM coefficients come from (RFC 8439 known answers) */
 int ssa_debug_chacha20(ssa_ctx *ctx, const uint8_t key[32], const uint8_t nonce[12], uint32_t counter0,
                        size_t n_blocks, uint8_t *out);

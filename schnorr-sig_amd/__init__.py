@@ -203,6 +203,10 @@ def _load():
         "ssa_verify_batch_screened_device": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz, vp, u32, vp, vp]),
         "ssa_debug_screen_plan": (i32, [sz, u32, vp]),
         "ssa_debug_screen_segments": (i32, [vp, u32]),
+        "ssa_verify_many_dedup": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz, u32, vp, u64p, vp]),
+        "ssa_verify_many_dedup_device": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz, u32, vp, vp, vp]),
+        "ssa_debug_dedup_device": (i32, [vp, vp, vp, sz, vp, vp]),
+        "ssa_debug_dedup_config": (i32, [vp, C.c_double, u32]),
         "ssa_xprv_master_many": (i32, [vp, vp, sz, vp, vp]),
         "ssa_xprv_master_many_device": (i32, [vp, vp, sz, vp, vp]),
         "ssa_xprv_derive_many": (i32, [vp, vp, sz, vp, vp, sz, u32, vp, vp]),
@@ -344,6 +348,54 @@ class Engine:
         _check(_lib.ssa_verify_many(self._ctx, _ptr(sigs), _ptr(pks), _ptr(inf), _ptr(m), _ptr(off), stride,
                                     mlen, n, flags, _ptr(status), C.byref(nfail)), "ssa_verify_many")
         return status, int(nfail.value)
+
+    def verify_many_dedup(self, sigs, pks, msgs, offsets=None, check_torsion=True, pk_inf=None, mode=None,
+                          sig_flag_byte=False):
+        """verify_many with each distinct public key of a slice checked once on the GPU ->
+        (status uint8[n], n_fail, stats uint64[4]); status and n_fail are those of verify_many.  stats: distinct keys
+        summed over slices, slices on the keyed route, slices that fell back, lanes that hit the probe bound."""
+        sigs, pks = _np_u8(sigs, 81), _np_u8(pks, 96)
+        n = sigs.shape[0]
+        assert pks.shape[0] == n
+        m, off, stride, mlen = self._msg_args(msgs, offsets, n)
+        inf = _np_u8(pk_inf) if pk_inf is not None else None
+        status = np.full(n, 255, dtype=np.uint8)
+        nfail = C.c_uint64(0)
+        stats = np.zeros(4, dtype=np.uint64)
+        flags = (FLAG_CHECK_TORSION if check_torsion else 0) | _MODE_FLAGS[mode] | \
+            (FLAG_SIG_FLAG_BYTE if sig_flag_byte else 0)
+        _check(_lib.ssa_verify_many_dedup(self._ctx, _ptr(sigs), _ptr(pks), _ptr(inf), _ptr(m), _ptr(off), stride,
+                                          mlen, n, flags, _ptr(status), C.byref(nfail), stats.ctypes.data),
+               "ssa_verify_many_dedup")
+        return status, int(nfail.value), stats
+
+    def verify_many_dedup_device(self, d_sigs, d_pks, d_msgs, n, msg_len, d_status, d_nfail, msg_stride=None,
+                                 d_offsets=0, d_pk_inf=0, check_torsion=False, mode=None, sig_flag_byte=False):
+        """device form of verify_many_dedup (synchronises the stream once per slice to read the number of distinct keys);
+        returns the statistics (uint64[4], host)"""
+        flags = (FLAG_CHECK_TORSION if check_torsion else 0) | _MODE_FLAGS[mode] | \
+            (FLAG_SIG_FLAG_BYTE if sig_flag_byte else 0)
+        stats = np.zeros(4, dtype=np.uint64)
+        _check(_lib.ssa_verify_many_dedup_device(self._ctx, d_sigs, d_pks, d_pk_inf or None, d_msgs, d_offsets or None,
+                                                 msg_stride if msg_stride is not None else msg_len, msg_len, n, flags,
+                                                 d_status, d_nfail or None, stats.ctypes.data),
+               "ssa_verify_many_dedup_device")
+        return stats
+
+    def debug_dedup_device(self, d_pks, n, d_key_idx=0, d_pk_inf=0):
+        """tests: the key dedup alone over one slice of device keys -> (distinct keys, lanes at the probe bound);
+        d_key_idx (optional, device, n x uint32) receives each lane's key index"""
+        out = np.zeros(2, dtype=np.uint64)
+        _check(_lib.ssa_debug_dedup_device(self._ctx, d_pks, d_pk_inf or None, n, d_key_idx or None, out.ctypes.data),
+               "ssa_debug_dedup_device")
+        return int(out[0]), int(out[1])
+
+    def debug_dedup_config(self, max_distinct_ratio=-1.0, probe_bound=0):
+        """tests: the policy of verify_many_dedup on this engine -- keyed route when u < max_distinct_ratio * lanes
+        (0 forces the fallback, above 1 the keyed route, negative: the measured defaults), probes per lane (0: the
+        default)"""
+        _check(_lib.ssa_debug_dedup_config(self._ctx, float(max_distinct_ratio), int(probe_bound)),
+               "ssa_debug_dedup_config")
 
     def verify_batch_status(self, sigs, pks, msgs, offsets=None, check_torsion=False, pk_inf=None):
         sigs, pks = _np_u8(sigs, 81), _np_u8(pks, 96)
@@ -1423,6 +1475,30 @@ class ExtendedPublicKey:
 
     def __eq__(self, o):
         return isinstance(o, ExtendedPublicKey) and o.key == self.key and o.chaincode == self.chaincode
+
+
+def verify_many(signatures, public_keys, messages, engine=None):
+    """Signature::verify (src/signature.rs:181-205) for every (signature, public key, message) of a slice in one call:
+    a list with None where the reference returns Ok(()) and the SignatureError it returns otherwise -- not raised; a
+    MalformedInput instance where the reference would panic.  Public keys may repeat: each distinct key's subgroup
+    check and table run once (Engine.verify_many_dedup)."""
+    if len(signatures) != len(public_keys):
+        raise MalformedInput("We should have the same number of signatures than public keys")
+    if len(messages) != len(public_keys):
+        raise MalformedInput("We should have the same number of messages than public keys")
+    if not signatures:
+        return []
+    eng = engine or default_engine()
+    sigs = np.frombuffer(b"".join(s.bytes for s in signatures), np.uint8)
+    pks = np.frombuffer(b"".join(p.affine for p in public_keys), np.uint8)
+    inf = np.array([1 if p.is_identity else 0 for p in public_keys], np.uint8)
+    flat, off = pack_messages(messages)
+    status, _, _ = eng.verify_many_dedup(sigs, pks, flat, offsets=off, check_torsion=True, pk_inf=inf)
+    errors = {OK: lambda: None,
+              INVALID_PUBLIC_KEY: lambda: SignatureError(SignatureError.InvalidPublicKey),
+              INVALID_SIGNATURE: lambda: SignatureError(SignatureError.InvalidSignature),
+              MALFORMED: lambda: MalformedInput("non-canonical field element or scalar (the reference panics here)")}
+    return [errors[int(st)]() for st in status]
 
 
 def verify_batch_statuses(signatures, public_keys, messages, rng=None, engine=None):

@@ -3,6 +3,9 @@
 // device or fails with an SSA_ERR_* code.
 #define SSA_KERNELS_DEFINE 1
 #include "ssa_ctx.hpp"
+#include "ssa_dedup.hpp"
+
+#include <sys/random.h>
 
 #include <atomic>
 #include <mutex>
@@ -371,6 +374,9 @@ ssa_ctx *ssa_internal_twin(ssa_ctx *ctx) {
     }
     ctx->twin->timing = ctx->timing;
     ctx->twin->screen_segs = ctx->screen_segs;
+    ctx->twin->dedup_ratio[0] = ctx->dedup_ratio[0];
+    ctx->twin->dedup_ratio[1] = ctx->dedup_ratio[1];
+    ctx->twin->dedup_probe_bound = ctx->dedup_probe_bound;
     return ctx->twin;
 }
 
@@ -1126,6 +1132,237 @@ extern "C" int ssa_verify_many_indexed(ssa_ctx *ctx, ssa_keyset *ks, const uint3
         }))
         return rc;
     if (n_fail_out) *n_fail_out = nf;
+    return 0;
+}
+
+// ------------------------------------------------------------------ key dedup
+// what the dedup entry points report: distinct keys summed over slices, slices on the keyed route, slices that fell
+// back, lanes that hit the probe bound (the host form's two threads add to it under the lock)
+struct DedupStats {
+    std::mutex mu;
+    uint64_t v[4] = {0, 0, 0, 0};
+    void add(uint64_t distinct, uint64_t keyed, uint64_t fell_back, uint64_t bound_hits) {
+        std::lock_guard<std::mutex> lock(mu);
+        v[0] += distinct;
+        v[1] += keyed;
+        v[2] += fell_back;
+        v[3] += bound_hits;
+    }
+};
+
+static int dedup_fingerprint_key(ssa_ctx *ctx) {
+    if (ctx->dedup_key_set) return 0;
+    uint8_t *p = (uint8_t *)ctx->dedup_key;
+    for (size_t got = 0; got < sizeof ctx->dedup_key;) {
+        const ssize_t r = getrandom(p + got, sizeof ctx->dedup_key - got, 0);
+        if (r <= 0) return SSA_ERR_HIP;
+        got += (size_t)r;
+    }
+    ctx->dedup_key_set = true;
+    return 0;
+}
+
+// The distinct keys of cnt <= lane_slice lanes on ctx->stream, into the context's workspaces: dd_idx (a key index per
+// lane), dd_reps (the representative lane of each key).  Synchronises the stream ONCE to read u and the number of lanes
+// that hit the probe bound: the policy of the caller needs u on the host.
+static int dedup_slice(ssa_ctx *ctx, const uint8_t *d_pks, const uint8_t *d_pk_inf, size_t cnt, uint64_t *u_out,
+                       uint64_t *bound_hits_out) {
+    if (int rc = dedup_fingerprint_key(ctx)) return rc;
+    const size_t cap = dd_slots_for(cnt), nb = grid_for(cnt, DD_BLOCK);
+    if (ctx->dd_slots.reserve(cap * sizeof(u64)) || ctx->dd_rep.reserve(cnt * sizeof(u32)) ||
+        ctx->dd_num.reserve(cnt * sizeof(u32)) || ctx->dd_reps.reserve(cnt * sizeof(u32)) ||
+        ctx->dd_idx.reserve(cnt * sizeof(u32)) || ctx->dd_blk.reserve(2 * nb * sizeof(u32)) || ctx->dd_stats.reserve(64))
+        return SSA_ERR_HIP;
+    unsigned long long *d_stats = (unsigned long long *)ctx->dd_stats.p;
+    u32 *blk_cnt = (u32 *)ctx->dd_blk.p, *blk_off = blk_cnt + nb;
+    int rc = timed_launch(ctx, "dedup", [&] {
+        (void)hipMemsetAsync(ctx->dd_slots.p, 0xff, cap * sizeof(u64), ctx->stream);
+        (void)hipMemsetAsync(d_stats, 0, 2 * sizeof(unsigned long long), ctx->stream);
+        hipLaunchKernelGGL(dd_k_insert, dim3((unsigned)nb), dim3(DD_BLOCK), 0, ctx->stream, d_pks, d_pk_inf, (u32)cnt,
+                           (u64)ctx->dedup_key[0], (u64)ctx->dedup_key[1], (u64 *)ctx->dd_slots.p, (u32)(cap - 1),
+                           (u32)ctx->dedup_probe_bound, (u32 *)ctx->dd_rep.p, blk_cnt, d_stats);
+        hipLaunchKernelGGL(dd_k_scan, dim3(1), dim3(DD_BLOCK), 0, ctx->stream, (const u32 *)blk_cnt, (u32)nb, blk_off,
+                           d_stats);
+        hipLaunchKernelGGL(dd_k_number, dim3((unsigned)nb), dim3(DD_BLOCK), 0, ctx->stream, (const u32 *)ctx->dd_rep.p,
+                           (u32)cnt, (const u32 *)blk_off, (u32 *)ctx->dd_num.p, (u32 *)ctx->dd_reps.p);
+        hipLaunchKernelGGL(dd_k_index, dim3((unsigned)nb), dim3(DD_BLOCK), 0, ctx->stream, (const u32 *)ctx->dd_rep.p,
+                           (const u32 *)ctx->dd_num.p, (u32)cnt, (u32 *)ctx->dd_idx.p);
+    });
+    if (rc) return rc;
+    unsigned long long st[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(st, d_stats, sizeof st, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (st[1] == 0 || st[1] > cnt) return SSA_ERR_HIP;      // (never: every lane has a representative)
+    *bound_hits_out = st[0];
+    *u_out = st[1];
+    return 0;
+}
+
+// ONE slice (cnt <= ctx->lane_slice lanes) of the lane kernels' route on ctx->stream with ctx's workspaces; hashed: the
+// challenge scalars are already in ctx->ws_h.  *d_fail is added to.
+static int dedup_verify_slice(ssa_ctx *ctx, const DevBatch &b, size_t cnt, uint32_t flags, bool hashed,
+                              uint8_t *d_status_out, unsigned long long *d_fail, DedupStats *stats) {
+    const double ratio = ctx->dedup_ratio[(flags & SSA_FLAG_CHECK_TORSION) ? 1 : 0];
+    uint64_t u = cnt, hits = 0;
+    // (a threshold of 0 sends every slice to the fallback: the keys are then counted only for the statistics)
+    if (ratio > 0 || stats)
+        if (int rc = dedup_slice(ctx, b.pks, b.pk_inf, cnt, &u, &hits)) return rc;
+    const bool keyed = (double)u < ratio * (double)cnt;
+    if (stats) stats->add(u, keyed ? 1 : 0, keyed ? 0 : 1, hits);
+    constexpr size_t TAB_BYTES = (size_t)(PTAB_ENTRIES * PTAB_ENTRY_U64) * sizeof(u64);
+    if (!keyed) {       // (nearly) every key is distinct: the path of ssa_verify_many
+        if (!hashed) return verify_one_slice(ctx, b, cnt, flags, d_status_out, d_fail);
+        if (ctx->ws_tab.reserve(cnt * TAB_BYTES)) return SSA_ERR_HIP;
+        return verify_slices(ctx, b, (const u64 *)ctx->ws_h.p, cnt, flags, d_status_out, d_fail);
+    }
+    // the u keys, compacted, and what ssa_k_verify does once per LANE done once per KEY: limb and curve checks, the
+    // subgroup check, the sixteen multiples (into the lanes' table workspace: u tables never need more than cnt)
+    if (ctx->dd_pks.reserve(u * 96) || ctx->dd_inf.reserve(u + 16) || ctx->dd_kstatus.reserve(u + 16) ||
+        ctx->ws_tab.reserve(u * TAB_BYTES) || ctx->ws_h.reserve(cnt * 4 * sizeof(u64)))
+        return SSA_ERR_HIP;
+    int rc = timed_launch(ctx, "dedup_gather", [&] {
+        hipLaunchKernelGGL(dd_k_gather, dim3(grid_for(u * 12, DD_BLOCK)), dim3(DD_BLOCK), 0, ctx->stream, b.pks, b.pk_inf,
+                           (const u32 *)ctx->dd_reps.p, (u32)u, (u64 *)ctx->dd_pks.p, (u8 *)ctx->dd_inf.p);
+    });
+    if (rc) return rc;
+    rc = timed_launch(ctx, "ssa_k_keyset_build", [&] {
+        hipLaunchKernelGGL(ssa_k_keyset_build, dim3(grid_for(u, 256)), dim3(256), 0, ctx->stream, (const u8 *)ctx->dd_pks.p,
+                           (const u8 *)ctx->dd_inf.p, (size_t)u, (u64 *)ctx->ws_tab.p, (u8 *)ctx->dd_kstatus.p);
+    });
+    if (rc) return rc;
+    if (!hashed) {
+        rc = timed_launch(ctx, "ssa_k_hash", [&] {
+            hipLaunchKernelGGL(ssa_k_hash, dim3(grid_for(cnt, 256)), dim3(256), 0, ctx->stream, ctx->d_params, b.sigs, b.pks,
+                               b.msgs, cnt, (u64 *)ctx->ws_h.p, (u8 *)nullptr, (const u32 *)nullptr, 0u);
+        });
+        if (rc) return rc;
+    }
+    return timed_launch(ctx, "ssa_k_verify_keyed", [&] {
+        hipLaunchKernelGGL(ssa_k_verify_keyed, dim3(grid_for(cnt, 256)), dim3(256), 0, ctx->stream, b.sigs,
+                           (const u32 *)ctx->dd_idx.p, (const u64 *)ctx->ws_tab.p, (const u8 *)ctx->dd_kstatus.p, (u32)u,
+                           (const u64 *)ctx->ws_h.p, (const u64 *)ctx->d_gtab, cnt, flags, d_status_out, d_fail);
+    });
+}
+
+static inline bool dedup_takes_coop(const ssa_ctx *ctx, size_t n, uint32_t flags) {
+    const size_t coop_lim = (flags & SSA_FLAG_CHECK_TORSION) ? ctx->coop_max_n_torsion : ctx->coop_max_n;
+    return (flags & SSA_FLAG_FORCE_COOP) || (!(flags & SSA_FLAG_FORCE_LANE) && n <= coop_lim);
+}
+
+// A batch for the cooperative kernel takes the path of ssa_verify_many unchanged; its keys are counted, slice by slice,
+// only for a caller that asked for the statistics.
+static int dedup_count_only(ssa_ctx *ctx, const DevBatch &b, size_t n, DedupStats *stats) {
+    if (!stats) return 0;
+    const size_t slice = ctx->lane_slice < n ? ctx->lane_slice : n;
+    for (size_t lo = 0; lo < n; lo += slice) {
+        const size_t cnt = n - lo < slice ? n - lo : slice;
+        const DevBatch s = b.slice(lo);
+        uint64_t u = 0, hits = 0;
+        if (int rc = dedup_slice(ctx, s.pks, s.pk_inf, cnt, &u, &hits)) return rc;
+        stats->add(u, 0, 1, hits);
+    }
+    return 0;
+}
+
+static void dedup_stats_out(const DedupStats &st, uint64_t stats_out[4]) {
+    if (stats_out)
+        for (int k = 0; k < 4; k++) stats_out[k] = st.v[k];
+}
+
+extern "C" int ssa_verify_many_dedup_device(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks,
+                                            const uint8_t *d_pk_inf, const uint8_t *d_msgs, const uint64_t *d_msg_off,
+                                            size_t msg_stride, size_t msg_len, size_t n, uint32_t flags,
+                                            uint8_t *d_status_out, uint64_t *d_n_fail_out, uint64_t stats_out[4]) {
+    const DevBatch b{d_sigs, d_pks, d_pk_inf, {d_msgs, d_msg_off, msg_stride, msg_len}};
+    if (!ctx || (n && (!d_sigs || !d_pks || !d_status_out))) return SSA_ERR_ARG;
+    if (int rc = check_msgs(b.msgs, n)) return rc;
+    if (stats_out) std::memset(stats_out, 0, 4 * sizeof(uint64_t));
+    HIP_TRY(hipSetDevice(ctx->device));
+    unsigned long long *d_fail;
+    if (int rc = reset_fail_counter(ctx, d_n_fail_out, &d_fail)) return rc;
+    if (n == 0) return 0;
+    DedupStats st;
+    int rc = 0;
+    if (dedup_takes_coop(ctx, n, flags)) {
+        rc = dedup_count_only(ctx, b, n, stats_out ? &st : nullptr);
+        if (rc == 0) rc = verify_launch(ctx, b, n, flags, d_status_out, d_fail);
+    } else {
+        // slice after slice on the context's stream (each slice's policy waits for its u: the slices of this form do not
+        // alternate between two streams)
+        const size_t slice = ctx->lane_slice < n ? ctx->lane_slice : n;
+        for (size_t lo = 0; lo < n && rc == 0; lo += slice) {
+            const size_t cnt = n - lo < slice ? n - lo : slice;
+            rc = dedup_verify_slice(ctx, b.slice(lo), cnt, flags, false, d_status_out + lo, d_fail, stats_out ? &st : nullptr);
+        }
+    }
+    if (rc) return rc;
+    dedup_stats_out(st, stats_out);
+    return 0;
+}
+
+// ONE slice from host buffers: the staging and copy-back of verify_many_host_one around the dedup pipeline
+static int dedup_host_one(ssa_ctx *ctx, const HostBatch &b, size_t n, uint32_t flags, uint8_t *status_out,
+                          uint64_t *n_fail_out, DedupStats *stats) {
+    const bool lane_kernels = !dedup_takes_coop(ctx, n, flags);
+    HostCall hc(ctx);
+    PipelinedInputs pin;      // its destructor drains the side streams on every error return
+    const StagedInputs s = slice_inputs(hc, pin, b, n, nullptr, lane_kernels, true);
+    u8 *d_status = hc.out(ctx->st_status, s.hashed ? ctx->pin_out.p : status_out, n, 16);
+    unsigned long long nf = 0, *d_fail = (unsigned long long *)ctx->ws_fail.p;
+    hc.copy_back(&nf, d_fail, sizeof nf);
+    const int rc = hc.finish([&] {
+        HIP_TRY(hipMemsetAsync(d_fail, 0, sizeof(unsigned long long), ctx->stream));
+        if (lane_kernels) return dedup_verify_slice(ctx, s.batch, n, flags, s.hashed, d_status, d_fail, stats);
+        if (int r = dedup_count_only(ctx, s.batch, n, stats)) return r;
+        return verify_launch(ctx, s.batch, n, flags, d_status, d_fail);
+    });
+    if (rc) return rc;
+    pin.done();
+    if (s.hashed) std::memcpy(status_out, ctx->pin_out.p, n);
+    if (n_fail_out) *n_fail_out = nf;
+    return 0;
+}
+
+extern "C" int ssa_verify_many_dedup(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_inf,
+                                     const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len,
+                                     size_t n, uint32_t flags, uint8_t *status_out, uint64_t *n_fail_out,
+                                     uint64_t stats_out[4]) {
+    if (!ctx || (n && (!sigs || !pks || !status_out))) return SSA_ERR_ARG;
+    if (int rc = check_msgs({msgs, msg_off, msg_stride, msg_len}, n)) return rc;
+    if (int rc = check_host_offsets(msg_off, n)) return rc;
+    if (n_fail_out) *n_fail_out = 0;
+    if (stats_out) std::memset(stats_out, 0, 4 * sizeof(uint64_t));
+    if (n == 0) return 0;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const HostBatch b{sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len};
+    DedupStats st;
+    const int rc = run_host_slices_counted(ctx, b, n, ctx->lane_slice, n_fail_out,
+                                           [&](ssa_ctx *c, size_t lo, size_t cnt, const HostBatch &s, uint64_t *nf) {
+                                               return dedup_host_one(c, s, cnt, flags, status_out + lo, nf,
+                                                                     stats_out ? &st : nullptr);
+                                           });
+    if (rc) return rc;
+    dedup_stats_out(st, stats_out);
+    return 0;
+}
+
+extern "C" int ssa_debug_dedup_device(ssa_ctx *ctx, const uint8_t *d_pks, const uint8_t *d_pk_inf, size_t n,
+                                      uint32_t *d_key_idx_out, uint64_t out[2]) {
+    if (!ctx || !d_pks || !out || n == 0 || n > SSA_MAX_BATCH || n > ctx->lane_slice) return SSA_ERR_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (int rc = dedup_slice(ctx, d_pks, d_pk_inf, n, &out[0], &out[1])) return rc;
+    if (d_key_idx_out) {
+        HIP_TRY(hipMemcpyAsync(d_key_idx_out, ctx->dd_idx.p, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    return 0;
+}
+
+extern "C" int ssa_debug_dedup_config(ssa_ctx *ctx, double max_distinct_ratio, uint32_t probe_bound) {
+    if (!ctx || max_distinct_ratio > 2.0 || max_distinct_ratio != max_distinct_ratio) return SSA_ERR_ARG;
+    ctx->dedup_ratio[0] = max_distinct_ratio < 0 ? DEDUP_RATIO_NO_CHECK : max_distinct_ratio;
+    ctx->dedup_ratio[1] = max_distinct_ratio < 0 ? DEDUP_RATIO_CHECK : max_distinct_ratio;
+    ctx->dedup_probe_bound = probe_bound ? probe_bound : DEDUP_PROBE_BOUND;
     return 0;
 }
 

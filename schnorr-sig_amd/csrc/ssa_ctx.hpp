@@ -85,6 +85,10 @@ struct TimedLaunch {
     hipEvent_t start, stop;
 };
 
+// key dedup defaults: keyed route when u < ratio * lanes, without / with the subgroup check
+constexpr double DEDUP_RATIO_NO_CHECK = 0.0, DEDUP_RATIO_CHECK = 1.0;
+constexpr unsigned DEDUP_PROBE_BOUND = 128;
+
 struct ssa_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;
@@ -134,6 +138,17 @@ struct ssa_ctx {
     // challenge scalars), their statuses, and a scratch rejection counter
     unsigned screen_segs = 0;
     DevBuf scr_ok, scr_in, scr_status, scr_fail;
+    // key dedup (ssa_dedup.hpp): the slot table, each lane's representative, the representatives'
+    // numbers and list, each lane's key index, per-workgroup counts and offsets, two counters (lanes at the probe bound,
+    // u), and the compacted keys, flags and key statuses.  The 16-multiple tables of the u keys live in ws_tab.
+    DevBuf dd_slots, dd_rep, dd_num, dd_reps, dd_idx, dd_blk, dd_stats, dd_pks, dd_inf, dd_kstatus;
+    // a slice takes the keyed route when u < dedup_ratio[subgroup check on] * lanes: the measured thresholds of DESIGN.md
+    // section 14 (without the check the keyed route never paid, with it always but for all-distinct keys);
+    // ssa_debug_dedup_config overrides both.  A lane probes at most dedup_probe_bound slots.
+    double dedup_ratio[2] = {DEDUP_RATIO_NO_CHECK, DEDUP_RATIO_CHECK};
+    unsigned dedup_probe_bound = DEDUP_PROBE_BOUND;
+    uint64_t dedup_key[2] = {0, 0};   // the fingerprint's key: getrandom(2) at the first use
+    bool dedup_key_set = false;
     // signing (ssa_sign.hip): the 4-bit comb table of the constant-time signer (98 KB, built at the first use) and the
     // intermediates of the keyed (130-byte) output
     DevBuf ctab, sg_sigs, sg_pks;
@@ -173,8 +188,9 @@ static inline void for_each_devbuf(Ctx *c, F &&f) {
                     &c->msm_keys2, &c->msm_vals2, &c->msm_sort_tmp, &c->msm_bounds, &c->msm_buckets, &c->msm_chunks,
                     &c->msm_windows, &c->msm_partials, &c->msm_flags, &c->st_coeffs, &c->msm_cnt, &c->msm_cnt2,
                     &c->msm_ids, &c->msm_ids2, &c->msm_comb_pts, &c->msm_comb_lins, &c->msm_slice_recs, &c->msm_sbuf,
-                    &c->scr_ok, &c->scr_in, &c->scr_status, &c->scr_fail, &c->ctab, &c->sg_sigs, &c->sg_pks, &c->tc_out,
-                    &c->dv_recs, &c->rng_seed, &c->rng_scratch, &c->tail_done, &c->tail_park})
+                    &c->scr_ok, &c->scr_in, &c->scr_status, &c->scr_fail, &c->dd_slots, &c->dd_rep, &c->dd_num, &c->dd_reps,
+                    &c->dd_idx, &c->dd_blk, &c->dd_stats, &c->dd_pks, &c->dd_inf, &c->dd_kstatus, &c->ctab, &c->sg_sigs,
+                    &c->sg_pks, &c->tc_out, &c->dv_recs, &c->rng_seed, &c->rng_scratch, &c->tail_done, &c->tail_park})
         f(*b);
 }
 

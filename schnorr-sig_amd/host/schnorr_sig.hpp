@@ -588,6 +588,36 @@ inline std::vector<uint8_t> verify_batch_statuses(Context &cx, const std::vector
     return status;
 }
 
+// Signature::verify (src/signature.rs:181-205) over a slice of signatures in which public keys repeat: one status per
+// signature (0 Ok, 1 InvalidPublicKey, 2 InvalidSignature, 3 malformed: the reference would panic), the same vector as n
+// single calls, with each DISTINCT key's subgroup check and table run once on the GPU.
+inline std::vector<uint8_t> verify_many_statuses(Context &cx, const std::vector<Signature> &signatures,
+                                                 const std::vector<PublicKey> &public_keys,
+                                                 const std::vector<std::pair<const uint8_t *, size_t>> &messages,
+                                                 uint64_t *stats_out = nullptr) {
+    if (signatures.size() != public_keys.size())
+        throw Panic("We should have the same number of signatures than public keys");
+    if (messages.size() != public_keys.size())
+        throw Panic("We should have the same number of messages than public keys");
+    const size_t n = signatures.size();
+    std::vector<uint8_t> status(n, 0);
+    if (n == 0) return status;
+    std::vector<uint8_t> sigs(n * SIGNATURE_LENGTH), pks(n * AFFINE_PUBLIC_KEY_LENGTH), inf(n), flat;
+    std::vector<uint64_t> off(n + 1, 0);
+    for (size_t i = 0; i < n; i++) {
+        std::memcpy(&sigs[i * SIGNATURE_LENGTH], signatures[i].bytes.data(), SIGNATURE_LENGTH);
+        std::memcpy(&pks[i * AFFINE_PUBLIC_KEY_LENGTH], public_keys[i].affine.data(), AFFINE_PUBLIC_KEY_LENGTH);
+        inf[i] = public_keys[i].is_identity ? 1 : 0;
+        flat.insert(flat.end(), messages[i].first, messages[i].first + messages[i].second);
+        off[i + 1] = flat.size();
+    }
+    flat.push_back(0);
+    const int rc = ssa_verify_many_dedup(cx.get(), sigs.data(), pks.data(), inf.data(), flat.data(), off.data(), 0, 0, n,
+                                         SSA_FLAG_CHECK_TORSION, status.data(), nullptr, stats_out);
+    if (rc != 0) throw std::runtime_error(std::string("ssa_verify_many_dedup: ") + ssa_strerror(rc));
+    return status;
+}
+
 // ---- hierarchical deterministic key derivation (src/derivation.rs) ---------------------------------------------------
 constexpr size_t CHAIN_CODE_LENGTH = SSA_CHAIN_CODE_LENGTH, EXTENDED_PRIVATE_KEY_LENGTH = SSA_EXTENDED_PRIVATE_KEY_LENGTH,
                  EXTENDED_PUBLIC_KEY_LENGTH = SSA_EXTENDED_PUBLIC_KEY_LENGTH;
