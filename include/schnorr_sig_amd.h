@@ -14,6 +14,8 @@
  *   ssa_verify_many         <- n x Signature::verify (the per-signature accept/reject vector
  *                              BASELINE.json's north_star asks for)
  *   ssa_verify_many_dedup   <- the same over a slice in which keys repeat: each distinct key is checked once
+ *   ssa_verify_many_screened <- the same vector at about the price of one MSM: segments of the batch are screened by
+ *                              a random linear combination, each distinct key's subgroup check runs once
  *   ssa_hash_message_many   <- hash_message                 src/signature.rs:274-306
  *   ssa_rescue_hash_many    <- RescueHash::hash_field       src/signature.rs:303
  *   ssa_verify_keyed_many   <- KeyedSignature::{from_bytes, verify}  src/signature.rs:232-271
@@ -472,6 +474,63 @@ int ssa_verify_many_dedup_device(ssa_ctx *ctx, const uint8_t *d_sigs, const uint
                                  const uint8_t *d_msgs, const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len,
                                  size_t n, uint32_t flags, uint8_t *d_status_out, uint64_t *d_n_fail_out,
                                  uint64_t stats_out[4]);
+
+/* ---- Signature::verify screened: the status vector of ssa_verify_many at about the price of one MSM (DESIGN.md
+ * section 15) ------------------------------------------------------------------------------------------------------
+ * The screen of ssa_verify_batch_screened under the semantics of ssa_verify_many.  flags: any combination of
+ * SSA_FLAG_CHECK_TORSION and SSA_FLAG_SIG_FLAG_BYTE (any other bit: SSA_ERR_ARG).  SSA_FLAG_CHECK_TORSION alone is
+ * Signature::verify (src/signature.rs:181-205).  SSA_FLAG_SIG_FLAG_BYTE alone IS ssa_verify_batch_screened: the call
+ * is handed to it and stats_out stays zero.  For the other three settings, per slice of at most SSA_LANE_SLICE lanes
+ * (2^20; segments never straddle slices):
+ *   1. the distinct keys of the slice are found as ssa_verify_many_dedup finds them, and the limb, curve and subgroup
+ *      checks and the table of sixteen multiples run once per distinct key;
+ *   2. the segments of the slice (256 of 4096 lanes at 2^20) are screened by the segmented MSM, on points as in
+ *      ssa_verify_batch_screened;
+ *   3. the lanes of failing segments, and the lanes that could not be screened, run the exact keyed kernel (no subgroup
+ *      work, no table build per lane) on the challenge scalars the screen hashed.  If they are more than half the
+ *      slice, that kernel runs over the whole slice in place.
+ * status_out[i] is the status ssa_verify_many gives lane i for the same inputs and flags (0, 1, 2 or 3, in the order
+ * of src/signature.rs:182-186: the key first, then the signature), with one exception:
+ *   - A lane the exact check accepts is never rejected.
+ *   - The screen only ever ACCEPTS.  Every nonzero status is written by the exact kernel.
+ *   - A lane that cannot be screened gets no status from the screen: it is left out of its segment's sums (it does not
+ *     make the segment fail) and is re-checked exactly.  Those are the lanes whose key the per-key check refused
+ *     (malformed, or outside the prime-order subgroup -- with or without SSA_FLAG_CHECK_TORSION: the per-key check
+ *     computes [q]P == O anyway, so no key outside the subgroup ever enters a sum; without the flag the exact kernel
+ *     then verifies the lane against that key as ssa_verify_many does) and the lanes whose signature gives no R to add
+ *     up: non-canonical limbs, e >= q, an x that is not on the curve, a flag byte that does not decode.
+ *   - A lane the exact check rejects keeps its exact status unless the random combination of its segment vanishes:
+ *     about 2^-128 for an error with a prime-order component.  Every key that enters a sum has passed [q]P == O, so
+ *     the key-side small-order case of ssa_verify_batch_screened (a key P + T2) cannot occur: such a lane gets its
+ *     exact status (SSA_INVALID_PUBLIC_KEY with SSA_FLAG_CHECK_TORSION).  What remains is an R outside the prime-order subgroup,
+ *     R = R' + T with T of small order l and e made for R': the exact status is 2, and the screen misses it with
+ *     probability 1/l (for l = 2: exactly when the lane's coefficient, reduced mod q, is even).  Building such a lane
+ *     appears to take the secret key, because h depends on R.x (changing R changes h, and solving for e is then the
+ *     forgery problem itself): a signer spoiling their own signature, not a third party.  No reduction is claimed.
+ * Without SSA_FLAG_SIG_FLAG_BYTE Signature::verify ignores byte 48 of the signature.  The screen still reads its sort
+ * bit to choose between R and -R, since an honest signer sets it.  A valid signature with the wrong sort bit therefore
+ * makes its segment fail and is then accepted by the re-check: correct, at the price of one segment's re-check.  A
+ * byte that does not decode at all sends only its own lane to the re-check.
+ * coeffs, n_fail_out, host staging, n == 0, SSA_MAX_BATCH: as ssa_verify_batch_screened.  Batches of at most
+ * SSA_MSM_SMALL_MAX lanes (3072), and a trailing slice that small, take ssa_verify_many with the caller's flags.
+ * stats_out (optional, HOST memory in both forms), summed over the slices: [0] distinct keys, [1] segments screened,
+ * [2] segments that failed, [3] lanes sent to the exact re-check, [4] lanes that could not be screened, [5] slices
+ * screened, [6] slices whose every lane ran the exact kernel (a re-check of more than half the slice, which was also
+ * screened, or a slice of at most SSA_MSM_SMALL_MAX lanes, which was not), [7] lanes that hit the probe bound of the
+ * dedup table.
+ * Both forms synchronise the context's stream TWICE per slice: once to read the number of distinct keys, once to read
+ * the segment verdicts together with the length of the re-check list.  No allocation per call once the workspaces
+ * have grown.  Measured (2^20 signatures, SSA_FLAG_CHECK_TORSION): 18.2 ms by 65 536 signers
+ * against 34.7 for ssa_verify_many_dedup, 40.9 ms by all-distinct signers against 56.8 for ssa_verify_many.  When every
+ * segment fails the call costs the screen on top of the keyed kernel: 42.8 ms, 1.24x ssa_verify_many_dedup. */
+int ssa_verify_many_screened(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_inf,
+                             const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len, size_t n,
+                             uint32_t flags, const uint8_t *coeffs, uint8_t *status_out, uint64_t *n_fail_out,
+                             uint64_t stats_out[8]);
+int ssa_verify_many_screened_device(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_pk_inf,
+                                    const uint8_t *d_msgs, const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len,
+                                    size_t n, uint32_t flags, const uint8_t *d_coeffs, uint32_t coeff_bytes,
+                                    uint8_t *d_status_out, uint64_t *d_n_fail_out, uint64_t stats_out[8]);
 
 /* ---- signer sets: many signatures by few signers (the signing twin of the key set) ---------------------------
  * A signer set holds m key pairs on the device: the secret key, the 96-byte affine public key, the 49-byte compressed

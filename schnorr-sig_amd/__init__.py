@@ -205,6 +205,8 @@ def _load():
         "ssa_debug_screen_segments": (i32, [vp, u32]),
         "ssa_verify_many_dedup": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz, u32, vp, u64p, vp]),
         "ssa_verify_many_dedup_device": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz, u32, vp, vp, vp]),
+        "ssa_verify_many_screened": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz, u32, vp, vp, u64p, vp]),
+        "ssa_verify_many_screened_device": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz, u32, vp, u32, vp, vp, vp]),
         "ssa_debug_dedup_device": (i32, [vp, vp, vp, sz, vp, vp]),
         "ssa_debug_dedup_config": (i32, [vp, C.c_double, u32]),
         "ssa_xprv_master_many": (i32, [vp, vp, sz, vp, vp]),
@@ -456,6 +458,50 @@ class Engine:
             self._ctx, d_sigs, d_pks, d_pk_inf or None, d_msgs, d_offsets or None,
             msg_stride if msg_stride is not None else msg_len, msg_len, n, d_coeffs or None, coeff_bytes, d_status,
             d_nfail or None), "ssa_verify_batch_screened_device")
+
+    def verify_many_screened(self, sigs, pks, msgs, offsets=None, check_torsion=True, pk_inf=None, sig_flag_byte=False,
+                             coeffs=None):
+        """the status vector of verify_many at about the price of one MSM -> (status uint8[n],
+        n_fail, stats uint64[8]).  Each distinct key of a slice is checked once, the segments of the slice are screened
+        by the MSM, and only the lanes of failing segments and the lanes that could not be screened run the exact keyed
+        kernel.  check_torsion alone is Signature::verify; sig_flag_byte alone is verify_batch_screened.  coeffs: n x
+        32-byte scalars, or None (drawn on the device).  stats: distinct keys, segments screened, segments that failed,
+        lanes re-checked, lanes that could not be screened, slices screened, slices run entirely by the exact kernel,
+        lanes at the dedup probe bound."""
+        sigs, pks = _np_u8(sigs, 81), _np_u8(pks, 96)
+        n = sigs.shape[0]
+        if pks.shape[0] != n:
+            raise MalformedInput("We should have the same number of signatures than public keys")
+        if n:
+            m, off, stride, mlen = self._msg_args(msgs, offsets, n)
+        else:
+            m, off, stride, mlen = None, None, 0, 0
+        c = _np_u8(coeffs, 32) if coeffs is not None else None
+        if c is not None:
+            assert c.shape[0] == n
+        inf = _np_u8(pk_inf) if pk_inf is not None else None
+        status = np.full(n, 255, dtype=np.uint8)
+        nfail = C.c_uint64(0)
+        stats = np.zeros(8, dtype=np.uint64)
+        flags = (FLAG_CHECK_TORSION if check_torsion else 0) | (FLAG_SIG_FLAG_BYTE if sig_flag_byte else 0)
+        _check(_lib.ssa_verify_many_screened(self._ctx, _ptr(sigs) if n else None, _ptr(pks) if n else None, _ptr(inf),
+                                             _ptr(m), _ptr(off), stride, mlen, n, flags, _ptr(c),
+                                             _ptr(status) if n else None, C.byref(nfail), stats.ctypes.data),
+               "ssa_verify_many_screened")
+        return status, int(nfail.value), stats
+
+    def verify_many_screened_device(self, d_sigs, d_pks, d_msgs, n, msg_len, d_coeffs, coeff_bytes, d_status, d_nfail,
+                                    msg_stride=None, d_offsets=0, d_pk_inf=0, check_torsion=True, sig_flag_byte=False):
+        """device form of verify_many_screened (synchronises the stream twice per slice: for the number of distinct
+        keys, and for the segment verdicts with the length of the re-check list); returns the statistics (uint64[8],
+        host)"""
+        flags = (FLAG_CHECK_TORSION if check_torsion else 0) | (FLAG_SIG_FLAG_BYTE if sig_flag_byte else 0)
+        stats = np.zeros(8, dtype=np.uint64)
+        _check(_lib.ssa_verify_many_screened_device(
+            self._ctx, d_sigs, d_pks, d_pk_inf or None, d_msgs, d_offsets or None,
+            msg_stride if msg_stride is not None else msg_len, msg_len, n, flags, d_coeffs or None, coeff_bytes, d_status,
+            d_nfail or None, stats.ctypes.data), "ssa_verify_many_screened_device")
+        return stats
 
     def debug_screen_segments(self, k):
         """tests: k segments per slice in the screened form on this engine (0 = automatic)"""
@@ -1477,28 +1523,63 @@ class ExtendedPublicKey:
         return isinstance(o, ExtendedPublicKey) and o.key == self.key and o.chaincode == self.chaincode
 
 
-def verify_many(signatures, public_keys, messages, engine=None):
-    """Signature::verify (src/signature.rs:181-205) for every (signature, public key, message) of a slice in one call:
-    a list with None where the reference returns Ok(()) and the SignatureError it returns otherwise -- not raised; a
-    MalformedInput instance where the reference would panic.  Public keys may repeat: each distinct key's subgroup
-    check and table run once (Engine.verify_many_dedup, DESIGN.md section 14)."""
+def _pack_triples(signatures, public_keys, messages):
+    """(signature, public key, message) objects -> the arrays the engine takes (signatures, keys, identity flags,
+    messages, offsets), or None for an empty slice; the length checks of the reference's verify_batch"""
     if len(signatures) != len(public_keys):
         raise MalformedInput("We should have the same number of signatures than public keys")
     if len(messages) != len(public_keys):
         raise MalformedInput("We should have the same number of messages than public keys")
     if not signatures:
-        return []
-    eng = engine or default_engine()
+        return None
     sigs = np.frombuffer(b"".join(s.bytes for s in signatures), np.uint8)
     pks = np.frombuffer(b"".join(p.affine for p in public_keys), np.uint8)
     inf = np.array([1 if p.is_identity else 0 for p in public_keys], np.uint8)
     flat, off = pack_messages(messages)
-    status, _, _ = eng.verify_many_dedup(sigs, pks, flat, offsets=off, check_torsion=True, pk_inf=inf)
+    return sigs, pks, inf, flat, off
+
+
+def _status_results(status):
+    """statuses of Signature::verify -> None, the SignatureError the reference returns, or a MalformedInput instance"""
     errors = {OK: lambda: None,
               INVALID_PUBLIC_KEY: lambda: SignatureError(SignatureError.InvalidPublicKey),
               INVALID_SIGNATURE: lambda: SignatureError(SignatureError.InvalidSignature),
               MALFORMED: lambda: MalformedInput("non-canonical field element or scalar (the reference panics here)")}
     return [errors[int(st)]() for st in status]
+
+
+def verify_many(signatures, public_keys, messages, engine=None):
+    """Signature::verify (src/signature.rs:181-205) for every (signature, public key, message) of a slice in one call:
+    a list with None where the reference returns Ok(()) and the SignatureError it returns otherwise -- not raised; a
+    MalformedInput instance where the reference would panic.  Public keys may repeat: each distinct key's subgroup
+    check and table run once (Engine.verify_many_dedup, DESIGN.md section 14)."""
+    packed = _pack_triples(signatures, public_keys, messages)
+    if packed is None:
+        return []
+    sigs, pks, inf, flat, off = packed
+    eng = engine or default_engine()
+    status, _, _ = eng.verify_many_dedup(sigs, pks, flat, offsets=off, check_torsion=True, pk_inf=inf)
+    return _status_results(status)
+
+
+def verify_many_screened(signatures, public_keys, messages, rng=None, engine=None):
+    """Signature::verify (src/signature.rs:181-205) for every (signature, public key, message) of a slice, screened on
+    the GPU (Engine.verify_many_screened): the list verify_many returns -- None where the
+    reference returns Ok(()), the SignatureError it returns otherwise, a MalformedInput instance where it would panic
+    -- at about the price of one MSM for an honest slice.  Coefficients from `rng(64)` per signature reduced mod q, or
+    drawn on the device when rng is None.  A rejected signature is reported except with the probability stated in
+    DESIGN.md section 15."""
+    packed = _pack_triples(signatures, public_keys, messages)
+    if packed is None:
+        return []
+    sigs, pks, inf, flat, off = packed
+    eng = engine or default_engine()
+    coeffs = None
+    if rng is not None:
+        coeffs = np.frombuffer(b"".join((int.from_bytes(rng(64), "little") % Q).to_bytes(32, "little")
+                                        for _ in signatures), np.uint8)
+    status, _, _ = eng.verify_many_screened(sigs, pks, flat, offsets=off, check_torsion=True, pk_inf=inf, coeffs=coeffs)
+    return _status_results(status)
 
 
 def verify_batch_statuses(signatures, public_keys, messages, rng=None, engine=None):

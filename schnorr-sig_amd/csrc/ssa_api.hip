@@ -1198,6 +1198,46 @@ static int dedup_slice(ssa_ctx *ctx, const uint8_t *d_pks, const uint8_t *d_pk_i
     return 0;
 }
 
+// The u keys dedup_slice found, compacted, and what ssa_k_verify does once per LANE done once per KEY: limb and curve
+// checks, the subgroup check, the sixteen multiples -- ctx->dd_kstatus (0 / 1 / 3 per key) and the tables in ctx->ws_tab
+// (the lanes' table workspace: u tables never need more than one per lane)
+static int dedup_check_keys(ssa_ctx *ctx, const uint8_t *d_pks, const uint8_t *d_pk_inf, uint64_t u) {
+    constexpr size_t TAB_BYTES = (size_t)(PTAB_ENTRIES * PTAB_ENTRY_U64) * sizeof(u64);
+    if (ctx->dd_pks.reserve(u * 96) || ctx->dd_inf.reserve(u + 16) || ctx->dd_kstatus.reserve(u + 16) ||
+        ctx->ws_tab.reserve(u * TAB_BYTES))
+        return SSA_ERR_HIP;
+    int rc = timed_launch(ctx, "dedup_gather", [&] {
+        hipLaunchKernelGGL(dd_k_gather, dim3(grid_for(u * 12, DD_BLOCK)), dim3(DD_BLOCK), 0, ctx->stream, d_pks, d_pk_inf,
+                           (const u32 *)ctx->dd_reps.p, (u32)u, (u64 *)ctx->dd_pks.p, (u8 *)ctx->dd_inf.p);
+    });
+    if (rc) return rc;
+    return timed_launch(ctx, "ssa_k_keyset_build", [&] {
+        hipLaunchKernelGGL(ssa_k_keyset_build, dim3(grid_for(u, 256)), dim3(256), 0, ctx->stream, (const u8 *)ctx->dd_pks.p,
+                           (const u8 *)ctx->dd_inf.p, (size_t)u, (u64 *)ctx->ws_tab.p, (u8 *)ctx->dd_kstatus.p);
+    });
+}
+
+// The two ends of the keyed route, shared with ssa_verify_many_screened (ssa_msm.hip), which puts
+// the segmented MSM between them.  ssa_internal_dedup_keys: the distinct keys of one slice (cnt <= ctx->lane_slice
+// lanes) checked once each: ctx->dd_idx (a key index per lane) and what dedup_check_keys leaves; synchronises the
+// stream once, for u.
+int ssa_internal_dedup_keys(ssa_ctx *ctx, const uint8_t *d_pks, const uint8_t *d_pk_inf, size_t cnt, uint64_t *u_out,
+                            uint64_t *bound_hits_out) {
+    if (int rc = dedup_slice(ctx, d_pks, d_pk_inf, cnt, u_out, bound_hits_out)) return rc;
+    return dedup_check_keys(ctx, d_pks, d_pk_inf, *u_out);
+}
+
+// ssa_k_verify_keyed over n lanes against the u keys dedup_check_keys left in the context; *d_fail is added to
+int ssa_internal_verify_keyed(ssa_ctx *ctx, const uint8_t *d_sigs, const uint32_t *d_key_idx, uint64_t u,
+                              const uint64_t *d_h, size_t n, uint32_t flags, uint8_t *d_status_out,
+                              unsigned long long *d_fail) {
+    return timed_launch(ctx, "ssa_k_verify_keyed", [&] {
+        hipLaunchKernelGGL(ssa_k_verify_keyed, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, d_sigs, d_key_idx,
+                           (const u64 *)ctx->ws_tab.p, (const u8 *)ctx->dd_kstatus.p, (u32)u, (const u64 *)d_h,
+                           (const u64 *)ctx->d_gtab, n, flags, d_status_out, d_fail);
+    });
+}
+
 // ONE slice (cnt <= ctx->lane_slice lanes) of the lane kernels' route on ctx->stream with ctx's workspaces; hashed: the
 // challenge scalars are already in ctx->ws_h.  *d_fail is added to.
 static int dedup_verify_slice(ssa_ctx *ctx, const DevBatch &b, size_t cnt, uint32_t flags, bool hashed,
@@ -1215,33 +1255,17 @@ static int dedup_verify_slice(ssa_ctx *ctx, const DevBatch &b, size_t cnt, uint3
         if (ctx->ws_tab.reserve(cnt * TAB_BYTES)) return SSA_ERR_HIP;
         return verify_slices(ctx, b, (const u64 *)ctx->ws_h.p, cnt, flags, d_status_out, d_fail);
     }
-    // the u keys, compacted, and what ssa_k_verify does once per LANE done once per KEY: limb and curve checks, the
-    // subgroup check, the sixteen multiples (into the lanes' table workspace: u tables never need more than cnt)
-    if (ctx->dd_pks.reserve(u * 96) || ctx->dd_inf.reserve(u + 16) || ctx->dd_kstatus.reserve(u + 16) ||
-        ctx->ws_tab.reserve(u * TAB_BYTES) || ctx->ws_h.reserve(cnt * 4 * sizeof(u64)))
-        return SSA_ERR_HIP;
-    int rc = timed_launch(ctx, "dedup_gather", [&] {
-        hipLaunchKernelGGL(dd_k_gather, dim3(grid_for(u * 12, DD_BLOCK)), dim3(DD_BLOCK), 0, ctx->stream, b.pks, b.pk_inf,
-                           (const u32 *)ctx->dd_reps.p, (u32)u, (u64 *)ctx->dd_pks.p, (u8 *)ctx->dd_inf.p);
-    });
-    if (rc) return rc;
-    rc = timed_launch(ctx, "ssa_k_keyset_build", [&] {
-        hipLaunchKernelGGL(ssa_k_keyset_build, dim3(grid_for(u, 256)), dim3(256), 0, ctx->stream, (const u8 *)ctx->dd_pks.p,
-                           (const u8 *)ctx->dd_inf.p, (size_t)u, (u64 *)ctx->ws_tab.p, (u8 *)ctx->dd_kstatus.p);
-    });
-    if (rc) return rc;
+    if (int rc = dedup_check_keys(ctx, b.pks, b.pk_inf, u)) return rc;
+    if (ctx->ws_h.reserve(cnt * 4 * sizeof(u64))) return SSA_ERR_HIP;
     if (!hashed) {
-        rc = timed_launch(ctx, "ssa_k_hash", [&] {
+        const int rc = timed_launch(ctx, "ssa_k_hash", [&] {
             hipLaunchKernelGGL(ssa_k_hash, dim3(grid_for(cnt, 256)), dim3(256), 0, ctx->stream, ctx->d_params, b.sigs, b.pks,
                                b.msgs, cnt, (u64 *)ctx->ws_h.p, (u8 *)nullptr, (const u32 *)nullptr, 0u);
         });
         if (rc) return rc;
     }
-    return timed_launch(ctx, "ssa_k_verify_keyed", [&] {
-        hipLaunchKernelGGL(ssa_k_verify_keyed, dim3(grid_for(cnt, 256)), dim3(256), 0, ctx->stream, b.sigs,
-                           (const u32 *)ctx->dd_idx.p, (const u64 *)ctx->ws_tab.p, (const u8 *)ctx->dd_kstatus.p, (u32)u,
-                           (const u64 *)ctx->ws_h.p, (const u64 *)ctx->d_gtab, cnt, flags, d_status_out, d_fail);
-    });
+    return ssa_internal_verify_keyed(ctx, b.sigs, (const u32 *)ctx->dd_idx.p, u, (const uint64_t *)ctx->ws_h.p, cnt, flags,
+                                     d_status_out, d_fail);
 }
 
 static inline bool dedup_takes_coop(const ssa_ctx *ctx, size_t n, uint32_t flags) {

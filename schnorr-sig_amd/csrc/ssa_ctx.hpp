@@ -138,6 +138,9 @@ struct ssa_ctx {
     // challenge scalars), their statuses, and a scratch rejection counter
     unsigned screen_segs = 0;
     DevBuf scr_ok, scr_in, scr_status, scr_fail;
+    // ssa_verify_many_screened: per lane "cannot be screened" (from its key) and "re-check" bytes,
+    // the re-check list (lane numbers), per-workgroup counts and offsets of the list, and three counters
+    DevBuf scr_mask, scr_mark, scr_list, scr_blk, scr_cnt;
     // key dedup (ssa_dedup.hpp): the slot table, each lane's representative, the representatives'
     // numbers and list, each lane's key index, per-workgroup counts and offsets, two counters (lanes at the probe bound,
     // u), and the compacted keys, flags and key statuses.  The 16-multiple tables of the u keys live in ws_tab.
@@ -188,7 +191,8 @@ static inline void for_each_devbuf(Ctx *c, F &&f) {
                     &c->msm_keys2, &c->msm_vals2, &c->msm_sort_tmp, &c->msm_bounds, &c->msm_buckets, &c->msm_chunks,
                     &c->msm_windows, &c->msm_partials, &c->msm_flags, &c->st_coeffs, &c->msm_cnt, &c->msm_cnt2,
                     &c->msm_ids, &c->msm_ids2, &c->msm_comb_pts, &c->msm_comb_lins, &c->msm_slice_recs, &c->msm_sbuf,
-                    &c->scr_ok, &c->scr_in, &c->scr_status, &c->scr_fail, &c->dd_slots, &c->dd_rep, &c->dd_num, &c->dd_reps,
+                    &c->scr_ok, &c->scr_in, &c->scr_status, &c->scr_fail, &c->scr_mask, &c->scr_mark,
+                    &c->scr_list, &c->scr_blk, &c->scr_cnt, &c->dd_slots, &c->dd_rep, &c->dd_num, &c->dd_reps,
                     &c->dd_idx, &c->dd_blk, &c->dd_stats, &c->dd_pks, &c->dd_inf, &c->dd_kstatus, &c->ctab, &c->sg_sigs,
                     &c->sg_pks, &c->tc_out, &c->dv_recs, &c->rng_seed, &c->rng_scratch, &c->tail_done, &c->tail_park})
         f(*b);
@@ -597,6 +601,15 @@ int ssa_internal_hash_scalars(ssa_ctx *ctx, const DevBatch &b, size_t n);
 // d_h (the per-lane workspace reserved for one slice of lanes); *d_fail is added to
 int ssa_internal_verify_hashed(ssa_ctx *ctx, const DevBatch &b, const uint64_t *d_h, size_t n, uint32_t flags,
                                uint8_t *d_status_out, unsigned long long *d_fail);
+
+// defined in ssa_api.hip, for ssa_verify_many_screened (ssa_msm.hip): the distinct keys of one slice of at most
+// ctx->lane_slice lanes checked once each (ctx->dd_idx, ctx->dd_kstatus, tables in ctx->ws_tab; one synchronisation, for
+// u), and ssa_k_verify_keyed over n lanes against those keys (*d_fail is added to)
+int ssa_internal_dedup_keys(ssa_ctx *ctx, const uint8_t *d_pks, const uint8_t *d_pk_inf, size_t cnt, uint64_t *u_out,
+                            uint64_t *bound_hits_out);
+int ssa_internal_verify_keyed(ssa_ctx *ctx, const uint8_t *d_sigs, const uint32_t *d_key_idx, uint64_t u,
+                              const uint64_t *d_h, size_t n, uint32_t flags, uint8_t *d_status_out,
+                              unsigned long long *d_fail);
 
 // defined in ssa_sign.hip (ssa_selfcheck.hpp): the exact check of a comb table for G (res[0] failing rows, res[1] the
 // first failing row or ~0) and of the context's constant-time table (out[0] rows checked, out[1], out[2] as res)

@@ -106,7 +106,11 @@ msm_k_prepare(const u8 *__restrict__ sigs, const u8 *__restrict__ pks, const u8 
               const u64 *__restrict__ h_in,
               const u8 *__restrict__ coeffs, u32 coeff_bytes, size_t n, MsmShape shp, u32 wa, u64 *__restrict__ points,
               short *__restrict__ digits, u64 *__restrict__ partials, u32 *__restrict__ malformed,
-              u64 *__restrict__ s_out, u8 *__restrict__ status) {
+              u64 *__restrict__ s_out, u8 *__restrict__ status, const u8 *__restrict__ lane_mask,
+              u8 *__restrict__ recheck) {
+    // recheck != nullptr (ssa_verify_many_screened): a lane whose key could not be screened
+    // (lane_mask[i] != 0) or that fails a check here enters the sums as the identity, like a malformed lane, but gets NO
+    // status from this kernel: recheck[i] = 1 sends it to the exact kernel, the only authority for a nonzero status.
     // h_in == nullptr (round 5): everything that does not need the challenge scalars -- the checks, R's square root,
     // the coefficient's digits, s_i e_i -- so that this kernel can run on a second stream UNDER ssa_k_hash (it fills the
     // hash kernel's tail and its own); the coefficient s_i is left in s_out for msm_k_prepare_h, which writes the digits
@@ -130,6 +134,10 @@ msm_k_prepare(const u8 *__restrict__ sigs, const u8 *__restrict__ pks, const u8 
         aff R;
         bool r_inf = false;
         if (ok) ok = decompress_lane(sigs + 81 * i, R, r_inf) == 0;   // from_compressed(..).unwrap(), :104
+        if (recheck) {
+            ok = ok && lane_mask[i] == 0;
+            recheck[i] = (u8)(ok ? 0u : 1u);
+        }
         if (!ok) {
             atomicOr(malformed, 1u);
             R.x = f6_zero(); R.y = f6_zero();
@@ -137,7 +145,7 @@ msm_k_prepare(const u8 *__restrict__ sigs, const u8 *__restrict__ pks, const u8 
         }
         // the screened form's per-lane status: 3 exactly where the per-lane check with the flag byte says 3 (the same
         // limb, range, curve and decompression checks); 0 stands until the lane's segment fails
-        if (status) status[i] = (u8)(ok ? ST_OK : ST_MALFORMED);
+        if (status) status[i] = (u8)(ok || recheck ? ST_OK : ST_MALFORMED);
         if (r_inf) {  // identity R: the (0, 0) sentinel jac_madd skips
             R.x = f6_zero();
             R.y = f6_zero();
@@ -906,6 +914,107 @@ msm_k_screen_count(const u8 *__restrict__ status, size_t n, unsigned long long *
     if ((threadIdx.x & 63u) == 0 && bad) atomicAdd(n_fail, (unsigned long long)__popcll(bad));
 }
 
+// ---- ssa_verify_many_screened: the lanes to re-check as an index list ------------------------
+// Everything these kernels write is read by a LATER launch on the same stream (or by the host after the stream has been
+// synchronised); the only values that workgroups of one launch combine are counters, by agent-scope atomic adds.
+constexpr u32 SCR_BLOCK = 256;
+
+// lane_mask[i] = lane i cannot be screened because of its key: the per-key check found it malformed or outside the
+// prime-order subgroup.  Such a lane stays out of every sum, WHATEVER the flags: the per-key check computes [q]P == O
+// anyway, and a key outside the subgroup is the one way an error of pure small order gets into a sum on the key side.
+// Without SSA_FLAG_CHECK_TORSION the exact kernel then verifies the lane against that key as ssa_verify_many does.
+__global__ void __launch_bounds__(256)
+msm_k_screen_keymask(const u32 *__restrict__ key_idx, const u8 *__restrict__ key_status, u32 n_keys, u32 n,
+                     u8 *__restrict__ lane_mask) {
+    const u32 i = blockIdx.x * SCR_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const u32 k = key_idx[i];
+    lane_mask[i] = (u8)((k < n_keys && key_status[k] == ST_OK) ? 0u : 1u);
+}
+
+// mark[i] (in: msm_k_prepare's "could not be screened"; out: "re-check") |= the lane's segment failed;
+// blk_cnt[b] = marked lanes of workgroup b; cnt[0] += lanes that could not be screened
+__global__ void __launch_bounds__(256)
+msm_k_screen_mark(const u8 *__restrict__ seg_ok, u32 seg_lanes, u32 n, u8 *__restrict__ mark, u32 *__restrict__ blk_cnt,
+                  unsigned long long *__restrict__ cnt) {
+    __shared__ u32 wave_cnt[SCR_BLOCK / 64];
+    const u32 i = blockIdx.x * SCR_BLOCK + threadIdx.x;
+    const bool unscreened = i < n && mark[i] != 0;
+    const bool m = i < n && (unscreened || seg_ok[i / seg_lanes] == 0);
+    if (i < n) mark[i] = (u8)(m ? 1u : 0u);
+    const unsigned long long ms = __ballot(m), us = __ballot(unscreened);
+    if ((threadIdx.x & 63u) == 0) {
+        wave_cnt[threadIdx.x >> 6] = (u32)__popcll(ms);
+        if (us) atomicAdd(cnt, (unsigned long long)__popcll(us));
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) blk_cnt[blockIdx.x] = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+}
+
+// ONE workgroup: blk_off[b] = marked lanes in front of workgroup b's; cnt[1] = the length of the list
+__global__ void __launch_bounds__(256)
+msm_k_screen_scan(const u32 *__restrict__ blk_cnt, u32 nb, u32 *__restrict__ blk_off, unsigned long long *__restrict__ cnt) {
+    __shared__ u32 part[SCR_BLOCK];
+    const u32 t = threadIdx.x, per = (nb + SCR_BLOCK - 1) / SCR_BLOCK;
+    const u32 lo = t * per < nb ? t * per : nb, hi = lo + per < nb ? lo + per : nb;
+    u32 sum = 0;
+    for (u32 b = lo; b < hi; b++) sum += blk_cnt[b];
+    part[t] = sum;
+    __syncthreads();
+    if (t == 0) {
+        u32 acc = 0;
+        for (u32 k = 0; k < SCR_BLOCK; k++) {
+            const u32 v = part[k];
+            part[k] = acc;
+            acc += v;
+        }
+        cnt[1] = acc;
+    }
+    __syncthreads();
+    u32 acc = part[t];
+    for (u32 b = lo; b < hi; b++) {
+        blk_off[b] = acc;
+        acc += blk_cnt[b];
+    }
+}
+
+// list[c] = the c-th marked lane, in lane order
+__global__ void __launch_bounds__(256)
+msm_k_screen_list(const u8 *__restrict__ mark, u32 n, const u32 *__restrict__ blk_off, u32 *__restrict__ list) {
+    __shared__ u32 wave_cnt[SCR_BLOCK / 64];
+    const u32 i = blockIdx.x * SCR_BLOCK + threadIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const bool m = i < n && mark[i] != 0;
+    const unsigned long long ms = __ballot(m);
+    if (lane == 0) wave_cnt[wave] = (u32)__popcll(ms);
+    __syncthreads();
+    if (!m) return;
+    u32 pos = blk_off[blockIdx.x] + (u32)__popcll(ms & ((1ull << lane) - 1ull));
+    for (u32 k = 0; k < wave; k++) pos += wave_cnt[k];
+    list[pos] = i;
+}
+
+// the listed lanes -> compact buffers: signature (81 B, thread t copies byte t % 81 of list entry t / 81), challenge
+// scalar (32 B) and key index
+__global__ void __launch_bounds__(256)
+msm_k_screen_gather_list(const u32 *__restrict__ list, u32 m, const u8 *__restrict__ sigs, const u64 *__restrict__ h,
+                         const u32 *__restrict__ key_idx, u8 *__restrict__ g_sigs, u64 *__restrict__ g_h,
+                         u32 *__restrict__ g_idx) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (size_t)m * 81) return;
+    const u32 c = (u32)(t / 81), k = (u32)(t % 81);
+    const size_t src = list[c];
+    g_sigs[t] = sigs[81 * src + k];
+    if (k < 4) g_h[4 * (size_t)c + k] = h[4 * src + k];
+    else if (k == 4) g_idx[c] = key_idx[src];
+}
+
+// compact statuses -> the listed lanes
+__global__ void __launch_bounds__(256)
+msm_k_screen_scatter_list(const u32 *__restrict__ list, u32 m, const u8 *__restrict__ g_status, u8 *__restrict__ status) {
+    const u32 c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c < m) status[list[c]] = g_status[c];
+}
+
 // ---- small batches: Straus on cooperating waves ---------------------------------------------------
 // The bucket method pays ~20 launches of lone, latency-bound waves however small the batch is (2.5 ms at the
 // reference's own bench sizes, benches/schnorr.rs:78-96: 4..128 signatures).  Below MSM_SMALL_MAX signatures the
@@ -1270,6 +1379,10 @@ extern "C" int ssa_msm_combine(ssa_ctx *ctx, const uint64_t *parts24, size_t k) 
 struct ScreenArgs {
     u32 segs, seg_blocks;
     u8 *status, *seg_ok;
+    // ssa_verify_many_screened only (null in ssa_verify_batch_screened): lanes to leave out of the sums, and where
+    // msm_k_prepare marks them and its own decode failures for the exact re-check instead of writing a status
+    const u8 *lane_mask = nullptr;
+    u8 *recheck = nullptr;
 };
 constexpr u32 SCREEN_C = 8;                 // window bits: K * 2^(c-1) <= 256 * 128 stays within the grouping grid
 static MsmShape screen_shape(u32 segs) {
@@ -1388,7 +1501,8 @@ static int msm_run_one(ssa_ctx *ctx, const DevBatch &b, size_t n, const uint8_t 
         hipLaunchKernelGGL(msm_k_prepare, dim3(n_blocks), dim3(256), 0, side, b.sigs, b.pks, b.pk_inf,
                            (const u64 *)nullptr, d_coeffs, coeff_bytes, n, sh, wa, (u64 *)ctx->msm_points.p,
                            (short *)ctx->msm_scalars.p, (u64 *)ctx->msm_partials.p, (u32 *)ctx->msm_flags.p,
-                           (u64 *)ctx->msm_sbuf.p, scr ? scr->status : (u8 *)nullptr);
+                           (u64 *)ctx->msm_sbuf.p, scr ? scr->status : (u8 *)nullptr,
+                           scr ? scr->lane_mask : (const u8 *)nullptr, scr ? scr->recheck : (u8 *)nullptr);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(ctx->hash_done[0], side));
         if (int hrc = ssa_internal_hash_scalars(ctx, b, n)) return hrc;
@@ -1410,7 +1524,8 @@ static int msm_run_one(ssa_ctx *ctx, const DevBatch &b, size_t n, const uint8_t 
             hipLaunchKernelGGL(msm_k_prepare, dim3(n_blocks), dim3(256), 0, ctx->stream, b.sigs, b.pks, b.pk_inf,
                                d_h, d_coeffs, coeff_bytes, n, sh, wa, (u64 *)ctx->msm_points.p,
                                (short *)ctx->msm_scalars.p, (u64 *)ctx->msm_partials.p, (u32 *)ctx->msm_flags.p,
-                               (u64 *)nullptr, scr ? scr->status : (u8 *)nullptr);
+                               (u64 *)nullptr, scr ? scr->status : (u8 *)nullptr,
+                               scr ? scr->lane_mask : (const u8 *)nullptr, scr ? scr->recheck : (u8 *)nullptr);
         });
         if (rc) return rc;
     }
@@ -1770,4 +1885,218 @@ extern "C" int ssa_verify_batch_screened(ssa_ctx *ctx, const uint8_t *sigs, cons
                                        return screen_host_one(c, s, cnt, coeffs ? coeffs + 32 * lo : nullptr,
                                                               status_out + lo, nf);
                                    });
+}
+
+// ------------------------------------------------------------------------------------------------
+// ssa_verify_many_screened: the screen above under the semantics of ssa_verify_many, for any
+// combination of SSA_FLAG_CHECK_TORSION and SSA_FLAG_SIG_FLAG_BYTE.  Per slice of at most SSA_LANE_SLICE lanes: the
+// distinct keys are found and checked once each (ssa_internal_dedup_keys), a lane whose key failed that check -- or whose
+// signature gives msm_k_prepare no R -- is left out of the sums and marked, the segments are screened, and the marked
+// lanes together with the lanes of failing segments run ssa_k_verify_keyed on the keys' tables and the hashes of the
+// screen.  The screen only ever accepts: every nonzero status comes from the exact kernel.
+constexpr uint32_t MANY_SCREEN_FLAGS = SSA_FLAG_CHECK_TORSION | SSA_FLAG_SIG_FLAG_BYTE;
+
+// what the entry points report (the host form's two threads add to it under the lock)
+struct ManyScreenStats {
+    std::mutex mu;
+    uint64_t v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    void add(const uint64_t d[8]) {
+        std::lock_guard<std::mutex> lock(mu);
+        for (int k = 0; k < 8; k++) v[k] += d[k];
+    }
+};
+
+// ONE slice (n <= ctx->lane_slice) on ctx->stream into d_status[0, n): d_h = the slice's challenge scalars if they exist
+// (else they are computed into ctx->ws_h).  Synchronises the stream twice: for u, and for the segment verdicts together
+// with the length of the re-check list.
+static int screen_many_slice(ssa_ctx *ctx, const DevBatch &b, size_t n, const uint8_t *d_coeffs, uint32_t coeff_bytes,
+                             uint32_t flags, const u64 *d_h, uint8_t *d_status, ManyScreenStats *stats) {
+    uint64_t sv[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (ctx->scr_fail.reserve(16)) return SSA_ERR_HIP;
+    unsigned long long *scratch_fail = (unsigned long long *)ctx->scr_fail.p;    // (the caller counts the statuses)
+    if (n <= ctx->msm_small_max) {      // the exact per-lane path, the caller's flags
+        sv[6] = 1;
+        const int rc = d_h ? ssa_internal_verify_hashed(ctx, b, d_h, n, flags, d_status, scratch_fail)
+                           : ssa_verify_many_device(ctx, b.sigs, b.pks, b.pk_inf, b.msgs.msgs, b.msgs.off, b.msgs.stride,
+                                                    b.msgs.len, n, flags, d_status, (uint64_t *)scratch_fail);
+        if (rc == 0 && stats) stats->add(sv);
+        return rc;
+    }
+    uint64_t u = 0, hits = 0;
+    if (int rc = ssa_internal_dedup_keys(ctx, b.pks, b.pk_inf, n, &u, &hits)) return rc;
+    const unsigned nb = grid_for(n, SCR_BLOCK);
+    if (ctx->scr_mask.reserve(n + 16) || ctx->scr_mark.reserve(n + 16) || ctx->scr_list.reserve(n * sizeof(u32)) ||
+        ctx->scr_blk.reserve(2 * (size_t)nb * sizeof(u32)) || ctx->scr_cnt.reserve(64) || ctx->scr_ok.reserve(SCREEN_MAX_SEGS))
+        return SSA_ERR_HIP;
+    const u32 *key_idx = (const u32 *)ctx->dd_idx.p;
+    u8 *mark = (u8 *)ctx->scr_mark.p;
+    u32 *blk_cnt = (u32 *)ctx->scr_blk.p, *blk_off = blk_cnt + nb, *list = (u32 *)ctx->scr_list.p;
+    unsigned long long *d_cnt = (unsigned long long *)ctx->scr_cnt.p;
+    int rc = timed_launch(ctx, "screen_keymask", [&] {
+        hipLaunchKernelGGL(msm_k_screen_keymask, dim3(nb), dim3(SCR_BLOCK), 0, ctx->stream, key_idx,
+                           (const u8 *)ctx->dd_kstatus.p, (u32)u, (u32)n, (u8 *)ctx->scr_mask.p);
+    });
+    if (rc) return rc;
+    // (the side stream of msm_run_one waits for everything queued on ctx->stream so far: the key check and the mask are
+    //  ordered before the half of msm_k_prepare that reads the mask, and that half still runs under the hash)
+    const ScreenPlan pl = screen_plan(n, ctx->screen_segs);
+    ScreenArgs sa{pl.segs, pl.seg_lanes / 256u, d_status, (u8 *)ctx->scr_ok.p};
+    sa.lane_mask = (const u8 *)ctx->scr_mask.p;
+    sa.recheck = mark;
+    if ((rc = msm_run_one(ctx, b, n, d_coeffs, coeff_bytes, nullptr, nullptr, d_h, &sa))) return rc;
+    const u64 *h = d_h ? d_h : (const u64 *)ctx->ws_h.p;     // (msm_run_one hashed into ws_h)
+    HIP_TRY(hipMemsetAsync(d_cnt, 0, 2 * sizeof(unsigned long long), ctx->stream));
+    rc = timed_launch(ctx, "screen_mark", [&] {
+        hipLaunchKernelGGL(msm_k_screen_mark, dim3(nb), dim3(SCR_BLOCK), 0, ctx->stream, (const u8 *)ctx->scr_ok.p,
+                           pl.seg_lanes, (u32)n, mark, blk_cnt, d_cnt);
+        hipLaunchKernelGGL(msm_k_screen_scan, dim3(1), dim3(SCR_BLOCK), 0, ctx->stream, (const u32 *)blk_cnt, (u32)nb,
+                           blk_off, d_cnt);
+    });
+    if (rc) return rc;
+    uint8_t ok[SCREEN_MAX_SEGS];
+    unsigned long long cnt[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(ok, ctx->scr_ok.p, pl.segs, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    const size_t m = (size_t)cnt[1];
+    if (m > n || cnt[0] > m) return SSA_ERR_HIP;     // (never)
+    sv[0] = u;
+    sv[1] = pl.segs;
+    for (u32 s = 0; s < pl.segs; s++) sv[2] += ok[s] ? 0 : 1;
+    sv[3] = m;
+    sv[4] = cnt[0];
+    sv[5] = 1;
+    sv[7] = hits;
+    if (m == 0) {
+        if (stats) stats->add(sv);
+        return 0;
+    }
+    if (2 * m > n) {     // most of the slice: no list, the keyed kernel over all of it in place
+        sv[6] = 1;
+        rc = ssa_internal_verify_keyed(ctx, b.sigs, key_idx, u, h, n, flags, d_status, scratch_fail);
+        if (rc == 0 && stats) stats->add(sv);
+        return rc;
+    }
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t o_h = al(m * 81), o_idx = o_h + al(m * 32), total = o_idx + al(m * sizeof(u32));
+    if (ctx->scr_in.reserve(total) || ctx->scr_status.reserve(m + 16)) return SSA_ERR_HIP;
+    u8 *g = (u8 *)ctx->scr_in.p;
+    rc = timed_launch(ctx, "screen_list_gather", [&] {
+        hipLaunchKernelGGL(msm_k_screen_list, dim3(nb), dim3(SCR_BLOCK), 0, ctx->stream, (const u8 *)mark, (u32)n,
+                           (const u32 *)blk_off, list);
+        hipLaunchKernelGGL(msm_k_screen_gather_list, dim3(grid_for(m * 81, 256)), dim3(256), 0, ctx->stream,
+                           (const u32 *)list, (u32)m, b.sigs, h, key_idx, g, (u64 *)(g + o_h), (u32 *)(g + o_idx));
+    });
+    if (rc) return rc;
+    if ((rc = ssa_internal_verify_keyed(ctx, g, (const u32 *)(g + o_idx), u, (const u64 *)(g + o_h), m, flags,
+                                        (u8 *)ctx->scr_status.p, scratch_fail)))
+        return rc;
+    rc = timed_launch(ctx, "screen_list_scatter", [&] {
+        hipLaunchKernelGGL(msm_k_screen_scatter_list, dim3(grid_for(m, 256)), dim3(256), 0, ctx->stream, (const u32 *)list,
+                           (u32)m, (const u8 *)ctx->scr_status.p, d_status);
+    });
+    if (rc == 0 && stats) stats->add(sv);
+    return rc;
+}
+
+static void many_screen_stats_out(const ManyScreenStats &st, uint64_t stats_out[8]) {
+    if (stats_out)
+        for (int k = 0; k < 8; k++) stats_out[k] = st.v[k];
+}
+
+// slices of this call: SSA_LANE_SLICE lanes (the dedup table, the per-key tables and the screen share one slice)
+static size_t many_screen_slice_lanes(const ssa_ctx *ctx) {
+    const size_t cap = (size_t)1 << 23;      // (msm_run_one: an item carries its point index in 24 bits)
+    return ctx->lane_slice < cap ? ctx->lane_slice : cap;
+}
+
+extern "C" int ssa_verify_many_screened_device(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks,
+                                               const uint8_t *d_pk_inf, const uint8_t *d_msgs, const uint64_t *d_msg_off,
+                                               size_t msg_stride, size_t msg_len, size_t n, uint32_t flags,
+                                               const uint8_t *d_coeffs, uint32_t coeff_bytes, uint8_t *d_status_out,
+                                               uint64_t *d_n_fail_out, uint64_t stats_out[8]) {
+    if (flags & ~MANY_SCREEN_FLAGS) return SSA_ERR_ARG;
+    const DevBatch b{d_sigs, d_pks, d_pk_inf, {d_msgs, d_msg_off, msg_stride, msg_len}};
+    if (!ctx || (n && (!d_sigs || !d_pks || !d_status_out))) return SSA_ERR_ARG;
+    if (d_coeffs && (coeff_bytes == 0 || coeff_bytes > 32)) return SSA_ERR_ARG;
+    if (int rc = check_msgs(b.msgs, n)) return rc;
+    if (stats_out) std::memset(stats_out, 0, 8 * sizeof(uint64_t));
+    if (flags == SSA_FLAG_SIG_FLAG_BYTE)      // verify_batch semantics: no key check to add, the screened form as it is
+        return ssa_verify_batch_screened_device(ctx, d_sigs, d_pks, d_pk_inf, d_msgs, d_msg_off, msg_stride, msg_len, n,
+                                                d_coeffs, coeff_bytes, d_status_out, d_n_fail_out);
+    HIP_TRY(hipSetDevice(ctx->device));
+    unsigned long long *d_fail;
+    if (int rc = reset_fail_counter(ctx, d_n_fail_out, &d_fail)) return rc;
+    if (n == 0) return 0;
+    ManyScreenStats st;
+    if (n <= ctx->msm_small_max) {
+        const int rc = ssa_verify_many_device(ctx, d_sigs, d_pks, d_pk_inf, d_msgs, d_msg_off, msg_stride, msg_len, n, flags,
+                                              d_status_out, (uint64_t *)d_fail);
+        if (rc == 0 && stats_out) stats_out[6] = 1;
+        return rc;
+    }
+    const size_t slice = many_screen_slice_lanes(ctx);
+    for (size_t lo = 0; lo < n; lo += slice) {      // segments never straddle two slices
+        const size_t cnt = n - lo < slice ? n - lo : slice;
+        if (int rc = screen_many_slice(ctx, b.slice(lo), cnt, d_coeffs ? d_coeffs + (size_t)coeff_bytes * lo : nullptr,
+                                       coeff_bytes, flags, nullptr, d_status_out + lo, stats_out ? &st : nullptr))
+            return rc;
+    }
+    if (int rc = screen_count(ctx, d_status_out, n, d_fail)) return rc;
+    many_screen_stats_out(st, stats_out);
+    return 0;
+}
+
+// ONE slice from host buffers (the staging of screen_host_one): statuses into status_out[0, n), *nf the count
+static int screen_many_host_one(ssa_ctx *ctx, const HostBatch &b, size_t n, uint32_t flags, const uint8_t *coeffs,
+                                uint8_t *status_out, uint64_t *nf, ManyScreenStats *stats) {
+    HostCall hc(ctx);
+    PipelinedInputs pin;      // its destructor drains the side streams on every error return
+    const StagedInputs s = slice_inputs(hc, pin, b, n, coeffs, true, false);
+    u8 *d_status = hc.out(ctx->st_status, status_out, n, 16);
+    unsigned long long v = 0, *d_fail = (unsigned long long *)ctx->ws_fail.p;
+    hc.copy_back(&v, d_fail, sizeof v);
+    if (int rc = hc.finish([&] {
+            if (int r = screen_many_slice(ctx, s.batch, n, s.coeffs, 32, flags,
+                                          s.hashed ? (const u64 *)ctx->ws_h.p : nullptr, d_status, stats))
+                return r;
+            return screen_count(ctx, d_status, n, d_fail);
+        }))
+        return rc;
+    pin.done();
+    if (nf) *nf = v;
+    return 0;
+}
+
+extern "C" int ssa_verify_many_screened(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_inf,
+                                        const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len,
+                                        size_t n, uint32_t flags, const uint8_t *coeffs, uint8_t *status_out,
+                                        uint64_t *n_fail_out, uint64_t stats_out[8]) {
+    if (flags & ~MANY_SCREEN_FLAGS) return SSA_ERR_ARG;
+    if (!ctx || (n && (!sigs || !pks || !status_out))) return SSA_ERR_ARG;
+    if (int rc = check_msgs({msgs, msg_off, msg_stride, msg_len}, n)) return rc;
+    if (int rc = check_host_offsets(msg_off, n)) return rc;
+    if (stats_out) std::memset(stats_out, 0, 8 * sizeof(uint64_t));
+    if (flags == SSA_FLAG_SIG_FLAG_BYTE)
+        return ssa_verify_batch_screened(ctx, sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len, n, coeffs, status_out,
+                                         n_fail_out);
+    if (n_fail_out) *n_fail_out = 0;
+    if (n == 0) return 0;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (n <= ctx->msm_small_max) {
+        const int rc = ssa_verify_many(ctx, sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len, n, flags, status_out,
+                                       n_fail_out);
+        if (rc == 0 && stats_out) stats_out[6] = 1;
+        return rc;
+    }
+    const HostBatch b{sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len};
+    ManyScreenStats st;
+    const int rc = run_host_slices_counted(ctx, b, n, many_screen_slice_lanes(ctx), n_fail_out,
+                                           [&](ssa_ctx *c, size_t lo, size_t cnt, const HostBatch &s, uint64_t *nf) {
+                                               return screen_many_host_one(c, s, cnt, flags, coeffs ? coeffs + 32 * lo : nullptr,
+                                                                           status_out + lo, nf, stats_out ? &st : nullptr);
+                                           });
+    if (rc) return rc;
+    many_screen_stats_out(st, stats_out);
+    return 0;
 }

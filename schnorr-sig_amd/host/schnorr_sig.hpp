@@ -588,6 +588,35 @@ inline std::vector<uint8_t> verify_batch_statuses(Context &cx, const std::vector
     return status;
 }
 
+// (signature, public key, message) triples as the batch entry points take them: 81-byte signatures, 96-byte affine keys,
+// identity flags, the messages back to back with their n + 1 offsets.  The length checks of the reference's verify_batch.
+struct PackedTriples {
+    std::vector<uint8_t> sigs, pks, inf, flat;
+    std::vector<uint64_t> off;
+};
+inline PackedTriples pack_triples(const std::vector<Signature> &signatures, const std::vector<PublicKey> &public_keys,
+                                  const std::vector<std::pair<const uint8_t *, size_t>> &messages) {
+    if (signatures.size() != public_keys.size())
+        throw Panic("We should have the same number of signatures than public keys");
+    if (messages.size() != public_keys.size())
+        throw Panic("We should have the same number of messages than public keys");
+    const size_t n = signatures.size();
+    PackedTriples t;
+    t.sigs.resize(n * SIGNATURE_LENGTH);
+    t.pks.resize(n * AFFINE_PUBLIC_KEY_LENGTH);
+    t.inf.resize(n);
+    t.off.assign(n + 1, 0);
+    for (size_t i = 0; i < n; i++) {
+        std::memcpy(&t.sigs[i * SIGNATURE_LENGTH], signatures[i].bytes.data(), SIGNATURE_LENGTH);
+        std::memcpy(&t.pks[i * AFFINE_PUBLIC_KEY_LENGTH], public_keys[i].affine.data(), AFFINE_PUBLIC_KEY_LENGTH);
+        t.inf[i] = public_keys[i].is_identity ? 1 : 0;
+        t.flat.insert(t.flat.end(), messages[i].first, messages[i].first + messages[i].second);
+        t.off[i + 1] = t.flat.size();
+    }
+    t.flat.push_back(0);
+    return t;
+}
+
 // Signature::verify (src/signature.rs:181-205) over a slice of signatures in which public keys repeat: one status per
 // signature (0 Ok, 1 InvalidPublicKey, 2 InvalidSignature, 3 malformed: the reference would panic), the same vector as n
 // single calls, with each DISTINCT key's subgroup check and table run once on the GPU.
@@ -595,26 +624,36 @@ inline std::vector<uint8_t> verify_many_statuses(Context &cx, const std::vector<
                                                  const std::vector<PublicKey> &public_keys,
                                                  const std::vector<std::pair<const uint8_t *, size_t>> &messages,
                                                  uint64_t *stats_out = nullptr) {
-    if (signatures.size() != public_keys.size())
-        throw Panic("We should have the same number of signatures than public keys");
-    if (messages.size() != public_keys.size())
-        throw Panic("We should have the same number of messages than public keys");
+    const PackedTriples t = pack_triples(signatures, public_keys, messages);
     const size_t n = signatures.size();
     std::vector<uint8_t> status(n, 0);
     if (n == 0) return status;
-    std::vector<uint8_t> sigs(n * SIGNATURE_LENGTH), pks(n * AFFINE_PUBLIC_KEY_LENGTH), inf(n), flat;
-    std::vector<uint64_t> off(n + 1, 0);
-    for (size_t i = 0; i < n; i++) {
-        std::memcpy(&sigs[i * SIGNATURE_LENGTH], signatures[i].bytes.data(), SIGNATURE_LENGTH);
-        std::memcpy(&pks[i * AFFINE_PUBLIC_KEY_LENGTH], public_keys[i].affine.data(), AFFINE_PUBLIC_KEY_LENGTH);
-        inf[i] = public_keys[i].is_identity ? 1 : 0;
-        flat.insert(flat.end(), messages[i].first, messages[i].first + messages[i].second);
-        off[i + 1] = flat.size();
-    }
-    flat.push_back(0);
-    const int rc = ssa_verify_many_dedup(cx.get(), sigs.data(), pks.data(), inf.data(), flat.data(), off.data(), 0, 0, n,
-                                         SSA_FLAG_CHECK_TORSION, status.data(), nullptr, stats_out);
+    const int rc = ssa_verify_many_dedup(cx.get(), t.sigs.data(), t.pks.data(), t.inf.data(), t.flat.data(), t.off.data(),
+                                         0, 0, n, SSA_FLAG_CHECK_TORSION, status.data(), nullptr, stats_out);
     if (rc != 0) throw std::runtime_error(std::string("ssa_verify_many_dedup: ") + ssa_strerror(rc));
+    return status;
+}
+
+// The same vector as verify_many_statuses at about the price of one MSM for an honest slice: each
+// distinct key checked once, the segments of the slice screened by a random linear combination (coefficients from `rng`,
+// or drawn on the device), only the lanes of failing segments and the lanes that could not be screened checked exactly.
+// A rejected signature is reported except with the probability the header states.  stats_out: 8 words, optional.
+inline std::vector<uint8_t> verify_many_screened_statuses(Context &cx, const std::vector<Signature> &signatures,
+                                                          const std::vector<PublicKey> &public_keys,
+                                                          const std::vector<std::pair<const uint8_t *, size_t>> &messages,
+                                                          Rng rng = nullptr, uint64_t *stats_out = nullptr) {
+    const PackedTriples t = pack_triples(signatures, public_keys, messages);
+    const size_t n = signatures.size();
+    std::vector<uint8_t> status(n, 0), coeffs;
+    if (n == 0) return status;
+    if (rng) {
+        coeffs.resize(n * SCALAR_LENGTH);
+        for (size_t i = 0; i < n; i++) KeyPair::random_scalar(rng, &coeffs[i * SCALAR_LENGTH]);
+    }
+    const int rc = ssa_verify_many_screened(cx.get(), t.sigs.data(), t.pks.data(), t.inf.data(), t.flat.data(),
+                                            t.off.data(), 0, 0, n, SSA_FLAG_CHECK_TORSION, rng ? coeffs.data() : nullptr,
+                                            status.data(), nullptr, stats_out);
+    if (rc != 0) throw std::runtime_error(std::string("ssa_verify_many_screened: ") + ssa_strerror(rc));
     return status;
 }
 
