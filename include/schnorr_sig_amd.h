@@ -16,6 +16,8 @@
  *   ssa_verify_many_dedup   <- the same over a slice in which keys repeat: each distinct key is checked once
  *   ssa_verify_many_screened <- the same vector at about the price of one MSM: segments of the batch are screened by
  *                              a random linear combination, each distinct key's subgroup check runs once
+ *   ssa_verify_many_cached   <- the same call with a key cache on the device: every distinct public key is checked once,
+ *                              not once per batch (ssa_keycache_create).
  *   ssa_hash_message_many   <- hash_message                 src/signature.rs:274-306
  *   ssa_rescue_hash_many    <- RescueHash::hash_field       src/signature.rs:303
  *   ssa_verify_keyed_many   <- KeyedSignature::{from_bytes, verify}  src/signature.rs:232-271
@@ -532,6 +534,76 @@ int ssa_verify_many_screened_device(ssa_ctx *ctx, const uint8_t *d_sigs, const u
                                     size_t n, uint32_t flags, const uint8_t *d_coeffs, uint32_t coeff_bytes,
                                     uint8_t *d_status_out, uint64_t *d_n_fail_out, uint64_t stats_out[8]);
 
+/* ---- key cache: each public key checked once, not once per batch ------------------------
+ * A key cache is a key set that fills itself.  ssa_verify_many_cached is ssa_verify_many_screened with its per-key
+ * check (limbs, curve, [q]P == O, the table of sixteen multiples) behind a cache on the device: every distinct key of a
+ * slice is looked up by its bytes, only the keys never seen are checked, and their statuses and tables stay for the
+ * next slice and the next call.  The caller hands in no index and need not know the signers in advance.
+ *
+ * The object.  capacity = keys the cache can hold, 1 <= capacity <= 2^24 (anything else: SSA_ERR_ARG, *out = NULL).
+ * ALL device memory is allocated by ssa_keycache_create, none per call: per key the 4 KB table of sixteen multiples,
+ * the 96 key bytes, the pk_inf boolean and the status byte (the storage of a ladder-kind key set), and an
+ * open-addressing table of 64-bit words with at least four slots per key: about 4.2 KB per key, 4.4 GB for 2^20 keys.
+ * A failed allocation is SSA_ERR_HIP and leaves nothing behind.  ssa_keycache_clear empties the cache (one memset of
+ * the slot words on the context's stream; the next call is cold).  ssa_keycache_info: out[0] capacity, [1] keys held,
+ * [2] clears since creation (explicit and automatic), [3] device bytes.  A cache belongs to one context; the calls that
+ * use it are serialised by the caller, as calls on a context are.  A cache that outlives its context is orphaned, not
+ * dangling, as key sets are: its device memory is freed by ssa_ctx_destroy, every call on it but ssa_keycache_destroy
+ * then returns SSA_ERR_ARG.  ssa_keycache_destroy(NULL) is a no-op.
+ * A key's identity is the one of ssa_verify_many_dedup: the 96 key bytes and pk_inf as a boolean.  Equality is decided
+ * on those bytes, never on the fingerprint that picks the slot (keyed SipHash-2-4 under the context's random key).
+ * Keys with a nonzero status (malformed, or outside the prime-order subgroup) are cached like any other: a sender
+ * cannot force the check again by repeating a bad key.
+ *
+ * The calls.  Arguments, flag rules (SSA_FLAG_CHECK_TORSION and SSA_FLAG_SIG_FLAG_BYTE only; any other bit is
+ * SSA_ERR_ARG before anything else is looked at), coeffs, n == 0, SSA_MAX_BATCH, n_fail_out: those of
+ * ssa_verify_many_screened.  SSA_FLAG_SIG_FLAG_BYTE alone is handed to ssa_verify_batch_screened, and batches and
+ * trailing slices of at most SSA_MSM_SMALL_MAX lanes to ssa_verify_many: the cache is then not touched.  kc == NULL,
+ * or a cache of another context (or an orphaned one), is SSA_ERR_ARG.
+ * With the same coeffs the status vector is BYTE FOR BYTE the one ssa_verify_many_screened returns, in every state of
+ * the cache -- cold, warm, partly warm, just cleared, bypassed: the same keys with the same statuses and tables enter
+ * the same sums.  That is an equality, not a probability.
+ * Per slice of at most SSA_LANE_SLICE lanes:
+ *   1. the distinct keys of the slice, as in ssa_verify_many_dedup (u of them);
+ *   2. one lane per distinct key probes the cache (queued behind the dedup, in front of its read-back): u, the number
+ *      of lanes at the probe bound and the number of misses m come back in the dedup's one read-back;
+ *   3. on the host, a pure function of (capacity, held, u, m) (ssa_debug_keycache_plan):
+ *        held + m <= capacity   the m misses are inserted;
+ *        else u <= capacity     the cache is cleared (whole-cache eviction: no entry is ever deleted alone, so an
+ *                               empty slot always ends a probe chain) and all u keys of the slice are inserted;
+ *        else                   the slice BYPASSES the cache and runs exactly as in ssa_verify_many_screened; the
+ *                               cache is left as it was;
+ *   4. the new keys' bytes are gathered into the next rows, ssa_k_keyset_build runs over those rows only, and a
+ *      publishing launch claims a slot per new row by a vector compare-and-swap.  It is queued after the build: a row is
+ *      complete before any later launch can find it.  A row that finds no empty slot within the probe bound is used by
+ *      this call and is simply not found by the next one;
+ *   5. every lane gets its key's cache row, and the mask, the segmented MSM and the keyed exact kernel run as in
+ *      ssa_verify_many_screened, reading the cache's statuses and tables.
+ * The slices of one call run IN ORDER ON THE CONTEXT'S STREAM IN BOTH FORMS: the host form does not alternate its
+ * slices between the context and its second set of streams as the other host forms do, because two streams would
+ * mutate one cache.  It gives up the ~2 % overlap of multi-slice host calls.  Two synchronisations per slice, as
+ * ssa_verify_many_screened; no allocation per call once the context's workspaces have grown.
+ * stats_out (optional, HOST memory in both forms, 12 words, summed over the slices): [0..7] as
+ * ssa_verify_many_screened, with the rows that could not be published added to [7]; [8] distinct keys found in the
+ * cache, [9] keys checked and inserted, [10] automatic clears, [11] slices that bypassed the cache.  [8] + [9] == [0]
+ * over the slices that used the cache.
+ * Timing keys beside those of ssa_verify_many_screened: keycache_lookup, keycache_insert (gather and publish),
+ * keycache_map; ssa_k_keyset_build keeps its key, and a warm call launches none.  Measured: DESIGN.md section 16. */
+typedef struct ssa_keycache ssa_keycache;
+int ssa_keycache_create(ssa_ctx *ctx, size_t capacity, ssa_keycache **out);
+void ssa_keycache_destroy(ssa_keycache *kc);
+int ssa_keycache_clear(ssa_keycache *kc);
+int ssa_keycache_info(ssa_keycache *kc, uint64_t out[4]);
+int ssa_verify_many_cached(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_inf,
+                           const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len, size_t n,
+                           uint32_t flags, const uint8_t *coeffs, uint8_t *status_out, uint64_t *n_fail_out,
+                           uint64_t stats_out[12]);
+int ssa_verify_many_cached_device(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *d_sigs, const uint8_t *d_pks,
+                                  const uint8_t *d_pk_inf, const uint8_t *d_msgs, const uint64_t *d_msg_off,
+                                  size_t msg_stride, size_t msg_len, size_t n, uint32_t flags, const uint8_t *d_coeffs,
+                                  uint32_t coeff_bytes, uint8_t *d_status_out, uint64_t *d_n_fail_out,
+                                  uint64_t stats_out[12]);
+
 /* ---- signer sets: many signatures by few signers (the signing twin of the key set) ---------------------------
  * A signer set holds m key pairs on the device: the secret key, the 96-byte affine public key, the 49-byte compressed
  * key and a per-key status.  Signature i is then KeyPair::sign (src/signature.rs:114-129) -- or, with
@@ -732,6 +804,11 @@ int ssa_debug_screen_segments(ssa_ctx *ctx, uint32_t k);
 int ssa_debug_dedup_device(ssa_ctx *ctx, const uint8_t *d_pks, const uint8_t *d_pk_inf, size_t n,
                            uint32_t *d_key_idx_out, uint64_t out[2]);
 int ssa_debug_dedup_config(ssa_ctx *ctx, double max_distinct_ratio, uint32_t probe_bound);
+/* host logic of the key cache, no context and no device needed: what a slice with u distinct keys, m of them not in the
+ * cache, does to a cache of `capacity` rows holding `held`.  *plan_out: 0 insert the m misses, 1 clear the cache and
+ * insert all u keys, 2 bypass the cache.  SSA_ERR_ARG for a capacity outside 1..2^24, held > capacity, m > u or
+ * u > SSA_MAX_BATCH. */
+int ssa_debug_keycache_plan(uint64_t capacity, uint64_t held, uint64_t u, uint64_t m, uint32_t *plan_out);
 /* n_blocks 64-byte blocks of the ChaCha20 keystream the MSM coefficients come from (RFC 8439 known answers) */
 int ssa_debug_chacha20(ssa_ctx *ctx, const uint8_t key[32], const uint8_t nonce[12], uint32_t counter0,
                        size_t n_blocks, uint8_t *out);

@@ -207,6 +207,13 @@ def _load():
         "ssa_verify_many_dedup_device": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz, u32, vp, vp, vp]),
         "ssa_verify_many_screened": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz, u32, vp, vp, u64p, vp]),
         "ssa_verify_many_screened_device": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz, u32, vp, u32, vp, vp, vp]),
+        "ssa_keycache_create": (i32, [vp, sz, C.POINTER(vp)]),
+        "ssa_keycache_destroy": (None, [vp]),
+        "ssa_keycache_clear": (i32, [vp]),
+        "ssa_keycache_info": (i32, [vp, u64p]),
+        "ssa_verify_many_cached": (i32, [vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, u32, vp, vp, u64p, vp]),
+        "ssa_verify_many_cached_device": (i32, [vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, u32, vp, u32, vp, vp, vp]),
+        "ssa_debug_keycache_plan": (i32, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(u32)]),
         "ssa_debug_dedup_device": (i32, [vp, vp, vp, sz, vp, vp]),
         "ssa_debug_dedup_config": (i32, [vp, C.c_double, u32]),
         "ssa_xprv_master_many": (i32, [vp, vp, sz, vp, vp]),
@@ -501,6 +508,54 @@ class Engine:
             self._ctx, d_sigs, d_pks, d_pk_inf or None, d_msgs, d_offsets or None,
             msg_stride if msg_stride is not None else msg_len, msg_len, n, flags, d_coeffs or None, coeff_bytes, d_status,
             d_nfail or None, stats.ctypes.data), "ssa_verify_many_screened_device")
+        return stats
+
+    def keycache_create(self, capacity):
+        """a key cache of `capacity` keys on this engine's device: all of its device memory, about
+        4.2 KB per key, is allocated here"""
+        h = C.c_void_p()
+        _check(_lib.ssa_keycache_create(self._ctx, int(capacity), C.byref(h)), "ssa_keycache_create")
+        return KeyCache(self, h)
+
+    def verify_many_cached(self, cache, sigs, pks, msgs, offsets=None, check_torsion=True, pk_inf=None,
+                           sig_flag_byte=False, coeffs=None):
+        """verify_many_screened with the per-key check behind a key cache -> (status uint8[n],
+        n_fail, stats uint64[12]).  The status vector is byte for byte the one verify_many_screened returns with the
+        same coeffs, in every state of the cache.  stats[0..7] as verify_many_screened (rows that could not be published
+        are added to [7]); [8] distinct keys found in the cache, [9] keys checked and inserted, [10] automatic clears,
+        [11] slices that bypassed the cache."""
+        sigs, pks = _np_u8(sigs, 81), _np_u8(pks, 96)
+        n = sigs.shape[0]
+        if pks.shape[0] != n:
+            raise MalformedInput("We should have the same number of signatures than public keys")
+        if n:
+            m, off, stride, mlen = self._msg_args(msgs, offsets, n)
+        else:
+            m, off, stride, mlen = None, None, 0, 0
+        c = _np_u8(coeffs, 32) if coeffs is not None else None
+        if c is not None:
+            assert c.shape[0] == n
+        inf = _np_u8(pk_inf) if pk_inf is not None else None
+        status = np.full(n, 255, dtype=np.uint8)
+        nfail = C.c_uint64(0)
+        stats = np.zeros(12, dtype=np.uint64)
+        flags = (FLAG_CHECK_TORSION if check_torsion else 0) | (FLAG_SIG_FLAG_BYTE if sig_flag_byte else 0)
+        _check(_lib.ssa_verify_many_cached(self._ctx, cache.handle, _ptr(sigs) if n else None, _ptr(pks) if n else None,
+                                           _ptr(inf), _ptr(m), _ptr(off), stride, mlen, n, flags, _ptr(c),
+                                           _ptr(status) if n else None, C.byref(nfail), stats.ctypes.data),
+               "ssa_verify_many_cached")
+        return status, int(nfail.value), stats
+
+    def verify_many_cached_device(self, cache, d_sigs, d_pks, d_msgs, n, msg_len, d_coeffs, coeff_bytes, d_status, d_nfail,
+                                  msg_stride=None, d_offsets=0, d_pk_inf=0, check_torsion=True, sig_flag_byte=False):
+        """device form of verify_many_cached (two synchronisations per slice, as verify_many_screened_device; the slices
+        run in order on the engine's stream); returns the statistics (uint64[12], host)"""
+        flags = (FLAG_CHECK_TORSION if check_torsion else 0) | (FLAG_SIG_FLAG_BYTE if sig_flag_byte else 0)
+        stats = np.zeros(12, dtype=np.uint64)
+        _check(_lib.ssa_verify_many_cached_device(
+            self._ctx, cache.handle, d_sigs, d_pks, d_pk_inf or None, d_msgs, d_offsets or None,
+            msg_stride if msg_stride is not None else msg_len, msg_len, n, flags, d_coeffs or None, coeff_bytes, d_status,
+            d_nfail or None, stats.ctypes.data), "ssa_verify_many_cached_device")
         return stats
 
     def debug_screen_segments(self, k):
@@ -1013,6 +1068,44 @@ class KeySet:
         if self.handle:
             _lib.ssa_keyset_destroy(self.handle)
             self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class KeyCache:
+    """ssa_keycache handle (Engine.keycache_create): checked public keys, their statuses and tables, kept on the device
+    across slices and calls of verify_many_cached.  Tied to its Engine like KeySet; destroyed exactly once (close(), the
+    end of a `with` block, or when the object goes away)."""
+
+    def __init__(self, engine, handle):
+        self.engine = engine      # keeps the context alive
+        self.handle = handle
+
+    def info(self):
+        """{'capacity', 'held', 'clears', 'device_bytes'}"""
+        out = (C.c_uint64 * 4)()
+        _check(_lib.ssa_keycache_info(self.handle, out), "ssa_keycache_info")
+        return {"capacity": int(out[0]), "held": int(out[1]), "clears": int(out[2]), "device_bytes": int(out[3])}
+
+    def clear(self):
+        """forget every key: the next call is cold"""
+        _check(_lib.ssa_keycache_clear(self.handle), "ssa_keycache_clear")
+
+    def close(self):
+        if self.handle:
+            _lib.ssa_keycache_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
 
     def __del__(self):
         try:
@@ -1580,6 +1673,31 @@ def verify_many_screened(signatures, public_keys, messages, rng=None, engine=Non
                                         for _ in signatures), np.uint8)
     status, _, _ = eng.verify_many_screened(sigs, pks, flat, offsets=off, check_torsion=True, pk_inf=inf, coeffs=coeffs)
     return _status_results(status)
+
+
+def verify_many_cached(signatures, public_keys, messages, cache, rng=None, engine=None):
+    """verify_many_screened with the public keys' checks kept in `cache` (Engine.keycache_create, DESIGN.md section
+    16): the same list, and a key that was seen in an earlier slice or call is not checked again.  The cache belongs to
+    the engine that made it: `engine` defaults to it."""
+    packed = _pack_triples(signatures, public_keys, messages)
+    if packed is None:
+        return []
+    sigs, pks, inf, flat, off = packed
+    eng = engine or cache.engine
+    coeffs = None
+    if rng is not None:
+        coeffs = np.frombuffer(b"".join((int.from_bytes(rng(64), "little") % Q).to_bytes(32, "little")
+                                        for _ in signatures), np.uint8)
+    status, _, _ = eng.verify_many_cached(cache, sigs, pks, flat, offsets=off, check_torsion=True, pk_inf=inf,
+                                          coeffs=coeffs)
+    return _status_results(status)
+
+
+def keycache_plan(capacity, held, u, m):
+    """host logic of the key cache (no device): 0 insert the m misses, 1 clear and insert all u keys, 2 bypass"""
+    out = C.c_uint32(0)
+    _check(_lib.ssa_debug_keycache_plan(int(capacity), int(held), int(u), int(m), C.byref(out)), "ssa_debug_keycache_plan")
+    return int(out.value)
 
 
 def verify_batch_statuses(signatures, public_keys, messages, rng=None, engine=None):

@@ -3,11 +3,12 @@
 // device or fails with an SSA_ERR_* code.
 #define SSA_KERNELS_DEFINE 1
 #include "ssa_ctx.hpp"
-#include "ssa_dedup.hpp"
+#include "ssa_keycache.hpp"
 
 #include <sys/random.h>
 
 #include <atomic>
+#include <functional>
 #include <mutex>
 #include <thread>
 
@@ -33,20 +34,6 @@ extern "C" const char *ssa_strerror(int rc) {
 extern "C" const void *ssa_default_params(void) { return k_default_params; }
 
 extern "C" int ssa_abi_version(void) { return SSA_ABI_VERSION; }
-
-// keyed context (defined here because ssa_ctx_destroy orphans the key sets that outlive their context)
-struct ssa_keyset {
-    ssa_ctx *ctx = nullptr;   // nullptr: the context is gone, the device memory went with it
-    size_t m = 0;
-    bool comb = false;      // per-key comb tables (16 x 65536 rows = 100 MB per key) instead of the ladder's 16 multiples
-    DevBuf tab, status, pks, ktab;
-    void release_all() {
-        tab.release();
-        status.release();
-        pks.release();
-        ktab.release();
-    }
-};
 
 // The comb table depends on the device, the generator and its geometry only, and it is up to 17.7 GB: contexts of one
 // process share it (reference-counted; ssa_multi_create with several contexts per device, the tests' many engines, a
@@ -400,6 +387,11 @@ extern "C" void ssa_ctx_destroy(ssa_ctx *ctx) {
         ss->ctx = nullptr;
     }
     ctx->signer_sets.clear();
+    for (ssa_keycache *kc : ctx->keycaches) {
+        kc->release_all();
+        kc->ctx = nullptr;
+    }
+    ctx->keycaches.clear();
     for (auto &kv : ctx->timed)
         for (auto &t : kv.second) {
             (void)hipEventDestroy(t.start);
@@ -1165,8 +1157,14 @@ static int dedup_fingerprint_key(ssa_ctx *ctx) {
 // The distinct keys of cnt <= lane_slice lanes on ctx->stream, into the context's workspaces: dd_idx (a key index per
 // lane), dd_reps (the representative lane of each key).  Synchronises the stream ONCE to read u and the number of lanes
 // that hit the probe bound: the policy of the caller needs u on the host.
+// A caller with a hook queues its own launches behind dd_k_index and in front of that read-back: they read u from
+// d_stats[1] on the device, and what they leave in d_stats[2] and d_stats[3] comes back in the same copy (extra[]).
+struct DedupHook {
+    std::function<int(unsigned long long *d_stats)> queue;
+    unsigned long long extra[2] = {0, 0};
+};
 static int dedup_slice(ssa_ctx *ctx, const uint8_t *d_pks, const uint8_t *d_pk_inf, size_t cnt, uint64_t *u_out,
-                       uint64_t *bound_hits_out) {
+                       uint64_t *bound_hits_out, DedupHook *hook = nullptr) {
     if (int rc = dedup_fingerprint_key(ctx)) return rc;
     const size_t cap = dd_slots_for(cnt), nb = grid_for(cnt, DD_BLOCK);
     if (ctx->dd_slots.reserve(cap * sizeof(u64)) || ctx->dd_rep.reserve(cnt * sizeof(u32)) ||
@@ -1177,7 +1175,7 @@ static int dedup_slice(ssa_ctx *ctx, const uint8_t *d_pks, const uint8_t *d_pk_i
     u32 *blk_cnt = (u32 *)ctx->dd_blk.p, *blk_off = blk_cnt + nb;
     int rc = timed_launch(ctx, "dedup", [&] {
         (void)hipMemsetAsync(ctx->dd_slots.p, 0xff, cap * sizeof(u64), ctx->stream);
-        (void)hipMemsetAsync(d_stats, 0, 2 * sizeof(unsigned long long), ctx->stream);
+        (void)hipMemsetAsync(d_stats, 0, (hook ? 4 : 2) * sizeof(unsigned long long), ctx->stream);
         hipLaunchKernelGGL(dd_k_insert, dim3((unsigned)nb), dim3(DD_BLOCK), 0, ctx->stream, d_pks, d_pk_inf, (u32)cnt,
                            (u64)ctx->dedup_key[0], (u64)ctx->dedup_key[1], (u64 *)ctx->dd_slots.p, (u32)(cap - 1),
                            (u32)ctx->dedup_probe_bound, (u32 *)ctx->dd_rep.p, blk_cnt, d_stats);
@@ -1189,10 +1187,16 @@ static int dedup_slice(ssa_ctx *ctx, const uint8_t *d_pks, const uint8_t *d_pk_i
                            (const u32 *)ctx->dd_num.p, (u32)cnt, (u32 *)ctx->dd_idx.p);
     });
     if (rc) return rc;
-    unsigned long long st[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(st, d_stats, sizeof st, hipMemcpyDeviceToHost, ctx->stream));
+    if (hook)
+        if ((rc = hook->queue(d_stats))) return rc;
+    unsigned long long st[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(st, d_stats, (hook ? 4 : 2) * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     if (st[1] == 0 || st[1] > cnt) return SSA_ERR_HIP;      // (never: every lane has a representative)
+    if (hook) {
+        hook->extra[0] = st[2];
+        hook->extra[1] = st[3];
+    }
     *bound_hits_out = st[0];
     *u_out = st[1];
     return 0;
@@ -1231,9 +1235,16 @@ int ssa_internal_dedup_keys(ssa_ctx *ctx, const uint8_t *d_pks, const uint8_t *d
 int ssa_internal_verify_keyed(ssa_ctx *ctx, const uint8_t *d_sigs, const uint32_t *d_key_idx, uint64_t u,
                               const uint64_t *d_h, size_t n, uint32_t flags, uint8_t *d_status_out,
                               unsigned long long *d_fail) {
+    return ssa_internal_verify_keyed_view(ctx, d_sigs, d_key_idx, ctx_key_view(ctx, u), d_h, n, flags, d_status_out, d_fail);
+}
+
+// the same against keys named by a view: the lanes' key numbers are d_lane_key (the view's own, or a gathered copy)
+int ssa_internal_verify_keyed_view(ssa_ctx *ctx, const uint8_t *d_sigs, const uint32_t *d_lane_key, const KeyView &kv,
+                                   const uint64_t *d_h, size_t n, uint32_t flags, uint8_t *d_status_out,
+                                   unsigned long long *d_fail) {
     return timed_launch(ctx, "ssa_k_verify_keyed", [&] {
-        hipLaunchKernelGGL(ssa_k_verify_keyed, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, d_sigs, d_key_idx,
-                           (const u64 *)ctx->ws_tab.p, (const u8 *)ctx->dd_kstatus.p, (u32)u, (const u64 *)d_h,
+        hipLaunchKernelGGL(ssa_k_verify_keyed, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, d_sigs, d_lane_key,
+                           (const u64 *)kv.tab, (const u8 *)kv.status, (u32)kv.n_keys, (const u64 *)d_h,
                            (const u64 *)ctx->d_gtab, n, flags, d_status_out, d_fail);
     });
 }
@@ -1387,6 +1398,173 @@ extern "C" int ssa_debug_dedup_config(ssa_ctx *ctx, double max_distinct_ratio, u
     ctx->dedup_ratio[0] = max_distinct_ratio < 0 ? DEDUP_RATIO_NO_CHECK : max_distinct_ratio;
     ctx->dedup_ratio[1] = max_distinct_ratio < 0 ? DEDUP_RATIO_CHECK : max_distinct_ratio;
     ctx->dedup_probe_bound = probe_bound ? probe_bound : DEDUP_PROBE_BOUND;
+    return 0;
+}
+
+// ------------------------------------------------------------------ key cache
+extern "C" int ssa_keycache_create(ssa_ctx *ctx, size_t capacity, ssa_keycache **out) {
+    if (out) *out = nullptr;
+    if (!ctx || !out || capacity == 0 || capacity > KC_MAX_CAPACITY) return SSA_ERR_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    constexpr size_t TAB_BYTES = (size_t)(PTAB_ENTRIES * PTAB_ENTRY_U64) * sizeof(u64);
+    ssa_keycache *kc = new ssa_keycache();
+    kc->ctx = ctx;
+    kc->capacity = capacity;
+    kc->n_slots = dd_slots_for(capacity);
+    kc->rows.ctx = ctx;
+    kc->rows.m = capacity;
+    // everything the cache will ever hold, now: no call that uses it allocates for it
+    if (kc->rows.tab.reserve_exact(capacity * TAB_BYTES) || kc->rows.status.reserve_exact(capacity + 16) ||
+        kc->rows.pks.reserve_exact(capacity * 96) || kc->inf.reserve_exact(capacity + 16) ||
+        kc->slots.reserve_exact(kc->n_slots * sizeof(u64)) ||
+        hipMemsetAsync(kc->slots.p, 0xff, kc->n_slots * sizeof(u64), ctx->stream) != hipSuccess ||
+        hipStreamSynchronize(ctx->stream) != hipSuccess) {
+        (void)hipGetLastError();
+        kc->release_all();
+        delete kc;
+        return SSA_ERR_HIP;
+    }
+    ctx->keycaches.push_back(kc);
+    *out = kc;
+    return 0;
+}
+
+extern "C" void ssa_keycache_destroy(ssa_keycache *kc) {
+    if (!kc) return;
+    if (kc->ctx) {
+        (void)hipSetDevice(kc->ctx->device);
+        (void)hipStreamSynchronize(kc->ctx->stream);
+        auto &v = kc->ctx->keycaches;
+        for (size_t i = 0; i < v.size(); i++)
+            if (v[i] == kc) {
+                v.erase(v.begin() + (long)i);
+                break;
+            }
+        kc->release_all();
+    }
+    delete kc;
+}
+
+// every slot empty again, on the context's stream (behind whatever still reads the cache): the rows stay where they are
+// and are handed out again from row 0
+static int keycache_reset(ssa_keycache *kc) {
+    HIP_TRY(hipMemsetAsync(kc->slots.p, 0xff, kc->n_slots * sizeof(u64), kc->ctx->stream));
+    kc->held = 0;
+    kc->clears++;
+    return 0;
+}
+
+extern "C" int ssa_keycache_clear(ssa_keycache *kc) {
+    if (!kc || !kc->ctx) return SSA_ERR_ARG;
+    HIP_TRY(hipSetDevice(kc->ctx->device));
+    return keycache_reset(kc);
+}
+
+extern "C" int ssa_keycache_info(ssa_keycache *kc, uint64_t out[4]) {
+    if (!kc || !kc->ctx || !out) return SSA_ERR_ARG;
+    out[0] = kc->capacity;
+    out[1] = kc->held;
+    out[2] = kc->clears;
+    out[3] = kc->device_bytes();
+    return 0;
+}
+
+extern "C" int ssa_debug_keycache_plan(uint64_t capacity, uint64_t held, uint64_t u, uint64_t m, uint32_t *plan_out) {
+    if (!plan_out || capacity == 0 || capacity > KC_MAX_CAPACITY || held > capacity || m > u || u > SSA_MAX_BATCH)
+        return SSA_ERR_ARG;
+    *plan_out = (uint32_t)kc_plan(capacity, held, u, m);
+    return 0;
+}
+
+// Rows base .. base + m of the cache from the keys of the representative lanes reps[0, m): dd_k_gather and
+// ssa_k_keyset_build as they are, with their outputs offset into the cache, then the slots of the new rows
+static int keycache_insert(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *d_pks, const uint8_t *d_pk_inf, const u32 *reps,
+                           size_t base, size_t m, unsigned long long *d_unpublished) {
+    constexpr size_t TAB_WORDS = (size_t)(PTAB_ENTRIES * PTAB_ENTRY_U64);
+    u64 *c_pks = (u64 *)kc->rows.pks.p;
+    u8 *c_inf = (u8 *)kc->inf.p;
+    int rc = timed_launch(ctx, "keycache_insert", [&] {
+        hipLaunchKernelGGL(dd_k_gather, dim3(grid_for(m * 12, DD_BLOCK)), dim3(DD_BLOCK), 0, ctx->stream, d_pks, d_pk_inf,
+                           reps, (u32)m, c_pks + 12 * base, c_inf + base);
+    });
+    if (rc) return rc;
+    rc = timed_launch(ctx, "ssa_k_keyset_build", [&] {
+        hipLaunchKernelGGL(ssa_k_keyset_build, dim3(grid_for(m, 256)), dim3(256), 0, ctx->stream,
+                           (const u8 *)(c_pks + 12 * base), (const u8 *)(c_inf + base), m,
+                           (u64 *)kc->rows.tab.p + base * TAB_WORDS, (u8 *)kc->rows.status.p + base);
+    });
+    if (rc) return rc;
+    return timed_launch(ctx, "keycache_insert", [&] {
+        hipLaunchKernelGGL(kc_k_publish, dim3(grid_for(m, DD_BLOCK)), dim3(DD_BLOCK), 0, ctx->stream, (const u64 *)c_pks,
+                           (const u8 *)c_inf, (u32)base, (u32)m, (u64)ctx->dedup_key[0], (u64)ctx->dedup_key[1],
+                           (u64 *)kc->slots.p, (u32)(kc->n_slots - 1), (u32)ctx->dedup_probe_bound, d_unpublished);
+    });
+}
+
+int ssa_internal_keycache_slice(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *d_pks, const uint8_t *d_pk_inf, size_t cnt,
+                                KeyView *kv, uint64_t *u_out, uint64_t *bound_hits_out, uint64_t ks[4],
+                                const unsigned long long **d_unpublished) {
+    const size_t nb = grid_for(cnt, DD_BLOCK);
+    if (ctx->kc_found.reserve(cnt * sizeof(u32)) || ctx->kc_missrep.reserve(cnt * sizeof(u32)) ||
+        ctx->kc_blk.reserve(2 * nb * sizeof(u32)) || ctx->kc_lane_row.reserve(cnt * sizeof(u32)))
+        return SSA_ERR_HIP;
+    u32 *found = (u32 *)ctx->kc_found.p, *miss_rep = (u32 *)ctx->kc_missrep.p, *blk_cnt = (u32 *)ctx->kc_blk.p,
+        *blk_off = blk_cnt + nb;
+    const size_t held = kc->held;
+    DedupHook hook;
+    // d_stats: [0] lanes at the probe bound, [1] u, [2] m (dd_k_scan writes its total one word on), [3] unpublished rows
+    hook.queue = [&](unsigned long long *d_stats) {
+        return timed_launch(ctx, "keycache_lookup", [&] {
+            hipLaunchKernelGGL(kc_k_lookup, dim3((unsigned)nb), dim3(DD_BLOCK), 0, ctx->stream, d_pks, d_pk_inf,
+                               (const u32 *)ctx->dd_reps.p, (u32)cnt, (const unsigned long long *)d_stats,
+                               (u64)ctx->dedup_key[0], (u64)ctx->dedup_key[1], (const u64 *)kc->slots.p,
+                               (u32)(kc->n_slots - 1), (u32)ctx->dedup_probe_bound, (const u64 *)kc->rows.pks.p,
+                               (const u8 *)kc->inf.p, (u32)held, found, blk_cnt);
+            hipLaunchKernelGGL(dd_k_scan, dim3(1), dim3(DD_BLOCK), 0, ctx->stream, (const u32 *)blk_cnt, (u32)nb, blk_off,
+                               d_stats + 1);
+            hipLaunchKernelGGL(kc_k_number, dim3((unsigned)nb), dim3(DD_BLOCK), 0, ctx->stream,
+                               (const u32 *)ctx->dd_reps.p, (u32)cnt, (const unsigned long long *)d_stats,
+                               (const u32 *)blk_off, found, miss_rep);
+        });
+    };
+    uint64_t u = 0;
+    if (int rc = dedup_slice(ctx, d_pks, d_pk_inf, cnt, &u, bound_hits_out, &hook)) return rc;
+    const uint64_t m = hook.extra[0];
+    if (m > u) return SSA_ERR_HIP;      // (never)
+    *u_out = u;
+    ks[0] = ks[1] = ks[2] = ks[3] = 0;
+    *d_unpublished = nullptr;
+    const int plan = kc_plan(kc->capacity, held, u, m);
+    if (plan == KC_PLAN_BYPASS) {       // more keys than rows: the slice as ssa_verify_many_screened runs it
+        ks[3] = 1;
+        *kv = ctx_key_view(ctx, u);
+        return dedup_check_keys(ctx, d_pks, d_pk_inf, u);
+    }
+    unsigned long long *d_unpub = (unsigned long long *)ctx->dd_stats.p + 3;
+    size_t base = held, fresh = (size_t)m;
+    const u32 *reps = miss_rep;
+    if (plan == KC_PLAN_CLEAR) {        // every key of the slice is new: key j of the dedup takes row j
+        if (int rc = keycache_reset(kc)) return rc;
+        ks[2] = 1;
+        base = 0;
+        fresh = (size_t)u;
+        reps = (const u32 *)ctx->dd_reps.p;
+    }
+    ks[0] = u - fresh;
+    ks[1] = fresh;
+    if (fresh) {
+        if (int rc = keycache_insert(ctx, kc, d_pks, d_pk_inf, reps, base, fresh, d_unpub)) return rc;
+        kc->held = base + fresh;
+        *d_unpublished = d_unpub;
+    }
+    const int rc = timed_launch(ctx, "keycache_map", [&] {
+        hipLaunchKernelGGL(kc_k_map, dim3((unsigned)nb), dim3(DD_BLOCK), 0, ctx->stream, (const u32 *)ctx->dd_idx.p,
+                           (const u32 *)found, (u32)cnt, (u32)base, plan == KC_PLAN_CLEAR ? 1u : 0u,
+                           (u32 *)ctx->kc_lane_row.p);
+    });
+    if (rc) return rc;
+    *kv = {(const uint32_t *)ctx->kc_lane_row.p, (const uint64_t *)kc->rows.tab.p, (const uint8_t *)kc->rows.status.p,
+           (uint32_t)kc->capacity};
     return 0;
 }
 

@@ -48,6 +48,17 @@ struct DevBuf {
         cap = want;
         return 0;
     }
+    // exactly `bytes` (rounded up to 256), for a buffer whose final size is known when it is made: no room to grow into
+    int reserve_exact(size_t bytes) {
+        release();
+        const size_t want = (bytes + 255) & ~(size_t)255;
+        if (hipMalloc(&p, want) != hipSuccess) {
+            p = nullptr;
+            return SSA_ERR_HIP;
+        }
+        cap = want;
+        return 0;
+    }
     void release() {
         if (p) (void)hipFree(p);
         p = nullptr;
@@ -152,6 +163,9 @@ struct ssa_ctx {
     unsigned dedup_probe_bound = DEDUP_PROBE_BOUND;
     uint64_t dedup_key[2] = {0, 0};   // the fingerprint's key: getrandom(2) at the first use
     bool dedup_key_set = false;
+    // key cache (ssa_keycache.hpp): per distinct key of the slice its cache row or miss number, the
+    // misses' representative lanes, per-workgroup counts and offsets of the misses, and a cache row per lane
+    DevBuf kc_found, kc_missrep, kc_blk, kc_lane_row;
     // signing (ssa_sign.hip): the 4-bit comb table of the constant-time signer (98 KB, built at the first use) and the
     // intermediates of the keyed (130-byte) output
     DevBuf ctab, sg_sigs, sg_pks;
@@ -181,6 +195,7 @@ struct ssa_ctx {
     std::map<std::string, std::vector<TimedLaunch>> timed;
     std::vector<struct ssa_keyset *> keysets;   // live key sets of this context (orphaned, not leaked, by ssa_ctx_destroy)
     std::vector<struct ssa_signer_set *> signer_sets;   // live signer sets (ssa_sign.hip), orphaned the same way
+    std::vector<struct ssa_keycache *> keycaches;       // live key caches, orphaned the same way
 };
 
 // every DevBuf of a context, once: ssa_ctx_destroy releases them, ssa_ctx_info sums their capacities
@@ -193,10 +208,42 @@ static inline void for_each_devbuf(Ctx *c, F &&f) {
                     &c->msm_ids, &c->msm_ids2, &c->msm_comb_pts, &c->msm_comb_lins, &c->msm_slice_recs, &c->msm_sbuf,
                     &c->scr_ok, &c->scr_in, &c->scr_status, &c->scr_fail, &c->scr_mask, &c->scr_mark,
                     &c->scr_list, &c->scr_blk, &c->scr_cnt, &c->dd_slots, &c->dd_rep, &c->dd_num, &c->dd_reps,
-                    &c->dd_idx, &c->dd_blk, &c->dd_stats, &c->dd_pks, &c->dd_inf, &c->dd_kstatus, &c->ctab, &c->sg_sigs,
-                    &c->sg_pks, &c->tc_out, &c->dv_recs, &c->rng_seed, &c->rng_scratch, &c->tail_done, &c->tail_park})
+                    &c->dd_idx, &c->dd_blk, &c->dd_stats, &c->dd_pks, &c->dd_inf, &c->dd_kstatus, &c->kc_found,
+                    &c->kc_missrep, &c->kc_blk, &c->kc_lane_row, &c->ctab, &c->sg_sigs, &c->sg_pks, &c->tc_out, &c->dv_recs, &c->rng_seed, &c->rng_scratch, &c->tail_done, &c->tail_park})
         f(*b);
 }
+
+// keyed context (entry points in ssa_api.hip; ssa_ctx_destroy orphans the key sets that outlive their context)
+struct ssa_keyset {
+    ssa_ctx *ctx = nullptr;   // nullptr: the context is gone, the device memory went with it
+    size_t m = 0;
+    bool comb = false;      // per-key comb tables (16 x 65536 rows = 100 MB per key) instead of the ladder's 16 multiples
+    DevBuf tab, status, pks, ktab;
+    void release_all() {
+        tab.release();
+        status.release();
+        pks.release();
+        ktab.release();
+    }
+};
+
+// key cache (entry points in ssa_api.hip and ssa_msm.hip): a ladder-kind key set of `capacity` rows
+// that fills itself (rows.tab, rows.status, rows.pks: rows [0, held) are complete), the pk_inf boolean of each row, and
+// the slot table over the rows (ssa_keycache.hpp).  The host knows `held`: rows are handed out in order and never freed
+// but by a clear of the whole cache.
+struct ssa_keycache {
+    ssa_ctx *ctx = nullptr;   // nullptr: the context is gone, the device memory went with it
+    size_t capacity = 0, held = 0, n_slots = 0;
+    uint64_t clears = 0;
+    ssa_keyset rows;          // never registered with the context: owned by the cache
+    DevBuf inf, slots;
+    uint64_t device_bytes() const { return rows.tab.cap + rows.status.cap + rows.pks.cap + inf.cap + slots.cap; }
+    void release_all() {
+        rows.release_all();
+        inf.release();
+        slots.release();
+    }
+};
 
 // signer set (the signing twin of ssa_keyset; entry points in ssa_sign.hip): m key pairs resident on the device
 struct ssa_signer_set {
@@ -610,6 +657,32 @@ int ssa_internal_dedup_keys(ssa_ctx *ctx, const uint8_t *d_pks, const uint8_t *d
 int ssa_internal_verify_keyed(ssa_ctx *ctx, const uint8_t *d_sigs, const uint32_t *d_key_idx, uint64_t u,
                               const uint64_t *d_h, size_t n, uint32_t flags, uint8_t *d_status_out,
                               unsigned long long *d_fail);
+
+// where the checked keys of a slice are: a key number per lane, the keys' tables of sixteen multiples and status bytes,
+// and the bound of the key numbers.  The context's own (ssa_internal_dedup_keys) or rows of a key cache.
+struct KeyView {
+    const uint32_t *lane_key;
+    const uint64_t *tab;
+    const uint8_t *status;
+    uint32_t n_keys;
+};
+// the view ssa_internal_dedup_keys leaves: ctx->dd_idx, ctx->ws_tab, ctx->dd_kstatus
+static inline KeyView ctx_key_view(const ssa_ctx *ctx, uint64_t u) {
+    return {(const uint32_t *)ctx->dd_idx.p, (const uint64_t *)ctx->ws_tab.p, (const uint8_t *)ctx->dd_kstatus.p, (uint32_t)u};
+}
+// ssa_internal_verify_keyed with explicit pointers
+int ssa_internal_verify_keyed_view(ssa_ctx *ctx, const uint8_t *d_sigs, const uint32_t *d_lane_key, const KeyView &kv,
+                                   const uint64_t *d_h, size_t n, uint32_t flags, uint8_t *d_status_out,
+                                   unsigned long long *d_fail);
+
+// defined in ssa_api.hip, for ssa_verify_many_cached (ssa_msm.hip): the distinct keys of one slice looked up in the cache
+// and the unseen ones checked and inserted (or the cache cleared, or bypassed: ssa_keycache.hpp).
+// One synchronisation, the one of the dedup.  *kv is where the slice's keys are; ks[0] keys found, ks[1] keys inserted,
+// ks[2] automatic clears, ks[3] 1 when the slice bypassed the cache; *d_unpublished (device, read it behind the slice's
+// later launches) counts rows that found no slot, or is nullptr.
+int ssa_internal_keycache_slice(ssa_ctx *ctx, struct ssa_keycache *kc, const uint8_t *d_pks, const uint8_t *d_pk_inf,
+                                size_t cnt, KeyView *kv, uint64_t *u_out, uint64_t *bound_hits_out, uint64_t ks[4],
+                                const unsigned long long **d_unpublished);
 
 // defined in ssa_sign.hip (ssa_selfcheck.hpp): the exact check of a comb table for G (res[0] failing rows, res[1] the
 // first failing row or ~0) and of the context's constant-time table (out[0] rows checked, out[1], out[2] as res)

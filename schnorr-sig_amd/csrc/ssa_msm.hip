@@ -1897,21 +1897,24 @@ extern "C" int ssa_verify_batch_screened(ssa_ctx *ctx, const uint8_t *sigs, cons
 constexpr uint32_t MANY_SCREEN_FLAGS = SSA_FLAG_CHECK_TORSION | SSA_FLAG_SIG_FLAG_BYTE;
 
 // what the entry points report (the host form's two threads add to it under the lock)
+// (words 8..11 are the key cache's: ssa_verify_many_cached)
 struct ManyScreenStats {
     std::mutex mu;
-    uint64_t v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    void add(const uint64_t d[8]) {
+    uint64_t v[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    void add(const uint64_t d[12]) {
         std::lock_guard<std::mutex> lock(mu);
-        for (int k = 0; k < 8; k++) v[k] += d[k];
+        for (int k = 0; k < 12; k++) v[k] += d[k];
     }
 };
 
 // ONE slice (n <= ctx->lane_slice) on ctx->stream into d_status[0, n): d_h = the slice's challenge scalars if they exist
 // (else they are computed into ctx->ws_h).  Synchronises the stream twice: for u, and for the segment verdicts together
-// with the length of the re-check list.
+// with the length of the re-check list.  With a key cache (ssa_verify_many_cached) the keys are
+// looked up there and only the unseen ones are checked; everything behind the key check is the same code.
 static int screen_many_slice(ssa_ctx *ctx, const DevBatch &b, size_t n, const uint8_t *d_coeffs, uint32_t coeff_bytes,
-                             uint32_t flags, const u64 *d_h, uint8_t *d_status, ManyScreenStats *stats) {
-    uint64_t sv[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+                             uint32_t flags, const u64 *d_h, uint8_t *d_status, ManyScreenStats *stats,
+                             ssa_keycache *kc = nullptr) {
+    uint64_t sv[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     if (ctx->scr_fail.reserve(16)) return SSA_ERR_HIP;
     unsigned long long *scratch_fail = (unsigned long long *)ctx->scr_fail.p;    // (the caller counts the statuses)
     if (n <= ctx->msm_small_max) {      // the exact per-lane path, the caller's flags
@@ -1923,18 +1926,25 @@ static int screen_many_slice(ssa_ctx *ctx, const DevBatch &b, size_t n, const ui
         return rc;
     }
     uint64_t u = 0, hits = 0;
-    if (int rc = ssa_internal_dedup_keys(ctx, b.pks, b.pk_inf, n, &u, &hits)) return rc;
+    KeyView kv{};
+    const unsigned long long *d_unpublished = nullptr;     // rows of the cache that found no slot (read with the verdicts)
+    if (kc) {
+        if (int rc = ssa_internal_keycache_slice(ctx, kc, b.pks, b.pk_inf, n, &kv, &u, &hits, sv + 8, &d_unpublished)) return rc;
+    } else {
+        if (int rc = ssa_internal_dedup_keys(ctx, b.pks, b.pk_inf, n, &u, &hits)) return rc;
+        kv = ctx_key_view(ctx, u);
+    }
     const unsigned nb = grid_for(n, SCR_BLOCK);
     if (ctx->scr_mask.reserve(n + 16) || ctx->scr_mark.reserve(n + 16) || ctx->scr_list.reserve(n * sizeof(u32)) ||
         ctx->scr_blk.reserve(2 * (size_t)nb * sizeof(u32)) || ctx->scr_cnt.reserve(64) || ctx->scr_ok.reserve(SCREEN_MAX_SEGS))
         return SSA_ERR_HIP;
-    const u32 *key_idx = (const u32 *)ctx->dd_idx.p;
+    const u32 *key_idx = kv.lane_key;
     u8 *mark = (u8 *)ctx->scr_mark.p;
     u32 *blk_cnt = (u32 *)ctx->scr_blk.p, *blk_off = blk_cnt + nb, *list = (u32 *)ctx->scr_list.p;
     unsigned long long *d_cnt = (unsigned long long *)ctx->scr_cnt.p;
     int rc = timed_launch(ctx, "screen_keymask", [&] {
         hipLaunchKernelGGL(msm_k_screen_keymask, dim3(nb), dim3(SCR_BLOCK), 0, ctx->stream, key_idx,
-                           (const u8 *)ctx->dd_kstatus.p, (u32)u, (u32)n, (u8 *)ctx->scr_mask.p);
+                           kv.status, kv.n_keys, (u32)n, (u8 *)ctx->scr_mask.p);
     });
     if (rc) return rc;
     // (the side stream of msm_run_one waits for everything queued on ctx->stream so far: the key check and the mask are
@@ -1954,9 +1964,11 @@ static int screen_many_slice(ssa_ctx *ctx, const DevBatch &b, size_t n, const ui
     });
     if (rc) return rc;
     uint8_t ok[SCREEN_MAX_SEGS];
-    unsigned long long cnt[2] = {0, 0};
+    unsigned long long cnt[2] = {0, 0}, unpublished = 0;
     HIP_TRY(hipMemcpyAsync(ok, ctx->scr_ok.p, pl.segs, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipMemcpyAsync(cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, ctx->stream));
+    if (d_unpublished)
+        HIP_TRY(hipMemcpyAsync(&unpublished, d_unpublished, sizeof unpublished, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     const size_t m = (size_t)cnt[1];
     if (m > n || cnt[0] > m) return SSA_ERR_HIP;     // (never)
@@ -1966,14 +1978,14 @@ static int screen_many_slice(ssa_ctx *ctx, const DevBatch &b, size_t n, const ui
     sv[3] = m;
     sv[4] = cnt[0];
     sv[5] = 1;
-    sv[7] = hits;
+    sv[7] = hits + unpublished;
     if (m == 0) {
         if (stats) stats->add(sv);
         return 0;
     }
     if (2 * m > n) {     // most of the slice: no list, the keyed kernel over all of it in place
         sv[6] = 1;
-        rc = ssa_internal_verify_keyed(ctx, b.sigs, key_idx, u, h, n, flags, d_status, scratch_fail);
+        rc = ssa_internal_verify_keyed_view(ctx, b.sigs, key_idx, kv, h, n, flags, d_status, scratch_fail);
         if (rc == 0 && stats) stats->add(sv);
         return rc;
     }
@@ -1988,8 +2000,8 @@ static int screen_many_slice(ssa_ctx *ctx, const DevBatch &b, size_t n, const ui
                            (const u32 *)list, (u32)m, b.sigs, h, key_idx, g, (u64 *)(g + o_h), (u32 *)(g + o_idx));
     });
     if (rc) return rc;
-    if ((rc = ssa_internal_verify_keyed(ctx, g, (const u32 *)(g + o_idx), u, (const u64 *)(g + o_h), m, flags,
-                                        (u8 *)ctx->scr_status.p, scratch_fail)))
+    if ((rc = ssa_internal_verify_keyed_view(ctx, g, (const u32 *)(g + o_idx), kv, (const u64 *)(g + o_h), m, flags,
+                                             (u8 *)ctx->scr_status.p, scratch_fail)))
         return rc;
     rc = timed_launch(ctx, "screen_list_scatter", [&] {
         hipLaunchKernelGGL(msm_k_screen_scatter_list, dim3(grid_for(m, 256)), dim3(256), 0, ctx->stream, (const u32 *)list,
@@ -2049,7 +2061,7 @@ extern "C" int ssa_verify_many_screened_device(ssa_ctx *ctx, const uint8_t *d_si
 
 // ONE slice from host buffers (the staging of screen_host_one): statuses into status_out[0, n), *nf the count
 static int screen_many_host_one(ssa_ctx *ctx, const HostBatch &b, size_t n, uint32_t flags, const uint8_t *coeffs,
-                                uint8_t *status_out, uint64_t *nf, ManyScreenStats *stats) {
+                                uint8_t *status_out, uint64_t *nf, ManyScreenStats *stats, ssa_keycache *kc = nullptr) {
     HostCall hc(ctx);
     PipelinedInputs pin;      // its destructor drains the side streams on every error return
     const StagedInputs s = slice_inputs(hc, pin, b, n, coeffs, true, false);
@@ -2058,7 +2070,7 @@ static int screen_many_host_one(ssa_ctx *ctx, const HostBatch &b, size_t n, uint
     hc.copy_back(&v, d_fail, sizeof v);
     if (int rc = hc.finish([&] {
             if (int r = screen_many_slice(ctx, s.batch, n, s.coeffs, 32, flags,
-                                          s.hashed ? (const u64 *)ctx->ws_h.p : nullptr, d_status, stats))
+                                          s.hashed ? (const u64 *)ctx->ws_h.p : nullptr, d_status, stats, kc))
                 return r;
             return screen_count(ctx, d_status, n, d_fail);
         }))
@@ -2098,5 +2110,91 @@ extern "C" int ssa_verify_many_screened(ssa_ctx *ctx, const uint8_t *sigs, const
                                            });
     if (rc) return rc;
     many_screen_stats_out(st, stats_out);
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// ssa_verify_many_cached: ssa_verify_many_screened with its per-key check behind a key cache.
+// The slices of one call run in order on the context's stream in BOTH forms: every slice reads and may extend the one
+// cache, so the host form does not alternate its slices between the context and a second set of streams.
+static void many_cached_stats_out(const ManyScreenStats &st, uint64_t stats_out[12]) {
+    if (stats_out)
+        for (int k = 0; k < 12; k++) stats_out[k] = st.v[k];
+}
+
+extern "C" int ssa_verify_many_cached_device(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *d_sigs, const uint8_t *d_pks,
+                                             const uint8_t *d_pk_inf, const uint8_t *d_msgs, const uint64_t *d_msg_off,
+                                             size_t msg_stride, size_t msg_len, size_t n, uint32_t flags,
+                                             const uint8_t *d_coeffs, uint32_t coeff_bytes, uint8_t *d_status_out,
+                                             uint64_t *d_n_fail_out, uint64_t stats_out[12]) {
+    if (flags & ~MANY_SCREEN_FLAGS) return SSA_ERR_ARG;
+    const DevBatch b{d_sigs, d_pks, d_pk_inf, {d_msgs, d_msg_off, msg_stride, msg_len}};
+    if (!ctx || !kc || kc->ctx != ctx || (n && (!d_sigs || !d_pks || !d_status_out))) return SSA_ERR_ARG;
+    if (d_coeffs && (coeff_bytes == 0 || coeff_bytes > 32)) return SSA_ERR_ARG;
+    if (int rc = check_msgs(b.msgs, n)) return rc;
+    if (stats_out) std::memset(stats_out, 0, 12 * sizeof(uint64_t));
+    if (flags == SSA_FLAG_SIG_FLAG_BYTE)      // verify_batch semantics: no key check, so nothing to cache
+        return ssa_verify_batch_screened_device(ctx, d_sigs, d_pks, d_pk_inf, d_msgs, d_msg_off, msg_stride, msg_len, n,
+                                                d_coeffs, coeff_bytes, d_status_out, d_n_fail_out);
+    HIP_TRY(hipSetDevice(ctx->device));
+    unsigned long long *d_fail;
+    if (int rc = reset_fail_counter(ctx, d_n_fail_out, &d_fail)) return rc;
+    if (n == 0) return 0;
+    if (n <= ctx->msm_small_max) {
+        const int rc = ssa_verify_many_device(ctx, d_sigs, d_pks, d_pk_inf, d_msgs, d_msg_off, msg_stride, msg_len, n, flags,
+                                              d_status_out, (uint64_t *)d_fail);
+        if (rc == 0 && stats_out) stats_out[6] = 1;
+        return rc;
+    }
+    ManyScreenStats st;
+    const size_t slice = many_screen_slice_lanes(ctx);
+    for (size_t lo = 0; lo < n; lo += slice) {
+        const size_t cnt = n - lo < slice ? n - lo : slice;
+        if (int rc = screen_many_slice(ctx, b.slice(lo), cnt, d_coeffs ? d_coeffs + (size_t)coeff_bytes * lo : nullptr,
+                                       coeff_bytes, flags, nullptr, d_status_out + lo, stats_out ? &st : nullptr, kc))
+            return rc;
+    }
+    if (int rc = screen_count(ctx, d_status_out, n, d_fail)) return rc;
+    many_cached_stats_out(st, stats_out);
+    return 0;
+}
+
+extern "C" int ssa_verify_many_cached(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *sigs, const uint8_t *pks,
+                                      const uint8_t *pk_inf, const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride,
+                                      size_t msg_len, size_t n, uint32_t flags, const uint8_t *coeffs, uint8_t *status_out,
+                                      uint64_t *n_fail_out, uint64_t stats_out[12]) {
+    if (flags & ~MANY_SCREEN_FLAGS) return SSA_ERR_ARG;
+    if (!ctx || !kc || kc->ctx != ctx || (n && (!sigs || !pks || !status_out))) return SSA_ERR_ARG;
+    if (int rc = check_msgs({msgs, msg_off, msg_stride, msg_len}, n)) return rc;
+    if (int rc = check_host_offsets(msg_off, n)) return rc;
+    if (stats_out) std::memset(stats_out, 0, 12 * sizeof(uint64_t));
+    if (flags == SSA_FLAG_SIG_FLAG_BYTE)
+        return ssa_verify_batch_screened(ctx, sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len, n, coeffs, status_out,
+                                         n_fail_out);
+    if (n_fail_out) *n_fail_out = 0;
+    if (n == 0) return 0;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (n <= ctx->msm_small_max) {
+        const int rc = ssa_verify_many(ctx, sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len, n, flags, status_out,
+                                       n_fail_out);
+        if (rc == 0 && stats_out) stats_out[6] = 1;
+        return rc;
+    }
+    const HostBatch b{sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len};
+    ManyScreenStats st;
+    // slice after slice on this context alone: two streams would mutate one cache
+    const size_t slice = many_screen_slice_lanes(ctx);
+    uint64_t total = 0;
+    for (size_t lo = 0; lo < n; lo += slice) {
+        const size_t cnt = n - lo < slice ? n - lo : slice;
+        std::vector<uint64_t> off;
+        uint64_t nf = 0;
+        if (int rc = screen_many_host_one(ctx, b.slice(lo, cnt, off), cnt, flags, coeffs ? coeffs + 32 * lo : nullptr,
+                                          status_out + lo, &nf, stats_out ? &st : nullptr, kc))
+            return rc;
+        total += nf;
+    }
+    if (n_fail_out) *n_fail_out = total;
+    many_cached_stats_out(st, stats_out);
     return 0;
 }

@@ -657,6 +657,57 @@ inline std::vector<uint8_t> verify_many_screened_statuses(Context &cx, const std
     return status;
 }
 
+// A key cache on the device (ssa_keycache_create): the checks and tables of the public keys that
+// verify_many_cached_statuses has seen, kept across slices and calls.  Belongs to the context it was made on.
+class KeyCache {
+  public:
+    struct Info {
+        uint64_t capacity, held, clears, device_bytes;
+    };
+    KeyCache(Context &cx, size_t capacity) {
+        const int rc = ssa_keycache_create(cx.get(), capacity, &kc_);
+        if (rc != 0) throw std::runtime_error(std::string("ssa_keycache_create: ") + ssa_strerror(rc));
+    }
+    ~KeyCache() { ssa_keycache_destroy(kc_); }
+    KeyCache(const KeyCache &) = delete;
+    KeyCache &operator=(const KeyCache &) = delete;
+    ssa_keycache *get() const { return kc_; }
+    void clear() {
+        const int rc = ssa_keycache_clear(kc_);
+        if (rc != 0) throw std::runtime_error(std::string("ssa_keycache_clear: ") + ssa_strerror(rc));
+    }
+    Info info() const {
+        uint64_t v[4] = {0, 0, 0, 0};
+        const int rc = ssa_keycache_info(kc_, v);
+        if (rc != 0) throw std::runtime_error(std::string("ssa_keycache_info: ") + ssa_strerror(rc));
+        return {v[0], v[1], v[2], v[3]};
+    }
+
+  private:
+    ssa_keycache *kc_ = nullptr;
+};
+
+// verify_many_screened_statuses with each public key's check done once per cache, not once per slice: byte for byte the
+// same vector for the same coefficients, whatever the cache holds.  stats_out: 12 words, optional.
+inline std::vector<uint8_t> verify_many_cached_statuses(Context &cx, KeyCache &cache, const std::vector<Signature> &signatures,
+                                                        const std::vector<PublicKey> &public_keys,
+                                                        const std::vector<std::pair<const uint8_t *, size_t>> &messages,
+                                                        Rng rng = nullptr, uint64_t *stats_out = nullptr) {
+    const PackedTriples t = pack_triples(signatures, public_keys, messages);
+    const size_t n = signatures.size();
+    std::vector<uint8_t> status(n, 0), coeffs;
+    if (n == 0) return status;
+    if (rng) {
+        coeffs.resize(n * SCALAR_LENGTH);
+        for (size_t i = 0; i < n; i++) KeyPair::random_scalar(rng, &coeffs[i * SCALAR_LENGTH]);
+    }
+    const int rc = ssa_verify_many_cached(cx.get(), cache.get(), t.sigs.data(), t.pks.data(), t.inf.data(), t.flat.data(),
+                                          t.off.data(), 0, 0, n, SSA_FLAG_CHECK_TORSION, rng ? coeffs.data() : nullptr,
+                                          status.data(), nullptr, stats_out);
+    if (rc != 0) throw std::runtime_error(std::string("ssa_verify_many_cached: ") + ssa_strerror(rc));
+    return status;
+}
+
 // ---- hierarchical deterministic key derivation (src/derivation.rs) ---------------------------------------------------
 constexpr size_t CHAIN_CODE_LENGTH = SSA_CHAIN_CODE_LENGTH, EXTENDED_PRIVATE_KEY_LENGTH = SSA_EXTENDED_PRIVATE_KEY_LENGTH,
                  EXTENDED_PUBLIC_KEY_LENGTH = SSA_EXTENDED_PUBLIC_KEY_LENGTH;
