@@ -340,22 +340,42 @@ class Engine:
         assert m.ndim == 2 and m.shape[0] == n, "dense messages must be an (n, len) array"
         return m, None, m.shape[1], m.shape[1]
 
+    def _host_batch(self, sigs, pks, msgs, offsets, pk_inf, coeffs=None):
+        """a batch in host memory as the verification entry points take it -> (n, the arguments from sigs to n in the
+        order of the ABI, the pointer to the n x 32-byte coefficients or None, the arrays all of these point into: hold
+        them until the call has returned).  An empty batch passes no signatures, keys or messages."""
+        sigs, pks = _np_u8(sigs, 81), _np_u8(pks, 96)
+        n = sigs.shape[0]
+        if pks.shape[0] != n:
+            raise MalformedInput("We should have the same number of signatures than public keys")
+        m, off, stride, mlen = self._msg_args(msgs, offsets, n) if n else (None, None, 0, 0)
+        inf = _np_u8(pk_inf) if pk_inf is not None else None
+        c = _np_u8(coeffs, 32) if coeffs is not None else None
+        assert c is None or c.shape[0] == n
+        batch = (_ptr(sigs) if n else None, _ptr(pks) if n else None, _ptr(inf), _ptr(m), _ptr(off), stride, mlen, n)
+        return n, batch, _ptr(c), (sigs, pks, m, off, inf, c)
+
+    @staticmethod
+    def _dev_batch(d_pk_inf, d_msgs, d_offsets, msg_stride, msg_len, n):
+        """the arguments from pk_inf to n of a device form: 0 stands for no flags / no offset table, msg_stride None for
+        dense rows of msg_len bytes"""
+        return d_pk_inf or None, d_msgs, d_offsets or None, msg_stride if msg_stride is not None else msg_len, msg_len, n
+
+    @staticmethod
+    def _verify_flags(check_torsion, sig_flag_byte, mode=None):
+        return (FLAG_CHECK_TORSION if check_torsion else 0) | _MODE_FLAGS[mode] | \
+            (FLAG_SIG_FLAG_BYTE if sig_flag_byte else 0)
+
     def verify_many(self, sigs, pks, msgs, offsets=None, check_torsion=True, pk_inf=None, mode=None,
                     sig_flag_byte=False):
         """n x Signature::verify -> (status uint8[n], n_fail).  mode: None/"auto" (wave-per-signature
         kernel for small batches, lane-per-signature kernels for large ones), "lane" or "coop".
         sig_flag_byte: honour byte 48 of the signature as verify_batch does (src/batch.rs:104)."""
-        sigs, pks = _np_u8(sigs, 81), _np_u8(pks, 96)
-        n = sigs.shape[0]
-        assert pks.shape[0] == n
-        m, off, stride, mlen = self._msg_args(msgs, offsets, n)
-        inf = _np_u8(pk_inf) if pk_inf is not None else None
+        n, batch, _, keep = self._host_batch(sigs, pks, msgs, offsets, pk_inf)
         status = np.full(n, 255, dtype=np.uint8)
         nfail = C.c_uint64(0)
-        flags = (FLAG_CHECK_TORSION if check_torsion else 0) | _MODE_FLAGS[mode] | \
-            (FLAG_SIG_FLAG_BYTE if sig_flag_byte else 0)
-        _check(_lib.ssa_verify_many(self._ctx, _ptr(sigs), _ptr(pks), _ptr(inf), _ptr(m), _ptr(off), stride,
-                                    mlen, n, flags, _ptr(status), C.byref(nfail)), "ssa_verify_many")
+        _check(_lib.ssa_verify_many(self._ctx, *batch, self._verify_flags(check_torsion, sig_flag_byte, mode),
+                                    _ptr(status) if n else None, C.byref(nfail)), "ssa_verify_many")
         return status, int(nfail.value)
 
     def verify_many_dedup(self, sigs, pks, msgs, offsets=None, check_torsion=True, pk_inf=None, mode=None,
@@ -363,18 +383,12 @@ class Engine:
         """verify_many with each distinct public key of a slice checked once on the GPU ->
         (status uint8[n], n_fail, stats uint64[4]); status and n_fail are those of verify_many.  stats: distinct keys
         summed over slices, slices on the keyed route, slices that fell back, lanes that hit the probe bound."""
-        sigs, pks = _np_u8(sigs, 81), _np_u8(pks, 96)
-        n = sigs.shape[0]
-        assert pks.shape[0] == n
-        m, off, stride, mlen = self._msg_args(msgs, offsets, n)
-        inf = _np_u8(pk_inf) if pk_inf is not None else None
+        n, batch, _, keep = self._host_batch(sigs, pks, msgs, offsets, pk_inf)
         status = np.full(n, 255, dtype=np.uint8)
         nfail = C.c_uint64(0)
         stats = np.zeros(4, dtype=np.uint64)
-        flags = (FLAG_CHECK_TORSION if check_torsion else 0) | _MODE_FLAGS[mode] | \
-            (FLAG_SIG_FLAG_BYTE if sig_flag_byte else 0)
-        _check(_lib.ssa_verify_many_dedup(self._ctx, _ptr(sigs), _ptr(pks), _ptr(inf), _ptr(m), _ptr(off), stride,
-                                          mlen, n, flags, _ptr(status), C.byref(nfail), stats.ctypes.data),
+        _check(_lib.ssa_verify_many_dedup(self._ctx, *batch, self._verify_flags(check_torsion, sig_flag_byte, mode),
+                                          _ptr(status) if n else None, C.byref(nfail), stats.ctypes.data),
                "ssa_verify_many_dedup")
         return status, int(nfail.value), stats
 
@@ -382,13 +396,11 @@ class Engine:
                                  d_offsets=0, d_pk_inf=0, check_torsion=False, mode=None, sig_flag_byte=False):
         """device form of verify_many_dedup (synchronises the stream once per slice to read the number of distinct keys);
         returns the statistics (uint64[4], host)"""
-        flags = (FLAG_CHECK_TORSION if check_torsion else 0) | _MODE_FLAGS[mode] | \
-            (FLAG_SIG_FLAG_BYTE if sig_flag_byte else 0)
         stats = np.zeros(4, dtype=np.uint64)
-        _check(_lib.ssa_verify_many_dedup_device(self._ctx, d_sigs, d_pks, d_pk_inf or None, d_msgs, d_offsets or None,
-                                                 msg_stride if msg_stride is not None else msg_len, msg_len, n, flags,
-                                                 d_status, d_nfail or None, stats.ctypes.data),
-               "ssa_verify_many_dedup_device")
+        _check(_lib.ssa_verify_many_dedup_device(
+            self._ctx, d_sigs, d_pks, *self._dev_batch(d_pk_inf, d_msgs, d_offsets, msg_stride, msg_len, n),
+            self._verify_flags(check_torsion, sig_flag_byte, mode), d_status, d_nfail or None, stats.ctypes.data),
+            "ssa_verify_many_dedup_device")
         return stats
 
     def debug_dedup_device(self, d_pks, n, d_key_idx=0, d_pk_inf=0):
@@ -407,54 +419,29 @@ class Engine:
                "ssa_debug_dedup_config")
 
     def verify_batch_status(self, sigs, pks, msgs, offsets=None, check_torsion=False, pk_inf=None):
-        sigs, pks = _np_u8(sigs, 81), _np_u8(pks, 96)
-        n = sigs.shape[0]
-        if pks.shape[0] != n:
-            raise MalformedInput("We should have the same number of signatures than public keys")
-        m, off, stride, mlen = self._msg_args(msgs, offsets, n)
-        inf = _np_u8(pk_inf) if pk_inf is not None else None
-        return _check(_lib.ssa_verify_batch(self._ctx, _ptr(sigs), _ptr(pks), _ptr(inf), _ptr(m), _ptr(off), stride,
-                                            mlen, n, FLAG_CHECK_TORSION if check_torsion else 0), "ssa_verify_batch")
+        n, batch, _, keep = self._host_batch(sigs, pks, msgs, offsets, pk_inf)
+        return _check(_lib.ssa_verify_batch(self._ctx, *batch, FLAG_CHECK_TORSION if check_torsion else 0),
+                      "ssa_verify_batch")
 
     def verify_batch_msm(self, sigs, pks, msgs, offsets=None, coeffs=None, pk_inf=None):
         """verify_batch as the reference runs it (random linear combination + MSM); one status."""
-        sigs, pks = _np_u8(sigs, 81), _np_u8(pks, 96)
-        n = sigs.shape[0]
-        if pks.shape[0] != n:
-            raise MalformedInput("We should have the same number of signatures than public keys")
-        m, off, stride, mlen = self._msg_args(msgs, offsets, n)
-        c = _np_u8(coeffs, 32) if coeffs is not None else None
-        inf = _np_u8(pk_inf) if pk_inf is not None else None
-        return _check(_lib.ssa_verify_batch_msm(self._ctx, _ptr(sigs), _ptr(pks), _ptr(inf), _ptr(m), _ptr(off),
-                                                stride, mlen, n, _ptr(c)), "ssa_verify_batch_msm")
+        n, batch, c, keep = self._host_batch(sigs, pks, msgs, offsets, pk_inf, coeffs)
+        return _check(_lib.ssa_verify_batch_msm(self._ctx, *batch, c), "ssa_verify_batch_msm")
 
     def verify_batch_msm_device(self, d_sigs, d_pks, d_msgs, n, msg_len, d_coeffs, coeff_bytes, d_verdict,
                                 msg_stride=None, d_offsets=0, d_pk_inf=0):
-        _check(_lib.ssa_verify_batch_msm_device(self._ctx, d_sigs, d_pks, d_pk_inf or None, d_msgs, d_offsets or None,
-                                                msg_stride if msg_stride is not None else msg_len, msg_len, n,
-                                                d_coeffs, coeff_bytes, d_verdict), "ssa_verify_batch_msm_device")
+        _check(_lib.ssa_verify_batch_msm_device(
+            self._ctx, d_sigs, d_pks, *self._dev_batch(d_pk_inf, d_msgs, d_offsets, msg_stride, msg_len, n), d_coeffs,
+            coeff_bytes, d_verdict), "ssa_verify_batch_msm_device")
 
     def verify_batch_screened(self, sigs, pks, msgs, offsets=None, coeffs=None, pk_inf=None):
         """verify_batch semantics per signature at about the price of the MSM verdict -> (status uint8[n], n_fail).
         Segments of the batch are screened by the MSM; only lanes of failing segments run the per-lane check
         (include/schnorr_sig_amd.h).  coeffs: n x 32-byte scalars, or None (drawn on the device)."""
-        sigs, pks = _np_u8(sigs, 81), _np_u8(pks, 96)
-        n = sigs.shape[0]
-        if pks.shape[0] != n:
-            raise MalformedInput("We should have the same number of signatures than public keys")
-        if n:
-            m, off, stride, mlen = self._msg_args(msgs, offsets, n)
-        else:
-            m, off, stride, mlen = None, None, 0, 0
-        c = _np_u8(coeffs, 32) if coeffs is not None else None
-        if c is not None:
-            assert c.shape[0] == n
-        inf = _np_u8(pk_inf) if pk_inf is not None else None
+        n, batch, c, keep = self._host_batch(sigs, pks, msgs, offsets, pk_inf, coeffs)
         status = np.full(n, 255, dtype=np.uint8)
         nfail = C.c_uint64(0)
-        _check(_lib.ssa_verify_batch_screened(self._ctx, _ptr(sigs) if n else None, _ptr(pks) if n else None, _ptr(inf),
-                                              _ptr(m), _ptr(off), stride, mlen, n, _ptr(c),
-                                              _ptr(status) if n else None, C.byref(nfail)),
+        _check(_lib.ssa_verify_batch_screened(self._ctx, *batch, c, _ptr(status) if n else None, C.byref(nfail)),
                "ssa_verify_batch_screened")
         return status, int(nfail.value)
 
@@ -462,9 +449,8 @@ class Engine:
                                      msg_stride=None, d_offsets=0, d_pk_inf=0):
         """device form (synchronises the stream once per slice to read the segment verdicts)"""
         _check(_lib.ssa_verify_batch_screened_device(
-            self._ctx, d_sigs, d_pks, d_pk_inf or None, d_msgs, d_offsets or None,
-            msg_stride if msg_stride is not None else msg_len, msg_len, n, d_coeffs or None, coeff_bytes, d_status,
-            d_nfail or None), "ssa_verify_batch_screened_device")
+            self._ctx, d_sigs, d_pks, *self._dev_batch(d_pk_inf, d_msgs, d_offsets, msg_stride, msg_len, n),
+            d_coeffs or None, coeff_bytes, d_status, d_nfail or None), "ssa_verify_batch_screened_device")
 
     def verify_many_screened(self, sigs, pks, msgs, offsets=None, check_torsion=True, pk_inf=None, sig_flag_byte=False,
                              coeffs=None):
@@ -475,24 +461,11 @@ class Engine:
         32-byte scalars, or None (drawn on the device).  stats: distinct keys, segments screened, segments that failed,
         lanes re-checked, lanes that could not be screened, slices screened, slices run entirely by the exact kernel,
         lanes at the dedup probe bound."""
-        sigs, pks = _np_u8(sigs, 81), _np_u8(pks, 96)
-        n = sigs.shape[0]
-        if pks.shape[0] != n:
-            raise MalformedInput("We should have the same number of signatures than public keys")
-        if n:
-            m, off, stride, mlen = self._msg_args(msgs, offsets, n)
-        else:
-            m, off, stride, mlen = None, None, 0, 0
-        c = _np_u8(coeffs, 32) if coeffs is not None else None
-        if c is not None:
-            assert c.shape[0] == n
-        inf = _np_u8(pk_inf) if pk_inf is not None else None
+        n, batch, c, keep = self._host_batch(sigs, pks, msgs, offsets, pk_inf, coeffs)
         status = np.full(n, 255, dtype=np.uint8)
         nfail = C.c_uint64(0)
         stats = np.zeros(8, dtype=np.uint64)
-        flags = (FLAG_CHECK_TORSION if check_torsion else 0) | (FLAG_SIG_FLAG_BYTE if sig_flag_byte else 0)
-        _check(_lib.ssa_verify_many_screened(self._ctx, _ptr(sigs) if n else None, _ptr(pks) if n else None, _ptr(inf),
-                                             _ptr(m), _ptr(off), stride, mlen, n, flags, _ptr(c),
+        _check(_lib.ssa_verify_many_screened(self._ctx, *batch, self._verify_flags(check_torsion, sig_flag_byte), c,
                                              _ptr(status) if n else None, C.byref(nfail), stats.ctypes.data),
                "ssa_verify_many_screened")
         return status, int(nfail.value), stats
@@ -502,12 +475,11 @@ class Engine:
         """device form of verify_many_screened (synchronises the stream twice per slice: for the number of distinct
         keys, and for the segment verdicts with the length of the re-check list); returns the statistics (uint64[8],
         host)"""
-        flags = (FLAG_CHECK_TORSION if check_torsion else 0) | (FLAG_SIG_FLAG_BYTE if sig_flag_byte else 0)
         stats = np.zeros(8, dtype=np.uint64)
         _check(_lib.ssa_verify_many_screened_device(
-            self._ctx, d_sigs, d_pks, d_pk_inf or None, d_msgs, d_offsets or None,
-            msg_stride if msg_stride is not None else msg_len, msg_len, n, flags, d_coeffs or None, coeff_bytes, d_status,
-            d_nfail or None, stats.ctypes.data), "ssa_verify_many_screened_device")
+            self._ctx, d_sigs, d_pks, *self._dev_batch(d_pk_inf, d_msgs, d_offsets, msg_stride, msg_len, n),
+            self._verify_flags(check_torsion, sig_flag_byte), d_coeffs or None, coeff_bytes, d_status, d_nfail or None,
+            stats.ctypes.data), "ssa_verify_many_screened_device")
         return stats
 
     def keycache_create(self, capacity):
@@ -524,24 +496,12 @@ class Engine:
         same coeffs, in every state of the cache.  stats[0..7] as verify_many_screened (rows that could not be published
         are added to [7]); [8] distinct keys found in the cache, [9] keys checked and inserted, [10] automatic clears,
         [11] slices that bypassed the cache."""
-        sigs, pks = _np_u8(sigs, 81), _np_u8(pks, 96)
-        n = sigs.shape[0]
-        if pks.shape[0] != n:
-            raise MalformedInput("We should have the same number of signatures than public keys")
-        if n:
-            m, off, stride, mlen = self._msg_args(msgs, offsets, n)
-        else:
-            m, off, stride, mlen = None, None, 0, 0
-        c = _np_u8(coeffs, 32) if coeffs is not None else None
-        if c is not None:
-            assert c.shape[0] == n
-        inf = _np_u8(pk_inf) if pk_inf is not None else None
+        n, batch, c, keep = self._host_batch(sigs, pks, msgs, offsets, pk_inf, coeffs)
         status = np.full(n, 255, dtype=np.uint8)
         nfail = C.c_uint64(0)
         stats = np.zeros(12, dtype=np.uint64)
-        flags = (FLAG_CHECK_TORSION if check_torsion else 0) | (FLAG_SIG_FLAG_BYTE if sig_flag_byte else 0)
-        _check(_lib.ssa_verify_many_cached(self._ctx, cache.handle, _ptr(sigs) if n else None, _ptr(pks) if n else None,
-                                           _ptr(inf), _ptr(m), _ptr(off), stride, mlen, n, flags, _ptr(c),
+        _check(_lib.ssa_verify_many_cached(self._ctx, cache.handle, *batch,
+                                           self._verify_flags(check_torsion, sig_flag_byte), c,
                                            _ptr(status) if n else None, C.byref(nfail), stats.ctypes.data),
                "ssa_verify_many_cached")
         return status, int(nfail.value), stats
@@ -550,12 +510,11 @@ class Engine:
                                   msg_stride=None, d_offsets=0, d_pk_inf=0, check_torsion=True, sig_flag_byte=False):
         """device form of verify_many_cached (two synchronisations per slice, as verify_many_screened_device; the slices
         run in order on the engine's stream); returns the statistics (uint64[12], host)"""
-        flags = (FLAG_CHECK_TORSION if check_torsion else 0) | (FLAG_SIG_FLAG_BYTE if sig_flag_byte else 0)
         stats = np.zeros(12, dtype=np.uint64)
         _check(_lib.ssa_verify_many_cached_device(
-            self._ctx, cache.handle, d_sigs, d_pks, d_pk_inf or None, d_msgs, d_offsets or None,
-            msg_stride if msg_stride is not None else msg_len, msg_len, n, flags, d_coeffs or None, coeff_bytes, d_status,
-            d_nfail or None, stats.ctypes.data), "ssa_verify_many_cached_device")
+            self._ctx, cache.handle, d_sigs, d_pks, *self._dev_batch(d_pk_inf, d_msgs, d_offsets, msg_stride, msg_len, n),
+            self._verify_flags(check_torsion, sig_flag_byte), d_coeffs or None, coeff_bytes, d_status, d_nfail or None,
+            stats.ctypes.data), "ssa_verify_many_cached_device")
         return stats
 
     def debug_screen_segments(self, k):
@@ -567,24 +526,14 @@ class Engine:
                                         msg_stride=None, d_offsets=0, d_pk_inf=0):
         """this rank's shard -> one 24-word record at device address d_partial24 (enqueued on the stream)"""
         _check(_lib.ssa_verify_batch_msm_partial_device(
-            self._ctx, d_sigs, d_pks, d_pk_inf or None, d_msgs, d_offsets or None,
-            msg_stride if msg_stride is not None else msg_len, msg_len, n, d_coeffs or None, coeff_bytes, d_partial24),
-            "ssa_verify_batch_msm_partial_device")
+            self._ctx, d_sigs, d_pks, *self._dev_batch(d_pk_inf, d_msgs, d_offsets, msg_stride, msg_len, n),
+            d_coeffs or None, coeff_bytes, d_partial24), "ssa_verify_batch_msm_partial_device")
 
     def verify_batch_msm_partial(self, sigs, pks, msgs, offsets=None, coeffs=None, pk_inf=None):
         """host buffers -> the shard's record as uint64[24]"""
-        sigs, pks = _np_u8(sigs, 81), _np_u8(pks, 96)
-        n = sigs.shape[0]
-        if n:
-            m, off, stride, mlen = self._msg_args(msgs, offsets, n)
-        else:
-            m, off, stride, mlen = None, None, 0, 0
-        c = _np_u8(coeffs, 32) if coeffs is not None else None
-        inf = _np_u8(pk_inf) if pk_inf is not None else None
+        n, batch, c, keep = self._host_batch(sigs, pks, msgs, offsets, pk_inf, coeffs)
         out = np.zeros(MSM_PARTIAL_WORDS, dtype=np.uint64)
-        _check(_lib.ssa_verify_batch_msm_partial(self._ctx, _ptr(sigs) if n else None, _ptr(pks) if n else None,
-                                                 _ptr(inf), _ptr(m), _ptr(off), stride, mlen, n, _ptr(c), _ptr(out)),
-               "ssa_verify_batch_msm_partial")
+        _check(_lib.ssa_verify_batch_msm_partial(self._ctx, *batch, c, _ptr(out)), "ssa_verify_batch_msm_partial")
         return out
 
     def msm_combine_device(self, d_parts24, k, d_verdict):
@@ -977,11 +926,9 @@ class Engine:
                            d_offsets=0, d_pk_inf=0, check_torsion=False, mode=None, sig_flag_byte=False):
         """sig_flag_byte=True with check_torsion=False is what ssa_verify_batch runs (src/batch.rs:104: R is decompressed
         with the flag byte of sig.x, no subgroup check)"""
-        flags = (FLAG_CHECK_TORSION if check_torsion else 0) | _MODE_FLAGS[mode] | \
-            (FLAG_SIG_FLAG_BYTE if sig_flag_byte else 0)
-        _check(_lib.ssa_verify_many_device(self._ctx, d_sigs, d_pks, d_pk_inf or None, d_msgs, d_offsets or None,
-                                           msg_stride if msg_stride is not None else msg_len, msg_len, n,
-                                           flags, d_status, d_nfail), "ssa_verify_many_device")
+        _check(_lib.ssa_verify_many_device(
+            self._ctx, d_sigs, d_pks, *self._dev_batch(d_pk_inf, d_msgs, d_offsets, msg_stride, msg_len, n),
+            self._verify_flags(check_torsion, sig_flag_byte, mode), d_status, d_nfail), "ssa_verify_many_device")
 
     def keygen_sign_many_device(self, d_sks, d_nonces, d_msgs, n, msg_len, d_pks, d_sigs, msg_stride=None,
                                 d_offsets=0, constant_time=False, keyed=False):

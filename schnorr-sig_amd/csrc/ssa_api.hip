@@ -678,10 +678,7 @@ extern "C" int ssa_debug_tail_plan(unsigned waves, unsigned pieces, unsigned gen
 // per-lane table workspace never exceeds one slice (the caller has reserved it).  *d_fail is added to.
 static int verify_slices(ssa_ctx *ctx, const DevBatch &b, const u64 *d_h, size_t n, uint32_t flags, uint8_t *d_status_out,
                          unsigned long long *d_fail) {
-    const size_t slice = ctx->lane_slice < n ? ctx->lane_slice : n;
-    for (size_t lo = 0; lo < n; lo += slice) {
-        const size_t cnt = n - lo < slice ? n - lo : slice;
-        const DevBatch s = b.slice(lo);
+    return for_dev_slices(b, n, ctx->lane_slice, [&](size_t lo, size_t cnt, const DevBatch &s) {
         const TailPlan tp = tail_plan(ctx, cnt, flags);
         unsigned blocks = grid_for(cnt, ctx->verify_block);
         if (tp.n_pieces) {
@@ -691,15 +688,13 @@ static int verify_slices(ssa_ctx *ctx, const DevBatch &b, const u64 *d_h, size_t
             HIP_TRY(hipMemsetAsync(ctx->tail_done.p, 0, 2 * (size_t)tp.tail_groups * sizeof(u32), ctx->stream));
             blocks = tail_grid_blocks(tp);
         }
-        int rc = timed_launch(ctx, "ssa_k_verify", [&] {
+        return timed_launch(ctx, "ssa_k_verify", [&] {
             hipLaunchKernelGGL(ssa_k_verify, dim3(blocks), dim3(ctx->verify_block), 0,
                                ctx->stream, s.sigs, s.pks, s.pk_inf, d_h + 4 * lo, (const u64 *)ctx->d_gtab,
                                (u64 *)ctx->ws_tab.p, cnt, flags, d_status_out + lo, d_fail, tp, (u32 *)ctx->tail_done.p,
                                (u64 *)ctx->tail_park.p);
         });
-        if (rc) return rc;
-    }
-    return 0;
+    });
 }
 
 int ssa_internal_verify_hashed(ssa_ctx *ctx, const DevBatch &b, const uint64_t *d_h, size_t n, uint32_t flags,
@@ -726,9 +721,7 @@ static int verify_one_slice(ssa_ctx *c, const DevBatch &b, size_t cnt, uint32_t 
 static int verify_launch(ssa_ctx *ctx, const DevBatch &b, size_t n, uint32_t flags, uint8_t *d_status_out,
                          unsigned long long *d_fail) {
     // small batches: one wave per signature (low latency); large ones: one lane per signature (throughput)
-    const size_t coop_lim = (flags & SSA_FLAG_CHECK_TORSION) ? ctx->coop_max_n_torsion : ctx->coop_max_n;
-    const bool coop = (flags & SSA_FLAG_FORCE_COOP) || (!(flags & SSA_FLAG_FORCE_LANE) && n <= coop_lim);
-    if (coop) {
+    if (takes_coop(ctx, n, flags)) {
         return timed_launch(ctx, "ssa_k_verify_coop", [&] {
             hipLaunchKernelGGL(ssa_k_verify_coop, dim3((unsigned)n), dim3(128), 0, ctx->stream, ctx->d_params, b.sigs,
                                b.pks, b.pk_inf, b.msgs, (const u64 *)ctx->d_gtab, n, flags, d_status_out, d_fail);
@@ -769,9 +762,7 @@ extern "C" int ssa_verify_many_device(ssa_ctx *ctx, const uint8_t *d_sigs, const
                                       size_t n, uint32_t flags, uint8_t *d_status_out,
                                       uint64_t *d_n_fail_out) {
     const DevBatch b{d_sigs, d_pks, d_pk_inf, {d_msgs, d_msg_off, msg_stride, msg_len}};
-    if (!ctx || (n && (!d_sigs || !d_pks || !d_status_out))) return SSA_ERR_ARG;
-    if (int rc = check_msgs(b.msgs, n)) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
+    if (int rc = check_dev_batch(ctx, b, n, d_status_out)) return rc;
     unsigned long long *d_fail;
     if (int rc = reset_fail_counter(ctx, d_n_fail_out, &d_fail)) return rc;
     if (n == 0) return 0;
@@ -824,38 +815,25 @@ extern "C" int ssa_decompress_many_device(ssa_ctx *ctx, const uint8_t *d_compres
 // page-locked memory.
 static int verify_many_host_one(ssa_ctx *ctx, const HostBatch &b, size_t n, uint32_t flags, uint8_t *status_out,
                                 uint64_t *n_fail_out) {
-    const size_t coop_lim = (flags & SSA_FLAG_CHECK_TORSION) ? ctx->coop_max_n_torsion : ctx->coop_max_n;
-    const bool lane_kernels = !(flags & SSA_FLAG_FORCE_COOP) && ((flags & SSA_FLAG_FORCE_LANE) || n > coop_lim);
-    HostCall hc(ctx);
-    PipelinedInputs pin;      // its destructor drains the side streams on every error return
-    const StagedInputs s = slice_inputs(hc, pin, b, n, nullptr, lane_kernels, true);
-    u8 *d_status = hc.out(ctx->st_status, s.hashed ? ctx->pin_out.p : status_out, n, 16);
-    unsigned long long nf = 0, *d_fail = (unsigned long long *)ctx->ws_fail.p;
-    hc.copy_back(&nf, d_fail, sizeof nf);
-    const int rc = hc.finish([&] {
+    // (only the lane kernels read the hashes the pipeline leaves)
+    return status_host_one(ctx, b, n, nullptr, !takes_coop(ctx, n, flags), true, status_out, n_fail_out,
+                           [&](const StagedInputs &s, u8 *d_status, unsigned long long *d_fail) {
         HIP_TRY(hipMemsetAsync(d_fail, 0, sizeof(unsigned long long), ctx->stream));
         if (!s.hashed) return verify_launch(ctx, s.batch, n, flags, d_status, d_fail);
         // (the pipeline hashed the whole slice into ws_h, 32 B per lane, while it was uploading)
         return ssa_internal_verify_hashed(ctx, s.batch, (const uint64_t *)ctx->ws_h.p, n, flags, d_status, d_fail);
     });
-    if (rc) return rc;
-    pin.done();
-    if (s.hashed) std::memcpy(status_out, ctx->pin_out.p, n);
-    if (n_fail_out) *n_fail_out = nf;
-    return 0;
 }
 
 extern "C" int ssa_verify_many(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_inf,
                                const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride,
                                size_t msg_len, size_t n, uint32_t flags, uint8_t *status_out,
                                uint64_t *n_fail_out) {
-    if (!ctx || (n && (!sigs || !pks || !status_out))) return SSA_ERR_ARG;
-    if (int rc = check_msgs({msgs, msg_off, msg_stride, msg_len}, n)) return rc;
-    if (int rc = check_host_offsets(msg_off, n)) return rc;
+    const HostBatch b{sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len};
+    if (int rc = check_host_batch(ctx, b, n, status_out)) return rc;
     if (n_fail_out) *n_fail_out = 0;
     if (n == 0) return 0;
     HIP_TRY(hipSetDevice(ctx->device));
-    const HostBatch b{sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len};
     return run_host_slices_counted(ctx, b, n, ctx->lane_slice, n_fail_out,
                                    [&](ssa_ctx *c, size_t lo, size_t cnt, const HostBatch &s, uint64_t *nf) {
                                        return verify_many_host_one(c, s, cnt, flags, status_out + lo, nf);
@@ -1080,7 +1058,6 @@ extern "C" int ssa_verify_many_indexed_device(ssa_ctx *ctx, ssa_keyset *ks, cons
     const MsgView mv{d_msgs, d_msg_off, msg_stride, msg_len};
     if (!ctx || !ks || ks->ctx != ctx || (n && (!d_key_idx || !d_sigs || !d_status_out))) return SSA_ERR_ARG;
     if (int rc = check_msgs(mv, n)) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
     unsigned long long *d_fail;
     if (int rc = reset_fail_counter(ctx, d_n_fail_out, &d_fail)) return rc;
     if (n == 0) return 0;
@@ -1128,19 +1105,12 @@ extern "C" int ssa_verify_many_indexed(ssa_ctx *ctx, ssa_keyset *ks, const uint3
 }
 
 // ------------------------------------------------------------------ key dedup
-// what the dedup entry points report: distinct keys summed over slices, slices on the keyed route, slices that fell
-// back, lanes that hit the probe bound (the host form's two threads add to it under the lock)
-struct DedupStats {
-    std::mutex mu;
-    uint64_t v[4] = {0, 0, 0, 0};
-    void add(uint64_t distinct, uint64_t keyed, uint64_t fell_back, uint64_t bound_hits) {
-        std::lock_guard<std::mutex> lock(mu);
-        v[0] += distinct;
-        v[1] += keyed;
-        v[2] += fell_back;
-        v[3] += bound_hits;
-    }
-};
+// what the dedup entry points report (a CallStats of four words): distinct keys summed over slices, slices on the keyed
+// route, slices that fell back, lanes that hit the probe bound
+static void dedup_stats_add(CallStats *stats, uint64_t distinct, bool keyed, uint64_t bound_hits) {
+    const uint64_t d[4] = {distinct, keyed ? 1u : 0u, keyed ? 0u : 1u, bound_hits};
+    if (stats) stats->add(d);
+}
 
 static int dedup_fingerprint_key(ssa_ctx *ctx) {
     if (ctx->dedup_key_set) return 0;
@@ -1252,14 +1222,14 @@ int ssa_internal_verify_keyed_view(ssa_ctx *ctx, const uint8_t *d_sigs, const ui
 // ONE slice (cnt <= ctx->lane_slice lanes) of the lane kernels' route on ctx->stream with ctx's workspaces; hashed: the
 // challenge scalars are already in ctx->ws_h.  *d_fail is added to.
 static int dedup_verify_slice(ssa_ctx *ctx, const DevBatch &b, size_t cnt, uint32_t flags, bool hashed,
-                              uint8_t *d_status_out, unsigned long long *d_fail, DedupStats *stats) {
+                              uint8_t *d_status_out, unsigned long long *d_fail, CallStats *stats) {
     const double ratio = ctx->dedup_ratio[(flags & SSA_FLAG_CHECK_TORSION) ? 1 : 0];
     uint64_t u = cnt, hits = 0;
     // (a threshold of 0 sends every slice to the fallback: the keys are then counted only for the statistics)
     if (ratio > 0 || stats)
         if (int rc = dedup_slice(ctx, b.pks, b.pk_inf, cnt, &u, &hits)) return rc;
     const bool keyed = (double)u < ratio * (double)cnt;
-    if (stats) stats->add(u, keyed ? 1 : 0, keyed ? 0 : 1, hits);
+    dedup_stats_add(stats, u, keyed, hits);
     constexpr size_t TAB_BYTES = (size_t)(PTAB_ENTRIES * PTAB_ENTRY_U64) * sizeof(u64);
     if (!keyed) {       // (nearly) every key is distinct: the path of ssa_verify_many
         if (!hashed) return verify_one_slice(ctx, b, cnt, flags, d_status_out, d_fail);
@@ -1279,29 +1249,16 @@ static int dedup_verify_slice(ssa_ctx *ctx, const DevBatch &b, size_t cnt, uint3
                                      d_status_out, d_fail);
 }
 
-static inline bool dedup_takes_coop(const ssa_ctx *ctx, size_t n, uint32_t flags) {
-    const size_t coop_lim = (flags & SSA_FLAG_CHECK_TORSION) ? ctx->coop_max_n_torsion : ctx->coop_max_n;
-    return (flags & SSA_FLAG_FORCE_COOP) || (!(flags & SSA_FLAG_FORCE_LANE) && n <= coop_lim);
-}
-
 // A batch for the cooperative kernel takes the path of ssa_verify_many unchanged; its keys are counted, slice by slice,
 // only for a caller that asked for the statistics.
-static int dedup_count_only(ssa_ctx *ctx, const DevBatch &b, size_t n, DedupStats *stats) {
+static int dedup_count_only(ssa_ctx *ctx, const DevBatch &b, size_t n, CallStats *stats) {
     if (!stats) return 0;
-    const size_t slice = ctx->lane_slice < n ? ctx->lane_slice : n;
-    for (size_t lo = 0; lo < n; lo += slice) {
-        const size_t cnt = n - lo < slice ? n - lo : slice;
-        const DevBatch s = b.slice(lo);
+    return for_dev_slices(b, n, ctx->lane_slice, [&](size_t, size_t cnt, const DevBatch &s) {
         uint64_t u = 0, hits = 0;
         if (int rc = dedup_slice(ctx, s.pks, s.pk_inf, cnt, &u, &hits)) return rc;
-        stats->add(u, 0, 1, hits);
-    }
-    return 0;
-}
-
-static void dedup_stats_out(const DedupStats &st, uint64_t stats_out[4]) {
-    if (stats_out)
-        for (int k = 0; k < 4; k++) stats_out[k] = st.v[k];
+        dedup_stats_add(stats, u, false, hits);
+        return 0;
+    });
 }
 
 extern "C" int ssa_verify_many_dedup_device(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks,
@@ -1309,75 +1266,59 @@ extern "C" int ssa_verify_many_dedup_device(ssa_ctx *ctx, const uint8_t *d_sigs,
                                             size_t msg_stride, size_t msg_len, size_t n, uint32_t flags,
                                             uint8_t *d_status_out, uint64_t *d_n_fail_out, uint64_t stats_out[4]) {
     const DevBatch b{d_sigs, d_pks, d_pk_inf, {d_msgs, d_msg_off, msg_stride, msg_len}};
-    if (!ctx || (n && (!d_sigs || !d_pks || !d_status_out))) return SSA_ERR_ARG;
-    if (int rc = check_msgs(b.msgs, n)) return rc;
-    if (stats_out) std::memset(stats_out, 0, 4 * sizeof(uint64_t));
-    HIP_TRY(hipSetDevice(ctx->device));
+    if (int rc = check_dev_batch(ctx, b, n, d_status_out)) return rc;
+    CallStats st(4);
+    st.out(stats_out);      // (still empty: the caller's words are zeroed)
     unsigned long long *d_fail;
     if (int rc = reset_fail_counter(ctx, d_n_fail_out, &d_fail)) return rc;
     if (n == 0) return 0;
-    DedupStats st;
     int rc = 0;
-    if (dedup_takes_coop(ctx, n, flags)) {
+    if (takes_coop(ctx, n, flags)) {
         rc = dedup_count_only(ctx, b, n, stats_out ? &st : nullptr);
         if (rc == 0) rc = verify_launch(ctx, b, n, flags, d_status_out, d_fail);
     } else {
         // slice after slice on the context's stream (each slice's policy waits for its u: the slices of this form do not
         // alternate between two streams)
-        const size_t slice = ctx->lane_slice < n ? ctx->lane_slice : n;
-        for (size_t lo = 0; lo < n && rc == 0; lo += slice) {
-            const size_t cnt = n - lo < slice ? n - lo : slice;
-            rc = dedup_verify_slice(ctx, b.slice(lo), cnt, flags, false, d_status_out + lo, d_fail, stats_out ? &st : nullptr);
-        }
+        rc = for_dev_slices(b, n, ctx->lane_slice, [&](size_t lo, size_t cnt, const DevBatch &s) {
+            return dedup_verify_slice(ctx, s, cnt, flags, false, d_status_out + lo, d_fail, stats_out ? &st : nullptr);
+        });
     }
     if (rc) return rc;
-    dedup_stats_out(st, stats_out);
+    st.out(stats_out);
     return 0;
 }
 
-// ONE slice from host buffers: the staging and copy-back of verify_many_host_one around the dedup pipeline
+// ONE slice from host buffers: the shell of verify_many_host_one (status_host_one) around the dedup pipeline
 static int dedup_host_one(ssa_ctx *ctx, const HostBatch &b, size_t n, uint32_t flags, uint8_t *status_out,
-                          uint64_t *n_fail_out, DedupStats *stats) {
-    const bool lane_kernels = !dedup_takes_coop(ctx, n, flags);
-    HostCall hc(ctx);
-    PipelinedInputs pin;      // its destructor drains the side streams on every error return
-    const StagedInputs s = slice_inputs(hc, pin, b, n, nullptr, lane_kernels, true);
-    u8 *d_status = hc.out(ctx->st_status, s.hashed ? ctx->pin_out.p : status_out, n, 16);
-    unsigned long long nf = 0, *d_fail = (unsigned long long *)ctx->ws_fail.p;
-    hc.copy_back(&nf, d_fail, sizeof nf);
-    const int rc = hc.finish([&] {
+                          uint64_t *n_fail_out, CallStats *stats) {
+    const bool lane_kernels = !takes_coop(ctx, n, flags);
+    return status_host_one(ctx, b, n, nullptr, lane_kernels, true, status_out, n_fail_out,
+                           [&](const StagedInputs &s, u8 *d_status, unsigned long long *d_fail) {
         HIP_TRY(hipMemsetAsync(d_fail, 0, sizeof(unsigned long long), ctx->stream));
         if (lane_kernels) return dedup_verify_slice(ctx, s.batch, n, flags, s.hashed, d_status, d_fail, stats);
         if (int r = dedup_count_only(ctx, s.batch, n, stats)) return r;
         return verify_launch(ctx, s.batch, n, flags, d_status, d_fail);
     });
-    if (rc) return rc;
-    pin.done();
-    if (s.hashed) std::memcpy(status_out, ctx->pin_out.p, n);
-    if (n_fail_out) *n_fail_out = nf;
-    return 0;
 }
 
 extern "C" int ssa_verify_many_dedup(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_inf,
                                      const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len,
                                      size_t n, uint32_t flags, uint8_t *status_out, uint64_t *n_fail_out,
                                      uint64_t stats_out[4]) {
-    if (!ctx || (n && (!sigs || !pks || !status_out))) return SSA_ERR_ARG;
-    if (int rc = check_msgs({msgs, msg_off, msg_stride, msg_len}, n)) return rc;
-    if (int rc = check_host_offsets(msg_off, n)) return rc;
+    const HostBatch b{sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len};
+    if (int rc = check_host_batch(ctx, b, n, status_out)) return rc;
     if (n_fail_out) *n_fail_out = 0;
-    if (stats_out) std::memset(stats_out, 0, 4 * sizeof(uint64_t));
+    CallStats st(4);
+    st.out(stats_out);      // (still empty: the caller's words are zeroed)
     if (n == 0) return 0;
     HIP_TRY(hipSetDevice(ctx->device));
-    const HostBatch b{sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len};
-    DedupStats st;
     const int rc = run_host_slices_counted(ctx, b, n, ctx->lane_slice, n_fail_out,
                                            [&](ssa_ctx *c, size_t lo, size_t cnt, const HostBatch &s, uint64_t *nf) {
                                                return dedup_host_one(c, s, cnt, flags, status_out + lo, nf,
                                                                      stats_out ? &st : nullptr);
                                            });
     if (rc) return rc;
-    dedup_stats_out(st, stats_out);
+    st.out(stats_out);
     return 0;
 }
 

@@ -353,6 +353,52 @@ struct DevBatch {
     }
 };
 
+// fn(lo, cnt, lanes [lo, lo + cnt) of b) for every slice of at most `slice` lanes, in order; stops at the first error
+template <class F>
+static inline int for_dev_slices(const DevBatch &b, size_t n, size_t slice, F &&fn) {
+    for (size_t lo = 0; lo < n; lo += slice)
+        if (int rc = fn(lo, n - lo < slice ? n - lo : slice, b.slice(lo))) return rc;
+    return 0;
+}
+
+// The argument checks of the entry points that return one status byte per signature, before anything is zeroed or
+// enqueued: host forms (the offset table is read here) and device forms (d_coeffs: coefficients of coeff_bytes each)
+static inline int check_host_batch(const ssa_ctx *ctx, const HostBatch &b, size_t n, const uint8_t *status_out) {
+    if (!ctx || (n && (!b.sigs || !b.pks || !status_out))) return SSA_ERR_ARG;
+    if (int rc = check_msgs({b.msgs, b.msg_off, b.msg_stride, b.msg_len}, n)) return rc;
+    return check_host_offsets(b.msg_off, n);
+}
+static inline int check_dev_batch(const ssa_ctx *ctx, const DevBatch &b, size_t n, const uint8_t *d_status_out,
+                                  const uint8_t *d_coeffs = nullptr, uint32_t coeff_bytes = 32) {
+    if (!ctx || (n && (!b.sigs || !b.pks || !d_status_out))) return SSA_ERR_ARG;
+    if (d_coeffs && (coeff_bytes == 0 || coeff_bytes > 32)) return SSA_ERR_ARG;
+    return check_msgs(b.msgs, n);
+}
+
+// small batches take the cooperative kernel (one wave per signature: low latency), large ones the lane kernels (one lane
+// per signature: throughput).  The host forms stage their inputs by this answer and the device forms launch by it.
+static inline bool takes_coop(const ssa_ctx *ctx, size_t n, uint32_t flags) {
+    const size_t coop_lim = (flags & SSA_FLAG_CHECK_TORSION) ? ctx->coop_max_n_torsion : ctx->coop_max_n;
+    return (flags & SSA_FLAG_FORCE_COOP) || (!(flags & SSA_FLAG_FORCE_LANE) && n <= coop_lim);
+}
+
+// the statistics words an entry point reports (`width` of them: 4 for the dedup, 8 screened, 12 with a key cache), summed
+// over its slices; the host forms' two threads add to it under the lock
+struct CallStats {
+    const int width;
+    std::mutex mu;
+    uint64_t v[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    explicit CallStats(int words) : width(words) {}
+    void add(const uint64_t *d) {
+        std::lock_guard<std::mutex> lock(mu);
+        for (int k = 0; k < width; k++) v[k] += d[k];
+    }
+    void out(uint64_t *stats_out) const {
+        if (stats_out)
+            for (int k = 0; k < width; k++) stats_out[k] = v[k];
+    }
+};
+
 // device copies of one slice of a batch; hashed: ctx->ws_h already holds the challenge scalars (pipelined_upload_hash)
 struct StagedInputs {
     DevBatch batch{};
@@ -360,8 +406,10 @@ struct StagedInputs {
     bool hashed = false;
 };
 
-// the rejection counter of a counted device form: the caller's, or the context's own; zeroed on ctx->stream
+// a counted device form begins: the context's device is selected, and the rejection counter (the caller's, or the
+// context's own) is zeroed on ctx->stream
 static inline int reset_fail_counter(ssa_ctx *ctx, uint64_t *d_n_fail_out, unsigned long long **d_fail) {
+    HIP_TRY(hipSetDevice(ctx->device));
     *d_fail = (unsigned long long *)(d_n_fail_out ? (void *)d_n_fail_out : ctx->ws_fail.p);
     HIP_TRY(hipMemsetAsync(*d_fail, 0, sizeof(unsigned long long), ctx->stream));
     return 0;
@@ -603,7 +651,7 @@ static inline int pipelined_upload_hash(ssa_ctx *ctx, const HostBatch &b, size_t
     return 0;
 }
 
-// The inputs of ONE host slice on the device, for verify_many_host_one, msm_host_one and screen_host_one: a large slice
+// The inputs of ONE host slice on the device, for status_host_one and msm_host_one: a large slice
 // (with `pipeline`, from ctx->pipeline_min_n lanes on) goes through pipelined_upload_hash, which leaves the challenge
 // hashes in ctx->ws_h (hashed) and arms `pin`; any other slice, or one that finds no page-locked memory for its
 // statuses (pin_out) or for the caller's 32-byte coefficients, is staged by `hc`.  Errors are left in hc.rc.
@@ -639,6 +687,27 @@ static inline StagedInputs slice_inputs(HostCall &hc, PipelinedInputs &pin, cons
     s.batch.msgs = hc.msgs(b.msgs, b.msg_off, b.msg_stride, b.msg_len, n);
     if (coeffs) s.coeffs = hc.in(ctx->st_coeffs, coeffs, n * 32);
     return s;
+}
+
+// ONE slice from host buffers for the entry points that return one status byte per signature: the inputs staged or
+// pipelined (slice_inputs: coeffs, pipeline and pin_out are its arguments), device_form(inputs, d_status, d_fail) run on
+// ctx->stream -- it leaves the rejection count in *d_fail, zeroing or counting as its pipeline needs -- and statuses and
+// count copied back.  With pin_out the statuses of a pipelined slice come back through page-locked memory.
+template <class F>
+static int status_host_one(ssa_ctx *ctx, const HostBatch &b, size_t n, const uint8_t *coeffs, bool pipeline, bool pin_out,
+                           uint8_t *status_out, uint64_t *n_fail_out, F &&device_form) {
+    HostCall hc(ctx);
+    PipelinedInputs pin;      // its destructor drains the side streams on every error return
+    const StagedInputs s = slice_inputs(hc, pin, b, n, coeffs, pipeline, pin_out);
+    const bool through_pin = pin_out && s.hashed;
+    u8 *d_status = hc.out(ctx->st_status, through_pin ? ctx->pin_out.p : status_out, n, 16);
+    unsigned long long nf = 0, *d_fail = (unsigned long long *)ctx->ws_fail.p;
+    hc.copy_back(&nf, d_fail, sizeof nf);
+    if (int rc = hc.finish([&] { return device_form(s, d_status, d_fail); })) return rc;
+    pin.done();
+    if (through_pin) std::memcpy(status_out, ctx->pin_out.p, n);
+    if (n_fail_out) *n_fail_out = nf;
+    return 0;
 }
 
 // defined in ssa_api.hip: hash_message + Scalar::from_bits_vartime for n signatures into ctx->ws_h

@@ -1604,12 +1604,11 @@ static int msm_run(ssa_ctx *ctx, const DevBatch &b, size_t n, const uint8_t *d_c
     const size_t slice = ctx->msm_slice, k = (n + slice - 1) / slice;
     if (ctx->msm_slice_recs.reserve(k * 24 * sizeof(u64))) return SSA_ERR_HIP;
     u64 *recs = (u64 *)ctx->msm_slice_recs.p;
-    for (size_t j = 0; j < k; j++) {
-        const size_t lo = j * slice, cnt = n - lo < slice ? n - lo : slice;
-        if (int rc = msm_run_one(ctx, b.slice(lo), cnt, d_coeffs ? d_coeffs + (size_t)coeff_bytes * lo : nullptr, coeff_bytes,
-                                 nullptr, recs + 24 * j, d_h ? d_h + 4 * lo : nullptr))
-            return rc;
-    }
+    if (int rc = for_dev_slices(b, n, slice, [&](size_t lo, size_t cnt, const DevBatch &s) {
+            return msm_run_one(ctx, s, cnt, d_coeffs ? d_coeffs + (size_t)coeff_bytes * lo : nullptr, coeff_bytes, nullptr,
+                               recs + 24 * (lo / slice), d_h ? d_h + 4 * lo : nullptr);
+        }))
+        return rc;
     return msm_combine_records(ctx, recs, k, d_verdict_out, d_partial_out);
 }
 
@@ -1827,59 +1826,44 @@ extern "C" int ssa_verify_batch_screened_device(ssa_ctx *ctx, const uint8_t *d_s
                                                 size_t msg_stride, size_t msg_len, size_t n, const uint8_t *d_coeffs,
                                                 uint32_t coeff_bytes, uint8_t *d_status_out, uint64_t *d_n_fail_out) {
     const DevBatch b{d_sigs, d_pks, d_pk_inf, {d_msgs, d_msg_off, msg_stride, msg_len}};
-    if (!ctx || (n && (!d_sigs || !d_pks || !d_status_out))) return SSA_ERR_ARG;
-    if (d_coeffs && (coeff_bytes == 0 || coeff_bytes > 32)) return SSA_ERR_ARG;
-    if (int rc = check_msgs(b.msgs, n)) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
+    if (int rc = check_dev_batch(ctx, b, n, d_status_out, d_coeffs, coeff_bytes)) return rc;
     unsigned long long *d_fail;
     if (int rc = reset_fail_counter(ctx, d_n_fail_out, &d_fail)) return rc;
     if (n == 0) return 0;
     if (n <= ctx->msm_small_max)
         return ssa_verify_many_device(ctx, d_sigs, d_pks, d_pk_inf, d_msgs, d_msg_off, msg_stride, msg_len, n,
                                       SSA_FLAG_SIG_FLAG_BYTE, d_status_out, (uint64_t *)d_fail);
-    const size_t slice = ctx->msm_slice;
-    for (size_t lo = 0; lo < n; lo += slice) {      // segments never straddle two slices
-        const size_t cnt = n - lo < slice ? n - lo : slice;
-        if (int rc = screen_slice(ctx, b.slice(lo), cnt, d_coeffs ? d_coeffs + (size_t)coeff_bytes * lo : nullptr, coeff_bytes,
-                                  nullptr, d_status_out + lo))
-            return rc;
-    }
+    // (segments never straddle two slices)
+    if (int rc = for_dev_slices(b, n, ctx->msm_slice, [&](size_t lo, size_t cnt, const DevBatch &s) {
+            return screen_slice(ctx, s, cnt, d_coeffs ? d_coeffs + (size_t)coeff_bytes * lo : nullptr, coeff_bytes, nullptr,
+                                d_status_out + lo);
+        }))
+        return rc;
     return screen_count(ctx, d_status_out, n, d_fail);
 }
 
 // ONE slice from host buffers (the staging of msm_host_one): statuses into status_out[0, n), *nf the count
 static int screen_host_one(ssa_ctx *ctx, const HostBatch &b, size_t n, const uint8_t *coeffs, uint8_t *status_out,
                            uint64_t *nf) {
-    HostCall hc(ctx);
-    PipelinedInputs pin;      // its destructor drains the side streams on every error return
-    const StagedInputs s = slice_inputs(hc, pin, b, n, coeffs, true, false);
-    u8 *d_status = hc.out(ctx->st_status, status_out, n, 16);
-    unsigned long long v = 0, *d_fail = (unsigned long long *)ctx->ws_fail.p;
-    hc.copy_back(&v, d_fail, sizeof v);
-    if (int rc = hc.finish([&] {
-            if (int r = screen_slice(ctx, s.batch, n, s.coeffs, 32, s.hashed ? (const u64 *)ctx->ws_h.p : nullptr, d_status))
-                return r;
-            return screen_count(ctx, d_status, n, d_fail);
-        }))
-        return rc;
-    pin.done();
-    if (nf) *nf = v;
-    return 0;
+    return status_host_one(ctx, b, n, coeffs, true, false, status_out, nf,
+                           [&](const StagedInputs &s, u8 *d_status, unsigned long long *d_fail) {
+        if (int r = screen_slice(ctx, s.batch, n, s.coeffs, 32, s.hashed ? (const u64 *)ctx->ws_h.p : nullptr, d_status))
+            return r;
+        return screen_count(ctx, d_status, n, d_fail);
+    });
 }
 
 extern "C" int ssa_verify_batch_screened(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_inf,
                                          const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len,
                                          size_t n, const uint8_t *coeffs, uint8_t *status_out, uint64_t *n_fail_out) {
-    if (!ctx || (n && (!sigs || !pks || !status_out))) return SSA_ERR_ARG;
-    if (int rc = check_msgs({msgs, msg_off, msg_stride, msg_len}, n)) return rc;
-    if (int rc = check_host_offsets(msg_off, n)) return rc;
+    const HostBatch b{sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len};
+    if (int rc = check_host_batch(ctx, b, n, status_out)) return rc;
     if (n_fail_out) *n_fail_out = 0;
     if (n == 0) return 0;
     HIP_TRY(hipSetDevice(ctx->device));
     if (n <= ctx->msm_small_max)
         return ssa_verify_many(ctx, sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len, n, SSA_FLAG_SIG_FLAG_BYTE,
                                status_out, n_fail_out);
-    const HostBatch b{sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len};
     return run_host_slices_counted(ctx, b, n, ctx->msm_slice, n_fail_out,
                                    [&](ssa_ctx *c, size_t lo, size_t cnt, const HostBatch &s, uint64_t *nf) {
                                        return screen_host_one(c, s, cnt, coeffs ? coeffs + 32 * lo : nullptr,
@@ -1896,24 +1880,13 @@ extern "C" int ssa_verify_batch_screened(ssa_ctx *ctx, const uint8_t *sigs, cons
 // screen.  The screen only ever accepts: every nonzero status comes from the exact kernel.
 constexpr uint32_t MANY_SCREEN_FLAGS = SSA_FLAG_CHECK_TORSION | SSA_FLAG_SIG_FLAG_BYTE;
 
-// what the entry points report (the host form's two threads add to it under the lock)
-// (words 8..11 are the key cache's: ssa_verify_many_cached)
-struct ManyScreenStats {
-    std::mutex mu;
-    uint64_t v[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    void add(const uint64_t d[12]) {
-        std::lock_guard<std::mutex> lock(mu);
-        for (int k = 0; k < 12; k++) v[k] += d[k];
-    }
-};
-
 // ONE slice (n <= ctx->lane_slice) on ctx->stream into d_status[0, n): d_h = the slice's challenge scalars if they exist
 // (else they are computed into ctx->ws_h).  Synchronises the stream twice: for u, and for the segment verdicts together
 // with the length of the re-check list.  With a key cache (ssa_verify_many_cached) the keys are
 // looked up there and only the unseen ones are checked; everything behind the key check is the same code.
+// stats: what the entry points report, a CallStats of 8 words, or of 12 with a key cache (words 8..11 are the cache's).
 static int screen_many_slice(ssa_ctx *ctx, const DevBatch &b, size_t n, const uint8_t *d_coeffs, uint32_t coeff_bytes,
-                             uint32_t flags, const u64 *d_h, uint8_t *d_status, ManyScreenStats *stats,
-                             ssa_keycache *kc = nullptr) {
+                             uint32_t flags, const u64 *d_h, uint8_t *d_status, CallStats *stats, ssa_keycache *kc) {
     uint64_t sv[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     if (ctx->scr_fail.reserve(16)) return SSA_ERR_HIP;
     unsigned long long *scratch_fail = (unsigned long long *)ctx->scr_fail.p;    // (the caller counts the statuses)
@@ -2011,15 +1984,43 @@ static int screen_many_slice(ssa_ctx *ctx, const DevBatch &b, size_t n, const ui
     return rc;
 }
 
-static void many_screen_stats_out(const ManyScreenStats &st, uint64_t stats_out[8]) {
-    if (stats_out)
-        for (int k = 0; k < 8; k++) stats_out[k] = st.v[k];
-}
-
 // slices of this call: SSA_LANE_SLICE lanes (the dedup table, the per-key tables and the screen share one slice)
 static size_t many_screen_slice_lanes(const ssa_ctx *ctx) {
     const size_t cap = (size_t)1 << 23;      // (msm_run_one: an item carries its point index in 24 bits)
     return ctx->lane_slice < cap ? ctx->lane_slice : cap;
+}
+
+// The device form of ssa_verify_many_screened (kc == nullptr, 8 statistics words) and of ssa_verify_many_cached (its key
+// cache, 12 words): slice after slice on the context's stream.
+static int many_screened_device(ssa_ctx *ctx, ssa_keycache *kc, const DevBatch &b, size_t n, uint32_t flags,
+                                const uint8_t *d_coeffs, uint32_t coeff_bytes, uint8_t *d_status_out, uint64_t *d_n_fail_out,
+                                uint64_t *stats_out, int stats_words) {
+    if (flags & ~MANY_SCREEN_FLAGS) return SSA_ERR_ARG;
+    if (int rc = check_dev_batch(ctx, b, n, d_status_out, d_coeffs, coeff_bytes)) return rc;
+    if (kc && kc->ctx != ctx) return SSA_ERR_ARG;
+    CallStats st(stats_words);
+    st.out(stats_out);      // (still empty: the caller's words are zeroed)
+    if (flags == SSA_FLAG_SIG_FLAG_BYTE)      // verify_batch semantics: no key check to add or to cache, the screened form as it is
+        return ssa_verify_batch_screened_device(ctx, b.sigs, b.pks, b.pk_inf, b.msgs.msgs, b.msgs.off, b.msgs.stride,
+                                                b.msgs.len, n, d_coeffs, coeff_bytes, d_status_out, d_n_fail_out);
+    unsigned long long *d_fail;
+    if (int rc = reset_fail_counter(ctx, d_n_fail_out, &d_fail)) return rc;
+    if (n == 0) return 0;
+    if (n <= ctx->msm_small_max) {
+        const int rc = ssa_verify_many_device(ctx, b.sigs, b.pks, b.pk_inf, b.msgs.msgs, b.msgs.off, b.msgs.stride,
+                                              b.msgs.len, n, flags, d_status_out, (uint64_t *)d_fail);
+        if (rc == 0 && stats_out) stats_out[6] = 1;
+        return rc;
+    }
+    // (segments never straddle two slices)
+    if (int rc = for_dev_slices(b, n, many_screen_slice_lanes(ctx), [&](size_t lo, size_t cnt, const DevBatch &s) {
+            return screen_many_slice(ctx, s, cnt, d_coeffs ? d_coeffs + (size_t)coeff_bytes * lo : nullptr, coeff_bytes,
+                                     flags, nullptr, d_status_out + lo, stats_out ? &st : nullptr, kc);
+        }))
+        return rc;
+    if (int rc = screen_count(ctx, d_status_out, n, d_fail)) return rc;
+    st.out(stats_out);
+    return 0;
 }
 
 extern "C" int ssa_verify_many_screened_device(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks,
@@ -2027,56 +2028,72 @@ extern "C" int ssa_verify_many_screened_device(ssa_ctx *ctx, const uint8_t *d_si
                                                size_t msg_stride, size_t msg_len, size_t n, uint32_t flags,
                                                const uint8_t *d_coeffs, uint32_t coeff_bytes, uint8_t *d_status_out,
                                                uint64_t *d_n_fail_out, uint64_t stats_out[8]) {
-    if (flags & ~MANY_SCREEN_FLAGS) return SSA_ERR_ARG;
-    const DevBatch b{d_sigs, d_pks, d_pk_inf, {d_msgs, d_msg_off, msg_stride, msg_len}};
-    if (!ctx || (n && (!d_sigs || !d_pks || !d_status_out))) return SSA_ERR_ARG;
-    if (d_coeffs && (coeff_bytes == 0 || coeff_bytes > 32)) return SSA_ERR_ARG;
-    if (int rc = check_msgs(b.msgs, n)) return rc;
-    if (stats_out) std::memset(stats_out, 0, 8 * sizeof(uint64_t));
-    if (flags == SSA_FLAG_SIG_FLAG_BYTE)      // verify_batch semantics: no key check to add, the screened form as it is
-        return ssa_verify_batch_screened_device(ctx, d_sigs, d_pks, d_pk_inf, d_msgs, d_msg_off, msg_stride, msg_len, n,
-                                                d_coeffs, coeff_bytes, d_status_out, d_n_fail_out);
-    HIP_TRY(hipSetDevice(ctx->device));
-    unsigned long long *d_fail;
-    if (int rc = reset_fail_counter(ctx, d_n_fail_out, &d_fail)) return rc;
-    if (n == 0) return 0;
-    ManyScreenStats st;
-    if (n <= ctx->msm_small_max) {
-        const int rc = ssa_verify_many_device(ctx, d_sigs, d_pks, d_pk_inf, d_msgs, d_msg_off, msg_stride, msg_len, n, flags,
-                                              d_status_out, (uint64_t *)d_fail);
-        if (rc == 0 && stats_out) stats_out[6] = 1;
-        return rc;
-    }
-    const size_t slice = many_screen_slice_lanes(ctx);
-    for (size_t lo = 0; lo < n; lo += slice) {      // segments never straddle two slices
-        const size_t cnt = n - lo < slice ? n - lo : slice;
-        if (int rc = screen_many_slice(ctx, b.slice(lo), cnt, d_coeffs ? d_coeffs + (size_t)coeff_bytes * lo : nullptr,
-                                       coeff_bytes, flags, nullptr, d_status_out + lo, stats_out ? &st : nullptr))
-            return rc;
-    }
-    if (int rc = screen_count(ctx, d_status_out, n, d_fail)) return rc;
-    many_screen_stats_out(st, stats_out);
-    return 0;
+    return many_screened_device(ctx, nullptr, {d_sigs, d_pks, d_pk_inf, {d_msgs, d_msg_off, msg_stride, msg_len}}, n, flags,
+                                d_coeffs, coeff_bytes, d_status_out, d_n_fail_out, stats_out, 8);
 }
 
 // ONE slice from host buffers (the staging of screen_host_one): statuses into status_out[0, n), *nf the count
 static int screen_many_host_one(ssa_ctx *ctx, const HostBatch &b, size_t n, uint32_t flags, const uint8_t *coeffs,
-                                uint8_t *status_out, uint64_t *nf, ManyScreenStats *stats, ssa_keycache *kc = nullptr) {
-    HostCall hc(ctx);
-    PipelinedInputs pin;      // its destructor drains the side streams on every error return
-    const StagedInputs s = slice_inputs(hc, pin, b, n, coeffs, true, false);
-    u8 *d_status = hc.out(ctx->st_status, status_out, n, 16);
-    unsigned long long v = 0, *d_fail = (unsigned long long *)ctx->ws_fail.p;
-    hc.copy_back(&v, d_fail, sizeof v);
-    if (int rc = hc.finish([&] {
-            if (int r = screen_many_slice(ctx, s.batch, n, s.coeffs, 32, flags,
-                                          s.hashed ? (const u64 *)ctx->ws_h.p : nullptr, d_status, stats, kc))
-                return r;
-            return screen_count(ctx, d_status, n, d_fail);
-        }))
+                                uint8_t *status_out, uint64_t *nf, CallStats *stats, ssa_keycache *kc) {
+    return status_host_one(ctx, b, n, coeffs, true, false, status_out, nf,
+                           [&](const StagedInputs &s, u8 *d_status, unsigned long long *d_fail) {
+        if (int r = screen_many_slice(ctx, s.batch, n, s.coeffs, 32, flags, s.hashed ? (const u64 *)ctx->ws_h.p : nullptr,
+                                      d_status, stats, kc))
+            return r;
+        return screen_count(ctx, d_status, n, d_fail);
+    });
+}
+
+// The slices of a host batch one after the other on the context itself, for a call whose slices share state (the key
+// cache): fn as run_host_slices_counted takes it, the counts added up into *n_fail_out.  No second set of streams.
+template <class F>
+static int host_slices_in_order(ssa_ctx *ctx, const HostBatch &b, size_t n, size_t slice, uint64_t *n_fail_out, F &&fn) {
+    uint64_t total = 0;
+    for (size_t lo = 0; lo < n; lo += slice) {
+        const size_t cnt = n - lo < slice ? n - lo : slice;
+        std::vector<uint64_t> off;
+        uint64_t nf = 0;
+        if (int rc = fn(ctx, lo, cnt, b.slice(lo, cnt, off), &nf)) return rc;
+        total += nf;
+    }
+    if (n_fail_out) *n_fail_out = total;
+    return 0;
+}
+
+// The host form of ssa_verify_many_screened (kc == nullptr, 8 statistics words) and of ssa_verify_many_cached (DESIGN.md
+// section 16: ssa_verify_many_screened with its per-key check behind a key cache, 12 words).
+static int many_screened_host(ssa_ctx *ctx, ssa_keycache *kc, const HostBatch &b, size_t n, uint32_t flags,
+                              const uint8_t *coeffs, uint8_t *status_out, uint64_t *n_fail_out, uint64_t *stats_out,
+                              int stats_words) {
+    if (flags & ~MANY_SCREEN_FLAGS) return SSA_ERR_ARG;
+    if (int rc = check_host_batch(ctx, b, n, status_out)) return rc;
+    if (kc && kc->ctx != ctx) return SSA_ERR_ARG;
+    CallStats st(stats_words);
+    st.out(stats_out);      // (still empty: the caller's words are zeroed)
+    if (flags == SSA_FLAG_SIG_FLAG_BYTE)      // verify_batch semantics: no key check to add or to cache
+        return ssa_verify_batch_screened(ctx, b.sigs, b.pks, b.pk_inf, b.msgs, b.msg_off, b.msg_stride, b.msg_len, n, coeffs,
+                                         status_out, n_fail_out);
+    if (n_fail_out) *n_fail_out = 0;
+    if (n == 0) return 0;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (n <= ctx->msm_small_max) {
+        const int rc = ssa_verify_many(ctx, b.sigs, b.pks, b.pk_inf, b.msgs, b.msg_off, b.msg_stride, b.msg_len, n, flags,
+                                       status_out, n_fail_out);
+        if (rc == 0 && stats_out) stats_out[6] = 1;
         return rc;
-    pin.done();
-    if (nf) *nf = v;
+    }
+    auto one = [&](ssa_ctx *c, size_t lo, size_t cnt, const HostBatch &s, uint64_t *nf) {
+        return screen_many_host_one(c, s, cnt, flags, coeffs ? coeffs + 32 * lo : nullptr, status_out + lo, nf,
+                                    stats_out ? &st : nullptr, kc);
+    };
+    // The one difference between the two host forms.  Every slice reads and may extend the one cache, and two streams
+    // would mutate it at once: with a cache the slices run in order on this context alone; without one they alternate
+    // between the context and its second set of streams.
+    const size_t slice = many_screen_slice_lanes(ctx);
+    const int rc = kc ? host_slices_in_order(ctx, b, n, slice, n_fail_out, one)
+                      : run_host_slices_counted(ctx, b, n, slice, n_fail_out, one);
+    if (rc) return rc;
+    st.out(stats_out);
     return 0;
 }
 
@@ -2084,117 +2101,28 @@ extern "C" int ssa_verify_many_screened(ssa_ctx *ctx, const uint8_t *sigs, const
                                         const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len,
                                         size_t n, uint32_t flags, const uint8_t *coeffs, uint8_t *status_out,
                                         uint64_t *n_fail_out, uint64_t stats_out[8]) {
-    if (flags & ~MANY_SCREEN_FLAGS) return SSA_ERR_ARG;
-    if (!ctx || (n && (!sigs || !pks || !status_out))) return SSA_ERR_ARG;
-    if (int rc = check_msgs({msgs, msg_off, msg_stride, msg_len}, n)) return rc;
-    if (int rc = check_host_offsets(msg_off, n)) return rc;
-    if (stats_out) std::memset(stats_out, 0, 8 * sizeof(uint64_t));
-    if (flags == SSA_FLAG_SIG_FLAG_BYTE)
-        return ssa_verify_batch_screened(ctx, sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len, n, coeffs, status_out,
-                                         n_fail_out);
-    if (n_fail_out) *n_fail_out = 0;
-    if (n == 0) return 0;
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (n <= ctx->msm_small_max) {
-        const int rc = ssa_verify_many(ctx, sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len, n, flags, status_out,
-                                       n_fail_out);
-        if (rc == 0 && stats_out) stats_out[6] = 1;
-        return rc;
-    }
-    const HostBatch b{sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len};
-    ManyScreenStats st;
-    const int rc = run_host_slices_counted(ctx, b, n, many_screen_slice_lanes(ctx), n_fail_out,
-                                           [&](ssa_ctx *c, size_t lo, size_t cnt, const HostBatch &s, uint64_t *nf) {
-                                               return screen_many_host_one(c, s, cnt, flags, coeffs ? coeffs + 32 * lo : nullptr,
-                                                                           status_out + lo, nf, stats_out ? &st : nullptr);
-                                           });
-    if (rc) return rc;
-    many_screen_stats_out(st, stats_out);
-    return 0;
+    return many_screened_host(ctx, nullptr, {sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len}, n, flags, coeffs,
+                              status_out, n_fail_out, stats_out, 8);
 }
 
 // ------------------------------------------------------------------------------------------------
 // ssa_verify_many_cached: ssa_verify_many_screened with its per-key check behind a key cache.
-// The slices of one call run in order on the context's stream in BOTH forms: every slice reads and may extend the one
-// cache, so the host form does not alternate its slices between the context and a second set of streams.
-static void many_cached_stats_out(const ManyScreenStats &st, uint64_t stats_out[12]) {
-    if (stats_out)
-        for (int k = 0; k < 12; k++) stats_out[k] = st.v[k];
-}
-
+// The slices of one call run in order on the context's stream in BOTH forms (many_screened_host has the reason).
 extern "C" int ssa_verify_many_cached_device(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *d_sigs, const uint8_t *d_pks,
                                              const uint8_t *d_pk_inf, const uint8_t *d_msgs, const uint64_t *d_msg_off,
                                              size_t msg_stride, size_t msg_len, size_t n, uint32_t flags,
                                              const uint8_t *d_coeffs, uint32_t coeff_bytes, uint8_t *d_status_out,
                                              uint64_t *d_n_fail_out, uint64_t stats_out[12]) {
-    if (flags & ~MANY_SCREEN_FLAGS) return SSA_ERR_ARG;
-    const DevBatch b{d_sigs, d_pks, d_pk_inf, {d_msgs, d_msg_off, msg_stride, msg_len}};
-    if (!ctx || !kc || kc->ctx != ctx || (n && (!d_sigs || !d_pks || !d_status_out))) return SSA_ERR_ARG;
-    if (d_coeffs && (coeff_bytes == 0 || coeff_bytes > 32)) return SSA_ERR_ARG;
-    if (int rc = check_msgs(b.msgs, n)) return rc;
-    if (stats_out) std::memset(stats_out, 0, 12 * sizeof(uint64_t));
-    if (flags == SSA_FLAG_SIG_FLAG_BYTE)      // verify_batch semantics: no key check, so nothing to cache
-        return ssa_verify_batch_screened_device(ctx, d_sigs, d_pks, d_pk_inf, d_msgs, d_msg_off, msg_stride, msg_len, n,
-                                                d_coeffs, coeff_bytes, d_status_out, d_n_fail_out);
-    HIP_TRY(hipSetDevice(ctx->device));
-    unsigned long long *d_fail;
-    if (int rc = reset_fail_counter(ctx, d_n_fail_out, &d_fail)) return rc;
-    if (n == 0) return 0;
-    if (n <= ctx->msm_small_max) {
-        const int rc = ssa_verify_many_device(ctx, d_sigs, d_pks, d_pk_inf, d_msgs, d_msg_off, msg_stride, msg_len, n, flags,
-                                              d_status_out, (uint64_t *)d_fail);
-        if (rc == 0 && stats_out) stats_out[6] = 1;
-        return rc;
-    }
-    ManyScreenStats st;
-    const size_t slice = many_screen_slice_lanes(ctx);
-    for (size_t lo = 0; lo < n; lo += slice) {
-        const size_t cnt = n - lo < slice ? n - lo : slice;
-        if (int rc = screen_many_slice(ctx, b.slice(lo), cnt, d_coeffs ? d_coeffs + (size_t)coeff_bytes * lo : nullptr,
-                                       coeff_bytes, flags, nullptr, d_status_out + lo, stats_out ? &st : nullptr, kc))
-            return rc;
-    }
-    if (int rc = screen_count(ctx, d_status_out, n, d_fail)) return rc;
-    many_cached_stats_out(st, stats_out);
-    return 0;
+    if (!kc) return SSA_ERR_ARG;
+    return many_screened_device(ctx, kc, {d_sigs, d_pks, d_pk_inf, {d_msgs, d_msg_off, msg_stride, msg_len}}, n, flags,
+                                d_coeffs, coeff_bytes, d_status_out, d_n_fail_out, stats_out, 12);
 }
 
 extern "C" int ssa_verify_many_cached(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *sigs, const uint8_t *pks,
                                       const uint8_t *pk_inf, const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride,
                                       size_t msg_len, size_t n, uint32_t flags, const uint8_t *coeffs, uint8_t *status_out,
                                       uint64_t *n_fail_out, uint64_t stats_out[12]) {
-    if (flags & ~MANY_SCREEN_FLAGS) return SSA_ERR_ARG;
-    if (!ctx || !kc || kc->ctx != ctx || (n && (!sigs || !pks || !status_out))) return SSA_ERR_ARG;
-    if (int rc = check_msgs({msgs, msg_off, msg_stride, msg_len}, n)) return rc;
-    if (int rc = check_host_offsets(msg_off, n)) return rc;
-    if (stats_out) std::memset(stats_out, 0, 12 * sizeof(uint64_t));
-    if (flags == SSA_FLAG_SIG_FLAG_BYTE)
-        return ssa_verify_batch_screened(ctx, sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len, n, coeffs, status_out,
-                                         n_fail_out);
-    if (n_fail_out) *n_fail_out = 0;
-    if (n == 0) return 0;
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (n <= ctx->msm_small_max) {
-        const int rc = ssa_verify_many(ctx, sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len, n, flags, status_out,
-                                       n_fail_out);
-        if (rc == 0 && stats_out) stats_out[6] = 1;
-        return rc;
-    }
-    const HostBatch b{sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len};
-    ManyScreenStats st;
-    // slice after slice on this context alone: two streams would mutate one cache
-    const size_t slice = many_screen_slice_lanes(ctx);
-    uint64_t total = 0;
-    for (size_t lo = 0; lo < n; lo += slice) {
-        const size_t cnt = n - lo < slice ? n - lo : slice;
-        std::vector<uint64_t> off;
-        uint64_t nf = 0;
-        if (int rc = screen_many_host_one(ctx, b.slice(lo, cnt, off), cnt, flags, coeffs ? coeffs + 32 * lo : nullptr,
-                                          status_out + lo, &nf, stats_out ? &st : nullptr, kc))
-            return rc;
-        total += nf;
-    }
-    if (n_fail_out) *n_fail_out = total;
-    many_cached_stats_out(st, stats_out);
-    return 0;
+    if (!kc) return SSA_ERR_ARG;
+    return many_screened_host(ctx, kc, {sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len}, n, flags, coeffs, status_out,
+                              n_fail_out, stats_out, 12);
 }

@@ -516,78 +516,6 @@ class SignerSet {
     ssa_signer_set *ss_ = nullptr;
 };
 
-// verify_batch, src/batch.rs:31-50.
-//   msm = false: AND of exact per-signature checks (`rng` unused; DESIGN.md lists the divergence classes)
-//   msm = true : the reference's own algorithm on the GPU (random linear combination + 2n-point MSM), the
-//                coefficients are Scalar::random(rng) per signature (src/batch.rs:75-78); rng == nullptr lets the
-//                library draw them (ChaCha20 keyed with getrandom(2))
-inline Result verify_batch(Context &cx, const std::vector<Signature> &signatures,
-                           const std::vector<PublicKey> &public_keys,
-                           const std::vector<std::pair<const uint8_t *, size_t>> &messages, Rng rng = nullptr,
-                           bool msm = false) {
-    if (signatures.size() != public_keys.size())
-        throw Panic("We should have the same number of signatures than public keys");  // src/batch.rs:37-40
-    if (messages.size() != public_keys.size())
-        throw Panic("We should have the same number of messages than public keys");    // src/batch.rs:41-44
-    const size_t n = signatures.size();
-    if (n == 0) return std::nullopt;
-    std::vector<uint8_t> sigs(n * SIGNATURE_LENGTH), pks(n * AFFINE_PUBLIC_KEY_LENGTH), inf(n), flat;
-    std::vector<uint64_t> off(n + 1, 0);
-    for (size_t i = 0; i < n; i++) {
-        std::memcpy(&sigs[i * SIGNATURE_LENGTH], signatures[i].bytes.data(), SIGNATURE_LENGTH);
-        std::memcpy(&pks[i * AFFINE_PUBLIC_KEY_LENGTH], public_keys[i].affine.data(), AFFINE_PUBLIC_KEY_LENGTH);
-        inf[i] = public_keys[i].is_identity ? 1 : 0;
-        flat.insert(flat.end(), messages[i].first, messages[i].first + messages[i].second);
-        off[i + 1] = flat.size();
-    }
-    flat.push_back(0);
-    if (msm) {
-        std::vector<uint8_t> coeffs;
-        if (rng) {
-            coeffs.resize(n * SCALAR_LENGTH);
-            for (size_t i = 0; i < n; i++) KeyPair::random_scalar(rng, &coeffs[i * SCALAR_LENGTH]);
-        }
-        return status_to_result(ssa_verify_batch_msm(cx.get(), sigs.data(), pks.data(), inf.data(), flat.data(),
-                                                     off.data(), 0, 0, n, rng ? coeffs.data() : nullptr));
-    }
-    return status_to_result(
-        ssa_verify_batch(cx.get(), sigs.data(), pks.data(), inf.data(), flat.data(), off.data(), 0, 0, n, 0));
-}
-
-// verify_batch semantics per signature, screened on the GPU (DESIGN.md section 13): statuses 0 (Ok), 2 (invalid
-// signature) or 3 (malformed: the reference would panic), with the same coefficients as verify_batch(msm = true).  A
-// rejected lane is reported except with the probability the header states (random combination of its segment vanishes).
-inline std::vector<uint8_t> verify_batch_statuses(Context &cx, const std::vector<Signature> &signatures,
-                                                  const std::vector<PublicKey> &public_keys,
-                                                  const std::vector<std::pair<const uint8_t *, size_t>> &messages,
-                                                  Rng rng = nullptr) {
-    if (signatures.size() != public_keys.size())
-        throw Panic("We should have the same number of signatures than public keys");
-    if (messages.size() != public_keys.size())
-        throw Panic("We should have the same number of messages than public keys");
-    const size_t n = signatures.size();
-    std::vector<uint8_t> status(n, 0);
-    if (n == 0) return status;
-    std::vector<uint8_t> sigs(n * SIGNATURE_LENGTH), pks(n * AFFINE_PUBLIC_KEY_LENGTH), inf(n), flat, coeffs;
-    std::vector<uint64_t> off(n + 1, 0);
-    for (size_t i = 0; i < n; i++) {
-        std::memcpy(&sigs[i * SIGNATURE_LENGTH], signatures[i].bytes.data(), SIGNATURE_LENGTH);
-        std::memcpy(&pks[i * AFFINE_PUBLIC_KEY_LENGTH], public_keys[i].affine.data(), AFFINE_PUBLIC_KEY_LENGTH);
-        inf[i] = public_keys[i].is_identity ? 1 : 0;
-        flat.insert(flat.end(), messages[i].first, messages[i].first + messages[i].second);
-        off[i + 1] = flat.size();
-    }
-    flat.push_back(0);
-    if (rng) {
-        coeffs.resize(n * SCALAR_LENGTH);
-        for (size_t i = 0; i < n; i++) KeyPair::random_scalar(rng, &coeffs[i * SCALAR_LENGTH]);
-    }
-    const int rc = ssa_verify_batch_screened(cx.get(), sigs.data(), pks.data(), inf.data(), flat.data(), off.data(), 0, 0,
-                                             n, rng ? coeffs.data() : nullptr, status.data(), nullptr);
-    if (rc != 0) throw std::runtime_error(std::string("ssa_verify_batch_screened: ") + ssa_strerror(rc));
-    return status;
-}
-
 // (signature, public key, message) triples as the batch entry points take them: 81-byte signatures, 96-byte affine keys,
 // identity flags, the messages back to back with their n + 1 offsets.  The length checks of the reference's verify_batch.
 struct PackedTriples {
@@ -617,6 +545,61 @@ inline PackedTriples pack_triples(const std::vector<Signature> &signatures, cons
     return t;
 }
 
+// The tail the *_statuses functions share: one status byte per triple (none for an empty slice), Scalar::random(rng)
+// coefficients when there is an rng, call(statuses, coefficients or nullptr), and an ABI error thrown under `what`.
+template <class F>
+inline std::vector<uint8_t> statuses_of(size_t n, Rng rng, const char *what, F &&call) {
+    std::vector<uint8_t> status(n, 0), coeffs;
+    if (n == 0) return status;
+    if (rng) {
+        coeffs.resize(n * SCALAR_LENGTH);
+        for (size_t i = 0; i < n; i++) KeyPair::random_scalar(rng, &coeffs[i * SCALAR_LENGTH]);
+    }
+    const int rc = call(status.data(), rng ? coeffs.data() : nullptr);
+    if (rc != 0) throw std::runtime_error(std::string(what) + ": " + ssa_strerror(rc));
+    return status;
+}
+
+// verify_batch, src/batch.rs:31-50.
+//   msm = false: AND of exact per-signature checks (`rng` unused; DESIGN.md lists the divergence classes)
+//   msm = true : the reference's own algorithm on the GPU (random linear combination + 2n-point MSM), the
+//                coefficients are Scalar::random(rng) per signature (src/batch.rs:75-78); rng == nullptr lets the
+//                library draw them (ChaCha20 keyed with getrandom(2))
+inline Result verify_batch(Context &cx, const std::vector<Signature> &signatures,
+                           const std::vector<PublicKey> &public_keys,
+                           const std::vector<std::pair<const uint8_t *, size_t>> &messages, Rng rng = nullptr,
+                           bool msm = false) {
+    const PackedTriples t = pack_triples(signatures, public_keys, messages);     // (its length checks: src/batch.rs:37-44)
+    const size_t n = signatures.size();
+    if (n == 0) return std::nullopt;
+    if (msm) {
+        std::vector<uint8_t> coeffs;
+        if (rng) {
+            coeffs.resize(n * SCALAR_LENGTH);
+            for (size_t i = 0; i < n; i++) KeyPair::random_scalar(rng, &coeffs[i * SCALAR_LENGTH]);
+        }
+        return status_to_result(ssa_verify_batch_msm(cx.get(), t.sigs.data(), t.pks.data(), t.inf.data(), t.flat.data(),
+                                                     t.off.data(), 0, 0, n, rng ? coeffs.data() : nullptr));
+    }
+    return status_to_result(
+        ssa_verify_batch(cx.get(), t.sigs.data(), t.pks.data(), t.inf.data(), t.flat.data(), t.off.data(), 0, 0, n, 0));
+}
+
+// verify_batch semantics per signature, screened on the GPU (DESIGN.md section 13): statuses 0 (Ok), 2 (invalid
+// signature) or 3 (malformed: the reference would panic), with the same coefficients as verify_batch(msm = true).  A
+// rejected lane is reported except with the probability the header states (random combination of its segment vanishes).
+inline std::vector<uint8_t> verify_batch_statuses(Context &cx, const std::vector<Signature> &signatures,
+                                                  const std::vector<PublicKey> &public_keys,
+                                                  const std::vector<std::pair<const uint8_t *, size_t>> &messages,
+                                                  Rng rng = nullptr) {
+    const PackedTriples t = pack_triples(signatures, public_keys, messages);
+    const size_t n = signatures.size();
+    return statuses_of(n, rng, "ssa_verify_batch_screened", [&](uint8_t *status, const uint8_t *coeffs) {
+        return ssa_verify_batch_screened(cx.get(), t.sigs.data(), t.pks.data(), t.inf.data(), t.flat.data(), t.off.data(), 0,
+                                         0, n, coeffs, status, nullptr);
+    });
+}
+
 // Signature::verify (src/signature.rs:181-205) over a slice of signatures in which public keys repeat: one status per
 // signature (0 Ok, 1 InvalidPublicKey, 2 InvalidSignature, 3 malformed: the reference would panic), the same vector as n
 // single calls, with each DISTINCT key's subgroup check and table run once on the GPU.
@@ -626,12 +609,10 @@ inline std::vector<uint8_t> verify_many_statuses(Context &cx, const std::vector<
                                                  uint64_t *stats_out = nullptr) {
     const PackedTriples t = pack_triples(signatures, public_keys, messages);
     const size_t n = signatures.size();
-    std::vector<uint8_t> status(n, 0);
-    if (n == 0) return status;
-    const int rc = ssa_verify_many_dedup(cx.get(), t.sigs.data(), t.pks.data(), t.inf.data(), t.flat.data(), t.off.data(),
-                                         0, 0, n, SSA_FLAG_CHECK_TORSION, status.data(), nullptr, stats_out);
-    if (rc != 0) throw std::runtime_error(std::string("ssa_verify_many_dedup: ") + ssa_strerror(rc));
-    return status;
+    return statuses_of(n, nullptr, "ssa_verify_many_dedup", [&](uint8_t *status, const uint8_t *) {
+        return ssa_verify_many_dedup(cx.get(), t.sigs.data(), t.pks.data(), t.inf.data(), t.flat.data(), t.off.data(), 0, 0,
+                                     n, SSA_FLAG_CHECK_TORSION, status, nullptr, stats_out);
+    });
 }
 
 // The same vector as verify_many_statuses at about the price of one MSM for an honest slice: each
@@ -644,17 +625,10 @@ inline std::vector<uint8_t> verify_many_screened_statuses(Context &cx, const std
                                                           Rng rng = nullptr, uint64_t *stats_out = nullptr) {
     const PackedTriples t = pack_triples(signatures, public_keys, messages);
     const size_t n = signatures.size();
-    std::vector<uint8_t> status(n, 0), coeffs;
-    if (n == 0) return status;
-    if (rng) {
-        coeffs.resize(n * SCALAR_LENGTH);
-        for (size_t i = 0; i < n; i++) KeyPair::random_scalar(rng, &coeffs[i * SCALAR_LENGTH]);
-    }
-    const int rc = ssa_verify_many_screened(cx.get(), t.sigs.data(), t.pks.data(), t.inf.data(), t.flat.data(),
-                                            t.off.data(), 0, 0, n, SSA_FLAG_CHECK_TORSION, rng ? coeffs.data() : nullptr,
-                                            status.data(), nullptr, stats_out);
-    if (rc != 0) throw std::runtime_error(std::string("ssa_verify_many_screened: ") + ssa_strerror(rc));
-    return status;
+    return statuses_of(n, rng, "ssa_verify_many_screened", [&](uint8_t *status, const uint8_t *coeffs) {
+        return ssa_verify_many_screened(cx.get(), t.sigs.data(), t.pks.data(), t.inf.data(), t.flat.data(), t.off.data(), 0,
+                                        0, n, SSA_FLAG_CHECK_TORSION, coeffs, status, nullptr, stats_out);
+    });
 }
 
 // A key cache on the device (ssa_keycache_create): the checks and tables of the public keys that
@@ -695,17 +669,10 @@ inline std::vector<uint8_t> verify_many_cached_statuses(Context &cx, KeyCache &c
                                                         Rng rng = nullptr, uint64_t *stats_out = nullptr) {
     const PackedTriples t = pack_triples(signatures, public_keys, messages);
     const size_t n = signatures.size();
-    std::vector<uint8_t> status(n, 0), coeffs;
-    if (n == 0) return status;
-    if (rng) {
-        coeffs.resize(n * SCALAR_LENGTH);
-        for (size_t i = 0; i < n; i++) KeyPair::random_scalar(rng, &coeffs[i * SCALAR_LENGTH]);
-    }
-    const int rc = ssa_verify_many_cached(cx.get(), cache.get(), t.sigs.data(), t.pks.data(), t.inf.data(), t.flat.data(),
-                                          t.off.data(), 0, 0, n, SSA_FLAG_CHECK_TORSION, rng ? coeffs.data() : nullptr,
-                                          status.data(), nullptr, stats_out);
-    if (rc != 0) throw std::runtime_error(std::string("ssa_verify_many_cached: ") + ssa_strerror(rc));
-    return status;
+    return statuses_of(n, rng, "ssa_verify_many_cached", [&](uint8_t *status, const uint8_t *coeffs) {
+        return ssa_verify_many_cached(cx.get(), cache.get(), t.sigs.data(), t.pks.data(), t.inf.data(), t.flat.data(),
+                                      t.off.data(), 0, 0, n, SSA_FLAG_CHECK_TORSION, coeffs, status, nullptr, stats_out);
+    });
 }
 
 // ---- hierarchical deterministic key derivation (src/derivation.rs) ---------------------------------------------------

@@ -191,20 +191,35 @@ def _function_body(text, signature):
 
 
 def test_the_host_form_stays_on_the_context_and_its_stream():
-    """Two streams would mutate one cache: the host form runs its slices itself, in order, and never asks for the
-    context's second set of streams (directly, or through the helpers that alternate slices)."""
+    """Two streams would mutate one cache: with a cache the host form runs its slices in order on the context, and no
+    function on that path asks for the context's second set of streams (directly, or through the helpers that alternate
+    slices).  The one place that chooses between the two ways to run the slices sends a cache to the in-order loop."""
     msm = open(os.path.join(CSRC, "ssa_msm.hip")).read()
-    body = _function_body(msm, 'extern "C" int ssa_verify_many_cached(')
-    assert "screen_many_host_one(ctx," in body
-    for name in ("ssa_internal_twin", "run_host_slices", "std::thread", "->twin"):
-        assert name not in body, name
-    one = _function_body(msm, "static int screen_many_host_one(")
-    for name in ("ssa_internal_twin", "run_host_slices", "std::thread", "->twin"):
-        assert name not in one, name
-    # the slice function is shared with ssa_verify_many_screened, not copied
+    ctx_hpp = open(os.path.join(CSRC, "ssa_ctx.hpp")).read()
+    names = ("ssa_internal_twin", "run_host_slices", "std::thread", "->twin")
+    entry = _function_body(msm, 'extern "C" int ssa_verify_many_cached(')
+    assert "many_screened_host(ctx, kc," in entry
+    # every function the cached host form runs through, the shared one-slice shell included
+    for text, signature in ((msm, 'extern "C" int ssa_verify_many_cached('), (msm, "static int host_slices_in_order("),
+                            (msm, "static int screen_many_host_one("), (ctx_hpp, "static int status_host_one(")):
+        body = _function_body(text, signature)
+        for name in names:
+            assert name not in body, (signature, name)
+    assert "screen_many_host_one(c," in _function_body(msm, "static int many_screened_host(")
+    assert "status_host_one(ctx," in _function_body(msm, "static int screen_many_host_one(")
+    # the choice: the alternating helper is named once, in the arm WITHOUT a cache, and nothing else of the second set of
+    # streams is; the in-order loop and the alternating helper are two functions
+    choice = _function_body(msm, "static int many_screened_host(")
+    assert re.search(r"=\s*kc\s*\?\s*host_slices_in_order\(ctx,[^;?:]*\)\s*:\s*run_host_slices_counted\(ctx,[^;?:]*\);", choice)
+    assert choice.count("run_host_slices") == 1 and choice.count("host_slices_in_order(") == 1
+    for name in ("ssa_internal_twin", "std::thread", "->twin"):
+        assert name not in choice, name
+    assert msm.count("static int host_slices_in_order(") == 1
+    # the slice function is shared with ssa_verify_many_screened, not copied, and the device path with a cache reaches it
     assert msm.count("static int screen_many_slice(") == 1
     dev = _function_body(msm, 'extern "C" int ssa_verify_many_cached_device(')
-    assert "screen_many_slice(ctx," in dev
+    assert "many_screened_device(ctx, kc," in dev
+    assert re.search(r"screen_many_slice\(ctx,[^;]*\bkc\)", _function_body(msm, "static int many_screened_device("))
 
 
 def _asm():
