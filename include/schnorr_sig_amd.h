@@ -604,6 +604,47 @@ int ssa_verify_many_cached_device(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t 
                                   uint32_t coeff_bytes, uint8_t *d_status_out, uint64_t *d_n_fail_out,
                                   uint64_t stats_out[12]);
 
+/* Exact self-check of the per-key tables of a key set or a key cache, on the owning context's
+ * stream; returns when it is done.  ssa_ctx_selfcheck covers the tables for G; these two cover what lives as long as a
+ * validator set does: per key the 4 KB table of sixteen multiples, the status byte and, in comb mode, the 100 MB comb.
+ * The root of trust of a row is what it was built from: its 96 stored key bytes and its pk_inf boolean (a key set keeps
+ * both from its creation on).  What "a key passes" means depends on its stored status:
+ *   0, finite key  the bytes are canonical and on the curve; entry 1P is the key bit for bit, 2P the tangent of 1P, mP
+ *                  (3 <= m <= 16) the chord (m-1)P + P (section 11's two equations, no inversion), and the second line of
+ *                  every entry is (x, -y).  A clean pass proves every entry exact.
+ *   0, identity    all sixteen entries are the (0, 0) sentinel in both lines.
+ *   1              the table is built again into scratch and the words the kernels read are compared (no [q]P).
+ *   3              no kernel reads the table; the status itself is checked, always: the bytes must fail the limb or the
+ *                  curve test.  Any other status byte fails.
+ * Table words are compared as residues mod p (the builder stores loose limbs and every kernel reads them as such); the
+ * key bytes, and entry 1P against them, bit for bit.  Words 12-15 and 28-31 of an entry are read by no kernel and are
+ * not checked.  WITHOUT SSA_KEYCHECK_DEEP A STATUS BYTE FLIPPED BETWEEN 0 AND 1 IS NOT DETECTED: the table of such a key
+ * is right.  DEEP recomputes [q]P from the proven table of every key of status 0 or 1 whose table passed -- exactly what
+ * ssa_k_keyset_build computes -- and compares with the stored byte; it costs about one key check per key.
+ * Key sets in comb mode: the comb of every key of status 0 is checked like the comb for G (16 windows of 16 bits, no
+ * header word, row (0, 1) = the key; an identity key's comb is all sentinels).  COMBS OF KEYS OF STATUS 1 OR 3 ARE NOT
+ * CHECKED; out[6] counts them.
+ *   out[0] keys checked (m / keys held)              out[4] comb rows checked (key sets in comb mode)
+ *   out[1] keys that fail (before any repair)        out[5] keys checked by rebuild-and-compare (status 1)
+ *   out[2] first failing key (UINT64_MAX: none)      out[6] keys whose comb was skipped
+ *   out[3] ladder-table entries checked by relations out[7] rows rebuilt (SSA_KEYCHECK_REPAIR)
+ * bad_out (key sets; host, m bytes, optional) receives 1 per failing key, 0 otherwise: a key set is indexed by the
+ * caller, who has to hand those keys in again (a new key set); it has no repair, because rebuilding position i from
+ * device bytes that may themselves be what flipped would answer for another key under the caller's index.
+ * SSA_KEYCHECK_REPAIR (key caches only) rebuilds every failing row in place from its stored bytes and pk_inf with
+ * ssa_k_keyset_build and checks again.  That is safe in a cache even when the key bytes were what flipped: the row becomes
+ * a correct row for the bytes it now holds, look-ups compare all 97 bytes, so the original key misses and is inserted
+ * again, and the status vector stays byte for byte that of ssa_verify_many_screened.
+ * Returns SSA_OK when clean, or clean after repair (an empty cache: SSA_OK, all zero but out[2]); SSA_ERR_TABLE when a
+ * key failed and was not repaired, or still fails after it; SSA_ERR_ARG for a NULL or orphaned object, an unknown flag
+ * bit, REPAIR on a key set, or out == NULL; SSA_ERR_HIP as usual.  Both only read the object, but for repair.  Their
+ * workspaces belong to the context: from the second call on nothing is allocated.  Timing keys: ssa_k_keytab_check,
+ * ssa_k_keytab_rebuild, ssa_k_keytab_deep, ssa_k_keycomb_check, keycheck_repair (and ssa_k_keyset_build in a repair). */
+#define SSA_KEYCHECK_DEEP   1u  /* also recompute [q]P per key from the proven table and compare with the stored status */
+#define SSA_KEYCHECK_REPAIR 2u  /* key caches only: rebuild failing rows in place from their stored key bytes */
+int ssa_keyset_selfcheck(ssa_keyset *ks, uint32_t flags, uint8_t *bad_out, uint64_t out[8]);
+int ssa_keycache_selfcheck(ssa_keycache *kc, uint32_t flags, uint64_t out[8]);
+
 /* ---- signer sets: many signatures by few signers (the signing twin of the key set) ---------------------------
  * A signer set holds m key pairs on the device: the secret key, the 96-byte affine public key, the 49-byte compressed
  * key and a per-key status.  Signature i is then KeyPair::sign (src/signature.rs:114-129) -- or, with
@@ -778,6 +819,16 @@ int ssa_debug_fault_after_chunk(ssa_ctx *ctx, int chunk);
 int ssa_debug_table_read(ssa_ctx *ctx, int which, uint64_t first_row, uint64_t n, uint64_t *rows_out);
 int ssa_debug_table_xor(ssa_ctx *ctx, int which, uint64_t row, uint32_t word, uint64_t mask);
 int ssa_debug_corrupt_table_builds(int n);
+/* key-table self-check tests: one key of a key set or of a key cache (exactly one of ks, kc non-NULL; key < m / keys
+ * held).  what: 0 the ladder table (512 words), 1 the status byte, 2 the key bytes (12 words), 3 the pk_inf byte, 4 the
+ * key's comb (key sets in comb mode: 12 words per row, word = 12 row + word of the row).  Anything outside the object is
+ * SSA_ERR_ARG, nothing is read or written out of bounds.
+ *   ssa_debug_keytab_xor   XORs `mask` into word `word` ON THE DEVICE (a byte target: word 0, mask < 256).  Afterwards
+ *                          only the self-check, its repair and the destroy call may run on the object.
+ *   ssa_debug_keytab_read  copies the target to words_out: 512 words, 12 words, one word holding the byte, or (what 4)
+ *                          rows (0, 0) and (0, 1) of the comb, 24 words. */
+int ssa_debug_keytab_xor(ssa_keyset *ks, ssa_keycache *kc, int what, uint64_t key, uint32_t word, uint64_t mask);
+int ssa_debug_keytab_read(ssa_keyset *ks, ssa_keycache *kc, int what, uint64_t key, uint64_t *words_out);
 /* host logic of ssa_k_verify's end game, no context and no device needed: the launch plan for n lanes when `waves`
  * waves are resident (pieces / gens / uniform / min_main: what SSA_TAIL_PIECES, _GENS, _UNIFORM, _MIN_MAIN set).
  * out: number of pieces (0: no end game), 64-lane tail groups, ordinary workgroups, workgroups of the grid, the eight

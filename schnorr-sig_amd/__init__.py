@@ -234,6 +234,10 @@ def _load():
         "ssa_debug_table_read": (i32, [vp, i32, C.c_uint64, C.c_uint64, vp]),
         "ssa_debug_table_xor": (i32, [vp, i32, C.c_uint64, u32, C.c_uint64]),
         "ssa_debug_corrupt_table_builds": (i32, [i32]),
+        "ssa_keyset_selfcheck": (i32, [vp, u32, vp, u64p]),
+        "ssa_keycache_selfcheck": (i32, [vp, u32, u64p]),
+        "ssa_debug_keytab_xor": (i32, [vp, vp, i32, C.c_uint64, u32, C.c_uint64]),
+        "ssa_debug_keytab_read": (i32, [vp, vp, i32, C.c_uint64, vp]),
         "ssa_keygen_sign_many_rng": (i32, [vp, vp, vp, vp, sz, sz, sz, u32, vp, vp]),
         "ssa_keygen_sign_many_rng_device": (i32, [vp, vp, vp, vp, sz, sz, sz, u32, vp, vp]),
         "ssa_sign_many_indexed_rng": (i32, [vp, vp, vp, vp, vp, sz, sz, sz, u32, vp]),
@@ -1002,7 +1006,46 @@ def debug_corrupt_table_builds(n):
     _check(_lib.ssa_debug_corrupt_table_builds(int(n)), "ssa_debug_corrupt_table_builds")
 
 
-class KeySet:
+KEYCHECK_DEEP, KEYCHECK_REPAIR = 1, 2      # SSA_KEYCHECK_*
+KEYCHECK_FIELDS = ("keys_checked", "keys_bad", "first_bad_key", "ladder_entries_checked", "comb_rows_checked",
+                   "keys_rebuilt_and_compared", "combs_skipped", "rows_repaired")
+# `what` of ssa_debug_keytab_xor / _read: the target and the words a read returns
+KEYTAB_LADDER, KEYTAB_STATUS, KEYTAB_KEY, KEYTAB_PK_INF, KEYTAB_COMB = 0, 1, 2, 3, 4
+_KEYTAB_READ_WORDS = {KEYTAB_LADDER: 512, KEYTAB_STATUS: 1, KEYTAB_KEY: 12, KEYTAB_PK_INF: 1, KEYTAB_COMB: 24}
+
+
+def _keycheck_result(rc, out, what):
+    """the eight out[] fields by name plus ok; failing keys are a result (ok False), not an exception"""
+    if rc != ERR_TABLE:
+        _check(rc, what)
+    res = dict(zip(KEYCHECK_FIELDS, (int(v) for v in out)))
+    res["ok"] = rc == OK
+    return res
+
+
+class _KeyTables:
+    """what KeySet and KeyCache share: the self-check of their per-key tables and its test hooks"""
+
+    def _pair(self):
+        """(key set handle, key cache handle): exactly one is set"""
+        raise NotImplementedError
+
+    def debug_keytab_xor(self, what, key, word, mask):
+        """tests: XOR `mask` into one word (or the one byte) of a key's row ON THE DEVICE.  Only selfcheck, its repair and
+        close may run on the object afterwards."""
+        ks, kc = self._pair()
+        _check(_lib.ssa_debug_keytab_xor(ks, kc, int(what), int(key), int(word), C.c_uint64(int(mask))),
+               "ssa_debug_keytab_xor")
+
+    def debug_keytab_read(self, what, key):
+        """tests: a key's ladder table (512 words), status byte, key words (12), pk_inf byte or first two comb rows"""
+        ks, kc = self._pair()
+        out = np.zeros(_KEYTAB_READ_WORDS[int(what)], dtype=np.uint64)
+        _check(_lib.ssa_debug_keytab_read(ks, kc, int(what), int(key), _ptr(out)), "ssa_debug_keytab_read")
+        return out
+
+
+class KeySet(_KeyTables):
     """ssa_keyset handle tied to its Engine: the engine cannot be collected before the key set, and the handle is
     destroyed exactly once (close(), or when the object goes away)."""
 
@@ -1010,6 +1053,20 @@ class KeySet:
         self.engine = engine      # keeps the context alive
         self.handle = handle
         self.m = int(m)
+
+    def _pair(self):
+        return self.handle, None
+
+    def selfcheck(self, deep=False):
+        """ssa_keyset_selfcheck: the exact check of every key's ladder table, status and (comb mode) comb against the
+        stored key bytes.  deep=True also recomputes [q]P per key: without it a status flipped between 0 and 1 is not
+        seen.  -> the KEYCHECK_FIELDS by name, ok, and bad: a uint8[m] with 1 per failing key (hand those in again)."""
+        out = (C.c_uint64 * 8)()
+        bad = np.zeros(self.m, dtype=np.uint8)
+        rc = _lib.ssa_keyset_selfcheck(self.handle, KEYCHECK_DEEP if deep else 0, _ptr(bad), out)
+        res = _keycheck_result(rc, out, "ssa_keyset_selfcheck")
+        res["bad"] = bad
+        return res
 
     def close(self):
         if self.handle:
@@ -1023,7 +1080,7 @@ class KeySet:
             pass
 
 
-class KeyCache:
+class KeyCache(_KeyTables):
     """ssa_keycache handle (Engine.keycache_create): checked public keys, their statuses and tables, kept on the device
     across slices and calls of verify_many_cached.  Tied to its Engine like KeySet; destroyed exactly once (close(), the
     end of a `with` block, or when the object goes away)."""
@@ -1037,6 +1094,18 @@ class KeyCache:
         out = (C.c_uint64 * 4)()
         _check(_lib.ssa_keycache_info(self.handle, out), "ssa_keycache_info")
         return {"capacity": int(out[0]), "held": int(out[1]), "clears": int(out[2]), "device_bytes": int(out[3])}
+
+    def _pair(self):
+        return None, self.handle
+
+    def selfcheck(self, deep=False, repair=False):
+        """ssa_keycache_selfcheck: the exact check of every held row (ladder table and status against the row's stored
+        key bytes).  deep=True also recomputes [q]P per key; repair=True rebuilds failing rows in place from their
+        stored bytes and checks again (ok is then True when the cache is clean afterwards).  -> the KEYCHECK_FIELDS by
+        name plus ok."""
+        out = (C.c_uint64 * 8)()
+        flags = (KEYCHECK_DEEP if deep else 0) | (KEYCHECK_REPAIR if repair else 0)
+        return _keycheck_result(_lib.ssa_keycache_selfcheck(self.handle, flags, out), out, "ssa_keycache_selfcheck")
 
     def clear(self):
         """forget every key: the next call is cold"""

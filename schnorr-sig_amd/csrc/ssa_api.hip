@@ -957,6 +957,16 @@ extern "C" int ssa_verify_keyed_many(ssa_ctx *ctx, const uint8_t *keyed, const u
 
 // ------------------------------------------------------------------ keyed context
 
+// ssa_k_keyset_build over m keys on the context's stream (every caller's launch; the key-table repair of
+// ssa_keycheck.hpp lives in another translation unit)
+int ssa_internal_keyset_build(ssa_ctx *ctx, const uint8_t *d_pks, const uint8_t *d_pk_inf, size_t m, uint64_t *d_tab,
+                              uint8_t *d_status) {
+    return timed_launch(ctx, "ssa_k_keyset_build", [&] {
+        hipLaunchKernelGGL(ssa_k_keyset_build, dim3(grid_for(m, 256)), dim3(256), 0, ctx->stream, d_pks, d_pk_inf, m,
+                           (u64 *)d_tab, d_status);
+    });
+}
+
 extern "C" int ssa_keyset_create_device(ssa_ctx *ctx, const uint8_t *d_pks, const uint8_t *d_pk_inf, size_t m,
                                         uint32_t flags, ssa_keyset **out) {
     if (!ctx || !out || !d_pks || m == 0 || m > 0xffffffffull || flags > SSA_KEYSET_LADDER) return SSA_ERR_ARG;
@@ -966,19 +976,20 @@ extern "C" int ssa_keyset_create_device(ssa_ctx *ctx, const uint8_t *d_pks, cons
     ks->ctx = ctx;
     ks->m = m;
     if (ks->tab.reserve(m * (size_t)(PTAB_ENTRIES * PTAB_ENTRY_U64) * sizeof(u64)) || ks->status.reserve(m + 16) ||
-        ks->pks.reserve(m * 96)) {
+        ks->pks.reserve(m * 96) || ks->inf.reserve(m + 16)) {
         ssa_keyset_destroy(ks);
         return SSA_ERR_HIP;
     }
-    // the hash kernel reads the keys (x, y_0) through the index: keep a copy so that the caller's buffer can go
-    if (hipMemcpyAsync(ks->pks.p, d_pks, m * 96, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) {
+    // the hash kernel reads the keys (x, y_0) through the index: keep a copy so that the caller's buffer can go; the
+    // flags are kept beside them (all zero without d_pk_inf): bytes and flag are what ssa_keyset_selfcheck trusts
+    if (hipMemcpyAsync(ks->pks.p, d_pks, m * 96, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess ||
+        (d_pk_inf ? hipMemcpyAsync(ks->inf.p, d_pk_inf, m, hipMemcpyDeviceToDevice, ctx->stream)
+                  : hipMemsetAsync(ks->inf.p, 0, m, ctx->stream)) != hipSuccess) {
         ssa_keyset_destroy(ks);
         return SSA_ERR_HIP;
     }
-    int rc = timed_launch(ctx, "ssa_k_keyset_build", [&] {
-        hipLaunchKernelGGL(ssa_k_keyset_build, dim3(grid_for(m, 256)), dim3(256), 0, ctx->stream,
-                           (const u8 *)ks->pks.p, d_pk_inf, m, (u64 *)ks->tab.p, (u8 *)ks->status.p);
-    });
+    int rc = ssa_internal_keyset_build(ctx, (const u8 *)ks->pks.p, (const u8 *)ks->inf.p, m, (u64 *)ks->tab.p,
+                                       (u8 *)ks->status.p);
     if (rc != 0 || hipStreamSynchronize(ctx->stream) != hipSuccess) {
         ssa_keyset_destroy(ks);
         return rc ? rc : SSA_ERR_HIP;
@@ -1003,7 +1014,7 @@ extern "C" int ssa_keyset_create_device(ssa_ctx *ctx, const uint8_t *d_pks, cons
     if (ks->comb) {
         rc = timed_launch(ctx, "ssa_k_keycomb_build", [&] {
             hipLaunchKernelGGL(ssa_k_keycomb_base, dim3(grid_for(m * KBASE_ENTRIES_PER_KEY, 256)), dim3(256), 0,
-                               ctx->stream, (const u8 *)ks->pks.p, d_pk_inf, (const u8 *)ks->status.p, m,
+                               ctx->stream, (const u8 *)ks->pks.p, (const u8 *)ks->inf.p, (const u8 *)ks->status.p, m,
                                (u64 *)kbase.p);
             hipLaunchKernelGGL(ssa_k_keycomb_build, dim3(grid_for(m * (KTAB_ENTRIES_PER_KEY / 8), 256)), dim3(256), 0,
                                ctx->stream, (const u64 *)kbase.p, m, (u64 *)ks->ktab.p);
@@ -1185,10 +1196,8 @@ static int dedup_check_keys(ssa_ctx *ctx, const uint8_t *d_pks, const uint8_t *d
                            (const u32 *)ctx->dd_reps.p, (u32)u, (u64 *)ctx->dd_pks.p, (u8 *)ctx->dd_inf.p);
     });
     if (rc) return rc;
-    return timed_launch(ctx, "ssa_k_keyset_build", [&] {
-        hipLaunchKernelGGL(ssa_k_keyset_build, dim3(grid_for(u, 256)), dim3(256), 0, ctx->stream, (const u8 *)ctx->dd_pks.p,
-                           (const u8 *)ctx->dd_inf.p, (size_t)u, (u64 *)ctx->ws_tab.p, (u8 *)ctx->dd_kstatus.p);
-    });
+    return ssa_internal_keyset_build(ctx, (const u8 *)ctx->dd_pks.p, (const u8 *)ctx->dd_inf.p, (size_t)u,
+                                     (u64 *)ctx->ws_tab.p, (u8 *)ctx->dd_kstatus.p);
 }
 
 // The two ends of the keyed route, shared with ssa_verify_many_screened (ssa_msm.hip), which puts
@@ -1429,11 +1438,8 @@ static int keycache_insert(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *d_pks,
                            reps, (u32)m, c_pks + 12 * base, c_inf + base);
     });
     if (rc) return rc;
-    rc = timed_launch(ctx, "ssa_k_keyset_build", [&] {
-        hipLaunchKernelGGL(ssa_k_keyset_build, dim3(grid_for(m, 256)), dim3(256), 0, ctx->stream,
-                           (const u8 *)(c_pks + 12 * base), (const u8 *)(c_inf + base), m,
-                           (u64 *)kc->rows.tab.p + base * TAB_WORDS, (u8 *)kc->rows.status.p + base);
-    });
+    rc = ssa_internal_keyset_build(ctx, (const u8 *)(c_pks + 12 * base), (const u8 *)(c_inf + base), m,
+                                   (u64 *)kc->rows.tab.p + base * TAB_WORDS, (u8 *)kc->rows.status.p + base);
     if (rc) return rc;
     return timed_launch(ctx, "keycache_insert", [&] {
         hipLaunchKernelGGL(kc_k_publish, dim3(grid_for(m, DD_BLOCK)), dim3(DD_BLOCK), 0, ctx->stream, (const u64 *)c_pks,

@@ -171,6 +171,7 @@ struct ssa_ctx {
     DevBuf ctab, sg_sigs, sg_pks;
     bool ctab_ready = false;
     DevBuf tc_out;                // table self-check (ssa_selfcheck.hpp): failing rows, first failing row
+    DevBuf kck_ws;                // key-table self-check (ssa_keycheck.hpp): a bad flag per key and two lists of key numbers
     DevBuf dv_recs;               // key derivation (ssa_derive.hpp): one record per parent, wiped after each call
     // device-drawn scalars (ssa_rng.hpp): the call's 44-byte seed, one slice of drawn scalars (both zeroed on the stream
     // after each call), the page-locked host copy of the seed (wiped before the call returns) and the test pin
@@ -209,7 +210,7 @@ static inline void for_each_devbuf(Ctx *c, F &&f) {
                     &c->scr_ok, &c->scr_in, &c->scr_status, &c->scr_fail, &c->scr_mask, &c->scr_mark,
                     &c->scr_list, &c->scr_blk, &c->scr_cnt, &c->dd_slots, &c->dd_rep, &c->dd_num, &c->dd_reps,
                     &c->dd_idx, &c->dd_blk, &c->dd_stats, &c->dd_pks, &c->dd_inf, &c->dd_kstatus, &c->kc_found,
-                    &c->kc_missrep, &c->kc_blk, &c->kc_lane_row, &c->ctab, &c->sg_sigs, &c->sg_pks, &c->tc_out, &c->dv_recs, &c->rng_seed, &c->rng_scratch, &c->tail_done, &c->tail_park})
+                    &c->kc_missrep, &c->kc_blk, &c->kc_lane_row, &c->ctab, &c->sg_sigs, &c->sg_pks, &c->tc_out, &c->kck_ws, &c->dv_recs, &c->rng_seed, &c->rng_scratch, &c->tail_done, &c->tail_park})
         f(*b);
 }
 
@@ -218,11 +219,12 @@ struct ssa_keyset {
     ssa_ctx *ctx = nullptr;   // nullptr: the context is gone, the device memory went with it
     size_t m = 0;
     bool comb = false;      // per-key comb tables (16 x 65536 rows = 100 MB per key) instead of the ladder's 16 multiples
-    DevBuf tab, status, pks, ktab;
+    DevBuf tab, status, pks, inf, ktab;     // inf: the pk_inf boolean of each key (zeros when the caller gave none)
     void release_all() {
         tab.release();
         status.release();
         pks.release();
+        inf.release();
         ktab.release();
     }
 };
@@ -752,6 +754,10 @@ int ssa_internal_verify_keyed_view(ssa_ctx *ctx, const uint8_t *d_sigs, const ui
 int ssa_internal_keycache_slice(ssa_ctx *ctx, struct ssa_keycache *kc, const uint8_t *d_pks, const uint8_t *d_pk_inf,
                                 size_t cnt, KeyView *kv, uint64_t *u_out, uint64_t *bound_hits_out, uint64_t ks[4],
                                 const unsigned long long **d_unpublished);
+
+// defined in ssa_api.hip: ssa_k_keyset_build over m keys, queued on the context's stream (timing key ssa_k_keyset_build)
+int ssa_internal_keyset_build(ssa_ctx *ctx, const uint8_t *d_pks, const uint8_t *d_pk_inf, size_t m, uint64_t *d_tab,
+                              uint8_t *d_status);
 
 // defined in ssa_sign.hip (ssa_selfcheck.hpp): the exact check of a comb table for G (res[0] failing rows, res[1] the
 // first failing row or ~0) and of the context's constant-time table (out[0] rows checked, out[1], out[2] as res)

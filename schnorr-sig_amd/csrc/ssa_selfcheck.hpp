@@ -4,7 +4,8 @@
 //   ssa_k_gtab_check   every row of a comb table of `bits`-bit windows, [d 2^(bits w)]G, checked against the rows before
 //                      it: (w, 0) is zero (row (0, 0) carries the header word), (0, 1) is G, (w, 1) = (w-1, 2^bits-1) +
 //                      B_{w-1}, (w, 2) = 2 B_w, (w, d) = (w, d-1) + B_w, with B_w = row (w, 1); every limb < p.  The same
-//                      kernel checks the 64 x 16 rows of the constant-time table (bits = 4, no header word).
+//                      kernel checks the 64 x 16 rows of the constant-time table (bits = 4, no header word).  The walk
+//                      itself is comb_rows_check, which the per-key combs of key sets share (ssa_keycheck.hpp).
 //   ssa_k_ctab_check_b the two offset rows of the constant-time table: B = [b]G by one walk of the (checked) comb, -B
 //
 // A relation R = P + Q (chord) or R = 2P (tangent) is checked without an inversion: with the slope num / den,
@@ -48,6 +49,49 @@ SSA_DEV bool chain_rel(const aff &R, const aff &P, const aff &Q, bool tangent) {
     return ex && ey;
 }
 
+#ifndef SSA_CHECK_FUNCTIONS_ONLY      // (tests/csrc/keycheck_host.cpp compiles the relations alone, for the CPU)
+// The 8 rows lane `t` takes of a comb of `bits`-bit windows at `tab` (see "Work layout"): nbad = how many fail, first =
+// the first of them (TC_NONE: none).  `head` is word 0 of row (0, 0) (0: none); base_eq(R) says whether R is the point
+// the comb is a table of -- row (0, 1), the one row that no relation ties to the rows before it.
+template <class BaseEq>
+SSA_DEV void comb_rows_check(const u64 *__restrict__ tab, u32 bits, size_t t, u64 head, BaseEq base_eq, u32 &nbad,
+                             u64 &first) {
+    const u32 mask = (1u << bits) - 1u;
+    const u32 w = (u32)((t * 8) >> bits), d0 = (u32)((t * 8) & mask);
+    const u64 *win = tab + ((size_t)w << bits) * 12;
+    const aff B = ld_aff(win + 12);
+    aff prev;
+    prev.x = f6_zero();
+    prev.y = f6_zero();
+    if (d0 > 0) prev = ld_aff(win + 12 * (size_t)(d0 - 1));
+    else if (w > 0) prev = ld_aff(win - 12);                 // (w - 1, 2^bits - 1)
+#pragma unroll 1
+    for (u32 k = 0; k < 8; k++) {
+        const u32 d = d0 + k;
+        const aff R = ld_aff(win + 12 * (size_t)d);
+        bool ok = row_canonical(R);
+        if (d == 0) {
+            u64 z = R.x.c[0] ^ (w == 0 ? head : 0ull);
+#pragma unroll
+            for (int i = 1; i < 6; i++) z |= R.x.c[i];
+#pragma unroll
+            for (int i = 0; i < 6; i++) z |= R.y.c[i];
+            ok = ok && z == 0ull;
+        } else if (d == 1 && w == 0) {
+            ok = ok && base_eq(R);
+        } else {
+            aff Q = B;
+            if (d == 1) Q = ld_aff(win - 12 * (size_t)mask);    // B_{w-1} = (w - 1, 1)
+            ok = ok && chain_rel(R, d == 2 ? B : prev, Q, d == 2);
+            prev = R;
+        }
+        if (!ok) {
+            nbad++;
+            if (first == TC_NONE) first = ((size_t)w << bits) + d;
+        }
+    }
+}
+
 // out[0] += failing rows, out[1] = min(out[1], first failing row); `head` is word 0 of row (0, 0) (0: none)
 __global__ void __launch_bounds__(256)
 ssa_k_gtab_check(const DevParams *__restrict__ prm, const u64 *__restrict__ tab, u32 bits, u32 windows, u64 head,
@@ -55,45 +99,13 @@ ssa_k_gtab_check(const DevParams *__restrict__ prm, const u64 *__restrict__ tab,
     const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     u32 nbad = 0;
     u64 first = TC_NONE;
-    if (t < ((size_t)windows << bits) / 8) {     // (no early return: every lane takes part in the ballots below)
-        const u32 mask = (1u << bits) - 1u;
-        const u32 w = (u32)((t * 8) >> bits), d0 = (u32)((t * 8) & mask);
-        const u64 *win = tab + ((size_t)w << bits) * 12;
-        const aff B = ld_aff(win + 12);
-        aff prev;
-        prev.x = f6_zero();
-        prev.y = f6_zero();
-        if (d0 > 0) prev = ld_aff(win + 12 * (size_t)(d0 - 1));
-        else if (w > 0) prev = ld_aff(win - 12);                 // (w - 1, 2^bits - 1)
-#pragma unroll 1
-        for (u32 k = 0; k < 8; k++) {
-            const u32 d = d0 + k;
-            const aff R = ld_aff(win + 12 * (size_t)d);
-            bool ok = row_canonical(R);
-            if (d == 0) {
-                u64 z = R.x.c[0] ^ (w == 0 ? head : 0ull);
+    if (t < ((size_t)windows << bits) / 8)       // (no early return: every lane takes part in the ballots below)
+        comb_rows_check(tab, bits, t, head, [&](const aff &R) {
+            bool eq = true;
 #pragma unroll
-                for (int i = 1; i < 6; i++) z |= R.x.c[i];
-#pragma unroll
-                for (int i = 0; i < 6; i++) z |= R.y.c[i];
-                ok = ok && z == 0ull;
-            } else if (d == 1 && w == 0) {
-                bool eq = true;
-#pragma unroll
-                for (int i = 0; i < 6; i++) eq = eq && fp_eq(R.x.c[i], prm->gen_x[i]) && fp_eq(R.y.c[i], prm->gen_y[i]);
-                ok = ok && eq;
-            } else {
-                aff Q = B;
-                if (d == 1) Q = ld_aff(win - 12 * (size_t)mask);    // B_{w-1} = (w - 1, 1)
-                ok = ok && chain_rel(R, d == 2 ? B : prev, Q, d == 2);
-                prev = R;
-            }
-            if (!ok) {
-                nbad++;
-                if (first == TC_NONE) first = ((size_t)w << bits) + d;
-            }
-        }
-    }
+            for (int i = 0; i < 6; i++) eq = eq && fp_eq(R.x.c[i], prm->gen_x[i]) && fp_eq(R.y.c[i], prm->gen_y[i]);
+            return eq;
+        }, nbad, first);
     unsigned long long wave_bad = 0;
 #pragma unroll
     for (int b = 0; b < 4; b++) wave_bad += (unsigned long long)__popcll(__ballot((nbad >> b) & 1u)) << b;
@@ -119,8 +131,10 @@ ssa_k_ctab_check_b(const u64 *__restrict__ gtab, const u64 *__restrict__ ctab, u
     }
 }
 
+#endif  // SSA_CHECK_FUNCTIONS_ONLY
 }  // namespace ssa
 
+#ifndef SSA_CHECK_FUNCTIONS_ONLY
 // res[0] failing rows, res[1] first failing row (TC_NONE: none) of the table `tab` of `windows` x 2^bits rows, checked
 // on the context's stream; with `ctab`, also the two offset rows of the constant-time table.  Synchronous.
 static int table_check(ssa_ctx *ctx, const char *name, const u64 *tab, u32 bits, u32 windows, u64 head, bool ctab,
@@ -209,3 +223,4 @@ extern "C" int ssa_debug_table_xor(ssa_ctx *ctx, int which, uint64_t row, uint32
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return 0;
 }
+#endif  // SSA_CHECK_FUNCTIONS_ONLY

@@ -63,6 +63,19 @@ struct SelfCheck {
     bool ok;
 };
 
+// ssa_keyset_selfcheck's / ssa_keycache_selfcheck's out[8] by name; ok == false means keys fail (SSA_ERR_TABLE), not an
+// exception.  bad: one byte per key of a key set, 1 for a failing key (empty for a key cache).
+struct KeyCheck {
+    uint64_t keys_checked, keys_bad, first_bad_key, ladder_entries_checked, comb_rows_checked, keys_rebuilt_and_compared,
+        combs_skipped, rows_repaired;
+    bool ok;
+    std::vector<uint8_t> bad;
+};
+inline KeyCheck keycheck_result(int rc, const uint64_t o[8], const char *what, std::vector<uint8_t> bad = {}) {
+    if (rc != SSA_OK && rc != SSA_ERR_TABLE) throw std::runtime_error(std::string(what) + ": " + ssa_strerror(rc));
+    return KeyCheck{o[0], o[1], o[2], o[3], o[4], o[5], o[6], o[7], rc == SSA_OK, std::move(bad)};
+}
+
 class Context {
   public:
     // gtab_bits / hbm_budget_bytes: the comb for G (the reference's const BASEPOINT_TABLE) as a speed-for-memory choice of
@@ -376,6 +389,14 @@ class KeySet {
     KeySet(const KeySet &) = delete;
     KeySet &operator=(const KeySet &) = delete;
     size_t size() const { return m_; }
+    // the exact check of every key's table, status and (comb mode) comb against the stored key bytes; deep: also [q]P
+    // per key (without it a status flipped between 0 and 1 is not seen).  Keys with bad[i] == 1 go into a new key set.
+    KeyCheck selfcheck(bool deep = false) {
+        uint64_t o[8] = {};
+        std::vector<uint8_t> bad(m_, 0);
+        const int rc = ssa_keyset_selfcheck(ks_, deep ? SSA_KEYCHECK_DEEP : 0u, bad.data(), o);
+        return keycheck_result(rc, o, "ssa_keyset_selfcheck", std::move(bad));
+    }
     // one Result per signature (a Panic for inputs the reference would panic on)
     std::vector<Result> verify(const std::vector<Signature> &signatures, const std::vector<uint32_t> &key_idx,
                                const std::vector<std::pair<const uint8_t *, size_t>> &messages) const {
@@ -655,6 +676,13 @@ class KeyCache {
         const int rc = ssa_keycache_info(kc_, v);
         if (rc != 0) throw std::runtime_error(std::string("ssa_keycache_info: ") + ssa_strerror(rc));
         return {v[0], v[1], v[2], v[3]};
+    }
+    // the exact check of every held row against its stored key bytes; deep: also [q]P per key; repair: failing rows are
+    // rebuilt in place from their stored bytes and checked again (ok: clean afterwards)
+    KeyCheck selfcheck(bool deep = false, bool repair = false) {
+        uint64_t o[8] = {};
+        const int rc = ssa_keycache_selfcheck(kc_, (deep ? SSA_KEYCHECK_DEEP : 0u) | (repair ? SSA_KEYCHECK_REPAIR : 0u), o);
+        return keycheck_result(rc, o, "ssa_keycache_selfcheck");
     }
 
   private:
