@@ -8,7 +8,10 @@
 #include <sys/random.h>
 
 #include <atomic>
+#include <climits>
 #include <functional>
+#include <initializer_list>
+#include <memory>
 #include <mutex>
 #include <thread>
 
@@ -135,11 +138,7 @@ static void gtab_release(SharedGtab *g) {
     if (!g) return;
     std::lock_guard<std::mutex> lock(g_gtab_mu);
     if (--g->refs > 0) return;
-    for (size_t i = 0; i < g_gtabs.size(); i++)
-        if (g_gtabs[i] == g) {
-            g_gtabs.erase(g_gtabs.begin() + (long)i);
-            break;
-        }
+    forget_handle(g_gtabs, g);
     (void)hipSetDevice(g->device);
     (void)hipFree(g->d_gtab);
     delete g;
@@ -160,8 +159,57 @@ static int validate_params(const DevParams &p) {
     return 0;
 }
 
-extern "C" int ssa_ctx_create(ssa_ctx **out, int device, const void *params, size_t params_len) {
-    return ssa_ctx_create_ex(out, device, params, params_len, 0u, 0ull);
+// A variable of the environment into a knob, if it is set and its value passes the knob's rule (true; otherwise the
+// knob keeps what it has): a number in [lo, hi] -- read with strtoull, or with atoi where the rule is on an int --, one
+// of a set, or a boolean (non-zero: true).
+template <class T>
+static bool env_u64(const char *name, uint64_t lo, uint64_t hi, T &knob) {
+    const char *e = std::getenv(name);
+    const uint64_t v = e ? std::strtoull(e, nullptr, 10) : 0;
+    if (!e || v < lo || v > hi) return false;
+    knob = (T)v;
+    return true;
+}
+template <class T>
+static bool env_int(const char *name, int lo, int hi, T &knob) {
+    const char *e = std::getenv(name);
+    const int v = e ? std::atoi(e) : 0;
+    if (!e || v < lo || v > hi) return false;
+    knob = (T)v;
+    return true;
+}
+template <class T>
+static void env_one_of(const char *name, std::initializer_list<int> set, T &knob) {
+    int v = 0;
+    if (env_int(name, INT_MIN, INT_MAX, v) && std::find(set.begin(), set.end(), v) != set.end()) knob = (T)v;
+}
+static void env_flag(const char *name, bool &knob) {
+    int v = 0;
+    if (env_int(name, INT_MIN, INT_MAX, v)) knob = v != 0;
+}
+
+// Everything a context takes from the environment, read HERE and once, when the context is created: one line per
+// variable.  *gtab_bits and *hbm_budget_bytes are the caller's arguments: the environment overrides a zero only.
+static void ctx_read_env(ssa_ctx *ctx, uint32_t *gtab_bits, uint64_t *hbm_budget_bytes) {
+    CtxKnobs &k = ctx->knobs;
+    if (env_u64("SSA_COOP_MAX_N", 0, UINT64_MAX, k.coop_max_n)) k.coop_max_n_torsion = k.coop_max_n;   // both crossovers
+    env_u64("SSA_MSM_SMALL_MAX", 0, UINT64_MAX, k.msm_small_max);
+    env_one_of("SSA_VERIFY_BLOCK", {64, 128, 256}, k.verify_block);
+    env_u64("SSA_LANE_SLICE", 256, UINT64_MAX, k.lane_slice);        // lanes per slice of the per-lane kernels (workspace bound)
+    env_u64("SSA_MSM_SLICE", 256, (uint64_t)1 << 23, k.msm_slice);   // signatures per slice of the MSM-form pipeline
+    env_int("SSA_MSM_TREE_GROUP", 2, 64, k.msm_tree_group);
+    env_int("SSA_TAIL_PIECES", 0, VP_MAX, k.tail_pieces);            // pieces of a tail group's work (0 / 1: no end game)
+    env_int("SSA_TAIL_GENS", 1, 8, k.tail_gens);                     // tail groups, in generations of resident waves
+    env_flag("SSA_TAIL_UNIFORM", k.tail_uniform);
+    env_int("SSA_TAIL_MIN_MAIN", INT_MIN, INT_MAX, k.tail_min_main);
+    env_flag("SSA_TAIL_REVERSED", k.tail_reversed);
+    env_int("SSA_TAIL_WAVES", INT_MIN, INT_MAX, k.tail_waves_override);   // tests: a small "generation"
+    env_flag("SSA_MSM_OVERLAP", k.msm_overlap);
+    env_int("SSA_PIPELINE_CHUNKS", 1, 8, k.pipeline_chunks);
+    env_flag("SSA_TWO_STREAMS", ctx->two_streams);
+    uint64_t mb = 0;
+    if (*hbm_budget_bytes == 0 && env_u64("SSA_HBM_BUDGET_MB", 0, UINT64_MAX, mb)) *hbm_budget_bytes = mb << 20;
+    if (*gtab_bits == 0) env_one_of("SSA_GTAB_BITS", {16, 20, 22, 24}, *gtab_bits);
 }
 
 // gtab_bits: window width of the comb for G (16, 20, 22 or 24; 0 = the widest whose table fits the budget; the
@@ -169,8 +217,9 @@ extern "C" int ssa_ctx_create(ssa_ctx **out, int device, const void *params, siz
 // speed-for-memory trade (the comb for G, per-key combs of a key set); 0 = a tenth of the device memory that is free
 // when the context is created (SSA_HBM_BUDGET_MB overrides 0).  An allocation that fails falls back to the next
 // smaller table instead of failing the context: the 16-bit comb (100 MB) is the floor.
-extern "C" int ssa_ctx_create_ex(ssa_ctx **out, int device, const void *params, size_t params_len, uint32_t gtab_bits,
-                                 uint64_t hbm_budget_bytes) {
+// inherit: the knobs of the context whose twin this one becomes -- then nothing is read from the environment.
+static int ctx_create(ssa_ctx **out, int device, const void *params, size_t params_len, uint32_t gtab_bits,
+                      uint64_t hbm_budget_bytes, const CtxKnobs *inherit) {
     if (!out) return SSA_ERR_ARG;
     *out = nullptr;
     if (gtab_bits != 0 && gtab_bits != 16 && gtab_bits != 20 && gtab_bits != 22 && gtab_bits != 24) return SSA_ERR_ARG;
@@ -196,102 +245,42 @@ extern "C" int ssa_ctx_create_ex(ssa_ctx **out, int device, const void *params, 
     for (int i = 0; i < 144; i++) tiny_mds = tiny_mds && hp.mds[i] < 0x10000ull;
     if (tiny_mds) hp.flags |= PRM_FLAG_TINY_MDS;
     HIP_TRY(hipSetDevice(device));
-    ssa_ctx *ctx = new ssa_ctx();
+    // owned here until it is handed out: every early return destroys what exists of it
+    std::unique_ptr<ssa_ctx, decltype(&ssa_ctx_destroy)> guard(new ssa_ctx(), ssa_ctx_destroy);
+    ssa_ctx *ctx = guard.get();
     ctx->device = device;
     ctx->default_params = is_default;
-    if (const char *cm = std::getenv("SSA_COOP_MAX_N"))
-        ctx->coop_max_n = ctx->coop_max_n_torsion = (size_t)std::strtoull(cm, nullptr, 10);
-    if (const char *sm = std::getenv("SSA_MSM_SMALL_MAX")) ctx->msm_small_max = (size_t)std::strtoull(sm, nullptr, 10);
-    if (const char *vb = std::getenv("SSA_VERIFY_BLOCK")) {
-        const int v = std::atoi(vb);
-        if (v == 64 || v == 128 || v == 256) ctx->verify_block = (unsigned)v;
+    if (inherit) ctx->knobs = *inherit;
+    else ctx_read_env(ctx, &gtab_bits, &hbm_budget_bytes);
+    HIP_TRY(hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking));
+    HIP_TRY(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
+    for (auto &st : ctx->hash_stream) HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    HIP_TRY(hipEventCreateWithFlags(&ctx->pipe_start, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&ctx->order_ev, hipEventDisableTiming));
+    for (int i = 0; i < 8; i++) {
+        HIP_TRY(hipEventCreateWithFlags(&ctx->copy_done[i], hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&ctx->hash_done[i], hipEventDisableTiming));
     }
-    if (const char *ls = std::getenv("SSA_LANE_SLICE")) {      // lanes per slice of the per-lane kernels (workspace bound)
-        const size_t v = (size_t)std::strtoull(ls, nullptr, 10);
-        if (v >= 256) ctx->lane_slice = v;
-    }
-    if (const char *ms = std::getenv("SSA_MSM_SLICE")) {       // signatures per slice of the MSM-form pipeline
-        const size_t v = (size_t)std::strtoull(ms, nullptr, 10);
-        if (v >= 256 && v <= ((size_t)1 << 23)) ctx->msm_slice = v;
-    }
-    if (const char *tg = std::getenv("SSA_MSM_TREE_GROUP")) {
-        const int v = std::atoi(tg);
-        if (v >= 2 && v <= 64) ctx->msm_tree_group = (unsigned)v;
-    }
-    if (const char *tpc = std::getenv("SSA_TAIL_PIECES")) {    // pieces of a tail group's work (0 / 1: no end game)
-        const int v = std::atoi(tpc);
-        if (v >= 0 && v <= VP_MAX) ctx->tail_pieces = (unsigned)v;
-    }
-    if (const char *tg = std::getenv("SSA_TAIL_GENS")) {       // tail groups, in generations of resident waves
-        const int v = std::atoi(tg);
-        if (v >= 1 && v <= 8) ctx->tail_gens = (unsigned)v;
-    }
-    if (const char *tu = std::getenv("SSA_TAIL_UNIFORM")) ctx->tail_uniform = std::atoi(tu) != 0;
-    if (const char *tm = std::getenv("SSA_TAIL_MIN_MAIN")) ctx->tail_min_main = (unsigned)std::atoi(tm);
-    if (const char *tr = std::getenv("SSA_TAIL_REVERSED")) ctx->tail_reversed = std::atoi(tr) != 0;
-    if (const char *tw = std::getenv("SSA_TAIL_WAVES")) ctx->tail_waves_override = (unsigned)std::atoi(tw);   // tests: a small "generation"
-    if (const char *ts = std::getenv("SSA_TWO_STREAMS")) ctx->two_streams = std::atoi(ts) != 0;
-    if (const char *mo = std::getenv("SSA_MSM_OVERLAP")) ctx->msm_overlap = std::atoi(mo) != 0;
-    if (const char *pc = std::getenv("SSA_PIPELINE_CHUNKS")) {
-        const int v = std::atoi(pc);
-        if (v >= 1 && v <= 8) ctx->pipeline_chunks = (unsigned)v;
-    }
-    if (hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking) != hipSuccess ||
-        hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking) != hipSuccess) {
-        ssa_ctx_destroy(ctx);
-        return SSA_ERR_HIP;
-    }
-    for (auto &st : ctx->hash_stream)
-        if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) {
-            ssa_ctx_destroy(ctx);
-            return SSA_ERR_HIP;
-        }
-    if (hipEventCreateWithFlags(&ctx->pipe_start, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->order_ev, hipEventDisableTiming) != hipSuccess) {
-        ssa_ctx_destroy(ctx);
-        return SSA_ERR_HIP;
-    }
-    for (int i = 0; i < 8; i++)
-        if (hipEventCreateWithFlags(&ctx->copy_done[i], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&ctx->hash_done[i], hipEventDisableTiming) != hipSuccess) {
-            ssa_ctx_destroy(ctx);
-            return SSA_ERR_HIP;
-        }
     ctx->stream = ctx->own_stream;
-    {   // the waves of ssa_k_verify that are resident at once: the size of its end game
+    if (!inherit) {   // the waves of ssa_k_verify that are resident at once: the size of its end game
         hipDeviceProp_t prop;
         int occ = 0;
         if (hipGetDeviceProperties(&prop, device) == hipSuccess &&
             hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, ssa_k_verify, 256, 0) == hipSuccess && occ > 0)
-            ctx->verify_waves = (unsigned)prop.multiProcessorCount * (unsigned)occ * 4u;
+            ctx->knobs.verify_waves = (unsigned)prop.multiProcessorCount * (unsigned)occ * 4u;
         (void)hipGetLastError();
-        if (ctx->tail_waves_override) ctx->verify_waves = ctx->tail_waves_override;
+        if (ctx->knobs.tail_waves_override) ctx->knobs.verify_waves = ctx->knobs.tail_waves_override;
     }
-    if (hipMalloc((void **)&ctx->d_params, sizeof(DevParams)) != hipSuccess) {
-        ssa_ctx_destroy(ctx);
-        return SSA_ERR_HIP;
-    }
-    if (hipMemcpy(ctx->d_params, &hp, sizeof hp, hipMemcpyHostToDevice) != hipSuccess) {
-        ssa_ctx_destroy(ctx);
-        return SSA_ERR_HIP;
-    }
+    HIP_TRY(hipMalloc((void **)&ctx->d_params, sizeof(DevParams)));
+    HIP_TRY(hipMemcpy(ctx->d_params, &hp, sizeof hp, hipMemcpyHostToDevice));
     ctx->h_params = hp;
     // HBM budget of the speed-for-memory tables, and the comb geometry it allows
-    if (hbm_budget_bytes == 0) {
-        if (const char *mb = std::getenv("SSA_HBM_BUDGET_MB")) hbm_budget_bytes = std::strtoull(mb, nullptr, 10) << 20;
-    }
     if (hbm_budget_bytes == 0) {
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
         hbm_budget_bytes = free_b / 10;
     }
     ctx->hbm_budget = hbm_budget_bytes;
-    if (gtab_bits == 0) {
-        if (const char *gb = std::getenv("SSA_GTAB_BITS")) {
-            const int v = std::atoi(gb);
-            if (v == 16 || v == 20 || v == 22 || v == 24) gtab_bits = (uint32_t)v;
-        }
-    }
     // the comb table of this generator on this device: shared by every context that asks for the same geometry.
     // Forced width: that one first; automatic: the widest within the budget.  Either way a failed allocation moves on
     // to the next smaller table.
@@ -303,11 +292,8 @@ extern "C" int ssa_ctx_create_ex(ssa_ctx **out, int device, const void *params, 
         ctx->gtab_share = gtab_acquire(ctx, hp, wbits, &bad_table);
         if (ctx->gtab_share) break;
     }
-    if (!ctx->gtab_share || ctx->ws_fail.reserve(64)) {
-        const int rc = !ctx->gtab_share && bad_table ? SSA_ERR_TABLE : SSA_ERR_HIP;
-        ssa_ctx_destroy(ctx);
-        return rc;
-    }
+    if (!ctx->gtab_share) return bad_table ? SSA_ERR_TABLE : SSA_ERR_HIP;
+    if (ctx->ws_fail.reserve(64)) return SSA_ERR_HIP;
     ctx->d_gtab = ctx->gtab_share->d_gtab;
     ctx->gtab_bits = ctx->gtab_share->bits;
     // the generator must be a point of the prime-order subgroup: on the curve, [q]G == O (through the comb table
@@ -315,56 +301,51 @@ extern "C" int ssa_ctx_create_ex(ssa_ctx **out, int device, const void *params, 
     unsigned gen_ok = 0;
     hipLaunchKernelGGL(ssa_k_check_generator, dim3(1), dim3(64), 0, ctx->stream, ctx->d_params,
                        (const u64 *)ctx->d_gtab, (unsigned *)ctx->ws_fail.p);
-    if (hipGetLastError() != hipSuccess ||
-        hipMemcpyAsync(&gen_ok, ctx->ws_fail.p, sizeof gen_ok, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-        hipStreamSynchronize(ctx->stream) != hipSuccess) {
-        ssa_ctx_destroy(ctx);
-        return SSA_ERR_HIP;
-    }
-    if (gen_ok != 1u) {
-        ssa_ctx_destroy(ctx);
-        return SSA_ERR_PARAMS;
-    }
-    *out = ctx;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&gen_ok, ctx->ws_fail.p, sizeof gen_ok, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (gen_ok != 1u) return SSA_ERR_PARAMS;
+    *out = guard.release();
     return 0;
+}
+
+extern "C" int ssa_ctx_create_ex(ssa_ctx **out, int device, const void *params, size_t params_len, uint32_t gtab_bits,
+                                 uint64_t hbm_budget_bytes) {
+    return ctx_create(out, device, params, params_len, gtab_bits, hbm_budget_bytes, nullptr);
+}
+
+extern "C" int ssa_ctx_create(ssa_ctx **out, int device, const void *params, size_t params_len) {
+    return ssa_ctx_create_ex(out, device, params, params_len, 0u, 0ull);
 }
 
 // The second set of streams and workspaces of a context (calls of more than one slice alternate between the two, so
 // that the tail of one slice's kernels -- the last wave of every SIMD runs alone, the XCDs finish 1.5-4 % apart: 0.9 ms
 // of a 26.6 ms ssa_k_verify, 0.35 of an 8 ms ssa_k_hash -- is filled by the next slice's): a context of its own on the
-// same device, blob and comb table (the registry hands the table out again: no second copy), owned by `ctx`.
+// same device, blob and comb table (the registry hands the table out again: no second copy), owned by `ctx`.  It reads
+// no environment: it is created from the knobs of `ctx` and takes them again at every call (the debug setters).
 ssa_ctx *ssa_internal_twin(ssa_ctx *ctx) {
     if (ctx->is_twin || !ctx->two_streams) return nullptr;
     if (!ctx->twin) {
         DevParams hp = ctx->h_params;
         hp.flags = 0;
-        ssa_ctx *t = nullptr;
-        if (ssa_ctx_create_ex(&t, ctx->device, &hp, sizeof hp, ctx->gtab_bits, ctx->hbm_budget) != 0) {
+        if (ctx_create(&ctx->twin, ctx->device, &hp, sizeof hp, ctx->gtab_bits, ctx->hbm_budget, &ctx->knobs) != 0) {
             ctx->two_streams = false;          // no memory for a second workspace: one stream, as before
             return nullptr;
         }
-        t->is_twin = true;
-        t->default_params = ctx->default_params;
-        t->lane_slice = ctx->lane_slice;
-        t->coop_max_n = ctx->coop_max_n;
-        t->coop_max_n_torsion = ctx->coop_max_n_torsion;
-        t->pipeline_chunks = ctx->pipeline_chunks;
-        t->pipeline_min_n = ctx->pipeline_min_n;
-        t->verify_block = ctx->verify_block;
-        t->tail_pieces = ctx->tail_pieces;
-        t->tail_gens = ctx->tail_gens;
-        t->tail_uniform = ctx->tail_uniform;
-        t->tail_min_main = ctx->tail_min_main;
-        t->tail_reversed = ctx->tail_reversed;
-        t->verify_waves = ctx->verify_waves;
-        ctx->twin = t;
+        ctx->twin->is_twin = true;
     }
-    ctx->twin->timing = ctx->timing;
-    ctx->twin->screen_segs = ctx->screen_segs;
-    ctx->twin->dedup_ratio[0] = ctx->dedup_ratio[0];
-    ctx->twin->dedup_ratio[1] = ctx->dedup_ratio[1];
-    ctx->twin->dedup_probe_bound = ctx->dedup_probe_bound;
+    ctx->twin->knobs = ctx->knobs;
     return ctx->twin;
+}
+
+// every live handle of a dead context gives its device memory back and forgets the context
+template <class T, class F>
+static void orphan_handles(std::vector<T *> &v, F &&release) {
+    for (T *h : v) {
+        release(h);
+        h->ctx = nullptr;
+    }
+    v.clear();
 }
 
 extern "C" void ssa_ctx_destroy(ssa_ctx *ctx) {
@@ -377,28 +358,16 @@ extern "C" void ssa_ctx_destroy(ssa_ctx *ctx) {
     }
     // a key set that outlives its context (garbage-collection order of a binding) must not touch the dead stream:
     // its tables are freed here, the handle stays valid for ssa_keyset_destroy and is refused everywhere else
-    for (ssa_keyset *ks : ctx->keysets) {
-        ks->release_all();
-        ks->ctx = nullptr;
-    }
-    ctx->keysets.clear();
-    for (ssa_signer_set *ss : ctx->signer_sets) {
-        ss->wipe_release();
-        ss->ctx = nullptr;
-    }
-    ctx->signer_sets.clear();
-    for (ssa_keycache *kc : ctx->keycaches) {
-        kc->release_all();
-        kc->ctx = nullptr;
-    }
-    ctx->keycaches.clear();
+    orphan_handles(ctx->keysets, [](ssa_keyset *ks) { ks->release_all(); });
+    orphan_handles(ctx->signer_sets, [](ssa_signer_set *ss) { ss->wipe_release(); });
+    orphan_handles(ctx->keycaches, [](ssa_keycache *kc) { kc->release_all(); });
     for (auto &kv : ctx->timed)
         for (auto &t : kv.second) {
             (void)hipEventDestroy(t.start);
             (void)hipEventDestroy(t.stop);
         }
     for_each_devbuf(ctx, [](DevBuf &b) { b.release(); });
-    for (HostBuf *b : {&ctx->pin_in, &ctx->pin_coeffs, &ctx->pin_out, &ctx->pin_seed}) b->release();
+    for_each_hostbuf(ctx, [](HostBuf &b) { b.release(); });
     if (ctx->d_params) (void)hipFree(ctx->d_params);
     gtab_release(ctx->gtab_share);
     ctx->gtab_share = nullptr;
@@ -431,8 +400,8 @@ extern "C" int ssa_ctx_info(const ssa_ctx *ctx, uint64_t out[8]) {
     out[1] = gtab_windows(ctx->gtab_bits);
     out[2] = gtab_bytes(ctx->gtab_bits);
     out[3] = reserved(ctx) + (ctx->twin ? reserved(ctx->twin) : 0);
-    out[4] = ctx->lane_slice;
-    out[5] = ctx->msm_slice;
+    out[4] = ctx->knobs.lane_slice;
+    out[5] = ctx->knobs.msm_slice;
     out[6] = ctx->hbm_budget;
     out[7] = ctx->two_streams && !ctx->is_twin ? 1 : 0;
     return 0;
@@ -463,11 +432,7 @@ extern "C" int ssa_ctx_selfcheck(ssa_ctx *ctx, uint32_t flags, uint64_t out[8]) 
         SharedGtab *sg = ctx->gtab_share;
         if (!sg->retired) {
             sg->retired = true;
-            for (size_t i = 0; i < g_gtabs.size(); i++)
-                if (g_gtabs[i] == sg) {
-                    g_gtabs.erase(g_gtabs.begin() + (long)i);
-                    break;
-                }
+            forget_handle(g_gtabs, sg);
         }
     }
     return g[0] || c[1] ? SSA_ERR_TABLE : SSA_OK;
@@ -509,7 +474,7 @@ extern "C" int ssa_ctx_sync(ssa_ctx *ctx) {
 
 extern "C" int ssa_ctx_enable_timing(ssa_ctx *ctx, int on) {
     if (!ctx) return SSA_ERR_ARG;
-    ctx->timing = on != 0;
+    ctx->knobs.timing = on != 0;
     return 0;
 }
 
@@ -653,8 +618,8 @@ static TailPlan tail_plan_of(const TailKnobs &kn, size_t cnt, uint32_t flags) {
     return tp;
 }
 static TailPlan tail_plan(const ssa_ctx *ctx, size_t cnt, uint32_t flags) {
-    return tail_plan_of({ctx->tail_pieces, ctx->tail_gens, ctx->verify_waves, ctx->verify_block, ctx->tail_min_main,
-                         ctx->tail_uniform, ctx->tail_reversed}, cnt, flags);
+    return tail_plan_of({ctx->knobs.tail_pieces, ctx->knobs.tail_gens, ctx->knobs.verify_waves, ctx->knobs.verify_block, ctx->knobs.tail_min_main,
+                         ctx->knobs.tail_uniform, ctx->knobs.tail_reversed}, cnt, flags);
 }
 
 // the plan for explicit knobs: no context and no device needed, so the host logic is tested on the CPU
@@ -674,13 +639,13 @@ extern "C" int ssa_debug_tail_plan(unsigned waves, unsigned pieces, unsigned gen
     return 0;
 }
 
-// ssa_k_verify over n lanes whose challenge scalars are in d_h, in slices of at most ctx->lane_slice lanes: the 4 KB
+// ssa_k_verify over n lanes whose challenge scalars are in d_h, in slices of at most ctx->knobs.lane_slice lanes: the 4 KB
 // per-lane table workspace never exceeds one slice (the caller has reserved it).  *d_fail is added to.
 static int verify_slices(ssa_ctx *ctx, const DevBatch &b, const u64 *d_h, size_t n, uint32_t flags, uint8_t *d_status_out,
                          unsigned long long *d_fail) {
-    return for_dev_slices(b, n, ctx->lane_slice, [&](size_t lo, size_t cnt, const DevBatch &s) {
+    return for_dev_slices(b, n, ctx->knobs.lane_slice, [&](size_t lo, size_t cnt, const DevBatch &s) {
         const TailPlan tp = tail_plan(ctx, cnt, flags);
-        unsigned blocks = grid_for(cnt, ctx->verify_block);
+        unsigned blocks = grid_for(cnt, ctx->knobs.verify_block);
         if (tp.n_pieces) {
             if (ctx->tail_done.reserve(2 * (size_t)tp.tail_groups * sizeof(u32)) ||       // finished pieces, claimed pieces
                 ctx->tail_park.reserve((size_t)tp.tail_groups * PARK_WORDS * 64 * sizeof(u64)))
@@ -689,7 +654,7 @@ static int verify_slices(ssa_ctx *ctx, const DevBatch &b, const u64 *d_h, size_t
             blocks = tail_grid_blocks(tp);
         }
         return timed_launch(ctx, "ssa_k_verify", [&] {
-            hipLaunchKernelGGL(ssa_k_verify, dim3(blocks), dim3(ctx->verify_block), 0,
+            hipLaunchKernelGGL(ssa_k_verify, dim3(blocks), dim3(ctx->knobs.verify_block), 0,
                                ctx->stream, s.sigs, s.pks, s.pk_inf, d_h + 4 * lo, (const u64 *)ctx->d_gtab,
                                (u64 *)ctx->ws_tab.p, cnt, flags, d_status_out + lo, d_fail, tp, (u32 *)ctx->tail_done.p,
                                (u64 *)ctx->tail_park.p);
@@ -699,12 +664,12 @@ static int verify_slices(ssa_ctx *ctx, const DevBatch &b, const u64 *d_h, size_t
 
 int ssa_internal_verify_hashed(ssa_ctx *ctx, const DevBatch &b, const uint64_t *d_h, size_t n, uint32_t flags,
                                uint8_t *d_status_out, unsigned long long *d_fail) {
-    const size_t slice = ctx->lane_slice < n ? ctx->lane_slice : n;
+    const size_t slice = ctx->knobs.lane_slice < n ? ctx->knobs.lane_slice : n;
     if (ctx->ws_tab.reserve(slice * (size_t)(PTAB_ENTRIES * PTAB_ENTRY_U64) * sizeof(u64))) return SSA_ERR_HIP;
     return verify_slices(ctx, b, (const u64 *)d_h, n, flags, d_status_out, d_fail);
 }
 
-// hash + verification of ONE slice (cnt <= c->lane_slice lanes) on c->stream with c's workspaces; *d_fail is added to
+// hash + verification of ONE slice (cnt <= c->knobs.lane_slice lanes) on c->stream with c's workspaces; *d_fail is added to
 static int verify_one_slice(ssa_ctx *c, const DevBatch &b, size_t cnt, uint32_t flags, uint8_t *d_status_out,
                             unsigned long long *d_fail) {
     if (c->ws_h.reserve(cnt * 4 * sizeof(u64))) return SSA_ERR_HIP;
@@ -728,10 +693,10 @@ static int verify_launch(ssa_ctx *ctx, const DevBatch &b, size_t n, uint32_t fla
         });
     }
     // The per-lane workspaces (32 B of challenge scalar, 4 KB of table) are sized for ONE slice of at most
-    // ctx->lane_slice lanes, whatever n is (4.3 GB of tables at the default 2^20; the reference takes slices of any
+    // ctx->knobs.lane_slice lanes, whatever n is (4.3 GB of tables at the default 2^20; the reference takes slices of any
     // length, src/batch.rs:31-50): a larger batch runs slice after slice, into the caller's one status array and the one
     // rejection counter.  At n <= lane_slice this is the single pair of launches it always was.
-    const size_t slice = ctx->lane_slice < n ? ctx->lane_slice : n;
+    const size_t slice = ctx->knobs.lane_slice < n ? ctx->knobs.lane_slice : n;
     if (n <= slice) return verify_one_slice(ctx, b, n, flags, d_status_out, d_fail);
     // More than one slice: the slices alternate between the context's stream and its twin's (a second set of
     // workspaces), so that one slice's kernels fill the tails of the other's -- ordered after everything queued on
@@ -809,7 +774,7 @@ extern "C" int ssa_decompress_many_device(ssa_ctx *ctx, const uint8_t *d_compres
 }
 
 // ------------------------------------------------------------------ host entry points
-// ONE slice (n <= ctx->lane_slice, or a batch for the cooperative kernel) from host buffers.  A large one takes the shared
+// ONE slice (n <= ctx->knobs.lane_slice, or a batch for the cooperative kernel) from host buffers.  A large one takes the shared
 // upload + hash pipeline (ssa_ctx.hpp: pipelined_upload_hash), then ONE verification launch over the whole slice: the
 // ladder kernel keeps its full-size grid, only the first chunk's upload is exposed, and the statuses come back through
 // page-locked memory.
@@ -834,7 +799,7 @@ extern "C" int ssa_verify_many(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t 
     if (n_fail_out) *n_fail_out = 0;
     if (n == 0) return 0;
     HIP_TRY(hipSetDevice(ctx->device));
-    return run_host_slices_counted(ctx, b, n, ctx->lane_slice, n_fail_out,
+    return run_host_slices_counted(ctx, b, n, ctx->knobs.lane_slice, n_fail_out,
                                    [&](ssa_ctx *c, size_t lo, size_t cnt, const HostBatch &s, uint64_t *nf) {
                                        return verify_many_host_one(c, s, cnt, flags, status_out + lo, nf);
                                    });
@@ -914,7 +879,7 @@ extern "C" int ssa_decompress_many(ssa_ctx *ctx, const uint8_t *compressed, size
     return hc.finish([&] { return ssa_decompress_many_device(ctx, d_in, n, d_pks, d_inf, d_status); });
 }
 
-// one slice of KeyedSignature records (n <= ctx->lane_slice) from host buffers (b: the messages only)
+// one slice of KeyedSignature records (n <= ctx->knobs.lane_slice) from host buffers (b: the messages only)
 static int verify_keyed_host_one(ssa_ctx *ctx, const uint8_t *keyed, const HostBatch &b, size_t n, uint32_t flags,
                                  uint8_t *status_out, uint64_t *n_fail_out) {
     HostCall hc(ctx);
@@ -949,7 +914,7 @@ extern "C" int ssa_verify_keyed_many(ssa_ctx *ctx, const uint8_t *keyed, const u
     if (n == 0) return 0;
     HIP_TRY(hipSetDevice(ctx->device));
     const HostBatch b{nullptr, nullptr, nullptr, msgs, msg_off, msg_stride, msg_len};
-    return run_host_slices_counted(ctx, b, n, ctx->lane_slice, n_fail_out,
+    return run_host_slices_counted(ctx, b, n, ctx->knobs.lane_slice, n_fail_out,
                                    [&](ssa_ctx *c, size_t lo, size_t cnt, const HostBatch &s, uint64_t *nf) {
                                        return verify_keyed_host_one(c, keyed + 130 * lo, s, cnt, flags, status_out + lo, nf);
                                    });
@@ -972,28 +937,23 @@ extern "C" int ssa_keyset_create_device(ssa_ctx *ctx, const uint8_t *d_pks, cons
     if (!ctx || !out || !d_pks || m == 0 || m > 0xffffffffull || flags > SSA_KEYSET_LADDER) return SSA_ERR_ARG;
     *out = nullptr;
     HIP_TRY(hipSetDevice(ctx->device));
-    ssa_keyset *ks = new ssa_keyset();
+    // owned here until it is registered and handed out: every early return destroys it
+    std::unique_ptr<ssa_keyset, decltype(&ssa_keyset_destroy)> guard(new ssa_keyset(), ssa_keyset_destroy);
+    ssa_keyset *ks = guard.get();
     ks->ctx = ctx;
     ks->m = m;
     if (ks->tab.reserve(m * (size_t)(PTAB_ENTRIES * PTAB_ENTRY_U64) * sizeof(u64)) || ks->status.reserve(m + 16) ||
-        ks->pks.reserve(m * 96) || ks->inf.reserve(m + 16)) {
-        ssa_keyset_destroy(ks);
+        ks->pks.reserve(m * 96) || ks->inf.reserve(m + 16))
         return SSA_ERR_HIP;
-    }
     // the hash kernel reads the keys (x, y_0) through the index: keep a copy so that the caller's buffer can go; the
     // flags are kept beside them (all zero without d_pk_inf): bytes and flag are what ssa_keyset_selfcheck trusts
-    if (hipMemcpyAsync(ks->pks.p, d_pks, m * 96, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess ||
-        (d_pk_inf ? hipMemcpyAsync(ks->inf.p, d_pk_inf, m, hipMemcpyDeviceToDevice, ctx->stream)
-                  : hipMemsetAsync(ks->inf.p, 0, m, ctx->stream)) != hipSuccess) {
-        ssa_keyset_destroy(ks);
-        return SSA_ERR_HIP;
-    }
-    int rc = ssa_internal_keyset_build(ctx, (const u8 *)ks->pks.p, (const u8 *)ks->inf.p, m, (u64 *)ks->tab.p,
-                                       (u8 *)ks->status.p);
-    if (rc != 0 || hipStreamSynchronize(ctx->stream) != hipSuccess) {
-        ssa_keyset_destroy(ks);
-        return rc ? rc : SSA_ERR_HIP;
-    }
+    HIP_TRY(hipMemcpyAsync(ks->pks.p, d_pks, m * 96, hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_TRY(d_pk_inf ? hipMemcpyAsync(ks->inf.p, d_pk_inf, m, hipMemcpyDeviceToDevice, ctx->stream)
+                     : hipMemsetAsync(ks->inf.p, 0, m, ctx->stream));
+    if (int rc = ssa_internal_keyset_build(ctx, (const u8 *)ks->pks.p, (const u8 *)ks->inf.p, m, (u64 *)ks->tab.p,
+                                           (u8 *)ks->status.p))
+        return rc;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
     // few keys: a comb table per key (no doublings at verification time); many keys: the ladder tables only
     // (100 MB per key: AUTO takes the combs while they fit the context's HBM budget and 16 GiB, and falls back to the
     // ladder tables when the allocation fails; SSA_KEYSET_COMB insists and reports the failure)
@@ -1005,14 +965,11 @@ extern "C" int ssa_keyset_create_device(ssa_ctx *ctx, const uint8_t *d_pks, cons
         kbase.release();
         ks->ktab.release();
         (void)hipGetLastError();
-        if (flags == SSA_KEYSET_COMB) {
-            ssa_keyset_destroy(ks);
-            return SSA_ERR_HIP;
-        }
+        if (flags == SSA_KEYSET_COMB) return SSA_ERR_HIP;
         ks->comb = false;
     }
     if (ks->comb) {
-        rc = timed_launch(ctx, "ssa_k_keycomb_build", [&] {
+        const int rc = timed_launch(ctx, "ssa_k_keycomb_build", [&] {
             hipLaunchKernelGGL(ssa_k_keycomb_base, dim3(grid_for(m * KBASE_ENTRIES_PER_KEY, 256)), dim3(256), 0,
                                ctx->stream, (const u8 *)ks->pks.p, (const u8 *)ks->inf.p, (const u8 *)ks->status.p, m,
                                (u64 *)kbase.p);
@@ -1021,13 +978,10 @@ extern "C" int ssa_keyset_create_device(ssa_ctx *ctx, const uint8_t *d_pks, cons
         });
         const bool synced = hipStreamSynchronize(ctx->stream) == hipSuccess;
         kbase.release();
-        if (rc != 0 || !synced) {
-            ssa_keyset_destroy(ks);
-            return rc ? rc : SSA_ERR_HIP;
-        }
+        if (rc != 0 || !synced) return rc ? rc : SSA_ERR_HIP;
     }
     ctx->keysets.push_back(ks);
-    *out = ks;
+    *out = guard.release();
     return 0;
 }
 
@@ -1044,12 +998,7 @@ extern "C" void ssa_keyset_destroy(ssa_keyset *ks) {
     if (ks->ctx) {
         (void)hipSetDevice(ks->ctx->device);
         (void)hipStreamSynchronize(ks->ctx->stream);
-        auto &v = ks->ctx->keysets;
-        for (size_t i = 0; i < v.size(); i++)
-            if (v[i] == ks) {
-                v.erase(v.begin() + (long)i);
-                break;
-            }
+        forget_handle(ks->ctx->keysets, ks);
         ks->release_all();
     }
     delete ks;
@@ -1159,7 +1108,7 @@ static int dedup_slice(ssa_ctx *ctx, const uint8_t *d_pks, const uint8_t *d_pk_i
         (void)hipMemsetAsync(d_stats, 0, (hook ? 4 : 2) * sizeof(unsigned long long), ctx->stream);
         hipLaunchKernelGGL(dd_k_insert, dim3((unsigned)nb), dim3(DD_BLOCK), 0, ctx->stream, d_pks, d_pk_inf, (u32)cnt,
                            (u64)ctx->dedup_key[0], (u64)ctx->dedup_key[1], (u64 *)ctx->dd_slots.p, (u32)(cap - 1),
-                           (u32)ctx->dedup_probe_bound, (u32 *)ctx->dd_rep.p, blk_cnt, d_stats);
+                           (u32)ctx->knobs.dedup_probe_bound, (u32 *)ctx->dd_rep.p, blk_cnt, d_stats);
         hipLaunchKernelGGL(dd_k_scan, dim3(1), dim3(DD_BLOCK), 0, ctx->stream, (const u32 *)blk_cnt, (u32)nb, blk_off,
                            d_stats);
         hipLaunchKernelGGL(dd_k_number, dim3((unsigned)nb), dim3(DD_BLOCK), 0, ctx->stream, (const u32 *)ctx->dd_rep.p,
@@ -1201,7 +1150,7 @@ static int dedup_check_keys(ssa_ctx *ctx, const uint8_t *d_pks, const uint8_t *d
 }
 
 // The two ends of the keyed route, shared with ssa_verify_many_screened (ssa_msm.hip), which puts
-// the segmented MSM between them.  ssa_internal_dedup_keys: the distinct keys of one slice (cnt <= ctx->lane_slice
+// the segmented MSM between them.  ssa_internal_dedup_keys: the distinct keys of one slice (cnt <= ctx->knobs.lane_slice
 // lanes) checked once each: ctx->dd_idx (a key index per lane) and what dedup_check_keys leaves; synchronises the
 // stream once, for u.
 int ssa_internal_dedup_keys(ssa_ctx *ctx, const uint8_t *d_pks, const uint8_t *d_pk_inf, size_t cnt, uint64_t *u_out,
@@ -1228,11 +1177,11 @@ int ssa_internal_verify_keyed_view(ssa_ctx *ctx, const uint8_t *d_sigs, const ui
     });
 }
 
-// ONE slice (cnt <= ctx->lane_slice lanes) of the lane kernels' route on ctx->stream with ctx's workspaces; hashed: the
+// ONE slice (cnt <= ctx->knobs.lane_slice lanes) of the lane kernels' route on ctx->stream with ctx's workspaces; hashed: the
 // challenge scalars are already in ctx->ws_h.  *d_fail is added to.
 static int dedup_verify_slice(ssa_ctx *ctx, const DevBatch &b, size_t cnt, uint32_t flags, bool hashed,
                               uint8_t *d_status_out, unsigned long long *d_fail, CallStats *stats) {
-    const double ratio = ctx->dedup_ratio[(flags & SSA_FLAG_CHECK_TORSION) ? 1 : 0];
+    const double ratio = ctx->knobs.dedup_ratio[(flags & SSA_FLAG_CHECK_TORSION) ? 1 : 0];
     uint64_t u = cnt, hits = 0;
     // (a threshold of 0 sends every slice to the fallback: the keys are then counted only for the statistics)
     if (ratio > 0 || stats)
@@ -1262,7 +1211,7 @@ static int dedup_verify_slice(ssa_ctx *ctx, const DevBatch &b, size_t cnt, uint3
 // only for a caller that asked for the statistics.
 static int dedup_count_only(ssa_ctx *ctx, const DevBatch &b, size_t n, CallStats *stats) {
     if (!stats) return 0;
-    return for_dev_slices(b, n, ctx->lane_slice, [&](size_t, size_t cnt, const DevBatch &s) {
+    return for_dev_slices(b, n, ctx->knobs.lane_slice, [&](size_t, size_t cnt, const DevBatch &s) {
         uint64_t u = 0, hits = 0;
         if (int rc = dedup_slice(ctx, s.pks, s.pk_inf, cnt, &u, &hits)) return rc;
         dedup_stats_add(stats, u, false, hits);
@@ -1288,7 +1237,7 @@ extern "C" int ssa_verify_many_dedup_device(ssa_ctx *ctx, const uint8_t *d_sigs,
     } else {
         // slice after slice on the context's stream (each slice's policy waits for its u: the slices of this form do not
         // alternate between two streams)
-        rc = for_dev_slices(b, n, ctx->lane_slice, [&](size_t lo, size_t cnt, const DevBatch &s) {
+        rc = for_dev_slices(b, n, ctx->knobs.lane_slice, [&](size_t lo, size_t cnt, const DevBatch &s) {
             return dedup_verify_slice(ctx, s, cnt, flags, false, d_status_out + lo, d_fail, stats_out ? &st : nullptr);
         });
     }
@@ -1321,7 +1270,7 @@ extern "C" int ssa_verify_many_dedup(ssa_ctx *ctx, const uint8_t *sigs, const ui
     st.out(stats_out);      // (still empty: the caller's words are zeroed)
     if (n == 0) return 0;
     HIP_TRY(hipSetDevice(ctx->device));
-    const int rc = run_host_slices_counted(ctx, b, n, ctx->lane_slice, n_fail_out,
+    const int rc = run_host_slices_counted(ctx, b, n, ctx->knobs.lane_slice, n_fail_out,
                                            [&](ssa_ctx *c, size_t lo, size_t cnt, const HostBatch &s, uint64_t *nf) {
                                                return dedup_host_one(c, s, cnt, flags, status_out + lo, nf,
                                                                      stats_out ? &st : nullptr);
@@ -1333,7 +1282,7 @@ extern "C" int ssa_verify_many_dedup(ssa_ctx *ctx, const uint8_t *sigs, const ui
 
 extern "C" int ssa_debug_dedup_device(ssa_ctx *ctx, const uint8_t *d_pks, const uint8_t *d_pk_inf, size_t n,
                                       uint32_t *d_key_idx_out, uint64_t out[2]) {
-    if (!ctx || !d_pks || !out || n == 0 || n > SSA_MAX_BATCH || n > ctx->lane_slice) return SSA_ERR_ARG;
+    if (!ctx || !d_pks || !out || n == 0 || n > SSA_MAX_BATCH || n > ctx->knobs.lane_slice) return SSA_ERR_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
     if (int rc = dedup_slice(ctx, d_pks, d_pk_inf, n, &out[0], &out[1])) return rc;
     if (d_key_idx_out) {
@@ -1345,9 +1294,9 @@ extern "C" int ssa_debug_dedup_device(ssa_ctx *ctx, const uint8_t *d_pks, const 
 
 extern "C" int ssa_debug_dedup_config(ssa_ctx *ctx, double max_distinct_ratio, uint32_t probe_bound) {
     if (!ctx || max_distinct_ratio > 2.0 || max_distinct_ratio != max_distinct_ratio) return SSA_ERR_ARG;
-    ctx->dedup_ratio[0] = max_distinct_ratio < 0 ? DEDUP_RATIO_NO_CHECK : max_distinct_ratio;
-    ctx->dedup_ratio[1] = max_distinct_ratio < 0 ? DEDUP_RATIO_CHECK : max_distinct_ratio;
-    ctx->dedup_probe_bound = probe_bound ? probe_bound : DEDUP_PROBE_BOUND;
+    ctx->knobs.dedup_ratio[0] = max_distinct_ratio < 0 ? DEDUP_RATIO_NO_CHECK : max_distinct_ratio;
+    ctx->knobs.dedup_ratio[1] = max_distinct_ratio < 0 ? DEDUP_RATIO_CHECK : max_distinct_ratio;
+    ctx->knobs.dedup_probe_bound = probe_bound ? probe_bound : DEDUP_PROBE_BOUND;
     return 0;
 }
 
@@ -1384,12 +1333,7 @@ extern "C" void ssa_keycache_destroy(ssa_keycache *kc) {
     if (kc->ctx) {
         (void)hipSetDevice(kc->ctx->device);
         (void)hipStreamSynchronize(kc->ctx->stream);
-        auto &v = kc->ctx->keycaches;
-        for (size_t i = 0; i < v.size(); i++)
-            if (v[i] == kc) {
-                v.erase(v.begin() + (long)i);
-                break;
-            }
+        forget_handle(kc->ctx->keycaches, kc);
         kc->release_all();
     }
     delete kc;
@@ -1444,7 +1388,7 @@ static int keycache_insert(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *d_pks,
     return timed_launch(ctx, "keycache_insert", [&] {
         hipLaunchKernelGGL(kc_k_publish, dim3(grid_for(m, DD_BLOCK)), dim3(DD_BLOCK), 0, ctx->stream, (const u64 *)c_pks,
                            (const u8 *)c_inf, (u32)base, (u32)m, (u64)ctx->dedup_key[0], (u64)ctx->dedup_key[1],
-                           (u64 *)kc->slots.p, (u32)(kc->n_slots - 1), (u32)ctx->dedup_probe_bound, d_unpublished);
+                           (u64 *)kc->slots.p, (u32)(kc->n_slots - 1), (u32)ctx->knobs.dedup_probe_bound, d_unpublished);
     });
 }
 
@@ -1465,7 +1409,7 @@ int ssa_internal_keycache_slice(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *d
             hipLaunchKernelGGL(kc_k_lookup, dim3((unsigned)nb), dim3(DD_BLOCK), 0, ctx->stream, d_pks, d_pk_inf,
                                (const u32 *)ctx->dd_reps.p, (u32)cnt, (const unsigned long long *)d_stats,
                                (u64)ctx->dedup_key[0], (u64)ctx->dedup_key[1], (const u64 *)kc->slots.p,
-                               (u32)(kc->n_slots - 1), (u32)ctx->dedup_probe_bound, (const u64 *)kc->rows.pks.p,
+                               (u32)(kc->n_slots - 1), (u32)ctx->knobs.dedup_probe_bound, (const u64 *)kc->rows.pks.p,
                                (const u8 *)kc->inf.p, (u32)held, found, blk_cnt);
             hipLaunchKernelGGL(dd_k_scan, dim3(1), dim3(DD_BLOCK), 0, ctx->stream, (const u32 *)blk_cnt, (u32)nb, blk_off,
                                d_stats + 1);

@@ -100,85 +100,24 @@ struct TimedLaunch {
 constexpr double DEDUP_RATIO_NO_CHECK = 0.0, DEDUP_RATIO_CHECK = 1.0;
 constexpr unsigned DEDUP_PROBE_BOUND = 128;
 
-struct ssa_ctx {
-    int device = 0;
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;
-    hipStream_t copy_stream = nullptr;        // uploads of the host-buffer entry points, overlapped with the kernels
-    hipEvent_t copy_done[8] = {};             // one per upload chunk
-    hipStream_t hash_stream[2] = {};          // the chunks' hash launches alternate between two streams, so that the
-    hipEvent_t hash_done[8] = {};             //   tail of one launch (a lane hashes for ~4 ms) overlaps the next
-    hipEvent_t pipe_start = nullptr;          // everything queued on `stream` before a pipelined upload began
-    hipEvent_t order_ev = nullptr;            // ssa_ctx_stream_release / _acquire
+// Everything that configures HOW calls run on a context, and that its second set of streams must share: filled from the
+// environment once, at ssa_ctx_create (ctx_read_env in ssa_api.hip: one line per variable), changed afterwards by the
+// debug setters alone, and handed to the twin whole (ssa_internal_twin).  State of ONE context -- streams, events,
+// buffers, handle lists, one-shot hooks, the comb geometry -- stays in ssa_ctx.
+struct CtxKnobs {
     size_t pipeline_min_n = 1 << 17;          // host-buffer batches from this size on are uploaded in chunks
     unsigned pipeline_chunks = 8;             // SSA_PIPELINE_CHUNKS overrides (1 = off)
-    DevParams *d_params = nullptr;
-    u64 *d_gtab = nullptr;                    // the comb table for G: owned by gtab_share (one per device, generator and
-    struct SharedGtab *gtab_share = nullptr;  //   geometry); its first word carries the geometry (ssa_kernels.hpp)
-    uint32_t gtab_bits = 0;                   // window width of that table (16 / 20 / 22 / 24)
-    uint64_t hbm_budget = 0;                  // bytes the speed-for-memory tables may take (comb for G, per-key combs)
-    DevParams h_params;                       // host copy of the blob the context was created from (derived flags set)
-    ssa_ctx *twin = nullptr;                  // second set of streams and workspaces: calls of more than one slice
-                                              //   alternate their slices between the two (created at the first such call)
-    bool is_twin = false, two_streams = true; // SSA_TWO_STREAMS=0 turns the alternation off
-    DevBuf ws_h, ws_tab, ws_fail;
-    // staging for the host-buffer entry points
-    DevBuf st_sigs, st_pks, st_inf, st_msgs, st_off, st_status, st_aux, st_aux2;
-    // MSM-form batch verification (ssa_msm.hip)
-    DevBuf msm_points, msm_scalars, msm_keys, msm_vals, msm_keys2, msm_vals2, msm_sort_tmp, msm_bounds,
-        msm_buckets, msm_chunks, msm_windows, msm_partials, msm_flags, st_coeffs, msm_cnt, msm_cnt2, msm_ids, msm_ids2,
-        msm_comb_pts, msm_comb_lins;
-    bool timing = false;
-    bool default_params = false;   // created from the built-in (unpinned) blob
     // batches up to these sizes take the cooperative (waves-per-signature) kernel: measured crossovers without /
     // with the subgroup check (tools/mode_crossover.py); SSA_COOP_MAX_N overrides both
     size_t coop_max_n = 7680, coop_max_n_torsion = 10496;   // lane kernels: 3.5 / 5.4 ms flat up to 2^15 (round 2, window asm)
     size_t msm_small_max = 3072;  // MSM-form batches up to this size: one cooperative block per signature (measured
                                   // crossover with the bucket method: tools/msm_small_crossover.py; SSA_MSM_SMALL_MAX)
-    int fault_after_chunk = -1;   // ssa_debug_fault_after_chunk (tests)
     // Workspace bound: the per-lane kernels run over slices of at most lane_slice lanes (2 KB of table + 32 B of scalar
     // each: 2.1 GB at 2^20), the MSM-form pipeline over slices of at most msm_slice signatures whose records are
     // combined like the shards of a multi-GPU batch.  SSA_LANE_SLICE / SSA_MSM_SLICE override (tests force small ones).
     size_t lane_slice = (size_t)1 << 20, msm_slice = (size_t)1 << 23;
-    DevBuf msm_slice_recs;        // one 24-word record per MSM slice
-    DevBuf msm_sbuf;              // the coefficients s_i between the two halves of the preparation (32 B per signature)
     bool msm_overlap = true;      // the h-independent half of msm_k_prepare runs under ssa_k_hash (SSA_MSM_OVERLAP=0: off)
     unsigned msm_tree_group = 16; // chunk sums added per cooperating wave and tree level (SSA_MSM_TREE_GROUP: 2..64)
-    // screened batch verification (ssa_msm.hip): segments per slice forced by
-    // ssa_debug_screen_segments (0 = automatic), the segment verdicts, the gathered lanes of failing segments (inputs and
-    // challenge scalars), their statuses, and a scratch rejection counter
-    unsigned screen_segs = 0;
-    DevBuf scr_ok, scr_in, scr_status, scr_fail;
-    // ssa_verify_many_screened: per lane "cannot be screened" (from its key) and "re-check" bytes,
-    // the re-check list (lane numbers), per-workgroup counts and offsets of the list, and three counters
-    DevBuf scr_mask, scr_mark, scr_list, scr_blk, scr_cnt;
-    // key dedup (ssa_dedup.hpp): the slot table, each lane's representative, the representatives'
-    // numbers and list, each lane's key index, per-workgroup counts and offsets, two counters (lanes at the probe bound,
-    // u), and the compacted keys, flags and key statuses.  The 16-multiple tables of the u keys live in ws_tab.
-    DevBuf dd_slots, dd_rep, dd_num, dd_reps, dd_idx, dd_blk, dd_stats, dd_pks, dd_inf, dd_kstatus;
-    // a slice takes the keyed route when u < dedup_ratio[subgroup check on] * lanes: the measured thresholds of DESIGN.md
-    // section 14 (without the check the keyed route never paid, with it always but for all-distinct keys);
-    // ssa_debug_dedup_config overrides both.  A lane probes at most dedup_probe_bound slots.
-    double dedup_ratio[2] = {DEDUP_RATIO_NO_CHECK, DEDUP_RATIO_CHECK};
-    unsigned dedup_probe_bound = DEDUP_PROBE_BOUND;
-    uint64_t dedup_key[2] = {0, 0};   // the fingerprint's key: getrandom(2) at the first use
-    bool dedup_key_set = false;
-    // key cache (ssa_keycache.hpp): per distinct key of the slice its cache row or miss number, the
-    // misses' representative lanes, per-workgroup counts and offsets of the misses, and a cache row per lane
-    DevBuf kc_found, kc_missrep, kc_blk, kc_lane_row;
-    // signing (ssa_sign.hip): the 4-bit comb table of the constant-time signer (98 KB, built at the first use) and the
-    // intermediates of the keyed (130-byte) output
-    DevBuf ctab, sg_sigs, sg_pks;
-    bool ctab_ready = false;
-    DevBuf tc_out;                // table self-check (ssa_selfcheck.hpp): failing rows, first failing row
-    DevBuf kck_ws;                // key-table self-check (ssa_keycheck.hpp): a bad flag per key and two lists of key numbers
-    DevBuf dv_recs;               // key derivation (ssa_derive.hpp): one record per parent, wiped after each call
-    // device-drawn scalars (ssa_rng.hpp): the call's 44-byte seed, one slice of drawn scalars (both zeroed on the stream
-    // after each call), the page-locked host copy of the seed (wiped before the call returns) and the test pin
-    DevBuf rng_seed, rng_scratch;
-    HostBuf pin_seed;
-    bool rng_pinned = false;
-    uint8_t rng_pin[44] = {};
     unsigned verify_block = 256;  // threads per block of ssa_k_verify (SSA_VERIFY_BLOCK overrides: 64/128/256)
     // the end game of ssa_k_verify (ssa_kernels.hpp "The end game of a launch"): the last generation of lanes runs in
     // tail_pieces pieces per ladder pass, only the last of which stand at the end of the grid
@@ -189,29 +128,115 @@ struct ssa_ctx {
     bool tail_reversed = false;   // SSA_TAIL_REVERSED=1 (tests): the end game's roles dealt from the end of the grid
     unsigned tail_min_main = 0;   // SSA_TAIL_MIN_MAIN: generations of ordinary workgroups a launch must have beside its tail
     unsigned tail_waves_override = 0;   // SSA_TAIL_WAVES: the tests' small "generation" (the end game on batches of thousands)
-    DevBuf tail_done, tail_park;  // per tail group: finished pieces; parked accumulators + status (152 B per lane)
-    // page-locked bounce buffers of the host-buffer entry points: one slice of inputs (257 B + message per lane), the
-    // caller's coefficients of the MSM form, one slice of statuses
-    HostBuf pin_in, pin_coeffs, pin_out;
+    bool timing = false;          // ssa_ctx_enable_timing
+    unsigned screen_segs = 0;     // segments per slice of the screened forms forced by ssa_debug_screen_segments (0 = automatic)
+    // a slice takes the keyed route when u < dedup_ratio[subgroup check on] * lanes: the measured thresholds of DESIGN.md
+    // section 14 (without the check the keyed route never paid, with it always but for all-distinct keys);
+    // ssa_debug_dedup_config overrides both.  A lane probes at most dedup_probe_bound slots.
+    double dedup_ratio[2] = {DEDUP_RATIO_NO_CHECK, DEDUP_RATIO_CHECK};
+    unsigned dedup_probe_bound = DEDUP_PROBE_BOUND;
+};
+
+// Every DevBuf of a context, declared HERE and nowhere else: the members of ssa_ctx and for_each_devbuf (what
+// ssa_ctx_destroy releases and ssa_ctx_info sums) both expand from this list.
+#define SSA_CTX_DEVBUFS(X) \
+    X(ws_h) X(ws_tab) X(ws_fail) \
+    /* staging for the host-buffer entry points */ \
+    X(st_sigs) X(st_pks) X(st_inf) X(st_msgs) X(st_off) X(st_status) X(st_aux) X(st_aux2) X(st_coeffs) \
+    /* MSM-form batch verification (ssa_msm.hip) */ \
+    X(msm_points) X(msm_scalars) X(msm_keys) X(msm_vals) X(msm_keys2) X(msm_vals2) X(msm_sort_tmp) X(msm_bounds) \
+    X(msm_buckets) X(msm_chunks) X(msm_windows) X(msm_partials) X(msm_flags) X(msm_cnt) X(msm_cnt2) X(msm_ids) \
+    X(msm_ids2) X(msm_comb_pts) X(msm_comb_lins) \
+    X(msm_slice_recs)   /* one 24-word record per MSM slice */ \
+    X(msm_sbuf)         /* the coefficients s_i between the two halves of the preparation (32 B per signature) */ \
+    /* screened batch verification (ssa_msm.hip): the segment verdicts, the gathered lanes of \
+       failing segments (inputs and challenge scalars), their statuses, and a scratch rejection counter */ \
+    X(scr_ok) X(scr_in) X(scr_status) X(scr_fail) \
+    /* ssa_verify_many_screened: per lane "cannot be screened" (from its key) and "re-check" \
+       bytes, the re-check list (lane numbers), per-workgroup counts and offsets of the list, and three counters */ \
+    X(scr_mask) X(scr_mark) X(scr_list) X(scr_blk) X(scr_cnt) \
+    /* key dedup (ssa_dedup.hpp): the slot table, each lane's representative, the \
+       representatives' numbers and list, each lane's key index, per-workgroup counts and offsets, two counters (lanes \
+       at the probe bound, u), and the compacted keys, flags and key statuses.  The 16-multiple tables of the u keys \
+       live in ws_tab. */ \
+    X(dd_slots) X(dd_rep) X(dd_num) X(dd_reps) X(dd_idx) X(dd_blk) X(dd_stats) X(dd_pks) X(dd_inf) X(dd_kstatus) \
+    /* key cache (ssa_keycache.hpp): per distinct key of the slice its cache row or miss number, \
+       the misses' representative lanes, per-workgroup counts and offsets of the misses, and a cache row per lane */ \
+    X(kc_found) X(kc_missrep) X(kc_blk) X(kc_lane_row) \
+    /* signing (ssa_sign.hip): the 4-bit comb table of the constant-time signer (98 KB, built at the first use) and \
+       the intermediates of the keyed (130-byte) output */ \
+    X(ctab) X(sg_sigs) X(sg_pks) \
+    X(tc_out)           /* table self-check (ssa_selfcheck.hpp): failing rows, first failing row */ \
+    X(kck_ws)           /* key-table self-check (ssa_keycheck.hpp): a bad flag per key and two lists of key numbers */ \
+    X(dv_recs)          /* key derivation (ssa_derive.hpp): one record per parent, wiped after each call */ \
+    /* device-drawn scalars (ssa_rng.hpp): the call's 44-byte seed and one slice of drawn scalars (both zeroed on the \
+       stream after each call) */ \
+    X(rng_seed) X(rng_scratch) \
+    /* the end game of ssa_k_verify, per tail group: finished pieces; parked accumulators + status (152 B per lane) */ \
+    X(tail_done) X(tail_park)
+
+// The page-locked buffers of a context, in the same way: the bounce buffers of the host-buffer entry points (one slice of
+// inputs, 257 B + message per lane; the caller's coefficients of the MSM form; one slice of statuses) and the host copy of
+// the device RNG's seed (wiped before the call returns)
+#define SSA_CTX_HOSTBUFS(X) X(pin_in) X(pin_coeffs) X(pin_out) X(pin_seed)
+
+struct ssa_ctx {
+    int device = 0;
+    hipStream_t own_stream = nullptr;
+    hipStream_t stream = nullptr;
+    hipStream_t copy_stream = nullptr;        // uploads of the host-buffer entry points, overlapped with the kernels
+    hipEvent_t copy_done[8] = {};             // one per upload chunk
+    hipStream_t hash_stream[2] = {};          // the chunks' hash launches alternate between two streams, so that the
+    hipEvent_t hash_done[8] = {};             //   tail of one launch (a lane hashes for ~4 ms) overlaps the next
+    hipEvent_t pipe_start = nullptr;          // everything queued on `stream` before a pipelined upload began
+    hipEvent_t order_ev = nullptr;            // ssa_ctx_stream_release / _acquire
+    CtxKnobs knobs;
+    DevParams *d_params = nullptr;
+    u64 *d_gtab = nullptr;                    // the comb table for G: owned by gtab_share (one per device, generator and
+    struct SharedGtab *gtab_share = nullptr;  //   geometry); its first word carries the geometry (ssa_kernels.hpp)
+    uint32_t gtab_bits = 0;                   // window width of that table (16 / 20 / 22 / 24)
+    uint64_t hbm_budget = 0;                  // bytes the speed-for-memory tables may take (comb for G, per-key combs)
+    DevParams h_params;                       // host copy of the blob the context was created from (derived flags set)
+    ssa_ctx *twin = nullptr;                  // second set of streams and workspaces: calls of more than one slice
+                                              //   alternate their slices between the two (created at the first such call)
+    bool is_twin = false, two_streams = true; // SSA_TWO_STREAMS=0 turns the alternation off
+#define X(name) DevBuf name;
+    SSA_CTX_DEVBUFS(X)
+#undef X
+#define X(name) HostBuf name;
+    SSA_CTX_HOSTBUFS(X)
+#undef X
+    bool default_params = false;   // created from the built-in (unpinned) blob
+    int fault_after_chunk = -1;   // ssa_debug_fault_after_chunk (tests)
+    uint64_t dedup_key[2] = {0, 0};   // the key of the dedup's fingerprint (ssa_dedup.hpp): getrandom(2) at the first use
+    bool dedup_key_set = false;
+    bool ctab_ready = false;      // the constant-time signer's table (ctab) is built
+    bool rng_pinned = false;      // the test pin of the device-drawn scalars (ssa_rng.hpp)
+    uint8_t rng_pin[44] = {};
     std::map<std::string, std::vector<TimedLaunch>> timed;
     std::vector<struct ssa_keyset *> keysets;   // live key sets of this context (orphaned, not leaked, by ssa_ctx_destroy)
     std::vector<struct ssa_signer_set *> signer_sets;   // live signer sets (ssa_sign.hip), orphaned the same way
     std::vector<struct ssa_keycache *> keycaches;       // live key caches, orphaned the same way
 };
 
-// every DevBuf of a context, once: ssa_ctx_destroy releases them, ssa_ctx_info sums their capacities
 template <class Ctx, class F>
 static inline void for_each_devbuf(Ctx *c, F &&f) {
-    for (auto *b : {&c->ws_h, &c->ws_tab, &c->ws_fail, &c->st_sigs, &c->st_pks, &c->st_inf, &c->st_msgs, &c->st_off,
-                    &c->st_status, &c->st_aux, &c->st_aux2, &c->msm_points, &c->msm_scalars, &c->msm_keys, &c->msm_vals,
-                    &c->msm_keys2, &c->msm_vals2, &c->msm_sort_tmp, &c->msm_bounds, &c->msm_buckets, &c->msm_chunks,
-                    &c->msm_windows, &c->msm_partials, &c->msm_flags, &c->st_coeffs, &c->msm_cnt, &c->msm_cnt2,
-                    &c->msm_ids, &c->msm_ids2, &c->msm_comb_pts, &c->msm_comb_lins, &c->msm_slice_recs, &c->msm_sbuf,
-                    &c->scr_ok, &c->scr_in, &c->scr_status, &c->scr_fail, &c->scr_mask, &c->scr_mark,
-                    &c->scr_list, &c->scr_blk, &c->scr_cnt, &c->dd_slots, &c->dd_rep, &c->dd_num, &c->dd_reps,
-                    &c->dd_idx, &c->dd_blk, &c->dd_stats, &c->dd_pks, &c->dd_inf, &c->dd_kstatus, &c->kc_found,
-                    &c->kc_missrep, &c->kc_blk, &c->kc_lane_row, &c->ctab, &c->sg_sigs, &c->sg_pks, &c->tc_out, &c->kck_ws, &c->dv_recs, &c->rng_seed, &c->rng_scratch, &c->tail_done, &c->tail_park})
-        f(*b);
+#define X(name) f(c->name);
+    SSA_CTX_DEVBUFS(X)
+#undef X
+}
+template <class Ctx, class F>
+static inline void for_each_hostbuf(Ctx *c, F &&f) {
+#define X(name) f(c->name);
+    SSA_CTX_HOSTBUFS(X)
+#undef X
+}
+
+// p out of a list of live handles (a context's key sets, signer sets or key caches; the comb registry), if it is there
+template <class T>
+static inline void forget_handle(std::vector<T *> &v, T *p) {
+    const auto it = std::find(v.begin(), v.end(), p);
+    if (it != v.end()) v.erase(it);
 }
 
 // keyed context (entry points in ssa_api.hip; ssa_ctx_destroy orphans the key sets that outlive their context)
@@ -271,7 +296,7 @@ static inline unsigned grid_for(size_t n, unsigned block) { return (unsigned)((n
 
 template <class F>
 static inline int timed_launch(ssa_ctx *ctx, const char *name, F &&launch) {
-    if (!ctx->timing) {
+    if (!ctx->knobs.timing) {
         launch();
         HIP_TRY(hipGetLastError());
         return 0;
@@ -380,7 +405,7 @@ static inline int check_dev_batch(const ssa_ctx *ctx, const DevBatch &b, size_t 
 // small batches take the cooperative kernel (one wave per signature: low latency), large ones the lane kernels (one lane
 // per signature: throughput).  The host forms stage their inputs by this answer and the device forms launch by it.
 static inline bool takes_coop(const ssa_ctx *ctx, size_t n, uint32_t flags) {
-    const size_t coop_lim = (flags & SSA_FLAG_CHECK_TORSION) ? ctx->coop_max_n_torsion : ctx->coop_max_n;
+    const size_t coop_lim = (flags & SSA_FLAG_CHECK_TORSION) ? ctx->knobs.coop_max_n_torsion : ctx->knobs.coop_max_n;
     return (flags & SSA_FLAG_FORCE_COOP) || (!(flags & SSA_FLAG_FORCE_LANE) && n <= coop_lim);
 }
 
@@ -627,7 +652,7 @@ static inline int pipelined_upload_hash(ssa_ctx *ctx, const HostBatch &b, size_t
         HIP_TRY(hipMemcpyAsync(ctx->st_inf.p, h_inf, n, hipMemcpyHostToDevice, ctx->copy_stream));
         d.pk_inf = (const u8 *)ctx->st_inf.p;
     }
-    const unsigned chunks = ctx->pipeline_chunks;
+    const unsigned chunks = ctx->knobs.pipeline_chunks;
     for (unsigned c = 0; c < chunks; c++) {
         const size_t lo = n * c / chunks, hi = n * (c + 1) / chunks, cnt = hi - lo;
         if (cnt == 0) continue;
@@ -654,13 +679,13 @@ static inline int pipelined_upload_hash(ssa_ctx *ctx, const HostBatch &b, size_t
 }
 
 // The inputs of ONE host slice on the device, for status_host_one and msm_host_one: a large slice
-// (with `pipeline`, from ctx->pipeline_min_n lanes on) goes through pipelined_upload_hash, which leaves the challenge
+// (with `pipeline`, from ctx->knobs.pipeline_min_n lanes on) goes through pipelined_upload_hash, which leaves the challenge
 // hashes in ctx->ws_h (hashed) and arms `pin`; any other slice, or one that finds no page-locked memory for its
 // statuses (pin_out) or for the caller's 32-byte coefficients, is staged by `hc`.  Errors are left in hc.rc.
 static inline StagedInputs slice_inputs(HostCall &hc, PipelinedInputs &pin, const HostBatch &b, size_t n,
                                         const uint8_t *coeffs, bool pipeline, bool pin_out) {
     ssa_ctx *ctx = hc.ctx;
-    if (hc.ok() && pipeline && n >= ctx->pipeline_min_n && ctx->pipeline_chunks > 1 && !(pin_out && ctx->pin_out.reserve(n)) &&
+    if (hc.ok() && pipeline && n >= ctx->knobs.pipeline_min_n && ctx->knobs.pipeline_chunks > 1 && !(pin_out && ctx->pin_out.reserve(n)) &&
         (!coeffs || ctx->pin_coeffs.reserve(n * 32) == 0)) {
         bool used = false;
         if (coeffs && ctx->st_coeffs.reserve(n * 32)) hc.rc = SSA_ERR_HIP;
@@ -721,7 +746,7 @@ int ssa_internal_verify_hashed(ssa_ctx *ctx, const DevBatch &b, const uint64_t *
                                uint8_t *d_status_out, unsigned long long *d_fail);
 
 // defined in ssa_api.hip, for ssa_verify_many_screened (ssa_msm.hip): the distinct keys of one slice of at most
-// ctx->lane_slice lanes checked once each (ctx->dd_idx, ctx->dd_kstatus, tables in ctx->ws_tab; one synchronisation, for
+// ctx->knobs.lane_slice lanes checked once each (ctx->dd_idx, ctx->dd_kstatus, tables in ctx->ws_tab; one synchronisation, for
 // u), and ssa_k_verify_keyed over n lanes against those keys (*d_fail is added to)
 int ssa_internal_dedup_keys(ssa_ctx *ctx, const uint8_t *d_pks, const uint8_t *d_pk_inf, size_t cnt, uint64_t *u_out,
                             uint64_t *bound_hits_out);

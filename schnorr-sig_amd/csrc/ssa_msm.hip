@@ -38,7 +38,7 @@
 namespace ssa {
 
 constexpr int MSM_CHUNK = 8;   // buckets per lane in the running-sum pass (short chains, many lanes)
-// (the tree: one cooperating wave sums ctx->msm_tree_group = 16 chunk sums -- 15 additions of ~2.2 us --: 4096 -> 256 -> 16 -> 1)
+// (the tree: one cooperating wave sums ctx->knobs.msm_tree_group = 16 chunk sums -- 15 additions of ~2.2 us --: 4096 -> 256 -> 16 -> 1)
 
 struct MsmShape {
     u32 c;        // window bits
@@ -1394,7 +1394,7 @@ static MsmShape screen_shape(u32 segs) {
     return sh;
 }
 
-// Small batch (n <= ctx->msm_small_max): one cooperative block per signature, then the records are summed -- in
+// Small batch (n <= ctx->knobs.msm_small_max): one cooperative block per signature, then the records are summed -- in
 // groups of 16 by one wave each while there are more than 16 of them, the rest by the combination kernel, which also
 // computes [sum s_i e_i] G and compares (or emits the shard's record).
 static int msm_run_small(ssa_ctx *ctx, const DevBatch &b, size_t n, const uint8_t *d_coeffs, uint32_t coeff_bytes,
@@ -1446,7 +1446,7 @@ static int msm_run_one(ssa_ctx *ctx, const DevBatch &b, size_t n, const uint8_t 
         d_coeffs = (const uint8_t *)p;
         coeff_bytes = 16;
     }
-    if (!scr && n <= ctx->msm_small_max)
+    if (!scr && n <= ctx->knobs.msm_small_max)
         return msm_run_small(ctx, b, n, d_coeffs, coeff_bytes, d_verdict_out, d_partial_out);
     const MsmShape sh = scr ? screen_shape(scr->segs) : msm_shape(n);
     // windows the coefficients themselves can reach (32-byte ones are reduced mod q: all of them).  A narrower coefficient
@@ -1486,7 +1486,7 @@ static int msm_run_one(ssa_ctx *ctx, const DevBatch &b, size_t n, const uint8_t 
         return SSA_ERR_HIP;
     HIP_TRY(hipMemsetAsync(ctx->msm_flags.p, 0, 64, ctx->stream));
     int rc = 0;
-    if (!d_h && ctx->msm_overlap) {
+    if (!d_h && ctx->knobs.msm_overlap) {
         // The challenge hashes are 62 % of this form and nothing but the digits of s_i h_i needs them: the rest of the
         // preparation (R's square roots above all) runs on a second stream UNDER ssa_k_hash -- its waves fill the hash
         // kernel's tail (the last wave of every SIMD alone, 0.35 ms) and the hash fills theirs --, ctx->stream joins it
@@ -1567,9 +1567,9 @@ static int msm_run_one(ssa_ctx *ctx, const DevBatch &b, size_t n, const uint8_t 
                            dim3(256), 0, ctx->stream, (const u64 *)ctx->msm_buckets.p, sh, (u64 *)ctx->msm_chunks.p);
         u32 count = sh.chunks / runs;
         while (count > 1) {
-            const u32 groups = (count + ctx->msm_tree_group - 1) / ctx->msm_tree_group;
+            const u32 groups = (count + ctx->knobs.msm_tree_group - 1) / ctx->knobs.msm_tree_group;
             hipLaunchKernelGGL(msm_k_tree, dim3(sh.windows * runs * groups), dim3(64), 0, ctx->stream,
-                               (const u64 *)ping, sh.windows * runs, count, ctx->msm_tree_group, pong);
+                               (const u64 *)ping, sh.windows * runs, count, ctx->knobs.msm_tree_group, pong);
             u64 *tmp = ping;
             ping = pong;
             pong = tmp;
@@ -1588,7 +1588,7 @@ static int msm_run_one(ssa_ctx *ctx, const DevBatch &b, size_t n, const uint8_t 
     });
 }
 
-// A batch of any size (n <= SSA_MAX_BATCH) in bounded memory: more than ctx->msm_slice signatures run slice after slice,
+// A batch of any size (n <= SSA_MAX_BATCH) in bounded memory: more than ctx->knobs.msm_slice signatures run slice after slice,
 // every slice reduced to its 24-word record exactly as a shard of a multi-GPU batch is (src/batch.rs:98-129: one point
 // and one scalar per part), and the records are added up by the combination kernel -- one point addition per slice.
 // hashed: ctx->ws_h already holds the challenge scalars of the WHOLE batch (the host-buffer pipeline computed them).
@@ -1600,8 +1600,8 @@ static int msm_run(ssa_ctx *ctx, const DevBatch &b, size_t n, const uint8_t *d_c
     if (int rc = check_msgs(b.msgs, n)) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     const u64 *d_h = hashed ? (const u64 *)ctx->ws_h.p : nullptr;
-    if (n <= ctx->msm_slice) return msm_run_one(ctx, b, n, d_coeffs, coeff_bytes, d_verdict_out, d_partial_out, d_h);
-    const size_t slice = ctx->msm_slice, k = (n + slice - 1) / slice;
+    if (n <= ctx->knobs.msm_slice) return msm_run_one(ctx, b, n, d_coeffs, coeff_bytes, d_verdict_out, d_partial_out, d_h);
+    const size_t slice = ctx->knobs.msm_slice, k = (n + slice - 1) / slice;
     if (ctx->msm_slice_recs.reserve(k * 24 * sizeof(u64))) return SSA_ERR_HIP;
     u64 *recs = (u64 *)ctx->msm_slice_recs.p;
     if (int rc = for_dev_slices(b, n, slice, [&](size_t lo, size_t cnt, const DevBatch &s) {
@@ -1634,7 +1634,7 @@ extern "C" int ssa_verify_batch_msm_partial_device(ssa_ctx *ctx, const uint8_t *
                    nullptr, (u64 *)d_partial_out);
 }
 
-// ONE slice (n <= ctx->msm_slice) from host buffers: the verdict (out24 == nullptr) or the slice's 24-word record
+// ONE slice (n <= ctx->knobs.msm_slice) from host buffers: the verdict (out24 == nullptr) or the slice's 24-word record
 static int msm_host_one(ssa_ctx *ctx, const HostBatch &b, size_t n, const uint8_t *coeffs, int *verdict_out,
                         uint64_t *out24) {
     HostCall hc(ctx);
@@ -1659,7 +1659,7 @@ static int msm_host_one(ssa_ctx *ctx, const HostBatch &b, size_t n, const uint8_
 // (src/batch.rs:98-129: one point and one scalar per part): a verdict, or the whole batch's own record.
 static int msm_host_sliced(ssa_ctx *ctx, const HostBatch &b, size_t n, const uint8_t *coeffs, int *verdict_out,
                            uint64_t *out24) {
-    const size_t slice = ctx->msm_slice, k = (n + slice - 1) / slice;
+    const size_t slice = ctx->knobs.msm_slice, k = (n + slice - 1) / slice;
     if (k > 4096) return SSA_ERR_ARG;
     std::vector<uint64_t> recs(k * SSA_MSM_PARTIAL_WORDS, 0);
     int rc = run_host_slices(ctx, n, slice, [&](ssa_ctx *c, size_t lo, size_t cnt) {
@@ -1695,7 +1695,7 @@ extern "C" int ssa_verify_batch_msm_partial(ssa_ctx *ctx, const uint8_t *sigs, c
     }
     if (int rc = check_host_offsets(msg_off, n)) return rc;
     const HostBatch b{sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len};
-    return n > ctx->msm_slice ? msm_host_sliced(ctx, b, n, coeffs, nullptr, out24)
+    return n > ctx->knobs.msm_slice ? msm_host_sliced(ctx, b, n, coeffs, nullptr, out24)
                               : msm_host_one(ctx, b, n, coeffs, nullptr, out24);
 }
 
@@ -1709,7 +1709,7 @@ extern "C" int ssa_verify_batch_msm(ssa_ctx *ctx, const uint8_t *sigs, const uin
     HIP_TRY(hipSetDevice(ctx->device));
     const HostBatch b{sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len};
     int verdict = SSA_MALFORMED;
-    const int rc = n > ctx->msm_slice ? msm_host_sliced(ctx, b, n, coeffs, &verdict, nullptr)
+    const int rc = n > ctx->knobs.msm_slice ? msm_host_sliced(ctx, b, n, coeffs, &verdict, nullptr)
                                       : msm_host_one(ctx, b, n, coeffs, &verdict, nullptr);
     return rc ? rc : verdict;
 }
@@ -1757,22 +1757,22 @@ extern "C" int ssa_debug_screen_plan(size_t n, uint32_t coeff_bytes, uint64_t ou
 
 extern "C" int ssa_debug_screen_segments(ssa_ctx *ctx, uint32_t k) {
     if (!ctx || k > SCREEN_MAX_SEGS) return SSA_ERR_ARG;
-    ctx->screen_segs = k;
+    ctx->knobs.screen_segs = k;
     return 0;
 }
 
-// ONE slice (n <= ctx->msm_slice) on ctx->stream into d_status[0, n): d_h = the slice's challenge scalars if they exist
+// ONE slice (n <= ctx->knobs.msm_slice) on ctx->stream into d_status[0, n): d_h = the slice's challenge scalars if they exist
 // (else they are computed into ctx->ws_h).  Synchronises the stream once, to read the segment verdicts.
 static int screen_slice(ssa_ctx *ctx, const DevBatch &b, size_t n, const uint8_t *d_coeffs, uint32_t coeff_bytes,
                         const u64 *d_h, uint8_t *d_status) {
     if (ctx->scr_fail.reserve(16)) return SSA_ERR_HIP;
     unsigned long long *scratch_fail = (unsigned long long *)ctx->scr_fail.p;    // (the caller counts the statuses)
-    if (n <= ctx->msm_small_max) {      // the exact per-lane path
+    if (n <= ctx->knobs.msm_small_max) {      // the exact per-lane path
         if (d_h) return ssa_internal_verify_hashed(ctx, b, d_h, n, SSA_FLAG_SIG_FLAG_BYTE, d_status, scratch_fail);
         return ssa_verify_many_device(ctx, b.sigs, b.pks, b.pk_inf, b.msgs.msgs, b.msgs.off, b.msgs.stride, b.msgs.len, n,
                                       SSA_FLAG_SIG_FLAG_BYTE, d_status, (uint64_t *)scratch_fail);
     }
-    const ScreenPlan pl = screen_plan(n, ctx->screen_segs);
+    const ScreenPlan pl = screen_plan(n, ctx->knobs.screen_segs);
     if (ctx->scr_ok.reserve(SCREEN_MAX_SEGS)) return SSA_ERR_HIP;
     const ScreenArgs sa{pl.segs, pl.seg_lanes / 256u, d_status, (u8 *)ctx->scr_ok.p};
     if (int rc = msm_run_one(ctx, b, n, d_coeffs, coeff_bytes, nullptr, nullptr, d_h, &sa)) return rc;
@@ -1830,11 +1830,11 @@ extern "C" int ssa_verify_batch_screened_device(ssa_ctx *ctx, const uint8_t *d_s
     unsigned long long *d_fail;
     if (int rc = reset_fail_counter(ctx, d_n_fail_out, &d_fail)) return rc;
     if (n == 0) return 0;
-    if (n <= ctx->msm_small_max)
+    if (n <= ctx->knobs.msm_small_max)
         return ssa_verify_many_device(ctx, d_sigs, d_pks, d_pk_inf, d_msgs, d_msg_off, msg_stride, msg_len, n,
                                       SSA_FLAG_SIG_FLAG_BYTE, d_status_out, (uint64_t *)d_fail);
     // (segments never straddle two slices)
-    if (int rc = for_dev_slices(b, n, ctx->msm_slice, [&](size_t lo, size_t cnt, const DevBatch &s) {
+    if (int rc = for_dev_slices(b, n, ctx->knobs.msm_slice, [&](size_t lo, size_t cnt, const DevBatch &s) {
             return screen_slice(ctx, s, cnt, d_coeffs ? d_coeffs + (size_t)coeff_bytes * lo : nullptr, coeff_bytes, nullptr,
                                 d_status_out + lo);
         }))
@@ -1861,10 +1861,10 @@ extern "C" int ssa_verify_batch_screened(ssa_ctx *ctx, const uint8_t *sigs, cons
     if (n_fail_out) *n_fail_out = 0;
     if (n == 0) return 0;
     HIP_TRY(hipSetDevice(ctx->device));
-    if (n <= ctx->msm_small_max)
+    if (n <= ctx->knobs.msm_small_max)
         return ssa_verify_many(ctx, sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len, n, SSA_FLAG_SIG_FLAG_BYTE,
                                status_out, n_fail_out);
-    return run_host_slices_counted(ctx, b, n, ctx->msm_slice, n_fail_out,
+    return run_host_slices_counted(ctx, b, n, ctx->knobs.msm_slice, n_fail_out,
                                    [&](ssa_ctx *c, size_t lo, size_t cnt, const HostBatch &s, uint64_t *nf) {
                                        return screen_host_one(c, s, cnt, coeffs ? coeffs + 32 * lo : nullptr,
                                                               status_out + lo, nf);
@@ -1880,7 +1880,7 @@ extern "C" int ssa_verify_batch_screened(ssa_ctx *ctx, const uint8_t *sigs, cons
 // screen.  The screen only ever accepts: every nonzero status comes from the exact kernel.
 constexpr uint32_t MANY_SCREEN_FLAGS = SSA_FLAG_CHECK_TORSION | SSA_FLAG_SIG_FLAG_BYTE;
 
-// ONE slice (n <= ctx->lane_slice) on ctx->stream into d_status[0, n): d_h = the slice's challenge scalars if they exist
+// ONE slice (n <= ctx->knobs.lane_slice) on ctx->stream into d_status[0, n): d_h = the slice's challenge scalars if they exist
 // (else they are computed into ctx->ws_h).  Synchronises the stream twice: for u, and for the segment verdicts together
 // with the length of the re-check list.  With a key cache (ssa_verify_many_cached) the keys are
 // looked up there and only the unseen ones are checked; everything behind the key check is the same code.
@@ -1890,7 +1890,7 @@ static int screen_many_slice(ssa_ctx *ctx, const DevBatch &b, size_t n, const ui
     uint64_t sv[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     if (ctx->scr_fail.reserve(16)) return SSA_ERR_HIP;
     unsigned long long *scratch_fail = (unsigned long long *)ctx->scr_fail.p;    // (the caller counts the statuses)
-    if (n <= ctx->msm_small_max) {      // the exact per-lane path, the caller's flags
+    if (n <= ctx->knobs.msm_small_max) {      // the exact per-lane path, the caller's flags
         sv[6] = 1;
         const int rc = d_h ? ssa_internal_verify_hashed(ctx, b, d_h, n, flags, d_status, scratch_fail)
                            : ssa_verify_many_device(ctx, b.sigs, b.pks, b.pk_inf, b.msgs.msgs, b.msgs.off, b.msgs.stride,
@@ -1922,7 +1922,7 @@ static int screen_many_slice(ssa_ctx *ctx, const DevBatch &b, size_t n, const ui
     if (rc) return rc;
     // (the side stream of msm_run_one waits for everything queued on ctx->stream so far: the key check and the mask are
     //  ordered before the half of msm_k_prepare that reads the mask, and that half still runs under the hash)
-    const ScreenPlan pl = screen_plan(n, ctx->screen_segs);
+    const ScreenPlan pl = screen_plan(n, ctx->knobs.screen_segs);
     ScreenArgs sa{pl.segs, pl.seg_lanes / 256u, d_status, (u8 *)ctx->scr_ok.p};
     sa.lane_mask = (const u8 *)ctx->scr_mask.p;
     sa.recheck = mark;
@@ -1987,7 +1987,7 @@ static int screen_many_slice(ssa_ctx *ctx, const DevBatch &b, size_t n, const ui
 // slices of this call: SSA_LANE_SLICE lanes (the dedup table, the per-key tables and the screen share one slice)
 static size_t many_screen_slice_lanes(const ssa_ctx *ctx) {
     const size_t cap = (size_t)1 << 23;      // (msm_run_one: an item carries its point index in 24 bits)
-    return ctx->lane_slice < cap ? ctx->lane_slice : cap;
+    return ctx->knobs.lane_slice < cap ? ctx->knobs.lane_slice : cap;
 }
 
 // The device form of ssa_verify_many_screened (kc == nullptr, 8 statistics words) and of ssa_verify_many_cached (its key
@@ -2006,7 +2006,7 @@ static int many_screened_device(ssa_ctx *ctx, ssa_keycache *kc, const DevBatch &
     unsigned long long *d_fail;
     if (int rc = reset_fail_counter(ctx, d_n_fail_out, &d_fail)) return rc;
     if (n == 0) return 0;
-    if (n <= ctx->msm_small_max) {
+    if (n <= ctx->knobs.msm_small_max) {
         const int rc = ssa_verify_many_device(ctx, b.sigs, b.pks, b.pk_inf, b.msgs.msgs, b.msgs.off, b.msgs.stride,
                                               b.msgs.len, n, flags, d_status_out, (uint64_t *)d_fail);
         if (rc == 0 && stats_out) stats_out[6] = 1;
@@ -2076,7 +2076,7 @@ static int many_screened_host(ssa_ctx *ctx, ssa_keycache *kc, const HostBatch &b
     if (n_fail_out) *n_fail_out = 0;
     if (n == 0) return 0;
     HIP_TRY(hipSetDevice(ctx->device));
-    if (n <= ctx->msm_small_max) {
+    if (n <= ctx->knobs.msm_small_max) {
         const int rc = ssa_verify_many(ctx, b.sigs, b.pks, b.pk_inf, b.msgs, b.msg_off, b.msg_stride, b.msg_len, n, flags,
                                        status_out, n_fail_out);
         if (rc == 0 && stats_out) stats_out[6] = 1;

@@ -146,12 +146,12 @@ static int rng_stage_seed(ssa_ctx *ctx) {
     return 0;
 }
 
-// n scalars drawn slice by slice (at most ctx->lane_slice lanes of scratch, 32 B each), each slice handed to
+// n scalars drawn slice by slice (at most ctx->knobs.lane_slice lanes of scratch, 32 B each), each slice handed to
 // consume(lo, cnt, d_scalars) on the context's stream.  The device seed and the scratch are zeroed on the stream
 // after the last consumer, whichever way this returns.
 template <class F>
 static int rng_draw_slices(ssa_ctx *ctx, size_t n, F &&consume) {
-    const size_t slice = ctx->lane_slice < n ? ctx->lane_slice : n;
+    const size_t slice = ctx->knobs.lane_slice < n ? ctx->knobs.lane_slice : n;
     if (ctx->rng_scratch.reserve(slice * 32)) return SSA_ERR_HIP;
     SecretWipe wipe{ctx, {{&ctx->rng_scratch, slice * 32}, {&ctx->rng_seed, 64}}};
     if (int rc = rng_stage_seed(ctx)) return rc;

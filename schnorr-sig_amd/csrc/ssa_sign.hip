@@ -606,12 +606,7 @@ extern "C" void ssa_signer_set_destroy(ssa_signer_set *ss) {
     if (ss->ctx) {
         (void)hipSetDevice(ss->ctx->device);
         (void)hipStreamSynchronize(ss->ctx->stream);
-        auto &v = ss->ctx->signer_sets;
-        for (size_t i = 0; i < v.size(); i++)
-            if (v[i] == ss) {
-                v.erase(v.begin() + (long)i);
-                break;
-            }
+        forget_handle(ss->ctx->signer_sets, ss);
         ss->wipe_release();
     }
     delete ss;

@@ -236,6 +236,35 @@ def test_slices_on_two_streams_equal_one_stream(engine):
         two.close()
 
 
+def test_second_stream_set_inherits_the_contexts_knobs(engine):
+    """the twin is created at the first call of more than one slice, long after the environment the context was created
+    under is gone: it runs its slices under the CONTEXT's knobs all the same.  SSA_MSM_SLICE=2048 and SSA_MSM_SMALL_MAX=256
+    at creation, then 3 slices of 2048 signatures through the screened batch form: every slice is above the small-batch
+    bound and takes the MSM screen (one msm_k_prepare each, the twin's slice included).  A twin that read the environment
+    again would find the default bound of 3072 and run slice 1 through the per-lane kernels: 2 launches, not 3."""
+    import schnorr_sig_amd as ssa
+    rng = np.random.default_rng(5250)
+    n = 3 * 2048
+    sigs, pks, msgs = honest(engine, rng, n)
+    sigs, pks, msgs, inf, bad = _spoil(rng, sigs, pks, msgs, 8)
+    ref, nf_ref = engine.verify_many(sigs, pks, msgs, check_torsion=False, pk_inf=inf, sig_flag_byte=True)
+    os.environ["SSA_MSM_SLICE"], os.environ["SSA_MSM_SMALL_MAX"] = "2048", "256"
+    try:
+        eng = ssa.Engine(0)
+    finally:
+        del os.environ["SSA_MSM_SLICE"], os.environ["SSA_MSM_SMALL_MAX"]
+    try:
+        assert eng.info()["msm_slice"] == 2048 and eng.info()["two_streams"]
+        eng.enable_timing(True)
+        got, nf = eng.verify_batch_screened(sigs, pks, msgs, pk_inf=inf)
+        launches = eng.read_timing("msm_k_prepare")[1]
+        print("msm_k_prepare launches over 3 slices:", launches)
+        assert nf == nf_ref == 8 and (got == ref).all()
+        assert launches == 3
+    finally:
+        eng.close()
+
+
 # ---------------------------------------------------------------- PublicKey::from(&PrivateKey)
 def test_pubkey_many_is_one_base_multiplication(engine, oracle):
     """ssa_pubkey_many = PublicKey::from(&PrivateKey) (src/public.rs:26-32): the keys of the signer and of the oracle,
