@@ -696,6 +696,69 @@ def test_generated_files_are_up_to_date():
         assert os.path.getmtime(path) == mtime, "the freshness test wrote " + inc
 
 
+def _isa_probe_gen():
+    import importlib.util
+    import io
+    from contextlib import redirect_stdout
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("isa_probe_gen", os.path.join(root, "tools", "isa_probe", "gen.py"))
+    mod = importlib.util.module_from_spec(spec)
+    with redirect_stdout(io.StringIO()):
+        spec.loader.exec_module(mod)
+    return mod
+
+
+def test_isa_probe_is_up_to_date():
+    """tools/isa_probe/gen.py generates the probe program whose pieces tests/golden/isa_probe.sha256 records, kernel by
+    kernel (2 MB of text that are written outside git): no stale generator -- it imports the S-box generator's squaring
+    -- and no probe whose text moved unnoticed.  And every probe other than the sq_chains_N ones is, byte for byte, the
+    kernel of the committed tools/isa_probe/isa_probe.hip (the probe text of round 4, kept as measured).  Generated IN
+    MEMORY and compared, nothing is written."""
+    gen = _isa_probe_gen()
+    here = os.path.dirname(os.path.abspath(__file__))
+    assert os.path.abspath(gen.HASH_PATH) == os.path.join(here, "golden", "isa_probe.sha256")
+    assert os.path.abspath(gen.ROUND4_PATH) == os.path.join(os.path.dirname(here), "tools", "isa_probe", "isa_probe.hip")
+    mtimes = [os.path.getmtime(p) for p in (gen.HASH_PATH, gen.ROUND4_PATH)]
+    text = gen.generate()
+    want = dict(ln.split() for ln in open(gen.HASH_PATH).read().splitlines())
+    got = dict(ln.split() for ln in gen.probe_hashes(text).splitlines())
+    assert list(got) == list(want) == ["HEAD"] + [p[0] for p in gen.PROBES] + ["MAIN"], sorted(set(got) ^ set(want))
+    assert got == want, "not what tools/isa_probe/gen.py generates: %s" % [k for k in got if got[k] != want[k]]
+    assert {"sq_chains_2", "sq_chains_3"} <= set(got)
+    new, old = gen.pieces(text), gen.pieces(open(gen.ROUND4_PATH).read())
+    same = [k for k in new if not k.startswith("sq_chains_") and k != "MAIN"]       # MAIN holds the table of the probes' names
+    assert len(same) == len(gen.PROBES) - 5 + 1 and set(old) - set(same) == {"sq_chains_2", "sq_chains_3", "sq_chains_4", "sq_chains_6", "MAIN"}
+    assert [k for k in same if new[k] != old.get(k)] == []
+    strip = lambda t: "".join(ln for ln in t.splitlines(True) if '{"sq_chains_' not in ln)
+    assert strip(new["MAIN"]) == strip(old["MAIN"])                                  # ... and is the same but for those names
+    assert [os.path.getmtime(p) for p in (gen.HASH_PATH, gen.ROUND4_PATH)] == mtimes
+
+
+def test_regenerated_sq_chains_probes_on_the_cpu():
+    """the bodies of the sq_chains_N probes -- the current squaring on the probe's own registers and dummy pair, N chains
+    scheduled together -- in the interpreter (default min_gap: every carry's wait states): each chain's value is the
+    square mod p, or the lane's bit of the probe's sticky pair s[62:63] is set (the rule of
+    test_generated_sbox_asm_on_the_cpu).  One chain has no schedule without s_nop and hence no probe; its padded body is
+    run all the same."""
+    gen = _isa_probe_gen()
+    patterns = {name: pattern for name, pattern, _, _ in gen.PROBES}
+    assert "sq_chains_1" not in patterns
+    vals = [0, 1, P - 1, 2**32, 2**63, 2**64 - 1]
+    for n in (1, 2, 3):
+        body, lay = gen.sq_body(n), gen.sq_layout(n)
+        if n > 1:
+            assert patterns["sq_chains_%d" % n] == body and not any(ln.startswith("s_nop") for ln in body)
+        assert sum(ln.startswith("v_") for ln in body) == 11 * n
+        for i in range(len(vals)):
+            ins = [vals[(i + c) % len(vals)] for c in range(n)]
+            lane = ai.Lane({}, dummy_pairs=(lay.dummy,))
+            for g, x in zip(lay.chains, ins):
+                lane.v[g["X"]], lane.v[g["X"] + 1] = x & M32, x >> 32
+            lane.run(body)
+            got = [lane.v[g["X"]] | (lane.v[g["X"] + 1] << 32) for g in lay.chains]
+            assert lane.s.get(62, 0) or [v % P for v in got] == [x * x % P for x in ins], (n, [hex(x) for x in ins])
+
+
 def test_order_q_schedule_is_q():
     """qnaf.inc: the (gap, digit) schedule the subgroup check runs evaluates to the subgroup order (plain integers),
     uses only the odd table rows 1P..15P and never asks the window statement for zero doublings"""

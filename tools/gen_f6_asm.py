@@ -29,6 +29,8 @@ behind one branch per group of three reductions: see REDUCE_STEPS)
 """
 import os
 
+from asmgen import ENTRY_WAIT, clobbers, pad_wait_states, statement
+
 # caller-saved VGPRs above the argument registers and below v128 (a non-kernel function may not touch
 # v128+), as even-aligned pairs.  Three accumulators (27 registers) are live at a time; the first
 # group's six result words wait in RES until the end.
@@ -206,26 +208,19 @@ REDUCE_STEPS = [
 ]
 
 
-# First instruction of every block (as in tools/gen_jac_asm.py, where the reason was found): the compiler reloads values it
-# keeps in registers a block clobbers from scratch behind the block and does not wait for such a reload in front of the
-# NEXT block that merely clobbers the register; a reload still in flight would land in the block's accumulators.
-ENTRY_WAIT = "s_waitcnt vmcnt(0)"
+def reduce_regs(a, j, out):
+    """the names REDUCE_STEPS uses, for accumulator a as chain j of a group (carries s[4j:4j+3], mask s[14+2j:15+2j])"""
+    return {"c0p": a.pair(0), "c0l": a.lo(0), "c0h": a.hi(0), "c1l": a.lo(1), "c1h": a.hi(1), "c2l": a.lo(2), "c2h": a.hi(2),
+            "k0": a.kk(0), "k1": a.kk(1), "k2": a.kk(2), "A": "s[%d:%d]" % (4 * j, 4 * j + 1),
+            "B": "s[%d:%d]" % (4 * j + 2, 4 * j + 3), "T": "s[%d:%d]" % (14 + 2 * j, 15 + 2 * j), "outl": out[0], "outh": out[1]}
 
 
 def reduce3(accs, outs, label):
     """outs[j] = (lo, hi) destination of chain j's result; label: unique name stem of this group's cold path.
     Returns (hot lines, cold lines): the hot lines end in a branch to the cold path (taken ~once in 10^8 groups) and the
     label it returns to; the cold lines are to be placed out of the way by the caller."""
-    lines = []
-    ms = []
-    for j, a in enumerate(accs):
-        ms.append({"c0p": a.pair(0), "c0l": a.lo(0), "c0h": a.hi(0), "c1l": a.lo(1), "c1h": a.hi(1), "c2l": a.lo(2), "c2h": a.hi(2),
-                   "k0": a.kk(0), "k1": a.kk(1), "k2": a.kk(2), "A": "s[%d:%d]" % (4 * j, 4 * j + 1),
-                   "B": "s[%d:%d]" % (4 * j + 2, 4 * j + 3), "T": "s[%d:%d]" % (14 + 2 * j, 15 + 2 * j),
-                   "outl": outs[j][0], "outh": outs[j][1]})
-    for step in REDUCE_STEPS:
-        for m in ms:
-            lines.append(step.format(**m))
+    ms = [reduce_regs(a, j, outs[j]) for j, a in enumerate(accs)]
+    lines = [step.format(**m) for step in REDUCE_STEPS for m in ms]
     # any lane of any of the three chains negative?  (s_or sets SCC = result != 0; A of chain 0 is free by now)
     u = ms[0]["A"]
     lines += ["s_or_b64 %s, %s, %s" % (u, ms[0]["T"], ms[1]["T"]), "s_or_b64 %s, %s, %s" % (u, u, ms[2]["T"]),
@@ -282,64 +277,57 @@ def sqr_terms():
     return out
 
 
-def emit(name, terms, inputs, doc, extras=()):
-    """extras: fused linear terms (sign, small constant, operand prefix); their operand arrays are appended to inputs"""
-    accs = [Acc(j) for j in range(6)]
-    lines = [ENTRY_WAIT]
-    cold = []
-    bias, bias_setup = extras_bias(extras)
-    lines += bias_setup
-    for g in range(2):
-        for k in range(3 * g, 3 * g + 3):
+def product_groups(terms, extras, outs, labels):
+    """the accumulation of every coefficient -- terms[k]: its products, extras: fused linear terms (sign, small constant,
+    operand prefix) -- and the reductions, three coefficients at a time; outs[k] = (lo, hi) destination of coefficient k,
+    labels[g]: name stem of group g's cold path.  Returns (hot lines, cold lines) as reduce3 does."""
+    accs = [Acc(k) for k in range(len(terms))]
+    bias, setup = extras_bias(extras)
+    lines, cold = list(setup), []
+    for g, label in enumerate(labels):
+        ks = range(3 * g, 3 * g + 3)
+        for k in ks:
             t = terms[k]
             assert len(t) >= 2
             lines += init2(accs[k], t[0][0], t[0][1], t[1][0], t[1][1], bias)
             for x, y in t[2:]:
                 lines += mac(accs[k], x, y)
             lines += extra_terms(accs[k], k, extras)
-        if g == 0:   # inputs are still needed: park the results in fixed registers
-            outs = [("v%d" % RES[2 * j], "v%d" % RES[2 * j + 1]) for j in range(3)]
-        else:
-            outs = [("%%[r%dl]" % k, "%%[r%dh]" % k) for k in range(3, 6)]
-        hot, cld = reduce3(accs[3 * g:3 * g + 3], outs, "r%d" % g)
+        hot, cld = reduce3([accs[k] for k in ks], [outs[k] for k in ks], label)
         lines += hot
         cold += cld
-    for j in range(3):
-        lines.append("v_mov_b32 %%[r%dl], v%d" % (j, RES[2 * j]))
-        lines.append("v_mov_b32 %%[r%dh], v%d" % (j, RES[2 * j + 1]))
+    return lines, cold
+
+
+def emit(name, terms, inputs, doc, extras=()):
+    """one block of len(terms) = 6 (Fp6) or 3 (Fp3) coefficients; extras: fused linear terms (sign, small constant, operand
+    prefix), their operand arrays are appended to inputs"""
+    n = len(terms)
+    # the first group's results wait in the parking registers until the end: the inputs are still needed (six coefficients),
+    # and an output operand may share a register with an input the compiler still needs (three); a second group goes
+    # straight to the outputs
+    park = [("v%d" % RES[2 * j], "v%d" % RES[2 * j + 1]) for j in range(3)]
+    hot, cold = product_groups(terms, extras, park + [("%%[r%dl]" % k, "%%[r%dh]" % k) for k in range(3, n)],
+                               ["r%d" % g for g in range(n // 3)])
+    lines = [ENTRY_WAIT] + hot
+    for j, (lo, hi) in enumerate(park):
+        lines += ["v_mov_b32 %%[r%dl], %s" % (j, lo), "v_mov_b32 %%[r%dh], %s" % (j, hi)]
     lines += ["s_branch L_end_%="] + cold + ["L_end_%=:"]
-    used = set()
-    for ln in lines:
-        for tok in ln.replace(",", " ").split():
-            if tok.startswith("%["):
-                used.add(tok[2:-1])
-    out = ["// %s" % doc, "SSA_DEV void %s(%s, u64 (&r)[6]) {" % (name, ", ".join("const u64 (&%s)[6]" % n for n, _ in inputs))]
-    out.append("    u32 " + ", ".join("r%dl, r%dh" % (j, j) for j in range(6)) + ";")
-    out.append("    asm(")
-    for i, ln in enumerate(lines):
-        out.append('        "%s%s"' % (ln, "\\n\\t" if i + 1 < len(lines) else ""))
-    outs = []
-    for j in range(6):
-        outs.append('[r%dl] "=v"(r%dl)' % (j, j))
-        outs.append('[r%dh] "=v"(r%dh)' % (j, j))
-    out.append("        : " + ", ".join(outs))
+    used = {tok[2:-1] for ln in lines for tok in ln.replace(",", " ").split() if tok.startswith("%[")}
     ins = []
     for arr, prefix in inputs:
-        for j in range(6):
+        for j in range(n):
             nm = "%s%d" % (prefix, j)
             if nm + "l" in used or nm + "h" in used:
-                ins.append('[%sl] "v"(lo32(%s[%d]))' % (nm, arr, j))
-                ins.append('[%sh] "v"(hi32(%s[%d]))' % (nm, arr, j))
-    out.append("        : " + ",\n          ".join(ins))
+                ins += ['[%sl] "v"(lo32(%s[%d]))' % (nm, arr, j), '[%sh] "v"(hi32(%s[%d]))' % (nm, arr, j)]
     n_fixed = N_FIXED + (4 if any(sg < 0 for sg, _, _ in extras) else 0)
-    n_sgpr = 20       # s[0:11] carries, s[12:13] the bias of the fused blocks, s[14:19] scratch masks of the reductions
-    clob = ['"v%d"' % r for r in POOL[:n_fixed]] + ['"s%d"' % i for i in range(n_sgpr)] + ['"vcc"', '"scc"']
-    out.append("        : " + ", ".join(clob) + ");")
-    for j in range(6):
-        out.append("    r[%d] = mk64(r%dl, r%dh);" % (j, j, j))
-    out.append("}")
-    nm = sum(1 for ln in lines if ln.startswith("v_mad"))
-    return out, len(lines), nm
+    # s[0:11] carries, s[12:13] the bias of the fused blocks, s[14:19] scratch masks of the reductions
+    out = statement([doc], "void %s(%s, u64 (&r)[%d])" % (name, ", ".join("const u64 (&%s)[%d]" % (a, n) for a, _ in inputs), n),
+                    lines, [", ".join('[r%dl] "=v"(r%dl), [r%dh] "=v"(r%dh)' % (j, j, j, j) for j in range(n))], ins,
+                    clobbers(POOL[:n_fixed], 20, ("vcc", "scc")),
+                    before=["u32 " + ", ".join("r%dl, r%dh" % (j, j) for j in range(n)) + ";"],
+                    after=["r[%d] = mk64(r%dl, r%dh);" % (j, j, j) for j in range(n)])
+    return out, len(lines), sum(1 for ln in lines if ln.startswith("v_mad"))
 
 
 # ---- Fp3 = Fp[t]/(t^3 - 7): the product and the square of the square-root descent (fp3.hpp, round 4) -------------------
@@ -359,117 +347,28 @@ def f3_sqr_terms():
             [("a0", "d2"), ("a1", "a1")]]
 
 
-def emit3(name, terms, inputs, doc):
-    accs = [Acc(j) for j in range(3)]
-    lines = [ENTRY_WAIT]
-    for k in range(3):
-        t = terms[k]
-        lines += init2(accs[k], t[0][0], t[0][1], t[1][0], t[1][1], None)
-        for x, y in t[2:]:
-            lines += mac(accs[k], x, y)
-    # the inputs are dead once the last product is issued, but an output operand may share a register with an input the
-    # compiler still needs: the results wait in the parking registers until the end, as in the six-coefficient blocks
-    outs = [("v%d" % RES[2 * j], "v%d" % RES[2 * j + 1]) for j in range(3)]
-    hot, cold = reduce3(accs, outs, "r0")
-    lines += hot
-    for j in range(3):
-        lines.append("v_mov_b32 %%[r%dl], v%d" % (j, RES[2 * j]))
-        lines.append("v_mov_b32 %%[r%dh], v%d" % (j, RES[2 * j + 1]))
-    lines += ["s_branch L_end_%="] + cold + ["L_end_%=:"]
-    used = set()
-    for ln in lines:
-        for tok in ln.replace(",", " ").split():
-            if tok.startswith("%["):
-                used.add(tok[2:-1])
-    out = ["// %s" % doc, "SSA_DEV void %s(%s, u64 (&r)[3]) {" % (name, ", ".join("const u64 (&%s)[3]" % n for n, _ in inputs))]
-    out.append("    u32 " + ", ".join("r%dl, r%dh" % (j, j) for j in range(3)) + ";")
-    out.append("    asm(")
-    for i, ln in enumerate(lines):
-        out.append('        "%s%s"' % (ln, "\\n\\t" if i + 1 < len(lines) else ""))
-    outs = []
-    for j in range(3):
-        outs.append('[r%dl] "=v"(r%dl)' % (j, j))
-        outs.append('[r%dh] "=v"(r%dh)' % (j, j))
-    out.append("        : " + ", ".join(outs))
-    ins = []
-    for arr, prefix in inputs:
-        for j in range(3):
-            nm = "%s%d" % (prefix, j)
-            if nm + "l" in used or nm + "h" in used:
-                ins.append('[%sl] "v"(lo32(%s[%d]))' % (nm, arr, j))
-                ins.append('[%sh] "v"(hi32(%s[%d]))' % (nm, arr, j))
-    out.append("        : " + ",\n          ".join(ins))
-    clob = ['"v%d"' % r for r in POOL[:N_FIXED]] + ['"s%d"' % i for i in range(20)] + ['"vcc"', '"scc"']
-    out.append("        : " + ", ".join(clob) + ");")
-    for j in range(3):
-        out.append("    r[%d] = mk64(r%dl, r%dh);" % (j, j, j))
-    out.append("}")
-    nm = sum(1 for ln in lines if ln.startswith("v_mad"))
-    return out, len(lines), nm
-
-
 # ---- one accumulator: r = x0 y0 + x1 y1 + x2 y2 (mod p) -- what ONE lane of the cooperative kernels computes per product
 # round (ssa_coop.hpp coop_group_mul: twelve lanes per Fp6 product, three terms each).  The latency path: the reduction
 # of a single chain cannot fill the wait states of its carries with a neighbour's instructions, so they are padded (s_nop).
-def pad_wait_states(lines, gap=3):
-    """insert s_nop so that a VALU read of an SGPR pair / VCC comes at least `gap` positions after its VALU write"""
-    import re
-    out, written = [], {}
-    for ln in lines:
-        if ln.startswith("v_"):
-            ops = [o.strip() for o in ln.split(None, 1)[1].split(",")]
-            mnem = ln.split()[0]
-            n_dst = 2 if mnem in ("v_mad_u64_u32", "v_add_co_u32", "v_addc_co_u32", "v_sub_co_u32", "v_subb_co_u32", "v_subbrev_co_u32") else 1
-            reads = [o for o in ops[n_dst:] if re.match(r"(s\[\d+:\d+\]|vcc)$", o)]
-            need = 0
-            for r in reads:
-                if r in written:
-                    need = max(need, gap - (len(out) - written[r]))
-            if need > 0:
-                out.append("s_nop %d" % (need - 1))
-                # an s_nop N occupies one position and N + 1 wait states: account for it as `need` positions
-                for k in list(written):
-                    written[k] -= need - 1
-            out.append(ln)
-            if n_dst == 2 and re.match(r"(s\[\d+:\d+\]|vcc)$", ops[1]):
-                written[ops[1]] = len(out) - 1
-        else:
-            out.append(ln)
-    return out
-
-
 def emit_acc3(name, doc):
     acc = Acc(0)
-    lines = [ENTRY_WAIT] + init2(acc, "x0", "y0", "x1", "y1", None) + mac(acc, "x2", "y2")
-    m = {"c0p": acc.pair(0), "c0l": acc.lo(0), "c0h": acc.hi(0), "c1l": acc.lo(1), "c1h": acc.hi(1), "c2l": acc.lo(2),
-         "c2h": acc.hi(2), "k0": acc.kk(0), "k1": acc.kk(1), "k2": acc.kk(2), "A": "s[0:1]", "B": "s[2:3]", "T": "s[14:15]",
-         "outl": "%[rl]", "outh": "%[rh]"}
-    red = [st.format(**m) for st in REDUCE_STEPS]
-    lines = pad_wait_states(lines + red)
+    m = reduce_regs(acc, 0, ("%[rl]", "%[rh]"))
+    lines = pad_wait_states([ENTRY_WAIT] + init2(acc, "x0", "y0", "x1", "y1", None) + mac(acc, "x2", "y2") +
+                            [st.format(**m) for st in REDUCE_STEPS])
     # the rare negative result (mask T, SCC from s_andn2): - EPS = + (1, 2^32 - 1) in the flagged lanes
     lines += ["s_cbranch_scc1 L_fix_%=", "L_back_%=:", "s_branch L_end_%=", "L_fix_%=:",
               "v_cndmask_b32_e64 {k0}, 0, 1, {T}".format(**m), "v_cndmask_b32_e64 {k1}, 0, -1, {T}".format(**m),
               "v_add_co_u32 %[rl], {A}, %[rl], {k0}".format(**m), "s_nop 1",
               "v_addc_co_u32 %[rh], {A}, %[rh], {k1}, {A}".format(**m), "s_branch L_back_%=", "L_end_%=:"]
-    out = ["// %s" % doc, "SSA_DEV u64 %s(const u64 (&x)[3], const u64 (&y)[3]) {" % name, "    u32 rl, rh;", "    asm("]
-    for i, ln in enumerate(lines):
-        out.append('        "%s%s"' % (ln, "\\n\\t" if i + 1 < len(lines) else ""))
-    out.append('        : [rl] "=&v"(rl), [rh] "=&v"(rh)')
-    ins = []
-    for arr in ("x", "y"):
-        for j in range(3):
-            ins.append('[%s%dl] "v"(lo32(%s[%d]))' % (arr, j, arr, j))
-            ins.append('[%s%dh] "v"(hi32(%s[%d]))' % (arr, j, arr, j))
-    out.append("        : " + ",\n          ".join(ins))
+    ins = ['[%s%d%s] "v"(%s(%s[%d]))' % (arr, j, h, fn, arr, j) for arr in ("x", "y") for j in range(3)
+           for h, fn in (("l", "lo32"), ("h", "hi32"))]
     fixed = sorted(set(r for pr in acc.c for r in pr) | set(acc.k))
-    clob = ['"v%d"' % r for r in fixed] + ['"s%d"' % i for i in (0, 1, 2, 3, 4, 5, 14, 15)] + ['"vcc"', '"scc"']
-    out.append("        : " + ", ".join(clob) + ");")
-    out += ["    return mk64(rl, rh);", "}"]
+    out = statement([doc], "u64 %s(const u64 (&x)[3], const u64 (&y)[3])" % name, lines, ['[rl] "=&v"(rl), [rh] "=&v"(rh)'], ins,
+                    clobbers(fixed, (0, 1, 2, 3, 4, 5, 14, 15), ("vcc", "scc")), before=["u32 rl, rh;"], after=["return mk64(rl, rh);"])
     n_valu = sum(1 for ln in lines if ln.startswith("v_"))
     n_nop = sum(int(ln.split()[1]) + 1 for ln in lines if ln.startswith("s_nop"))
     print("%s: %d VALU instructions on the hot path + %d wait states" % (name, n_valu - 4, n_nop - 2))
     return out
-
 
 OUT_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "schnorr-sig_amd", "csrc", "fp6_asm.inc")
 
@@ -505,7 +404,7 @@ def generate():
             ("f3_mul_core_asm", f3_mul_terms(), [("a", "a"), ("b", "b"), ("b7", "s")], "r = a * b in Fp[t]/(t^3 - 7); b7[j] = 7 b[j] (j = 1, 2)"),
             ("f3_sqr_core_asm", f3_sqr_terms(), [("a", "a"), ("a2", "d"), ("a7", "s"), ("a14", "t")],
              "r = a^2 in Fp[t]/(t^3 - 7); a2[j] = 2 a[j] (j = 1, 2), a7[2] = 7 a[2], a14[2] = 14 a[2]")):
-        blk, nl, nmad = emit3(nm, terms, ins, doc)
+        blk, nl, nmad = emit(nm, terms, ins, doc)
         print("%s: %d instructions, %d mads" % (nm, nl, nmad))
         f3 += [""] + blk
     acc3 = [""] + emit_acc3("fp_acc3_core_asm", "r = x0 y0 + x1 y1 + x2 y2 (mod p, loose): one lane's share of a cooperative Fp6 product")

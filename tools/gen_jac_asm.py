@@ -28,6 +28,11 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import gen_f6_asm as g6
+from asmgen import ENTRY_WAIT, clobbers, pinned, statement
+
+# the fair-turn experiment (see fair_read below): 0 off, 1 once per doubling, 2 after every Fp6 block (~400 instructions)
+FAIR = int(os.environ.get("SSA_GEN_FAIR", "0"))
+FAIR_SHIFT = int(os.environ.get("SSA_GEN_FAIR_SHIFT", "13"))
 
 # ---- registers ------------------------------------------------------------------------------------------------
 # The point: callee-saved VGPRs of the amdgpu calling convention (v136-143, v152-159, ...), so that it survives the
@@ -37,7 +42,13 @@ PIN = [136, 138, 140, 142, 152, 154,      # X
        184, 186, 188, 190, 200, 202]      # Z
 XR, YR, ZR = PIN[0:6], PIN[6:12], PIN[12:18]
 _G6_FIXED = set(g6.POOL[:g6.N_FIXED + 4])               # accumulators, counters, complements (gen_f6_asm's registers)
-_pin_regs = set(r for p in PIN for r in (p, p + 1))
+
+
+def pair_regs(pairs):
+    return set(r for p in pairs for r in (p, p + 1))
+
+
+_pin_regs = pair_regs(PIN)
 FREE = [r for r in range(56, 256, 2) if r not in _G6_FIXED and r + 1 not in _G6_FIXED and r not in _pin_regs]
 
 
@@ -69,6 +80,7 @@ class Gen:
         self.cold = []          # cold paths, after the loop
         self.nsite = 0
         self.nred = 0           # groups of three reductions (one cold path each: gen_f6_asm.reduce3)
+        self.nfair = 0          # fair-turn sites between Fp6 blocks (FAIR = 2)
         a = self.al
         self.IN = [a.free.pop() for _ in range(n_pinned_in)][::-1]    # further pinned operands (highest free pairs)
         self.S = [a.fp6() for _ in range(n_slots)]    # Fp6 temporaries
@@ -157,22 +169,10 @@ class Gen:
     def block(self, terms, regs, out, extras=(), extra_regs=None):
         """terms[k]: [(name, name)]; regs: {name: pair}; out: six pairs; extras: [(sign, c, prefix)] with
         extra_regs[prefix] = six pairs"""
-        accs = [g6.Acc(j) for j in range(6)]
-        lines = []
-        bias, bias_setup = g6.extras_bias(extras)
-        lines += bias_setup
-        for g in range(2):
-            for k in range(3 * g, 3 * g + 3):
-                t = terms[k]
-                lines += g6.init2(accs[k], t[0][0], t[0][1], t[1][0], t[1][1], bias)
-                for x, y in t[2:]:
-                    lines += g6.mac(accs[k], x, y)
-                lines += g6.extra_terms(accs[k], k, extras)
-            outs = [("v%d" % out[k], "v%d" % (out[k] + 1)) for k in range(3 * g, 3 * g + 3)]
-            hot, cold = g6.reduce3(accs[3 * g:3 * g + 3], outs, "%sred%d" % (self.tag, self.nred))
-            self.nred += 1
-            lines += hot
-            self.cold += cold
+        lines, cold = g6.product_groups(terms, extras, [("v%d" % r, "v%d" % (r + 1)) for r in out],
+                                        ["%sred%d" % (self.tag, self.nred + g) for g in range(2)])
+        self.nred += 2
+        self.cold += cold
         m = dict(regs)
         for _, _, prefix in extras:
             for k in range(6):
@@ -182,7 +182,7 @@ class Gen:
             nm, half = mo.group(1), mo.group(2)
             return "v%d" % (m[nm] + (1 if half == "h" else 0))
         self.main += [re.sub(r"%\[(\w+?)([lh])\]", sub, ln) for ln in lines]
-        self.nfair = getattr(self, "nfair", 0) + 1
+        self.nfair += 1
         self.main += fair_now("%sq%d" % (self.tag, self.nfair))
 
     # ---- dst = (2)a - b coefficient-wise (a = None: -b); one guard: the doubling needs a's high word below all ones,
@@ -327,13 +327,6 @@ def build_dbl(tag=""):
     return gen
 
 
-# First instruction of every statement.  The compiler keeps values in registers these statements clobber and reloads them from
-# scratch behind each statement; it waits for such a reload where the VALUE is next used -- not in front of an inline asm
-# that merely clobbers the register (measured: ssa_k_sign entered the gathering addition with four reloads in flight, which
-# then landed in the statement's temporaries: wrong signatures on ~7 % of the waves, different ones from run to run).  The
-# statements whose operands the compiler loads itself were shielded by its wait for those operands; the gathering ones are
-# not.  So: nothing of the compiler's may be in flight when a statement starts.
-ENTRY_WAIT = "s_waitcnt vmcnt(0)"
 Q_WAIT = "s_waitcnt vmcnt(2)"       # late_q: the statement's own six loads of (x2, y2) have landed; its two touches may be out
 
 
@@ -425,8 +418,6 @@ def build_madd(tag="", late_q=False):
 # end) and in the compiled phases, the first generation's spread shrinks from 2.19-3.75 to 2.73-3.78 ms and the kernel
 # time does not move (26.70 against 26.65 ms); ssa_k_hash with four rotating priorities gets 4.6 % SLOWER.  Whatever
 # favours slot 0 in a kernel whose code does not fit the instruction buffers is not the issue arbitration alone.
-FAIR = int(os.environ.get("SSA_GEN_FAIR", "0"))      # 0 off, 1 once per doubling, 2 after every Fp6 block (~400 instructions)
-FAIR_SHIFT = int(os.environ.get("SSA_GEN_FAIR_SHIFT", "13"))
 
 
 def fair_read():
@@ -460,69 +451,80 @@ def check_and_stats(gen, body, pinned):
     return used, n_valu, n_mad, n_nop
 
 
-def asm_lines(out, body):
-    for i, ln in enumerate(body):
-        out.append('        "%s%s"' % (ln, "\\n\\t" if i + 1 < len(body) else ""))
+PF = 117         # the touches' landing register: outside every register the statements name
+KEEP = 38        # v[38:39]: outside every register the window / gather statements name
+
+# ---- the pieces the four statements are put together from ----
+POINT_ARGS = "u64 (&X)[6], u64 (&Y)[6], u64 (&Z)[6]"
+N_OPERAND = '[n] "s"(__builtin_amdgcn_readfirstlane(n))'
+OK_OUT = '[ok] "=&v"(ok)'
+SET_OK = "v_mov_b32 %[ok], 1"
+BAIL = ["L_bail_%=:", "v_mov_b32 %[ok], 0"]          # a possible exceptional input of the addition: report 0
+RETURNS_OK = dict(volatile=True, before=["u32 ok;"], after=["return ok;"])
+
+
+def zeros(regs):
+    return ["v_mov_b32 v%d, 0" % r for r in regs]
+
+
+def point_operands():
+    return pinned(XR, "X") + pinned(YR, "Y") + pinned(ZR, "Z")
+
+
+def keep_operand(used, pinned_regs):
+    assert not ({KEEP, KEEP + 1} & (set(used) | set(pinned_regs)))
+    return '"+{v[%d:%d]}"(keep)' % (KEEP, KEEP + 1)
+
+
+def row_loads(IN):
+    """the six 16-byte loads of (x2, y2) = row[0..11] into IN's 24 consecutive VGPRs"""
+    assert IN == list(range(IN[0], IN[0] + 24, 2)) and IN[0] % 4 == 0
+    return ["global_load_dwordx4 v[%d:%d], %%[row], off%s" % (IN[0] + 4 * k, IN[0] + 4 * k + 3, " offset:%d" % (16 * k) if k else "")
+            for k in range(6)]
+
+
+def loop_top():
+    return ["s_mov_b32 s20, %[n]", "L_top_%=:"] + fair_read()
+
+
+def loop_end():
+    return fair_set("f") + ["s_sub_u32 s20, s20, 1", "s_cmp_lg_u32 s20, 0", "s_cbranch_scc1 L_top_%="]
+
+
+def sgpr_clobbers(exec_saved=False):
+    """SGPRs a statement clobbers, as a count from s0: carries, masks and the loop counter s20; s[22:23] where EXEC is saved
+    (the window); s21 and s[24:25] for the fair turns"""
+    return 26 if FAIR else (24 if exec_saved else 21)
 
 
 def emit_dbl():
     gen = build_dbl()
-    pre = [ENTRY_WAIT] + ["v_mov_b32 v%d, 0" % r for r in gen.zero_regs] + ["s_mov_b32 s20, %[n]", "L_top_%=:"] + fair_read()
-    post = fair_set("f") + ["s_sub_u32 s20, s20, 1", "s_cmp_lg_u32 s20, 0", "s_cbranch_scc1 L_top_%=", "s_branch L_end_%="]
-    body = pre + gen.main + post + gen.cold + ["L_end_%=:"]
+    body = [ENTRY_WAIT] + zeros(gen.zero_regs) + loop_top() + gen.main + loop_end() + ["s_branch L_end_%="] + gen.cold + ["L_end_%=:"]
     used, n_valu, n_mad, n_nop = check_and_stats(gen, body, _pin_regs)
-    out = ["// (X, Y, Z) <- [2^n](X, Y, Z), n >= 1, Jacobian, a = 1 (loose in / loose out; Z == 0 stays Z == 0).",
-           "// One doubling: %d VALU instructions (%d multiplies) + %d s_nop on the hot path." % (n_valu, n_mad, n_nop),
-           "SSA_DEV void jac_dbl_n_asm(u64 (&X)[6], u64 (&Y)[6], u64 (&Z)[6], u32 n) {", "    asm volatile("]
-    asm_lines(out, body)
-    ops = []
-    for nm, regs in (("X", XR), ("Y", YR), ("Z", ZR)):
-        for j in range(6):
-            ops.append('"+{v[%d:%d]}"(%s[%d])' % (regs[j], regs[j] + 1, nm, j))
-    out.append("        : " + ",\n          ".join(ops))
-    out.append('        : [n] "s"(__builtin_amdgcn_readfirstlane(n))      // wave-uniform by contract')
-    clob = ['"v%d"' % r for r in sorted(used)] + ['"s%d"' % i for i in range(26 if FAIR else 21)] + ['"vcc"', '"scc"']
-    out.append("        : " + ", ".join(clob) + ");")
-    out.append("}")
     print("doubling: %d VALU (%d multiplies), %d s_nop; %d fixed VGPRs + 36 pinned; %d cold-path lines"
           % (n_valu, n_mad, n_nop, len(used), len(gen.cold)))
-    return out
+    return statement(["(X, Y, Z) <- [2^n](X, Y, Z), n >= 1, Jacobian, a = 1 (loose in / loose out; Z == 0 stays Z == 0).",
+                      "One doubling: %d VALU instructions (%d multiplies) + %d s_nop on the hot path." % (n_valu, n_mad, n_nop)],
+                     "void jac_dbl_n_asm(%s, u32 n)" % POINT_ARGS, body, point_operands(),
+                     [N_OPERAND + "      // wave-uniform by contract"], clobbers(sorted(used), sgpr_clobbers(), ("vcc", "scc")), volatile=True)
+
+
+def madd_body(gen, loads=()):
+    return [ENTRY_WAIT] + list(loads) + zeros(gen.zero_regs) + [SET_OK] + gen.main + ["s_branch L_end_%="] + gen.cold + BAIL + ["L_end_%=:"]
 
 
 def emit_madd():
     gen = build_madd()
-    pinned = _pin_regs | set(r for p in gen.IN for r in (p, p + 1))
-    pre = [ENTRY_WAIT] + ["v_mov_b32 v%d, 0" % r for r in gen.zero_regs] + ["v_mov_b32 %[ok], 1"]
-    post = ["s_branch L_end_%="]
-    bail = ["L_bail_%=:", "v_mov_b32 %[ok], 0"]
-    body = pre + gen.main + post + gen.cold + bail + ["L_end_%=:"]
-    used, n_valu, n_mad, n_nop = check_and_stats(gen, [ln for ln in body if "%[ok]" not in ln], pinned)
-    out = ["// (X, Y, Z) += (x2, y2): the generic path of the mixed addition; returns 0 with the point untouched when an",
-           "// exceptional input is possible (Z, x2 or H with a first coefficient = 0 mod p): the caller then runs jac_madd.",
-           "// %d VALU instructions (%d multiplies) + %d s_nop on the hot path." % (n_valu, n_mad, n_nop),
-           "SSA_DEV u32 jac_madd_asm(u64 (&X)[6], u64 (&Y)[6], u64 (&Z)[6], const u64 (&x2)[6], const u64 (&y2)[6]) {",
-           "    u32 ok;", "    asm volatile("]
-    asm_lines(out, body)
-    ops = ['[ok] "=&v"(ok)']
-    for nm, regs in (("X", XR), ("Y", YR), ("Z", ZR)):
-        for j in range(6):
-            ops.append('"+{v[%d:%d]}"(%s[%d])' % (regs[j], regs[j] + 1, nm, j))
-    out.append("        : " + ",\n          ".join(ops))
-    ins = []
-    for nm, regs in (("x2", gen.IN[0:6]), ("y2", gen.IN[6:12])):
-        for j in range(6):
-            ins.append('"{v[%d:%d]}"(%s[%d])' % (regs[j], regs[j] + 1, nm, j))
-    out.append("        : " + ",\n          ".join(ins))
-    clob = ['"v%d"' % r for r in sorted(used)] + ['"s%d"' % i for i in range(26 if FAIR else 21)] + ['"vcc"', '"scc"']
-    out.append("        : " + ", ".join(clob) + ");")
-    out += ["    return ok;", "}"]
+    body = madd_body(gen)
+    used, n_valu, n_mad, n_nop = check_and_stats(gen, [ln for ln in body if "%[" not in ln], _pin_regs | pair_regs(gen.IN))
     print("mixed addition: %d VALU (%d multiplies), %d s_nop; %d fixed VGPRs + 60 pinned; %d cold-path lines"
           % (n_valu, n_mad, n_nop, len(used), len(gen.cold)))
-    return out
-
-
-PF = 117         # the touches' landing register: outside every register the statements name
-KEEP = 38        # v[38:39]: outside every register the window / gather statements name
+    return statement(["(X, Y, Z) += (x2, y2): the generic path of the mixed addition; returns 0 with the point untouched when an",
+                      "exceptional input is possible (Z, x2 or H with a first coefficient = 0 mod p): the caller then runs jac_madd.",
+                      "%d VALU instructions (%d multiplies) + %d s_nop on the hot path." % (n_valu, n_mad, n_nop)],
+                     "u32 jac_madd_asm(%s, const u64 (&x2)[6], const u64 (&y2)[6])" % POINT_ARGS, body, [OK_OUT] + point_operands(),
+                     pinned(gen.IN[0:6], "x2", "") + pinned(gen.IN[6:12], "y2", ""),
+                     clobbers(sorted(used), sgpr_clobbers(), ("vcc", "scc")), **RETURNS_OK)
 
 
 def emit_madd_gather():
@@ -533,44 +535,23 @@ def emit_madd_gather():
     additions' own loads are awaited after the 57 products that do not need them (loads return in order: vmcnt(2)), the
     touches at the end of the statement, long landed."""
     gen = build_madd("g", late_q=True)
-    in_regs = set(r for p in gen.IN for r in (p, p + 1))
-    assert gen.IN == list(range(gen.IN[0], gen.IN[0] + 24, 2)) and gen.IN[0] % 4 == 0
-    pinned = _pin_regs | in_regs
-    loads = ["global_load_dwordx4 v[%d:%d], %%[row], off%s" % (gen.IN[0] + 4 * k, gen.IN[0] + 4 * k + 3, " offset:%d" % (16 * k) if k else "")
-             for k in range(6)]
-    loads += ["global_load_dword v%d, %%[next], off" % PF, "global_load_dword v%d, %%[next], off offset:92" % PF]
-    pre = [ENTRY_WAIT] + loads + ["v_mov_b32 v%d, 0" % r for r in gen.zero_regs] + ["v_mov_b32 %[ok], 1"]
-    post = ["s_branch L_end_%="]
-    bail = ["L_bail_%=:", "v_mov_b32 %[ok], 0"]
-    body = pre + gen.main + post + gen.cold + bail + ["L_end_%=:", "s_waitcnt vmcnt(0)"]
+    in_regs = pair_regs(gen.IN)
+    touches = ["global_load_dword v%d, %%[next], off" % PF, "global_load_dword v%d, %%[next], off offset:92" % PF]
+    body = madd_body(gen, row_loads(gen.IN) + touches) + ["s_waitcnt vmcnt(0)"]
     assert body.count(Q_WAIT) == 1
-    used, n_valu, n_mad, n_nop = check_and_stats(gen, [ln for ln in body if "%[" not in ln], pinned | {PF})
+    used, n_valu, n_mad, n_nop = check_and_stats(gen, [ln for ln in body if "%[" not in ln], _pin_regs | in_regs | {PF})
     used = used | in_regs | {PF}
     assert PF not in _pin_regs and PF not in set(gen.al.used)
-    out = ["// (X, Y, Z) += the point at row[0..11], gathered by the statement itself; `next`: the entry the NEXT addition will",
-           "// want (its first and last word are loaded and dropped: a prefetch).  Returns 0 with the point untouched when an",
-           "// exceptional input is possible: the caller then loads the point and runs jac_madd.",
-           "// %d VALU instructions (%d multiplies) + %d s_nop on the hot path." % (n_valu, n_mad, n_nop),
-           "// keep: as in jac_window_asm (the table's base, handed through in v[%d:%d])." % (KEEP, KEEP + 1),
-           "SSA_DEV u32 jac_madd_gather_asm(u64 (&X)[6], u64 (&Y)[6], u64 (&Z)[6], const u64 *row, const u64 *next, const u64 *&keep) {",
-           "    u32 ok;", "    asm volatile("]
-    asm_lines(out, body)
-    ops = ['[ok] "=&v"(ok)']
-    for nm, regs in (("X", XR), ("Y", YR), ("Z", ZR)):
-        for j in range(6):
-            ops.append('"+{v[%d:%d]}"(%s[%d])' % (regs[j], regs[j] + 1, nm, j))
-    assert KEEP not in used and KEEP + 1 not in used and KEEP not in pinned and KEEP + 1 not in pinned
-    ops.append('"+{v[%d:%d]}"(keep)' % (KEEP, KEEP + 1))
-    out.append("        : " + ",\n          ".join(ops))
-    out.append('        : [row] "v"(row), [next] "v"(next)')
-    clob = ['"v%d"' % r for r in sorted(used)] + ['"s%d"' % i for i in range(26 if FAIR else 21)] + ['"vcc"', '"scc"', '"memory"']
-    out.append("        : " + ", ".join(clob) + ");")
-    out += ["    return ok;", "}"]
     print("mixed addition with its gather: %d VALU (%d multiplies), %d s_nop; %d VGPRs + 36 pinned; %d cold-path lines"
           % (n_valu, n_mad, n_nop, len(used), len(gen.cold)))
-    return out
-
-
+    return statement(["(X, Y, Z) += the point at row[0..11], gathered by the statement itself; `next`: the entry the NEXT addition will",
+                      "want (its first and last word are loaded and dropped: a prefetch).  Returns 0 with the point untouched when an",
+                      "exceptional input is possible: the caller then loads the point and runs jac_madd.",
+                      "%d VALU instructions (%d multiplies) + %d s_nop on the hot path." % (n_valu, n_mad, n_nop),
+                      "keep: as in jac_window_asm (the table's base, handed through in v[%d:%d])." % (KEEP, KEEP + 1)],
+                     "u32 jac_madd_gather_asm(%s, const u64 *row, const u64 *next, const u64 *&keep)" % POINT_ARGS, body,
+                     [OK_OUT] + point_operands() + [keep_operand(used, _pin_regs | in_regs)], ['[row] "v"(row), [next] "v"(next)'],
+                     clobbers(sorted(used), sgpr_clobbers(), ("vcc", "scc", "memory")), **RETURNS_OK)
 
 
 def emit_window():
@@ -582,46 +563,26 @@ def emit_window():
     (profiles/r05/gather_ab.txt).  The wait stands in front of the EXEC narrowing, on every path out of the statement: the
     loaded registers are the statement's clobbers, the compiler may reuse them right behind it."""
     gd, gm = build_dbl("d"), build_madd("m")
-    in_regs = set(r for p in gm.IN for r in (p, p + 1))
+    in_regs = pair_regs(gm.IN)
     assert not (set(gd.al.used) & in_regs)
-    assert gm.IN == list(range(gm.IN[0], gm.IN[0] + 24, 2)) and gm.IN[0] % 4 == 0      # x2, y2: 24 consecutive VGPRs
-    pinned = _pin_regs | in_regs
-    loads = ["global_load_dwordx4 v[%d:%d], %%[row], off%s" % (gm.IN[0] + 4 * k, gm.IN[0] + 4 * k + 3, " offset:%d" % (16 * k) if k else "")
-             for k in range(6)]
-    pre = [ENTRY_WAIT] + loads + ["v_mov_b32 v%d, 0" % r for r in gd.zero_regs] + ["v_mov_b32 %[ok], 1", "s_mov_b32 s20, %[n]", "L_top_%=:"] + fair_read()
-    loop_end = fair_set("f") + ["s_sub_u32 s20, s20, 1", "s_cmp_lg_u32 s20, 0", "s_cbranch_scc1 L_top_%=", "s_waitcnt vmcnt(0)"]
+    pinned_regs = _pin_regs | in_regs
     narrow = ["v_cmp_ne_u32 vcc, 0, %[act]", "s_and_saveexec_b64 s[22:23], vcc", "s_cbranch_execz L_skip_%="]
-    zero_m = ["v_mov_b32 v%d, 0" % r for r in gm.zero_regs if r not in gd.zero_regs]
     skip = ["L_skip_%=:", "s_mov_b64 exec, s[22:23]", "s_branch L_end_%="]
-    bail = ["L_bail_%=:", "v_mov_b32 %[ok], 0", "s_branch L_skip_%="]
-    body = pre + gd.main + loop_end + narrow + zero_m + gm.main + skip + gd.cold + gm.cold + bail + ["L_end_%=:"]
-    plain = [ln for ln in body if "%[" not in ln]
-    used_d, nv_d, nm_d, nn_d = check_and_stats(gd, [ln for ln in plain], pinned | set(gm.al.used) | set(g6.POOL[:g6.N_FIXED + 4]))
-    used = used_d | set(gm.al.used) | in_regs
-    out = ["// n doublings, then (X, Y, Z) += (x2, y2) on the lanes with act != 0: one ladder window as ONE statement.",
-           "// (x2, y2) = row[0..11]: the statement loads them itself, under the doublings (row: this lane's table entry).",
-           "// Returns 0 when the addition met a possible exceptional input on some lane (the doublings are done, the addition",
-           "// is not: the caller runs the compiled jac_madd on the lanes with act != 0).",
-           "// keep: a pointer the caller wants to find in a REGISTER behind the statement (the ladder's table base: the",
-           "// compiler otherwise parks it in scratch and waits for the reload in front of every window); pinned to",
-           "// v[%d:%d], which the statement does not touch." % (KEEP, KEEP + 1),
-           "SSA_DEV u32 jac_window_asm(u64 (&X)[6], u64 (&Y)[6], u64 (&Z)[6], const u64 *row, u32 act, u32 n, const u64 *&keep) {",
-           "    u32 ok;", "    asm volatile("]
-    asm_lines(out, body)
-    ops = ['[ok] "=&v"(ok)']
-    for nm, regs in (("X", XR), ("Y", YR), ("Z", ZR)):
-        for j in range(6):
-            ops.append('"+{v[%d:%d]}"(%s[%d])' % (regs[j], regs[j] + 1, nm, j))
-    assert KEEP not in used and KEEP + 1 not in used and KEEP not in pinned and KEEP + 1 not in pinned
-    ops.append('"+{v[%d:%d]}"(keep)' % (KEEP, KEEP + 1))
-    out.append("        : " + ",\n          ".join(ops))
-    ins = ['[act] "v"(act)', '[n] "s"(__builtin_amdgcn_readfirstlane(n))', '[row] "v"(row)']
-    out.append("        : " + ",\n          ".join(ins))
-    clob = ['"v%d"' % r for r in sorted(used)] + ['"s%d"' % i for i in range(26 if FAIR else 24)] + ['"vcc"', '"scc"', '"memory"']
-    out.append("        : " + ", ".join(clob) + ");")
-    out += ["    return ok;", "}"]
+    body = [ENTRY_WAIT] + row_loads(gm.IN) + zeros(gd.zero_regs) + [SET_OK] + loop_top() + gd.main + loop_end() + ["s_waitcnt vmcnt(0)"] + \
+        narrow + zeros(r for r in gm.zero_regs if r not in gd.zero_regs) + gm.main + skip + gd.cold + gm.cold + \
+        BAIL + ["s_branch L_skip_%=", "L_end_%=:"]
+    used = check_and_stats(gd, [ln for ln in body if "%[" not in ln], pinned_regs | set(gm.al.used))[0] | set(gm.al.used) | in_regs
     print("window: %d fixed VGPRs + 36 pinned" % len(used))
-    return out
+    return statement(["n doublings, then (X, Y, Z) += (x2, y2) on the lanes with act != 0: one ladder window as ONE statement.",
+                      "(x2, y2) = row[0..11]: the statement loads them itself, under the doublings (row: this lane's table entry).",
+                      "Returns 0 when the addition met a possible exceptional input on some lane (the doublings are done, the addition",
+                      "is not: the caller runs the compiled jac_madd on the lanes with act != 0).",
+                      "keep: a pointer the caller wants to find in a REGISTER behind the statement (the ladder's table base: the",
+                      "compiler otherwise parks it in scratch and waits for the reload in front of every window); pinned to",
+                      "v[%d:%d], which the statement does not touch." % (KEEP, KEEP + 1)],
+                     "u32 jac_window_asm(%s, const u64 *row, u32 act, u32 n, const u64 *&keep)" % POINT_ARGS, body,
+                     [OK_OUT] + point_operands() + [keep_operand(used, pinned_regs)], ['[act] "v"(act)', N_OPERAND, '[row] "v"(row)'],
+                     clobbers(sorted(used), sgpr_clobbers(exec_saved=True), ("vcc", "scc", "memory")), **RETURNS_OK)
 
 
 OUT_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "schnorr-sig_amd", "csrc", "jac_asm.inc")

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Generates tools/isa_probe/isa_probe.hip: a micro-benchmark of the ISSUE cost of single gfx950 VALU / SALU /
+"""Generates the probe program isa_probe.hip: a micro-benchmark of the ISSUE cost of single gfx950 VALU / SALU /
 LDS instructions (cycles per wave-instruction per SIMD), the numbers the Fp / Fp6 instruction sequences are
 designed against (DESIGN.md "instruction cost table").
 
@@ -7,8 +7,29 @@ Each probe is a kernel whose body is one inline-asm loop of R copies of a short 
 threads (w waves on each of the CU's 4 SIMDs; 96 KB of dynamic LDS pins one block per CU) are timed with HIP
 events; cost = elapsed / (blocks per CU * iterations * instructions per wave * w), reported in ns and relative
 to v_add_u32 at the same occupancy.
+
+Two files.  `python tools/isa_probe/gen.py` writes tools/isa_probe/build/isa_probe.hip (2 MB, not in git; then
+`hipcc --offload-arch=gfx950 -O2 -o tools/isa_probe/isa_probe tools/isa_probe/build/isa_probe.hip`) and the sha256 of every
+probe's kernel to tests/golden/isa_probe.sha256, which the CPU suite compares with what this file generates: a probe whose
+text moves shows up there by name.  The committed tools/isa_probe/isa_probe.hip is the probe text of round 4 and stays as
+the record of what was measured then: every probe in it other than sq_chains_* is what this file still generates (the
+CPU suite compares them byte for byte); its sq_chains_* kernels are the EARLIER text of those probes -- the same
+instructions in the same order on other registers, six chains reaching past v127 -- and it has no sq_chains_5.
+
+The sq_chains_N probes are the CURRENT squaring of tools/gen_fp_chain_asm.py (eleven instructions and two scalar ones per
+chain).  The cycles-per-instruction figures quoted in that generator's header and in profiles/r04/sq_chains_probe.txt
+(4.73 / 4.35 / 4.33 / 4.39 for 2 / 3 / 4 / 6 chains) were measured with that earlier probe text;
+profiles/r10/sq_chains_probe.txt has the regenerated probes' figures, which agree with them (4.74 / 4.35 / 4.32 / 4.34,
+and 4.31 for five chains).
 """
+import hashlib
 import os
+import re
+import sys
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(HERE))
+import gen_fp_chain_asm as g
 
 R = 48          # pattern copies per loop iteration
 PROBES = []
@@ -225,32 +246,27 @@ probe("coef_salu_c1", _coef_salu(), n_instr=59)        # reported per instructio
 # ---- round 4 (second session): the Rescue squaring (tools/gen_fp_chain_asm.py) on TWO against THREE interleaved chains:
 # does a third independent chain buy issue slots (the S-box blocks are sensitive to the distance between dependent
 # instructions: profiles/r04/hash_ab.txt (g))?  Cycles per instruction; 11 instructions per squaring and chain.
-def _sq_chains(n):
-    import sys
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-    import gen_fp_chain_asm as g
+def sq_layout(n):
+    """n chains on the probes' registers: value and temporary pairs from v40 on, the dummy carry-out in s[60:61].  The carry
+    pairs S of the chains follow the loop counter s36 (from s38); S2 and S3 come behind them where all fit below s60 (three
+    chains), else they end below the stack pointer s32.  Never above s63: the same instructions with their carries in
+    s64 .. issue 4 % slower at four waves per SIMD, and the S-box blocks keep theirs in s20 .. s43
+    (profiles/r10/sq_chains_probe.txt)"""
+    carries = (38, 38 + 2 * n, 38 + 4 * n) if n <= 3 else (38, 32 - 4 * n, 32 - 2 * n)
+    return g.Layout(n, base=40, names=("X", "T", "A", "U", "H", "M", "E"), carries=carries, dummy="s[60:61]",
+                    sgprs=tuple(r for c in carries for r in range(c, c + 2 * n)))
 
-    def regs_n(c):
-        pair = lambda k: 40 + 2 * c + 2 * n * k
-        d = {"X": pair(0), "T": pair(1), "A": pair(2), "U": pair(3), "H": pair(4), "R": pair(5), "M": pair(6), "E": pair(7),
-             "C": pair(8), "S": 38 + 2 * c}
-        return d
-    old = (g.regs, g.DUMMY)
-    g.regs, g.DUMMY = regs_n, "s[60:61]"
-    try:
-        chains = [g.square(c, None, None, "s[62:63]") for c in range(n)]
-        seq = g.schedule(chains)
-    finally:
-        g.regs, g.DUMMY = old
-    assert not any(ln.startswith("s_nop") for ln in seq), seq
-    return seq
+
+def sq_body(n):
+    """one squaring of each of n chains, scheduled together (s_nop where nothing else is ready)"""
+    lay = sq_layout(n)
+    return g.schedule([g.square(c, None, None, "s[62:63]", lay) for c in range(n)])
 
 
 for _n in (1, 2, 3, 4, 5, 6):
-    try:
-        probe("sq_chains_%d" % _n, _sq_chains(_n), n_instr=11 * _n, setup="chains")
-    except AssertionError:
-        pass
+    _seq = sq_body(_n)
+    if not any(ln.startswith("s_nop") for ln in _seq):      # a probe only where the chains fill each other's wait states
+        probe("sq_chains_%d" % _n, _seq, n_instr=11 * _n, setup="chains%d" % _n)
 
 
 def body(pattern):
@@ -265,7 +281,12 @@ def body(pattern):
     return lines
 
 
-def main():
+OUT_PATH = os.path.join(HERE, "build", "isa_probe.hip")
+ROUND4_PATH = os.path.join(HERE, "isa_probe.hip")      # the committed probe text of round 4 (see the module docstring)
+
+
+def generate():
+    """the text of isa_probe.hip (the freshness test compares it with the committed files without writing anything)"""
     out = ["// generated by tools/isa_probe/gen.py -- do not edit", "#include <hip/hip_runtime.h>", "#include <cstdio>",
            "#include <cstring>", "#include <vector>", ""]
     clob = ", ".join('"v%d"' % r for r in range(10, 128)) + ", " + ", ".join('"s%d"' % r for r in range(36, 64)) + \
@@ -279,9 +300,11 @@ def main():
         pre = ["v_mov_b32 v%d, %%1" % r for r in range(10, 40)]
         pre += ["v_lshlrev_b32 v18, 4, %1", "s_mov_b64 vcc, exec", "s_mov_b64 s[60:61], exec", "s_mov_b64 s[62:63], 0", "s_mov_b32 s36, %2"]
         pre += ["s_mov_b64 s[%d:%d], 0" % (s, s + 1) for s in range(40, 60, 2)]
-        if setup == "chains":       # the chains' value pairs = the lane index (any value), every other register 0
+        more = ""
+        if setup.startswith("chains"):       # the first value pairs = the lane index (any value), every other register 0
             pre += ["v_mov_b32 v%d, 0" % r for r in range(40, 128)]
             pre += ["v_mov_b32 v%d, %%1" % r for r in range(40, 46)]
+            more = "".join(', "s%d"' % r for r in sq_layout(int(setup[6:])).sgprs if r < 36)     # s36 .. s63: every probe's
         for ln in pre:
             out.append('        "%s\\n\\t"' % ln)
         out.append('        "L_%s_%%=:\\n\\t"' % name)
@@ -293,7 +316,7 @@ def main():
         out.append('        "s_cmp_lg_u32 s36, 0\\n\\t"')
         out.append('        "s_cbranch_scc1 L_%s_%%=\\n\\t"' % name)
         out.append('        "v_xor_b32 %0, v20, v21"')
-        out.append('        : "=v"(y) : "v"(x), "s"(iters) : %s);' % clob)
+        out.append('        : "=v"(y) : "v"(x), "s"(iters) : %s%s);' % (clob, more))
         out.append("    if (y == 0x12345u) out[threadIdx.x] = y + lds[0];")
         out.append("}")
         out.append("")
@@ -302,10 +325,34 @@ def main():
     for name, pattern, n_instr, setup in PROBES:
         out.append('    {"%s", k_%s, %d},' % (name, name, R * n_instr))
     out.append("};")
-    out.append(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "main.inc")).read())
-    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "isa_probe.hip"), "w") as fh:
-        fh.write("\n".join(out) + "\n")
-    print("%d probes" % len(PROBES))
+    out.append(open(os.path.join(HERE, "main.inc")).read())
+    return "\n".join(out) + "\n"
+
+
+HASH_PATH = os.path.join(os.path.dirname(os.path.dirname(HERE)), "tests", "golden", "isa_probe.sha256")
+
+
+def pieces(text):
+    """{name: text} of a probe program: the includes (HEAD), every probe's kernel by the probe's name, and the probe table
+    with the main program (MAIN), in the file's order"""
+    parts = re.split(r"(?=__global__ void __launch_bounds__\(1024\) k_|struct Probe \{)", text)
+    names = ["HEAD"] + [re.match(r"__global__ void __launch_bounds__\(1024\) k_(\w+)\(", p).group(1) for p in parts[1:-1]] + ["MAIN"]
+    assert "".join(parts) == text and len(set(names)) == len(names)
+    return dict(zip(names, parts))
+
+
+def probe_hashes(text):
+    """the text of tests/golden/isa_probe.sha256: one line `name sha256` per piece of the probe program"""
+    return "".join("%s %s\n" % (nm, hashlib.sha256(p.encode()).hexdigest()) for nm, p in pieces(text).items())
+
+
+def main():
+    text = generate()
+    os.makedirs(os.path.dirname(OUT_PATH), exist_ok=True)
+    for path, content in ((OUT_PATH, text), (HASH_PATH, probe_hashes(text))):
+        with open(path, "w") as fh:
+            fh.write(content)
+    print("wrote %s (%d probes) and %s" % (OUT_PATH, len(PROBES), HASH_PATH))
 
 
 if __name__ == "__main__":
