@@ -18,6 +18,11 @@
  *                              a random linear combination, each distinct key's subgroup check runs once
  *   ssa_verify_many_cached   <- the same call with a key cache on the device: every distinct public key is checked once,
  *                              not once per batch (ssa_keycache_create).
+ *   ssa_verify_keyed_many_cached <- n x KeyedSignature::{from_bytes, verify} (src/signature.rs:230-271) on the 130-byte
+ *                              wire records, through a key cache whose key identity is the 49 bytes of
+ *                              PublicKey::to_bytes (src/public.rs:49-56): the decompression's square root, the subgroup
+ *                              check and the key's table run once per key (SSA_KEYCACHE_WIRE).
+ *   ssa_verify_keyed_many_device <- ssa_verify_keyed_many on device buffers
  *   ssa_hash_message_many   <- hash_message                 src/signature.rs:274-306
  *   ssa_rescue_hash_many    <- RescueHash::hash_field       src/signature.rs:303
  *   ssa_verify_keyed_many   <- KeyedSignature::{from_bytes, verify}  src/signature.rs:232-271
@@ -604,6 +609,54 @@ int ssa_verify_many_cached_device(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t 
                                   uint32_t coeff_bytes, uint8_t *d_status_out, uint64_t *d_n_fail_out,
                                   uint64_t stats_out[12]);
 
+/* ---- KeyedSignature wire records through a key cache in wire mode -------------------------
+ * ssa_keycache_create_ex(ctx, capacity, flags, &out): flags == 0 is exactly ssa_keycache_create; SSA_KEYCACHE_WIRE makes
+ * the identity of a row the 49 compressed key bytes AS RECEIVED (any other flag bit: SSA_ERR_ARG before anything else is
+ * looked at, *out = NULL).  A wire row holds everything an affine row holds -- the 96 key bytes, pk_inf, the status and
+ * the table, produced by the decompression and then by the same key check -- and the 49 bytes it was built from (56 more
+ * bytes per key; ssa_keycache_info reports the larger footprint).  Slot words, probe bound, clear-only eviction, the plan
+ * of ssa_debug_keycache_plan, orphaning, clear / info / destroy and the statistics are those of an affine cache.
+ * A key that does not decode -- a flag byte with one of its six low bits set, a limb >= p, an infinity bit with x != 0 or
+ * with the sort bit, x^3 + x + u + 395 not a square -- is cached like any other key: its row holds the affine bytes
+ * (0, 0), which the key check reports as SSA_MALFORMED, so a sender cannot force the square root again by repeating a
+ * bad key.  Two different undecodable strings are two keys.
+ * Every call checks the mode: ssa_verify_many_cached(_device) on a wire cache and the calls below on an affine cache
+ * return SSA_ERR_ARG and leave the cache as it was.
+ *
+ * ssa_verify_keyed_many_cached(_device): keyed = n records of 130 bytes, pk (49) || signature (81).  Flags, coeffs,
+ * n == 0, SSA_MAX_BATCH, the slice length, n_fail_out and stats_out are those of ssa_verify_many_cached, word for word;
+ * stats[0], [8] and [9] count distinct 49-byte strings.
+ * The contract is an equality.  Let P(keyed) be what ssa_verify_keyed_many unpacks a batch into: affine keys, (0, 0) for
+ * undecodable ones, pk_inf, and the 81-byte signatures.  With the same coeffs the status vector equals
+ * ssa_verify_many_screened on P(keyed) BYTE FOR BYTE, in every state of the cache; so it equals ssa_verify_keyed_many
+ * lane for lane except with the probability the screen already allows.
+ * Batches and trailing slices of at most SSA_MSM_SMALL_MAX lanes go to the exact keyed path (ssa_verify_keyed_many_device)
+ * and flags == SSA_FLAG_SIG_FLAG_BYTE alone to unpacking plus ssa_verify_batch_screened_device: the cache is not touched.
+ * Per slice: the 81 signature bytes are split into a dense array; the distinct 49-byte keys are found (the dedup of
+ * section 14 on 49 bytes) and looked up against the rows' stored 49 bytes; one lane per MISS decompresses its key into
+ * the next rows, the key check runs over those rows as it is, and the rows are published; every lane's 96 key bytes and
+ * flag are then copied out of its row into a per-lane workspace, which is what the screen's MSM and challenge hash read.
+ * From there on the slice is a slice of ssa_verify_many_cached.  Still two synchronisations per slice.  Under a bypass
+ * the u keys are decompressed into the context's own workspaces.
+ * The host form uploads the 130-byte records and the messages (130 B per lane in place of 177) and runs the device
+ * slice; the challenge hash needs y, which exists only after the look-up, so the pipelined upload-and-hash is not used.
+ * Slices run in order on the context's stream in both forms.
+ * Timing keys beside those of ssa_verify_many_cached: keyed_split, ssa_k_keyed_decompress, keyed_expand; a warm call
+ * launches neither ssa_k_keyed_decompress nor ssa_k_keyset_build.
+ * ssa_verify_keyed_many_device: ssa_verify_keyed_many on device buffers (d_n_fail_out optional, device memory). */
+#define SSA_KEYCACHE_WIRE 1u    /* ssa_keycache_create_ex: rows are identified by the 49 compressed key bytes */
+int ssa_keycache_create_ex(ssa_ctx *ctx, size_t capacity, uint32_t flags, ssa_keycache **out);
+int ssa_verify_keyed_many_cached(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *keyed, const uint8_t *msgs,
+                                 const uint64_t *msg_off, size_t msg_stride, size_t msg_len, size_t n, uint32_t flags,
+                                 const uint8_t *coeffs, uint8_t *status_out, uint64_t *n_fail_out, uint64_t stats_out[12]);
+int ssa_verify_keyed_many_cached_device(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *d_keyed, const uint8_t *d_msgs,
+                                        const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len, size_t n,
+                                        uint32_t flags, const uint8_t *d_coeffs, uint32_t coeff_bytes,
+                                        uint8_t *d_status_out, uint64_t *d_n_fail_out, uint64_t stats_out[12]);
+int ssa_verify_keyed_many_device(ssa_ctx *ctx, const uint8_t *d_keyed, const uint8_t *d_msgs, const uint64_t *d_msg_off,
+                                 size_t msg_stride, size_t msg_len, size_t n, uint32_t flags, uint8_t *d_status_out,
+                                 uint64_t *d_n_fail_out);
+
 /* Exact self-check of the per-key tables of a key set or a key cache, on the owning context's
  * stream; returns when it is done.  ssa_ctx_selfcheck covers the tables for G; these two cover what lives as long as a
  * validator set does: per key the 4 KB table of sixteen multiples, the status byte and, in comb mode, the 100 MB comb.
@@ -635,6 +688,13 @@ int ssa_verify_many_cached_device(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t 
  * ssa_k_keyset_build and checks again.  That is safe in a cache even when the key bytes were what flipped: the row becomes
  * a correct row for the bytes it now holds, look-ups compare all 97 bytes, so the original key misses and is inserted
  * again, and the status vector stays byte for byte that of ssa_verify_many_screened.
+ * A cache in WIRE mode (SSA_KEYCACHE_WIRE) trusts the 49 bytes a row was built from.  A row also fails when its stored
+ * 96 bytes and pk_inf are not what those 49 bytes stand for -- x equal bit for bit, the sort bit equal to
+ * lex_largest(y), the identity encoding, (0, 0) and no flag for a string that cannot decode; with the curve relation
+ * above that fixes y, and no square root is computed -- and, under SSA_KEYCHECK_DEEP, when a row of status 3 decodes
+ * after all (one decompression per such row).  Such rows are counted in out[1] and out[2] like any other.  REPAIR
+ * rebuilds a failing row from its 49 bytes: the decompression, then the key check.  When the 49 bytes were what flipped
+ * the row becomes a correct row for the string it now holds; the original key misses and is inserted again.
  * Returns SSA_OK when clean, or clean after repair (an empty cache: SSA_OK, all zero but out[2]); SSA_ERR_TABLE when a
  * key failed and was not repaired, or still fails after it; SSA_ERR_ARG for a NULL or orphaned object, an unknown flag
  * bit, REPAIR on a key set, or out == NULL; SSA_ERR_HIP as usual.  Both only read the object, but for repair.  Their
@@ -821,12 +881,13 @@ int ssa_debug_table_xor(ssa_ctx *ctx, int which, uint64_t row, uint32_t word, ui
 int ssa_debug_corrupt_table_builds(int n);
 /* key-table self-check tests: one key of a key set or of a key cache (exactly one of ks, kc non-NULL; key < m / keys
  * held).  what: 0 the ladder table (512 words), 1 the status byte, 2 the key bytes (12 words), 3 the pk_inf byte, 4 the
- * key's comb (key sets in comb mode: 12 words per row, word = 12 row + word of the row).  Anything outside the object is
- * SSA_ERR_ARG, nothing is read or written out of bounds.
+ * key's comb (key sets in comb mode: 12 words per row, word = 12 row + word of the row), 5 the 49 compressed bytes of a
+ * row of a key cache in wire mode (7 words: the six of x, and one holding the flag byte).  Anything outside the object
+ * is SSA_ERR_ARG, nothing is read or written out of bounds.
  *   ssa_debug_keytab_xor   XORs `mask` into word `word` ON THE DEVICE (a byte target: word 0, mask < 256).  Afterwards
  *                          only the self-check, its repair and the destroy call may run on the object.
- *   ssa_debug_keytab_read  copies the target to words_out: 512 words, 12 words, one word holding the byte, or (what 4)
- *                          rows (0, 0) and (0, 1) of the comb, 24 words. */
+ *   ssa_debug_keytab_read  copies the target to words_out: 512 words, 12 words, one word holding the byte, (what 4)
+ *                          rows (0, 0) and (0, 1) of the comb, 24 words, or (what 5) 7 words. */
 int ssa_debug_keytab_xor(ssa_keyset *ks, ssa_keycache *kc, int what, uint64_t key, uint32_t word, uint64_t mask);
 int ssa_debug_keytab_read(ssa_keyset *ks, ssa_keycache *kc, int what, uint64_t key, uint64_t *words_out);
 /* host logic of ssa_k_verify's end game, no context and no device needed: the launch plan for n lanes when `waves`

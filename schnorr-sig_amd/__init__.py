@@ -213,6 +213,10 @@ def _load():
         "ssa_keycache_info": (i32, [vp, u64p]),
         "ssa_verify_many_cached": (i32, [vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, u32, vp, vp, u64p, vp]),
         "ssa_verify_many_cached_device": (i32, [vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, u32, vp, u32, vp, vp, vp]),
+        "ssa_keycache_create_ex": (i32, [vp, sz, u32, C.POINTER(vp)]),
+        "ssa_verify_keyed_many_cached": (i32, [vp, vp, vp, vp, vp, sz, sz, sz, u32, vp, vp, u64p, vp]),
+        "ssa_verify_keyed_many_cached_device": (i32, [vp, vp, vp, vp, vp, sz, sz, sz, u32, vp, u32, vp, vp, vp]),
+        "ssa_verify_keyed_many_device": (i32, [vp, vp, vp, vp, sz, sz, sz, u32, vp, vp]),
         "ssa_debug_keycache_plan": (i32, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(u32)]),
         "ssa_debug_dedup_device": (i32, [vp, vp, vp, sz, vp, vp]),
         "ssa_debug_dedup_config": (i32, [vp, C.c_double, u32]),
@@ -486,12 +490,56 @@ class Engine:
             stats.ctypes.data), "ssa_verify_many_screened_device")
         return stats
 
-    def keycache_create(self, capacity):
+    def keycache_create(self, capacity, wire=False):
         """a key cache of `capacity` keys on this engine's device: all of its device memory, about
-        4.2 KB per key, is allocated here"""
+        4.2 KB per key, is allocated here.  wire=True (SSA_KEYCACHE_WIRE): a key is identified by
+        its 49 compressed bytes as received; such a cache serves verify_keyed_many_cached and no other call."""
         h = C.c_void_p()
-        _check(_lib.ssa_keycache_create(self._ctx, int(capacity), C.byref(h)), "ssa_keycache_create")
-        return KeyCache(self, h)
+        _check(_lib.ssa_keycache_create_ex(self._ctx, int(capacity), KEYCACHE_WIRE if wire else 0, C.byref(h)),
+               "ssa_keycache_create_ex")
+        return KeyCache(self, h, wire=wire)
+
+    def verify_keyed_many_cached(self, cache, keyed, msgs, offsets=None, check_torsion=True, sig_flag_byte=False,
+                                 coeffs=None):
+        """verify_many_cached on 130-byte KeyedSignature records pk(49) || sig(81) through a cache made with wire=True
+         -> (status uint8[n], n_fail, stats uint64[12]).  A key that was seen before -- one that
+        does not decode included -- is neither decompressed nor checked again.  With the same coeffs the status vector is
+        byte for byte verify_many_screened on the unpacked records, in every state of the cache.  stats as
+        verify_many_cached; [0], [8] and [9] count distinct 49-byte strings."""
+        kd = _np_u8(keyed, 130)
+        n = kd.shape[0]
+        m, off, stride, mlen = self._msg_args(msgs, offsets, n) if n else (None, None, 0, 0)
+        c = None
+        if coeffs is not None:
+            c = _np_u8(coeffs, 32)
+            if c.shape[0] != n:
+                raise ValueError("coeffs needs one 32-byte scalar per record")
+        status = np.full(n, 255, dtype=np.uint8)
+        nfail = C.c_uint64(0)
+        stats = np.zeros(12, dtype=np.uint64)
+        _check(_lib.ssa_verify_keyed_many_cached(self._ctx, cache.handle, _ptr(kd), _ptr(m), _ptr(off), stride, mlen, n,
+                                                 self._verify_flags(check_torsion, sig_flag_byte), _ptr(c),
+                                                 _ptr(status) if n else None, C.byref(nfail), stats.ctypes.data),
+               "ssa_verify_keyed_many_cached")
+        return status, int(nfail.value), stats
+
+    def verify_keyed_many_cached_device(self, cache, d_keyed, d_msgs, n, msg_len, d_coeffs, coeff_bytes, d_status, d_nfail,
+                                        msg_stride=None, d_offsets=0, check_torsion=True, sig_flag_byte=False):
+        """device form of verify_keyed_many_cached (two synchronisations per slice; the slices run in order on the
+        engine's stream); returns the statistics (uint64[12], host)"""
+        stats = np.zeros(12, dtype=np.uint64)
+        _check(_lib.ssa_verify_keyed_many_cached_device(
+            self._ctx, cache.handle, d_keyed, *self._dev_batch(0, d_msgs, d_offsets, msg_stride, msg_len, n)[1:],
+            self._verify_flags(check_torsion, sig_flag_byte), d_coeffs or None, coeff_bytes, d_status, d_nfail or None,
+            stats.ctypes.data), "ssa_verify_keyed_many_cached_device")
+        return stats
+
+    def verify_keyed_many_device(self, d_keyed, d_msgs, n, msg_len, d_status, d_nfail, msg_stride=None, d_offsets=0,
+                                 check_torsion=True):
+        """device form of verify_keyed_many (enqueued on the engine's stream)"""
+        _check(_lib.ssa_verify_keyed_many_device(
+            self._ctx, d_keyed, *self._dev_batch(0, d_msgs, d_offsets, msg_stride, msg_len, n)[1:],
+            FLAG_CHECK_TORSION if check_torsion else 0, d_status, d_nfail or None), "ssa_verify_keyed_many_device")
 
     def verify_many_cached(self, cache, sigs, pks, msgs, offsets=None, check_torsion=True, pk_inf=None,
                            sig_flag_byte=False, coeffs=None):
@@ -1011,7 +1059,10 @@ KEYCHECK_FIELDS = ("keys_checked", "keys_bad", "first_bad_key", "ladder_entries_
                    "keys_rebuilt_and_compared", "combs_skipped", "rows_repaired")
 # `what` of ssa_debug_keytab_xor / _read: the target and the words a read returns
 KEYTAB_LADDER, KEYTAB_STATUS, KEYTAB_KEY, KEYTAB_PK_INF, KEYTAB_COMB = 0, 1, 2, 3, 4
-_KEYTAB_READ_WORDS = {KEYTAB_LADDER: 512, KEYTAB_STATUS: 1, KEYTAB_KEY: 12, KEYTAB_PK_INF: 1, KEYTAB_COMB: 24}
+KEYTAB_WIRE = 5     # key caches in wire mode: the row's 49 compressed bytes as seven words (six of x, one holding the flag byte)
+_KEYTAB_READ_WORDS = {KEYTAB_LADDER: 512, KEYTAB_STATUS: 1, KEYTAB_KEY: 12, KEYTAB_PK_INF: 1, KEYTAB_COMB: 24,
+                      KEYTAB_WIRE: 7}
+KEYCACHE_WIRE = 1   # SSA_KEYCACHE_WIRE
 
 
 def _keycheck_result(rc, out, what):
@@ -1085,9 +1136,10 @@ class KeyCache(_KeyTables):
     across slices and calls of verify_many_cached.  Tied to its Engine like KeySet; destroyed exactly once (close(), the
     end of a `with` block, or when the object goes away)."""
 
-    def __init__(self, engine, handle):
+    def __init__(self, engine, handle, wire=False):
         self.engine = engine      # keeps the context alive
         self.handle = handle
+        self.wire = bool(wire)    # rows identified by the 49 compressed key bytes (DESIGN.md section 18)
 
     def info(self):
         """{'capacity', 'held', 'clears', 'device_bytes'}"""
@@ -1706,6 +1758,31 @@ def verify_many_cached(signatures, public_keys, messages, cache, rng=None, engin
                                         for _ in signatures), np.uint8)
     status, _, _ = eng.verify_many_cached(cache, sigs, pks, flat, offsets=off, check_torsion=True, pk_inf=inf,
                                           coeffs=coeffs)
+    return _status_results(status)
+
+
+def verify_keyed_many_cached(keyed_signatures, messages, cache, rng=None, engine=None):
+    """KeyedSignature::verify (src/signature.rs:232-234) for every (keyed signature, message) of a slice through a key
+    cache in wire mode (Engine.keycache_create(capacity, wire=True)): the list verify_many returns.
+    A public key seen in an earlier slice or call is neither decompressed nor checked again."""
+    if len(messages) != len(keyed_signatures):
+        raise MalformedInput("We should have the same number of messages than keyed signatures")
+    if not keyed_signatures:
+        return []
+    eng = engine or cache.engine
+    pks = np.frombuffer(b"".join(k.public_key.affine for k in keyed_signatures), np.uint8)
+    inf = np.array([1 if k.public_key.is_identity else 0 for k in keyed_signatures], np.uint8)
+    comp, st = eng.compress_many(pks, pk_inf=inf)
+    if (st != OK).any():
+        raise MalformedInput("PublicKey holds a non-canonical limb")
+    keyed = np.concatenate([comp, np.frombuffer(b"".join(k.signature.bytes for k in keyed_signatures),
+                                                np.uint8).reshape(-1, 81)], axis=1)
+    flat, off = pack_messages(messages)
+    coeffs = None
+    if rng is not None:
+        coeffs = np.frombuffer(b"".join((int.from_bytes(rng(64), "little") % Q).to_bytes(32, "little")
+                                        for _ in keyed_signatures), np.uint8)
+    status, _, _ = eng.verify_keyed_many_cached(cache, keyed, flat, offsets=off, check_torsion=True, coeffs=coeffs)
     return _status_results(status)
 
 

@@ -4,6 +4,7 @@
 #define SSA_KERNELS_DEFINE 1
 #include "ssa_ctx.hpp"
 #include "ssa_keycache.hpp"
+#include "ssa_keyed.hpp"
 
 #include <sys/random.h>
 
@@ -883,7 +884,7 @@ extern "C" int ssa_decompress_many(ssa_ctx *ctx, const uint8_t *compressed, size
 static int verify_keyed_host_one(ssa_ctx *ctx, const uint8_t *keyed, const HostBatch &b, size_t n, uint32_t flags,
                                  uint8_t *status_out, uint64_t *n_fail_out) {
     HostCall hc(ctx);
-    const u8 *d_keyed = hc.in(ctx->st_coeffs, keyed, n * 130);
+    const u8 *d_keyed = hc.in(ctx->st_keyed, keyed, n * 130);
     u8 *d_sigs = hc.out(ctx->st_sigs, nullptr, n * 81), *d_pks = hc.out(ctx->st_pks, nullptr, n * 96),
        *d_inf = hc.out(ctx->st_inf, nullptr, n, 16), *d_status = hc.out(ctx->st_status, status_out, n, 16);
     hc.step([&] {
@@ -1089,12 +1090,13 @@ static int dedup_fingerprint_key(ssa_ctx *ctx) {
 // that hit the probe bound: the policy of the caller needs u on the host.
 // A caller with a hook queues its own launches behind dd_k_index and in front of that read-back: they read u from
 // d_stats[1] on the device, and what they leave in d_stats[2] and d_stats[3] comes back in the same copy (extra[]).
+// With d_keyed the keys are the 49 compressed bytes in front of 130-byte records (ssa_keyed.hpp) and d_pks is unused.
 struct DedupHook {
     std::function<int(unsigned long long *d_stats)> queue;
     unsigned long long extra[2] = {0, 0};
 };
 static int dedup_slice(ssa_ctx *ctx, const uint8_t *d_pks, const uint8_t *d_pk_inf, size_t cnt, uint64_t *u_out,
-                       uint64_t *bound_hits_out, DedupHook *hook = nullptr) {
+                       uint64_t *bound_hits_out, DedupHook *hook = nullptr, const uint8_t *d_keyed = nullptr) {
     if (int rc = dedup_fingerprint_key(ctx)) return rc;
     const size_t cap = dd_slots_for(cnt), nb = grid_for(cnt, DD_BLOCK);
     if (ctx->dd_slots.reserve(cap * sizeof(u64)) || ctx->dd_rep.reserve(cnt * sizeof(u32)) ||
@@ -1106,9 +1108,14 @@ static int dedup_slice(ssa_ctx *ctx, const uint8_t *d_pks, const uint8_t *d_pk_i
     int rc = timed_launch(ctx, "dedup", [&] {
         (void)hipMemsetAsync(ctx->dd_slots.p, 0xff, cap * sizeof(u64), ctx->stream);
         (void)hipMemsetAsync(d_stats, 0, (hook ? 4 : 2) * sizeof(unsigned long long), ctx->stream);
-        hipLaunchKernelGGL(dd_k_insert, dim3((unsigned)nb), dim3(DD_BLOCK), 0, ctx->stream, d_pks, d_pk_inf, (u32)cnt,
-                           (u64)ctx->dedup_key[0], (u64)ctx->dedup_key[1], (u64 *)ctx->dd_slots.p, (u32)(cap - 1),
-                           (u32)ctx->knobs.dedup_probe_bound, (u32 *)ctx->dd_rep.p, blk_cnt, d_stats);
+        if (d_keyed)
+            hipLaunchKernelGGL(ky_k_insert, dim3((unsigned)nb), dim3(DD_BLOCK), 0, ctx->stream, d_keyed, (u32)cnt,
+                               (u64)ctx->dedup_key[0], (u64)ctx->dedup_key[1], (u64 *)ctx->dd_slots.p, (u32)(cap - 1),
+                               (u32)ctx->knobs.dedup_probe_bound, (u32 *)ctx->dd_rep.p, blk_cnt, d_stats);
+        else
+            hipLaunchKernelGGL(dd_k_insert, dim3((unsigned)nb), dim3(DD_BLOCK), 0, ctx->stream, d_pks, d_pk_inf, (u32)cnt,
+                               (u64)ctx->dedup_key[0], (u64)ctx->dedup_key[1], (u64 *)ctx->dd_slots.p, (u32)(cap - 1),
+                               (u32)ctx->knobs.dedup_probe_bound, (u32 *)ctx->dd_rep.p, blk_cnt, d_stats);
         hipLaunchKernelGGL(dd_k_scan, dim3(1), dim3(DD_BLOCK), 0, ctx->stream, (const u32 *)blk_cnt, (u32)nb, blk_off,
                            d_stats);
         hipLaunchKernelGGL(dd_k_number, dim3((unsigned)nb), dim3(DD_BLOCK), 0, ctx->stream, (const u32 *)ctx->dd_rep.p,
@@ -1302,7 +1309,12 @@ extern "C" int ssa_debug_dedup_config(ssa_ctx *ctx, double max_distinct_ratio, u
 
 // ------------------------------------------------------------------ key cache
 extern "C" int ssa_keycache_create(ssa_ctx *ctx, size_t capacity, ssa_keycache **out) {
+    return ssa_keycache_create_ex(ctx, capacity, 0u, out);
+}
+
+extern "C" int ssa_keycache_create_ex(ssa_ctx *ctx, size_t capacity, uint32_t flags, ssa_keycache **out) {
     if (out) *out = nullptr;
+    if (flags & ~SSA_KEYCACHE_WIRE) return SSA_ERR_ARG;
     if (!ctx || !out || capacity == 0 || capacity > KC_MAX_CAPACITY) return SSA_ERR_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
     constexpr size_t TAB_BYTES = (size_t)(PTAB_ENTRIES * PTAB_ENTRY_U64) * sizeof(u64);
@@ -1310,12 +1322,14 @@ extern "C" int ssa_keycache_create(ssa_ctx *ctx, size_t capacity, ssa_keycache *
     kc->ctx = ctx;
     kc->capacity = capacity;
     kc->n_slots = dd_slots_for(capacity);
+    kc->wire_mode = (flags & SSA_KEYCACHE_WIRE) != 0;
     kc->rows.ctx = ctx;
     kc->rows.m = capacity;
     // everything the cache will ever hold, now: no call that uses it allocates for it
     if (kc->rows.tab.reserve_exact(capacity * TAB_BYTES) || kc->rows.status.reserve_exact(capacity + 16) ||
         kc->rows.pks.reserve_exact(capacity * 96) || kc->inf.reserve_exact(capacity + 16) ||
         kc->slots.reserve_exact(kc->n_slots * sizeof(u64)) ||
+        (kc->wire_mode && kc->wire.reserve_exact(capacity * KY_WIRE_WORDS * sizeof(u64))) ||
         hipMemsetAsync(kc->slots.p, 0xff, kc->n_slots * sizeof(u64), ctx->stream) != hipSuccess ||
         hipStreamSynchronize(ctx->stream) != hipSuccess) {
         (void)hipGetLastError();
@@ -1456,6 +1470,136 @@ int ssa_internal_keycache_slice(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *d
     if (rc) return rc;
     *kv = {(const uint32_t *)ctx->kc_lane_row.p, (const uint64_t *)kc->rows.tab.p, (const uint8_t *)kc->rows.status.p,
            (uint32_t)kc->capacity};
+    return 0;
+}
+
+// ------------------------------------------------------------------ wire records through a wire cache
+int ssa_internal_unpack_keyed(ssa_ctx *ctx, const uint8_t *d_keyed, size_t n, DevBatch *b) {
+    if (ctx->ky_sigs.reserve(n * 81 + 16) || ctx->ky_pks.reserve(n * 96) || ctx->ky_inf.reserve(n + 16)) return SSA_ERR_HIP;
+    b->sigs = (const u8 *)ctx->ky_sigs.p;
+    b->pks = (const u8 *)ctx->ky_pks.p;
+    b->pk_inf = (const u8 *)ctx->ky_inf.p;
+    return timed_launch(ctx, "ssa_k_unpack_keyed", [&] {
+        hipLaunchKernelGGL(ssa_k_unpack_keyed, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, d_keyed, n,
+                           (u8 *)ctx->ky_pks.p, (u8 *)ctx->ky_inf.p, (u8 *)ctx->ky_sigs.p);
+    });
+}
+
+// the keys of the representative lanes reps[0, m) decompressed into rows [0, m) of the given arrays
+static int keyed_decompress(ssa_ctx *ctx, const uint8_t *d_keyed, const u32 *reps, size_t m, size_t cnt, u64 *pks, u8 *inf,
+                            u64 *wire) {
+    return timed_launch(ctx, "ssa_k_keyed_decompress", [&] {
+        hipLaunchKernelGGL(ky_k_decompress, dim3(grid_for(m, 256)), dim3(256), 0, ctx->stream, d_keyed, reps, (u32)m,
+                           (u32)cnt, pks, inf, wire);
+    });
+}
+
+int ssa_internal_keyed_cache_slice(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *d_keyed, size_t cnt, DevBatch *b,
+                                   KeyView *kv, uint64_t *u_out, uint64_t *bound_hits_out, uint64_t ks[4],
+                                   const unsigned long long **d_unpublished) {
+    constexpr size_t TAB_WORDS = (size_t)(PTAB_ENTRIES * PTAB_ENTRY_U64);
+    const size_t nb = grid_for(cnt, DD_BLOCK);
+    if (ctx->kc_found.reserve(cnt * sizeof(u32)) || ctx->kc_missrep.reserve(cnt * sizeof(u32)) ||
+        ctx->kc_blk.reserve(2 * nb * sizeof(u32)) || ctx->kc_lane_row.reserve(cnt * sizeof(u32)) ||
+        ctx->ky_sigs.reserve(cnt * 81 + 16) || ctx->ky_pks.reserve(cnt * 96) || ctx->ky_inf.reserve(cnt + 16))
+        return SSA_ERR_HIP;
+    u32 *found = (u32 *)ctx->kc_found.p, *miss_rep = (u32 *)ctx->kc_missrep.p, *blk_cnt = (u32 *)ctx->kc_blk.p,
+        *blk_off = blk_cnt + nb;
+    int rc = timed_launch(ctx, "keyed_split", [&] {
+        hipLaunchKernelGGL(ky_k_split, dim3(grid_for((cnt * 81 + 3) / 4, 256)), dim3(256), 0, ctx->stream, d_keyed, cnt,
+                           (u8 *)ctx->ky_sigs.p);
+    });
+    if (rc) return rc;
+    const size_t held = kc->held;
+    u64 *c_pks = (u64 *)kc->rows.pks.p, *c_wire = (u64 *)kc->wire.p;
+    u8 *c_inf = (u8 *)kc->inf.p;
+    DedupHook hook;
+    // d_stats: [0] lanes at the probe bound, [1] u, [2] m (dd_k_scan writes its total one word on), [3] unpublished rows
+    hook.queue = [&](unsigned long long *d_stats) {
+        return timed_launch(ctx, "keycache_lookup", [&] {
+            hipLaunchKernelGGL(ky_k_lookup, dim3((unsigned)nb), dim3(DD_BLOCK), 0, ctx->stream, d_keyed,
+                               (const u32 *)ctx->dd_reps.p, (u32)cnt, (const unsigned long long *)d_stats,
+                               (u64)ctx->dedup_key[0], (u64)ctx->dedup_key[1], (const u64 *)kc->slots.p,
+                               (u32)(kc->n_slots - 1), (u32)ctx->knobs.dedup_probe_bound, (const u64 *)c_wire, (u32)held,
+                               found, blk_cnt);
+            hipLaunchKernelGGL(dd_k_scan, dim3(1), dim3(DD_BLOCK), 0, ctx->stream, (const u32 *)blk_cnt, (u32)nb, blk_off,
+                               d_stats + 1);
+            hipLaunchKernelGGL(kc_k_number, dim3((unsigned)nb), dim3(DD_BLOCK), 0, ctx->stream,
+                               (const u32 *)ctx->dd_reps.p, (u32)cnt, (const unsigned long long *)d_stats,
+                               (const u32 *)blk_off, found, miss_rep);
+        });
+    };
+    uint64_t u = 0;
+    if ((rc = dedup_slice(ctx, nullptr, nullptr, cnt, &u, bound_hits_out, &hook, d_keyed))) return rc;
+    const uint64_t m = hook.extra[0];
+    if (m > u) return SSA_ERR_HIP;      // (never)
+    *u_out = u;
+    ks[0] = ks[1] = ks[2] = ks[3] = 0;
+    *d_unpublished = nullptr;
+    const int plan = kc_plan(kc->capacity, held, u, m);
+    const u64 *row_pks = c_pks;
+    const u8 *row_inf = c_inf;
+    if (plan == KC_PLAN_BYPASS) {       // more keys than rows: the u keys into the context's own workspaces
+        ks[3] = 1;
+        if (ctx->dd_pks.reserve(u * 96) || ctx->dd_inf.reserve(u + 16) || ctx->dd_kstatus.reserve(u + 16) ||
+            ctx->ws_tab.reserve(u * TAB_WORDS * sizeof(u64)))
+            return SSA_ERR_HIP;
+        if ((rc = keyed_decompress(ctx, d_keyed, (const u32 *)ctx->dd_reps.p, (size_t)u, cnt, (u64 *)ctx->dd_pks.p,
+                                   (u8 *)ctx->dd_inf.p, nullptr)))
+            return rc;
+        if ((rc = ssa_internal_keyset_build(ctx, (const u8 *)ctx->dd_pks.p, (const u8 *)ctx->dd_inf.p, (size_t)u,
+                                            (u64 *)ctx->ws_tab.p, (u8 *)ctx->dd_kstatus.p)))
+            return rc;
+        *kv = ctx_key_view(ctx, u);
+        row_pks = (const u64 *)ctx->dd_pks.p;
+        row_inf = (const u8 *)ctx->dd_inf.p;
+    } else {
+        unsigned long long *d_unpub = (unsigned long long *)ctx->dd_stats.p + 3;
+        size_t base = held, fresh = (size_t)m;
+        const u32 *reps = miss_rep;
+        if (plan == KC_PLAN_CLEAR) {        // every key of the slice is new: key j of the dedup takes row j
+            if ((rc = keycache_reset(kc))) return rc;
+            ks[2] = 1;
+            base = 0;
+            fresh = (size_t)u;
+            reps = (const u32 *)ctx->dd_reps.p;
+        }
+        ks[0] = u - fresh;
+        ks[1] = fresh;
+        if (fresh) {
+            if ((rc = keyed_decompress(ctx, d_keyed, reps, fresh, cnt, c_pks + 12 * base, c_inf + base,
+                                       c_wire + KY_WIRE_WORDS * base)))
+                return rc;
+            if ((rc = ssa_internal_keyset_build(ctx, (const u8 *)(c_pks + 12 * base), (const u8 *)(c_inf + base), fresh,
+                                                (u64 *)kc->rows.tab.p + base * TAB_WORDS, (u8 *)kc->rows.status.p + base)))
+                return rc;
+            rc = timed_launch(ctx, "keycache_insert", [&] {
+                hipLaunchKernelGGL(ky_k_publish, dim3(grid_for(fresh, DD_BLOCK)), dim3(DD_BLOCK), 0, ctx->stream,
+                                   (const u64 *)c_wire, (u32)base, (u32)fresh, (u64)ctx->dedup_key[0],
+                                   (u64)ctx->dedup_key[1], (u64 *)kc->slots.p, (u32)(kc->n_slots - 1),
+                                   (u32)ctx->knobs.dedup_probe_bound, d_unpub);
+            });
+            if (rc) return rc;
+            kc->held = base + fresh;
+            *d_unpublished = d_unpub;
+        }
+        rc = timed_launch(ctx, "keycache_map", [&] {
+            hipLaunchKernelGGL(kc_k_map, dim3((unsigned)nb), dim3(DD_BLOCK), 0, ctx->stream, (const u32 *)ctx->dd_idx.p,
+                               (const u32 *)found, (u32)cnt, (u32)base, plan == KC_PLAN_CLEAR ? 1u : 0u,
+                               (u32 *)ctx->kc_lane_row.p);
+        });
+        if (rc) return rc;
+        *kv = {(const uint32_t *)ctx->kc_lane_row.p, (const uint64_t *)kc->rows.tab.p, (const uint8_t *)kc->rows.status.p,
+               (uint32_t)kc->capacity};
+    }
+    rc = timed_launch(ctx, "keyed_expand", [&] {
+        hipLaunchKernelGGL(ky_k_expand, dim3(grid_for(cnt * 12, 256)), dim3(256), 0, ctx->stream, kv->lane_key, row_pks,
+                           row_inf, kv->n_keys, (u32)cnt, (u64 *)ctx->ky_pks.p, (u8 *)ctx->ky_inf.p);
+    });
+    if (rc) return rc;
+    b->sigs = (const u8 *)ctx->ky_sigs.p;
+    b->pks = (const u8 *)ctx->ky_pks.p;
+    b->pk_inf = (const u8 *)ctx->ky_inf.p;
     return 0;
 }
 

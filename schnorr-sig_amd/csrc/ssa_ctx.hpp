@@ -163,6 +163,9 @@ struct CtxKnobs {
     /* key cache (ssa_keycache.hpp): per distinct key of the slice its cache row or miss number, \
        the misses' representative lanes, per-workgroup counts and offsets of the misses, and a cache row per lane */ \
     X(kc_found) X(kc_missrep) X(kc_blk) X(kc_lane_row) \
+    /* KeyedSignature wire records (ssa_keyed.hpp): one slice of 130-byte records staged by the \
+       host forms, and per lane of a slice the 81 signature bytes, the 96 key bytes and the pk_inf boolean */ \
+    X(st_keyed) X(ky_sigs) X(ky_pks) X(ky_inf) \
     /* signing (ssa_sign.hip): the 4-bit comb table of the constant-time signer (98 KB, built at the first use) and \
        the intermediates of the keyed (130-byte) output */ \
     X(ctab) X(sg_sigs) X(sg_pks) \
@@ -257,18 +260,21 @@ struct ssa_keyset {
 // key cache (entry points in ssa_api.hip and ssa_msm.hip): a ladder-kind key set of `capacity` rows
 // that fills itself (rows.tab, rows.status, rows.pks: rows [0, held) are complete), the pk_inf boolean of each row, and
 // the slot table over the rows (ssa_keycache.hpp).  The host knows `held`: rows are handed out in order and never freed
-// but by a clear of the whole cache.
+// but by a clear of the whole cache.  In wire mode (SSA_KEYCACHE_WIRE) the identity of a row is the
+// 49 compressed bytes it was built from, kept in `wire` as seven words per row.
 struct ssa_keycache {
     ssa_ctx *ctx = nullptr;   // nullptr: the context is gone, the device memory went with it
     size_t capacity = 0, held = 0, n_slots = 0;
     uint64_t clears = 0;
+    bool wire_mode = false;
     ssa_keyset rows;          // never registered with the context: owned by the cache
-    DevBuf inf, slots;
-    uint64_t device_bytes() const { return rows.tab.cap + rows.status.cap + rows.pks.cap + inf.cap + slots.cap; }
+    DevBuf inf, slots, wire;
+    uint64_t device_bytes() const { return rows.tab.cap + rows.status.cap + rows.pks.cap + inf.cap + slots.cap + wire.cap; }
     void release_all() {
         rows.release_all();
         inf.release();
         slots.release();
+        wire.release();
     }
 };
 
@@ -779,6 +785,17 @@ int ssa_internal_verify_keyed_view(ssa_ctx *ctx, const uint8_t *d_sigs, const ui
 int ssa_internal_keycache_slice(ssa_ctx *ctx, struct ssa_keycache *kc, const uint8_t *d_pks, const uint8_t *d_pk_inf,
                                 size_t cnt, KeyView *kv, uint64_t *u_out, uint64_t *bound_hits_out, uint64_t ks[4],
                                 const unsigned long long **d_unpublished);
+
+// defined in ssa_api.hip, for ssa_verify_keyed_many_cached (ssa_msm.hip): ONE slice of cnt 130-byte
+// records through a key cache in wire mode.  The signatures are split into ctx->ky_sigs, the distinct 49-byte keys are
+// found and looked up, the misses decompressed, checked and inserted (or the cache cleared, or bypassed), and every
+// lane's key bytes and flag expanded into ctx->ky_pks / ctx->ky_inf: *b is the slice as the screen reads it (its
+// messages are left alone).  The other results as ssa_internal_keycache_slice gives them; one synchronisation.
+int ssa_internal_keyed_cache_slice(ssa_ctx *ctx, struct ssa_keycache *kc, const uint8_t *d_keyed, size_t cnt, DevBatch *b,
+                                   KeyView *kv, uint64_t *u_out, uint64_t *bound_hits_out, uint64_t ks[4],
+                                   const unsigned long long **d_unpublished);
+// defined in ssa_api.hip: ssa_k_unpack_keyed over n records into ctx->ky_sigs / ky_pks / ky_inf (the exact keyed path)
+int ssa_internal_unpack_keyed(ssa_ctx *ctx, const uint8_t *d_keyed, size_t n, DevBatch *b);
 
 // defined in ssa_api.hip: ssa_k_keyset_build over m keys, queued on the context's stream (timing key ssa_k_keyset_build)
 int ssa_internal_keyset_build(ssa_ctx *ctx, const uint8_t *d_pks, const uint8_t *d_pk_inf, size_t m, uint64_t *d_tab,

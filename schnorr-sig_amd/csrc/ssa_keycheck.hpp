@@ -32,6 +32,16 @@
 // Lists are filled wave by wave: a ballot, one atomicAdd of the wave's count, plain stores of the row numbers (their
 // order does not matter: every verdict is per key).  All device writes are vector stores and vector atomics, and
 // every kernel only reads the object but for bad[], the lists and, in repair, the rows being rebuilt.
+//
+// A key cache in WIRE mode also keeps the 49 compressed bytes each row was built from, and those
+// are the root of trust: the row's 96 bytes and pk_inf must be what the 49 bytes stand for.
+//   kck_k_wire          one lane per row, after kck_k_tables: a string that cannot decode by its form (flag bits, a limb
+//                       >= p, a bad infinity encoding) or that claims "not a square" must hold (0, 0) and no flag; the
+//                       identity encoding (0, 0) and the flag; any other row x bit for bit and the sort bit of its y
+//                       (f6_lex_largest).  With kck_k_tables' curve relation that fixes y: no square root is computed.
+//                       Under DEEP a row of status 3 is decompressed after all, and fails if it decodes.
+//   kck_k_wire_rebuild  repair: the listed rows' 96 bytes and flag again from their 49 bytes (decompress_lane), in front
+//                       of the gather / build / scatter above.
 namespace ssa {
 
 constexpr int KCK_TAB_WORDS = PTAB_ENTRIES * PTAB_ENTRY_U64;        // 512 words per key
@@ -251,6 +261,74 @@ kck_k_scatter(const u64 *__restrict__ g_tab, const u8 *__restrict__ g_status, co
     if (k == 0) status[i] = g_status[r];
 }
 
+// a row's seven wire words as the 49 bytes decompress_lane reads (little-endian words: the bytes as they arrived)
+SSA_DEV u32 kck_wire_decompress(const u64 *__restrict__ w, aff &P, bool &inf) {
+    u64 buf[KY_WIRE_WORDS];
+#pragma unroll
+    for (int k = 0; k < KY_WIRE_WORDS; k++) buf[k] = w[k];
+    return decompress_lane(reinterpret_cast<const u8 *>(buf), P, inf);
+}
+
+// bad[i] = 1 for a row whose stored key is not what its 49 bytes stand for (kck_k_tables wrote bad[] before)
+__global__ void __launch_bounds__(256)
+kck_k_wire(const u64 *__restrict__ wire, const u64 *__restrict__ pks, const u8 *__restrict__ pk_inf,
+           const u8 *__restrict__ status, u32 m, u32 deep, u8 *__restrict__ bad) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    const u64 *w = wire + (size_t)i * KY_WIRE_WORDS;
+    const u64 flag = w[6];
+    bool canon;
+    const aff P = kck_ld_key(pks, i, canon);
+    const bool zero = f6_is_zero(P.x) && f6_is_zero(P.y), inf = pk_inf[i] != 0;
+    bool x_canon = true, x_zero = true, x_eq = true;
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+        x_canon = x_canon && w[k] < FP_P;
+        x_zero = x_zero && w[k] == 0;
+        x_eq = x_eq && w[k] == P.x.c[k];
+    }
+    const bool f_inf = (flag & 0x80u) != 0, f_sort = (flag & 0x40u) != 0;
+    bool fail;
+    if (flag > 0xffull) {
+        fail = true;                                           // (the word holds one byte)
+    } else if ((flag & 0x3fu) || !x_canon || (f_inf && (!x_zero || f_sort))) {
+        fail = !zero || inf;                                   // cannot decode: (0, 0), no flag
+    } else if (f_inf) {
+        fail = !zero || !inf;                                  // the identity
+    } else if (zero && !inf) {
+        fail = false;                                          // "not a square": DEEP looks below
+    } else {
+        fail = inf || !canon || !x_eq || f6_lex_largest(P.y) != f_sort;
+    }
+    if (!fail && deep && status[i] == ST_MALFORMED) {
+        aff Q;
+        bool q_inf;
+        fail = kck_wire_decompress(w, Q, q_inf) == 0;          // it decodes after all
+    }
+    if (fail) bad[i] = 1;
+}
+
+// rows list[0, n): the 96 bytes and the flag again from the 49 bytes (a flag word with more than its byte set is cut)
+__global__ void __launch_bounds__(256)
+kck_k_wire_rebuild(u64 *__restrict__ wire, const u32 *__restrict__ list, u32 n, u32 m, u64 *__restrict__ pks,
+                   u8 *__restrict__ pk_inf) {
+    const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    const u32 i = list[t];
+    if (i >= m) return;       // (never)
+    u64 *w = wire + (size_t)i * KY_WIRE_WORDS;
+    if (w[6] > 0xffull) w[6] &= 0xffull;
+    aff P;
+    bool inf;
+    (void)kck_wire_decompress(w, P, inf);
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+        pks[12 * (size_t)i + k] = P.x.c[k];
+        pks[12 * (size_t)i + 6 + k] = P.y.c[k];
+    }
+    pk_inf[i] = inf ? 1 : 0;
+}
+
 #endif  // SSA_CHECK_FUNCTIONS_ONLY
 }  // namespace ssa
 
@@ -264,6 +342,7 @@ struct KeyRows {
     u64 *tab;
     const u64 *ktab;      // per-key combs (key sets in comb mode), or nullptr
     size_t m;
+    u64 *wire = nullptr;  // the rows' 49 compressed bytes, seven words each (key caches in wire mode), or nullptr
 };
 
 static inline size_t kck_pad(size_t m) { return (m + 15) & ~(size_t)15; }
@@ -307,6 +386,12 @@ static int keycheck_pass(const KeyRows &r, bool deep, uint64_t res[KCK_WORDS]) {
                                    (const unsigned long long *)d, bad);
             }))
             return rc;
+    if (r.wire)
+        if (int rc = timed_launch(ctx, "ssa_k_keytab_check", [&] {
+                hipLaunchKernelGGL(kck_k_wire, dim3(grid_for(m, 256)), dim3(256), 0, ctx->stream, (const u64 *)r.wire, r.pks,
+                                   r.inf, (const u8 *)r.status, (u32)m, deep ? 1u : 0u, bad);
+            }))
+            return rc;
     if (r.ktab)
         if (int rc = timed_launch(ctx, "ssa_k_keycomb_check", [&] {
                 hipLaunchKernelGGL(kck_k_comb, dim3((unsigned)(m * KCK_COMB_BLOCKS)), dim3(256), 0, ctx->stream, r.pks,
@@ -337,6 +422,12 @@ static int keycheck_repair(const KeyRows &r, uint64_t *rebuilt) {
     HIP_TRY(hipMemcpyAsync(&n_bad, d + KCK_LISTED, sizeof n_bad, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     if (n_bad > m) return SSA_ERR_HIP;      // (never)
+    if (r.wire && n_bad)        // a wire row is rebuilt from its 49 bytes: first the 96 bytes and the flag they stand for
+        if (int rc = timed_launch(ctx, "keycheck_repair", [&] {
+                hipLaunchKernelGGL(kck_k_wire_rebuild, dim3(grid_for(n_bad, 256)), dim3(256), 0, ctx->stream, r.wire,
+                                   (const u32 *)list, (u32)n_bad, (u32)m, (u64 *)r.pks, (u8 *)r.inf);
+            }))
+            return rc;
     // a chunk's scratch in ws_tab: the tables, then the gathered key words, flags and statuses
     constexpr size_t TAB_BYTES = KCK_TAB_WORDS * sizeof(u64);
     for (size_t lo = 0; lo < n_bad; lo += KCK_CHUNK) {
@@ -393,7 +484,7 @@ static KeyRows keyset_rows(ssa_keyset *ks) {
 }
 static KeyRows keycache_rows(ssa_keycache *kc) {
     return {kc->ctx, (const u64 *)kc->rows.pks.p, (const u8 *)kc->inf.p, (u8 *)kc->rows.status.p, (u64 *)kc->rows.tab.p,
-            nullptr, kc->held};
+            nullptr, kc->held, kc->wire_mode ? (u64 *)kc->wire.p : nullptr};
 }
 
 extern "C" int ssa_keyset_selfcheck(ssa_keyset *ks, uint32_t flags, uint8_t *bad_out, uint64_t out[8]) {
@@ -424,6 +515,11 @@ static int debug_keytab_span(ssa_keyset *ks, ssa_keycache *kc, int what, uint64_
         if (!r.ktab) return SSA_ERR_ARG;
         *p = (u8 *)(r.ktab + key * KTAB_ENTRIES_PER_KEY * 12);
         *words = KTAB_ENTRIES_PER_KEY * 12;
+        return 0;
+    case 5:
+        if (!r.wire) return SSA_ERR_ARG;
+        *p = (u8 *)(r.wire + key * KY_WIRE_WORDS);
+        *words = KY_WIRE_WORDS;
         return 0;
     default: return SSA_ERR_ARG;
     }

@@ -1885,6 +1885,10 @@ constexpr uint32_t MANY_SCREEN_FLAGS = SSA_FLAG_CHECK_TORSION | SSA_FLAG_SIG_FLA
 // with the length of the re-check list.  With a key cache (ssa_verify_many_cached) the keys are
 // looked up there and only the unseen ones are checked; everything behind the key check is the same code.
 // stats: what the entry points report, a CallStats of 8 words, or of 12 with a key cache (words 8..11 are the cache's).
+static int screen_slice_after_keys(ssa_ctx *ctx, const DevBatch &b, size_t n, const uint8_t *d_coeffs, uint32_t coeff_bytes,
+                                   uint32_t flags, const u64 *d_h, uint8_t *d_status, CallStats *stats, const KeyView &kv,
+                                   uint64_t u, uint64_t hits, const unsigned long long *d_unpublished, uint64_t sv[12]);
+
 static int screen_many_slice(ssa_ctx *ctx, const DevBatch &b, size_t n, const uint8_t *d_coeffs, uint32_t coeff_bytes,
                              uint32_t flags, const u64 *d_h, uint8_t *d_status, CallStats *stats, ssa_keycache *kc) {
     uint64_t sv[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -1907,6 +1911,17 @@ static int screen_many_slice(ssa_ctx *ctx, const DevBatch &b, size_t n, const ui
         if (int rc = ssa_internal_dedup_keys(ctx, b.pks, b.pk_inf, n, &u, &hits)) return rc;
         kv = ctx_key_view(ctx, u);
     }
+    return screen_slice_after_keys(ctx, b, n, d_coeffs, coeff_bytes, flags, d_h, d_status, stats, kv, u, hits, d_unpublished,
+                                   sv);
+}
+
+// The slice from its checked keys on: kv = where they are (the context's own, or rows of a key cache), u of them, `hits`
+// lanes at the dedup's probe bound, sv[8..11] the cache's statistics.  Shared by the affine forms above and the wire form
+// (ssa_verify_keyed_many_cached), whose b holds the split signatures and the expanded keys.
+static int screen_slice_after_keys(ssa_ctx *ctx, const DevBatch &b, size_t n, const uint8_t *d_coeffs, uint32_t coeff_bytes,
+                                   uint32_t flags, const u64 *d_h, uint8_t *d_status, CallStats *stats, const KeyView &kv,
+                                   uint64_t u, uint64_t hits, const unsigned long long *d_unpublished, uint64_t sv[12]) {
+    unsigned long long *scratch_fail = (unsigned long long *)ctx->scr_fail.p;    // (the caller counts the statuses)
     const unsigned nb = grid_for(n, SCR_BLOCK);
     if (ctx->scr_mask.reserve(n + 16) || ctx->scr_mark.reserve(n + 16) || ctx->scr_list.reserve(n * sizeof(u32)) ||
         ctx->scr_blk.reserve(2 * (size_t)nb * sizeof(u32)) || ctx->scr_cnt.reserve(64) || ctx->scr_ok.reserve(SCREEN_MAX_SEGS))
@@ -1997,7 +2012,7 @@ static int many_screened_device(ssa_ctx *ctx, ssa_keycache *kc, const DevBatch &
                                 uint64_t *stats_out, int stats_words) {
     if (flags & ~MANY_SCREEN_FLAGS) return SSA_ERR_ARG;
     if (int rc = check_dev_batch(ctx, b, n, d_status_out, d_coeffs, coeff_bytes)) return rc;
-    if (kc && kc->ctx != ctx) return SSA_ERR_ARG;
+    if (kc && (kc->ctx != ctx || kc->wire_mode)) return SSA_ERR_ARG;      // (a wire cache takes wire records: section 18)
     CallStats st(stats_words);
     st.out(stats_out);      // (still empty: the caller's words are zeroed)
     if (flags == SSA_FLAG_SIG_FLAG_BYTE)      // verify_batch semantics: no key check to add or to cache, the screened form as it is
@@ -2067,7 +2082,7 @@ static int many_screened_host(ssa_ctx *ctx, ssa_keycache *kc, const HostBatch &b
                               int stats_words) {
     if (flags & ~MANY_SCREEN_FLAGS) return SSA_ERR_ARG;
     if (int rc = check_host_batch(ctx, b, n, status_out)) return rc;
-    if (kc && kc->ctx != ctx) return SSA_ERR_ARG;
+    if (kc && (kc->ctx != ctx || kc->wire_mode)) return SSA_ERR_ARG;      // (a wire cache takes wire records: section 18)
     CallStats st(stats_words);
     st.out(stats_out);      // (still empty: the caller's words are zeroed)
     if (flags == SSA_FLAG_SIG_FLAG_BYTE)      // verify_batch semantics: no key check to add or to cache
@@ -2125,4 +2140,177 @@ extern "C" int ssa_verify_many_cached(ssa_ctx *ctx, ssa_keycache *kc, const uint
     if (!kc) return SSA_ERR_ARG;
     return many_screened_host(ctx, kc, {sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len}, n, flags, coeffs, status_out,
                               n_fail_out, stats_out, 12);
+}
+
+// ------------------------------------------------------------------------------------------------
+// KeyedSignature wire records.  ssa_verify_keyed_many_device: the exact call on device buffers.
+// ssa_verify_keyed_many_cached: ssa_verify_many_cached on 130-byte records through a cache in wire mode -- the key's 49
+// bytes are its identity, so a warm call decompresses nothing.  Kernels: ssa_keyed.hpp; the slice: ssa_api.hip.
+
+// ONE slice of at most lane_slice records on the exact path: unpacked into the context's per-lane workspaces, then
+// ssa_verify_many_device with the caller's flags (*d_fail is zeroed by it)
+static int keyed_exact_slice(ssa_ctx *ctx, const uint8_t *d_keyed, const MsgView &mv, size_t n, uint32_t flags,
+                             uint8_t *d_status, unsigned long long *d_fail) {
+    DevBatch b{nullptr, nullptr, nullptr, mv};
+    if (int rc = ssa_internal_unpack_keyed(ctx, d_keyed, n, &b)) return rc;
+    return ssa_verify_many_device(ctx, b.sigs, b.pks, b.pk_inf, mv.msgs, mv.off, mv.stride, mv.len, n, flags, d_status,
+                                  (uint64_t *)d_fail);
+}
+
+// check_dev_batch for records: the argument checks of the device forms, before anything is zeroed or enqueued
+static int check_keyed_dev(const ssa_ctx *ctx, const uint8_t *d_keyed, const MsgView &mv, size_t n,
+                           const uint8_t *d_status_out, const uint8_t *d_coeffs, uint32_t coeff_bytes) {
+    if (!ctx || (n && (!d_keyed || !d_status_out))) return SSA_ERR_ARG;
+    if (d_coeffs && (coeff_bytes == 0 || coeff_bytes > 32)) return SSA_ERR_ARG;
+    return check_msgs(mv, n);
+}
+
+extern "C" int ssa_verify_keyed_many_device(ssa_ctx *ctx, const uint8_t *d_keyed, const uint8_t *d_msgs,
+                                            const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len, size_t n,
+                                            uint32_t flags, uint8_t *d_status_out, uint64_t *d_n_fail_out) {
+    const MsgView mv{d_msgs, d_msg_off, msg_stride, msg_len};
+    if (int rc = check_keyed_dev(ctx, d_keyed, mv, n, d_status_out, nullptr, 32)) return rc;
+    unsigned long long *d_fail;
+    if (int rc = reset_fail_counter(ctx, d_n_fail_out, &d_fail)) return rc;
+    if (n == 0) return 0;
+    if (n <= ctx->knobs.lane_slice) return keyed_exact_slice(ctx, d_keyed, mv, n, flags, d_status_out, d_fail);
+    if (ctx->scr_fail.reserve(16)) return SSA_ERR_HIP;
+    const DevBatch b{nullptr, nullptr, nullptr, mv};
+    if (int rc = for_dev_slices(b, n, ctx->knobs.lane_slice, [&](size_t lo, size_t cnt, const DevBatch &s) {
+            return keyed_exact_slice(ctx, d_keyed + 130 * lo, s.msgs, cnt, flags, d_status_out + lo,
+                                     (unsigned long long *)ctx->scr_fail.p);
+        }))
+        return rc;
+    return screen_count(ctx, d_status_out, n, d_fail);
+}
+
+// ONE slice (n <= SSA_LANE_SLICE records) of the wire form on ctx->stream into d_status[0, n): screen_many_slice with
+// the keys looked up by their 49 bytes.  A slice of at most msm_small_max lanes takes the exact keyed path.
+static int keyed_cached_slice(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *d_keyed, const MsgView &mv, size_t n,
+                              const uint8_t *d_coeffs, uint32_t coeff_bytes, uint32_t flags, uint8_t *d_status,
+                              CallStats *stats) {
+    uint64_t sv[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    if (ctx->scr_fail.reserve(16)) return SSA_ERR_HIP;
+    if (n <= ctx->knobs.msm_small_max) {
+        sv[6] = 1;
+        const int rc = keyed_exact_slice(ctx, d_keyed, mv, n, flags, d_status, (unsigned long long *)ctx->scr_fail.p);
+        if (rc == 0 && stats) stats->add(sv);
+        return rc;
+    }
+    uint64_t u = 0, hits = 0;
+    KeyView kv{};
+    DevBatch b{nullptr, nullptr, nullptr, mv};
+    const unsigned long long *d_unpublished = nullptr;
+    if (int rc = ssa_internal_keyed_cache_slice(ctx, kc, d_keyed, n, &b, &kv, &u, &hits, sv + 8, &d_unpublished)) return rc;
+    return screen_slice_after_keys(ctx, b, n, d_coeffs, coeff_bytes, flags, nullptr, d_status, stats, kv, u, hits,
+                                   d_unpublished, sv);
+}
+
+// flags == SSA_FLAG_SIG_FLAG_BYTE alone (verify_batch semantics: no key check to cache): the records unpacked, slice by
+// slice of the MSM form, and ssa_verify_batch_screened_device as it is; the cache is not touched
+static int keyed_batch_screened_device(ssa_ctx *ctx, const uint8_t *d_keyed, const MsgView &mv, size_t n,
+                                       const uint8_t *d_coeffs, uint32_t coeff_bytes, uint8_t *d_status_out,
+                                       uint64_t *d_n_fail_out) {
+    unsigned long long *d_fail;
+    if (int rc = reset_fail_counter(ctx, d_n_fail_out, &d_fail)) return rc;
+    if (n == 0) return 0;
+    if (ctx->scr_fail.reserve(16)) return SSA_ERR_HIP;
+    const DevBatch whole{nullptr, nullptr, nullptr, mv};
+    if (int rc = for_dev_slices(whole, n, ctx->knobs.msm_slice, [&](size_t lo, size_t cnt, const DevBatch &s) {
+            DevBatch b = s;
+            if (int r = ssa_internal_unpack_keyed(ctx, d_keyed + 130 * lo, cnt, &b)) return r;
+            return ssa_verify_batch_screened_device(ctx, b.sigs, b.pks, b.pk_inf, b.msgs.msgs, b.msgs.off, b.msgs.stride,
+                                                    b.msgs.len, cnt, d_coeffs ? d_coeffs + (size_t)coeff_bytes * lo : nullptr,
+                                                    coeff_bytes, d_status_out + lo, (uint64_t *)ctx->scr_fail.p);
+        }))
+        return rc;
+    return screen_count(ctx, d_status_out, n, d_fail);
+}
+
+extern "C" int ssa_verify_keyed_many_cached_device(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *d_keyed,
+                                                   const uint8_t *d_msgs, const uint64_t *d_msg_off, size_t msg_stride,
+                                                   size_t msg_len, size_t n, uint32_t flags, const uint8_t *d_coeffs,
+                                                   uint32_t coeff_bytes, uint8_t *d_status_out, uint64_t *d_n_fail_out,
+                                                   uint64_t stats_out[12]) {
+    if (flags & ~MANY_SCREEN_FLAGS) return SSA_ERR_ARG;
+    if (!kc) return SSA_ERR_ARG;
+    const MsgView mv{d_msgs, d_msg_off, msg_stride, msg_len};
+    if (int rc = check_keyed_dev(ctx, d_keyed, mv, n, d_status_out, d_coeffs, coeff_bytes)) return rc;
+    if (kc->ctx != ctx || !kc->wire_mode) return SSA_ERR_ARG;      // (an affine cache takes affine keys: section 16)
+    CallStats st(12);
+    st.out(stats_out);      // (still empty: the caller's words are zeroed)
+    if (flags == SSA_FLAG_SIG_FLAG_BYTE)
+        return keyed_batch_screened_device(ctx, d_keyed, mv, n, d_coeffs, coeff_bytes, d_status_out, d_n_fail_out);
+    unsigned long long *d_fail;
+    if (int rc = reset_fail_counter(ctx, d_n_fail_out, &d_fail)) return rc;
+    if (n == 0) return 0;
+    if (n <= ctx->knobs.msm_small_max) {
+        const int rc = keyed_exact_slice(ctx, d_keyed, mv, n, flags, d_status_out, d_fail);
+        if (rc == 0 && stats_out) stats_out[6] = 1;
+        return rc;
+    }
+    const DevBatch whole{nullptr, nullptr, nullptr, mv};
+    if (int rc = for_dev_slices(whole, n, many_screen_slice_lanes(ctx), [&](size_t lo, size_t cnt, const DevBatch &s) {
+            return keyed_cached_slice(ctx, kc, d_keyed + 130 * lo, s.msgs, cnt,
+                                      d_coeffs ? d_coeffs + (size_t)coeff_bytes * lo : nullptr, coeff_bytes, flags,
+                                      d_status_out + lo, stats_out ? &st : nullptr);
+        }))
+        return rc;
+    if (int rc = screen_count(ctx, d_status_out, n, d_fail)) return rc;
+    st.out(stats_out);
+    return 0;
+}
+
+// ONE slice of the wire form from host buffers (b: the messages only): the 130-byte records, the messages and the
+// coefficients are staged on the context's stream -- no pipelined upload-and-hash: the hash needs y, which exists only
+// after the look-up -- and device_form(d_keyed, messages, d_coeffs, d_status, d_fail) leaves the statuses and their count
+template <class F>
+static int keyed_host_one(ssa_ctx *ctx, const uint8_t *keyed, const HostBatch &b, size_t n, const uint8_t *coeffs,
+                          uint8_t *status_out, uint64_t *nf_out, F &&device_form) {
+    HostCall hc(ctx);
+    const u8 *d_keyed = hc.in(ctx->st_keyed, keyed, n * 130);
+    const MsgView mv = hc.msgs(b.msgs, b.msg_off, b.msg_stride, b.msg_len, n);
+    const u8 *d_coeffs = coeffs ? hc.in(ctx->st_coeffs, coeffs, n * 32) : nullptr;
+    u8 *d_status = hc.out(ctx->st_status, status_out, n, 16);
+    unsigned long long nf = 0, *d_fail = (unsigned long long *)ctx->ws_fail.p;
+    hc.copy_back(&nf, d_fail, sizeof nf);
+    if (int rc = hc.finish([&] { return device_form(d_keyed, mv, d_coeffs, d_status, d_fail); })) return rc;
+    if (nf_out) *nf_out = nf;
+    return 0;
+}
+
+extern "C" int ssa_verify_keyed_many_cached(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *keyed, const uint8_t *msgs,
+                                            const uint64_t *msg_off, size_t msg_stride, size_t msg_len, size_t n,
+                                            uint32_t flags, const uint8_t *coeffs, uint8_t *status_out,
+                                            uint64_t *n_fail_out, uint64_t stats_out[12]) {
+    if (flags & ~MANY_SCREEN_FLAGS) return SSA_ERR_ARG;
+    if (!ctx || !kc || (n && (!keyed || !status_out))) return SSA_ERR_ARG;
+    if (int rc = check_msgs({msgs, msg_off, msg_stride, msg_len}, n)) return rc;
+    if (int rc = check_host_offsets(msg_off, n)) return rc;
+    if (kc->ctx != ctx || !kc->wire_mode) return SSA_ERR_ARG;      // (an affine cache takes affine keys: section 16)
+    CallStats st(12);
+    st.out(stats_out);      // (still empty: the caller's words are zeroed)
+    if (n_fail_out) *n_fail_out = 0;
+    if (n == 0) return 0;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const HostBatch b{nullptr, nullptr, nullptr, msgs, msg_off, msg_stride, msg_len};
+    const bool batch_form = flags == SSA_FLAG_SIG_FLAG_BYTE, small = !batch_form && n <= ctx->knobs.msm_small_max;
+    // every slice reads and may extend the one cache: in order, on this context alone (host_slices_in_order)
+    const size_t slice = batch_form ? ctx->knobs.msm_slice : many_screen_slice_lanes(ctx);
+    const int rc = host_slices_in_order(ctx, b, n, slice, n_fail_out,
+                                        [&](ssa_ctx *c, size_t lo, size_t cnt, const HostBatch &s, uint64_t *nf) {
+        return keyed_host_one(c, keyed + 130 * lo, s, cnt, coeffs ? coeffs + 32 * lo : nullptr, status_out + lo, nf,
+                              [&](const u8 *d_keyed, const MsgView &mv, const u8 *d_coeffs, u8 *d_status,
+                                  unsigned long long *d_fail) {
+            if (batch_form) return keyed_batch_screened_device(c, d_keyed, mv, cnt, d_coeffs, 32, d_status, (uint64_t *)d_fail);
+            if (small) return keyed_exact_slice(c, d_keyed, mv, cnt, flags, d_status, d_fail);
+            if (int r = keyed_cached_slice(c, kc, d_keyed, mv, cnt, d_coeffs, 32, flags, d_status, stats_out ? &st : nullptr))
+                return r;
+            return screen_count(c, d_status, cnt, d_fail);
+        });
+    });
+    if (rc) return rc;
+    if (small && stats_out) stats_out[6] = 1;
+    if (!small && !batch_form) st.out(stats_out);
+    return 0;
 }

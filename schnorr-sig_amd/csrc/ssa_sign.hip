@@ -421,6 +421,7 @@ int ssa_internal_sign_indexed_vartime(ssa_ctx *ctx, const ssa_signer_set *ss, co
 
 // the exact check of the tables (ssa_k_gtab_check, ssa_k_ctab_check_b) and its test hooks
 #include "ssa_selfcheck.hpp"
+#include "ssa_keyed.hpp"      // (the layout of a wire row: KY_WIRE_WORDS)
 #include "ssa_keycheck.hpp"
 
 // the 98 KB table of the constant-time signer, built once per context -- and COMPLETE before the call returns: a later

@@ -659,10 +659,14 @@ class KeyCache {
     struct Info {
         uint64_t capacity, held, clears, device_bytes;
     };
-    KeyCache(Context &cx, size_t capacity) {
-        const int rc = ssa_keycache_create(cx.get(), capacity, &kc_);
-        if (rc != 0) throw std::runtime_error(std::string("ssa_keycache_create: ") + ssa_strerror(rc));
+    // Wire (SSA_KEYCACHE_WIRE): a key is identified by its 49 compressed bytes as received; such a
+    // cache serves verify_keyed_many_cached_statuses / verify_keyed_many_cached_device and no other call
+    enum Mode : uint32_t { Affine = 0u, Wire = SSA_KEYCACHE_WIRE };
+    KeyCache(Context &cx, size_t capacity, Mode mode = Affine) : wire_(mode == Wire) {
+        const int rc = ssa_keycache_create_ex(cx.get(), capacity, (uint32_t)mode, &kc_);
+        if (rc != 0) throw std::runtime_error(std::string("ssa_keycache_create_ex: ") + ssa_strerror(rc));
     }
+    bool wire() const { return wire_; }
     ~KeyCache() { ssa_keycache_destroy(kc_); }
     KeyCache(const KeyCache &) = delete;
     KeyCache &operator=(const KeyCache &) = delete;
@@ -687,6 +691,7 @@ class KeyCache {
 
   private:
     ssa_keycache *kc_ = nullptr;
+    bool wire_ = false;
 };
 
 // verify_many_screened_statuses with each public key's check done once per cache, not once per slice: byte for byte the
@@ -701,6 +706,44 @@ inline std::vector<uint8_t> verify_many_cached_statuses(Context &cx, KeyCache &c
         return ssa_verify_many_cached(cx.get(), cache.get(), t.sigs.data(), t.pks.data(), t.inf.data(), t.flat.data(),
                                       t.off.data(), 0, 0, n, SSA_FLAG_CHECK_TORSION, coeffs, status, nullptr, stats_out);
     });
+}
+
+// KeyedSignature::verify (src/signature.rs:232-234) over n wire records of 130 bytes, pk (49) || signature (81), as they
+// arrive from the network, through a key cache in Wire mode: a key seen before -- one that does not
+// decode included -- is neither decompressed nor checked again.  The statuses of verify_many_cached_statuses on the
+// unpacked records, byte for byte for the same coefficients; a record whose key does not decode gets 3.  stats_out: 12
+// words, optional.
+inline std::vector<uint8_t> verify_keyed_many_cached_statuses(Context &cx, KeyCache &cache, const std::vector<uint8_t> &keyed,
+                                                              const std::vector<std::pair<const uint8_t *, size_t>> &messages,
+                                                              Rng rng = nullptr, uint64_t *stats_out = nullptr) {
+    if (keyed.size() != messages.size() * KEYED_SIGNATURE_LENGTH)
+        throw std::invalid_argument("We should have the same number of messages than keyed signatures");
+    const size_t n = messages.size();
+    std::vector<uint8_t> flat;
+    std::vector<uint64_t> off(n + 1, 0);
+    for (size_t i = 0; i < n; i++) {
+        flat.insert(flat.end(), messages[i].first, messages[i].first + messages[i].second);
+        off[i + 1] = flat.size();
+    }
+    flat.push_back(0);
+    return statuses_of(n, rng, "ssa_verify_keyed_many_cached", [&](uint8_t *status, const uint8_t *coeffs) {
+        return ssa_verify_keyed_many_cached(cx.get(), cache.get(), keyed.data(), flat.data(), off.data(), 0, 0, n,
+                                            SSA_FLAG_CHECK_TORSION, coeffs, status, nullptr, stats_out);
+    });
+}
+
+// the device forms as they are: n records and n messages of msg_len bytes, side by side, in device memory
+inline int verify_keyed_many_cached_device(Context &cx, KeyCache &cache, const uint8_t *d_keyed, const uint8_t *d_msgs,
+                                           size_t msg_len, size_t n, uint32_t flags, const uint8_t *d_coeffs,
+                                           uint32_t coeff_bytes, uint8_t *d_status_out, uint64_t *d_n_fail_out,
+                                           uint64_t *stats_out = nullptr) {
+    return ssa_verify_keyed_many_cached_device(cx.get(), cache.get(), d_keyed, d_msgs, nullptr, msg_len, msg_len, n, flags,
+                                               d_coeffs, coeff_bytes, d_status_out, d_n_fail_out, stats_out);
+}
+inline int verify_keyed_many_device(Context &cx, const uint8_t *d_keyed, const uint8_t *d_msgs, size_t msg_len, size_t n,
+                                    uint32_t flags, uint8_t *d_status_out, uint64_t *d_n_fail_out) {
+    return ssa_verify_keyed_many_device(cx.get(), d_keyed, d_msgs, nullptr, msg_len, msg_len, n, flags, d_status_out,
+                                        d_n_fail_out);
 }
 
 // ---- hierarchical deterministic key derivation (src/derivation.rs) ---------------------------------------------------
