@@ -867,6 +867,12 @@ int ssa_debug_arith(ssa_ctx *ctx, int op, const uint64_t *a, const uint64_t *b, 
  * has been enqueued (one shot; chunk < 0 disarms).  Replaces round 3's SSA_FAULT_AFTER_CHUNK environment variable: the
  * production path reads no environment per call. */
 int ssa_debug_fault_after_chunk(ssa_ctx *ctx, int chunk);
+/* call-order tests: fills every workspace and staging buffer of the context (and of its second set, once a call of more
+ * than one slice has made it) with `byte` (0..255), up to each buffer's full capacity, and the page-locked host buffers
+ * too; waits for the context's stream first and returns when the fill is done.  The constant-time signer's table is
+ * left alone (it is state that persists between calls, not a workspace), and so is everything a context shares or
+ * hands out: the comb for G, the parameters, key sets, key caches, signer sets.  Results of later calls must not change. */
+int ssa_debug_poison_workspaces(ssa_ctx *ctx, int byte);
 /* self-check tests.  which: 0 the comb for G, 1 the constant-time table (SSA_ERR_ARG before it is built).  Rows are 12
  * words (x[6], y[6]); rows and words outside the table are SSA_ERR_ARG, nothing is read or written out of bounds.
  *   ssa_debug_table_read  copies rows [first_row, first_row + n) to rows_out (n x 12 words)

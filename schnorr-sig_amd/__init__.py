@@ -250,6 +250,7 @@ def _load():
         "ssa_signer_set_secret_keys": (i32, [vp, vp]),
         "ssa_debug_pin_rng": (i32, [vp, vp]),
         "ssa_debug_draw_scalars": (i32, [vp, vp, sz, vp]),
+        "ssa_debug_poison_workspaces": (i32, [vp, i32]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)      # AttributeError here == ABI symbol missing: fail loudly
@@ -973,6 +974,11 @@ class Engine:
     def debug_fault_after_chunk(self, chunk):
         """tests: the NEXT pipelined host-buffer upload fails after chunk `chunk` (one shot; < 0 disarms)"""
         _check(_lib.ssa_debug_fault_after_chunk(self._ctx, int(chunk)), "ssa_debug_fault_after_chunk")
+
+    def debug_poison_workspaces(self, byte):
+        """tests: every workspace, staging and page-locked buffer of the context (and of its second set) filled with
+        `byte` up to its capacity; the constant-time table and everything shared or handed out stay as they are"""
+        _check(_lib.ssa_debug_poison_workspaces(self._ctx, int(byte)), "ssa_debug_poison_workspaces")
 
     def verify_many_device(self, d_sigs, d_pks, d_msgs, n, msg_len, d_status, d_nfail, msg_stride=None,
                            d_offsets=0, d_pk_inf=0, check_torsion=False, mode=None, sig_flag_byte=False):

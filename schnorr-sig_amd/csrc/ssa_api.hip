@@ -1714,6 +1714,37 @@ extern "C" int ssa_debug_fault_after_chunk(ssa_ctx *ctx, int chunk) {
     return 0;
 }
 
+// Tests of "a call's result does not depend on what its workspaces held before" ("What a call may assume
+// about its workspaces"): every byte up to `cap` of every DevBuf of the context and of its twin becomes `byte`, on each
+// one's own stream and behind whatever is queued there, and every HostBuf on the host.  The one listed buffer left out
+// is ctab: it is no workspace but the constant-time signer's table, built once and trusted from then on (ctab_ready);
+// filling it would make every later constant-time signature wrong by design.  No other listed buffer is read by a call
+// that did not write it first (rng_seed, rng_scratch and dv_recs are wiped after each call, not kept).  What is not in
+// the list -- the comb, d_params, key sets, key caches, signer sets -- is not touched.
+extern "C" int ssa_debug_poison_workspaces(ssa_ctx *ctx, int byte) {
+    if (!ctx || byte < 0 || byte > 255) return SSA_ERR_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    for (ssa_ctx *c : {ctx, ctx->twin}) {
+        if (!c) continue;
+        // (every public call returns with its side streams joined to c->stream or drained; they are waited for all the
+        //  same, so that the fill can never race a copy or a hash launch still reading a staging buffer)
+        HIP_TRY(hipStreamSynchronize(c->copy_stream));
+        for (auto &hs : c->hash_stream) HIP_TRY(hipStreamSynchronize(hs));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        hipError_t err = hipSuccess;
+        for_each_devbuf(c, [&](DevBuf &b) {
+            if (&b == &c->ctab || !b.p || !b.cap || err != hipSuccess) return;
+            err = hipMemsetAsync(b.p, byte, b.cap, c->stream);
+        });
+        HIP_TRY(err);
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        for_each_hostbuf(c, [&](HostBuf &b) {
+            if (b.p && b.cap) std::memset(b.p, byte, b.cap);
+        });
+    }
+    return 0;
+}
+
 extern "C" int ssa_debug_arith(ssa_ctx *ctx, int op, const uint64_t *a, const uint64_t *b, size_t n,
                                size_t a_stride, size_t b_stride, uint64_t *out, size_t out_stride) {
     if (!ctx || !a || !out || n == 0 || op < 0 || op > 18) return SSA_ERR_ARG;

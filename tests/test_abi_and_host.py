@@ -21,6 +21,17 @@ def test_library_exports_every_declared_symbol():
     assert declared == set(ssa.ABI_SYMBOLS)
 
 
+def test_poison_hook_is_declared_mirrored_and_refuses_no_context():
+    """ssa_debug_poison_workspaces (the call-order tests' hook): in the header's debug section, in the ctypes table, on
+    Engine, and SSA_ERR_ARG without a context -- an additive symbol, the ABI version stays"""
+    import schnorr_sig_amd as ssa
+    hdr = open(os.path.join(ROOT, "include", "schnorr_sig_amd.h")).read()
+    assert hdr.index("int ssa_debug_poison_workspaces(ssa_ctx *ctx, int byte);") > hdr.index("#define SSA_ABI_VERSION")
+    assert "ssa_debug_poison_workspaces" in ssa.ABI_SYMBOLS and callable(ssa.Engine.debug_poison_workspaces)
+    assert ssa._lib.ssa_debug_poison_workspaces(None, 0) == ssa.ERR_ARG
+    assert ssa._lib.ssa_debug_poison_workspaces(None, 256) == ssa.ERR_ARG
+
+
 def test_header_constants_match_reference_lengths():
     hdr = open(os.path.join(ROOT, "include", "schnorr_sig_amd.h")).read()
     vals = dict(re.findall(r"#define (SSA_[A-Z_]+) +\(?(-?\d+)u?\)?", hdr))

@@ -2,6 +2,7 @@
 rule: a context is used by one thread at a time, any number of contexts may run side by side -- include/schnorr_sig_amd.h;
 the contexts share the generator's comb table through a reference-counted registry).  Every lane against statuses known by
 construction; contexts are created and destroyed inside the threads as well.
+The long soak; tests/test_gpu_concurrent_contexts.py is the suite's quick version (every family of calls, exact equality).
     python tools/soak_threads.py [seconds] [threads]"""
 import os
 import sys
