@@ -657,6 +657,43 @@ int ssa_verify_keyed_many_device(ssa_ctx *ctx, const uint8_t *d_keyed, const uin
                                  size_t msg_stride, size_t msg_len, size_t n, uint32_t flags, uint8_t *d_status_out,
                                  uint64_t *d_n_fail_out);
 
+/* ---- key cache eviction: keep the keys used most recently when the cache fills -----------
+ * A cache clears itself when a slice's misses do not fit (step 3 above) until ssa_keycache_set_eviction(kc,
+ * SSA_KEYCACHE_EVICT_RECENT) is called on it; SSA_KEYCACHE_EVICT_CLEAR goes back.  Both work on affine and wire
+ * caches, empty or not.  The policy is no flag of ssa_keycache_create_ex.  A NULL or orphaned cache, or any other
+ * policy value, is SSA_ERR_ARG.
+ * SSA_KEYCACHE_EVICT_RECENT allocates, at that call, everything the policy will ever need: a 32-bit stamp per row and
+ * the compaction's scratch (12 bytes per row and a little per 256 rows), sized for `capacity`.  ssa_keycache_info()[3]
+ * reports the larger footprint from then on and it never changes again (going back to CLEAR keeps the memory).  A
+ * failed allocation is SSA_ERR_HIP and leaves the policy as it was.  Rows already held count as used now.
+ * Under SSA_KEYCACHE_EVICT_RECENT the cache has an epoch, one more for every slice that looks keys up in it.  The
+ * look-up stores the epoch into the stamp of every row it hits; inserted rows get the current epoch.  The plan stays a
+ * pure function of (capacity, held, u, m): insert if held + m <= capacity, else COMPACT (where the default policy clears)
+ * if u <= capacity, else bypass.
+ * A compaction: age(r) = epoch - stamp(r) (32-bit; 0 for the rows this slice hit); hist[a] = rows of age a for a in
+ * 0..62, hist[63] = all older rows, never kept; budget = max(u - m, (capacity - m) / 2); a* = the largest a in 0..62
+ * with hist[0] + .. + hist[a] <= budget and K = that sum (ssa_debug_keycache_keep: out[0] = a*, out[1] = K).  The K
+ * rows of age <= a* survive and are packed into rows [0, K) -- survivors below K stay, the t-th survivor at a row >= K
+ * moves whole into the t-th other row below K --, every slot is emptied and rows [0, K) are published again, the
+ * slice's hits follow their rows, and the m misses are inserted at rows K .. K + m as ever: held = K + m <= capacity.
+ * K < held, so a compaction always drops a row, and since at most half of the room beside the misses is kept the next
+ * compaction is at least (capacity - m) / 2 insertions away.  No key that is still in use is checked twice.  Stamps alias
+ * after 2^32 slices: that can change which rows are kept, never a status (should the aliased ages leave no a*, the
+ * cache is cleared as under the default policy).
+ * The contract of ssa_verify_many_cached / ssa_verify_keyed_many_cached is unchanged -- the status vector equals
+ * ssa_verify_many_screened's BYTE FOR BYTE in every state of the cache, during and after a compaction included -- and
+ * so are stats[0..9] and [11]; [10] counts automatic evictions: clears of a CLEAR cache, compactions of a RECENT one.
+ * Rows that find no slot when they are published again are counted in [7].  ssa_keycache_info is unchanged (its clears
+ * count clears only); ssa_keycache_selfcheck, its repair and ssa_debug_keytab_read work on rows [0, held) as before.
+ * ssa_keycache_eviction_info: out[0] policy, [1] compactions since creation, [2] rows dropped by them, [3] rows kept
+ * and [4] rows moved by the last one, [5] the epoch, [6] = [7] = 0.
+ * A compaction costs two more read-backs in its slice.  Timing key: keycache_compact (ages, marking, move, publishing,
+ * remapping). */
+#define SSA_KEYCACHE_EVICT_CLEAR  0u   /* whole-cache eviction, the default */
+#define SSA_KEYCACHE_EVICT_RECENT 1u   /* keep the rows used most recently */
+int ssa_keycache_set_eviction(ssa_keycache *kc, uint32_t policy);
+int ssa_keycache_eviction_info(ssa_keycache *kc, uint64_t out[8]);
+
 /* Exact self-check of the per-key tables of a key set or a key cache, on the owning context's
  * stream; returns when it is done.  ssa_ctx_selfcheck covers the tables for G; these two cover what lives as long as a
  * validator set does: per key the 4 KB table of sixteen multiples, the status byte and, in comb mode, the 100 MB comb.
@@ -927,6 +964,11 @@ int ssa_debug_dedup_config(ssa_ctx *ctx, double max_distinct_ratio, uint32_t pro
  * insert all u keys, 2 bypass the cache.  SSA_ERR_ARG for a capacity outside 1..2^24, held > capacity, m > u or
  * u > SSA_MAX_BATCH. */
 int ssa_debug_keycache_plan(uint64_t capacity, uint64_t held, uint64_t u, uint64_t m, uint32_t *plan_out);
+/* host logic of a compaction (SSA_KEYCACHE_EVICT_RECENT), no context and no device needed: hist[a] = rows of age a (a < 63),
+ * hist[63] = older rows; out[0] = a*, out[1] = K as defined with ssa_keycache_set_eviction.  SSA_ERR_ARG for a capacity
+ * outside 1..2^24, m > u, u > capacity, more rows in hist than capacity, or hist[0] above the budget (more rows of age 0
+ * than the slice has hits: no a* exists). */
+int ssa_debug_keycache_keep(uint64_t capacity, uint64_t u, uint64_t m, const uint64_t hist[64], uint64_t out[2]);
 /* n_blocks 64-byte blocks of the ChaCha20 keystream the MSM coefficients come from (RFC 8439 known answers) */
 int ssa_debug_chacha20(ssa_ctx *ctx, const uint8_t key[32], const uint8_t nonce[12], uint32_t counter0,
                        size_t n_blocks, uint8_t *out);

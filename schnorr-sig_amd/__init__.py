@@ -218,6 +218,9 @@ def _load():
         "ssa_verify_keyed_many_cached_device": (i32, [vp, vp, vp, vp, vp, sz, sz, sz, u32, vp, u32, vp, vp, vp]),
         "ssa_verify_keyed_many_device": (i32, [vp, vp, vp, vp, sz, sz, sz, u32, vp, vp]),
         "ssa_debug_keycache_plan": (i32, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(u32)]),
+        "ssa_keycache_set_eviction": (i32, [vp, u32]),
+        "ssa_keycache_eviction_info": (i32, [vp, u64p]),
+        "ssa_debug_keycache_keep": (i32, [C.c_uint64, C.c_uint64, C.c_uint64, u64p, u64p]),
         "ssa_debug_dedup_device": (i32, [vp, vp, vp, sz, vp, vp]),
         "ssa_debug_dedup_config": (i32, [vp, C.c_double, u32]),
         "ssa_xprv_master_many": (i32, [vp, vp, sz, vp, vp]),
@@ -491,14 +494,25 @@ class Engine:
             stats.ctypes.data), "ssa_verify_many_screened_device")
         return stats
 
-    def keycache_create(self, capacity, wire=False):
+    def keycache_create(self, capacity, wire=False, evict="clear"):
         """a key cache of `capacity` keys on this engine's device: all of its device memory, about
         4.2 KB per key, is allocated here.  wire=True (SSA_KEYCACHE_WIRE): a key is identified by
-        its 49 compressed bytes as received; such a cache serves verify_keyed_many_cached and no other call."""
+        its 49 compressed bytes as received; such a cache serves verify_keyed_many_cached and no other call.
+        evict="recent" (KeyCache.set_eviction): a full cache keeps the keys used most recently
+        instead of clearing itself."""
+        if evict not in KEYCACHE_EVICT:
+            raise ValueError("evict must be one of %s" % sorted(KEYCACHE_EVICT))
         h = C.c_void_p()
         _check(_lib.ssa_keycache_create_ex(self._ctx, int(capacity), KEYCACHE_WIRE if wire else 0, C.byref(h)),
                "ssa_keycache_create_ex")
-        return KeyCache(self, h, wire=wire)
+        cache = KeyCache(self, h, wire=wire)
+        if evict != "clear":
+            try:
+                cache.set_eviction(evict)
+            except Exception:
+                cache.close()
+                raise
+        return cache
 
     def verify_keyed_many_cached(self, cache, keyed, msgs, offsets=None, check_torsion=True, sig_flag_byte=False,
                                  coeffs=None):
@@ -1069,6 +1083,7 @@ KEYTAB_WIRE = 5     # key caches in wire mode: the row's 49 compressed bytes as 
 _KEYTAB_READ_WORDS = {KEYTAB_LADDER: 512, KEYTAB_STATUS: 1, KEYTAB_KEY: 12, KEYTAB_PK_INF: 1, KEYTAB_COMB: 24,
                       KEYTAB_WIRE: 7}
 KEYCACHE_WIRE = 1   # SSA_KEYCACHE_WIRE
+KEYCACHE_EVICT = {"clear": 0, "recent": 1}   # SSA_KEYCACHE_EVICT_CLEAR / _RECENT
 
 
 def _keycheck_result(rc, out, what):
@@ -1152,6 +1167,22 @@ class KeyCache(_KeyTables):
         out = (C.c_uint64 * 4)()
         _check(_lib.ssa_keycache_info(self.handle, out), "ssa_keycache_info")
         return {"capacity": int(out[0]), "held": int(out[1]), "clears": int(out[2]), "device_bytes": int(out[3])}
+
+    def set_eviction(self, policy):
+        """ssa_keycache_set_eviction: "clear" (the default: a full cache clears itself) or "recent" (a full cache keeps
+        the rows used most recently: DESIGN.md section 19).  "recent" allocates the rows' stamps and the compaction's
+        scratch, once: info()["device_bytes"] grows here and never again."""
+        if policy not in KEYCACHE_EVICT:
+            raise ValueError("policy must be one of %s" % sorted(KEYCACHE_EVICT))
+        _check(_lib.ssa_keycache_set_eviction(self.handle, KEYCACHE_EVICT[policy]), "ssa_keycache_set_eviction")
+
+    def eviction_info(self):
+        """{'policy' ("clear" / "recent"), 'compactions', 'dropped', 'last_kept', 'last_moved', 'epoch'}"""
+        out = (C.c_uint64 * 8)()
+        _check(_lib.ssa_keycache_eviction_info(self.handle, out), "ssa_keycache_eviction_info")
+        names = {v: k for k, v in KEYCACHE_EVICT.items()}
+        return {"policy": names[int(out[0])], "compactions": int(out[1]), "dropped": int(out[2]),
+                "last_kept": int(out[3]), "last_moved": int(out[4]), "epoch": int(out[5])}
 
     def _pair(self):
         return None, self.handle
@@ -1790,6 +1821,14 @@ def verify_keyed_many_cached(keyed_signatures, messages, cache, rng=None, engine
                                         for _ in keyed_signatures), np.uint8)
     status, _, _ = eng.verify_keyed_many_cached(cache, keyed, flat, offsets=off, check_torsion=True, coeffs=coeffs)
     return _status_results(status)
+
+
+def keycache_keep(capacity, u, m, hist):
+    """ssa_debug_keycache_keep: (a*, K) of a compaction from the 64 age counts (no device needed)"""
+    h = (C.c_uint64 * 64)(*[int(v) for v in hist])
+    out = (C.c_uint64 * 2)()
+    _check(_lib.ssa_debug_keycache_keep(int(capacity), int(u), int(m), h, out), "ssa_debug_keycache_keep")
+    return int(out[0]), int(out[1])
 
 
 def keycache_plan(capacity, held, u, m):

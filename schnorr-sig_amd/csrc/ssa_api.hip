@@ -1384,6 +1384,204 @@ extern "C" int ssa_debug_keycache_plan(uint64_t capacity, uint64_t held, uint64_
     return 0;
 }
 
+extern "C" int ssa_debug_keycache_keep(uint64_t capacity, uint64_t u, uint64_t m, const uint64_t hist[64],
+                                       uint64_t out[2]) {
+    if (!hist || !out || capacity == 0 || capacity > KC_MAX_CAPACITY || m > u || u > capacity) return SSA_ERR_ARG;
+    uint64_t total = 0;
+    for (int a = 0; a < KC_AGE_BINS; a++) {
+        if (hist[a] > capacity) return SSA_ERR_ARG;
+        total += hist[a];
+    }
+    if (total > capacity) return SSA_ERR_ARG;      // more rows than the cache has
+    uint64_t age = 0, kept = 0;
+    if (!kc_keep(capacity, u, m, hist, &age, &kept)) return SSA_ERR_ARG;      // hist[0] > u - m: no slice leaves that
+    out[0] = age;
+    out[1] = kept;
+    return 0;
+}
+
+// ------------------------------------------------------------------ eviction by compaction
+// The compaction's scratch, sized for `capacity` rows when the policy is chosen: two totals of dd_k_scan, the 64 age
+// counts, remap[] and the lists of holes and movers (a u32 per row each), and per workgroup of rows two counts and two
+// offsets
+struct EvictWs {
+    unsigned long long *totals;
+    u32 *hist, *remap, *holes, *movers, *blk;
+    size_t nb_max;
+};
+static size_t evict_ws_bytes(size_t capacity) {
+    return 512 + (3 * capacity + 4 * (size_t)grid_for(capacity, DD_BLOCK)) * sizeof(u32);
+}
+static EvictWs evict_ws_of(ssa_keycache *kc) {
+    u8 *p = (u8 *)kc->evict_ws.p;
+    EvictWs w;
+    w.totals = (unsigned long long *)p;
+    w.hist = (u32 *)(p + 64);
+    w.remap = (u32 *)(p + 512);
+    w.holes = w.remap + kc->capacity;
+    w.movers = w.holes + kc->capacity;
+    w.blk = w.movers + kc->capacity;
+    w.nb_max = grid_for(kc->capacity, DD_BLOCK);
+    return w;
+}
+
+extern "C" int ssa_keycache_set_eviction(ssa_keycache *kc, uint32_t policy) {
+    if (!kc || !kc->ctx || (policy != SSA_KEYCACHE_EVICT_CLEAR && policy != SSA_KEYCACHE_EVICT_RECENT)) return SSA_ERR_ARG;
+    if (policy == SSA_KEYCACHE_EVICT_RECENT && kc->policy != policy) {
+        HIP_TRY(hipSetDevice(kc->ctx->device));
+        // everything the policy will ever need, now: no call that uses the cache allocates for it
+        if (!kc->stamps.p &&
+            (kc->stamps.reserve_exact(kc->capacity * sizeof(u32)) || kc->evict_ws.reserve_exact(evict_ws_bytes(kc->capacity)))) {
+            (void)hipGetLastError();
+            kc->stamps.release();
+            kc->evict_ws.release();
+            return SSA_ERR_HIP;
+        }
+        // the rows already held count as used now
+        if (kc->held)
+            HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)kc->stamps.p, (int)(u32)kc->epoch, kc->held, kc->ctx->stream));
+    }
+    kc->policy = policy;
+    return 0;
+}
+
+extern "C" int ssa_keycache_eviction_info(ssa_keycache *kc, uint64_t out[8]) {
+    if (!kc || !kc->ctx || !out) return SSA_ERR_ARG;
+    out[0] = kc->policy;
+    out[1] = kc->compactions;
+    out[2] = kc->dropped;
+    out[3] = kc->last_kept;
+    out[4] = kc->last_moved;
+    out[5] = kc->epoch;
+    out[6] = out[7] = 0;
+    return 0;
+}
+
+// A full SSA_KEYCACHE_EVICT_RECENT cache makes room for the m misses of a slice of u distinct keys (m <= u <= capacity,
+// held + m > capacity): the rows used most recently stay, packed into rows [0, K), the slots are rebuilt over them and
+// the slice's found[] follows its hits to their new rows; kc->held = K.  Two read-backs (the ages, the number of rows to
+// move): a compaction is the rare path.  *done = false, and nothing changed, when the ages say that no keep rule
+// applies (kc_keep): the caller clears.
+static int keycache_compact(ssa_ctx *ctx, ssa_keycache *kc, uint64_t u, uint64_t m, u32 *found,
+                            unsigned long long *d_unpublished, bool *done) {
+    constexpr u32 TAB_WORDS = (u32)(PTAB_ENTRIES * PTAB_ENTRY_U64);
+    static_assert(TAB_WORDS % 2 == 0 && KY_WIRE_WORDS <= 16, "kc_k_evict_move");
+    *done = false;
+    const EvictWs w = evict_ws_of(kc);
+    const u32 held = (u32)kc->held, epoch = (u32)kc->epoch, nb = grid_for(held, DD_BLOCK);
+    if (held == 0 || held > kc->capacity || nb > w.nb_max) return SSA_ERR_HIP;      // (never: the plan saw held + m > capacity)
+    u32 *stamps = (u32 *)kc->stamps.p, *hole_cnt = w.blk, *mover_cnt = hole_cnt + w.nb_max, *hole_off = mover_cnt + w.nb_max,
+        *mover_off = hole_off + w.nb_max;
+    int rc = timed_launch(ctx, "keycache_compact", [&] {
+        (void)hipMemsetAsync(kc->evict_ws.p, 0, 512, ctx->stream);
+        hipLaunchKernelGGL(kc_k_age_hist, dim3(nb), dim3(DD_BLOCK), 0, ctx->stream, (const u32 *)stamps, held, epoch, w.hist);
+    });
+    if (rc) return rc;
+    u32 h32[KC_AGE_BINS];
+    HIP_TRY(hipMemcpyAsync(h32, w.hist, sizeof h32, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    uint64_t hist[KC_AGE_BINS], age = 0, kept = 0, total = 0;
+    for (int a = 0; a < KC_AGE_BINS; a++) total += hist[a] = h32[a];
+    if (total != held) return SSA_ERR_HIP;      // (never)
+    if (!kc_keep(kc->capacity, u, m, hist, &age, &kept)) return 0;
+    const u32 K = (u32)kept, max_age = (u32)age;
+    rc = timed_launch(ctx, "keycache_compact", [&] {
+        hipLaunchKernelGGL(kc_k_evict_count, dim3(nb), dim3(DD_BLOCK), 0, ctx->stream, (const u32 *)stamps, held, epoch,
+                           max_age, K, hole_cnt, mover_cnt);
+        hipLaunchKernelGGL(dd_k_scan, dim3(1), dim3(DD_BLOCK), 0, ctx->stream, (const u32 *)hole_cnt, nb, hole_off, w.totals);
+        hipLaunchKernelGGL(dd_k_scan, dim3(1), dim3(DD_BLOCK), 0, ctx->stream, (const u32 *)mover_cnt, nb, mover_off,
+                           w.totals + 1);
+    });
+    if (rc) return rc;
+    unsigned long long tot[3] = {0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(tot, w.totals, sizeof tot, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    const u32 n_move = (u32)tot[1];
+    if (tot[1] != tot[2] || tot[1] > K || tot[1] > held - K) return SSA_ERR_HIP;      // (never: as many holes as movers)
+    rc = timed_launch(ctx, "keycache_compact", [&] {
+        hipLaunchKernelGGL(kc_k_evict_assign, dim3(nb), dim3(DD_BLOCK), 0, ctx->stream, (const u32 *)stamps, held, epoch,
+                           max_age, K, (const u32 *)hole_off, (const u32 *)mover_off, (u32)kc->capacity, w.holes, w.movers,
+                           w.remap);
+        if (n_move)
+            hipLaunchKernelGGL(kc_k_evict_move, dim3(grid_for(n_move, DD_BLOCK / 64)), dim3(DD_BLOCK), 0, ctx->stream,
+                               (const u32 *)w.movers, (const u32 *)w.holes, n_move, held, K, TAB_WORDS, (u64 *)kc->rows.tab.p,
+                               (u64 *)kc->rows.pks.p, (u8 *)kc->inf.p, (u8 *)kc->rows.status.p, stamps, (u64 *)kc->wire.p,
+                               kc->wire_mode ? (u32)KY_WIRE_WORDS : 0u, w.remap);
+        (void)hipMemsetAsync(kc->slots.p, 0xff, kc->n_slots * sizeof(u64), ctx->stream);
+        if (K && kc->wire_mode)
+            hipLaunchKernelGGL(ky_k_publish, dim3(grid_for(K, DD_BLOCK)), dim3(DD_BLOCK), 0, ctx->stream,
+                               (const u64 *)kc->wire.p, 0u, K, (u64)ctx->dedup_key[0], (u64)ctx->dedup_key[1],
+                               (u64 *)kc->slots.p, (u32)(kc->n_slots - 1), (u32)ctx->knobs.dedup_probe_bound, d_unpublished);
+        else if (K)
+            hipLaunchKernelGGL(kc_k_publish, dim3(grid_for(K, DD_BLOCK)), dim3(DD_BLOCK), 0, ctx->stream,
+                               (const u64 *)kc->rows.pks.p, (const u8 *)kc->inf.p, 0u, K, (u64)ctx->dedup_key[0],
+                               (u64)ctx->dedup_key[1], (u64 *)kc->slots.p, (u32)(kc->n_slots - 1),
+                               (u32)ctx->knobs.dedup_probe_bound, d_unpublished);
+        hipLaunchKernelGGL(kc_k_remap, dim3(grid_for(u, DD_BLOCK)), dim3(DD_BLOCK), 0, ctx->stream, found, (u32)u,
+                           (const u32 *)w.remap, held);
+    });
+    if (rc) return rc;
+    kc->compactions++;
+    kc->dropped += held - K;
+    kc->last_kept = K;
+    kc->last_moved = n_move;
+    kc->held = K;
+    *done = true;
+    return 0;
+}
+
+// Where the keys of a slice that uses the cache go (plan: KC_PLAN_INSERT or KC_PLAN_CLEAR), the ONE place that handles a
+// full cache, for affine and wire caches alike: the m misses behind the rows held; or, the cache being full, behind the
+// rows a compaction kept (SSA_KEYCACHE_EVICT_RECENT); or all u keys of the slice from row 0 of a cleared cache (key j of
+// the dedup takes row j).  ks[0..2] = hits, keys to insert, automatic evictions.
+struct KcPlace {
+    size_t base = 0, fresh = 0;
+    const u32 *reps = nullptr;      // the representative lanes of the keys to insert
+    bool all_new = false;           // the cache was cleared for this slice
+    bool republished = false;       // a compaction published rows again: *d_unpublished counts
+};
+static int keycache_place(ssa_ctx *ctx, ssa_keycache *kc, int plan, uint64_t u, uint64_t m, u32 *found, const u32 *miss_rep,
+                          unsigned long long *d_unpublished, uint64_t ks[4], KcPlace *pl) {
+    pl->base = kc->held;
+    pl->fresh = (size_t)m;
+    pl->reps = miss_rep;
+    if (plan == KC_PLAN_CLEAR) {
+        bool compacted = false;
+        if (kc->policy == SSA_KEYCACHE_EVICT_RECENT)
+            if (int rc = keycache_compact(ctx, kc, u, m, found, d_unpublished, &compacted)) return rc;
+        if (compacted) {
+            pl->base = kc->held;
+            pl->republished = kc->held > 0;
+        } else {
+            if (int rc = keycache_reset(kc)) return rc;
+            pl->base = 0;
+            pl->fresh = (size_t)u;
+            pl->reps = (const u32 *)ctx->dd_reps.p;
+            pl->all_new = true;
+        }
+        ks[2] = 1;
+    }
+    ks[0] = u - pl->fresh;
+    ks[1] = pl->fresh;
+    return 0;
+}
+
+// rows base .. base + fresh are built and published: they are held, and used now
+static int keycache_placed(ssa_keycache *kc, const KcPlace &pl) {
+    kc->held = pl.base + pl.fresh;
+    if (kc->policy == SSA_KEYCACHE_EVICT_RECENT && pl.fresh)
+        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)((u32 *)kc->stamps.p + pl.base), (int)(u32)kc->epoch, pl.fresh,
+                                  kc->ctx->stream));
+    return 0;
+}
+
+// the stamps and the epoch a look-up writes on its hits: a new epoch per slice under SSA_KEYCACHE_EVICT_RECENT, else none
+static u32 *keycache_new_epoch(ssa_keycache *kc) {
+    if (kc->policy != SSA_KEYCACHE_EVICT_RECENT) return nullptr;
+    kc->epoch++;
+    return (u32 *)kc->stamps.p;
+}
+
 // Rows base .. base + m of the cache from the keys of the representative lanes reps[0, m): dd_k_gather and
 // ssa_k_keyset_build as they are, with their outputs offset into the cache, then the slots of the new rows
 static int keycache_insert(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *d_pks, const uint8_t *d_pk_inf, const u32 *reps,
@@ -1416,6 +1614,7 @@ int ssa_internal_keycache_slice(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *d
     u32 *found = (u32 *)ctx->kc_found.p, *miss_rep = (u32 *)ctx->kc_missrep.p, *blk_cnt = (u32 *)ctx->kc_blk.p,
         *blk_off = blk_cnt + nb;
     const size_t held = kc->held;
+    u32 *stamps = keycache_new_epoch(kc);
     DedupHook hook;
     // d_stats: [0] lanes at the probe bound, [1] u, [2] m (dd_k_scan writes its total one word on), [3] unpublished rows
     hook.queue = [&](unsigned long long *d_stats) {
@@ -1424,7 +1623,7 @@ int ssa_internal_keycache_slice(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *d
                                (const u32 *)ctx->dd_reps.p, (u32)cnt, (const unsigned long long *)d_stats,
                                (u64)ctx->dedup_key[0], (u64)ctx->dedup_key[1], (const u64 *)kc->slots.p,
                                (u32)(kc->n_slots - 1), (u32)ctx->knobs.dedup_probe_bound, (const u64 *)kc->rows.pks.p,
-                               (const u8 *)kc->inf.p, (u32)held, found, blk_cnt);
+                               (const u8 *)kc->inf.p, (u32)held, found, blk_cnt, stamps, (u32)kc->epoch);
             hipLaunchKernelGGL(dd_k_scan, dim3(1), dim3(DD_BLOCK), 0, ctx->stream, (const u32 *)blk_cnt, (u32)nb, blk_off,
                                d_stats + 1);
             hipLaunchKernelGGL(kc_k_number, dim3((unsigned)nb), dim3(DD_BLOCK), 0, ctx->stream,
@@ -1446,26 +1645,16 @@ int ssa_internal_keycache_slice(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *d
         return dedup_check_keys(ctx, d_pks, d_pk_inf, u);
     }
     unsigned long long *d_unpub = (unsigned long long *)ctx->dd_stats.p + 3;
-    size_t base = held, fresh = (size_t)m;
-    const u32 *reps = miss_rep;
-    if (plan == KC_PLAN_CLEAR) {        // every key of the slice is new: key j of the dedup takes row j
-        if (int rc = keycache_reset(kc)) return rc;
-        ks[2] = 1;
-        base = 0;
-        fresh = (size_t)u;
-        reps = (const u32 *)ctx->dd_reps.p;
+    KcPlace pl;
+    if (int rc = keycache_place(ctx, kc, plan, u, m, found, miss_rep, d_unpub, ks, &pl)) return rc;
+    if (pl.fresh) {
+        if (int rc = keycache_insert(ctx, kc, d_pks, d_pk_inf, pl.reps, pl.base, pl.fresh, d_unpub)) return rc;
+        if (int rc = keycache_placed(kc, pl)) return rc;
     }
-    ks[0] = u - fresh;
-    ks[1] = fresh;
-    if (fresh) {
-        if (int rc = keycache_insert(ctx, kc, d_pks, d_pk_inf, reps, base, fresh, d_unpub)) return rc;
-        kc->held = base + fresh;
-        *d_unpublished = d_unpub;
-    }
+    if (pl.fresh || pl.republished) *d_unpublished = d_unpub;
     const int rc = timed_launch(ctx, "keycache_map", [&] {
         hipLaunchKernelGGL(kc_k_map, dim3((unsigned)nb), dim3(DD_BLOCK), 0, ctx->stream, (const u32 *)ctx->dd_idx.p,
-                           (const u32 *)found, (u32)cnt, (u32)base, plan == KC_PLAN_CLEAR ? 1u : 0u,
-                           (u32 *)ctx->kc_lane_row.p);
+                           (const u32 *)found, (u32)cnt, (u32)pl.base, pl.all_new ? 1u : 0u, (u32 *)ctx->kc_lane_row.p);
     });
     if (rc) return rc;
     *kv = {(const uint32_t *)ctx->kc_lane_row.p, (const uint64_t *)kc->rows.tab.p, (const uint8_t *)kc->rows.status.p,
@@ -1513,6 +1702,7 @@ int ssa_internal_keyed_cache_slice(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t
     const size_t held = kc->held;
     u64 *c_pks = (u64 *)kc->rows.pks.p, *c_wire = (u64 *)kc->wire.p;
     u8 *c_inf = (u8 *)kc->inf.p;
+    u32 *stamps = keycache_new_epoch(kc);
     DedupHook hook;
     // d_stats: [0] lanes at the probe bound, [1] u, [2] m (dd_k_scan writes its total one word on), [3] unpublished rows
     hook.queue = [&](unsigned long long *d_stats) {
@@ -1521,7 +1711,7 @@ int ssa_internal_keyed_cache_slice(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t
                                (const u32 *)ctx->dd_reps.p, (u32)cnt, (const unsigned long long *)d_stats,
                                (u64)ctx->dedup_key[0], (u64)ctx->dedup_key[1], (const u64 *)kc->slots.p,
                                (u32)(kc->n_slots - 1), (u32)ctx->knobs.dedup_probe_bound, (const u64 *)c_wire, (u32)held,
-                               found, blk_cnt);
+                               found, blk_cnt, stamps, (u32)kc->epoch);
             hipLaunchKernelGGL(dd_k_scan, dim3(1), dim3(DD_BLOCK), 0, ctx->stream, (const u32 *)blk_cnt, (u32)nb, blk_off,
                                d_stats + 1);
             hipLaunchKernelGGL(kc_k_number, dim3((unsigned)nb), dim3(DD_BLOCK), 0, ctx->stream,
@@ -1555,19 +1745,11 @@ int ssa_internal_keyed_cache_slice(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t
         row_inf = (const u8 *)ctx->dd_inf.p;
     } else {
         unsigned long long *d_unpub = (unsigned long long *)ctx->dd_stats.p + 3;
-        size_t base = held, fresh = (size_t)m;
-        const u32 *reps = miss_rep;
-        if (plan == KC_PLAN_CLEAR) {        // every key of the slice is new: key j of the dedup takes row j
-            if ((rc = keycache_reset(kc))) return rc;
-            ks[2] = 1;
-            base = 0;
-            fresh = (size_t)u;
-            reps = (const u32 *)ctx->dd_reps.p;
-        }
-        ks[0] = u - fresh;
-        ks[1] = fresh;
+        KcPlace pl;
+        if ((rc = keycache_place(ctx, kc, plan, u, m, found, miss_rep, d_unpub, ks, &pl))) return rc;
+        const size_t base = pl.base, fresh = pl.fresh;
         if (fresh) {
-            if ((rc = keyed_decompress(ctx, d_keyed, reps, fresh, cnt, c_pks + 12 * base, c_inf + base,
+            if ((rc = keyed_decompress(ctx, d_keyed, pl.reps, fresh, cnt, c_pks + 12 * base, c_inf + base,
                                        c_wire + KY_WIRE_WORDS * base)))
                 return rc;
             if ((rc = ssa_internal_keyset_build(ctx, (const u8 *)(c_pks + 12 * base), (const u8 *)(c_inf + base), fresh,
@@ -1580,13 +1762,12 @@ int ssa_internal_keyed_cache_slice(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t
                                    (u32)ctx->knobs.dedup_probe_bound, d_unpub);
             });
             if (rc) return rc;
-            kc->held = base + fresh;
-            *d_unpublished = d_unpub;
+            if ((rc = keycache_placed(kc, pl))) return rc;
         }
+        if (fresh || pl.republished) *d_unpublished = d_unpub;
         rc = timed_launch(ctx, "keycache_map", [&] {
             hipLaunchKernelGGL(kc_k_map, dim3((unsigned)nb), dim3(DD_BLOCK), 0, ctx->stream, (const u32 *)ctx->dd_idx.p,
-                               (const u32 *)found, (u32)cnt, (u32)base, plan == KC_PLAN_CLEAR ? 1u : 0u,
-                               (u32 *)ctx->kc_lane_row.p);
+                               (const u32 *)found, (u32)cnt, (u32)base, pl.all_new ? 1u : 0u, (u32 *)ctx->kc_lane_row.p);
         });
         if (rc) return rc;
         *kv = {(const uint32_t *)ctx->kc_lane_row.p, (const uint64_t *)kc->rows.tab.p, (const uint8_t *)kc->rows.status.p,

@@ -260,7 +260,7 @@ struct ssa_keyset {
 // key cache (entry points in ssa_api.hip and ssa_msm.hip): a ladder-kind key set of `capacity` rows
 // that fills itself (rows.tab, rows.status, rows.pks: rows [0, held) are complete), the pk_inf boolean of each row, and
 // the slot table over the rows (ssa_keycache.hpp).  The host knows `held`: rows are handed out in order and never freed
-// but by a clear of the whole cache.  In wire mode (SSA_KEYCACHE_WIRE) the identity of a row is the
+// but by a clear of the whole cache or a compaction (below).  In wire mode (SSA_KEYCACHE_WIRE) the identity of a row is the
 // 49 compressed bytes it was built from, kept in `wire` as seven words per row.
 struct ssa_keycache {
     ssa_ctx *ctx = nullptr;   // nullptr: the context is gone, the device memory went with it
@@ -269,12 +269,22 @@ struct ssa_keycache {
     bool wire_mode = false;
     ssa_keyset rows;          // never registered with the context: owned by the cache
     DevBuf inf, slots, wire;
-    uint64_t device_bytes() const { return rows.tab.cap + rows.status.cap + rows.pks.cap + inf.cap + slots.cap + wire.cap; }
+    // eviction (ssa_keycache_set_eviction): the policy, the epoch (one per slice that looks keys up
+    // under SSA_KEYCACHE_EVICT_RECENT), the rows' stamps and the compaction's scratch (both allocated at the first switch
+    // to that policy and kept), and what ssa_keycache_eviction_info reports
+    uint32_t policy = 0;
+    uint64_t epoch = 0, compactions = 0, dropped = 0, last_kept = 0, last_moved = 0;
+    DevBuf stamps, evict_ws;
+    uint64_t device_bytes() const {
+        return rows.tab.cap + rows.status.cap + rows.pks.cap + inf.cap + slots.cap + wire.cap + stamps.cap + evict_ws.cap;
+    }
     void release_all() {
         rows.release_all();
         inf.release();
         slots.release();
         wire.release();
+        stamps.release();
+        evict_ws.release();
     }
 };
 

@@ -24,6 +24,25 @@
 // Everything written with ordinary stores (key bytes, flags, statuses, tables, found[], the row map) is read by a LATER
 // launch on the same stream: kc_k_publish is launched after the build, so a row is complete before any later launch
 // can find it.  All device writes are vector stores and vector atomics.
+//
+// Eviction.  A cache keeps the clear-only policy above until ssa_keycache_set_eviction makes it
+// SSA_KEYCACHE_EVICT_RECENT.  Then every row has a 32-bit stamp, the cache's epoch (one per slice that looks keys up) at
+// its last use: the look-up kernels store it on a hit (one lane per distinct key, so one writer per row; a plain store,
+// read by a later launch), inserted rows get the current epoch.  Where the clear-only policy clears, the cache COMPACTS:
+//   kc_k_age_hist      rows of each age (epoch - stamp, 0..62, 63 = older) over rows [0, held): counts per workgroup
+//                      in LDS, then vector atomics on 64 words the call has zeroed.  The host reads them and kc_keep
+//                      picks the largest age a* whose rows fit the budget: K rows survive.
+//   kc_k_evict_count   per workgroup: non-survivors below row K (holes), survivors at rows >= K (movers).  There are
+//                      equally many of each.  dd_k_scan (as it is, twice) turns the counts into offsets.
+//   kc_k_evict_assign  hole t and mover t, in row order, into two lists; remap[r] = r for a survivor below K, KC_MISS
+//                      for every dropped row.
+//   kc_k_evict_move    one wave per mover: the whole row (4 KB table at 16 bytes per lane per load, key words, pk_inf,
+//                      status, stamp, wire words) from mover t to hole t, and remap[mover] = hole.  Rows read are all
+//                      >= K, rows written all < K and no survivor: the two sets are disjoint, so one launch moves every
+//                      row with no order between workgroups.
+//   kc_k_remap         the slice's found[] through remap[] (its hits have age 0: they always survive).
+// The slot words are then emptied and rows [0, K) published again by kc_k_publish / ky_k_publish, still the only
+// writers of slot words.  Everything else is ordinary vector stores read by a later launch.
 #pragma once
 #include "ssa_dedup.hpp"
 
@@ -39,6 +58,28 @@ __host__ inline int kc_plan(uint64_t capacity, uint64_t held, uint64_t u, uint64
     return u <= capacity ? KC_PLAN_CLEAR : KC_PLAN_BYPASS;
 }
 
+// Which rows a compaction keeps: hist[a] = rows of age a (a < 63; hist[63] = all older rows, never kept), u distinct keys
+// in the slice of which m missed, m <= u <= capacity.  budget = max(u - m, (capacity - m) / 2); *age_out = the largest a
+// in 0..62 with hist[0] + .. + hist[a] <= budget, *kept_out = that sum.  The rows the slice hit have age 0 and there
+// are at most u - m of them, so an age exists; false only when hist[0] says otherwise (stamps that alias after 2^32
+// slices: the caller then clears).  kept + m <= capacity, and at most half of the room left beside the misses is kept,
+// so the next compaction is at least (capacity - m) / 2 insertions away.
+constexpr int KC_AGE_BINS = 64;
+__host__ inline bool kc_keep(uint64_t capacity, uint64_t u, uint64_t m, const uint64_t hist[KC_AGE_BINS], uint64_t *age_out,
+                             uint64_t *kept_out) {
+    const uint64_t half = (capacity - m) / 2, budget = u - m > half ? u - m : half;
+    uint64_t sum = 0;
+    bool any = false;
+    for (int a = 0; a < KC_AGE_BINS - 1; a++) {
+        if (hist[a] > budget - sum) break;
+        sum += hist[a];
+        *age_out = (uint64_t)a;
+        *kept_out = sum;
+        any = true;
+    }
+    return any;
+}
+
 #ifndef SSA_NO_KERNELS
 // the 12 key words and the flag of cache row r
 SSA_DEV u64 kc_row_fingerprint(const u64 *__restrict__ c_pks, const u8 *__restrict__ c_inf, u32 r, u64 k0, u64 k1) {
@@ -48,12 +89,13 @@ SSA_DEV u64 kc_row_fingerprint(const u64 *__restrict__ c_pks, const u8 *__restri
     return dd_fingerprint(w, c_inf[r] ? 1u : 0u, k0, k1);
 }
 
-// stats[1] = u (dd_k_scan's); n = the lanes of the slice (the grid covers them: u <= n)
+// stats[1] = u (dd_k_scan's); n = the lanes of the slice (the grid covers them: u <= n); stamps (or nullptr): the rows'
+// stamps, which get `epoch` on a hit
 __global__ void __launch_bounds__(256)
 kc_k_lookup(const u8 *__restrict__ pks, const u8 *__restrict__ pk_inf, const u32 *__restrict__ reps, u32 n,
             const unsigned long long *__restrict__ stats, u64 k0, u64 k1, const u64 *__restrict__ slots, u32 mask,
             u32 bound, const u64 *__restrict__ c_pks, const u8 *__restrict__ c_inf, u32 held, u32 *__restrict__ found,
-            u32 *__restrict__ blk_cnt) {
+            u32 *__restrict__ blk_cnt, u32 *__restrict__ stamps, u32 epoch) {
     __shared__ u32 wave_cnt[DD_BLOCK / 64];
     const u32 j = blockIdx.x * DD_BLOCK + threadIdx.x;
     const u32 u = (u32)stats[1];
@@ -86,6 +128,7 @@ kc_k_lookup(const u8 *__restrict__ pks, const u8 *__restrict__ pk_inf, const u32
         }
         found[j] = row;
         miss = row == KC_MISS;
+        if (stamps && !miss) stamps[row] = epoch;     // (SSA_KEYCACHE_EVICT_RECENT: the row's last use)
     }
     const unsigned long long misses = __ballot(miss);
     if ((threadIdx.x & 63u) == 0) wave_cnt[threadIdx.x >> 6] = (u32)__popcll(misses);
@@ -154,6 +197,102 @@ kc_k_map(const u32 *__restrict__ key_idx, const u32 *__restrict__ found, u32 n, 
     }
     const u32 f = found[j];
     lane_row[i] = (f & KC_MISS_BIT) ? base + (f & ~KC_MISS_BIT) : f;
+}
+// ---- compaction (SSA_KEYCACHE_EVICT_RECENT): see the head of this file
+
+// hist[a] += rows of [0, held) whose age is a (63: any older); hist is zeroed by the caller on the same stream
+__global__ void __launch_bounds__(256)
+kc_k_age_hist(const u32 *__restrict__ stamps, u32 held, u32 epoch, u32 *__restrict__ hist) {
+    __shared__ u32 h[KC_AGE_BINS];
+    if (threadIdx.x < KC_AGE_BINS) h[threadIdx.x] = 0;
+    __syncthreads();
+    const u32 r = blockIdx.x * DD_BLOCK + threadIdx.x;
+    if (r < held) {
+        const u32 age = epoch - stamps[r];
+        atomicAdd(&h[age < KC_AGE_BINS - 1 ? age : KC_AGE_BINS - 1], 1u);
+    }
+    __syncthreads();
+    if (threadIdx.x < KC_AGE_BINS && h[threadIdx.x]) atomicAdd(hist + threadIdx.x, h[threadIdx.x]);
+}
+
+// row r < held survives a compaction that keeps the ages 0..max_age
+SSA_DEV bool kc_survives(const u32 *__restrict__ stamps, u32 r, u32 epoch, u32 max_age) { return epoch - stamps[r] <= max_age; }
+
+// hole_cnt[b] = rows of workgroup b below `kept` that do not survive; mover_cnt[b] = its rows at or above `kept` that do
+__global__ void __launch_bounds__(256)
+kc_k_evict_count(const u32 *__restrict__ stamps, u32 held, u32 epoch, u32 max_age, u32 kept, u32 *__restrict__ hole_cnt,
+                 u32 *__restrict__ mover_cnt) {
+    __shared__ u32 wave_cnt[2][DD_BLOCK / 64];
+    const u32 r = blockIdx.x * DD_BLOCK + threadIdx.x;
+    const bool surv = r < held && kc_survives(stamps, r, epoch, max_age);
+    const unsigned long long holes = __ballot(r < kept && r < held && !surv), movers = __ballot(r >= kept && surv);
+    if ((threadIdx.x & 63u) == 0) {
+        wave_cnt[0][threadIdx.x >> 6] = (u32)__popcll(holes);
+        wave_cnt[1][threadIdx.x >> 6] = (u32)__popcll(movers);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        hole_cnt[blockIdx.x] = wave_cnt[0][0] + wave_cnt[0][1] + wave_cnt[0][2] + wave_cnt[0][3];
+        mover_cnt[blockIdx.x] = wave_cnt[1][0] + wave_cnt[1][1] + wave_cnt[1][2] + wave_cnt[1][3];
+    }
+}
+
+// holes[t] = the t-th hole, movers[t] = the t-th mover, in row order (cap = the length of both lists); remap[r] for every
+// row that is no mover: itself for a survivor below `kept`, KC_MISS for a dropped row
+__global__ void __launch_bounds__(256)
+kc_k_evict_assign(const u32 *__restrict__ stamps, u32 held, u32 epoch, u32 max_age, u32 kept,
+                  const u32 *__restrict__ hole_off, const u32 *__restrict__ mover_off, u32 cap, u32 *__restrict__ holes,
+                  u32 *__restrict__ movers, u32 *__restrict__ remap) {
+    __shared__ u32 wave_cnt[2][DD_BLOCK / 64];
+    const u32 r = blockIdx.x * DD_BLOCK + threadIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const bool in = r < held, surv = in && kc_survives(stamps, r, epoch, max_age);
+    const bool hole = in && r < kept && !surv, mover = r >= kept && surv;
+    const unsigned long long hm = __ballot(hole), mm = __ballot(mover);
+    if (lane == 0) {
+        wave_cnt[0][wave] = (u32)__popcll(hm);
+        wave_cnt[1][wave] = (u32)__popcll(mm);
+    }
+    __syncthreads();
+    if (!in) return;
+    if (hole || mover) {
+        const int w = hole ? 0 : 1;
+        u32 t = (hole ? hole_off : mover_off)[blockIdx.x] + (u32)__popcll((hole ? hm : mm) & ((1ull << lane) - 1ull));
+        for (u32 k = 0; k < wave; k++) t += wave_cnt[w][k];
+        if (t < cap) (hole ? holes : movers)[t] = r;
+    }
+    if (!mover) remap[r] = surv ? r : KC_MISS;
+}
+
+// one wave per mover t < n_move: row movers[t] (>= kept) into row holes[t] (< kept), whole; remap[movers[t]] = holes[t].
+// tab_words = the u64 words of a row's table (even: the table moves as 16-byte words); wire_words = the words of a wire
+// row (at most 16; 0 for an affine cache, whose c_wire is not read)
+__global__ void __launch_bounds__(256)
+kc_k_evict_move(const u32 *__restrict__ movers, const u32 *__restrict__ holes, u32 n_move, u32 held, u32 kept,
+                u32 tab_words, u64 *__restrict__ c_tab, u64 *__restrict__ c_pks, u8 *__restrict__ c_inf,
+                u8 *__restrict__ c_status, u32 *__restrict__ stamps, u64 *__restrict__ c_wire, u32 wire_words, u32 *__restrict__ remap) {
+    const u32 t = blockIdx.x * (DD_BLOCK / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (t >= n_move) return;
+    const u32 src = movers[t], dst = holes[t];
+    if (src >= held || src < kept || dst >= kept) return;      // (never)
+    const uint4 *from = reinterpret_cast<const uint4 *>(c_tab + (size_t)src * tab_words);
+    uint4 *to = reinterpret_cast<uint4 *>(c_tab + (size_t)dst * tab_words);
+    for (u32 k = lane; k < tab_words / 2; k += 64) to[k] = from[k];
+    if (lane < 12) c_pks[(size_t)dst * 12 + lane] = c_pks[(size_t)src * 12 + lane];
+    if (lane >= 16 && lane - 16 < wire_words)
+        c_wire[(size_t)dst * wire_words + (lane - 16)] = c_wire[(size_t)src * wire_words + (lane - 16)];
+    if (lane == 32) c_inf[dst] = c_inf[src];
+    if (lane == 33) c_status[dst] = c_status[src];
+    if (lane == 34) stamps[dst] = stamps[src];
+    if (lane == 35) remap[src] = dst;
+}
+
+// found[j] of the slice's u distinct keys through remap[]: a hit's row after the compaction (misses keep their numbers)
+__global__ void __launch_bounds__(256)
+kc_k_remap(u32 *__restrict__ found, u32 u, const u32 *__restrict__ remap, u32 held) {
+    const u32 j = blockIdx.x * DD_BLOCK + threadIdx.x;
+    if (j >= u) return;
+    const u32 f = found[j];
+    if (!(f & KC_MISS_BIT) && f < held) found[j] = remap[f];
 }
 #endif  // SSA_NO_KERNELS
 

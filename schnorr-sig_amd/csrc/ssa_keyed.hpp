@@ -126,7 +126,7 @@ ky_k_insert(const u8 *__restrict__ keyed, u32 n, u64 k0, u64 k1, u64 *__restrict
 __global__ void __launch_bounds__(256)
 ky_k_lookup(const u8 *__restrict__ keyed, const u32 *__restrict__ reps, u32 n, const unsigned long long *__restrict__ stats,
             u64 k0, u64 k1, const u64 *__restrict__ slots, u32 mask, u32 bound, const u64 *__restrict__ c_wire, u32 held,
-            u32 *__restrict__ found, u32 *__restrict__ blk_cnt) {
+            u32 *__restrict__ found, u32 *__restrict__ blk_cnt, u32 *__restrict__ stamps, u32 epoch) {
     __shared__ u32 wave_cnt[DD_BLOCK / 64];
     const u32 j = blockIdx.x * DD_BLOCK + threadIdx.x;
     const u32 u = (u32)stats[1];
@@ -157,6 +157,7 @@ ky_k_lookup(const u8 *__restrict__ keyed, const u32 *__restrict__ reps, u32 n, c
         }
         found[j] = row;
         miss = row == KC_MISS;
+        if (stamps && !miss) stamps[row] = epoch;     // (SSA_KEYCACHE_EVICT_RECENT: the row's last use)
     }
     const unsigned long long misses = __ballot(miss);
     if ((threadIdx.x & 63u) == 0) wave_cnt[threadIdx.x >> 6] = (u32)__popcll(misses);

@@ -681,6 +681,22 @@ class KeyCache {
         if (rc != 0) throw std::runtime_error(std::string("ssa_keycache_info: ") + ssa_strerror(rc));
         return {v[0], v[1], v[2], v[3]};
     }
+    // What a full cache does: Clear (the default) empties it; Recent keeps the rows used most
+    // recently.  Recent allocates the rows' stamps and the compaction's scratch, once: info().device_bytes grows here.
+    enum Eviction : uint32_t { Clear = SSA_KEYCACHE_EVICT_CLEAR, Recent = SSA_KEYCACHE_EVICT_RECENT };
+    struct EvictionInfo {
+        uint64_t policy, compactions, dropped, last_kept, last_moved, epoch;
+    };
+    void set_eviction(Eviction policy) {
+        const int rc = ssa_keycache_set_eviction(kc_, (uint32_t)policy);
+        if (rc != 0) throw std::runtime_error(std::string("ssa_keycache_set_eviction: ") + ssa_strerror(rc));
+    }
+    EvictionInfo eviction_info() const {
+        uint64_t v[8] = {};
+        const int rc = ssa_keycache_eviction_info(kc_, v);
+        if (rc != 0) throw std::runtime_error(std::string("ssa_keycache_eviction_info: ") + ssa_strerror(rc));
+        return {v[0], v[1], v[2], v[3], v[4], v[5]};
+    }
     // the exact check of every held row against its stored key bytes; deep: also [q]P per key; repair: failing rows are
     // rebuilt in place from their stored bytes and checked again (ok: clean afterwards)
     KeyCheck selfcheck(bool deep = false, bool repair = false) {
