@@ -877,6 +877,57 @@ int ssa_msm_combine_device(ssa_ctx *ctx, const uint64_t *d_parts24, size_t k, ui
 /* the same from host memory; returns the status */
 int ssa_msm_combine(ssa_ctx *ctx, const uint64_t *parts24, size_t k);
 
+/* ---- half-aggregation of signatures -------------------------------------------------
+ * "Non-interactive half-aggregation of EdDSA and variants of Schnorr signatures" (Chalkias, Garillot, Kondi,
+ * Nikolaenko, CT-RSA 2021), which src/batch.rs:1-3 announces and does not ship: n signatures (R_i, e_i) become the n
+ * R's and ONE scalar, 49 n + 32 bytes instead of 81 n,
+ *     aggregate = R_0 || ... || R_(n-1) || e_agg,      e_agg = sum a_i e_i mod q   (32 bytes, little-endian, canonical)
+ * where R_i is the first 49 bytes of signature i verbatim and the coefficients a_i are hashed out of a transcript that
+ * binds every R_i (its flag byte too), key, message and the ORDER of the lanes (H = RescueHash::hash_field):
+ *     d_i = the 4-felt digest of hash_message(R_i.x, P_i, m_i), before any reduction mod q
+ *     leaf_i = H(d_i || flag byte of R_i || 0xA1);   node = H(left || right), an odd last node of a level moves up
+ *     unchanged, until one node, top, is left;   root = H(top || n || 0xA2)
+ *     a_i = the first 16 bytes of Digest::to_bytes(H(root || i || 0xA3)), little-endian, masked to 126 bits, 0 -> 1
+ * The verifier recomputes the a_i and accepts iff
+ *     sum a_i R_i - sum (a_i h_i mod q) P_i == [e_agg] G        AS POINTS (both coordinates; no x-only comparison)
+ * -- the equation of ssa_verify_batch_msm with hash-derived coefficients, through the same bucket MSM.  Semantics are
+ * those of verify_batch: the flag byte of R_i is honoured, pk_inf marks identity keys, and there is NO subgroup check
+ * (keys or R's with a small-order component: the caveat of ssa_verify_batch_screened applies; take key statuses from a
+ * key set or a key cache where it matters).  An aggregate verifies only if every input verified with
+ * SSA_FLAG_SIG_FLAG_BYTE; a forgery succeeds with probability about 2^-126 per transcript tried.
+ * n above the context's MSM slice (2^23, SSA_MSM_SLICE) is SSA_ERR_ARG: no slicing, no multi-GPU form.
+ *
+ * ssa_aggregate_many: agg_out receives SSA_AGGREGATE_LENGTH(n) bytes.  flags: 0 or SSA_AGG_CHECK (any other bit:
+ * SSA_ERR_ARG).  With SSA_AGG_CHECK the statuses of ssa_verify_batch_screened are computed first: if any is nonzero,
+ * agg_out is zeroed, status_out names the lanes and the smallest nonzero status is returned.  Without it only inputs
+ * the verifier would call malformed are refused (non-canonical limbs, e_i >= q, a key off the curve, an R that does not
+ * decode): status_out[i] is then 0 or 3, agg_out is zeroed and SSA_MALFORMED is returned.  status_out (n bytes) and
+ * n_fail_out may be NULL.  n == 0: 32 zero bytes, SSA_OK.  The _device form takes device pointers (d_n_fail_out too) and
+ * SYNCHRONISES the context's stream, since the status it returns is read from the device.
+ *
+ * ssa_verify_aggregate returns SSA_OK, SSA_INVALID_SIGNATURE (the equation fails) or SSA_MALFORMED (a non-canonical
+ * limb, an undecodable R_i or flag byte, a key off the curve, e_agg >= q).  n == 0: the 32 bytes must be zero.  The
+ * _device form writes the status to *d_verdict_out and only enqueues on the context's stream, like
+ * ssa_verify_batch_msm_device. */
+#define SSA_AGGREGATE_LENGTH(n) ((size_t)49 * (size_t)(n) + 32)
+#define SSA_AGG_CHECK 1u
+int ssa_aggregate_many(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_inf,
+                       const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len, size_t n,
+                       uint32_t flags, uint8_t *agg_out, uint8_t *status_out, uint64_t *n_fail_out);
+int ssa_aggregate_many_device(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_pk_inf,
+                              const uint8_t *d_msgs, const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len,
+                              size_t n, uint32_t flags, uint8_t *d_agg_out, uint8_t *d_status_out,
+                              uint64_t *d_n_fail_out);
+int ssa_verify_aggregate(ssa_ctx *ctx, const uint8_t *agg, const uint8_t *pks, const uint8_t *pk_inf,
+                         const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len, size_t n);
+int ssa_verify_aggregate_device(ssa_ctx *ctx, const uint8_t *d_agg, const uint8_t *d_pks, const uint8_t *d_pk_inf,
+                                const uint8_t *d_msgs, const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len,
+                                size_t n, uint32_t *d_verdict_out);
+/* tests: the coefficients a_i of an aggregate's R's (rs49: n x 49 bytes, host), keys and messages -> n x 16 bytes */
+int ssa_debug_aggregate_coeffs(ssa_ctx *ctx, const uint8_t *rs49, const uint8_t *pks, const uint8_t *pk_inf,
+                               const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len, size_t n,
+                               uint8_t *coeffs16_out);
+
 /* ---- ABI version -------------------------------------------------------------------------------------------
  * Bumped whenever an exported signature changes (round 2 inserted pk_inf into the batch entry points under the same
  * symbol names: a shim built against the older header would still link and pass msgs as pk_inf).  A binding checks

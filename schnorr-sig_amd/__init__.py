@@ -47,6 +47,7 @@ FLAG_FORCE_COOP = 4   # low-latency kernel (one wave per signature) whatever the
 FLAG_SIG_FLAG_BYTE = 8  # verify_batch's semantics for byte 48 of the signature (src/batch.rs:104)
 FLAG_SIGN_CT = 16       # constant-time signing (the reference's `&BASEPOINT_TABLE * r`, src/signature.rs:67,116)
 FLAG_SIGN_KEYED = 32    # 130-byte KeyedSignature records out (src/signature.rs:237-245)
+AGG_CHECK = 1            # SSA_AGG_CHECK: ssa_aggregate_many screens the signatures first
 FLAG_DERIVE_PUBLIC = 64  # xprv -> xpub children (ExtendedPrivateKey::derive_public, src/derivation.rs:160-174)
 # src/derivation.rs, src/constants.rs
 CHAIN_CODE_LENGTH = 32
@@ -254,6 +255,11 @@ def _load():
         "ssa_debug_pin_rng": (i32, [vp, vp]),
         "ssa_debug_draw_scalars": (i32, [vp, vp, sz, vp]),
         "ssa_debug_poison_workspaces": (i32, [vp, i32]),
+        "ssa_aggregate_many": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz, u32, vp, vp, u64p]),
+        "ssa_aggregate_many_device": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz, u32, vp, vp, vp]),
+        "ssa_verify_aggregate": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz]),
+        "ssa_verify_aggregate_device": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz, vp]),
+        "ssa_debug_aggregate_coeffs": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)      # AttributeError here == ABI symbol missing: fail loudly
@@ -610,6 +616,61 @@ class Engine:
         """uint64[k, 24] records (host) -> status of the whole batch"""
         parts = np.ascontiguousarray(parts, dtype=np.uint64).reshape(-1, MSM_PARTIAL_WORDS)
         return _check(_lib.ssa_msm_combine(self._ctx, _ptr(parts), parts.shape[0]), "ssa_msm_combine")
+
+    # ---- half-aggregation (include/schnorr_sig_amd.h, DESIGN.md section 20) ----
+    def _agg_batch(self, lead, width, pks, msgs, offsets, pk_inf):
+        """(n, the arguments from the leading array to n, the arrays they point into): `lead` holds `width` bytes per
+        lane, plus 32 bytes of e_agg when it is an aggregate (width 49 and a length that says so)"""
+        pks = _np_u8(pks, 96)
+        n = pks.shape[0]
+        lead = _np_u8(lead).reshape(-1)
+        if lead.size not in (width * n, width * n + 32 if width == 49 else -1):
+            raise MalformedInput("We should have the same number of signatures than public keys")
+        m, off, stride, mlen = self._msg_args(msgs, offsets, n) if n else (None, None, 0, 0)
+        inf = _np_u8(pk_inf) if pk_inf is not None else None
+        return n, (_ptr(lead), _ptr(pks) if n else None, _ptr(inf), _ptr(m), _ptr(off), stride, mlen, n), (lead, pks, m, off, inf)
+
+    def aggregate(self, sigs, pks, msgs, offsets=None, pk_inf=None, check=False):
+        """n signatures -> (status, aggregate uint8[49 n + 32], per-lane status uint8[n], n_fail): the n R's and
+        e_agg = sum a_i e_i mod q.  check: screen the signatures first (SSA_AGG_CHECK).  A nonzero status (the smallest
+        of the lanes') comes with an all-zero aggregate."""
+        n, batch, keep = self._agg_batch(sigs, 81, pks, msgs, offsets, pk_inf)
+        agg = np.full(49 * n + 32, 255, dtype=np.uint8)
+        status = np.full(n, 255, dtype=np.uint8)
+        nfail = C.c_uint64(0)
+        st = _check(_lib.ssa_aggregate_many(self._ctx, *batch, AGG_CHECK if check else 0, _ptr(agg),
+                                            _ptr(status) if n else None, C.byref(nfail)), "ssa_aggregate_many")
+        return st, agg, status, int(nfail.value)
+
+    def aggregate_device(self, d_sigs, d_pks, d_msgs, n, msg_len, d_agg, d_status=0, d_nfail=0, msg_stride=None,
+                         d_offsets=0, d_pk_inf=0, check=False):
+        """device form (synchronises the stream: the status is read from the device) -> status"""
+        return _check(_lib.ssa_aggregate_many_device(
+            self._ctx, d_sigs, d_pks, *self._dev_batch(d_pk_inf, d_msgs, d_offsets, msg_stride, msg_len, n),
+            AGG_CHECK if check else 0, d_agg, d_status or None, d_nfail or None), "ssa_aggregate_many_device")
+
+    def verify_aggregate(self, agg, pks, msgs, offsets=None, pk_inf=None):
+        """an aggregate (49 n + 32 bytes), the keys and the messages in the aggregator's order -> status"""
+        n, batch, keep = self._agg_batch(agg, 49, pks, msgs, offsets, pk_inf)
+        if keep[0].size != 49 * n + 32:
+            raise MalformedInput("an aggregate of n signatures is 49 n + 32 bytes")
+        return _check(_lib.ssa_verify_aggregate(self._ctx, *batch), "ssa_verify_aggregate")
+
+    def verify_aggregate_device(self, d_agg, d_pks, d_msgs, n, msg_len, d_verdict, msg_stride=None, d_offsets=0,
+                                d_pk_inf=0):
+        """device form: only enqueues; the status lands in the uint32 at d_verdict"""
+        _check(_lib.ssa_verify_aggregate_device(
+            self._ctx, d_agg, d_pks, *self._dev_batch(d_pk_inf, d_msgs, d_offsets, msg_stride, msg_len, n), d_verdict),
+            "ssa_verify_aggregate_device")
+
+    def aggregate_coeffs(self, rs49, pks, msgs, offsets=None, pk_inf=None):
+        """tests: the transcript's coefficients a_i of n R's (n x 49 bytes), keys and messages -> uint8[n, 16]"""
+        n, batch, keep = self._agg_batch(rs49, 49, pks, msgs, offsets, pk_inf)
+        if keep[0].size != 49 * n:
+            raise MalformedInput("n R's are 49 n bytes")
+        out = np.zeros((n, 16), dtype=np.uint8)
+        _check(_lib.ssa_debug_aggregate_coeffs(self._ctx, *batch, _ptr(out) if n else None), "ssa_debug_aggregate_coeffs")
+        return out
 
     def debug_chacha20(self, key32, nonce12, counter0, n_blocks):
         """keystream blocks of the generator the MSM coefficients come from (RFC 8439 block function)"""
@@ -1537,6 +1598,66 @@ class KeyedSignature:
 
     def __eq__(self, o):
         return isinstance(o, KeyedSignature) and o.public_key == self.public_key and o.signature == self.signature
+
+
+class AggregateSignature:
+    """The half-aggregate of n signatures: their R's, 49 bytes each, and e_agg = sum a_i e_i mod q
+    -- 49 n + 32 bytes for 81 n.  The order of the lanes is part of it."""
+
+    def __init__(self, agg_bytes):
+        b = bytes(agg_bytes)
+        if len(b) < 32 or (len(b) - 32) % 49:
+            raise ValueError("AggregateSignature needs 49 n + 32 bytes")
+        self.bytes = b
+
+    def __len__(self):
+        return (len(self.bytes) - 32) // 49
+
+    @classmethod
+    def aggregate(cls, signatures, public_keys, messages, check=True, engine=None):
+        """Engine.aggregate over (signature, public key, message) objects.  check: every signature is verified first
+        (verify_batch semantics) and a slice with a bad one raises the SignatureError / MalformedInput of verify_batch."""
+        packed = _pack_triples(signatures, public_keys, messages)
+        if packed is None:
+            return cls(bytes(32))
+        sigs, pks, inf, flat, off = packed
+        st, agg, _, _ = (engine or default_engine()).aggregate(sigs, pks, flat, offsets=off, pk_inf=inf, check=check)
+        if st == MALFORMED:
+            raise MalformedInput("undecodable signature in batch (the reference panics here)")
+        if st != OK:
+            raise SignatureError(SignatureError.InvalidSignature)
+        return cls(agg.tobytes())
+
+    def verify(self, public_keys, messages, engine=None):
+        """Ok -> None; otherwise raises SignatureError (the equation fails) or MalformedInput"""
+        if len(public_keys) != len(self) or len(messages) != len(self):
+            raise MalformedInput("We should have the same number of messages than public keys")
+        eng = engine or default_engine()
+        if len(self) == 0:
+            st = eng.verify_aggregate(np.frombuffer(self.bytes, np.uint8), np.zeros((0, 96), np.uint8), None)
+        else:
+            pks = np.frombuffer(b"".join(p.affine for p in public_keys), np.uint8)
+            inf = np.array([1 if p.is_identity else 0 for p in public_keys], np.uint8)
+            flat, off = pack_messages(messages)
+            st = eng.verify_aggregate(np.frombuffer(self.bytes, np.uint8), pks, flat, offsets=off, pk_inf=inf)
+        if st == OK:
+            return None
+        if st == MALFORMED:
+            raise MalformedInput("undecodable aggregate (non-canonical limb or scalar, R or key off the curve)")
+        raise SignatureError(SignatureError.InvalidSignature)
+
+    def to_bytes(self):
+        return self.bytes
+
+    @classmethod
+    def from_bytes(cls, b):  # None when the length is not 49 n + 32 or e_agg is not canonical
+        b = bytes(b)
+        if len(b) < 32 or (len(b) - 32) % 49 or int.from_bytes(b[-32:], "little") >= Q:
+            return None
+        return cls(b)
+
+    def __eq__(self, o):
+        return isinstance(o, AggregateSignature) and o.bytes == self.bytes
 
 
 class KeyPair:

@@ -5,6 +5,7 @@
 #include "ssa_ctx.hpp"
 #include "ssa_keycache.hpp"
 #include "ssa_keyed.hpp"
+#include "ssa_aggregate.hpp"
 
 #include <sys/random.h>
 
@@ -1880,6 +1881,209 @@ extern "C" int ssa_multi_verify_batch_msm(ssa_multi *m, const uint8_t *sigs, con
     for (size_t r = 0; r < world; r++)
         if (rcs[r] != 0) return rcs[r];
     return ssa_msm_combine(m->ctxs[0], parts.data(), world);
+}
+
+// ------------------------------------------------------------------ half-aggregation (ssa_aggregate.hpp)
+// ctx->ag_misc: the transcript's root, the MSM's record, e_agg, the rejection counter of the unchecked form
+constexpr size_t AG_ROOT = 0, AG_REC = 64, AG_E = 256, AG_MISC_BYTES = 512;
+static inline u8 *ag_misc(ssa_ctx *ctx, size_t off) { return (u8 *)ctx->ag_misc.p + off; }
+
+// The coefficients a_i of n lanes whose R's stand at stride 81 in b.sigs into ctx->ag_coeffs (n x 16 bytes), on
+// ctx->stream.  with_h: the same launch of ssa_k_hash leaves the challenge scalars mod q in ctx->ws_h.
+static int agg_coefficients(ssa_ctx *ctx, const DevBatch &b, size_t n, bool with_h) {
+    const size_t g1 = (n + AG_TREE_SPAN - 1) / AG_TREE_SPAN;
+    if (ctx->ag_dig.reserve(n * 32) || ctx->ag_nodes.reserve(n * 32) || ctx->ag_nodes2.reserve(g1 * 32) ||
+        ctx->ag_coeffs.reserve(n * 16) || ctx->ag_misc.reserve(AG_MISC_BYTES) || (with_h && ctx->ws_h.reserve(n * 32)))
+        return SSA_ERR_HIP;
+    int rc = timed_launch(ctx, "ssa_k_hash", [&] {
+        hipLaunchKernelGGL(ssa_k_hash, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, ctx->d_params, b.sigs, b.pks,
+                           b.msgs, n, with_h ? (u64 *)ctx->ws_h.p : (u64 *)nullptr, (u8 *)ctx->ag_dig.p,
+                           (const u32 *)nullptr, 0u);
+    });
+    if (rc) return rc;
+    rc = timed_launch(ctx, "ag_k_leaf", [&] {
+        hipLaunchKernelGGL(ag_k_leaf, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, ctx->d_params,
+                           (const u64 *)ctx->ag_dig.p, b.sigs, n, (u64 *)ctx->ag_nodes.p);
+    });
+    if (rc) return rc;
+    // passes of AG_TREE_LEVELS levels between the two node buffers; the pass of one workgroup also hashes the root
+    rc = timed_launch(ctx, "ag_k_tree", [&] {
+        const u64 *in = (const u64 *)ctx->ag_nodes.p;
+        u64 *ping = (u64 *)ctx->ag_nodes2.p, *pong = (u64 *)ctx->ag_nodes.p;
+        size_t count = n;
+        for (;;) {
+            const size_t g = (count + AG_TREE_SPAN - 1) / AG_TREE_SPAN;
+            const bool top = g == 1;
+            u64 *out = top ? (u64 *)ag_misc(ctx, AG_ROOT) : ping;
+            hipLaunchKernelGGL(ag_k_tree, dim3((unsigned)g), dim3(256), 0, ctx->stream, ctx->d_params, in, (u32)count,
+                               (u64)n, top ? 1u : 0u, out);
+            if (top) break;
+            in = out;
+            std::swap(ping, pong);
+            count = g;
+        }
+    });
+    if (rc) return rc;
+    return timed_launch(ctx, "ag_k_coeff", [&] {
+        hipLaunchKernelGGL(ag_k_coeff, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, ctx->d_params,
+                           (const u64 *)ag_misc(ctx, AG_ROOT), n, (u64 *)ctx->ag_coeffs.p);
+    });
+}
+
+static int agg_check_args(const ssa_ctx *ctx, const MsgView &mv, size_t n) {
+    if (int rc = check_msgs(mv, n)) return rc;
+    return n > ctx->knobs.msm_slice ? SSA_ERR_ARG : 0;      // one MSM slice: DESIGN.md section 20, out of scope
+}
+
+// Synchronises the stream: the status it returns is read from the device.
+extern "C" int ssa_aggregate_many_device(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_pk_inf,
+                                         const uint8_t *d_msgs, const uint64_t *d_msg_off, size_t msg_stride,
+                                         size_t msg_len, size_t n, uint32_t flags, uint8_t *d_agg_out,
+                                         uint8_t *d_status_out, uint64_t *d_n_fail_out) {
+    const DevBatch b{d_sigs, d_pks, d_pk_inf, {d_msgs, d_msg_off, msg_stride, msg_len}};
+    if (!ctx || !d_agg_out || (flags & ~SSA_AGG_CHECK) || (n && (!d_sigs || !d_pks))) return SSA_ERR_ARG;
+    if (int rc = agg_check_args(ctx, b.msgs, n)) return rc;
+    unsigned long long *d_fail;
+    if (int rc = reset_fail_counter(ctx, d_n_fail_out, &d_fail)) return rc;
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(d_agg_out, 0, 32, ctx->stream));
+        return SSA_OK;
+    }
+    if (!d_status_out && ctx->ag_status.reserve(n + 16)) return SSA_ERR_HIP;
+    u8 *d_status = d_status_out ? d_status_out : (u8 *)ctx->ag_status.p;
+    const bool screened = (flags & SSA_AGG_CHECK) != 0;
+    if (screened)
+        if (int rc = ssa_verify_batch_screened_device(ctx, d_sigs, d_pks, d_pk_inf, d_msgs, d_msg_off, msg_stride, msg_len, n,
+                                                      nullptr, 0, d_status, (uint64_t *)d_fail))
+            return rc;
+    if (int rc = agg_coefficients(ctx, b, n, false)) return rc;
+    const unsigned n_blocks = grid_for(n, 256);
+    if (ctx->ag_partials.reserve((size_t)n_blocks * 32)) return SSA_ERR_HIP;
+    int rc = timed_launch(ctx, "ag_k_fold", [&] {
+        hipLaunchKernelGGL(ag_k_fold, dim3(n_blocks), dim3(256), 0, ctx->stream, d_sigs, d_pks, d_pk_inf,
+                           (const u64 *)ctx->ag_coeffs.p, n, (u64 *)ctx->ag_partials.p, screened ? (u8 *)nullptr : d_status,
+                           d_fail);
+        hipLaunchKernelGGL(ag_k_fold_finish, dim3(1), dim3(256), 0, ctx->stream, (const u64 *)ctx->ag_partials.p, n_blocks,
+                           ag_misc(ctx, AG_E));
+    });
+    if (rc) return rc;
+    unsigned long long nf = 0;
+    HIP_TRY(hipMemcpyAsync(&nf, d_fail, sizeof nf, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (nf) {     // refused: no aggregate, the smallest nonzero status
+        HIP_TRY(hipMemsetAsync(d_agg_out, 0, SSA_AGGREGATE_LENGTH(n), ctx->stream));
+        int st = SSA_MALFORMED;
+        if (screened) {
+            std::vector<uint8_t> h(n);
+            HIP_TRY(hipMemcpyAsync(h.data(), d_status, n, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(hipStreamSynchronize(ctx->stream));
+            for (uint8_t s : h)
+                if (s && (int)s < st) st = s;
+        }
+        return st;
+    }
+    hipLaunchKernelGGL(ag_k_pack, dim3(grid_for((n * 49 + 3) / 4, 256)), dim3(256), 0, ctx->stream, d_sigs, n, d_agg_out);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(d_agg_out + 49 * n, ag_misc(ctx, AG_E), 32, hipMemcpyDeviceToDevice, ctx->stream));
+    return SSA_OK;
+}
+
+extern "C" int ssa_aggregate_many(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_inf,
+                                  const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len, size_t n,
+                                  uint32_t flags, uint8_t *agg_out, uint8_t *status_out, uint64_t *n_fail_out) {
+    if (!ctx || !agg_out || (flags & ~SSA_AGG_CHECK) || (n && (!sigs || !pks))) return SSA_ERR_ARG;
+    if (int rc = agg_check_args(ctx, {msgs, msg_off, msg_stride, msg_len}, n)) return rc;
+    if (int rc = check_host_offsets(msg_off, n)) return rc;
+    if (n_fail_out) *n_fail_out = 0;
+    if (n == 0) {
+        std::memset(agg_out, 0, 32);
+        return SSA_OK;
+    }
+    HostCall hc(ctx);
+    const u8 *d_sigs = hc.in(ctx->st_sigs, sigs, n * 81), *d_pks = hc.in(ctx->st_pks, pks, n * 96);
+    const u8 *d_inf = pk_inf ? hc.in(ctx->st_inf, pk_inf, n) : nullptr;
+    const MsgView mv = hc.msgs(msgs, msg_off, msg_stride, msg_len, n);
+    u8 *d_agg = hc.out(ctx->st_aux, agg_out, SSA_AGGREGATE_LENGTH(n), 16);
+    u8 *d_status = hc.out(ctx->st_status, status_out, n, 16);
+    unsigned long long nf = 0;
+    hc.copy_back(&nf, ctx->ws_fail.p, sizeof nf);
+    int st = SSA_OK;       // a refusal is a result, not an error: the zeroed aggregate and the statuses still come back
+    const int rc = hc.finish([&] {
+        const int r = ssa_aggregate_many_device(ctx, d_sigs, d_pks, d_inf, mv.msgs, mv.off, msg_stride, msg_len, n, flags,
+                                                d_agg, d_status, nullptr);
+        if (r > 0) st = r;
+        return r > 0 ? 0 : r;
+    });
+    if (rc) return rc;
+    if (n_fail_out) *n_fail_out = nf;
+    return st;
+}
+
+extern "C" int ssa_verify_aggregate_device(ssa_ctx *ctx, const uint8_t *d_agg, const uint8_t *d_pks, const uint8_t *d_pk_inf,
+                                           const uint8_t *d_msgs, const uint64_t *d_msg_off, size_t msg_stride,
+                                           size_t msg_len, size_t n, uint32_t *d_verdict_out) {
+    const MsgView mv{d_msgs, d_msg_off, msg_stride, msg_len};
+    if (!ctx || !d_agg || !d_verdict_out || (n && !d_pks)) return SSA_ERR_ARG;
+    if (int rc = agg_check_args(ctx, mv, n)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (n == 0) {
+        hipLaunchKernelGGL(ag_k_empty, dim3(1), dim3(64), 0, ctx->stream, d_agg, d_verdict_out);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
+    if (ctx->ag_sigs.reserve(n * 81 + 16) || ctx->ag_misc.reserve(AG_MISC_BYTES)) return SSA_ERR_HIP;
+    hipLaunchKernelGGL(ag_k_expand, dim3(grid_for((n * 81 + 3) / 4, 256)), dim3(256), 0, ctx->stream, d_agg, n,
+                       (u8 *)ctx->ag_sigs.p);
+    HIP_TRY(hipGetLastError());
+    // the MSM of ssa_verify_batch_msm over (R_i, e = 0) with the transcript's coefficients, reduced to its record
+    const DevBatch b{(const u8 *)ctx->ag_sigs.p, d_pks, d_pk_inf, mv};
+    if (int rc = agg_coefficients(ctx, b, n, true)) return rc;
+    if (int rc = ssa_internal_msm_record(ctx, b, n, (const u8 *)ctx->ag_coeffs.p, 16, (const uint64_t *)ctx->ws_h.p,
+                                         (uint64_t *)ag_misc(ctx, AG_REC)))
+        return rc;
+    return timed_launch(ctx, "ag_k_finish", [&] {
+        hipLaunchKernelGGL(ag_k_finish, dim3(1), dim3(64), 0, ctx->stream, (const u64 *)ag_misc(ctx, AG_REC), d_agg + 49 * n,
+                           (const u64 *)ctx->d_gtab, d_verdict_out);
+    });
+}
+
+extern "C" int ssa_verify_aggregate(ssa_ctx *ctx, const uint8_t *agg, const uint8_t *pks, const uint8_t *pk_inf,
+                                    const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len,
+                                    size_t n) {
+    if (!ctx || !agg || (n && !pks)) return SSA_ERR_ARG;
+    if (int rc = agg_check_args(ctx, {msgs, msg_off, msg_stride, msg_len}, n)) return rc;
+    if (int rc = check_host_offsets(msg_off, n)) return rc;
+    HostCall hc(ctx);
+    const u8 *d_agg = hc.in(ctx->st_sigs, agg, SSA_AGGREGATE_LENGTH(n)), *d_pks = hc.in(ctx->st_pks, pks, n * 96);
+    const u8 *d_inf = pk_inf ? hc.in(ctx->st_inf, pk_inf, n) : nullptr;
+    const MsgView mv = hc.msgs(msgs, msg_off, msg_stride, msg_len, n);
+    uint32_t v = SSA_MALFORMED, *d_verdict = (uint32_t *)((char *)ctx->ws_fail.p + 32);
+    hc.copy_back(&v, d_verdict, sizeof v);
+    const int rc = hc.finish([&] {
+        return ssa_verify_aggregate_device(ctx, d_agg, d_pks, d_inf, mv.msgs, mv.off, msg_stride, msg_len, n, d_verdict);
+    });
+    return rc ? rc : (int)v;
+}
+
+// tests: the coefficients a_i of an aggregate's R's (n x 49 bytes), keys and messages -> n x 16 bytes
+extern "C" int ssa_debug_aggregate_coeffs(ssa_ctx *ctx, const uint8_t *rs49, const uint8_t *pks, const uint8_t *pk_inf,
+                                          const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len,
+                                          size_t n, uint8_t *coeffs16_out) {
+    (void)pk_inf;         // (the transcript reads the key bytes, not the flag)
+    if (!ctx || (n && (!rs49 || !pks || !coeffs16_out))) return SSA_ERR_ARG;
+    if (int rc = agg_check_args(ctx, {msgs, msg_off, msg_stride, msg_len}, n)) return rc;
+    if (int rc = check_host_offsets(msg_off, n)) return rc;
+    if (n == 0) return 0;
+    HostCall hc(ctx);
+    const u8 *d_rs = hc.in(ctx->st_sigs, rs49, n * 49), *d_pks = hc.in(ctx->st_pks, pks, n * 96);
+    const MsgView mv = hc.msgs(msgs, msg_off, msg_stride, msg_len, n);
+    u8 *d_sigs = hc.out(ctx->ag_sigs, nullptr, n * 81, 16);
+    (void)hc.out(ctx->ag_coeffs, coeffs16_out, n * 16);
+    return hc.finish([&] {
+        hipLaunchKernelGGL(ag_k_expand, dim3(grid_for((n * 81 + 3) / 4, 256)), dim3(256), 0, ctx->stream, d_rs, n, d_sigs);
+        HIP_TRY(hipGetLastError());
+        return agg_coefficients(ctx, {d_sigs, d_pks, nullptr, mv}, n, false);
+    });
 }
 
 // ------------------------------------------------------------------ probes

@@ -175,6 +175,10 @@ struct CtxKnobs {
     /* device-drawn scalars (ssa_rng.hpp): the call's 44-byte seed and one slice of drawn scalars (both zeroed on the \
        stream after each call) */ \
     X(rng_seed) X(rng_scratch) \
+    /* half-aggregation (ssa_aggregate.hpp): the aggregate's R's at stride 81, the raw challenge \
+       digests, the tree's nodes (two buffers, passes alternate), the coefficients a_i, the fold's partial sums, a status \
+       byte per lane, and one small block: root, MSM record, e_agg, rejection counter, verdict */ \
+    X(ag_sigs) X(ag_dig) X(ag_nodes) X(ag_nodes2) X(ag_coeffs) X(ag_partials) X(ag_status) X(ag_misc) \
     /* the end game of ssa_k_verify, per tail group: finished pieces; parked accumulators + status (152 B per lane) */ \
     X(tail_done) X(tail_park)
 
@@ -755,6 +759,12 @@ static int status_host_one(ssa_ctx *ctx, const HostBatch &b, size_t n, const uin
 
 // defined in ssa_api.hip: hash_message + Scalar::from_bits_vartime for n signatures into ctx->ws_h
 int ssa_internal_hash_scalars(ssa_ctx *ctx, const DevBatch &b, size_t n);
+
+// defined in ssa_msm.hip, for ssa_verify_aggregate (ssa_api.hip): ONE slice (n <= ctx->knobs.msm_slice) of the MSM form
+// reduced to its 24-word record on ctx->stream -- the left-hand point in canonical form, sum s_i e_i, the malformed flag.
+// d_h: the slice's challenge scalars if they exist (batches of at most ctx->knobs.msm_small_max lanes hash for themselves)
+int ssa_internal_msm_record(ssa_ctx *ctx, const DevBatch &b, size_t n, const uint8_t *d_coeffs, uint32_t coeff_bytes,
+                            const uint64_t *d_h, uint64_t *d_record_out);
 
 // defined in ssa_api.hip: ssa_k_verify over n lanes of b (its messages unused) whose challenge scalars are already in
 // d_h (the per-lane workspace reserved for one slice of lanes); *d_fail is added to

@@ -1588,6 +1588,12 @@ static int msm_run_one(ssa_ctx *ctx, const DevBatch &b, size_t n, const uint8_t 
     });
 }
 
+int ssa_internal_msm_record(ssa_ctx *ctx, const DevBatch &b, size_t n, const uint8_t *d_coeffs, uint32_t coeff_bytes,
+                            const uint64_t *d_h, uint64_t *d_record_out) {
+    if (!d_coeffs || !d_record_out || n > ctx->knobs.msm_slice) return SSA_ERR_ARG;
+    return msm_run_one(ctx, b, n, d_coeffs, coeff_bytes, nullptr, (u64 *)d_record_out, (const u64 *)d_h);
+}
+
 // A batch of any size (n <= SSA_MAX_BATCH) in bounded memory: more than ctx->knobs.msm_slice signatures run slice after slice,
 // every slice reduced to its 24-word record exactly as a shard of a multi-GPU batch is (src/batch.rs:98-129: one point
 // and one scalar per part), and the records are added up by the combination kernel -- one point addition per slice.

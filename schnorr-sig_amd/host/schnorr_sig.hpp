@@ -621,6 +621,54 @@ inline std::vector<uint8_t> verify_batch_statuses(Context &cx, const std::vector
     });
 }
 
+// The half-aggregate of n signatures: their R's, 49 bytes each, and e_agg = sum a_i e_i mod q with
+// coefficients hashed out of every R, key, message and the order of the lanes -- 49 n + 32 bytes for 81 n.  verify_batch
+// semantics: the flag byte of R is honoured, there is no subgroup check.
+struct AggregateSignature {
+    std::vector<uint8_t> bytes;                 // SSA_AGGREGATE_LENGTH(n)
+    size_t size() const { return (bytes.size() - 32) / 49; }
+    // check: every signature is verified first (SSA_AGG_CHECK) and a slice with a bad one yields its error instead of an
+    // aggregate; without it only inputs the verifier would call malformed are refused (Panic)
+    static std::optional<AggregateSignature> aggregate(Context &cx, const std::vector<Signature> &signatures,
+                                                       const std::vector<PublicKey> &public_keys,
+                                                       const std::vector<std::pair<const uint8_t *, size_t>> &messages,
+                                                       bool check = true) {
+        const PackedTriples t = pack_triples(signatures, public_keys, messages);
+        const size_t n = signatures.size();
+        AggregateSignature a;
+        a.bytes.assign(SSA_AGGREGATE_LENGTH(n), 0);
+        const int rc = ssa_aggregate_many(cx.get(), t.sigs.data(), t.pks.data(), t.inf.data(), t.flat.data(), t.off.data(), 0,
+                                          0, n, check ? SSA_AGG_CHECK : 0u, a.bytes.data(), nullptr, nullptr);
+        if (rc < 0) throw std::runtime_error(std::string("ssa_aggregate_many: ") + ssa_strerror(rc));
+        if (rc == SSA_MALFORMED) throw Panic("undecodable signature in batch (the reference panics here)");
+        if (rc != SSA_OK) return std::nullopt;
+        return a;
+    }
+    Result verify(Context &cx, const std::vector<PublicKey> &public_keys,
+                  const std::vector<std::pair<const uint8_t *, size_t>> &messages) const {
+        if (public_keys.size() != size() || messages.size() != size())
+            throw Panic("We should have the same number of messages than public keys");
+        const PackedTriples t = pack_triples(std::vector<Signature>(size()), public_keys, messages);
+        return status_to_result(ssa_verify_aggregate(cx.get(), bytes.data(), t.pks.data(), t.inf.data(), t.flat.data(),
+                                                     t.off.data(), 0, 0, size()));
+    }
+    const std::vector<uint8_t> &to_bytes() const { return bytes; }
+    // nullopt when the length is not 49 n + 32 or e_agg is not canonical
+    static std::optional<AggregateSignature> from_bytes(const std::vector<uint8_t> &b) {
+        static const uint64_t Q[4] = {0xd443623eaed4accfULL, 0x327aa72330157722ULL, 0x563fbf0f990a37b5ULL, 0x7af2599b3b3f22d0ULL};
+        if (b.size() < 32 || (b.size() - 32) % 49) return std::nullopt;
+        for (int k = 3; k >= 0; k--) {
+            uint64_t w = 0;
+            for (int j = 7; j >= 0; j--) w = (w << 8) | b[b.size() - 32 + 8 * k + j];
+            if (w < Q[k]) break;
+            if (w > Q[k] || k == 0) return std::nullopt;
+        }
+        AggregateSignature a;
+        a.bytes = b;
+        return a;
+    }
+};
+
 // Signature::verify (src/signature.rs:181-205) over a slice of signatures in which public keys repeat: one status per
 // signature (0 Ok, 1 InvalidPublicKey, 2 InvalidSignature, 3 malformed: the reference would panic), the same vector as n
 // single calls, with each DISTINCT key's subgroup check and table run once on the GPU.
