@@ -1086,18 +1086,27 @@ static int dedup_fingerprint_key(ssa_ctx *ctx) {
     return 0;
 }
 
+// the words of a key's table of sixteen multiples
+constexpr size_t TAB_WORDS = (size_t)(PTAB_ENTRIES * PTAB_ENTRY_U64), TAB_BYTES = TAB_WORDS * sizeof(u64);
+
+// Where the keys of a slice are, and with that what identifies a key (ssa_dedup.hpp): 96-byte affine keys with their
+// optional pk_inf bytes, or (keyed non-null; the other two unused) the 49 compressed bytes in front of 130-byte wire
+// records (ssa_keyed.hpp)
+struct KeySource {
+    const uint8_t *pks, *pk_inf, *keyed;
+};
+
 // The distinct keys of cnt <= lane_slice lanes on ctx->stream, into the context's workspaces: dd_idx (a key index per
 // lane), dd_reps (the representative lane of each key).  Synchronises the stream ONCE to read u and the number of lanes
 // that hit the probe bound: the policy of the caller needs u on the host.
 // A caller with a hook queues its own launches behind dd_k_index and in front of that read-back: they read u from
 // d_stats[1] on the device, and what they leave in d_stats[2] and d_stats[3] comes back in the same copy (extra[]).
-// With d_keyed the keys are the 49 compressed bytes in front of 130-byte records (ssa_keyed.hpp) and d_pks is unused.
 struct DedupHook {
     std::function<int(unsigned long long *d_stats)> queue;
     unsigned long long extra[2] = {0, 0};
 };
-static int dedup_slice(ssa_ctx *ctx, const uint8_t *d_pks, const uint8_t *d_pk_inf, size_t cnt, uint64_t *u_out,
-                       uint64_t *bound_hits_out, DedupHook *hook = nullptr, const uint8_t *d_keyed = nullptr) {
+static int dedup_slice(ssa_ctx *ctx, const KeySource &src, size_t cnt, uint64_t *u_out, uint64_t *bound_hits_out,
+                       DedupHook *hook = nullptr) {
     if (int rc = dedup_fingerprint_key(ctx)) return rc;
     const size_t cap = dd_slots_for(cnt), nb = grid_for(cnt, DD_BLOCK);
     if (ctx->dd_slots.reserve(cap * sizeof(u64)) || ctx->dd_rep.reserve(cnt * sizeof(u32)) ||
@@ -1109,14 +1118,17 @@ static int dedup_slice(ssa_ctx *ctx, const uint8_t *d_pks, const uint8_t *d_pk_i
     int rc = timed_launch(ctx, "dedup", [&] {
         (void)hipMemsetAsync(ctx->dd_slots.p, 0xff, cap * sizeof(u64), ctx->stream);
         (void)hipMemsetAsync(d_stats, 0, (hook ? 4 : 2) * sizeof(unsigned long long), ctx->stream);
-        if (d_keyed)
-            hipLaunchKernelGGL(ky_k_insert, dim3((unsigned)nb), dim3(DD_BLOCK), 0, ctx->stream, d_keyed, (u32)cnt,
-                               (u64)ctx->dedup_key[0], (u64)ctx->dedup_key[1], (u64 *)ctx->dd_slots.p, (u32)(cap - 1),
-                               (u32)ctx->knobs.dedup_probe_bound, (u32 *)ctx->dd_rep.p, blk_cnt, d_stats);
+        const dim3 grid((unsigned)nb), block(DD_BLOCK);
+        const u64 k0 = ctx->dedup_key[0], k1 = ctx->dedup_key[1];
+        u64 *slots = (u64 *)ctx->dd_slots.p;
+        const u32 mask = (u32)(cap - 1), bound = (u32)ctx->knobs.dedup_probe_bound;
+        u32 *rep = (u32 *)ctx->dd_rep.p;
+        if (src.keyed)
+            hipLaunchKernelGGL(ky_k_insert, grid, block, 0, ctx->stream, src.keyed, (u32)cnt, k0, k1, slots, mask, bound, rep,
+                               blk_cnt, d_stats);
         else
-            hipLaunchKernelGGL(dd_k_insert, dim3((unsigned)nb), dim3(DD_BLOCK), 0, ctx->stream, d_pks, d_pk_inf, (u32)cnt,
-                               (u64)ctx->dedup_key[0], (u64)ctx->dedup_key[1], (u64 *)ctx->dd_slots.p, (u32)(cap - 1),
-                               (u32)ctx->knobs.dedup_probe_bound, (u32 *)ctx->dd_rep.p, blk_cnt, d_stats);
+            hipLaunchKernelGGL(dd_k_insert, grid, block, 0, ctx->stream, src.pks, src.pk_inf, (u32)cnt, k0, k1, slots, mask,
+                               bound, rep, blk_cnt, d_stats);
         hipLaunchKernelGGL(dd_k_scan, dim3(1), dim3(DD_BLOCK), 0, ctx->stream, (const u32 *)blk_cnt, (u32)nb, blk_off,
                            d_stats);
         hipLaunchKernelGGL(dd_k_number, dim3((unsigned)nb), dim3(DD_BLOCK), 0, ctx->stream, (const u32 *)ctx->dd_rep.p,
@@ -1140,21 +1152,33 @@ static int dedup_slice(ssa_ctx *ctx, const uint8_t *d_pks, const uint8_t *d_pk_i
     return 0;
 }
 
-// The u keys dedup_slice found, compacted, and what ssa_k_verify does once per LANE done once per KEY: limb and curve
-// checks, the subgroup check, the sixteen multiples -- ctx->dd_kstatus (0 / 1 / 3 per key) and the tables in ctx->ws_tab
-// (the lanes' table workspace: u tables never need more than one per lane)
-static int dedup_check_keys(ssa_ctx *ctx, const uint8_t *d_pks, const uint8_t *d_pk_inf, uint64_t u) {
-    constexpr size_t TAB_BYTES = (size_t)(PTAB_ENTRIES * PTAB_ENTRY_U64) * sizeof(u64);
+// Rows [0, m) of pks / inf (and of wire, unless nullptr: only a wire cache keeps the 49 bytes) from the keys of the
+// representative lanes reps[0, m) of a slice of cnt lanes, and what ssa_k_verify does once per LANE done once per KEY
+// over those rows: limb and curve checks, the subgroup check, the sixteen multiples -- status (0 / 1 / 3 per key) and
+// tab.  Affine keys are copied (timed as `gather_stage`: the caller's), wire keys decompressed.
+static int key_rows_build(ssa_ctx *ctx, const KeySource &src, const char *gather_stage, const u32 *reps, size_t m, size_t cnt,
+                          u64 *pks, u8 *inf, u64 *wire, u64 *tab, u8 *status) {
+    const int rc = timed_launch(ctx, src.keyed ? "ssa_k_keyed_decompress" : gather_stage, [&] {
+        if (src.keyed)
+            hipLaunchKernelGGL(ky_k_decompress, dim3(grid_for(m, 256)), dim3(256), 0, ctx->stream, src.keyed, reps, (u32)m,
+                               (u32)cnt, pks, inf, wire);
+        else
+            hipLaunchKernelGGL(dd_k_gather, dim3(grid_for(m * 12, DD_BLOCK)), dim3(DD_BLOCK), 0, ctx->stream, src.pks,
+                               src.pk_inf, reps, (u32)m, pks, inf);
+    });
+    if (rc) return rc;
+    return ssa_internal_keyset_build(ctx, (const u8 *)pks, (const u8 *)inf, m, tab, status);
+}
+
+// The u keys dedup_slice found in a slice of cnt lanes, compacted and checked once each, in the context's own
+// workspaces: ctx->dd_pks, ctx->dd_inf, ctx->dd_kstatus and the tables in ctx->ws_tab (the lanes' table workspace: u
+// tables never need more than one per lane)
+static int dedup_check_keys(ssa_ctx *ctx, const KeySource &src, uint64_t u, size_t cnt) {
     if (ctx->dd_pks.reserve(u * 96) || ctx->dd_inf.reserve(u + 16) || ctx->dd_kstatus.reserve(u + 16) ||
         ctx->ws_tab.reserve(u * TAB_BYTES))
         return SSA_ERR_HIP;
-    int rc = timed_launch(ctx, "dedup_gather", [&] {
-        hipLaunchKernelGGL(dd_k_gather, dim3(grid_for(u * 12, DD_BLOCK)), dim3(DD_BLOCK), 0, ctx->stream, d_pks, d_pk_inf,
-                           (const u32 *)ctx->dd_reps.p, (u32)u, (u64 *)ctx->dd_pks.p, (u8 *)ctx->dd_inf.p);
-    });
-    if (rc) return rc;
-    return ssa_internal_keyset_build(ctx, (const u8 *)ctx->dd_pks.p, (const u8 *)ctx->dd_inf.p, (size_t)u,
-                                     (u64 *)ctx->ws_tab.p, (u8 *)ctx->dd_kstatus.p);
+    return key_rows_build(ctx, src, "dedup_gather", (const u32 *)ctx->dd_reps.p, (size_t)u, cnt, (u64 *)ctx->dd_pks.p,
+                          (u8 *)ctx->dd_inf.p, nullptr, (u64 *)ctx->ws_tab.p, (u8 *)ctx->dd_kstatus.p);
 }
 
 // The two ends of the keyed route, shared with ssa_verify_many_screened (ssa_msm.hip), which puts
@@ -1163,8 +1187,9 @@ static int dedup_check_keys(ssa_ctx *ctx, const uint8_t *d_pks, const uint8_t *d
 // stream once, for u.
 int ssa_internal_dedup_keys(ssa_ctx *ctx, const uint8_t *d_pks, const uint8_t *d_pk_inf, size_t cnt, uint64_t *u_out,
                             uint64_t *bound_hits_out) {
-    if (int rc = dedup_slice(ctx, d_pks, d_pk_inf, cnt, u_out, bound_hits_out)) return rc;
-    return dedup_check_keys(ctx, d_pks, d_pk_inf, *u_out);
+    const KeySource src{d_pks, d_pk_inf, nullptr};
+    if (int rc = dedup_slice(ctx, src, cnt, u_out, bound_hits_out)) return rc;
+    return dedup_check_keys(ctx, src, *u_out, cnt);
 }
 
 // ssa_k_verify_keyed over n lanes against the u keys dedup_check_keys left in the context; *d_fail is added to
@@ -1193,16 +1218,15 @@ static int dedup_verify_slice(ssa_ctx *ctx, const DevBatch &b, size_t cnt, uint3
     uint64_t u = cnt, hits = 0;
     // (a threshold of 0 sends every slice to the fallback: the keys are then counted only for the statistics)
     if (ratio > 0 || stats)
-        if (int rc = dedup_slice(ctx, b.pks, b.pk_inf, cnt, &u, &hits)) return rc;
+        if (int rc = dedup_slice(ctx, {b.pks, b.pk_inf, nullptr}, cnt, &u, &hits)) return rc;
     const bool keyed = (double)u < ratio * (double)cnt;
     dedup_stats_add(stats, u, keyed, hits);
-    constexpr size_t TAB_BYTES = (size_t)(PTAB_ENTRIES * PTAB_ENTRY_U64) * sizeof(u64);
     if (!keyed) {       // (nearly) every key is distinct: the path of ssa_verify_many
         if (!hashed) return verify_one_slice(ctx, b, cnt, flags, d_status_out, d_fail);
         if (ctx->ws_tab.reserve(cnt * TAB_BYTES)) return SSA_ERR_HIP;
         return verify_slices(ctx, b, (const u64 *)ctx->ws_h.p, cnt, flags, d_status_out, d_fail);
     }
-    if (int rc = dedup_check_keys(ctx, b.pks, b.pk_inf, u)) return rc;
+    if (int rc = dedup_check_keys(ctx, {b.pks, b.pk_inf, nullptr}, u, cnt)) return rc;
     if (ctx->ws_h.reserve(cnt * 4 * sizeof(u64))) return SSA_ERR_HIP;
     if (!hashed) {
         const int rc = timed_launch(ctx, "ssa_k_hash", [&] {
@@ -1221,7 +1245,7 @@ static int dedup_count_only(ssa_ctx *ctx, const DevBatch &b, size_t n, CallStats
     if (!stats) return 0;
     return for_dev_slices(b, n, ctx->knobs.lane_slice, [&](size_t, size_t cnt, const DevBatch &s) {
         uint64_t u = 0, hits = 0;
-        if (int rc = dedup_slice(ctx, s.pks, s.pk_inf, cnt, &u, &hits)) return rc;
+        if (int rc = dedup_slice(ctx, {s.pks, s.pk_inf, nullptr}, cnt, &u, &hits)) return rc;
         dedup_stats_add(stats, u, false, hits);
         return 0;
     });
@@ -1292,7 +1316,7 @@ extern "C" int ssa_debug_dedup_device(ssa_ctx *ctx, const uint8_t *d_pks, const 
                                       uint32_t *d_key_idx_out, uint64_t out[2]) {
     if (!ctx || !d_pks || !out || n == 0 || n > SSA_MAX_BATCH || n > ctx->knobs.lane_slice) return SSA_ERR_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
-    if (int rc = dedup_slice(ctx, d_pks, d_pk_inf, n, &out[0], &out[1])) return rc;
+    if (int rc = dedup_slice(ctx, {d_pks, d_pk_inf, nullptr}, n, &out[0], &out[1])) return rc;
     if (d_key_idx_out) {
         HIP_TRY(hipMemcpyAsync(d_key_idx_out, ctx->dd_idx.p, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -1318,7 +1342,6 @@ extern "C" int ssa_keycache_create_ex(ssa_ctx *ctx, size_t capacity, uint32_t fl
     if (flags & ~SSA_KEYCACHE_WIRE) return SSA_ERR_ARG;
     if (!ctx || !out || capacity == 0 || capacity > KC_MAX_CAPACITY) return SSA_ERR_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
-    constexpr size_t TAB_BYTES = (size_t)(PTAB_ENTRIES * PTAB_ENTRY_U64) * sizeof(u64);
     ssa_keycache *kc = new ssa_keycache();
     kc->ctx = ctx;
     kc->capacity = capacity;
@@ -1458,6 +1481,21 @@ extern "C" int ssa_keycache_eviction_info(ssa_keycache *kc, uint64_t out[8]) {
     return 0;
 }
 
+// Rows [base, base + m) of the cache, complete, get their slots (kc_k_publish / ky_k_publish: *d_unpublished += rows
+// that found none).  A bare launch: the caller times it.
+static void keycache_publish_launch(ssa_ctx *ctx, ssa_keycache *kc, size_t base, size_t m, unsigned long long *d_unpublished) {
+    const dim3 grid(grid_for(m, DD_BLOCK)), block(DD_BLOCK);
+    const u64 k0 = ctx->dedup_key[0], k1 = ctx->dedup_key[1];
+    u64 *slots = (u64 *)kc->slots.p;
+    const u32 mask = (u32)(kc->n_slots - 1), bound = (u32)ctx->knobs.dedup_probe_bound;
+    if (kc->wire_mode)
+        hipLaunchKernelGGL(ky_k_publish, grid, block, 0, ctx->stream, (const u64 *)kc->wire.p, (u32)base, (u32)m, k0, k1, slots,
+                           mask, bound, d_unpublished);
+    else
+        hipLaunchKernelGGL(kc_k_publish, grid, block, 0, ctx->stream, (const u64 *)kc->rows.pks.p, (const u8 *)kc->inf.p,
+                           (u32)base, (u32)m, k0, k1, slots, mask, bound, d_unpublished);
+}
+
 // A full SSA_KEYCACHE_EVICT_RECENT cache makes room for the m misses of a slice of u distinct keys (m <= u <= capacity,
 // held + m > capacity): the rows used most recently stay, packed into rows [0, K), the slots are rebuilt over them and
 // the slice's found[] follows its hits to their new rows; kc->held = K.  Two read-backs (the ages, the number of rows to
@@ -1465,7 +1503,6 @@ extern "C" int ssa_keycache_eviction_info(ssa_keycache *kc, uint64_t out[8]) {
 // applies (kc_keep): the caller clears.
 static int keycache_compact(ssa_ctx *ctx, ssa_keycache *kc, uint64_t u, uint64_t m, u32 *found,
                             unsigned long long *d_unpublished, bool *done) {
-    constexpr u32 TAB_WORDS = (u32)(PTAB_ENTRIES * PTAB_ENTRY_U64);
     static_assert(TAB_WORDS % 2 == 0 && KY_WIRE_WORDS <= 16, "kc_k_evict_move");
     *done = false;
     const EvictWs w = evict_ws_of(kc);
@@ -1505,19 +1542,11 @@ static int keycache_compact(ssa_ctx *ctx, ssa_keycache *kc, uint64_t u, uint64_t
                            w.remap);
         if (n_move)
             hipLaunchKernelGGL(kc_k_evict_move, dim3(grid_for(n_move, DD_BLOCK / 64)), dim3(DD_BLOCK), 0, ctx->stream,
-                               (const u32 *)w.movers, (const u32 *)w.holes, n_move, held, K, TAB_WORDS, (u64 *)kc->rows.tab.p,
+                               (const u32 *)w.movers, (const u32 *)w.holes, n_move, held, K, (u32)TAB_WORDS, (u64 *)kc->rows.tab.p,
                                (u64 *)kc->rows.pks.p, (u8 *)kc->inf.p, (u8 *)kc->rows.status.p, stamps, (u64 *)kc->wire.p,
                                kc->wire_mode ? (u32)KY_WIRE_WORDS : 0u, w.remap);
         (void)hipMemsetAsync(kc->slots.p, 0xff, kc->n_slots * sizeof(u64), ctx->stream);
-        if (K && kc->wire_mode)
-            hipLaunchKernelGGL(ky_k_publish, dim3(grid_for(K, DD_BLOCK)), dim3(DD_BLOCK), 0, ctx->stream,
-                               (const u64 *)kc->wire.p, 0u, K, (u64)ctx->dedup_key[0], (u64)ctx->dedup_key[1],
-                               (u64 *)kc->slots.p, (u32)(kc->n_slots - 1), (u32)ctx->knobs.dedup_probe_bound, d_unpublished);
-        else if (K)
-            hipLaunchKernelGGL(kc_k_publish, dim3(grid_for(K, DD_BLOCK)), dim3(DD_BLOCK), 0, ctx->stream,
-                               (const u64 *)kc->rows.pks.p, (const u8 *)kc->inf.p, 0u, K, (u64)ctx->dedup_key[0],
-                               (u64)ctx->dedup_key[1], (u64 *)kc->slots.p, (u32)(kc->n_slots - 1),
-                               (u32)ctx->knobs.dedup_probe_bound, d_unpublished);
+        if (K) keycache_publish_launch(ctx, kc, 0, K, d_unpublished);
         hipLaunchKernelGGL(kc_k_remap, dim3(grid_for(u, DD_BLOCK)), dim3(DD_BLOCK), 0, ctx->stream, found, (u32)u,
                            (const u32 *)w.remap, held);
     });
@@ -1583,164 +1612,79 @@ static u32 *keycache_new_epoch(ssa_keycache *kc) {
     return (u32 *)kc->stamps.p;
 }
 
-// Rows base .. base + m of the cache from the keys of the representative lanes reps[0, m): dd_k_gather and
-// ssa_k_keyset_build as they are, with their outputs offset into the cache, then the slots of the new rows
-static int keycache_insert(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *d_pks, const uint8_t *d_pk_inf, const u32 *reps,
-                           size_t base, size_t m, unsigned long long *d_unpublished) {
-    constexpr size_t TAB_WORDS = (size_t)(PTAB_ENTRIES * PTAB_ENTRY_U64);
-    u64 *c_pks = (u64 *)kc->rows.pks.p;
-    u8 *c_inf = (u8 *)kc->inf.p;
-    int rc = timed_launch(ctx, "keycache_insert", [&] {
-        hipLaunchKernelGGL(dd_k_gather, dim3(grid_for(m * 12, DD_BLOCK)), dim3(DD_BLOCK), 0, ctx->stream, d_pks, d_pk_inf,
-                           reps, (u32)m, c_pks + 12 * base, c_inf + base);
-    });
-    if (rc) return rc;
-    rc = ssa_internal_keyset_build(ctx, (const u8 *)(c_pks + 12 * base), (const u8 *)(c_inf + base), m,
-                                   (u64 *)kc->rows.tab.p + base * TAB_WORDS, (u8 *)kc->rows.status.p + base);
-    if (rc) return rc;
-    return timed_launch(ctx, "keycache_insert", [&] {
-        hipLaunchKernelGGL(kc_k_publish, dim3(grid_for(m, DD_BLOCK)), dim3(DD_BLOCK), 0, ctx->stream, (const u64 *)c_pks,
-                           (const u8 *)c_inf, (u32)base, (u32)m, (u64)ctx->dedup_key[0], (u64)ctx->dedup_key[1],
-                           (u64 *)kc->slots.p, (u32)(kc->n_slots - 1), (u32)ctx->knobs.dedup_probe_bound, d_unpublished);
+// The look-up of a slice's u distinct keys (u is read from d_stats[1] on the device) in the cache: found[j] = the row of
+// key j or KC_MISS_BIT | its number among the misses, miss_rep[t] = the representative lane of miss t, d_stats[2] = m.
+// Rows hit get the cache's epoch in stamps (nullptr: the policy keeps none).
+static int keycache_lookup(ssa_ctx *ctx, ssa_keycache *kc, const KeySource &src, size_t cnt, unsigned long long *d_stats,
+                           u32 *found, u32 *miss_rep, u32 *blk_cnt, u32 *stamps) {
+    const size_t nb = grid_for(cnt, DD_BLOCK);
+    u32 *blk_off = blk_cnt + nb;
+    return timed_launch(ctx, "keycache_lookup", [&] {
+        const dim3 grid((unsigned)nb), block(DD_BLOCK);
+        const u32 *reps = (const u32 *)ctx->dd_reps.p;
+        const unsigned long long *stats = d_stats;
+        const u64 k0 = ctx->dedup_key[0], k1 = ctx->dedup_key[1];
+        const u64 *slots = (const u64 *)kc->slots.p;
+        const u32 mask = (u32)(kc->n_slots - 1), bound = (u32)ctx->knobs.dedup_probe_bound, held = (u32)kc->held,
+                  epoch = (u32)kc->epoch;
+        if (src.keyed)
+            hipLaunchKernelGGL(ky_k_lookup, grid, block, 0, ctx->stream, src.keyed, reps, (u32)cnt, stats, k0, k1, slots, mask,
+                               bound, (const u64 *)kc->wire.p, held, found, blk_cnt, stamps, epoch);
+        else
+            hipLaunchKernelGGL(kc_k_lookup, grid, block, 0, ctx->stream, src.pks, src.pk_inf, reps, (u32)cnt, stats, k0, k1,
+                               slots, mask, bound, (const u64 *)kc->rows.pks.p, (const u8 *)kc->inf.p, held, found, blk_cnt,
+                               stamps, epoch);
+        hipLaunchKernelGGL(dd_k_scan, dim3(1), dim3(DD_BLOCK), 0, ctx->stream, (const u32 *)blk_cnt, (u32)nb, blk_off,
+                           d_stats + 1);
+        hipLaunchKernelGGL(kc_k_number, grid, block, 0, ctx->stream, reps, (u32)cnt, stats, (const u32 *)blk_off, found,
+                           miss_rep);
     });
 }
 
-int ssa_internal_keycache_slice(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *d_pks, const uint8_t *d_pk_inf, size_t cnt,
-                                KeyView *kv, uint64_t *u_out, uint64_t *bound_hits_out, uint64_t ks[4],
-                                const unsigned long long **d_unpublished) {
+// ONE slice of cnt lanes through the cache, for affine keys and wire records alike (a wire cache for wire records: the
+// callers check): the distinct keys found and looked up, the misses checked and inserted -- or the cache cleared or
+// compacted first, or bypassed (kc_plan).  One synchronisation, the one of the dedup.  For wire records the signatures
+// are split off in front and every lane's key bytes and flag expanded out of the rows behind: *b (unused otherwise).
+static int keycache_slice(ssa_ctx *ctx, ssa_keycache *kc, const KeySource &src, size_t cnt, DevBatch *b, KeyView *kv,
+                          uint64_t *u_out, uint64_t *bound_hits_out, uint64_t ks[4], const unsigned long long **d_unpublished) {
+    const bool wire = src.keyed != nullptr;
     const size_t nb = grid_for(cnt, DD_BLOCK);
     if (ctx->kc_found.reserve(cnt * sizeof(u32)) || ctx->kc_missrep.reserve(cnt * sizeof(u32)) ||
         ctx->kc_blk.reserve(2 * nb * sizeof(u32)) || ctx->kc_lane_row.reserve(cnt * sizeof(u32)))
         return SSA_ERR_HIP;
-    u32 *found = (u32 *)ctx->kc_found.p, *miss_rep = (u32 *)ctx->kc_missrep.p, *blk_cnt = (u32 *)ctx->kc_blk.p,
-        *blk_off = blk_cnt + nb;
-    const size_t held = kc->held;
-    u32 *stamps = keycache_new_epoch(kc);
-    DedupHook hook;
-    // d_stats: [0] lanes at the probe bound, [1] u, [2] m (dd_k_scan writes its total one word on), [3] unpublished rows
-    hook.queue = [&](unsigned long long *d_stats) {
-        return timed_launch(ctx, "keycache_lookup", [&] {
-            hipLaunchKernelGGL(kc_k_lookup, dim3((unsigned)nb), dim3(DD_BLOCK), 0, ctx->stream, d_pks, d_pk_inf,
-                               (const u32 *)ctx->dd_reps.p, (u32)cnt, (const unsigned long long *)d_stats,
-                               (u64)ctx->dedup_key[0], (u64)ctx->dedup_key[1], (const u64 *)kc->slots.p,
-                               (u32)(kc->n_slots - 1), (u32)ctx->knobs.dedup_probe_bound, (const u64 *)kc->rows.pks.p,
-                               (const u8 *)kc->inf.p, (u32)held, found, blk_cnt, stamps, (u32)kc->epoch);
-            hipLaunchKernelGGL(dd_k_scan, dim3(1), dim3(DD_BLOCK), 0, ctx->stream, (const u32 *)blk_cnt, (u32)nb, blk_off,
-                               d_stats + 1);
-            hipLaunchKernelGGL(kc_k_number, dim3((unsigned)nb), dim3(DD_BLOCK), 0, ctx->stream,
-                               (const u32 *)ctx->dd_reps.p, (u32)cnt, (const unsigned long long *)d_stats,
-                               (const u32 *)blk_off, found, miss_rep);
-        });
-    };
-    uint64_t u = 0;
-    if (int rc = dedup_slice(ctx, d_pks, d_pk_inf, cnt, &u, bound_hits_out, &hook)) return rc;
-    const uint64_t m = hook.extra[0];
-    if (m > u) return SSA_ERR_HIP;      // (never)
-    *u_out = u;
-    ks[0] = ks[1] = ks[2] = ks[3] = 0;
-    *d_unpublished = nullptr;
-    const int plan = kc_plan(kc->capacity, held, u, m);
-    if (plan == KC_PLAN_BYPASS) {       // more keys than rows: the slice as ssa_verify_many_screened runs it
-        ks[3] = 1;
-        *kv = ctx_key_view(ctx, u);
-        return dedup_check_keys(ctx, d_pks, d_pk_inf, u);
-    }
-    unsigned long long *d_unpub = (unsigned long long *)ctx->dd_stats.p + 3;
-    KcPlace pl;
-    if (int rc = keycache_place(ctx, kc, plan, u, m, found, miss_rep, d_unpub, ks, &pl)) return rc;
-    if (pl.fresh) {
-        if (int rc = keycache_insert(ctx, kc, d_pks, d_pk_inf, pl.reps, pl.base, pl.fresh, d_unpub)) return rc;
-        if (int rc = keycache_placed(kc, pl)) return rc;
-    }
-    if (pl.fresh || pl.republished) *d_unpublished = d_unpub;
-    const int rc = timed_launch(ctx, "keycache_map", [&] {
-        hipLaunchKernelGGL(kc_k_map, dim3((unsigned)nb), dim3(DD_BLOCK), 0, ctx->stream, (const u32 *)ctx->dd_idx.p,
-                           (const u32 *)found, (u32)cnt, (u32)pl.base, pl.all_new ? 1u : 0u, (u32 *)ctx->kc_lane_row.p);
-    });
-    if (rc) return rc;
-    *kv = {(const uint32_t *)ctx->kc_lane_row.p, (const uint64_t *)kc->rows.tab.p, (const uint8_t *)kc->rows.status.p,
-           (uint32_t)kc->capacity};
-    return 0;
-}
-
-// ------------------------------------------------------------------ wire records through a wire cache (DESIGN.md section 18)
-int ssa_internal_unpack_keyed(ssa_ctx *ctx, const uint8_t *d_keyed, size_t n, DevBatch *b) {
-    if (ctx->ky_sigs.reserve(n * 81 + 16) || ctx->ky_pks.reserve(n * 96) || ctx->ky_inf.reserve(n + 16)) return SSA_ERR_HIP;
-    b->sigs = (const u8 *)ctx->ky_sigs.p;
-    b->pks = (const u8 *)ctx->ky_pks.p;
-    b->pk_inf = (const u8 *)ctx->ky_inf.p;
-    return timed_launch(ctx, "ssa_k_unpack_keyed", [&] {
-        hipLaunchKernelGGL(ssa_k_unpack_keyed, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, d_keyed, n,
-                           (u8 *)ctx->ky_pks.p, (u8 *)ctx->ky_inf.p, (u8 *)ctx->ky_sigs.p);
-    });
-}
-
-// the keys of the representative lanes reps[0, m) decompressed into rows [0, m) of the given arrays
-static int keyed_decompress(ssa_ctx *ctx, const uint8_t *d_keyed, const u32 *reps, size_t m, size_t cnt, u64 *pks, u8 *inf,
-                            u64 *wire) {
-    return timed_launch(ctx, "ssa_k_keyed_decompress", [&] {
-        hipLaunchKernelGGL(ky_k_decompress, dim3(grid_for(m, 256)), dim3(256), 0, ctx->stream, d_keyed, reps, (u32)m,
-                           (u32)cnt, pks, inf, wire);
-    });
-}
-
-int ssa_internal_keyed_cache_slice(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *d_keyed, size_t cnt, DevBatch *b,
-                                   KeyView *kv, uint64_t *u_out, uint64_t *bound_hits_out, uint64_t ks[4],
-                                   const unsigned long long **d_unpublished) {
-    constexpr size_t TAB_WORDS = (size_t)(PTAB_ENTRIES * PTAB_ENTRY_U64);
-    const size_t nb = grid_for(cnt, DD_BLOCK);
-    if (ctx->kc_found.reserve(cnt * sizeof(u32)) || ctx->kc_missrep.reserve(cnt * sizeof(u32)) ||
-        ctx->kc_blk.reserve(2 * nb * sizeof(u32)) || ctx->kc_lane_row.reserve(cnt * sizeof(u32)) ||
-        ctx->ky_sigs.reserve(cnt * 81 + 16) || ctx->ky_pks.reserve(cnt * 96) || ctx->ky_inf.reserve(cnt + 16))
+    if (wire && (ctx->ky_sigs.reserve(cnt * 81 + 16) || ctx->ky_pks.reserve(cnt * 96) || ctx->ky_inf.reserve(cnt + 16)))
         return SSA_ERR_HIP;
-    u32 *found = (u32 *)ctx->kc_found.p, *miss_rep = (u32 *)ctx->kc_missrep.p, *blk_cnt = (u32 *)ctx->kc_blk.p,
-        *blk_off = blk_cnt + nb;
-    int rc = timed_launch(ctx, "keyed_split", [&] {
-        hipLaunchKernelGGL(ky_k_split, dim3(grid_for((cnt * 81 + 3) / 4, 256)), dim3(256), 0, ctx->stream, d_keyed, cnt,
-                           (u8 *)ctx->ky_sigs.p);
-    });
-    if (rc) return rc;
+    u32 *found = (u32 *)ctx->kc_found.p, *miss_rep = (u32 *)ctx->kc_missrep.p;
+    int rc = 0;
+    if (wire) {
+        rc = timed_launch(ctx, "keyed_split", [&] {
+            hipLaunchKernelGGL(ky_k_split, dim3(grid_for((cnt * 81 + 3) / 4, 256)), dim3(256), 0, ctx->stream, src.keyed, cnt,
+                               (u8 *)ctx->ky_sigs.p);
+        });
+        if (rc) return rc;
+    }
     const size_t held = kc->held;
-    u64 *c_pks = (u64 *)kc->rows.pks.p, *c_wire = (u64 *)kc->wire.p;
-    u8 *c_inf = (u8 *)kc->inf.p;
     u32 *stamps = keycache_new_epoch(kc);
     DedupHook hook;
     // d_stats: [0] lanes at the probe bound, [1] u, [2] m (dd_k_scan writes its total one word on), [3] unpublished rows
     hook.queue = [&](unsigned long long *d_stats) {
-        return timed_launch(ctx, "keycache_lookup", [&] {
-            hipLaunchKernelGGL(ky_k_lookup, dim3((unsigned)nb), dim3(DD_BLOCK), 0, ctx->stream, d_keyed,
-                               (const u32 *)ctx->dd_reps.p, (u32)cnt, (const unsigned long long *)d_stats,
-                               (u64)ctx->dedup_key[0], (u64)ctx->dedup_key[1], (const u64 *)kc->slots.p,
-                               (u32)(kc->n_slots - 1), (u32)ctx->knobs.dedup_probe_bound, (const u64 *)c_wire, (u32)held,
-                               found, blk_cnt, stamps, (u32)kc->epoch);
-            hipLaunchKernelGGL(dd_k_scan, dim3(1), dim3(DD_BLOCK), 0, ctx->stream, (const u32 *)blk_cnt, (u32)nb, blk_off,
-                               d_stats + 1);
-            hipLaunchKernelGGL(kc_k_number, dim3((unsigned)nb), dim3(DD_BLOCK), 0, ctx->stream,
-                               (const u32 *)ctx->dd_reps.p, (u32)cnt, (const unsigned long long *)d_stats,
-                               (const u32 *)blk_off, found, miss_rep);
-        });
+        return keycache_lookup(ctx, kc, src, cnt, d_stats, found, miss_rep, (u32 *)ctx->kc_blk.p, stamps);
     };
     uint64_t u = 0;
-    if ((rc = dedup_slice(ctx, nullptr, nullptr, cnt, &u, bound_hits_out, &hook, d_keyed))) return rc;
+    if ((rc = dedup_slice(ctx, src, cnt, &u, bound_hits_out, &hook))) return rc;
     const uint64_t m = hook.extra[0];
     if (m > u) return SSA_ERR_HIP;      // (never)
     *u_out = u;
     ks[0] = ks[1] = ks[2] = ks[3] = 0;
     *d_unpublished = nullptr;
     const int plan = kc_plan(kc->capacity, held, u, m);
-    const u64 *row_pks = c_pks;
+    u64 *c_pks = (u64 *)kc->rows.pks.p;
+    u8 *c_inf = (u8 *)kc->inf.p;
+    const u64 *row_pks = c_pks;       // the rows kv->lane_key numbers
     const u8 *row_inf = c_inf;
     if (plan == KC_PLAN_BYPASS) {       // more keys than rows: the u keys into the context's own workspaces
         ks[3] = 1;
-        if (ctx->dd_pks.reserve(u * 96) || ctx->dd_inf.reserve(u + 16) || ctx->dd_kstatus.reserve(u + 16) ||
-            ctx->ws_tab.reserve(u * TAB_WORDS * sizeof(u64)))
-            return SSA_ERR_HIP;
-        if ((rc = keyed_decompress(ctx, d_keyed, (const u32 *)ctx->dd_reps.p, (size_t)u, cnt, (u64 *)ctx->dd_pks.p,
-                                   (u8 *)ctx->dd_inf.p, nullptr)))
-            return rc;
-        if ((rc = ssa_internal_keyset_build(ctx, (const u8 *)ctx->dd_pks.p, (const u8 *)ctx->dd_inf.p, (size_t)u,
-                                            (u64 *)ctx->ws_tab.p, (u8 *)ctx->dd_kstatus.p)))
-            return rc;
+        if ((rc = dedup_check_keys(ctx, src, u, cnt))) return rc;
         *kv = ctx_key_view(ctx, u);
         row_pks = (const u64 *)ctx->dd_pks.p;
         row_inf = (const u8 *)ctx->dd_inf.p;
@@ -1749,20 +1693,13 @@ int ssa_internal_keyed_cache_slice(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t
         KcPlace pl;
         if ((rc = keycache_place(ctx, kc, plan, u, m, found, miss_rep, d_unpub, ks, &pl))) return rc;
         const size_t base = pl.base, fresh = pl.fresh;
-        if (fresh) {
-            if ((rc = keyed_decompress(ctx, d_keyed, pl.reps, fresh, cnt, c_pks + 12 * base, c_inf + base,
-                                       c_wire + KY_WIRE_WORDS * base)))
+        if (fresh) {        // rows base .. base + fresh: the keys, their checks and tables, then (complete) their slots
+            if ((rc = key_rows_build(ctx, src, "keycache_insert", pl.reps, fresh, cnt, c_pks + 12 * base, c_inf + base,
+                                     wire ? (u64 *)kc->wire.p + KY_WIRE_WORDS * base : nullptr,
+                                     (u64 *)kc->rows.tab.p + base * TAB_WORDS, (u8 *)kc->rows.status.p + base)))
                 return rc;
-            if ((rc = ssa_internal_keyset_build(ctx, (const u8 *)(c_pks + 12 * base), (const u8 *)(c_inf + base), fresh,
-                                                (u64 *)kc->rows.tab.p + base * TAB_WORDS, (u8 *)kc->rows.status.p + base)))
+            if ((rc = timed_launch(ctx, "keycache_insert", [&] { keycache_publish_launch(ctx, kc, base, fresh, d_unpub); })))
                 return rc;
-            rc = timed_launch(ctx, "keycache_insert", [&] {
-                hipLaunchKernelGGL(ky_k_publish, dim3(grid_for(fresh, DD_BLOCK)), dim3(DD_BLOCK), 0, ctx->stream,
-                                   (const u64 *)c_wire, (u32)base, (u32)fresh, (u64)ctx->dedup_key[0],
-                                   (u64)ctx->dedup_key[1], (u64 *)kc->slots.p, (u32)(kc->n_slots - 1),
-                                   (u32)ctx->knobs.dedup_probe_bound, d_unpub);
-            });
-            if (rc) return rc;
             if ((rc = keycache_placed(kc, pl))) return rc;
         }
         if (fresh || pl.republished) *d_unpublished = d_unpub;
@@ -1774,6 +1711,7 @@ int ssa_internal_keyed_cache_slice(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t
         *kv = {(const uint32_t *)ctx->kc_lane_row.p, (const uint64_t *)kc->rows.tab.p, (const uint8_t *)kc->rows.status.p,
                (uint32_t)kc->capacity};
     }
+    if (!wire) return 0;
     rc = timed_launch(ctx, "keyed_expand", [&] {
         hipLaunchKernelGGL(ky_k_expand, dim3(grid_for(cnt * 12, 256)), dim3(256), 0, ctx->stream, kv->lane_key, row_pks,
                            row_inf, kv->n_keys, (u32)cnt, (u64 *)ctx->ky_pks.p, (u8 *)ctx->ky_inf.p);
@@ -1783,6 +1721,31 @@ int ssa_internal_keyed_cache_slice(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t
     b->pks = (const u8 *)ctx->ky_pks.p;
     b->pk_inf = (const u8 *)ctx->ky_inf.p;
     return 0;
+}
+
+int ssa_internal_keycache_slice(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *d_pks, const uint8_t *d_pk_inf, size_t cnt,
+                                KeyView *kv, uint64_t *u_out, uint64_t *bound_hits_out, uint64_t ks[4],
+                                const unsigned long long **d_unpublished) {
+    return keycache_slice(ctx, kc, {d_pks, d_pk_inf, nullptr}, cnt, nullptr, kv, u_out, bound_hits_out, ks, d_unpublished);
+}
+
+// ------------------------------------------------------------------ wire records through a wire cache (DESIGN.md section 18)
+int ssa_internal_keyed_cache_slice(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *d_keyed, size_t cnt, DevBatch *b,
+                                   KeyView *kv, uint64_t *u_out, uint64_t *bound_hits_out, uint64_t ks[4],
+                                   const unsigned long long **d_unpublished) {
+    if (!d_keyed || !b) return SSA_ERR_ARG;
+    return keycache_slice(ctx, kc, {nullptr, nullptr, d_keyed}, cnt, b, kv, u_out, bound_hits_out, ks, d_unpublished);
+}
+
+int ssa_internal_unpack_keyed(ssa_ctx *ctx, const uint8_t *d_keyed, size_t n, DevBatch *b) {
+    if (ctx->ky_sigs.reserve(n * 81 + 16) || ctx->ky_pks.reserve(n * 96) || ctx->ky_inf.reserve(n + 16)) return SSA_ERR_HIP;
+    b->sigs = (const u8 *)ctx->ky_sigs.p;
+    b->pks = (const u8 *)ctx->ky_pks.p;
+    b->pk_inf = (const u8 *)ctx->ky_inf.p;
+    return timed_launch(ctx, "ssa_k_unpack_keyed", [&] {
+        hipLaunchKernelGGL(ssa_k_unpack_keyed, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, d_keyed, n,
+                           (u8 *)ctx->ky_pks.p, (u8 *)ctx->ky_inf.p, (u8 *)ctx->ky_sigs.p);
+    });
 }
 
 // ------------------------------------------------------------------ several GPUs from one process

@@ -1,29 +1,33 @@
 // Internal: the device key cache (ssa_verify_many_cached).  A key cache is a ladder-kind key set
 // that fills itself: rows of checked keys (the 96 key bytes, the pk_inf boolean, the status byte, the table of sixteen
-// multiples) and an open-addressing table of 64-bit slot words over them (fingerprint's upper half << 32 | cache row;
-// all ones = empty; at least four slots per row; linear probing; the context's probe bound).  The fingerprint is
-// dd_fingerprint (ssa_dedup.hpp) under the context's key, and as there it only picks slots: a slot with a matching
-// upper half is a CANDIDATE and the 97 bytes stored in the row decide.  Equality is never decided on the fingerprint.
+// multiples; in wire mode also the 49 bytes the row was built from, ssa_keyed.hpp) and an open-addressing table of
+// 64-bit slot words over them (fingerprint's upper half << 32 | cache row; all ones = empty; at least four slots per
+// row; linear probing; the context's probe bound).  What identifies a key, its fingerprint and the rule that the words
+// stored in the row decide, never the fingerprint, are those of ssa_dedup.hpp.  The publishing loop is written once
+// over a row source (kc_publish_body); the look-up loop over a lane source and a row source (kc_lookup_body) serves the
+// wire cache, and kc_k_lookup keeps the same loop written out for affine lanes (see there).
 //
-//   kc_k_lookup   one lane per DISTINCT key of the slice (u is read from the device: the launch is queued behind
-//                 dd_k_index and in front of the read-back of dedup_slice).  found[j] = the cache row of key j, or
-//                 KC_MISS; blk_cnt[b] = misses among the keys of workgroup b.  An empty slot ends a probe chain (the
-//                 cache never deletes an entry: eviction is a clear of the whole table); the probe bound ends it too.
+//   kc_k_lookup   (and kc_lookup_body, the body of ky_k_lookup)  one lane per DISTINCT key of the slice (u is
+//                 read from the device: the launch is queued behind dd_k_index and in front of the read-back of
+//                 dedup_slice).  found[j] = the cache row of key j, or KC_MISS; blk_cnt[b] = misses among the keys of
+//                 workgroup b.  An empty slot ends a probe chain (the cache never deletes an entry: eviction empties
+//                 the whole table); the probe bound ends it too.  It writes no slot.
 //   dd_k_scan     (as it is) the per-workgroup offsets and m, the number of misses.
 //   kc_k_number   miss t of the slice, in key order: found[j] = KC_MISS_BIT | t, miss_rep[t] = the key's representative
-//                 lane (what dd_k_gather reads: it copies the misses' bytes into cache rows held .. held + m).
-//   kc_k_publish  after ssa_k_keyset_build has filled rows base .. base + m: one lane per new row claims the first empty
-//                 slot of the row's probe sequence by compare-and-swap.  A row that finds none within the probe bound
-//                 stays unpublished: used by this call, not found by the next (counted).
+//                 lane (whose key goes into cache row held + t).
+//   kc_publish_body  (the body of kc_k_publish and ky_k_publish)  after ssa_k_keyset_build has filled rows base .. base +
+//                 m: one lane per new row claims the first empty slot of the row's probe sequence by compare-and-swap.
+//                 A row that finds none within the probe bound stays unpublished: used by this call, not found by the
+//                 next (counted).
 //   kc_k_map      a cache row per lane from dd_idx and found[] (what ssa_k_verify_keyed and msm_k_screen_keymask index
 //                 the cache's tables and statuses with).
 //
 // Memory model (the rules of ssa_dedup.hpp): workgroups of ONE launch exchange nothing but slot words, and those only
-// through agent-scope atomics (kc_k_publish is the only writer; a compare-and-swap decides every claim and the load in
-// front of it only saves the swap when the slot is taken).  A slot changes once between clears, from empty to owned.
-// Everything written with ordinary stores (key bytes, flags, statuses, tables, found[], the row map) is read by a LATER
-// launch on the same stream: kc_k_publish is launched after the build, so a row is complete before any later launch
-// can find it.  All device writes are vector stores and vector atomics.
+// through agent-scope atomics (the publishing kernels are the only writers; a compare-and-swap decides every claim and
+// the load in front of it only saves the swap when the slot is taken).  A slot changes once between clears, from empty
+// to owned.  Everything written with ordinary stores (key bytes, flags, wire words, statuses, tables, found[], the row
+// map) is read by a LATER launch on the same stream: the publishing kernel is launched after the build, so a row is
+// complete before any later launch can find it.  All device writes are vector stores and vector atomics.
 //
 // Eviction.  A cache keeps the clear-only policy above until ssa_keycache_set_eviction makes it
 // SSA_KEYCACHE_EVICT_RECENT.  Then every row has a 32-bit stamp, the cache's epoch (one per slice that looks keys up) at
@@ -81,14 +85,48 @@ __host__ inline bool kc_keep(uint64_t capacity, uint64_t u, uint64_t m, const ui
 }
 
 #ifndef SSA_NO_KERNELS
-// the 12 key words and the flag of cache row r
-SSA_DEV u64 kc_row_fingerprint(const u64 *__restrict__ c_pks, const u8 *__restrict__ c_inf, u32 r, u64 k0, u64 k1) {
-    u64 w[12];
-#pragma unroll
-    for (int k = 0; k < 12; k++) w[k] = c_pks[(size_t)r * 12 + k];
-    return dd_fingerprint(w, c_inf[r] ? 1u : 0u, k0, k1);
+// The look-up over a lane source and a row source (the body of ky_k_lookup): one lane per distinct key of the slice.  stats[1] = u (dd_k_scan's); n = the
+// lanes of the slice (the grid covers them: u <= n); stamps (or nullptr): the rows' stamps, which get `epoch` on a hit
+template <class Lanes, class Rows>
+SSA_DEV void kc_lookup_body(const Lanes lanes, const Rows rows, const u32 *__restrict__ reps, u32 n,
+                            const unsigned long long *__restrict__ stats, u64 k0, u64 k1, const u64 *__restrict__ slots,
+                            u32 mask, u32 bound, u32 held, u32 *__restrict__ found, u32 *__restrict__ blk_cnt,
+                            u32 *__restrict__ stamps, u32 epoch) {
+    static_assert(Lanes::WORDS == Rows::WORDS && Lanes::BYTES == Rows::BYTES, "lanes and rows of one kind of key");
+    __shared__ u32 wave_cnt[DD_BLOCK / 64];
+    const u32 j = blockIdx.x * DD_BLOCK + threadIdx.x;
+    const u32 u = (u32)stats[1];
+    bool miss = false;
+    if (j < u && j < n) {
+        const u32 i = reps[j];
+        u64 w[Lanes::WORDS] = {};
+        if (i < n) dd_load(lanes, i, w);                  // (always: a representative is a lane of the slice)
+        const u64 fp = dd_fingerprint_of<Lanes>(w, k0, k1);
+        const u64 tag = fp >> 32;
+        u32 s = (u32)fp & mask, row = KC_MISS;
+#pragma unroll 1
+        for (u32 p = 0; p < bound; p++) {
+            const u64 cur = __hip_atomic_load(slots + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (cur == DD_EMPTY) break;
+            const u32 r = (u32)cur;
+            if ((cur >> 32) == tag && r < held && dd_same_key(rows, r, w)) {      // a candidate: the bytes decide
+                row = r;
+                break;
+            }
+            s = (s + 1u) & mask;
+        }
+        found[j] = row;
+        miss = row == KC_MISS;
+        if (stamps && !miss) stamps[row] = epoch;     // (SSA_KEYCACHE_EVICT_RECENT: the row's last use)
+    }
+    const unsigned long long misses = __ballot(miss);
+    if ((threadIdx.x & 63u) == 0) wave_cnt[threadIdx.x >> 6] = (u32)__popcll(misses);
+    __syncthreads();
+    if (threadIdx.x == 0) blk_cnt[blockIdx.x] = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
 }
 
+// kc_k_lookup keeps a body of its own, for the reason given at dd_k_insert (ssa_dedup.hpp): the loop of kc_lookup_body
+// over an affine lane and the 12 words and the flag of an affine row, the flag compared first.
 // stats[1] = u (dd_k_scan's); n = the lanes of the slice (the grid covers them: u <= n); stamps (or nullptr): the rows'
 // stamps, which get `epoch` on a hit
 __global__ void __launch_bounds__(256)
@@ -153,16 +191,18 @@ kc_k_number(const u32 *__restrict__ reps, u32 n, const unsigned long long *__res
     miss_rep[t] = reps[j];
 }
 
-// rows base .. base + m are complete (an earlier launch built them): claim a slot for each; *unpublished += rows that
-// found no empty slot within the probe bound
-__global__ void __launch_bounds__(256)
-kc_k_publish(const u64 *__restrict__ c_pks, const u8 *__restrict__ c_inf, u32 base, u32 m, u64 k0, u64 k1,
-             u64 *__restrict__ slots, u32 mask, u32 bound, unsigned long long *__restrict__ unpublished) {
+// The body of kc_k_publish / ky_k_publish, the only writers of slot words: rows base .. base + m are complete (an
+// earlier launch built them): claim a slot for each; *unpublished += rows that found no empty slot within the probe bound
+template <class Rows>
+SSA_DEV void kc_publish_body(const Rows rows, u32 base, u32 m, u64 k0, u64 k1, u64 *__restrict__ slots, u32 mask,
+                             u32 bound, unsigned long long *__restrict__ unpublished) {
     const u32 t = blockIdx.x * DD_BLOCK + threadIdx.x;
     bool lost = false;
     if (t < m) {
         const u32 r = base + t;
-        const u64 fp = kc_row_fingerprint(c_pks, c_inf, r, k0, k1);
+        u64 w[Rows::WORDS];
+        dd_load(rows, r, w);
+        const u64 fp = dd_fingerprint_of<Rows>(w, k0, k1);
         const u64 mine = ((fp >> 32) << 32) | (u64)r;
         u32 s = (u32)fp & mask;
         lost = true;
@@ -181,6 +221,12 @@ kc_k_publish(const u64 *__restrict__ c_pks, const u8 *__restrict__ c_inf, u32 ba
     }
     const unsigned long long losts = __ballot(lost);
     if ((threadIdx.x & 63u) == 0 && losts) atomicAdd(unpublished, (unsigned long long)__popcll(losts));
+}
+
+__global__ void __launch_bounds__(256)
+kc_k_publish(const u64 *__restrict__ c_pks, const u8 *__restrict__ c_inf, u32 base, u32 m, u64 k0, u64 k1,
+             u64 *__restrict__ slots, u32 mask, u32 bound, unsigned long long *__restrict__ unpublished) {
+    kc_publish_body(DdAffineRows{c_pks, c_inf}, base, m, k0, k1, slots, mask, bound, unpublished);
 }
 
 // lane_row[i] = the cache row of lane i's key: a hit's row, base + t for miss t; all_new (the cache was cleared for this

@@ -642,3 +642,68 @@ def test_module_level_call_over_keyed_signature_objects(engine):
             assert cache.info()["held"] == u
         assert ssa.verify_keyed_many_cached(objs[:12], mo[:12], cache)[4] is not None     # a small batch: the exact path
         assert cache.info()["held"] == u
+
+
+def test_short_probe_bound(engine):
+    """the wire twin of tests/test_gpu_keycache.py::test_short_probe_bound: with a probe bound of 1 lanes become keys of
+    their own and rows stay unpublished, and every status is still the exact one.  (On the suite's engine; its
+    dedup policy is put back whatever happens.  Run alone, the test also pays for the first use of the device through
+    torch in its process, which takes seconds.)"""
+    rng = np.random.default_rng(18961)
+    n, u = 5000, 250
+    keyed, msgs = keyed_honest(engine, rng, n, u)
+    for i in range(3, n, 701):                                      # a handful of bad signatures and one bad key
+        keyed[i, 99] ^= 1
+    keyed[11, :49] = 0xFF
+    co = coeffs32(rng, n)
+    want, wnf = engine.verify_keyed_many(keyed, msgs, check_torsion=True)
+    assert wnf == int((want != 0).sum()) >= 8
+    engine.debug_dedup_config(-1.0, 1)
+    try:
+        with engine.keycache_create(1024, wire=True) as cache:
+            for k in range(2):
+                for form in ("host", "device"):
+                    if form == "host":
+                        st, nf, stats = engine.verify_keyed_many_cached(cache, keyed, msgs, coeffs=co, **T)
+                    else:
+                        st, nf, stats = keyed_cached_device(engine, cache, keyed, msgs, coeffs=co, **T)
+                    print("probe bound 1: call", k, form, [int(v) for v in stats], cache.info())
+                    assert st.tobytes() == want.tobytes() and nf == wnf          # whatever stats[7] says
+                    assert int(stats[HITS]) + int(stats[INSERTED]) == int(stats[0]) >= u
+                    assert cache.info()["held"] <= 1024
+    finally:
+        engine.debug_dedup_config()
+
+
+@pytest.mark.parametrize("evict", ["clear", "recent"])
+def test_affine_and_wire_caches_walk_the_same_plans(engine, evict):
+    """One slice routine serves both kinds of cache: over the same keys, call after call, an affine cache and a wire
+    cache of one capacity take the same plan (insert, hit, clear or compact, bypass) and hold the same number of rows.
+    Every key decodes, so the distinct 49-byte strings are the distinct affine keys."""
+    rng = np.random.default_rng(18971)
+    n, cap = 4096, 256
+    sks = make_scalars(rng, 750)
+    steps = (("cold", sks[:100], (0, 100, 0, 0)), ("warm", sks[:100], (100, 0, 0, 0)),
+             ("partly warm", sks[50:200], (50, 100, 0, 0)), ("overflow", sks[200:400], (0, 200, 1, 0)),
+             ("bypass", sks[400:700], (0, 0, 0, 1)))
+    with engine.keycache_create(cap, evict=evict) as affine, engine.keycache_create(cap, wire=True, evict=evict) as wire:
+        for name, keys, plan in steps:
+            keyed, msgs = keyed_honest(engine, rng, n, keys.shape[0], sks=keys)
+            for i in range(5, n, 577):
+                keyed[i, 99] ^= 1
+            sigs, pks, inf = unpack(engine, keyed)
+            assert not inf.any()
+            co = coeffs32(rng, n)
+            want, wnf = engine.verify_many(sigs, pks, msgs, pk_inf=inf, **T)
+            assert wnf == int((want != 0).sum()) == len(range(5, n, 577))
+            sa, nfa, stats_a = engine.verify_many_cached(affine, sigs, pks, msgs, coeffs=co, pk_inf=inf, **T)
+            sw, nfw, stats_w = engine.verify_keyed_many_cached(wire, keyed, msgs, coeffs=co, **T)
+            stats_a, stats_w = [int(v) for v in stats_a], [int(v) for v in stats_w]
+            print(evict, name, stats_a, stats_w, affine.info(), wire.info())
+            assert sa.tobytes() == sw.tobytes() == want.tobytes() and nfa == nfw == wnf, name
+            assert stats_a[7] == 0 and stats_w[7] == 0, name
+            assert stats_a[0] == stats_w[0] == keys.shape[0], name
+            assert stats_a[HITS:BYPASSED + 1] == stats_w[HITS:BYPASSED + 1] == list(plan), name
+            assert affine.info()["held"] == wire.info()["held"], name
+        if evict == "recent":
+            assert affine.eviction_info()["compactions"] == wire.eviction_info()["compactions"] == 1

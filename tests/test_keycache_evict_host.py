@@ -169,13 +169,32 @@ def test_cxx_mirror_declares_the_eviction_methods(tmp_path):
     subprocess.check_call([cxx, "-std=c++17", "-fsyntax-only", "-Wall", "-Werror", str(src)])
 
 
+def _function_body(text, signature):
+    """the text of the function whose definition starts with `signature`, braces balanced"""
+    a = text.index(signature)
+    i = text.index("{", text.index(")", a))
+    depth, j = 0, i
+    while True:
+        depth += {"{": 1, "}": -1}.get(text[j], 0)
+        j += 1
+        if depth == 0:
+            return text[a:j]
+
+
 def test_one_function_handles_a_full_cache_for_both_kinds_of_cache():
-    """the overflow handling is written once: both slice functions call keycache_place, and only it clears or compacts"""
+    """the overflow handling is written once: ONE slice function serves both kinds of cache, it calls keycache_place
+    once, only keycache_place clears or compacts, and the two entry points only hand their keys to the slice function"""
     api = open(os.path.join(ROOT, "schnorr-sig_amd", "csrc", "ssa_api.hip")).read()
     assert api.count("static int keycache_place(") == 1 and api.count("static int keycache_compact(") == 1
-    a = api.index("int ssa_internal_keycache_slice(")
-    b = api.index("int ssa_internal_keyed_cache_slice(")
-    end = api.index("// ------------------------------------------------------------------ several GPUs")
-    for body in (api[a:b], api[b:end]):
-        assert body.count("keycache_place(ctx, kc, plan,") == 1
+    assert api.count("static int keycache_slice(") == 1
+    assert api.count("keycache_place(ctx, kc, plan,") == 1
+    shared = _function_body(api, "static int keycache_slice(")
+    wrappers = [_function_body(api, "int ssa_internal_keycache_slice("),
+                _function_body(api, "int ssa_internal_keyed_cache_slice(")]
+    assert shared.count("keycache_place(ctx, kc, plan,") == 1
+    for body in [shared] + wrappers:
         assert "keycache_reset(" not in body and "keycache_compact(" not in body
+    for body in wrappers:
+        assert body.count("keycache_slice(ctx, kc,") == 1
+        for name in ("keycache_place(", "hipLaunchKernelGGL", "dedup_slice("):
+            assert name not in body, name

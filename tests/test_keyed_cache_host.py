@@ -170,7 +170,8 @@ def test_the_host_form_stays_on_the_context_and_its_stream():
     for text, signature in ((msm, 'extern "C" int ssa_verify_keyed_many_cached('), (msm, "static int keyed_host_one("),
                             (msm, "static int keyed_cached_slice("), (msm, "static int keyed_exact_slice("),
                             (msm, "static int keyed_batch_screened_device("), (msm, "static int host_slices_in_order("),
-                            (api, "int ssa_internal_keyed_cache_slice("), (api, "int ssa_internal_unpack_keyed(")):
+                            (api, "int ssa_internal_keyed_cache_slice("), (api, "static int keycache_slice("),
+                            (api, "int ssa_internal_unpack_keyed(")):
         body = _function_body(text, signature)
         for name in names:
             assert name not in body, (signature, name)
@@ -185,6 +186,8 @@ def test_the_host_form_stays_on_the_context_and_its_stream():
     assert re.search(r"screen_slice_after_keys\(ctx, b, n, d_coeffs, coeff_bytes, flags, nullptr,", sl)
     assert msm.count("static int screen_slice_after_keys(") == 2          # a declaration and the one definition
     assert "screen_slice_after_keys(ctx, b, n," in _function_body(msm, "static int screen_many_slice(")
+    # ... whose keys go through the one slice function of both kinds of cache
+    assert "keycache_slice(ctx, kc," in _function_body(api, "int ssa_internal_keyed_cache_slice(")
     dev = _function_body(msm, 'extern "C" int ssa_verify_keyed_many_cached_device(')
     assert "keyed_cached_slice(ctx, kc," in dev and "run_host_slices" not in dev
     # both directions of the mode check
