@@ -928,6 +928,35 @@ int ssa_debug_aggregate_coeffs(ssa_ctx *ctx, const uint8_t *rs49, const uint8_t 
                                const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len, size_t n,
                                uint8_t *coeffs16_out);
 
+/* ---- many aggregates in one call --------------------------------------------------------
+ * k aggregates, one verdict each: verdicts_out[j] is the value ssa_verify_aggregate returns for aggregate j handed in
+ * alone with its own keys and messages -- SSA_OK, SSA_INVALID_SIGNATURE or SSA_MALFORMED; for n_j = 0 the 32 bytes must
+ * be zero --, for every input and on every internal path.  The transcript is that of section 20, bit for bit.
+ *   counts[j] = n_j, a HOST array in both forms (the library plans its launches from it without a read-back);
+ *   aggs      = the k aggregates in their wire form, end to end: aggregate j starts at byte 49 (n_0 + ... + n_(j-1)) + 32 j;
+ *   pks, pk_inf, messages belong to the N = sum n_j lanes, in the same order.
+ * The return value reports errors only (a rejected aggregate is a result): SSA_ERR_ARG for an n_j above the context's
+ * MSM slice, N above SSA_MAX_BATCH, or a null pointer the single call refuses.  k == 0: SSA_OK.  The _device form takes
+ * device pointers but for counts, and only enqueues on the context's stream. */
+int ssa_verify_aggregates_many(ssa_ctx *ctx, const uint8_t *aggs, const uint64_t *counts, size_t k, const uint8_t *pks,
+                               const uint8_t *pk_inf, const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride,
+                               size_t msg_len, uint32_t *verdicts_out);
+int ssa_verify_aggregates_many_device(ssa_ctx *ctx, const uint8_t *d_aggs, const uint64_t *counts, size_t k,
+                                      const uint8_t *d_pks, const uint8_t *d_pk_inf, const uint8_t *d_msgs,
+                                      const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len,
+                                      uint32_t *d_verdicts_out);
+/* tests: the plan of such a call from its counts alone (host code, no device).  out[0..4) = lanes, tree passes, groups,
+ * descriptors in all; six words per group (first aggregate, aggregates, first lane, lanes, padded segment length,
+ * 1 = bucket path); then per pass its number of workgroups and four words each (first node, nodes, output slot, n_j if
+ * the workgroup writes a root, else 0).  Returns the words the plan takes -- out receives them if out_words is enough --
+ * or SSA_ERR_ARG. */
+int64_t ssa_debug_aggregates_plan(const uint64_t *counts, size_t k, size_t msm_slice, size_t small_max, uint64_t *out,
+                                  size_t out_words);
+/* tests: the coefficients of all N lanes as ssa_verify_aggregates_many derives them (host buffers) -> N x 16 bytes */
+int ssa_debug_aggregates_many_coeffs(ssa_ctx *ctx, const uint8_t *aggs, const uint64_t *counts, size_t k,
+                                     const uint8_t *pks, const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride,
+                                     size_t msg_len, uint8_t *coeffs16_out);
+
 /* ---- ABI version -------------------------------------------------------------------------------------------
  * Bumped whenever an exported signature changes (round 2 inserted pk_inf into the batch entry points under the same
  * symbol names: a shim built against the older header would still link and pass msgs as pk_inf).  A binding checks

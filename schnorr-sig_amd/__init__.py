@@ -260,6 +260,10 @@ def _load():
         "ssa_verify_aggregate": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz]),
         "ssa_verify_aggregate_device": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz, vp]),
         "ssa_debug_aggregate_coeffs": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz, vp]),
+        "ssa_verify_aggregates_many": (i32, [vp, vp, u64p, sz, vp, vp, vp, vp, sz, sz, vp]),
+        "ssa_verify_aggregates_many_device": (i32, [vp, vp, u64p, sz, vp, vp, vp, vp, sz, sz, vp]),
+        "ssa_debug_aggregates_plan": (C.c_int64, [u64p, sz, sz, sz, u64p, sz]),
+        "ssa_debug_aggregates_many_coeffs": (i32, [vp, vp, u64p, sz, vp, vp, vp, sz, sz, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)      # AttributeError here == ABI symbol missing: fail loudly
@@ -304,6 +308,17 @@ def pack_messages(messages):
         off[1:] = np.cumsum([len(m) for m in messages], dtype=np.uint64)
     flat = np.frombuffer(b"".join(bytes(m) for m in messages) + b"\0", dtype=np.uint8).copy()
     return flat, off
+
+
+def pack_aggregates(aggregates):
+    """AggregateSignature objects or their bytes -> (counts uint64[k], the wire forms end to end as a uint8 array):
+    aggregate j starts at byte 49 (n_0 + ... + n_(j-1)) + 32 j (ssa_verify_aggregates_many)"""
+    raw = [bytes(a.bytes if isinstance(a, AggregateSignature) else a) for a in aggregates]
+    for r in raw:
+        if len(r) < 32 or (len(r) - 32) % 49:
+            raise MalformedInput("an aggregate of n signatures is 49 n + 32 bytes")
+    counts = np.array([(len(r) - 32) // 49 for r in raw], dtype=np.uint64)
+    return counts, np.frombuffer(b"".join(raw) + b"\0", dtype=np.uint8).copy()
 
 
 class Engine:
@@ -670,6 +685,61 @@ class Engine:
             raise MalformedInput("n R's are 49 n bytes")
         out = np.zeros((n, 16), dtype=np.uint8)
         _check(_lib.ssa_debug_aggregate_coeffs(self._ctx, *batch, _ptr(out) if n else None), "ssa_debug_aggregate_coeffs")
+        return out
+
+    # ---- many aggregates in one call (include/schnorr_sig_amd.h) ----
+    def _aggs_batch(self, aggregates, pks, msgs, offsets, pk_inf):
+        """(counts uint64[k], the wire bytes end to end, keys, messages, offsets, stride, length, flags) of a list of
+        AggregateSignature objects or byte strings; the keys and messages of all lanes follow in the same order"""
+        counts, wire = pack_aggregates(aggregates)
+        n = int(counts.sum())
+        pks = _np_u8(pks, 96)
+        if pks.shape[0] != n:
+            raise MalformedInput("We should have the same number of signatures than public keys")
+        m, off, stride, mlen = self._msg_args(msgs, offsets, n) if n else (None, None, 0, 0)
+        inf = _np_u8(pk_inf) if pk_inf is not None else None
+        return counts, wire, pks, m, off, stride, mlen, inf
+
+    def verify_aggregates(self, aggregates, pks, msgs, pk_inf=None, offsets=None):
+        """k aggregates (AggregateSignature objects or their bytes), the keys and messages of all their lanes in order
+        -> uint32[k]: for each aggregate the status verify_aggregate gives it alone"""
+        counts, wire, pks, m, off, stride, mlen, inf = self._aggs_batch(aggregates, pks, msgs, offsets, pk_inf)
+        k = counts.size
+        out = np.full(k, 255, dtype=np.uint32)
+        _check(_lib.ssa_verify_aggregates_many(
+            self._ctx, _ptr(wire) if k else None, counts.ctypes.data_as(C.POINTER(C.c_uint64)) if k else None, k,
+            _ptr(pks) if pks.shape[0] else None, _ptr(inf), _ptr(m), _ptr(off), stride, mlen, _ptr(out) if k else None),
+            "ssa_verify_aggregates_many")
+        return out
+
+    def verify_aggregates_device(self, d_aggs, counts, d_pks, d_msgs, d_verdicts=None, d_pk_inf=None, d_offsets=None,
+                                 msg_len=None, msg_stride=None):
+        """device form over torch tensors on this engine's device: d_aggs the wire bytes end to end, counts a HOST
+        sequence, d_msgs an (N, len) uint8 tensor (or flat bytes with a uint64-valued d_offsets and msg_len left None).
+        Only enqueues; the statuses land in d_verdicts (int32[k], allocated when None), which is returned."""
+        import torch
+        counts = np.ascontiguousarray(counts, dtype=np.uint64)
+        k = counts.size
+        if d_verdicts is None:
+            d_verdicts = torch.empty(max(k, 1), dtype=torch.int32, device=d_aggs.device)[:k]
+        if d_offsets is None and msg_len is None:
+            msg_len = d_msgs.shape[1] if d_msgs.dim() == 2 else 0
+        msg_len = msg_len or 0
+        addr = lambda t: t.data_ptr() if t is not None and t.numel() else None    # noqa: E731
+        _check(_lib.ssa_verify_aggregates_many_device(
+            self._ctx, addr(d_aggs), counts.ctypes.data_as(C.POINTER(C.c_uint64)) if k else None, k, addr(d_pks),
+            addr(d_pk_inf), addr(d_msgs), addr(d_offsets), msg_stride if msg_stride is not None else msg_len, msg_len,
+            addr(d_verdicts)), "ssa_verify_aggregates_many_device")
+        return d_verdicts
+
+    def aggregates_coeffs(self, aggregates, pks, msgs, offsets=None):
+        """tests: the coefficients of all N lanes as verify_aggregates derives them -> uint8[N, 16]"""
+        counts, wire, pks, m, off, stride, mlen, _ = self._aggs_batch(aggregates, pks, msgs, offsets, None)
+        out = np.zeros((pks.shape[0], 16), dtype=np.uint8)
+        if pks.shape[0]:
+            _check(_lib.ssa_debug_aggregates_many_coeffs(
+                self._ctx, _ptr(wire), counts.ctypes.data_as(C.POINTER(C.c_uint64)), counts.size, _ptr(pks), _ptr(m),
+                _ptr(off), stride, mlen, _ptr(out)), "ssa_debug_aggregates_many_coeffs")
         return out
 
     def debug_chacha20(self, key32, nonce12, counter0, n_blocks):
@@ -1418,6 +1488,28 @@ def debug_screen_plan(n, coeff_bytes=0):
     keys = ("segments", "segment_lanes", "window_bits", "windows", "r_windows", "buckets_per_window", "slices",
             "total_segments")
     return {k: int(v) for k, v in zip(keys, out)}
+
+
+def debug_aggregates_plan(counts, msm_slice=1 << 23, small_max=3072):
+    """host logic of verify_aggregates (no device needed): the plan of a call from its counts -> lanes, groups (one dict
+    each) and the tree's passes (lists of (first node, nodes, slot, n_j of a top workgroup or 0)); None when refused"""
+    counts = np.ascontiguousarray(counts, dtype=np.uint64)
+    cp = counts.ctypes.data_as(C.POINTER(C.c_uint64)) if counts.size else None
+    need = _lib.ssa_debug_aggregates_plan(cp, counts.size, int(msm_slice), int(small_max), None, 0)
+    if need < 0:
+        return None
+    out = np.zeros(need, dtype=np.uint64)
+    _check(_lib.ssa_debug_aggregates_plan(cp, counts.size, int(msm_slice), int(small_max),
+                                          out.ctypes.data_as(C.POINTER(C.c_uint64)), need), "ssa_debug_aggregates_plan")
+    w = [int(v) for v in out]
+    keys = ("first_aggregate", "aggregates", "first_lane", "lanes", "segment_lanes", "bucket")
+    groups = [dict(zip(keys, w[4 + 6 * g:10 + 6 * g])) for g in range(w[2])]
+    pos, passes = 4 + 6 * w[2], []
+    for _ in range(w[1]):
+        cnt = w[pos]
+        passes.append([tuple(w[pos + 1 + 4 * d:pos + 5 + 4 * d]) for d in range(cnt)])
+        pos += 1 + 4 * cnt
+    return {"lanes": w[0], "groups": groups, "passes": passes, "descriptors": w[3]}
 
 
 def default_engine():

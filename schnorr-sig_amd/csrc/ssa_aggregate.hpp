@@ -21,7 +21,16 @@
 // whether it is cut out of the level-by-level definition or reduced on its own, and the ragged last run follows the same
 // odd-node rule, so passes of nine levels reproduce the definition for every n.  Everything is written with ordinary
 // vector stores and read by a later launch on the same stream.
+//
+// Many aggregates in one call (ssa_verify_aggregates_many): the transcript runs over all N lanes at
+// once -- ag_k_lane_map (lane -> aggregate, from the uploaded prefix sums), ag_k_expand_many, ssa_k_hash and ag_k_leaf
+// unchanged, ag_k_tree_seg (one descriptor per workgroup, built on the host by ag_plan: no aggregate's nodes mix with
+// another's), ag_k_coeff_many --, then every group of consecutive aggregates takes the small path (msm_k_small over the
+// group's lanes, one wave per aggregate adds its records, ag_k_finish_many) or the bucket path (ag_k_gather* pad the
+// group to equal segments, the screened MSM gives one exact comparison per segment against [e_agg_j]G,
+// ag_k_verdicts_seg turns it into the aggregate's verdict).
 #pragma once
+#include <vector>
 #include "ssa_kernels.hpp"
 
 namespace ssa {
@@ -39,6 +48,83 @@ SSA_DEV void ag_hash8(u64 *A, const DevParams *__restrict__ prm, const u64 (&in)
             if (idx == (u32)k) v = in[k];
         return v;
     }, d);
+}
+
+// ---- the plan of one ssa_verify_aggregates_many call: host code, from the caller's counts alone ----
+// a workgroup of ag_k_tree_seg: nodes [first, first + count) of this pass's input belong to one aggregate and reduce to
+// one node, out[slot]; top_n != 0: the node is that aggregate's top, top_n its n_j, and roots[slot] receives the root
+struct AgTreeDesc {
+    u32 first, count, slot, top_n;
+};
+// consecutive aggregates [agg0, agg0 + aggs) with lanes [lane0, lane0 + lanes); seg_lanes: the largest n_j of the group
+// rounded up to 256 (the padded segment of the bucket path); bucket: which path the group takes
+struct AgGroup {
+    u32 agg0, aggs, lane0, lanes, seg_lanes, bucket;
+};
+constexpr u32 AG_GROUP_MAX = 256;        // segments of one screened MSM (SCREEN_MAX_SEGS)
+struct AgPlan {
+    std::vector<u32> first;                          // k + 1 prefix sums of the counts
+    std::vector<std::vector<AgTreeDesc>> passes;     // the passes per call are those of the largest aggregate
+    std::vector<AgGroup> groups;
+};
+
+// Groups are formed greedily from consecutive aggregates: at most AG_GROUP_MAX of them, and padded lanes
+// (aggregates x seg_lanes) within one MSM slice.  A group whose real lanes fit small_max takes the small path.
+// SSA_ERR_ARG: an aggregate above the slice, or more than SSA_MAX_BATCH lanes in all.
+static inline int ag_plan(const uint64_t *counts, size_t k, size_t slice, size_t small_max, AgPlan &pl) {
+    pl.first.assign(k + 1, 0u);
+    pl.passes.clear();
+    pl.groups.clear();
+    uint64_t total = 0;
+    for (size_t j = 0; j < k; j++) {
+        if (counts[j] > slice || counts[j] > SSA_MAX_BATCH) return SSA_ERR_ARG;
+        total += counts[j];
+        if (total > SSA_MAX_BATCH) return SSA_ERR_ARG;
+        pl.first[j + 1] = (u32)total;
+    }
+    // the tree: every aggregate advances in the same pass; (offset, count) of its nodes in the pass's input
+    std::vector<u32> off(pl.first.begin(), pl.first.end() - 1), cnt(k);
+    size_t live = 0;
+    for (size_t j = 0; j < k; j++) live += (cnt[j] = (u32)counts[j]) != 0;
+    while (live) {
+        std::vector<AgTreeDesc> pass;
+        u32 next = 0;
+        for (size_t j = 0; j < k; j++) {
+            if (!cnt[j]) continue;
+            const u32 g = (cnt[j] + AG_TREE_SPAN - 1) / AG_TREE_SPAN;
+            const bool top = g == 1;
+            for (u32 b = 0; b < g; b++) {
+                const u32 lo = b * AG_TREE_SPAN, c = cnt[j] - lo < AG_TREE_SPAN ? cnt[j] - lo : AG_TREE_SPAN;
+                pass.push_back({off[j] + lo, c, top ? (u32)j : next + b, top ? (u32)counts[j] : 0u});
+            }
+            if (top) {
+                cnt[j] = 0;
+                live--;
+            } else {
+                off[j] = next;
+                cnt[j] = g;
+                next += g;
+            }
+        }
+        pl.passes.push_back(std::move(pass));
+    }
+    auto pad = [](uint64_t n) { return (n + 255) & ~(uint64_t)255; };
+    for (size_t j = 0; j < k;) {
+        AgGroup g{(u32)j, 0u, pl.first[j], 0u, 0u, 0u};
+        uint64_t seg = 256;
+        while (j < k && g.aggs < AG_GROUP_MAX) {
+            const uint64_t s2 = pad(counts[j]) > seg ? pad(counts[j]) : seg;
+            if (g.aggs && s2 * (g.aggs + 1) > slice) break;     // (one aggregate always fits: n_j <= slice, checked by the caller's bound)
+            seg = s2;
+            g.aggs++;
+            j++;
+        }
+        g.lanes = pl.first[g.agg0 + g.aggs] - g.lane0;
+        g.seg_lanes = (u32)seg;
+        g.bucket = g.lanes > small_max ? 1u : 0u;
+        pl.groups.push_back(g);
+    }
+    return 0;
 }
 
 #ifndef SSA_NO_KERNELS
@@ -96,18 +182,12 @@ ag_k_leaf(const DevParams *__restrict__ prm, const u64 *__restrict__ dig, const 
     for (int k = 0; k < 4; k++) nodes[4 * i + k] = d[k];
 }
 
-// One pass of the tree: workgroup b reduces nodes [512 b, 512 b + 512) of `in` (count of them in all) to out[b].  top != 0
-// (a launch of ONE workgroup): the node left is the tree's top and out[0] receives the root, H(top || n_total || 0xA2).
-__global__ void __launch_bounds__(256, 4)
-ag_k_tree(const DevParams *__restrict__ prm, const u64 *__restrict__ in, u32 count, u64 n_total, u32 top,
-          u64 *__restrict__ out) {
-    __shared__ u64 lds[RS_LDS_U64];
-    __shared__ u64 node[256 * 4];
+// cnt (>= 1) nodes at src reduced by one workgroup of 256 lanes to one node at out (four words); top != 0: the node left
+// is a tree's top and out receives the root, H(top || n_total || 0xA2).  lds, node: the workgroup's shared arrays.
+SSA_DEV void ag_tree_reduce(u64 *lds, u64 *node, const DevParams *__restrict__ prm, const u64 *__restrict__ src, u32 cnt,
+                            u64 n_total, u32 top, u64 *__restrict__ out) {
     u64 *A = lds + threadIdx.x;
-    const u32 t = threadIdx.x, first = blockIdx.x * AG_TREE_SPAN;
-    if (first >= count) return;                       // (block-uniform)
-    u32 cnt = count - first < AG_TREE_SPAN ? count - first : AG_TREE_SPAN;
-    const u64 *src = in + 4 * (size_t)first;          // this level's nodes: global for the first level, then LDS
+    const u32 t = threadIdx.x;
 #pragma unroll 1
     for (u32 lvl = 0; lvl < AG_TREE_LEVELS && cnt > 1; lvl++) {
         const u32 outc = (cnt + 1) / 2;
@@ -143,7 +223,65 @@ ag_k_tree(const DevParams *__restrict__ prm, const u64 *__restrict__ in, u32 cou
         ag_hash8(A, prm, v, 6u, r);
     }
 #pragma unroll
-    for (int k = 0; k < 4; k++) out[4 * (size_t)blockIdx.x + k] = r[k];
+    for (int k = 0; k < 4; k++) out[k] = r[k];
+}
+
+// One pass of the tree: workgroup b reduces nodes [512 b, 512 b + 512) of `in` (count of them in all) to out[b].  top != 0
+// (a launch of ONE workgroup): the node left is the tree's top and out[0] receives the root, H(top || n_total || 0xA2).
+__global__ void __launch_bounds__(256, 4)
+ag_k_tree(const DevParams *__restrict__ prm, const u64 *__restrict__ in, u32 count, u64 n_total, u32 top,
+          u64 *__restrict__ out) {
+    __shared__ u64 lds[RS_LDS_U64];
+    __shared__ u64 node[256 * 4];
+    const u32 first = blockIdx.x * AG_TREE_SPAN;
+    if (first >= count) return;                       // (block-uniform)
+    const u32 cnt = count - first < AG_TREE_SPAN ? count - first : AG_TREE_SPAN;
+    ag_tree_reduce(lds, node, prm, in + 4 * (size_t)first, cnt, n_total, top, out + 4 * (size_t)blockIdx.x);
+}
+
+// The same pass over many aggregates at once: workgroup b follows desc[b] (ag_plan), so one aggregate's nodes never mix
+// with another's; a top workgroup writes its aggregate's root to roots[slot], any other its node to out[slot].
+__global__ void __launch_bounds__(256, 4)
+ag_k_tree_seg(const DevParams *__restrict__ prm, const u64 *__restrict__ in, const AgTreeDesc *__restrict__ desc,
+              u32 n_desc, u64 *__restrict__ out, u64 *__restrict__ roots) {
+    __shared__ u64 lds[RS_LDS_U64];
+    __shared__ u64 node[256 * 4];
+    if (blockIdx.x >= n_desc) return;                 // (block-uniform)
+    const AgTreeDesc d = desc[blockIdx.x];
+    ag_tree_reduce(lds, node, prm, in + 4 * (size_t)d.first, d.count, (u64)d.top_n, d.top_n != 0u,
+                   (d.top_n ? roots : out) + 4 * (size_t)d.slot);
+}
+
+// map[i] = the aggregate of lane i: the smallest j with first[j + 1] > i (empty aggregates own no lane)
+__global__ void __launch_bounds__(256)
+ag_k_lane_map(const u32 *__restrict__ first, u32 k, size_t n, u32 *__restrict__ map) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    u32 lo = 0, hi = k - 1;
+    while (lo < hi) {
+        const u32 mid = (lo + hi) / 2;
+        if ((size_t)first[mid + 1] <= i) lo = mid + 1;
+        else hi = mid;
+    }
+    map[i] = lo;
+}
+
+// ag_k_expand over k aggregates laid end to end: lane i of aggregate j reads its R behind the j e_agg's before it
+__global__ void __launch_bounds__(256)
+ag_k_expand_many(const u8 *__restrict__ aggs, const u32 *__restrict__ map, size_t n, u8 *__restrict__ sigs_out) {
+    const size_t d = (size_t)blockIdx.x * 256 + threadIdx.x, total = n * 81, o = 4 * d;
+    if (o >= total) return;
+    u32 v = 0;
+    const int cnt = total - o < 4 ? (int)(total - o) : 4;
+    for (int k = 0; k < cnt; k++) {
+        const size_t b = o + k, i = b / 81, r = b - 81 * i;
+        if (r < 49) v |= (u32)aggs[49 * i + 32 * (size_t)map[i] + r] << (8 * k);
+    }
+    if (cnt == 4) {
+        reinterpret_cast<u32 *>(sigs_out)[d] = v;
+    } else {
+        for (int k = 0; k < cnt; k++) sigs_out[o + k] = (u8)(v >> (8 * k));
+    }
 }
 
 __global__ void __launch_bounds__(256, 4)
@@ -160,6 +298,28 @@ ag_k_coeff(const DevParams *__restrict__ prm, const u64 *__restrict__ root, size
     in[6] = in[7] = 0;
     ag_hash8(A, prm, in, 6u, d);
     // the first 16 bytes of Digest::to_bytes, little-endian, masked to 126 bits; 0 becomes 1
+    u64 lo = d[0];
+    const u64 hi = d[1] & AG_COEFF_HI_MASK;
+    if ((lo | hi) == 0) lo = 1;
+    reinterpret_cast<ulonglong2 *>(coeffs)[i] = make_ulonglong2(lo, hi);
+}
+
+// ag_k_coeff with the root and the index of the lane's own aggregate: a_i = H(root_j || i - first_j || 0xA3)
+__global__ void __launch_bounds__(256, 4)
+ag_k_coeff_many(const DevParams *__restrict__ prm, const u64 *__restrict__ roots, const u32 *__restrict__ map,
+                const u32 *__restrict__ first, size_t n, u64 *__restrict__ coeffs) {
+    __shared__ u64 lds[RS_LDS_U64];
+    u64 *A = lds + threadIdx.x;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const u32 j = map[i];
+    u64 in[8], d[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) in[k] = roots[4 * (size_t)j + k];
+    in[4] = (u64)(i - first[j]);
+    in[5] = AG_TAG_COEFF;
+    in[6] = in[7] = 0;
+    ag_hash8(A, prm, in, 6u, d);
     u64 lo = d[0];
     const u64 hi = d[1] & AG_COEFF_HI_MASK;
     if ((lo | hi) == 0) lo = 1;
@@ -269,10 +429,8 @@ ag_k_empty(const u8 *__restrict__ e_agg, u32 *__restrict__ verdict) {
 // sum a_i R_i - sum (a_i h_i) P_i in canonical form (affine (x, y, 1), or (0, 0, 0) for the identity), and the malformed
 // flag.  right = [e_agg]G from the comb (the walk of msm_k_finish's second wave, same slots); then the comparison of
 // msm_k_finish_seg: both coordinates, the identity equal to the identity only.
-__global__ void __launch_bounds__(64)
-ag_k_finish(const u64 *__restrict__ rec, const u8 *__restrict__ e_agg, const u64 *__restrict__ gtab,
-            u32 *__restrict__ verdict) {
-    __shared__ CoopLds L;
+SSA_DEV void ag_finish_wave(CoopLds &L, const u64 *__restrict__ rec, const u8 *__restrict__ e_agg,
+                            const u64 *__restrict__ gtab, u32 *__restrict__ verdict) {
     const u32 lane = threadIdx.x;
     const int ws = 0;
     const sc256 e = ld_sc(e_agg);
@@ -327,6 +485,100 @@ ag_k_finish(const u64 *__restrict__ rec, const u8 *__restrict__ e_agg, const u64
         eq = eq && coop_eq(L, 8, 10, lane, ws);
     }
     if (lane == 0) *verdict = eq ? ST_OK : ST_INVALID_SIG;
+}
+
+__global__ void __launch_bounds__(64)
+ag_k_finish(const u64 *__restrict__ rec, const u8 *__restrict__ e_agg, const u64 *__restrict__ gtab,
+            u32 *__restrict__ verdict) {
+    __shared__ CoopLds L;
+    ag_finish_wave(L, rec, e_agg, gtab, verdict);
+}
+
+// The small path's finish, one wave per aggregate of a group: block s compares recs[s], the sum of the records of
+// aggregate agg0 + s, with [e_agg]G for that aggregate's own scalar; an empty aggregate follows ag_k_empty's rule.
+__global__ void __launch_bounds__(64)
+ag_k_finish_many(const u64 *__restrict__ recs, const u8 *__restrict__ aggs, const u32 *__restrict__ first, u32 agg0,
+                 const u64 *__restrict__ gtab, u32 *__restrict__ verdicts) {
+    __shared__ CoopLds L;
+    const u32 j = agg0 + blockIdx.x;
+    const u8 *e_agg = aggs + 49 * (size_t)first[j + 1] + 32 * (size_t)j;
+    if (first[j + 1] == first[j]) {                   // (block-uniform)
+        if (threadIdx.x == 0) {
+            const sc256 e = ld_sc(e_agg);
+            const bool zero = (e.w[0] | e.w[1] | e.w[2] | e.w[3]) == 0;
+            verdicts[j] = zero ? ST_OK : (sc_geq_q(e) ? ST_MALFORMED : ST_INVALID_SIG);
+        }
+        return;
+    }
+    ag_finish_wave(L, recs + 24 * (size_t)blockIdx.x, e_agg, gtab, verdicts + j);
+}
+
+// ---- the bucket path: a group of `segs` consecutive aggregates padded to segments of seg_lanes lanes each ----
+// Padded lane p = s * seg_lanes + l is lane first[agg0 + s] + l of the call when l < n_(agg0 + s), else padding:
+// mask 1 (left out of the sums by msm_k_prepare), zero key, zero R, zero scalars.
+// One thread per dword of the padded R's at stride 81 (e = 0), straight from the wire form.
+__global__ void __launch_bounds__(256)
+ag_k_gather_rs(const u8 *__restrict__ aggs, const u32 *__restrict__ first, u32 agg0, u32 segs, u32 seg_lanes,
+               u8 *__restrict__ sigs_out) {
+    const size_t d = (size_t)blockIdx.x * 256 + threadIdx.x, total = (size_t)segs * seg_lanes * 81, o = 4 * d;
+    if (o >= total) return;                            // (total is a multiple of 4: seg_lanes is one of 256)
+    u32 v = 0;
+    for (int k = 0; k < 4; k++) {
+        const size_t b = o + k, p = b / 81, r = b - 81 * p;
+        if (r >= 49) continue;
+        const u32 j = agg0 + (u32)(p / seg_lanes), l = (u32)(p % seg_lanes);
+        if (l < first[j + 1] - first[j]) v |= (u32)aggs[49 * ((size_t)first[j] + l) + 32 * (size_t)j + r] << (8 * k);
+    }
+    reinterpret_cast<u32 *>(sigs_out)[d] = v;
+}
+
+// One thread per padded lane: key, pk_inf, challenge scalar, coefficient and mask; the first 32 * segs threads also copy
+// the e_agg's of the group side by side (rhs: what msm_k_finish_seg multiplies G by).
+__global__ void __launch_bounds__(256)
+ag_k_gather(const u8 *__restrict__ aggs, const u32 *__restrict__ first, u32 agg0, u32 segs, u32 seg_lanes,
+            const u8 *__restrict__ pks, const u8 *__restrict__ pk_inf, const u64 *__restrict__ h,
+            const u64 *__restrict__ coeffs, u8 *__restrict__ g_pks, u8 *__restrict__ g_inf, u64 *__restrict__ g_h,
+            u64 *__restrict__ g_coeffs, u8 *__restrict__ g_mask, u8 *__restrict__ g_rhs) {
+    const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x, total = (size_t)segs * seg_lanes;
+    if (p >= total) return;
+    if (p < 32 * (size_t)segs) {
+        const u32 j = agg0 + (u32)(p >> 5);
+        g_rhs[p] = aggs[49 * (size_t)first[j + 1] + 32 * (size_t)j + (p & 31u)];
+    }
+    const u32 j = agg0 + (u32)(p / seg_lanes), l = (u32)(p % seg_lanes);
+    const bool real = l < first[j + 1] - first[j];
+    const size_t i = (size_t)first[j] + l;
+    u64 *kd = reinterpret_cast<u64 *>(g_pks + 96 * p);      // (the library's own buffer: aligned)
+    if (real && (reinterpret_cast<uintptr_t>(pks) & 7u) == 0) {
+        const u64 *ks = reinterpret_cast<const u64 *>(pks + 96 * i);
+#pragma unroll
+        for (int k = 0; k < 12; k++) kd[k] = ks[k];
+    } else {
+#pragma unroll 1
+        for (int k = 0; k < 12; k++) kd[k] = real ? ld_u64_le(pks + 96 * i + 8 * k) : 0ull;
+    }
+    g_inf[p] = (u8)(real && pk_inf && pk_inf[i] ? 1u : 0u);
+#pragma unroll
+    for (int k = 0; k < 4; k++) g_h[4 * p + k] = real ? h[4 * i + k] : 0ull;
+#pragma unroll
+    for (int k = 0; k < 2; k++) g_coeffs[2 * p + k] = real ? coeffs[2 * i + k] : 0ull;
+    g_mask[p] = (u8)(real ? 0u : 1u);
+}
+
+// Block s, after the screened MSM over the padded group: the verdict of aggregate agg0 + s.  recheck[p] != 0 on a real
+// lane (mask[p] == 0) is a failed check of msm_k_prepare -- a non-canonical limb, a key off the curve, an R that does not
+// decode --: SSA_MALFORMED, as is e_agg >= q; else seg_ok[s] is the exact comparison with [e_agg]G.
+__global__ void __launch_bounds__(256)
+ag_k_verdicts_seg(const u8 *__restrict__ seg_ok, const u8 *__restrict__ recheck, const u8 *__restrict__ mask,
+                  const u8 *__restrict__ rhs, u32 seg_lanes, u32 *__restrict__ verdicts) {
+    const u32 s = blockIdx.x;
+    const size_t lo = (size_t)s * seg_lanes;
+    int bad = 0;
+    for (u32 l = threadIdx.x; l < seg_lanes; l += 256u) bad |= (recheck[lo + l] != 0 && mask[lo + l] == 0) ? 1 : 0;
+    bad = __syncthreads_or(bad);
+    if (threadIdx.x != 0) return;
+    const sc256 e = ld_sc(rhs + 32 * (size_t)s);
+    verdicts[s] = (bad || sc_geq_q(e)) ? ST_MALFORMED : (seg_ok[s] ? ST_OK : ST_INVALID_SIG);
 }
 #endif  // SSA_NO_KERNELS
 

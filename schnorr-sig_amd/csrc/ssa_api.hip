@@ -380,6 +380,7 @@ extern "C" void ssa_ctx_destroy(ssa_ctx *ctx) {
         if (ev) (void)hipEventDestroy(ev);
     if (ctx->pipe_start) (void)hipEventDestroy(ctx->pipe_start);
     if (ctx->order_ev) (void)hipEventDestroy(ctx->order_ev);
+    if (ctx->agm_plan_ev) (void)hipEventDestroy(ctx->agm_plan_ev);
     for (auto &st : ctx->hash_stream)
         if (st) (void)hipStreamDestroy(st);
     if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
@@ -2026,6 +2027,204 @@ extern "C" int ssa_verify_aggregate(ssa_ctx *ctx, const uint8_t *agg, const uint
         return ssa_verify_aggregate_device(ctx, d_agg, d_pks, d_inf, mv.msgs, mv.off, msg_stride, msg_len, n, d_verdict);
     });
     return rc ? rc : (int)v;
+}
+
+// ------------------------------------------------------------------ many aggregates in one call
+// The plan on the device (ctx->agm_plan): k + 1 prefix sums, then the tree's descriptors pass after pass.  The host copy
+// lives in the context; the event says when the last upload has read it.
+static int agm_upload_plan(ssa_ctx *ctx, const AgPlan &pl, std::vector<size_t> &pass_off) {
+    if (!ctx->agm_plan_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->agm_plan_ev, hipEventDisableTiming));
+    else HIP_TRY(hipEventSynchronize(ctx->agm_plan_ev));
+    std::vector<uint32_t> &h = ctx->agm_plan_host;
+    h.assign(pl.first.begin(), pl.first.end());
+    while (h.size() & 3u) h.push_back(0u);             // descriptors are four words: keep them 16-byte aligned
+    pass_off.clear();
+    for (const auto &pass : pl.passes) {
+        pass_off.push_back(h.size() * sizeof(uint32_t));
+        for (const AgTreeDesc &d : pass) h.insert(h.end(), {d.first, d.count, d.slot, d.top_n});
+    }
+    if (ctx->agm_plan.reserve(h.size() * sizeof(uint32_t))) return SSA_ERR_HIP;
+    HIP_TRY(hipMemcpyAsync(ctx->agm_plan.p, h.data(), h.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->agm_plan_ev, ctx->stream));
+    return 0;
+}
+
+// The transcript of every aggregate over all n lanes at once: the R's at stride 81 into ctx->ag_sigs, the challenge
+// scalars into ctx->ws_h, the coefficients into ctx->ag_coeffs.  One launch per stage; the tree takes the passes of the
+// largest aggregate.
+static int agm_transcript(ssa_ctx *ctx, const AgPlan &pl, const std::vector<size_t> &pass_off, const uint8_t *d_aggs, size_t k,
+                          const uint8_t *d_pks, const uint8_t *d_pk_inf, const MsgView &mv, size_t n) {
+    size_t widest = 1;                  // nodes a pass writes (a top workgroup writes a root instead)
+    for (const auto &pass : pl.passes) widest = std::max(widest, pass.size());
+    if (ctx->ag_sigs.reserve(n * 81 + 16) || ctx->agm_map.reserve(n * 4) || ctx->agm_roots.reserve(k * 32) ||
+        ctx->ag_dig.reserve(n * 32) || ctx->ag_nodes.reserve(std::max(n, widest) * 32) || ctx->ag_nodes2.reserve(widest * 32) ||
+        ctx->ag_coeffs.reserve(n * 16) || ctx->ws_h.reserve(n * 32))
+        return SSA_ERR_HIP;
+    const u32 *d_first = (const u32 *)ctx->agm_plan.p;
+    const DevBatch b{(const u8 *)ctx->ag_sigs.p, d_pks, d_pk_inf, mv};
+    int rc = timed_launch(ctx, "ag_k_expand_many", [&] {
+        hipLaunchKernelGGL(ag_k_lane_map, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, d_first, (u32)k, n,
+                           (u32 *)ctx->agm_map.p);
+        hipLaunchKernelGGL(ag_k_expand_many, dim3(grid_for((n * 81 + 3) / 4, 256)), dim3(256), 0, ctx->stream, d_aggs,
+                           (const u32 *)ctx->agm_map.p, n, (u8 *)ctx->ag_sigs.p);
+    });
+    if (rc) return rc;
+    rc = timed_launch(ctx, "ssa_k_hash", [&] {
+        hipLaunchKernelGGL(ssa_k_hash, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, ctx->d_params, b.sigs, b.pks,
+                           b.msgs, n, (u64 *)ctx->ws_h.p, (u8 *)ctx->ag_dig.p, (const u32 *)nullptr, 0u);
+    });
+    if (rc) return rc;
+    rc = timed_launch(ctx, "ag_k_leaf", [&] {
+        hipLaunchKernelGGL(ag_k_leaf, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, ctx->d_params,
+                           (const u64 *)ctx->ag_dig.p, b.sigs, n, (u64 *)ctx->ag_nodes.p);
+    });
+    if (rc) return rc;
+    rc = timed_launch(ctx, "ag_k_tree", [&] {
+        const u64 *in = (const u64 *)ctx->ag_nodes.p;
+        u64 *ping = (u64 *)ctx->ag_nodes2.p, *pong = (u64 *)ctx->ag_nodes.p;
+        for (size_t p = 0; p < pl.passes.size(); p++) {
+            hipLaunchKernelGGL(ag_k_tree_seg, dim3((unsigned)pl.passes[p].size()), dim3(256), 0, ctx->stream, ctx->d_params,
+                               in, (const AgTreeDesc *)((const u8 *)ctx->agm_plan.p + pass_off[p]),
+                               (u32)pl.passes[p].size(), ping, (u64 *)ctx->agm_roots.p);
+            in = ping;
+            std::swap(ping, pong);
+        }
+    });
+    if (rc) return rc;
+    return timed_launch(ctx, "ag_k_coeff", [&] {
+        hipLaunchKernelGGL(ag_k_coeff_many, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, ctx->d_params,
+                           (const u64 *)ctx->agm_roots.p, (const u32 *)ctx->agm_map.p, d_first, n, (u64 *)ctx->ag_coeffs.p);
+    });
+}
+
+// arguments of both forms: the plan from the caller's counts; *n_out = the lanes in all
+static int agm_check_args(const ssa_ctx *ctx, const void *aggs, const uint64_t *counts, size_t k, const void *pks,
+                          const MsgView &mv, const void *verdicts_out, AgPlan &pl, size_t *n_out) {
+    *n_out = 0;
+    if (!ctx) return SSA_ERR_ARG;
+    if (k == 0) return 0;
+    if (!aggs || !counts || !verdicts_out || k > SSA_MAX_BATCH) return SSA_ERR_ARG;
+    if (int rc = ag_plan(counts, k, ctx->knobs.msm_slice, ctx->knobs.msm_small_max, pl)) return rc;
+    *n_out = pl.first[k];
+    if (*n_out && !pks) return SSA_ERR_ARG;
+    return check_msgs(mv, *n_out);
+}
+
+static int agm_run(ssa_ctx *ctx, const AgPlan &pl, const uint8_t *d_aggs, size_t k, const uint8_t *d_pks,
+                   const uint8_t *d_pk_inf, const MsgView &mv, size_t n, uint32_t *d_verdicts_out) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    std::vector<size_t> pass_off;
+    if (int rc = agm_upload_plan(ctx, pl, pass_off)) return rc;
+    if (n)
+        if (int rc = agm_transcript(ctx, pl, pass_off, d_aggs, k, d_pks, d_pk_inf, mv, n)) return rc;
+    if (!d_verdicts_out) return 0;       // (ssa_debug_aggregates_many_coeffs: the transcript alone)
+    const u32 *d_first = (const u32 *)ctx->agm_plan.p;
+    const DevBatch b{(const u8 *)ctx->ag_sigs.p, d_pks, d_pk_inf, mv};
+    for (const AgGroup &g : pl.groups) {
+        if (!g.bucket) {
+            const uint64_t *d_recs = nullptr;
+            if (int rc = ssa_internal_msm_agg_small(ctx, b.slice(g.lane0), g.lanes,
+                                                    (const u8 *)ctx->ag_coeffs.p + 16 * (size_t)g.lane0, d_first, g.agg0,
+                                                    g.aggs, &d_recs))
+                return rc;
+            const int rc = timed_launch(ctx, "ag_k_finish", [&] {
+                hipLaunchKernelGGL(ag_k_finish_many, dim3(g.aggs), dim3(64), 0, ctx->stream, (const u64 *)d_recs, d_aggs,
+                                   d_first, g.agg0, (const u64 *)ctx->d_gtab, d_verdicts_out);
+            });
+            if (rc) return rc;
+            continue;
+        }
+        // the padded group: R's | keys | challenge scalars | coefficients, then the byte arrays
+        const size_t m = (size_t)g.aggs * g.seg_lanes;
+        auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+        const size_t o_pks = al(m * 81 + 16), o_h = o_pks + m * 96, o_co = o_h + m * 32, in_total = o_co + m * 16;
+        const size_t o_mask = al(m), o_re = o_mask + al(m), o_ok = o_re + al(m), o_rhs = o_ok + 256,
+                     by_total = o_rhs + 32 * (size_t)AG_GROUP_MAX;
+        if (ctx->agm_in.reserve(in_total) || ctx->agm_bytes.reserve(by_total)) return SSA_ERR_HIP;
+        u8 *gi = (u8 *)ctx->agm_in.p, *gb = (u8 *)ctx->agm_bytes.p;
+        int rc = timed_launch(ctx, "ag_k_gather", [&] {
+            hipLaunchKernelGGL(ag_k_gather_rs, dim3(grid_for(m * 81 / 4, 256)), dim3(256), 0, ctx->stream, d_aggs, d_first,
+                               g.agg0, g.aggs, g.seg_lanes, gi);
+            hipLaunchKernelGGL(ag_k_gather, dim3(grid_for(m, 256)), dim3(256), 0, ctx->stream, d_aggs, d_first, g.agg0, g.aggs,
+                               g.seg_lanes, d_pks, d_pk_inf, (const u64 *)ctx->ws_h.p, (const u64 *)ctx->ag_coeffs.p,
+                               gi + o_pks, gb, (u64 *)(gi + o_h), (u64 *)(gi + o_co), gb + o_mask, gb + o_rhs);
+        });
+        if (rc) return rc;
+        const DevBatch padded{gi, gi + o_pks, gb, {}};
+        if ((rc = ssa_internal_msm_agg_segments(ctx, padded, g.aggs, g.seg_lanes, gi + o_co, (const uint64_t *)(gi + o_h),
+                                                gb + o_mask, gb + o_re, gb + o_rhs, gb + o_ok)))
+            return rc;
+        rc = timed_launch(ctx, "ag_k_finish", [&] {
+            hipLaunchKernelGGL(ag_k_verdicts_seg, dim3(g.aggs), dim3(256), 0, ctx->stream, gb + o_ok, gb + o_re, gb + o_mask,
+                               gb + o_rhs, g.seg_lanes, d_verdicts_out + g.agg0);
+        });
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+extern "C" int ssa_verify_aggregates_many_device(ssa_ctx *ctx, const uint8_t *d_aggs, const uint64_t *counts, size_t k,
+                                                 const uint8_t *d_pks, const uint8_t *d_pk_inf, const uint8_t *d_msgs,
+                                                 const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len,
+                                                 uint32_t *d_verdicts_out) {
+    const MsgView mv{d_msgs, d_msg_off, msg_stride, msg_len};
+    AgPlan pl;
+    size_t n = 0;
+    if (int rc = agm_check_args(ctx, d_aggs, counts, k, d_pks, mv, d_verdicts_out, pl, &n)) return rc;
+    if (k == 0) return SSA_OK;
+    return agm_run(ctx, pl, d_aggs, k, d_pks, d_pk_inf, mv, n, d_verdicts_out);
+}
+
+extern "C" int ssa_verify_aggregates_many(ssa_ctx *ctx, const uint8_t *aggs, const uint64_t *counts, size_t k,
+                                          const uint8_t *pks, const uint8_t *pk_inf, const uint8_t *msgs,
+                                          const uint64_t *msg_off, size_t msg_stride, size_t msg_len, uint32_t *verdicts_out) {
+    AgPlan pl;
+    size_t n = 0;
+    if (int rc = agm_check_args(ctx, aggs, counts, k, pks, {msgs, msg_off, msg_stride, msg_len}, verdicts_out, pl, &n)) return rc;
+    if (int rc = check_host_offsets(msg_off, n)) return rc;
+    if (k == 0) return SSA_OK;
+    HostCall hc(ctx);
+    const u8 *d_aggs = hc.in(ctx->st_sigs, aggs, 49 * n + 32 * k), *d_pks = hc.in(ctx->st_pks, pks, n * 96);
+    const u8 *d_inf = pk_inf ? hc.in(ctx->st_inf, pk_inf, n) : nullptr;
+    const MsgView mv = hc.msgs(msgs, msg_off, msg_stride, msg_len, n);
+    uint32_t *d_verdicts = (uint32_t *)hc.out(ctx->st_status, verdicts_out, k * sizeof(uint32_t), 16);
+    return hc.finish([&] { return agm_run(ctx, pl, d_aggs, k, d_pks, d_inf, mv, n, d_verdicts); });
+}
+
+// tests: the plan of a call from its counts alone (no device): out[0..4) = lanes, tree passes, groups, descriptors in
+// all; then six words per group (first aggregate, aggregates, first lane, lanes, padded segment, 1 = bucket path); then
+// per pass its number of descriptors and four words each (first node, nodes, slot, n_j of a top workgroup or 0).
+// Returns the words the plan takes (out receives them only if out_words is enough), or SSA_ERR_ARG.
+extern "C" int64_t ssa_debug_aggregates_plan(const uint64_t *counts, size_t k, size_t msm_slice, size_t small_max,
+                                             uint64_t *out, size_t out_words) {
+    if ((k && !counts) || k > SSA_MAX_BATCH) return SSA_ERR_ARG;
+    AgPlan pl;
+    if (int rc = ag_plan(counts, k, msm_slice, small_max, pl)) return rc;
+    std::vector<uint64_t> w{pl.first[k], pl.passes.size(), pl.groups.size(), 0};
+    for (const AgGroup &g : pl.groups) w.insert(w.end(), {g.agg0, g.aggs, g.lane0, g.lanes, g.seg_lanes, g.bucket});
+    for (const auto &pass : pl.passes) {
+        w[3] += pass.size();
+        w.push_back(pass.size());
+        for (const AgTreeDesc &d : pass) w.insert(w.end(), {d.first, d.count, d.slot, d.top_n});
+    }
+    if (out && out_words >= w.size()) std::memcpy(out, w.data(), w.size() * sizeof(uint64_t));
+    return (int64_t)w.size();
+}
+
+// tests: the coefficients of all N lanes as ssa_verify_aggregates_many derives them -> N x 16 bytes
+extern "C" int ssa_debug_aggregates_many_coeffs(ssa_ctx *ctx, const uint8_t *aggs, const uint64_t *counts, size_t k,
+                                                const uint8_t *pks, const uint8_t *msgs, const uint64_t *msg_off,
+                                                size_t msg_stride, size_t msg_len, uint8_t *coeffs16_out) {
+    AgPlan pl;
+    size_t n = 0;
+    if (int rc = agm_check_args(ctx, aggs, counts, k, pks, {msgs, msg_off, msg_stride, msg_len}, coeffs16_out, pl, &n)) return rc;
+    if (int rc = check_host_offsets(msg_off, n)) return rc;
+    if (n == 0) return 0;
+    HostCall hc(ctx);
+    const u8 *d_aggs = hc.in(ctx->st_sigs, aggs, 49 * n + 32 * k), *d_pks = hc.in(ctx->st_pks, pks, n * 96);
+    const MsgView mv = hc.msgs(msgs, msg_off, msg_stride, msg_len, n);
+    (void)hc.out(ctx->ag_coeffs, coeffs16_out, n * 16);
+    return hc.finish([&] { return agm_run(ctx, pl, d_aggs, k, d_pks, nullptr, mv, n, nullptr); });
 }
 
 // tests: the coefficients a_i of an aggregate's R's (n x 49 bytes), keys and messages -> n x 16 bytes

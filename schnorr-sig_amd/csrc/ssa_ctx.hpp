@@ -179,6 +179,10 @@ struct CtxKnobs {
        digests, the tree's nodes (two buffers, passes alternate), the coefficients a_i, the fold's partial sums, a status \
        byte per lane, and one small block: root, MSM record, e_agg, rejection counter, verdict */ \
     X(ag_sigs) X(ag_dig) X(ag_nodes) X(ag_nodes2) X(ag_coeffs) X(ag_partials) X(ag_status) X(ag_misc) \
+    /* many aggregates in one call: the plan (prefix sums, then the tree's descriptors), each \
+       lane's aggregate, one root per aggregate, and a padded group of the bucket path: its inputs (R's, keys, flags, \
+       challenge scalars, coefficients) and its bytes (mask, re-check marks, segment verdicts, right-hand scalars) */ \
+    X(agm_plan) X(agm_map) X(agm_roots) X(agm_in) X(agm_bytes) \
     /* the end game of ssa_k_verify, per tail group: finished pieces; parked accumulators + status (152 B per lane) */ \
     X(tail_done) X(tail_park)
 
@@ -197,6 +201,8 @@ struct ssa_ctx {
     hipEvent_t hash_done[8] = {};             //   tail of one launch (a lane hashes for ~4 ms) overlaps the next
     hipEvent_t pipe_start = nullptr;          // everything queued on `stream` before a pipelined upload began
     hipEvent_t order_ev = nullptr;            // ssa_ctx_stream_release / _acquire
+    hipEvent_t agm_plan_ev = nullptr;         // the last upload of agm_plan_host has left the host (created at the first use)
+    std::vector<uint32_t> agm_plan_host;      // ssa_verify_aggregates_many: the plan as it is uploaded
     CtxKnobs knobs;
     DevParams *d_params = nullptr;
     u64 *d_gtab = nullptr;                    // the comb table for G: owned by gtab_share (one per device, generator and
@@ -765,6 +771,14 @@ int ssa_internal_hash_scalars(ssa_ctx *ctx, const DevBatch &b, size_t n);
 // d_h: the slice's challenge scalars if they exist (batches of at most ctx->knobs.msm_small_max lanes hash for themselves)
 int ssa_internal_msm_record(ssa_ctx *ctx, const DevBatch &b, size_t n, const uint8_t *d_coeffs, uint32_t coeff_bytes,
                             const uint64_t *d_h, uint64_t *d_record_out);
+
+// defined in ssa_msm.hip, for ssa_verify_aggregates_many (ssa_api.hip): the left-hand sides of one
+// group of aggregates, by msm_k_small and one record sum per aggregate, or by the screened MSM over padded segments
+int ssa_internal_msm_agg_small(ssa_ctx *ctx, const DevBatch &b, size_t n, const uint8_t *d_coeffs16, const uint32_t *d_first,
+                               uint32_t agg0, uint32_t aggs, const uint64_t **d_recs_out);
+int ssa_internal_msm_agg_segments(ssa_ctx *ctx, const DevBatch &b, uint32_t segs, uint32_t seg_lanes,
+                                  const uint8_t *d_coeffs16, const uint64_t *d_h, const uint8_t *d_mask, uint8_t *d_recheck,
+                                  const uint8_t *d_rhs, uint8_t *d_seg_ok);
 
 // defined in ssa_api.hip: ssa_k_verify over n lanes of b (its messages unused) whose challenge scalars are already in
 // d_h (the per-lane workspace reserved for one slice of lanes); *d_fail is added to

@@ -757,7 +757,7 @@ msm_k_finish(const u64 *__restrict__ win_in, MsmShape sh, const u64 *__restrict_
 // the sums as the identity with s_i e_i = 0 (msm_k_prepare); the global flag is not read.
 __global__ void __launch_bounds__(128)
 msm_k_finish_seg(const u64 *__restrict__ win_in, MsmShape sh, u32 segs, u32 seg_blocks, const u64 *__restrict__ partials,
-                 u32 n_partials, const u64 *__restrict__ gtab, u8 *__restrict__ seg_ok) {
+                 u32 n_partials, const u64 *__restrict__ gtab, u8 *__restrict__ seg_ok, const u8 *__restrict__ rhs) {
     __shared__ CoopLds L;
     __shared__ u64 lin_sh[64][4];
     const u32 lane = threadIdx.x & 63u, s = blockIdx.x;
@@ -819,6 +819,9 @@ msm_k_finish_seg(const u64 *__restrict__ win_in, MsmShape sh, u32 segs, u32 seg_
         sc256 lin;
 #pragma unroll
         for (int k = 0; k < 4; k++) lin.w[k] = lin_sh[0][k];
+        // rhs != nullptr (ssa_verify_aggregates_many): the segment's right-hand scalar is given --
+        // 32 bytes per segment, the aggregate's e_agg -- instead of the sum of the block partials (zero there: e = 0)
+        if (rhs) lin = ld_sc(rhs + 32 * (size_t)s);
         coop_set(L, 20, 1ull, lane, ws);
         coop_set(L, 21, 1ull, lane, ws);
         coop_set(L, 22, 0ull, lane, ws);
@@ -1170,14 +1173,10 @@ msm_k_small(const DevParams *__restrict__ prm, const u8 *__restrict__ sigs, cons
     }
 }
 
-// records [g * group, (g + 1) * group) -> one record (one wave per group): the points by cooperative general
-// additions, the scalars mod q, the malformed flags OR-ed
-__global__ void __launch_bounds__(64)
-msm_k_sum_records(const u64 *__restrict__ in, u32 count, u32 group, u64 *__restrict__ out) {
-    __shared__ CoopLds L;
-    const u32 lane = threadIdx.x, g = blockIdx.x;
-    const u32 lo = g * group, hi = lo + group < count ? lo + group : count;
-    if (lo >= hi) return;
+// records [lo, hi) of `in` (lo < hi) -> one record at rec, by ONE wave: the points by cooperative general additions, the
+// scalars mod q, the malformed flags OR-ed
+SSA_DEV void sum_records_range(CoopLds &L, const u64 *__restrict__ in, u32 lo, u32 hi, u64 *__restrict__ rec) {
+    const u32 lane = threadIdx.x;
     int t[9];
 #pragma unroll
     for (int k = 0; k < 9; k++) t[k] = 7 + k;
@@ -1209,11 +1208,35 @@ msm_k_sum_records(const u64 *__restrict__ in, u32 count, u32 group, u64 *__restr
             coop_jac_add(L, 0, 4, t, lane, 0);
         }
     }
-    u64 *rec = out + 24 * (size_t)g;
     if (lane < 18) rec[lane] = bad ? 0ull : fp_canon(L.slot[(int)(lane / 6u)][lane % 6u]);
     else if (lane < 22) rec[lane] = lin.w[lane - 18u];
     else if (lane == 22) rec[lane] = bad ? 1ull : 0ull;
     else if (lane == 23) rec[lane] = SSA_MSM_RECORD_MAGIC;
+}
+
+// records [g * group, (g + 1) * group) -> one record (one wave per group)
+__global__ void __launch_bounds__(64)
+msm_k_sum_records(const u64 *__restrict__ in, u32 count, u32 group, u64 *__restrict__ out) {
+    __shared__ CoopLds L;
+    const u32 g = blockIdx.x;
+    const u32 lo = g * group, hi = lo + group < count ? lo + group : count;
+    if (lo >= hi) return;
+    sum_records_range(L, in, lo, hi, out + 24 * (size_t)g);
+}
+
+// The segmented form (ssa_verify_aggregates_many's small path): wave s adds the contiguous records of aggregate
+// agg0 + s -- lanes [first[agg0 + s], first[agg0 + s + 1]) of the call, `in` starting at lane first[agg0] -- into out[s];
+// an aggregate without lanes gets the record of an empty shard.
+__global__ void __launch_bounds__(64)
+msm_k_sum_records_seg(const u64 *__restrict__ in, const u32 *__restrict__ first, u32 agg0, u64 *__restrict__ out) {
+    __shared__ CoopLds L;
+    const u32 j = agg0 + blockIdx.x, lo = first[j] - first[agg0], hi = first[j + 1] - first[agg0];
+    u64 *rec = out + 24 * (size_t)blockIdx.x;
+    if (lo >= hi) {                                   // (block-uniform)
+        if (threadIdx.x < 24) rec[threadIdx.x] = threadIdx.x == 23 ? SSA_MSM_RECORD_MAGIC : 0ull;
+        return;
+    }
+    sum_records_range(L, in, lo, hi, rec);
 }
 
 // the record of an empty shard: the identity (Z = 0), sum s_i e_i = 0, not malformed -- and the magic word: a buffer that
@@ -1383,6 +1406,8 @@ struct ScreenArgs {
     // msm_k_prepare marks them and its own decode failures for the exact re-check instead of writing a status
     const u8 *lane_mask = nullptr;
     u8 *recheck = nullptr;
+    // ssa_verify_aggregates_many only: 32 bytes per segment, the right-hand scalar of its comparison
+    const u8 *rhs = nullptr;
 };
 constexpr u32 SCREEN_C = 8;                 // window bits: K * 2^(c-1) <= 256 * 128 stays within the grouping grid
 static MsmShape screen_shape(u32 segs) {
@@ -1584,7 +1609,7 @@ static int msm_run_one(ssa_ctx *ctx, const DevBatch &b, size_t n, const uint8_t 
     return timed_launch(ctx, "msm_k_finish_seg", [&] {
         hipLaunchKernelGGL(msm_k_finish_seg, dim3(scr->segs), dim3(128), 0, ctx->stream, (const u64 *)ping, sh, scr->segs,
                            scr->seg_blocks, (const u64 *)ctx->msm_partials.p, n_blocks, (const u64 *)ctx->d_gtab,
-                           scr->seg_ok);
+                           scr->seg_ok, scr->rhs);
     });
 }
 
@@ -1592,6 +1617,44 @@ int ssa_internal_msm_record(ssa_ctx *ctx, const DevBatch &b, size_t n, const uin
                             const uint64_t *d_h, uint64_t *d_record_out) {
     if (!d_coeffs || !d_record_out || n > ctx->knobs.msm_slice) return SSA_ERR_ARG;
     return msm_run_one(ctx, b, n, d_coeffs, coeff_bytes, nullptr, (u64 *)d_record_out, (const u64 *)d_h);
+}
+
+// The left-hand sides of ssa_verify_aggregates_many (ssa_api.hip), one group of aggregates each.
+// Small path: msm_k_small over the n lanes of b (the group's, the transcript's coefficients), then one wave per aggregate
+// adds its records: *d_recs_out = `aggs` records, 24 words each.  d_first: the call's prefix sums on the device.
+int ssa_internal_msm_agg_small(ssa_ctx *ctx, const DevBatch &b, size_t n, const uint8_t *d_coeffs16, const uint32_t *d_first,
+                               uint32_t agg0, uint32_t aggs, const uint64_t **d_recs_out) {
+    if (!d_coeffs16 || !d_first || !d_recs_out || aggs == 0) return SSA_ERR_ARG;
+    if (ctx->msm_buckets.reserve((n ? n : 1) * 24 * sizeof(u64)) || ctx->msm_chunks.reserve((size_t)aggs * 24 * sizeof(u64)))
+        return SSA_ERR_HIP;
+    if (n) {
+        const int rc = timed_launch(ctx, "msm_k_small", [&] {
+            hipLaunchKernelGGL(msm_k_small, dim3((unsigned)n), dim3(128), 0, ctx->stream, ctx->d_params, b.sigs, b.pks,
+                               b.pk_inf, b.msgs, d_coeffs16, 16u, n, (u64 *)ctx->msm_buckets.p);
+        });
+        if (rc) return rc;
+    }
+    *d_recs_out = (const uint64_t *)ctx->msm_chunks.p;
+    return timed_launch(ctx, "msm_k_sum_records_seg", [&] {
+        hipLaunchKernelGGL(msm_k_sum_records_seg, dim3(aggs), dim3(64), 0, ctx->stream, (const u64 *)ctx->msm_buckets.p,
+                           d_first, agg0, (u64 *)ctx->msm_chunks.p);
+    });
+}
+
+// Bucket path: b holds segs x seg_lanes padded lanes (seg_lanes a multiple of 256; padding lanes have d_mask 1 and enter
+// no sum), d_h and d_coeffs16 their challenge scalars and coefficients.  The screened pipeline keyed by (window, segment,
+// digit) leaves in d_seg_ok[s] the exact comparison of segment s with [d_rhs[s]]G, and in d_recheck the lanes that
+// msm_k_prepare left out: the padding and every lane that failed one of its checks.
+int ssa_internal_msm_agg_segments(ssa_ctx *ctx, const DevBatch &b, uint32_t segs, uint32_t seg_lanes,
+                                  const uint8_t *d_coeffs16, const uint64_t *d_h, const uint8_t *d_mask, uint8_t *d_recheck,
+                                  const uint8_t *d_rhs, uint8_t *d_seg_ok) {
+    if (!d_coeffs16 || !d_h || !d_mask || !d_recheck || !d_rhs || !d_seg_ok) return SSA_ERR_ARG;
+    if (segs == 0 || segs > 256u || seg_lanes == 0 || (seg_lanes & 255u)) return SSA_ERR_ARG;
+    ScreenArgs sa{segs, seg_lanes / 256u, nullptr, d_seg_ok};
+    sa.lane_mask = d_mask;
+    sa.recheck = d_recheck;
+    sa.rhs = d_rhs;
+    return msm_run_one(ctx, b, (size_t)segs * seg_lanes, d_coeffs16, 16, nullptr, nullptr, (const u64 *)d_h, &sa);
 }
 
 // A batch of any size (n <= SSA_MAX_BATCH) in bounded memory: more than ctx->knobs.msm_slice signatures run slice after slice,

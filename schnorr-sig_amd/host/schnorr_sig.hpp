@@ -652,6 +652,30 @@ struct AggregateSignature {
         return status_to_result(ssa_verify_aggregate(cx.get(), bytes.data(), t.pks.data(), t.inf.data(), t.flat.data(),
                                                      t.off.data(), 0, 0, size()));
     }
+    // Many aggregates in one call: the keys and messages of all their lanes, in order.  One status
+    // per aggregate -- SSA_OK, SSA_INVALID_SIGNATURE or SSA_MALFORMED (where verify() panics) --, each the value verify()
+    // stands for on that aggregate alone.
+    static std::vector<uint32_t> verify_many(Context &cx, const std::vector<AggregateSignature> &aggregates,
+                                             const std::vector<PublicKey> &public_keys,
+                                             const std::vector<std::pair<const uint8_t *, size_t>> &messages) {
+        std::vector<uint64_t> counts;
+        std::vector<uint8_t> wire;
+        size_t n = 0;
+        for (const AggregateSignature &a : aggregates) {
+            counts.push_back(a.size());
+            n += a.size();
+            wire.insert(wire.end(), a.bytes.begin(), a.bytes.end());
+        }
+        if (public_keys.size() != n || messages.size() != n)
+            throw Panic("We should have the same number of messages than public keys");
+        std::vector<uint32_t> verdicts(aggregates.size(), SSA_MALFORMED);
+        if (aggregates.empty()) return verdicts;
+        const PackedTriples t = pack_triples(std::vector<Signature>(n), public_keys, messages);
+        const int rc = ssa_verify_aggregates_many(cx.get(), wire.data(), counts.data(), counts.size(), t.pks.data(),
+                                                  t.inf.data(), t.flat.data(), t.off.data(), 0, 0, verdicts.data());
+        if (rc != 0) throw std::runtime_error(std::string("ssa_verify_aggregates_many: ") + ssa_strerror(rc));
+        return verdicts;
+    }
     const std::vector<uint8_t> &to_bytes() const { return bytes; }
     // nullopt when the length is not 49 n + 32 or e_agg is not canonical
     static std::optional<AggregateSignature> from_bytes(const std::vector<uint8_t> &b) {

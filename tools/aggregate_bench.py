@@ -11,7 +11,16 @@ Legs, timed in one process and ALTERNATING round by round (each call closed by a
 Every timed verify_aggregate verdict must be SSA_OK, and every timed aggregate must equal the first one byte for byte.
 Per-kernel times of one extra verify_aggregate and one extra aggregate come from ssa_ctx_read_timing; the transcript
 kernels' time per Rescue permutation is set beside ssa_k_hash's of the same run (an 80-byte message: four permutations per
-lane; leaf, node and coefficient: about one each).  One JSON line out."""
+lane; leaf, node and coefficient: about one each).  One JSON line out.
+
+--many KxS (repeatable) measures ssa_verify_aggregates_many_device instead: K aggregates of S
+signatures each, cut out of one pool of signatures.  Legs, alternating in the same way, every verdict vector checked:
+  many            one call for all K aggregates, the context's own choice of path per group
+  many_small      the same call on a context created under SSA_MSM_SMALL_MAX = 2^40 (every group: small path)
+  many_bucket     ... under SSA_MSM_SMALL_MAX = 0 (every group: bucket path)
+  loop            K calls of ssa_verify_aggregate_device on this tree's library
+  loop_baseline   the same K calls through the library given by --baseline-lib (another build, e.g. the parent commit's)
+and, once, `single`: the whole pool as ONE aggregate through ssa_verify_aggregate_device."""
 import argparse
 import hashlib
 import json
@@ -34,13 +43,177 @@ def _scalars(rng, n):
     return v
 
 
+MANY_KERNELS = ("ag_k_expand_many", "ssa_k_hash", "ag_k_leaf", "ag_k_tree", "ag_k_coeff", "msm_k_small",
+                "msm_k_sum_records_seg", "ag_k_gather", "msm_k_prepare", "msm_sort", "msm_k_buckets", "msm_reduce",
+                "msm_k_finish_seg", "ag_k_finish")
+
+
+class BaselineLoop:
+    """ssa_verify_aggregate_device of ANOTHER build of the library, loaded beside this tree's in the same process"""
+
+    def __init__(self, path):
+        import ctypes as C
+        self.C, self.lib = C, C.CDLL(path)
+        vp, sz, i32 = C.c_void_p, C.c_size_t, C.c_int
+        self.lib.ssa_ctx_create_ex.argtypes = [C.POINTER(vp), i32, vp, sz, C.c_uint32, C.c_uint64]
+        self.lib.ssa_verify_aggregate_device.argtypes = [vp, vp, vp, vp, vp, vp, sz, sz, sz, vp]
+        self.lib.ssa_ctx_sync.argtypes = [vp]
+        self.lib.ssa_ctx_destroy.argtypes = [vp]
+        self.lib.ssa_ctx_destroy.restype = None
+        self.ctx = vp()
+        if self.lib.ssa_ctx_create_ex(C.byref(self.ctx), 0, None, 0, 0, 0) != 0:
+            raise RuntimeError("baseline library: ssa_ctx_create_ex failed")
+
+    def verify(self, d_agg, d_pks, d_msgs, n, d_verdict):
+        if self.lib.ssa_verify_aggregate_device(self.ctx, d_agg, d_pks, None, d_msgs, None, 80, 80, n, d_verdict) != 0:
+            raise RuntimeError("baseline library: ssa_verify_aggregate_device failed")
+
+    def sync(self):
+        self.lib.ssa_ctx_sync(self.ctx)
+
+    def close(self):
+        self.lib.ssa_ctx_destroy(self.ctx)
+
+
+def engine_under(small_max):
+    import schnorr_sig_amd as ssa
+    old = os.environ.get("SSA_MSM_SMALL_MAX")
+    os.environ["SSA_MSM_SMALL_MAX"] = str(small_max)
+    try:
+        return ssa.Engine(0)
+    finally:
+        if old is None:
+            del os.environ["SSA_MSM_SMALL_MAX"]
+        else:
+            os.environ["SSA_MSM_SMALL_MAX"] = old
+
+
+def many_main(a):
+    import torch
+    import schnorr_sig_amd as ssa
+    dev = torch.device("cuda", 0)
+    shapes = [tuple(int(v) for v in w.lower().split("x")) for w in a.many]
+    n = max(k * s for k, s in shapes)
+    eng = ssa.Engine(0)
+    engs = {"many": eng, "many_small": engine_under(1 << 40), "many_bucket": engine_under(0)}
+    base = BaselineLoop(a.baseline_lib) if a.baseline_lib else None
+    rng = np.random.default_rng(a.seed)
+    msgs = rng.integers(0, 256, (n, 80), dtype=np.uint8)
+    pks, sigs = eng.keygen_sign_many(_scalars(rng, n), _scalars(rng, n), msgs)
+    t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)   # noqa: E731
+    d_sigs, d_pks, d_msgs = t(sigs), t(pks), t(msgs)
+    torch.cuda.synchronize()
+    res = {"metric": "aggregates_many", "msg_len": 80, "rounds": a.rounds, "warmup": a.warmup,
+           "library_sha256": hashlib.sha256(open(ssa.LIB_PATH, "rb").read()).hexdigest()[:16],
+           "baseline_sha256": hashlib.sha256(open(a.baseline_lib, "rb").read()).hexdigest()[:16] if base else None,
+           "device": torch.cuda.get_device_name(0), "date": time.strftime("%Y-%m-%d"), "mismatches": 0, "workloads": []}
+
+    def wall(fn, sync):
+        sync()
+        t0 = time.perf_counter()
+        fn()
+        sync()
+        return (time.perf_counter() - t0) * 1e3
+
+    for k, s in shapes:
+        lanes = k * s
+        d_wire = torch.zeros(49 * lanes + 32 * k, dtype=torch.uint8, device=dev)
+        for j in range(k):        # the honest aggregates, in their wire form end to end
+            lo = j * s
+            if eng.aggregate_device(d_sigs.data_ptr() + 81 * lo, d_pks.data_ptr() + 96 * lo, d_msgs.data_ptr() + 80 * lo, s, 80,
+                                    d_wire.data_ptr() + 49 * lo + 32 * j) != 0:
+                res["mismatches"] += 1
+        eng.sync()
+        counts = [s] * k
+        d_v = torch.full((k,), 255, dtype=torch.int32, device=dev)
+
+        def many(e):
+            return lambda: e.verify_aggregates_device(d_wire, counts, d_pks[:lanes], d_msgs[:lanes], d_verdicts=d_v)
+
+        def loop(verify):
+            def run():
+                for j in range(k):
+                    lo = j * s
+                    verify(d_wire.data_ptr() + 49 * lo + 32 * j, d_pks.data_ptr() + 96 * lo, d_msgs.data_ptr() + 80 * lo, s,
+                           d_v.data_ptr() + 4 * j)
+            return run
+
+        legs = {name: (many(e), e.sync) for name, e in engs.items()}
+        legs["loop"] = (loop(lambda ag, pk, ms, cnt, v: eng.verify_aggregate_device(ag, pk, ms, cnt, 80, v)), eng.sync)
+        if base:
+            legs["loop_baseline"] = (loop(base.verify), base.sync)
+        times = {leg: [] for leg in legs}
+        for rnd in range(a.warmup + a.rounds):
+            for leg, (fn, sync) in legs.items():
+                d_v.fill_(255)
+                torch.cuda.synchronize()
+                ms = wall(fn, sync)
+                if bool((d_v != 0).any()):
+                    res["mismatches"] += 1
+                if rnd >= a.warmup:
+                    times[leg].append(ms)
+        w = {"aggregates": k, "signatures_each": s, "plan": {}, "ms_median": {leg: round(float(np.median(v)), 3) for leg, v in times.items()},
+             "ms_min": {leg: round(float(np.min(v)), 3) for leg, v in times.items()}}
+        pl = ssa.debug_aggregates_plan(counts)
+        w["plan"] = {"groups": len(pl["groups"]), "bucket_groups": sum(g["bucket"] for g in pl["groups"]),
+                     "tree_passes": len(pl["passes"]),
+                     "padded_lanes": sum(g["aggregates"] * g["segment_lanes"] for g in pl["groups"]), "lanes": lanes}
+        med = w["ms_median"]
+        w["ratio"] = {"loop/many": round(med["loop"] / med["many"], 3)}
+        if base:
+            w["ratio"]["loop_baseline/many"] = round(med["loop_baseline"] / med["many"], 3)
+        w["msigs_per_s"] = {leg: round(lanes / v / 1e3, 3) for leg, v in med.items()}
+        kern = {}
+        for name in ("many", "many_small", "many_bucket"):
+            e = engs[name]
+            e.sync()
+            e.enable_timing(True)
+            many(e)()
+            e.sync()
+            kern[name] = {}
+            for kn in MANY_KERNELS:
+                avg, cnt = e.read_timing(kn)
+                if cnt:
+                    kern[name][kn] = [round(avg, 4), int(cnt)]
+            e.enable_timing(False)
+        w["kernel_ms_avg_launches"] = kern
+        res["workloads"].append(w)
+    # the floor: the whole pool as ONE aggregate
+    d_one = torch.zeros(49 * n + 32, dtype=torch.uint8, device=dev)
+    d_v1 = torch.full((1,), 255, dtype=torch.int32, device=dev)
+    if eng.aggregate_device(d_sigs.data_ptr(), d_pks.data_ptr(), d_msgs.data_ptr(), n, 80, d_one.data_ptr()) != 0:
+        res["mismatches"] += 1
+    one = []
+    for rnd in range(a.warmup + a.rounds):
+        d_v1.fill_(255)
+        torch.cuda.synchronize()
+        ms = wall(lambda: eng.verify_aggregate_device(d_one.data_ptr(), d_pks.data_ptr(), d_msgs.data_ptr(), n, 80,
+                                                      d_v1.data_ptr()), eng.sync)
+        if int(d_v1.item()) != 0:
+            res["mismatches"] += 1
+        if rnd >= a.warmup:
+            one.append(ms)
+    res["single"] = {"n": n, "ms_median": round(float(np.median(one)), 3), "ms_min": round(float(np.min(one)), 3)}
+    print(json.dumps(res))
+    for e in engs.values():
+        e.close()
+    if base:
+        base.close()
+    return 0 if res["mismatches"] == 0 else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1 << 20)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--seed", type=int, default=0xA66)
+    ap.add_argument("--many", action="append", default=[], metavar="KxS",
+                    help="K aggregates of S signatures in one ssa_verify_aggregates_many call (repeatable)")
+    ap.add_argument("--baseline-lib", default=None, help="another build of the library for the loop_baseline leg")
     a = ap.parse_args()
+    if a.many:
+        return many_main(a)
     import torch
     import schnorr_sig_amd as ssa
     dev = torch.device("cuda", 0)
