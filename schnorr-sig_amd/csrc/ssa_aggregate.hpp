@@ -9,26 +9,31 @@
 //   root   = H(top || n || 0xA2)                                                        nine levels through LDS
 //   a_i    = low 126 bits of Digest::to_bytes(H(root || i || 0xA3)), 0 -> 1   ag_k_coeff   n x 16 bytes
 //
+// ONE transcript with an optional plan.  The kernels run over all N lanes of a call at once and take the plan's device
+// pointers: first (k + 1 prefix sums of the aggregates' sizes), map (lane -> aggregate, ag_k_lane_map) and the tree's
+// descriptors (one per workgroup and pass, built on the host by ag_plan: no aggregate's nodes mix with another's).  A null
+// plan is the single call: one aggregate of n lanes starting at lane 0, the uniform cut of the
+// tree, root 0.  Many aggregates in one call (ssa_verify_aggregates_many) upload a plan; verdict j
+// is then the single call's for aggregate j alone by construction, as far as the transcript goes.
+//
+//   ag_k_expand    the aggregates' R's back at stride 81 with e = 0: what ssa_k_hash and the MSM preparation read
 //   ag_k_fold / ag_k_fold_finish   sum a_i e_i mod q: per-workgroup partial sums, then one finishing workgroup; the
 //                                  first also makes the checks of msm_k_prepare (canonical limbs, e < q, key on the
 //                                  curve, R decodable) when the caller did not screen the signatures
 //   ag_k_pack      the first 49 bytes of every signature side by side: the aggregate's R's
-//   ag_k_expand    the aggregate's R's back at stride 81 with e = 0: what ssa_k_hash and the MSM preparation read
-//   ag_k_finish    one wave: [e_agg]G from the comb and the EXACT comparison with the left-hand point of the MSM's record
-//                  (affine x and y, or the identity) -- not the x-only one of msm_k_finish
+//   ag_k_finish    one wave per aggregate: [e_agg]G from the comb and the EXACT comparison with the left-hand point of
+//                  the MSM's record (affine x and y, or the identity) -- not the x-only one of msm_k_finish; the empty
+//                  aggregate is valid iff its scalar is zero
 //
-// A workgroup of ag_k_tree takes 512 consecutive nodes: the tree over an aligned run of 2^9 leaves is the same subtree
-// whether it is cut out of the level-by-level definition or reduced on its own, and the ragged last run follows the same
-// odd-node rule, so passes of nine levels reproduce the definition for every n.  Everything is written with ordinary
-// vector stores and read by a later launch on the same stream.
+// A workgroup of ag_k_tree takes at most 512 consecutive nodes: the tree over an aligned run of 2^9 leaves is the same
+// subtree whether it is cut out of the level-by-level definition or reduced on its own, and the ragged last run follows
+// the same odd-node rule, so passes of nine levels reproduce the definition for every n.  Everything is written with
+// ordinary vector stores and read by a later launch on the same stream.
 //
-// Many aggregates in one call (ssa_verify_aggregates_many): the transcript runs over all N lanes at
-// once -- ag_k_lane_map (lane -> aggregate, from the uploaded prefix sums), ag_k_expand_many, ssa_k_hash and ag_k_leaf
-// unchanged, ag_k_tree_seg (one descriptor per workgroup, built on the host by ag_plan: no aggregate's nodes mix with
-// another's), ag_k_coeff_many --, then every group of consecutive aggregates takes the small path (msm_k_small over the
-// group's lanes, one wave per aggregate adds its records, ag_k_finish_many) or the bucket path (ag_k_gather* pad the
-// group to equal segments, the screened MSM gives one exact comparison per segment against [e_agg_j]G,
-// ag_k_verdicts_seg turns it into the aggregate's verdict).
+// After the transcript, every group of consecutive aggregates of a many-call takes the small path (msm_k_small over the
+// group's lanes, one wave per aggregate adds its records, ag_k_finish) or the bucket path (ag_k_gather* pad the group to
+// equal segments, the screened MSM gives one exact comparison per segment against [e_agg_j]G, ag_k_verdicts_seg turns it
+// into the aggregate's verdict).
 #pragma once
 #include <vector>
 #include "ssa_kernels.hpp"
@@ -51,7 +56,7 @@ SSA_DEV void ag_hash8(u64 *A, const DevParams *__restrict__ prm, const u64 (&in)
 }
 
 // ---- the plan of one ssa_verify_aggregates_many call: host code, from the caller's counts alone ----
-// a workgroup of ag_k_tree_seg: nodes [first, first + count) of this pass's input belong to one aggregate and reduce to
+// a workgroup of ag_k_tree: nodes [first, first + count) of this pass's input belong to one aggregate and reduce to
 // one node, out[slot]; top_n != 0: the node is that aggregate's top, top_n its n_j, and roots[slot] receives the root
 struct AgTreeDesc {
     u32 first, count, slot, top_n;
@@ -128,16 +133,23 @@ static inline int ag_plan(const uint64_t *counts, size_t k, size_t slice, size_t
 }
 
 #ifndef SSA_NO_KERNELS
-// sigs_out (the library's own buffer: dword-aligned, n * 81 bytes) = R_i (49 bytes) || 32 zero bytes.  One lane per dword.
+// The wire form of a call: aggregate j is its n_j R's (49 bytes each) and then e_agg_j (32 bytes), the aggregates end to
+// end.  lane: the lane's number in the call (first_j + l); a single aggregate is j = 0.
+SSA_DEV size_t ag_wire_r(size_t lane, u32 j) { return 49 * lane + 32 * (size_t)j; }
+// e_agg_j stands behind the aggregate's last R; first == nullptr: the one aggregate of n lanes
+SSA_DEV size_t ag_wire_e(const u32 *__restrict__ first, u32 j, size_t n) { return ag_wire_r(first ? first[j + 1] : n, j); }
+
+// sigs_out (the library's own buffer: dword-aligned, n * 81 bytes) = R_i (49 bytes) || 32 zero bytes, over the n lanes of
+// the wire form `aggs`; map[i]: the aggregate of lane i, nullptr: one aggregate.  One lane per dword.
 __global__ void __launch_bounds__(256)
-ag_k_expand(const u8 *__restrict__ rs49, size_t n, u8 *__restrict__ sigs_out) {
+ag_k_expand(const u8 *__restrict__ aggs, const u32 *__restrict__ map, size_t n, u8 *__restrict__ sigs_out) {
     const size_t d = (size_t)blockIdx.x * 256 + threadIdx.x, total = n * 81, o = 4 * d;
     if (o >= total) return;
     u32 v = 0;
     const int cnt = total - o < 4 ? (int)(total - o) : 4;
     for (int k = 0; k < cnt; k++) {
         const size_t b = o + k, i = b / 81, r = b - 81 * i;
-        if (r < 49) v |= (u32)rs49[49 * i + r] << (8 * k);
+        if (r < 49) v |= (u32)aggs[ag_wire_r(i, map ? map[i] : 0u) + r] << (8 * k);
     }
     if (cnt == 4) {
         reinterpret_cast<u32 *>(sigs_out)[d] = v;
@@ -226,28 +238,24 @@ SSA_DEV void ag_tree_reduce(u64 *lds, u64 *node, const DevParams *__restrict__ p
     for (int k = 0; k < 4; k++) out[k] = r[k];
 }
 
-// One pass of the tree: workgroup b reduces nodes [512 b, 512 b + 512) of `in` (count of them in all) to out[b].  top != 0
-// (a launch of ONE workgroup): the node left is the tree's top and out[0] receives the root, H(top || n_total || 0xA2).
+// One pass of the tree.  Workgroup b follows desc[b] (ag_plan; count of them), so one aggregate's nodes never mix with
+// another's.  desc == nullptr, one aggregate: it forms its own descriptor, nodes [512 b, 512 b + 512) of the count in all
+// into slot b, and top_n (its n on the pass of ONE workgroup, else 0).  A top workgroup writes its aggregate's root,
+// H(top || n || 0xA2), to roots[slot], any other its node to out[slot].
 __global__ void __launch_bounds__(256, 4)
-ag_k_tree(const DevParams *__restrict__ prm, const u64 *__restrict__ in, u32 count, u64 n_total, u32 top,
-          u64 *__restrict__ out) {
+ag_k_tree(const DevParams *__restrict__ prm, const u64 *__restrict__ in, const AgTreeDesc *__restrict__ desc, u32 count,
+          u32 top_n, u64 *__restrict__ out, u64 *__restrict__ roots) {
     __shared__ u64 lds[RS_LDS_U64];
     __shared__ u64 node[256 * 4];
-    const u32 first = blockIdx.x * AG_TREE_SPAN;
-    if (first >= count) return;                       // (block-uniform)
-    const u32 cnt = count - first < AG_TREE_SPAN ? count - first : AG_TREE_SPAN;
-    ag_tree_reduce(lds, node, prm, in + 4 * (size_t)first, cnt, n_total, top, out + 4 * (size_t)blockIdx.x);
-}
-
-// The same pass over many aggregates at once: workgroup b follows desc[b] (ag_plan), so one aggregate's nodes never mix
-// with another's; a top workgroup writes its aggregate's root to roots[slot], any other its node to out[slot].
-__global__ void __launch_bounds__(256, 4)
-ag_k_tree_seg(const DevParams *__restrict__ prm, const u64 *__restrict__ in, const AgTreeDesc *__restrict__ desc,
-              u32 n_desc, u64 *__restrict__ out, u64 *__restrict__ roots) {
-    __shared__ u64 lds[RS_LDS_U64];
-    __shared__ u64 node[256 * 4];
-    if (blockIdx.x >= n_desc) return;                 // (block-uniform)
-    const AgTreeDesc d = desc[blockIdx.x];
+    AgTreeDesc d;
+    if (desc) {
+        if (blockIdx.x >= count) return;              // (block-uniform)
+        d = desc[blockIdx.x];
+    } else {
+        const u32 first = blockIdx.x * AG_TREE_SPAN;
+        if (first >= count) return;                   // (block-uniform)
+        d = {first, count - first < AG_TREE_SPAN ? count - first : AG_TREE_SPAN, blockIdx.x, top_n};
+    }
     ag_tree_reduce(lds, node, prm, in + 4 * (size_t)d.first, d.count, (u64)d.top_n, d.top_n != 0u,
                    (d.top_n ? roots : out) + 4 * (size_t)d.slot);
 }
@@ -266,34 +274,20 @@ ag_k_lane_map(const u32 *__restrict__ first, u32 k, size_t n, u32 *__restrict__ 
     map[i] = lo;
 }
 
-// ag_k_expand over k aggregates laid end to end: lane i of aggregate j reads its R behind the j e_agg's before it
-__global__ void __launch_bounds__(256)
-ag_k_expand_many(const u8 *__restrict__ aggs, const u32 *__restrict__ map, size_t n, u8 *__restrict__ sigs_out) {
-    const size_t d = (size_t)blockIdx.x * 256 + threadIdx.x, total = n * 81, o = 4 * d;
-    if (o >= total) return;
-    u32 v = 0;
-    const int cnt = total - o < 4 ? (int)(total - o) : 4;
-    for (int k = 0; k < cnt; k++) {
-        const size_t b = o + k, i = b / 81, r = b - 81 * i;
-        if (r < 49) v |= (u32)aggs[49 * i + 32 * (size_t)map[i] + r] << (8 * k);
-    }
-    if (cnt == 4) {
-        reinterpret_cast<u32 *>(sigs_out)[d] = v;
-    } else {
-        for (int k = 0; k < cnt; k++) sigs_out[o + k] = (u8)(v >> (8 * k));
-    }
-}
-
+// a_i = H(root_j || i - first_j || 0xA3) with the root and the index of the lane's own aggregate j = map[i]; map and
+// first == nullptr: one aggregate, root 0 and index i
 __global__ void __launch_bounds__(256, 4)
-ag_k_coeff(const DevParams *__restrict__ prm, const u64 *__restrict__ root, size_t n, u64 *__restrict__ coeffs) {
+ag_k_coeff(const DevParams *__restrict__ prm, const u64 *__restrict__ roots, const u32 *__restrict__ map,
+           const u32 *__restrict__ first, size_t n, u64 *__restrict__ coeffs) {
     __shared__ u64 lds[RS_LDS_U64];
     u64 *A = lds + threadIdx.x;
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    const u32 j = map ? map[i] : 0u;
     u64 in[8], d[4];
 #pragma unroll
-    for (int k = 0; k < 4; k++) in[k] = root[k];
-    in[4] = (u64)i;
+    for (int k = 0; k < 4; k++) in[k] = roots[4 * (size_t)j + k];
+    in[4] = (u64)(i - (first ? first[j] : 0u));
     in[5] = AG_TAG_COEFF;
     in[6] = in[7] = 0;
     ag_hash8(A, prm, in, 6u, d);
@@ -304,26 +298,26 @@ ag_k_coeff(const DevParams *__restrict__ prm, const u64 *__restrict__ root, size
     reinterpret_cast<ulonglong2 *>(coeffs)[i] = make_ulonglong2(lo, hi);
 }
 
-// ag_k_coeff with the root and the index of the lane's own aggregate: a_i = H(root_j || i - first_j || 0xA3)
-__global__ void __launch_bounds__(256, 4)
-ag_k_coeff_many(const DevParams *__restrict__ prm, const u64 *__restrict__ roots, const u32 *__restrict__ map,
-                const u32 *__restrict__ first, size_t n, u64 *__restrict__ coeffs) {
-    __shared__ u64 lds[RS_LDS_U64];
-    u64 *A = lds + threadIdx.x;
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const u32 j = map[i];
-    u64 in[8], d[4];
+// The sum mod q of one scalar per lane of a workgroup of 256, through red (256 x 4 words): red[0, 4) holds it once the
+// call returns.
+SSA_DEV void ag_block_sum(u64 *red, const sc256 &v) {
 #pragma unroll
-    for (int k = 0; k < 4; k++) in[k] = roots[4 * (size_t)j + k];
-    in[4] = (u64)(i - first[j]);
-    in[5] = AG_TAG_COEFF;
-    in[6] = in[7] = 0;
-    ag_hash8(A, prm, in, 6u, d);
-    u64 lo = d[0];
-    const u64 hi = d[1] & AG_COEFF_HI_MASK;
-    if ((lo | hi) == 0) lo = 1;
-    reinterpret_cast<ulonglong2 *>(coeffs)[i] = make_ulonglong2(lo, hi);
+    for (int k = 0; k < 4; k++) red[threadIdx.x * 4 + k] = v.w[k];
+    __syncthreads();
+    for (u32 stride = 128; stride > 0; stride >>= 1) {
+        if (threadIdx.x < stride) {
+            sc256 a, b;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                a.w[k] = red[threadIdx.x * 4 + k];
+                b.w[k] = red[(threadIdx.x + stride) * 4 + k];
+            }
+            a = sc_add_mod(a, b);
+#pragma unroll
+            for (int k = 0; k < 4; k++) red[threadIdx.x * 4 + k] = a.w[k];
+        }
+        __syncthreads();
+    }
 }
 
 // partials[b] = sum over the lanes of workgroup b of a_i e_i mod q.  status != nullptr: the checks of msm_k_prepare too --
@@ -359,23 +353,7 @@ ag_k_fold(const u8 *__restrict__ sigs, const u8 *__restrict__ pks, const u8 *__r
             ae = sc_mul_mod(a, e);
         }
     }
-#pragma unroll
-    for (int k = 0; k < 4; k++) red[threadIdx.x * 4 + k] = ae.w[k];
-    __syncthreads();
-    for (u32 stride = 128; stride > 0; stride >>= 1) {
-        if (threadIdx.x < stride) {
-            sc256 a, b;
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                a.w[k] = red[threadIdx.x * 4 + k];
-                b.w[k] = red[(threadIdx.x + stride) * 4 + k];
-            }
-            a = sc_add_mod(a, b);
-#pragma unroll
-            for (int k = 0; k < 4; k++) red[threadIdx.x * 4 + k] = a.w[k];
-        }
-        __syncthreads();
-    }
+    ag_block_sum(red, ae);
     if (threadIdx.x == 0) {
 #pragma unroll
         for (int k = 0; k < 4; k++) partials[4 * (size_t)blockIdx.x + k] = red[k];
@@ -396,33 +374,8 @@ ag_k_fold_finish(const u64 *__restrict__ partials, u32 n_partials, u8 *__restric
         for (int k = 0; k < 4; k++) p.w[k] = partials[4 * (size_t)b + k];
         acc = sc_add_mod(acc, p);
     }
-#pragma unroll
-    for (int k = 0; k < 4; k++) red[threadIdx.x * 4 + k] = acc.w[k];
-    __syncthreads();
-    for (u32 stride = 128; stride > 0; stride >>= 1) {
-        if (threadIdx.x < stride) {
-            sc256 a, b;
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                a.w[k] = red[threadIdx.x * 4 + k];
-                b.w[k] = red[(threadIdx.x + stride) * 4 + k];
-            }
-            a = sc_add_mod(a, b);
-#pragma unroll
-            for (int k = 0; k < 4; k++) red[threadIdx.x * 4 + k] = a.w[k];
-        }
-        __syncthreads();
-    }
+    ag_block_sum(red, acc);
     if (threadIdx.x < 32) e_out[threadIdx.x] = (u8)(red[threadIdx.x >> 3] >> (8 * (threadIdx.x & 7u)));
-}
-
-// the empty aggregate (n == 0): valid iff its 32 bytes are zero
-__global__ void __launch_bounds__(64)
-ag_k_empty(const u8 *__restrict__ e_agg, u32 *__restrict__ verdict) {
-    if (threadIdx.x != 0) return;
-    const sc256 e = ld_sc(e_agg);
-    const bool zero = (e.w[0] | e.w[1] | e.w[2] | e.w[3]) == 0;
-    *verdict = zero ? ST_OK : (sc_geq_q(e) ? ST_MALFORMED : ST_INVALID_SIG);
 }
 
 // ONE wave.  rec: the 24-word record of the MSM over the aggregate's R's with e = 0 -- the left-hand point
@@ -487,22 +440,16 @@ SSA_DEV void ag_finish_wave(CoopLds &L, const u64 *__restrict__ rec, const u8 *_
     if (lane == 0) *verdict = eq ? ST_OK : ST_INVALID_SIG;
 }
 
+// One wave per aggregate: block s compares recs[s], the record of aggregate j = agg0 + s (the small path: the sum of its
+// lanes' records), with [e_agg_j]G for that aggregate's own scalar.  first == nullptr: one aggregate of n lanes.  The empty
+// aggregate has no record: it is valid iff its 32 bytes are zero.
 __global__ void __launch_bounds__(64)
-ag_k_finish(const u64 *__restrict__ rec, const u8 *__restrict__ e_agg, const u64 *__restrict__ gtab,
-            u32 *__restrict__ verdict) {
-    __shared__ CoopLds L;
-    ag_finish_wave(L, rec, e_agg, gtab, verdict);
-}
-
-// The small path's finish, one wave per aggregate of a group: block s compares recs[s], the sum of the records of
-// aggregate agg0 + s, with [e_agg]G for that aggregate's own scalar; an empty aggregate follows ag_k_empty's rule.
-__global__ void __launch_bounds__(64)
-ag_k_finish_many(const u64 *__restrict__ recs, const u8 *__restrict__ aggs, const u32 *__restrict__ first, u32 agg0,
-                 const u64 *__restrict__ gtab, u32 *__restrict__ verdicts) {
+ag_k_finish(const u64 *__restrict__ recs, const u8 *__restrict__ aggs, const u32 *__restrict__ first, size_t n, u32 agg0,
+            const u64 *__restrict__ gtab, u32 *__restrict__ verdicts) {
     __shared__ CoopLds L;
     const u32 j = agg0 + blockIdx.x;
-    const u8 *e_agg = aggs + 49 * (size_t)first[j + 1] + 32 * (size_t)j;
-    if (first[j + 1] == first[j]) {                   // (block-uniform)
+    const u8 *e_agg = aggs + ag_wire_e(first, j, n);
+    if (first ? first[j + 1] == first[j] : n == 0) {  // (block-uniform)
         if (threadIdx.x == 0) {
             const sc256 e = ld_sc(e_agg);
             const bool zero = (e.w[0] | e.w[1] | e.w[2] | e.w[3]) == 0;
@@ -527,7 +474,7 @@ ag_k_gather_rs(const u8 *__restrict__ aggs, const u32 *__restrict__ first, u32 a
         const size_t b = o + k, p = b / 81, r = b - 81 * p;
         if (r >= 49) continue;
         const u32 j = agg0 + (u32)(p / seg_lanes), l = (u32)(p % seg_lanes);
-        if (l < first[j + 1] - first[j]) v |= (u32)aggs[49 * ((size_t)first[j] + l) + 32 * (size_t)j + r] << (8 * k);
+        if (l < first[j + 1] - first[j]) v |= (u32)aggs[ag_wire_r((size_t)first[j] + l, j) + r] << (8 * k);
     }
     reinterpret_cast<u32 *>(sigs_out)[d] = v;
 }
@@ -543,7 +490,7 @@ ag_k_gather(const u8 *__restrict__ aggs, const u32 *__restrict__ first, u32 agg0
     if (p >= total) return;
     if (p < 32 * (size_t)segs) {
         const u32 j = agg0 + (u32)(p >> 5);
-        g_rhs[p] = aggs[49 * (size_t)first[j + 1] + 32 * (size_t)j + (p & 31u)];
+        g_rhs[p] = aggs[ag_wire_e(first, j, 0) + (p & 31u)];
     }
     const u32 j = agg0 + (u32)(p / seg_lanes), l = (u32)(p % seg_lanes);
     const bool real = l < first[j + 1] - first[j];

@@ -1848,49 +1848,82 @@ extern "C" int ssa_multi_verify_batch_msm(ssa_multi *m, const uint8_t *sigs, con
 }
 
 // ------------------------------------------------------------------ half-aggregation (ssa_aggregate.hpp)
-// ctx->ag_misc: the transcript's root, the MSM's record, e_agg, the rejection counter of the unchecked form
-constexpr size_t AG_ROOT = 0, AG_REC = 64, AG_E = 256, AG_MISC_BYTES = 512;
+// ctx->ag_misc: the MSM's record and e_agg of the single-aggregate calls
+constexpr size_t AG_REC = 0, AG_E = 256, AG_MISC_BYTES = 512;
 static inline u8 *ag_misc(ssa_ctx *ctx, size_t off) { return (u8 *)ctx->ag_misc.p + off; }
 
-// The coefficients a_i of n lanes whose R's stand at stride 81 in b.sigs into ctx->ag_coeffs (n x 16 bytes), on
-// ctx->stream.  with_h: the same launch of ssa_k_hash leaves the challenge scalars mod q in ctx->ws_h.
-static int agg_coefficients(ssa_ctx *ctx, const DevBatch &b, size_t n, bool with_h) {
-    const size_t g1 = (n + AG_TREE_SPAN - 1) / AG_TREE_SPAN;
-    if (ctx->ag_dig.reserve(n * 32) || ctx->ag_nodes.reserve(n * 32) || ctx->ag_nodes2.reserve(g1 * 32) ||
-        ctx->ag_coeffs.reserve(n * 16) || ctx->ag_misc.reserve(AG_MISC_BYTES) || (with_h && ctx->ws_h.reserve(n * 32)))
+// One pass of the tree as ag_transcript launches it: `count` workgroups that follow the plan's descriptors at byte desc_off
+// of ctx->agm_plan; or, desc_off == AG_UNIFORM, the uniform cut of the count nodes of ONE aggregate, top_n its n on the
+// pass of one workgroup and 0 before.
+constexpr size_t AG_UNIFORM = ~(size_t)0;
+struct AgPass {
+    size_t desc_off;
+    u32 count, top_n;
+    unsigned groups() const { return desc_off == AG_UNIFORM ? (count + AG_TREE_SPAN - 1) / AG_TREE_SPAN : count; }
+};
+// the passes of one aggregate of n (>= 1) lanes: nothing to upload
+static std::vector<AgPass> ag_uniform_passes(size_t n) {
+    std::vector<AgPass> passes;
+    for (size_t count = n;; count = passes.back().groups()) {
+        const bool top = count <= AG_TREE_SPAN;
+        passes.push_back({AG_UNIFORM, (u32)count, top ? (u32)n : 0u});
+        if (top) return passes;
+    }
+}
+
+// The transcript over the n (>= 1) lanes of a call, on ctx->stream: the coefficients a_i into ctx->ag_coeffs (n x 16
+// bytes).  d_first: the k + 1 prefix sums of an uploaded plan (agm_upload_plan, `passes` from it); nullptr: one aggregate,
+// no plan, no lane map (passes from ag_uniform_passes).  d_wire != nullptr: the R's come out of the wire form and are
+// laid out at stride 81 in ctx->ag_sigs first; else they stand so in d_sigs.  with_h: the same launch of ssa_k_hash
+// leaves the challenge scalars mod q in ctx->ws_h.  One launch per stage and tree pass.
+static int ag_transcript(ssa_ctx *ctx, const u8 *d_wire, const u8 *d_sigs, const u8 *d_pks, const MsgView &mv, size_t n,
+                         bool with_h, const u32 *d_first, size_t k, const std::vector<AgPass> &passes) {
+    size_t widest = 1;                  // nodes a pass writes (a top workgroup writes a root instead)
+    for (const AgPass &p : passes) widest = std::max(widest, (size_t)p.groups());
+    if ((d_wire && ctx->ag_sigs.reserve(n * 81 + 16)) || (d_first && ctx->agm_map.reserve(n * 4)) ||
+        ctx->agm_roots.reserve(k * 32) || ctx->ag_dig.reserve(n * 32) || ctx->ag_nodes.reserve(std::max(n, widest) * 32) ||
+        ctx->ag_nodes2.reserve(widest * 32) || ctx->ag_coeffs.reserve(n * 16) || (with_h && ctx->ws_h.reserve(n * 32)))
         return SSA_ERR_HIP;
-    int rc = timed_launch(ctx, "ssa_k_hash", [&] {
-        hipLaunchKernelGGL(ssa_k_hash, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, ctx->d_params, b.sigs, b.pks,
-                           b.msgs, n, with_h ? (u64 *)ctx->ws_h.p : (u64 *)nullptr, (u8 *)ctx->ag_dig.p,
-                           (const u32 *)nullptr, 0u);
+    const u32 *d_map = d_first ? (const u32 *)ctx->agm_map.p : nullptr;
+    int rc = 0;
+    if (d_wire) {
+        rc = timed_launch(ctx, d_first ? "ag_k_expand_many" : "ag_k_expand", [&] {
+            if (d_first)
+                hipLaunchKernelGGL(ag_k_lane_map, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, d_first, (u32)k, n,
+                                   (u32 *)ctx->agm_map.p);
+            hipLaunchKernelGGL(ag_k_expand, dim3(grid_for((n * 81 + 3) / 4, 256)), dim3(256), 0, ctx->stream, d_wire, d_map, n,
+                               (u8 *)ctx->ag_sigs.p);
+        });
+        if (rc) return rc;
+        d_sigs = (const u8 *)ctx->ag_sigs.p;
+    }
+    rc = timed_launch(ctx, "ssa_k_hash", [&] {
+        hipLaunchKernelGGL(ssa_k_hash, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, ctx->d_params, d_sigs, d_pks, mv, n,
+                           with_h ? (u64 *)ctx->ws_h.p : (u64 *)nullptr, (u8 *)ctx->ag_dig.p, (const u32 *)nullptr, 0u);
     });
     if (rc) return rc;
     rc = timed_launch(ctx, "ag_k_leaf", [&] {
         hipLaunchKernelGGL(ag_k_leaf, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, ctx->d_params,
-                           (const u64 *)ctx->ag_dig.p, b.sigs, n, (u64 *)ctx->ag_nodes.p);
+                           (const u64 *)ctx->ag_dig.p, d_sigs, n, (u64 *)ctx->ag_nodes.p);
     });
     if (rc) return rc;
-    // passes of AG_TREE_LEVELS levels between the two node buffers; the pass of one workgroup also hashes the root
+    // passes of AG_TREE_LEVELS levels between the two node buffers; a top workgroup writes its aggregate's root instead
     rc = timed_launch(ctx, "ag_k_tree", [&] {
         const u64 *in = (const u64 *)ctx->ag_nodes.p;
         u64 *ping = (u64 *)ctx->ag_nodes2.p, *pong = (u64 *)ctx->ag_nodes.p;
-        size_t count = n;
-        for (;;) {
-            const size_t g = (count + AG_TREE_SPAN - 1) / AG_TREE_SPAN;
-            const bool top = g == 1;
-            u64 *out = top ? (u64 *)ag_misc(ctx, AG_ROOT) : ping;
-            hipLaunchKernelGGL(ag_k_tree, dim3((unsigned)g), dim3(256), 0, ctx->stream, ctx->d_params, in, (u32)count,
-                               (u64)n, top ? 1u : 0u, out);
-            if (top) break;
-            in = out;
+        for (const AgPass &p : passes) {
+            const AgTreeDesc *desc =
+                p.desc_off == AG_UNIFORM ? nullptr : (const AgTreeDesc *)((const u8 *)ctx->agm_plan.p + p.desc_off);
+            hipLaunchKernelGGL(ag_k_tree, dim3(p.groups()), dim3(256), 0, ctx->stream, ctx->d_params, in, desc, p.count,
+                               p.top_n, ping, (u64 *)ctx->agm_roots.p);
+            in = ping;
             std::swap(ping, pong);
-            count = g;
         }
     });
     if (rc) return rc;
     return timed_launch(ctx, "ag_k_coeff", [&] {
         hipLaunchKernelGGL(ag_k_coeff, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, ctx->d_params,
-                           (const u64 *)ag_misc(ctx, AG_ROOT), n, (u64 *)ctx->ag_coeffs.p);
+                           (const u64 *)ctx->agm_roots.p, d_map, d_first, n, (u64 *)ctx->ag_coeffs.p);
     });
 }
 
@@ -1920,9 +1953,9 @@ extern "C" int ssa_aggregate_many_device(ssa_ctx *ctx, const uint8_t *d_sigs, co
         if (int rc = ssa_verify_batch_screened_device(ctx, d_sigs, d_pks, d_pk_inf, d_msgs, d_msg_off, msg_stride, msg_len, n,
                                                       nullptr, 0, d_status, (uint64_t *)d_fail))
             return rc;
-    if (int rc = agg_coefficients(ctx, b, n, false)) return rc;
+    if (int rc = ag_transcript(ctx, nullptr, d_sigs, d_pks, b.msgs, n, false, nullptr, 1, ag_uniform_passes(n))) return rc;
     const unsigned n_blocks = grid_for(n, 256);
-    if (ctx->ag_partials.reserve((size_t)n_blocks * 32)) return SSA_ERR_HIP;
+    if (ctx->ag_partials.reserve((size_t)n_blocks * 32) || ctx->ag_misc.reserve(AG_MISC_BYTES)) return SSA_ERR_HIP;
     int rc = timed_launch(ctx, "ag_k_fold", [&] {
         hipLaunchKernelGGL(ag_k_fold, dim3(n_blocks), dim3(256), 0, ctx->stream, d_sigs, d_pks, d_pk_inf,
                            (const u64 *)ctx->ag_coeffs.p, n, (u64 *)ctx->ag_partials.p, screened ? (u8 *)nullptr : d_status,
@@ -1990,24 +2023,18 @@ extern "C" int ssa_verify_aggregate_device(ssa_ctx *ctx, const uint8_t *d_agg, c
     if (!ctx || !d_agg || !d_verdict_out || (n && !d_pks)) return SSA_ERR_ARG;
     if (int rc = agg_check_args(ctx, mv, n)) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
-    if (n == 0) {
-        hipLaunchKernelGGL(ag_k_empty, dim3(1), dim3(64), 0, ctx->stream, d_agg, d_verdict_out);
-        HIP_TRY(hipGetLastError());
-        return 0;
+    if (n) {
+        if (ctx->ag_misc.reserve(AG_MISC_BYTES)) return SSA_ERR_HIP;
+        if (int rc = ag_transcript(ctx, d_agg, nullptr, d_pks, mv, n, true, nullptr, 1, ag_uniform_passes(n))) return rc;
+        // the MSM of ssa_verify_batch_msm over (R_i, e = 0) with the transcript's coefficients, reduced to its record
+        const DevBatch b{(const u8 *)ctx->ag_sigs.p, d_pks, d_pk_inf, mv};
+        if (int rc = ssa_internal_msm_record(ctx, b, n, (const u8 *)ctx->ag_coeffs.p, 16, (const uint64_t *)ctx->ws_h.p,
+                                             (uint64_t *)ag_misc(ctx, AG_REC)))
+            return rc;
     }
-    if (ctx->ag_sigs.reserve(n * 81 + 16) || ctx->ag_misc.reserve(AG_MISC_BYTES)) return SSA_ERR_HIP;
-    hipLaunchKernelGGL(ag_k_expand, dim3(grid_for((n * 81 + 3) / 4, 256)), dim3(256), 0, ctx->stream, d_agg, n,
-                       (u8 *)ctx->ag_sigs.p);
-    HIP_TRY(hipGetLastError());
-    // the MSM of ssa_verify_batch_msm over (R_i, e = 0) with the transcript's coefficients, reduced to its record
-    const DevBatch b{(const u8 *)ctx->ag_sigs.p, d_pks, d_pk_inf, mv};
-    if (int rc = agg_coefficients(ctx, b, n, true)) return rc;
-    if (int rc = ssa_internal_msm_record(ctx, b, n, (const u8 *)ctx->ag_coeffs.p, 16, (const uint64_t *)ctx->ws_h.p,
-                                         (uint64_t *)ag_misc(ctx, AG_REC)))
-        return rc;
-    return timed_launch(ctx, "ag_k_finish", [&] {
-        hipLaunchKernelGGL(ag_k_finish, dim3(1), dim3(64), 0, ctx->stream, (const u64 *)ag_misc(ctx, AG_REC), d_agg + 49 * n,
-                           (const u64 *)ctx->d_gtab, d_verdict_out);
+    return timed_launch(ctx, "ag_k_finish", [&] {       // (the empty aggregate has no record: the kernel reads none)
+        hipLaunchKernelGGL(ag_k_finish, dim3(1), dim3(64), 0, ctx->stream, (const u64 *)ag_misc(ctx, AG_REC), d_agg,
+                           (const u32 *)nullptr, n, 0u, (const u64 *)ctx->d_gtab, d_verdict_out);
     });
 }
 
@@ -2032,69 +2059,21 @@ extern "C" int ssa_verify_aggregate(ssa_ctx *ctx, const uint8_t *agg, const uint
 // ------------------------------------------------------------------ many aggregates in one call
 // The plan on the device (ctx->agm_plan): k + 1 prefix sums, then the tree's descriptors pass after pass.  The host copy
 // lives in the context; the event says when the last upload has read it.
-static int agm_upload_plan(ssa_ctx *ctx, const AgPlan &pl, std::vector<size_t> &pass_off) {
+static int agm_upload_plan(ssa_ctx *ctx, const AgPlan &pl, std::vector<AgPass> &passes) {
     if (!ctx->agm_plan_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->agm_plan_ev, hipEventDisableTiming));
     else HIP_TRY(hipEventSynchronize(ctx->agm_plan_ev));
     std::vector<uint32_t> &h = ctx->agm_plan_host;
     h.assign(pl.first.begin(), pl.first.end());
     while (h.size() & 3u) h.push_back(0u);             // descriptors are four words: keep them 16-byte aligned
-    pass_off.clear();
+    passes.clear();
     for (const auto &pass : pl.passes) {
-        pass_off.push_back(h.size() * sizeof(uint32_t));
+        passes.push_back({h.size() * sizeof(uint32_t), (u32)pass.size(), 0u});
         for (const AgTreeDesc &d : pass) h.insert(h.end(), {d.first, d.count, d.slot, d.top_n});
     }
     if (ctx->agm_plan.reserve(h.size() * sizeof(uint32_t))) return SSA_ERR_HIP;
     HIP_TRY(hipMemcpyAsync(ctx->agm_plan.p, h.data(), h.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipEventRecord(ctx->agm_plan_ev, ctx->stream));
     return 0;
-}
-
-// The transcript of every aggregate over all n lanes at once: the R's at stride 81 into ctx->ag_sigs, the challenge
-// scalars into ctx->ws_h, the coefficients into ctx->ag_coeffs.  One launch per stage; the tree takes the passes of the
-// largest aggregate.
-static int agm_transcript(ssa_ctx *ctx, const AgPlan &pl, const std::vector<size_t> &pass_off, const uint8_t *d_aggs, size_t k,
-                          const uint8_t *d_pks, const uint8_t *d_pk_inf, const MsgView &mv, size_t n) {
-    size_t widest = 1;                  // nodes a pass writes (a top workgroup writes a root instead)
-    for (const auto &pass : pl.passes) widest = std::max(widest, pass.size());
-    if (ctx->ag_sigs.reserve(n * 81 + 16) || ctx->agm_map.reserve(n * 4) || ctx->agm_roots.reserve(k * 32) ||
-        ctx->ag_dig.reserve(n * 32) || ctx->ag_nodes.reserve(std::max(n, widest) * 32) || ctx->ag_nodes2.reserve(widest * 32) ||
-        ctx->ag_coeffs.reserve(n * 16) || ctx->ws_h.reserve(n * 32))
-        return SSA_ERR_HIP;
-    const u32 *d_first = (const u32 *)ctx->agm_plan.p;
-    const DevBatch b{(const u8 *)ctx->ag_sigs.p, d_pks, d_pk_inf, mv};
-    int rc = timed_launch(ctx, "ag_k_expand_many", [&] {
-        hipLaunchKernelGGL(ag_k_lane_map, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, d_first, (u32)k, n,
-                           (u32 *)ctx->agm_map.p);
-        hipLaunchKernelGGL(ag_k_expand_many, dim3(grid_for((n * 81 + 3) / 4, 256)), dim3(256), 0, ctx->stream, d_aggs,
-                           (const u32 *)ctx->agm_map.p, n, (u8 *)ctx->ag_sigs.p);
-    });
-    if (rc) return rc;
-    rc = timed_launch(ctx, "ssa_k_hash", [&] {
-        hipLaunchKernelGGL(ssa_k_hash, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, ctx->d_params, b.sigs, b.pks,
-                           b.msgs, n, (u64 *)ctx->ws_h.p, (u8 *)ctx->ag_dig.p, (const u32 *)nullptr, 0u);
-    });
-    if (rc) return rc;
-    rc = timed_launch(ctx, "ag_k_leaf", [&] {
-        hipLaunchKernelGGL(ag_k_leaf, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, ctx->d_params,
-                           (const u64 *)ctx->ag_dig.p, b.sigs, n, (u64 *)ctx->ag_nodes.p);
-    });
-    if (rc) return rc;
-    rc = timed_launch(ctx, "ag_k_tree", [&] {
-        const u64 *in = (const u64 *)ctx->ag_nodes.p;
-        u64 *ping = (u64 *)ctx->ag_nodes2.p, *pong = (u64 *)ctx->ag_nodes.p;
-        for (size_t p = 0; p < pl.passes.size(); p++) {
-            hipLaunchKernelGGL(ag_k_tree_seg, dim3((unsigned)pl.passes[p].size()), dim3(256), 0, ctx->stream, ctx->d_params,
-                               in, (const AgTreeDesc *)((const u8 *)ctx->agm_plan.p + pass_off[p]),
-                               (u32)pl.passes[p].size(), ping, (u64 *)ctx->agm_roots.p);
-            in = ping;
-            std::swap(ping, pong);
-        }
-    });
-    if (rc) return rc;
-    return timed_launch(ctx, "ag_k_coeff", [&] {
-        hipLaunchKernelGGL(ag_k_coeff_many, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, ctx->d_params,
-                           (const u64 *)ctx->agm_roots.p, (const u32 *)ctx->agm_map.p, d_first, n, (u64 *)ctx->ag_coeffs.p);
-    });
 }
 
 // arguments of both forms: the plan from the caller's counts; *n_out = the lanes in all
@@ -2113,12 +2092,13 @@ static int agm_check_args(const ssa_ctx *ctx, const void *aggs, const uint64_t *
 static int agm_run(ssa_ctx *ctx, const AgPlan &pl, const uint8_t *d_aggs, size_t k, const uint8_t *d_pks,
                    const uint8_t *d_pk_inf, const MsgView &mv, size_t n, uint32_t *d_verdicts_out) {
     HIP_TRY(hipSetDevice(ctx->device));
-    std::vector<size_t> pass_off;
-    if (int rc = agm_upload_plan(ctx, pl, pass_off)) return rc;
-    if (n)
-        if (int rc = agm_transcript(ctx, pl, pass_off, d_aggs, k, d_pks, d_pk_inf, mv, n)) return rc;
-    if (!d_verdicts_out) return 0;       // (ssa_debug_aggregates_many_coeffs: the transcript alone)
+    std::vector<AgPass> passes;
+    if (int rc = agm_upload_plan(ctx, pl, passes)) return rc;
     const u32 *d_first = (const u32 *)ctx->agm_plan.p;
+    // the R's at stride 81 into ctx->ag_sigs, the challenge scalars into ctx->ws_h, the coefficients into ctx->ag_coeffs
+    if (n)
+        if (int rc = ag_transcript(ctx, d_aggs, nullptr, d_pks, mv, n, true, d_first, k, passes)) return rc;
+    if (!d_verdicts_out) return 0;       // (ssa_debug_aggregates_many_coeffs: the transcript alone)
     const DevBatch b{(const u8 *)ctx->ag_sigs.p, d_pks, d_pk_inf, mv};
     for (const AgGroup &g : pl.groups) {
         if (!g.bucket) {
@@ -2128,8 +2108,8 @@ static int agm_run(ssa_ctx *ctx, const AgPlan &pl, const uint8_t *d_aggs, size_t
                                                     g.aggs, &d_recs))
                 return rc;
             const int rc = timed_launch(ctx, "ag_k_finish", [&] {
-                hipLaunchKernelGGL(ag_k_finish_many, dim3(g.aggs), dim3(64), 0, ctx->stream, (const u64 *)d_recs, d_aggs,
-                                   d_first, g.agg0, (const u64 *)ctx->d_gtab, d_verdicts_out);
+                hipLaunchKernelGGL(ag_k_finish, dim3(g.aggs), dim3(64), 0, ctx->stream, (const u64 *)d_recs, d_aggs, d_first,
+                                   (size_t)0, g.agg0, (const u64 *)ctx->d_gtab, d_verdicts_out);
             });
             if (rc) return rc;
             continue;
@@ -2239,13 +2219,9 @@ extern "C" int ssa_debug_aggregate_coeffs(ssa_ctx *ctx, const uint8_t *rs49, con
     HostCall hc(ctx);
     const u8 *d_rs = hc.in(ctx->st_sigs, rs49, n * 49), *d_pks = hc.in(ctx->st_pks, pks, n * 96);
     const MsgView mv = hc.msgs(msgs, msg_off, msg_stride, msg_len, n);
-    u8 *d_sigs = hc.out(ctx->ag_sigs, nullptr, n * 81, 16);
     (void)hc.out(ctx->ag_coeffs, coeffs16_out, n * 16);
-    return hc.finish([&] {
-        hipLaunchKernelGGL(ag_k_expand, dim3(grid_for((n * 81 + 3) / 4, 256)), dim3(256), 0, ctx->stream, d_rs, n, d_sigs);
-        HIP_TRY(hipGetLastError());
-        return agg_coefficients(ctx, {d_sigs, d_pks, nullptr, mv}, n, false);
-    });
+    // (n R's side by side are the wire form of one aggregate, short of its scalar)
+    return hc.finish([&] { return ag_transcript(ctx, d_rs, nullptr, d_pks, mv, n, false, nullptr, 1, ag_uniform_passes(n)); });
 }
 
 // ------------------------------------------------------------------ probes

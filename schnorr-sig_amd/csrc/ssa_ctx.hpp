@@ -177,11 +177,12 @@ struct CtxKnobs {
     X(rng_seed) X(rng_scratch) \
     /* half-aggregation (ssa_aggregate.hpp): the aggregate's R's at stride 81, the raw challenge \
        digests, the tree's nodes (two buffers, passes alternate), the coefficients a_i, the fold's partial sums, a status \
-       byte per lane, and one small block: root, MSM record, e_agg, rejection counter, verdict */ \
+       byte per lane, and one small block: MSM record and e_agg of the single calls */ \
     X(ag_sigs) X(ag_dig) X(ag_nodes) X(ag_nodes2) X(ag_coeffs) X(ag_partials) X(ag_status) X(ag_misc) \
     /* many aggregates in one call: the plan (prefix sums, then the tree's descriptors), each \
-       lane's aggregate, one root per aggregate, and a padded group of the bucket path: its inputs (R's, keys, flags, \
-       challenge scalars, coefficients) and its bytes (mask, re-check marks, segment verdicts, right-hand scalars) */ \
+       lane's aggregate, one root per aggregate (the single calls': slot 0), and a padded group of the bucket path: its \
+       inputs (R's, keys, flags, challenge scalars, coefficients) and its bytes (mask, re-check marks, segment verdicts, \
+       right-hand scalars) */ \
     X(agm_plan) X(agm_map) X(agm_roots) X(agm_in) X(agm_bytes) \
     /* the end game of ssa_k_verify, per tail group: finished pieces; parked accumulators + status (152 B per lane) */ \
     X(tail_done) X(tail_park)

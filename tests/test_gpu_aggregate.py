@@ -73,6 +73,24 @@ def test_coefficients_are_the_models_byte_for_byte(engine, case, n):
     assert (got[:, 15] < 0x40).all()                                      # 126 bits
 
 
+@pytest.mark.parametrize("n", [1, 2, 512, 513, 262145])
+def test_null_plan_and_uploaded_plan_give_the_same_coefficients(engine, n):
+    """One, two and three passes of the tree (262 145 = 512^2 + 1 is the smallest n with three): the single call forms
+    its descriptors in the kernel, the many-call of ONE aggregate reads them from the uploaded plan.  Same kernels,
+    same bytes; the test above ties the first to the model."""
+    rng = np.random.default_rng(0xA6600 + n)
+    msgs = rng.integers(0, 256, size=(n, 80), dtype=np.uint8)
+    pks, sigs = engine.keygen_sign_many(make_scalars(rng, n), make_scalars(rng, n), msgs)
+    rs = np.ascontiguousarray(sigs[:, :49])
+    agg = np.concatenate([rs.reshape(-1), np.zeros(32, np.uint8)])       # (the transcript does not read e_agg)
+    null_plan = engine.aggregate_coeffs(rs, pks, msgs)
+    uploaded = engine.aggregates_coeffs([agg], pks, msgs)
+    assert null_plan.shape == uploaded.shape == (n, 16)
+    bad = np.nonzero((null_plan != uploaded).any(axis=1))[0]
+    assert bad.size == 0, (bad[:8], null_plan[bad[:2]], uploaded[bad[:2]])
+    assert null_plan.any(axis=1).all()                                     # no coefficient is 0
+
+
 @pytest.mark.parametrize("n", SIZES)
 def test_aggregate_bytes(engine, case, n):
     c = case(n)

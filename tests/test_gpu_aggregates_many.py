@@ -142,6 +142,14 @@ def test_boundary_sizes_in_one_call(engine, engines, oracle, pool, path):
         lo, hi = rg[j]
         alone = engine.aggregate_coeffs(aggs[j][:-32], pool.pks[lo:hi], pool.msgs[lo:hi])
         assert (co[lo:hi] == alone).all(), j
+    # and the model's, for EVERY aggregate of the pool: the single call runs the same transcript kernels, the model does not
+    if "boundary_coeffs" not in _STATE:
+        be = am.oracle_backend(oracle)
+        _STATE["boundary_coeffs"] = [am.coeff_bytes(am.coefficients(be, pool.sigs[lo:hi, :49], pool.pks[lo:hi], pool.msgs[lo:hi]))
+                                     if hi > lo else np.zeros((0, 16), np.uint8) for lo, hi in rg]
+    assert co.shape == (POOL, 16)
+    for j, (lo, hi) in enumerate(rg):
+        assert (co[lo:hi] == _STATE["boundary_coeffs"][j]).all(), j
 
 
 @pytest.mark.parametrize("path", PATHS)
