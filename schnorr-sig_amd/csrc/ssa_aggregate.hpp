@@ -380,8 +380,8 @@ ag_k_fold_finish(const u64 *__restrict__ partials, u32 n_partials, u8 *__restric
 
 // ONE wave.  rec: the 24-word record of the MSM over the aggregate's R's with e = 0 -- the left-hand point
 // sum a_i R_i - sum (a_i h_i) P_i in canonical form (affine (x, y, 1), or (0, 0, 0) for the identity), and the malformed
-// flag.  right = [e_agg]G from the comb (the walk of msm_k_finish's second wave, same slots); then the comparison of
-// msm_k_finish_seg: both coordinates, the identity equal to the identity only.
+// flag.  right = [e_agg]G from the comb (coop_comb_add), then the exact comparison (coop_jac_equal): what
+// msm_k_finish_seg does with a segment.
 SSA_DEV void ag_finish_wave(CoopLds &L, const u64 *__restrict__ rec, const u8 *__restrict__ e_agg,
                             const u64 *__restrict__ gtab, u32 *__restrict__ verdict) {
     const u32 lane = threadIdx.x;
@@ -391,52 +391,14 @@ SSA_DEV void ag_finish_wave(CoopLds &L, const u64 *__restrict__ rec, const u8 *_
         if (lane == 0) *verdict = ST_MALFORMED;
         return;
     }
-    // slots: left 0..2 (X, Y, Z); right accumulator 20..23, addend 24..25, scratch 26..34; comparison 7..10
+    // slots as msm_k_finish_seg: left 0..2 (X, Y, Z); right accumulator 20..23, addend 24..25, scratch 26..34; comparison 7..10
     int t[9];
 #pragma unroll
     for (int k = 0; k < 9; k++) t[k] = 26 + k;
-    if (lane < 36) {
-        const u32 v = lane / 12u, c = lane % 12u;
-        const u64 w = rec[6u * v + c % 6u];
-        L.slot[(int)v][c] = c < 6 ? w : fp_mul_small(w, 7u);
-    }
-    coop_sync();
-    coop_set(L, 20, 1ull, lane, ws);
-    coop_set(L, 21, 1ull, lane, ws);
-    coop_set(L, 22, 0ull, lane, ws);
-    coop_set(L, 23, 0ull, lane, ws);
-    const GtabGeom gg = gtab_geom(gtab);
-#pragma unroll 1
-    for (u32 w = 0; w < gg.count; w++) {              // BASEPOINT_TABLE.multiply_vartime
-        const u32 d = sc_bits(e, w * gg.bits, gg.bits);
-        if (d != 0) {
-            const u64 *rowp = gtab + (((size_t)w << gg.bits) + d) * 12;
-            if (lane < 24) {
-                const u32 half = lane / 12u, c = lane % 12u;
-                const u64 v = rowp[6u * half + c % 6u];
-                L.slot[half ? 25 : 24][c] = c < 6 ? v : fp_mul_small(v, 7u);
-            }
-            coop_sync();
-            coop_jac_madd(L, 20, 24, 25, t, lane, ws);
-        }
-    }
-    // X_l Z_r^2 == X_r Z_l^2 and Y_l Z_r^3 == Y_r Z_l^3 (X_r and Y_r only as first operands: their 7x halves may be stale)
-    const bool li = coop_is_zero(L, 2, lane, ws), ri = coop_is_zero(L, 22, lane, ws);
-    bool eq;
-    if (li || ri) {
-        eq = li && ri;
-    } else {
-        coop_mul(L, 7, 22, 22, lane, ws);      // Z_r^2
-        coop_mul(L, 8, 0, 7, lane, ws);        // X_l Z_r^2
-        coop_mul(L, 9, 2, 2, lane, ws);        // Z_l^2
-        coop_mul(L, 10, 20, 9, lane, ws);      // X_r Z_l^2
-        eq = coop_eq(L, 8, 10, lane, ws);
-        coop_mul(L, 7, 7, 22, lane, ws);       // Z_r^3
-        coop_mul(L, 8, 1, 7, lane, ws);        // Y_l Z_r^3
-        coop_mul(L, 9, 9, 2, lane, ws);        // Z_l^3
-        coop_mul(L, 10, 21, 9, lane, ws);      // Y_r Z_l^3
-        eq = eq && coop_eq(L, 8, 10, lane, ws);
-    }
+    coop_load_jac(L, 0, rec, lane);
+    coop_set_identity(L, 20, lane, ws);
+    coop_comb_add(L, 20, 24, 25, e, gtab, t, lane, ws);
+    const bool eq = coop_jac_equal(L, 0, 20, 7, lane, ws);
     if (lane == 0) *verdict = eq ? ST_OK : ST_INVALID_SIG;
 }
 

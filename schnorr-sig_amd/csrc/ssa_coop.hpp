@@ -405,6 +405,116 @@ COOP_FN void coop_jac_add(CoopLds &L, int P1, int P2, const int *t, u32 lane, in
     coop_sync();
 }
 
+// ---- the finish steps of every batch form: sum points, walk the comb, compare (one wave each) ----
+// X, Y, Z at src[0..17] -> slots s0 .. s0 + 2 with their 7x halves
+COOP_FN void coop_load_jac(CoopLds &L, int s0, const u64 *__restrict__ src, u32 lane) {
+    if (lane < 36) {
+        const u32 v = lane / 12u, c = lane % 12u;
+        const u64 w = src[6u * v + c % 6u];
+        L.slot[s0 + (int)v][c] = c < 6 ? w : fp_mul_small(w, 7u);
+    }
+    coop_sync();
+}
+
+// acc (four slots, W = Z^4) <- point 0, then for j = 1 .. count - 1: `dbl` doublings and + point j (through the three
+// slots at `addend`).  dbl = 0 is the plain sum, dbl = c Horner's rule over c-bit windows.  fetch(j) -> the 18 words of
+// point j in the caller's own order.  The order of the additions fixes the Jacobian representative of the result: keep it.
+template <typename Fetch>
+COOP_FN void coop_sum_points(CoopLds &L, int acc, int addend, const int *t, u32 lane, int ws, u32 count, u32 dbl,
+                             Fetch fetch) {
+    coop_load_jac(L, acc, fetch(0u), lane);
+    coop_mul(L, acc + 3, acc + 2, acc + 2, lane, ws);
+    coop_mul(L, acc + 3, acc + 3, acc + 3, lane, ws);
+#pragma unroll 1
+    for (u32 j = 1; j < count; j++) {
+#pragma unroll 1
+        for (u32 d = 0; d < dbl; d++) coop_jac_dbl(L, acc, t, lane, ws);
+        coop_load_jac(L, addend, fetch(j), lane);
+        coop_jac_add(L, acc, addend, t, lane, ws);
+    }
+}
+
+COOP_FN void coop_set_identity(CoopLds &L, int acc, u32 lane, int ws) {   // (1, 1, 0, 0)
+    coop_set(L, acc, 1ull, lane, ws);
+    coop_set(L, acc + 1, 1ull, lane, ws);
+    coop_set(L, acc + 2, 0ull, lane, ws);
+    coop_set(L, acc + 3, 0ull, lane, ws);
+}
+
+// acc += [k] G from the comb table (BASEPOINT_TABLE.multiply_vartime): per window with a nonzero digit the table's row
+// is staged in slots qx, qy with its 7x halves (lanes 0..11: x, 7x; lanes 12..23: y, 7y) and added; t[0..8] scratch
+COOP_FN void coop_comb_add(CoopLds &L, int acc, int qx, int qy, const sc256 &k, const u64 *__restrict__ gtab,
+                           const int *t, u32 lane, int ws) {
+    const GtabGeom gg = gtab_geom(gtab);
+#pragma unroll 1
+    for (u32 w = 0; w < gg.count; w++) {
+        const u32 d = sc_bits(k, w * gg.bits, gg.bits);
+        if (d != 0) {
+            const u64 *rowp = gtab + (((size_t)w << gg.bits) + d) * 12;
+            if (lane < 24) {
+                const u32 half = lane / 12u, c = lane % 12u;
+                const u64 v = rowp[6u * half + c % 6u];
+                L.slot[half ? qy : qx][c] = c < 6 ? v : fp_mul_small(v, 7u);
+            }
+            coop_sync();
+            coop_jac_madd(L, acc, qx, qy, t, lane, ws);
+        }
+    }
+}
+
+// The exact comparison of two Jacobian points at slots l .. l + 2 and r .. r + 2 (s .. s + 3 scratch):
+// X_l Z_r^2 == X_r Z_l^2 and Y_l Z_r^3 == Y_r Z_l^3, the identity (Z = 0) equal to the identity only.  X and Y enter
+// only as FIRST operands: their 7x halves may be stale.
+COOP_FN bool coop_jac_equal(CoopLds &L, int l, int r, int s, u32 lane, int ws) {
+    const bool li = coop_is_zero(L, l + 2, lane, ws), ri = coop_is_zero(L, r + 2, lane, ws);
+    if (li || ri) return li && ri;
+    coop_mul(L, s, r + 2, r + 2, lane, ws);          // Z_r^2
+    coop_mul(L, s + 1, l, s, lane, ws);              // X_l Z_r^2
+    coop_mul(L, s + 2, l + 2, l + 2, lane, ws);      // Z_l^2
+    coop_mul(L, s + 3, r, s + 2, lane, ws);          // X_r Z_l^2
+    const bool eq = coop_eq(L, s + 1, s + 3, lane, ws);
+    coop_mul(L, s, s, r + 2, lane, ws);              // Z_r^3
+    coop_mul(L, s + 1, l + 1, s, lane, ws);          // Y_l Z_r^3
+    coop_mul(L, s + 2, s + 2, l + 2, lane, ws);      // Z_l^3
+    coop_mul(L, s + 3, r + 1, s + 2, lane, ws);      // Y_r Z_l^3
+    return eq && coop_eq(L, s + 1, s + 3, lane, ws);
+}
+
+// sum of the scalars partials[4 b .. 4 b + 3], b in [lo, hi), mod q, by one wave: a strided pass, then a tree in lin_sh
+COOP_FN sc256 wave_sum_mod_q(u64 (*lin_sh)[4], const u64 *__restrict__ partials, u32 lo, u32 hi, u32 lane) {
+    sc256 acc;
+#pragma unroll
+    for (int k = 0; k < 4; k++) acc.w[k] = 0;
+#pragma unroll 1
+    for (u32 b = lo + lane; b < hi; b += 64) {
+        sc256 p;
+#pragma unroll
+        for (int k = 0; k < 4; k++) p.w[k] = partials[4 * (size_t)b + k];
+        acc = sc_add_mod(acc, p);
+    }
+#pragma unroll
+    for (int k = 0; k < 4; k++) lin_sh[lane][k] = acc.w[k];
+    coop_sync();
+#pragma unroll 1
+    for (u32 stride = 32; stride >= 1; stride >>= 1) {
+        if (lane < stride) {
+            sc256 a, b;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                a.w[k] = lin_sh[lane][k];
+                b.w[k] = lin_sh[lane + stride][k];
+            }
+            a = sc_add_mod(a, b);
+#pragma unroll
+            for (int k = 0; k < 4; k++) lin_sh[lane][k] = a.w[k];
+        }
+        coop_sync();
+    }
+#pragma unroll
+    for (int k = 0; k < 4; k++) acc.w[k] = lin_sh[0][k];
+    return acc;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Signature::verify for ONE signature by ONE wave (reference src/signature.rs:181-205): the same
 // algorithm as ssa_k_hash + ssa_k_verify (affine table 1P..8P, signed 4-bit windows, comb for G,
@@ -686,9 +796,11 @@ COOP_FN u32 coop_verify_two_waves(CoopLds &L, CoopShared &sh, const DevParams *_
 #pragma unroll
             for (int k = 0; k < 4; k++) h.w[k] = sh.h[k];
             coop_mul_table(L, h, lane, ws);                               // [h]P
+            // + [e]G, src/signature.rs:196-198.  The walk of coop_comb_add, spelled out: this is the one user on a throughput
+            // path, and through the call ssa_k_verify_coop did not keep its time at 1024 signatures (profiles/r17/README.md)
             const GtabGeom gg = gtab_geom(gtab);
 #pragma unroll 1
-            for (u32 w = 0; w < gg.count; w++) {                          // + [e]G, src/signature.rs:196-198
+            for (u32 w = 0; w < gg.count; w++) {
                 const u32 d = sc_bits(e, w * gg.bits, gg.bits);
                 if (d != 0) {
                     const u64 *rowp = gtab + (((size_t)w << gg.bits) + d) * 12;

@@ -544,22 +544,7 @@ msm_k_tree(const u64 *__restrict__ in, u32 windows, u32 count, u32 group, u64 *_
 #pragma unroll
     for (int k = 0; k < 9; k++) tt[k] = 7 + k;
     // accumulator 0..3 (X, Y, Z, W = Z^4), addend 4..6
-    auto load = [&](int s0, u32 k) {
-        if (lane < 36) {
-            const u32 v = lane / 12u, c = lane % 12u;
-            const u64 w = in[18 * ((size_t)j * count + k) + 6u * v + c % 6u];
-            L.slot[s0 + (int)v][c] = c < 6 ? w : fp_mul_small(w, 7u);
-        }
-        coop_sync();
-    };
-    load(0, lo);
-    coop_mul(L, 3, 2, 2, lane, 0);
-    coop_mul(L, 3, 3, 3, lane, 0);
-#pragma unroll 1
-    for (u32 k = lo + 1; k < hi; k++) {
-        load(4, k);
-        coop_jac_add(L, 0, 4, tt, lane, 0);
-    }
+    coop_sum_points(L, 0, 4, tt, lane, 0, hi - lo, 0u, [&](u32 k) { return in + 18 * ((size_t)j * count + lo + k); });
     if (lane < 18) out[18 * (size_t)t + lane] = fp_canon(L.slot[(int)(lane / 6u)][lane % 6u]);
 }
 
@@ -601,6 +586,13 @@ msm_k_chacha20(ChaChaKey kn, u32 counter0, size_t n_blocks, u32 *__restrict__ ou
     for (int i = 0; i < 16; i++) out[16 * t + i] = x[i] + st[i];   // little-endian words = the keystream bytes
 }
 
+// A record that carries no point (include/schnorr_sig_amd.h, "shard records"): 24 words, all zero but the malformed flag
+// at word 22 and SSA_MSM_RECORD_MAGIC at word 23.  malformed = false is the record of an empty shard: the identity (Z = 0),
+// sum s_i e_i = 0 -- and the magic word: a buffer that nobody wrote (all zero) is NOT a record.  Called by whole blocks.
+SSA_DEV void msm_record_flag(u64 *__restrict__ rec, bool malformed) {
+    if (threadIdx.x < 24) rec[threadIdx.x] = threadIdx.x == 22 ? (u64)malformed : threadIdx.x == 23 ? SSA_MSM_RECORD_MAGIC : 0ull;
+}
+
 // ---- the one sequential chain of the reduction ---------------------------------------------------
 // left = sum_j 2^(c j) W_j by Horner's rule: (windows - 1) x (c doublings + one addition), a chain of ~240
 // dependent doublings.  A lone lane ran it at ~80 us per doubling; here wave 0 of the block works on the
@@ -619,12 +611,8 @@ msm_k_finish(const u64 *__restrict__ win_in, MsmShape sh, const u64 *__restrict_
     const u32 lane = threadIdx.x & 63u;
     const int ws = (int)(threadIdx.x >> 6);
     if (*malformed) {   // block-uniform
-        if (partial_out) {   // a whole, well-formed record: no word is left to whatever the buffer held before
-            if (threadIdx.x < 24)
-                partial_out[threadIdx.x] = threadIdx.x == 22 ? 1ull : threadIdx.x == 23 ? SSA_MSM_RECORD_MAGIC : 0ull;
-        } else if (threadIdx.x == 0) {
-            *verdict = ST_MALFORMED;
-        }
+        if (partial_out) msm_record_flag(partial_out, true);
+        else if (threadIdx.x == 0) *verdict = ST_MALFORMED;
         return;
     }
     // slots: wave 0 accumulator 0..3 (X, Y, Z, W), addend 4..6, scratch 7..15; wave 1 accumulator 20..23,
@@ -632,76 +620,16 @@ msm_k_finish(const u64 *__restrict__ win_in, MsmShape sh, const u64 *__restrict_
     int t[9];
 #pragma unroll
     for (int k = 0; k < 9; k++) t[k] = (ws ? 26 : 7) + k;
-    if (ws == 0) {
-        auto load = [&](int s0, u32 j) {   // X, Y, Z of window j with their 7x halves
-            if (lane < 36) {
-                const u32 v = lane / 12u, c = lane % 12u;
-                const u64 w = win_in[18 * (size_t)j + 6u * v + c % 6u];
-                L.slot[s0 + (int)v][c] = c < 6 ? w : fp_mul_small(w, 7u);
-            }
-            coop_sync();
-        };
-        load(0, sh.windows - 1);
-        coop_mul(L, 3, 2, 2, lane, ws);    // W = Z^4 of the accumulator
-        coop_mul(L, 3, 3, 3, lane, ws);
-#pragma unroll 1
-        for (int j = (int)sh.windows - 2; j >= 0; j--) {
-#pragma unroll 1
-            for (u32 d = 0; d < sh.c; d++) coop_jac_dbl(L, 0, t, lane, ws);
-            load(4, (u32)j);
-            coop_jac_add(L, 0, 4, t, lane, ws);
-        }
+    if (ws == 0) {   // Horner from the top window down
+        coop_sum_points(L, 0, 4, t, lane, ws, sh.windows, sh.c,
+                        [&](u32 k) { return win_in + 18 * (size_t)(sh.windows - 1 - k); });
     } else {
-        sc256 acc;
-#pragma unroll
-        for (int k = 0; k < 4; k++) acc.w[k] = 0;
-#pragma unroll 1
-        for (u32 b = lane; b < n_partials; b += 64) {
-            sc256 p;
-#pragma unroll
-            for (int k = 0; k < 4; k++) p.w[k] = partials[4 * b + k];
-            acc = sc_add_mod(acc, p);
-        }
-#pragma unroll
-        for (int k = 0; k < 4; k++) lin_sh[lane][k] = acc.w[k];
-        coop_sync();
-#pragma unroll 1
-        for (u32 stride = 32; stride >= 1; stride >>= 1) {
-            if (lane < stride) {
-                sc256 a, b;
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    a.w[k] = lin_sh[lane][k];
-                    b.w[k] = lin_sh[lane + stride][k];
-                }
-                a = sc_add_mod(a, b);
-#pragma unroll
-                for (int k = 0; k < 4; k++) lin_sh[lane][k] = a.w[k];
-            }
-            coop_sync();
-        }
-        sc256 lin;
-#pragma unroll
-        for (int k = 0; k < 4; k++) lin.w[k] = lin_sh[0][k];
-        if (partial_out && lane < 4) partial_out[18 + lane] = lin.w[lane];
-        coop_set(L, 20, 1ull, lane, ws);
-        coop_set(L, 21, 1ull, lane, ws);
-        coop_set(L, 22, 0ull, lane, ws);
-        coop_set(L, 23, 0ull, lane, ws);
-        const GtabGeom gg = gtab_geom(gtab);
-#pragma unroll 1
-        for (u32 w = 0; w < (partial_out ? 0u : gg.count); w++) {     // BASEPOINT_TABLE.multiply_vartime
-            const u32 d = sc_bits(lin, w * gg.bits, gg.bits);
-            if (d != 0) {
-                const u64 *rowp = gtab + (((size_t)w << gg.bits) + d) * 12;
-                if (lane < 24) {
-                    const u32 half = lane / 12u, c = lane % 12u;
-                    const u64 v = rowp[6u * half + c % 6u];
-                    L.slot[half ? 25 : 24][c] = c < 6 ? v : fp_mul_small(v, 7u);
-                }
-                coop_sync();
-                coop_jac_madd(L, 20, 24, 25, t, lane, ws);
-            }
+        const sc256 lin = wave_sum_mod_q(lin_sh, partials, 0, n_partials, lane);
+        if (partial_out) {   // the record carries lin itself, not [lin]G
+            if (lane < 4) partial_out[18 + lane] = lin.w[lane];
+        } else {
+            coop_set_identity(L, 20, lane, ws);
+            coop_comb_add(L, 20, 24, 25, lin, gtab, t, lane, ws);
         }
     }
     __syncthreads();
@@ -767,100 +695,21 @@ msm_k_finish_seg(const u64 *__restrict__ win_in, MsmShape sh, u32 segs, u32 seg_
     int t[9];
 #pragma unroll
     for (int k = 0; k < 9; k++) t[k] = (ws ? 26 : 7) + k;
-    if (ws == 0) {
-        auto load = [&](int s0, u32 j) {   // X, Y, Z of window j of this segment with their 7x halves
-            if (lane < 36) {
-                const u32 v = lane / 12u, c = lane % 12u;
-                const u64 w = win_in[18 * ((size_t)j * segs + s) + 6u * v + c % 6u];
-                L.slot[s0 + (int)v][c] = c < 6 ? w : fp_mul_small(w, 7u);
-            }
-            coop_sync();
-        };
-        load(0, sh.windows - 1);
-        coop_mul(L, 3, 2, 2, lane, ws);    // W = Z^4 of the accumulator
-        coop_mul(L, 3, 3, 3, lane, ws);
-#pragma unroll 1
-        for (int j = (int)sh.windows - 2; j >= 0; j--) {
-#pragma unroll 1
-            for (u32 d = 0; d < sh.c; d++) coop_jac_dbl(L, 0, t, lane, ws);
-            load(4, (u32)j);
-            coop_jac_add(L, 0, 4, t, lane, ws);
-        }
+    if (ws == 0) {   // Horner over this segment's window sums
+        coop_sum_points(L, 0, 4, t, lane, ws, sh.windows, sh.c,
+                        [&](u32 k) { return win_in + 18 * ((size_t)(sh.windows - 1 - k) * segs + s); });
     } else {
         const u32 b_lo = s * seg_blocks, b_hi = b_lo + seg_blocks < n_partials ? b_lo + seg_blocks : n_partials;
-        sc256 acc;
-#pragma unroll
-        for (int k = 0; k < 4; k++) acc.w[k] = 0;
-#pragma unroll 1
-        for (u32 b = b_lo + lane; b < b_hi; b += 64) {
-            sc256 p;
-#pragma unroll
-            for (int k = 0; k < 4; k++) p.w[k] = partials[4 * (size_t)b + k];
-            acc = sc_add_mod(acc, p);
-        }
-#pragma unroll
-        for (int k = 0; k < 4; k++) lin_sh[lane][k] = acc.w[k];
-        coop_sync();
-#pragma unroll 1
-        for (u32 stride = 32; stride >= 1; stride >>= 1) {
-            if (lane < stride) {
-                sc256 a, b;
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    a.w[k] = lin_sh[lane][k];
-                    b.w[k] = lin_sh[lane + stride][k];
-                }
-                a = sc_add_mod(a, b);
-#pragma unroll
-                for (int k = 0; k < 4; k++) lin_sh[lane][k] = a.w[k];
-            }
-            coop_sync();
-        }
-        sc256 lin;
-#pragma unroll
-        for (int k = 0; k < 4; k++) lin.w[k] = lin_sh[0][k];
+        sc256 lin = wave_sum_mod_q(lin_sh, partials, b_lo, b_hi, lane);
         // rhs != nullptr (ssa_verify_aggregates_many): the segment's right-hand scalar is given --
         // 32 bytes per segment, the aggregate's e_agg -- instead of the sum of the block partials (zero there: e = 0)
         if (rhs) lin = ld_sc(rhs + 32 * (size_t)s);
-        coop_set(L, 20, 1ull, lane, ws);
-        coop_set(L, 21, 1ull, lane, ws);
-        coop_set(L, 22, 0ull, lane, ws);
-        coop_set(L, 23, 0ull, lane, ws);
-        const GtabGeom gg = gtab_geom(gtab);
-#pragma unroll 1
-        for (u32 w = 0; w < gg.count; w++) {
-            const u32 d = sc_bits(lin, w * gg.bits, gg.bits);
-            if (d != 0) {
-                const u64 *rowp = gtab + (((size_t)w << gg.bits) + d) * 12;
-                if (lane < 24) {
-                    const u32 half = lane / 12u, c = lane % 12u;
-                    const u64 v = rowp[6u * half + c % 6u];
-                    L.slot[half ? 25 : 24][c] = c < 6 ? v : fp_mul_small(v, 7u);
-                }
-                coop_sync();
-                coop_jac_madd(L, 20, 24, 25, t, lane, ws);
-            }
-        }
+        coop_set_identity(L, 20, lane, ws);
+        coop_comb_add(L, 20, 24, 25, lin, gtab, t, lane, ws);
     }
     __syncthreads();
     if (ws == 0) {
-        // X_l Z_r^2 == X_r Z_l^2 and Y_l Z_r^3 == Y_r Z_l^3 (X and Y only as first operands: their 7x halves may be stale)
-        const bool li = coop_is_zero(L, 2, lane, ws), ri = coop_is_zero(L, 22, lane, ws);
-        bool eq;
-        if (li || ri) {
-            eq = li && ri;
-        } else {
-            coop_mul(L, 7, 22, 22, lane, ws);      // Z_r^2
-            coop_mul(L, 8, 0, 7, lane, ws);        // X_l Z_r^2
-            coop_mul(L, 9, 2, 2, lane, ws);        // Z_l^2
-            coop_mul(L, 10, 20, 9, lane, ws);      // X_r Z_l^2
-            eq = coop_eq(L, 8, 10, lane, ws);
-            coop_mul(L, 7, 7, 22, lane, ws);       // Z_r^3
-            coop_mul(L, 8, 1, 7, lane, ws);        // Y_l Z_r^3
-            coop_mul(L, 9, 9, 2, lane, ws);        // Z_l^3
-            coop_mul(L, 10, 21, 9, lane, ws);      // Y_r Z_l^3
-            eq = eq && coop_eq(L, 8, 10, lane, ws);
-        }
+        const bool eq = coop_jac_equal(L, 0, 20, 7, lane, ws);
         if (lane == 0) seg_ok[s] = eq ? 1u : 0u;
     }
 }
@@ -1133,7 +982,7 @@ msm_k_small(const DevParams *__restrict__ prm, const u8 *__restrict__ sigs, cons
     }
     __syncthreads();
     if (!sh.ok) {   // block-uniform
-        if (threadIdx.x < 24) rec[threadIdx.x] = threadIdx.x == 22 ? 1ull : threadIdx.x == 23 ? SSA_MSM_RECORD_MAGIC : 0ull;
+        msm_record_flag(rec, true);
         return;
     }
     if (ws == 0) {
@@ -1153,7 +1002,7 @@ msm_k_small(const DevParams *__restrict__ prm, const u8 *__restrict__ sigs, cons
     }
     __syncthreads();
     if (!sh.r_ok) {
-        if (threadIdx.x < 24) rec[threadIdx.x] = threadIdx.x == 22 ? 1ull : threadIdx.x == 23 ? SSA_MSM_RECORD_MAGIC : 0ull;
+        msm_record_flag(rec, true);
         return;
     }
     if (ws == 0) {
@@ -1184,16 +1033,9 @@ SSA_DEV void sum_records_range(CoopLds &L, const u64 *__restrict__ in, u32 lo, u
     sc256 lin;
 #pragma unroll
     for (int k = 0; k < 4; k++) lin.w[k] = 0;
-    // accumulator 0..3 (X, Y, Z, W = Z^4), addend 4..6
-    auto load = [&](int s0, u32 j) {
-        if (lane < 36) {
-            const u32 v = lane / 12u, c = lane % 12u;
-            const u64 w = in[24 * (size_t)j + 6u * v + c % 6u];
-            L.slot[s0 + (int)v][c] = c < 6 ? w : fp_mul_small(w, 7u);
-        }
-        coop_sync();
-    };
-    load(0, lo);
+    // accumulator 0..3 (X, Y, Z, W = Z^4), addend 4..6.  The loop of coop_sum_points with dbl = 0, spelled out: it also
+    // folds each record's scalar and flag, and through the helper the kernels were 1 % slower (profiles/r17/README.md)
+    coop_load_jac(L, 0, in + 24 * (size_t)lo, lane);
     coop_mul(L, 3, 2, 2, lane, 0);
     coop_mul(L, 3, 3, 3, lane, 0);
 #pragma unroll 1
@@ -1204,7 +1046,7 @@ SSA_DEV void sum_records_range(CoopLds &L, const u64 *__restrict__ in, u32 lo, u
         for (int k = 0; k < 4; k++) p.w[k] = in[24 * (size_t)j + 18 + k];
         lin = sc_add_mod(lin, p);
         if (j > lo) {
-            load(4, j);
+            coop_load_jac(L, 4, in + 24 * (size_t)j, lane);
             coop_jac_add(L, 0, 4, t, lane, 0);
         }
     }
@@ -1233,17 +1075,14 @@ msm_k_sum_records_seg(const u64 *__restrict__ in, const u32 *__restrict__ first,
     const u32 j = agg0 + blockIdx.x, lo = first[j] - first[agg0], hi = first[j + 1] - first[agg0];
     u64 *rec = out + 24 * (size_t)blockIdx.x;
     if (lo >= hi) {                                   // (block-uniform)
-        if (threadIdx.x < 24) rec[threadIdx.x] = threadIdx.x == 23 ? SSA_MSM_RECORD_MAGIC : 0ull;
+        msm_record_flag(rec, false);
         return;
     }
     sum_records_range(L, in, lo, hi, rec);
 }
 
-// the record of an empty shard: the identity (Z = 0), sum s_i e_i = 0, not malformed -- and the magic word: a buffer that
-// nobody wrote (all zero) is NOT a record
-__global__ void msm_k_empty_record(u64 *__restrict__ rec) {
-    if (threadIdx.x < 24) rec[threadIdx.x] = threadIdx.x == 23 ? SSA_MSM_RECORD_MAGIC : 0ull;
-}
+// the record of an empty shard
+__global__ void msm_k_empty_record(u64 *__restrict__ rec) { msm_record_flag(rec, false); }
 
 }  // namespace ssa
 

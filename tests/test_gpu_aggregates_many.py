@@ -339,6 +339,29 @@ def test_unequal_sizes_in_one_group(engine, engines, pool, path):
 
 
 @pytest.mark.parametrize("path", PATHS)
+def test_identity_on_both_sides_and_on_one_side_only(engine, engines, oracle, path):
+    """Every lane the identity key with the identity R: the left side is the identity whatever the coefficients are, so
+    the comparison meets identity == identity where e_agg = 0 (valid) and the identity against [e_agg]G where it is not
+    (invalid) -- in one call, in the single call on the same path, and in the model."""
+    counts = [1, 3, 0, 17]
+    n = sum(counts)
+    rng = np.random.default_rng(0x1D1D)
+    pks, inf = np.zeros((n, 96), np.uint8), np.ones(n, np.uint8)
+    msgs = rng.integers(0, 256, size=(n, 80), dtype=np.uint8)
+    r = np.zeros(49, np.uint8)
+    r[48] = 0x80                                     # x = 0 with the infinity flag
+    for k, es in enumerate(([0, 0, 0, 0], [1, Q - 1, 0, 0x1234567 << 200], [0, 5, 0, 0])):
+        aggs = [np.concatenate([np.tile(r, c), e_bytes(e)]) for c, e in zip(counts, es)]
+        expect = [OK if e == 0 else INVALID for e in es]
+        got = many(engines[path], aggs, pks, msgs, inf)
+        assert got == expect == singles(engines[path], aggs, pks, msgs, inf) == singles(engine, aggs, pks, msgs, inf)
+        key = ("identity_sides", k)
+        if key not in _STATE:                        # (the model's answer does not depend on the path: asked once)
+            _STATE[key] = model(oracle, aggs, pks, msgs, range(4), inf)
+        assert _STATE[key] == expect
+
+
+@pytest.mark.parametrize("path", PATHS)
 def test_hygiene(engine, engines, pool, path):
     import schnorr_sig_amd as ssa
     eng = engines[path]

@@ -189,6 +189,45 @@ def test_identity_keys_identity_r_and_one_key_with_equal_coefficients(engine, or
     assert st[same[77]] == 2 and (np.delete(st[same], 77) == 0).all()
 
 
+def test_segments_whose_two_sides_are_the_identity_or_only_one_is(oracle):
+    """Every lane the identity key with the identity R: a segment's left side is the identity, its right side
+    [sum s_i e_i]G.  Where every e is 0 the comparison meets identity == identity and the segment passes; where not, the
+    identity against a point, and its lanes fail the exact check too.  600 lanes in three forced segments above a
+    small-batch bound of 256: three 256-lane blocks, the last ragged."""
+    import schnorr_sig_amd as ssa
+    old = os.environ.get("SSA_MSM_SMALL_MAX")
+    os.environ["SSA_MSM_SMALL_MAX"] = "256"
+    try:
+        eng = ssa.Engine(0)
+    finally:
+        if old is None:
+            os.environ.pop("SSA_MSM_SMALL_MAX", None)
+        else:
+            os.environ["SSA_MSM_SMALL_MAX"] = old
+    try:
+        eng.debug_screen_segments(3)
+        rng = np.random.default_rng(9551)
+        n = 600
+        pks, inf = np.zeros((n, 96), np.uint8), np.ones(n, np.uint8)
+        msgs = rng.integers(0, 256, size=(n, 80), dtype=np.uint8)
+        co = coeffs32(rng, n)
+        samp = np.array([0, 255, 256, 511, 512, 599])
+        for nonzero in (slice(0, 0), slice(0, n), slice(256, 512)):
+            sigs = np.zeros((n, 81), np.uint8)
+            sigs[:, 48] = 0x80                                    # x = 0 with the infinity flag; e = 0
+            sigs[nonzero, 49:] = make_scalars(rng, n)[nonzero]
+            expect = np.zeros(n, np.uint8)
+            expect[nonzero] = 2
+            for c in (co, None):
+                st = assert_matches(eng, sigs, pks, msgs, coeffs=c, pk_inf=inf)
+                assert (st == expect).all()
+            want = oracle.verify_many(sigs[samp], pks[samp], msgs[samp], check_torsion=False, pk_inf=inf[samp],
+                                      sig_flag_byte=True)
+            assert (expect[samp] == want).all()
+    finally:
+        eng.close()
+
+
 def test_global_sign_is_rejected_lane_by_lane(engine):
     """e -> q - e in every signature: the x-only MSM verdict accepts (class 2), the screened
     form compares points and rejects every lane"""
