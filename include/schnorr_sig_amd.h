@@ -957,6 +957,38 @@ int ssa_debug_aggregates_many_coeffs(ssa_ctx *ctx, const uint8_t *aggs, const ui
                                      const uint8_t *pks, const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride,
                                      size_t msg_len, uint8_t *coeffs16_out);
 
+/* ---- filtering half-aggregation: drop the lanes that fail, aggregate the rest ----------
+ * What a block producer needs: n signatures in, the aggregate of exactly the lanes that verify out, and the list of
+ * those lanes.  Let S be the status vector ssa_verify_batch_screened (library-drawn coefficients) gives the input and
+ * K = { i : S[i] == 0 } in ascending order.  Then
+ *   *n_kept_out = |K|,  kept_out[0, |K|) = K,  status_out = S (status_out may be NULL),
+ *   the first SSA_AGGREGATE_LENGTH(|K|) bytes of agg_out are byte for byte what ssa_aggregate_many (flags 0) returns
+ *   for the lanes of K handed in alone in that order,
+ *   the rest of agg_out (capacity SSA_AGGREGATE_LENGTH(n)) and of kept_out (capacity n words) is zero.
+ * |K| == 0 gives 32 zero bytes: the empty aggregate, which ssa_verify_aggregate accepts for n = 0.  n == 0: SSA_OK,
+ * *n_kept_out = 0, 32 zero bytes.  The return value reports errors only (a dropped lane is a result): SSA_ERR_ARG for a
+ * null agg_out, kept_out or n_kept_out, and for n above the context's MSM slice.
+ * The guarantee is that of SSA_AGG_CHECK: verify_batch semantics (the flag byte of R_i honoured, pk_inf marks identity
+ * keys, NO subgroup check of keys or R's), and a lane that does not verify is kept only with the probability a
+ * screened segment accepts it: about 2^-128 for an error with a prime-order component, 1/l for
+ * an error of pure small order l, which needs a key or an R outside the prime-order subgroup.
+ * The call hashes every message ONCE: the same launch gives the screen its challenge scalars and the transcript its
+ * digests; only the digests and signatures of the kept lanes are moved, keys and messages never.
+ * The _device form takes device pointers except n_kept_out, a HOST pointer in both forms: the call SYNCHRONISES the
+ * context's stream twice -- once inside the screen (for its segment verdicts; not at all for a batch of at most
+ * SSA_MSM_SMALL_MAX lanes) and once for |K|, by which it sizes its remaining launches and the caller whatever reads the
+ * aggregate.  The remaining launches are only enqueued. */
+int ssa_aggregate_valid_many(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_inf,
+                             const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len, size_t n,
+                             uint8_t *agg_out, uint32_t *kept_out, uint64_t *n_kept_out, uint8_t *status_out);
+int ssa_aggregate_valid_many_device(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_pk_inf,
+                                    const uint8_t *d_msgs, const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len,
+                                    size_t n, uint8_t *d_agg_out, uint32_t *d_kept_out, uint64_t *n_kept_out,
+                                    uint8_t *d_status_out);
+/* tests: the compaction alone.  status (n bytes, host) -> kept_out (the indices of the zero bytes, ascending, then zeros
+ * up to n), *n_kept_out their number */
+int ssa_debug_aggregate_keep(ssa_ctx *ctx, const uint8_t *status, size_t n, uint32_t *kept_out, uint64_t *n_kept_out);
+
 /* ---- ABI version -------------------------------------------------------------------------------------------
  * Bumped whenever an exported signature changes (round 2 inserted pk_inf into the batch entry points under the same
  * symbol names: a shim built against the older header would still link and pass msgs as pk_inf).  A binding checks

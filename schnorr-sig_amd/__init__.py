@@ -260,6 +260,9 @@ def _load():
         "ssa_verify_aggregate": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz]),
         "ssa_verify_aggregate_device": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz, vp]),
         "ssa_debug_aggregate_coeffs": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz, vp]),
+        "ssa_aggregate_valid_many": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz, vp, vp, u64p, vp]),
+        "ssa_aggregate_valid_many_device": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz, vp, vp, u64p, vp]),
+        "ssa_debug_aggregate_keep": (i32, [vp, vp, sz, vp, u64p]),
         "ssa_verify_aggregates_many": (i32, [vp, vp, u64p, sz, vp, vp, vp, vp, sz, sz, vp]),
         "ssa_verify_aggregates_many_device": (i32, [vp, vp, u64p, sz, vp, vp, vp, vp, sz, sz, vp]),
         "ssa_debug_aggregates_plan": (C.c_int64, [u64p, sz, sz, sz, u64p, sz]),
@@ -686,6 +689,43 @@ class Engine:
         out = np.zeros((n, 16), dtype=np.uint8)
         _check(_lib.ssa_debug_aggregate_coeffs(self._ctx, *batch, _ptr(out) if n else None), "ssa_debug_aggregate_coeffs")
         return out
+
+    # ---- filtering half-aggregation (include/schnorr_sig_amd.h) ----
+    def aggregate_valid(self, sigs, pks, msgs, offsets=None, pk_inf=None):
+        """n signatures -> (aggregate uint8[49 |K| + 32] of the lanes that verify, their indices uint32[|K|] ascending,
+        per-lane status uint8[n] as verify_batch_screened gives it).  The aggregate is what aggregate() returns for
+        those lanes handed in alone; with none kept it is the 32 zero bytes of the empty aggregate."""
+        n, batch, keep = self._agg_batch(sigs, 81, pks, msgs, offsets, pk_inf)
+        agg = np.full(49 * n + 32, 255, dtype=np.uint8)
+        kept = np.full(max(n, 1), 0xFFFFFFFF, dtype=np.uint32)
+        status = np.full(n, 255, dtype=np.uint8)
+        n_kept = C.c_uint64(0)
+        _check(_lib.ssa_aggregate_valid_many(self._ctx, *batch, _ptr(agg), _ptr(kept), C.byref(n_kept),
+                                             _ptr(status) if n else None), "ssa_aggregate_valid_many")
+        m = int(n_kept.value)
+        return agg[:49 * m + 32].copy(), kept[:m].copy(), status
+
+    def aggregate_valid_device(self, d_sigs, d_pks, d_msgs, n, msg_len, d_agg, d_kept, d_status=0, msg_stride=None,
+                               d_offsets=0, d_pk_inf=0):
+        """device form (synchronises the stream twice: inside the screen and for the number of kept lanes) -> that
+        number; the aggregate of the kept lanes lands at d_agg (capacity 49 n + 32 bytes, zero behind it), their indices
+        at d_kept (capacity n uint32, zero behind them), the statuses at d_status if it is given"""
+        n_kept = C.c_uint64(0)
+        _check(_lib.ssa_aggregate_valid_many_device(
+            self._ctx, d_sigs, d_pks, *self._dev_batch(d_pk_inf, d_msgs, d_offsets, msg_stride, msg_len, n),
+            d_agg, d_kept, C.byref(n_kept), d_status or None), "ssa_aggregate_valid_many_device")
+        return int(n_kept.value)
+
+    def debug_aggregate_keep(self, status):
+        """tests: the compaction alone -> (the indices of the zero bytes of `status`, ascending, as the device lists
+        them; the whole uint32[n] output, zero behind the list)"""
+        status = _np_u8(status).reshape(-1)
+        n = status.size
+        kept = np.full(max(n, 1), 0xFFFFFFFF, dtype=np.uint32)
+        n_kept = C.c_uint64(0)
+        _check(_lib.ssa_debug_aggregate_keep(self._ctx, _ptr(status) if n else None, n, _ptr(kept) if n else None,
+                                             C.byref(n_kept)), "ssa_debug_aggregate_keep")
+        return kept[:int(n_kept.value)], kept[:n]
 
     # ---- many aggregates in one call (include/schnorr_sig_amd.h, DESIGN.md section 21) ----
     def _aggs_batch(self, aggregates, pks, msgs, offsets, pk_inf):
@@ -1719,6 +1759,18 @@ class AggregateSignature:
         if st != OK:
             raise SignatureError(SignatureError.InvalidSignature)
         return cls(agg.tobytes())
+
+    @classmethod
+    def aggregate_valid(cls, signatures, public_keys, messages, engine=None):
+        """Engine.aggregate_valid over (signature, public key, message) objects -> (the AggregateSignature of the
+        triples that verify under verify_batch semantics, the list of their indices).  A triple that does not verify is
+        dropped, not raised."""
+        packed = _pack_triples(signatures, public_keys, messages)
+        if packed is None:
+            return cls(bytes(32)), []
+        sigs, pks, inf, flat, off = packed
+        agg, kept, _ = (engine or default_engine()).aggregate_valid(sigs, pks, flat, offsets=off, pk_inf=inf)
+        return cls(agg.tobytes()), [int(i) for i in kept]
 
     def verify(self, public_keys, messages, engine=None):
         """Ok -> None; otherwise raises SignatureError (the equation fails) or MalformedInput"""

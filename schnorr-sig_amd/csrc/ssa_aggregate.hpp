@@ -34,6 +34,11 @@
 // group's lanes, one wave per aggregate adds its records, ag_k_finish) or the bucket path (ag_k_gather* pad the group to
 // equal segments, the screened MSM gives one exact comparison per segment against [e_agg_j]G, ag_k_verdicts_seg turns it
 // into the aggregate's verdict).
+//
+// ssa_aggregate_valid_many aggregates only the lanes that pass the screen: av_k_keep_count,
+// av_k_keep_scan and av_k_keep_list turn the status vector into the ascending list of kept lanes (ballots and sums, no
+// atomic), av_k_gather_sigs and av_k_gather_dig lay those lanes' signatures and raw digests side by side, and leaf, tree,
+// coefficient, fold and pack run over them as over any batch: a lane's digest does not depend on its place.
 #pragma once
 #include <vector>
 #include "ssa_kernels.hpp"
@@ -488,6 +493,95 @@ ag_k_verdicts_seg(const u8 *__restrict__ seg_ok, const u8 *__restrict__ recheck,
     if (threadIdx.x != 0) return;
     const sc256 e = ld_sc(rhs + 32 * (size_t)s);
     verdicts[s] = (bad || sc_geq_q(e)) ? ST_MALFORMED : (seg_ok[s] ? ST_OK : ST_INVALID_SIG);
+}
+
+// ---- ssa_aggregate_valid_many: the lanes that verify, as an ascending list, and their gathers ----
+// A lane is kept iff its status byte is zero.  Its place in the list is a sum of counts and nothing else: the kept lanes
+// of the workgroups in front of its own (av_k_keep_scan), of the waves in front of its own within the workgroup, and of
+// the lanes below it in its wave's 64-bit ballot.  So the list is ascending and the same on every run: no atomic takes
+// part.  Three launches; each reads what the one before wrote.
+constexpr u32 AV_BLOCK = 256;
+
+// blk_cnt[b] = kept lanes of workgroup b
+__global__ void __launch_bounds__(256)
+av_k_keep_count(const u8 *__restrict__ status, u32 n, u32 *__restrict__ blk_cnt) {
+    __shared__ u32 wave_cnt[AV_BLOCK / 64];
+    const u32 i = blockIdx.x * AV_BLOCK + threadIdx.x;
+    const unsigned long long keeps = __ballot(i < n && status[i] == 0);
+    if ((threadIdx.x & 63u) == 0) wave_cnt[threadIdx.x >> 6] = (u32)__popcll(keeps);
+    __syncthreads();
+    if (threadIdx.x == 0) blk_cnt[blockIdx.x] = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+}
+
+// ONE workgroup: blk_off[b] = kept lanes in front of workgroup b's, blk_off[nb] = the length of the list.  Thread t sums
+// a strip of ceil(nb / 256) consecutive counts (128 of them for a full slice of 2^23 lanes), the 256 strip sums are
+// scanned through LDS, and the thread walks its strip again from its exclusive sum.
+__global__ void __launch_bounds__(256)
+av_k_keep_scan(const u32 *__restrict__ blk_cnt, u32 nb, u32 *__restrict__ blk_off) {
+    __shared__ u32 part[AV_BLOCK];
+    const u32 t = threadIdx.x, per = (nb + AV_BLOCK - 1) / AV_BLOCK;
+    const u32 lo = t * per < nb ? t * per : nb, hi = lo + per < nb ? lo + per : nb;
+    u32 sum = 0;
+    for (u32 b = lo; b < hi; b++) sum += blk_cnt[b];
+    part[t] = sum;
+    __syncthreads();
+    for (u32 d = 1; d < AV_BLOCK; d <<= 1) {
+        const u32 v = t >= d ? part[t - d] : 0u;
+        __syncthreads();                              // every read of this step before its first write
+        part[t] += v;
+        __syncthreads();
+    }
+    u32 acc = part[t] - sum;
+    if (t == AV_BLOCK - 1) blk_off[nb] = part[t];
+    for (u32 b = lo; b < hi; b++) {
+        blk_off[b] = acc;
+        acc += blk_cnt[b];
+    }
+}
+
+// kept[c] = the c-th kept lane, in lane order; kept[c] = 0 from the length of the list up to n
+__global__ void __launch_bounds__(256)
+av_k_keep_list(const u8 *__restrict__ status, u32 n, const u32 *__restrict__ blk_off, u32 nb, u32 *__restrict__ kept) {
+    __shared__ u32 wave_cnt[AV_BLOCK / 64];
+    const u32 i = blockIdx.x * AV_BLOCK + threadIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const bool keep = i < n && status[i] == 0;
+    const unsigned long long keeps = __ballot(keep);
+    if (lane == 0) wave_cnt[wave] = (u32)__popcll(keeps);
+    __syncthreads();
+    if (i < n && i >= blk_off[nb]) kept[i] = 0;       // (a list entry is below the length: no two threads write one word)
+    if (!keep) return;
+    u32 pos = blk_off[blockIdx.x] + (u32)__popcll(keeps & ((1ull << lane) - 1ull));
+    for (u32 k = 0; k < wave; k++) pos += wave_cnt[k];
+    kept[pos] = i;
+}
+
+// sigs_out (the library's own buffer: dword-aligned, m * 81 bytes) = the signatures of the m listed lanes side by side.
+// One thread per dword, as ag_k_pack; the source lane of every byte is looked up in the list.
+__global__ void __launch_bounds__(256)
+av_k_gather_sigs(const u8 *__restrict__ sigs, const u32 *__restrict__ kept, size_t m, u8 *__restrict__ sigs_out) {
+    const size_t d = (size_t)blockIdx.x * 256 + threadIdx.x, total = m * 81, o = 4 * d;
+    if (o >= total) return;
+    u32 v = 0;
+    const int cnt = total - o < 4 ? (int)(total - o) : 4;
+    for (int k = 0; k < cnt; k++) {
+        const size_t b = o + k, c = b / 81;
+        v |= (u32)sigs[81 * (size_t)kept[c] + (b - 81 * c)] << (8 * k);
+    }
+    if (cnt == 4) {
+        reinterpret_cast<u32 *>(sigs_out)[d] = v;
+    } else {
+        for (int k = 0; k < cnt; k++) sigs_out[o + k] = (u8)(v >> (8 * k));
+    }
+}
+
+// dig_out[c] = dig[kept[c]]: the raw digests (four words) of the m listed lanes, two threads of 16 bytes per lane.  Both
+// buffers are the library's own.
+__global__ void __launch_bounds__(256)
+av_k_gather_dig(const u64 *__restrict__ dig, const u32 *__restrict__ kept, size_t m, u64 *__restrict__ dig_out) {
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= 2 * m) return;
+    reinterpret_cast<ulonglong2 *>(dig_out)[t] =
+        reinterpret_cast<const ulonglong2 *>(dig)[2 * (size_t)kept[t >> 1] + (t & 1u)];
 }
 #endif  // SSA_NO_KERNELS
 

@@ -1871,40 +1871,48 @@ static std::vector<AgPass> ag_uniform_passes(size_t n) {
     }
 }
 
-// The transcript over the n (>= 1) lanes of a call, on ctx->stream: the coefficients a_i into ctx->ag_coeffs (n x 16
-// bytes).  d_first: the k + 1 prefix sums of an uploaded plan (agm_upload_plan, `passes` from it); nullptr: one aggregate,
-// no plan, no lane map (passes from ag_uniform_passes).  d_wire != nullptr: the R's come out of the wire form and are
-// laid out at stride 81 in ctx->ag_sigs first; else they stand so in d_sigs.  with_h: the same launch of ssa_k_hash
-// leaves the challenge scalars mod q in ctx->ws_h.  One launch per stage and tree pass.
-static int ag_transcript(ssa_ctx *ctx, const u8 *d_wire, const u8 *d_sigs, const u8 *d_pks, const MsgView &mv, size_t n,
-                         bool with_h, const u32 *d_first, size_t k, const std::vector<AgPass> &passes) {
-    size_t widest = 1;                  // nodes a pass writes (a top workgroup writes a root instead)
-    for (const AgPass &p : passes) widest = std::max(widest, (size_t)p.groups());
+// The transcript over the n (>= 1) lanes of a call, on ctx->stream, in two halves.  d_first: the k + 1 prefix sums of an
+// uploaded plan (agm_upload_plan); nullptr: one aggregate, no plan, no lane map.
+// The front: the R's and the challenge hashes.  d_wire != nullptr: the R's come out of the wire form and are laid out at
+// stride 81 in ctx->ag_sigs first, and *d_sigs then points there; else they stand so in *d_sigs.  ONE launch of ssa_k_hash
+// leaves the raw digests in ctx->ag_dig and, with_h, the challenge scalars mod q in ctx->ws_h.
+static int ag_transcript_front(ssa_ctx *ctx, const u8 *d_wire, const u8 **d_sigs, const u8 *d_pks, const MsgView &mv,
+                               size_t n, bool with_h, const u32 *d_first, size_t k) {
     if ((d_wire && ctx->ag_sigs.reserve(n * 81 + 16)) || (d_first && ctx->agm_map.reserve(n * 4)) ||
-        ctx->agm_roots.reserve(k * 32) || ctx->ag_dig.reserve(n * 32) || ctx->ag_nodes.reserve(std::max(n, widest) * 32) ||
-        ctx->ag_nodes2.reserve(widest * 32) || ctx->ag_coeffs.reserve(n * 16) || (with_h && ctx->ws_h.reserve(n * 32)))
+        ctx->ag_dig.reserve(n * 32) || (with_h && ctx->ws_h.reserve(n * 32)))
         return SSA_ERR_HIP;
-    const u32 *d_map = d_first ? (const u32 *)ctx->agm_map.p : nullptr;
-    int rc = 0;
     if (d_wire) {
-        rc = timed_launch(ctx, d_first ? "ag_k_expand_many" : "ag_k_expand", [&] {
+        const int rc = timed_launch(ctx, d_first ? "ag_k_expand_many" : "ag_k_expand", [&] {
             if (d_first)
                 hipLaunchKernelGGL(ag_k_lane_map, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, d_first, (u32)k, n,
                                    (u32 *)ctx->agm_map.p);
-            hipLaunchKernelGGL(ag_k_expand, dim3(grid_for((n * 81 + 3) / 4, 256)), dim3(256), 0, ctx->stream, d_wire, d_map, n,
-                               (u8 *)ctx->ag_sigs.p);
+            hipLaunchKernelGGL(ag_k_expand, dim3(grid_for((n * 81 + 3) / 4, 256)), dim3(256), 0, ctx->stream, d_wire,
+                               d_first ? (const u32 *)ctx->agm_map.p : (const u32 *)nullptr, n, (u8 *)ctx->ag_sigs.p);
         });
         if (rc) return rc;
-        d_sigs = (const u8 *)ctx->ag_sigs.p;
+        *d_sigs = (const u8 *)ctx->ag_sigs.p;
     }
-    rc = timed_launch(ctx, "ssa_k_hash", [&] {
-        hipLaunchKernelGGL(ssa_k_hash, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, ctx->d_params, d_sigs, d_pks, mv, n,
+    return timed_launch(ctx, "ssa_k_hash", [&] {
+        hipLaunchKernelGGL(ssa_k_hash, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, ctx->d_params, *d_sigs, d_pks, mv, n,
                            with_h ? (u64 *)ctx->ws_h.p : (u64 *)nullptr, (u8 *)ctx->ag_dig.p, (const u32 *)nullptr, 0u);
     });
-    if (rc) return rc;
-    rc = timed_launch(ctx, "ag_k_leaf", [&] {
-        hipLaunchKernelGGL(ag_k_leaf, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, ctx->d_params,
-                           (const u64 *)ctx->ag_dig.p, d_sigs, n, (u64 *)ctx->ag_nodes.p);
+}
+
+// From digests on: d_dig holds the raw digest of every lane (four words), d_sigs the lanes at stride 81 (only the flag
+// byte of R is read); the coefficients a_i go into ctx->ag_coeffs (n x 16 bytes).  `passes` from the uploaded plan, or
+// ag_uniform_passes.  One launch per stage and tree pass.  Nothing here reads keys, messages or the lanes' positions in
+// the caller's batch: lanes gathered out of a larger one take the same route.
+static int ag_transcript_from_digests(ssa_ctx *ctx, const u64 *d_dig, const u8 *d_sigs, size_t n, const u32 *d_first,
+                                      size_t k, const std::vector<AgPass> &passes) {
+    size_t widest = 1;                  // nodes a pass writes (a top workgroup writes a root instead)
+    for (const AgPass &p : passes) widest = std::max(widest, (size_t)p.groups());
+    if (ctx->agm_roots.reserve(k * 32) || ctx->ag_nodes.reserve(std::max(n, widest) * 32) ||
+        ctx->ag_nodes2.reserve(widest * 32) || ctx->ag_coeffs.reserve(n * 16))
+        return SSA_ERR_HIP;
+    const u32 *d_map = d_first ? (const u32 *)ctx->agm_map.p : nullptr;
+    int rc = timed_launch(ctx, "ag_k_leaf", [&] {
+        hipLaunchKernelGGL(ag_k_leaf, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, ctx->d_params, d_dig, d_sigs, n,
+                           (u64 *)ctx->ag_nodes.p);
     });
     if (rc) return rc;
     // passes of AG_TREE_LEVELS levels between the two node buffers; a top workgroup writes its aggregate's root instead
@@ -1924,6 +1932,27 @@ static int ag_transcript(ssa_ctx *ctx, const u8 *d_wire, const u8 *d_sigs, const
     return timed_launch(ctx, "ag_k_coeff", [&] {
         hipLaunchKernelGGL(ag_k_coeff, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, ctx->d_params,
                            (const u64 *)ctx->agm_roots.p, d_map, d_first, n, (u64 *)ctx->ag_coeffs.p);
+    });
+}
+
+// Both halves: what every call that starts from signatures or a wire form runs.
+static int ag_transcript(ssa_ctx *ctx, const u8 *d_wire, const u8 *d_sigs, const u8 *d_pks, const MsgView &mv, size_t n,
+                         bool with_h, const u32 *d_first, size_t k, const std::vector<AgPass> &passes) {
+    if (int rc = ag_transcript_front(ctx, d_wire, &d_sigs, d_pks, mv, n, with_h, d_first, k)) return rc;
+    return ag_transcript_from_digests(ctx, (const u64 *)ctx->ag_dig.p, d_sigs, n, d_first, k, passes);
+}
+
+// sum a_i e_i mod q over n lanes at stride 81 with the coefficients of ctx->ag_coeffs, into ag_misc(ctx, AG_E).
+// d_status != nullptr: the checks of msm_k_prepare too (ag_k_fold), *d_fail counts the lanes that fail one.
+static int ag_fold(ssa_ctx *ctx, const u8 *d_sigs, const u8 *d_pks, const u8 *d_pk_inf, size_t n, u8 *d_status,
+                   unsigned long long *d_fail) {
+    const unsigned n_blocks = grid_for(n, 256);
+    if (ctx->ag_partials.reserve((size_t)n_blocks * 32) || ctx->ag_misc.reserve(AG_MISC_BYTES)) return SSA_ERR_HIP;
+    return timed_launch(ctx, "ag_k_fold", [&] {
+        hipLaunchKernelGGL(ag_k_fold, dim3(n_blocks), dim3(256), 0, ctx->stream, d_sigs, d_pks, d_pk_inf,
+                           (const u64 *)ctx->ag_coeffs.p, n, (u64 *)ctx->ag_partials.p, d_status, d_fail);
+        hipLaunchKernelGGL(ag_k_fold_finish, dim3(1), dim3(256), 0, ctx->stream, (const u64 *)ctx->ag_partials.p, n_blocks,
+                           ag_misc(ctx, AG_E));
     });
 }
 
@@ -1954,16 +1983,7 @@ extern "C" int ssa_aggregate_many_device(ssa_ctx *ctx, const uint8_t *d_sigs, co
                                                       nullptr, 0, d_status, (uint64_t *)d_fail))
             return rc;
     if (int rc = ag_transcript(ctx, nullptr, d_sigs, d_pks, b.msgs, n, false, nullptr, 1, ag_uniform_passes(n))) return rc;
-    const unsigned n_blocks = grid_for(n, 256);
-    if (ctx->ag_partials.reserve((size_t)n_blocks * 32) || ctx->ag_misc.reserve(AG_MISC_BYTES)) return SSA_ERR_HIP;
-    int rc = timed_launch(ctx, "ag_k_fold", [&] {
-        hipLaunchKernelGGL(ag_k_fold, dim3(n_blocks), dim3(256), 0, ctx->stream, d_sigs, d_pks, d_pk_inf,
-                           (const u64 *)ctx->ag_coeffs.p, n, (u64 *)ctx->ag_partials.p, screened ? (u8 *)nullptr : d_status,
-                           d_fail);
-        hipLaunchKernelGGL(ag_k_fold_finish, dim3(1), dim3(256), 0, ctx->stream, (const u64 *)ctx->ag_partials.p, n_blocks,
-                           ag_misc(ctx, AG_E));
-    });
-    if (rc) return rc;
+    if (int rc = ag_fold(ctx, d_sigs, d_pks, d_pk_inf, n, screened ? (u8 *)nullptr : d_status, d_fail)) return rc;
     unsigned long long nf = 0;
     HIP_TRY(hipMemcpyAsync(&nf, d_fail, sizeof nf, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -2014,6 +2034,116 @@ extern "C" int ssa_aggregate_many(ssa_ctx *ctx, const uint8_t *sigs, const uint8
     if (rc) return rc;
     if (n_fail_out) *n_fail_out = nf;
     return st;
+}
+
+// ------------------------------------------------------------------ filtering half-aggregation
+// d_kept[0, *m_out) = the lanes of d_status[0, n) whose byte is zero, ascending, and zeros up to n; *m_out their number.
+// Synchronises the stream: the number is read from the device.
+static int av_keep(ssa_ctx *ctx, const u8 *d_status, size_t n, u32 *d_kept, uint64_t *m_out) {
+    const unsigned nb = grid_for(n, AV_BLOCK);
+    if (ctx->av_blk.reserve((2 * (size_t)nb + 1) * sizeof(u32))) return SSA_ERR_HIP;
+    u32 *blk_cnt = (u32 *)ctx->av_blk.p, *blk_off = blk_cnt + nb;
+    const int rc = timed_launch(ctx, "av_k_keep", [&] {
+        hipLaunchKernelGGL(av_k_keep_count, dim3(nb), dim3(AV_BLOCK), 0, ctx->stream, d_status, (u32)n, blk_cnt);
+        hipLaunchKernelGGL(av_k_keep_scan, dim3(1), dim3(AV_BLOCK), 0, ctx->stream, (const u32 *)blk_cnt, nb, blk_off);
+        hipLaunchKernelGGL(av_k_keep_list, dim3(nb), dim3(AV_BLOCK), 0, ctx->stream, d_status, (u32)n, (const u32 *)blk_off,
+                           nb, d_kept);
+    });
+    if (rc) return rc;
+    u32 m = 0;
+    HIP_TRY(hipMemcpyAsync(&m, blk_off + nb, sizeof m, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    *m_out = m;
+    return 0;
+}
+
+// Two synchronisations: the screen's (for its segment verdicts; none at n <= msm_small_max) and one for |K|.
+extern "C" int ssa_aggregate_valid_many_device(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks,
+                                               const uint8_t *d_pk_inf, const uint8_t *d_msgs, const uint64_t *d_msg_off,
+                                               size_t msg_stride, size_t msg_len, size_t n, uint8_t *d_agg_out,
+                                               uint32_t *d_kept_out, uint64_t *n_kept_out, uint8_t *d_status_out) {
+    const DevBatch b{d_sigs, d_pks, d_pk_inf, {d_msgs, d_msg_off, msg_stride, msg_len}};
+    if (!ctx || !d_agg_out || !d_kept_out || !n_kept_out || (n && (!d_sigs || !d_pks))) return SSA_ERR_ARG;
+    if (int rc = agg_check_args(ctx, b.msgs, n)) return rc;
+    *n_kept_out = 0;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(d_agg_out, 0, 32, ctx->stream));
+        return SSA_OK;
+    }
+    if (!d_status_out && ctx->ag_status.reserve(n + 16)) return SSA_ERR_HIP;
+    u8 *d_status = d_status_out ? d_status_out : (u8 *)ctx->ag_status.p;
+    // ONE challenge hash over all n lanes: the scalars mod q for the screen, the raw digests for the transcript
+    if (int rc = ag_transcript_front(ctx, nullptr, &d_sigs, d_pks, b.msgs, n, true, nullptr, 1)) return rc;
+    // The screen reads ws_h and writes neither it nor ag_dig: with ready hashes msm_run_one and
+    // ssa_internal_verify_hashed launch no ssa_k_hash, the gather of failing segments copies the scalars into scr_in, and
+    // no ag_* buffer belongs to it.
+    if (int rc = ssa_internal_screen_hashed(ctx, b, n, (const uint64_t *)ctx->ws_h.p, d_status, nullptr)) return rc;
+    uint64_t m = 0;
+    if (int rc = av_keep(ctx, d_status, n, d_kept_out, &m)) return rc;
+    *n_kept_out = m;
+    // everything behind the aggregate of the kept lanes is zero; with none kept, that is the empty aggregate
+    const size_t used = m ? SSA_AGGREGATE_LENGTH(m) : 0;
+    if (used < SSA_AGGREGATE_LENGTH(n))
+        HIP_TRY(hipMemsetAsync(d_agg_out + used, 0, SSA_AGGREGATE_LENGTH(n) - used, ctx->stream));
+    if (m == 0) return SSA_OK;
+    // A lane's digest does not depend on its place, so the kept lanes' signatures and digests side by side are what the
+    // transcript of those lanes handed in alone starts from; keys and messages are not needed again.
+    if (ctx->av_sigs.reserve(m * 81 + 16) || ctx->av_dig.reserve(m * 32)) return SSA_ERR_HIP;
+    const u8 *k_sigs = (const u8 *)ctx->av_sigs.p;
+    int rc = timed_launch(ctx, "av_k_gather", [&] {
+        hipLaunchKernelGGL(av_k_gather_sigs, dim3(grid_for((m * 81 + 3) / 4, 256)), dim3(256), 0, ctx->stream, d_sigs,
+                           (const u32 *)d_kept_out, (size_t)m, (u8 *)ctx->av_sigs.p);
+        hipLaunchKernelGGL(av_k_gather_dig, dim3(grid_for(2 * m, 256)), dim3(256), 0, ctx->stream,
+                           (const u64 *)ctx->ag_dig.p, (const u32 *)d_kept_out, (size_t)m, (u64 *)ctx->av_dig.p);
+    });
+    if (rc) return rc;
+    if ((rc = ag_transcript_from_digests(ctx, (const u64 *)ctx->av_dig.p, k_sigs, m, nullptr, 1, ag_uniform_passes(m))))
+        return rc;
+    // (every kept lane passed the screen: e_i < q, and the fold has nothing left to check)
+    if ((rc = ag_fold(ctx, k_sigs, nullptr, nullptr, m, nullptr, nullptr))) return rc;
+    return timed_launch(ctx, "ag_k_pack", [&] {
+        hipLaunchKernelGGL(ag_k_pack, dim3(grid_for((m * 49 + 3) / 4, 256)), dim3(256), 0, ctx->stream, k_sigs, (size_t)m,
+                           d_agg_out);
+        (void)hipMemcpyAsync(d_agg_out + 49 * m, ag_misc(ctx, AG_E), 32, hipMemcpyDeviceToDevice, ctx->stream);
+    });
+}
+
+extern "C" int ssa_aggregate_valid_many(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_inf,
+                                        const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len,
+                                        size_t n, uint8_t *agg_out, uint32_t *kept_out, uint64_t *n_kept_out,
+                                        uint8_t *status_out) {
+    if (!ctx || !agg_out || !kept_out || !n_kept_out || (n && (!sigs || !pks))) return SSA_ERR_ARG;
+    if (int rc = agg_check_args(ctx, {msgs, msg_off, msg_stride, msg_len}, n)) return rc;
+    if (int rc = check_host_offsets(msg_off, n)) return rc;
+    *n_kept_out = 0;
+    if (n == 0) {
+        std::memset(agg_out, 0, 32);
+        return SSA_OK;
+    }
+    HostCall hc(ctx);
+    const u8 *d_sigs = hc.in(ctx->st_sigs, sigs, n * 81), *d_pks = hc.in(ctx->st_pks, pks, n * 96);
+    const u8 *d_inf = pk_inf ? hc.in(ctx->st_inf, pk_inf, n) : nullptr;
+    const MsgView mv = hc.msgs(msgs, msg_off, msg_stride, msg_len, n);
+    u8 *d_agg = hc.out(ctx->st_aux, agg_out, SSA_AGGREGATE_LENGTH(n), 16);
+    u32 *d_kept = (u32 *)hc.out(ctx->st_aux2, kept_out, n * sizeof(u32));
+    u8 *d_status = hc.out(ctx->st_status, status_out, n, 16);
+    return hc.finish([&] {
+        return ssa_aggregate_valid_many_device(ctx, d_sigs, d_pks, d_inf, mv.msgs, mv.off, msg_stride, msg_len, n, d_agg,
+                                               d_kept, n_kept_out, d_status);
+    });
+}
+
+// tests: the compaction alone, from a host status vector
+extern "C" int ssa_debug_aggregate_keep(ssa_ctx *ctx, const uint8_t *status, size_t n, uint32_t *kept_out,
+                                        uint64_t *n_kept_out) {
+    if (!ctx || !n_kept_out || (n && (!status || !kept_out)) || n > SSA_MAX_BATCH) return SSA_ERR_ARG;
+    *n_kept_out = 0;
+    if (n == 0) return SSA_OK;
+    HostCall hc(ctx);
+    const u8 *d_status = hc.in(ctx->st_status, status, n);
+    u32 *d_kept = (u32 *)hc.out(ctx->st_aux2, kept_out, n * sizeof(u32));
+    return hc.finish([&] { return av_keep(ctx, d_status, n, d_kept, n_kept_out); });
 }
 
 extern "C" int ssa_verify_aggregate_device(ssa_ctx *ctx, const uint8_t *d_agg, const uint8_t *d_pks, const uint8_t *d_pk_inf,

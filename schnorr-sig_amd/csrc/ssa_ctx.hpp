@@ -184,6 +184,9 @@ struct CtxKnobs {
        inputs (R's, keys, flags, challenge scalars, coefficients) and its bytes (mask, re-check marks, segment verdicts, \
        right-hand scalars) */ \
     X(agm_plan) X(agm_map) X(agm_roots) X(agm_in) X(agm_bytes) \
+    /* filtering half-aggregation: per-workgroup counts and offsets of the kept lanes (the \
+       length of the list behind them), and the kept lanes' signatures and raw digests side by side */ \
+    X(av_blk) X(av_sigs) X(av_dig) \
     /* the end game of ssa_k_verify, per tail group: finished pieces; parked accumulators + status (152 B per lane) */ \
     X(tail_done) X(tail_park)
 
@@ -780,6 +783,13 @@ int ssa_internal_msm_agg_small(ssa_ctx *ctx, const DevBatch &b, size_t n, const 
 int ssa_internal_msm_agg_segments(ssa_ctx *ctx, const DevBatch &b, uint32_t segs, uint32_t seg_lanes,
                                   const uint8_t *d_coeffs16, const uint64_t *d_h, const uint8_t *d_mask, uint8_t *d_recheck,
                                   const uint8_t *d_rhs, uint8_t *d_seg_ok);
+
+// defined in ssa_msm.hip, for ssa_aggregate_valid_many (ssa_api.hip): the statuses of
+// ssa_verify_batch_screened (library-drawn coefficients) for ONE slice whose challenge scalars are already in d_h, into
+// d_status[0, n); d_fail != nullptr: *d_fail = the number of nonzero ones.  The messages of b are not read; d_h is only
+// read.  At most one synchronisation (none at n <= ctx->knobs.msm_small_max).
+int ssa_internal_screen_hashed(ssa_ctx *ctx, const DevBatch &b, size_t n, const uint64_t *d_h, uint8_t *d_status,
+                               unsigned long long *d_fail);
 
 // defined in ssa_api.hip: ssa_k_verify over n lanes of b (its messages unused) whose challenge scalars are already in
 // d_h (the per-lane workspace reserved for one slice of lanes); *d_fail is added to

@@ -1729,6 +1729,13 @@ static int screen_count(ssa_ctx *ctx, const uint8_t *d_status, size_t n, unsigne
     return 0;
 }
 
+int ssa_internal_screen_hashed(ssa_ctx *ctx, const DevBatch &b, size_t n, const uint64_t *d_h, uint8_t *d_status,
+                               unsigned long long *d_fail) {
+    if (!d_h || !d_status || n == 0 || n > ctx->knobs.msm_slice) return SSA_ERR_ARG;
+    if (int rc = screen_slice(ctx, b, n, nullptr, 0, (const u64 *)d_h, d_status)) return rc;
+    return d_fail ? screen_count(ctx, d_status, n, d_fail) : 0;
+}
+
 extern "C" int ssa_verify_batch_screened_device(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks,
                                                 const uint8_t *d_pk_inf, const uint8_t *d_msgs, const uint64_t *d_msg_off,
                                                 size_t msg_stride, size_t msg_len, size_t n, const uint8_t *d_coeffs,

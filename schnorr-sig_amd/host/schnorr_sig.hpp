@@ -644,6 +644,25 @@ struct AggregateSignature {
         if (rc != SSA_OK) return std::nullopt;
         return a;
     }
+    // Filtering half-aggregation: the aggregate of exactly the triples that verify under
+    // verify_batch semantics, and their indices in ascending order.  A triple that does not verify is dropped, not
+    // reported as an error; with none kept the aggregate is the empty one (32 zero bytes).
+    static std::pair<AggregateSignature, std::vector<uint32_t>>
+    aggregate_valid(Context &cx, const std::vector<Signature> &signatures, const std::vector<PublicKey> &public_keys,
+                    const std::vector<std::pair<const uint8_t *, size_t>> &messages) {
+        const PackedTriples t = pack_triples(signatures, public_keys, messages);
+        const size_t n = signatures.size();
+        AggregateSignature a;
+        a.bytes.assign(SSA_AGGREGATE_LENGTH(n), 0);
+        std::vector<uint32_t> kept(n ? n : 1, 0u);
+        uint64_t n_kept = 0;
+        const int rc = ssa_aggregate_valid_many(cx.get(), t.sigs.data(), t.pks.data(), t.inf.data(), t.flat.data(),
+                                                t.off.data(), 0, 0, n, a.bytes.data(), kept.data(), &n_kept, nullptr);
+        if (rc != 0) throw std::runtime_error(std::string("ssa_aggregate_valid_many: ") + ssa_strerror(rc));
+        a.bytes.resize(SSA_AGGREGATE_LENGTH(n_kept));
+        kept.resize(n_kept);
+        return {std::move(a), std::move(kept)};
+    }
     Result verify(Context &cx, const std::vector<PublicKey> &public_keys,
                   const std::vector<std::pair<const uint8_t *, size_t>> &messages) const {
         if (public_keys.size() != size() || messages.size() != size())

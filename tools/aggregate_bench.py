@@ -20,7 +20,18 @@ signatures each, cut out of one pool of signatures.  Legs, alternating in the sa
   many_bucket     ... under SSA_MSM_SMALL_MAX = 0 (every group: bucket path)
   loop            K calls of ssa_verify_aggregate_device on this tree's library
   loop_baseline   the same K calls through the library given by --baseline-lib (another build, e.g. the parent commit's)
-and, once, `single`: the whole pool as ONE aggregate through ssa_verify_aggregate_device."""
+and, once, `single`: the whole pool as ONE aggregate through ssa_verify_aggregate_device.
+
+--valid measures ssa_aggregate_valid_many_device against the only route there was before it, run
+through the library given by --baseline-lib (a build of the parent commit; without it, this tree's own library).  Three
+workloads of --n signatures: an honest batch, 16 bad lanes, 1 % bad lanes (a flipped bit of e, at random places).  Legs,
+alternating in the same way, every timed output checked:
+  valid                      the new call: the aggregate of the lanes that verify, and their list
+  baseline_checked           ssa_aggregate_many_device with SSA_AGG_CHECK on the whole batch: the aggregate of an honest
+                             batch, a refusal of any other
+  baseline_filtered          ssa_aggregate_many_device without the check on arrays filtered beforehand (bad lanes only;
+                             the time the caller needs to filter is NOT counted)
+The bar: valid < baseline_checked on the honest batch, valid < baseline_checked + baseline_filtered on the others."""
 import argparse
 import hashlib
 import json
@@ -202,6 +213,137 @@ def many_main(a):
     return 0 if res["mismatches"] == 0 else 1
 
 
+VALID_KERNELS = ("ssa_k_hash", "msm_k_prepare", "msm_sort", "msm_k_buckets", "msm_reduce", "msm_k_finish_seg",
+                 "screen_gather", "ssa_k_verify", "screen_scatter", "av_k_keep", "av_k_gather", "ag_k_leaf", "ag_k_tree",
+                 "ag_k_coeff", "ag_k_fold", "ag_k_pack")
+
+
+class BaselineAggregate:
+    """ssa_aggregate_many_device of a build of the library given by its path, on a context of its own"""
+
+    def __init__(self, path):
+        import ctypes as C
+        self.lib = C.CDLL(path)
+        vp, sz, i32 = C.c_void_p, C.c_size_t, C.c_int
+        self.lib.ssa_ctx_create_ex.argtypes = [C.POINTER(vp), i32, vp, sz, C.c_uint32, C.c_uint64]
+        self.lib.ssa_aggregate_many_device.argtypes = [vp, vp, vp, vp, vp, vp, sz, sz, sz, C.c_uint32, vp, vp, vp]
+        self.lib.ssa_ctx_sync.argtypes = [vp]
+        self.lib.ssa_ctx_destroy.argtypes = [vp]
+        self.lib.ssa_ctx_destroy.restype = None
+        self.ctx = vp()
+        if self.lib.ssa_ctx_create_ex(C.byref(self.ctx), 0, None, 0, 0, 0) != 0:
+            raise RuntimeError("baseline library: ssa_ctx_create_ex failed")
+
+    def aggregate(self, d_sigs, d_pks, d_msgs, n, d_agg, check):
+        rc = self.lib.ssa_aggregate_many_device(self.ctx, d_sigs, d_pks, None, d_msgs, None, 80, 80, n, 1 if check else 0,
+                                                d_agg, None, None)
+        if rc < 0:
+            raise RuntimeError("baseline library: ssa_aggregate_many_device failed (%d)" % rc)
+        return rc
+
+    def sync(self):
+        self.lib.ssa_ctx_sync(self.ctx)
+
+    def close(self):
+        self.lib.ssa_ctx_destroy(self.ctx)
+
+
+def valid_main(a):
+    import torch
+    import schnorr_sig_amd as ssa
+    dev = torch.device("cuda", 0)
+    eng = ssa.Engine(0)
+    base_path = a.baseline_lib or ssa.LIB_PATH
+    base = BaselineAggregate(base_path)
+    rng = np.random.default_rng(a.seed)
+    n = a.n
+    msgs = rng.integers(0, 256, (n, 80), dtype=np.uint8)
+    pks, honest = eng.keygen_sign_many(_scalars(rng, n), _scalars(rng, n), msgs)
+    t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)   # noqa: E731
+    d_pks, d_msgs = t(pks), t(msgs)
+    sha = lambda path: hashlib.sha256(open(path, "rb").read()).hexdigest()[:16]   # noqa: E731
+    res = {"metric": "aggregate_valid", "n": n, "msg_len": 80, "rounds": a.rounds, "warmup": a.warmup,
+           "library_sha256": sha(ssa.LIB_PATH), "baseline_sha256": sha(base_path), "baseline_is_this_tree": not a.baseline_lib,
+           "device": torch.cuda.get_device_name(0), "date": time.strftime("%Y-%m-%d"), "mismatches": 0, "workloads": []}
+
+    def wall(fn, sync):
+        sync()
+        t0 = time.perf_counter()
+        fn()
+        sync()
+        return (time.perf_counter() - t0) * 1e3
+
+    for name, n_bad in (("honest", 0), ("16 bad", 16), ("1 % bad", n // 100)):
+        bad = np.sort(rng.choice(n, size=min(n_bad, n), replace=False))
+        sigs = honest.copy()
+        sigs[bad, 49] ^= 1
+        keep = np.setdiff1d(np.arange(n), bad)
+        m = keep.size
+        d_sigs = t(sigs)
+        d_fs, d_fp, d_fm = t(sigs[keep]), t(pks[keep]), t(msgs[keep])
+        d_want = torch.zeros(49 * n + 32, dtype=torch.uint8, device=dev)          # the aggregate of the kept lanes, zeros behind
+        d_keep = torch.zeros(n, dtype=torch.int32, device=dev)
+        d_keep[:m] = t(keep.astype(np.int32))
+        if m and eng.aggregate_device(d_fs.data_ptr(), d_fp.data_ptr(), d_fm.data_ptr(), m, 80, d_want.data_ptr()) != 0:
+            res["mismatches"] += 1
+        eng.sync()
+        d_agg = torch.zeros(49 * n + 32, dtype=torch.uint8, device=dev)
+        d_kept = torch.zeros(n, dtype=torch.int32, device=dev)
+        got = {}
+
+        def valid():
+            got["m"] = eng.aggregate_valid_device(d_sigs.data_ptr(), d_pks.data_ptr(), d_msgs.data_ptr(), n, 80,
+                                                  d_agg.data_ptr(), d_kept.data_ptr())
+
+        def checked():
+            got["rc"] = base.aggregate(d_sigs.data_ptr(), d_pks.data_ptr(), d_msgs.data_ptr(), n, d_agg.data_ptr(), True)
+
+        def filtered():
+            got["rc"] = base.aggregate(d_fs.data_ptr(), d_fp.data_ptr(), d_fm.data_ptr(), m, d_agg.data_ptr(), False)
+
+        legs = {"valid": (valid, eng.sync), "baseline_checked": (checked, base.sync)}
+        if n_bad and m:
+            legs["baseline_filtered"] = (filtered, base.sync)
+        times = {leg: [] for leg in legs}
+        for rnd in range(a.warmup + a.rounds):
+            for leg, (fn, sync) in legs.items():
+                d_agg.fill_(0xEE)
+                d_kept.fill_(-1)
+                torch.cuda.synchronize()
+                ms = wall(fn, sync)
+                if leg == "valid":
+                    good = got["m"] == m and bool((d_agg == d_want).all()) and bool((d_kept == d_keep).all())
+                elif leg == "baseline_checked" and n_bad:
+                    good = got["rc"] != 0 and not bool(d_agg.any())                # refused: a zeroed aggregate
+                else:
+                    good = got["rc"] == 0 and bool((d_agg[:49 * m + 32] == d_want[:49 * m + 32]).all())
+                res["mismatches"] += 0 if good else 1
+                if rnd >= a.warmup:
+                    times[leg].append(ms)
+        med = {leg: round(float(np.median(v)), 3) for leg, v in times.items()}
+        route = round(med["baseline_checked"] + med.get("baseline_filtered", 0.0), 3)
+        w = {"workload": name, "bad_lanes": int(bad.size), "kept": int(m), "ms_median": med,
+             "ms_min": {leg: round(float(np.min(v)), 3) for leg, v in times.items()},
+             "ms_all": {leg: [round(x, 3) for x in v] for leg, v in times.items()},
+             "baseline_route_ms": route, "valid/baseline_route": round(med["valid"] / route, 3),
+             "faster_than_baseline_route": bool(med["valid"] < route)}
+        eng.sync()
+        eng.enable_timing(True)
+        valid()
+        eng.sync()
+        w["kernel_ms_avg_launches"] = {}
+        for k in VALID_KERNELS:
+            avg, cnt = eng.read_timing(k)
+            if cnt:
+                w["kernel_ms_avg_launches"][k] = [round(avg, 4), int(cnt)]
+        eng.enable_timing(False)
+        res["workloads"].append(w)
+    print(json.dumps(res))
+    eng.close()
+    base.close()
+    return 0 if res["mismatches"] == 0 else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1 << 20)
@@ -210,10 +352,15 @@ def main():
     ap.add_argument("--seed", type=int, default=0xA66)
     ap.add_argument("--many", action="append", default=[], metavar="KxS",
                     help="K aggregates of S signatures in one ssa_verify_aggregates_many call (repeatable)")
-    ap.add_argument("--baseline-lib", default=None, help="another build of the library for the loop_baseline leg")
+    ap.add_argument("--baseline-lib", default=None,
+                    help="another build of the library for the loop_baseline leg (--many) or the baseline legs (--valid)")
+    ap.add_argument("--valid", action="store_true",
+                    help="ssa_aggregate_valid_many_device against the checked call (and the unchecked one on filtered arrays)")
     a = ap.parse_args()
     if a.many:
         return many_main(a)
+    if a.valid:
+        return valid_main(a)
     import torch
     import schnorr_sig_amd as ssa
     dev = torch.device("cuda", 0)
