@@ -957,6 +957,55 @@ int ssa_debug_aggregates_many_coeffs(ssa_ctx *ctx, const uint8_t *aggs, const ui
                                      const uint8_t *pks, const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride,
                                      size_t msg_len, uint8_t *coeffs16_out);
 
+/* ---- many aggregates through a key cache, subgroup check included -----------------------
+ * ssa_verify_aggregates_many with the key cache of sections 16, 18 and 19 in front: every distinct key is checked
+ * (limbs, curve, [q]P) once and then found in the cache, a wire key is decompressed once, and an aggregate that holds a
+ * key outside the prime-order subgroup is answered SSA_INVALID_PUBLIC_KEY -- the guarantee of Signature::verify
+ * (src/signature.rs:182-186) for every lane of the aggregate.  aggs, counts (a HOST array in both forms), k and the
+ * messages are those of ssa_verify_aggregates_many; N = sum counts[j].
+ *   ssa_verify_aggregates_many_cached(_device)       N affine keys (96 bytes each, optional pk_inf), an affine cache;
+ *   ssa_verify_aggregates_many_cached_wire(_device)  N dense 49-byte keys, a cache made with SSA_KEYCACHE_WIRE.
+ * Let U be the keys as the aggregate verifier reads them: the caller's arrays, or for wire keys what
+ * ssa_decompress_many gives (the affine key, (0, 0) for a key that does not decode, and pk_inf); V_j the value
+ * ssa_verify_aggregate returns for aggregate j alone on U; ks_i the status byte ssa_keyset_status reports for key i
+ * (0, SSA_INVALID_PUBLIC_KEY for a key on the curve outside the subgroup, else SSA_MALFORMED).  Then
+ *   verdicts_out[j] = SSA_INVALID_PUBLIC_KEY   if some lane i of aggregate j has ks_i == SSA_INVALID_PUBLIC_KEY,
+ *                   = V_j                      otherwise
+ * -- an equality, not a probability (no screen is involved), in every state of the cache (cold, warm, cleared or
+ * compacted in the middle of the call, bypassed) and on both group paths of section 21.  The key decides, as in the
+ * reference and in ssa_verify_many.  A malformed key needs no rule: V_j is then SSA_MALFORMED.  An empty aggregate has no
+ * key: V_j.
+ * NOT added: a subgroup check of the R's.  Signature::verify makes none (its R is recomputed).  With every key in the
+ * subgroup the sum of the a_i R_i is forced into it; small-order parts of single R's that cancel under the
+ * transcript's coefficients remain possible.
+ * Errors: a NULL cache, a cache of the other mode, of another context or orphaned is SSA_ERR_ARG, and the cache is left
+ * untouched; every other argument error is that of ssa_verify_aggregates_many.  k == 0: SSA_OK.  The return value
+ * reports errors only.  The cache is used for every N >= 1: there is no small-batch bypass.
+ * stats_out (8 words, HOST memory in both forms, may be NULL), summed over the slices of SSA_LANE_SLICE lanes:
+ *   [0] distinct keys  [1] keys found in the cache  [2] keys checked and inserted  [3] automatic clears or compactions
+ *   [4] slices that bypassed the cache  [5] lanes at the probe bound plus rows that could not be published
+ *   [6] aggregates answered SSA_INVALID_PUBLIC_KEY  [7] 0;   [1] + [2] == [0] over the slices that used the cache.
+ * The _device forms take device pointers but for counts and stats_out.  They SYNCHRONISE the context's stream once per
+ * slice of SSA_LANE_SLICE lanes -- the key dedup's one read-back, as in ssa_verify_many_cached_device; the aggregate
+ * stages behind it are only enqueued.  A caller that passes stats_out waits once more, at the end, for words [5] and
+ * [6], which the device counts. */
+int ssa_verify_aggregates_many_cached(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *aggs, const uint64_t *counts, size_t k,
+                                      const uint8_t *pks, const uint8_t *pk_inf, const uint8_t *msgs,
+                                      const uint64_t *msg_off, size_t msg_stride, size_t msg_len, uint32_t *verdicts_out,
+                                      uint64_t stats_out[8]);
+int ssa_verify_aggregates_many_cached_device(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *d_aggs, const uint64_t *counts,
+                                             size_t k, const uint8_t *d_pks, const uint8_t *d_pk_inf, const uint8_t *d_msgs,
+                                             const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len,
+                                             uint32_t *d_verdicts_out, uint64_t stats_out[8]);
+int ssa_verify_aggregates_many_cached_wire(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *aggs, const uint64_t *counts,
+                                           size_t k, const uint8_t *pks49, const uint8_t *msgs, const uint64_t *msg_off,
+                                           size_t msg_stride, size_t msg_len, uint32_t *verdicts_out,
+                                           uint64_t stats_out[8]);
+int ssa_verify_aggregates_many_cached_wire_device(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *d_aggs,
+                                                  const uint64_t *counts, size_t k, const uint8_t *d_pks49,
+                                                  const uint8_t *d_msgs, const uint64_t *d_msg_off, size_t msg_stride,
+                                                  size_t msg_len, uint32_t *d_verdicts_out, uint64_t stats_out[8]);
+
 /* ---- filtering half-aggregation: drop the lanes that fail, aggregate the rest ----------
  * What a block producer needs: n signatures in, the aggregate of exactly the lanes that verify out, and the list of
  * those lanes.  Let S be the status vector ssa_verify_batch_screened (library-drawn coefficients) gives the input and

@@ -267,6 +267,10 @@ def _load():
         "ssa_verify_aggregates_many_device": (i32, [vp, vp, u64p, sz, vp, vp, vp, vp, sz, sz, vp]),
         "ssa_debug_aggregates_plan": (C.c_int64, [u64p, sz, sz, sz, u64p, sz]),
         "ssa_debug_aggregates_many_coeffs": (i32, [vp, vp, u64p, sz, vp, vp, vp, sz, sz, vp]),
+        "ssa_verify_aggregates_many_cached": (i32, [vp, vp, vp, u64p, sz, vp, vp, vp, vp, sz, sz, vp, vp]),
+        "ssa_verify_aggregates_many_cached_device": (i32, [vp, vp, vp, u64p, sz, vp, vp, vp, vp, sz, sz, vp, vp]),
+        "ssa_verify_aggregates_many_cached_wire": (i32, [vp, vp, vp, u64p, sz, vp, vp, vp, sz, sz, vp, vp]),
+        "ssa_verify_aggregates_many_cached_wire_device": (i32, [vp, vp, vp, u64p, sz, vp, vp, vp, sz, sz, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)      # AttributeError here == ABI symbol missing: fail loudly
@@ -521,7 +525,8 @@ class Engine:
     def keycache_create(self, capacity, wire=False, evict="clear"):
         """a key cache of `capacity` keys on this engine's device: all of its device memory, about
         4.2 KB per key, is allocated here.  wire=True (SSA_KEYCACHE_WIRE): a key is identified by
-        its 49 compressed bytes as received; such a cache serves verify_keyed_many_cached and no other call.
+        its 49 compressed bytes as received; such a cache serves verify_keyed_many_cached and (with dense 49-byte keys)
+        verify_aggregates_cached, and no other call.
         evict="recent" (KeyCache.set_eviction): a full cache keeps the keys used most recently
         instead of clearing itself."""
         if evict not in KEYCACHE_EVICT:
@@ -771,6 +776,82 @@ class Engine:
             addr(d_pk_inf), addr(d_msgs), addr(d_offsets), msg_stride if msg_stride is not None else msg_len, msg_len,
             addr(d_verdicts)), "ssa_verify_aggregates_many_device")
         return d_verdicts
+
+    # ---- many aggregates through a key cache (include/schnorr_sig_amd.h) ----
+    def verify_aggregates_cached(self, cache, aggregates, keys, msgs, pk_inf=None, offsets=None):
+        """verify_aggregates with the key cache in front and the subgroup check of every key included -> (uint32[k],
+        stats uint64[8]).  keys: (N, 96) affine keys with an affine cache, (N, 49) compressed keys with a cache made with
+        wire=True (then pk_inf must be None: the wire form carries the flag).  An aggregate that holds a key outside the
+        prime-order subgroup is answered INVALID_PUBLIC_KEY; every other verdict is the one verify_aggregate gives that
+        aggregate alone, in every state of the cache.  stats: [0] distinct keys, [1] found in the cache, [2] checked and
+        inserted, [3] automatic clears or compactions, [4] slices that bypassed the cache, [5] lanes at the probe bound
+        plus rows that could not be published, [6] aggregates answered INVALID_PUBLIC_KEY."""
+        counts, wire = pack_aggregates(aggregates)
+        n, k = int(counts.sum()), counts.size
+        width = 49 if cache.wire else 96
+        keys = np.ascontiguousarray(keys, dtype=np.uint8)
+        if keys.ndim != 2 and keys.size:
+            raise ValueError("keys must be an (N, %d) array" % width)
+        if keys.size and keys.shape[1] != width:
+            raise ValueError("a %s key cache takes (N, %d) keys, not (N, %d)"
+                             % ("wire" if cache.wire else "affine", width, keys.shape[1]))
+        if cache.wire and pk_inf is not None:
+            raise ValueError("pk_inf does not go with wire keys: the 49 bytes carry the identity flag")
+        keys = keys.reshape(-1, width)
+        if keys.shape[0] != n:
+            raise MalformedInput("We should have the same number of signatures than public keys")
+        inf = _np_u8(pk_inf) if pk_inf is not None else None
+        if inf is not None and inf.size != n:
+            raise ValueError("pk_inf needs one byte per key")
+        m, off, stride, mlen = self._msg_args(msgs, offsets, n) if n else (None, None, 0, 0)
+        out = np.full(k, 255, dtype=np.uint32)
+        stats = np.zeros(8, dtype=np.uint64)
+        head = (self._ctx, cache.handle, _ptr(wire) if k else None,
+                counts.ctypes.data_as(C.POINTER(C.c_uint64)) if k else None, k, _ptr(keys) if n else None)
+        tail = (_ptr(m), _ptr(off), stride, mlen, _ptr(out) if k else None, stats.ctypes.data)
+        if cache.wire:
+            _check(_lib.ssa_verify_aggregates_many_cached_wire(*head, *tail), "ssa_verify_aggregates_many_cached_wire")
+        else:
+            _check(_lib.ssa_verify_aggregates_many_cached(*head, _ptr(inf), *tail), "ssa_verify_aggregates_many_cached")
+        return out, stats
+
+    def verify_aggregates_cached_device(self, cache, d_aggs, counts, d_keys, d_msgs, d_verdicts=None, d_pk_inf=None,
+                                        d_offsets=None, msg_len=None, msg_stride=None, want_stats=True):
+        """device form over torch tensors, as verify_aggregates_device: d_keys holds N x 96 or (wire cache) N x 49 bytes.
+        One synchronisation per slice of SSA_LANE_SLICE lanes (the key dedup's); the aggregate stages are only enqueued,
+        and with want_stats the call waits once more for the two words the device counts.  -> (d_verdicts, stats or
+        None)"""
+        import torch
+        counts = np.ascontiguousarray(counts, dtype=np.uint64)
+        k, n = counts.size, int(counts.sum())
+        if cache.wire and d_pk_inf is not None:
+            raise ValueError("pk_inf does not go with wire keys: the 49 bytes carry the identity flag")
+        # the kernels read width * N key bytes and N flags: a tensor of the other mode's width would be read past its end
+        width = 49 if cache.wire else 96
+        have = 0 if d_keys is None else d_keys.numel() * d_keys.element_size()
+        if have != n * width:
+            raise ValueError("a %s key cache takes %d key bytes for %d lanes, not %d"
+                             % ("wire" if cache.wire else "affine", n * width, n, have))
+        if d_pk_inf is not None and d_pk_inf.numel() * d_pk_inf.element_size() != n:
+            raise ValueError("pk_inf needs one byte per key")
+        if d_verdicts is None:
+            d_verdicts = torch.empty(max(k, 1), dtype=torch.int32, device=d_aggs.device)[:k]
+        if d_offsets is None and msg_len is None:
+            msg_len = d_msgs.shape[1] if d_msgs is not None and d_msgs.dim() == 2 else 0
+        msg_len = msg_len or 0
+        stats = np.zeros(8, dtype=np.uint64) if want_stats else None
+        addr = lambda t: t.data_ptr() if t is not None and t.numel() else None    # noqa: E731
+        head = (self._ctx, cache.handle, addr(d_aggs), counts.ctypes.data_as(C.POINTER(C.c_uint64)) if k else None, k,
+                addr(d_keys))
+        tail = (addr(d_msgs), addr(d_offsets), msg_stride if msg_stride is not None else msg_len, msg_len,
+                addr(d_verdicts), stats.ctypes.data if want_stats else None)
+        if cache.wire:
+            _check(_lib.ssa_verify_aggregates_many_cached_wire_device(*head, *tail),
+                   "ssa_verify_aggregates_many_cached_wire_device")
+        else:
+            _check(_lib.ssa_verify_aggregates_many_cached_device(*head, addr(d_pk_inf), *tail),
+                   "ssa_verify_aggregates_many_cached_device")
+        return d_verdicts, stats
 
     def aggregates_coeffs(self, aggregates, pks, msgs, offsets=None):
         """tests: the coefficients of all N lanes as verify_aggregates derives them -> uint8[N, 16]"""
@@ -1789,6 +1870,27 @@ class AggregateSignature:
         if st == MALFORMED:
             raise MalformedInput("undecodable aggregate (non-canonical limb or scalar, R or key off the curve)")
         raise SignatureError(SignatureError.InvalidSignature)
+
+    @staticmethod
+    def verify_many(aggregates, public_keys, messages, cache=None, engine=None):
+        """Many aggregates in one call (DESIGN.md sections 21 and 23): the PublicKey objects and messages of all their
+        lanes, in order -> uint32[k], one status per aggregate, each the value verify() stands for on that aggregate
+        alone.  With a KeyCache every key's subgroup check is included (INVALID_PUBLIC_KEY for an aggregate that holds a
+        key outside the prime-order subgroup) and runs once per key and cache; a cache made with wire=True is handed the
+        keys' 49 compressed bytes."""
+        eng = engine or (cache.engine if cache is not None else default_engine())
+        n = sum(len(a) for a in aggregates)
+        if len(public_keys) != n or len(messages) != n:
+            raise MalformedInput("We should have the same number of messages than public keys")
+        flat, off = pack_messages(messages)
+        pks = np.frombuffer(b"".join(p.affine for p in public_keys), np.uint8).reshape(-1, 96)
+        inf = np.array([1 if p.is_identity else 0 for p in public_keys], np.uint8)
+        if cache is None:
+            return eng.verify_aggregates(aggregates, pks, flat, pk_inf=inf, offsets=off)
+        if cache.wire:
+            wire, _ = eng.compress_many(pks, pk_inf=inf) if n else (np.zeros((0, 49), np.uint8), None)
+            return eng.verify_aggregates_cached(cache, aggregates, np.asarray(wire).reshape(-1, 49), flat, offsets=off)[0]
+        return eng.verify_aggregates_cached(cache, aggregates, pks, flat, pk_inf=inf, offsets=off)[0]
 
     def to_bytes(self):
         return self.bytes

@@ -6,6 +6,7 @@
 #include "ssa_keycache.hpp"
 #include "ssa_keyed.hpp"
 #include "ssa_aggregate.hpp"
+#include "ssa_aggcache.hpp"
 
 #include <sys/random.h>
 
@@ -1091,10 +1092,11 @@ static int dedup_fingerprint_key(ssa_ctx *ctx) {
 constexpr size_t TAB_WORDS = (size_t)(PTAB_ENTRIES * PTAB_ENTRY_U64), TAB_BYTES = TAB_WORDS * sizeof(u64);
 
 // Where the keys of a slice are, and with that what identifies a key (ssa_dedup.hpp): 96-byte affine keys with their
-// optional pk_inf bytes, or (keyed non-null; the other two unused) the 49 compressed bytes in front of 130-byte wire
-// records (ssa_keyed.hpp)
+// optional pk_inf bytes, or (keyed non-null; the other two unused) the 49 compressed bytes of wire keys `stride` bytes
+// apart: in front of 130-byte wire records (ssa_keyed.hpp), or side by side (stride 49: DESIGN.md section 23)
 struct KeySource {
     const uint8_t *pks, *pk_inf, *keyed;
+    uint32_t stride = 130;
 };
 
 // The distinct keys of cnt <= lane_slice lanes on ctx->stream, into the context's workspaces: dd_idx (a key index per
@@ -1125,8 +1127,8 @@ static int dedup_slice(ssa_ctx *ctx, const KeySource &src, size_t cnt, uint64_t 
         const u32 mask = (u32)(cap - 1), bound = (u32)ctx->knobs.dedup_probe_bound;
         u32 *rep = (u32 *)ctx->dd_rep.p;
         if (src.keyed)
-            hipLaunchKernelGGL(ky_k_insert, grid, block, 0, ctx->stream, src.keyed, (u32)cnt, k0, k1, slots, mask, bound, rep,
-                               blk_cnt, d_stats);
+            hipLaunchKernelGGL(ky_k_insert, grid, block, 0, ctx->stream, src.keyed, src.stride, (u32)cnt, k0, k1, slots, mask,
+                               bound, rep, blk_cnt, d_stats);
         else
             hipLaunchKernelGGL(dd_k_insert, grid, block, 0, ctx->stream, src.pks, src.pk_inf, (u32)cnt, k0, k1, slots, mask,
                                bound, rep, blk_cnt, d_stats);
@@ -1161,8 +1163,8 @@ static int key_rows_build(ssa_ctx *ctx, const KeySource &src, const char *gather
                           u64 *pks, u8 *inf, u64 *wire, u64 *tab, u8 *status) {
     const int rc = timed_launch(ctx, src.keyed ? "ssa_k_keyed_decompress" : gather_stage, [&] {
         if (src.keyed)
-            hipLaunchKernelGGL(ky_k_decompress, dim3(grid_for(m, 256)), dim3(256), 0, ctx->stream, src.keyed, reps, (u32)m,
-                               (u32)cnt, pks, inf, wire);
+            hipLaunchKernelGGL(ky_k_decompress, dim3(grid_for(m, 256)), dim3(256), 0, ctx->stream, src.keyed, src.stride, reps,
+                               (u32)m, (u32)cnt, pks, inf, wire);
         else
             hipLaunchKernelGGL(dd_k_gather, dim3(grid_for(m * 12, DD_BLOCK)), dim3(DD_BLOCK), 0, ctx->stream, src.pks,
                                src.pk_inf, reps, (u32)m, pks, inf);
@@ -1629,8 +1631,8 @@ static int keycache_lookup(ssa_ctx *ctx, ssa_keycache *kc, const KeySource &src,
         const u32 mask = (u32)(kc->n_slots - 1), bound = (u32)ctx->knobs.dedup_probe_bound, held = (u32)kc->held,
                   epoch = (u32)kc->epoch;
         if (src.keyed)
-            hipLaunchKernelGGL(ky_k_lookup, grid, block, 0, ctx->stream, src.keyed, reps, (u32)cnt, stats, k0, k1, slots, mask,
-                               bound, (const u64 *)kc->wire.p, held, found, blk_cnt, stamps, epoch);
+            hipLaunchKernelGGL(ky_k_lookup, grid, block, 0, ctx->stream, src.keyed, src.stride, reps, (u32)cnt, stats, k0, k1,
+                               slots, mask, bound, (const u64 *)kc->wire.p, held, found, blk_cnt, stamps, epoch);
         else
             hipLaunchKernelGGL(kc_k_lookup, grid, block, 0, ctx->stream, src.pks, src.pk_inf, reps, (u32)cnt, stats, k0, k1,
                                slots, mask, bound, (const u64 *)kc->rows.pks.p, (const u8 *)kc->inf.p, held, found, blk_cnt,
@@ -1645,19 +1647,28 @@ static int keycache_lookup(ssa_ctx *ctx, ssa_keycache *kc, const KeySource &src,
 // ONE slice of cnt lanes through the cache, for affine keys and wire records alike (a wire cache for wire records: the
 // callers check): the distinct keys found and looked up, the misses checked and inserted -- or the cache cleared or
 // compacted first, or bypassed (kc_plan).  One synchronisation, the one of the dedup.  For wire records the signatures
-// are split off in front and every lane's key bytes and flag expanded out of the rows behind: *b (unused otherwise).
+// are split off in front and every lane's key bytes and flag expanded out of the rows behind: *b (required for records,
+// unused otherwise).  Dense wire keys (src.stride == 49: no records, nothing to split) are not expanded here either: *rows
+// says where the rows are that kv->lane_key numbers -- the cache's, or under a bypass the context's own -- and the
+// caller gathers from them.
+struct KeyRows {
+    const u64 *pks;
+    const u8 *inf;
+};
 static int keycache_slice(ssa_ctx *ctx, ssa_keycache *kc, const KeySource &src, size_t cnt, DevBatch *b, KeyView *kv,
-                          uint64_t *u_out, uint64_t *bound_hits_out, uint64_t ks[4], const unsigned long long **d_unpublished) {
-    const bool wire = src.keyed != nullptr;
+                          uint64_t *u_out, uint64_t *bound_hits_out, uint64_t ks[4], const unsigned long long **d_unpublished,
+                          KeyRows *rows = nullptr) {
+    const bool records = src.keyed != nullptr && src.stride == 130;
+    if (records && !b) return SSA_ERR_ARG;
     const size_t nb = grid_for(cnt, DD_BLOCK);
     if (ctx->kc_found.reserve(cnt * sizeof(u32)) || ctx->kc_missrep.reserve(cnt * sizeof(u32)) ||
         ctx->kc_blk.reserve(2 * nb * sizeof(u32)) || ctx->kc_lane_row.reserve(cnt * sizeof(u32)))
         return SSA_ERR_HIP;
-    if (wire && (ctx->ky_sigs.reserve(cnt * 81 + 16) || ctx->ky_pks.reserve(cnt * 96) || ctx->ky_inf.reserve(cnt + 16)))
+    if (records && (ctx->ky_sigs.reserve(cnt * 81 + 16) || ctx->ky_pks.reserve(cnt * 96) || ctx->ky_inf.reserve(cnt + 16)))
         return SSA_ERR_HIP;
     u32 *found = (u32 *)ctx->kc_found.p, *miss_rep = (u32 *)ctx->kc_missrep.p;
     int rc = 0;
-    if (wire) {
+    if (records) {
         rc = timed_launch(ctx, "keyed_split", [&] {
             hipLaunchKernelGGL(ky_k_split, dim3(grid_for((cnt * 81 + 3) / 4, 256)), dim3(256), 0, ctx->stream, src.keyed, cnt,
                                (u8 *)ctx->ky_sigs.p);
@@ -1696,7 +1707,7 @@ static int keycache_slice(ssa_ctx *ctx, ssa_keycache *kc, const KeySource &src, 
         const size_t base = pl.base, fresh = pl.fresh;
         if (fresh) {        // rows base .. base + fresh: the keys, their checks and tables, then (complete) their slots
             if ((rc = key_rows_build(ctx, src, "keycache_insert", pl.reps, fresh, cnt, c_pks + 12 * base, c_inf + base,
-                                     wire ? (u64 *)kc->wire.p + KY_WIRE_WORDS * base : nullptr,
+                                     src.keyed ? (u64 *)kc->wire.p + KY_WIRE_WORDS * base : nullptr,
                                      (u64 *)kc->rows.tab.p + base * TAB_WORDS, (u8 *)kc->rows.status.p + base)))
                 return rc;
             if ((rc = timed_launch(ctx, "keycache_insert", [&] { keycache_publish_launch(ctx, kc, base, fresh, d_unpub); })))
@@ -1712,7 +1723,8 @@ static int keycache_slice(ssa_ctx *ctx, ssa_keycache *kc, const KeySource &src, 
         *kv = {(const uint32_t *)ctx->kc_lane_row.p, (const uint64_t *)kc->rows.tab.p, (const uint8_t *)kc->rows.status.p,
                (uint32_t)kc->capacity};
     }
-    if (!wire) return 0;
+    if (rows) *rows = {row_pks, row_inf};
+    if (!records) return 0;
     rc = timed_launch(ctx, "keyed_expand", [&] {
         hipLaunchKernelGGL(ky_k_expand, dim3(grid_for(cnt * 12, 256)), dim3(256), 0, ctx->stream, kv->lane_key, row_pks,
                            row_inf, kv->n_keys, (u32)cnt, (u64 *)ctx->ky_pks.p, (u8 *)ctx->ky_inf.p);
@@ -2299,6 +2311,146 @@ extern "C" int ssa_verify_aggregates_many(ssa_ctx *ctx, const uint8_t *aggs, con
     const MsgView mv = hc.msgs(msgs, msg_off, msg_stride, msg_len, n);
     uint32_t *d_verdicts = (uint32_t *)hc.out(ctx->st_status, verdicts_out, k * sizeof(uint32_t), 16);
     return hc.finish([&] { return agm_run(ctx, pl, d_aggs, k, d_pks, d_inf, mv, n, d_verdicts); });
+}
+
+// ------------------------------------------------------------------ aggregates through a key cache
+// The cache in front of agm_run, and the fold of the key statuses behind it.  The N lanes go through the cache in slices
+// of at most lane_slice lanes, in order, whatever the aggregate boundaries; a later slice may clear or compact the
+// cache, so each slice leaves what the aggregate stages need of its rows in N-lane buffers of the context
+// (agc_k_expand) before the next one starts.  Then agm_run as it is over U, then agc_k_key_verdicts.
+// wire: d_keys = N dense 49-byte keys (a wire cache), else N affine keys with d_pk_inf (an affine cache).
+// sv (or nullptr): words 0..4 of the statistics and the host's part of word 5; the device's part of word 5 and word 6
+// are ctx->agc_cnt, read by the caller behind everything queued here.  One synchronisation per slice, the dedup's.
+static int agc_check_cache(const ssa_ctx *ctx, const ssa_keycache *kc, bool wire) {
+    return !ctx || !kc || kc->ctx != ctx || kc->wire_mode != wire ? SSA_ERR_ARG : 0;
+}
+
+static int agc_run(ssa_ctx *ctx, ssa_keycache *kc, const AgPlan &pl, const uint8_t *d_aggs, size_t k, const uint8_t *d_keys,
+                   const uint8_t *d_pk_inf, bool wire, const MsgView &mv, size_t n, uint32_t *d_verdicts_out, uint64_t *sv) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (ctx->agc_cnt.reserve(64) || ctx->agc_kst.reserve(n + 16) ||
+        (wire && (ctx->agc_pks.reserve(n * 96 + 16) || ctx->agc_inf.reserve(n + 16))))
+        return SSA_ERR_HIP;
+    unsigned long long *d_cnt = (unsigned long long *)ctx->agc_cnt.p;
+    HIP_TRY(hipMemsetAsync(d_cnt, 0, AGC_CNT_WORDS * sizeof(unsigned long long), ctx->stream));
+    u8 *kst = (u8 *)ctx->agc_kst.p, *u_inf = wire ? (u8 *)ctx->agc_inf.p : nullptr;
+    u64 *u_pks = wire ? (u64 *)ctx->agc_pks.p : nullptr;
+    const size_t slice = ctx->knobs.lane_slice;
+    for (size_t lo = 0; lo < n; lo += slice) {
+        const size_t cnt = n - lo < slice ? n - lo : slice;
+        const KeySource src = wire ? KeySource{nullptr, nullptr, d_keys + 49 * lo, 49}
+                                   : KeySource{d_keys + 96 * lo, d_pk_inf ? d_pk_inf + lo : nullptr, nullptr};
+        KeyView kv{};
+        KeyRows rows{};
+        uint64_t u = 0, hits = 0, ks[4] = {0, 0, 0, 0};
+        const unsigned long long *d_unpub = nullptr;
+        if (int rc = keycache_slice(ctx, kc, src, cnt, nullptr, &kv, &u, &hits, ks, &d_unpub, &rows)) return rc;
+        const int rc = timed_launch(ctx, "agc_expand", [&] {
+            hipLaunchKernelGGL(agc_k_expand, dim3(grid_for(wire ? cnt * 12 : cnt, 256)), dim3(256), 0, ctx->stream, kv.lane_key,
+                               kv.status, wire ? rows.pks : (const u64 *)nullptr, rows.inf, kv.n_keys, (u32)cnt, kst + lo,
+                               wire ? u_pks + 12 * lo : (u64 *)nullptr, wire ? u_inf + lo : (u8 *)nullptr, d_unpub, d_cnt);
+        });
+        if (rc) return rc;
+        if (sv) {
+            sv[0] += u;
+            for (int w = 0; w < 4; w++) sv[1 + w] += ks[w];
+            sv[5] += hits;
+        }
+    }
+    if (int rc = agm_run(ctx, pl, d_aggs, k, wire ? (const u8 *)u_pks : d_keys, wire ? (const u8 *)u_inf : d_pk_inf, mv, n,
+                         d_verdicts_out))
+        return rc;
+    if (n == 0) return 0;       // (no lane, no key: every verdict is V_j)
+    return timed_launch(ctx, "agc_k_key_verdicts", [&] {
+        hipLaunchKernelGGL(agc_k_key_verdicts, dim3(grid_for(k, AGC_WAVES)), dim3(AGC_BLOCK), 0, ctx->stream, (const u8 *)kst,
+                           (const u32 *)ctx->agm_plan.p, (u32)k, d_verdicts_out, d_cnt);
+    });
+}
+
+// statistics words 5 and 6 from the counters the device kept
+static void agc_stats_out(uint64_t stats_out[8], const uint64_t sv[8], const unsigned long long cnt[AGC_CNT_WORDS]) {
+    if (!stats_out) return;
+    for (int w = 0; w < 8; w++) stats_out[w] = sv[w];
+    stats_out[5] += cnt[AGC_CNT_UNPUB];
+    stats_out[6] = cnt[AGC_CNT_BAD];
+}
+
+static int agc_device(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *d_aggs, const uint64_t *counts, size_t k,
+                      const uint8_t *d_keys, const uint8_t *d_pk_inf, bool wire, const MsgView &mv, uint32_t *d_verdicts_out,
+                      uint64_t stats_out[8]) {
+    AgPlan pl;
+    size_t n = 0;
+    if (int rc = agc_check_cache(ctx, kc, wire)) return rc;
+    if (int rc = agm_check_args(ctx, d_aggs, counts, k, d_keys, mv, d_verdicts_out, pl, &n)) return rc;
+    uint64_t sv[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned long long cnt[AGC_CNT_WORDS] = {0, 0};
+    agc_stats_out(stats_out, sv, cnt);      // (still empty: the caller's words are zeroed)
+    if (k == 0) return SSA_OK;
+    if (int rc = agc_run(ctx, kc, pl, d_aggs, k, d_keys, d_pk_inf, wire, mv, n, d_verdicts_out, sv)) return rc;
+    if (!stats_out) return 0;
+    // the two words the device counted: read behind the aggregate stages, the one extra wait of a caller that asks
+    HIP_TRY(hipMemcpyAsync(cnt, ctx->agc_cnt.p, sizeof cnt, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    agc_stats_out(stats_out, sv, cnt);
+    return 0;
+}
+
+static int agc_host(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *aggs, const uint64_t *counts, size_t k,
+                    const uint8_t *keys, const uint8_t *pk_inf, bool wire, const uint8_t *msgs, const uint64_t *msg_off,
+                    size_t msg_stride, size_t msg_len, uint32_t *verdicts_out, uint64_t stats_out[8]) {
+    AgPlan pl;
+    size_t n = 0;
+    if (int rc = agc_check_cache(ctx, kc, wire)) return rc;
+    if (int rc = agm_check_args(ctx, aggs, counts, k, keys, {msgs, msg_off, msg_stride, msg_len}, verdicts_out, pl, &n)) return rc;
+    if (int rc = check_host_offsets(msg_off, n)) return rc;
+    uint64_t sv[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned long long cnt[AGC_CNT_WORDS] = {0, 0};
+    agc_stats_out(stats_out, sv, cnt);      // (still empty: the caller's words are zeroed)
+    if (k == 0) return SSA_OK;
+    HostCall hc(ctx);
+    const u8 *d_aggs = hc.in(ctx->st_sigs, aggs, 49 * n + 32 * k);
+    const u8 *d_keys = wire ? hc.in(ctx->st_keyed, keys, n * 49) : hc.in(ctx->st_pks, keys, n * 96);
+    const u8 *d_inf = pk_inf ? hc.in(ctx->st_inf, pk_inf, n) : nullptr;
+    const MsgView mv = hc.msgs(msgs, msg_off, msg_stride, msg_len, n);
+    uint32_t *d_verdicts = (uint32_t *)hc.out(ctx->st_status, verdicts_out, k * sizeof(uint32_t), 16);
+    (void)hc.out(ctx->agc_cnt, cnt, sizeof cnt, 48);      // (copied back behind the verdicts)
+    if (int rc = hc.finish([&] { return agc_run(ctx, kc, pl, d_aggs, k, d_keys, d_inf, wire, mv, n, d_verdicts, sv); }))
+        return rc;
+    agc_stats_out(stats_out, sv, cnt);
+    return 0;
+}
+
+extern "C" int ssa_verify_aggregates_many_cached_device(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *d_aggs,
+                                                        const uint64_t *counts, size_t k, const uint8_t *d_pks,
+                                                        const uint8_t *d_pk_inf, const uint8_t *d_msgs,
+                                                        const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len,
+                                                        uint32_t *d_verdicts_out, uint64_t stats_out[8]) {
+    return agc_device(ctx, kc, d_aggs, counts, k, d_pks, d_pk_inf, false, {d_msgs, d_msg_off, msg_stride, msg_len},
+                      d_verdicts_out, stats_out);
+}
+
+extern "C" int ssa_verify_aggregates_many_cached(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *aggs, const uint64_t *counts,
+                                                 size_t k, const uint8_t *pks, const uint8_t *pk_inf, const uint8_t *msgs,
+                                                 const uint64_t *msg_off, size_t msg_stride, size_t msg_len,
+                                                 uint32_t *verdicts_out, uint64_t stats_out[8]) {
+    return agc_host(ctx, kc, aggs, counts, k, pks, pk_inf, false, msgs, msg_off, msg_stride, msg_len, verdicts_out, stats_out);
+}
+
+extern "C" int ssa_verify_aggregates_many_cached_wire_device(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *d_aggs,
+                                                             const uint64_t *counts, size_t k, const uint8_t *d_pks49,
+                                                             const uint8_t *d_msgs, const uint64_t *d_msg_off,
+                                                             size_t msg_stride, size_t msg_len, uint32_t *d_verdicts_out,
+                                                             uint64_t stats_out[8]) {
+    return agc_device(ctx, kc, d_aggs, counts, k, d_pks49, nullptr, true, {d_msgs, d_msg_off, msg_stride, msg_len},
+                      d_verdicts_out, stats_out);
+}
+
+extern "C" int ssa_verify_aggregates_many_cached_wire(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *aggs,
+                                                      const uint64_t *counts, size_t k, const uint8_t *pks49,
+                                                      const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride,
+                                                      size_t msg_len, uint32_t *verdicts_out, uint64_t stats_out[8]) {
+    return agc_host(ctx, kc, aggs, counts, k, pks49, nullptr, true, msgs, msg_off, msg_stride, msg_len, verdicts_out,
+                    stats_out);
 }
 
 // tests: the plan of a call from its counts alone (no device): out[0..4) = lanes, tree passes, groups, descriptors in

@@ -187,6 +187,9 @@ struct CtxKnobs {
     /* filtering half-aggregation: per-workgroup counts and offsets of the kept lanes (the \
        length of the list behind them), and the kept lanes' signatures and raw digests side by side */ \
     X(av_blk) X(av_sigs) X(av_dig) \
+    /* aggregates through a key cache (ssa_aggcache.hpp): per lane of the CALL (not of a slice) \
+       its key's status byte and, for wire keys, its 96 key bytes and pk_inf boolean; and the call's two counters */ \
+    X(agc_kst) X(agc_pks) X(agc_inf) X(agc_cnt) \
     /* the end game of ssa_k_verify, per tail group: finished pieces; parked accumulators + status (152 B per lane) */ \
     X(tail_done) X(tail_park)
 

@@ -89,9 +89,10 @@ SSA_DEV u32 dd_key_flag(const u8 *__restrict__ pk_inf, size_t i) { return pk_inf
 
 constexpr int KY_WIRE_WORDS = 7;      // a wire key's 49 bytes: six words of x, one word holding the flag byte
 
-// word k < 6 of x, or (k == 6) the flag byte, of record i (records are 130 bytes apart: never aligned)
-SSA_DEV u64 ky_wire_word(const u8 *__restrict__ keyed, size_t i, int k) {
-    const u8 *p = keyed + 130 * i;
+// word k < 6 of x, or (k == 6) the flag byte, of wire key i; the keys are `stride` bytes apart: 130 in front of wire
+// records, 49 side by side (never aligned either way)
+SSA_DEV u64 ky_wire_word(const u8 *__restrict__ keyed, size_t i, int k, u32 stride) {
+    const u8 *p = keyed + (size_t)stride * i;
     return k < 6 ? ld_u64_le(p + 8 * k) : (u64)p[48];
 }
 
@@ -110,7 +111,8 @@ SSA_DEV u64 dd_fingerprint(const u64 w[12], u32 flag, u64 k0, u64 k1) {
 struct DdWireLanes {
     static constexpr int WORDS = KY_WIRE_WORDS, BYTES = 49;
     const u8 *keyed;
-    SSA_DEV u64 word(size_t i, int k) const { return ky_wire_word(keyed, i, k); }
+    u32 stride = 130;       // bytes from one lane's key to the next: wire records by default, 49 for dense keys
+    SSA_DEV u64 word(size_t i, int k) const { return ky_wire_word(keyed, i, k, stride); }
 };
 struct DdAffineRows {
     static constexpr int WORDS = 13, BYTES = 97;

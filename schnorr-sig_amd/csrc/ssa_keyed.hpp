@@ -45,18 +45,20 @@ ky_k_split(const u8 *__restrict__ keyed, size_t n, u8 *__restrict__ sigs_out) {
 }
 
 // dd_k_insert, kc_k_lookup and kc_k_publish for wire keys: the shared bodies over the 49 bytes of the records and the
-// seven words of the rows (c_wire)
+// seven words of the rows (c_wire).  stride: the bytes from one lane's key to the next, 130 for records, 49 for dense
+// keys (ssa_verify_aggregates_many_cached_wire)
 __global__ void __launch_bounds__(256)
-ky_k_insert(const u8 *__restrict__ keyed, u32 n, u64 k0, u64 k1, u64 *__restrict__ slots, u32 mask, u32 bound,
+ky_k_insert(const u8 *__restrict__ keyed, u32 stride, u32 n, u64 k0, u64 k1, u64 *__restrict__ slots, u32 mask, u32 bound,
             u32 *__restrict__ rep, u32 *__restrict__ blk_cnt, unsigned long long *__restrict__ stats) {
-    dd_insert_body(DdWireLanes{keyed}, n, k0, k1, slots, mask, bound, rep, blk_cnt, stats);
+    dd_insert_body(DdWireLanes{keyed, stride}, n, k0, k1, slots, mask, bound, rep, blk_cnt, stats);
 }
 __global__ void __launch_bounds__(256)
-ky_k_lookup(const u8 *__restrict__ keyed, const u32 *__restrict__ reps, u32 n, const unsigned long long *__restrict__ stats,
-            u64 k0, u64 k1, const u64 *__restrict__ slots, u32 mask, u32 bound, const u64 *__restrict__ c_wire, u32 held,
-            u32 *__restrict__ found, u32 *__restrict__ blk_cnt, u32 *__restrict__ stamps, u32 epoch) {
-    kc_lookup_body(DdWireLanes{keyed}, DdWireRows{c_wire}, reps, n, stats, k0, k1, slots, mask, bound, held, found, blk_cnt,
-                   stamps, epoch);
+ky_k_lookup(const u8 *__restrict__ keyed, u32 stride, const u32 *__restrict__ reps, u32 n,
+            const unsigned long long *__restrict__ stats, u64 k0, u64 k1, const u64 *__restrict__ slots, u32 mask,
+            u32 bound, const u64 *__restrict__ c_wire, u32 held, u32 *__restrict__ found, u32 *__restrict__ blk_cnt,
+            u32 *__restrict__ stamps, u32 epoch) {
+    kc_lookup_body(DdWireLanes{keyed, stride}, DdWireRows{c_wire}, reps, n, stats, k0, k1, slots, mask, bound, held, found,
+                   blk_cnt, stamps, epoch);
 }
 __global__ void __launch_bounds__(256)
 ky_k_publish(const u64 *__restrict__ c_wire, u32 base, u32 m, u64 k0, u64 k1, u64 *__restrict__ slots, u32 mask,
@@ -68,13 +70,13 @@ ky_k_publish(const u64 *__restrict__ c_wire, u32 base, u32 m, u64 k0, u64 k1, u6
 // it fills); out_wire (or nullptr: the context's own workspaces, which keep no wire bytes) gets the 49 bytes.  A key
 // that does not decode leaves (0, 0) and no flag.
 __global__ void __launch_bounds__(256)
-ky_k_decompress(const u8 *__restrict__ keyed, const u32 *__restrict__ reps, u32 m, u32 n, u64 *__restrict__ out_pks,
-                u8 *__restrict__ out_inf, u64 *__restrict__ out_wire) {
+ky_k_decompress(const u8 *__restrict__ keyed, u32 stride, const u32 *__restrict__ reps, u32 m, u32 n,
+                u64 *__restrict__ out_pks, u8 *__restrict__ out_inf, u64 *__restrict__ out_wire) {
     const u32 t = blockIdx.x * 256 + threadIdx.x;
     if (t >= m) return;
     const u32 i = reps[t];
     if (i >= n) return;       // (never: a representative is a lane of the slice)
-    const u8 *rec = keyed + 130 * (size_t)i;
+    const u8 *rec = keyed + (size_t)stride * i;
     aff p;
     bool inf;
     (void)decompress_lane(rec, p, inf);
@@ -86,7 +88,7 @@ ky_k_decompress(const u8 *__restrict__ keyed, const u32 *__restrict__ reps, u32 
     out_inf[t] = inf ? 1 : 0;
     if (out_wire) {
 #pragma unroll
-        for (int k = 0; k < KY_WIRE_WORDS; k++) out_wire[(size_t)t * KY_WIRE_WORDS + k] = ky_wire_word(keyed, i, k);
+        for (int k = 0; k < KY_WIRE_WORDS; k++) out_wire[(size_t)t * KY_WIRE_WORDS + k] = ky_wire_word(keyed, i, k, stride);
     }
 }
 

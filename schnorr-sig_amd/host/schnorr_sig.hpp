@@ -621,6 +621,8 @@ inline std::vector<uint8_t> verify_batch_statuses(Context &cx, const std::vector
     });
 }
 
+class KeyCache;
+
 // The half-aggregate of n signatures: their R's, 49 bytes each, and e_agg = sum a_i e_i mod q with
 // coefficients hashed out of every R, key, message and the order of the lanes -- 49 n + 32 bytes for 81 n.  verify_batch
 // semantics: the flag byte of R is honoured, there is no subgroup check.
@@ -695,6 +697,19 @@ struct AggregateSignature {
         if (rc != 0) throw std::runtime_error(std::string("ssa_verify_aggregates_many: ") + ssa_strerror(rc));
         return verdicts;
     }
+    // The same through a key cache, the subgroup check of every key included: an aggregate that
+    // holds a key outside the prime-order subgroup gets SSA_INVALID_PUBLIC_KEY, every other status is verify_many's, in
+    // every state of the cache; each distinct key is checked once per cache.  An Affine cache takes PublicKey objects; a
+    // Wire cache takes the keys as they arrive, 49 bytes each side by side, and decompresses each distinct one once.
+    // stats_out: 8 words, optional.  (Defined behind KeyCache.)
+    static std::vector<uint32_t> verify_many(Context &cx, KeyCache &cache, const std::vector<AggregateSignature> &aggregates,
+                                             const std::vector<PublicKey> &public_keys,
+                                             const std::vector<std::pair<const uint8_t *, size_t>> &messages,
+                                             uint64_t *stats_out = nullptr);
+    static std::vector<uint32_t> verify_many(Context &cx, KeyCache &cache, const std::vector<AggregateSignature> &aggregates,
+                                             const std::vector<uint8_t> &wire_keys,
+                                             const std::vector<std::pair<const uint8_t *, size_t>> &messages,
+                                             uint64_t *stats_out = nullptr);
     const std::vector<uint8_t> &to_bytes() const { return bytes; }
     // nullopt when the length is not 49 n + 32 or e_agg is not canonical
     static std::optional<AggregateSignature> from_bytes(const std::vector<uint8_t> &b) {
@@ -751,7 +766,8 @@ class KeyCache {
         uint64_t capacity, held, clears, device_bytes;
     };
     // Wire (SSA_KEYCACHE_WIRE): a key is identified by its 49 compressed bytes as received; such a
-    // cache serves verify_keyed_many_cached_statuses / verify_keyed_many_cached_device and no other call
+    // cache serves verify_keyed_many_cached_statuses / verify_keyed_many_cached_device and the wire-key overload of
+    // AggregateSignature::verify_many, and no other call
     enum Mode : uint32_t { Affine = 0u, Wire = SSA_KEYCACHE_WIRE };
     KeyCache(Context &cx, size_t capacity, Mode mode = Affine) : wire_(mode == Wire) {
         const int rc = ssa_keycache_create_ex(cx.get(), capacity, (uint32_t)mode, &kc_);
@@ -800,6 +816,82 @@ class KeyCache {
     ssa_keycache *kc_ = nullptr;
     bool wire_ = false;
 };
+
+// AggregateSignature::verify_many through a key cache
+namespace detail {
+struct PackedAggregates {
+    std::vector<uint64_t> counts;
+    std::vector<uint8_t> wire;
+    size_t n = 0;
+};
+inline PackedAggregates pack_aggregates(const std::vector<AggregateSignature> &aggregates) {
+    PackedAggregates p;
+    for (const AggregateSignature &a : aggregates) {
+        p.counts.push_back(a.size());
+        p.n += a.size();
+        p.wire.insert(p.wire.end(), a.bytes.begin(), a.bytes.end());
+    }
+    return p;
+}
+// n messages end to end and their n + 1 offsets
+struct PackedMessages {
+    std::vector<uint8_t> flat;
+    std::vector<uint64_t> off;
+};
+inline PackedMessages pack_messages(const std::vector<std::pair<const uint8_t *, size_t>> &messages) {
+    PackedMessages m;
+    m.off.assign(messages.size() + 1, 0);
+    for (size_t i = 0; i < messages.size(); i++) {
+        m.flat.insert(m.flat.end(), messages[i].first, messages[i].first + messages[i].second);
+        m.off[i + 1] = m.flat.size();
+    }
+    m.flat.push_back(0);
+    return m;
+}
+}  // namespace detail
+
+inline std::vector<uint32_t> AggregateSignature::verify_many(Context &cx, KeyCache &cache,
+                                                             const std::vector<AggregateSignature> &aggregates,
+                                                             const std::vector<PublicKey> &public_keys,
+                                                             const std::vector<std::pair<const uint8_t *, size_t>> &messages,
+                                                             uint64_t *stats_out) {
+    if (cache.wire()) throw std::invalid_argument("a Wire key cache takes 49-byte keys, not PublicKey objects");
+    const detail::PackedAggregates p = detail::pack_aggregates(aggregates);
+    if (public_keys.size() != p.n || messages.size() != p.n)
+        throw Panic("We should have the same number of messages than public keys");
+    std::vector<uint32_t> verdicts(aggregates.size(), SSA_MALFORMED);
+    if (aggregates.empty()) return verdicts;
+    std::vector<uint8_t> pks(p.n * AFFINE_PUBLIC_KEY_LENGTH + 1), inf(p.n + 1);
+    for (size_t i = 0; i < p.n; i++) {
+        std::memcpy(&pks[i * AFFINE_PUBLIC_KEY_LENGTH], public_keys[i].affine.data(), AFFINE_PUBLIC_KEY_LENGTH);
+        inf[i] = public_keys[i].is_identity ? 1 : 0;
+    }
+    const detail::PackedMessages m = detail::pack_messages(messages);
+    const int rc = ssa_verify_aggregates_many_cached(cx.get(), cache.get(), p.wire.data(), p.counts.data(), p.counts.size(),
+                                                     pks.data(), inf.data(), m.flat.data(), m.off.data(), 0, 0,
+                                                     verdicts.data(), stats_out);
+    if (rc != 0) throw std::runtime_error(std::string("ssa_verify_aggregates_many_cached: ") + ssa_strerror(rc));
+    return verdicts;
+}
+
+inline std::vector<uint32_t> AggregateSignature::verify_many(Context &cx, KeyCache &cache,
+                                                             const std::vector<AggregateSignature> &aggregates,
+                                                             const std::vector<uint8_t> &wire_keys,
+                                                             const std::vector<std::pair<const uint8_t *, size_t>> &messages,
+                                                             uint64_t *stats_out) {
+    if (!cache.wire()) throw std::invalid_argument("an Affine key cache takes PublicKey objects, not 49-byte keys");
+    const detail::PackedAggregates p = detail::pack_aggregates(aggregates);
+    if (wire_keys.size() != p.n * PUBLIC_KEY_LENGTH || messages.size() != p.n)
+        throw Panic("We should have the same number of messages than public keys");
+    std::vector<uint32_t> verdicts(aggregates.size(), SSA_MALFORMED);
+    if (aggregates.empty()) return verdicts;
+    const detail::PackedMessages m = detail::pack_messages(messages);
+    const int rc = ssa_verify_aggregates_many_cached_wire(cx.get(), cache.get(), p.wire.data(), p.counts.data(),
+                                                          p.counts.size(), wire_keys.data(), m.flat.data(), m.off.data(), 0, 0,
+                                                          verdicts.data(), stats_out);
+    if (rc != 0) throw std::runtime_error(std::string("ssa_verify_aggregates_many_cached_wire: ") + ssa_strerror(rc));
+    return verdicts;
+}
 
 // verify_many_screened_statuses with each public key's check done once per cache, not once per slice: byte for byte the
 // same vector for the same coefficients, whatever the cache holds.  stats_out: 12 words, optional.

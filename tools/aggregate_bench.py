@@ -31,7 +31,20 @@ alternating in the same way, every timed output checked:
                              batch, a refusal of any other
   baseline_filtered          ssa_aggregate_many_device without the check on arrays filtered beforehand (bad lanes only;
                              the time the caller needs to filter is NOT counted)
-The bar: valid < baseline_checked on the honest batch, valid < baseline_checked + baseline_filtered on the others."""
+The bar: valid < baseline_checked on the honest batch, valid < baseline_checked + baseline_filtered on the others.
+
+--cached measures ssa_verify_aggregates_many_cached(_wire)_device on section 21's first workload,
+--many's first KxS (default 1024x1024), signed by --signers distinct signers (0: every lane its own).  The validator's keys
+arrive as 49 wire bytes.  Legs, alternating in the same way, every verdict vector checked:
+  wire_cold                 the wire call on a cache cleared in front of it (the clear is not timed)
+  wire_warm                 the wire call on a cache that holds every key
+  affine_warm               the affine call on affine keys, a warm affine cache
+  baseline                  the route there was before, through --baseline-lib (a build of the parent commit; without it
+                            this tree's own library): ssa_decompress_many_device + ssa_verify_aggregates_many_device.  No
+                            subgroup guarantee.
+  baseline_keyset           the same plus ssa_keyset_create_device (ladder tables) over the distinct keys, which gives
+                            the statuses of the subgroup check.  The HOST time a caller needs to find the distinct keys
+                            and to map the statuses back onto aggregates is NOT counted."""
 import argparse
 import hashlib
 import json
@@ -344,6 +357,173 @@ def valid_main(a):
     return 0 if res["mismatches"] == 0 else 1
 
 
+CACHED_KERNELS = ("dedup", "keycache_lookup", "keycache_insert", "ssa_k_keyed_decompress", "ssa_k_keyset_build",
+                  "keycache_map", "agc_expand") + MANY_KERNELS + ("agc_k_key_verdicts",)
+
+
+class BaselineRoute:
+    """decompress + verify_aggregates_many (+ a key set over the distinct keys) of a build of the library given by its
+    path, on a context of its own"""
+
+    def __init__(self, path):
+        import ctypes as C
+        self.C, self.lib = C, C.CDLL(path)
+        vp, sz, i32, u64p = C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_uint64)
+        self.lib.ssa_ctx_create_ex.argtypes = [C.POINTER(vp), i32, vp, sz, C.c_uint32, C.c_uint64]
+        self.lib.ssa_decompress_many_device.argtypes = [vp, vp, sz, vp, vp, vp]
+        self.lib.ssa_verify_aggregates_many_device.argtypes = [vp, vp, u64p, sz, vp, vp, vp, vp, sz, sz, vp]
+        self.lib.ssa_keyset_create_device.argtypes = [vp, vp, vp, sz, C.c_uint32, C.POINTER(vp)]
+        self.lib.ssa_keyset_destroy.argtypes = [vp]
+        self.lib.ssa_keyset_destroy.restype = None
+        self.lib.ssa_ctx_sync.argtypes = [vp]
+        self.lib.ssa_ctx_destroy.argtypes = [vp]
+        self.lib.ssa_ctx_destroy.restype = None
+        self.ctx = vp()
+        self.keysets = []
+        if self.lib.ssa_ctx_create_ex(C.byref(self.ctx), 0, None, 0, 0, 0) != 0:
+            raise RuntimeError("baseline library: ssa_ctx_create_ex failed")
+
+    def route(self, d_wire_keys, d_pks, d_inf, d_st, n, d_aggs, counts, d_msgs, d_v, d_distinct=0, m=0):
+        if m:       # the statuses of the subgroup check: ladder tables (4 KB per key) over the distinct keys
+            ks = self.C.c_void_p()
+            if self.lib.ssa_keyset_create_device(self.ctx, d_distinct, None, m, 2, self.C.byref(ks)) != 0:
+                raise RuntimeError("baseline library: ssa_keyset_create_device failed")
+            self.keysets.append(ks)
+        if self.lib.ssa_decompress_many_device(self.ctx, d_wire_keys, n, d_pks, d_inf, d_st) != 0:
+            raise RuntimeError("baseline library: ssa_decompress_many_device failed")
+        cp = counts.ctypes.data_as(self.C.POINTER(self.C.c_uint64))
+        if self.lib.ssa_verify_aggregates_many_device(self.ctx, d_aggs, cp, counts.size, d_pks, d_inf, d_msgs, None, 80, 80,
+                                                      d_v) != 0:
+            raise RuntimeError("baseline library: ssa_verify_aggregates_many_device failed")
+
+    def drop_keysets(self):         # (outside the timed region)
+        for ks in self.keysets:
+            self.lib.ssa_keyset_destroy(ks)
+        self.keysets = []
+
+    def sync(self):
+        self.lib.ssa_ctx_sync(self.ctx)
+
+    def close(self):
+        self.drop_keysets()
+        self.lib.ssa_ctx_destroy(self.ctx)
+
+
+def cached_main(a):
+    import torch
+    import schnorr_sig_amd as ssa
+    dev = torch.device("cuda", 0)
+    k, s = tuple(int(v) for v in (a.many[0] if a.many else "1024x1024").lower().split("x"))
+    n = k * s
+    if a.signers < 0 or a.signers > n:
+        raise SystemExit("--signers must lie in [0, K * S = %d]" % n)
+    signers = a.signers or n
+    eng = ssa.Engine(0)
+    base_path = a.baseline_lib or ssa.LIB_PATH
+    base = BaselineRoute(base_path)
+    rng = np.random.default_rng(a.seed)
+    msgs = rng.integers(0, 256, (n, 80), dtype=np.uint8)
+    idx = rng.integers(0, signers, size=n)
+    idx[:signers] = np.arange(signers)
+    rng.shuffle(idx)
+    sks = _scalars(rng, signers)
+    pks, sigs = eng.keygen_sign_many(sks[idx], _scalars(rng, n), msgs)
+    wire_keys, st = eng.compress_many(pks)
+    distinct = eng.pubkey_many(sks)
+    assert (st == 0).all()
+    t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)   # noqa: E731
+    d_sigs, d_pks, d_msgs, d_wk, d_distinct = t(sigs), t(pks), t(msgs), t(wire_keys), t(distinct)
+    d_upks = torch.zeros(96 * n, dtype=torch.uint8, device=dev)       # what the baseline's decompression writes
+    d_uinf = torch.zeros(n, dtype=torch.uint8, device=dev)
+    d_ust = torch.zeros(n, dtype=torch.uint8, device=dev)
+    d_wire = torch.zeros(49 * n + 32 * k, dtype=torch.uint8, device=dev)
+    sha = lambda path: hashlib.sha256(open(path, "rb").read()).hexdigest()[:16]   # noqa: E731
+    res = {"metric": "aggregates_cached", "aggregates": k, "signatures_each": s, "signers": signers, "msg_len": 80,
+           "rounds": a.rounds, "warmup": a.warmup, "library_sha256": sha(ssa.LIB_PATH), "baseline_sha256": sha(base_path),
+           "baseline_is_this_tree": not a.baseline_lib, "device": torch.cuda.get_device_name(0),
+           "date": time.strftime("%Y-%m-%d"), "mismatches": 0}
+    for j in range(k):        # the honest aggregates, in their wire form end to end
+        lo = j * s
+        if eng.aggregate_device(d_sigs.data_ptr() + 81 * lo, d_pks.data_ptr() + 96 * lo, d_msgs.data_ptr() + 80 * lo, s, 80,
+                                d_wire.data_ptr() + 49 * lo + 32 * j) != 0:
+            res["mismatches"] += 1
+    eng.sync()
+    counts = np.full(k, s, dtype=np.uint64)
+    d_v = torch.full((k,), 255, dtype=torch.int32, device=dev)
+    wc, ac = eng.keycache_create(signers, wire=True), eng.keycache_create(signers)
+    stats = {}
+
+    def cached(cache, d_keys, leg):
+        def run():
+            stats[leg] = eng.verify_aggregates_cached_device(cache, d_wire, counts, d_keys, d_msgs, d_verdicts=d_v)[1]
+        return run
+
+    def baseline(with_keyset):
+        return lambda: base.route(d_wk.data_ptr(), d_upks.data_ptr(), d_uinf.data_ptr(), d_ust.data_ptr(), n,
+                                  d_wire.data_ptr(), counts, d_msgs.data_ptr(), d_v.data_ptr(),
+                                  d_distinct.data_ptr() if with_keyset else 0, signers if with_keyset else 0)
+
+    legs = {"wire_cold": (cached(wc, d_wk, "wire_cold"), eng.sync), "wire_warm": (cached(wc, d_wk, "wire_warm"), eng.sync),
+            "affine_warm": (cached(ac, d_pks, "affine_warm"), eng.sync), "baseline": (baseline(False), base.sync),
+            "baseline_keyset": (baseline(True), base.sync)}
+    cached(ac, d_pks, "affine_warm")()        # the affine cache is warm from here on
+    eng.sync()
+    times = {leg: [] for leg in legs}
+    for rnd in range(a.warmup + a.rounds):
+        for leg, (fn, sync) in legs.items():
+            d_v.fill_(255)
+            if leg == "wire_cold":
+                wc.clear()
+            eng.sync()
+            torch.cuda.synchronize()
+            sync()
+            t0 = time.perf_counter()
+            fn()
+            sync()
+            ms = (time.perf_counter() - t0) * 1e3
+            base.drop_keysets()
+            good = not bool((d_v != 0).any())
+            if leg in stats:      # cold: every key inserted; warm: every key found; nothing refused
+                st = [int(x) for x in stats[leg]]
+                good = good and st[0] == signers and st[6] == 0 and \
+                    (st[2] == signers and st[1] == 0 if leg == "wire_cold" else st[1] == signers and st[2] == 0)
+            elif bool((d_upks.view(-1, 96) != d_pks).any()):
+                good = False
+            res["mismatches"] += 0 if good else 1
+            if rnd >= a.warmup:
+                times[leg].append(ms)
+    med = {leg: round(float(np.median(v)), 3) for leg, v in times.items()}
+    res["ms_median"] = med
+    res["ms_min"] = {leg: round(float(np.min(v)), 3) for leg, v in times.items()}
+    res["ms_all"] = {leg: [round(x, 3) for x in v] for leg, v in times.items()}
+    res["ratio"] = {"wire_warm/baseline": round(med["wire_warm"] / med["baseline"], 3),
+                    "wire_warm/baseline_keyset": round(med["wire_warm"] / med["baseline_keyset"], 3),
+                    "wire_cold/baseline_keyset": round(med["wire_cold"] / med["baseline_keyset"], 3),
+                    "affine_warm/wire_warm": round(med["affine_warm"] / med["wire_warm"], 3)}
+    res["stats"] = {leg: [int(x) for x in v] for leg, v in stats.items()}
+    kern = {}
+    for leg in ("wire_warm", "wire_cold"):
+        if leg == "wire_cold":
+            wc.clear()
+        eng.sync()
+        eng.enable_timing(True)
+        legs[leg][0]()
+        eng.sync()
+        kern[leg] = {}
+        for kn in CACHED_KERNELS:
+            avg, cnt = eng.read_timing(kn)
+            if cnt:
+                kern[leg][kn] = [round(avg, 4), int(cnt)]
+        eng.enable_timing(False)
+    res["kernel_ms_avg_launches"] = kern
+    print(json.dumps(res))
+    wc.close()
+    ac.close()
+    eng.close()
+    base.close()
+    return 0 if res["mismatches"] == 0 else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1 << 20)
@@ -353,10 +533,16 @@ def main():
     ap.add_argument("--many", action="append", default=[], metavar="KxS",
                     help="K aggregates of S signatures in one ssa_verify_aggregates_many call (repeatable)")
     ap.add_argument("--baseline-lib", default=None,
-                    help="another build of the library for the loop_baseline leg (--many) or the baseline legs (--valid)")
+                    help="another build of the library for the loop_baseline leg (--many) or the baseline legs (--valid, "
+                         "--cached)")
     ap.add_argument("--valid", action="store_true",
                     help="ssa_aggregate_valid_many_device against the checked call (and the unchecked one on filtered arrays)")
+    ap.add_argument("--cached", action="store_true",
+                    help="ssa_verify_aggregates_many_cached(_wire)_device against decompress + ssa_verify_aggregates_many")
+    ap.add_argument("--signers", type=int, default=65536, help="--cached: distinct signers (0: every lane its own)")
     a = ap.parse_args()
+    if a.cached:
+        return cached_main(a)
     if a.many:
         return many_main(a)
     if a.valid:
