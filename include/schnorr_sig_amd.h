@@ -1038,6 +1038,58 @@ int ssa_aggregate_valid_many_device(ssa_ctx *ctx, const uint8_t *d_sigs, const u
  * up to n), *n_kept_out their number */
 int ssa_debug_aggregate_keep(ssa_ctx *ctx, const uint8_t *status, size_t n, uint32_t *kept_out, uint64_t *n_kept_out);
 
+/* ---- filtering half-aggregation through a key cache, subgroup check included -----------
+ * ssa_aggregate_valid_many under the verdict the validator's call applies (ssa_verify_aggregates_many_cached, section
+ * 23): a lane is kept iff ssa_verify_many_cached -- respectively ssa_verify_keyed_many_cached -- with
+ * SSA_FLAG_CHECK_TORSION | SSA_FLAG_SIG_FLAG_BYTE and library-drawn coefficients gives it status 0, so a key outside
+ * the prime-order subgroup drops its lane (status SSA_INVALID_PUBLIC_KEY; the key decides) instead of spoiling the
+ * block.  Let S be that status vector and K = { i : S[i] == 0 } in ascending order.  Then, in every state of the cache
+ * (cold, warm, partly warm, cleared or compacted in the middle of the call, bypassed):
+ *   status_out = S, stats_out = the 12 words of that call, and the cache is left as that call leaves it: it is used
+ *     exactly where that call uses it (not for a call, or a last slice, of at most SSA_MSM_SMALL_MAX lanes);
+ *   *n_kept_out = |K|,  kept_out[0, |K|) = K;
+ *   the first SSA_AGGREGATE_LENGTH(|K|) bytes of agg_out are byte for byte what ssa_aggregate_many (flags 0) returns
+ *     for the lanes of K handed in alone in that order (for records: split into signatures and decompressed keys);
+ *   pks_out (96 bytes per kept lane) and pk_inf_out (one byte per kept lane; all zero when pk_inf is NULL), or
+ *     keys49_out (49 bytes per kept lane: the first 49 bytes of the lane's record), hold the kept lanes' keys
+ *     verbatim, in that order;
+ *   the rest of agg_out (capacity SSA_AGGREGATE_LENGTH(n)), kept_out (n words) and the key outputs (n keys) is zero.
+ * agg_out and the key output, unchanged, with the kept lanes' messages, k = 1 and counts = { |K| }, are what
+ * ssa_verify_aggregates_many_cached (respectively _cached_wire) takes, and on the same cache that call answers SSA_OK
+ * without building a key table or decompressing a key: every kept key is in the cache, unless the call above bypassed
+ * it or did not use it.
+ *   ssa_aggregate_valid_many_cached(_device)        signatures and affine keys, an affine cache;
+ *   ssa_aggregate_valid_keyed_many_cached(_device)  n x 130-byte KeyedSignature records (key 49 || signature 81), a
+ *                                                   cache made with SSA_KEYCACHE_WIRE.
+ * The MESSAGES of the kept lanes are NOT gathered: the caller has kept_out, and compacting messages of variable length
+ * is a piece of work of its own.
+ * Every message is hashed ONCE, as in ssa_aggregate_valid_many: the affine form hashes all n lanes in front of the
+ * first slice, the keyed form hashes each slice behind its cache look-up (the affine key exists only then).
+ * Errors: a NULL cache, a cache of the other mode, of another context or orphaned is SSA_ERR_ARG, as are a null
+ * agg_out, kept_out or n_kept_out and n above the context's MSM slice (SSA_MSM_SLICE); the cache is then untouched.
+ * n == 0: SSA_OK, *n_kept_out = 0, 32 zero bytes.  The return value reports errors only: a dropped lane is a result.
+ * status_out, pks_out, pk_inf_out, keys49_out and stats_out may be NULL.  stats_out and n_kept_out are HOST memory in
+ * both forms.  The _device forms synchronise the context's stream as ssa_verify_many_cached_device does, slice by
+ * slice, and once more for |K|; the launches behind that are only enqueued. */
+int ssa_aggregate_valid_many_cached(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *sigs, const uint8_t *pks,
+                                    const uint8_t *pk_inf, const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride,
+                                    size_t msg_len, size_t n, uint8_t *agg_out, uint32_t *kept_out, uint64_t *n_kept_out,
+                                    uint8_t *status_out, uint8_t *pks_out, uint8_t *pk_inf_out, uint64_t stats_out[12]);
+int ssa_aggregate_valid_many_cached_device(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *d_sigs, const uint8_t *d_pks,
+                                           const uint8_t *d_pk_inf, const uint8_t *d_msgs, const uint64_t *d_msg_off,
+                                           size_t msg_stride, size_t msg_len, size_t n, uint8_t *d_agg_out,
+                                           uint32_t *d_kept_out, uint64_t *n_kept_out, uint8_t *d_status_out,
+                                           uint8_t *d_pks_out, uint8_t *d_pk_inf_out, uint64_t stats_out[12]);
+int ssa_aggregate_valid_keyed_many_cached(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *keyed, const uint8_t *msgs,
+                                          const uint64_t *msg_off, size_t msg_stride, size_t msg_len, size_t n,
+                                          uint8_t *agg_out, uint32_t *kept_out, uint64_t *n_kept_out, uint8_t *status_out,
+                                          uint8_t *keys49_out, uint64_t stats_out[12]);
+int ssa_aggregate_valid_keyed_many_cached_device(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *d_keyed,
+                                                 const uint8_t *d_msgs, const uint64_t *d_msg_off, size_t msg_stride,
+                                                 size_t msg_len, size_t n, uint8_t *d_agg_out, uint32_t *d_kept_out,
+                                                 uint64_t *n_kept_out, uint8_t *d_status_out, uint8_t *d_keys49_out,
+                                                 uint64_t stats_out[12]);
+
 /* ---- ABI version -------------------------------------------------------------------------------------------
  * Bumped whenever an exported signature changes (round 2 inserted pk_inf into the batch entry points under the same
  * symbol names: a shim built against the older header would still link and pass msgs as pk_inf).  A binding checks

@@ -262,6 +262,11 @@ def _load():
         "ssa_debug_aggregate_coeffs": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz, vp]),
         "ssa_aggregate_valid_many": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz, vp, vp, u64p, vp]),
         "ssa_aggregate_valid_many_device": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz, vp, vp, u64p, vp]),
+        "ssa_aggregate_valid_many_cached": (i32, [vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, vp, vp, u64p, vp, vp, vp, vp]),
+        "ssa_aggregate_valid_many_cached_device": (i32, [vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, vp, vp, u64p, vp, vp, vp,
+                                                         vp]),
+        "ssa_aggregate_valid_keyed_many_cached": (i32, [vp, vp, vp, vp, vp, sz, sz, sz, vp, vp, u64p, vp, vp, vp]),
+        "ssa_aggregate_valid_keyed_many_cached_device": (i32, [vp, vp, vp, vp, vp, sz, sz, sz, vp, vp, u64p, vp, vp, vp]),
         "ssa_debug_aggregate_keep": (i32, [vp, vp, sz, vp, u64p]),
         "ssa_verify_aggregates_many": (i32, [vp, vp, u64p, sz, vp, vp, vp, vp, sz, sz, vp]),
         "ssa_verify_aggregates_many_device": (i32, [vp, vp, u64p, sz, vp, vp, vp, vp, sz, sz, vp]),
@@ -720,6 +725,75 @@ class Engine:
             self._ctx, d_sigs, d_pks, *self._dev_batch(d_pk_inf, d_msgs, d_offsets, msg_stride, msg_len, n),
             d_agg, d_kept, C.byref(n_kept), d_status or None), "ssa_aggregate_valid_many_device")
         return int(n_kept.value)
+
+    # ---- filtering half-aggregation through a key cache (include/schnorr_sig_amd.h) ----
+    def aggregate_valid_cached(self, cache, sigs, pks, msgs, offsets=None, pk_inf=None):
+        """aggregate_valid under the statuses of verify_many_cached(check_torsion=True, sig_flag_byte=True): a lane whose
+        key lies outside the prime-order subgroup is dropped (status INVALID_PUBLIC_KEY) -> (aggregate uint8[49 |K| + 32],
+        kept uint32[|K|], status uint8[n], the kept keys uint8[|K|, 96], their pk_inf uint8[|K|], stats uint64[12] as
+        verify_many_cached).  Aggregate and kept keys are what verify_aggregates_cached takes on the same cache."""
+        if cache.wire:
+            raise ValueError("an affine batch takes an affine key cache (records: aggregate_valid_keyed_cached)")
+        n, batch, keep = self._agg_batch(sigs, 81, pks, msgs, offsets, pk_inf)
+        agg = np.full(49 * n + 32, 255, dtype=np.uint8)
+        kept = np.full(max(n, 1), 0xFFFFFFFF, dtype=np.uint32)
+        status = np.full(n, 255, dtype=np.uint8)
+        pks_out = np.full((max(n, 1), 96), 255, dtype=np.uint8)
+        inf_out = np.full(max(n, 1), 255, dtype=np.uint8)
+        stats = np.zeros(12, dtype=np.uint64)
+        n_kept = C.c_uint64(0)
+        _check(_lib.ssa_aggregate_valid_many_cached(self._ctx, cache.handle, *batch, _ptr(agg), _ptr(kept), C.byref(n_kept),
+                                                    _ptr(status) if n else None, _ptr(pks_out), _ptr(inf_out),
+                                                    stats.ctypes.data), "ssa_aggregate_valid_many_cached")
+        m = int(n_kept.value)
+        return agg[:49 * m + 32].copy(), kept[:m].copy(), status, pks_out[:m].copy(), inf_out[:m].copy(), stats
+
+    def aggregate_valid_keyed_cached(self, cache, keyed, msgs, offsets=None):
+        """aggregate_valid_cached on 130-byte KeyedSignature records pk(49) || sig(81) through a cache made with
+        wire=True -> (aggregate, kept uint32[|K|], status uint8[n] as verify_keyed_many_cached gives it, the kept keys
+        uint8[|K|, 49], stats uint64[12])"""
+        if not cache.wire:
+            raise ValueError("records take a key cache made with wire=True")
+        kd = _np_u8(keyed, 130)
+        n = kd.shape[0]
+        m_, off, stride, mlen = self._msg_args(msgs, offsets, n) if n else (None, None, 0, 0)
+        agg = np.full(49 * n + 32, 255, dtype=np.uint8)
+        kept = np.full(max(n, 1), 0xFFFFFFFF, dtype=np.uint32)
+        status = np.full(n, 255, dtype=np.uint8)
+        keys_out = np.full((max(n, 1), 49), 255, dtype=np.uint8)
+        stats = np.zeros(12, dtype=np.uint64)
+        n_kept = C.c_uint64(0)
+        _check(_lib.ssa_aggregate_valid_keyed_many_cached(
+            self._ctx, cache.handle, _ptr(kd) if n else None, _ptr(m_), _ptr(off), stride, mlen, n, _ptr(agg), _ptr(kept),
+            C.byref(n_kept), _ptr(status) if n else None, _ptr(keys_out), stats.ctypes.data),
+            "ssa_aggregate_valid_keyed_many_cached")
+        m = int(n_kept.value)
+        return agg[:49 * m + 32].copy(), kept[:m].copy(), status, keys_out[:m].copy(), stats
+
+    def aggregate_valid_cached_device(self, cache, d_sigs, d_pks, d_msgs, n, msg_len, d_agg, d_kept, d_status=0, d_pks_out=0,
+                                      d_pk_inf_out=0, msg_stride=None, d_offsets=0, d_pk_inf=0, want_stats=True):
+        """device form of aggregate_valid_cached (device addresses; the synchronisations of verify_many_cached_device
+        and one for the number of kept lanes) -> (that number, stats uint64[12] or None).  Capacities: d_agg 49 n + 32
+        bytes, d_kept n uint32, d_pks_out 96 n bytes, d_pk_inf_out n bytes; all zero behind the kept lanes."""
+        n_kept = C.c_uint64(0)
+        stats = np.zeros(12, dtype=np.uint64) if want_stats else None
+        _check(_lib.ssa_aggregate_valid_many_cached_device(
+            self._ctx, cache.handle, d_sigs, d_pks, *self._dev_batch(d_pk_inf, d_msgs, d_offsets, msg_stride, msg_len, n),
+            d_agg, d_kept, C.byref(n_kept), d_status or None, d_pks_out or None, d_pk_inf_out or None,
+            stats.ctypes.data if want_stats else None), "ssa_aggregate_valid_many_cached_device")
+        return int(n_kept.value), stats
+
+    def aggregate_valid_keyed_cached_device(self, cache, d_keyed, d_msgs, n, msg_len, d_agg, d_kept, d_status=0,
+                                            d_keys49_out=0, msg_stride=None, d_offsets=0, want_stats=True):
+        """device form of aggregate_valid_keyed_cached -> (the number of kept lanes, stats uint64[12] or None);
+        d_keys49_out: capacity 49 n bytes"""
+        n_kept = C.c_uint64(0)
+        stats = np.zeros(12, dtype=np.uint64) if want_stats else None
+        _check(_lib.ssa_aggregate_valid_keyed_many_cached_device(
+            self._ctx, cache.handle, d_keyed, *self._dev_batch(0, d_msgs, d_offsets, msg_stride, msg_len, n)[1:],
+            d_agg, d_kept, C.byref(n_kept), d_status or None, d_keys49_out or None,
+            stats.ctypes.data if want_stats else None), "ssa_aggregate_valid_keyed_many_cached_device")
+        return int(n_kept.value), stats
 
     def debug_aggregate_keep(self, status):
         """tests: the compaction alone -> (the indices of the zero bytes of `status`, ascending, as the device lists
@@ -1813,6 +1887,15 @@ class KeyedSignature:
         return isinstance(o, KeyedSignature) and o.public_key == self.public_key and o.signature == self.signature
 
 
+def pack_keyed_records(engine, sigs, pks, pk_inf=None):
+    """n x 130 KeyedSignature records pk(49) || sig(81) from n signatures (81 bytes each) and n affine keys"""
+    sigs, pks = _np_u8(sigs).reshape(-1, 81), _np_u8(pks, 96)
+    if sigs.shape[0] != pks.shape[0]:
+        raise MalformedInput("We should have the same number of signatures than public keys")
+    wire = engine.compress_many(pks, pk_inf=pk_inf)[0] if pks.shape[0] else np.zeros((0, 49), np.uint8)
+    return np.ascontiguousarray(np.concatenate([np.asarray(wire, dtype=np.uint8).reshape(-1, 49), sigs], axis=1))
+
+
 class AggregateSignature:
     """The half-aggregate of n signatures: their R's, 49 bytes each, and e_agg = sum a_i e_i mod q
     -- 49 n + 32 bytes for 81 n.  The order of the lanes is part of it."""
@@ -1842,15 +1925,23 @@ class AggregateSignature:
         return cls(agg.tobytes())
 
     @classmethod
-    def aggregate_valid(cls, signatures, public_keys, messages, engine=None):
+    def aggregate_valid(cls, signatures, public_keys, messages, engine=None, cache=None):
         """Engine.aggregate_valid over (signature, public key, message) objects -> (the AggregateSignature of the
         triples that verify under verify_batch semantics, the list of their indices).  A triple that does not verify is
-        dropped, not raised."""
+        dropped, not raised.  With a KeyCache (DESIGN.md section 24) a triple is kept iff Signature::verify accepts it --
+        the subgroup check of its key included, once per key and cache -- so verify_many(..., cache=cache) accepts the
+        result; a cache made with wire=True is handed KeyedSignature records."""
         packed = _pack_triples(signatures, public_keys, messages)
         if packed is None:
             return cls(bytes(32)), []
         sigs, pks, inf, flat, off = packed
-        agg, kept, _ = (engine or default_engine()).aggregate_valid(sigs, pks, flat, offsets=off, pk_inf=inf)
+        eng = engine or (cache.engine if cache is not None else default_engine())
+        if cache is None:
+            agg, kept = eng.aggregate_valid(sigs, pks, flat, offsets=off, pk_inf=inf)[:2]
+        elif cache.wire:
+            agg, kept = eng.aggregate_valid_keyed_cached(cache, pack_keyed_records(eng, sigs, pks, inf), flat, offsets=off)[:2]
+        else:
+            agg, kept = eng.aggregate_valid_cached(cache, sigs, pks, flat, offsets=off, pk_inf=inf)[:2]
         return cls(agg.tobytes()), [int(i) for i in kept]
 
     def verify(self, public_keys, messages, engine=None):

@@ -39,6 +39,10 @@
 // av_k_keep_scan and av_k_keep_list turn the status vector into the ascending list of kept lanes (ballots and sums, no
 // atomic), av_k_gather_sigs and av_k_gather_dig lay those lanes' signatures and raw digests side by side, and leaf, tree,
 // coefficient, fold and pack run over them as over any batch: a lane's digest does not depend on its place.
+//
+// ssa_aggregate_valid_many_cached keeps the lanes that pass ssa_verify_many_cached instead -- the
+// subgroup check of the key included -- and hands the kept lanes' keys on: av_k_gather_sigs also reads signatures out of
+// 130-byte records, av_k_gather_keys lays the kept keys (49 or 96 bytes, and the pk_inf byte) side by side.
 #pragma once
 #include <vector>
 #include "ssa_kernels.hpp"
@@ -556,21 +560,54 @@ av_k_keep_list(const u8 *__restrict__ status, u32 n, const u32 *__restrict__ blk
 }
 
 // sigs_out (the library's own buffer: dword-aligned, m * 81 bytes) = the signatures of the m listed lanes side by side.
-// One thread per dword, as ag_k_pack; the source lane of every byte is looked up in the list.
+// The signature of lane i stands at sigs + stride * i + off: (81, 0) for an array of signatures, (130, 49) for
+// KeyedSignature records.  One thread per dword, as ag_k_pack; the source lane of every byte is looked up in the list.
 __global__ void __launch_bounds__(256)
-av_k_gather_sigs(const u8 *__restrict__ sigs, const u32 *__restrict__ kept, size_t m, u8 *__restrict__ sigs_out) {
+av_k_gather_sigs(const u8 *__restrict__ sigs, u32 stride, u32 off, const u32 *__restrict__ kept, size_t m,
+                 u8 *__restrict__ sigs_out) {
     const size_t d = (size_t)blockIdx.x * 256 + threadIdx.x, total = m * 81, o = 4 * d;
     if (o >= total) return;
     u32 v = 0;
     const int cnt = total - o < 4 ? (int)(total - o) : 4;
     for (int k = 0; k < cnt; k++) {
         const size_t b = o + k, c = b / 81;
-        v |= (u32)sigs[81 * (size_t)kept[c] + (b - 81 * c)] << (8 * k);
+        v |= (u32)sigs[(size_t)stride * kept[c] + off + (b - 81 * c)] << (8 * k);
     }
     if (cnt == 4) {
         reinterpret_cast<u32 *>(sigs_out)[d] = v;
     } else {
         for (int k = 0; k < cnt; k++) sigs_out[o + k] = (u8)(v >> (8 * k));
+    }
+}
+
+// The keys of the m listed lanes side by side, and zeros behind them up to the capacity of `cap` lanes (DESIGN.md
+// section 24): out[width * c + r] = src[stride * kept[c] + r] for c < m and r < width, out[width * m, width * cap) = 0.
+// Three shapes: 49 bytes out of 130-byte records, 96-byte affine keys, and the pk_inf byte (width 1); src == nullptr (no
+// pk_inf given) writes zeros only.  One thread per output dword, the source lane looked up in the list as above; a dword
+// that lies within one key and whose source is aligned is one load.  out is the caller's: dwords only when it is aligned.
+__global__ void __launch_bounds__(256)
+av_k_gather_keys(const u8 *__restrict__ src, u32 stride, u32 width, const u32 *__restrict__ kept, size_t m, size_t cap,
+                 u8 *__restrict__ out) {
+    const size_t d = (size_t)blockIdx.x * 256 + threadIdx.x, total = cap * width, used = src ? m * width : 0, o = 4 * d;
+    if (o >= total) return;
+    const int cnt = total - o < 4 ? (int)(total - o) : 4;
+    u32 v = 0;
+    if (o < used) {
+        const size_t c0 = o / width, r0 = o - c0 * width;
+        const u8 *p = src + (size_t)stride * kept[c0] + r0;
+        if (r0 + 4 <= width && (reinterpret_cast<uintptr_t>(p) & 3u) == 0) {      // (then cnt == 4: c0 < m <= cap)
+            v = *reinterpret_cast<const u32 *>(p);
+        } else {
+            for (int k = 0; k < cnt && o + k < used; k++) {
+                const size_t b = o + k, c = b / width;
+                v |= (u32)src[(size_t)stride * kept[c] + (b - c * width)] << (8 * k);
+            }
+        }
+    }
+    if (cnt == 4 && (reinterpret_cast<uintptr_t>(out) & 3u) == 0) {
+        reinterpret_cast<u32 *>(out)[d] = v;
+    } else {
+        for (int k = 0; k < cnt; k++) out[o + k] = (u8)(v >> (8 * k));
     }
 }
 

@@ -553,6 +553,13 @@ int ssa_internal_hash_scalars(ssa_ctx *ctx, const DevBatch &b, size_t n) {
     });
 }
 
+int ssa_internal_hash_scalars_digests(ssa_ctx *ctx, const DevBatch &b, size_t n, uint64_t *d_h, uint8_t *d_dig) {
+    return timed_launch(ctx, "ssa_k_hash", [&] {
+        hipLaunchKernelGGL(ssa_k_hash, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, ctx->d_params,
+                           b.sigs, b.pks, b.msgs, n, (u64 *)d_h, (u8 *)d_dig, (const u32 *)nullptr, 0u);
+    });
+}
+
 // The end game of an ssa_k_verify launch over cnt lanes: which groups run in pieces, where their work is cut.  The cuts
 // follow instruction counts (a doubling 2642 VALU instructions, a mixed addition 3738; the table build ~57 k in front of
 // the first pass, the comb for G and the comparison ~45 k behind the last): the first piece is half of a lane's work, the
@@ -2069,6 +2076,30 @@ static int av_keep(ssa_ctx *ctx, const u8 *d_status, size_t n, u32 *d_kept, uint
     return 0;
 }
 
+// The aggregate of the m (>= 1) listed lanes into d_agg_out, from the raw digests of all lanes in ctx->ag_dig and the
+// signatures at d_sigs + stride * lane + off.  A lane's digest does not depend on its place, so the kept lanes'
+// signatures and digests side by side are what the transcript of those lanes handed in alone starts from; keys and
+// messages are not needed again.
+static int av_aggregate_kept(ssa_ctx *ctx, const u8 *d_sigs, u32 stride, u32 off, const u32 *d_kept, size_t m, u8 *d_agg_out) {
+    if (ctx->av_sigs.reserve(m * 81 + 16) || ctx->av_dig.reserve(m * 32)) return SSA_ERR_HIP;
+    const u8 *k_sigs = (const u8 *)ctx->av_sigs.p;
+    int rc = timed_launch(ctx, "av_k_gather", [&] {
+        hipLaunchKernelGGL(av_k_gather_sigs, dim3(grid_for((m * 81 + 3) / 4, 256)), dim3(256), 0, ctx->stream, d_sigs, stride,
+                           off, d_kept, m, (u8 *)ctx->av_sigs.p);
+        hipLaunchKernelGGL(av_k_gather_dig, dim3(grid_for(2 * m, 256)), dim3(256), 0, ctx->stream,
+                           (const u64 *)ctx->ag_dig.p, d_kept, m, (u64 *)ctx->av_dig.p);
+    });
+    if (rc) return rc;
+    if ((rc = ag_transcript_from_digests(ctx, (const u64 *)ctx->av_dig.p, k_sigs, m, nullptr, 1, ag_uniform_passes(m))))
+        return rc;
+    // (every kept lane passed the screen: e_i < q, and the fold has nothing left to check)
+    if ((rc = ag_fold(ctx, k_sigs, nullptr, nullptr, m, nullptr, nullptr))) return rc;
+    return timed_launch(ctx, "ag_k_pack", [&] {
+        hipLaunchKernelGGL(ag_k_pack, dim3(grid_for((m * 49 + 3) / 4, 256)), dim3(256), 0, ctx->stream, k_sigs, m, d_agg_out);
+        (void)hipMemcpyAsync(d_agg_out + 49 * m, ag_misc(ctx, AG_E), 32, hipMemcpyDeviceToDevice, ctx->stream);
+    });
+}
+
 // Two synchronisations: the screen's (for its segment verdicts; none at n <= msm_small_max) and one for |K|.
 extern "C" int ssa_aggregate_valid_many_device(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks,
                                                const uint8_t *d_pk_inf, const uint8_t *d_msgs, const uint64_t *d_msg_off,
@@ -2099,26 +2130,7 @@ extern "C" int ssa_aggregate_valid_many_device(ssa_ctx *ctx, const uint8_t *d_si
     if (used < SSA_AGGREGATE_LENGTH(n))
         HIP_TRY(hipMemsetAsync(d_agg_out + used, 0, SSA_AGGREGATE_LENGTH(n) - used, ctx->stream));
     if (m == 0) return SSA_OK;
-    // A lane's digest does not depend on its place, so the kept lanes' signatures and digests side by side are what the
-    // transcript of those lanes handed in alone starts from; keys and messages are not needed again.
-    if (ctx->av_sigs.reserve(m * 81 + 16) || ctx->av_dig.reserve(m * 32)) return SSA_ERR_HIP;
-    const u8 *k_sigs = (const u8 *)ctx->av_sigs.p;
-    int rc = timed_launch(ctx, "av_k_gather", [&] {
-        hipLaunchKernelGGL(av_k_gather_sigs, dim3(grid_for((m * 81 + 3) / 4, 256)), dim3(256), 0, ctx->stream, d_sigs,
-                           (const u32 *)d_kept_out, (size_t)m, (u8 *)ctx->av_sigs.p);
-        hipLaunchKernelGGL(av_k_gather_dig, dim3(grid_for(2 * m, 256)), dim3(256), 0, ctx->stream,
-                           (const u64 *)ctx->ag_dig.p, (const u32 *)d_kept_out, (size_t)m, (u64 *)ctx->av_dig.p);
-    });
-    if (rc) return rc;
-    if ((rc = ag_transcript_from_digests(ctx, (const u64 *)ctx->av_dig.p, k_sigs, m, nullptr, 1, ag_uniform_passes(m))))
-        return rc;
-    // (every kept lane passed the screen: e_i < q, and the fold has nothing left to check)
-    if ((rc = ag_fold(ctx, k_sigs, nullptr, nullptr, m, nullptr, nullptr))) return rc;
-    return timed_launch(ctx, "ag_k_pack", [&] {
-        hipLaunchKernelGGL(ag_k_pack, dim3(grid_for((m * 49 + 3) / 4, 256)), dim3(256), 0, ctx->stream, k_sigs, (size_t)m,
-                           d_agg_out);
-        (void)hipMemcpyAsync(d_agg_out + 49 * m, ag_misc(ctx, AG_E), 32, hipMemcpyDeviceToDevice, ctx->stream);
-    });
+    return av_aggregate_kept(ctx, d_sigs, 81, 0, d_kept_out, m, d_agg_out);
 }
 
 extern "C" int ssa_aggregate_valid_many(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_inf,
@@ -2451,6 +2463,157 @@ extern "C" int ssa_verify_aggregates_many_cached_wire(ssa_ctx *ctx, ssa_keycache
                                                       size_t msg_len, uint32_t *verdicts_out, uint64_t stats_out[8]) {
     return agc_host(ctx, kc, aggs, counts, k, pks49, nullptr, true, msgs, msg_off, msg_stride, msg_len, verdicts_out,
                     stats_out);
+}
+
+// ------------------------------------------------------------------ filtering half-aggregation through a key cache
+// ssa_aggregate_valid_many with the statuses of ssa_verify_many_cached (affine keys) or ssa_verify_keyed_many_cached
+// (130-byte records: d_keyed, and b holds the messages alone) in place of the screen's, and the kept lanes' keys handed
+// on.  Every message is hashed once: over all n lanes in front (affine), or slice by slice behind the slice's keys
+// (records); either way the scalars of all n lanes stand in ctx->ws_h and the raw digests in ctx->ag_dig when the slices
+// are through.  Nothing between the hash and the gathers writes either: with ready hashes neither msm_run_one nor the
+// exact kernels hash, the cache slice works in the dd_*, kc_* and ky_* buffers, ssa_k_keyset_build writes rows of the
+// cache or ctx->ws_tab, and the re-check gather copies scalars into ctx->scr_in.  Both are reserved for n lanes before
+// the first slice, so no later reserve of a slice's size moves them.
+// The synchronisations of the slices (ssa_verify_many_cached_device has the count) and one for |K|.
+static int avc_run(ssa_ctx *ctx, ssa_keycache *kc, const DevBatch &b, const u8 *d_keyed, size_t n, u8 *d_agg_out,
+                   u32 *d_kept_out, uint64_t *n_kept_out, u8 *d_status_out, u8 *d_keys_out, u8 *d_inf_out,
+                   uint64_t *stats_out) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (!d_status_out && ctx->ag_status.reserve(n + 16)) return SSA_ERR_HIP;
+    u8 *d_status = d_status_out ? d_status_out : (u8 *)ctx->ag_status.p;
+    if (d_keyed) {
+        if (ctx->ws_h.reserve(n * 32) || ctx->ag_dig.reserve(n * 32)) return SSA_ERR_HIP;
+        if (int rc = ssa_internal_screen_keyed_hashed(ctx, kc, d_keyed, b.msgs, n, (uint64_t *)ctx->ws_h.p,
+                                                      (uint8_t *)ctx->ag_dig.p, d_status, stats_out))
+            return rc;
+    } else {
+        const u8 *d_sigs = b.sigs;
+        if (int rc = ag_transcript_front(ctx, nullptr, &d_sigs, b.pks, b.msgs, n, true, nullptr, 1)) return rc;
+        if (int rc = ssa_internal_screen_many_hashed(ctx, kc, b, n, (const uint64_t *)ctx->ws_h.p, d_status, stats_out))
+            return rc;
+    }
+    uint64_t m = 0;
+    if (int rc = av_keep(ctx, d_status, n, d_kept_out, &m)) return rc;
+    *n_kept_out = m;
+    // everything behind the aggregate of the kept lanes is zero; with none kept, that is the empty aggregate
+    const size_t used = m ? SSA_AGGREGATE_LENGTH(m) : 0;
+    if (used < SSA_AGGREGATE_LENGTH(n))
+        HIP_TRY(hipMemsetAsync(d_agg_out + used, 0, SSA_AGGREGATE_LENGTH(n) - used, ctx->stream));
+    // the kept lanes' keys as the caller gave them, and zeros up to the capacity of n lanes (the kernel writes both)
+    if (d_keys_out || d_inf_out) {
+        const u32 width = d_keyed ? 49u : 96u;
+        const int rc = timed_launch(ctx, "av_k_gather_keys", [&] {
+            if (d_keys_out)
+                hipLaunchKernelGGL(av_k_gather_keys, dim3(grid_for((n * width + 3) / 4, 256)), dim3(256), 0, ctx->stream,
+                                   d_keyed ? d_keyed : b.pks, d_keyed ? 130u : 96u, width, (const u32 *)d_kept_out, (size_t)m, n,
+                                   d_keys_out);
+            if (d_inf_out)
+                hipLaunchKernelGGL(av_k_gather_keys, dim3(grid_for((n + 3) / 4, 256)), dim3(256), 0, ctx->stream, b.pk_inf, 1u,
+                                   1u, (const u32 *)d_kept_out, (size_t)m, n, d_inf_out);
+        });
+        if (rc) return rc;
+    }
+    if (m == 0) return SSA_OK;
+    return d_keyed ? av_aggregate_kept(ctx, d_keyed, 130, 49, d_kept_out, m, d_agg_out)
+                   : av_aggregate_kept(ctx, b.sigs, 81, 0, d_kept_out, m, d_agg_out);
+}
+
+// arguments of all four forms, before anything is written: in0, in1 = the inputs that must not be null when n != 0
+static int avc_check_args(const ssa_ctx *ctx, const ssa_keycache *kc, bool keyed, const void *in0, const void *in1,
+                          const MsgView &mv, size_t n, const void *agg_out, const void *kept_out, uint64_t *n_kept_out,
+                          uint64_t *stats_out) {
+    if (int rc = agc_check_cache(ctx, kc, keyed)) return rc;
+    if (!agg_out || !kept_out || !n_kept_out || (n && (!in0 || !in1))) return SSA_ERR_ARG;
+    if (int rc = agg_check_args(ctx, mv, n)) return rc;
+    *n_kept_out = 0;
+    if (stats_out) std::memset(stats_out, 0, 12 * sizeof(uint64_t));
+    return 0;
+}
+
+extern "C" int ssa_aggregate_valid_many_cached_device(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *d_sigs,
+                                                      const uint8_t *d_pks, const uint8_t *d_pk_inf, const uint8_t *d_msgs,
+                                                      const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len, size_t n,
+                                                      uint8_t *d_agg_out, uint32_t *d_kept_out, uint64_t *n_kept_out,
+                                                      uint8_t *d_status_out, uint8_t *d_pks_out, uint8_t *d_pk_inf_out,
+                                                      uint64_t stats_out[12]) {
+    const DevBatch b{d_sigs, d_pks, d_pk_inf, {d_msgs, d_msg_off, msg_stride, msg_len}};
+    if (int rc = avc_check_args(ctx, kc, false, d_sigs, d_pks, b.msgs, n, d_agg_out, d_kept_out, n_kept_out, stats_out)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(d_agg_out, 0, 32, ctx->stream));
+        return SSA_OK;
+    }
+    return avc_run(ctx, kc, b, nullptr, n, d_agg_out, d_kept_out, n_kept_out, d_status_out, d_pks_out, d_pk_inf_out, stats_out);
+}
+
+extern "C" int ssa_aggregate_valid_keyed_many_cached_device(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *d_keyed,
+                                                            const uint8_t *d_msgs, const uint64_t *d_msg_off,
+                                                            size_t msg_stride, size_t msg_len, size_t n, uint8_t *d_agg_out,
+                                                            uint32_t *d_kept_out, uint64_t *n_kept_out, uint8_t *d_status_out,
+                                                            uint8_t *d_keys49_out, uint64_t stats_out[12]) {
+    const DevBatch b{nullptr, nullptr, nullptr, {d_msgs, d_msg_off, msg_stride, msg_len}};
+    if (int rc = avc_check_args(ctx, kc, true, d_keyed, d_keyed, b.msgs, n, d_agg_out, d_kept_out, n_kept_out, stats_out)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(d_agg_out, 0, 32, ctx->stream));
+        return SSA_OK;
+    }
+    return avc_run(ctx, kc, b, d_keyed, n, d_agg_out, d_kept_out, n_kept_out, d_status_out, d_keys49_out, nullptr, stats_out);
+}
+
+extern "C" int ssa_aggregate_valid_many_cached(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *sigs, const uint8_t *pks,
+                                               const uint8_t *pk_inf, const uint8_t *msgs, const uint64_t *msg_off,
+                                               size_t msg_stride, size_t msg_len, size_t n, uint8_t *agg_out,
+                                               uint32_t *kept_out, uint64_t *n_kept_out, uint8_t *status_out, uint8_t *pks_out,
+                                               uint8_t *pk_inf_out, uint64_t stats_out[12]) {
+    if (int rc = avc_check_args(ctx, kc, false, sigs, pks, {msgs, msg_off, msg_stride, msg_len}, n, agg_out, kept_out,
+                                n_kept_out, nullptr))
+        return rc;
+    if (int rc = check_host_offsets(msg_off, n)) return rc;
+    if (stats_out) std::memset(stats_out, 0, 12 * sizeof(uint64_t));
+    if (n == 0) {
+        std::memset(agg_out, 0, 32);
+        return SSA_OK;
+    }
+    HostCall hc(ctx);
+    const u8 *d_sigs = hc.in(ctx->st_sigs, sigs, n * 81), *d_pks = hc.in(ctx->st_pks, pks, n * 96);
+    const u8 *d_inf = pk_inf ? hc.in(ctx->st_inf, pk_inf, n) : nullptr;
+    const MsgView mv = hc.msgs(msgs, msg_off, msg_stride, msg_len, n);
+    u8 *d_agg = hc.out(ctx->st_aux, agg_out, SSA_AGGREGATE_LENGTH(n), 16);
+    u32 *d_kept = (u32 *)hc.out(ctx->st_aux2, kept_out, n * sizeof(u32));
+    u8 *d_status = hc.out(ctx->st_status, status_out, n, 16);
+    u8 *d_pks_out = pks_out ? hc.out(ctx->avc_keys, pks_out, n * 96) : nullptr;
+    u8 *d_inf_out = pk_inf_out ? hc.out(ctx->avc_inf, pk_inf_out, n, 16) : nullptr;
+    return hc.finish([&] {
+        return avc_run(ctx, kc, {d_sigs, d_pks, d_inf, mv}, nullptr, n, d_agg, d_kept, n_kept_out, d_status, d_pks_out, d_inf_out,
+                       stats_out);
+    });
+}
+
+extern "C" int ssa_aggregate_valid_keyed_many_cached(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *keyed, const uint8_t *msgs,
+                                                     const uint64_t *msg_off, size_t msg_stride, size_t msg_len, size_t n,
+                                                     uint8_t *agg_out, uint32_t *kept_out, uint64_t *n_kept_out,
+                                                     uint8_t *status_out, uint8_t *keys49_out, uint64_t stats_out[12]) {
+    if (int rc = avc_check_args(ctx, kc, true, keyed, keyed, {msgs, msg_off, msg_stride, msg_len}, n, agg_out, kept_out,
+                                n_kept_out, nullptr))
+        return rc;
+    if (int rc = check_host_offsets(msg_off, n)) return rc;
+    if (stats_out) std::memset(stats_out, 0, 12 * sizeof(uint64_t));
+    if (n == 0) {
+        std::memset(agg_out, 0, 32);
+        return SSA_OK;
+    }
+    HostCall hc(ctx);
+    const u8 *d_keyed = hc.in(ctx->st_keyed, keyed, n * 130);
+    const MsgView mv = hc.msgs(msgs, msg_off, msg_stride, msg_len, n);
+    u8 *d_agg = hc.out(ctx->st_aux, agg_out, SSA_AGGREGATE_LENGTH(n), 16);
+    u32 *d_kept = (u32 *)hc.out(ctx->st_aux2, kept_out, n * sizeof(u32));
+    u8 *d_status = hc.out(ctx->st_status, status_out, n, 16);
+    u8 *d_keys_out = keys49_out ? hc.out(ctx->avc_keys, keys49_out, n * 49, 16) : nullptr;
+    return hc.finish([&] {
+        return avc_run(ctx, kc, {nullptr, nullptr, nullptr, mv}, d_keyed, n, d_agg, d_kept, n_kept_out, d_status, d_keys_out,
+                       nullptr, stats_out);
+    });
 }
 
 // tests: the plan of a call from its counts alone (no device): out[0..4) = lanes, tree passes, groups, descriptors in

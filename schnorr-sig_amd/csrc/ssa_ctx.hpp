@@ -187,6 +187,9 @@ struct CtxKnobs {
     /* filtering half-aggregation: per-workgroup counts and offsets of the kept lanes (the \
        length of the list behind them), and the kept lanes' signatures and raw digests side by side */ \
     X(av_blk) X(av_sigs) X(av_dig) \
+    /* filtering half-aggregation through a key cache: the kept keys (49 or 96 bytes each) and \
+       their pk_inf bytes as the host forms stage them */ \
+    X(avc_keys) X(avc_inf) \
     /* aggregates through a key cache (ssa_aggcache.hpp): per lane of the CALL (not of a slice) \
        its key's status byte and, for wire keys, its 96 key bytes and pk_inf boolean; and the call's two counters */ \
     X(agc_kst) X(agc_pks) X(agc_inf) X(agc_cnt) \
@@ -773,6 +776,10 @@ static int status_host_one(ssa_ctx *ctx, const HostBatch &b, size_t n, const uin
 // defined in ssa_api.hip: hash_message + Scalar::from_bits_vartime for n signatures into ctx->ws_h
 int ssa_internal_hash_scalars(ssa_ctx *ctx, const DevBatch &b, size_t n);
 
+// the same launch (timing key ssa_k_hash) with its outputs named: the scalars into d_h (n x 4 words) and the raw digests
+// into d_dig (n x 32 bytes), both the caller's
+int ssa_internal_hash_scalars_digests(ssa_ctx *ctx, const DevBatch &b, size_t n, uint64_t *d_h, uint8_t *d_dig);
+
 // defined in ssa_msm.hip, for ssa_verify_aggregate (ssa_api.hip): ONE slice (n <= ctx->knobs.msm_slice) of the MSM form
 // reduced to its 24-word record on ctx->stream -- the left-hand point in canonical form, sum s_i e_i, the malformed flag.
 // d_h: the slice's challenge scalars if they exist (batches of at most ctx->knobs.msm_small_max lanes hash for themselves)
@@ -793,6 +800,17 @@ int ssa_internal_msm_agg_segments(ssa_ctx *ctx, const DevBatch &b, uint32_t segs
 // read.  At most one synchronisation (none at n <= ctx->knobs.msm_small_max).
 int ssa_internal_screen_hashed(ssa_ctx *ctx, const DevBatch &b, size_t n, const uint64_t *d_h, uint8_t *d_status,
                                unsigned long long *d_fail);
+
+// defined in ssa_msm.hip, for ssa_aggregate_valid_many_cached (ssa_api.hip): the statuses and the
+// 12 statistics words of ssa_verify_many_cached_device / ssa_verify_keyed_many_cached_device (subgroup check and flag
+// byte, library-drawn coefficients) for the n >= 1 lanes of a call, slice after slice through the cache as those calls
+// take them, with ONE hash per lane.  Affine: the scalars are ready in d_h and only read.  Records: the keys exist only
+// behind each slice's look-up, so one ssa_k_hash per slice writes that slice's scalars into d_h and raw digests into
+// d_dig, and nothing else hashes.  stats_out: host memory, may be null.
+int ssa_internal_screen_many_hashed(ssa_ctx *ctx, struct ssa_keycache *kc, const DevBatch &b, size_t n, const uint64_t *d_h,
+                                    uint8_t *d_status, uint64_t stats_out[12]);
+int ssa_internal_screen_keyed_hashed(ssa_ctx *ctx, struct ssa_keycache *kc, const uint8_t *d_keyed, const MsgView &mv,
+                                     size_t n, uint64_t *d_h, uint8_t *d_dig, uint8_t *d_status, uint64_t stats_out[12]);
 
 // defined in ssa_api.hip: ssa_k_verify over n lanes of b (its messages unused) whose challenge scalars are already in
 // d_h (the per-lane workspace reserved for one slice of lanes); *d_fail is added to

@@ -2062,12 +2062,29 @@ extern "C" int ssa_verify_many_cached(ssa_ctx *ctx, ssa_keycache *kc, const uint
 // ssa_verify_keyed_many_cached: ssa_verify_many_cached on 130-byte records through a cache in wire mode -- the key's 49
 // bytes are its identity, so a warm call decompresses nothing.  Kernels: ssa_keyed.hpp; the slice: ssa_api.hip.
 
+// Where ONE launch of ssa_k_hash over a slice of records leaves the challenge scalars mod q (h, four words per lane) and
+// the raw digests (dig, 32 bytes per lane): the slice's keys exist only after its unpack or cache look-up, so a caller
+// that needs both (ssa_aggregate_valid_keyed_many_cached) has the slice hash in between and the
+// verification behind it then takes h as ready hashes.
+struct SliceHash {
+    u64 *h;
+    u8 *dig;
+};
+static int keyed_hash_slice(ssa_ctx *ctx, const DevBatch &b, size_t n, const SliceHash &sh) {
+    return ssa_internal_hash_scalars_digests(ctx, b, n, sh.h, sh.dig);
+}
+
 // ONE slice of at most lane_slice records on the exact path: unpacked into the context's per-lane workspaces, then
-// ssa_verify_many_device with the caller's flags (*d_fail is zeroed by it)
+// ssa_verify_many_device with the caller's flags (*d_fail is zeroed by it); sh != nullptr: the hash as SliceHash says,
+// then ssa_k_verify on those scalars (*d_fail is added to)
 static int keyed_exact_slice(ssa_ctx *ctx, const uint8_t *d_keyed, const MsgView &mv, size_t n, uint32_t flags,
-                             uint8_t *d_status, unsigned long long *d_fail) {
+                             uint8_t *d_status, unsigned long long *d_fail, const SliceHash *sh = nullptr) {
     DevBatch b{nullptr, nullptr, nullptr, mv};
     if (int rc = ssa_internal_unpack_keyed(ctx, d_keyed, n, &b)) return rc;
+    if (sh) {
+        if (int rc = keyed_hash_slice(ctx, b, n, *sh)) return rc;
+        return ssa_internal_verify_hashed(ctx, b, sh->h, n, flags, d_status, d_fail);
+    }
     return ssa_verify_many_device(ctx, b.sigs, b.pks, b.pk_inf, mv.msgs, mv.off, mv.stride, mv.len, n, flags, d_status,
                                   (uint64_t *)d_fail);
 }
@@ -2101,14 +2118,15 @@ extern "C" int ssa_verify_keyed_many_device(ssa_ctx *ctx, const uint8_t *d_keyed
 
 // ONE slice (n <= SSA_LANE_SLICE records) of the wire form on ctx->stream into d_status[0, n): screen_many_slice with
 // the keys looked up by their 49 bytes.  A slice of at most msm_small_max lanes takes the exact keyed path.
+// sh != nullptr: one hash launch between the keys and the screen (SliceHash), and no other.
 static int keyed_cached_slice(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *d_keyed, const MsgView &mv, size_t n,
                               const uint8_t *d_coeffs, uint32_t coeff_bytes, uint32_t flags, uint8_t *d_status,
-                              CallStats *stats) {
+                              CallStats *stats, const SliceHash *sh = nullptr) {
     uint64_t sv[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     if (ctx->scr_fail.reserve(16)) return SSA_ERR_HIP;
     if (n <= ctx->knobs.msm_small_max) {
         sv[6] = 1;
-        const int rc = keyed_exact_slice(ctx, d_keyed, mv, n, flags, d_status, (unsigned long long *)ctx->scr_fail.p);
+        const int rc = keyed_exact_slice(ctx, d_keyed, mv, n, flags, d_status, (unsigned long long *)ctx->scr_fail.p, sh);
         if (rc == 0 && stats) stats->add(sv);
         return rc;
     }
@@ -2117,6 +2135,11 @@ static int keyed_cached_slice(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *d_k
     DevBatch b{nullptr, nullptr, nullptr, mv};
     const unsigned long long *d_unpublished = nullptr;
     if (int rc = ssa_internal_keyed_cache_slice(ctx, kc, d_keyed, n, &b, &kv, &u, &hits, sv + 8, &d_unpublished)) return rc;
+    if (sh) {
+        if (int rc = keyed_hash_slice(ctx, b, n, *sh)) return rc;
+        return screen_slice_after_keys(ctx, b, n, d_coeffs, coeff_bytes, flags, sh->h, d_status, stats, kv, u, hits,
+                                       d_unpublished, sv);
+    }
     return screen_slice_after_keys(ctx, b, n, d_coeffs, coeff_bytes, flags, nullptr, d_status, stats, kv, u, hits,
                                    d_unpublished, sv);
 }
@@ -2227,5 +2250,57 @@ extern "C" int ssa_verify_keyed_many_cached(ssa_ctx *ctx, ssa_keycache *kc, cons
     if (rc) return rc;
     if (small && stats_out) stats_out[6] = 1;
     if (!small && !batch_form) st.out(stats_out);
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// For ssa_aggregate_valid_many_cached (ssa_api.hip): the device forms of ssa_verify_many_cached and
+// ssa_verify_keyed_many_cached with SSA_FLAG_CHECK_TORSION | SSA_FLAG_SIG_FLAG_BYTE and library-drawn coefficients, slice
+// after slice as those calls take them, on challenge scalars that are hashed once for the caller and the screen alike.
+// The arguments are the caller's to check (n >= 1, the cache of the right mode and of this context).
+int ssa_internal_screen_many_hashed(ssa_ctx *ctx, ssa_keycache *kc, const DevBatch &b, size_t n, const uint64_t *d_h,
+                                    uint8_t *d_status, uint64_t stats_out[12]) {
+    if (!kc || !d_h || !d_status || n == 0) return SSA_ERR_ARG;
+    CallStats st(12);
+    st.out(stats_out);
+    if (ctx->scr_fail.reserve(16)) return SSA_ERR_HIP;
+    if (n <= ctx->knobs.msm_small_max) {      // (the whole call on the exact path: the cache is not used)
+        const int rc = ssa_internal_verify_hashed(ctx, b, d_h, n, MANY_SCREEN_FLAGS, d_status,
+                                                  (unsigned long long *)ctx->scr_fail.p);
+        if (rc == 0 && stats_out) stats_out[6] = 1;
+        return rc;
+    }
+    if (int rc = for_dev_slices(b, n, many_screen_slice_lanes(ctx), [&](size_t lo, size_t cnt, const DevBatch &s) {
+            return screen_many_slice(ctx, s, cnt, nullptr, 0, MANY_SCREEN_FLAGS, (const u64 *)d_h + 4 * lo, d_status + lo,
+                                     stats_out ? &st : nullptr, kc);
+        }))
+        return rc;
+    st.out(stats_out);
+    return 0;
+}
+
+// The same for 130-byte records through a wire cache.  d_h (n x 4 words) and d_dig (n x 32 bytes) are WRITTEN: one launch
+// of ssa_k_hash per slice, behind the slice's keys, leaves lanes [lo, lo + cnt) of both.
+int ssa_internal_screen_keyed_hashed(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *d_keyed, const MsgView &mv, size_t n,
+                                     uint64_t *d_h, uint8_t *d_dig, uint8_t *d_status, uint64_t stats_out[12]) {
+    if (!kc || !d_keyed || !d_h || !d_dig || !d_status || n == 0) return SSA_ERR_ARG;
+    CallStats st(12);
+    st.out(stats_out);
+    if (ctx->scr_fail.reserve(16)) return SSA_ERR_HIP;
+    if (n <= ctx->knobs.msm_small_max) {
+        const SliceHash sh{(u64 *)d_h, d_dig};
+        const int rc = keyed_exact_slice(ctx, d_keyed, mv, n, MANY_SCREEN_FLAGS, d_status, (unsigned long long *)ctx->scr_fail.p,
+                                         &sh);
+        if (rc == 0 && stats_out) stats_out[6] = 1;
+        return rc;
+    }
+    const DevBatch whole{nullptr, nullptr, nullptr, mv};
+    if (int rc = for_dev_slices(whole, n, many_screen_slice_lanes(ctx), [&](size_t lo, size_t cnt, const DevBatch &s) {
+            const SliceHash sh{(u64 *)d_h + 4 * lo, d_dig + 32 * lo};
+            return keyed_cached_slice(ctx, kc, d_keyed + 130 * lo, s.msgs, cnt, nullptr, 0, MANY_SCREEN_FLAGS, d_status + lo,
+                                      stats_out ? &st : nullptr, &sh);
+        }))
+        return rc;
+    st.out(stats_out);
     return 0;
 }

@@ -665,6 +665,19 @@ struct AggregateSignature {
         kept.resize(n_kept);
         return {std::move(a), std::move(kept)};
     }
+    // The same through a key cache: a triple is kept iff Signature::verify accepts it -- the
+    // subgroup check of its key included, once per key and cache -- so verify_many on the same cache accepts the result.
+    // An Affine cache takes the objects and hands the kept keys back in *kept_keys; a Wire cache takes n 130-byte
+    // KeyedSignature records (key 49 || signature 81) side by side and hands back the kept lanes' 49 key bytes, which
+    // the wire-key overload of verify_many takes.  stats_out: 12 words, optional.  (Defined behind KeyCache.)
+    static std::pair<AggregateSignature, std::vector<uint32_t>>
+    aggregate_valid(Context &cx, KeyCache &cache, const std::vector<Signature> &signatures,
+                    const std::vector<PublicKey> &public_keys, const std::vector<std::pair<const uint8_t *, size_t>> &messages,
+                    std::vector<PublicKey> *kept_keys = nullptr, uint64_t *stats_out = nullptr);
+    static std::pair<AggregateSignature, std::vector<uint32_t>>
+    aggregate_valid(Context &cx, KeyCache &cache, const std::vector<uint8_t> &keyed_records,
+                    const std::vector<std::pair<const uint8_t *, size_t>> &messages,
+                    std::vector<uint8_t> *kept_keys49 = nullptr, uint64_t *stats_out = nullptr);
     Result verify(Context &cx, const std::vector<PublicKey> &public_keys,
                   const std::vector<std::pair<const uint8_t *, size_t>> &messages) const {
         if (public_keys.size() != size() || messages.size() != size())
@@ -891,6 +904,61 @@ inline std::vector<uint32_t> AggregateSignature::verify_many(Context &cx, KeyCac
                                                           verdicts.data(), stats_out);
     if (rc != 0) throw std::runtime_error(std::string("ssa_verify_aggregates_many_cached_wire: ") + ssa_strerror(rc));
     return verdicts;
+}
+
+// AggregateSignature::aggregate_valid through a key cache
+inline std::pair<AggregateSignature, std::vector<uint32_t>>
+AggregateSignature::aggregate_valid(Context &cx, KeyCache &cache, const std::vector<Signature> &signatures,
+                                    const std::vector<PublicKey> &public_keys,
+                                    const std::vector<std::pair<const uint8_t *, size_t>> &messages,
+                                    std::vector<PublicKey> *kept_keys, uint64_t *stats_out) {
+    if (cache.wire()) throw std::invalid_argument("a Wire key cache takes KeyedSignature records, not objects");
+    const PackedTriples t = pack_triples(signatures, public_keys, messages);
+    const size_t n = signatures.size();
+    AggregateSignature a;
+    a.bytes.assign(SSA_AGGREGATE_LENGTH(n), 0);
+    std::vector<uint32_t> kept(n ? n : 1, 0u);
+    std::vector<uint8_t> pks(n * AFFINE_PUBLIC_KEY_LENGTH + 1), inf(n + 1);
+    uint64_t n_kept = 0;
+    const int rc = ssa_aggregate_valid_many_cached(cx.get(), cache.get(), t.sigs.data(), t.pks.data(), t.inf.data(),
+                                                   t.flat.data(), t.off.data(), 0, 0, n, a.bytes.data(), kept.data(), &n_kept,
+                                                   nullptr, pks.data(), inf.data(), stats_out);
+    if (rc != 0) throw std::runtime_error(std::string("ssa_aggregate_valid_many_cached: ") + ssa_strerror(rc));
+    a.bytes.resize(SSA_AGGREGATE_LENGTH(n_kept));
+    kept.resize(n_kept);
+    if (kept_keys) {
+        kept_keys->assign(n_kept, PublicKey{});
+        for (size_t i = 0; i < n_kept; i++) {
+            std::memcpy((*kept_keys)[i].affine.data(), &pks[i * AFFINE_PUBLIC_KEY_LENGTH], AFFINE_PUBLIC_KEY_LENGTH);
+            (*kept_keys)[i].is_identity = inf[i] != 0;
+        }
+    }
+    return {std::move(a), std::move(kept)};
+}
+
+inline std::pair<AggregateSignature, std::vector<uint32_t>>
+AggregateSignature::aggregate_valid(Context &cx, KeyCache &cache, const std::vector<uint8_t> &keyed_records,
+                                    const std::vector<std::pair<const uint8_t *, size_t>> &messages,
+                                    std::vector<uint8_t> *kept_keys49, uint64_t *stats_out) {
+    constexpr size_t RECORD = KEYED_SIGNATURE_LENGTH;
+    if (!cache.wire()) throw std::invalid_argument("an Affine key cache takes objects, not KeyedSignature records");
+    if (keyed_records.size() % RECORD || keyed_records.size() / RECORD != messages.size())
+        throw Panic("We should have the same number of messages than public keys");
+    const size_t n = messages.size();
+    const detail::PackedMessages m = detail::pack_messages(messages);
+    AggregateSignature a;
+    a.bytes.assign(SSA_AGGREGATE_LENGTH(n), 0);
+    std::vector<uint32_t> kept(n ? n : 1, 0u);
+    std::vector<uint8_t> keys(n * PUBLIC_KEY_LENGTH + 1);
+    uint64_t n_kept = 0;
+    const int rc = ssa_aggregate_valid_keyed_many_cached(cx.get(), cache.get(), keyed_records.data(), m.flat.data(),
+                                                         m.off.data(), 0, 0, n, a.bytes.data(), kept.data(), &n_kept, nullptr,
+                                                         keys.data(), stats_out);
+    if (rc != 0) throw std::runtime_error(std::string("ssa_aggregate_valid_keyed_many_cached: ") + ssa_strerror(rc));
+    a.bytes.resize(SSA_AGGREGATE_LENGTH(n_kept));
+    kept.resize(n_kept);
+    if (kept_keys49) kept_keys49->assign(keys.begin(), keys.begin() + (std::ptrdiff_t)(n_kept * PUBLIC_KEY_LENGTH));
+    return {std::move(a), std::move(kept)};
 }
 
 // verify_many_screened_statuses with each public key's check done once per cache, not once per slice: byte for byte the

@@ -44,7 +44,20 @@ arrive as 49 wire bytes.  Legs, alternating in the same way, every verdict vecto
                             subgroup guarantee.
   baseline_keyset           the same plus ssa_keyset_create_device (ladder tables) over the distinct keys, which gives
                             the statuses of the subgroup check.  The HOST time a caller needs to find the distinct keys
-                            and to map the statuses back onto aggregates is NOT counted."""
+                            and to map the statuses back onto aggregates is NOT counted.
+
+--valid-cached measures ssa_aggregate_valid_many_cached_device and ssa_aggregate_valid_keyed_many_cached_device (DESIGN.md
+section 24): --n signatures by --signers distinct signers (0: every lane its own), three workloads -- an honest batch, 16
+bad lanes (a flipped bit of e), 1 % bad lanes of which every second one has a key outside the prime-order subgroup.  Legs,
+alternating in the same way, every timed output checked (kept count and list, aggregate, kept keys):
+  affine_cold, affine_warm   the affine form on a cache cleared in front of it (the clear is not timed) / that holds every key
+  keyed_cold, keyed_warm     the keyed form (130-byte records) through a wire cache, likewise
+  baseline_valid             ssa_aggregate_valid_many_device through --baseline-lib (a build of the parent commit; without it
+                             this tree's own library): NO guarantee about the keys
+  baseline_guarded           the guarded route there was before, through the same library: ssa_verify_many_cached_device
+                             (warm affine cache, subgroup check and flag byte), then ssa_aggregate_many_device on arrays
+                             filtered beforehand.  The HOST time a caller needs to filter four arrays and upload them again
+                             is NOT counted."""
 import argparse
 import hashlib
 import json
@@ -357,6 +370,205 @@ def valid_main(a):
     return 0 if res["mismatches"] == 0 else 1
 
 
+VALID_CACHED_KERNELS = ("keyed_split", "dedup", "keycache_lookup", "keycache_insert", "ssa_k_keyed_decompress",
+                        "ssa_k_keyset_build", "keycache_map", "keyed_expand", "ssa_k_hash", "screen_keymask", "msm_k_prepare",
+                        "msm_sort", "msm_k_buckets", "msm_reduce", "msm_k_finish_seg", "screen_mark", "screen_list_gather",
+                        "ssa_k_verify_keyed", "screen_list_scatter", "av_k_keep", "av_k_gather_keys", "av_k_gather",
+                        "ag_k_leaf", "ag_k_tree", "ag_k_coeff", "ag_k_fold", "ag_k_pack")
+
+
+class BaselineGuarded:
+    """ssa_aggregate_valid_many_device, and ssa_verify_many_cached_device + ssa_aggregate_many_device, of a build of the
+    library given by its path, on a context and an affine key cache of its own"""
+
+    def __init__(self, path, capacity):
+        import ctypes as C
+        self.C, self.lib = C, C.CDLL(path)
+        vp, sz, i32, u32 = C.c_void_p, C.c_size_t, C.c_int, C.c_uint32
+        self.lib.ssa_ctx_create_ex.argtypes = [C.POINTER(vp), i32, vp, sz, u32, C.c_uint64]
+        self.lib.ssa_keycache_create.argtypes = [vp, sz, C.POINTER(vp)]
+        self.lib.ssa_keycache_destroy.argtypes = [vp]
+        self.lib.ssa_keycache_destroy.restype = None
+        self.lib.ssa_verify_many_cached_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, u32, vp, u32, vp, vp, vp]
+        self.lib.ssa_aggregate_many_device.argtypes = [vp, vp, vp, vp, vp, vp, sz, sz, sz, u32, vp, vp, vp]
+        self.lib.ssa_aggregate_valid_many_device.argtypes = [vp, vp, vp, vp, vp, vp, sz, sz, sz, vp, vp,
+                                                             C.POINTER(C.c_uint64), vp]
+        self.lib.ssa_ctx_sync.argtypes = [vp]
+        self.lib.ssa_ctx_destroy.argtypes = [vp]
+        self.lib.ssa_ctx_destroy.restype = None
+        self.ctx, self.kc = vp(), vp()
+        if self.lib.ssa_ctx_create_ex(C.byref(self.ctx), 0, None, 0, 0, 0) != 0:
+            raise RuntimeError("baseline library: ssa_ctx_create_ex failed")
+        if self.lib.ssa_keycache_create(self.ctx, capacity, C.byref(self.kc)) != 0:
+            raise RuntimeError("baseline library: ssa_keycache_create failed")
+
+    def valid(self, d_sigs, d_pks, d_msgs, n, d_agg, d_kept):
+        nk = self.C.c_uint64(0)
+        if self.lib.ssa_aggregate_valid_many_device(self.ctx, d_sigs, d_pks, None, d_msgs, None, 80, 80, n, d_agg, d_kept,
+                                                    self.C.byref(nk), None) != 0:
+            raise RuntimeError("baseline library: ssa_aggregate_valid_many_device failed")
+        return int(nk.value)
+
+    def statuses(self, d_sigs, d_pks, d_msgs, n, d_status):
+        if self.lib.ssa_verify_many_cached_device(self.ctx, self.kc, d_sigs, d_pks, None, d_msgs, None, 80, 80, n, 1 | 8, None,
+                                                  32, d_status, None, None) != 0:
+            raise RuntimeError("baseline library: ssa_verify_many_cached_device failed")
+
+    def aggregate(self, d_sigs, d_pks, d_msgs, n, d_agg):
+        if self.lib.ssa_aggregate_many_device(self.ctx, d_sigs, d_pks, None, d_msgs, None, 80, 80, n, 0, d_agg, None, None) != 0:
+            raise RuntimeError("baseline library: ssa_aggregate_many_device failed")
+
+    def sync(self):
+        self.lib.ssa_ctx_sync(self.ctx)
+
+    def close(self):
+        self.lib.ssa_keycache_destroy(self.kc)
+        self.lib.ssa_ctx_destroy(self.ctx)
+
+
+def valid_cached_main(a):
+    import torch
+    import schnorr_sig_amd as ssa
+    sys.path.insert(0, os.path.join(ROOT, "oracle"))
+    import pymodel as pm
+    dev = torch.device("cuda", 0)
+    n = a.n
+    if a.signers < 0 or a.signers > n:
+        raise SystemExit("--signers must lie in [0, n = %d]" % n)
+    signers = a.signers or n
+    eng = ssa.Engine(0)
+    base_path = a.baseline_lib or ssa.LIB_PATH
+    base = BaselineGuarded(base_path, signers + 16)
+    rng = np.random.default_rng(a.seed)
+    msgs = rng.integers(0, 256, (n, 80), dtype=np.uint8)
+    idx = rng.integers(0, signers, size=n)
+    idx[:signers] = np.arange(signers)
+    rng.shuffle(idx)
+    pks, honest = eng.keygen_sign_many(_scalars(rng, signers)[idx], _scalars(rng, n), msgs)
+    # a key on the curve and outside the prime-order subgroup: the point of order 2
+    t2 = np.frombuffer(pm.fp6_to_bytes48(pm.SMALL_ORDER_POINTS[2][0]) + pm.fp6_to_bytes48(pm.SMALL_ORDER_POINTS[2][1]), np.uint8)
+    t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)   # noqa: E731
+    d_msgs = t(msgs)
+    sha = lambda path: hashlib.sha256(open(path, "rb").read()).hexdigest()[:16]   # noqa: E731
+    res = {"metric": "aggregate_valid_cached", "n": n, "signers": signers, "msg_len": 80, "rounds": a.rounds,
+           "warmup": a.warmup, "library_sha256": sha(ssa.LIB_PATH), "baseline_sha256": sha(base_path),
+           "baseline_is_this_tree": not a.baseline_lib, "device": torch.cuda.get_device_name(0),
+           "date": time.strftime("%Y-%m-%d"), "mismatches": 0, "workloads": []}
+    ac, wc = eng.keycache_create(signers + 16), eng.keycache_create(signers + 16, wire=True)
+
+    for name, n_bad in (("honest", 0), ("16 bad", 16), ("1 % bad, half of them keys", n // 100)):
+        bad = np.sort(rng.choice(n, size=min(n_bad, n), replace=False))
+        sigs, keys = honest.copy(), pks.copy()
+        sigs[bad[0::2], 49] ^= 1
+        if name.startswith("1 %"):
+            keys[bad[1::2]] = t2
+        else:
+            sigs[bad[1::2], 49] ^= 1
+        wire, st = eng.compress_many(keys)
+        assert (st == 0).all()
+        keep = np.setdiff1d(np.arange(n), bad)
+        m = keep.size
+        rec = np.concatenate([wire, sigs], axis=1)
+        d_sigs, d_pks, d_rec = t(sigs), t(keys), t(rec)
+        d_fs, d_fp, d_fm = t(sigs[keep]), t(keys[keep]), t(msgs[keep])
+        d_want = torch.zeros(49 * n + 32, dtype=torch.uint8, device=dev)          # the aggregate of the kept lanes, zeros behind
+        d_keep = torch.zeros(n, dtype=torch.int32, device=dev)
+        d_keep[:m] = t(keep.astype(np.int32))
+        d_want_pks, d_want_w = torch.zeros(n, 96, dtype=torch.uint8, device=dev), torch.zeros(n, 49, dtype=torch.uint8, device=dev)
+        d_want_pks[:m], d_want_w[:m] = d_fp, t(wire[keep])
+        if m and eng.aggregate_device(d_fs.data_ptr(), d_fp.data_ptr(), d_fm.data_ptr(), m, 80, d_want.data_ptr()) != 0:
+            res["mismatches"] += 1
+        eng.sync()
+        d_agg = torch.zeros(49 * n + 32, dtype=torch.uint8, device=dev)
+        d_kept = torch.zeros(n, dtype=torch.int32, device=dev)
+        d_ko, d_io = torch.zeros(n, 96, dtype=torch.uint8, device=dev), torch.zeros(n, dtype=torch.uint8, device=dev)
+        d_wo = torch.zeros(n, 49, dtype=torch.uint8, device=dev)
+        d_status = torch.zeros(n, dtype=torch.uint8, device=dev)
+        got = {}
+
+        def affine():
+            got["m"], got["stats"] = eng.aggregate_valid_cached_device(
+                ac, d_sigs.data_ptr(), d_pks.data_ptr(), d_msgs.data_ptr(), n, 80, d_agg.data_ptr(), d_kept.data_ptr(),
+                d_pks_out=d_ko.data_ptr(), d_pk_inf_out=d_io.data_ptr())
+
+        def keyed():
+            got["m"], got["stats"] = eng.aggregate_valid_keyed_cached_device(
+                wc, d_rec.data_ptr(), d_msgs.data_ptr(), n, 80, d_agg.data_ptr(), d_kept.data_ptr(), d_keys49_out=d_wo.data_ptr())
+
+        def base_valid():
+            got["m"] = base.valid(d_sigs.data_ptr(), d_pks.data_ptr(), d_msgs.data_ptr(), n, d_agg.data_ptr(), d_kept.data_ptr())
+
+        def base_guarded():
+            base.statuses(d_sigs.data_ptr(), d_pks.data_ptr(), d_msgs.data_ptr(), n, d_status.data_ptr())
+            base.aggregate(d_fs.data_ptr(), d_fp.data_ptr(), d_fm.data_ptr(), m, d_agg.data_ptr())
+
+        legs = {"affine_cold": (affine, eng.sync), "affine_warm": (affine, eng.sync), "keyed_cold": (keyed, eng.sync),
+                "keyed_warm": (keyed, eng.sync), "baseline_valid": (base_valid, base.sync),
+                "baseline_guarded": (base_guarded, base.sync)}
+        base_guarded()          # the baseline's cache is warm from here on
+        base.sync()
+        times = {leg: [] for leg in legs}
+        for rnd in range(a.warmup + a.rounds):
+            for leg, (fn, sync) in legs.items():
+                for buf in (d_agg, d_ko, d_io, d_wo, d_status):
+                    buf.fill_(0xEE)
+                d_kept.fill_(-1)
+                if leg == "affine_cold":
+                    ac.clear()
+                if leg == "keyed_cold":
+                    wc.clear()
+                eng.sync()
+                torch.cuda.synchronize()
+                sync()
+                t0 = time.perf_counter()
+                fn()
+                sync()
+                ms = (time.perf_counter() - t0) * 1e3
+                if leg == "baseline_guarded":
+                    good = bool((d_agg[:49 * m + 32] == d_want[:49 * m + 32]).all()) and \
+                        np.flatnonzero(d_status.cpu().numpy()).tolist() == bad.tolist()
+                else:
+                    good = got["m"] == m and bool((d_agg == d_want).all()) and bool((d_kept == d_keep).all())
+                if leg.startswith("affine"):
+                    good = good and bool((d_ko == d_want_pks).all()) and not bool(d_io.any())
+                if leg.startswith("keyed"):
+                    good = good and bool((d_wo == d_want_w).all())
+                if leg.endswith("_cold"):
+                    good = good and int(got["stats"][8]) == 0
+                if leg.endswith("_warm"):
+                    good = good and int(got["stats"][9]) == 0
+                res["mismatches"] += 0 if good else 1
+                if rnd >= a.warmup:
+                    times[leg].append(ms)
+        med = {leg: round(float(np.median(v)), 3) for leg, v in times.items()}
+        w = {"workload": name, "bad_lanes": int(bad.size), "kept": int(m), "ms_median": med,
+             "ms_min": {leg: round(float(np.min(v)), 3) for leg, v in times.items()},
+             "ms_all": {leg: [round(x, 3) for x in v] for leg, v in times.items()},
+             "ratio": {leg + "/" + b: round(med[leg] / med[b], 3) for leg in ("affine_cold", "affine_warm", "keyed_cold", "keyed_warm")
+                       for b in ("baseline_valid", "baseline_guarded")}}
+        if n_bad == 0:
+            kern = {}
+            for leg in ("affine_warm", "keyed_warm"):
+                eng.sync()
+                eng.enable_timing(True)
+                legs[leg][0]()
+                eng.sync()
+                kern[leg] = {}
+                for kn in VALID_CACHED_KERNELS:
+                    avg, cnt = eng.read_timing(kn)
+                    if cnt:
+                        kern[leg][kn] = [round(avg, 4), int(cnt)]
+                eng.enable_timing(False)
+            w["kernel_ms_avg_launches"] = kern
+        res["workloads"].append(w)
+    print(json.dumps(res))
+    ac.close()
+    wc.close()
+    eng.close()
+    base.close()
+    return 0 if res["mismatches"] == 0 else 1
+
+
 CACHED_KERNELS = ("dedup", "keycache_lookup", "keycache_insert", "ssa_k_keyed_decompress", "ssa_k_keyset_build",
                   "keycache_map", "agc_expand") + MANY_KERNELS + ("agc_k_key_verdicts",)
 
@@ -539,8 +751,14 @@ def main():
                     help="ssa_aggregate_valid_many_device against the checked call (and the unchecked one on filtered arrays)")
     ap.add_argument("--cached", action="store_true",
                     help="ssa_verify_aggregates_many_cached(_wire)_device against decompress + ssa_verify_aggregates_many")
-    ap.add_argument("--signers", type=int, default=65536, help="--cached: distinct signers (0: every lane its own)")
+    ap.add_argument("--valid-cached", action="store_true",
+                    help="ssa_aggregate_valid_(keyed_)many_cached_device against ssa_aggregate_valid_many_device and against "
+                         "ssa_verify_many_cached_device + ssa_aggregate_many_device on filtered arrays")
+    ap.add_argument("--signers", type=int, default=65536,
+                    help="--cached, --valid-cached: distinct signers (0: every lane its own)")
     a = ap.parse_args()
+    if a.valid_cached:
+        return valid_cached_main(a)
     if a.cached:
         return cached_main(a)
     if a.many:
