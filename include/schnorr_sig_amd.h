@@ -895,7 +895,8 @@ int ssa_msm_combine(ssa_ctx *ctx, const uint64_t *parts24, size_t k);
  * (keys or R's with a small-order component: the caveat of ssa_verify_batch_screened applies; take key statuses from a
  * key set or a key cache where it matters).  An aggregate verifies only if every input verified with
  * SSA_FLAG_SIG_FLAG_BYTE; a forgery succeeds with probability about 2^-126 per transcript tried.
- * n above the context's MSM slice (2^23, SSA_MSM_SLICE) is SSA_ERR_ARG: no slicing, no multi-GPU form.
+ * n above the context's MSM slice (2^23, SSA_MSM_SLICE) is SSA_ERR_ARG in the calls of this section; the sliced,
+ * sharded and multi-GPU forms are the calls of "sharded half-aggregation" below.
  *
  * ssa_aggregate_many: agg_out receives SSA_AGGREGATE_LENGTH(n) bytes.  flags: 0 or SSA_AGG_CHECK (any other bit:
  * SSA_ERR_ARG).  With SSA_AGG_CHECK the statuses of ssa_verify_batch_screened are computed first: if any is nonzero,
@@ -927,6 +928,83 @@ int ssa_verify_aggregate_device(ssa_ctx *ctx, const uint8_t *d_agg, const uint8_
 int ssa_debug_aggregate_coeffs(ssa_ctx *ctx, const uint8_t *rs49, const uint8_t *pks, const uint8_t *pk_inf,
                                const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len, size_t n,
                                uint8_t *coeffs16_out);
+
+/* ---- sharded half-aggregation: slices, devices, processes -----------------------------------
+ * The same aggregate, byte for byte, and the same verdict as the calls above, for any n <= SSA_MAX_BATCH and with the
+ * lanes spread over slices of one context, several devices or several processes.  The tree of the transcript is defined
+ * level by level, so an aligned run of B = 2^t lanes is a whole subtree of it: a SHARD -- consecutive lanes whose first
+ * stands on a multiple of B in the aggregate; every shard but the last holds whole blocks of B -- reduces its lanes to one
+ * 32-byte TOP per block.  The tops of all shards, in lane order, give the root; the root goes back to the shards; each
+ * derives its lanes' coefficients from the root and the lanes' places and returns 32 bytes (producer: its part of
+ * e_agg) or one record of SSA_MSM_PARTIAL_WORDS words (validator: its part of the left-hand point).  Traffic: 32 bytes
+ * per block in, 32 bytes out, 32 or 192 bytes per shard back.
+ *
+ * The primitives are device forms and only enqueue on the context's stream; ORDERING for collectives on other streams
+ * is that of ssa_verify_batch_msm_partial_device above (ssa_ctx_stream_release / ssa_ctx_stream_acquire).  Tops, roots,
+ * challenge scalars and partial scalars are read and written as 64-bit words: 8-byte aligned, else SSA_ERR_ARG.
+ *   ssa_aggregate_shard_tops_device   n_s lanes at d_lanes -- signatures (lane_stride 81) or R's (lane_stride 49) -- with
+ *       their keys and messages -> ceil(n_s / block_lanes) tops; d_h_out (or NULL): the n_s challenge scalars mod q, four
+ *       words each, which ssa_verify_aggregate_shard_device takes.  block_lanes: a power of two, else SSA_ERR_ARG.
+ *       One ssa_k_hash, one ag_k_leaf and log2(block_lanes) launches of ag_k_level per MSM slice of lanes.
+ *   ssa_aggregate_root_device         n_tops tops of an aggregate of n lanes -> the 32-byte root.  block_lanes: 0, or the
+ *       B the tops were made with; then n_tops must be ceil(n / B).  n == 0 (no root exists), n_tops == 0 or n_tops > n:
+ *       SSA_ERR_ARG.
+ *   ssa_aggregate_shard_fold_device   producer: n_s signatures whose first is lane `lane0` of the aggregate and the root
+ *       -> d_e_out = sum a_i e_i mod q over them (32 bytes) and d_rs_out = their R's (49 n_s bytes).  d_status_out (or
+ *       NULL: no checks, the keys are not read): the checks, status bytes and count of ssa_aggregate_many without
+ *       SSA_AGG_CHECK; a lane that fails adds nothing to the sum.
+ *   ssa_verify_aggregate_shard_device validator: n_s R's at stride 49, keys, pk_inf and messages, the challenge scalars
+ *       from the tops call (d_h; NULL: hashed again), lane0 and the root -> one record in the format of
+ *       ssa_verify_batch_msm_partial (words 18..21 are zero: e = 0 on every lane).  An empty shard gives the identity
+ *       record.  The messages are read only by shards of at most SSA_MSM_SMALL_MAX lanes, whose kernel hashes for itself.
+ *   ssa_aggregate_combine_device      k (1..4096) partial scalars -> e_agg (canonical).
+ *   ssa_verify_aggregate_combine_device   k (1..4096) records, e_agg (32 bytes) and n -> the verdict of
+ *       ssa_verify_aggregate: the records are added up and compared with [e_agg]G in BOTH coordinates.  FAILS CLOSED as
+ *       ssa_msm_combine: a record without the magic word, with a set malformed word, a non-canonical limb or scalar or a
+ *       point off the curve gives SSA_MALFORMED.  n == 0: the rule of the empty aggregate (records are not read).
+ *
+ * ssa_aggregate_many_sliced / ssa_verify_aggregate_sliced (and _device): arguments, flags and return values of
+ * ssa_aggregate_many / ssa_verify_aggregate, on one context, for any n <= SSA_MAX_BATCH: the slices are the shards.  B is
+ * the largest power of two not above the context's MSM slice (SSA_AGG_BLOCK overrides it, for tests).  The validator
+ * keeps the challenge scalars of all n lanes (32 bytes per lane); every other workspace is one slice's.
+ * ssa_multi_aggregate_many / ssa_multi_verify_aggregate: host buffers, the blocks dealt to the devices of an ssa_multi
+ * in contiguous runs whose block counts differ by at most one (B from the first context); one host thread per device,
+ * root and combination on device 0. */
+int ssa_aggregate_shard_tops_device(ssa_ctx *ctx, const uint8_t *d_lanes, uint32_t lane_stride, const uint8_t *d_pks,
+                                    const uint8_t *d_msgs, const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len,
+                                    size_t n_s, size_t block_lanes, uint8_t *d_tops_out, uint64_t *d_h_out);
+int ssa_aggregate_root_device(ssa_ctx *ctx, const uint8_t *d_tops, size_t n_tops, size_t n, size_t block_lanes,
+                              uint8_t *d_root_out);
+int ssa_aggregate_shard_fold_device(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_pk_inf,
+                                    size_t n_s, size_t lane0, const uint8_t *d_root, uint8_t *d_e_out, uint8_t *d_rs_out,
+                                    uint8_t *d_status_out, uint64_t *d_n_fail_out);
+int ssa_verify_aggregate_shard_device(ssa_ctx *ctx, const uint8_t *d_rs49, const uint8_t *d_pks, const uint8_t *d_pk_inf,
+                                      const uint8_t *d_msgs, const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len,
+                                      const uint64_t *d_h, size_t n_s, size_t lane0, const uint8_t *d_root,
+                                      uint64_t *d_record_out);
+int ssa_aggregate_combine_device(ssa_ctx *ctx, const uint8_t *d_partials32, size_t k, uint8_t *d_e_agg_out);
+int ssa_verify_aggregate_combine_device(ssa_ctx *ctx, const uint64_t *d_records24, size_t k, const uint8_t *d_e_agg,
+                                        size_t n, uint32_t *d_verdict_out);
+int ssa_aggregate_many_sliced(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_inf,
+                              const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len, size_t n,
+                              uint32_t flags, uint8_t *agg_out, uint8_t *status_out, uint64_t *n_fail_out);
+int ssa_aggregate_many_sliced_device(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_pk_inf,
+                                     const uint8_t *d_msgs, const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len,
+                                     size_t n, uint32_t flags, uint8_t *d_agg_out, uint8_t *d_status_out,
+                                     uint64_t *d_n_fail_out);
+int ssa_verify_aggregate_sliced(ssa_ctx *ctx, const uint8_t *agg, const uint8_t *pks, const uint8_t *pk_inf,
+                                const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len, size_t n);
+int ssa_verify_aggregate_sliced_device(ssa_ctx *ctx, const uint8_t *d_agg, const uint8_t *d_pks, const uint8_t *d_pk_inf,
+                                       const uint8_t *d_msgs, const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len,
+                                       size_t n, uint32_t *d_verdict_out);
+int ssa_multi_aggregate_many(ssa_multi *m, const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_inf,
+                             const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len, size_t n,
+                             uint32_t flags, uint8_t *agg_out, uint8_t *status_out, uint64_t *n_fail_out);
+int ssa_multi_verify_aggregate(ssa_multi *m, const uint8_t *agg, const uint8_t *pks, const uint8_t *pk_inf,
+                               const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len, size_t n);
+/* tests: the coefficients a_(lane0 + i), i < n_s, of an aggregate with this root (host) -> n_s x 16 bytes */
+int ssa_debug_aggregate_shard_coeffs(ssa_ctx *ctx, const uint8_t root[32], size_t n_s, size_t lane0,
+                                     uint8_t *coeffs16_out);
 
 /* ---- many aggregates in one call --------------------------------------------------------
  * k aggregates, one verdict each: verdicts_out[j] is the value ssa_verify_aggregate returns for aggregate j handed in

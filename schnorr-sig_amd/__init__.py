@@ -260,6 +260,19 @@ def _load():
         "ssa_verify_aggregate": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz]),
         "ssa_verify_aggregate_device": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz, vp]),
         "ssa_debug_aggregate_coeffs": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz, vp]),
+        "ssa_aggregate_shard_tops_device": (i32, [vp, vp, u32, vp, vp, vp, sz, sz, sz, sz, vp, vp]),
+        "ssa_aggregate_root_device": (i32, [vp, vp, sz, sz, sz, vp]),
+        "ssa_aggregate_shard_fold_device": (i32, [vp, vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]),
+        "ssa_verify_aggregate_shard_device": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, vp, sz, sz, vp, vp]),
+        "ssa_aggregate_combine_device": (i32, [vp, vp, sz, vp]),
+        "ssa_verify_aggregate_combine_device": (i32, [vp, vp, sz, vp, sz, vp]),
+        "ssa_aggregate_many_sliced": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz, u32, vp, vp, u64p]),
+        "ssa_aggregate_many_sliced_device": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz, u32, vp, vp, vp]),
+        "ssa_verify_aggregate_sliced": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz]),
+        "ssa_verify_aggregate_sliced_device": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz, vp]),
+        "ssa_multi_aggregate_many": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz, u32, vp, vp, u64p]),
+        "ssa_multi_verify_aggregate": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz]),
+        "ssa_debug_aggregate_shard_coeffs": (i32, [vp, vp, sz, sz, vp]),
         "ssa_aggregate_valid_many": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz, vp, vp, u64p, vp]),
         "ssa_aggregate_valid_many_device": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz, vp, vp, u64p, vp]),
         "ssa_aggregate_valid_many_cached": (i32, [vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, vp, vp, u64p, vp, vp, vp, vp]),
@@ -690,6 +703,88 @@ class Engine:
         _check(_lib.ssa_verify_aggregate_device(
             self._ctx, d_agg, d_pks, *self._dev_batch(d_pk_inf, d_msgs, d_offsets, msg_stride, msg_len, n), d_verdict),
             "ssa_verify_aggregate_device")
+
+    # ---- sharded half-aggregation (include/schnorr_sig_amd.h) ----
+    def aggregate_sliced(self, sigs, pks, msgs, offsets=None, pk_inf=None, check=False):
+        """aggregate() for any n <= SSA_MAX_BATCH: slice after slice of this context, the same bytes"""
+        n, batch, keep = self._agg_batch(sigs, 81, pks, msgs, offsets, pk_inf)
+        agg = np.full(49 * n + 32, 255, dtype=np.uint8)
+        status = np.full(n, 255, dtype=np.uint8)
+        nfail = C.c_uint64(0)
+        st = _check(_lib.ssa_aggregate_many_sliced(self._ctx, *batch, AGG_CHECK if check else 0, _ptr(agg),
+                                                   _ptr(status) if n else None, C.byref(nfail)),
+                    "ssa_aggregate_many_sliced")
+        return st, agg, status, int(nfail.value)
+
+    def aggregate_sliced_device(self, d_sigs, d_pks, d_msgs, n, msg_len, d_agg, d_status=0, d_nfail=0, msg_stride=None,
+                                d_offsets=0, d_pk_inf=0, check=False):
+        """device form of aggregate_sliced (synchronises the stream, as aggregate_device does) -> status"""
+        return _check(_lib.ssa_aggregate_many_sliced_device(
+            self._ctx, d_sigs, d_pks, *self._dev_batch(d_pk_inf, d_msgs, d_offsets, msg_stride, msg_len, n),
+            AGG_CHECK if check else 0, d_agg, d_status or None, d_nfail or None), "ssa_aggregate_many_sliced_device")
+
+    def verify_aggregate_sliced(self, agg, pks, msgs, offsets=None, pk_inf=None):
+        """verify_aggregate() for any n <= SSA_MAX_BATCH -> status"""
+        n, batch, keep = self._agg_batch(agg, 49, pks, msgs, offsets, pk_inf)
+        if keep[0].size != 49 * n + 32:
+            raise MalformedInput("an aggregate of n signatures is 49 n + 32 bytes")
+        return _check(_lib.ssa_verify_aggregate_sliced(self._ctx, *batch), "ssa_verify_aggregate_sliced")
+
+    def verify_aggregate_sliced_device(self, d_agg, d_pks, d_msgs, n, msg_len, d_verdict, msg_stride=None, d_offsets=0,
+                                       d_pk_inf=0):
+        """device form: only enqueues; the status lands in the uint32 at d_verdict"""
+        _check(_lib.ssa_verify_aggregate_sliced_device(
+            self._ctx, d_agg, d_pks, *self._dev_batch(d_pk_inf, d_msgs, d_offsets, msg_stride, msg_len, n), d_verdict),
+            "ssa_verify_aggregate_sliced_device")
+
+    # The shard primitives: device addresses, everything only enqueued on the engine's stream.  A shard is n_s
+    # consecutive lanes of an aggregate whose first, lane0, stands on a multiple of block_lanes.
+    def aggregate_shard_tops_device(self, d_lanes, lane_stride, d_pks, d_msgs, n_s, msg_len, block_lanes, d_tops, d_h=0,
+                                    msg_stride=None, d_offsets=0):
+        """n_s signatures (lane_stride 81) or R's (49) -> ceil(n_s / block_lanes) x 32 bytes of tops at d_tops; d_h: the
+        n_s x 32 bytes of challenge scalars the validator's shard call takes"""
+        _check(_lib.ssa_aggregate_shard_tops_device(
+            self._ctx, d_lanes, lane_stride, d_pks, d_msgs, d_offsets or None,
+            msg_stride if msg_stride is not None else msg_len, msg_len, n_s, block_lanes, d_tops, d_h or None),
+            "ssa_aggregate_shard_tops_device")
+
+    def aggregate_root_device(self, d_tops, n_tops, n, d_root, block_lanes=0):
+        """the tops of all shards in lane order and the total n -> the 32-byte root at d_root"""
+        _check(_lib.ssa_aggregate_root_device(self._ctx, d_tops, n_tops, n, block_lanes, d_root),
+               "ssa_aggregate_root_device")
+
+    def aggregate_shard_fold_device(self, d_sigs, d_pks, n_s, lane0, d_root, d_e, d_rs, d_status=0, d_nfail=0, d_pk_inf=0):
+        """producer: the shard's sum a_i e_i mod q (32 bytes at d_e) and its R's (49 n_s bytes at d_rs); d_status: the
+        checks of aggregate() without check=True, one byte per lane"""
+        _check(_lib.ssa_aggregate_shard_fold_device(self._ctx, d_sigs, d_pks or None, d_pk_inf or None, n_s, lane0, d_root,
+                                                    d_e, d_rs or None, d_status or None, d_nfail or None),
+               "ssa_aggregate_shard_fold_device")
+
+    def verify_aggregate_shard_device(self, d_rs49, d_pks, d_msgs, n_s, msg_len, d_h, lane0, d_root, d_record24,
+                                      msg_stride=None, d_offsets=0, d_pk_inf=0):
+        """validator: the shard's R's, keys, messages and saved challenge scalars -> one 24-word record at d_record24"""
+        _check(_lib.ssa_verify_aggregate_shard_device(
+            self._ctx, d_rs49 or None, d_pks or None, d_pk_inf or None, d_msgs, d_offsets or None,
+            msg_stride if msg_stride is not None else msg_len, msg_len, d_h or None, n_s, lane0, d_root, d_record24),
+            "ssa_verify_aggregate_shard_device")
+
+    def aggregate_combine_device(self, d_partials32, k, d_e_agg):
+        """k partial scalars (32 bytes each) -> e_agg at d_e_agg"""
+        _check(_lib.ssa_aggregate_combine_device(self._ctx, d_partials32, k, d_e_agg), "ssa_aggregate_combine_device")
+
+    def verify_aggregate_combine_device(self, d_records24, k, d_e_agg, n, d_verdict):
+        """k records, e_agg and the total n -> the status in the uint32 at d_verdict; fails closed (MALFORMED) on a
+        record that is not one"""
+        _check(_lib.ssa_verify_aggregate_combine_device(self._ctx, d_records24 or None, k, d_e_agg, n, d_verdict),
+               "ssa_verify_aggregate_combine_device")
+
+    def aggregate_shard_coeffs(self, root32, n_s, lane0):
+        """tests: the coefficients of lanes [lane0, lane0 + n_s) of an aggregate with this root -> uint8[n_s, 16]"""
+        root = _np_u8(root32).reshape(32)
+        out = np.zeros((n_s, 16), dtype=np.uint8)
+        _check(_lib.ssa_debug_aggregate_shard_coeffs(self._ctx, _ptr(root), n_s, lane0, _ptr(out) if n_s else None),
+               "ssa_debug_aggregate_shard_coeffs")
+        return out
 
     def aggregate_coeffs(self, rs49, pks, msgs, offsets=None, pk_inf=None):
         """tests: the transcript's coefficients a_i of n R's (n x 49 bytes), keys and messages -> uint8[n, 16]"""
@@ -1658,6 +1753,30 @@ class MultiEngine:
                                                       stride, mlen, n, _ptr(c)), "ssa_multi_verify_batch_msm")
 
 
+    # half-aggregation with the blocks of the transcript dealt to the devices
+    _msg_args = Engine._msg_args
+    _agg_batch = Engine._agg_batch
+
+    def aggregate(self, sigs, pks, msgs, offsets=None, pk_inf=None, check=False):
+        """Engine.aggregate over the devices: the same (status, aggregate, per-lane status, n_fail), the same bytes"""
+        n, batch, keep = self._agg_batch(sigs, 81, pks, msgs, offsets, pk_inf)
+        agg = np.full(49 * n + 32, 255, dtype=np.uint8)
+        status = np.full(n, 255, dtype=np.uint8)
+        nfail = C.c_uint64(0)
+        st = _check(_lib.ssa_multi_aggregate_many(self._m, *batch, AGG_CHECK if check else 0, _ptr(agg),
+                                                  _ptr(status) if n else None, C.byref(nfail)), "ssa_multi_aggregate_many")
+        return st, agg, status, int(nfail.value)
+
+    def verify_aggregate(self, agg, pks, msgs, offsets=None, pk_inf=None):
+        """Engine.verify_aggregate over the devices -> status"""
+        n, batch, keep = self._agg_batch(agg, 49, pks, msgs, offsets, pk_inf)
+        if keep[0].size != 49 * n + 32:
+            raise MalformedInput("an aggregate of n signatures is 49 n + 32 bytes")
+        return _check(_lib.ssa_multi_verify_aggregate(self._m, *batch), "ssa_multi_verify_aggregate")
+
+    aggregate_sliced, verify_aggregate_sliced = aggregate, verify_aggregate     # (its shards are sliced as they need)
+
+
 _default_engine = None
 
 
@@ -1910,14 +2029,17 @@ class AggregateSignature:
         return (len(self.bytes) - 32) // 49
 
     @classmethod
-    def aggregate(cls, signatures, public_keys, messages, check=True, engine=None):
+    def aggregate(cls, signatures, public_keys, messages, check=True, engine=None, sliced=False):
         """Engine.aggregate over (signature, public key, message) objects.  check: every signature is verified first
-        (verify_batch semantics) and a slice with a bad one raises the SignatureError / MalformedInput of verify_batch."""
+        (verify_batch semantics) and a slice with a bad one raises the SignatureError / MalformedInput of verify_batch.
+        sliced: through Engine.aggregate_sliced (any n, the same bytes); engine may be a MultiEngine."""
         packed = _pack_triples(signatures, public_keys, messages)
         if packed is None:
             return cls(bytes(32))
         sigs, pks, inf, flat, off = packed
-        st, agg, _, _ = (engine or default_engine()).aggregate(sigs, pks, flat, offsets=off, pk_inf=inf, check=check)
+        eng = engine or default_engine()
+        st, agg, _, _ = (eng.aggregate_sliced if sliced else eng.aggregate)(sigs, pks, flat, offsets=off, pk_inf=inf,
+                                                                            check=check)
         if st == MALFORMED:
             raise MalformedInput("undecodable signature in batch (the reference panics here)")
         if st != OK:
@@ -1944,18 +2066,20 @@ class AggregateSignature:
             agg, kept = eng.aggregate_valid_cached(cache, sigs, pks, flat, offsets=off, pk_inf=inf)[:2]
         return cls(agg.tobytes()), [int(i) for i in kept]
 
-    def verify(self, public_keys, messages, engine=None):
-        """Ok -> None; otherwise raises SignatureError (the equation fails) or MalformedInput"""
+    def verify(self, public_keys, messages, engine=None, sliced=False):
+        """Ok -> None; otherwise raises SignatureError (the equation fails) or MalformedInput.  sliced: through
+        Engine.verify_aggregate_sliced (any n, the same verdict); engine may be a MultiEngine."""
         if len(public_keys) != len(self) or len(messages) != len(self):
             raise MalformedInput("We should have the same number of messages than public keys")
         eng = engine or default_engine()
+        verify_aggregate = eng.verify_aggregate_sliced if sliced else eng.verify_aggregate
         if len(self) == 0:
-            st = eng.verify_aggregate(np.frombuffer(self.bytes, np.uint8), np.zeros((0, 96), np.uint8), None)
+            st = verify_aggregate(np.frombuffer(self.bytes, np.uint8), np.zeros((0, 96), np.uint8), None)
         else:
             pks = np.frombuffer(b"".join(p.affine for p in public_keys), np.uint8)
             inf = np.array([1 if p.is_identity else 0 for p in public_keys], np.uint8)
             flat, off = pack_messages(messages)
-            st = eng.verify_aggregate(np.frombuffer(self.bytes, np.uint8), pks, flat, offsets=off, pk_inf=inf)
+            st = verify_aggregate(np.frombuffer(self.bytes, np.uint8), pks, flat, offsets=off, pk_inf=inf)
         if st == OK:
             return None
         if st == MALFORMED:

@@ -21,6 +21,8 @@
 //                                  first also makes the checks of msm_k_prepare (canonical limbs, e < q, key on the
 //                                  curve, R decodable) when the caller did not screen the signatures
 //   ag_k_pack      the first 49 bytes of every signature side by side: the aggregate's R's
+//   ag_k_level     one level of the tree as one flat launch, a lane per output node: what a shard
+//                  of a larger aggregate reduces its blocks of 2^t lanes with
 //   ag_k_finish    one wave per aggregate: [e_agg]G from the comb and the EXACT comparison with the left-hand point of
 //                  the MSM's record (affine x and y, or the identity) -- not the x-only one of msm_k_finish; the empty
 //                  aggregate is valid iff its scalar is zero
@@ -203,6 +205,32 @@ ag_k_leaf(const DevParams *__restrict__ prm, const u64 *__restrict__ dig, const 
     for (int k = 0; k < 4; k++) nodes[4 * i + k] = d[k];
 }
 
+// One level of the tree, flat: lane j of the launch writes node j of the next level,
+// H(in[2j] || in[2j + 1]), or in[2j] unchanged when it is the odd last node of its level; count nodes come in,
+// (count + 1) / 2 go out.  One permutation per lane at ag_k_leaf's shape; nodes travel through global memory alone (in and
+// out are different buffers), so no lane waits for another.  Over the lanes of a shard that starts on a multiple of
+// B = 2^t, pairs of the first t levels never cross a block of B leaves: t launches leave one top per block, the ragged
+// last block's by the same odd-node rule.
+__global__ void __launch_bounds__(256, 4)
+ag_k_level(const DevParams *__restrict__ prm, const u64 *__restrict__ in, size_t count, u64 *__restrict__ out) {
+    __shared__ u64 lds[RS_LDS_U64];
+    u64 *A = lds + threadIdx.x;
+    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= (count + 1) / 2) return;
+    u64 r[4];
+    if (2 * j + 1 < count) {
+        u64 v[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) v[k] = in[8 * j + k];
+        ag_hash8(A, prm, v, 8u, r);
+    } else {                                          // the odd last node moves up unchanged
+#pragma unroll
+        for (int k = 0; k < 4; k++) r[k] = in[8 * j + k];
+    }
+#pragma unroll
+    for (int k = 0; k < 4; k++) out[4 * j + k] = r[k];
+}
+
 // cnt (>= 1) nodes at src reduced by one workgroup of 256 lanes to one node at out (four words); top != 0: the node left
 // is a tree's top and out receives the root, H(top || n_total || 0xA2).  lds, node: the workgroup's shared arrays.
 SSA_DEV void ag_tree_reduce(u64 *lds, u64 *node, const DevParams *__restrict__ prm, const u64 *__restrict__ src, u32 cnt,
@@ -284,10 +312,11 @@ ag_k_lane_map(const u32 *__restrict__ first, u32 k, size_t n, u32 *__restrict__ 
 }
 
 // a_i = H(root_j || i - first_j || 0xA3) with the root and the index of the lane's own aggregate j = map[i]; map and
-// first == nullptr: one aggregate, root 0 and index i
+// first == nullptr: one aggregate, root 0 and index lane0 + i -- lane0 is the place of the launch's first lane in its
+// aggregate: 0 but for a shard of a larger aggregate
 __global__ void __launch_bounds__(256, 4)
 ag_k_coeff(const DevParams *__restrict__ prm, const u64 *__restrict__ roots, const u32 *__restrict__ map,
-           const u32 *__restrict__ first, size_t n, u64 *__restrict__ coeffs) {
+           const u32 *__restrict__ first, size_t n, u64 *__restrict__ coeffs, u64 lane0) {
     __shared__ u64 lds[RS_LDS_U64];
     u64 *A = lds + threadIdx.x;
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -296,7 +325,7 @@ ag_k_coeff(const DevParams *__restrict__ prm, const u64 *__restrict__ roots, con
     u64 in[8], d[4];
 #pragma unroll
     for (int k = 0; k < 4; k++) in[k] = roots[4 * (size_t)j + k];
-    in[4] = (u64)(i - (first ? first[j] : 0u));
+    in[4] = lane0 + (u64)(i - (first ? first[j] : 0u));
     in[5] = AG_TAG_COEFF;
     in[6] = in[7] = 0;
     ag_hash8(A, prm, in, 6u, d);
@@ -414,6 +443,13 @@ SSA_DEV void ag_finish_wave(CoopLds &L, const u64 *__restrict__ rec, const u8 *_
 // One wave per aggregate: block s compares recs[s], the record of aggregate j = agg0 + s (the small path: the sum of its
 // lanes' records), with [e_agg_j]G for that aggregate's own scalar.  first == nullptr: one aggregate of n lanes.  The empty
 // aggregate has no record: it is valid iff its 32 bytes are zero.
+// the verdict of an aggregate without lanes
+SSA_DEV u32 ag_empty_verdict(const u8 *__restrict__ e_agg) {
+    const sc256 e = ld_sc(e_agg);
+    const bool zero = (e.w[0] | e.w[1] | e.w[2] | e.w[3]) == 0;
+    return zero ? ST_OK : (sc_geq_q(e) ? ST_MALFORMED : ST_INVALID_SIG);
+}
+
 __global__ void __launch_bounds__(64)
 ag_k_finish(const u64 *__restrict__ recs, const u8 *__restrict__ aggs, const u32 *__restrict__ first, size_t n, u32 agg0,
             const u64 *__restrict__ gtab, u32 *__restrict__ verdicts) {
@@ -421,14 +457,23 @@ ag_k_finish(const u64 *__restrict__ recs, const u8 *__restrict__ aggs, const u32
     const u32 j = agg0 + blockIdx.x;
     const u8 *e_agg = aggs + ag_wire_e(first, j, n);
     if (first ? first[j + 1] == first[j] : n == 0) {  // (block-uniform)
-        if (threadIdx.x == 0) {
-            const sc256 e = ld_sc(e_agg);
-            const bool zero = (e.w[0] | e.w[1] | e.w[2] | e.w[3]) == 0;
-            verdicts[j] = zero ? ST_OK : (sc_geq_q(e) ? ST_MALFORMED : ST_INVALID_SIG);
-        }
+        if (threadIdx.x == 0) verdicts[j] = ag_empty_verdict(e_agg);
         return;
     }
     ag_finish_wave(L, recs + 24 * (size_t)blockIdx.x, e_agg, gtab, verdicts + j);
+}
+
+// ONE wave, one aggregate whose scalar stands on its own (ssa_verify_aggregate_combine_device): rec against [e_agg]G, or
+// the rule of the empty aggregate when it has no lanes (rec is then not read)
+__global__ void __launch_bounds__(64)
+ag_k_finish_scalar(const u64 *__restrict__ rec, const u8 *__restrict__ e_agg, u32 empty, const u64 *__restrict__ gtab,
+                   u32 *__restrict__ verdict) {
+    __shared__ CoopLds L;
+    if (empty) {                                      // (block-uniform)
+        if (threadIdx.x == 0) *verdict = ag_empty_verdict(e_agg);
+        return;
+    }
+    ag_finish_wave(L, rec, e_agg, gtab, verdict);
 }
 
 // ---- the bucket path: a group of `segs` consecutive aggregates padded to segments of seg_lanes lanes each ----

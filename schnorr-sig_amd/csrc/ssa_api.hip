@@ -200,6 +200,7 @@ static void ctx_read_env(ssa_ctx *ctx, uint32_t *gtab_bits, uint64_t *hbm_budget
     env_one_of("SSA_VERIFY_BLOCK", {64, 128, 256}, k.verify_block);
     env_u64("SSA_LANE_SLICE", 256, UINT64_MAX, k.lane_slice);        // lanes per slice of the per-lane kernels (workspace bound)
     env_u64("SSA_MSM_SLICE", 256, (uint64_t)1 << 23, k.msm_slice);   // signatures per slice of the MSM-form pipeline
+    env_u64("SSA_AGG_BLOCK", 1, (uint64_t)1 << 30, k.agg_block);     // tests: lanes per block of the sharded half-aggregation
     env_int("SSA_MSM_TREE_GROUP", 2, 64, k.msm_tree_group);
     env_int("SSA_TAIL_PIECES", 0, VP_MAX, k.tail_pieces);            // pieces of a tail group's work (0 / 1: no end game)
     env_int("SSA_TAIL_GENS", 1, 8, k.tail_gens);                     // tail groups, in generations of resident waves
@@ -1880,26 +1881,30 @@ struct AgPass {
     u32 count, top_n;
     unsigned groups() const { return desc_off == AG_UNIFORM ? (count + AG_TREE_SPAN - 1) / AG_TREE_SPAN : count; }
 };
-// the passes of one aggregate of n (>= 1) lanes: nothing to upload
-static std::vector<AgPass> ag_uniform_passes(size_t n) {
+// the passes over `nodes` (>= 1) nodes of one aggregate of n lanes: nothing to upload.  The nodes are the n leaves, or
+// the ceil(n / B) tops of its blocks of B lanes: the root hashes n either way.
+static std::vector<AgPass> ag_uniform_passes(size_t nodes, size_t n) {
     std::vector<AgPass> passes;
-    for (size_t count = n;; count = passes.back().groups()) {
+    for (size_t count = nodes;; count = passes.back().groups()) {
         const bool top = count <= AG_TREE_SPAN;
         passes.push_back({AG_UNIFORM, (u32)count, top ? (u32)n : 0u});
         if (top) return passes;
     }
 }
+static std::vector<AgPass> ag_uniform_passes(size_t n) { return ag_uniform_passes(n, n); }
 
 // The transcript over the n (>= 1) lanes of a call, on ctx->stream, in two halves.  d_first: the k + 1 prefix sums of an
 // uploaded plan (agm_upload_plan); nullptr: one aggregate, no plan, no lane map.
 // The front: the R's and the challenge hashes.  d_wire != nullptr: the R's come out of the wire form and are laid out at
 // stride 81 in ctx->ag_sigs first, and *d_sigs then points there; else they stand so in *d_sigs.  ONE launch of ssa_k_hash
-// leaves the raw digests in ctx->ag_dig and, with_h, the challenge scalars mod q in ctx->ws_h.
+// leaves the raw digests in ctx->ag_dig and, with_h, the challenge scalars mod q in ctx->ws_h (d_h_out: there instead --
+// a slice of a larger call's scalars).
 static int ag_transcript_front(ssa_ctx *ctx, const u8 *d_wire, const u8 **d_sigs, const u8 *d_pks, const MsgView &mv,
-                               size_t n, bool with_h, const u32 *d_first, size_t k) {
+                               size_t n, bool with_h, const u32 *d_first, size_t k, u64 *d_h_out = nullptr) {
     if ((d_wire && ctx->ag_sigs.reserve(n * 81 + 16)) || (d_first && ctx->agm_map.reserve(n * 4)) ||
         ctx->ag_dig.reserve(n * 32) || (with_h && ctx->ws_h.reserve(n * 32)))
         return SSA_ERR_HIP;
+    if (with_h) d_h_out = (u64 *)ctx->ws_h.p;
     if (d_wire) {
         const int rc = timed_launch(ctx, d_first ? "ag_k_expand_many" : "ag_k_expand", [&] {
             if (d_first)
@@ -1913,7 +1918,7 @@ static int ag_transcript_front(ssa_ctx *ctx, const u8 *d_wire, const u8 **d_sigs
     }
     return timed_launch(ctx, "ssa_k_hash", [&] {
         hipLaunchKernelGGL(ssa_k_hash, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, ctx->d_params, *d_sigs, d_pks, mv, n,
-                           with_h ? (u64 *)ctx->ws_h.p : (u64 *)nullptr, (u8 *)ctx->ag_dig.p, (const u32 *)nullptr, 0u);
+                           d_h_out, (u8 *)ctx->ag_dig.p, (const u32 *)nullptr, 0u);
     });
 }
 
@@ -1950,7 +1955,7 @@ static int ag_transcript_from_digests(ssa_ctx *ctx, const u64 *d_dig, const u8 *
     if (rc) return rc;
     return timed_launch(ctx, "ag_k_coeff", [&] {
         hipLaunchKernelGGL(ag_k_coeff, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, ctx->d_params,
-                           (const u64 *)ctx->agm_roots.p, d_map, d_first, n, (u64 *)ctx->ag_coeffs.p);
+                           (const u64 *)ctx->agm_roots.p, d_map, d_first, n, (u64 *)ctx->ag_coeffs.p, (u64)0);
     });
 }
 
@@ -1975,9 +1980,32 @@ static int ag_fold(ssa_ctx *ctx, const u8 *d_sigs, const u8 *d_pks, const u8 *d_
     });
 }
 
-static int agg_check_args(const ssa_ctx *ctx, const MsgView &mv, size_t n) {
+// sliced: the forms of DESIGN.md section 25, any n <= SSA_MAX_BATCH; every other call takes one MSM slice at most
+static int agg_check_args(const ssa_ctx *ctx, const MsgView &mv, size_t n, bool sliced = false) {
     if (int rc = check_msgs(mv, n)) return rc;
-    return n > ctx->knobs.msm_slice ? SSA_ERR_ARG : 0;      // one MSM slice: DESIGN.md section 20, out of scope
+    return !sliced && n > ctx->knobs.msm_slice ? SSA_ERR_ARG : 0;
+}
+
+// What a producer call returns once the fold has counted: the stream is synchronised and *d_fail read.  Refused
+// (*st_out != 0): d_agg_out is zeroed and *st_out is SSA_MALFORMED or, screened, the smallest nonzero status.
+static int ag_refusal(ssa_ctx *ctx, size_t n, bool screened, const u8 *d_status, const unsigned long long *d_fail,
+                      u8 *d_agg_out, int *st_out) {
+    *st_out = SSA_OK;
+    unsigned long long nf = 0;
+    HIP_TRY(hipMemcpyAsync(&nf, d_fail, sizeof nf, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (!nf) return 0;
+    HIP_TRY(hipMemsetAsync(d_agg_out, 0, SSA_AGGREGATE_LENGTH(n), ctx->stream));
+    int st = SSA_MALFORMED;
+    if (screened) {
+        std::vector<uint8_t> h(n);
+        HIP_TRY(hipMemcpyAsync(h.data(), d_status, n, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        for (uint8_t v : h)
+            if (v && (int)v < st) st = v;
+    }
+    *st_out = st;
+    return 0;
 }
 
 // Synchronises the stream: the status it returns is read from the device.
@@ -2003,32 +2031,21 @@ extern "C" int ssa_aggregate_many_device(ssa_ctx *ctx, const uint8_t *d_sigs, co
             return rc;
     if (int rc = ag_transcript(ctx, nullptr, d_sigs, d_pks, b.msgs, n, false, nullptr, 1, ag_uniform_passes(n))) return rc;
     if (int rc = ag_fold(ctx, d_sigs, d_pks, d_pk_inf, n, screened ? (u8 *)nullptr : d_status, d_fail)) return rc;
-    unsigned long long nf = 0;
-    HIP_TRY(hipMemcpyAsync(&nf, d_fail, sizeof nf, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (nf) {     // refused: no aggregate, the smallest nonzero status
-        HIP_TRY(hipMemsetAsync(d_agg_out, 0, SSA_AGGREGATE_LENGTH(n), ctx->stream));
-        int st = SSA_MALFORMED;
-        if (screened) {
-            std::vector<uint8_t> h(n);
-            HIP_TRY(hipMemcpyAsync(h.data(), d_status, n, hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(hipStreamSynchronize(ctx->stream));
-            for (uint8_t s : h)
-                if (s && (int)s < st) st = s;
-        }
-        return st;
-    }
+    int st;
+    if (int rc = ag_refusal(ctx, n, screened, d_status, d_fail, d_agg_out, &st)) return rc;
+    if (st) return st;     // refused: no aggregate
     hipLaunchKernelGGL(ag_k_pack, dim3(grid_for((n * 49 + 3) / 4, 256)), dim3(256), 0, ctx->stream, d_sigs, n, d_agg_out);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(d_agg_out + 49 * n, ag_misc(ctx, AG_E), 32, hipMemcpyDeviceToDevice, ctx->stream));
     return SSA_OK;
 }
 
-extern "C" int ssa_aggregate_many(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_inf,
-                                  const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len, size_t n,
-                                  uint32_t flags, uint8_t *agg_out, uint8_t *status_out, uint64_t *n_fail_out) {
+// the host form of ssa_aggregate_many and of its sliced twin: staging and copies back are the same
+static int aggregate_many_host(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_inf,
+                               const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len, size_t n,
+                               uint32_t flags, uint8_t *agg_out, uint8_t *status_out, uint64_t *n_fail_out, bool sliced) {
     if (!ctx || !agg_out || (flags & ~SSA_AGG_CHECK) || (n && (!sigs || !pks))) return SSA_ERR_ARG;
-    if (int rc = agg_check_args(ctx, {msgs, msg_off, msg_stride, msg_len}, n)) return rc;
+    if (int rc = agg_check_args(ctx, {msgs, msg_off, msg_stride, msg_len}, n, sliced)) return rc;
     if (int rc = check_host_offsets(msg_off, n)) return rc;
     if (n_fail_out) *n_fail_out = 0;
     if (n == 0) {
@@ -2045,14 +2062,21 @@ extern "C" int ssa_aggregate_many(ssa_ctx *ctx, const uint8_t *sigs, const uint8
     hc.copy_back(&nf, ctx->ws_fail.p, sizeof nf);
     int st = SSA_OK;       // a refusal is a result, not an error: the zeroed aggregate and the statuses still come back
     const int rc = hc.finish([&] {
-        const int r = ssa_aggregate_many_device(ctx, d_sigs, d_pks, d_inf, mv.msgs, mv.off, msg_stride, msg_len, n, flags,
-                                                d_agg, d_status, nullptr);
+        const int r = (sliced ? ssa_aggregate_many_sliced_device : ssa_aggregate_many_device)(
+            ctx, d_sigs, d_pks, d_inf, mv.msgs, mv.off, msg_stride, msg_len, n, flags, d_agg, d_status, nullptr);
         if (r > 0) st = r;
         return r > 0 ? 0 : r;
     });
     if (rc) return rc;
     if (n_fail_out) *n_fail_out = nf;
     return st;
+}
+
+extern "C" int ssa_aggregate_many(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_inf,
+                                  const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len, size_t n,
+                                  uint32_t flags, uint8_t *agg_out, uint8_t *status_out, uint64_t *n_fail_out) {
+    return aggregate_many_host(ctx, sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len, n, flags, agg_out, status_out,
+                               n_fail_out, false);
 }
 
 // ------------------------------------------------------------------ filtering half-aggregation
@@ -2192,11 +2216,11 @@ extern "C" int ssa_verify_aggregate_device(ssa_ctx *ctx, const uint8_t *d_agg, c
     });
 }
 
-extern "C" int ssa_verify_aggregate(ssa_ctx *ctx, const uint8_t *agg, const uint8_t *pks, const uint8_t *pk_inf,
-                                    const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len,
-                                    size_t n) {
+static int verify_aggregate_host(ssa_ctx *ctx, const uint8_t *agg, const uint8_t *pks, const uint8_t *pk_inf,
+                                 const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len, size_t n,
+                                 bool sliced) {
     if (!ctx || !agg || (n && !pks)) return SSA_ERR_ARG;
-    if (int rc = agg_check_args(ctx, {msgs, msg_off, msg_stride, msg_len}, n)) return rc;
+    if (int rc = agg_check_args(ctx, {msgs, msg_off, msg_stride, msg_len}, n, sliced)) return rc;
     if (int rc = check_host_offsets(msg_off, n)) return rc;
     HostCall hc(ctx);
     const u8 *d_agg = hc.in(ctx->st_sigs, agg, SSA_AGGREGATE_LENGTH(n)), *d_pks = hc.in(ctx->st_pks, pks, n * 96);
@@ -2205,9 +2229,484 @@ extern "C" int ssa_verify_aggregate(ssa_ctx *ctx, const uint8_t *agg, const uint
     uint32_t v = SSA_MALFORMED, *d_verdict = (uint32_t *)((char *)ctx->ws_fail.p + 32);
     hc.copy_back(&v, d_verdict, sizeof v);
     const int rc = hc.finish([&] {
-        return ssa_verify_aggregate_device(ctx, d_agg, d_pks, d_inf, mv.msgs, mv.off, msg_stride, msg_len, n, d_verdict);
+        return (sliced ? ssa_verify_aggregate_sliced_device : ssa_verify_aggregate_device)(
+            ctx, d_agg, d_pks, d_inf, mv.msgs, mv.off, msg_stride, msg_len, n, d_verdict);
     });
     return rc ? rc : (int)v;
+}
+
+extern "C" int ssa_verify_aggregate(ssa_ctx *ctx, const uint8_t *agg, const uint8_t *pks, const uint8_t *pk_inf,
+                                    const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len,
+                                    size_t n) {
+    return verify_aggregate_host(ctx, agg, pks, pk_inf, msgs, msg_off, msg_stride, msg_len, n, false);
+}
+
+// ------------------------------------------------------------------ sliced and sharded half-aggregation
+// The transcript's tree is defined level by level, so an aligned run of B = 2^t leaves is a whole subtree: a shard (a
+// slice of one context, a device, a rank) reduces ITS lanes to one 32-byte top per block of B, whoever holds all the tops
+// finishes the tree and hashes the root with the total n, and every shard derives its lanes' coefficients from the root
+// and the lanes' places in the aggregate.  What is left is linear: a partial sum a_i e_i mod q per shard for the producer,
+// one MSM record per shard for the validator.  The four steps below take any number of lanes and walk them in pieces of
+// at most one MSM slice; the primitives of the ABI, the sliced calls and the ssa_multi calls are these steps in a row.
+static inline size_t pow2_floor(size_t v) {
+    size_t p = 1;
+    while (p <= v / 2) p *= 2;
+    return p;
+}
+static inline bool is_pow2(size_t v) { return v && !(v & (v - 1)); }
+static inline bool aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
+// lanes per block of the sliced and ssa_multi calls: the largest power of two within the MSM slice, or the tests' knob
+static size_t ags_block(const ssa_ctx *ctx) {
+    return pow2_floor(ctx->knobs.agg_block ? ctx->knobs.agg_block : ctx->knobs.msm_slice);
+}
+// lanes per piece of a walk: a power of two, so whole blocks of B -- one MSM slice, or one block where a block is larger
+static size_t ags_piece(const ssa_ctx *ctx, size_t B = 1) { return std::max(B, pow2_floor(ctx->knobs.msm_slice)); }
+
+// Step 1.  The n_s lanes at d_lanes (signatures at stride 81 or R's at stride 49; the shard's first lane stands on a
+// multiple of B in its aggregate) -> ceil(n_s / B) tops at d_tops_out, and with d_h_out the n_s challenge scalars mod q.
+// Per piece: ag_k_expand for R's, ONE ssa_k_hash, ONE ag_k_leaf and log2(B) launches of ag_k_level (fewer once one node
+// is left), between ctx->ag_nodes and ctx->ag_nodes2; the last launch writes the tops where they go.
+static int ags_tops(ssa_ctx *ctx, const u8 *d_lanes, u32 stride, const u8 *d_pks, const MsgView &mv, size_t n_s, size_t B,
+                    u64 *d_tops_out, u64 *d_h_out) {
+    const DevBatch b{nullptr, d_pks, nullptr, mv};
+    const size_t piece = ags_piece(ctx, B);
+    for (size_t lo = 0; lo < n_s; lo += piece) {
+        const size_t cnt = std::min(piece, n_s - lo);
+        const DevBatch s = b.slice(lo);
+        const u8 *d_sigs = d_lanes + (size_t)stride * lo;
+        if (int rc = ag_transcript_front(ctx, stride == 49 ? d_sigs : nullptr, &d_sigs, s.pks, s.msgs, cnt, false, nullptr, 1,
+                                         d_h_out ? d_h_out + 4 * lo : nullptr))
+            return rc;
+        unsigned launches = 0;
+        for (size_t c = cnt, l = B; l > 1 && c > 1; l /= 2, c = (c + 1) / 2) launches++;
+        if (ctx->ag_nodes.reserve(cnt * 32) || ctx->ag_nodes2.reserve((cnt + 1) / 2 * 32)) return SSA_ERR_HIP;
+        u64 *const dst = d_tops_out + 4 * (lo / B), *bufs[2] = {(u64 *)ctx->ag_nodes.p, (u64 *)ctx->ag_nodes2.p};
+        int rc = timed_launch(ctx, "ag_k_leaf", [&] {
+            hipLaunchKernelGGL(ag_k_leaf, dim3(grid_for(cnt, 256)), dim3(256), 0, ctx->stream, ctx->d_params,
+                               (const u64 *)ctx->ag_dig.p, d_sigs, cnt, launches ? bufs[0] : dst);
+        });
+        if (rc) return rc;
+        if (!launches) continue;
+        rc = timed_launch(ctx, "ag_k_level", [&] {
+            size_t c = cnt;
+            for (unsigned l = 0; l < launches; l++, c = (c + 1) / 2)
+                hipLaunchKernelGGL(ag_k_level, dim3(grid_for((c + 1) / 2, 256)), dim3(256), 0, ctx->stream, ctx->d_params,
+                                   (const u64 *)bufs[l & 1u], c, l + 1 == launches ? dst : bufs[(l + 1) & 1u]);
+        });
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+// Step 2.  The n_tops (>= 1) tops of an aggregate of n lanes -> its root: the passes of ag_k_tree over them, and the
+// last workgroup hashes n.
+static int ags_root(ssa_ctx *ctx, const u64 *d_tops, size_t n_tops, size_t n, u64 *d_root_out) {
+    const std::vector<AgPass> passes = ag_uniform_passes(n_tops, n);
+    const size_t widest = passes[0].groups();
+    if (ctx->ag_nodes.reserve(widest * 32) || ctx->ag_nodes2.reserve(widest * 32)) return SSA_ERR_HIP;
+    return timed_launch(ctx, "ag_k_tree", [&] {
+        const u64 *in = d_tops;
+        u64 *ping = (u64 *)ctx->ag_nodes2.p, *pong = (u64 *)ctx->ag_nodes.p;
+        for (const AgPass &p : passes) {
+            hipLaunchKernelGGL(ag_k_tree, dim3(p.groups()), dim3(256), 0, ctx->stream, ctx->d_params, in,
+                               (const AgTreeDesc *)nullptr, p.count, p.top_n, ping, d_root_out);
+            in = ping;
+            std::swap(ping, pong);
+        }
+    });
+}
+
+// the coefficients of cnt lanes whose first stands at `lane0` of its aggregate, from the root at d_root, into ctx->ag_coeffs
+static int ags_coeffs(ssa_ctx *ctx, const u64 *d_root, size_t cnt, size_t lane0) {
+    if (ctx->ag_coeffs.reserve(cnt * 16)) return SSA_ERR_HIP;
+    return timed_launch(ctx, "ag_k_coeff", [&] {
+        hipLaunchKernelGGL(ag_k_coeff, dim3(grid_for(cnt, 256)), dim3(256), 0, ctx->stream, ctx->d_params, d_root,
+                           (const u32 *)nullptr, (const u32 *)nullptr, cnt, (u64 *)ctx->ag_coeffs.p, (u64)lane0);
+    });
+}
+
+// Step 3, producer.  The n_s signatures of b, the first at `lane0` of the aggregate: d_e_out (32 bytes) = sum a_i e_i mod
+// q over them, d_rs_out their 49 n_s bytes of R's; d_status != nullptr: the checks of ag_k_fold, *d_fail is added to.
+static int ags_fold(ssa_ctx *ctx, const DevBatch &b, size_t n_s, size_t lane0, const u64 *d_root, u8 *d_e_out, u8 *d_rs_out,
+                    u8 *d_status, unsigned long long *d_fail) {
+    if (n_s == 0) {
+        HIP_TRY(hipMemsetAsync(d_e_out, 0, 32, ctx->stream));
+        return 0;
+    }
+    const size_t piece = ags_piece(ctx), k = (n_s + piece - 1) / piece;
+    if (ctx->ags_parts.reserve(k * 32) || ctx->ag_partials.reserve((size_t)grid_for(std::min(piece, n_s), 256) * 32))
+        return SSA_ERR_HIP;
+    if (int rc = for_dev_slices(b, n_s, piece, [&](size_t lo, size_t cnt, const DevBatch &s) {
+            if (int rc = ags_coeffs(ctx, d_root, cnt, lane0 + lo)) return rc;
+            const unsigned n_blocks = grid_for(cnt, 256);
+            return timed_launch(ctx, "ag_k_fold", [&] {
+                hipLaunchKernelGGL(ag_k_fold, dim3(n_blocks), dim3(256), 0, ctx->stream, s.sigs, s.pks, s.pk_inf,
+                                   (const u64 *)ctx->ag_coeffs.p, cnt, (u64 *)ctx->ag_partials.p,
+                                   d_status ? d_status + lo : (u8 *)nullptr, d_fail);
+                hipLaunchKernelGGL(ag_k_fold_finish, dim3(1), dim3(256), 0, ctx->stream, (const u64 *)ctx->ag_partials.p,
+                                   n_blocks, k == 1 ? d_e_out : (u8 *)ctx->ags_parts.p + 32 * (lo / piece));
+                hipLaunchKernelGGL(ag_k_pack, dim3(grid_for((cnt * 49 + 3) / 4, 256)), dim3(256), 0, ctx->stream, s.sigs, cnt,
+                                   d_rs_out + 49 * lo);
+            });
+        }))
+        return rc;
+    if (k == 1) return 0;
+    return timed_launch(ctx, "ag_k_fold", [&] {
+        hipLaunchKernelGGL(ag_k_fold_finish, dim3(1), dim3(256), 0, ctx->stream, (const u64 *)ctx->ags_parts.p, (u32)k, d_e_out);
+    });
+}
+
+// Step 3, validator.  The n_s R's at d_rs49 with their keys and messages (b; its sigs are not read) and challenge scalars
+// d_h (nullptr: hashed again), the first at `lane0` of the aggregate: d_rec_out = the record of the MSM over (R_i, e = 0)
+// with the transcript's coefficients -- per piece through ssa_internal_msm_record, the pieces' records added up.  A piece
+// of at most msm_small_max lanes goes through msm_k_small, which hashes for itself: that is what the messages are for.
+// expanded: ctx->ag_sigs still holds the R's at stride 81 from the walk of the tops (one piece in all).
+static int ags_record(ssa_ctx *ctx, const u8 *d_rs49, const DevBatch &b, const u64 *d_h, size_t n_s, size_t lane0,
+                      const u64 *d_root, u64 *d_rec_out, bool expanded = false) {
+    const size_t piece = ags_piece(ctx), k = n_s ? (n_s + piece - 1) / piece : 1;
+    if (k > 4096) return SSA_ERR_ARG;
+    if (ctx->ags_recs.reserve(k * 24 * sizeof(u64)) || ctx->ag_coeffs.reserve(16)) return SSA_ERR_HIP;
+    for (size_t lo = 0, j = 0; j < k; lo += piece, j++) {
+        const size_t cnt = std::min(piece, n_s - lo);
+        if (cnt && !(expanded && k == 1)) {
+            if (ctx->ag_sigs.reserve(cnt * 81 + 16)) return SSA_ERR_HIP;
+            const int rc = timed_launch(ctx, "ag_k_expand", [&] {
+                hipLaunchKernelGGL(ag_k_expand, dim3(grid_for((cnt * 81 + 3) / 4, 256)), dim3(256), 0, ctx->stream,
+                                   d_rs49 + 49 * lo, (const u32 *)nullptr, cnt, (u8 *)ctx->ag_sigs.p);
+            });
+            if (rc) return rc;
+        }
+        if (cnt)
+            if (int rc = ags_coeffs(ctx, d_root, cnt, lane0 + lo)) return rc;
+        DevBatch s = b.slice(lo);
+        s.sigs = (const u8 *)ctx->ag_sigs.p;
+        if (int rc = ssa_internal_msm_record(ctx, s, cnt, (const u8 *)ctx->ag_coeffs.p, 16,
+                                             d_h ? (const uint64_t *)(d_h + 4 * lo) : nullptr,
+                                             k == 1 ? (uint64_t *)d_rec_out : (uint64_t *)ctx->ags_recs.p + 24 * j))
+            return rc;
+    }
+    return k == 1 ? 0 : ssa_internal_msm_sum_records(ctx, (const uint64_t *)ctx->ags_recs.p, k, false, (uint64_t *)d_rec_out);
+}
+
+// ---- the primitives: each only enqueues on the context's stream
+extern "C" int ssa_aggregate_shard_tops_device(ssa_ctx *ctx, const uint8_t *d_lanes, uint32_t lane_stride,
+                                               const uint8_t *d_pks, const uint8_t *d_msgs, const uint64_t *d_msg_off,
+                                               size_t msg_stride, size_t msg_len, size_t n_s, size_t block_lanes,
+                                               uint8_t *d_tops_out, uint64_t *d_h_out) {
+    const MsgView mv{d_msgs, d_msg_off, msg_stride, msg_len};
+    if (!ctx || (lane_stride != 81 && lane_stride != 49) || !is_pow2(block_lanes) || block_lanes > SSA_MAX_BATCH ||
+        (n_s && (!d_lanes || !d_pks || !d_tops_out)) || !aligned8(d_tops_out) || !aligned8(d_h_out))
+        return SSA_ERR_ARG;
+    if (int rc = check_msgs(mv, n_s)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    return ags_tops(ctx, d_lanes, lane_stride, d_pks, mv, n_s, block_lanes, (u64 *)d_tops_out, (u64 *)d_h_out);
+}
+
+extern "C" int ssa_aggregate_root_device(ssa_ctx *ctx, const uint8_t *d_tops, size_t n_tops, size_t n, size_t block_lanes,
+                                         uint8_t *d_root_out) {
+    if (!ctx || !d_tops || !d_root_out || !aligned8(d_tops) || !aligned8(d_root_out) || n == 0 || n > SSA_MAX_BATCH ||
+        n_tops == 0 || n_tops > n)
+        return SSA_ERR_ARG;
+    if (block_lanes && (!is_pow2(block_lanes) || n_tops != (n + block_lanes - 1) / block_lanes)) return SSA_ERR_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    return ags_root(ctx, (const u64 *)d_tops, n_tops, n, (u64 *)d_root_out);
+}
+
+extern "C" int ssa_aggregate_shard_fold_device(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks,
+                                               const uint8_t *d_pk_inf, size_t n_s, size_t lane0, const uint8_t *d_root,
+                                               uint8_t *d_e_out, uint8_t *d_rs_out, uint8_t *d_status_out,
+                                               uint64_t *d_n_fail_out) {
+    if (!ctx || !d_root || !aligned8(d_root) || !d_e_out || n_s > SSA_MAX_BATCH || lane0 > SSA_MAX_BATCH - n_s ||
+        (n_s && (!d_sigs || !d_rs_out || (d_status_out && !d_pks))))
+        return SSA_ERR_ARG;
+    unsigned long long *d_fail;
+    if (int rc = reset_fail_counter(ctx, d_n_fail_out, &d_fail)) return rc;
+    return ags_fold(ctx, {d_sigs, d_pks, d_pk_inf, {}}, n_s, lane0, (const u64 *)d_root, d_e_out, d_rs_out, d_status_out,
+                    d_fail);
+}
+
+extern "C" int ssa_verify_aggregate_shard_device(ssa_ctx *ctx, const uint8_t *d_rs49, const uint8_t *d_pks,
+                                                 const uint8_t *d_pk_inf, const uint8_t *d_msgs, const uint64_t *d_msg_off,
+                                                 size_t msg_stride, size_t msg_len, const uint64_t *d_h, size_t n_s,
+                                                 size_t lane0, const uint8_t *d_root, uint64_t *d_record_out) {
+    const MsgView mv{d_msgs, d_msg_off, msg_stride, msg_len};
+    if (!ctx || !d_root || !aligned8(d_root) || !d_record_out || n_s > SSA_MAX_BATCH || lane0 > SSA_MAX_BATCH - n_s ||
+        (n_s && (!d_rs49 || !d_pks)))
+        return SSA_ERR_ARG;
+    if (int rc = check_msgs(mv, n_s)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    return ags_record(ctx, d_rs49, {nullptr, d_pks, d_pk_inf, mv}, (const u64 *)d_h, n_s, lane0, (const u64 *)d_root,
+                      (u64 *)d_record_out);
+}
+
+extern "C" int ssa_aggregate_combine_device(ssa_ctx *ctx, const uint8_t *d_partials32, size_t k, uint8_t *d_e_agg_out) {
+    if (!ctx || !d_partials32 || !aligned8(d_partials32) || !d_e_agg_out || k == 0 || k > 4096) return SSA_ERR_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    return timed_launch(ctx, "ag_k_fold", [&] {
+        hipLaunchKernelGGL(ag_k_fold_finish, dim3(1), dim3(256), 0, ctx->stream, (const u64 *)d_partials32, (u32)k, d_e_agg_out);
+    });
+}
+
+extern "C" int ssa_verify_aggregate_combine_device(ssa_ctx *ctx, const uint64_t *d_records24, size_t k,
+                                                   const uint8_t *d_e_agg, size_t n, uint32_t *d_verdict_out) {
+    if (!ctx || !d_e_agg || !d_verdict_out || n > SSA_MAX_BATCH || (n && (!d_records24 || k == 0 || k > 4096)))
+        return SSA_ERR_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (ctx->ag_misc.reserve(AG_MISC_BYTES)) return SSA_ERR_HIP;
+    if (n)
+        if (int rc = ssa_internal_msm_sum_records(ctx, d_records24, k, true, (uint64_t *)ag_misc(ctx, AG_REC))) return rc;
+    return timed_launch(ctx, "ag_k_finish", [&] {
+        hipLaunchKernelGGL(ag_k_finish_scalar, dim3(1), dim3(64), 0, ctx->stream, (const u64 *)ag_misc(ctx, AG_REC), d_e_agg,
+                           n == 0 ? 1u : 0u, (const u64 *)ctx->d_gtab, d_verdict_out);
+    });
+}
+
+// ---- one context, any n <= SSA_MAX_BATCH: the slices are the shards
+// tops of all n lanes into ctx->ags_tops and the root into ctx->agm_roots; d_h_out as ags_tops
+static int ags_root_of(ssa_ctx *ctx, const u8 *d_lanes, u32 stride, const u8 *d_pks, const MsgView &mv, size_t n,
+                       u64 *d_h_out) {
+    const size_t B = ags_block(ctx), n_tops = (n + B - 1) / B;
+    if (ctx->ags_tops.reserve(n_tops * 32) || ctx->agm_roots.reserve(32)) return SSA_ERR_HIP;
+    if (int rc = ags_tops(ctx, d_lanes, stride, d_pks, mv, n, B, (u64 *)ctx->ags_tops.p, d_h_out)) return rc;
+    return ags_root(ctx, (const u64 *)ctx->ags_tops.p, n_tops, n, (u64 *)ctx->agm_roots.p);
+}
+
+// Synchronises the stream, as ssa_aggregate_many_device does.
+extern "C" int ssa_aggregate_many_sliced_device(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks,
+                                                const uint8_t *d_pk_inf, const uint8_t *d_msgs, const uint64_t *d_msg_off,
+                                                size_t msg_stride, size_t msg_len, size_t n, uint32_t flags,
+                                                uint8_t *d_agg_out, uint8_t *d_status_out, uint64_t *d_n_fail_out) {
+    const DevBatch b{d_sigs, d_pks, d_pk_inf, {d_msgs, d_msg_off, msg_stride, msg_len}};
+    if (!ctx || !d_agg_out || (flags & ~SSA_AGG_CHECK) || (n && (!d_sigs || !d_pks))) return SSA_ERR_ARG;
+    if (int rc = agg_check_args(ctx, b.msgs, n, true)) return rc;
+    unsigned long long *d_fail;
+    if (int rc = reset_fail_counter(ctx, d_n_fail_out, &d_fail)) return rc;
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(d_agg_out, 0, 32, ctx->stream));
+        return SSA_OK;
+    }
+    if ((!d_status_out && ctx->ag_status.reserve(n + 16)) || ctx->ag_misc.reserve(AG_MISC_BYTES)) return SSA_ERR_HIP;
+    u8 *d_status = d_status_out ? d_status_out : (u8 *)ctx->ag_status.p;
+    const bool screened = (flags & SSA_AGG_CHECK) != 0;
+    if (screened)
+        if (int rc = ssa_verify_batch_screened_device(ctx, d_sigs, d_pks, d_pk_inf, d_msgs, d_msg_off, msg_stride, msg_len, n,
+                                                      nullptr, 0, d_status, (uint64_t *)d_fail))
+            return rc;
+    if (int rc = ags_root_of(ctx, d_sigs, 81, d_pks, b.msgs, n, nullptr)) return rc;
+    if (int rc = ags_fold(ctx, b, n, 0, (const u64 *)ctx->agm_roots.p, ag_misc(ctx, AG_E), d_agg_out,
+                          screened ? (u8 *)nullptr : d_status, d_fail))
+        return rc;
+    int st;
+    if (int rc = ag_refusal(ctx, n, screened, d_status, d_fail, d_agg_out, &st)) return rc;
+    if (st) return st;
+    HIP_TRY(hipMemcpyAsync(d_agg_out + 49 * n, ag_misc(ctx, AG_E), 32, hipMemcpyDeviceToDevice, ctx->stream));
+    return SSA_OK;
+}
+
+extern "C" int ssa_aggregate_many_sliced(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_inf,
+                                         const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len,
+                                         size_t n, uint32_t flags, uint8_t *agg_out, uint8_t *status_out,
+                                         uint64_t *n_fail_out) {
+    return aggregate_many_host(ctx, sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len, n, flags, agg_out, status_out,
+                               n_fail_out, true);
+}
+
+// Only enqueues.  The challenge scalars of all n lanes stay in ctx->ws_h between the two walks (32 bytes per lane);
+// everything else is one piece's workspace.
+extern "C" int ssa_verify_aggregate_sliced_device(ssa_ctx *ctx, const uint8_t *d_agg, const uint8_t *d_pks,
+                                                  const uint8_t *d_pk_inf, const uint8_t *d_msgs, const uint64_t *d_msg_off,
+                                                  size_t msg_stride, size_t msg_len, size_t n, uint32_t *d_verdict_out) {
+    const MsgView mv{d_msgs, d_msg_off, msg_stride, msg_len};
+    if (!ctx || !d_agg || !d_verdict_out || (n && !d_pks)) return SSA_ERR_ARG;
+    if (int rc = agg_check_args(ctx, mv, n, true)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (n) {
+        if (ctx->ag_misc.reserve(AG_MISC_BYTES) || ctx->ws_h.reserve(n * 32)) return SSA_ERR_HIP;
+        if (int rc = ags_root_of(ctx, d_agg, 49, d_pks, mv, n, (u64 *)ctx->ws_h.p)) return rc;
+        if (int rc = ags_record(ctx, d_agg, {nullptr, d_pks, d_pk_inf, mv}, (const u64 *)ctx->ws_h.p, n, 0,
+                                (const u64 *)ctx->agm_roots.p, (u64 *)ag_misc(ctx, AG_REC), n <= ags_piece(ctx, ags_block(ctx))))
+            return rc;
+    }
+    return timed_launch(ctx, "ag_k_finish", [&] {
+        hipLaunchKernelGGL(ag_k_finish, dim3(1), dim3(64), 0, ctx->stream, (const u64 *)ag_misc(ctx, AG_REC), d_agg,
+                           (const u32 *)nullptr, n, 0u, (const u64 *)ctx->d_gtab, d_verdict_out);
+    });
+}
+
+extern "C" int ssa_verify_aggregate_sliced(ssa_ctx *ctx, const uint8_t *agg, const uint8_t *pks, const uint8_t *pk_inf,
+                                           const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len,
+                                           size_t n) {
+    return verify_aggregate_host(ctx, agg, pks, pk_inf, msgs, msg_off, msg_stride, msg_len, n, true);
+}
+
+// ---- several devices in one process: every device takes a contiguous run of whole blocks, block counts differ by at
+// most one.  One host thread per device and walk; two joins: the tops come in (32 bytes per block), the root goes out.
+// The root, the sum of the partial scalars and the combination run on device 0.
+struct AgsShard {
+    size_t lo = 0, cnt = 0;            // lanes [lo, lo + cnt) of the call
+    DevBatch dev{};                    // the shard's inputs on its device, staged by the first walk
+    std::vector<uint64_t> off;         // its rebased offset table
+    int rc = 0;
+};
+static std::vector<AgsShard> ags_split(size_t n, size_t B, size_t world) {
+    std::vector<AgsShard> sh(world);
+    const size_t blocks = (n + B - 1) / B, base = blocks / world, rem = blocks % world;
+    for (size_t r = 0; r < world; r++) {
+        const size_t b0 = r * base + std::min(r, rem), nb = base + (r < rem ? 1 : 0);
+        sh[r].lo = std::min(b0 * B, n);
+        sh[r].cnt = std::min((b0 + nb) * B, n) - sh[r].lo;
+    }
+    return sh;
+}
+// fn(r) for every shard that has lanes, each on a thread of its own; the first error
+template <class F>
+static int ags_each_device(std::vector<AgsShard> &sh, F &&fn) {
+    std::vector<std::thread> threads;
+    for (size_t r = 0; r < sh.size(); r++)
+        if (sh[r].cnt) threads.emplace_back([&, r] { sh[r].rc = fn(r); });
+    for (auto &t : threads) t.join();
+    for (const AgsShard &s : sh)
+        if (s.rc) return s.rc;
+    return 0;
+}
+// the first walk of both calls: shard r's lanes (lanes: signatures or R's of the whole call at `stride`), keys, flags
+// and messages staged on its device, its tops into tops (host, 4 words per block of the call)
+static int ags_multi_tops(ssa_multi *m, std::vector<AgsShard> &sh, const HostBatch &b, const uint8_t *lanes, u32 stride,
+                          size_t B, bool with_h, std::vector<uint64_t> &tops) {
+    return ags_each_device(sh, [&](size_t r) {
+        ssa_ctx *c = m->ctxs[r];
+        AgsShard &s = sh[r];
+        const HostBatch hb = b.slice(s.lo, s.cnt, s.off);
+        HostCall hc(c);
+        s.dev.sigs = hc.in(c->st_sigs, lanes + (size_t)stride * s.lo, s.cnt * stride);
+        s.dev.pks = hc.in(c->st_pks, hb.pks, s.cnt * 96);
+        s.dev.pk_inf = hb.pk_inf ? hc.in(c->st_inf, hb.pk_inf, s.cnt) : nullptr;
+        s.dev.msgs = hc.msgs(hb.msgs, hb.msg_off, hb.msg_stride, hb.msg_len, s.cnt);
+        const size_t n_tops = (s.cnt + B - 1) / B;
+        u64 *d_tops = (u64 *)hc.out(c->ags_tops, tops.data() + 4 * (s.lo / B), n_tops * 32);
+        if (with_h && hc.ok() && c->ws_h.reserve(s.cnt * 32)) hc.rc = SSA_ERR_HIP;
+        return hc.finish([&] {
+            return ags_tops(c, s.dev.sigs, stride, s.dev.pks, s.dev.msgs, s.cnt, B, d_tops, with_h ? (u64 *)c->ws_h.p : nullptr);
+        });
+    });
+}
+// the first join: all tops to device 0, the root back to the host
+static int ags_multi_root(ssa_ctx *c0, const std::vector<uint64_t> &tops, size_t n, uint64_t root[4]) {
+    HostCall hc(c0);
+    const u64 *d_tops = hc.in<u64>(c0->ags_tops, tops.data(), tops.size() * sizeof(uint64_t));
+    u64 *d_root = (u64 *)hc.out(c0->agm_roots, root, 32);
+    return hc.finish([&] { return ags_root(c0, d_tops, tops.size() / 4, n, d_root); });
+}
+
+extern "C" int ssa_multi_aggregate_many(ssa_multi *m, const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_inf,
+                                        const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len,
+                                        size_t n, uint32_t flags, uint8_t *agg_out, uint8_t *status_out,
+                                        uint64_t *n_fail_out) {
+    if (!m || m->ctxs.empty() || !agg_out || (flags & ~SSA_AGG_CHECK) || (n && (!sigs || !pks))) return SSA_ERR_ARG;
+    if (int rc = check_msgs({msgs, msg_off, msg_stride, msg_len}, n)) return rc;
+    if (int rc = check_host_offsets(msg_off, n)) return rc;
+    if (n_fail_out) *n_fail_out = 0;
+    if (n == 0) {
+        std::memset(agg_out, 0, 32);
+        return SSA_OK;
+    }
+    ssa_ctx *c0 = m->ctxs[0];
+    const size_t world = m->ctxs.size(), B = ags_block(c0);
+    const HostBatch b{sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len};
+    const bool screened = (flags & SSA_AGG_CHECK) != 0;
+    std::vector<AgsShard> sh = ags_split(n, B, world);
+    std::vector<uint8_t> own_status(status_out ? 0 : n);
+    uint8_t *status = status_out ? status_out : own_status.data();
+    std::vector<uint64_t> fails(world, 0), tops(4 * ((n + B - 1) / B), 0), parts(4 * world, 0);
+    if (screened)      // the statuses of ssa_verify_batch_screened, every device its own lanes (before anything is staged)
+        if (int rc = ags_each_device(sh, [&](size_t r) {
+                std::vector<uint64_t> off;
+                const HostBatch hb = b.slice(sh[r].lo, sh[r].cnt, off);
+                return ssa_verify_batch_screened(m->ctxs[r], hb.sigs, hb.pks, hb.pk_inf, hb.msgs, hb.msg_off, msg_stride,
+                                                 msg_len, sh[r].cnt, nullptr, status + sh[r].lo, &fails[r]);
+            }))
+            return rc;
+    if (int rc = ags_multi_tops(m, sh, b, sigs, 81, B, false, tops)) return rc;
+    uint64_t root[4];
+    if (int rc = ags_multi_root(c0, tops, n, root)) return rc;
+    // the second walk: the root to every device, its partial scalar, R's, statuses and count back
+    if (int rc = ags_each_device(sh, [&](size_t r) {
+            ssa_ctx *c = m->ctxs[r];
+            const AgsShard &s = sh[r];
+            HostCall hc(c);
+            const u64 *d_root = hc.in<u64>(c->agm_roots, root, 32);
+            u8 *d_e = hc.out(c->ag_misc, &parts[4 * r], 32, AG_MISC_BYTES);
+            u8 *d_rs = hc.out(c->st_aux, agg_out + 49 * s.lo, 49 * s.cnt, 16);
+            u8 *d_status = screened ? nullptr : hc.out(c->st_status, status + s.lo, s.cnt, 16);
+            unsigned long long *d_fail = (unsigned long long *)c->ws_fail.p;
+            if (!screened) hc.copy_back(&fails[r], d_fail, sizeof(uint64_t));
+            return hc.finish([&] {
+                HIP_TRY(hipMemsetAsync(d_fail, 0, sizeof(unsigned long long), c->stream));
+                return ags_fold(c, s.dev, s.cnt, s.lo, d_root, d_e, d_rs, d_status, d_fail);
+            });
+        }))
+        return rc;
+    uint64_t nf = 0;
+    for (uint64_t f : fails) nf += f;
+    if (n_fail_out) *n_fail_out = nf;
+    if (nf) {          // refused: no aggregate, the smallest nonzero status
+        std::memset(agg_out, 0, SSA_AGGREGATE_LENGTH(n));
+        int st = SSA_MALFORMED;
+        if (screened)
+            for (size_t i = 0; i < n; i++)
+                if (status[i] && (int)status[i] < st) st = status[i];
+        return st;
+    }
+    HostCall hc(c0);
+    const u8 *d_parts = hc.in(c0->st_aux, parts.data(), 32 * world);
+    u8 *d_e = hc.out(c0->ag_misc, agg_out + 49 * n, 32, AG_MISC_BYTES);
+    return hc.finish([&] { return ssa_aggregate_combine_device(c0, d_parts, world, d_e); });
+}
+
+extern "C" int ssa_multi_verify_aggregate(ssa_multi *m, const uint8_t *agg, const uint8_t *pks, const uint8_t *pk_inf,
+                                          const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len,
+                                          size_t n) {
+    if (!m || m->ctxs.empty() || !agg || (n && !pks)) return SSA_ERR_ARG;
+    if (int rc = check_msgs({msgs, msg_off, msg_stride, msg_len}, n)) return rc;
+    if (int rc = check_host_offsets(msg_off, n)) return rc;
+    ssa_ctx *c0 = m->ctxs[0];
+    if (n == 0) return ssa_verify_aggregate(c0, agg, pks, pk_inf, msgs, msg_off, msg_stride, msg_len, 0);
+    const size_t world = m->ctxs.size(), B = ags_block(c0);
+    const HostBatch b{nullptr, pks, pk_inf, msgs, msg_off, msg_stride, msg_len};
+    std::vector<AgsShard> sh = ags_split(n, B, world);
+    std::vector<uint64_t> tops(4 * ((n + B - 1) / B), 0), recs(SSA_MSM_PARTIAL_WORDS * world, 0);
+    for (size_t r = 0; r < world; r++) recs[SSA_MSM_PARTIAL_WORDS * r + 23] = SSA_MSM_RECORD_MAGIC;   // a device without lanes: the empty shard's record
+    if (int rc = ags_multi_tops(m, sh, b, agg, 49, B, true, tops)) return rc;
+    uint64_t root[4];
+    if (int rc = ags_multi_root(c0, tops, n, root)) return rc;
+    if (int rc = ags_each_device(sh, [&](size_t r) {
+            ssa_ctx *c = m->ctxs[r];
+            const AgsShard &s = sh[r];
+            HostCall hc(c);
+            const u64 *d_root = hc.in<u64>(c->agm_roots, root, 32);
+            u64 *d_rec = (u64 *)hc.out(c->ag_misc, &recs[SSA_MSM_PARTIAL_WORDS * r], SSA_MSM_PARTIAL_WORDS * sizeof(u64),
+                                       AG_MISC_BYTES);
+            return hc.finish([&] { return ags_record(c, s.dev.sigs, s.dev, (const u64 *)c->ws_h.p, s.cnt, s.lo, d_root, d_rec); });
+        }))
+        return rc;
+    HostCall hc(c0);
+    const u64 *d_recs = hc.in<u64>(c0->st_aux, recs.data(), recs.size() * sizeof(uint64_t));
+    const u8 *d_e = hc.in(c0->st_aux2, agg + 49 * n, 32);
+    uint32_t v = SSA_MALFORMED, *d_verdict = (uint32_t *)((char *)c0->ws_fail.p + 32);
+    hc.copy_back(&v, d_verdict, sizeof v);
+    const int rc = hc.finish([&] { return ssa_verify_aggregate_combine_device(c0, d_recs, world, d_e, n, d_verdict); });
+    return rc ? rc : (int)v;
+}
+
+// tests: the coefficients of n_s lanes whose first stands at lane0, from a root in host memory -> n_s x 16 bytes
+extern "C" int ssa_debug_aggregate_shard_coeffs(ssa_ctx *ctx, const uint8_t root[32], size_t n_s, size_t lane0,
+                                                uint8_t *coeffs16_out) {
+    if (!ctx || !root || n_s > SSA_MAX_BATCH || lane0 > SSA_MAX_BATCH - n_s || (n_s && !coeffs16_out)) return SSA_ERR_ARG;
+    if (n_s == 0) return 0;
+    HostCall hc(ctx);
+    const u64 *d_root = hc.in<u64>(ctx->agm_roots, root, 32);
+    (void)hc.out(ctx->ag_coeffs, coeffs16_out, n_s * 16);
+    return hc.finish([&] { return ags_coeffs(ctx, d_root, n_s, lane0); });
 }
 
 // ------------------------------------------------------------------ many aggregates in one call

@@ -116,6 +116,8 @@ struct CtxKnobs {
     // each: 2.1 GB at 2^20), the MSM-form pipeline over slices of at most msm_slice signatures whose records are
     // combined like the shards of a multi-GPU batch.  SSA_LANE_SLICE / SSA_MSM_SLICE override (tests force small ones).
     size_t lane_slice = (size_t)1 << 20, msm_slice = (size_t)1 << 23;
+    size_t agg_block = 0;         // lanes per block of the sliced and sharded half-aggregation; 0: the
+                                  // largest power of two not above msm_slice.  SSA_AGG_BLOCK (tests); rounded down to a power of two
     bool msm_overlap = true;      // the h-independent half of msm_k_prepare runs under ssa_k_hash (SSA_MSM_OVERLAP=0: off)
     unsigned msm_tree_group = 16; // chunk sums added per cooperating wave and tree level (SSA_MSM_TREE_GROUP: 2..64)
     unsigned verify_block = 256;  // threads per block of ssa_k_verify (SSA_VERIFY_BLOCK overrides: 64/128/256)
@@ -193,6 +195,9 @@ struct CtxKnobs {
     /* aggregates through a key cache (ssa_aggcache.hpp): per lane of the CALL (not of a slice) \
        its key's status byte and, for wire keys, its 96 key bytes and pk_inf boolean; and the call's two counters */ \
     X(agc_kst) X(agc_pks) X(agc_inf) X(agc_cnt) \
+    /* sliced and sharded half-aggregation: one 32-byte top per block of lanes, and one partial \
+       scalar and one MSM record per slice of a shard */ \
+    X(ags_tops) X(ags_parts) X(ags_recs) \
     /* the end game of ssa_k_verify, per tail group: finished pieces; parked accumulators + status (152 B per lane) */ \
     X(tail_done) X(tail_park)
 
@@ -785,6 +790,12 @@ int ssa_internal_hash_scalars_digests(ssa_ctx *ctx, const DevBatch &b, size_t n,
 // d_h: the slice's challenge scalars if they exist (batches of at most ctx->knobs.msm_small_max lanes hash for themselves)
 int ssa_internal_msm_record(ssa_ctx *ctx, const DevBatch &b, size_t n, const uint8_t *d_coeffs, uint32_t coeff_bytes,
                             const uint64_t *d_h, uint64_t *d_record_out);
+
+// defined in ssa_msm.hip, for the sharded half-aggregation (ssa_api.hip): k (1..4096) records added
+// up into ONE record by one wave on ctx->stream -- points, scalars mod q, malformed words OR-ed.  checked: the records
+// come from outside the call and are validated first (magic, malformed word, canonical limbs and scalar, point on the
+// curve); one that fails makes the sum the malformed record.
+int ssa_internal_msm_sum_records(ssa_ctx *ctx, const uint64_t *d_records, size_t k, bool checked, uint64_t *d_record_out);
 
 // defined in ssa_msm.hip, for ssa_verify_aggregates_many (ssa_api.hip): the left-hand sides of one
 // group of aggregates, by msm_k_small and one record sum per aggregate, or by the screened MSM over padded segments

@@ -1162,11 +1162,7 @@ __global__ void msm_k_unpack_parts(const u64 *__restrict__ parts, u32 k, u64 *__
 // One lane per record: the scalar is canonical (< q) and the point is the identity (Z = 0) or satisfies the Jacobian
 // curve equation Y^2 = X^3 + X Z^4 + (u + 395) Z^6.  Records cross process boundaries (all-gather): a corrupted or
 // foreign one gives SSA_MALFORMED, never an arbitrary verdict.  k <= 4096: the cost is one short launch.
-__global__ void __launch_bounds__(64)
-msm_k_check_parts(const u64 *__restrict__ parts, u32 k, u32 *__restrict__ malformed) {
-    const u32 j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= k) return;
-    const u64 *r = parts + 24u * (size_t)j;
+SSA_DEV bool msm_record_valid(const u64 *__restrict__ r) {
     bool ok = true;
     fp6 X, Y, Z;
 #pragma unroll
@@ -1188,7 +1184,32 @@ msm_k_check_parts(const u64 *__restrict__ parts, u32 k, u32 *__restrict__ malfor
         const fp6 rhs = f6_add(f6_add(f6_mul(f6_sqr(X), X), f6_mul(X, z4)), f6_mul(b, z6));
         ok = f6_eq(f6_sqr(Y), rhs);
     }
-    if (!ok) atomicOr(malformed, 1u);
+    return ok;
+}
+__global__ void __launch_bounds__(64)
+msm_k_check_parts(const u64 *__restrict__ parts, u32 k, u32 *__restrict__ malformed) {
+    const u32 j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= k) return;
+    if (!msm_record_valid(parts + 24u * (size_t)j)) atomicOr(malformed, 1u);
+}
+
+// ONE wave: k records that crossed a process or device boundary -> their sum as one record (the shards of a
+// half-aggregate, DESIGN.md section 25: the sum is compared exactly by ag_k_finish, not x-only by msm_k_finish).  Fails
+// closed as msm_k_unpack_parts and msm_k_check_parts do together: a record without the magic word, with a set malformed
+// word, a non-canonical limb or scalar or a point off the curve leaves the malformed record.
+__global__ void __launch_bounds__(64)
+msm_k_sum_records_checked(const u64 *__restrict__ in, u32 k, u64 *__restrict__ rec) {
+    __shared__ CoopLds L;
+    bool ok = true;
+    for (u32 j = threadIdx.x; j < k; j += 64u) {
+        const u64 *r = in + 24u * (size_t)j;
+        ok = ok && r[22] == 0 && r[23] == SSA_MSM_RECORD_MAGIC && msm_record_valid(r);
+    }
+    if (__ballot(!ok) != 0ull) {                      // (wave-uniform)
+        msm_record_flag(rec, true);
+        return;
+    }
+    sum_records_range(L, in, 0u, k, rec);
 }
 }  // namespace ssa
 
@@ -1456,6 +1477,18 @@ int ssa_internal_msm_record(ssa_ctx *ctx, const DevBatch &b, size_t n, const uin
                             const uint64_t *d_h, uint64_t *d_record_out) {
     if (!d_coeffs || !d_record_out || n > ctx->knobs.msm_slice) return SSA_ERR_ARG;
     return msm_run_one(ctx, b, n, d_coeffs, coeff_bytes, nullptr, (u64 *)d_record_out, (const u64 *)d_h);
+}
+
+int ssa_internal_msm_sum_records(ssa_ctx *ctx, const uint64_t *d_records, size_t k, bool checked, uint64_t *d_record_out) {
+    if (!d_records || !d_record_out || k == 0 || k > 4096) return SSA_ERR_ARG;
+    return timed_launch(ctx, "msm_k_sum_records", [&] {
+        if (checked)
+            hipLaunchKernelGGL(msm_k_sum_records_checked, dim3(1), dim3(64), 0, ctx->stream, (const u64 *)d_records, (u32)k,
+                               (u64 *)d_record_out);
+        else
+            hipLaunchKernelGGL(msm_k_sum_records, dim3(1), dim3(64), 0, ctx->stream, (const u64 *)d_records, (u32)k, (u32)k,
+                               (u64 *)d_record_out);
+    });
 }
 
 // The left-hand sides of ssa_verify_aggregates_many (ssa_api.hip), one group of aggregates each.

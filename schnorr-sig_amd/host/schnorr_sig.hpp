@@ -634,17 +634,26 @@ struct AggregateSignature {
     static std::optional<AggregateSignature> aggregate(Context &cx, const std::vector<Signature> &signatures,
                                                        const std::vector<PublicKey> &public_keys,
                                                        const std::vector<std::pair<const uint8_t *, size_t>> &messages,
-                                                       bool check = true) {
+                                                       bool check = true, bool sliced = false) {
         const PackedTriples t = pack_triples(signatures, public_keys, messages);
         const size_t n = signatures.size();
         AggregateSignature a;
         a.bytes.assign(SSA_AGGREGATE_LENGTH(n), 0);
-        const int rc = ssa_aggregate_many(cx.get(), t.sigs.data(), t.pks.data(), t.inf.data(), t.flat.data(), t.off.data(), 0,
-                                          0, n, check ? SSA_AGG_CHECK : 0u, a.bytes.data(), nullptr, nullptr);
+        const int rc = (sliced ? ssa_aggregate_many_sliced : ssa_aggregate_many)(
+            cx.get(), t.sigs.data(), t.pks.data(), t.inf.data(), t.flat.data(), t.off.data(), 0, 0, n,
+            check ? SSA_AGG_CHECK : 0u, a.bytes.data(), nullptr, nullptr);
         if (rc < 0) throw std::runtime_error(std::string("ssa_aggregate_many: ") + ssa_strerror(rc));
         if (rc == SSA_MALFORMED) throw Panic("undecodable signature in batch (the reference panics here)");
         if (rc != SSA_OK) return std::nullopt;
         return a;
+    }
+    // The same aggregate, byte for byte, for any number of signatures up to SSA_MAX_BATCH: slice after slice of the
+    // context in bounded workspaces (ssa_aggregate_many_sliced)
+    static std::optional<AggregateSignature> aggregate_sliced(Context &cx, const std::vector<Signature> &signatures,
+                                                              const std::vector<PublicKey> &public_keys,
+                                                              const std::vector<std::pair<const uint8_t *, size_t>> &messages,
+                                                              bool check = true) {
+        return aggregate(cx, signatures, public_keys, messages, check, true);
     }
     // Filtering half-aggregation: the aggregate of exactly the triples that verify under
     // verify_batch semantics, and their indices in ascending order.  A triple that does not verify is dropped, not
@@ -679,12 +688,17 @@ struct AggregateSignature {
                     const std::vector<std::pair<const uint8_t *, size_t>> &messages,
                     std::vector<uint8_t> *kept_keys49 = nullptr, uint64_t *stats_out = nullptr);
     Result verify(Context &cx, const std::vector<PublicKey> &public_keys,
-                  const std::vector<std::pair<const uint8_t *, size_t>> &messages) const {
+                  const std::vector<std::pair<const uint8_t *, size_t>> &messages, bool sliced = false) const {
         if (public_keys.size() != size() || messages.size() != size())
             throw Panic("We should have the same number of messages than public keys");
         const PackedTriples t = pack_triples(std::vector<Signature>(size()), public_keys, messages);
-        return status_to_result(ssa_verify_aggregate(cx.get(), bytes.data(), t.pks.data(), t.inf.data(), t.flat.data(),
-                                                     t.off.data(), 0, 0, size()));
+        return status_to_result((sliced ? ssa_verify_aggregate_sliced : ssa_verify_aggregate)(
+            cx.get(), bytes.data(), t.pks.data(), t.inf.data(), t.flat.data(), t.off.data(), 0, 0, size()));
+    }
+    // the same verdict for any size up to SSA_MAX_BATCH (ssa_verify_aggregate_sliced)
+    Result verify_sliced(Context &cx, const std::vector<PublicKey> &public_keys,
+                         const std::vector<std::pair<const uint8_t *, size_t>> &messages) const {
+        return verify(cx, public_keys, messages, true);
     }
     // Many aggregates in one call: the keys and messages of all their lanes, in order.  One status
     // per aggregate -- SSA_OK, SSA_INVALID_SIGNATURE or SSA_MALFORMED (where verify() panics) --, each the value verify()

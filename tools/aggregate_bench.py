@@ -57,7 +57,13 @@ alternating in the same way, every timed output checked (kept count and list, ag
   baseline_guarded           the guarded route there was before, through the same library: ssa_verify_many_cached_device
                              (warm affine cache, subgroup check and flag byte), then ssa_aggregate_many_device on arrays
                              filtered beforehand.  The HOST time a caller needs to filter four arrays and upload them again
-                             is NOT counted."""
+                             is NOT counted.
+
+--sharded measures the sliced calls against the single calls of --baseline-lib at --n signatures,
+device buffers, legs alternating: verify_sliced / verify_baseline, aggregate_sliced / aggregate_baseline, and this tree's own
+single calls.  Up to one MSM slice the routes differ in the tree alone (flat ag_k_level launches against ag_k_tree); above
+it (n a multiple of 2^20, 2^20 distinct lanes repeated) only the sliced legs run.  --multi adds MultiEngine([0, 0]) from
+host buffers beside this tree's host forms: two contexts on ONE device, which says nothing about scaling."""
 import argparse
 import hashlib
 import json
@@ -736,6 +742,132 @@ def cached_main(a):
     return 0 if res["mismatches"] == 0 else 1
 
 
+SHARDED_KERNELS = KERNELS[:3] + ("ag_k_level",) + KERNELS[3:] + ("ag_k_expand", "msm_k_sum_records")
+
+
+def sharded_main(a):
+    """--sharded: the sliced calls of DESIGN.md section 25 against the single calls of --baseline-lib (a build of the parent
+    commit; without it, this tree's own library), device buffers, the legs alternating in one process.  Up to one MSM slice
+    the two routes differ in the tree alone: flat ag_k_level launches against ag_k_tree.  Above it only this tree's legs
+    run (the single calls refuse the size); the batch is then 2^20 distinct lanes repeated.  With --multi also
+    MultiEngine([0, 0]) from host buffers against this tree's host forms: TWO CONTEXTS ON ONE DEVICE, not scaling."""
+    import torch
+    import schnorr_sig_amd as ssa
+    dev = torch.device("cuda", 0)
+    eng = ssa.Engine(0)
+    base_path = a.baseline_lib or ssa.LIB_PATH
+    n, n0 = a.n, min(a.n, 1 << 20)
+    if n % n0:
+        raise SystemExit("--sharded: n above 2^20 must be a multiple of it")
+    with_base = n <= 1 << 23
+    base_a, base_v = (BaselineAggregate(base_path), BaselineLoop(base_path)) if with_base else (None, None)
+    rng = np.random.default_rng(a.seed)
+    msgs = rng.integers(0, 256, (n0, 80), dtype=np.uint8)
+    pks, sigs = eng.keygen_sign_many(_scalars(rng, n0), _scalars(rng, n0), msgs)
+    t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev).repeat(n // n0, 1)   # noqa: E731
+    d_sigs, d_pks, d_msgs = t(sigs), t(pks), t(msgs)
+    d_agg = torch.zeros(49 * n + 32, dtype=torch.uint8, device=dev)
+    d_agg0 = torch.zeros(49 * n + 32, dtype=torch.uint8, device=dev)
+    d_verdict = torch.full((1,), 255, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+    sha = lambda path: hashlib.sha256(open(path, "rb").read()).hexdigest()[:16]   # noqa: E731
+    res = {"metric": "aggregate_sharded", "n": n, "distinct_lanes": n0, "msg_len": 80, "rounds": a.rounds, "warmup": a.warmup,
+           "library_sha256": sha(ssa.LIB_PATH), "baseline_sha256": sha(base_path), "baseline_is_this_tree": not a.baseline_lib,
+           "device": torch.cuda.get_device_name(0), "date": time.strftime("%Y-%m-%d"), "mismatches": 0}
+    ptrs = (d_sigs.data_ptr(), d_pks.data_ptr(), d_msgs.data_ptr())
+
+    def wall(fn, sync):
+        sync()
+        t0 = time.perf_counter()
+        fn()
+        sync()
+        return (time.perf_counter() - t0) * 1e3
+
+    if eng.aggregate_sliced_device(*ptrs, n, 80, d_agg0.data_ptr()) != 0:
+        res["mismatches"] += 1
+    eng.sync()
+    verify_ptrs = (d_agg0.data_ptr(), d_pks.data_ptr(), d_msgs.data_ptr())
+    legs = {"verify_sliced": (lambda: eng.verify_aggregate_sliced_device(*verify_ptrs, n, 80, d_verdict.data_ptr()), eng.sync),
+            "aggregate_sliced": (lambda: eng.aggregate_sliced_device(*ptrs, n, 80, d_agg.data_ptr()), eng.sync)}
+    if with_base:
+        legs.update({
+            "verify_baseline": (lambda: base_v.verify(*verify_ptrs, n, d_verdict.data_ptr()), base_v.sync),
+            "aggregate_baseline": (lambda: base_a.aggregate(*ptrs, n, d_agg.data_ptr(), False), base_a.sync),
+            "verify_single": (lambda: eng.verify_aggregate_device(*verify_ptrs, n, 80, d_verdict.data_ptr()), eng.sync),
+            "aggregate_single": (lambda: eng.aggregate_device(*ptrs, n, 80, d_agg.data_ptr()), eng.sync)})
+    times = {leg: [] for leg in legs}
+    for rnd in range(a.warmup + a.rounds):
+        for leg, (fn, sync) in legs.items():
+            d_verdict.fill_(255)
+            d_agg.fill_(0xEE)
+            torch.cuda.synchronize()
+            ms = wall(fn, sync)
+            good = int(d_verdict.item()) == 0 if leg.startswith("verify") else bool((d_agg == d_agg0).all())
+            res["mismatches"] += 0 if good else 1
+            if rnd >= a.warmup:
+                times[leg].append(ms)
+    med = res["ms_median"] = {leg: round(float(np.median(v)), 3) for leg, v in times.items()}
+    res["ms_all"] = {leg: [round(x, 3) for x in v] for leg, v in times.items()}
+    if with_base:
+        res["ratio"] = {"verify_sliced/verify_baseline": round(med["verify_sliced"] / med["verify_baseline"], 4),
+                        "aggregate_sliced/aggregate_baseline": round(med["aggregate_sliced"] / med["aggregate_baseline"], 4)}
+    kern = {}
+    for leg in ("verify_sliced", "aggregate_sliced") + (("verify_single",) if with_base else ()):
+        eng.sync()
+        eng.enable_timing(True)
+        legs[leg][0]()
+        eng.sync()
+        kern[leg] = {}
+        for k in SHARDED_KERNELS:
+            avg, cnt = eng.read_timing(k)
+            if cnt:
+                kern[leg][k] = [round(avg, 4), int(cnt)]
+        eng.enable_timing(False)
+    res["kernel_ms_avg_regions"] = kern
+    # nanoseconds per Rescue permutation: a leaf is one per lane; the flat levels of a slice of m lanes hash m - 1 pairs
+    # when the block is the slice, ag_k_tree over n leaves n - 1 and the root
+    kv, slices = kern["verify_sliced"], -(-n // (1 << 23))
+    if "ag_k_level" in kv and "ag_k_leaf" in kv:
+        res["ns_per_permutation"] = {"ag_k_leaf": round(kv["ag_k_leaf"][0] * kv["ag_k_leaf"][1] * 1e6 / n, 3),
+                                     "ag_k_level": round(kv["ag_k_level"][0] * kv["ag_k_level"][1] * 1e6 / (n - slices), 3)}
+        if with_base and "ag_k_tree" in kern["verify_single"]:
+            res["ns_per_permutation"]["ag_k_tree"] = round(kern["verify_single"]["ag_k_tree"][0] * 1e6 / n, 3)
+    if a.multi:
+        old = os.environ.get("SSA_AGG_BLOCK")
+        os.environ["SSA_AGG_BLOCK"] = str(n // 2)          # two blocks: one per context
+        try:
+            multi = ssa.MultiEngine([0, 0])
+        finally:
+            if old is None:
+                del os.environ["SSA_AGG_BLOCK"]
+            else:
+                os.environ["SSA_AGG_BLOCK"] = old
+        h_sigs, h_pks, h_msgs = (x.cpu().numpy() for x in (d_sigs, d_pks, d_msgs))
+        h_agg = d_agg0.cpu().numpy()
+        mlegs = {"multi_aggregate": lambda: multi.aggregate(h_sigs, h_pks, h_msgs)[1],
+                 "host_aggregate": lambda: eng.aggregate_sliced(h_sigs, h_pks, h_msgs)[1],
+                 "multi_verify": lambda: multi.verify_aggregate(h_agg, h_pks, h_msgs),
+                 "host_verify": lambda: eng.verify_aggregate_sliced(h_agg, h_pks, h_msgs)}
+        mt = {leg: [] for leg in mlegs}
+        for rnd in range(a.warmup + a.rounds):
+            for leg, fn in mlegs.items():
+                t0 = time.perf_counter()
+                out = fn()
+                ms = (time.perf_counter() - t0) * 1e3
+                good = out == 0 if leg.endswith("verify") else bool((out == h_agg).all())
+                res["mismatches"] += 0 if good else 1
+                if rnd >= a.warmup:
+                    mt[leg].append(ms)
+        res["two_contexts_on_one_device_host_buffers_ms_median"] = {leg: round(float(np.median(v)), 3) for leg, v in mt.items()}
+        multi.close()
+    print(json.dumps(res))
+    eng.close()
+    for b in (base_a, base_v):
+        if b:
+            b.close()
+    return 0 if res["mismatches"] == 0 else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1 << 20)
@@ -756,7 +888,13 @@ def main():
                          "ssa_verify_many_cached_device + ssa_aggregate_many_device on filtered arrays")
     ap.add_argument("--signers", type=int, default=65536,
                     help="--cached, --valid-cached: distinct signers (0: every lane its own)")
+    ap.add_argument("--sharded", action="store_true",
+                    help="ssa_aggregate_many_sliced_device / ssa_verify_aggregate_sliced_device against the single calls of "
+                         "--baseline-lib")
+    ap.add_argument("--multi", action="store_true", help="--sharded: also MultiEngine([0, 0]) from host buffers")
     a = ap.parse_args()
+    if a.sharded:
+        return sharded_main(a)
     if a.valid_cached:
         return valid_cached_main(a)
     if a.cached:
