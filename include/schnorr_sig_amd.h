@@ -1035,6 +1035,35 @@ int ssa_debug_aggregates_many_coeffs(ssa_ctx *ctx, const uint8_t *aggs, const ui
                                      const uint8_t *pks, const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride,
                                      size_t msg_len, uint8_t *coeffs16_out);
 
+/* ---- many aggregates produced in one call -----------------------------------------------
+ * The producer's side of ssa_verify_aggregates_many: k batches of signatures become k aggregates, in the wire layout that
+ * call reads.  The contract is one equality, per aggregate: the 49 n_j + 32 bytes of aggregate j, results_out[j] and the
+ * status bytes of its lanes are what ssa_aggregate_many writes to agg_out, returns and writes to status_out for batch j
+ * handed in alone with the same flags.
+ *   counts[j] = n_j, a HOST array in both forms;
+ *   sigs (stride 81), pks, pk_inf and the messages belong to the N = sum n_j lanes, in order;
+ *   flags     = 0 or SSA_AGG_CHECK (any other bit: SSA_ERR_ARG);
+ *   aggs_out  receives 49 N + 32 k bytes: aggregate j at byte 49 (n_0 + ... + n_(j-1)) + 32 j;
+ *   results_out[j] = SSA_OK, SSA_MALFORMED or, with SSA_AGG_CHECK, the smallest nonzero status of the aggregate's lanes.
+ * A refused aggregate (results_out[j] != 0) is zeroed, all 49 n_j + 32 bytes of it, and changes no byte of any other;
+ * n_j = 0 gives 32 zero bytes and SSA_OK.  *n_fail_out = the failing lanes of the whole call.  status_out, n_fail_out and
+ * results_out may be NULL.  The return value reports errors only: SSA_ERR_ARG for exactly the sizes and null pointers
+ * ssa_verify_aggregates_many refuses (an n_j above the context's MSM slice, N above SSA_MAX_BATCH).  k == 0: SSA_OK.
+ * The refusal is decided on the device, per aggregate: without SSA_AGG_CHECK the _device form only enqueues on the
+ * context's stream, with it the call synchronises no more than ssa_verify_batch_screened_device over the N lanes does. */
+int ssa_aggregates_many(ssa_ctx *ctx, const uint8_t *sigs, const uint64_t *counts, size_t k, const uint8_t *pks,
+                        const uint8_t *pk_inf, const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride,
+                        size_t msg_len, uint32_t flags, uint8_t *aggs_out, uint32_t *results_out, uint8_t *status_out,
+                        uint64_t *n_fail_out);
+int ssa_aggregates_many_device(ssa_ctx *ctx, const uint8_t *d_sigs, const uint64_t *counts, size_t k, const uint8_t *d_pks,
+                               const uint8_t *d_pk_inf, const uint8_t *d_msgs, const uint64_t *d_msg_off, size_t msg_stride,
+                               size_t msg_len, uint32_t flags, uint8_t *d_aggs_out, uint32_t *d_results_out,
+                               uint8_t *d_status_out, uint64_t *d_n_fail_out);
+/* tests: the partial sums of that call's fold from its counts alone (host code, no device).  out[0] = partials in all,
+ * out[1 .. k + 2) = pfirst: aggregate j shares lanes with pfirst[j + 1] - pfirst[j] workgroups of 256 dense lanes (0 if it
+ * is empty).  Returns the k + 2 words this takes -- out receives them if out_words is enough -- or SSA_ERR_ARG. */
+int64_t ssa_debug_aggregates_fold_plan(const uint64_t *counts, size_t k, uint64_t *out, size_t out_words);
+
 /* ---- many aggregates through a key cache, subgroup check included -----------------------
  * ssa_verify_aggregates_many with the key cache of sections 16, 18 and 19 in front: every distinct key is checked
  * (limbs, curve, [q]P) once and then found in the cache, a wire key is decompressed once, and an aggregate that holds a

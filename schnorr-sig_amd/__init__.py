@@ -285,6 +285,9 @@ def _load():
         "ssa_verify_aggregates_many_device": (i32, [vp, vp, u64p, sz, vp, vp, vp, vp, sz, sz, vp]),
         "ssa_debug_aggregates_plan": (C.c_int64, [u64p, sz, sz, sz, u64p, sz]),
         "ssa_debug_aggregates_many_coeffs": (i32, [vp, vp, u64p, sz, vp, vp, vp, sz, sz, vp]),
+        "ssa_aggregates_many": (i32, [vp, vp, u64p, sz, vp, vp, vp, vp, sz, sz, u32, vp, vp, vp, u64p]),
+        "ssa_aggregates_many_device": (i32, [vp, vp, u64p, sz, vp, vp, vp, vp, sz, sz, u32, vp, vp, vp, vp]),
+        "ssa_debug_aggregates_fold_plan": (C.c_int64, [u64p, sz, u64p, sz]),
         "ssa_verify_aggregates_many_cached": (i32, [vp, vp, vp, u64p, sz, vp, vp, vp, vp, sz, sz, vp, vp]),
         "ssa_verify_aggregates_many_cached_device": (i32, [vp, vp, vp, u64p, sz, vp, vp, vp, vp, sz, sz, vp, vp]),
         "ssa_verify_aggregates_many_cached_wire": (i32, [vp, vp, vp, u64p, sz, vp, vp, vp, sz, sz, vp, vp]),
@@ -344,6 +347,19 @@ def pack_aggregates(aggregates):
             raise MalformedInput("an aggregate of n signatures is 49 n + 32 bytes")
     counts = np.array([(len(r) - 32) // 49 for r in raw], dtype=np.uint64)
     return counts, np.frombuffer(b"".join(raw) + b"\0", dtype=np.uint8).copy()
+
+
+def split_aggregates(counts, wire):
+    """the inverse of pack_aggregates: the wire forms end to end (49 N + 32 k bytes) -> the k aggregates as uint8 arrays
+    (views of `wire`), aggregate j the 49 n_j + 32 bytes from byte 49 (n_0 + ... + n_(j-1)) + 32 j"""
+    wire = _np_u8(wire).reshape(-1)
+    out, lo = [], 0
+    for n in counts:
+        out.append(wire[lo:lo + 49 * int(n) + 32])
+        lo += 49 * int(n) + 32
+    if wire.size < lo:
+        raise MalformedInput("k aggregates of N signatures are 49 N + 32 k bytes")
+    return out
 
 
 class Engine:
@@ -945,6 +961,86 @@ class Engine:
             addr(d_pk_inf), addr(d_msgs), addr(d_offsets), msg_stride if msg_stride is not None else msg_len, msg_len,
             addr(d_verdicts)), "ssa_verify_aggregates_many_device")
         return d_verdicts
+
+    # ---- many aggregates produced in one call (include/schnorr_sig_amd.h) ----
+    def aggregates_wire(self, batches, check=False, counts=None, pk_inf=None, offsets=None):
+        """k batches of signatures -> (counts uint64[k]; wire uint8[49 N + 32 k], the aggregates end to end as the call
+        wrote them and as verify_aggregates reads them, a refused one all zero; results uint32[k]; per-lane status
+        uint8[N]; n_fail).  batches: a list of (sigs, pks, msgs) or (sigs, pks, msgs, pk_inf) batches, msgs an (n, len)
+        array or a list of byte strings; or, with counts, the flat (sigs, pks, msgs) of all N lanes in order, with pk_inf
+        and offsets as verify_aggregates takes them.  results[j]: OK, MALFORMED or, with check, the smallest nonzero
+        status of batch j's lanes."""
+        if counts is None:
+            counts = np.array([_np_u8(b[1], 96).shape[0] for b in batches], dtype=np.uint64)
+            n = int(counts.sum())
+            sigs = np.concatenate([_np_u8(b[0], 81) for b in batches] + [np.zeros((0, 81), np.uint8)])
+            pks = np.concatenate([_np_u8(b[1], 96) for b in batches] + [np.zeros((0, 96), np.uint8)])
+            if any(len(b) > 3 and b[3] is not None for b in batches):
+                pk_inf = np.concatenate([_np_u8(b[3]).reshape(-1) if len(b) > 3 and b[3] is not None
+                                         else np.zeros(int(c), np.uint8) for b, c in zip(batches, counts)])
+            rows = [b[2] for b, c in zip(batches, counts) if c]
+            if rows and all(isinstance(r, np.ndarray) and r.ndim == 2 and r.shape[1] == rows[0].shape[1] for r in rows):
+                msgs = np.concatenate(rows)
+            else:
+                msgs, offsets = pack_messages([bytes(m) for r in rows for m in r])
+        else:
+            sigs, pks, msgs = batches
+            counts = np.ascontiguousarray(counts, dtype=np.uint64)
+            n = int(counts.sum())
+            sigs, pks = _np_u8(sigs, 81), _np_u8(pks, 96)
+        if sigs.shape[0] != n or pks.shape[0] != n:
+            raise MalformedInput("We should have the same number of signatures than public keys")
+        k = counts.size
+        m, off, stride, mlen = self._msg_args(msgs, offsets, n) if n else (None, None, 0, 0)
+        inf = _np_u8(pk_inf) if pk_inf is not None else None
+        wire = np.full(49 * n + 32 * k + 1, 255, dtype=np.uint8)
+        results = np.full(k, 255, dtype=np.uint32)
+        status = np.full(n, 255, dtype=np.uint8)
+        nfail = C.c_uint64(0)
+        _check(_lib.ssa_aggregates_many(
+            self._ctx, _ptr(sigs) if n else None, counts.ctypes.data_as(C.POINTER(C.c_uint64)) if k else None, k,
+            _ptr(pks) if n else None, _ptr(inf), _ptr(m), _ptr(off), stride, mlen, AGG_CHECK if check else 0,
+            _ptr(wire) if k else None, _ptr(results) if k else None, _ptr(status) if n else None, C.byref(nfail)),
+            "ssa_aggregates_many")
+        return counts, wire[:-1], results, status, int(nfail.value)
+
+    def aggregates(self, batches, check=False, counts=None, pk_inf=None, offsets=None):
+        """aggregates_wire with the output split -> (list of AggregateSignature, None where the batch is refused;
+        results uint32[k]; per-lane status uint8[N]; n_fail): for each batch what aggregate() gives it alone, from one
+        call"""
+        counts, wire, results, status, nfail = self.aggregates_wire(batches, check, counts, pk_inf, offsets)
+        aggs = [AggregateSignature(a.tobytes()) if r == OK else None
+                for a, r in zip(split_aggregates(counts, wire), results)]
+        return aggs, results, status, nfail
+
+    def aggregates_device(self, d_sigs, counts, d_pks, d_msgs, d_aggs=None, d_results=None, d_status=None, d_nfail=None,
+                          d_pk_inf=None, d_offsets=None, msg_len=None, msg_stride=None, check=False):
+        """device form over torch tensors on this engine's device, arguments as verify_aggregates_device takes them:
+        counts a HOST sequence, d_sigs the (N, 81) signatures.  Without check it only enqueues.  The aggregates land in
+        d_aggs (uint8[49 N + 32 k]), the results in d_results (int32[k]), the statuses in d_status (uint8[N]) and the
+        count of failing lanes in d_nfail (int64[1]); each is allocated when None.  Returns the four tensors."""
+        import torch
+        counts = np.ascontiguousarray(counts, dtype=np.uint64)
+        k, n = counts.size, int(counts.sum())
+        dev = d_pks.device
+        if d_aggs is None:
+            d_aggs = torch.empty(49 * n + 32 * k + 4, dtype=torch.uint8, device=dev)[:49 * n + 32 * k]
+        if d_results is None:
+            d_results = torch.empty(max(k, 1), dtype=torch.int32, device=dev)[:k]
+        if d_status is None:
+            d_status = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)[:n]
+        if d_nfail is None:
+            d_nfail = torch.empty(1, dtype=torch.int64, device=dev)
+        if d_offsets is None and msg_len is None:
+            msg_len = d_msgs.shape[1] if d_msgs.dim() == 2 else 0
+        msg_len = msg_len or 0
+        addr = lambda t: t.data_ptr() if t is not None and t.numel() else None    # noqa: E731
+        _check(_lib.ssa_aggregates_many_device(
+            self._ctx, addr(d_sigs), counts.ctypes.data_as(C.POINTER(C.c_uint64)) if k else None, k, addr(d_pks),
+            addr(d_pk_inf), addr(d_msgs), addr(d_offsets), msg_stride if msg_stride is not None else msg_len, msg_len,
+            AGG_CHECK if check else 0, d_aggs.data_ptr() if k else None, addr(d_results), addr(d_status),
+            d_nfail.data_ptr()), "ssa_aggregates_many_device")
+        return d_aggs, d_results, d_status, d_nfail
 
     # ---- many aggregates through a key cache (include/schnorr_sig_amd.h, DESIGN.md section 23) ----
     def verify_aggregates_cached(self, cache, aggregates, keys, msgs, pk_inf=None, offsets=None):
@@ -1826,6 +1922,20 @@ def debug_aggregates_plan(counts, msm_slice=1 << 23, small_max=3072):
     return {"lanes": w[0], "groups": groups, "passes": passes, "descriptors": w[3]}
 
 
+def debug_aggregates_fold_plan(counts):
+    """host logic of Engine.aggregates (no device needed): (partials in all, pfirst uint64[k + 1]) -- aggregate j shares
+    lanes with pfirst[j + 1] - pfirst[j] workgroups of 256 dense lanes; None when refused"""
+    counts = np.ascontiguousarray(counts, dtype=np.uint64)
+    cp = counts.ctypes.data_as(C.POINTER(C.c_uint64)) if counts.size else None
+    need = _lib.ssa_debug_aggregates_fold_plan(cp, counts.size, None, 0)
+    if need < 0:
+        return None
+    out = np.zeros(need, dtype=np.uint64)
+    _check(_lib.ssa_debug_aggregates_fold_plan(cp, counts.size, out.ctypes.data_as(C.POINTER(C.c_uint64)), need),
+           "ssa_debug_aggregates_fold_plan")
+    return int(out[0]), out[1:]
+
+
 def default_engine():
     global _default_engine
     if _default_engine is None:
@@ -2065,6 +2175,18 @@ class AggregateSignature:
         else:
             agg, kept = eng.aggregate_valid_cached(cache, sigs, pks, flat, offsets=off, pk_inf=inf)[:2]
         return cls(agg.tobytes()), [int(i) for i in kept]
+
+    @classmethod
+    def aggregate_many(cls, batches, check=True, engine=None):
+        """Engine.aggregates over a list of (signatures, public keys, messages) slices of objects, one aggregate per
+        slice from ONE call (DESIGN.md section 26) -> (list of AggregateSignature, None where aggregate() would raise;
+        results uint32[k]: OK, MALFORMED or, with check, the smallest nonzero status of the slice's signatures)"""
+        packed = [_pack_triples(*b) for b in batches]
+        eng = engine or default_engine()
+        flat = [(np.zeros((0, 81), np.uint8), np.zeros((0, 96), np.uint8), [], None) if p is None else
+                (p[0], p[1], [bytes(m) for m in b[2]], p[2]) for p, b in zip(packed, batches)]
+        aggs, results, _, _ = eng.aggregates(flat, check=check)
+        return aggs, results
 
     def verify(self, public_keys, messages, engine=None, sliced=False):
         """Ok -> None; otherwise raises SignatureError (the equation fails) or MalformedInput.  sliced: through

@@ -45,6 +45,11 @@
 // ssa_aggregate_valid_many_cached keeps the lanes that pass ssa_verify_many_cached instead -- the
 // subgroup check of the key included -- and hands the kept lanes' keys on: av_k_gather_sigs also reads signatures out of
 // 130-byte records, av_k_gather_keys lays the kept keys (49 or 96 bytes, and the pk_inf byte) side by side.
+//
+// ssa_aggregates_many produces k aggregates in one call: the transcript with a plan over the
+// signatures themselves, then ag_k_fold_seg (one lane per signature over the dense lanes, a segmented sum per workgroup,
+// one partial per workgroup and aggregate), ag_k_fold_finish_seg (one wave per aggregate: its scalar and its refusal,
+// decided on the device) and ag_k_pack_many (the R's into the wire form ssa_verify_aggregates_many reads).
 #pragma once
 #include <vector>
 #include "ssa_kernels.hpp"
@@ -80,6 +85,7 @@ struct AgGroup {
 constexpr u32 AG_GROUP_MAX = 256;        // segments of one screened MSM (SCREEN_MAX_SEGS)
 struct AgPlan {
     std::vector<u32> first;                          // k + 1 prefix sums of the counts
+    std::vector<u32> pfirst;                         // k + 1 prefix sums of the 256-lane workgroups each aggregate touches
     std::vector<std::vector<AgTreeDesc>> passes;     // the passes per call are those of the largest aggregate
     std::vector<AgGroup> groups;
 };
@@ -98,6 +104,11 @@ static inline int ag_plan(const uint64_t *counts, size_t k, size_t slice, size_t
         if (total > SSA_MAX_BATCH) return SSA_ERR_ARG;
         pl.first[j + 1] = (u32)total;
     }
+    // the producer's fold (ag_k_fold_seg): over the dense lanes aggregate j shares lanes with the workgroups
+    // first[j] >> 8 .. (first[j + 1] - 1) >> 8, and each of them writes one partial for it; an empty one has none
+    pl.pfirst.assign(k + 1, 0u);
+    for (size_t j = 0; j < k; j++)
+        pl.pfirst[j + 1] = pl.pfirst[j] + (counts[j] ? ((pl.first[j + 1] - 1) >> 8) - (pl.first[j] >> 8) + 1 : 0u);
     // the tree: every aggregate advances in the same pass; (offset, count) of its nodes in the pass's input
     std::vector<u32> off(pl.first.begin(), pl.first.end() - 1), cnt(k);
     size_t live = 0;
@@ -358,6 +369,31 @@ SSA_DEV void ag_block_sum(u64 *red, const sc256 &v) {
     }
 }
 
+// Lane i of a fold: ae = a_i e_i mod q when the lane passes, else it stays as it came (zero).  e < q is checked always;
+// check: the other checks of msm_k_prepare too (canonical limbs, key on the curve, R decodable).  Returns "passed".
+SSA_DEV bool ag_fold_lane(const u8 *__restrict__ sigs, const u8 *__restrict__ pks, const u8 *__restrict__ pk_inf,
+                          const u64 *__restrict__ coeffs, size_t i, bool check, sc256 &ae) {
+    const sc256 e = ld_sc(sigs + 81 * i + 49);
+    bool ok = !sc_geq_q(e);
+    if (check) {
+        aff P;
+        P.x = ld_fp6(pks + 96 * i, ok);
+        P.y = ld_fp6(pks + 96 * i + 48, ok);
+        if (ok && !(pk_inf && pk_inf[i])) ok = aff_on_curve(P);
+        aff R;
+        bool r_inf = false;
+        if (ok) ok = decompress_lane(sigs + 81 * i, R, r_inf) == 0;
+    }
+    if (ok) {
+        sc256 a;
+        a.w[0] = coeffs[2 * i];
+        a.w[1] = coeffs[2 * i + 1];
+        a.w[2] = a.w[3] = 0;
+        ae = sc_mul_mod(a, e);
+    }
+    return ok;
+}
+
 // partials[b] = sum over the lanes of workgroup b of a_i e_i mod q.  status != nullptr: the checks of msm_k_prepare too --
 // status[i] = SSA_MALFORMED on a lane that fails one (and it adds nothing), else 0; *n_bad counts them.
 __global__ void __launch_bounds__(256)
@@ -370,25 +406,10 @@ ag_k_fold(const u8 *__restrict__ sigs, const u8 *__restrict__ pks, const u8 *__r
 #pragma unroll
     for (int k = 0; k < 4; k++) ae.w[k] = 0;
     if (i < n) {
-        const sc256 e = ld_sc(sigs + 81 * i + 49);
-        bool ok = !sc_geq_q(e);
+        const bool ok = ag_fold_lane(sigs, pks, pk_inf, coeffs, i, status != nullptr, ae);
         if (status) {
-            aff P;
-            P.x = ld_fp6(pks + 96 * i, ok);
-            P.y = ld_fp6(pks + 96 * i + 48, ok);
-            if (ok && !(pk_inf && pk_inf[i])) ok = aff_on_curve(P);
-            aff R;
-            bool r_inf = false;
-            if (ok) ok = decompress_lane(sigs + 81 * i, R, r_inf) == 0;
             status[i] = (u8)(ok ? ST_OK : ST_MALFORMED);
             if (!ok) atomicAdd(n_bad, 1ull);
-        }
-        if (ok) {
-            sc256 a;
-            a.w[0] = coeffs[2 * i];
-            a.w[1] = coeffs[2 * i + 1];
-            a.w[2] = a.w[3] = 0;
-            ae = sc_mul_mod(a, e);
         }
     }
     ag_block_sum(red, ae);
@@ -414,6 +435,138 @@ ag_k_fold_finish(const u64 *__restrict__ partials, u32 n_partials, u8 *__restric
     }
     ag_block_sum(red, acc);
     if (threadIdx.x < 32) e_out[threadIdx.x] = (u8)(red[threadIdx.x >> 3] >> (8 * (threadIdx.x & 7u)));
+}
+
+// ---- the producer of many aggregates (ssa_aggregates_many) ----
+// The fold over all N lanes of the call, densely packed: a workgroup of 256 lanes may hold the end of one aggregate,
+// several whole ones and the start of another.  map[i]: the aggregate of lane i (ag_k_lane_map: non-decreasing), so a
+// workgroup's lanes fall into runs of equal map.  The workgroup sums every run with a segmented suffix scan through LDS:
+// at step d lane t adds lane t + d's value iff both stand in the same run -- after eight steps the head of a run (lane
+// 0 of the workgroup, or map[i] != map[i - 1]) holds the run's sum, and writes it as ONE partial.  The partials of
+// aggregate j are contiguous: workgroup b's stands at pfirst[j] + b - (first[j] >> 8) (ag_plan).
+// screened == 0: the checks of ag_k_fold, status[i] written as there.  screened != 0: status[i] is the screen's and is
+// read.  Either way a lane with a nonzero status st adds 1 to acc[2 j] and raises acc[2 j + 1] to 256 - st (both zeroed
+// before the launch): the failing lanes of aggregate j and, turned round, the smallest nonzero status among them.
+__global__ void __launch_bounds__(256)
+ag_k_fold_seg(const u8 *__restrict__ sigs, const u8 *__restrict__ pks, const u8 *__restrict__ pk_inf,
+              const u64 *__restrict__ coeffs, const u32 *__restrict__ map, const u32 *__restrict__ first,
+              const u32 *__restrict__ pfirst, size_t n, u64 *__restrict__ partials, u8 *__restrict__ status, u32 screened,
+              u32 *__restrict__ acc) {
+    __shared__ u64 red[256 * 4];
+    __shared__ u32 key[256];
+    const u32 t = threadIdx.x;
+    const size_t i = (size_t)blockIdx.x * 256 + t;
+    sc256 v;
+#pragma unroll
+    for (int k = 0; k < 4; k++) v.w[k] = 0;
+    u32 j = 0xFFFFFFFFu;                              // (lanes behind the last one: a run of their own, never written)
+    if (i < n) {
+        j = map[i];
+        const bool ok = ag_fold_lane(sigs, pks, pk_inf, coeffs, i, screened == 0u, v);
+        u32 st;
+        if (screened) {
+            st = status[i];
+        } else {
+            st = ok ? ST_OK : ST_MALFORMED;
+            status[i] = (u8)st;
+        }
+        if (st) {
+            atomicAdd(acc + 2 * (size_t)j, 1u);
+            atomicMax(acc + 2 * (size_t)j + 1, 256u - st);
+        }
+    }
+    key[t] = j;
+#pragma unroll 1
+    for (u32 d = 1; d < 256u; d <<= 1) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) red[t * 4 + k] = v.w[k];
+        __syncthreads();                              // (the first one also publishes key)
+        if (t + d < 256u && key[t + d] == j) {
+            sc256 b;
+#pragma unroll
+            for (int k = 0; k < 4; k++) b.w[k] = red[(t + d) * 4 + k];
+            v = sc_add_mod(v, b);
+        }
+        __syncthreads();                              // every read of this step before the next one's writes
+    }
+    if (i < n && (t == 0 || key[t - 1] != j)) {
+        const size_t slot = (size_t)pfirst[j] + blockIdx.x - (first[j] >> 8);
+#pragma unroll
+        for (int k = 0; k < 4; k++) partials[4 * slot + k] = v.w[k];
+    }
+}
+
+// One wave per aggregate j: e_agg_j = the sum of its partials [pfirst[j], pfirst[j + 1]) mod q (none for an empty
+// aggregate: zero), and the refusal, decided here.  results[j] = 0, or the smallest nonzero status of the aggregate's
+// lanes (256 - acc[2 j + 1]) when acc[2 j] of them failed; the 32 bytes at ag_wire_e are e_agg_j, canonical, or zero for
+// a refused aggregate.  n_fail != nullptr: the failing lanes are added to the call's count.
+__global__ void __launch_bounds__(64)
+ag_k_fold_finish_seg(const u64 *__restrict__ partials, const u32 *__restrict__ first, const u32 *__restrict__ pfirst,
+                     const u32 *__restrict__ acc, u8 *__restrict__ aggs_out, u32 *__restrict__ results,
+                     unsigned long long *__restrict__ n_fail) {
+    __shared__ u64 red[64 * 4];
+    const u32 j = blockIdx.x, t = threadIdx.x;
+    sc256 v;
+#pragma unroll
+    for (int k = 0; k < 4; k++) v.w[k] = 0;
+#pragma unroll 1
+    for (u32 b = pfirst[j] + t; b < pfirst[j + 1]; b += 64u) {
+        sc256 p;
+#pragma unroll
+        for (int k = 0; k < 4; k++) p.w[k] = partials[4 * (size_t)b + k];
+        v = sc_add_mod(v, p);
+    }
+#pragma unroll
+    for (int k = 0; k < 4; k++) red[t * 4 + k] = v.w[k];
+    __syncthreads();
+    for (u32 stride = 32; stride > 0; stride >>= 1) {
+        if (t < stride) {
+            sc256 a, b;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                a.w[k] = red[t * 4 + k];
+                b.w[k] = red[(t + stride) * 4 + k];
+            }
+            a = sc_add_mod(a, b);
+#pragma unroll
+            for (int k = 0; k < 4; k++) red[t * 4 + k] = a.w[k];
+        }
+        __syncthreads();
+    }
+    const u32 bad = acc[2 * (size_t)j], res = bad ? 256u - acc[2 * (size_t)j + 1] : (u32)ST_OK;
+    if (t < 32) aggs_out[ag_wire_e(first, j, 0) + t] = res ? (u8)0 : (u8)(red[t >> 3] >> (8 * (t & 7u)));
+    if (t == 0) {
+        results[j] = res;
+        if (n_fail && bad) atomicAdd(n_fail, (unsigned long long)bad);
+    }
+}
+
+// The R's of the call's n signatures into the wire form of its aggregates: the inverse of ag_k_expand with the map.  Byte
+// r < 49 of lane i goes to ag_wire_r(i, map[i]) + r, zero where the lane's aggregate is refused (results[map[i]] != 0).
+// One thread per four bytes of the n x 49; aggs_out is the caller's: a dword only when it is aligned and the four bytes
+// stand in one aggregate (they then keep their distance: the shift of aggregate j is 32 j bytes).
+__global__ void __launch_bounds__(256)
+ag_k_pack_many(const u8 *__restrict__ sigs, const u32 *__restrict__ map, const u32 *__restrict__ results, size_t n,
+               u8 *__restrict__ aggs_out) {
+    const size_t d = (size_t)blockIdx.x * 256 + threadIdx.x, total = n * 49, o = 4 * d;
+    if (o >= total) return;
+    const int cnt = total - o < 4 ? (int)(total - o) : 4;
+    const size_t i0 = o / 49, i1 = (o + cnt - 1) / 49;
+    const u32 j0 = map[i0], j1 = map[i1];
+    const bool z0 = results[j0] != 0u, z1 = results[j1] != 0u;
+    u32 v = 0;
+    for (int k = 0; k < cnt; k++) {
+        const size_t b = o + k, i = b / 49;
+        if (!(i == i0 ? z0 : z1)) v |= (u32)sigs[81 * i + (b - 49 * i)] << (8 * k);
+    }
+    if (cnt == 4 && j0 == j1 && (reinterpret_cast<uintptr_t>(aggs_out) & 3u) == 0) {
+        *reinterpret_cast<u32 *>(aggs_out + ag_wire_r(i0, j0) + (o - 49 * i0)) = v;
+    } else {
+        for (int k = 0; k < cnt; k++) {
+            const size_t b = o + k, i = b / 49;
+            aggs_out[ag_wire_r(i, i == i0 ? j0 : j1) + (b - 49 * i)] = (u8)(v >> (8 * k));
+        }
+    }
 }
 
 // ONE wave.  rec: the 24-word record of the MSM over the aggregate's R's with e = 0 -- the left-hand point

@@ -1894,7 +1894,7 @@ static std::vector<AgPass> ag_uniform_passes(size_t nodes, size_t n) {
 static std::vector<AgPass> ag_uniform_passes(size_t n) { return ag_uniform_passes(n, n); }
 
 // The transcript over the n (>= 1) lanes of a call, on ctx->stream, in two halves.  d_first: the k + 1 prefix sums of an
-// uploaded plan (agm_upload_plan); nullptr: one aggregate, no plan, no lane map.
+// uploaded plan (agm_upload_plan), and ctx->agm_map receives the lane map; nullptr: one aggregate, no plan, no lane map.
 // The front: the R's and the challenge hashes.  d_wire != nullptr: the R's come out of the wire form and are laid out at
 // stride 81 in ctx->ag_sigs first, and *d_sigs then points there; else they stand so in *d_sigs.  ONE launch of ssa_k_hash
 // leaves the raw digests in ctx->ag_dig and, with_h, the challenge scalars mod q in ctx->ws_h (d_h_out: there instead --
@@ -1915,6 +1915,12 @@ static int ag_transcript_front(ssa_ctx *ctx, const u8 *d_wire, const u8 **d_sigs
         });
         if (rc) return rc;
         *d_sigs = (const u8 *)ctx->ag_sigs.p;
+    } else if (d_first) {       // a plan over signatures (ssa_aggregates_many): the lane map alone
+        const int rc = timed_launch(ctx, "ag_k_lane_map", [&] {
+            hipLaunchKernelGGL(ag_k_lane_map, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, d_first, (u32)k, n,
+                               (u32 *)ctx->agm_map.p);
+        });
+        if (rc) return rc;
     }
     return timed_launch(ctx, "ssa_k_hash", [&] {
         hipLaunchKernelGGL(ssa_k_hash, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, ctx->d_params, *d_sigs, d_pks, mv, n,
@@ -2711,8 +2717,9 @@ extern "C" int ssa_debug_aggregate_shard_coeffs(ssa_ctx *ctx, const uint8_t root
 
 // ------------------------------------------------------------------ many aggregates in one call
 // The plan on the device (ctx->agm_plan): k + 1 prefix sums, then the tree's descriptors pass after pass.  The host copy
-// lives in the context; the event says when the last upload has read it.
-static int agm_upload_plan(ssa_ctx *ctx, const AgPlan &pl, std::vector<AgPass> &passes) {
+// lives in the context; the event says when the last upload has read it.  pfirst_off != nullptr (the producer, DESIGN.md
+// section 26): the k + 1 partial offsets follow the descriptors, at that byte of the plan.
+static int agm_upload_plan(ssa_ctx *ctx, const AgPlan &pl, std::vector<AgPass> &passes, size_t *pfirst_off = nullptr) {
     if (!ctx->agm_plan_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->agm_plan_ev, hipEventDisableTiming));
     else HIP_TRY(hipEventSynchronize(ctx->agm_plan_ev));
     std::vector<uint32_t> &h = ctx->agm_plan_host;
@@ -2722,6 +2729,10 @@ static int agm_upload_plan(ssa_ctx *ctx, const AgPlan &pl, std::vector<AgPass> &
     for (const auto &pass : pl.passes) {
         passes.push_back({h.size() * sizeof(uint32_t), (u32)pass.size(), 0u});
         for (const AgTreeDesc &d : pass) h.insert(h.end(), {d.first, d.count, d.slot, d.top_n});
+    }
+    if (pfirst_off) {
+        *pfirst_off = h.size() * sizeof(uint32_t);
+        h.insert(h.end(), pl.pfirst.begin(), pl.pfirst.end());
     }
     if (ctx->agm_plan.reserve(h.size() * sizeof(uint32_t))) return SSA_ERR_HIP;
     HIP_TRY(hipMemcpyAsync(ctx->agm_plan.p, h.data(), h.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
@@ -2822,6 +2833,109 @@ extern "C" int ssa_verify_aggregates_many(ssa_ctx *ctx, const uint8_t *aggs, con
     const MsgView mv = hc.msgs(msgs, msg_off, msg_stride, msg_len, n);
     uint32_t *d_verdicts = (uint32_t *)hc.out(ctx->st_status, verdicts_out, k * sizeof(uint32_t), 16);
     return hc.finish([&] { return agm_run(ctx, pl, d_aggs, k, d_pks, d_inf, mv, n, d_verdicts); });
+}
+
+// ------------------------------------------------------------------ the producer of many aggregates
+// ctx->agp_acc: two words per aggregate (failing lanes, 256 - the smallest nonzero status), zeroed before every fold, and
+// behind them the results when the caller takes none
+static int agp_run(ssa_ctx *ctx, const AgPlan &pl, const uint8_t *d_sigs, size_t k, const uint8_t *d_pks,
+                   const uint8_t *d_pk_inf, const MsgView &mv, size_t n, uint32_t flags, uint8_t *d_aggs_out,
+                   uint32_t *d_results_out, uint8_t *d_status_out, uint64_t *d_n_fail_out) {
+    unsigned long long *d_fail;
+    if (int rc = reset_fail_counter(ctx, d_n_fail_out, &d_fail)) return rc;
+    const bool screened = (flags & SSA_AGG_CHECK) != 0;
+    const size_t acc_bytes = (2 * k * sizeof(u32) + 15) & ~(size_t)15;
+    if (ctx->agp_acc.reserve(acc_bytes + k * sizeof(u32)) || (n && !d_status_out && ctx->ag_status.reserve(n + 16)) ||
+        ctx->ag_partials.reserve((size_t)pl.pfirst[k] * 32 + 32))
+        return SSA_ERR_HIP;
+    u32 *d_acc = (u32 *)ctx->agp_acc.p;
+    u32 *d_results = d_results_out ? d_results_out : (u32 *)((u8 *)ctx->agp_acc.p + acc_bytes);
+    u8 *d_status = d_status_out ? d_status_out : (u8 *)ctx->ag_status.p;
+    // the screen counts the failing lanes of the call itself; its statuses do not depend on how the lanes are grouped
+    if (screened && n)
+        if (int rc = ssa_verify_batch_screened_device(ctx, d_sigs, d_pks, d_pk_inf, mv.msgs, mv.off, mv.stride, mv.len, n,
+                                                      nullptr, 0, d_status, (uint64_t *)d_fail))
+            return rc;
+    std::vector<AgPass> passes;
+    size_t pfirst_off = 0;
+    if (int rc = agm_upload_plan(ctx, pl, passes, &pfirst_off)) return rc;
+    const u32 *d_first = (const u32 *)ctx->agm_plan.p, *d_pfirst = (const u32 *)((const u8 *)ctx->agm_plan.p + pfirst_off);
+    HIP_TRY(hipMemsetAsync(d_acc, 0, acc_bytes, ctx->stream));
+    if (n) {
+        if (int rc = ag_transcript(ctx, nullptr, d_sigs, d_pks, mv, n, false, d_first, k, passes)) return rc;
+        const int rc = timed_launch(ctx, "ag_k_fold_seg", [&] {
+            hipLaunchKernelGGL(ag_k_fold_seg, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, d_sigs, d_pks, d_pk_inf,
+                               (const u64 *)ctx->ag_coeffs.p, (const u32 *)ctx->agm_map.p, d_first, d_pfirst, n,
+                               (u64 *)ctx->ag_partials.p, d_status, screened ? 1u : 0u, d_acc);
+        });
+        if (rc) return rc;
+    }
+    int rc = timed_launch(ctx, "ag_k_fold_finish_seg", [&] {
+        hipLaunchKernelGGL(ag_k_fold_finish_seg, dim3((unsigned)k), dim3(64), 0, ctx->stream, (const u64 *)ctx->ag_partials.p,
+                           d_first, d_pfirst, (const u32 *)d_acc, d_aggs_out, d_results,
+                           screened ? (unsigned long long *)nullptr : d_fail);
+    });
+    if (rc || !n) return rc;
+    return timed_launch(ctx, "ag_k_pack_many", [&] {
+        hipLaunchKernelGGL(ag_k_pack_many, dim3(grid_for((n * 49 + 3) / 4, 256)), dim3(256), 0, ctx->stream, d_sigs,
+                           (const u32 *)ctx->agm_map.p, (const u32 *)d_results, n, d_aggs_out);
+    });
+}
+
+// arguments of both forms: those of ssa_verify_aggregates_many with aggs_out in the place of the wire form and of the
+// verdicts, then the flags and the signatures
+static int agp_check_args(const ssa_ctx *ctx, const void *sigs, const uint64_t *counts, size_t k, const void *pks,
+                          const MsgView &mv, uint32_t flags, const void *aggs_out, AgPlan &pl, size_t *n_out) {
+    *n_out = 0;
+    if (!ctx || (flags & ~SSA_AGG_CHECK)) return SSA_ERR_ARG;
+    if (int rc = agm_check_args(ctx, aggs_out, counts, k, pks, mv, aggs_out, pl, n_out)) return rc;
+    return *n_out && !sigs ? SSA_ERR_ARG : 0;
+}
+
+// Only enqueues, but for what ssa_verify_batch_screened_device does under SSA_AGG_CHECK.
+extern "C" int ssa_aggregates_many_device(ssa_ctx *ctx, const uint8_t *d_sigs, const uint64_t *counts, size_t k,
+                                          const uint8_t *d_pks, const uint8_t *d_pk_inf, const uint8_t *d_msgs,
+                                          const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len, uint32_t flags,
+                                          uint8_t *d_aggs_out, uint32_t *d_results_out, uint8_t *d_status_out,
+                                          uint64_t *d_n_fail_out) {
+    const MsgView mv{d_msgs, d_msg_off, msg_stride, msg_len};
+    AgPlan pl;
+    size_t n = 0;
+    if (int rc = agp_check_args(ctx, d_sigs, counts, k, d_pks, mv, flags, d_aggs_out, pl, &n)) return rc;
+    if (k == 0) {
+        unsigned long long *d_fail;
+        return reset_fail_counter(ctx, d_n_fail_out, &d_fail);
+    }
+    return agp_run(ctx, pl, d_sigs, k, d_pks, d_pk_inf, mv, n, flags, d_aggs_out, d_results_out, d_status_out, d_n_fail_out);
+}
+
+extern "C" int ssa_aggregates_many(ssa_ctx *ctx, const uint8_t *sigs, const uint64_t *counts, size_t k, const uint8_t *pks,
+                                   const uint8_t *pk_inf, const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride,
+                                   size_t msg_len, uint32_t flags, uint8_t *aggs_out, uint32_t *results_out,
+                                   uint8_t *status_out, uint64_t *n_fail_out) {
+    AgPlan pl;
+    size_t n = 0;
+    if (int rc = agp_check_args(ctx, sigs, counts, k, pks, {msgs, msg_off, msg_stride, msg_len}, flags, aggs_out, pl, &n))
+        return rc;
+    if (int rc = check_host_offsets(msg_off, n)) return rc;
+    if (n_fail_out) *n_fail_out = 0;
+    if (k == 0) return SSA_OK;
+    HostCall hc(ctx);
+    const u8 *d_sigs = hc.in(ctx->st_sigs, sigs, n * 81), *d_pks = hc.in(ctx->st_pks, pks, n * 96);
+    const u8 *d_inf = pk_inf ? hc.in(ctx->st_inf, pk_inf, n) : nullptr;
+    const MsgView mv = hc.msgs(msgs, msg_off, msg_stride, msg_len, n);
+    u8 *d_aggs = hc.out(ctx->st_aux, aggs_out, 49 * n + 32 * k, 16);
+    uint32_t *d_results = (uint32_t *)hc.out(ctx->st_aux2, results_out, k * sizeof(uint32_t), 16);
+    u8 *d_status = hc.out(ctx->st_status, status_out, n, 16);
+    unsigned long long nf = 0;
+    hc.copy_back(&nf, ctx->ws_fail.p, sizeof nf);
+    const int rc = hc.finish([&] {
+        return agp_run(ctx, pl, n ? d_sigs : nullptr, k, n ? d_pks : nullptr, d_inf, mv, n, flags, d_aggs, d_results, d_status,
+                       nullptr);
+    });
+    if (rc) return rc;
+    if (n_fail_out) *n_fail_out = nf;
+    return SSA_OK;
 }
 
 // ------------------------------------------------------------------ aggregates through a key cache
@@ -3133,6 +3247,19 @@ extern "C" int64_t ssa_debug_aggregates_plan(const uint64_t *counts, size_t k, s
     }
     if (out && out_words >= w.size()) std::memcpy(out, w.data(), w.size() * sizeof(uint64_t));
     return (int64_t)w.size();
+}
+
+// tests: the partial offsets of the producer's fold (ssa_aggregates_many) from the counts alone: out[0] = the partials in
+// all, out[1 .. k + 2) = pfirst.  Returns the k + 2 words it takes (out receives them only if out_words is enough).
+extern "C" int64_t ssa_debug_aggregates_fold_plan(const uint64_t *counts, size_t k, uint64_t *out, size_t out_words) {
+    if ((k && !counts) || k > SSA_MAX_BATCH) return SSA_ERR_ARG;
+    AgPlan pl;
+    if (int rc = ag_plan(counts, k, SSA_MAX_BATCH, 0, pl)) return rc;
+    if (out && out_words >= k + 2) {
+        out[0] = pl.pfirst[k];
+        for (size_t j = 0; j <= k; j++) out[1 + j] = pl.pfirst[j];
+    }
+    return (int64_t)(k + 2);
 }
 
 // tests: the coefficients of all N lanes as ssa_verify_aggregates_many derives them -> N x 16 bytes

@@ -186,6 +186,9 @@ struct CtxKnobs {
        inputs (R's, keys, flags, challenge scalars, coefficients) and its bytes (mask, re-check marks, segment verdicts, \
        right-hand scalars) */ \
     X(agm_plan) X(agm_map) X(agm_roots) X(agm_in) X(agm_bytes) \
+    /* the producer of many aggregates: per aggregate its failing lanes and 256 - their smallest \
+       nonzero status, and the results when the caller takes none */ \
+    X(agp_acc) \
     /* filtering half-aggregation: per-workgroup counts and offsets of the kept lanes (the \
        length of the list behind them), and the kept lanes' signatures and raw digests side by side */ \
     X(av_blk) X(av_sigs) X(av_dig) \

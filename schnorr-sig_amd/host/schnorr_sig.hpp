@@ -655,6 +655,38 @@ struct AggregateSignature {
                                                               bool check = true) {
         return aggregate(cx, signatures, public_keys, messages, check, true);
     }
+    // Many aggregates from one call (ssa_aggregates_many): the triples of all slices in order,
+    // counts[j] of them for aggregate j.  Element j is what aggregate() gives slice j alone, byte for byte, and nullopt
+    // where it would refuse (also where it would throw Panic: nothing is thrown for one slice among many); *results_out
+    // (optional) receives the k statuses -- SSA_OK, SSA_MALFORMED or, with check, the smallest nonzero status of the
+    // slice's signatures.
+    static std::vector<std::optional<AggregateSignature>>
+    aggregate_many(Context &cx, const std::vector<uint64_t> &counts, const std::vector<Signature> &signatures,
+                   const std::vector<PublicKey> &public_keys, const std::vector<std::pair<const uint8_t *, size_t>> &messages,
+                   bool check = true, std::vector<uint32_t> *results_out = nullptr) {
+        const PackedTriples t = pack_triples(signatures, public_keys, messages);
+        const size_t n = signatures.size(), k = counts.size();
+        size_t total = 0;
+        for (uint64_t c : counts) total += c;
+        if (total != n) throw Panic("We should have the same number of signatures than the counts say");
+        std::vector<std::optional<AggregateSignature>> out(k);
+        std::vector<uint32_t> results(k, SSA_MALFORMED);
+        if (k) {
+            std::vector<uint8_t> wire(49 * n + 32 * k, 0);
+            const int rc = ssa_aggregates_many(cx.get(), t.sigs.data(), counts.data(), k, t.pks.data(), t.inf.data(),
+                                               t.flat.data(), t.off.data(), 0, 0, check ? SSA_AGG_CHECK : 0u, wire.data(),
+                                               results.data(), nullptr, nullptr);
+            if (rc != 0) throw std::runtime_error(std::string("ssa_aggregates_many: ") + ssa_strerror(rc));
+            size_t lo = 0;
+            for (size_t j = 0; j < k; lo += SSA_AGGREGATE_LENGTH(counts[j]), j++) {
+                if (results[j] != SSA_OK) continue;
+                out[j].emplace();
+                out[j]->bytes.assign(wire.begin() + lo, wire.begin() + lo + SSA_AGGREGATE_LENGTH(counts[j]));
+            }
+        }
+        if (results_out) *results_out = std::move(results);
+        return out;
+    }
     // Filtering half-aggregation: the aggregate of exactly the triples that verify under
     // verify_batch semantics, and their indices in ascending order.  A triple that does not verify is dropped, not
     // reported as an error; with none kept the aggregate is the empty one (32 zero bytes).

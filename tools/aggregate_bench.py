@@ -63,7 +63,15 @@ alternating in the same way, every timed output checked (kept count and list, ag
 device buffers, legs alternating: verify_sliced / verify_baseline, aggregate_sliced / aggregate_baseline, and this tree's own
 single calls.  Up to one MSM slice the routes differ in the tree alone (flat ag_k_level launches against ag_k_tree); above
 it (n a multiple of 2^20, 2^20 distinct lanes repeated) only the sliced legs run.  --multi adds MultiEngine([0, 0]) from
-host buffers beside this tree's host forms: two contexts on ONE device, which says nothing about scaling."""
+host buffers beside this tree's host forms: two contexts on ONE device, which says nothing about scaling.
+
+--produce-many [KxS] measures the producer of many aggregates (ssa_aggregates_many_device): K batches
+of S signatures (4096 x 256) with 80-byte messages, device buffers, legs alternating in one process:
+  many            ONE ssa_aggregates_many_device call over the K x S lanes
+  loop_baseline   K ssa_aggregate_many_device calls through --baseline-lib (a build of the parent commit, which has no other
+                  way; without it, this tree's own library)
+  single          the same lanes as ONE aggregate through this tree's ssa_aggregate_many_device (recorded, no bar)
+Every timed output is compared with the aggregates of the single call, batch by batch, made once before the rounds."""
 import argparse
 import hashlib
 import json
@@ -242,6 +250,112 @@ def many_main(a):
         e.close()
     if base:
         base.close()
+    return 0 if res["mismatches"] == 0 else 1
+
+
+PRODUCE_KERNELS = ("ag_k_lane_map", "ssa_k_hash", "ag_k_leaf", "ag_k_tree", "ag_k_coeff", "ag_k_fold_seg",
+                   "ag_k_fold_finish_seg", "ag_k_pack_many", "ag_k_fold")
+
+
+def produce_many_main(a):
+    import torch
+    import schnorr_sig_amd as ssa
+    dev = torch.device("cuda", 0)
+    k, s = (int(v) for v in a.produce_many.lower().split("x"))
+    n = k * s
+    sha = lambda path: hashlib.sha256(open(path, "rb").read()).hexdigest()[:16]   # noqa: E731
+    base_path = a.baseline_lib or ssa.LIB_PATH
+    eng = ssa.Engine(0)
+    base = BaselineAggregate(base_path)
+    rng = np.random.default_rng(a.seed)
+    msgs = rng.integers(0, 256, (n, 80), dtype=np.uint8)
+    pks, sigs = eng.keygen_sign_many(_scalars(rng, n), _scalars(rng, n), msgs)
+    t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)   # noqa: E731
+    d_sigs, d_pks, d_msgs = t(sigs), t(pks), t(msgs)
+    counts = [s] * k
+    wire = 49 * n + 32 * k
+    d_ref, d_out = (torch.zeros(wire, dtype=torch.uint8, device=dev) for _ in range(2))
+    d_one, d_one0 = (torch.zeros(49 * n + 32, dtype=torch.uint8, device=dev) for _ in range(2))
+    d_res = torch.full((k,), 255, dtype=torch.int32, device=dev)
+    d_status = torch.zeros(n, dtype=torch.uint8, device=dev)
+    d_nfail = torch.zeros(1, dtype=torch.int64, device=dev)
+    torch.cuda.synchronize()
+    res = {"metric": "aggregates_produce_many", "aggregates": k, "signatures_each": s, "lanes": n, "msg_len": 80,
+           "rounds": a.rounds, "warmup": a.warmup, "library_sha256": sha(ssa.LIB_PATH), "baseline_sha256": sha(base_path),
+           "baseline_is_this_tree": not a.baseline_lib, "device": torch.cuda.get_device_name(0),
+           "date": time.strftime("%Y-%m-%d"), "mismatches": 0}
+
+    def loop(aggregate, out):
+        def run():
+            for j in range(k):
+                lo = j * s
+                if aggregate(d_sigs.data_ptr() + 81 * lo, d_pks.data_ptr() + 96 * lo, d_msgs.data_ptr() + 80 * lo, s,
+                             out.data_ptr() + 49 * lo + 32 * j) != 0:
+                    res["mismatches"] += 1
+        return run
+
+    def many():
+        eng.aggregates_device(d_sigs, counts, d_pks, d_msgs, d_aggs=d_out, d_results=d_res, d_status=d_status, d_nfail=d_nfail)
+
+    def single(out):
+        return lambda: eng.aggregate_device(d_sigs.data_ptr(), d_pks.data_ptr(), d_msgs.data_ptr(), n, 80, out.data_ptr())
+
+    # the reference of every check: this tree's single call, batch by batch; and the N lanes as one aggregate
+    loop(lambda sg, pk, ms, cnt, out: eng.aggregate_device(sg, pk, ms, cnt, 80, out), d_ref)()
+    single_ok = n <= eng.info()["msm_slice"]
+    if single_ok and single(d_one0)() != 0:
+        res["mismatches"] += 1
+    eng.sync()
+
+    def wall(fn, sync):
+        sync()
+        t0 = time.perf_counter()
+        fn()
+        sync()
+        return (time.perf_counter() - t0) * 1e3
+
+    legs = {"many": (many, eng.sync, d_out, d_ref),
+            "loop_baseline": (loop(lambda sg, pk, ms, cnt, out: base.aggregate(sg, pk, ms, cnt, out, False), d_out), base.sync,
+                              d_out, d_ref)}
+    if single_ok:
+        legs["single"] = (single(d_one), eng.sync, d_one, d_one0)
+    times = {leg: [] for leg in legs}
+    for rnd in range(a.warmup + a.rounds):
+        for leg, (fn, sync, out, want) in legs.items():
+            out.fill_(255)
+            d_res.fill_(255)
+            torch.cuda.synchronize()
+            ms = wall(fn, sync)
+            if not bool((out == want).all()) or (leg == "many" and (bool((d_res != 0).any()) or int(d_nfail.item()) != 0)):
+                res["mismatches"] += 1
+            if rnd >= a.warmup:
+                times[leg].append(ms)
+    res["ms_rounds"] = {leg: [round(v, 3) for v in vs] for leg, vs in times.items()}
+    res["ms_median"] = {leg: round(float(np.median(v)), 3) for leg, v in times.items()}
+    res["ms_min"] = {leg: round(float(np.min(v)), 3) for leg, v in times.items()}
+    med = res["ms_median"]
+    res["ratio"] = {"loop_baseline/many": round(med["loop_baseline"] / med["many"], 3)}
+    if single_ok:
+        res["ratio"]["many/single"] = round(med["many"] / med["single"], 3)
+    res["msigs_per_s"] = {leg: round(n / v / 1e3, 3) for leg, v in med.items()}
+    kern = {}
+    for name, fn in (("many", many),) + ((("single", single(d_one)),) if single_ok else ()):
+        eng.sync()
+        eng.enable_timing(True)
+        fn()
+        eng.sync()
+        kern[name] = {}
+        for kn in PRODUCE_KERNELS:
+            avg, cnt = eng.read_timing(kn)
+            if cnt:
+                kern[name][kn] = [round(avg, 4), int(cnt)]
+        eng.enable_timing(False)
+    res["kernel_ms_avg_launches"] = kern
+    total, _ = ssa.debug_aggregates_fold_plan(counts)
+    res["plan"] = {"partials": total, "tree_passes": len(ssa.debug_aggregates_plan(counts)["passes"])}
+    print(json.dumps(res))
+    eng.close()
+    base.close()
     return 0 if res["mismatches"] == 0 else 1
 
 
@@ -892,7 +1006,12 @@ def main():
                     help="ssa_aggregate_many_sliced_device / ssa_verify_aggregate_sliced_device against the single calls of "
                          "--baseline-lib")
     ap.add_argument("--multi", action="store_true", help="--sharded: also MultiEngine([0, 0]) from host buffers")
+    ap.add_argument("--produce-many", nargs="?", const="4096x256", default=None, metavar="KxS",
+                    help="ssa_aggregates_many_device over K batches of S signatures against K ssa_aggregate_many_device "
+                         "calls of --baseline-lib")
     a = ap.parse_args()
+    if a.produce_many:
+        return produce_many_main(a)
     if a.sharded:
         return sharded_main(a)
     if a.valid_cached:
