@@ -1197,6 +1197,59 @@ int ssa_aggregate_valid_keyed_many_cached_device(ssa_ctx *ctx, ssa_keycache *kc,
                                                  uint64_t *n_kept_out, uint8_t *d_status_out, uint8_t *d_keys49_out,
                                                  uint64_t stats_out[12]);
 
+/* ---- streaming aggregator: push signatures as they arrive, finish at block time ----------
+ * Every producer call above takes the whole batch when the block is closed.  A block producer receives its signatures
+ * over the whole slot; only the coefficients have to wait for block time, because they need the root and the root needs
+ * every leaf.  An ssa_aggregator holds, on the device and in arrival order, the lanes admitted so far -- their R's in the
+ * aggregate's wire layout, their scalars, their leaves and the top of every complete block of block_lanes leaves -- so
+ * that the challenge hash, the admission check, the leaves and most of the tree are paid on arrival, and block time pays
+ * one permutation, one multiplication and a sum per lane.  It belongs to the context it was created on, like a key cache.
+ *   create   capacity: 1 .. SSA_MAX_BATCH lanes; block_lanes: 0 (the default, 512) or a power of two from 2 to 512 (small
+ *            values let tests reach every path of the tree at a few thousand lanes); flags: 0.  Anything else:
+ *            SSA_ERR_ARG.  All device memory is allocated here -- 49 capacity + 32 bytes of R's, 32 bytes of scalar and 32
+ *            bytes of leaf per lane, 32 bytes per block: about 113 bytes per lane -- and is the object's own: destroy
+ *            releases it, or ssa_ctx_destroy (the handle then stays valid for destroy and is refused everywhere else).
+ *   push     the arguments of ssa_aggregate_valid_many.  Let S be the status vector: with flags == 0 the one
+ *            ssa_verify_batch_screened (library-drawn coefficients) gives THIS batch alone, with its guarantee and its
+ *            exact path for small batches; with SSA_AGGR_NO_SCREEN, S[i] is 0 or SSA_MALFORMED by exactly the checks
+ *            ssa_aggregate_many makes without SSA_AGG_CHECK (e < q, canonical limbs, key on the curve, R decodable) -- for
+ *            a producer that made the signatures itself.  The lanes with S[i] == 0 are appended in lane order;
+ *            status_out (may be NULL) = S, *n_kept_out (HOST memory in both forms) = their number.  A dropped lane is a
+ *            result: the return value reports errors only.  SSA_ERR_ARG: a context other than the object's, an unknown
+ *            flag, n above the context's MSM slice, or n > capacity - held -- by n, not by the kept count, so that a push
+ *            is never applied in part; the object is then unchanged.  n == 0: SSA_OK.  The same signature pushed twice
+ *            is held twice.  Every message is hashed ONCE.  The _device form synchronises the context's stream as
+ *            ssa_aggregate_valid_many_device does: once inside the screen (never with SSA_AGGR_NO_SCREEN) and once for
+ *            the kept count, which the object keeps on the host from then on.
+ *   finish   writes SSA_AGGREGATE_LENGTH(n_take) bytes: byte for byte what ssa_aggregate_many (flags 0) returns for the
+ *            first n_take admitted lanes handed in alone in that order.  n_take == SIZE_MAX: all lanes held;
+ *            n_take > held: SSA_ERR_ARG; n_take == 0: 32 zero bytes.  n_take is the block-size limit: a producer whose
+ *            pool exceeds the block takes a prefix.  finish changes NO state of the object but a counter: it may be
+ *            repeated, called with another n_take, and followed by more pushes.  The _device form only enqueues.
+ *   reset    empties the object (counters included) and keeps its memory.
+ *   info     [0] lanes held  [1] capacity  [2] block_lanes  [3] pushes  [4] lanes offered  [5] lanes dropped
+ *            [6] blocks whose top is stored  [7] finishes.
+ * NOT here: removing the lanes a block took from the front (the rest changes place: reset and push it again), the
+ * validator's counterpart, admission through a key cache, ssa_multi forms. */
+typedef struct ssa_aggregator ssa_aggregator;
+#define SSA_AGGR_NO_SCREEN 1u      /* push flag */
+int ssa_aggregator_create(ssa_ctx *ctx, size_t capacity, size_t block_lanes, uint32_t flags, ssa_aggregator **out);
+void ssa_aggregator_destroy(ssa_aggregator *ag);
+int ssa_aggregator_reset(ssa_aggregator *ag);
+int ssa_aggregator_info(ssa_aggregator *ag, uint64_t out[8]);
+int ssa_aggregator_push(ssa_ctx *ctx, ssa_aggregator *ag, const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_inf,
+                        const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len, size_t n,
+                        uint32_t flags, uint8_t *status_out, uint64_t *n_kept_out);
+int ssa_aggregator_push_device(ssa_ctx *ctx, ssa_aggregator *ag, const uint8_t *d_sigs, const uint8_t *d_pks,
+                               const uint8_t *d_pk_inf, const uint8_t *d_msgs, const uint64_t *d_msg_off, size_t msg_stride,
+                               size_t msg_len, size_t n, uint32_t flags, uint8_t *d_status_out, uint64_t *n_kept_out);
+int ssa_aggregator_finish(ssa_ctx *ctx, ssa_aggregator *ag, size_t n_take, uint8_t *agg_out);
+int ssa_aggregator_finish_device(ssa_ctx *ctx, ssa_aggregator *ag, size_t n_take, uint8_t *d_agg_out);
+/* tests: what a push of m kept lanes onto `held` lanes completes with blocks of block_lanes (0: 512) lanes (host code, no
+ * device): out[0] the first completed block, out[1] the number of completed blocks, out[2] the first lane of the ragged
+ * tail, out[3] its length.  SSA_ERR_ARG for a block size create would refuse or held + m above SSA_MAX_BATCH. */
+int ssa_debug_aggregator_plan(uint64_t held, uint64_t m, uint64_t block_lanes, uint64_t out[4]);
+
 /* ---- ABI version -------------------------------------------------------------------------------------------
  * Bumped whenever an exported signature changes (round 2 inserted pk_inf into the batch entry points under the same
  * symbol names: a shim built against the older header would still link and pass msgs as pk_inf).  A binding checks

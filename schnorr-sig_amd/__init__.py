@@ -292,6 +292,15 @@ def _load():
         "ssa_verify_aggregates_many_cached_device": (i32, [vp, vp, vp, u64p, sz, vp, vp, vp, vp, sz, sz, vp, vp]),
         "ssa_verify_aggregates_many_cached_wire": (i32, [vp, vp, vp, u64p, sz, vp, vp, vp, sz, sz, vp, vp]),
         "ssa_verify_aggregates_many_cached_wire_device": (i32, [vp, vp, vp, u64p, sz, vp, vp, vp, sz, sz, vp, vp]),
+        "ssa_aggregator_create": (i32, [vp, sz, sz, u32, C.POINTER(vp)]),
+        "ssa_aggregator_destroy": (None, [vp]),
+        "ssa_aggregator_reset": (i32, [vp]),
+        "ssa_aggregator_info": (i32, [vp, u64p]),
+        "ssa_aggregator_push": (i32, [vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, u32, vp, u64p]),
+        "ssa_aggregator_push_device": (i32, [vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, u32, vp, u64p]),
+        "ssa_aggregator_finish": (i32, [vp, vp, sz, vp]),
+        "ssa_aggregator_finish_device": (i32, [vp, vp, sz, vp]),
+        "ssa_debug_aggregator_plan": (i32, [C.c_uint64, C.c_uint64, C.c_uint64, u64p]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)      # AttributeError here == ABI symbol missing: fail loudly
@@ -576,6 +585,15 @@ class Engine:
                 cache.close()
                 raise
         return cache
+
+    def aggregator(self, capacity, block_lanes=0):
+        """a streaming aggregator of `capacity` lanes on this engine's device: push signatures
+        as they arrive, finish at block time.  All of its device memory, about 113 bytes per lane, is allocated here.
+        block_lanes: 0 (512) or a power of two from 2 to 512."""
+        h = C.c_void_p()
+        _check(_lib.ssa_aggregator_create(self._ctx, int(capacity), int(block_lanes), 0, C.byref(h)),
+               "ssa_aggregator_create")
+        return Aggregator(self, h)
 
     def verify_keyed_many_cached(self, cache, keyed, msgs, offsets=None, check_torsion=True, sig_flag_byte=False,
                                  coeffs=None):
@@ -1720,6 +1738,117 @@ class KeyCache(_KeyTables):
     def close(self):
         if self.handle:
             _lib.ssa_keycache_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+AGGR_NO_SCREEN = 1    # SSA_AGGR_NO_SCREEN
+AGGREGATOR_FIELDS = ("held", "capacity", "block_lanes", "pushes", "offered", "dropped", "blocks", "finishes")
+AGGREGATOR_ALL = (1 << (8 * C.sizeof(C.c_size_t))) - 1      # SIZE_MAX: finish every lane held
+
+
+def aggregator_plan(held, m, block_lanes=0):
+    """tests: (first completed block, completed blocks, first lane of the ragged tail, its length) of a push of m kept
+    lanes onto `held` lanes (ssa_debug_aggregator_plan: host code, no device)"""
+    out = (C.c_uint64 * 4)()
+    _check(_lib.ssa_debug_aggregator_plan(int(held), int(m), int(block_lanes), out), "ssa_debug_aggregator_plan")
+    return tuple(int(v) for v in out)
+
+
+class Aggregator:
+    """ssa_aggregator handle (Engine.aggregator): the lanes admitted so far, on the device, in
+    arrival order.  push() admits a batch on arrival; finish() gives the AggregateSignature of the first n_take held
+    lanes -- what Engine.aggregate gives those lanes handed in alone -- and changes nothing.  Tied to its Engine like
+    KeyCache; destroyed exactly once (close(), the end of a `with` block, or when the object goes away)."""
+
+    def __init__(self, engine, handle):
+        self.engine = engine      # keeps the context alive
+        self.handle = handle
+
+    def info(self):
+        """the AGGREGATOR_FIELDS by name"""
+        out = (C.c_uint64 * 8)()
+        _check(_lib.ssa_aggregator_info(self.handle, out), "ssa_aggregator_info")
+        return dict(zip(AGGREGATOR_FIELDS, (int(v) for v in out)))
+
+    def __len__(self):
+        return self.info()["held"]
+
+    def push(self, sigs, pks, msgs, pk_inf=None, screen=True, offsets=None, engine=None):
+        """a batch of signatures, keys and messages as Engine.aggregate_valid takes them -> (status uint8[n], n_kept):
+        the lanes whose status is zero are appended in lane order.  screen=True: the statuses of
+        Engine.verify_batch_screened on this batch alone; screen=False (SSA_AGGR_NO_SCREEN): 0 or MALFORMED by the checks
+        of Engine.aggregate(check=False), for a producer that made the signatures itself.  A batch that does not fit
+        what is left of the capacity raises and changes nothing.  engine: tests (a context other than the object's)."""
+        eng = engine or self.engine
+        n, batch, keep = eng._agg_batch(sigs, 81, pks, msgs, offsets, pk_inf)
+        status = np.full(n, 255, dtype=np.uint8)
+        n_kept = C.c_uint64(0)
+        _check(_lib.ssa_aggregator_push(eng._ctx, self.handle, *batch, 0 if screen else AGGR_NO_SCREEN,
+                                        _ptr(status) if n else None, C.byref(n_kept)), "ssa_aggregator_push")
+        return status, int(n_kept.value)
+
+    def push_device(self, d_sigs, d_pks, d_msgs, d_status=None, d_pk_inf=None, d_offsets=None, msg_len=None,
+                    msg_stride=None, screen=True):
+        """device form over torch tensors on the engine's device: d_sigs (n, 81), d_pks (n, 96), d_msgs an (n, len) uint8
+        tensor (or flat bytes with a uint64-valued d_offsets and msg_len left None); the statuses land in d_status
+        (uint8[n]) when it is given.  Synchronises the stream (inside the screen, and for the kept count) -> n_kept."""
+        n = int(d_pks.shape[0])
+        if d_offsets is None and msg_len is None:
+            msg_len = d_msgs.shape[1] if d_msgs.dim() == 2 else 0
+        msg_len = msg_len or 0
+        addr = lambda t: t.data_ptr() if t is not None and t.numel() else None    # noqa: E731
+        n_kept = C.c_uint64(0)
+        _check(_lib.ssa_aggregator_push_device(
+            self.engine._ctx, self.handle, addr(d_sigs), addr(d_pks), addr(d_pk_inf), addr(d_msgs), addr(d_offsets),
+            msg_stride if msg_stride is not None else msg_len, msg_len, n, 0 if screen else AGGR_NO_SCREEN,
+            addr(d_status), C.byref(n_kept)), "ssa_aggregator_push_device")
+        return int(n_kept.value)
+
+    def finish_bytes(self, n_take=None):
+        """the aggregate of the first n_take held lanes (None: all) as a uint8[49 n + 32] array"""
+        held = self.info()["held"]
+        n = held if n_take is None else int(n_take)
+        agg = np.full(49 * min(n, held) + 32, 255, dtype=np.uint8)
+        _check(_lib.ssa_aggregator_finish(self.engine._ctx, self.handle, AGGREGATOR_ALL if n_take is None else n,
+                                          _ptr(agg)), "ssa_aggregator_finish")
+        return agg
+
+    def finish(self, n_take=None):
+        """-> the AggregateSignature of the first n_take held lanes (None: all of them; the block-size limit of a
+        producer whose pool exceeds the block).  Changes no state: it may be repeated, called with another n_take, and
+        followed by more pushes.  n_take above the lanes held raises."""
+        return AggregateSignature(self.finish_bytes(n_take).tobytes())
+
+    def finish_device(self, d_agg, n_take=None):
+        """device form: only enqueues on the engine's stream; the 49 n + 32 bytes land in the uint8 tensor d_agg (any
+        byte alignment), n = n_take or all lanes held.  Returns n."""
+        n = self.info()["held"] if n_take is None else int(n_take)
+        if d_agg.numel() < 49 * n + 32:
+            raise ValueError("an aggregate of %d signatures is %d bytes" % (n, 49 * n + 32))
+        _check(_lib.ssa_aggregator_finish_device(self.engine._ctx, self.handle, n, d_agg.data_ptr()),
+               "ssa_aggregator_finish_device")
+        return n
+
+    def reset(self):
+        """forget every lane and restart the counters; the memory stays"""
+        _check(_lib.ssa_aggregator_reset(self.handle), "ssa_aggregator_reset")
+
+    def close(self):
+        if self.handle:
+            _lib.ssa_aggregator_destroy(self.handle)
             self.handle = C.c_void_p()
 
     def __enter__(self):

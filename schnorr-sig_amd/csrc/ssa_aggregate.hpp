@@ -50,6 +50,9 @@
 // signatures themselves, then ag_k_fold_seg (one lane per signature over the dense lanes, a segmented sum per workgroup,
 // one partial per workgroup and aggregate), ag_k_fold_finish_seg (one wave per aggregate: its scalar and its refusal,
 // decided on the device) and ag_k_pack_many (the R's into the wire form ssa_verify_aggregates_many reads).
+//
+// The streaming aggregator (ssa_aggregator.hpp) does the work in front of the coefficients when the
+// lanes arrive and shares the per-lane bodies here: ag_leaf_hash, ag_lane_ok, ag_coeff_of_digest, ag_block_sum.
 #pragma once
 #include <vector>
 #include "ssa_kernels.hpp"
@@ -198,6 +201,18 @@ ag_k_pack(const u8 *__restrict__ sigs, size_t n, u8 *__restrict__ agg_out) {
     }
 }
 
+// leaf_i = H(d_i || flag byte of R_i || 0xA1): dig the raw digests (four words per lane), sigs the lanes at stride 81
+SSA_DEV void ag_leaf_hash(u64 *A, const DevParams *__restrict__ prm, const u64 *__restrict__ dig, const u8 *__restrict__ sigs,
+                          size_t i, u64 (&d)[4]) {
+    u64 in[8];
+#pragma unroll
+    for (int k = 0; k < 4; k++) in[k] = dig[4 * i + k];
+    in[4] = (u64)sigs[81 * i + 48];
+    in[5] = AG_TAG_LEAF;
+    in[6] = in[7] = 0;
+    ag_hash8(A, prm, in, 6u, d);
+}
+
 __global__ void __launch_bounds__(256, 4)
 ag_k_leaf(const DevParams *__restrict__ prm, const u64 *__restrict__ dig, const u8 *__restrict__ sigs, size_t n,
           u64 *__restrict__ nodes) {
@@ -205,13 +220,8 @@ ag_k_leaf(const DevParams *__restrict__ prm, const u64 *__restrict__ dig, const 
     u64 *A = lds + threadIdx.x;
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    u64 in[8], d[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) in[k] = dig[4 * i + k];
-    in[4] = (u64)sigs[81 * i + 48];
-    in[5] = AG_TAG_LEAF;
-    in[6] = in[7] = 0;
-    ag_hash8(A, prm, in, 6u, d);
+    u64 d[4];
+    ag_leaf_hash(A, prm, dig, sigs, i, d);
 #pragma unroll
     for (int k = 0; k < 4; k++) nodes[4 * i + k] = d[k];
 }
@@ -322,6 +332,15 @@ ag_k_lane_map(const u32 *__restrict__ first, u32 k, size_t n, u32 *__restrict__ 
     map[i] = lo;
 }
 
+// (lo, hi) = the coefficient out of the digest d = H(root || index || 0xA3): the first 16 bytes of Digest::to_bytes,
+// little-endian, masked to 126 bits; 0 becomes 1.  The one place where the mask and the 0 -> 1 rule stand: ag_k_coeff
+// writes the pair out, agx_k_coeff_fold (ssa_aggregator.hpp) multiplies by it.
+SSA_DEV void ag_coeff_of_digest(const u64 (&d)[4], u64 &lo, u64 &hi) {
+    lo = d[0];
+    hi = d[1] & AG_COEFF_HI_MASK;
+    if ((lo | hi) == 0) lo = 1;
+}
+
 // a_i = H(root_j || i - first_j || 0xA3) with the root and the index of the lane's own aggregate j = map[i]; map and
 // first == nullptr: one aggregate, root 0 and index lane0 + i -- lane0 is the place of the launch's first lane in its
 // aggregate: 0 but for a shard of a larger aggregate
@@ -340,10 +359,8 @@ ag_k_coeff(const DevParams *__restrict__ prm, const u64 *__restrict__ roots, con
     in[5] = AG_TAG_COEFF;
     in[6] = in[7] = 0;
     ag_hash8(A, prm, in, 6u, d);
-    // the first 16 bytes of Digest::to_bytes, little-endian, masked to 126 bits; 0 becomes 1
-    u64 lo = d[0];
-    const u64 hi = d[1] & AG_COEFF_HI_MASK;
-    if ((lo | hi) == 0) lo = 1;
+    u64 lo, hi;
+    ag_coeff_of_digest(d, lo, hi);
     reinterpret_cast<ulonglong2 *>(coeffs)[i] = make_ulonglong2(lo, hi);
 }
 
@@ -369,11 +386,11 @@ SSA_DEV void ag_block_sum(u64 *red, const sc256 &v) {
     }
 }
 
-// Lane i of a fold: ae = a_i e_i mod q when the lane passes, else it stays as it came (zero).  e < q is checked always;
-// check: the other checks of msm_k_prepare too (canonical limbs, key on the curve, R decodable).  Returns "passed".
-SSA_DEV bool ag_fold_lane(const u8 *__restrict__ sigs, const u8 *__restrict__ pks, const u8 *__restrict__ pk_inf,
-                          const u64 *__restrict__ coeffs, size_t i, bool check, sc256 &ae) {
-    const sc256 e = ld_sc(sigs + 81 * i + 49);
+// The checks a fold makes of lane i, and its scalar e: e < q always; check: the other checks of msm_k_prepare too
+// (canonical limbs, key on the curve, R decodable).  Returns "passed".
+SSA_DEV bool ag_lane_ok(const u8 *__restrict__ sigs, const u8 *__restrict__ pks, const u8 *__restrict__ pk_inf, size_t i,
+                        bool check, sc256 &e) {
+    e = ld_sc(sigs + 81 * i + 49);
     bool ok = !sc_geq_q(e);
     if (check) {
         aff P;
@@ -384,6 +401,15 @@ SSA_DEV bool ag_fold_lane(const u8 *__restrict__ sigs, const u8 *__restrict__ pk
         bool r_inf = false;
         if (ok) ok = decompress_lane(sigs + 81 * i, R, r_inf) == 0;
     }
+    return ok;
+}
+
+// Lane i of a fold: ae = a_i e_i mod q when the lane passes, else it stays as it came (zero).  e < q is checked always;
+// check: the other checks of msm_k_prepare too (canonical limbs, key on the curve, R decodable).  Returns "passed".
+SSA_DEV bool ag_fold_lane(const u8 *__restrict__ sigs, const u8 *__restrict__ pks, const u8 *__restrict__ pk_inf,
+                          const u64 *__restrict__ coeffs, size_t i, bool check, sc256 &ae) {
+    sc256 e;
+    const bool ok = ag_lane_ok(sigs, pks, pk_inf, i, check, e);
     if (ok) {
         sc256 a;
         a.w[0] = coeffs[2 * i];

@@ -7,6 +7,7 @@
 #include "ssa_keyed.hpp"
 #include "ssa_aggregate.hpp"
 #include "ssa_aggcache.hpp"
+#include "ssa_aggregator.hpp"
 
 #include <sys/random.h>
 
@@ -365,6 +366,7 @@ extern "C" void ssa_ctx_destroy(ssa_ctx *ctx) {
     orphan_handles(ctx->keysets, [](ssa_keyset *ks) { ks->release_all(); });
     orphan_handles(ctx->signer_sets, [](ssa_signer_set *ss) { ss->wipe_release(); });
     orphan_handles(ctx->keycaches, [](ssa_keycache *kc) { kc->release_all(); });
+    orphan_handles(ctx->aggregators, [](ssa_aggregator *ag) { ag->release_all(); });
     for (auto &kv : ctx->timed)
         for (auto &t : kv.second) {
             (void)hipEventDestroy(t.start);
@@ -2545,6 +2547,247 @@ extern "C" int ssa_verify_aggregate_sliced(ssa_ctx *ctx, const uint8_t *agg, con
     return verify_aggregate_host(ctx, agg, pks, pk_inf, msgs, msg_off, msg_stride, msg_len, n, true);
 }
 
+// ------------------------------------------------------------------ streaming aggregator (ssa_aggregator.hpp)
+extern "C" int ssa_debug_aggregator_plan(uint64_t held, uint64_t m, uint64_t block_lanes, uint64_t out[4]) {
+    const uint64_t B = block_lanes ? block_lanes : AG_TREE_SPAN;
+    if (!out || !is_pow2((size_t)B) || B < 2 || B > AG_TREE_SPAN || held > SSA_MAX_BATCH || m > SSA_MAX_BATCH - held)
+        return SSA_ERR_ARG;
+    const AgxPlan p = agx_plan(held, m, B);
+    out[0] = p.first;
+    out[1] = p.count;
+    out[2] = p.tail_first;
+    out[3] = p.tail_len;
+    return 0;
+}
+
+extern "C" int ssa_aggregator_create(ssa_ctx *ctx, size_t capacity, size_t block_lanes, uint32_t flags, ssa_aggregator **out) {
+    if (out) *out = nullptr;
+    const size_t B = block_lanes ? block_lanes : AG_TREE_SPAN;
+    if (!ctx || !out || flags != 0 || capacity == 0 || capacity > SSA_MAX_BATCH || !is_pow2(B) || B < 2 || B > AG_TREE_SPAN)
+        return SSA_ERR_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    ssa_aggregator *ag = new ssa_aggregator();
+    ag->ctx = ctx;
+    ag->capacity = capacity;
+    ag->block = B;
+    // everything the object will ever hold, now: no push or finish allocates for it
+    if (ag->wire.reserve_exact(49 * capacity + 32) || ag->scal.reserve_exact(32 * capacity) ||
+        ag->leaves.reserve_exact(32 * capacity) || ag->tops.reserve_exact(32 * ((capacity + B - 1) / B))) {
+        (void)hipGetLastError();
+        ag->release_all();
+        delete ag;
+        return SSA_ERR_HIP;
+    }
+    ctx->aggregators.push_back(ag);
+    *out = ag;
+    return 0;
+}
+
+extern "C" void ssa_aggregator_destroy(ssa_aggregator *ag) {
+    if (!ag) return;
+    if (ag->ctx) {
+        (void)hipSetDevice(ag->ctx->device);
+        (void)hipStreamSynchronize(ag->ctx->stream);
+        forget_handle(ag->ctx->aggregators, ag);
+        ag->release_all();
+    }
+    delete ag;
+}
+
+// Nothing on the device needs clearing: every array is written before it is read, up to `held`.
+extern "C" int ssa_aggregator_reset(ssa_aggregator *ag) {
+    if (!ag || !ag->ctx) return SSA_ERR_ARG;
+    ag->held = 0;
+    ag->pushes = ag->offered = ag->dropped = ag->finishes = 0;
+    return 0;
+}
+
+extern "C" int ssa_aggregator_info(ssa_aggregator *ag, uint64_t out[8]) {
+    if (!ag || !ag->ctx || !out) return SSA_ERR_ARG;
+    out[0] = ag->held;
+    out[1] = ag->capacity;
+    out[2] = ag->block;
+    out[3] = ag->pushes;
+    out[4] = ag->offered;
+    out[5] = ag->dropped;
+    out[6] = ag->held / ag->block;
+    out[7] = ag->finishes;
+    return 0;
+}
+
+// what both forms of push refuse before anything is enqueued or counted
+static int agx_push_args(const ssa_ctx *ctx, const ssa_aggregator *ag, const MsgView &mv, size_t n, uint32_t flags,
+                         const void *sigs, const void *pks, const uint64_t *n_kept_out) {
+    if (!ctx || !ag || ag->ctx != ctx || !n_kept_out || (flags & ~SSA_AGGR_NO_SCREEN) || (n && (!sigs || !pks)))
+        return SSA_ERR_ARG;
+    if (int rc = agg_check_args(ctx, mv, n)) return rc;
+    return n > ag->capacity - ag->held ? SSA_ERR_ARG : 0;      // by n, not by the kept count: never applied in part
+}
+
+// The blocks [first, first + count) of the object, complete since this push, reduced to their tops.  B = 512: ONE launch
+// of ag_k_tree over that range of the leaves, a workgroup per block (the uniform cut, no top).  Smaller B: log2 B launches
+// of ag_k_level over the count * B leaves -- every level is even, no node moves up unchanged -- between ctx->ag_nodes and
+// ctx->ag_nodes2; the first reads the object's leaves, the last writes the object's tops.
+static int agx_reduce_blocks(ssa_ctx *ctx, ssa_aggregator *ag, const AgxPlan &p) {
+    const size_t B = ag->block, cnt = (size_t)p.count * B;
+    const u64 *src = (const u64 *)ag->leaves.p + 4 * (size_t)p.first * B;
+    u64 *dst = (u64 *)ag->tops.p + 4 * (size_t)p.first;
+    if (B == AG_TREE_SPAN)
+        return timed_launch(ctx, "ag_k_tree", [&] {
+            hipLaunchKernelGGL(ag_k_tree, dim3((unsigned)p.count), dim3(256), 0, ctx->stream, ctx->d_params, src,
+                               (const AgTreeDesc *)nullptr, (u32)cnt, 0u, dst, (u64 *)nullptr);
+        });
+    unsigned launches = 0;
+    for (size_t l = B; l > 1; l /= 2) launches++;
+    if (ctx->ag_nodes.reserve(cnt / 2 * 32) || ctx->ag_nodes2.reserve(cnt / 4 * 32 + 32)) return SSA_ERR_HIP;
+    u64 *bufs[2] = {(u64 *)ctx->ag_nodes.p, (u64 *)ctx->ag_nodes2.p};
+    return timed_launch(ctx, "ag_k_level", [&] {
+        size_t c = cnt;
+        const u64 *in = src;
+        for (unsigned l = 0; l < launches; l++, c /= 2) {
+            u64 *o = l + 1 == launches ? dst : bufs[l & 1u];
+            hipLaunchKernelGGL(ag_k_level, dim3(grid_for(c / 2, 256)), dim3(256), 0, ctx->stream, ctx->d_params, in, c, o);
+            in = o;
+        }
+    });
+}
+
+// Synchronises the stream as ssa_aggregate_valid_many_device does: once inside the screen (not at all with
+// SSA_AGGR_NO_SCREEN or for at most msm_small_max lanes) and once for the kept count, which the object keeps on the host
+// from then on.
+extern "C" int ssa_aggregator_push_device(ssa_ctx *ctx, ssa_aggregator *ag, const uint8_t *d_sigs, const uint8_t *d_pks,
+                                          const uint8_t *d_pk_inf, const uint8_t *d_msgs, const uint64_t *d_msg_off,
+                                          size_t msg_stride, size_t msg_len, size_t n, uint32_t flags, uint8_t *d_status_out,
+                                          uint64_t *n_kept_out) {
+    const DevBatch b{d_sigs, d_pks, d_pk_inf, {d_msgs, d_msg_off, msg_stride, msg_len}};
+    if (int rc = agx_push_args(ctx, ag, b.msgs, n, flags, d_sigs, d_pks, n_kept_out)) return rc;
+    *n_kept_out = 0;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (n == 0) {
+        ag->pushes++;
+        return SSA_OK;
+    }
+    if ((!d_status_out && ctx->ag_status.reserve(n + 16)) || ctx->agx_kept.reserve(n * sizeof(u32))) return SSA_ERR_HIP;
+    u8 *d_status = d_status_out ? d_status_out : (u8 *)ctx->ag_status.p;
+    // ONE challenge hash over the n lanes: the raw digests for the leaves and, screened, the scalars mod q for the screen
+    const bool screen = !(flags & SSA_AGGR_NO_SCREEN);
+    if (int rc = ag_transcript_front(ctx, nullptr, &d_sigs, d_pks, b.msgs, n, screen, nullptr, 1)) return rc;
+    if (screen) {
+        if (int rc = ssa_internal_screen_hashed(ctx, b, n, (const uint64_t *)ctx->ws_h.p, d_status, nullptr)) return rc;
+    } else {
+        const int rc = timed_launch(ctx, "agx_k_check", [&] {
+            hipLaunchKernelGGL(agx_k_check, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, d_sigs, d_pks, d_pk_inf, n,
+                               d_status);
+        });
+        if (rc) return rc;
+    }
+    uint64_t m = 0;
+    if (int rc = av_keep(ctx, d_status, n, (u32 *)ctx->agx_kept.p, &m)) return rc;
+    if (m) {
+        int rc = timed_launch(ctx, "agx_k_append", [&] {
+            hipLaunchKernelGGL(agx_k_append, dim3(grid_for(m, 256)), dim3(256), 0, ctx->stream, ctx->d_params, d_sigs,
+                               (const u64 *)ctx->ag_dig.p, (const u32 *)ctx->agx_kept.p, (size_t)m, ag->held,
+                               (u64 *)ag->leaves.p, (u64 *)ag->scal.p, (u8 *)ag->wire.p);
+        });
+        if (rc) return rc;
+        const AgxPlan p = agx_plan(ag->held, m, ag->block);
+        if (p.count)
+            if ((rc = agx_reduce_blocks(ctx, ag, p))) return rc;
+    }
+    // (only now: a launch that could not be enqueued leaves the object as it was -- what it wrote lies behind `held`)
+    ag->held += m;
+    ag->pushes++;
+    ag->offered += n;
+    ag->dropped += n - m;
+    *n_kept_out = m;
+    return SSA_OK;
+}
+
+extern "C" int ssa_aggregator_push(ssa_ctx *ctx, ssa_aggregator *ag, const uint8_t *sigs, const uint8_t *pks,
+                                   const uint8_t *pk_inf, const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride,
+                                   size_t msg_len, size_t n, uint32_t flags, uint8_t *status_out, uint64_t *n_kept_out) {
+    if (int rc = agx_push_args(ctx, ag, {msgs, msg_off, msg_stride, msg_len}, n, flags, sigs, pks, n_kept_out)) return rc;
+    if (int rc = check_host_offsets(msg_off, n)) return rc;
+    if (n == 0) return ssa_aggregator_push_device(ctx, ag, nullptr, nullptr, nullptr, nullptr, nullptr, msg_stride, msg_len, 0,
+                                                  flags, nullptr, n_kept_out);
+    HostCall hc(ctx);
+    const u8 *d_sigs = hc.in(ctx->st_sigs, sigs, n * 81), *d_pks = hc.in(ctx->st_pks, pks, n * 96);
+    const u8 *d_inf = pk_inf ? hc.in(ctx->st_inf, pk_inf, n) : nullptr;
+    const MsgView mv = hc.msgs(msgs, msg_off, msg_stride, msg_len, n);
+    u8 *d_status = hc.out(ctx->st_status, status_out, n, 16);
+    return hc.finish([&] {
+        return ssa_aggregator_push_device(ctx, ag, d_sigs, d_pks, d_inf, mv.msgs, mv.off, msg_stride, msg_len, n, flags,
+                                          d_status, n_kept_out);
+    });
+}
+
+// Only enqueues on the context's stream: every size it needs is on the host.  Reads the object, writes workspaces of the
+// context and the caller's buffer.
+extern "C" int ssa_aggregator_finish_device(ssa_ctx *ctx, ssa_aggregator *ag, size_t n_take, uint8_t *d_agg_out) {
+    if (!ctx || !ag || ag->ctx != ctx || !d_agg_out) return SSA_ERR_ARG;
+    const size_t n = n_take == SIZE_MAX ? ag->held : n_take;
+    if (n > ag->held) return SSA_ERR_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    ag->finishes++;
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(d_agg_out, 0, 32, ctx->stream));
+        return SSA_OK;
+    }
+    const size_t B = ag->block;
+    const AgxPlan p = agx_plan(0, n, B);       // p.count stored tops, then the ragged block's
+    const size_t n_tops = (size_t)p.count + (p.tail_len ? 1 : 0);
+    const size_t piece = ags_piece(ctx), k = (n + piece - 1) / piece;
+    if (ctx->ags_tops.reserve(n_tops * 32) || ctx->agm_roots.reserve(32) || ctx->ag_misc.reserve(AG_MISC_BYTES) ||
+        ctx->ags_parts.reserve(k * 32) || ctx->ag_partials.reserve((size_t)grid_for(std::min(piece, n), 256) * 32))
+        return SSA_ERR_HIP;
+    u64 *d_tops = (u64 *)ctx->ags_tops.p;
+    if (p.count)
+        HIP_TRY(hipMemcpyAsync(d_tops, ag->tops.p, (size_t)p.count * 32, hipMemcpyDeviceToDevice, ctx->stream));
+    if (p.tail_len) {        // fewer than B <= 512 leaves: one workgroup, the odd-node rule, no root
+        const int rc = timed_launch(ctx, "ag_k_tree", [&] {
+            hipLaunchKernelGGL(ag_k_tree, dim3(1), dim3(256), 0, ctx->stream, ctx->d_params,
+                               (const u64 *)ag->leaves.p + 4 * (size_t)p.tail_first, (const AgTreeDesc *)nullptr,
+                               (u32)p.tail_len, 0u, d_tops + 4 * (size_t)p.count, (u64 *)nullptr);
+        });
+        if (rc) return rc;
+    }
+    const u64 *d_root = (const u64 *)ctx->agm_roots.p;
+    if (int rc = ags_root(ctx, d_tops, n_tops, n, (u64 *)ctx->agm_roots.p)) return rc;
+    for (size_t lo = 0, j = 0; lo < n; lo += piece, j++) {
+        const size_t cnt = std::min(piece, n - lo);
+        const unsigned n_blocks = grid_for(cnt, 256);
+        int rc = timed_launch(ctx, "agx_k_coeff_fold", [&] {
+            hipLaunchKernelGGL(agx_k_coeff_fold, dim3(n_blocks), dim3(256), 0, ctx->stream, ctx->d_params, d_root,
+                               (const u64 *)ag->scal.p + 4 * lo, cnt, (u64)lo, (u64 *)ctx->ag_partials.p);
+        });
+        if (rc) return rc;
+        rc = timed_launch(ctx, "ag_k_fold_finish", [&] {
+            hipLaunchKernelGGL(ag_k_fold_finish, dim3(1), dim3(256), 0, ctx->stream, (const u64 *)ctx->ag_partials.p, n_blocks,
+                               k == 1 ? ag_misc(ctx, AG_E) : (u8 *)ctx->ags_parts.p + 32 * j);
+        });
+        if (rc) return rc;
+    }
+    if (k > 1) {
+        const int rc = timed_launch(ctx, "ag_k_fold_finish", [&] {
+            hipLaunchKernelGGL(ag_k_fold_finish, dim3(1), dim3(256), 0, ctx->stream, (const u64 *)ctx->ags_parts.p, (u32)k,
+                               ag_misc(ctx, AG_E));
+        });
+        if (rc) return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(d_agg_out, ag->wire.p, 49 * n, hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(d_agg_out + 49 * n, ag_misc(ctx, AG_E), 32, hipMemcpyDeviceToDevice, ctx->stream));
+    return SSA_OK;
+}
+
+extern "C" int ssa_aggregator_finish(ssa_ctx *ctx, ssa_aggregator *ag, size_t n_take, uint8_t *agg_out) {
+    if (!ctx || !ag || ag->ctx != ctx || !agg_out) return SSA_ERR_ARG;
+    const size_t n = n_take == SIZE_MAX ? ag->held : n_take;
+    if (n > ag->held) return SSA_ERR_ARG;
+    HostCall hc(ctx);
+    u8 *d_agg = hc.out(ctx->st_aux, agg_out, SSA_AGGREGATE_LENGTH(n), 16);
+    return hc.finish([&] { return ssa_aggregator_finish_device(ctx, ag, n, d_agg); });
+}
+
 // ---- several devices in one process: every device takes a contiguous run of whole blocks, block counts differ by at
 // most one.  One host thread per device and walk; two joins: the tops come in (32 bytes per block), the root goes out.
 // The root, the sum of the partial scalars and the combination run on device 0.
@@ -3314,7 +3557,7 @@ extern "C" int ssa_debug_fault_after_chunk(ssa_ctx *ctx, int chunk) {
 // is ctab: it is no workspace but the constant-time signer's table, built once and trusted from then on (ctab_ready);
 // filling it would make every later constant-time signature wrong by design.  No other listed buffer is read by a call
 // that did not write it first (rng_seed, rng_scratch and dv_recs are wiped after each call, not kept).  What is not in
-// the list -- the comb, d_params, key sets, key caches, signer sets -- is not touched.
+// the list -- the comb, d_params, key sets, key caches, signer sets, streaming aggregators -- is not touched.
 extern "C" int ssa_debug_poison_workspaces(ssa_ctx *ctx, int byte) {
     if (!ctx || byte < 0 || byte > 255) return SSA_ERR_ARG;
     HIP_TRY(hipSetDevice(ctx->device));

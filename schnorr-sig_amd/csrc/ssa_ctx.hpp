@@ -201,6 +201,9 @@ struct CtxKnobs {
     /* sliced and sharded half-aggregation: one 32-byte top per block of lanes, and one partial \
        scalar and one MSM record per slice of a shard */ \
     X(ags_tops) X(ags_parts) X(ags_recs) \
+    /* the streaming aggregator (ssa_aggregator.hpp): the kept lanes of one push.  What the object \
+       holds between calls is its own and not listed here */ \
+    X(agx_kept) \
     /* the end game of ssa_k_verify, per tail group: finished pieces; parked accumulators + status (152 B per lane) */ \
     X(tail_done) X(tail_park)
 
@@ -248,6 +251,7 @@ struct ssa_ctx {
     std::vector<struct ssa_keyset *> keysets;   // live key sets of this context (orphaned, not leaked, by ssa_ctx_destroy)
     std::vector<struct ssa_signer_set *> signer_sets;   // live signer sets (ssa_sign.hip), orphaned the same way
     std::vector<struct ssa_keycache *> keycaches;       // live key caches, orphaned the same way
+    std::vector<struct ssa_aggregator *> aggregators;   // live streaming aggregators, the same way
 };
 
 template <class Ctx, class F>

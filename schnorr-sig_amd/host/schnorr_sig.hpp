@@ -876,6 +876,68 @@ class KeyCache {
     bool wire_ = false;
 };
 
+// A streaming aggregator on the device (ssa_aggregator_create): push signatures as they arrive,
+// finish at block time.  push admits a slice of triples and appends the ones that pass, in order; finish gives the
+// aggregate of the first n_take admitted triples -- byte for byte AggregateSignature::aggregate(check = false) of those
+// triples alone -- and changes nothing, so it may be repeated, called with another n_take, and followed by more pushes.
+// Belongs to the context it was made on.
+class Aggregator {
+  public:
+    struct Info {
+        uint64_t held, capacity, block_lanes, pushes, offered, dropped, blocks, finishes;
+    };
+    static constexpr size_t All = SIZE_MAX;       // finish: every triple held
+    // block_lanes: 0 (512) or a power of two from 2 to 512.  All device memory, about 113 bytes per lane, is allocated here.
+    Aggregator(Context &cx, size_t capacity, size_t block_lanes = 0) : cx_(cx) {
+        const int rc = ssa_aggregator_create(cx.get(), capacity, block_lanes, 0u, &ag_);
+        if (rc != 0) throw std::runtime_error(std::string("ssa_aggregator_create: ") + ssa_strerror(rc));
+    }
+    ~Aggregator() { ssa_aggregator_destroy(ag_); }
+    Aggregator(const Aggregator &) = delete;
+    Aggregator &operator=(const Aggregator &) = delete;
+    ssa_aggregator *get() const { return ag_; }
+    // One status byte per triple; the triples whose byte is zero were appended.  screen: the statuses of
+    // verify_batch_statuses on this slice alone (library-drawn coefficients); without it 0 or SSA_MALFORMED by the checks
+    // aggregate(check = false) makes (SSA_AGGR_NO_SCREEN: for a producer that made the signatures itself).  A slice that
+    // does not fit what is left of the capacity throws and changes nothing.
+    std::vector<uint8_t> push(const std::vector<Signature> &signatures, const std::vector<PublicKey> &public_keys,
+                              const std::vector<std::pair<const uint8_t *, size_t>> &messages, bool screen = true,
+                              uint64_t *n_kept_out = nullptr) {
+        const PackedTriples t = pack_triples(signatures, public_keys, messages);
+        const size_t n = signatures.size();
+        std::vector<uint8_t> status(n, 0);
+        uint64_t n_kept = 0;
+        const int rc = ssa_aggregator_push(cx_.get(), ag_, t.sigs.data(), t.pks.data(), t.inf.data(), t.flat.data(),
+                                           t.off.data(), 0, 0, n, screen ? 0u : SSA_AGGR_NO_SCREEN,
+                                           n ? status.data() : nullptr, &n_kept);
+        if (rc != 0) throw std::runtime_error(std::string("ssa_aggregator_push: ") + ssa_strerror(rc));
+        if (n_kept_out) *n_kept_out = n_kept;
+        return status;
+    }
+    AggregateSignature finish(size_t n_take = All) const {
+        const size_t n = n_take == All ? (size_t)info().held : n_take;
+        AggregateSignature a;
+        a.bytes.assign(SSA_AGGREGATE_LENGTH(n), 0);
+        const int rc = ssa_aggregator_finish(cx_.get(), ag_, n, a.bytes.data());
+        if (rc != 0) throw std::runtime_error(std::string("ssa_aggregator_finish: ") + ssa_strerror(rc));
+        return a;
+    }
+    void reset() {
+        const int rc = ssa_aggregator_reset(ag_);
+        if (rc != 0) throw std::runtime_error(std::string("ssa_aggregator_reset: ") + ssa_strerror(rc));
+    }
+    Info info() const {
+        uint64_t v[8] = {};
+        const int rc = ssa_aggregator_info(ag_, v);
+        if (rc != 0) throw std::runtime_error(std::string("ssa_aggregator_info: ") + ssa_strerror(rc));
+        return {v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]};
+    }
+
+  private:
+    Context &cx_;
+    ssa_aggregator *ag_ = nullptr;
+};
+
 // AggregateSignature::verify_many through a key cache
 namespace detail {
 struct PackedAggregates {

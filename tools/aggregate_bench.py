@@ -71,7 +71,12 @@ of S signatures (4096 x 256) with 80-byte messages, device buffers, legs alterna
   loop_baseline   K ssa_aggregate_many_device calls through --baseline-lib (a build of the parent commit, which has no other
                   way; without it, this tree's own library)
   single          the same lanes as ONE aggregate through this tree's ssa_aggregate_many_device (recorded, no bar)
-Every timed output is compared with the aggregates of the single call, batch by batch, made once before the rounds."""
+Every timed output is compared with the aggregates of the single call, batch by batch, made once before the rounds.
+
+--accumulator measures the streaming aggregator: --n honest signatures pushed in --pushes equal
+pushes, then ssa_aggregator_finish_device against ssa_aggregate_many_sliced_device of --baseline-lib over the same
+signatures, legs alternating; the pushes' own times and ssa_aggregate_valid_many_device at --n are recorded beside it.
+"""
 import argparse
 import hashlib
 import json
@@ -982,6 +987,162 @@ def sharded_main(a):
     return 0 if res["mismatches"] == 0 else 1
 
 
+ACCUMULATOR_KERNELS = ("ssa_k_hash", "msm_k_prepare", "msm_sort", "msm_k_buckets", "msm_reduce", "msm_k_finish_seg",
+                       "screen_gather", "ssa_k_verify", "screen_scatter", "agx_k_check", "av_k_keep", "agx_k_append",
+                       "ag_k_level", "ag_k_tree", "agx_k_coeff_fold", "ag_k_fold_finish")
+
+
+class BaselineProducer:
+    """ssa_aggregate_many_sliced_device and ssa_aggregate_valid_many_device of a build of the library given by its path,
+    on a context of its own"""
+
+    def __init__(self, path):
+        import ctypes as C
+        self.C, self.lib = C, C.CDLL(path)
+        vp, sz, i32 = C.c_void_p, C.c_size_t, C.c_int
+        self.lib.ssa_ctx_create_ex.argtypes = [C.POINTER(vp), i32, vp, sz, C.c_uint32, C.c_uint64]
+        self.lib.ssa_aggregate_many_sliced_device.argtypes = [vp, vp, vp, vp, vp, vp, sz, sz, sz, C.c_uint32, vp, vp, vp]
+        self.lib.ssa_aggregate_valid_many_device.argtypes = [vp, vp, vp, vp, vp, vp, sz, sz, sz, vp, vp,
+                                                             C.POINTER(C.c_uint64), vp]
+        self.lib.ssa_ctx_sync.argtypes = [vp]
+        self.lib.ssa_ctx_destroy.argtypes = [vp]
+        self.lib.ssa_ctx_destroy.restype = None
+        self.ctx = vp()
+        if self.lib.ssa_ctx_create_ex(C.byref(self.ctx), 0, None, 0, 0, 0) != 0:
+            raise RuntimeError("baseline library: ssa_ctx_create_ex failed")
+
+    def sliced(self, d_sigs, d_pks, d_msgs, n, d_agg):
+        rc = self.lib.ssa_aggregate_many_sliced_device(self.ctx, d_sigs, d_pks, None, d_msgs, None, 80, 80, n, 0, d_agg, None,
+                                                       None)
+        if rc != 0:
+            raise RuntimeError("baseline library: ssa_aggregate_many_sliced_device failed (%d)" % rc)
+
+    def valid(self, d_sigs, d_pks, d_msgs, n, d_agg, d_kept):
+        kept = self.C.c_uint64(0)
+        if self.lib.ssa_aggregate_valid_many_device(self.ctx, d_sigs, d_pks, None, d_msgs, None, 80, 80, n, d_agg, d_kept,
+                                                    self.C.byref(kept), None) != 0:
+            raise RuntimeError("baseline library: ssa_aggregate_valid_many_device failed")
+        return int(kept.value)
+
+    def sync(self):
+        self.lib.ssa_ctx_sync(self.ctx)
+
+    def close(self):
+        self.lib.ssa_ctx_destroy(self.ctx)
+
+
+def accumulator_main(a):
+    """--accumulator: the streaming aggregator.  --n honest signatures over 80-byte messages in
+    device buffers are pushed in --pushes equal pushes; then the legs alternate in one process:
+      finish            ssa_aggregator_finish_device and a stream synchronisation: what is left for block time
+      baseline_sliced   ssa_aggregate_many_sliced_device through --baseline-lib (a build of the parent commit; without
+                        it, this tree's own library) over the same signatures: the fastest one-shot producer call
+      pushes            reset and all the pushes again, each one timed: their sum (recorded only)
+      baseline_valid    ssa_aggregate_valid_many_device through the same library at --n (recorded only)
+    The bar: finish < baseline_sliced, by more than baseline_sliced differs between two processes."""
+    import torch
+    import schnorr_sig_amd as ssa
+    dev = torch.device("cuda", 0)
+    eng = ssa.Engine(0)
+    base_path = a.baseline_lib or ssa.LIB_PATH
+    base = BaselineProducer(base_path)
+    n, k = a.n, a.pushes
+    if n % k:
+        raise SystemExit("--accumulator: --n must be a multiple of --pushes")
+    per = n // k
+    rng = np.random.default_rng(a.seed)
+    msgs = rng.integers(0, 256, (n, 80), dtype=np.uint8)
+    pks, sigs = eng.keygen_sign_many(_scalars(rng, n), _scalars(rng, n), msgs)
+    t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)   # noqa: E731
+    d_sigs, d_pks, d_msgs = t(sigs), t(pks), t(msgs)
+    d_agg = torch.zeros(49 * n + 32, dtype=torch.uint8, device=dev)
+    d_agg0 = torch.zeros(49 * n + 32, dtype=torch.uint8, device=dev)
+    d_kept = torch.zeros(n, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+    sha = lambda path: hashlib.sha256(open(path, "rb").read()).hexdigest()[:16]   # noqa: E731
+    res = {"metric": "aggregator", "n": n, "pushes": k, "msg_len": 80, "rounds": a.rounds, "warmup": a.warmup,
+           "library_sha256": sha(ssa.LIB_PATH), "baseline_sha256": sha(base_path), "baseline_is_this_tree": not a.baseline_lib,
+           "device": torch.cuda.get_device_name(0), "date": time.strftime("%Y-%m-%d"), "mismatches": 0}
+    ptrs = (d_sigs.data_ptr(), d_pks.data_ptr(), d_msgs.data_ptr())
+    base.sliced(*ptrs, n, d_agg0.data_ptr())
+    base.sync()
+    ag = eng.aggregator(n)
+
+    def wall(fn, sync):
+        sync()
+        t0 = time.perf_counter()
+        fn()
+        sync()
+        return (time.perf_counter() - t0) * 1e3
+
+    def push_all():
+        """reset, then every push timed on its own -> their times"""
+        ag.reset()
+        out = []
+        for j in range(k):
+            sl = slice(j * per, (j + 1) * per)
+            out.append(wall(lambda: ag.push_device(d_sigs[sl], d_pks[sl], d_msgs[sl]), eng.sync))
+        if ag.info()["held"] != n:
+            res["mismatches"] += 1
+        return out
+
+    push_all()
+    push_ms, times = [], {"finish": [], "baseline_sliced": [], "pushes": [], "baseline_valid": []}
+    for rnd in range(a.warmup + a.rounds):
+        for leg in times:
+            d_agg.fill_(0xEE)
+            torch.cuda.synchronize()
+            if leg == "finish":
+                ms = wall(lambda: ag.finish_device(d_agg), eng.sync)
+            elif leg == "baseline_sliced":
+                ms = wall(lambda: base.sliced(*ptrs, n, d_agg.data_ptr()), base.sync)
+            elif leg == "pushes":
+                each = push_all()
+                ms = float(np.sum(each))
+                if rnd >= a.warmup:
+                    push_ms.append(each)
+                ag.finish_device(d_agg)
+                eng.sync()
+            else:
+                kept = []
+                ms = wall(lambda: kept.append(base.valid(*ptrs, n, d_agg.data_ptr(), d_kept.data_ptr())), base.sync)
+                res["mismatches"] += 0 if kept == [n] else 1
+            res["mismatches"] += 0 if bool((d_agg == d_agg0).all()) else 1
+            if rnd >= a.warmup:
+                times[leg].append(ms)
+    med = res["ms_median"] = {leg: round(float(np.median(v)), 3) for leg, v in times.items()}
+    res["ms_all"] = {leg: [round(x, 3) for x in v] for leg, v in times.items()}
+    res["push_ms_median_by_position"] = [round(float(x), 3) for x in np.median(np.array(push_ms), axis=0)]
+    res["ratio"] = {"finish/baseline_sliced": round(med["finish"] / med["baseline_sliced"], 4),
+                    "pushes/baseline_valid": round(med["pushes"] / med["baseline_valid"], 4)}
+    res["finish_faster_than_baseline_sliced"] = bool(med["finish"] < med["baseline_sliced"])
+
+    def timed(fn):
+        eng.sync()
+        eng.enable_timing(True)
+        fn()
+        eng.sync()
+        out = {}
+        for kn in ACCUMULATOR_KERNELS:
+            avg, cnt = eng.read_timing(kn)
+            if cnt:
+                out[kn] = [round(avg, 4), int(cnt)]
+        eng.enable_timing(False)
+        return out
+
+    kern = {"finish": timed(lambda: ag.finish_device(d_agg))}
+    ag.reset()
+    kern["push"] = timed(lambda: ag.push_device(d_sigs[:per], d_pks[:per], d_msgs[:per]))
+    kern["push_no_screen"] = timed(lambda: ag.push_device(d_sigs[per:2 * per], d_pks[per:2 * per], d_msgs[per:2 * per],
+                                                          screen=False))
+    res["kernel_ms_avg_launches"] = kern
+    print(json.dumps(res))
+    ag.close()
+    eng.close()
+    base.close()
+    return 0 if res["mismatches"] == 0 else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1 << 20)
@@ -1009,7 +1170,13 @@ def main():
     ap.add_argument("--produce-many", nargs="?", const="4096x256", default=None, metavar="KxS",
                     help="ssa_aggregates_many_device over K batches of S signatures against K ssa_aggregate_many_device "
                          "calls of --baseline-lib")
+    ap.add_argument("--accumulator", action="store_true",
+                    help="ssa_aggregator_finish_device after --pushes pushes against ssa_aggregate_many_sliced_device of "
+                         "--baseline-lib over the same --n signatures")
+    ap.add_argument("--pushes", type=int, default=16, help="--accumulator: equal pushes the --n signatures arrive in")
     a = ap.parse_args()
+    if a.accumulator:
+        return accumulator_main(a)
     if a.produce_many:
         return produce_many_main(a)
     if a.sharded:
