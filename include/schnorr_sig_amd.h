@@ -1229,8 +1229,8 @@ int ssa_aggregate_valid_keyed_many_cached_device(ssa_ctx *ctx, ssa_keycache *kc,
  *   reset    empties the object (counters included) and keeps its memory.
  *   info     [0] lanes held  [1] capacity  [2] block_lanes  [3] pushes  [4] lanes offered  [5] lanes dropped
  *            [6] blocks whose top is stored  [7] finishes.
- * NOT here: removing the lanes a block took from the front (the rest changes place: reset and push it again), the
- * validator's counterpart, admission through a key cache, ssa_multi forms. */
+ * NOT here: removing the lanes a block took from the front (the rest changes place: reset and push it again),
+ * admission through a key cache, ssa_multi forms.  The validator's counterpart is ssa_aggverifier, below. */
 typedef struct ssa_aggregator ssa_aggregator;
 #define SSA_AGGR_NO_SCREEN 1u      /* push flag */
 int ssa_aggregator_create(ssa_ctx *ctx, size_t capacity, size_t block_lanes, uint32_t flags, ssa_aggregator **out);
@@ -1249,6 +1249,51 @@ int ssa_aggregator_finish_device(ssa_ctx *ctx, ssa_aggregator *ag, size_t n_take
  * device): out[0] the first completed block, out[1] the number of completed blocks, out[2] the first lane of the ragged
  * tail, out[3] its length.  SSA_ERR_ARG for a block size create would refuse or held + m above SSA_MAX_BATCH. */
 int ssa_debug_aggregator_plan(uint64_t held, uint64_t m, uint64_t block_lanes, uint64_t out[4]);
+
+/* ---- streaming aggregate verifier: push a block body as it arrives, finish with e_agg ----
+ * The validator's counterpart of the streaming aggregator.  A block body -- the R's, keys and messages of a half-aggregate
+ * -- arrives before the verdict can be asked for, and only the coefficients have to wait for the last R.  An
+ * ssa_aggverifier holds, on the device and in arrival order, what ssa_verify_aggregate computes per lane without knowing
+ * the lane's place: R decompressed and -P as the MSM's point rows, the challenge scalar, the leaf, a "failed a check"
+ * byte, and the top of every complete block of block_lanes leaves.  finish pays one permutation and one multiplication
+ * per lane, the bucket MSM and the exact comparison.  It belongs to the context it was created on, like a key cache.
+ *   create   capacity: 1 .. SSA_MAX_BATCH lanes; block_lanes: 0 (the default, 512) or a power of two from 2 to 512;
+ *            flags: 0.  Anything else: SSA_ERR_ARG.  All device memory is allocated here -- 96 + 96 + 32 + 32 + 1 bytes
+ *            per lane and 32 bytes per block: about 257 bytes per lane -- and is the object's own: destroy releases it,
+ *            or ssa_ctx_destroy (the handle then stays valid for destroy and is refused everywhere else).
+ *   push     n R's at stride 49 (the aggregate's wire layout), their keys, pk_inf (may be NULL) and messages, as
+ *            ssa_verify_aggregate takes them.  ALL n lanes are appended: a validator cannot drop a lane, its place is
+ *            part of the transcript; a lane that fails a check (non-canonical limbs, key off the curve, R not decodable)
+ *            is held as such and makes every finish that takes it SSA_MALFORMED.  SSA_ERR_ARG: a context other than the
+ *            object's, n above the context's MSM slice, n > capacity - held, bad message arguments; the object is then
+ *            unchanged -- a push is never applied in part.  n == 0: SSA_OK.  Every message is hashed ONCE.  The _device
+ *            form only enqueues on the context's stream: it never synchronises.
+ *   finish   the status ssa_verify_aggregate returns for the first n_take held lanes handed in at once as
+ *            R_0 || ... || R_(n_take-1) || e_agg (e_agg32 / d_e_agg: 32 bytes).  n_take == SIZE_MAX: all lanes held;
+ *            n_take > held: SSA_ERR_ARG; n_take == 0: the rule of the empty aggregate (valid iff e_agg is zero).  finish
+ *            changes NO state of the object but a counter: it may be repeated, take prefixes, and be followed by more
+ *            pushes.  The host form returns the status; the _device form only enqueues and the status lands in the
+ *            uint32 at d_verdict_out.  Always the bucket MSM, whatever n_take is.
+ *   reset    empties the object (counters included) and keeps its memory.
+ *   info     [0] lanes held  [1] capacity  [2] block_lanes  [3] pushes  [4] lanes pushed  [5] 0 (lanes that failed a
+ *            check are known on the device alone: nothing is read back)  [6] blocks whose top is stored  [7] finishes.
+ * NOT here: admission through a key cache (the subgroup check), ssa_multi forms, removing lanes from the front. */
+typedef struct ssa_aggverifier ssa_aggverifier;
+int ssa_aggverifier_create(ssa_ctx *ctx, size_t capacity, size_t block_lanes, uint32_t flags, ssa_aggverifier **out);
+void ssa_aggverifier_destroy(ssa_aggverifier *av);
+int ssa_aggverifier_reset(ssa_aggverifier *av);
+int ssa_aggverifier_info(ssa_aggverifier *av, uint64_t out[8]);
+int ssa_aggverifier_push(ssa_ctx *ctx, ssa_aggverifier *av, const uint8_t *rs49, const uint8_t *pks, const uint8_t *pk_inf,
+                         const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len, size_t n);
+int ssa_aggverifier_push_device(ssa_ctx *ctx, ssa_aggverifier *av, const uint8_t *d_rs49, const uint8_t *d_pks,
+                                const uint8_t *d_pk_inf, const uint8_t *d_msgs, const uint64_t *d_msg_off,
+                                size_t msg_stride, size_t msg_len, size_t n);
+int ssa_aggverifier_finish(ssa_ctx *ctx, ssa_aggverifier *av, const uint8_t *e_agg32, size_t n_take);
+int ssa_aggverifier_finish_device(ssa_ctx *ctx, ssa_aggverifier *av, const uint8_t *d_e_agg, size_t n_take,
+                                  uint32_t *d_verdict_out);
+/* tests: the 24-word record finish compares with [e_agg]G -- the sum of the pieces' records -- at device address
+ * d_record24_out (8-byte aligned), without the comparison.  Only enqueues.  n_take == 0 (no record): SSA_ERR_ARG. */
+int ssa_debug_aggverifier_record(ssa_ctx *ctx, ssa_aggverifier *av, size_t n_take, uint64_t *d_record24_out);
 
 /* ---- ABI version -------------------------------------------------------------------------------------------
  * Bumped whenever an exported signature changes (round 2 inserted pk_inf into the batch entry points under the same

@@ -301,6 +301,15 @@ def _load():
         "ssa_aggregator_finish": (i32, [vp, vp, sz, vp]),
         "ssa_aggregator_finish_device": (i32, [vp, vp, sz, vp]),
         "ssa_debug_aggregator_plan": (i32, [C.c_uint64, C.c_uint64, C.c_uint64, u64p]),
+        "ssa_aggverifier_create": (i32, [vp, sz, sz, u32, C.POINTER(vp)]),
+        "ssa_aggverifier_destroy": (None, [vp]),
+        "ssa_aggverifier_reset": (i32, [vp]),
+        "ssa_aggverifier_info": (i32, [vp, u64p]),
+        "ssa_aggverifier_push": (i32, [vp, vp, vp, vp, vp, vp, vp, sz, sz, sz]),
+        "ssa_aggverifier_push_device": (i32, [vp, vp, vp, vp, vp, vp, vp, sz, sz, sz]),
+        "ssa_aggverifier_finish": (i32, [vp, vp, vp, sz]),
+        "ssa_aggverifier_finish_device": (i32, [vp, vp, vp, sz, vp]),
+        "ssa_debug_aggverifier_record": (i32, [vp, vp, sz, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)      # AttributeError here == ABI symbol missing: fail loudly
@@ -594,6 +603,15 @@ class Engine:
         _check(_lib.ssa_aggregator_create(self._ctx, int(capacity), int(block_lanes), 0, C.byref(h)),
                "ssa_aggregator_create")
         return Aggregator(self, h)
+
+    def aggregate_verifier(self, capacity, block_lanes=0):
+        """a streaming aggregate verifier of `capacity` lanes on this engine's device: push the
+        R's, keys and messages of a block body as they arrive, finish with e_agg.  All of its device memory, about 257
+        bytes per lane, is allocated here.  block_lanes: 0 (512) or a power of two from 2 to 512."""
+        h = C.c_void_p()
+        _check(_lib.ssa_aggverifier_create(self._ctx, int(capacity), int(block_lanes), 0, C.byref(h)),
+               "ssa_aggverifier_create")
+        return AggregateVerifier(self, h)
 
     def verify_keyed_many_cached(self, cache, keyed, msgs, offsets=None, check_torsion=True, sig_flag_byte=False,
                                  coeffs=None):
@@ -1756,6 +1774,7 @@ class KeyCache(_KeyTables):
 
 AGGR_NO_SCREEN = 1    # SSA_AGGR_NO_SCREEN
 AGGREGATOR_FIELDS = ("held", "capacity", "block_lanes", "pushes", "offered", "dropped", "blocks", "finishes")
+AGGVERIFIER_FIELDS = ("held", "capacity", "block_lanes", "pushes", "pushed", "reserved", "blocks", "finishes")
 AGGREGATOR_ALL = (1 << (8 * C.sizeof(C.c_size_t))) - 1      # SIZE_MAX: finish every lane held
 
 
@@ -1849,6 +1868,107 @@ class Aggregator:
     def close(self):
         if self.handle:
             _lib.ssa_aggregator_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class AggregateVerifier:
+    """ssa_aggverifier handle (Engine.aggregate_verifier): the lanes of a block body pushed so
+    far, on the device, in arrival order.  push() does the position-independent work of Engine.verify_aggregate on
+    arrival; finish(e_agg) gives the status Engine.verify_aggregate gives the first n_take held lanes handed in at once
+    with that e_agg -- and changes nothing.  Tied to its Engine like KeyCache; destroyed exactly once (close(), the end
+    of a `with` block, or when the object goes away)."""
+
+    def __init__(self, engine, handle):
+        self.engine = engine      # keeps the context alive
+        self.handle = handle
+
+    def info(self):
+        """the AGGVERIFIER_FIELDS by name"""
+        out = (C.c_uint64 * 8)()
+        _check(_lib.ssa_aggverifier_info(self.handle, out), "ssa_aggverifier_info")
+        return dict(zip(AGGVERIFIER_FIELDS, (int(v) for v in out)))
+
+    def __len__(self):
+        return self.info()["held"]
+
+    def push(self, rs49, pks, msgs, offsets=None, pk_inf=None, engine=None):
+        """n R's (n x 49 bytes, the aggregate's wire layout), keys and messages as Engine.verify_aggregate takes them:
+        ALL n lanes are appended (a lane that fails a check makes every finish that takes it MALFORMED).  A batch that
+        does not fit what is left of the capacity raises and changes nothing.  engine: tests (a context other than the
+        object's).  Returns n."""
+        eng = engine or self.engine
+        n, batch, keep = eng._agg_batch(rs49, 49, pks, msgs, offsets, pk_inf)
+        _check(_lib.ssa_aggverifier_push(eng._ctx, self.handle, *batch), "ssa_aggverifier_push")
+        return n
+
+    def push_aggregate(self, agg, pks, msgs, offsets=None, pk_inf=None):
+        """the R's of an AggregateSignature (or its 49 n + 32 bytes) with their keys and messages; e_agg is not kept:
+        hand it to finish().  Returns n."""
+        b = np.frombuffer(agg.bytes if isinstance(agg, AggregateSignature) else bytes(agg), np.uint8)
+        return self.push(b[:b.size - 32], pks, msgs, offsets=offsets, pk_inf=pk_inf)
+
+    def push_device(self, d_rs49, d_pks, d_msgs, d_pk_inf=None, d_offsets=None, msg_len=None, msg_stride=None):
+        """device form over torch tensors on the engine's device: d_rs49 (n, 49), d_pks (n, 96), d_msgs an (n, len)
+        uint8 tensor (or flat bytes with a uint64-valued d_offsets and msg_len left None).  Only enqueues.  Returns n."""
+        n = int(d_pks.shape[0])
+        if d_offsets is None and msg_len is None:
+            msg_len = d_msgs.shape[1] if d_msgs.dim() == 2 else 0
+        msg_len = msg_len or 0
+        addr = lambda t: t.data_ptr() if t is not None and t.numel() else None    # noqa: E731
+        _check(_lib.ssa_aggverifier_push_device(
+            self.engine._ctx, self.handle, addr(d_rs49), addr(d_pks), addr(d_pk_inf), addr(d_msgs), addr(d_offsets),
+            msg_stride if msg_stride is not None else msg_len, msg_len, n), "ssa_aggverifier_push_device")
+        return n
+
+    def finish(self, e_agg, n_take=None):
+        """-> the int status of the first n_take held lanes (None: all) under e_agg (32 bytes): OK, INVALID_SIGNATURE or
+        MALFORMED, what Engine.verify_aggregate returns for those lanes and that scalar.  Changes no state: it may be
+        repeated, take prefixes, and be followed by more pushes.  n_take above the lanes held raises."""
+        e = _np_u8(e_agg).reshape(-1)
+        if e.size != 32:
+            raise ValueError("e_agg is 32 bytes")
+        return _check(_lib.ssa_aggverifier_finish(self.engine._ctx, self.handle, _ptr(e),
+                                                  AGGREGATOR_ALL if n_take is None else int(n_take)),
+                      "ssa_aggverifier_finish")
+
+    def finish_device(self, d_e_agg, d_verdict, n_take=None):
+        """device form: only enqueues on the engine's stream; d_e_agg a uint8 tensor of 32 bytes, the status lands in the
+        first element of the int32 / uint32 tensor (view) d_verdict"""
+        _check(_lib.ssa_aggverifier_finish_device(self.engine._ctx, self.handle, d_e_agg.data_ptr(),
+                                                  AGGREGATOR_ALL if n_take is None else int(n_take),
+                                                  d_verdict.data_ptr()), "ssa_aggverifier_finish_device")
+
+    def record(self, n_take=None):
+        """tests: the 24-word record finish compares with [e_agg]G (ssa_debug_aggverifier_record) as uint64[24]"""
+        import torch
+        d_rec = torch.zeros(MSM_PARTIAL_WORDS, dtype=torch.int64, device="cuda:%d" % self.engine.device)
+        torch.cuda.synchronize(d_rec.device)      # (the engine's stream is not torch's)
+        _check(_lib.ssa_debug_aggverifier_record(self.engine._ctx, self.handle,
+                                                 AGGREGATOR_ALL if n_take is None else int(n_take), d_rec.data_ptr()),
+               "ssa_debug_aggverifier_record")
+        self.engine.sync()
+        return d_rec.cpu().numpy().view(np.uint64)
+
+    def reset(self):
+        """forget every lane and restart the counters; the memory stays"""
+        _check(_lib.ssa_aggverifier_reset(self.handle), "ssa_aggverifier_reset")
+
+    def close(self):
+        if self.handle:
+            _lib.ssa_aggverifier_destroy(self.handle)
             self.handle = C.c_void_p()
 
     def __enter__(self):

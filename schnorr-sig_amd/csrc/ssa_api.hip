@@ -8,6 +8,7 @@
 #include "ssa_aggregate.hpp"
 #include "ssa_aggcache.hpp"
 #include "ssa_aggregator.hpp"
+#include "ssa_aggverifier.hpp"
 
 #include <sys/random.h>
 
@@ -367,6 +368,7 @@ extern "C" void ssa_ctx_destroy(ssa_ctx *ctx) {
     orphan_handles(ctx->signer_sets, [](ssa_signer_set *ss) { ss->wipe_release(); });
     orphan_handles(ctx->keycaches, [](ssa_keycache *kc) { kc->release_all(); });
     orphan_handles(ctx->aggregators, [](ssa_aggregator *ag) { ag->release_all(); });
+    orphan_handles(ctx->aggverifiers, [](ssa_aggverifier *av) { av->release_all(); });
     for (auto &kv : ctx->timed)
         for (auto &t : kv.second) {
             (void)hipEventDestroy(t.start);
@@ -2624,14 +2626,15 @@ static int agx_push_args(const ssa_ctx *ctx, const ssa_aggregator *ag, const Msg
     return n > ag->capacity - ag->held ? SSA_ERR_ARG : 0;      // by n, not by the kept count: never applied in part
 }
 
-// The blocks [first, first + count) of the object, complete since this push, reduced to their tops.  B = 512: ONE launch
-// of ag_k_tree over that range of the leaves, a workgroup per block (the uniform cut, no top).  Smaller B: log2 B launches
-// of ag_k_level over the count * B leaves -- every level is even, no node moves up unchanged -- between ctx->ag_nodes and
-// ctx->ag_nodes2; the first reads the object's leaves, the last writes the object's tops.
-static int agx_reduce_blocks(ssa_ctx *ctx, ssa_aggregator *ag, const AgxPlan &p) {
-    const size_t B = ag->block, cnt = (size_t)p.count * B;
-    const u64 *src = (const u64 *)ag->leaves.p + 4 * (size_t)p.first * B;
-    u64 *dst = (u64 *)ag->tops.p + 4 * (size_t)p.first;
+// The blocks [first, first + count) of an object (a streaming aggregator or aggregate verifier: its leaves, its tops, its
+// B), complete since this push, reduced to their tops.  B = 512: ONE launch of ag_k_tree over that range of the leaves, a
+// workgroup per block (the uniform cut, no top).  Smaller B: log2 B launches of ag_k_level over the count * B leaves --
+// every level is even, no node moves up unchanged -- between ctx->ag_nodes and ctx->ag_nodes2; the first reads the
+// object's leaves, the last writes the object's tops.
+static int agx_reduce_blocks(ssa_ctx *ctx, const DevBuf &leaves, DevBuf &tops, size_t B, const AgxPlan &p) {
+    const size_t cnt = (size_t)p.count * B;
+    const u64 *src = (const u64 *)leaves.p + 4 * (size_t)p.first * B;
+    u64 *dst = (u64 *)tops.p + 4 * (size_t)p.first;
     if (B == AG_TREE_SPAN)
         return timed_launch(ctx, "ag_k_tree", [&] {
             hipLaunchKernelGGL(ag_k_tree, dim3((unsigned)p.count), dim3(256), 0, ctx->stream, ctx->d_params, src,
@@ -2650,6 +2653,28 @@ static int agx_reduce_blocks(ssa_ctx *ctx, ssa_aggregator *ag, const AgxPlan &p)
             in = o;
         }
     });
+}
+
+// The root of the first n (>= 1) lanes of an object (its leaves, its tops, its B) into ctx->agm_roots: the stored tops of
+// the n / B complete blocks are copied into ctx->ags_tops, the ragged block [B (n / B), n) is reduced behind them by one
+// workgroup of ag_k_tree -- into the workspace, never into the object: with n below the lanes held that slot is a complete
+// block's top -- and ags_root finishes the tree.
+static int agx_root(ssa_ctx *ctx, const DevBuf &leaves, const DevBuf &tops, size_t B, size_t n) {
+    const AgxPlan p = agx_plan(0, n, B);       // p.count stored tops, then the ragged block's
+    const size_t n_tops = (size_t)p.count + (p.tail_len ? 1 : 0);
+    if (ctx->ags_tops.reserve(n_tops * 32) || ctx->agm_roots.reserve(32)) return SSA_ERR_HIP;
+    u64 *d_tops = (u64 *)ctx->ags_tops.p;
+    if (p.count)
+        HIP_TRY(hipMemcpyAsync(d_tops, tops.p, (size_t)p.count * 32, hipMemcpyDeviceToDevice, ctx->stream));
+    if (p.tail_len) {        // fewer than B <= 512 leaves: one workgroup, the odd-node rule, no root
+        const int rc = timed_launch(ctx, "ag_k_tree", [&] {
+            hipLaunchKernelGGL(ag_k_tree, dim3(1), dim3(256), 0, ctx->stream, ctx->d_params,
+                               (const u64 *)leaves.p + 4 * (size_t)p.tail_first, (const AgTreeDesc *)nullptr,
+                               (u32)p.tail_len, 0u, d_tops + 4 * (size_t)p.count, (u64 *)nullptr);
+        });
+        if (rc) return rc;
+    }
+    return ags_root(ctx, d_tops, n_tops, n, (u64 *)ctx->agm_roots.p);
 }
 
 // Synchronises the stream as ssa_aggregate_valid_many_device does: once inside the screen (not at all with
@@ -2692,7 +2717,7 @@ extern "C" int ssa_aggregator_push_device(ssa_ctx *ctx, ssa_aggregator *ag, cons
         if (rc) return rc;
         const AgxPlan p = agx_plan(ag->held, m, ag->block);
         if (p.count)
-            if ((rc = agx_reduce_blocks(ctx, ag, p))) return rc;
+            if ((rc = agx_reduce_blocks(ctx, ag->leaves, ag->tops, ag->block, p))) return rc;
     }
     // (only now: a launch that could not be enqueued leaves the object as it was -- what it wrote lies behind `held`)
     ag->held += m;
@@ -2733,26 +2758,12 @@ extern "C" int ssa_aggregator_finish_device(ssa_ctx *ctx, ssa_aggregator *ag, si
         HIP_TRY(hipMemsetAsync(d_agg_out, 0, 32, ctx->stream));
         return SSA_OK;
     }
-    const size_t B = ag->block;
-    const AgxPlan p = agx_plan(0, n, B);       // p.count stored tops, then the ragged block's
-    const size_t n_tops = (size_t)p.count + (p.tail_len ? 1 : 0);
     const size_t piece = ags_piece(ctx), k = (n + piece - 1) / piece;
-    if (ctx->ags_tops.reserve(n_tops * 32) || ctx->agm_roots.reserve(32) || ctx->ag_misc.reserve(AG_MISC_BYTES) ||
-        ctx->ags_parts.reserve(k * 32) || ctx->ag_partials.reserve((size_t)grid_for(std::min(piece, n), 256) * 32))
+    if (ctx->ag_misc.reserve(AG_MISC_BYTES) || ctx->ags_parts.reserve(k * 32) ||
+        ctx->ag_partials.reserve((size_t)grid_for(std::min(piece, n), 256) * 32))
         return SSA_ERR_HIP;
-    u64 *d_tops = (u64 *)ctx->ags_tops.p;
-    if (p.count)
-        HIP_TRY(hipMemcpyAsync(d_tops, ag->tops.p, (size_t)p.count * 32, hipMemcpyDeviceToDevice, ctx->stream));
-    if (p.tail_len) {        // fewer than B <= 512 leaves: one workgroup, the odd-node rule, no root
-        const int rc = timed_launch(ctx, "ag_k_tree", [&] {
-            hipLaunchKernelGGL(ag_k_tree, dim3(1), dim3(256), 0, ctx->stream, ctx->d_params,
-                               (const u64 *)ag->leaves.p + 4 * (size_t)p.tail_first, (const AgTreeDesc *)nullptr,
-                               (u32)p.tail_len, 0u, d_tops + 4 * (size_t)p.count, (u64 *)nullptr);
-        });
-        if (rc) return rc;
-    }
-    const u64 *d_root = (const u64 *)ctx->agm_roots.p;
-    if (int rc = ags_root(ctx, d_tops, n_tops, n, (u64 *)ctx->agm_roots.p)) return rc;
+    if (int rc = agx_root(ctx, ag->leaves, ag->tops, ag->block, n)) return rc;
+    const u64 *d_root = (const u64 *)ctx->agm_roots.p;      // (only now: agx_root reserves it)
     for (size_t lo = 0, j = 0; lo < n; lo += piece, j++) {
         const size_t cnt = std::min(piece, n - lo);
         const unsigned n_blocks = grid_for(cnt, 256);
@@ -2786,6 +2797,194 @@ extern "C" int ssa_aggregator_finish(ssa_ctx *ctx, ssa_aggregator *ag, size_t n_
     HostCall hc(ctx);
     u8 *d_agg = hc.out(ctx->st_aux, agg_out, SSA_AGGREGATE_LENGTH(n), 16);
     return hc.finish([&] { return ssa_aggregator_finish_device(ctx, ag, n, d_agg); });
+}
+
+// ------------------------------------------------------------------ streaming aggregate verifier (ssa_aggverifier.hpp)
+extern "C" int ssa_aggverifier_create(ssa_ctx *ctx, size_t capacity, size_t block_lanes, uint32_t flags, ssa_aggverifier **out) {
+    if (out) *out = nullptr;
+    const size_t B = block_lanes ? block_lanes : AG_TREE_SPAN;
+    if (!ctx || !out || flags != 0 || capacity == 0 || capacity > SSA_MAX_BATCH || !is_pow2(B) || B < 2 || B > AG_TREE_SPAN)
+        return SSA_ERR_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    ssa_aggverifier *av = new ssa_aggverifier();
+    av->ctx = ctx;
+    av->capacity = capacity;
+    av->block = B;
+    // everything the object will ever hold, now: no push or finish allocates for it
+    if (av->rpts.reserve_exact(96 * capacity) || av->ppts.reserve_exact(96 * capacity) || av->h.reserve_exact(32 * capacity) ||
+        av->leaves.reserve_exact(32 * capacity) || av->bad.reserve_exact(capacity + 16) ||
+        av->tops.reserve_exact(32 * ((capacity + B - 1) / B))) {
+        (void)hipGetLastError();
+        av->release_all();
+        delete av;
+        return SSA_ERR_HIP;
+    }
+    ctx->aggverifiers.push_back(av);
+    *out = av;
+    return 0;
+}
+
+extern "C" void ssa_aggverifier_destroy(ssa_aggverifier *av) {
+    if (!av) return;
+    if (av->ctx) {
+        (void)hipSetDevice(av->ctx->device);
+        (void)hipStreamSynchronize(av->ctx->stream);
+        forget_handle(av->ctx->aggverifiers, av);
+        av->release_all();
+    }
+    delete av;
+}
+
+// Nothing on the device needs clearing: every array is written before it is read, up to `held`.
+extern "C" int ssa_aggverifier_reset(ssa_aggverifier *av) {
+    if (!av || !av->ctx) return SSA_ERR_ARG;
+    av->held = 0;
+    av->pushes = av->pushed = av->finishes = 0;
+    return 0;
+}
+
+extern "C" int ssa_aggverifier_info(ssa_aggverifier *av, uint64_t out[8]) {
+    if (!av || !av->ctx || !out) return SSA_ERR_ARG;
+    out[0] = av->held;
+    out[1] = av->capacity;
+    out[2] = av->block;
+    out[3] = av->pushes;
+    out[4] = av->pushed;
+    out[5] = 0;                       // (the lanes marked bad are known on the device alone: no read-back)
+    out[6] = av->held / av->block;
+    out[7] = av->finishes;
+    return 0;
+}
+
+// what both forms of push refuse before anything is enqueued or counted
+static int agv_push_args(const ssa_ctx *ctx, const ssa_aggverifier *av, const MsgView &mv, size_t n, const void *rs49,
+                         const void *pks) {
+    if (!ctx || !av || av->ctx != ctx || (n && (!rs49 || !pks))) return SSA_ERR_ARG;
+    if (int rc = agg_check_args(ctx, mv, n)) return rc;
+    return n > av->capacity - av->held ? SSA_ERR_ARG : 0;
+}
+
+// Only enqueues: every lane is appended, so the count is the caller's n and nothing is read back.
+extern "C" int ssa_aggverifier_push_device(ssa_ctx *ctx, ssa_aggverifier *av, const uint8_t *d_rs49, const uint8_t *d_pks,
+                                           const uint8_t *d_pk_inf, const uint8_t *d_msgs, const uint64_t *d_msg_off,
+                                           size_t msg_stride, size_t msg_len, size_t n) {
+    const MsgView mv{d_msgs, d_msg_off, msg_stride, msg_len};
+    if (int rc = agv_push_args(ctx, av, mv, n, d_rs49, d_pks)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (n == 0) {
+        av->pushes++;
+        return SSA_OK;
+    }
+    // ONE challenge hash over the n lanes: the raw digests for the leaves (ctx->ag_dig) and the scalars mod q (ctx->ws_h)
+    const u8 *d_sigs = nullptr;
+    if (int rc = ag_transcript_front(ctx, d_rs49, &d_sigs, d_pks, mv, n, true, nullptr, 1)) return rc;
+    int rc = timed_launch(ctx, "agv_k_append", [&] {
+        hipLaunchKernelGGL(agv_k_append, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, ctx->d_params, d_sigs, d_pks,
+                           d_pk_inf, (const u64 *)ctx->ag_dig.p, (const u64 *)ctx->ws_h.p, n, av->held, (u64 *)av->leaves.p,
+                           (u64 *)av->h.p, (u64 *)av->rpts.p, (u64 *)av->ppts.p, (u8 *)av->bad.p);
+    });
+    if (rc) return rc;
+    const AgxPlan p = agx_plan(av->held, n, av->block);
+    if (p.count)
+        if ((rc = agx_reduce_blocks(ctx, av->leaves, av->tops, av->block, p))) return rc;
+    // (only now: a launch that could not be enqueued leaves the object as it was -- what it wrote lies behind `held`)
+    av->held += n;
+    av->pushes++;
+    av->pushed += n;
+    return SSA_OK;
+}
+
+extern "C" int ssa_aggverifier_push(ssa_ctx *ctx, ssa_aggverifier *av, const uint8_t *rs49, const uint8_t *pks,
+                                    const uint8_t *pk_inf, const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride,
+                                    size_t msg_len, size_t n) {
+    if (int rc = agv_push_args(ctx, av, {msgs, msg_off, msg_stride, msg_len}, n, rs49, pks)) return rc;
+    if (int rc = check_host_offsets(msg_off, n)) return rc;
+    if (n == 0) return ssa_aggverifier_push_device(ctx, av, nullptr, nullptr, nullptr, nullptr, nullptr, msg_stride, msg_len, 0);
+    HostCall hc(ctx);
+    const u8 *d_rs = hc.in(ctx->st_sigs, rs49, n * 49), *d_pks = hc.in(ctx->st_pks, pks, n * 96);
+    const u8 *d_inf = pk_inf ? hc.in(ctx->st_inf, pk_inf, n) : nullptr;
+    const MsgView mv = hc.msgs(msgs, msg_off, msg_stride, msg_len, n);
+    const int rc = hc.finish([&] {
+        return ssa_aggverifier_push_device(ctx, av, d_rs, d_pks, d_inf, mv.msgs, mv.off, msg_stride, msg_len, n);
+    });
+    if (rc) return rc;
+    // nothing is copied back, so finish() did not wait: the staging buffers are free for the next call only once the
+    // kernels that read them are done
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return SSA_OK;
+}
+
+// The record of the MSM over the first n (>= 1) held lanes, at d_rec_out: the root of those lanes (agx_root), then per
+// piece of at most one MSM slice agv_k_scalars fills the bucket pipeline's inputs from the object (e = 0 on every lane: the
+// partial sums are zeroed), ssa_internal_msm_record_prepared runs the rest, and the pieces' records are added up as
+// ags_record adds them.
+static int agv_record(ssa_ctx *ctx, const ssa_aggverifier *av, size_t n, u64 *d_rec_out) {
+    const size_t piece = ags_piece(ctx), k = (n + piece - 1) / piece;
+    if (k > 4096) return SSA_ERR_ARG;
+    if (ctx->ags_recs.reserve(k * 24 * sizeof(u64))) return SSA_ERR_HIP;
+    if (int rc = agx_root(ctx, av->leaves, av->tops, av->block, n)) return rc;
+    const u64 *d_root = (const u64 *)ctx->agm_roots.p;      // (only now: agx_root reserves it)
+    for (size_t lo = 0, j = 0; j < k; lo += piece, j++) {
+        const size_t cnt = std::min(piece, n - lo);
+        const int rc = ssa_internal_msm_record_prepared(ctx, cnt, 16, [&](const MsmFill &f) {
+            return timed_launch(ctx, "agv_k_scalars", [&] {
+                (void)hipMemsetAsync(f.partials, 0, (size_t)f.n_blocks * 32, ctx->stream);
+                hipLaunchKernelGGL(agv_k_scalars, dim3(f.n_blocks), dim3(256), 0, ctx->stream, ctx->d_params, d_root,
+                                   (const u64 *)av->h.p + 4 * lo, (const u64 *)av->rpts.p + 12 * lo,
+                                   (const u64 *)av->ppts.p + 12 * lo, (const u8 *)av->bad.p + lo, cnt, (u64)lo, f.sh, f.wa,
+                                   f.points, f.digits, f.flags);
+            });
+        }, k == 1 ? (uint64_t *)d_rec_out : (uint64_t *)ctx->ags_recs.p + 24 * j);
+        if (rc) return rc;
+    }
+    return k == 1 ? 0 : ssa_internal_msm_sum_records(ctx, (const uint64_t *)ctx->ags_recs.p, k, false, (uint64_t *)d_rec_out);
+}
+
+// what finish and the debug record refuse; *n_out: the lanes taken
+static int agv_take(const ssa_ctx *ctx, const ssa_aggverifier *av, size_t n_take, size_t *n_out) {
+    if (!ctx || !av || av->ctx != ctx) return SSA_ERR_ARG;
+    *n_out = n_take == SIZE_MAX ? av->held : n_take;
+    return *n_out > av->held ? SSA_ERR_ARG : 0;
+}
+
+// Only enqueues on the context's stream: every size it needs is on the host.  Reads the object, writes workspaces of the
+// context and the caller's verdict word.
+extern "C" int ssa_aggverifier_finish_device(ssa_ctx *ctx, ssa_aggverifier *av, const uint8_t *d_e_agg, size_t n_take,
+                                             uint32_t *d_verdict_out) {
+    size_t n;
+    if (int rc = agv_take(ctx, av, n_take, &n)) return rc;
+    if (!d_e_agg || !d_verdict_out) return SSA_ERR_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (ctx->ag_misc.reserve(AG_MISC_BYTES)) return SSA_ERR_HIP;
+    av->finishes++;
+    if (n)
+        if (int rc = agv_record(ctx, av, n, (u64 *)ag_misc(ctx, AG_REC))) return rc;
+    // the exact comparison of ssa_verify_aggregate_combine_device; the empty aggregate has no record: the kernel reads none
+    return timed_launch(ctx, "ag_k_finish", [&] {
+        hipLaunchKernelGGL(ag_k_finish_scalar, dim3(1), dim3(64), 0, ctx->stream, (const u64 *)ag_misc(ctx, AG_REC), d_e_agg,
+                           n == 0 ? 1u : 0u, (const u64 *)ctx->d_gtab, d_verdict_out);
+    });
+}
+
+extern "C" int ssa_aggverifier_finish(ssa_ctx *ctx, ssa_aggverifier *av, const uint8_t *e_agg32, size_t n_take) {
+    size_t n;
+    if (int rc = agv_take(ctx, av, n_take, &n)) return rc;
+    if (!e_agg32) return SSA_ERR_ARG;
+    HostCall hc(ctx);
+    const u8 *d_e = hc.in(ctx->st_aux, e_agg32, 32);
+    uint32_t v = SSA_MALFORMED, *d_verdict = (uint32_t *)((char *)ctx->ws_fail.p + 32);
+    hc.copy_back(&v, d_verdict, sizeof v);
+    const int rc = hc.finish([&] { return ssa_aggverifier_finish_device(ctx, av, d_e, n, d_verdict); });
+    return rc ? rc : (int)v;
+}
+
+// tests: the summed record of finish without the comparison (no lanes, no record: SSA_ERR_ARG).  Only enqueues.
+extern "C" int ssa_debug_aggverifier_record(ssa_ctx *ctx, ssa_aggverifier *av, size_t n_take, uint64_t *d_record24_out) {
+    size_t n;
+    if (int rc = agv_take(ctx, av, n_take, &n)) return rc;
+    if (n == 0 || !d_record24_out || !aligned8(d_record24_out)) return SSA_ERR_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    return agv_record(ctx, av, n, (u64 *)d_record24_out);
 }
 
 // ---- several devices in one process: every device takes a contiguous run of whole blocks, block counts differ by at
@@ -3557,7 +3756,7 @@ extern "C" int ssa_debug_fault_after_chunk(ssa_ctx *ctx, int chunk) {
 // is ctab: it is no workspace but the constant-time signer's table, built once and trusted from then on (ctab_ready);
 // filling it would make every later constant-time signature wrong by design.  No other listed buffer is read by a call
 // that did not write it first (rng_seed, rng_scratch and dv_recs are wiped after each call, not kept).  What is not in
-// the list -- the comb, d_params, key sets, key caches, signer sets, streaming aggregators -- is not touched.
+// the list -- the comb, d_params, key sets, key caches, signer sets, streaming aggregators and aggregate verifiers -- is not touched.
 extern "C" int ssa_debug_poison_workspaces(ssa_ctx *ctx, int byte) {
     if (!ctx || byte < 0 || byte > 255) return SSA_ERR_ARG;
     HIP_TRY(hipSetDevice(ctx->device));

@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <string>
@@ -252,6 +253,7 @@ struct ssa_ctx {
     std::vector<struct ssa_signer_set *> signer_sets;   // live signer sets (ssa_sign.hip), orphaned the same way
     std::vector<struct ssa_keycache *> keycaches;       // live key caches, orphaned the same way
     std::vector<struct ssa_aggregator *> aggregators;   // live streaming aggregators, the same way
+    std::vector<struct ssa_aggverifier *> aggverifiers; // live streaming aggregate verifiers, the same way
 };
 
 template <class Ctx, class F>
@@ -797,6 +799,26 @@ int ssa_internal_hash_scalars_digests(ssa_ctx *ctx, const DevBatch &b, size_t n,
 // d_h: the slice's challenge scalars if they exist (batches of at most ctx->knobs.msm_small_max lanes hash for themselves)
 int ssa_internal_msm_record(ssa_ctx *ctx, const DevBatch &b, size_t n, const uint8_t *d_coeffs, uint32_t coeff_bytes,
                             const uint64_t *d_h, uint64_t *d_record_out);
+
+// defined in ssa_msm.hip, for the streaming aggregate verifier (ssa_api.hip): ONE slice of the
+// bucket pipeline -- never msm_k_small -- whose first stage is the caller's.  `fill` is called once, after the flags are
+// zeroed, and enqueues on ctx->stream whatever writes what MsmFill names for the n lanes: the 2n point rows (R_i at i,
+// -P_i at n + i, (0, 0) for the identity), the signed digits of the coefficients (coeff_bytes < 32 wide) over windows
+// [0, wa) for point i and of a_i h_i mod q over all windows for point n + i, n_blocks partial sums of a_i e_i (32 bytes
+// each), and flags[0] != 0 when a lane is malformed.  The record then comes out as ssa_internal_msm_record's.
+struct MsmFill {
+    MsmShape sh;
+    u32 wa;
+    size_t n;
+    unsigned n_blocks;
+    u64 *points;
+    short *digits;
+    u64 *partials;
+    u32 *flags;
+};
+using MsmFillFn = std::function<int(const MsmFill &)>;
+int ssa_internal_msm_record_prepared(ssa_ctx *ctx, size_t n, uint32_t coeff_bytes, const MsmFillFn &fill,
+                                     uint64_t *d_record_out);
 
 // defined in ssa_msm.hip, for the sharded half-aggregation (ssa_api.hip): k (1..4096) records added
 // up into ONE record by one wave on ctx->stream -- points, scalars mod q, malformed words OR-ed.  checked: the records

@@ -1411,6 +1411,68 @@ SSA_DEV u32 decompress_lane(const u8 *__restrict__ c, aff &out, bool &is_inf) {
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------
+// Per-lane pieces of the MSM preparation, shared by msm_k_prepare (ssa_msm.hip) and the streaming aggregate verifier
+// (ssa_aggverifier.hpp), which does the position-independent part of that work when a lane arrives
+// and the rest at block time.
+struct MsmShape {
+    u32 c;        // window bits
+    u32 windows;  // ceil(255 / c) (+ 0: the top window of a 255-bit scalar has c - 1 bits, the last carry fits)
+    u32 buckets;  // per window: 2^(c-1), for |digit| = 1 .. 2^(c-1) (signed digits; digit 0 contributes nothing)
+    u32 chunks;   // per window
+};
+
+SSA_DEV u32 sc_window(const u64 *__restrict__ k, u32 bit, u32 c) {
+    const u32 wi = bit >> 6, sh = bit & 63u;
+    if (wi > 3) return 0u;
+    u64 v = k[wi] >> sh;
+    if (sh + c > 64 && wi < 3) v |= k[wi + 1] << (64 - sh);
+    return (u32)(v & ((1ull << c) - 1ull));
+}
+
+// Signed c-bit digits, window-major: digits[j * npts + pt] in [-2^(c-1), 2^(c-1) - 1] -- every window read as a
+// two's-complement number with the carry of the window below:
+//   raw = window_j(k) + carry;  raw >= 2^(c-1): digit = raw - 2^c, carry 1.
+// Returns the carry out of the LAST window: the digits represent  k - carry_out * 2^(windows * c).  A scalar mod q
+// (< 2^255: its top window has c - 1 bits and a value below 2^(c-1) - 1) never carries out; a narrow coefficient that
+// fills its windows to the last bit may (see msm_k_prepare: the coefficient then IS the value its digits represent).
+SSA_DEV u32 write_signed_digits(const sc256 &k, u32 c, u32 windows, short *__restrict__ digits, size_t npts, size_t pt) {
+    const int half = 1 << (c - 1);
+    int carry = 0;
+#pragma unroll 1
+    for (u32 j = 0; j < windows; j++) {
+        int raw = (int)sc_window(k.w, j * c, c) + carry;
+        carry = 0;
+        if (raw >= half) {
+            raw -= 2 * half;
+            carry = 1;
+        }
+        digits[(size_t)j * npts + pt] = (short)raw;
+    }
+    return (u32)carry;
+}
+
+SSA_DEV void st_aff_row(u64 *__restrict__ row, const aff &p) {
+    st_f6(row, p.x);
+    st_f6(row + 6, p.y);
+}
+
+// The checks msm_k_prepare makes of a lane, and what they decode, in two steps (the kernel reads e between them).
+// First the key as it was loaded; ok is cleared on a non-canonical limb.
+SSA_DEV void msm_lane_key(const u8 *__restrict__ pks, size_t i, aff &P, bool &ok) {
+    P.x = ld_fp6(pks + 96 * i, ok);
+    P.y = ld_fp6(pks + 96 * i + 48, ok);
+}
+// Then, for a lane that passed so far, the key on the curve (an identity key, p_inf, is a valid PublicKey:
+// src/public.rs:95-101) and R = from_compressed(sig).unwrap() (src/batch.rs:104).  Returns "passed"; R is defined only
+// where the lane got as far as the decompression, r_inf: it decoded to the identity.
+SSA_DEV bool msm_lane_decode(bool ok, bool p_inf, const aff &P, const u8 *__restrict__ sig, aff &R, bool &r_inf) {
+    if (ok && !p_inf) ok = aff_on_curve(P);
+    r_inf = false;
+    if (ok) ok = decompress_lane(sig, R, r_inf) == 0;
+    return ok;
+}
+
 #ifndef SSA_NO_KERNELS
 __global__ void __launch_bounds__(256)
 ssa_k_decompress(const u8 *__restrict__ comp, size_t n, u8 *__restrict__ pks_out, u8 *__restrict__ inf_out,

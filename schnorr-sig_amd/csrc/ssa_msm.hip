@@ -40,13 +40,6 @@ namespace ssa {
 constexpr int MSM_CHUNK = 8;   // buckets per lane in the running-sum pass (short chains, many lanes)
 // (the tree: one cooperating wave sums ctx->knobs.msm_tree_group = 16 chunk sums -- 15 additions of ~2.2 us --: 4096 -> 256 -> 16 -> 1)
 
-struct MsmShape {
-    u32 c;        // window bits
-    u32 windows;  // ceil(255 / c) (+ 0: the top window of a 255-bit scalar has c - 1 bits, the last carry fits)
-    u32 buckets;  // per window: 2^(c-1), for |digit| = 1 .. 2^(c-1) (signed digits; digit 0 contributes nothing)
-    u32 chunks;   // per window
-};
-
 constexpr u32 MSM_TILE = 16384;         // items per tile of the grouping passes (256 threads x 64): a tile writes runs of
                                         // ~64 items (256 B) per group
 constexpr u32 MSM_HI_BINS = 256;        // groups per window: the bucket number's bits above the low 7
@@ -65,40 +58,7 @@ SSA_DEV u32 items_of_window(const MsmItems &it, u32 j) { return j < it.wa ? 2u *
 // item k of window j -> point index
 SSA_DEV u32 item_point(const MsmItems &it, u32 j, u32 k) { return j < it.wa ? k : it.n + k; }
 
-SSA_DEV u32 sc_window(const u64 *__restrict__ k, u32 bit, u32 c) {
-    const u32 wi = bit >> 6, sh = bit & 63u;
-    if (wi > 3) return 0u;
-    u64 v = k[wi] >> sh;
-    if (sh + c > 64 && wi < 3) v |= k[wi + 1] << (64 - sh);
-    return (u32)(v & ((1ull << c) - 1ull));
-}
-
-// Signed c-bit digits, window-major: digits[j * npts + pt] in [-2^(c-1), 2^(c-1) - 1] -- every window read as a
-// two's-complement number with the carry of the window below:
-//   raw = window_j(k) + carry;  raw >= 2^(c-1): digit = raw - 2^c, carry 1.
-// Returns the carry out of the LAST window: the digits represent  k - carry_out * 2^(windows * c).  A scalar mod q
-// (< 2^255: its top window has c - 1 bits and a value below 2^(c-1) - 1) never carries out; a narrow coefficient that
-// fills its windows to the last bit may (see msm_k_prepare: the coefficient then IS the value its digits represent).
-SSA_DEV u32 write_signed_digits(const sc256 &k, u32 c, u32 windows, short *__restrict__ digits, size_t npts, size_t pt) {
-    const int half = 1 << (c - 1);
-    int carry = 0;
-#pragma unroll 1
-    for (u32 j = 0; j < windows; j++) {
-        int raw = (int)sc_window(k.w, j * c, c) + carry;
-        carry = 0;
-        if (raw >= half) {
-            raw -= 2 * half;
-            carry = 1;
-        }
-        digits[(size_t)j * npts + pt] = (short)raw;
-    }
-    return (u32)carry;
-}
-
-SSA_DEV void st_aff_row(u64 *__restrict__ row, const aff &p) {
-    st_f6(row, p.x);
-    st_f6(row + 6, p.y);
-}
+// (MsmShape, sc_window, write_signed_digits, st_aff_row and the per-lane checks msm_lane_key / msm_lane_decode: ssa_kernels.hpp)
 
 // ---- 1. points and scalars ---------------------------------------------------------------------
 __global__ void __launch_bounds__(256)
@@ -123,17 +83,15 @@ msm_k_prepare(const u8 *__restrict__ sigs, const u8 *__restrict__ pks, const u8 
     if (i < n) {
         bool ok = true;
         aff P;
-        P.x = ld_fp6(pks + 96 * i, ok);
-        P.y = ld_fp6(pks + 96 * i + 48, ok);
+        msm_lane_key(pks, i, P, ok);
         const sc256 e = ld_sc(sigs + 81 * i + 49);
         ok = ok && !sc_geq_q(e);
         // an identity key is a valid PublicKey (src/public.rs:95-101); negated and fed to the MSM it adds nothing
         // (src/batch.rs:106): the (0, 0) sentinel jac_madd skips
         const bool p_inf = pk_inf && pk_inf[i];
-        if (ok && !p_inf) ok = aff_on_curve(P);
         aff R;
-        bool r_inf = false;
-        if (ok) ok = decompress_lane(sigs + 81 * i, R, r_inf) == 0;   // from_compressed(..).unwrap(), :104
+        bool r_inf;
+        ok = msm_lane_decode(ok, p_inf, P, sigs + 81 * i, R, r_inf);
         if (recheck) {
             ok = ok && lane_mask[i] == 0;
             recheck[i] = (u8)(ok ? 0u : 1u);
@@ -1309,36 +1267,13 @@ static int msm_run_small(ssa_ctx *ctx, const DevBatch &b, size_t n, const uint8_
     return msm_combine_records(ctx, recs, count, d_verdict_out, d_partial_out);
 }
 
-// the kernels of one MSM-form slice on ctx->stream: a verdict (d_partial_out == nullptr) or the slice's / shard's record
-// d_h: the challenge scalars if they exist already, else nullptr (they are computed into ctx->ws_h)
-// scr != nullptr: the screened form -- (window, segment, digit) buckets, a per-lane status, one verdict per segment in
-// scr->seg_ok (no verdict, no record)
-static int msm_run_one(ssa_ctx *ctx, const DevBatch &b, size_t n, const uint8_t *d_coeffs, uint32_t coeff_bytes,
-                       uint32_t *d_verdict_out, u64 *d_partial_out, const u64 *d_h, const ScreenArgs *scr = nullptr) {
-    if (n > (1ull << 23)) return SSA_ERR_ARG;   // an item carries its point index in 24 bits: 2n <= 2^24 (msm_run slices)
-    if (n == 0) {   // empty batch: Ok (src/batch.rs); an empty shard adds the identity and 0
-        if (d_partial_out) {
-            hipLaunchKernelGGL(msm_k_empty_record, dim3(1), dim3(64), 0, ctx->stream, d_partial_out);
-            HIP_TRY(hipGetLastError());
-            return 0;
-        }
-        HIP_TRY(hipMemsetAsync(d_verdict_out, 0, sizeof(uint32_t), ctx->stream));
-        return 0;
-    }
-    if (!d_coeffs) {   // Scalar::random(rng): the library draws 128-bit coefficients
-        const void *p;
-        if (int rc = msm_draw_coefficients(ctx, n, &p)) return rc;
-        d_coeffs = (const uint8_t *)p;
-        coeff_bytes = 16;
-    }
-    if (!scr && n <= ctx->knobs.msm_small_max)
-        return msm_run_small(ctx, b, n, d_coeffs, coeff_bytes, d_verdict_out, d_partial_out);
-    const MsmShape sh = scr ? screen_shape(scr->segs) : msm_shape(n);
-    // windows the coefficients themselves can reach (32-byte ones are reduced mod q: all of them).  A narrower coefficient
-    // whose width is a whole number of windows is read as a TWO'S-COMPLEMENT integer (msm_k_prepare): its signed digits
-    // then need no carry window -- which would hold the digit 1 for half of the points, one enormous bucket -- and a
-    // random coefficient is as good signed as unsigned (the same value multiplies R_i, h_i and e_i).
-    const u32 wa = coeff_bytes >= 32 ? sh.windows : (8u * coeff_bytes + sh.c - 1) / sh.c;
+// One slice of the bucket pipeline on ctx->stream, with the stage that fills it handed in: `fill` enqueues whatever writes
+// the 2n point rows (R_i at i, -P_i at n + i), the signed digits (window-major; the R's over their lowest wa windows, the
+// keys over all), the per-workgroup partial sums of s_i e_i and the malformed word of the flags (zeroed here, in front of
+// it); then sort, buckets and reduce run over them.  msm_run_one's preparation is one such stage, the streaming aggregate
+// verifier's agv_k_scalars (ssa_api.hip) the other.
+static int msm_run_prepared(ssa_ctx *ctx, size_t n, const MsmShape &sh, u32 wa, uint32_t *d_verdict_out, u64 *d_partial_out,
+                            const ScreenArgs *scr, const MsmFillFn &fill) {
     MsmItems it;
     it.n = (u32)n;
     it.wa = wa;
@@ -1354,7 +1289,7 @@ static int msm_run_one(ssa_ctx *ctx, const DevBatch &b, size_t n, const uint8_t 
     const u32 n_tiles = it.tile0[sh.windows], tmax = (u32)((2 * n + MSM_TILE - 1) / MSM_TILE);
     const size_t npts = 2 * n, total = it.base[sh.windows], nb = (size_t)sh.windows * sh.buckets;
     const unsigned n_blocks = grid_for(n, 256);
-    if ((!d_h && ctx->ws_h.reserve(n * 32)) || ctx->msm_points.reserve(npts * 96) ||
+    if (ctx->msm_points.reserve(npts * 96) ||
         ctx->msm_scalars.reserve(npts * sh.windows * sizeof(short)) ||                 // signed digits, window-major
         ctx->msm_keys.reserve((size_t)sh.windows * MSM_HI_BINS * tmax * 4) ||          // per-tile group counts / positions
         ctx->msm_vals.reserve(total * 4) ||                                            // items by group: point | low bits | sign
@@ -1370,50 +1305,9 @@ static int msm_run_one(ssa_ctx *ctx, const DevBatch &b, size_t n, const uint8_t 
         ctx->msm_partials.reserve((size_t)n_blocks * 32) || ctx->msm_flags.reserve(64))
         return SSA_ERR_HIP;
     HIP_TRY(hipMemsetAsync(ctx->msm_flags.p, 0, 64, ctx->stream));
-    int rc = 0;
-    if (!d_h && ctx->knobs.msm_overlap) {
-        // The challenge hashes are 62 % of this form and nothing but the digits of s_i h_i needs them: the rest of the
-        // preparation (R's square roots above all) runs on a second stream UNDER ssa_k_hash -- its waves fill the hash
-        // kernel's tail (the last wave of every SIMD alone, 0.35 ms) and the hash fills theirs --, ctx->stream joins it
-        // after the hash and writes the digits that were missing.
-        // Until msm_k_prepare_h is queued behind it, an error return waits for msm_k_prepare: it writes msm_points,
-        // msm_scalars, msm_sbuf and msm_flags.
-        if (ctx->msm_sbuf.reserve(n * 32)) return SSA_ERR_HIP;
-        hipStream_t side = ctx->hash_stream[0];
-        HIP_TRY(hipEventRecord(ctx->pipe_start, ctx->stream));
-        HIP_TRY(hipStreamWaitEvent(side, ctx->pipe_start, 0));
-        SideStreamDrain drain{ctx};
-        hipLaunchKernelGGL(msm_k_prepare, dim3(n_blocks), dim3(256), 0, side, b.sigs, b.pks, b.pk_inf,
-                           (const u64 *)nullptr, d_coeffs, coeff_bytes, n, sh, wa, (u64 *)ctx->msm_points.p,
-                           (short *)ctx->msm_scalars.p, (u64 *)ctx->msm_partials.p, (u32 *)ctx->msm_flags.p,
-                           (u64 *)ctx->msm_sbuf.p, scr ? scr->status : (u8 *)nullptr,
-                           scr ? scr->lane_mask : (const u8 *)nullptr, scr ? scr->recheck : (u8 *)nullptr);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(ctx->hash_done[0], side));
-        if (int hrc = ssa_internal_hash_scalars(ctx, b, n)) return hrc;
-        d_h = (const u64 *)ctx->ws_h.p;
-        HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->hash_done[0], 0));
-        rc = timed_launch(ctx, "msm_k_prepare", [&] {
-            hipLaunchKernelGGL(msm_k_prepare_h, dim3(n_blocks), dim3(256), 0, ctx->stream, d_h, (const u64 *)ctx->msm_sbuf.p,
-                               n, sh, (short *)ctx->msm_scalars.p);
-        });
-        if (rc) return rc;
-        drain.done();
-    } else {
-        // challenge scalars h_i with the kernel of the per-lane path
-        if (!d_h) {
-            if (int hrc = ssa_internal_hash_scalars(ctx, b, n)) return hrc;
-            d_h = (const u64 *)ctx->ws_h.p;
-        }
-        rc = timed_launch(ctx, "msm_k_prepare", [&] {
-            hipLaunchKernelGGL(msm_k_prepare, dim3(n_blocks), dim3(256), 0, ctx->stream, b.sigs, b.pks, b.pk_inf,
-                               d_h, d_coeffs, coeff_bytes, n, sh, wa, (u64 *)ctx->msm_points.p,
-                               (short *)ctx->msm_scalars.p, (u64 *)ctx->msm_partials.p, (u32 *)ctx->msm_flags.p,
-                               (u64 *)nullptr, scr ? scr->status : (u8 *)nullptr,
-                               scr ? scr->lane_mask : (const u8 *)nullptr, scr ? scr->recheck : (u8 *)nullptr);
-        });
-        if (rc) return rc;
-    }
+    int rc = fill({sh, wa, n, n_blocks, (u64 *)ctx->msm_points.p, (short *)ctx->msm_scalars.p, (u64 *)ctx->msm_partials.p,
+                   (u32 *)ctx->msm_flags.p});
+    if (rc) return rc;
     rc = timed_launch(ctx, "msm_sort", [&] {
         hipLaunchKernelGGL(scr ? msm_k_hist_seg : msm_k_hist, dim3(n_tiles), dim3(256), 0, ctx->stream,
                            (const short *)ctx->msm_scalars.p, it, tmax, (u32 *)ctx->msm_keys.p);
@@ -1473,10 +1367,103 @@ static int msm_run_one(ssa_ctx *ctx, const DevBatch &b, size_t n, const uint8_t 
     });
 }
 
+// the kernels of one MSM-form slice on ctx->stream: a verdict (d_partial_out == nullptr) or the slice's / shard's record
+// d_h: the challenge scalars if they exist already, else nullptr (they are computed into ctx->ws_h)
+// scr != nullptr: the screened form -- (window, segment, digit) buckets, a per-lane status, one verdict per segment in
+// scr->seg_ok (no verdict, no record)
+static int msm_run_one(ssa_ctx *ctx, const DevBatch &b, size_t n, const uint8_t *d_coeffs, uint32_t coeff_bytes,
+                       uint32_t *d_verdict_out, u64 *d_partial_out, const u64 *d_h, const ScreenArgs *scr = nullptr) {
+    if (n > (1ull << 23)) return SSA_ERR_ARG;   // an item carries its point index in 24 bits: 2n <= 2^24 (msm_run slices)
+    if (n == 0) {   // empty batch: Ok (src/batch.rs); an empty shard adds the identity and 0
+        if (d_partial_out) {
+            hipLaunchKernelGGL(msm_k_empty_record, dim3(1), dim3(64), 0, ctx->stream, d_partial_out);
+            HIP_TRY(hipGetLastError());
+            return 0;
+        }
+        HIP_TRY(hipMemsetAsync(d_verdict_out, 0, sizeof(uint32_t), ctx->stream));
+        return 0;
+    }
+    if (!d_coeffs) {   // Scalar::random(rng): the library draws 128-bit coefficients
+        const void *p;
+        if (int rc = msm_draw_coefficients(ctx, n, &p)) return rc;
+        d_coeffs = (const uint8_t *)p;
+        coeff_bytes = 16;
+    }
+    if (!scr && n <= ctx->knobs.msm_small_max)
+        return msm_run_small(ctx, b, n, d_coeffs, coeff_bytes, d_verdict_out, d_partial_out);
+    const MsmShape sh = scr ? screen_shape(scr->segs) : msm_shape(n);
+    // windows the coefficients themselves can reach (32-byte ones are reduced mod q: all of them).  A narrower coefficient
+    // whose width is a whole number of windows is read as a TWO'S-COMPLEMENT integer (msm_k_prepare): its signed digits
+    // then need no carry window -- which would hold the digit 1 for half of the points, one enormous bucket -- and a
+    // random coefficient is as good signed as unsigned (the same value multiplies R_i, h_i and e_i).
+    const u32 wa = coeff_bytes >= 32 ? sh.windows : (8u * coeff_bytes + sh.c - 1) / sh.c;
+    if (!d_h && ctx->ws_h.reserve(n * 32)) return SSA_ERR_HIP;
+    const unsigned n_blocks = grid_for(n, 256);
+    return msm_run_prepared(ctx, n, sh, wa, d_verdict_out, d_partial_out, scr, [&](const MsmFill &) -> int {
+        int rc = 0;
+        if (!d_h && ctx->knobs.msm_overlap) {
+            // The challenge hashes are 62 % of this form and nothing but the digits of s_i h_i needs them: the rest of the
+            // preparation (R's square roots above all) runs on a second stream UNDER ssa_k_hash -- its waves fill the hash
+            // kernel's tail (the last wave of every SIMD alone, 0.35 ms) and the hash fills theirs --, ctx->stream joins it
+            // after the hash and writes the digits that were missing.
+            // Until msm_k_prepare_h is queued behind it, an error return waits for msm_k_prepare: it writes msm_points,
+            // msm_scalars, msm_sbuf and msm_flags.
+            if (ctx->msm_sbuf.reserve(n * 32)) return SSA_ERR_HIP;
+            hipStream_t side = ctx->hash_stream[0];
+            HIP_TRY(hipEventRecord(ctx->pipe_start, ctx->stream));
+            HIP_TRY(hipStreamWaitEvent(side, ctx->pipe_start, 0));
+            SideStreamDrain drain{ctx};
+            hipLaunchKernelGGL(msm_k_prepare, dim3(n_blocks), dim3(256), 0, side, b.sigs, b.pks, b.pk_inf,
+                               (const u64 *)nullptr, d_coeffs, coeff_bytes, n, sh, wa, (u64 *)ctx->msm_points.p,
+                               (short *)ctx->msm_scalars.p, (u64 *)ctx->msm_partials.p, (u32 *)ctx->msm_flags.p,
+                               (u64 *)ctx->msm_sbuf.p, scr ? scr->status : (u8 *)nullptr,
+                               scr ? scr->lane_mask : (const u8 *)nullptr, scr ? scr->recheck : (u8 *)nullptr);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipEventRecord(ctx->hash_done[0], side));
+            if (int hrc = ssa_internal_hash_scalars(ctx, b, n)) return hrc;
+            d_h = (const u64 *)ctx->ws_h.p;
+            HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->hash_done[0], 0));
+            rc = timed_launch(ctx, "msm_k_prepare", [&] {
+                hipLaunchKernelGGL(msm_k_prepare_h, dim3(n_blocks), dim3(256), 0, ctx->stream, d_h, (const u64 *)ctx->msm_sbuf.p,
+                                   n, sh, (short *)ctx->msm_scalars.p);
+            });
+            if (rc) return rc;
+            drain.done();
+        } else {
+            // challenge scalars h_i with the kernel of the per-lane path
+            if (!d_h) {
+                if (int hrc = ssa_internal_hash_scalars(ctx, b, n)) return hrc;
+                d_h = (const u64 *)ctx->ws_h.p;
+            }
+            rc = timed_launch(ctx, "msm_k_prepare", [&] {
+                hipLaunchKernelGGL(msm_k_prepare, dim3(n_blocks), dim3(256), 0, ctx->stream, b.sigs, b.pks, b.pk_inf,
+                                   d_h, d_coeffs, coeff_bytes, n, sh, wa, (u64 *)ctx->msm_points.p,
+                                   (short *)ctx->msm_scalars.p, (u64 *)ctx->msm_partials.p, (u32 *)ctx->msm_flags.p,
+                                   (u64 *)nullptr, scr ? scr->status : (u8 *)nullptr,
+                                   scr ? scr->lane_mask : (const u8 *)nullptr, scr ? scr->recheck : (u8 *)nullptr);
+            });
+            if (rc) return rc;
+        }
+        return 0;
+    });
+}
+
 int ssa_internal_msm_record(ssa_ctx *ctx, const DevBatch &b, size_t n, const uint8_t *d_coeffs, uint32_t coeff_bytes,
                             const uint64_t *d_h, uint64_t *d_record_out) {
     if (!d_coeffs || !d_record_out || n > ctx->knobs.msm_slice) return SSA_ERR_ARG;
     return msm_run_one(ctx, b, n, d_coeffs, coeff_bytes, nullptr, (u64 *)d_record_out, (const u64 *)d_h);
+}
+
+// Always the bucket pipeline, whatever n is: msm_k_small hashes and decompresses for itself, which is what the caller of
+// this entry has done already.  msm_shape gives 8-bit windows below 4096 lanes, and the grouping passes take any n >= 1
+// (contexts with SSA_MSM_SMALL_MAX=0 drive them at n = 1): no floor is needed.
+int ssa_internal_msm_record_prepared(ssa_ctx *ctx, size_t n, uint32_t coeff_bytes, const MsmFillFn &fill,
+                                     uint64_t *d_record_out) {
+    if (!fill || !d_record_out || n == 0 || n > ctx->knobs.msm_slice || n > (1ull << 23) || coeff_bytes == 0 ||
+        coeff_bytes >= 32)
+        return SSA_ERR_ARG;
+    const MsmShape sh = msm_shape(n);
+    return msm_run_prepared(ctx, n, sh, (8u * coeff_bytes + sh.c - 1) / sh.c, nullptr, (u64 *)d_record_out, nullptr, fill);
 }
 
 int ssa_internal_msm_sum_records(ssa_ctx *ctx, const uint64_t *d_records, size_t k, bool checked, uint64_t *d_record_out) {

@@ -938,6 +938,66 @@ class Aggregator {
     ssa_aggregator *ag_ = nullptr;
 };
 
+// A streaming aggregate verifier on the device (ssa_aggverifier_create): push the R's, keys and
+// messages of a block body as they arrive, finish with e_agg.  push appends EVERY lane -- a validator cannot drop one, its
+// place is part of the transcript --; finish gives what AggregateSignature::verify gives the first n_take lanes handed in
+// at once with that scalar, and changes nothing, so it may be repeated, take prefixes, and be followed by more pushes.
+// Belongs to the context it was made on.
+class AggregateVerifier {
+  public:
+    struct Info {
+        uint64_t held, capacity, block_lanes, pushes, pushed, reserved, blocks, finishes;
+    };
+    static constexpr size_t All = SIZE_MAX;       // finish: every lane held
+    // block_lanes: 0 (512) or a power of two from 2 to 512.  All device memory, about 257 bytes per lane, is allocated here.
+    AggregateVerifier(Context &cx, size_t capacity, size_t block_lanes = 0) : cx_(cx) {
+        const int rc = ssa_aggverifier_create(cx.get(), capacity, block_lanes, 0u, &av_);
+        if (rc != 0) throw std::runtime_error(std::string("ssa_aggverifier_create: ") + ssa_strerror(rc));
+    }
+    ~AggregateVerifier() { ssa_aggverifier_destroy(av_); }
+    AggregateVerifier(const AggregateVerifier &) = delete;
+    AggregateVerifier &operator=(const AggregateVerifier &) = delete;
+    ssa_aggverifier *get() const { return av_; }
+    // rs49: the R's of public_keys.size() lanes side by side, 49 bytes each (the head of an aggregate's bytes).  A slice
+    // that does not fit what is left of the capacity throws and changes nothing.
+    void push(const uint8_t *rs49, const std::vector<PublicKey> &public_keys,
+              const std::vector<std::pair<const uint8_t *, size_t>> &messages) {
+        const size_t n = public_keys.size();
+        const PackedTriples t = pack_triples(std::vector<Signature>(n), public_keys, messages);
+        const int rc = ssa_aggverifier_push(cx_.get(), av_, rs49, t.pks.data(), t.inf.data(), t.flat.data(), t.off.data(),
+                                            0, 0, n);
+        if (rc != 0) throw std::runtime_error(std::string("ssa_aggverifier_push: ") + ssa_strerror(rc));
+    }
+    // the R's of an aggregate; its scalar is not kept: hand it to finish
+    void push(const AggregateSignature &agg, const std::vector<PublicKey> &public_keys,
+              const std::vector<std::pair<const uint8_t *, size_t>> &messages) {
+        if (agg.size() != public_keys.size()) throw Panic("We should have the same number of signatures than public keys");
+        push(agg.bytes.data(), public_keys, messages);
+    }
+    // the status word: SSA_OK, SSA_INVALID_SIGNATURE or SSA_MALFORMED
+    int finish_status(const uint8_t e_agg[32], size_t n_take = All) const {
+        const int rc = ssa_aggverifier_finish(cx_.get(), av_, e_agg, n_take);
+        if (rc < 0) throw std::runtime_error(std::string("ssa_aggverifier_finish: ") + ssa_strerror(rc));
+        return rc;
+    }
+    // as AggregateSignature::verify: nullopt (Ok), InvalidSignature, or Panic thrown for a malformed lane or scalar
+    Result finish(const uint8_t e_agg[32], size_t n_take = All) const { return status_to_result(finish_status(e_agg, n_take)); }
+    void reset() {
+        const int rc = ssa_aggverifier_reset(av_);
+        if (rc != 0) throw std::runtime_error(std::string("ssa_aggverifier_reset: ") + ssa_strerror(rc));
+    }
+    Info info() const {
+        uint64_t v[8] = {};
+        const int rc = ssa_aggverifier_info(av_, v);
+        if (rc != 0) throw std::runtime_error(std::string("ssa_aggverifier_info: ") + ssa_strerror(rc));
+        return {v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]};
+    }
+
+  private:
+    Context &cx_;
+    ssa_aggverifier *av_ = nullptr;
+};
+
 // AggregateSignature::verify_many through a key cache
 namespace detail {
 struct PackedAggregates {

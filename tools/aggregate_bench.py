@@ -76,6 +76,11 @@ Every timed output is compared with the aggregates of the single call, batch by 
 --accumulator measures the streaming aggregator: --n honest signatures pushed in --pushes equal
 pushes, then ssa_aggregator_finish_device against ssa_aggregate_many_sliced_device of --baseline-lib over the same
 signatures, legs alternating; the pushes' own times and ssa_aggregate_valid_many_device at --n are recorded beside it.
+
+--verifier measures the streaming aggregate verifier: the R's, keys and messages of --n honest
+signatures pushed in --pushes equal pushes, then ssa_aggverifier_finish_device against
+ssa_verify_aggregate_sliced_device of --baseline-lib over the same lanes, legs alternating; the pushes' own times, the
+kernels of one push and of finish, and finish at 256 and 2048 lanes beside ssa_verify_aggregate_device are recorded.
 """
 import argparse
 import hashlib
@@ -1143,6 +1148,187 @@ def accumulator_main(a):
     return 0 if res["mismatches"] == 0 else 1
 
 
+VERIFIER_KERNELS = ("ag_k_expand", "ssa_k_hash", "agv_k_append", "ag_k_level", "ag_k_tree", "agv_k_scalars", "msm_sort",
+                    "msm_k_buckets", "msm_reduce", "msm_k_sum_records", "ag_k_finish")
+
+
+class BaselineValidator:
+    """ssa_verify_aggregate_sliced_device and ssa_verify_aggregate_device of a build of the library given by its path, on a
+    context of its own"""
+
+    def __init__(self, path):
+        import ctypes as C
+        self.C, self.lib = C, C.CDLL(path)
+        vp, sz, i32 = C.c_void_p, C.c_size_t, C.c_int
+        self.lib.ssa_ctx_create_ex.argtypes = [C.POINTER(vp), i32, vp, sz, C.c_uint32, C.c_uint64]
+        for name in ("ssa_verify_aggregate_sliced_device", "ssa_verify_aggregate_device"):
+            getattr(self.lib, name).argtypes = [vp, vp, vp, vp, vp, vp, sz, sz, sz, vp]
+        self.lib.ssa_ctx_sync.argtypes = [vp]
+        self.lib.ssa_ctx_destroy.argtypes = [vp]
+        self.lib.ssa_ctx_destroy.restype = None
+        self.ctx = vp()
+        if self.lib.ssa_ctx_create_ex(C.byref(self.ctx), 0, None, 0, 0, 0) != 0:
+            raise RuntimeError("baseline library: ssa_ctx_create_ex failed")
+
+    def sliced(self, d_agg, d_pks, d_msgs, n, d_verdict):
+        if self.lib.ssa_verify_aggregate_sliced_device(self.ctx, d_agg, d_pks, None, d_msgs, None, 80, 80, n, d_verdict) != 0:
+            raise RuntimeError("baseline library: ssa_verify_aggregate_sliced_device failed")
+
+    def single(self, d_agg, d_pks, d_msgs, n, d_verdict):
+        if self.lib.ssa_verify_aggregate_device(self.ctx, d_agg, d_pks, None, d_msgs, None, 80, 80, n, d_verdict) != 0:
+            raise RuntimeError("baseline library: ssa_verify_aggregate_device failed")
+
+    def sync(self):
+        self.lib.ssa_ctx_sync(self.ctx)
+
+    def close(self):
+        self.lib.ssa_ctx_destroy(self.ctx)
+
+
+def verifier_main(a):
+    """--verifier: the streaming aggregate verifier.  The block body of --n honest signatures over
+    80-byte messages (R's, keys, messages: device buffers) is pushed in --pushes equal pushes; then the legs alternate in
+    one process:
+      finish            ssa_aggverifier_finish_device and a stream synchronisation: what is left once e_agg is known
+      baseline_sliced   ssa_verify_aggregate_sliced_device through --baseline-lib (a build of the parent commit; without
+                        it, this tree's own library) over the same lanes: the fastest one-shot validator call
+      pushes            reset and all the pushes again, each one timed: their sum (recorded only)
+    Every timed verdict is checked.  The bar: finish < baseline_sliced, by more than baseline_sliced differs between two
+    processes.  Recorded beside it: the kernels of finish and of one push, and finish at 256 and 2048 lanes against
+    ssa_verify_aggregate_device of the same library (the price of always taking the bucket path)."""
+    import torch
+    import schnorr_sig_amd as ssa
+    dev = torch.device("cuda", 0)
+    eng = ssa.Engine(0)
+    base_path = a.baseline_lib or ssa.LIB_PATH
+    base = BaselineValidator(base_path)
+    n, k = a.n, a.pushes
+    if n % k:
+        raise SystemExit("--verifier: --n must be a multiple of --pushes")
+    per = n // k
+    rng = np.random.default_rng(a.seed)
+    msgs = rng.integers(0, 256, (n, 80), dtype=np.uint8)
+    pks, sigs = eng.keygen_sign_many(_scalars(rng, n), _scalars(rng, n), msgs)
+    t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)   # noqa: E731
+    d_sigs, d_pks, d_msgs = t(sigs), t(pks), t(msgs)
+    d_agg = torch.zeros(49 * n + 32, dtype=torch.uint8, device=dev)
+    d_verdict = torch.full((1,), 255, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+    if eng.aggregate_sliced_device(d_sigs.data_ptr(), d_pks.data_ptr(), d_msgs.data_ptr(), n, 80, d_agg.data_ptr()) != 0:
+        raise SystemExit("--verifier: the honest batch did not aggregate")
+    eng.sync()
+    d_rs = d_agg[:49 * n].view(n, 49)
+    d_e = d_agg[49 * n:]
+    del d_sigs
+    sha = lambda path: hashlib.sha256(open(path, "rb").read()).hexdigest()[:16]   # noqa: E731
+    res = {"metric": "aggregate_verifier", "n": n, "pushes": k, "msg_len": 80, "rounds": a.rounds, "warmup": a.warmup,
+           "library_sha256": sha(ssa.LIB_PATH), "baseline_sha256": sha(base_path), "baseline_is_this_tree": not a.baseline_lib,
+           "device": torch.cuda.get_device_name(0), "date": time.strftime("%Y-%m-%d"), "mismatches": 0}
+    ptrs = (d_agg.data_ptr(), d_pks.data_ptr(), d_msgs.data_ptr())
+    av = eng.aggregate_verifier(n)
+
+    def wall(fn, sync):
+        sync()
+        t0 = time.perf_counter()
+        fn()
+        sync()
+        return (time.perf_counter() - t0) * 1e3
+
+    def push_all(obj=av, count=n, each=per):
+        """reset, then every push timed on its own -> their times"""
+        obj.reset()
+        out = []
+        for lo in range(0, count, each):
+            sl = slice(lo, min(lo + each, count))
+            out.append(wall(lambda: obj.push_device(d_rs[sl], d_pks[sl], d_msgs[sl]), eng.sync))
+        if obj.info()["held"] != count:
+            res["mismatches"] += 1
+        return out
+
+    def checked(ms):
+        res["mismatches"] += 0 if int(d_verdict.item()) == 0 else 1
+        return ms
+
+    push_all()
+    push_ms, times = [], {"finish": [], "baseline_sliced": [], "pushes": []}
+    for rnd in range(a.warmup + a.rounds):
+        for leg in times:
+            d_verdict.fill_(255)
+            torch.cuda.synchronize()
+            if leg == "finish":
+                ms = checked(wall(lambda: av.finish_device(d_e, d_verdict), eng.sync))
+            elif leg == "baseline_sliced":
+                ms = checked(wall(lambda: base.sliced(*ptrs, n, d_verdict.data_ptr()), base.sync))
+            else:
+                each = push_all()
+                ms = float(np.sum(each))
+                if rnd >= a.warmup:
+                    push_ms.append(each)
+                av.finish_device(d_e, d_verdict)
+                eng.sync()
+                checked(ms)
+            if rnd >= a.warmup:
+                times[leg].append(ms)
+    med = res["ms_median"] = {leg: round(float(np.median(v)), 3) for leg, v in times.items()}
+    res["ms_all"] = {leg: [round(x, 3) for x in v] for leg, v in times.items()}
+    res["push_ms_median_by_position"] = [round(float(x), 3) for x in np.median(np.array(push_ms), axis=0)]
+    res["ratio"] = {"finish/baseline_sliced": round(med["finish"] / med["baseline_sliced"], 4),
+                    "(pushes+finish)/baseline_sliced": round((med["pushes"] + med["finish"]) / med["baseline_sliced"], 4)}
+    res["finish_faster_than_baseline_sliced"] = bool(med["finish"] < med["baseline_sliced"])
+
+    def timed(fn):
+        eng.sync()
+        eng.enable_timing(True)
+        fn()
+        eng.sync()
+        out = {}
+        for kn in VERIFIER_KERNELS:
+            avg, cnt = eng.read_timing(kn)
+            if cnt:
+                out[kn] = [round(avg, 4), int(cnt)]
+        eng.enable_timing(False)
+        return out
+
+    kern = {"finish": timed(lambda: av.finish_device(d_e, d_verdict))}
+    av.reset()
+    kern["push"] = timed(lambda: av.push_device(d_rs[:per], d_pks[:per], d_msgs[:per]))
+    res["kernel_ms_avg_launches"] = kern
+    av.close()
+
+    # small aggregates: finish always takes the bucket path, the one-shot call takes msm_k_small up to 3072 lanes
+    small = {}
+    for m in (256, 2048):
+        if m > n:
+            continue
+        d_small = torch.zeros(49 * m + 32, dtype=torch.uint8, device=dev)
+        d_sg = t(sigs[:m])
+        if eng.aggregate_device(d_sg.data_ptr(), d_pks.data_ptr(), d_msgs.data_ptr(), m, 80, d_small.data_ptr()) != 0:
+            res["mismatches"] += 1
+        eng.sync()
+        sv = eng.aggregate_verifier(m)
+        sv.push_device(d_small[:49 * m].view(m, 49), d_pks[:m], d_msgs[:m])
+        eng.sync()
+        st = {"finish": [], "baseline_single": []}
+        for rnd in range(a.warmup + a.rounds):
+            for leg in st:
+                d_verdict.fill_(255)
+                torch.cuda.synchronize()
+                if leg == "finish":
+                    ms = checked(wall(lambda: sv.finish_device(d_small[49 * m:], d_verdict), eng.sync))
+                else:
+                    ms = checked(wall(lambda: base.single(d_small.data_ptr(), d_pks.data_ptr(), d_msgs.data_ptr(), m,
+                                                          d_verdict.data_ptr()), base.sync))
+                if rnd >= a.warmup:
+                    st[leg].append(ms)
+        small[str(m)] = {leg: round(float(np.median(v)), 4) for leg, v in st.items()}
+        sv.close()
+    res["small_ms_median"] = small
+    print(json.dumps(res))
+    eng.close()
+    base.close()
+    return 0 if res["mismatches"] == 0 else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1 << 20)
@@ -1173,8 +1359,14 @@ def main():
     ap.add_argument("--accumulator", action="store_true",
                     help="ssa_aggregator_finish_device after --pushes pushes against ssa_aggregate_many_sliced_device of "
                          "--baseline-lib over the same --n signatures")
-    ap.add_argument("--pushes", type=int, default=16, help="--accumulator: equal pushes the --n signatures arrive in")
+    ap.add_argument("--verifier", action="store_true",
+                    help="ssa_aggverifier_finish_device after --pushes pushes against ssa_verify_aggregate_sliced_device of "
+                         "--baseline-lib over the same --n lanes")
+    ap.add_argument("--pushes", type=int, default=16,
+                    help="--accumulator, --verifier: equal pushes the --n signatures arrive in")
     a = ap.parse_args()
+    if a.verifier:
+        return verifier_main(a)
     if a.accumulator:
         return accumulator_main(a)
     if a.produce_many:
