@@ -1258,8 +1258,8 @@ int ssa_debug_aggregator_plan(uint64_t held, uint64_t m, uint64_t block_lanes, u
  * byte, and the top of every complete block of block_lanes leaves.  finish pays one permutation and one multiplication
  * per lane, the bucket MSM and the exact comparison.  It belongs to the context it was created on, like a key cache.
  *   create   capacity: 1 .. SSA_MAX_BATCH lanes; block_lanes: 0 (the default, 512) or a power of two from 2 to 512;
- *            flags: 0.  Anything else: SSA_ERR_ARG.  All device memory is allocated here -- 96 + 96 + 32 + 32 + 1 bytes
- *            per lane and 32 bytes per block: about 257 bytes per lane -- and is the object's own: destroy releases it,
+ *            flags: 0.  Anything else: SSA_ERR_ARG.  All device memory is allocated here -- 96 + 96 + 32 + 32 + 1 + 1
+ *            bytes per lane and 32 bytes per block: about 258 bytes per lane -- and is the object's own: destroy releases it,
  *            or ssa_ctx_destroy (the handle then stays valid for destroy and is refused everywhere else).
  *   push     n R's at stride 49 (the aggregate's wire layout), their keys, pk_inf (may be NULL) and messages, as
  *            ssa_verify_aggregate takes them.  ALL n lanes are appended: a validator cannot drop a lane, its place is
@@ -1275,9 +1275,39 @@ int ssa_debug_aggregator_plan(uint64_t held, uint64_t m, uint64_t block_lanes, u
  *            pushes.  The host form returns the status; the _device form only enqueues and the status lands in the
  *            uint32 at d_verdict_out.  Always the bucket MSM, whatever n_take is.
  *   reset    empties the object (counters included) and keeps its memory.
- *   info     [0] lanes held  [1] capacity  [2] block_lanes  [3] pushes  [4] lanes pushed  [5] 0 (lanes that failed a
- *            check are known on the device alone: nothing is read back)  [6] blocks whose top is stored  [7] finishes.
- * NOT here: admission through a key cache (the subgroup check), ssa_multi forms, removing lanes from the front. */
+ *   info     [0] lanes held  [1] capacity  [2] block_lanes  [3] pushes  [4] lanes pushed  [5] lanes pushed through a key
+ *            cache (below; 0 for an object that sees plain pushes only.  Lanes that failed a check are known on the
+ *            device alone: nothing is read back)  [6] blocks whose top is stored  [7] finishes.
+ * NOT here: ssa_multi forms, removing lanes from the front.
+ *
+ * Through a key cache, subgroup check included.  The plain push verifies under verify_batch
+ * semantics: a key P + T with T of small order can pass.  The cached pushes put the key cache of sections 16, 18, 19 and
+ * 23 in front: every distinct key is checked (limbs, curve, [q]P) once and then found, a wire key is decompressed once,
+ * and the object keeps ONE MORE byte per lane, the key's status (258 bytes per lane in all).
+ *   push_cached(_device)       n affine keys (96 bytes each, optional pk_inf), an affine cache;
+ *   push_cached_wire(_device)  n dense 49-byte keys, a cache made with SSA_KEYCACHE_WIRE: the host form uploads 49
+ *                              bytes per key instead of 97, and U (section 23) is what ssa_decompress_many gives.
+ * The contract is section 23's equality.  If the first n held lanes were all pushed through a cache,
+ *   finish(e_agg, n) == ssa_verify_aggregates_many_cached(_wire) with k = 1, counts = {n} and
+ *                       aggs = R_0 || ... || R_(n-1) || e_agg on the same keys and messages:
+ * SSA_INVALID_PUBLIC_KEY if some lane i < n has key status SSA_INVALID_PUBLIC_KEY, else exactly what finish returns
+ * without the cache.  The key decides, also over a malformed R or a wrong e_agg in the same prefix; n_take == 0 keeps
+ * the rule of the empty aggregate; exact (no screen), in every state of the cache (cold, warm, partly warm, cleared or
+ * compacted between two slices of one push, bypassed).  finish, finish_device and ssa_debug_aggverifier_record keep
+ * their signatures, and the record is the same: the key status never enters the MSM.
+ * MIXING: plain and cached pushes may be mixed in one object.  A lane of a plain push carries key status 0, "not
+ * checked": it never answers SSA_INVALID_PUBLIC_KEY, whatever its key is, and the equality above speaks only of prefixes
+ * whose lanes all came through a cache (info word [5] == word [4] says so for the whole object).  An object that never
+ * sees a cached push enqueues exactly what it did before these entry points existed.
+ * Errors, all SSA_ERR_ARG, the object, the cache and info unchanged: a NULL cache, a cache of the other mode, of
+ * another context or orphaned, and everything the plain push refuses.  n == 0 counts a push and touches neither the
+ * cache nor the object.  A push is never applied in part (the cache may have taken keys from a push that then failed
+ * with SSA_ERR_HIP: the state ssa_verify_many_cached leaves too, and harmless).
+ * stats_out (8 words, HOST memory in both forms, may be NULL): words [0] .. [5] of section 23, summed over the slices of
+ * this push; [6] = [7] = 0, nothing about verdicts is known before finish.
+ * The _device forms SYNCHRONISE the context's stream once per slice of SSA_LANE_SLICE lanes (the key dedup's read-back,
+ * as in ssa_verify_aggregates_many_cached_device) and only enqueue behind that; a caller that passes stats_out waits
+ * once more, at the end, for the device's part of word [5].  The plain push_device stays enqueue-only. */
 typedef struct ssa_aggverifier ssa_aggverifier;
 int ssa_aggverifier_create(ssa_ctx *ctx, size_t capacity, size_t block_lanes, uint32_t flags, ssa_aggverifier **out);
 void ssa_aggverifier_destroy(ssa_aggverifier *av);
@@ -1294,6 +1324,22 @@ int ssa_aggverifier_finish_device(ssa_ctx *ctx, ssa_aggverifier *av, const uint8
 /* tests: the 24-word record finish compares with [e_agg]G -- the sum of the pieces' records -- at device address
  * d_record24_out (8-byte aligned), without the comparison.  Only enqueues.  n_take == 0 (no record): SSA_ERR_ARG. */
 int ssa_debug_aggverifier_record(ssa_ctx *ctx, ssa_aggverifier *av, size_t n_take, uint64_t *d_record24_out);
+int ssa_aggverifier_push_cached(ssa_ctx *ctx, ssa_aggverifier *av, ssa_keycache *kc, const uint8_t *rs49, const uint8_t *pks,
+                                const uint8_t *pk_inf, const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride,
+                                size_t msg_len, size_t n, uint64_t stats_out[8]);
+int ssa_aggverifier_push_cached_device(ssa_ctx *ctx, ssa_aggverifier *av, ssa_keycache *kc, const uint8_t *d_rs49,
+                                       const uint8_t *d_pks, const uint8_t *d_pk_inf, const uint8_t *d_msgs,
+                                       const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len, size_t n,
+                                       uint64_t stats_out[8]);
+int ssa_aggverifier_push_cached_wire(ssa_ctx *ctx, ssa_aggverifier *av, ssa_keycache *kc, const uint8_t *rs49,
+                                     const uint8_t *pks49, const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride,
+                                     size_t msg_len, size_t n, uint64_t stats_out[8]);
+int ssa_aggverifier_push_cached_wire_device(ssa_ctx *ctx, ssa_aggverifier *av, ssa_keycache *kc, const uint8_t *d_rs49,
+                                            const uint8_t *d_pks49, const uint8_t *d_msgs, const uint64_t *d_msg_off,
+                                            size_t msg_stride, size_t msg_len, size_t n, uint64_t stats_out[8]);
+/* tests: the lanes of key statuses one workgroup of finish's fold takes (AGV_KST_SPAN): its edges are where a fold of a
+ * long prefix can lose a byte */
+size_t ssa_debug_aggverifier_key_span(void);
 
 /* ---- ABI version -------------------------------------------------------------------------------------------
  * Bumped whenever an exported signature changes (round 2 inserted pk_inf into the batch entry points under the same

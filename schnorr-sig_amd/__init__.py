@@ -310,6 +310,11 @@ def _load():
         "ssa_aggverifier_finish": (i32, [vp, vp, vp, sz]),
         "ssa_aggverifier_finish_device": (i32, [vp, vp, vp, sz, vp]),
         "ssa_debug_aggverifier_record": (i32, [vp, vp, sz, vp]),
+        "ssa_aggverifier_push_cached": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, vp]),
+        "ssa_aggverifier_push_cached_device": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, vp]),
+        "ssa_aggverifier_push_cached_wire": (i32, [vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, vp]),
+        "ssa_aggverifier_push_cached_wire_device": (i32, [vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, vp]),
+        "ssa_debug_aggverifier_key_span": (sz, []),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)      # AttributeError here == ABI symbol missing: fail loudly
@@ -606,7 +611,7 @@ class Engine:
 
     def aggregate_verifier(self, capacity, block_lanes=0):
         """a streaming aggregate verifier of `capacity` lanes on this engine's device: push the
-        R's, keys and messages of a block body as they arrive, finish with e_agg.  All of its device memory, about 257
+        R's, keys and messages of a block body as they arrive, finish with e_agg.  All of its device memory, about 258
         bytes per lane, is allocated here.  block_lanes: 0 (512) or a power of two from 2 to 512."""
         h = C.c_void_p()
         _check(_lib.ssa_aggverifier_create(self._ctx, int(capacity), int(block_lanes), 0, C.byref(h)),
@@ -1775,7 +1780,14 @@ class KeyCache(_KeyTables):
 AGGR_NO_SCREEN = 1    # SSA_AGGR_NO_SCREEN
 AGGREGATOR_FIELDS = ("held", "capacity", "block_lanes", "pushes", "offered", "dropped", "blocks", "finishes")
 AGGVERIFIER_FIELDS = ("held", "capacity", "block_lanes", "pushes", "pushed", "reserved", "blocks", "finishes")
+#   ("reserved" is word [5] of ssa_aggverifier_info: since section 29 the lanes pushed through a key cache, 0 for an
+#    object that sees plain pushes only; the name stays, AggregateVerifier.cached_lanes() reads it)
 AGGREGATOR_ALL = (1 << (8 * C.sizeof(C.c_size_t))) - 1      # SIZE_MAX: finish every lane held
+
+
+def aggverifier_key_span():
+    """tests: AGV_KST_SPAN, the lanes of key statuses one workgroup of the keyed finish's fold takes"""
+    return int(_lib.ssa_debug_aggverifier_key_span())
 
 
 def aggregator_plan(held, m, block_lanes=0):
@@ -1901,37 +1913,110 @@ class AggregateVerifier:
         _check(_lib.ssa_aggverifier_info(self.handle, out), "ssa_aggverifier_info")
         return dict(zip(AGGVERIFIER_FIELDS, (int(v) for v in out)))
 
+    def cached_lanes(self):
+        """the lanes pushed through a key cache since create or reset (word [5] of ssa_aggverifier_info)"""
+        return self.info()["reserved"]
+
     def __len__(self):
         return self.info()["held"]
 
-    def push(self, rs49, pks, msgs, offsets=None, pk_inf=None, engine=None):
+    def push(self, rs49, pks, msgs, offsets=None, pk_inf=None, engine=None, cache=None):
         """n R's (n x 49 bytes, the aggregate's wire layout), keys and messages as Engine.verify_aggregate takes them:
         ALL n lanes are appended (a lane that fails a check makes every finish that takes it MALFORMED).  A batch that
         does not fit what is left of the capacity raises and changes nothing.  engine: tests (a context other than the
-        object's).  Returns n."""
+        object's).  Returns n.
+        cache: an AFFINE KeyCache -- every distinct key is checked once, subgroup check included,
+        and a finish that takes a lane whose key is outside the subgroup answers INVALID_PUBLIC_KEY.  Then returns
+        (n, stats uint64[8]): words [0..5] of Engine.verify_aggregates_cached, [6] = [7] = 0.  Lanes pushed without a
+        cache are "not checked" and never answer so; both kinds may be mixed in one object."""
         eng = engine or self.engine
         n, batch, keep = eng._agg_batch(rs49, 49, pks, msgs, offsets, pk_inf)
-        _check(_lib.ssa_aggverifier_push(eng._ctx, self.handle, *batch), "ssa_aggverifier_push")
-        return n
+        if cache is None:
+            _check(_lib.ssa_aggverifier_push(eng._ctx, self.handle, *batch), "ssa_aggverifier_push")
+            return n
+        if cache.wire:
+            raise ValueError("push takes affine keys and an affine key cache: push_wire takes the 49-byte keys")
+        stats = np.zeros(8, dtype=np.uint64)
+        _check(_lib.ssa_aggverifier_push_cached(eng._ctx, self.handle, cache.handle, *batch, stats.ctypes.data),
+               "ssa_aggverifier_push_cached")
+        return n, stats
 
-    def push_aggregate(self, agg, pks, msgs, offsets=None, pk_inf=None):
+    def push_wire(self, rs49, pks49, msgs, offsets=None, cache=None, engine=None):
+        """push with n dense 49-byte keys through a key cache made with wire=True (required): a key is decompressed
+        once, when the cache first sees it.  -> (n, stats uint64[8]) as push(cache=...)."""
+        if cache is None or not cache.wire:
+            raise ValueError("push_wire needs a key cache made with wire=True")
+        eng = engine or self.engine
+        keys = _np_u8(pks49, 49)
+        n = keys.shape[0]
+        lead = _np_u8(rs49).reshape(-1)
+        if lead.size not in (49 * n, 49 * n + 32):
+            raise MalformedInput("We should have the same number of signatures than public keys")
+        m, off, stride, mlen = eng._msg_args(msgs, offsets, n) if n else (None, None, 0, 0)
+        stats = np.zeros(8, dtype=np.uint64)
+        _check(_lib.ssa_aggverifier_push_cached_wire(eng._ctx, self.handle, cache.handle, _ptr(lead), _ptr(keys) if n else None,
+                                                     _ptr(m), _ptr(off), stride, mlen, n, stats.ctypes.data),
+               "ssa_aggverifier_push_cached_wire")
+        return n, stats
+
+    def push_aggregate(self, agg, pks, msgs, offsets=None, pk_inf=None, cache=None):
         """the R's of an AggregateSignature (or its 49 n + 32 bytes) with their keys and messages; e_agg is not kept:
-        hand it to finish().  Returns n."""
+        hand it to finish().  Returns n; with a cache (affine keys and an affine cache, or 49-byte keys and a wire
+        cache) what push(cache=...) / push_wire return."""
         b = np.frombuffer(agg.bytes if isinstance(agg, AggregateSignature) else bytes(agg), np.uint8)
-        return self.push(b[:b.size - 32], pks, msgs, offsets=offsets, pk_inf=pk_inf)
+        if cache is not None and cache.wire:
+            if pk_inf is not None:
+                raise ValueError("pk_inf does not go with wire keys: the 49 bytes carry the identity flag")
+            return self.push_wire(b[:b.size - 32], pks, msgs, offsets=offsets, cache=cache)
+        return self.push(b[:b.size - 32], pks, msgs, offsets=offsets, pk_inf=pk_inf, cache=cache)
 
-    def push_device(self, d_rs49, d_pks, d_msgs, d_pk_inf=None, d_offsets=None, msg_len=None, msg_stride=None):
-        """device form over torch tensors on the engine's device: d_rs49 (n, 49), d_pks (n, 96), d_msgs an (n, len)
-        uint8 tensor (or flat bytes with a uint64-valued d_offsets and msg_len left None).  Only enqueues.  Returns n."""
-        n = int(d_pks.shape[0])
+    def _push_device_args(self, d_keys, d_msgs, d_offsets, msg_len, msg_stride, width):
+        have = 0 if d_keys is None else d_keys.numel() * d_keys.element_size()
+        if have % width:
+            raise ValueError("the keys are %d bytes each" % width)
         if d_offsets is None and msg_len is None:
-            msg_len = d_msgs.shape[1] if d_msgs.dim() == 2 else 0
+            msg_len = d_msgs.shape[1] if d_msgs is not None and d_msgs.dim() == 2 else 0
         msg_len = msg_len or 0
+        return have // width, msg_stride if msg_stride is not None else msg_len, msg_len
+
+    def push_device(self, d_rs49, d_pks, d_msgs, d_pk_inf=None, d_offsets=None, msg_len=None, msg_stride=None, cache=None,
+                    want_stats=True):
+        """device form over torch tensors on the engine's device: d_rs49 (n, 49), d_pks (n, 96), d_msgs an (n, len)
+        uint8 tensor (or flat bytes with a uint64-valued d_offsets and msg_len left None).  Only enqueues.  Returns n.
+        cache: an affine KeyCache, as push().  Then the call synchronises the stream once per slice of SSA_LANE_SLICE
+        lanes (the key dedup's read-back), with want_stats once more at the end, and returns (n, stats or None)."""
         addr = lambda t: t.data_ptr() if t is not None and t.numel() else None    # noqa: E731
-        _check(_lib.ssa_aggverifier_push_device(
-            self.engine._ctx, self.handle, addr(d_rs49), addr(d_pks), addr(d_pk_inf), addr(d_msgs), addr(d_offsets),
-            msg_stride if msg_stride is not None else msg_len, msg_len, n), "ssa_aggverifier_push_device")
-        return n
+        if cache is None:
+            n = int(d_pks.shape[0])
+            if d_offsets is None and msg_len is None:
+                msg_len = d_msgs.shape[1] if d_msgs.dim() == 2 else 0
+            msg_len = msg_len or 0
+            _check(_lib.ssa_aggverifier_push_device(
+                self.engine._ctx, self.handle, addr(d_rs49), addr(d_pks), addr(d_pk_inf), addr(d_msgs), addr(d_offsets),
+                msg_stride if msg_stride is not None else msg_len, msg_len, n), "ssa_aggverifier_push_device")
+            return n
+        if cache.wire:
+            raise ValueError("push_device takes affine keys and an affine key cache: push_wire_device takes the 49-byte keys")
+        n, stride, mlen = self._push_device_args(d_pks, d_msgs, d_offsets, msg_len, msg_stride, 96)
+        stats = np.zeros(8, dtype=np.uint64) if want_stats else None
+        _check(_lib.ssa_aggverifier_push_cached_device(
+            self.engine._ctx, self.handle, cache.handle, addr(d_rs49), addr(d_pks), addr(d_pk_inf), addr(d_msgs),
+            addr(d_offsets), stride, mlen, n, stats.ctypes.data if want_stats else None), "ssa_aggverifier_push_cached_device")
+        return n, stats
+
+    def push_wire_device(self, d_rs49, d_pks49, d_msgs, d_offsets=None, msg_len=None, msg_stride=None, cache=None,
+                         want_stats=True):
+        """device form of push_wire: d_pks49 holds n x 49 bytes -> (n, stats or None).  Synchronises as
+        push_device(cache=...)."""
+        if cache is None or not cache.wire:
+            raise ValueError("push_wire_device needs a key cache made with wire=True")
+        addr = lambda t: t.data_ptr() if t is not None and t.numel() else None    # noqa: E731
+        n, stride, mlen = self._push_device_args(d_pks49, d_msgs, d_offsets, msg_len, msg_stride, 49)
+        stats = np.zeros(8, dtype=np.uint64) if want_stats else None
+        _check(_lib.ssa_aggverifier_push_cached_wire_device(
+            self.engine._ctx, self.handle, cache.handle, addr(d_rs49), addr(d_pks49), addr(d_msgs), addr(d_offsets), stride,
+            mlen, n, stats.ctypes.data if want_stats else None), "ssa_aggverifier_push_cached_wire_device")
+        return n, stats
 
     def finish(self, e_agg, n_take=None):
         """-> the int status of the first n_take held lanes (None: all) under e_agg (32 bytes): OK, INVALID_SIGNATURE or

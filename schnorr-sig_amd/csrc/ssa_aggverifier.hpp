@@ -11,6 +11,14 @@
 //   leaves  four words per lane: leaf_i
 //   bad     one byte per lane: nonzero iff the lane failed one of msm_k_prepare's checks
 //   tops    four words per COMPLETE block of B lanes: the top of its subtree
+//   kst     one byte per lane: the status of the lane's key as the key cache gave it (0, SSA_INVALID_PUBLIC_KEY,
+//           SSA_MALFORMED), 0 = "not checked" for a lane of a plain push.  RULE: kst is read only
+//           while the host flag `keyed` is on, and then every byte of kst[0, held) has been written by the push that
+//           brought its lane.  `keyed` turns on at the first push through a cache, which zeroes kst[0, held) on the
+//           context's stream first; from then on the cached pushes write their lanes' bytes through agc_k_expand and
+//           the plain push writes its n bytes with one hipMemsetAsync; reset turns it off.  So bytes that a failed push
+//           left behind `held`, or that an earlier life of the object left anywhere, are overwritten before they can be
+//           read as a status, and an object that never sees a cached push enqueues exactly what it did without kst.
 //
 //   push    ag_transcript_front (expand to stride 81, ONE ssa_k_hash: raw digests and scalars mod q) -> agv_k_append
 //           stores leaf, scalar, the two point rows and the bad byte of each lane -> the blocks this push completed are
@@ -20,18 +28,21 @@
 //           at most one MSM slice agv_k_scalars derives a_i, writes the digits of a_i and a_i h_i and copies the stored
 //           rows into the MSM's workspaces; sort, buckets and reduce run unchanged (ssa_internal_msm_record_prepared); the
 //           pieces' records are added up and compared exactly with [e_agg]G (ag_k_finish_scalar).  finish changes nothing
-//           in the object.
+//           in the object.  A keyed object then folds kst[0, n) into the verdict word (agv_k_key_verdict): the key
+//           decides, as in ssa_verify_aggregates_many_cached.  The key status never enters the MSM: the record is the same.
 //
-// The object's six arrays are its own allocations (released by destroy, or by the context's clean-up): they are not in
+// The object's seven arrays are its own allocations (released by destroy, or by the context's clean-up): they are not in
 // the context's list of workspaces, and nothing the object needs between two calls lives in one.
 #pragma once
+#include "ssa_aggcache.hpp"
 #include "ssa_aggregator.hpp"
 
 struct ssa_aggverifier {
     ssa_ctx *ctx = nullptr;   // nullptr: the context is gone, the device memory went with it
     size_t capacity = 0, block = 0, held = 0;     // block: B, a power of two from 2 to AG_TREE_SPAN
-    uint64_t pushes = 0, pushed = 0, finishes = 0;
-    DevBuf rpts, ppts, h, leaves, bad, tops;
+    uint64_t pushes = 0, pushed = 0, finishes = 0, cached = 0;     // cached: lanes pushed through a key cache
+    bool keyed = false;                           // kst[0, held) is valid and finish folds it (the rule above)
+    DevBuf rpts, ppts, h, leaves, bad, tops, kst;
     void release_all() {
         rpts.release();
         ppts.release();
@@ -39,10 +50,16 @@ struct ssa_aggverifier {
         leaves.release();
         bad.release();
         tops.release();
+        kst.release();
     }
 };
 
 namespace ssa {
+
+// lanes of kst one workgroup of agv_k_key_verdict folds: 256 threads x 16 bytes x 2 steps.  2^20 lanes are 128
+// workgroups; a multiple of 4096, so that every span but the last is whole 16-byte steps of the whole workgroup.
+constexpr u32 AGV_KST_SPAN = 8192;
+static_assert(AGV_KST_SPAN % 4096 == 0, "whole steps of 256 threads x 16 bytes");
 
 #ifndef SSA_NO_KERNELS
 // One lane per pushed lane: lane i of the push (sigs: its R's at stride 81 with e = 0, as ag_k_expand lays them out),
@@ -131,6 +148,22 @@ agv_k_scalars(const DevParams *__restrict__ prm, const u64 *__restrict__ root, c
         is_bad = bad[i] != 0;
     }
     if (__ballot(is_bad) != 0 && (threadIdx.x & 63u) == 0) atomicOr(malformed, 1u);
+}
+
+// Behind ag_k_finish_scalar, for a keyed object and n >= 1: *verdict = SSA_INVALID_PUBLIC_KEY iff some byte of kst[0, n)
+// says so; otherwise the word is left as the comparison wrote it.  One prefix of up to 2^30 bytes, where
+// agc_k_key_verdicts would fold a long aggregate with one workgroup: workgroup b scans kst[b SPAN, min((b + 1) SPAN, n))
+// with agc_scan (16-byte loads over the aligned middle -- a span starts at a multiple of 16, so only the tail of the
+// last one is ragged), one __ballot per wave, and lane 0 of every wave that saw the status stores the value: several
+// writers, one value, ordinary vector stores -- no atomic, no LDS, no barrier.  It reads kst alone, which no launch of a
+// finish writes.
+__global__ void __launch_bounds__(256)
+agv_k_key_verdict(const u8 *__restrict__ kst, size_t n, u32 *__restrict__ verdict) {
+    const size_t base = (size_t)blockIdx.x * AGV_KST_SPAN;
+    if (base >= n) return;       // (never: the grid is ceil(n / SPAN); uniform for the workgroup)
+    const u32 cnt = n - base < AGV_KST_SPAN ? (u32)(n - base) : AGV_KST_SPAN;
+    const bool any = __ballot(agc_scan(kst + base, 0u, cnt, threadIdx.x, 256u)) != 0ull;
+    if (any && (threadIdx.x & 63u) == 0) *verdict = AGC_BAD_KEY;
 }
 #endif  // SSA_NO_KERNELS
 

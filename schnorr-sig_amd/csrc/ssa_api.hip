@@ -2813,7 +2813,7 @@ extern "C" int ssa_aggverifier_create(ssa_ctx *ctx, size_t capacity, size_t bloc
     // everything the object will ever hold, now: no push or finish allocates for it
     if (av->rpts.reserve_exact(96 * capacity) || av->ppts.reserve_exact(96 * capacity) || av->h.reserve_exact(32 * capacity) ||
         av->leaves.reserve_exact(32 * capacity) || av->bad.reserve_exact(capacity + 16) ||
-        av->tops.reserve_exact(32 * ((capacity + B - 1) / B))) {
+        av->tops.reserve_exact(32 * ((capacity + B - 1) / B)) || av->kst.reserve_exact(capacity + 16)) {
         (void)hipGetLastError();
         av->release_all();
         delete av;
@@ -2835,11 +2835,13 @@ extern "C" void ssa_aggverifier_destroy(ssa_aggverifier *av) {
     delete av;
 }
 
-// Nothing on the device needs clearing: every array is written before it is read, up to `held`.
+// Nothing on the device needs clearing: every array is written before it is read, up to `held` (kst: the rule of
+// ssa_aggverifier.hpp -- with `keyed` off its bytes are not read until the next cached push has zeroed or written them).
 extern "C" int ssa_aggverifier_reset(ssa_aggverifier *av) {
     if (!av || !av->ctx) return SSA_ERR_ARG;
     av->held = 0;
-    av->pushes = av->pushed = av->finishes = 0;
+    av->pushes = av->pushed = av->finishes = av->cached = 0;
+    av->keyed = false;
     return 0;
 }
 
@@ -2850,7 +2852,7 @@ extern "C" int ssa_aggverifier_info(ssa_aggverifier *av, uint64_t out[8]) {
     out[2] = av->block;
     out[3] = av->pushes;
     out[4] = av->pushed;
-    out[5] = 0;                       // (the lanes marked bad are known on the device alone: no read-back)
+    out[5] = av->cached;              // lanes pushed through a key cache (the lanes marked bad are known on the device alone)
     out[6] = av->held / av->block;
     out[7] = av->finishes;
     return 0;
@@ -2864,17 +2866,11 @@ static int agv_push_args(const ssa_ctx *ctx, const ssa_aggverifier *av, const Ms
     return n > av->capacity - av->held ? SSA_ERR_ARG : 0;
 }
 
-// Only enqueues: every lane is appended, so the count is the caller's n and nothing is read back.
-extern "C" int ssa_aggverifier_push_device(ssa_ctx *ctx, ssa_aggverifier *av, const uint8_t *d_rs49, const uint8_t *d_pks,
-                                           const uint8_t *d_pk_inf, const uint8_t *d_msgs, const uint64_t *d_msg_off,
-                                           size_t msg_stride, size_t msg_len, size_t n) {
-    const MsgView mv{d_msgs, d_msg_off, msg_stride, msg_len};
-    if (int rc = agv_push_args(ctx, av, mv, n, d_rs49, d_pks)) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (n == 0) {
-        av->pushes++;
-        return SSA_OK;
-    }
+// The body of every push behind its argument checks, n >= 1 lanes over the keys U = d_pks / d_pk_inf as agv_k_append
+// reads them (the caller's, or what a wire cache expanded).  through_cache: the lanes' kst bytes are already written
+// (agc_k_expand, enqueued in front); otherwise a keyed object gets them zeroed here.  Only enqueues.
+static int agv_push_body(ssa_ctx *ctx, ssa_aggverifier *av, const u8 *d_rs49, const u8 *d_pks, const u8 *d_pk_inf,
+                         const MsgView &mv, size_t n, bool through_cache) {
     // ONE challenge hash over the n lanes: the raw digests for the leaves (ctx->ag_dig) and the scalars mod q (ctx->ws_h)
     const u8 *d_sigs = nullptr;
     if (int rc = ag_transcript_front(ctx, d_rs49, &d_sigs, d_pks, mv, n, true, nullptr, 1)) return rc;
@@ -2887,11 +2883,28 @@ extern "C" int ssa_aggverifier_push_device(ssa_ctx *ctx, ssa_aggverifier *av, co
     const AgxPlan p = agx_plan(av->held, n, av->block);
     if (p.count)
         if ((rc = agx_reduce_blocks(ctx, av->leaves, av->tops, av->block, p))) return rc;
+    // a plain push into a keyed object: its lanes' keys are "not checked"
+    if (av->keyed && !through_cache) HIP_TRY(hipMemsetAsync((u8 *)av->kst.p + av->held, 0, n, ctx->stream));
     // (only now: a launch that could not be enqueued leaves the object as it was -- what it wrote lies behind `held`)
     av->held += n;
     av->pushes++;
     av->pushed += n;
+    if (through_cache) av->cached += n;
     return SSA_OK;
+}
+
+// Only enqueues: every lane is appended, so the count is the caller's n and nothing is read back.
+extern "C" int ssa_aggverifier_push_device(ssa_ctx *ctx, ssa_aggverifier *av, const uint8_t *d_rs49, const uint8_t *d_pks,
+                                           const uint8_t *d_pk_inf, const uint8_t *d_msgs, const uint64_t *d_msg_off,
+                                           size_t msg_stride, size_t msg_len, size_t n) {
+    const MsgView mv{d_msgs, d_msg_off, msg_stride, msg_len};
+    if (int rc = agv_push_args(ctx, av, mv, n, d_rs49, d_pks)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (n == 0) {
+        av->pushes++;
+        return SSA_OK;
+    }
+    return agv_push_body(ctx, av, d_rs49, d_pks, d_pk_inf, mv, n, false);
 }
 
 extern "C" int ssa_aggverifier_push(ssa_ctx *ctx, ssa_aggverifier *av, const uint8_t *rs49, const uint8_t *pks,
@@ -2960,11 +2973,19 @@ extern "C" int ssa_aggverifier_finish_device(ssa_ctx *ctx, ssa_aggverifier *av, 
     if (n)
         if (int rc = agv_record(ctx, av, n, (u64 *)ag_misc(ctx, AG_REC))) return rc;
     // the exact comparison of ssa_verify_aggregate_combine_device; the empty aggregate has no record: the kernel reads none
-    return timed_launch(ctx, "ag_k_finish", [&] {
+    const int rc = timed_launch(ctx, "ag_k_finish", [&] {
         hipLaunchKernelGGL(ag_k_finish_scalar, dim3(1), dim3(64), 0, ctx->stream, (const u64 *)ag_misc(ctx, AG_REC), d_e_agg,
                            n == 0 ? 1u : 0u, (const u64 *)ctx->d_gtab, d_verdict_out);
     });
+    if (rc || !av->keyed || n == 0) return rc;       // (no lane, no key: the rule of the empty aggregate stands)
+    // the key decides: the fold of the key statuses of the prefix, behind the comparison
+    return timed_launch(ctx, "agv_k_key_verdict", [&] {
+        hipLaunchKernelGGL(agv_k_key_verdict, dim3(grid_for(n, AGV_KST_SPAN)), dim3(256), 0, ctx->stream,
+                           (const u8 *)av->kst.p, n, d_verdict_out);
+    });
 }
+
+extern "C" size_t ssa_debug_aggverifier_key_span(void) { return AGV_KST_SPAN; }
 
 extern "C" int ssa_aggverifier_finish(ssa_ctx *ctx, ssa_aggverifier *av, const uint8_t *e_agg32, size_t n_take) {
     size_t n;
@@ -3518,6 +3539,137 @@ extern "C" int ssa_verify_aggregates_many_cached_wire(ssa_ctx *ctx, ssa_keycache
                                                       size_t msg_len, uint32_t *verdicts_out, uint64_t stats_out[8]) {
     return agc_host(ctx, kc, aggs, counts, k, pks49, nullptr, true, msgs, msg_off, msg_stride, msg_len, verdicts_out,
                     stats_out);
+}
+
+// ------------------------------------------------------------------ the streaming verifier through a key cache
+// The cache in front of the push of section 28, as agc_run puts it in front of agm_run: the n lanes go through the
+// cache in slices of at most lane_slice lanes, and behind each slice, before the next one may clear or compact the
+// cache, agc_k_expand writes the lanes' key statuses into the OBJECT (kst + held + lo) and, for wire keys, the keys and
+// flags into the context's n-lane buffers.  Then the push body of section 28 unchanged over U.  The first cached push of
+// an object turns `keyed` on behind a zeroing of kst[0, held) (the rule in ssa_aggverifier.hpp).  `held` moves in the
+// body, behind the last launch: a push that fails on the way leaves the object's lanes as they were (the cache may have
+// taken keys, as after a failed ssa_verify_many_cached).  sv: words 0..4 of the statistics and the host's part of word
+// 5; the device's part is ctx->agc_cnt[AGC_CNT_UNPUB].  One synchronisation per slice, the dedup's.
+static int agv_push_cached_run(ssa_ctx *ctx, ssa_aggverifier *av, ssa_keycache *kc, const u8 *d_rs49, const u8 *d_keys,
+                               const u8 *d_pk_inf, bool wire, const MsgView &mv, size_t n, uint64_t *sv) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (ctx->agc_cnt.reserve(64) || (wire && (ctx->agc_pks.reserve(n * 96 + 16) || ctx->agc_inf.reserve(n + 16))))
+        return SSA_ERR_HIP;
+    unsigned long long *d_cnt = (unsigned long long *)ctx->agc_cnt.p;
+    HIP_TRY(hipMemsetAsync(d_cnt, 0, AGC_CNT_WORDS * sizeof(unsigned long long), ctx->stream));
+    if (!av->keyed) {
+        if (av->held) HIP_TRY(hipMemsetAsync(av->kst.p, 0, av->held, ctx->stream));
+        av->keyed = true;
+    }
+    u8 *kst = (u8 *)av->kst.p + av->held, *u_inf = wire ? (u8 *)ctx->agc_inf.p : nullptr;
+    u64 *u_pks = wire ? (u64 *)ctx->agc_pks.p : nullptr;
+    const size_t slice = ctx->knobs.lane_slice;
+    for (size_t lo = 0; lo < n; lo += slice) {
+        const size_t cnt = n - lo < slice ? n - lo : slice;
+        const KeySource src = wire ? KeySource{nullptr, nullptr, d_keys + 49 * lo, 49}
+                                   : KeySource{d_keys + 96 * lo, d_pk_inf ? d_pk_inf + lo : nullptr, nullptr};
+        KeyView kv{};
+        KeyRows rows{};
+        uint64_t u = 0, hits = 0, ks[4] = {0, 0, 0, 0};
+        const unsigned long long *d_unpub = nullptr;
+        if (int rc = keycache_slice(ctx, kc, src, cnt, nullptr, &kv, &u, &hits, ks, &d_unpub, &rows)) return rc;
+        const int rc = timed_launch(ctx, "agc_expand", [&] {
+            hipLaunchKernelGGL(agc_k_expand, dim3(grid_for(wire ? cnt * 12 : cnt, 256)), dim3(256), 0, ctx->stream, kv.lane_key,
+                               kv.status, wire ? rows.pks : (const u64 *)nullptr, rows.inf, kv.n_keys, (u32)cnt, kst + lo,
+                               wire ? u_pks + 12 * lo : (u64 *)nullptr, wire ? u_inf + lo : (u8 *)nullptr, d_unpub, d_cnt);
+        });
+        if (rc) return rc;
+        sv[0] += u;
+        for (int w = 0; w < 4; w++) sv[1 + w] += ks[w];
+        sv[5] += hits;
+    }
+    return agv_push_body(ctx, av, d_rs49, wire ? (const u8 *)u_pks : d_keys, wire ? (const u8 *)u_inf : d_pk_inf, mv, n, true);
+}
+
+// what all four cached pushes refuse before anything is enqueued, counted or written
+static int agv_push_cached_args(const ssa_ctx *ctx, const ssa_aggverifier *av, const ssa_keycache *kc, bool wire,
+                                const MsgView &mv, size_t n, const void *rs49, const void *keys) {
+    if (int rc = agc_check_cache(ctx, kc, wire)) return rc;
+    return agv_push_args(ctx, av, mv, n, rs49, keys);
+}
+
+// words 0..5 of section 23's statistics; [6] and [7] stay 0: nothing about verdicts is known before finish
+static void agv_stats_out(uint64_t stats_out[8], const uint64_t sv[8], unsigned long long unpublished) {
+    if (!stats_out) return;
+    for (int w = 0; w < 8; w++) stats_out[w] = w < 6 ? sv[w] : 0;
+    stats_out[5] += unpublished;
+}
+
+static int agv_push_cached_dev(ssa_ctx *ctx, ssa_aggverifier *av, ssa_keycache *kc, const u8 *d_rs49, const u8 *d_keys,
+                               const u8 *d_pk_inf, bool wire, const MsgView &mv, size_t n, uint64_t stats_out[8]) {
+    if (int rc = agv_push_cached_args(ctx, av, kc, wire, mv, n, d_rs49, d_keys)) return rc;
+    uint64_t sv[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    agv_stats_out(stats_out, sv, 0);
+    if (n == 0) {
+        av->pushes++;
+        return SSA_OK;
+    }
+    if (int rc = agv_push_cached_run(ctx, av, kc, d_rs49, d_keys, d_pk_inf, wire, mv, n, sv)) return rc;
+    if (!stats_out) return SSA_OK;
+    // the one word the device counted: read behind the push, the one extra wait of a caller that asks
+    unsigned long long cnt[AGC_CNT_WORDS] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(cnt, ctx->agc_cnt.p, sizeof cnt, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    agv_stats_out(stats_out, sv, cnt[AGC_CNT_UNPUB]);
+    return SSA_OK;
+}
+
+static int agv_push_cached_host(ssa_ctx *ctx, ssa_aggverifier *av, ssa_keycache *kc, const uint8_t *rs49,
+                                const uint8_t *keys, const uint8_t *pk_inf, bool wire, const uint8_t *msgs,
+                                const uint64_t *msg_off, size_t msg_stride, size_t msg_len, size_t n, uint64_t stats_out[8]) {
+    if (int rc = agv_push_cached_args(ctx, av, kc, wire, {msgs, msg_off, msg_stride, msg_len}, n, rs49, keys)) return rc;
+    if (int rc = check_host_offsets(msg_off, n)) return rc;
+    uint64_t sv[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    agv_stats_out(stats_out, sv, 0);
+    if (n == 0) {
+        av->pushes++;
+        return SSA_OK;
+    }
+    HostCall hc(ctx);
+    const u8 *d_rs = hc.in(ctx->st_sigs, rs49, n * 49);
+    const u8 *d_keys = wire ? hc.in(ctx->st_keyed, keys, n * 49) : hc.in(ctx->st_pks, keys, n * 96);
+    const u8 *d_inf = pk_inf ? hc.in(ctx->st_inf, pk_inf, n) : nullptr;
+    const MsgView mv = hc.msgs(msgs, msg_off, msg_stride, msg_len, n);
+    unsigned long long cnt[AGC_CNT_WORDS] = {0, 0};
+    (void)hc.out(ctx->agc_cnt, cnt, sizeof cnt, 48);      // (copied back behind the push: finish() waits for it, and with
+                                                          //  it for the kernels that read the staging buffers)
+    if (int rc = hc.finish([&] { return agv_push_cached_run(ctx, av, kc, d_rs, d_keys, d_inf, wire, mv, n, sv); })) return rc;
+    agv_stats_out(stats_out, sv, cnt[AGC_CNT_UNPUB]);
+    return SSA_OK;
+}
+
+extern "C" int ssa_aggverifier_push_cached_device(ssa_ctx *ctx, ssa_aggverifier *av, ssa_keycache *kc, const uint8_t *d_rs49,
+                                                  const uint8_t *d_pks, const uint8_t *d_pk_inf, const uint8_t *d_msgs,
+                                                  const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len, size_t n,
+                                                  uint64_t stats_out[8]) {
+    return agv_push_cached_dev(ctx, av, kc, d_rs49, d_pks, d_pk_inf, false, {d_msgs, d_msg_off, msg_stride, msg_len}, n,
+                               stats_out);
+}
+
+extern "C" int ssa_aggverifier_push_cached(ssa_ctx *ctx, ssa_aggverifier *av, ssa_keycache *kc, const uint8_t *rs49,
+                                           const uint8_t *pks, const uint8_t *pk_inf, const uint8_t *msgs,
+                                           const uint64_t *msg_off, size_t msg_stride, size_t msg_len, size_t n,
+                                           uint64_t stats_out[8]) {
+    return agv_push_cached_host(ctx, av, kc, rs49, pks, pk_inf, false, msgs, msg_off, msg_stride, msg_len, n, stats_out);
+}
+
+extern "C" int ssa_aggverifier_push_cached_wire_device(ssa_ctx *ctx, ssa_aggverifier *av, ssa_keycache *kc,
+                                                       const uint8_t *d_rs49, const uint8_t *d_pks49, const uint8_t *d_msgs,
+                                                       const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len, size_t n,
+                                                       uint64_t stats_out[8]) {
+    return agv_push_cached_dev(ctx, av, kc, d_rs49, d_pks49, nullptr, true, {d_msgs, d_msg_off, msg_stride, msg_len}, n,
+                               stats_out);
+}
+
+extern "C" int ssa_aggverifier_push_cached_wire(ssa_ctx *ctx, ssa_aggverifier *av, ssa_keycache *kc, const uint8_t *rs49,
+                                                const uint8_t *pks49, const uint8_t *msgs, const uint64_t *msg_off,
+                                                size_t msg_stride, size_t msg_len, size_t n, uint64_t stats_out[8]) {
+    return agv_push_cached_host(ctx, av, kc, rs49, pks49, nullptr, true, msgs, msg_off, msg_stride, msg_len, n, stats_out);
 }
 
 // ------------------------------------------------------------------ filtering half-aggregation through a key cache

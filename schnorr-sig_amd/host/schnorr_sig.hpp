@@ -946,10 +946,10 @@ class Aggregator {
 class AggregateVerifier {
   public:
     struct Info {
-        uint64_t held, capacity, block_lanes, pushes, pushed, reserved, blocks, finishes;
-    };
+        uint64_t held, capacity, block_lanes, pushes, pushed, reserved, blocks, finishes;     // reserved: lanes pushed
+    };                                                                                        // through a key cache
     static constexpr size_t All = SIZE_MAX;       // finish: every lane held
-    // block_lanes: 0 (512) or a power of two from 2 to 512.  All device memory, about 257 bytes per lane, is allocated here.
+    // block_lanes: 0 (512) or a power of two from 2 to 512.  All device memory, about 258 bytes per lane, is allocated here.
     AggregateVerifier(Context &cx, size_t capacity, size_t block_lanes = 0) : cx_(cx) {
         const int rc = ssa_aggverifier_create(cx.get(), capacity, block_lanes, 0u, &av_);
         if (rc != 0) throw std::runtime_error(std::string("ssa_aggverifier_create: ") + ssa_strerror(rc));
@@ -974,7 +974,42 @@ class AggregateVerifier {
         if (agg.size() != public_keys.size()) throw Panic("We should have the same number of signatures than public keys");
         push(agg.bytes.data(), public_keys, messages);
     }
-    // the status word: SSA_OK, SSA_INVALID_SIGNATURE or SSA_MALFORMED
+    // Through a key cache, subgroup check included: every distinct key is checked once, and a finish
+    // that takes a lane whose key lies outside the prime-order subgroup answers SSA_INVALID_PUBLIC_KEY -- the guarantee of
+    // Signature::verify.  An Affine cache here, a Wire cache for push_wire.  stats_out: 8 words (ssa_aggverifier_push_cached)
+    // or nullptr.  Lanes of the plain push are "not checked"; both kinds may be mixed in one object.
+    void push(KeyCache &cache, const uint8_t *rs49, const std::vector<PublicKey> &public_keys,
+              const std::vector<std::pair<const uint8_t *, size_t>> &messages, uint64_t *stats_out = nullptr) {
+        if (cache.wire()) throw std::invalid_argument("a Wire key cache takes 49-byte keys (push_wire), not PublicKey objects");
+        const size_t n = public_keys.size();
+        const PackedTriples t = pack_triples(std::vector<Signature>(n), public_keys, messages);
+        const int rc = ssa_aggverifier_push_cached(cx_.get(), av_, cache.get(), rs49, t.pks.data(), t.inf.data(),
+                                                   t.flat.data(), t.off.data(), 0, 0, n, stats_out);
+        if (rc != 0) throw std::runtime_error(std::string("ssa_aggverifier_push_cached: ") + ssa_strerror(rc));
+    }
+    void push(KeyCache &cache, const AggregateSignature &agg, const std::vector<PublicKey> &public_keys,
+              const std::vector<std::pair<const uint8_t *, size_t>> &messages, uint64_t *stats_out = nullptr) {
+        if (agg.size() != public_keys.size()) throw Panic("We should have the same number of signatures than public keys");
+        push(cache, agg.bytes.data(), public_keys, messages, stats_out);
+    }
+    // wire_keys: messages.size() keys side by side, 49 bytes each, as a block body carries them
+    void push_wire(KeyCache &cache, const uint8_t *rs49, const std::vector<uint8_t> &wire_keys,
+                   const std::vector<std::pair<const uint8_t *, size_t>> &messages, uint64_t *stats_out = nullptr) {
+        if (!cache.wire()) throw std::invalid_argument("an Affine key cache takes PublicKey objects (push), not 49-byte keys");
+        const size_t n = messages.size();
+        if (wire_keys.size() != n * PUBLIC_KEY_LENGTH) throw Panic("We should have the same number of messages than public keys");
+        std::vector<uint8_t> flat;
+        std::vector<uint64_t> off(n + 1, 0);
+        for (size_t i = 0; i < n; i++) {
+            flat.insert(flat.end(), messages[i].first, messages[i].first + messages[i].second);
+            off[i + 1] = flat.size();
+        }
+        flat.push_back(0);
+        const int rc = ssa_aggverifier_push_cached_wire(cx_.get(), av_, cache.get(), rs49, wire_keys.data(), flat.data(),
+                                                        off.data(), 0, 0, n, stats_out);
+        if (rc != 0) throw std::runtime_error(std::string("ssa_aggverifier_push_cached_wire: ") + ssa_strerror(rc));
+    }
+    // the status word: SSA_OK, SSA_INVALID_SIGNATURE or SSA_MALFORMED; SSA_INVALID_PUBLIC_KEY after pushes through a cache
     int finish_status(const uint8_t e_agg[32], size_t n_take = All) const {
         const int rc = ssa_aggverifier_finish(cx_.get(), av_, e_agg, n_take);
         if (rc < 0) throw std::runtime_error(std::string("ssa_aggverifier_finish: ") + ssa_strerror(rc));

@@ -81,6 +81,11 @@ signatures, legs alternating; the pushes' own times and ssa_aggregate_valid_many
 signatures pushed in --pushes equal pushes, then ssa_aggverifier_finish_device against
 ssa_verify_aggregate_sliced_device of --baseline-lib over the same lanes, legs alternating; the pushes' own times, the
 kernels of one push and of finish, and finish at 256 and 2048 lanes beside ssa_verify_aggregate_device are recorded.
+
+--verifier --cached measures the same object through the key cache: the lanes by --signers
+signers pushed with 49-byte wire keys through a wire cache, the keyed finish against the plain verifier's finish of
+--baseline-lib over the same lanes, and the sum of the pushes (cold, warm) beside ssa_decompress_many_device + the plain
+push of --baseline-lib (verifier_cached_main).
 """
 import argparse
 import hashlib
@@ -1329,6 +1334,260 @@ def verifier_main(a):
     return 0 if res["mismatches"] == 0 else 1
 
 
+CACHED_PUSH_KERNELS = ("dedup", "keycache_lookup", "keycache_insert", "keycache_map", "ssa_k_keyset_build",
+                       "ssa_k_keyed_decompress", "agc_expand", "ag_k_expand", "ssa_k_hash", "agv_k_append", "ag_k_level", "ag_k_tree")
+
+
+class BaselineStream:
+    """the streaming verifier and ssa_decompress_many_device of a build of the library given by its path (the parent
+    commit's: plain pushes only), on a context of its own"""
+
+    def __init__(self, path, capacity):
+        import ctypes as C
+        self.C, self.lib = C, C.CDLL(path)
+        vp, sz, i32 = C.c_void_p, C.c_size_t, C.c_int
+        self.lib.ssa_ctx_create_ex.argtypes = [C.POINTER(vp), i32, vp, sz, C.c_uint32, C.c_uint64]
+        self.lib.ssa_aggverifier_create.argtypes = [vp, sz, sz, C.c_uint32, C.POINTER(vp)]
+        self.lib.ssa_aggverifier_push_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz, sz, sz]
+        self.lib.ssa_aggverifier_finish_device.argtypes = [vp, vp, vp, sz, vp]
+        self.lib.ssa_aggverifier_reset.argtypes = [vp]
+        self.lib.ssa_aggverifier_destroy.argtypes = [vp]
+        self.lib.ssa_aggverifier_destroy.restype = None
+        self.lib.ssa_decompress_many_device.argtypes = [vp, vp, sz, vp, vp, vp]
+        self.lib.ssa_ctx_enable_timing.argtypes = [vp, i32]
+        self.lib.ssa_ctx_read_timing.argtypes = [vp, C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+        self.lib.ssa_ctx_sync.argtypes = [vp]
+        self.lib.ssa_ctx_destroy.argtypes = [vp]
+        self.lib.ssa_ctx_destroy.restype = None
+        self.ctx, self.av = vp(), vp()
+        if self.lib.ssa_ctx_create_ex(C.byref(self.ctx), 0, None, 0, 0, 0) != 0:
+            raise RuntimeError("baseline library: ssa_ctx_create_ex failed")
+        if self.lib.ssa_aggverifier_create(self.ctx, capacity, 0, 0, C.byref(self.av)) != 0:
+            raise RuntimeError("baseline library: ssa_aggverifier_create failed")
+
+    def reset(self):
+        self.lib.ssa_aggverifier_reset(self.av)
+
+    def decompress_push(self, d_rs, d_wk, d_msgs, n, d_upks, d_uinf, d_ust):
+        """the parent's route for a block body with wire keys: ssa_decompress_many_device, then the plain push"""
+        if self.lib.ssa_decompress_many_device(self.ctx, d_wk, n, d_upks, d_uinf, d_ust) != 0:
+            raise RuntimeError("baseline library: ssa_decompress_many_device failed")
+        if self.lib.ssa_aggverifier_push_device(self.ctx, self.av, d_rs, d_upks, d_uinf, d_msgs, None, 80, 80, n) != 0:
+            raise RuntimeError("baseline library: ssa_aggverifier_push_device failed")
+
+    def finish(self, d_e, d_verdict):
+        if self.lib.ssa_aggverifier_finish_device(self.ctx, self.av, d_e, self.C.c_size_t(-1).value, d_verdict) != 0:
+            raise RuntimeError("baseline library: ssa_aggverifier_finish_device failed")
+
+    def timed_finish(self, d_e, d_verdict, names):
+        """one finish under ssa_ctx_enable_timing -> {kernel: [ms per timed region, regions]}"""
+        C = self.C
+        self.sync()
+        self.lib.ssa_ctx_enable_timing(self.ctx, 1)
+        self.finish(d_e, d_verdict)
+        self.sync()
+        out = {}
+        for kn in names:
+            avg, cnt = C.c_double(0), C.c_uint64(0)
+            self.lib.ssa_ctx_read_timing(self.ctx, kn.encode(), C.byref(avg), C.byref(cnt))
+            if cnt.value:
+                out[kn] = [round(avg.value, 4), int(cnt.value)]
+        self.lib.ssa_ctx_enable_timing(self.ctx, 0)
+        return out
+
+    def sync(self):
+        self.lib.ssa_ctx_sync(self.ctx)
+
+    def close(self):
+        self.lib.ssa_aggverifier_destroy(self.av)
+        self.lib.ssa_ctx_destroy(self.ctx)
+
+
+def verifier_cached_main(a):
+    """--verifier --cached: the streaming verifier through the key cache.  --n honest lanes by
+    --signers signers (0: every lane its own) over 80-byte messages, device buffers, pushed in --pushes equal pushes with
+    49-byte wire keys.  Legs alternating in one process:
+      finish_keyed      ssa_aggverifier_finish_device of the keyed object (the fold of the key statuses included)
+      finish_plain      ssa_aggverifier_finish_device of a second object of THIS library on the same context, the same
+                        lanes pushed plainly: keyed against plain with everything else equal
+      finish_baseline   ssa_aggverifier_finish_device of --baseline-lib (a build of the parent commit; without it, this
+                        tree's own library) over the same lanes, pushed plainly behind ssa_decompress_many_device
+      push_wire_warm    reset, all the pushes through the warm wire cache: their sum
+      push_baseline     reset, per push ssa_decompress_many_device + the plain push of --baseline-lib: their sum
+    and once, in front, push_wire_cold (the same pushes into the empty cache).  Every timed verdict is checked.  The bar:
+    finish_keyed exceeds finish_baseline by no more than the larger of that leg's spread between two processes and the
+    timed duration of agv_k_key_verdict.  The pushes are recorded and have no bar."""
+    import torch
+    import schnorr_sig_amd as ssa
+    dev = torch.device("cuda", 0)
+    n, k = a.n, a.pushes
+    if n % k:
+        raise SystemExit("--verifier: --n must be a multiple of --pushes")
+    if a.signers < 0 or a.signers > n:
+        raise SystemExit("--signers must lie in [0, --n = %d]" % n)
+    per, signers = n // k, a.signers or n
+    # the lanes are made on a context of their own, which is closed before anything is timed: the timed object lives on a
+    # context that has done nothing else, as the baseline's does (a context that has signed and aggregated 2^20 lanes
+    # holds MSM workspaces of another history, and msm_k_buckets of its finish runs 0.1 ms slower: profiles/r25/)
+    gen = ssa.Engine(0)
+    base_path = a.baseline_lib or ssa.LIB_PATH
+    base = BaselineStream(base_path, n)
+    rng = np.random.default_rng(a.seed)
+    msgs = rng.integers(0, 256, (n, 80), dtype=np.uint8)
+    idx = rng.integers(0, signers, size=n)
+    idx[:signers] = np.arange(signers)
+    rng.shuffle(idx)
+    pks, sigs = gen.keygen_sign_many(_scalars(rng, signers)[idx], _scalars(rng, n), msgs)
+    wire_keys, st = gen.compress_many(pks)
+    assert (st == 0).all()
+    t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)   # noqa: E731
+    d_sigs, d_pks, d_msgs, d_wk = t(sigs), t(pks), t(msgs), t(wire_keys)
+    d_agg = torch.zeros(49 * n + 32, dtype=torch.uint8, device=dev)
+    d_upks = torch.zeros(96 * per, dtype=torch.uint8, device=dev)      # what the baseline's decompression writes, per push
+    d_uinf = torch.zeros(per, dtype=torch.uint8, device=dev)
+    d_ust = torch.zeros(per, dtype=torch.uint8, device=dev)
+    d_verdict = torch.full((1,), 255, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+    if gen.aggregate_sliced_device(d_sigs.data_ptr(), d_pks.data_ptr(), d_msgs.data_ptr(), n, 80, d_agg.data_ptr()) != 0:
+        raise SystemExit("--verifier --cached: the honest batch did not aggregate")
+    gen.sync()
+    gen.close()
+    eng = ssa.Engine(0)
+    d_rs, d_e = d_agg[:49 * n].view(n, 49), d_agg[49 * n:]
+    del d_sigs, d_pks
+    sha = lambda path: hashlib.sha256(open(path, "rb").read()).hexdigest()[:16]   # noqa: E731
+    res = {"metric": "aggregate_verifier_cached", "n": n, "pushes": k, "signers": signers, "msg_len": 80, "rounds": a.rounds,
+           "warmup": a.warmup, "library_sha256": sha(ssa.LIB_PATH), "baseline_sha256": sha(base_path),
+           "baseline_is_this_tree": not a.baseline_lib, "device": torch.cuda.get_device_name(0),
+           "date": time.strftime("%Y-%m-%d"), "mismatches": 0}
+    av, cache = eng.aggregate_verifier(n), eng.keycache_create(signers, wire=True)
+    stats = np.zeros(8, dtype=np.uint64)
+    # finish_plain: a second object of THIS library on the keyed object's context, the same lanes pushed plainly (keys
+    # decompressed once, outside the timed region): keyed against plain with everything else equal
+    av_plain = eng.aggregate_verifier(n)
+    d_upks_all = torch.zeros((n, 96), dtype=torch.uint8, device=dev)
+    d_uinf_all = torch.zeros(n, dtype=torch.uint8, device=dev)
+    d_ust_all = torch.zeros(n, dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize()
+    if ssa._lib.ssa_decompress_many_device(eng._ctx, d_wk.data_ptr(), n, d_upks_all.data_ptr(), d_uinf_all.data_ptr(),
+                                           d_ust_all.data_ptr()) != 0:
+        raise SystemExit("--verifier --cached: ssa_decompress_many_device failed")
+    for lo in range(0, n, per):
+        av_plain.push_device(d_rs[lo:lo + per], d_upks_all[lo:lo + per], d_msgs[lo:lo + per], d_pk_inf=d_uinf_all[lo:lo + per])
+    eng.sync()
+    if av_plain.info()["held"] != n or av_plain.info()["reserved"] != 0:
+        raise SystemExit("--verifier --cached: the plain object did not take the lanes")
+
+    def wall(fn, sync):
+        sync()
+        t0 = time.perf_counter()
+        fn()
+        sync()
+        return (time.perf_counter() - t0) * 1e3
+
+    def push_keyed():
+        av.reset()
+        stats[:] = 0
+        out = []
+        for lo in range(0, n, per):
+            sl = slice(lo, lo + per)
+            got = []
+            out.append(wall(lambda: got.append(av.push_wire_device(d_rs[sl], d_wk[sl], d_msgs[sl], cache=cache)[1]), eng.sync))
+            stats[:] += got[0]
+        if av.info()["held"] != n or av.info()["reserved"] != n:
+            res["mismatches"] += 1
+        return out
+
+    def push_base():
+        base.reset()
+        out = []
+        for lo in range(0, n, per):
+            out.append(wall(lambda: base.decompress_push(d_rs.data_ptr() + 49 * lo, d_wk.data_ptr() + 49 * lo,
+                                                         d_msgs.data_ptr() + 80 * lo, per, d_upks.data_ptr(), d_uinf.data_ptr(),
+                                                         d_ust.data_ptr()), base.sync))
+        return out
+
+    def checked(ms):
+        res["mismatches"] += 0 if int(d_verdict.item()) == 0 else 1
+        return ms
+
+    cold = push_keyed()
+    res["push_wire_cold_ms"] = round(float(np.sum(cold)), 3)
+    res["stats_cold"] = [int(x) for x in stats]
+    push_base()
+    times = {"finish_keyed": [], "finish_plain": [], "finish_baseline": [], "push_wire_warm": [], "push_baseline": []}
+    # --rotate-legs (a diagnostic): the two finish legs and the two push legs swap places every other round, and the times
+    # are also recorded by the order of the round (0: as listed, 1: swapped)
+    by_place = {leg: [[], []] for leg in times}
+    orders = [list(times), ["finish_baseline", "finish_plain", "finish_keyed", "push_baseline", "push_wire_warm"]]
+    for rnd in range(a.warmup + a.rounds):
+        order = orders[rnd % 2] if a.rotate_legs else orders[0]
+        for leg in order:
+            d_verdict.fill_(255)
+            torch.cuda.synchronize()
+            if leg.startswith("finish"):
+                # every timed finish follows one untimed finish of the same object: whichever finish is the first heavy
+                # work behind the push legs runs msm_k_buckets about 0.1 ms slower (profiles/r25/: runs 1 to 4), and
+                # without this the first leg of the round would carry that
+                fn, sync = {"finish_keyed": (lambda: av.finish_device(d_e, d_verdict), eng.sync),
+                            "finish_plain": (lambda: av_plain.finish_device(d_e, d_verdict), eng.sync),
+                            "finish_baseline": (lambda: base.finish(d_e.data_ptr(), d_verdict.data_ptr()), base.sync)}[leg]
+                fn()
+                sync()
+                d_verdict.fill_(255)
+                torch.cuda.synchronize()
+                ms = checked(wall(fn, sync))
+            elif leg == "push_wire_warm":
+                ms = float(np.sum(push_keyed()))
+                av.finish_device(d_e, d_verdict)
+                eng.sync()
+                checked(ms)
+            else:
+                ms = float(np.sum(push_base()))
+                base.finish(d_e.data_ptr(), d_verdict.data_ptr())
+                base.sync()
+                checked(ms)
+            if rnd >= a.warmup:
+                times[leg].append(ms)
+                by_place[leg][0 if order is orders[0] else 1].append(round(ms, 3))
+    if a.rotate_legs:
+        res["rotated_ms_by_place"] = by_place
+    res["stats_warm"] = [int(x) for x in stats]
+    med = res["ms_median"] = {leg: round(float(np.median(v)), 3) for leg, v in times.items()}
+    res["ms_all"] = {leg: [round(x, 3) for x in v] for leg, v in times.items()}
+    res["ratio"] = {"finish_keyed/finish_baseline": round(med["finish_keyed"] / med["finish_baseline"], 4),
+                    "push_wire_warm/push_baseline": round(med["push_wire_warm"] / med["push_baseline"], 4)}
+    res["finish_keyed_minus_baseline_ms"] = round(med["finish_keyed"] - med["finish_baseline"], 4)
+    res["finish_keyed_minus_plain_ms"] = round(med["finish_keyed"] - med["finish_plain"], 4)
+
+    def timed(fn, names):
+        eng.sync()
+        eng.enable_timing(True)
+        fn()
+        eng.sync()
+        out = {}
+        for kn in names:
+            avg, cnt = eng.read_timing(kn)
+            if cnt:
+                out[kn] = [round(avg, 4), int(cnt)]
+        eng.enable_timing(False)
+        return out
+
+    kern = {"finish": timed(lambda: av.finish_device(d_e, d_verdict), VERIFIER_KERNELS + ("agv_k_key_verdict",)),
+            "finish_plain": timed(lambda: av_plain.finish_device(d_e, d_verdict), VERIFIER_KERNELS + ("agv_k_key_verdict",)),
+            "finish_baseline": base.timed_finish(d_e.data_ptr(), d_verdict.data_ptr(), VERIFIER_KERNELS)}
+    av.reset()
+    kern["push_warm"] = timed(lambda: av.push_wire_device(d_rs[:per], d_wk[:per], d_msgs[:per], cache=cache), CACHED_PUSH_KERNELS)
+    res["kernel_ms_avg_launches"] = kern
+    print(json.dumps(res))
+    av.close()
+    av_plain.close()
+    cache.close()
+    eng.close()
+    base.close()
+    return 0 if res["mismatches"] == 0 else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1 << 20)
@@ -1343,12 +1602,14 @@ def main():
     ap.add_argument("--valid", action="store_true",
                     help="ssa_aggregate_valid_many_device against the checked call (and the unchecked one on filtered arrays)")
     ap.add_argument("--cached", action="store_true",
-                    help="ssa_verify_aggregates_many_cached(_wire)_device against decompress + ssa_verify_aggregates_many")
+                    help="ssa_verify_aggregates_many_cached(_wire)_device against decompress + ssa_verify_aggregates_many; "
+                         "with --verifier: the pushes through a wire key cache and the keyed finish against the plain "
+                         "verifier of --baseline-lib")
     ap.add_argument("--valid-cached", action="store_true",
                     help="ssa_aggregate_valid_(keyed_)many_cached_device against ssa_aggregate_valid_many_device and against "
                          "ssa_verify_many_cached_device + ssa_aggregate_many_device on filtered arrays")
     ap.add_argument("--signers", type=int, default=65536,
-                    help="--cached, --valid-cached: distinct signers (0: every lane its own)")
+                    help="--cached, --valid-cached, --verifier --cached: distinct signers (0: every lane its own)")
     ap.add_argument("--sharded", action="store_true",
                     help="ssa_aggregate_many_sliced_device / ssa_verify_aggregate_sliced_device against the single calls of "
                          "--baseline-lib")
@@ -1364,9 +1625,12 @@ def main():
                          "--baseline-lib over the same --n lanes")
     ap.add_argument("--pushes", type=int, default=16,
                     help="--accumulator, --verifier: equal pushes the --n signatures arrive in")
+    ap.add_argument("--rotate-legs", action="store_true",
+                    help="--verifier --cached: a diagnostic -- swap each leg with its counterpart every other round and "
+                         "record the times by place as well")
     a = ap.parse_args()
     if a.verifier:
-        return verifier_main(a)
+        return verifier_cached_main(a) if a.cached else verifier_main(a)
     if a.accumulator:
         return accumulator_main(a)
     if a.produce_many:
