@@ -352,6 +352,21 @@ def _ptr(a):
     return None if a is None else C.c_void_p(a.ctypes.data)
 
 
+def _addr(t):
+    """the device address of a torch tensor; None for no tensor or an empty one"""
+    return t.data_ptr() if t is not None and t.numel() else None
+
+
+def _dev_msg_shape(d_msgs, d_offsets, msg_len, msg_stride, no_msgs_ok=False):
+    """(msg_stride, msg_len) of a device form over torch tensors: without an offset table and a given msg_len the rows
+    of the 2-d d_msgs are the messages; msg_stride None: dense rows of msg_len bytes.  no_msgs_ok: the forms through a
+    key cache, which take d_msgs None for a call without lanes."""
+    if d_offsets is None and msg_len is None:
+        msg_len = d_msgs.shape[1] if not (no_msgs_ok and d_msgs is None) and d_msgs.dim() == 2 else 0
+    msg_len = msg_len or 0
+    return msg_stride if msg_stride is not None else msg_len, msg_len
+
+
 def pack_messages(messages):
     """list of bytes -> (concatenated uint8 array, uint64 offsets[n+1])."""
     off = np.zeros(len(messages) + 1, dtype=np.uint64)
@@ -993,14 +1008,11 @@ class Engine:
         k = counts.size
         if d_verdicts is None:
             d_verdicts = torch.empty(max(k, 1), dtype=torch.int32, device=d_aggs.device)[:k]
-        if d_offsets is None and msg_len is None:
-            msg_len = d_msgs.shape[1] if d_msgs.dim() == 2 else 0
-        msg_len = msg_len or 0
-        addr = lambda t: t.data_ptr() if t is not None and t.numel() else None    # noqa: E731
+        stride, mlen = _dev_msg_shape(d_msgs, d_offsets, msg_len, msg_stride)
         _check(_lib.ssa_verify_aggregates_many_device(
-            self._ctx, addr(d_aggs), counts.ctypes.data_as(C.POINTER(C.c_uint64)) if k else None, k, addr(d_pks),
-            addr(d_pk_inf), addr(d_msgs), addr(d_offsets), msg_stride if msg_stride is not None else msg_len, msg_len,
-            addr(d_verdicts)), "ssa_verify_aggregates_many_device")
+            self._ctx, _addr(d_aggs), counts.ctypes.data_as(C.POINTER(C.c_uint64)) if k else None, k, _addr(d_pks),
+            _addr(d_pk_inf), _addr(d_msgs), _addr(d_offsets), stride, mlen, _addr(d_verdicts)),
+            "ssa_verify_aggregates_many_device")
         return d_verdicts
 
     # ---- many aggregates produced in one call (include/schnorr_sig_amd.h) ----
@@ -1072,15 +1084,12 @@ class Engine:
             d_status = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)[:n]
         if d_nfail is None:
             d_nfail = torch.empty(1, dtype=torch.int64, device=dev)
-        if d_offsets is None and msg_len is None:
-            msg_len = d_msgs.shape[1] if d_msgs.dim() == 2 else 0
-        msg_len = msg_len or 0
-        addr = lambda t: t.data_ptr() if t is not None and t.numel() else None    # noqa: E731
+        stride, mlen = _dev_msg_shape(d_msgs, d_offsets, msg_len, msg_stride)
         _check(_lib.ssa_aggregates_many_device(
-            self._ctx, addr(d_sigs), counts.ctypes.data_as(C.POINTER(C.c_uint64)) if k else None, k, addr(d_pks),
-            addr(d_pk_inf), addr(d_msgs), addr(d_offsets), msg_stride if msg_stride is not None else msg_len, msg_len,
-            AGG_CHECK if check else 0, d_aggs.data_ptr() if k else None, addr(d_results), addr(d_status),
-            d_nfail.data_ptr()), "ssa_aggregates_many_device")
+            self._ctx, _addr(d_sigs), counts.ctypes.data_as(C.POINTER(C.c_uint64)) if k else None, k, _addr(d_pks),
+            _addr(d_pk_inf), _addr(d_msgs), _addr(d_offsets), stride, mlen, AGG_CHECK if check else 0,
+            d_aggs.data_ptr() if k else None, _addr(d_results), _addr(d_status), d_nfail.data_ptr()),
+            "ssa_aggregates_many_device")
         return d_aggs, d_results, d_status, d_nfail
 
     # ---- many aggregates through a key cache (include/schnorr_sig_amd.h) ----
@@ -1142,20 +1151,16 @@ class Engine:
             raise ValueError("pk_inf needs one byte per key")
         if d_verdicts is None:
             d_verdicts = torch.empty(max(k, 1), dtype=torch.int32, device=d_aggs.device)[:k]
-        if d_offsets is None and msg_len is None:
-            msg_len = d_msgs.shape[1] if d_msgs is not None and d_msgs.dim() == 2 else 0
-        msg_len = msg_len or 0
+        stride, mlen = _dev_msg_shape(d_msgs, d_offsets, msg_len, msg_stride, no_msgs_ok=True)
         stats = np.zeros(8, dtype=np.uint64) if want_stats else None
-        addr = lambda t: t.data_ptr() if t is not None and t.numel() else None    # noqa: E731
-        head = (self._ctx, cache.handle, addr(d_aggs), counts.ctypes.data_as(C.POINTER(C.c_uint64)) if k else None, k,
-                addr(d_keys))
-        tail = (addr(d_msgs), addr(d_offsets), msg_stride if msg_stride is not None else msg_len, msg_len,
-                addr(d_verdicts), stats.ctypes.data if want_stats else None)
+        head = (self._ctx, cache.handle, _addr(d_aggs), counts.ctypes.data_as(C.POINTER(C.c_uint64)) if k else None, k,
+                _addr(d_keys))
+        tail = (_addr(d_msgs), _addr(d_offsets), stride, mlen, _addr(d_verdicts), stats.ctypes.data if want_stats else None)
         if cache.wire:
             _check(_lib.ssa_verify_aggregates_many_cached_wire_device(*head, *tail),
                    "ssa_verify_aggregates_many_cached_wire_device")
         else:
-            _check(_lib.ssa_verify_aggregates_many_cached_device(*head, addr(d_pk_inf), *tail),
+            _check(_lib.ssa_verify_aggregates_many_cached_device(*head, _addr(d_pk_inf), *tail),
                    "ssa_verify_aggregates_many_cached_device")
         return d_verdicts, stats
 
@@ -1710,14 +1715,46 @@ class KeySet(_KeyTables):
             pass
 
 
-class KeyCache(_KeyTables):
+class _Handle:
+    """a device object (ssa_<_prefix>_* of the ABI) tied to its Engine like KeySet: destroyed exactly once, by close(),
+    the end of a `with` block, or when the object goes away"""
+    _prefix = None
+
+    def __init__(self, engine, handle):
+        self.engine = engine      # keeps the context alive
+        self.handle = handle
+
+    def _call(self, what, *args):
+        name = "ssa_%s_%s" % (self._prefix, what)
+        return _check(getattr(_lib, name)(*args), name)
+
+    def close(self):
+        if self.handle:
+            getattr(_lib, "ssa_%s_destroy" % self._prefix)(self.handle)
+            self.handle = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class KeyCache(_Handle, _KeyTables):
     """ssa_keycache handle (Engine.keycache_create): checked public keys, their statuses and tables, kept on the device
     across slices and calls of verify_many_cached.  Tied to its Engine like KeySet; destroyed exactly once (close(), the
     end of a `with` block, or when the object goes away)."""
+    _prefix = "keycache"
 
     def __init__(self, engine, handle, wire=False):
-        self.engine = engine      # keeps the context alive
-        self.handle = handle
+        super().__init__(engine, handle)
         self.wire = bool(wire)    # rows identified by the 49 compressed key bytes (DESIGN.md section 18)
 
     def info(self):
@@ -1758,24 +1795,6 @@ class KeyCache(_KeyTables):
         """forget every key: the next call is cold"""
         _check(_lib.ssa_keycache_clear(self.handle), "ssa_keycache_clear")
 
-    def close(self):
-        if self.handle:
-            _lib.ssa_keycache_destroy(self.handle)
-            self.handle = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 AGGR_NO_SCREEN = 1    # SSA_AGGR_NO_SCREEN
 AGGREGATOR_FIELDS = ("held", "capacity", "block_lanes", "pushes", "offered", "dropped", "blocks", "finishes")
@@ -1798,24 +1817,36 @@ def aggregator_plan(held, m, block_lanes=0):
     return tuple(int(v) for v in out)
 
 
-class Aggregator:
+def _n_take(n_take):
+    """the n_take argument of the ABI: None takes every lane held"""
+    return AGGREGATOR_ALL if n_take is None else int(n_take)
+
+
+class _LaneStore(_Handle):
+    """what the two streaming objects share: the eight info words under the names of _fields, len() = the lanes held,
+    reset()"""
+    _fields = None
+
+    def info(self):
+        """the eight words of ssa_<_prefix>_info by the names of _fields (AGGREGATOR_FIELDS, AGGVERIFIER_FIELDS)"""
+        out = (C.c_uint64 * 8)()
+        self._call("info", self.handle, out)
+        return dict(zip(self._fields, (int(v) for v in out)))
+
+    def __len__(self):
+        return self.info()["held"]
+
+    def reset(self):
+        """forget every lane and restart the counters; the memory stays"""
+        self._call("reset", self.handle)
+
+
+class Aggregator(_LaneStore):
     """ssa_aggregator handle (Engine.aggregator): the lanes admitted so far, on the device, in
     arrival order.  push() admits a batch on arrival; finish() gives the AggregateSignature of the first n_take held
     lanes -- what Engine.aggregate gives those lanes handed in alone -- and changes nothing.  Tied to its Engine like
     KeyCache; destroyed exactly once (close(), the end of a `with` block, or when the object goes away)."""
-
-    def __init__(self, engine, handle):
-        self.engine = engine      # keeps the context alive
-        self.handle = handle
-
-    def info(self):
-        """the AGGREGATOR_FIELDS by name"""
-        out = (C.c_uint64 * 8)()
-        _check(_lib.ssa_aggregator_info(self.handle, out), "ssa_aggregator_info")
-        return dict(zip(AGGREGATOR_FIELDS, (int(v) for v in out)))
-
-    def __len__(self):
-        return self.info()["held"]
+    _prefix, _fields = "aggregator", AGGREGATOR_FIELDS
 
     def push(self, sigs, pks, msgs, pk_inf=None, screen=True, offsets=None, engine=None):
         """a batch of signatures, keys and messages as Engine.aggregate_valid takes them -> (status uint8[n], n_kept):
@@ -1837,15 +1868,12 @@ class Aggregator:
         tensor (or flat bytes with a uint64-valued d_offsets and msg_len left None); the statuses land in d_status
         (uint8[n]) when it is given.  Synchronises the stream (inside the screen, and for the kept count) -> n_kept."""
         n = int(d_pks.shape[0])
-        if d_offsets is None and msg_len is None:
-            msg_len = d_msgs.shape[1] if d_msgs.dim() == 2 else 0
-        msg_len = msg_len or 0
-        addr = lambda t: t.data_ptr() if t is not None and t.numel() else None    # noqa: E731
+        stride, mlen = _dev_msg_shape(d_msgs, d_offsets, msg_len, msg_stride)
         n_kept = C.c_uint64(0)
         _check(_lib.ssa_aggregator_push_device(
-            self.engine._ctx, self.handle, addr(d_sigs), addr(d_pks), addr(d_pk_inf), addr(d_msgs), addr(d_offsets),
-            msg_stride if msg_stride is not None else msg_len, msg_len, n, 0 if screen else AGGR_NO_SCREEN,
-            addr(d_status), C.byref(n_kept)), "ssa_aggregator_push_device")
+            self.engine._ctx, self.handle, _addr(d_sigs), _addr(d_pks), _addr(d_pk_inf), _addr(d_msgs), _addr(d_offsets),
+            stride, mlen, n, 0 if screen else AGGR_NO_SCREEN, _addr(d_status), C.byref(n_kept)),
+            "ssa_aggregator_push_device")
         return int(n_kept.value)
 
     def finish_bytes(self, n_take=None):
@@ -1853,8 +1881,7 @@ class Aggregator:
         held = self.info()["held"]
         n = held if n_take is None else int(n_take)
         agg = np.full(49 * min(n, held) + 32, 255, dtype=np.uint8)
-        _check(_lib.ssa_aggregator_finish(self.engine._ctx, self.handle, AGGREGATOR_ALL if n_take is None else n,
-                                          _ptr(agg)), "ssa_aggregator_finish")
+        _check(_lib.ssa_aggregator_finish(self.engine._ctx, self.handle, _n_take(n_take), _ptr(agg)), "ssa_aggregator_finish")
         return agg
 
     def finish(self, n_take=None):
@@ -1873,52 +1900,18 @@ class Aggregator:
                "ssa_aggregator_finish_device")
         return n
 
-    def reset(self):
-        """forget every lane and restart the counters; the memory stays"""
-        _check(_lib.ssa_aggregator_reset(self.handle), "ssa_aggregator_reset")
 
-    def close(self):
-        if self.handle:
-            _lib.ssa_aggregator_destroy(self.handle)
-            self.handle = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class AggregateVerifier:
+class AggregateVerifier(_LaneStore):
     """ssa_aggverifier handle (Engine.aggregate_verifier): the lanes of a block body pushed so
     far, on the device, in arrival order.  push() does the position-independent work of Engine.verify_aggregate on
     arrival; finish(e_agg) gives the status Engine.verify_aggregate gives the first n_take held lanes handed in at once
     with that e_agg -- and changes nothing.  Tied to its Engine like KeyCache; destroyed exactly once (close(), the end
     of a `with` block, or when the object goes away)."""
-
-    def __init__(self, engine, handle):
-        self.engine = engine      # keeps the context alive
-        self.handle = handle
-
-    def info(self):
-        """the AGGVERIFIER_FIELDS by name"""
-        out = (C.c_uint64 * 8)()
-        _check(_lib.ssa_aggverifier_info(self.handle, out), "ssa_aggverifier_info")
-        return dict(zip(AGGVERIFIER_FIELDS, (int(v) for v in out)))
+    _prefix, _fields = "aggverifier", AGGVERIFIER_FIELDS
 
     def cached_lanes(self):
         """the lanes pushed through a key cache since create or reset (word [5] of ssa_aggverifier_info)"""
         return self.info()["reserved"]
-
-    def __len__(self):
-        return self.info()["held"]
 
     def push(self, rs49, pks, msgs, offsets=None, pk_inf=None, engine=None, cache=None):
         """n R's (n x 49 bytes, the aggregate's wire layout), keys and messages as Engine.verify_aggregate takes them:
@@ -1974,10 +1967,7 @@ class AggregateVerifier:
         have = 0 if d_keys is None else d_keys.numel() * d_keys.element_size()
         if have % width:
             raise ValueError("the keys are %d bytes each" % width)
-        if d_offsets is None and msg_len is None:
-            msg_len = d_msgs.shape[1] if d_msgs is not None and d_msgs.dim() == 2 else 0
-        msg_len = msg_len or 0
-        return have // width, msg_stride if msg_stride is not None else msg_len, msg_len
+        return (have // width,) + _dev_msg_shape(d_msgs, d_offsets, msg_len, msg_stride, no_msgs_ok=True)
 
     def push_device(self, d_rs49, d_pks, d_msgs, d_pk_inf=None, d_offsets=None, msg_len=None, msg_stride=None, cache=None,
                     want_stats=True):
@@ -1985,23 +1975,20 @@ class AggregateVerifier:
         uint8 tensor (or flat bytes with a uint64-valued d_offsets and msg_len left None).  Only enqueues.  Returns n.
         cache: an affine KeyCache, as push().  Then the call synchronises the stream once per slice of SSA_LANE_SLICE
         lanes (the key dedup's read-back), with want_stats once more at the end, and returns (n, stats or None)."""
-        addr = lambda t: t.data_ptr() if t is not None and t.numel() else None    # noqa: E731
         if cache is None:
             n = int(d_pks.shape[0])
-            if d_offsets is None and msg_len is None:
-                msg_len = d_msgs.shape[1] if d_msgs.dim() == 2 else 0
-            msg_len = msg_len or 0
+            stride, mlen = _dev_msg_shape(d_msgs, d_offsets, msg_len, msg_stride)
             _check(_lib.ssa_aggverifier_push_device(
-                self.engine._ctx, self.handle, addr(d_rs49), addr(d_pks), addr(d_pk_inf), addr(d_msgs), addr(d_offsets),
-                msg_stride if msg_stride is not None else msg_len, msg_len, n), "ssa_aggverifier_push_device")
+                self.engine._ctx, self.handle, _addr(d_rs49), _addr(d_pks), _addr(d_pk_inf), _addr(d_msgs), _addr(d_offsets),
+                stride, mlen, n), "ssa_aggverifier_push_device")
             return n
         if cache.wire:
             raise ValueError("push_device takes affine keys and an affine key cache: push_wire_device takes the 49-byte keys")
         n, stride, mlen = self._push_device_args(d_pks, d_msgs, d_offsets, msg_len, msg_stride, 96)
         stats = np.zeros(8, dtype=np.uint64) if want_stats else None
         _check(_lib.ssa_aggverifier_push_cached_device(
-            self.engine._ctx, self.handle, cache.handle, addr(d_rs49), addr(d_pks), addr(d_pk_inf), addr(d_msgs),
-            addr(d_offsets), stride, mlen, n, stats.ctypes.data if want_stats else None), "ssa_aggverifier_push_cached_device")
+            self.engine._ctx, self.handle, cache.handle, _addr(d_rs49), _addr(d_pks), _addr(d_pk_inf), _addr(d_msgs),
+            _addr(d_offsets), stride, mlen, n, stats.ctypes.data if want_stats else None), "ssa_aggverifier_push_cached_device")
         return n, stats
 
     def push_wire_device(self, d_rs49, d_pks49, d_msgs, d_offsets=None, msg_len=None, msg_stride=None, cache=None,
@@ -2010,11 +1997,10 @@ class AggregateVerifier:
         push_device(cache=...)."""
         if cache is None or not cache.wire:
             raise ValueError("push_wire_device needs a key cache made with wire=True")
-        addr = lambda t: t.data_ptr() if t is not None and t.numel() else None    # noqa: E731
         n, stride, mlen = self._push_device_args(d_pks49, d_msgs, d_offsets, msg_len, msg_stride, 49)
         stats = np.zeros(8, dtype=np.uint64) if want_stats else None
         _check(_lib.ssa_aggverifier_push_cached_wire_device(
-            self.engine._ctx, self.handle, cache.handle, addr(d_rs49), addr(d_pks49), addr(d_msgs), addr(d_offsets), stride,
+            self.engine._ctx, self.handle, cache.handle, _addr(d_rs49), _addr(d_pks49), _addr(d_msgs), _addr(d_offsets), stride,
             mlen, n, stats.ctypes.data if want_stats else None), "ssa_aggverifier_push_cached_wire_device")
         return n, stats
 
@@ -2025,15 +2011,13 @@ class AggregateVerifier:
         e = _np_u8(e_agg).reshape(-1)
         if e.size != 32:
             raise ValueError("e_agg is 32 bytes")
-        return _check(_lib.ssa_aggverifier_finish(self.engine._ctx, self.handle, _ptr(e),
-                                                  AGGREGATOR_ALL if n_take is None else int(n_take)),
+        return _check(_lib.ssa_aggverifier_finish(self.engine._ctx, self.handle, _ptr(e), _n_take(n_take)),
                       "ssa_aggverifier_finish")
 
     def finish_device(self, d_e_agg, d_verdict, n_take=None):
         """device form: only enqueues on the engine's stream; d_e_agg a uint8 tensor of 32 bytes, the status lands in the
         first element of the int32 / uint32 tensor (view) d_verdict"""
-        _check(_lib.ssa_aggverifier_finish_device(self.engine._ctx, self.handle, d_e_agg.data_ptr(),
-                                                  AGGREGATOR_ALL if n_take is None else int(n_take),
+        _check(_lib.ssa_aggverifier_finish_device(self.engine._ctx, self.handle, d_e_agg.data_ptr(), _n_take(n_take),
                                                   d_verdict.data_ptr()), "ssa_aggverifier_finish_device")
 
     def record(self, n_take=None):
@@ -2041,33 +2025,10 @@ class AggregateVerifier:
         import torch
         d_rec = torch.zeros(MSM_PARTIAL_WORDS, dtype=torch.int64, device="cuda:%d" % self.engine.device)
         torch.cuda.synchronize(d_rec.device)      # (the engine's stream is not torch's)
-        _check(_lib.ssa_debug_aggverifier_record(self.engine._ctx, self.handle,
-                                                 AGGREGATOR_ALL if n_take is None else int(n_take), d_rec.data_ptr()),
+        _check(_lib.ssa_debug_aggverifier_record(self.engine._ctx, self.handle, _n_take(n_take), d_rec.data_ptr()),
                "ssa_debug_aggverifier_record")
         self.engine.sync()
         return d_rec.cpu().numpy().view(np.uint64)
-
-    def reset(self):
-        """forget every lane and restart the counters; the memory stays"""
-        _check(_lib.ssa_aggverifier_reset(self.handle), "ssa_aggverifier_reset")
-
-    def close(self):
-        if self.handle:
-            _lib.ssa_aggverifier_destroy(self.handle)
-            self.handle = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class SignerSet:

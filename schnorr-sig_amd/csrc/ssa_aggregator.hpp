@@ -24,18 +24,33 @@
 #include "ssa_aggregate.hpp"
 #include "ssa_ctx.hpp"
 
-struct ssa_aggregator {
+// What the streaming aggregator and the streaming aggregate verifier (ssa_aggverifier.hpp) both are: lanes in arrival
+// order, their leaves, and the tops of the complete blocks of B.
+struct AgxStore {
     ssa_ctx *ctx = nullptr;   // nullptr: the context is gone, the device memory went with it
     size_t capacity = 0, block = 0, held = 0;     // block: B, a power of two from 2 to AG_TREE_SPAN
-    uint64_t pushes = 0, offered = 0, dropped = 0, finishes = 0;
-    DevBuf wire, scal, leaves, tops;
-    void release_all() {
-        wire.release();
-        scal.release();
-        leaves.release();
-        tops.release();
-    }
+    uint64_t pushes = 0, finishes = 0;
+    DevBuf leaves, tops;
+    // a buffer of the object and the bytes it takes at the object's capacity and B
+    struct Buf {
+        DevBuf *buf;
+        size_t bytes;
+    };
+    size_t n_tops() const { return block ? (capacity + block - 1) / block : 0; }
 };
+
+struct ssa_aggregator : AgxStore {
+    uint64_t offered = 0, dropped = 0;
+    DevBuf wire, scal;
+};
+// everything the object will ever hold, in the order it is allocated and released
+static inline std::vector<AgxStore::Buf> agx_bufs(ssa_aggregator &a) {
+    return {{&a.wire, 49 * a.capacity + 32}, {&a.scal, 32 * a.capacity}, {&a.leaves, 32 * a.capacity}, {&a.tops, 32 * a.n_tops()}};
+}
+template <class T>
+static inline void agx_release_all(T &obj) {
+    for (const AgxStore::Buf &b : agx_bufs(obj)) b.buf->release();
+}
 
 namespace ssa {
 

@@ -37,22 +37,16 @@
 #include "ssa_aggcache.hpp"
 #include "ssa_aggregator.hpp"
 
-struct ssa_aggverifier {
-    ssa_ctx *ctx = nullptr;   // nullptr: the context is gone, the device memory went with it
-    size_t capacity = 0, block = 0, held = 0;     // block: B, a power of two from 2 to AG_TREE_SPAN
-    uint64_t pushes = 0, pushed = 0, finishes = 0, cached = 0;     // cached: lanes pushed through a key cache
+struct ssa_aggverifier : AgxStore {
+    uint64_t pushed = 0, cached = 0;              // cached: lanes pushed through a key cache
     bool keyed = false;                           // kst[0, held) is valid and finish folds it (the rule above)
-    DevBuf rpts, ppts, h, leaves, bad, tops, kst;
-    void release_all() {
-        rpts.release();
-        ppts.release();
-        h.release();
-        leaves.release();
-        bad.release();
-        tops.release();
-        kst.release();
-    }
+    DevBuf rpts, ppts, h, bad, kst;
 };
+// everything the object will ever hold, in the order it is allocated and released
+static inline std::vector<AgxStore::Buf> agx_bufs(ssa_aggverifier &v) {
+    return {{&v.rpts, 96 * v.capacity}, {&v.ppts, 96 * v.capacity}, {&v.h, 32 * v.capacity},  {&v.leaves, 32 * v.capacity},
+            {&v.bad, v.capacity + 16},  {&v.tops, 32 * v.n_tops()}, {&v.kst, v.capacity + 16}};
+}
 
 namespace ssa {
 

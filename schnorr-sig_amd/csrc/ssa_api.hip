@@ -367,8 +367,8 @@ extern "C" void ssa_ctx_destroy(ssa_ctx *ctx) {
     orphan_handles(ctx->keysets, [](ssa_keyset *ks) { ks->release_all(); });
     orphan_handles(ctx->signer_sets, [](ssa_signer_set *ss) { ss->wipe_release(); });
     orphan_handles(ctx->keycaches, [](ssa_keycache *kc) { kc->release_all(); });
-    orphan_handles(ctx->aggregators, [](ssa_aggregator *ag) { ag->release_all(); });
-    orphan_handles(ctx->aggverifiers, [](ssa_aggverifier *av) { av->release_all(); });
+    orphan_handles(ctx->aggregators, [](ssa_aggregator *ag) { agx_release_all(*ag); });
+    orphan_handles(ctx->aggverifiers, [](ssa_aggverifier *av) { agx_release_all(*av); });
     for (auto &kv : ctx->timed)
         for (auto &t : kv.second) {
             (void)hipEventDestroy(t.start);
@@ -2018,36 +2018,10 @@ static int ag_refusal(ssa_ctx *ctx, size_t n, bool screened, const u8 *d_status,
     return 0;
 }
 
-// Synchronises the stream: the status it returns is read from the device.
-extern "C" int ssa_aggregate_many_device(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_pk_inf,
-                                         const uint8_t *d_msgs, const uint64_t *d_msg_off, size_t msg_stride,
-                                         size_t msg_len, size_t n, uint32_t flags, uint8_t *d_agg_out,
-                                         uint8_t *d_status_out, uint64_t *d_n_fail_out) {
-    const DevBatch b{d_sigs, d_pks, d_pk_inf, {d_msgs, d_msg_off, msg_stride, msg_len}};
-    if (!ctx || !d_agg_out || (flags & ~SSA_AGG_CHECK) || (n && (!d_sigs || !d_pks))) return SSA_ERR_ARG;
-    if (int rc = agg_check_args(ctx, b.msgs, n)) return rc;
-    unsigned long long *d_fail;
-    if (int rc = reset_fail_counter(ctx, d_n_fail_out, &d_fail)) return rc;
-    if (n == 0) {
-        HIP_TRY(hipMemsetAsync(d_agg_out, 0, 32, ctx->stream));
-        return SSA_OK;
-    }
-    if (!d_status_out && ctx->ag_status.reserve(n + 16)) return SSA_ERR_HIP;
-    u8 *d_status = d_status_out ? d_status_out : (u8 *)ctx->ag_status.p;
-    const bool screened = (flags & SSA_AGG_CHECK) != 0;
-    if (screened)
-        if (int rc = ssa_verify_batch_screened_device(ctx, d_sigs, d_pks, d_pk_inf, d_msgs, d_msg_off, msg_stride, msg_len, n,
-                                                      nullptr, 0, d_status, (uint64_t *)d_fail))
-            return rc;
-    if (int rc = ag_transcript(ctx, nullptr, d_sigs, d_pks, b.msgs, n, false, nullptr, 1, ag_uniform_passes(n))) return rc;
-    if (int rc = ag_fold(ctx, d_sigs, d_pks, d_pk_inf, n, screened ? (u8 *)nullptr : d_status, d_fail)) return rc;
-    int st;
-    if (int rc = ag_refusal(ctx, n, screened, d_status, d_fail, d_agg_out, &st)) return rc;
-    if (st) return st;     // refused: no aggregate
-    hipLaunchKernelGGL(ag_k_pack, dim3(grid_for((n * 49 + 3) / 4, 256)), dim3(256), 0, ctx->stream, d_sigs, n, d_agg_out);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(d_agg_out + 49 * n, ag_misc(ctx, AG_E), 32, hipMemcpyDeviceToDevice, ctx->stream));
-    return SSA_OK;
+// the caller's status buffer, or ctx->ag_status reserved for n lanes (nullptr: the reserve failed)
+static u8 *ag_status_buf(ssa_ctx *ctx, u8 *d_status_out, size_t n) {
+    if (d_status_out) return d_status_out;
+    return ctx->ag_status.reserve(n + 16) ? nullptr : (u8 *)ctx->ag_status.p;
 }
 
 // the host form of ssa_aggregate_many and of its sliced twin: staging and copies back are the same
@@ -2063,9 +2037,7 @@ static int aggregate_many_host(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t 
         return SSA_OK;
     }
     HostCall hc(ctx);
-    const u8 *d_sigs = hc.in(ctx->st_sigs, sigs, n * 81), *d_pks = hc.in(ctx->st_pks, pks, n * 96);
-    const u8 *d_inf = pk_inf ? hc.in(ctx->st_inf, pk_inf, n) : nullptr;
-    const MsgView mv = hc.msgs(msgs, msg_off, msg_stride, msg_len, n);
+    const DevBatch b = hc.lanes({sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len}, n * 81, n);
     u8 *d_agg = hc.out(ctx->st_aux, agg_out, SSA_AGGREGATE_LENGTH(n), 16);
     u8 *d_status = hc.out(ctx->st_status, status_out, n, 16);
     unsigned long long nf = 0;
@@ -2073,7 +2045,7 @@ static int aggregate_many_host(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t 
     int st = SSA_OK;       // a refusal is a result, not an error: the zeroed aggregate and the statuses still come back
     const int rc = hc.finish([&] {
         const int r = (sliced ? ssa_aggregate_many_sliced_device : ssa_aggregate_many_device)(
-            ctx, d_sigs, d_pks, d_inf, mv.msgs, mv.off, msg_stride, msg_len, n, flags, d_agg, d_status, nullptr);
+            ctx, b.sigs, b.pks, b.pk_inf, b.msgs.msgs, b.msgs.off, msg_stride, msg_len, n, flags, d_agg, d_status, nullptr);
         if (r > 0) st = r;
         return r > 0 ? 0 : r;
     });
@@ -2134,6 +2106,24 @@ static int av_aggregate_kept(ssa_ctx *ctx, const u8 *d_sigs, u32 stride, u32 off
     });
 }
 
+// The tail of every filtering aggregate, behind the n statuses: the kept lanes are listed (av_keep, one synchronisation
+// for |K|), *n_kept_out says how many, the caller's aggregate is zeroed behind what they will take, `between` (if any)
+// runs with |K|, and the kept lanes -- signatures at d_sigs + stride * lane + off -- are aggregated.
+static int av_finish_kept(ssa_ctx *ctx, const u8 *d_status, size_t n, const u8 *d_sigs, u32 stride, u32 off, u8 *d_agg_out,
+                          u32 *d_kept_out, uint64_t *n_kept_out, const std::function<int(size_t)> &between = nullptr) {
+    uint64_t m = 0;
+    if (int rc = av_keep(ctx, d_status, n, d_kept_out, &m)) return rc;
+    *n_kept_out = m;
+    // everything behind the aggregate of the kept lanes is zero; with none kept, that is the empty aggregate
+    const size_t used = m ? SSA_AGGREGATE_LENGTH(m) : 0;
+    if (used < SSA_AGGREGATE_LENGTH(n))
+        HIP_TRY(hipMemsetAsync(d_agg_out + used, 0, SSA_AGGREGATE_LENGTH(n) - used, ctx->stream));
+    if (between)
+        if (int rc = between(m)) return rc;
+    if (m == 0) return SSA_OK;
+    return av_aggregate_kept(ctx, d_sigs, stride, off, d_kept_out, m, d_agg_out);
+}
+
 // Two synchronisations: the screen's (for its segment verdicts; none at n <= msm_small_max) and one for |K|.
 extern "C" int ssa_aggregate_valid_many_device(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks,
                                                const uint8_t *d_pk_inf, const uint8_t *d_msgs, const uint64_t *d_msg_off,
@@ -2148,23 +2138,15 @@ extern "C" int ssa_aggregate_valid_many_device(ssa_ctx *ctx, const uint8_t *d_si
         HIP_TRY(hipMemsetAsync(d_agg_out, 0, 32, ctx->stream));
         return SSA_OK;
     }
-    if (!d_status_out && ctx->ag_status.reserve(n + 16)) return SSA_ERR_HIP;
-    u8 *d_status = d_status_out ? d_status_out : (u8 *)ctx->ag_status.p;
+    u8 *d_status = ag_status_buf(ctx, d_status_out, n);
+    if (!d_status) return SSA_ERR_HIP;
     // ONE challenge hash over all n lanes: the scalars mod q for the screen, the raw digests for the transcript
     if (int rc = ag_transcript_front(ctx, nullptr, &d_sigs, d_pks, b.msgs, n, true, nullptr, 1)) return rc;
     // The screen reads ws_h and writes neither it nor ag_dig: with ready hashes msm_run_one and
     // ssa_internal_verify_hashed launch no ssa_k_hash, the gather of failing segments copies the scalars into scr_in, and
     // no ag_* buffer belongs to it.
     if (int rc = ssa_internal_screen_hashed(ctx, b, n, (const uint64_t *)ctx->ws_h.p, d_status, nullptr)) return rc;
-    uint64_t m = 0;
-    if (int rc = av_keep(ctx, d_status, n, d_kept_out, &m)) return rc;
-    *n_kept_out = m;
-    // everything behind the aggregate of the kept lanes is zero; with none kept, that is the empty aggregate
-    const size_t used = m ? SSA_AGGREGATE_LENGTH(m) : 0;
-    if (used < SSA_AGGREGATE_LENGTH(n))
-        HIP_TRY(hipMemsetAsync(d_agg_out + used, 0, SSA_AGGREGATE_LENGTH(n) - used, ctx->stream));
-    if (m == 0) return SSA_OK;
-    return av_aggregate_kept(ctx, d_sigs, 81, 0, d_kept_out, m, d_agg_out);
+    return av_finish_kept(ctx, d_status, n, d_sigs, 81, 0, d_agg_out, d_kept_out, n_kept_out);
 }
 
 extern "C" int ssa_aggregate_valid_many(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_inf,
@@ -2180,15 +2162,13 @@ extern "C" int ssa_aggregate_valid_many(ssa_ctx *ctx, const uint8_t *sigs, const
         return SSA_OK;
     }
     HostCall hc(ctx);
-    const u8 *d_sigs = hc.in(ctx->st_sigs, sigs, n * 81), *d_pks = hc.in(ctx->st_pks, pks, n * 96);
-    const u8 *d_inf = pk_inf ? hc.in(ctx->st_inf, pk_inf, n) : nullptr;
-    const MsgView mv = hc.msgs(msgs, msg_off, msg_stride, msg_len, n);
+    const DevBatch b = hc.lanes({sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len}, n * 81, n);
     u8 *d_agg = hc.out(ctx->st_aux, agg_out, SSA_AGGREGATE_LENGTH(n), 16);
     u32 *d_kept = (u32 *)hc.out(ctx->st_aux2, kept_out, n * sizeof(u32));
     u8 *d_status = hc.out(ctx->st_status, status_out, n, 16);
     return hc.finish([&] {
-        return ssa_aggregate_valid_many_device(ctx, d_sigs, d_pks, d_inf, mv.msgs, mv.off, msg_stride, msg_len, n, d_agg,
-                                               d_kept, n_kept_out, d_status);
+        return ssa_aggregate_valid_many_device(ctx, b.sigs, b.pks, b.pk_inf, b.msgs.msgs, b.msgs.off, msg_stride, msg_len, n,
+                                               d_agg, d_kept, n_kept_out, d_status);
     });
 }
 
@@ -2233,14 +2213,12 @@ static int verify_aggregate_host(ssa_ctx *ctx, const uint8_t *agg, const uint8_t
     if (int rc = agg_check_args(ctx, {msgs, msg_off, msg_stride, msg_len}, n, sliced)) return rc;
     if (int rc = check_host_offsets(msg_off, n)) return rc;
     HostCall hc(ctx);
-    const u8 *d_agg = hc.in(ctx->st_sigs, agg, SSA_AGGREGATE_LENGTH(n)), *d_pks = hc.in(ctx->st_pks, pks, n * 96);
-    const u8 *d_inf = pk_inf ? hc.in(ctx->st_inf, pk_inf, n) : nullptr;
-    const MsgView mv = hc.msgs(msgs, msg_off, msg_stride, msg_len, n);
+    const DevBatch b = hc.lanes({agg, pks, pk_inf, msgs, msg_off, msg_stride, msg_len}, SSA_AGGREGATE_LENGTH(n), n);
     uint32_t v = SSA_MALFORMED, *d_verdict = (uint32_t *)((char *)ctx->ws_fail.p + 32);
     hc.copy_back(&v, d_verdict, sizeof v);
     const int rc = hc.finish([&] {
         return (sliced ? ssa_verify_aggregate_sliced_device : ssa_verify_aggregate_device)(
-            ctx, d_agg, d_pks, d_inf, mv.msgs, mv.off, msg_stride, msg_len, n, d_verdict);
+            ctx, b.sigs, b.pks, b.pk_inf, b.msgs.msgs, b.msgs.off, msg_stride, msg_len, n, d_verdict);
     });
     return rc ? rc : (int)v;
 }
@@ -2481,36 +2459,61 @@ static int ags_root_of(ssa_ctx *ctx, const u8 *d_lanes, u32 stride, const u8 *d_
     return ags_root(ctx, (const u64 *)ctx->ags_tops.p, n_tops, n, (u64 *)ctx->agm_roots.p);
 }
 
-// Synchronises the stream, as ssa_aggregate_many_device does.
-extern "C" int ssa_aggregate_many_sliced_device(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks,
-                                                const uint8_t *d_pk_inf, const uint8_t *d_msgs, const uint64_t *d_msg_off,
-                                                size_t msg_stride, size_t msg_len, size_t n, uint32_t flags,
-                                                uint8_t *d_agg_out, uint8_t *d_status_out, uint64_t *d_n_fail_out) {
-    const DevBatch b{d_sigs, d_pks, d_pk_inf, {d_msgs, d_msg_off, msg_stride, msg_len}};
-    if (!ctx || !d_agg_out || (flags & ~SSA_AGG_CHECK) || (n && (!d_sigs || !d_pks))) return SSA_ERR_ARG;
-    if (int rc = agg_check_args(ctx, b.msgs, n, true)) return rc;
+// The producer of one aggregate behind both device forms: they differ in how the lanes become e_agg and the R's.  One
+// MSM slice at most: ag_transcript, ag_fold, and ag_k_pack once the aggregate is not refused.  sliced (any n <=
+// SSA_MAX_BATCH): ags_root_of, and ags_fold packs the R's piece by piece.  Synchronises the stream: the status it returns
+// is read from the device.
+static int ag_produce(ssa_ctx *ctx, const DevBatch &b, size_t n, uint32_t flags, uint8_t *d_agg_out, uint8_t *d_status_out,
+                      uint64_t *d_n_fail_out, bool sliced) {
+    if (!ctx || !d_agg_out || (flags & ~SSA_AGG_CHECK) || (n && (!b.sigs || !b.pks))) return SSA_ERR_ARG;
+    if (int rc = agg_check_args(ctx, b.msgs, n, sliced)) return rc;
     unsigned long long *d_fail;
     if (int rc = reset_fail_counter(ctx, d_n_fail_out, &d_fail)) return rc;
     if (n == 0) {
         HIP_TRY(hipMemsetAsync(d_agg_out, 0, 32, ctx->stream));
         return SSA_OK;
     }
-    if ((!d_status_out && ctx->ag_status.reserve(n + 16)) || ctx->ag_misc.reserve(AG_MISC_BYTES)) return SSA_ERR_HIP;
-    u8 *d_status = d_status_out ? d_status_out : (u8 *)ctx->ag_status.p;
+    u8 *d_status = ag_status_buf(ctx, d_status_out, n);
+    if (!d_status || (sliced && ctx->ag_misc.reserve(AG_MISC_BYTES))) return SSA_ERR_HIP;
     const bool screened = (flags & SSA_AGG_CHECK) != 0;
     if (screened)
-        if (int rc = ssa_verify_batch_screened_device(ctx, d_sigs, d_pks, d_pk_inf, d_msgs, d_msg_off, msg_stride, msg_len, n,
-                                                      nullptr, 0, d_status, (uint64_t *)d_fail))
+        if (int rc = ssa_verify_batch_screened_device(ctx, b.sigs, b.pks, b.pk_inf, b.msgs.msgs, b.msgs.off, b.msgs.stride,
+                                                      b.msgs.len, n, nullptr, 0, d_status, (uint64_t *)d_fail))
             return rc;
-    if (int rc = ags_root_of(ctx, d_sigs, 81, d_pks, b.msgs, n, nullptr)) return rc;
-    if (int rc = ags_fold(ctx, b, n, 0, (const u64 *)ctx->agm_roots.p, ag_misc(ctx, AG_E), d_agg_out,
-                          screened ? (u8 *)nullptr : d_status, d_fail))
-        return rc;
+    u8 *d_fold_status = screened ? (u8 *)nullptr : d_status;
+    if (sliced) {
+        if (int rc = ags_root_of(ctx, b.sigs, 81, b.pks, b.msgs, n, nullptr)) return rc;
+        if (int rc = ags_fold(ctx, b, n, 0, (const u64 *)ctx->agm_roots.p, ag_misc(ctx, AG_E), d_agg_out, d_fold_status, d_fail))
+            return rc;
+    } else {
+        if (int rc = ag_transcript(ctx, nullptr, b.sigs, b.pks, b.msgs, n, false, nullptr, 1, ag_uniform_passes(n))) return rc;
+        if (int rc = ag_fold(ctx, b.sigs, b.pks, b.pk_inf, n, d_fold_status, d_fail)) return rc;
+    }
     int st;
     if (int rc = ag_refusal(ctx, n, screened, d_status, d_fail, d_agg_out, &st)) return rc;
-    if (st) return st;
+    if (st) return st;     // refused: no aggregate
+    if (!sliced) {
+        hipLaunchKernelGGL(ag_k_pack, dim3(grid_for((n * 49 + 3) / 4, 256)), dim3(256), 0, ctx->stream, b.sigs, n, d_agg_out);
+        HIP_TRY(hipGetLastError());
+    }
     HIP_TRY(hipMemcpyAsync(d_agg_out + 49 * n, ag_misc(ctx, AG_E), 32, hipMemcpyDeviceToDevice, ctx->stream));
     return SSA_OK;
+}
+
+extern "C" int ssa_aggregate_many_device(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_pk_inf,
+                                         const uint8_t *d_msgs, const uint64_t *d_msg_off, size_t msg_stride,
+                                         size_t msg_len, size_t n, uint32_t flags, uint8_t *d_agg_out,
+                                         uint8_t *d_status_out, uint64_t *d_n_fail_out) {
+    return ag_produce(ctx, {d_sigs, d_pks, d_pk_inf, {d_msgs, d_msg_off, msg_stride, msg_len}}, n, flags, d_agg_out,
+                      d_status_out, d_n_fail_out, false);
+}
+
+extern "C" int ssa_aggregate_many_sliced_device(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks,
+                                                const uint8_t *d_pk_inf, const uint8_t *d_msgs, const uint64_t *d_msg_off,
+                                                size_t msg_stride, size_t msg_len, size_t n, uint32_t flags,
+                                                uint8_t *d_agg_out, uint8_t *d_status_out, uint64_t *d_n_fail_out) {
+    return ag_produce(ctx, {d_sigs, d_pks, d_pk_inf, {d_msgs, d_msg_off, msg_stride, msg_len}}, n, flags, d_agg_out,
+                      d_status_out, d_n_fail_out, true);
 }
 
 extern "C" int ssa_aggregate_many_sliced(ssa_ctx *ctx, const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_inf,
@@ -2550,10 +2553,58 @@ extern "C" int ssa_verify_aggregate_sliced(ssa_ctx *ctx, const uint8_t *agg, con
 }
 
 // ------------------------------------------------------------------ streaming aggregator (ssa_aggregator.hpp)
-extern "C" int ssa_debug_aggregator_plan(uint64_t held, uint64_t m, uint64_t block_lanes, uint64_t out[4]) {
+// The rules of both streaming objects (AgxStore: ssa_aggregator, ssa_aggverifier), each written once.
+// B of a block_lanes argument: 0 means AG_TREE_SPAN, otherwise a power of two from 2 to AG_TREE_SPAN; 0: refused
+static size_t agx_block(uint64_t block_lanes) {
     const uint64_t B = block_lanes ? block_lanes : AG_TREE_SPAN;
-    if (!out || !is_pow2((size_t)B) || B < 2 || B > AG_TREE_SPAN || held > SSA_MAX_BATCH || m > SSA_MAX_BATCH - held)
-        return SSA_ERR_ARG;
+    return is_pow2((size_t)B) && B >= 2 && B <= AG_TREE_SPAN ? (size_t)B : 0;
+}
+
+// the lanes an n_take argument takes of the object: SIZE_MAX means all held, more than are held is refused
+static int agx_take(const ssa_ctx *ctx, const AgxStore *s, size_t n_take, size_t *n_out) {
+    if (!ctx || !s || s->ctx != ctx) return SSA_ERR_ARG;
+    *n_out = n_take == SIZE_MAX ? s->held : n_take;
+    return *n_out > s->held ? SSA_ERR_ARG : 0;
+}
+
+// (the caller puts *out on the context's list of live objects of the type)
+template <class T>
+static int agx_create(ssa_ctx *ctx, size_t capacity, size_t block_lanes, uint32_t flags, T **out) {
+    if (out) *out = nullptr;
+    const size_t B = agx_block(block_lanes);
+    if (!ctx || !out || flags != 0 || capacity == 0 || capacity > SSA_MAX_BATCH || !B) return SSA_ERR_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    T *obj = new T();
+    obj->ctx = ctx;
+    obj->capacity = capacity;
+    obj->block = B;
+    // everything the object will ever hold, now: no push or finish allocates for it
+    for (const AgxStore::Buf &b : agx_bufs(*obj))
+        if (b.buf->reserve_exact(b.bytes)) {
+            (void)hipGetLastError();
+            agx_release_all(*obj);
+            delete obj;
+            return SSA_ERR_HIP;
+        }
+    *out = obj;
+    return 0;
+}
+
+template <class T>
+static void agx_destroy(T *obj, std::vector<T *> ssa_ctx::*live) {
+    if (!obj) return;
+    if (obj->ctx) {
+        (void)hipSetDevice(obj->ctx->device);
+        (void)hipStreamSynchronize(obj->ctx->stream);
+        forget_handle(obj->ctx->*live, obj);
+        agx_release_all(*obj);
+    }
+    delete obj;
+}
+
+extern "C" int ssa_debug_aggregator_plan(uint64_t held, uint64_t m, uint64_t block_lanes, uint64_t out[4]) {
+    const size_t B = agx_block(block_lanes);
+    if (!out || !B || held > SSA_MAX_BATCH || m > SSA_MAX_BATCH - held) return SSA_ERR_ARG;
     const AgxPlan p = agx_plan(held, m, B);
     out[0] = p.first;
     out[1] = p.count;
@@ -2563,38 +2614,12 @@ extern "C" int ssa_debug_aggregator_plan(uint64_t held, uint64_t m, uint64_t blo
 }
 
 extern "C" int ssa_aggregator_create(ssa_ctx *ctx, size_t capacity, size_t block_lanes, uint32_t flags, ssa_aggregator **out) {
-    if (out) *out = nullptr;
-    const size_t B = block_lanes ? block_lanes : AG_TREE_SPAN;
-    if (!ctx || !out || flags != 0 || capacity == 0 || capacity > SSA_MAX_BATCH || !is_pow2(B) || B < 2 || B > AG_TREE_SPAN)
-        return SSA_ERR_ARG;
-    HIP_TRY(hipSetDevice(ctx->device));
-    ssa_aggregator *ag = new ssa_aggregator();
-    ag->ctx = ctx;
-    ag->capacity = capacity;
-    ag->block = B;
-    // everything the object will ever hold, now: no push or finish allocates for it
-    if (ag->wire.reserve_exact(49 * capacity + 32) || ag->scal.reserve_exact(32 * capacity) ||
-        ag->leaves.reserve_exact(32 * capacity) || ag->tops.reserve_exact(32 * ((capacity + B - 1) / B))) {
-        (void)hipGetLastError();
-        ag->release_all();
-        delete ag;
-        return SSA_ERR_HIP;
-    }
-    ctx->aggregators.push_back(ag);
-    *out = ag;
-    return 0;
+    const int rc = agx_create(ctx, capacity, block_lanes, flags, out);
+    if (rc == 0) ctx->aggregators.push_back(*out);
+    return rc;
 }
 
-extern "C" void ssa_aggregator_destroy(ssa_aggregator *ag) {
-    if (!ag) return;
-    if (ag->ctx) {
-        (void)hipSetDevice(ag->ctx->device);
-        (void)hipStreamSynchronize(ag->ctx->stream);
-        forget_handle(ag->ctx->aggregators, ag);
-        ag->release_all();
-    }
-    delete ag;
-}
+extern "C" void ssa_aggregator_destroy(ssa_aggregator *ag) { agx_destroy(ag, &ssa_ctx::aggregators); }
 
 // Nothing on the device needs clearing: every array is written before it is read, up to `held`.
 extern "C" int ssa_aggregator_reset(ssa_aggregator *ag) {
@@ -2631,10 +2656,11 @@ static int agx_push_args(const ssa_ctx *ctx, const ssa_aggregator *ag, const Msg
 // workgroup per block (the uniform cut, no top).  Smaller B: log2 B launches of ag_k_level over the count * B leaves --
 // every level is even, no node moves up unchanged -- between ctx->ag_nodes and ctx->ag_nodes2; the first reads the
 // object's leaves, the last writes the object's tops.
-static int agx_reduce_blocks(ssa_ctx *ctx, const DevBuf &leaves, DevBuf &tops, size_t B, const AgxPlan &p) {
-    const size_t cnt = (size_t)p.count * B;
-    const u64 *src = (const u64 *)leaves.p + 4 * (size_t)p.first * B;
-    u64 *dst = (u64 *)tops.p + 4 * (size_t)p.first;
+static int agx_reduce_blocks(const AgxStore &s, const AgxPlan &p) {
+    ssa_ctx *ctx = s.ctx;
+    const size_t B = s.block, cnt = (size_t)p.count * B;
+    const u64 *src = (const u64 *)s.leaves.p + 4 * (size_t)p.first * B;
+    u64 *dst = (u64 *)s.tops.p + 4 * (size_t)p.first;
     if (B == AG_TREE_SPAN)
         return timed_launch(ctx, "ag_k_tree", [&] {
             hipLaunchKernelGGL(ag_k_tree, dim3((unsigned)p.count), dim3(256), 0, ctx->stream, ctx->d_params, src,
@@ -2659,8 +2685,10 @@ static int agx_reduce_blocks(ssa_ctx *ctx, const DevBuf &leaves, DevBuf &tops, s
 // the n / B complete blocks are copied into ctx->ags_tops, the ragged block [B (n / B), n) is reduced behind them by one
 // workgroup of ag_k_tree -- into the workspace, never into the object: with n below the lanes held that slot is a complete
 // block's top -- and ags_root finishes the tree.
-static int agx_root(ssa_ctx *ctx, const DevBuf &leaves, const DevBuf &tops, size_t B, size_t n) {
-    const AgxPlan p = agx_plan(0, n, B);       // p.count stored tops, then the ragged block's
+static int agx_root(const AgxStore &s, size_t n) {
+    ssa_ctx *ctx = s.ctx;
+    const DevBuf &leaves = s.leaves, &tops = s.tops;
+    const AgxPlan p = agx_plan(0, n, s.block);       // p.count stored tops, then the ragged block's
     const size_t n_tops = (size_t)p.count + (p.tail_len ? 1 : 0);
     if (ctx->ags_tops.reserve(n_tops * 32) || ctx->agm_roots.reserve(32)) return SSA_ERR_HIP;
     u64 *d_tops = (u64 *)ctx->ags_tops.p;
@@ -2692,8 +2720,8 @@ extern "C" int ssa_aggregator_push_device(ssa_ctx *ctx, ssa_aggregator *ag, cons
         ag->pushes++;
         return SSA_OK;
     }
-    if ((!d_status_out && ctx->ag_status.reserve(n + 16)) || ctx->agx_kept.reserve(n * sizeof(u32))) return SSA_ERR_HIP;
-    u8 *d_status = d_status_out ? d_status_out : (u8 *)ctx->ag_status.p;
+    u8 *d_status = ag_status_buf(ctx, d_status_out, n);
+    if (!d_status || ctx->agx_kept.reserve(n * sizeof(u32))) return SSA_ERR_HIP;
     // ONE challenge hash over the n lanes: the raw digests for the leaves and, screened, the scalars mod q for the screen
     const bool screen = !(flags & SSA_AGGR_NO_SCREEN);
     if (int rc = ag_transcript_front(ctx, nullptr, &d_sigs, d_pks, b.msgs, n, screen, nullptr, 1)) return rc;
@@ -2717,7 +2745,7 @@ extern "C" int ssa_aggregator_push_device(ssa_ctx *ctx, ssa_aggregator *ag, cons
         if (rc) return rc;
         const AgxPlan p = agx_plan(ag->held, m, ag->block);
         if (p.count)
-            if ((rc = agx_reduce_blocks(ctx, ag->leaves, ag->tops, ag->block, p))) return rc;
+            if ((rc = agx_reduce_blocks(*ag, p))) return rc;
     }
     // (only now: a launch that could not be enqueued leaves the object as it was -- what it wrote lies behind `held`)
     ag->held += m;
@@ -2736,22 +2764,20 @@ extern "C" int ssa_aggregator_push(ssa_ctx *ctx, ssa_aggregator *ag, const uint8
     if (n == 0) return ssa_aggregator_push_device(ctx, ag, nullptr, nullptr, nullptr, nullptr, nullptr, msg_stride, msg_len, 0,
                                                   flags, nullptr, n_kept_out);
     HostCall hc(ctx);
-    const u8 *d_sigs = hc.in(ctx->st_sigs, sigs, n * 81), *d_pks = hc.in(ctx->st_pks, pks, n * 96);
-    const u8 *d_inf = pk_inf ? hc.in(ctx->st_inf, pk_inf, n) : nullptr;
-    const MsgView mv = hc.msgs(msgs, msg_off, msg_stride, msg_len, n);
+    const DevBatch b = hc.lanes({sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len}, n * 81, n);
     u8 *d_status = hc.out(ctx->st_status, status_out, n, 16);
     return hc.finish([&] {
-        return ssa_aggregator_push_device(ctx, ag, d_sigs, d_pks, d_inf, mv.msgs, mv.off, msg_stride, msg_len, n, flags,
-                                          d_status, n_kept_out);
+        return ssa_aggregator_push_device(ctx, ag, b.sigs, b.pks, b.pk_inf, b.msgs.msgs, b.msgs.off, msg_stride, msg_len, n,
+                                          flags, d_status, n_kept_out);
     });
 }
 
 // Only enqueues on the context's stream: every size it needs is on the host.  Reads the object, writes workspaces of the
 // context and the caller's buffer.
 extern "C" int ssa_aggregator_finish_device(ssa_ctx *ctx, ssa_aggregator *ag, size_t n_take, uint8_t *d_agg_out) {
-    if (!ctx || !ag || ag->ctx != ctx || !d_agg_out) return SSA_ERR_ARG;
-    const size_t n = n_take == SIZE_MAX ? ag->held : n_take;
-    if (n > ag->held) return SSA_ERR_ARG;
+    size_t n;
+    if (int rc = agx_take(ctx, ag, n_take, &n)) return rc;
+    if (!d_agg_out) return SSA_ERR_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
     ag->finishes++;
     if (n == 0) {
@@ -2762,7 +2788,7 @@ extern "C" int ssa_aggregator_finish_device(ssa_ctx *ctx, ssa_aggregator *ag, si
     if (ctx->ag_misc.reserve(AG_MISC_BYTES) || ctx->ags_parts.reserve(k * 32) ||
         ctx->ag_partials.reserve((size_t)grid_for(std::min(piece, n), 256) * 32))
         return SSA_ERR_HIP;
-    if (int rc = agx_root(ctx, ag->leaves, ag->tops, ag->block, n)) return rc;
+    if (int rc = agx_root(*ag, n)) return rc;
     const u64 *d_root = (const u64 *)ctx->agm_roots.p;      // (only now: agx_root reserves it)
     for (size_t lo = 0, j = 0; lo < n; lo += piece, j++) {
         const size_t cnt = std::min(piece, n - lo);
@@ -2791,9 +2817,9 @@ extern "C" int ssa_aggregator_finish_device(ssa_ctx *ctx, ssa_aggregator *ag, si
 }
 
 extern "C" int ssa_aggregator_finish(ssa_ctx *ctx, ssa_aggregator *ag, size_t n_take, uint8_t *agg_out) {
-    if (!ctx || !ag || ag->ctx != ctx || !agg_out) return SSA_ERR_ARG;
-    const size_t n = n_take == SIZE_MAX ? ag->held : n_take;
-    if (n > ag->held) return SSA_ERR_ARG;
+    size_t n;
+    if (int rc = agx_take(ctx, ag, n_take, &n)) return rc;
+    if (!agg_out) return SSA_ERR_ARG;
     HostCall hc(ctx);
     u8 *d_agg = hc.out(ctx->st_aux, agg_out, SSA_AGGREGATE_LENGTH(n), 16);
     return hc.finish([&] { return ssa_aggregator_finish_device(ctx, ag, n, d_agg); });
@@ -2801,39 +2827,12 @@ extern "C" int ssa_aggregator_finish(ssa_ctx *ctx, ssa_aggregator *ag, size_t n_
 
 // ------------------------------------------------------------------ streaming aggregate verifier (ssa_aggverifier.hpp)
 extern "C" int ssa_aggverifier_create(ssa_ctx *ctx, size_t capacity, size_t block_lanes, uint32_t flags, ssa_aggverifier **out) {
-    if (out) *out = nullptr;
-    const size_t B = block_lanes ? block_lanes : AG_TREE_SPAN;
-    if (!ctx || !out || flags != 0 || capacity == 0 || capacity > SSA_MAX_BATCH || !is_pow2(B) || B < 2 || B > AG_TREE_SPAN)
-        return SSA_ERR_ARG;
-    HIP_TRY(hipSetDevice(ctx->device));
-    ssa_aggverifier *av = new ssa_aggverifier();
-    av->ctx = ctx;
-    av->capacity = capacity;
-    av->block = B;
-    // everything the object will ever hold, now: no push or finish allocates for it
-    if (av->rpts.reserve_exact(96 * capacity) || av->ppts.reserve_exact(96 * capacity) || av->h.reserve_exact(32 * capacity) ||
-        av->leaves.reserve_exact(32 * capacity) || av->bad.reserve_exact(capacity + 16) ||
-        av->tops.reserve_exact(32 * ((capacity + B - 1) / B)) || av->kst.reserve_exact(capacity + 16)) {
-        (void)hipGetLastError();
-        av->release_all();
-        delete av;
-        return SSA_ERR_HIP;
-    }
-    ctx->aggverifiers.push_back(av);
-    *out = av;
-    return 0;
+    const int rc = agx_create(ctx, capacity, block_lanes, flags, out);
+    if (rc == 0) ctx->aggverifiers.push_back(*out);
+    return rc;
 }
 
-extern "C" void ssa_aggverifier_destroy(ssa_aggverifier *av) {
-    if (!av) return;
-    if (av->ctx) {
-        (void)hipSetDevice(av->ctx->device);
-        (void)hipStreamSynchronize(av->ctx->stream);
-        forget_handle(av->ctx->aggverifiers, av);
-        av->release_all();
-    }
-    delete av;
-}
+extern "C" void ssa_aggverifier_destroy(ssa_aggverifier *av) { agx_destroy(av, &ssa_ctx::aggverifiers); }
 
 // Nothing on the device needs clearing: every array is written before it is read, up to `held` (kst: the rule of
 // ssa_aggverifier.hpp -- with `keyed` off its bytes are not read until the next cached push has zeroed or written them).
@@ -2866,11 +2865,16 @@ static int agv_push_args(const ssa_ctx *ctx, const ssa_aggverifier *av, const Ms
     return n > av->capacity - av->held ? SSA_ERR_ARG : 0;
 }
 
-// The body of every push behind its argument checks, n >= 1 lanes over the keys U = d_pks / d_pk_inf as agv_k_append
+// The body of every push behind its argument checks, n lanes over the keys U = d_pks / d_pk_inf as agv_k_append
 // reads them (the caller's, or what a wire cache expanded).  through_cache: the lanes' kst bytes are already written
-// (agc_k_expand, enqueued in front); otherwise a keyed object gets them zeroed here.  Only enqueues.
+// (agc_k_expand, enqueued in front); otherwise a keyed object gets them zeroed here.  Only enqueues; no lanes: the push
+// is counted and nothing is enqueued.
 static int agv_push_body(ssa_ctx *ctx, ssa_aggverifier *av, const u8 *d_rs49, const u8 *d_pks, const u8 *d_pk_inf,
                          const MsgView &mv, size_t n, bool through_cache) {
+    if (n == 0) {
+        av->pushes++;
+        return SSA_OK;
+    }
     // ONE challenge hash over the n lanes: the raw digests for the leaves (ctx->ag_dig) and the scalars mod q (ctx->ws_h)
     const u8 *d_sigs = nullptr;
     if (int rc = ag_transcript_front(ctx, d_rs49, &d_sigs, d_pks, mv, n, true, nullptr, 1)) return rc;
@@ -2882,7 +2886,7 @@ static int agv_push_body(ssa_ctx *ctx, ssa_aggverifier *av, const u8 *d_rs49, co
     if (rc) return rc;
     const AgxPlan p = agx_plan(av->held, n, av->block);
     if (p.count)
-        if ((rc = agx_reduce_blocks(ctx, av->leaves, av->tops, av->block, p))) return rc;
+        if ((rc = agx_reduce_blocks(*av, p))) return rc;
     // a plain push into a keyed object: its lanes' keys are "not checked"
     if (av->keyed && !through_cache) HIP_TRY(hipMemsetAsync((u8 *)av->kst.p + av->held, 0, n, ctx->stream));
     // (only now: a launch that could not be enqueued leaves the object as it was -- what it wrote lies behind `held`)
@@ -2900,10 +2904,6 @@ extern "C" int ssa_aggverifier_push_device(ssa_ctx *ctx, ssa_aggverifier *av, co
     const MsgView mv{d_msgs, d_msg_off, msg_stride, msg_len};
     if (int rc = agv_push_args(ctx, av, mv, n, d_rs49, d_pks)) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
-    if (n == 0) {
-        av->pushes++;
-        return SSA_OK;
-    }
     return agv_push_body(ctx, av, d_rs49, d_pks, d_pk_inf, mv, n, false);
 }
 
@@ -2914,11 +2914,9 @@ extern "C" int ssa_aggverifier_push(ssa_ctx *ctx, ssa_aggverifier *av, const uin
     if (int rc = check_host_offsets(msg_off, n)) return rc;
     if (n == 0) return ssa_aggverifier_push_device(ctx, av, nullptr, nullptr, nullptr, nullptr, nullptr, msg_stride, msg_len, 0);
     HostCall hc(ctx);
-    const u8 *d_rs = hc.in(ctx->st_sigs, rs49, n * 49), *d_pks = hc.in(ctx->st_pks, pks, n * 96);
-    const u8 *d_inf = pk_inf ? hc.in(ctx->st_inf, pk_inf, n) : nullptr;
-    const MsgView mv = hc.msgs(msgs, msg_off, msg_stride, msg_len, n);
+    const DevBatch b = hc.lanes({rs49, pks, pk_inf, msgs, msg_off, msg_stride, msg_len}, n * 49, n);
     const int rc = hc.finish([&] {
-        return ssa_aggverifier_push_device(ctx, av, d_rs, d_pks, d_inf, mv.msgs, mv.off, msg_stride, msg_len, n);
+        return ssa_aggverifier_push_device(ctx, av, b.sigs, b.pks, b.pk_inf, b.msgs.msgs, b.msgs.off, msg_stride, msg_len, n);
     });
     if (rc) return rc;
     // nothing is copied back, so finish() did not wait: the staging buffers are free for the next call only once the
@@ -2935,7 +2933,7 @@ static int agv_record(ssa_ctx *ctx, const ssa_aggverifier *av, size_t n, u64 *d_
     const size_t piece = ags_piece(ctx), k = (n + piece - 1) / piece;
     if (k > 4096) return SSA_ERR_ARG;
     if (ctx->ags_recs.reserve(k * 24 * sizeof(u64))) return SSA_ERR_HIP;
-    if (int rc = agx_root(ctx, av->leaves, av->tops, av->block, n)) return rc;
+    if (int rc = agx_root(*av, n)) return rc;
     const u64 *d_root = (const u64 *)ctx->agm_roots.p;      // (only now: agx_root reserves it)
     for (size_t lo = 0, j = 0; j < k; lo += piece, j++) {
         const size_t cnt = std::min(piece, n - lo);
@@ -2953,19 +2951,12 @@ static int agv_record(ssa_ctx *ctx, const ssa_aggverifier *av, size_t n, u64 *d_
     return k == 1 ? 0 : ssa_internal_msm_sum_records(ctx, (const uint64_t *)ctx->ags_recs.p, k, false, (uint64_t *)d_rec_out);
 }
 
-// what finish and the debug record refuse; *n_out: the lanes taken
-static int agv_take(const ssa_ctx *ctx, const ssa_aggverifier *av, size_t n_take, size_t *n_out) {
-    if (!ctx || !av || av->ctx != ctx) return SSA_ERR_ARG;
-    *n_out = n_take == SIZE_MAX ? av->held : n_take;
-    return *n_out > av->held ? SSA_ERR_ARG : 0;
-}
-
 // Only enqueues on the context's stream: every size it needs is on the host.  Reads the object, writes workspaces of the
 // context and the caller's verdict word.
 extern "C" int ssa_aggverifier_finish_device(ssa_ctx *ctx, ssa_aggverifier *av, const uint8_t *d_e_agg, size_t n_take,
                                              uint32_t *d_verdict_out) {
     size_t n;
-    if (int rc = agv_take(ctx, av, n_take, &n)) return rc;
+    if (int rc = agx_take(ctx, av, n_take, &n)) return rc;
     if (!d_e_agg || !d_verdict_out) return SSA_ERR_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
     if (ctx->ag_misc.reserve(AG_MISC_BYTES)) return SSA_ERR_HIP;
@@ -2989,7 +2980,7 @@ extern "C" size_t ssa_debug_aggverifier_key_span(void) { return AGV_KST_SPAN; }
 
 extern "C" int ssa_aggverifier_finish(ssa_ctx *ctx, ssa_aggverifier *av, const uint8_t *e_agg32, size_t n_take) {
     size_t n;
-    if (int rc = agv_take(ctx, av, n_take, &n)) return rc;
+    if (int rc = agx_take(ctx, av, n_take, &n)) return rc;
     if (!e_agg32) return SSA_ERR_ARG;
     HostCall hc(ctx);
     const u8 *d_e = hc.in(ctx->st_aux, e_agg32, 32);
@@ -3002,7 +2993,7 @@ extern "C" int ssa_aggverifier_finish(ssa_ctx *ctx, ssa_aggverifier *av, const u
 // tests: the summed record of finish without the comparison (no lanes, no record: SSA_ERR_ARG).  Only enqueues.
 extern "C" int ssa_debug_aggverifier_record(ssa_ctx *ctx, ssa_aggverifier *av, size_t n_take, uint64_t *d_record24_out) {
     size_t n;
-    if (int rc = agv_take(ctx, av, n_take, &n)) return rc;
+    if (int rc = agx_take(ctx, av, n_take, &n)) return rc;
     if (n == 0 || !d_record24_out || !aligned8(d_record24_out)) return SSA_ERR_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
     return agv_record(ctx, av, n, (u64 *)d_record24_out);
@@ -3291,11 +3282,9 @@ extern "C" int ssa_verify_aggregates_many(ssa_ctx *ctx, const uint8_t *aggs, con
     if (int rc = check_host_offsets(msg_off, n)) return rc;
     if (k == 0) return SSA_OK;
     HostCall hc(ctx);
-    const u8 *d_aggs = hc.in(ctx->st_sigs, aggs, 49 * n + 32 * k), *d_pks = hc.in(ctx->st_pks, pks, n * 96);
-    const u8 *d_inf = pk_inf ? hc.in(ctx->st_inf, pk_inf, n) : nullptr;
-    const MsgView mv = hc.msgs(msgs, msg_off, msg_stride, msg_len, n);
+    const DevBatch b = hc.lanes({aggs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len}, 49 * n + 32 * k, n);
     uint32_t *d_verdicts = (uint32_t *)hc.out(ctx->st_status, verdicts_out, k * sizeof(uint32_t), 16);
-    return hc.finish([&] { return agm_run(ctx, pl, d_aggs, k, d_pks, d_inf, mv, n, d_verdicts); });
+    return hc.finish([&] { return agm_run(ctx, pl, b.sigs, k, b.pks, b.pk_inf, b.msgs, n, d_verdicts); });
 }
 
 // ------------------------------------------------------------------ the producer of many aggregates
@@ -3384,17 +3373,15 @@ extern "C" int ssa_aggregates_many(ssa_ctx *ctx, const uint8_t *sigs, const uint
     if (n_fail_out) *n_fail_out = 0;
     if (k == 0) return SSA_OK;
     HostCall hc(ctx);
-    const u8 *d_sigs = hc.in(ctx->st_sigs, sigs, n * 81), *d_pks = hc.in(ctx->st_pks, pks, n * 96);
-    const u8 *d_inf = pk_inf ? hc.in(ctx->st_inf, pk_inf, n) : nullptr;
-    const MsgView mv = hc.msgs(msgs, msg_off, msg_stride, msg_len, n);
+    const DevBatch b = hc.lanes({sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len}, n * 81, n);
     u8 *d_aggs = hc.out(ctx->st_aux, aggs_out, 49 * n + 32 * k, 16);
     uint32_t *d_results = (uint32_t *)hc.out(ctx->st_aux2, results_out, k * sizeof(uint32_t), 16);
     u8 *d_status = hc.out(ctx->st_status, status_out, n, 16);
     unsigned long long nf = 0;
     hc.copy_back(&nf, ctx->ws_fail.p, sizeof nf);
     const int rc = hc.finish([&] {
-        return agp_run(ctx, pl, n ? d_sigs : nullptr, k, n ? d_pks : nullptr, d_inf, mv, n, flags, d_aggs, d_results, d_status,
-                       nullptr);
+        return agp_run(ctx, pl, n ? b.sigs : nullptr, k, n ? b.pks : nullptr, b.pk_inf, b.msgs, n, flags, d_aggs, d_results,
+                       d_status, nullptr);
     });
     if (rc) return rc;
     if (n_fail_out) *n_fail_out = nf;
@@ -3413,15 +3400,25 @@ static int agc_check_cache(const ssa_ctx *ctx, const ssa_keycache *kc, bool wire
     return !ctx || !kc || kc->ctx != ctx || kc->wire_mode != wire ? SSA_ERR_ARG : 0;
 }
 
-static int agc_run(ssa_ctx *ctx, ssa_keycache *kc, const AgPlan &pl, const uint8_t *d_aggs, size_t k, const uint8_t *d_keys,
-                   const uint8_t *d_pk_inf, bool wire, const MsgView &mv, size_t n, uint32_t *d_verdicts_out, uint64_t *sv) {
+// The cache in front of an aggregate call, in two steps, because the streaming verifier zeroes its object's statuses
+// between them.  First: the context's device is selected, the n-lane buffers of wire keys reserved and the counters
+// ctx->agc_cnt zeroed on the stream.  own_kst: the statuses go to ctx->agc_kst, reserved here too.
+static int agc_begin(ssa_ctx *ctx, bool wire, size_t n, bool own_kst) {
     HIP_TRY(hipSetDevice(ctx->device));
-    if (ctx->agc_cnt.reserve(64) || ctx->agc_kst.reserve(n + 16) ||
+    if (ctx->agc_cnt.reserve(64) || (own_kst && ctx->agc_kst.reserve(n + 16)) ||
         (wire && (ctx->agc_pks.reserve(n * 96 + 16) || ctx->agc_inf.reserve(n + 16))))
         return SSA_ERR_HIP;
+    HIP_TRY(hipMemsetAsync(ctx->agc_cnt.p, 0, AGC_CNT_WORDS * sizeof(unsigned long long), ctx->stream));
+    return 0;
+}
+
+// Then the slices: the lanes' key statuses go to kst[0, n) -- ctx->agc_kst for the many-aggregates call, the object's
+// kst + held for the streaming verifier -- and *u names the keys and flags U that the following stage reads: the
+// caller's, or for wire keys what agc_k_expand wrote into ctx->agc_pks and ctx->agc_inf.  sv (or nullptr) as above.
+static int agc_slices(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *d_keys, const uint8_t *d_pk_inf, bool wire, size_t n,
+                      u8 *kst, uint64_t *sv, DevBatch *u) {
     unsigned long long *d_cnt = (unsigned long long *)ctx->agc_cnt.p;
-    HIP_TRY(hipMemsetAsync(d_cnt, 0, AGC_CNT_WORDS * sizeof(unsigned long long), ctx->stream));
-    u8 *kst = (u8 *)ctx->agc_kst.p, *u_inf = wire ? (u8 *)ctx->agc_inf.p : nullptr;
+    u8 *u_inf = wire ? (u8 *)ctx->agc_inf.p : nullptr;
     u64 *u_pks = wire ? (u64 *)ctx->agc_pks.p : nullptr;
     const size_t slice = ctx->knobs.lane_slice;
     for (size_t lo = 0; lo < n; lo += slice) {
@@ -3445,22 +3442,45 @@ static int agc_run(ssa_ctx *ctx, ssa_keycache *kc, const AgPlan &pl, const uint8
             sv[5] += hits;
         }
     }
-    if (int rc = agm_run(ctx, pl, d_aggs, k, wire ? (const u8 *)u_pks : d_keys, wire ? (const u8 *)u_inf : d_pk_inf, mv, n,
-                         d_verdicts_out))
-        return rc;
+    u->pks = wire ? (const u8 *)u_pks : d_keys;
+    u->pk_inf = wire ? (const u8 *)u_inf : d_pk_inf;
+    return 0;
+}
+
+static int agc_run(ssa_ctx *ctx, ssa_keycache *kc, const AgPlan &pl, const uint8_t *d_aggs, size_t k, const uint8_t *d_keys,
+                   const uint8_t *d_pk_inf, bool wire, const MsgView &mv, size_t n, uint32_t *d_verdicts_out, uint64_t *sv) {
+    if (int rc = agc_begin(ctx, wire, n, true)) return rc;
+    u8 *kst = (u8 *)ctx->agc_kst.p;
+    DevBatch u{};
+    if (int rc = agc_slices(ctx, kc, d_keys, d_pk_inf, wire, n, kst, sv, &u)) return rc;
+    if (int rc = agm_run(ctx, pl, d_aggs, k, u.pks, u.pk_inf, mv, n, d_verdicts_out)) return rc;
     if (n == 0) return 0;       // (no lane, no key: every verdict is V_j)
     return timed_launch(ctx, "agc_k_key_verdicts", [&] {
         hipLaunchKernelGGL(agc_k_key_verdicts, dim3(grid_for(k, AGC_WAVES)), dim3(AGC_BLOCK), 0, ctx->stream, (const u8 *)kst,
-                           (const u32 *)ctx->agm_plan.p, (u32)k, d_verdicts_out, d_cnt);
+                           (const u32 *)ctx->agm_plan.p, (u32)k, d_verdicts_out, (unsigned long long *)ctx->agc_cnt.p);
     });
 }
 
-// statistics words 5 and 6 from the counters the device kept
-static void agc_stats_out(uint64_t stats_out[8], const uint64_t sv[8], const unsigned long long cnt[AGC_CNT_WORDS]) {
+// The caller's eight statistics words (or nullptr): words 0..4 and the host's part of word 5 from sv, the device's part
+// of word 5 from the counters the device kept, and word 6 from them too where the call has verdicts (a push of the
+// streaming verifier has none before finish: its [6] and [7] stay 0).
+static void agc_stats_out(uint64_t stats_out[8], const uint64_t sv[8], const unsigned long long cnt[AGC_CNT_WORDS],
+                          bool verdicts) {
     if (!stats_out) return;
-    for (int w = 0; w < 8; w++) stats_out[w] = sv[w];
+    for (int w = 0; w < 8; w++) stats_out[w] = w < 6 ? sv[w] : 0;
     stats_out[5] += cnt[AGC_CNT_UNPUB];
-    stats_out[6] = cnt[AGC_CNT_BAD];
+    if (verdicts) stats_out[6] = cnt[AGC_CNT_BAD];
+}
+
+// the device forms, behind everything queued: the counters are read back only for a caller that asks for statistics,
+// and that is its one extra wait
+static int agc_stats_dev(ssa_ctx *ctx, uint64_t stats_out[8], const uint64_t sv[8], bool verdicts) {
+    if (!stats_out) return 0;
+    unsigned long long cnt[AGC_CNT_WORDS] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(cnt, ctx->agc_cnt.p, sizeof cnt, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    agc_stats_out(stats_out, sv, cnt, verdicts);
+    return 0;
 }
 
 static int agc_device(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *d_aggs, const uint64_t *counts, size_t k,
@@ -3472,15 +3492,10 @@ static int agc_device(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *d_aggs, con
     if (int rc = agm_check_args(ctx, d_aggs, counts, k, d_keys, mv, d_verdicts_out, pl, &n)) return rc;
     uint64_t sv[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long cnt[AGC_CNT_WORDS] = {0, 0};
-    agc_stats_out(stats_out, sv, cnt);      // (still empty: the caller's words are zeroed)
+    agc_stats_out(stats_out, sv, cnt, true);      // (still empty: the caller's words are zeroed)
     if (k == 0) return SSA_OK;
     if (int rc = agc_run(ctx, kc, pl, d_aggs, k, d_keys, d_pk_inf, wire, mv, n, d_verdicts_out, sv)) return rc;
-    if (!stats_out) return 0;
-    // the two words the device counted: read behind the aggregate stages, the one extra wait of a caller that asks
-    HIP_TRY(hipMemcpyAsync(cnt, ctx->agc_cnt.p, sizeof cnt, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    agc_stats_out(stats_out, sv, cnt);
-    return 0;
+    return agc_stats_dev(ctx, stats_out, sv, true);      // (the two words the device counted, behind the aggregate stages)
 }
 
 static int agc_host(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *aggs, const uint64_t *counts, size_t k,
@@ -3493,18 +3508,15 @@ static int agc_host(ssa_ctx *ctx, ssa_keycache *kc, const uint8_t *aggs, const u
     if (int rc = check_host_offsets(msg_off, n)) return rc;
     uint64_t sv[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long cnt[AGC_CNT_WORDS] = {0, 0};
-    agc_stats_out(stats_out, sv, cnt);      // (still empty: the caller's words are zeroed)
+    agc_stats_out(stats_out, sv, cnt, true);      // (still empty: the caller's words are zeroed)
     if (k == 0) return SSA_OK;
     HostCall hc(ctx);
-    const u8 *d_aggs = hc.in(ctx->st_sigs, aggs, 49 * n + 32 * k);
-    const u8 *d_keys = wire ? hc.in(ctx->st_keyed, keys, n * 49) : hc.in(ctx->st_pks, keys, n * 96);
-    const u8 *d_inf = pk_inf ? hc.in(ctx->st_inf, pk_inf, n) : nullptr;
-    const MsgView mv = hc.msgs(msgs, msg_off, msg_stride, msg_len, n);
+    const DevBatch b = hc.lanes({aggs, keys, pk_inf, msgs, msg_off, msg_stride, msg_len}, 49 * n + 32 * k, n, wire);
     uint32_t *d_verdicts = (uint32_t *)hc.out(ctx->st_status, verdicts_out, k * sizeof(uint32_t), 16);
     (void)hc.out(ctx->agc_cnt, cnt, sizeof cnt, 48);      // (copied back behind the verdicts)
-    if (int rc = hc.finish([&] { return agc_run(ctx, kc, pl, d_aggs, k, d_keys, d_inf, wire, mv, n, d_verdicts, sv); }))
+    if (int rc = hc.finish([&] { return agc_run(ctx, kc, pl, b.sigs, k, b.pks, b.pk_inf, wire, b.msgs, n, d_verdicts, sv); }))
         return rc;
-    agc_stats_out(stats_out, sv, cnt);
+    agc_stats_out(stats_out, sv, cnt, true);
     return 0;
 }
 
@@ -3552,38 +3564,14 @@ extern "C" int ssa_verify_aggregates_many_cached_wire(ssa_ctx *ctx, ssa_keycache
 // 5; the device's part is ctx->agc_cnt[AGC_CNT_UNPUB].  One synchronisation per slice, the dedup's.
 static int agv_push_cached_run(ssa_ctx *ctx, ssa_aggverifier *av, ssa_keycache *kc, const u8 *d_rs49, const u8 *d_keys,
                                const u8 *d_pk_inf, bool wire, const MsgView &mv, size_t n, uint64_t *sv) {
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (ctx->agc_cnt.reserve(64) || (wire && (ctx->agc_pks.reserve(n * 96 + 16) || ctx->agc_inf.reserve(n + 16))))
-        return SSA_ERR_HIP;
-    unsigned long long *d_cnt = (unsigned long long *)ctx->agc_cnt.p;
-    HIP_TRY(hipMemsetAsync(d_cnt, 0, AGC_CNT_WORDS * sizeof(unsigned long long), ctx->stream));
+    if (int rc = agc_begin(ctx, wire, n, false)) return rc;
     if (!av->keyed) {
         if (av->held) HIP_TRY(hipMemsetAsync(av->kst.p, 0, av->held, ctx->stream));
         av->keyed = true;
     }
-    u8 *kst = (u8 *)av->kst.p + av->held, *u_inf = wire ? (u8 *)ctx->agc_inf.p : nullptr;
-    u64 *u_pks = wire ? (u64 *)ctx->agc_pks.p : nullptr;
-    const size_t slice = ctx->knobs.lane_slice;
-    for (size_t lo = 0; lo < n; lo += slice) {
-        const size_t cnt = n - lo < slice ? n - lo : slice;
-        const KeySource src = wire ? KeySource{nullptr, nullptr, d_keys + 49 * lo, 49}
-                                   : KeySource{d_keys + 96 * lo, d_pk_inf ? d_pk_inf + lo : nullptr, nullptr};
-        KeyView kv{};
-        KeyRows rows{};
-        uint64_t u = 0, hits = 0, ks[4] = {0, 0, 0, 0};
-        const unsigned long long *d_unpub = nullptr;
-        if (int rc = keycache_slice(ctx, kc, src, cnt, nullptr, &kv, &u, &hits, ks, &d_unpub, &rows)) return rc;
-        const int rc = timed_launch(ctx, "agc_expand", [&] {
-            hipLaunchKernelGGL(agc_k_expand, dim3(grid_for(wire ? cnt * 12 : cnt, 256)), dim3(256), 0, ctx->stream, kv.lane_key,
-                               kv.status, wire ? rows.pks : (const u64 *)nullptr, rows.inf, kv.n_keys, (u32)cnt, kst + lo,
-                               wire ? u_pks + 12 * lo : (u64 *)nullptr, wire ? u_inf + lo : (u8 *)nullptr, d_unpub, d_cnt);
-        });
-        if (rc) return rc;
-        sv[0] += u;
-        for (int w = 0; w < 4; w++) sv[1 + w] += ks[w];
-        sv[5] += hits;
-    }
-    return agv_push_body(ctx, av, d_rs49, wire ? (const u8 *)u_pks : d_keys, wire ? (const u8 *)u_inf : d_pk_inf, mv, n, true);
+    DevBatch u{};
+    if (int rc = agc_slices(ctx, kc, d_keys, d_pk_inf, wire, n, (u8 *)av->kst.p + av->held, sv, &u)) return rc;
+    return agv_push_body(ctx, av, d_rs49, u.pks, u.pk_inf, mv, n, true);
 }
 
 // what all four cached pushes refuse before anything is enqueued, counted or written
@@ -3593,30 +3581,17 @@ static int agv_push_cached_args(const ssa_ctx *ctx, const ssa_aggverifier *av, c
     return agv_push_args(ctx, av, mv, n, rs49, keys);
 }
 
-// words 0..5 of section 23's statistics; [6] and [7] stay 0: nothing about verdicts is known before finish
-static void agv_stats_out(uint64_t stats_out[8], const uint64_t sv[8], unsigned long long unpublished) {
-    if (!stats_out) return;
-    for (int w = 0; w < 8; w++) stats_out[w] = w < 6 ? sv[w] : 0;
-    stats_out[5] += unpublished;
-}
-
+// The statistics of a cached push: words 0..5 of section 23's; [6] and [7] stay 0 (agc_stats_out without verdicts):
+// nothing about verdicts is known before finish.
 static int agv_push_cached_dev(ssa_ctx *ctx, ssa_aggverifier *av, ssa_keycache *kc, const u8 *d_rs49, const u8 *d_keys,
                                const u8 *d_pk_inf, bool wire, const MsgView &mv, size_t n, uint64_t stats_out[8]) {
     if (int rc = agv_push_cached_args(ctx, av, kc, wire, mv, n, d_rs49, d_keys)) return rc;
     uint64_t sv[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    agv_stats_out(stats_out, sv, 0);
-    if (n == 0) {
-        av->pushes++;
-        return SSA_OK;
-    }
+    const unsigned long long none[AGC_CNT_WORDS] = {0, 0};
+    agc_stats_out(stats_out, sv, none, false);
+    if (n == 0) return agv_push_body(ctx, av, nullptr, nullptr, nullptr, mv, 0, false);
     if (int rc = agv_push_cached_run(ctx, av, kc, d_rs49, d_keys, d_pk_inf, wire, mv, n, sv)) return rc;
-    if (!stats_out) return SSA_OK;
-    // the one word the device counted: read behind the push, the one extra wait of a caller that asks
-    unsigned long long cnt[AGC_CNT_WORDS] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(cnt, ctx->agc_cnt.p, sizeof cnt, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    agv_stats_out(stats_out, sv, cnt[AGC_CNT_UNPUB]);
-    return SSA_OK;
+    return agc_stats_dev(ctx, stats_out, sv, false);      // (the one word the device counted, behind the push)
 }
 
 static int agv_push_cached_host(ssa_ctx *ctx, ssa_aggverifier *av, ssa_keycache *kc, const uint8_t *rs49,
@@ -3624,22 +3599,19 @@ static int agv_push_cached_host(ssa_ctx *ctx, ssa_aggverifier *av, ssa_keycache 
                                 const uint64_t *msg_off, size_t msg_stride, size_t msg_len, size_t n, uint64_t stats_out[8]) {
     if (int rc = agv_push_cached_args(ctx, av, kc, wire, {msgs, msg_off, msg_stride, msg_len}, n, rs49, keys)) return rc;
     if (int rc = check_host_offsets(msg_off, n)) return rc;
+    if (n == 0)
+        return agv_push_cached_dev(ctx, av, kc, nullptr, nullptr, nullptr, wire, {nullptr, nullptr, msg_stride, msg_len}, 0,
+                                   stats_out);
     uint64_t sv[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    agv_stats_out(stats_out, sv, 0);
-    if (n == 0) {
-        av->pushes++;
-        return SSA_OK;
-    }
-    HostCall hc(ctx);
-    const u8 *d_rs = hc.in(ctx->st_sigs, rs49, n * 49);
-    const u8 *d_keys = wire ? hc.in(ctx->st_keyed, keys, n * 49) : hc.in(ctx->st_pks, keys, n * 96);
-    const u8 *d_inf = pk_inf ? hc.in(ctx->st_inf, pk_inf, n) : nullptr;
-    const MsgView mv = hc.msgs(msgs, msg_off, msg_stride, msg_len, n);
     unsigned long long cnt[AGC_CNT_WORDS] = {0, 0};
+    agc_stats_out(stats_out, sv, cnt, false);
+    HostCall hc(ctx);
+    const DevBatch b = hc.lanes({rs49, keys, pk_inf, msgs, msg_off, msg_stride, msg_len}, n * 49, n, wire);
     (void)hc.out(ctx->agc_cnt, cnt, sizeof cnt, 48);      // (copied back behind the push: finish() waits for it, and with
                                                           //  it for the kernels that read the staging buffers)
-    if (int rc = hc.finish([&] { return agv_push_cached_run(ctx, av, kc, d_rs, d_keys, d_inf, wire, mv, n, sv); })) return rc;
-    agv_stats_out(stats_out, sv, cnt[AGC_CNT_UNPUB]);
+    if (int rc = hc.finish([&] { return agv_push_cached_run(ctx, av, kc, b.sigs, b.pks, b.pk_inf, wire, b.msgs, n, sv); }))
+        return rc;
+    agc_stats_out(stats_out, sv, cnt, false);
     return SSA_OK;
 }
 
@@ -3686,8 +3658,8 @@ static int avc_run(ssa_ctx *ctx, ssa_keycache *kc, const DevBatch &b, const u8 *
                    u32 *d_kept_out, uint64_t *n_kept_out, u8 *d_status_out, u8 *d_keys_out, u8 *d_inf_out,
                    uint64_t *stats_out) {
     HIP_TRY(hipSetDevice(ctx->device));
-    if (!d_status_out && ctx->ag_status.reserve(n + 16)) return SSA_ERR_HIP;
-    u8 *d_status = d_status_out ? d_status_out : (u8 *)ctx->ag_status.p;
+    u8 *d_status = ag_status_buf(ctx, d_status_out, n);
+    if (!d_status) return SSA_ERR_HIP;
     if (d_keyed) {
         if (ctx->ws_h.reserve(n * 32) || ctx->ag_dig.reserve(n * 32)) return SSA_ERR_HIP;
         if (int rc = ssa_internal_screen_keyed_hashed(ctx, kc, d_keyed, b.msgs, n, (uint64_t *)ctx->ws_h.p,
@@ -3699,30 +3671,22 @@ static int avc_run(ssa_ctx *ctx, ssa_keycache *kc, const DevBatch &b, const u8 *
         if (int rc = ssa_internal_screen_many_hashed(ctx, kc, b, n, (const uint64_t *)ctx->ws_h.p, d_status, stats_out))
             return rc;
     }
-    uint64_t m = 0;
-    if (int rc = av_keep(ctx, d_status, n, d_kept_out, &m)) return rc;
-    *n_kept_out = m;
-    // everything behind the aggregate of the kept lanes is zero; with none kept, that is the empty aggregate
-    const size_t used = m ? SSA_AGGREGATE_LENGTH(m) : 0;
-    if (used < SSA_AGGREGATE_LENGTH(n))
-        HIP_TRY(hipMemsetAsync(d_agg_out + used, 0, SSA_AGGREGATE_LENGTH(n) - used, ctx->stream));
     // the kept lanes' keys as the caller gave them, and zeros up to the capacity of n lanes (the kernel writes both)
-    if (d_keys_out || d_inf_out) {
+    const auto gather_keys = [&](size_t m) {
+        if (!d_keys_out && !d_inf_out) return 0;
         const u32 width = d_keyed ? 49u : 96u;
-        const int rc = timed_launch(ctx, "av_k_gather_keys", [&] {
+        return timed_launch(ctx, "av_k_gather_keys", [&] {
             if (d_keys_out)
                 hipLaunchKernelGGL(av_k_gather_keys, dim3(grid_for((n * width + 3) / 4, 256)), dim3(256), 0, ctx->stream,
-                                   d_keyed ? d_keyed : b.pks, d_keyed ? 130u : 96u, width, (const u32 *)d_kept_out, (size_t)m, n,
+                                   d_keyed ? d_keyed : b.pks, d_keyed ? 130u : 96u, width, (const u32 *)d_kept_out, m, n,
                                    d_keys_out);
             if (d_inf_out)
                 hipLaunchKernelGGL(av_k_gather_keys, dim3(grid_for((n + 3) / 4, 256)), dim3(256), 0, ctx->stream, b.pk_inf, 1u,
-                                   1u, (const u32 *)d_kept_out, (size_t)m, n, d_inf_out);
+                                   1u, (const u32 *)d_kept_out, m, n, d_inf_out);
         });
-        if (rc) return rc;
-    }
-    if (m == 0) return SSA_OK;
-    return d_keyed ? av_aggregate_kept(ctx, d_keyed, 130, 49, d_kept_out, m, d_agg_out)
-                   : av_aggregate_kept(ctx, b.sigs, 81, 0, d_kept_out, m, d_agg_out);
+    };
+    return d_keyed ? av_finish_kept(ctx, d_status, n, d_keyed, 130, 49, d_agg_out, d_kept_out, n_kept_out, gather_keys)
+                   : av_finish_kept(ctx, d_status, n, b.sigs, 81, 0, d_agg_out, d_kept_out, n_kept_out, gather_keys);
 }
 
 // arguments of all four forms, before anything is written: in0, in1 = the inputs that must not be null when n != 0
@@ -3783,17 +3747,14 @@ extern "C" int ssa_aggregate_valid_many_cached(ssa_ctx *ctx, ssa_keycache *kc, c
         return SSA_OK;
     }
     HostCall hc(ctx);
-    const u8 *d_sigs = hc.in(ctx->st_sigs, sigs, n * 81), *d_pks = hc.in(ctx->st_pks, pks, n * 96);
-    const u8 *d_inf = pk_inf ? hc.in(ctx->st_inf, pk_inf, n) : nullptr;
-    const MsgView mv = hc.msgs(msgs, msg_off, msg_stride, msg_len, n);
+    const DevBatch b = hc.lanes({sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len}, n * 81, n);
     u8 *d_agg = hc.out(ctx->st_aux, agg_out, SSA_AGGREGATE_LENGTH(n), 16);
     u32 *d_kept = (u32 *)hc.out(ctx->st_aux2, kept_out, n * sizeof(u32));
     u8 *d_status = hc.out(ctx->st_status, status_out, n, 16);
     u8 *d_pks_out = pks_out ? hc.out(ctx->avc_keys, pks_out, n * 96) : nullptr;
     u8 *d_inf_out = pk_inf_out ? hc.out(ctx->avc_inf, pk_inf_out, n, 16) : nullptr;
     return hc.finish([&] {
-        return avc_run(ctx, kc, {d_sigs, d_pks, d_inf, mv}, nullptr, n, d_agg, d_kept, n_kept_out, d_status, d_pks_out, d_inf_out,
-                       stats_out);
+        return avc_run(ctx, kc, b, nullptr, n, d_agg, d_kept, n_kept_out, d_status, d_pks_out, d_inf_out, stats_out);
     });
 }
 

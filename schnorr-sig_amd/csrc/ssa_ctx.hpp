@@ -581,6 +581,17 @@ struct HostCall {
         mv.msgs = rc ? nullptr : (const u8 *)ctx->st_msgs.p;
         return mv;
     }
+    // the n lanes of an aggregate call, staged in this order: the lead array (b.sigs: lead_bytes of signatures, R's or a
+    // wire form) into ctx->st_sigs, the keys (96 bytes each into ctx->st_pks; wire_keys: 49 each into ctx->st_keyed),
+    // the identity flags if there are any, the messages
+    DevBatch lanes(const HostBatch &b, size_t lead_bytes, size_t n, bool wire_keys = false) {
+        DevBatch d{};
+        d.sigs = in(ctx->st_sigs, b.sigs, lead_bytes);
+        d.pks = wire_keys ? in(ctx->st_keyed, b.pks, n * 49) : in(ctx->st_pks, b.pks, n * 96);
+        d.pk_inf = b.pk_inf ? in(ctx->st_inf, b.pk_inf, n) : nullptr;
+        d.msgs = msgs(b.msgs, b.msg_off, b.msg_stride, b.msg_len, n);
+        return d;
+    }
     template <class F>
     int finish(F &&device_form) {
         step(device_form);
