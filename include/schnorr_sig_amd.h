@@ -1229,8 +1229,26 @@ int ssa_aggregate_valid_keyed_many_cached_device(ssa_ctx *ctx, ssa_keycache *kc,
  *   reset    empties the object (counters included) and keeps its memory.
  *   info     [0] lanes held  [1] capacity  [2] block_lanes  [3] pushes  [4] lanes offered  [5] lanes dropped
  *            [6] blocks whose top is stored  [7] finishes.
- * NOT here: removing the lanes a block took from the front (the rest changes place: reset and push it again),
- * admission through a key cache, ssa_multi forms.  The validator's counterpart is ssa_aggverifier, below. */
+ *   drop_front, remove   take lanes OUT of the object in place: the lanes a block took from the
+ *            front, or lanes withdrawn anywhere.  Let L be the lanes held and K the ascending list of the kept ones: after
+ *            the call the object is indistinguishable from one that admitted L[K[0]], L[K[1]], ... in that order --
+ *            info [0] == |K|, [6] == |K| / block_lanes, every finish(n_take <= |K|) is byte for byte the ssa_aggregate_many
+ *            of the first n_take kept lanes handed in alone, later pushes append behind lane |K|.  The counters pushes,
+ *            offered, dropped and finishes do not move ("dropped" counts refused admissions, not withdrawals).  No
+ *            message, key or signature is touched again: the stored R, scalar and leaf of a lane do not depend on its
+ *            place, so the kept lanes are moved and only the blocks that changed are reduced again.
+ *            drop_front(n) removes the first n held lanes; n == SIZE_MAX or n == held: all of them; n == 0: SSA_OK,
+ *            nothing is launched; n > held: SSA_ERR_ARG.  It only enqueues, as finish_device does.
+ *            remove takes one byte per held lane: n_bytes must equal the lanes held, and lane i is removed iff
+ *            drop[i] != 0 -- the status-vector convention, so the status_out of a screen can be handed in as it is; every
+ *            byte vector is valid.  *n_kept_out (HOST memory in both forms) = |K|.  The _device form synchronises the
+ *            context's stream once, for that count.
+ *            SSA_ERR_ARG, with the object, its info and every later finish unchanged: a context other than the object's,
+ *            an orphaned object, a NULL mask with lanes held, a NULL n_kept_out, the length and range errors above.
+ *            A move in place cannot be undone: a runtime error (SSA_ERR_HIP) once the move has begun leaves the object
+ *            EMPTY (0 lanes held, counters as they were), never half-moved.
+ * NOT here: reordering held lanes, finishing an arbitrary subset without removing it, admission through a key cache,
+ * ssa_multi forms.  The validator's counterpart is ssa_aggverifier, below. */
 typedef struct ssa_aggregator ssa_aggregator;
 #define SSA_AGGR_NO_SCREEN 1u      /* push flag */
 int ssa_aggregator_create(ssa_ctx *ctx, size_t capacity, size_t block_lanes, uint32_t flags, ssa_aggregator **out);
@@ -1249,6 +1267,20 @@ int ssa_aggregator_finish_device(ssa_ctx *ctx, ssa_aggregator *ag, size_t n_take
  * device): out[0] the first completed block, out[1] the number of completed blocks, out[2] the first lane of the ragged
  * tail, out[3] its length.  SSA_ERR_ARG for a block size create would refuse or held + m above SSA_MAX_BATCH. */
 int ssa_debug_aggregator_plan(uint64_t held, uint64_t m, uint64_t block_lanes, uint64_t out[4]);
+int ssa_aggregator_drop_front(ssa_ctx *ctx, ssa_aggregator *ag, size_t n);
+int ssa_aggregator_remove(ssa_ctx *ctx, ssa_aggregator *ag, const uint8_t *drop, size_t n_bytes, uint64_t *n_kept_out);
+int ssa_aggregator_remove_device(ssa_ctx *ctx, ssa_aggregator *ag, const uint8_t *d_drop, size_t n_bytes,
+                                 uint64_t *n_kept_out);
+/* tests: what a removal does to the stored tops (host code, no device).  held: the lanes held before; first_changed: the
+ * first place whose content changes -- the first removed lane; new_held: the lanes kept; first_changed <= new_held <=
+ * held.  first_changed == 0 stands for drop_front(held - new_held), the one removal the library plans with that value (a
+ * mask that removes lane 0 is planned with every block reduced again).  out[0]: blocks [0, out[0]) keep their tops;
+ * out[1]: the tops of blocks [0, out[1]) are MOVED from blocks (held - new_held) / block_lanes onwards (a front drop by a
+ * multiple of block_lanes only); blocks [out[2], out[2] + out[3]) are reduced again from the moved leaves.  Every
+ * complete block of the new object is in exactly one of the three.  SSA_ERR_ARG for a block size create would refuse,
+ * held above SSA_MAX_BATCH, or an order other than the above. */
+int ssa_debug_aggregator_remove_plan(uint64_t held, uint64_t first_changed, uint64_t new_held, uint64_t block_lanes,
+                                     uint64_t out[4]);
 
 /* ---- streaming aggregate verifier: push a block body as it arrives, finish with e_agg ----
  * The validator's counterpart of the streaming aggregator.  A block body -- the R's, keys and messages of a half-aggregate

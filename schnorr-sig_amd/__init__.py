@@ -301,6 +301,10 @@ def _load():
         "ssa_aggregator_finish": (i32, [vp, vp, sz, vp]),
         "ssa_aggregator_finish_device": (i32, [vp, vp, sz, vp]),
         "ssa_debug_aggregator_plan": (i32, [C.c_uint64, C.c_uint64, C.c_uint64, u64p]),
+        "ssa_aggregator_drop_front": (i32, [vp, vp, sz]),
+        "ssa_aggregator_remove": (i32, [vp, vp, vp, sz, u64p]),
+        "ssa_aggregator_remove_device": (i32, [vp, vp, vp, sz, u64p]),
+        "ssa_debug_aggregator_remove_plan": (i32, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, u64p]),
         "ssa_aggverifier_create": (i32, [vp, sz, sz, u32, C.POINTER(vp)]),
         "ssa_aggverifier_destroy": (None, [vp]),
         "ssa_aggverifier_reset": (i32, [vp]),
@@ -1817,6 +1821,16 @@ def aggregator_plan(held, m, block_lanes=0):
     return tuple(int(v) for v in out)
 
 
+def aggregator_remove_plan(held, first_changed, new_held, block_lanes=0):
+    """tests: (blocks whose tops stay, blocks whose tops are moved, first block reduced again, blocks reduced again) of a
+    removal that keeps new_held of `held` lanes and changes no place in front of first_changed; first_changed == 0
+    stands for drop_front(held - new_held) (ssa_debug_aggregator_remove_plan: host code, no device)"""
+    out = (C.c_uint64 * 4)()
+    _check(_lib.ssa_debug_aggregator_remove_plan(int(held), int(first_changed), int(new_held), int(block_lanes), out),
+           "ssa_debug_aggregator_remove_plan")
+    return tuple(int(v) for v in out)
+
+
 def _n_take(n_take):
     """the n_take argument of the ABI: None takes every lane held"""
     return AGGREGATOR_ALL if n_take is None else int(n_take)
@@ -1844,7 +1858,8 @@ class _LaneStore(_Handle):
 class Aggregator(_LaneStore):
     """ssa_aggregator handle (Engine.aggregator): the lanes admitted so far, on the device, in
     arrival order.  push() admits a batch on arrival; finish() gives the AggregateSignature of the first n_take held
-    lanes -- what Engine.aggregate gives those lanes handed in alone -- and changes nothing.  Tied to its Engine like
+    lanes -- what Engine.aggregate gives those lanes handed in alone -- and changes nothing; drop_front(), remove() and
+    take() remove lanes in place and keep the rest of the pool.  Tied to its Engine like
     KeyCache; destroyed exactly once (close(), the end of a `with` block, or when the object goes away)."""
     _prefix, _fields = "aggregator", AGGREGATOR_FIELDS
 
@@ -1899,6 +1914,39 @@ class Aggregator(_LaneStore):
         _check(_lib.ssa_aggregator_finish_device(self.engine._ctx, self.handle, n, d_agg.data_ptr()),
                "ssa_aggregator_finish_device")
         return n
+
+    def drop_front(self, n=None, engine=None):
+        """removes the first n held lanes in place (None: all of them): the object is then what
+        it would be had it admitted the remaining lanes alone, in their order; the counters but `held` and `blocks` do
+        not move.  Only enqueues.  n above the lanes held raises and changes nothing.  engine: tests."""
+        _check(_lib.ssa_aggregator_drop_front((engine or self.engine)._ctx, self.handle, _n_take(n)),
+               "ssa_aggregator_drop_front")
+
+    def remove(self, drop, engine=None):
+        """drop: one byte per held lane; lane i is removed iff drop[i] != 0 (the status vector of a screen can be handed
+        in as it is) -> the number of lanes kept.  The kept lanes stay in their order, as if they alone had been
+        admitted.  Another length raises and changes nothing.  engine: tests."""
+        drop = np.ascontiguousarray(drop, dtype=np.uint8).reshape(-1)
+        n_kept = C.c_uint64(0)
+        _check(_lib.ssa_aggregator_remove((engine or self.engine)._ctx, self.handle, _ptr(drop) if drop.size else None,
+                                          drop.size, C.byref(n_kept)), "ssa_aggregator_remove")
+        return int(n_kept.value)
+
+    def remove_device(self, d_drop):
+        """device form of remove over a uint8 torch tensor on the engine's device (any byte alignment), one byte per held
+        lane.  Synchronises the stream once, for the kept count -> that count."""
+        n_kept = C.c_uint64(0)
+        _check(_lib.ssa_aggregator_remove_device(self.engine._ctx, self.handle, _addr(d_drop), int(d_drop.numel()),
+                                                 C.byref(n_kept)), "ssa_aggregator_remove_device")
+        return int(n_kept.value)
+
+    def take(self, n_take=None):
+        """finish(n_take), then drop_front of the same lanes: the AggregateSignature of the first n_take held lanes
+        (None: all), which leave the object; the rest stays for the next block"""
+        n = self.info()["held"] if n_take is None else int(n_take)
+        agg = self.finish(n)
+        self.drop_front(n)
+        return agg
 
 
 class AggregateVerifier(_LaneStore):

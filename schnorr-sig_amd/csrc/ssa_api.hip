@@ -2063,20 +2063,25 @@ extern "C" int ssa_aggregate_many(ssa_ctx *ctx, const uint8_t *sigs, const uint8
 
 // ------------------------------------------------------------------ filtering half-aggregation
 // d_kept[0, *m_out) = the lanes of d_status[0, n) whose byte is zero, ascending, and zeros up to n; *m_out their number.
-// Synchronises the stream: the number is read from the device.
-static int av_keep(ssa_ctx *ctx, const u8 *d_status, size_t n, u32 *d_kept, uint64_t *m_out) {
+// av_keep_enqueue only enqueues the three launches and says where on the device the number will stand; av_keep then
+// synchronises the stream: the number is read from the device.
+static int av_keep_enqueue(ssa_ctx *ctx, const u8 *d_status, size_t n, u32 *d_kept, const u32 **d_m_out) {
     const unsigned nb = grid_for(n, AV_BLOCK);
     if (ctx->av_blk.reserve((2 * (size_t)nb + 1) * sizeof(u32))) return SSA_ERR_HIP;
     u32 *blk_cnt = (u32 *)ctx->av_blk.p, *blk_off = blk_cnt + nb;
-    const int rc = timed_launch(ctx, "av_k_keep", [&] {
+    *d_m_out = blk_off + nb;
+    return timed_launch(ctx, "av_k_keep", [&] {
         hipLaunchKernelGGL(av_k_keep_count, dim3(nb), dim3(AV_BLOCK), 0, ctx->stream, d_status, (u32)n, blk_cnt);
         hipLaunchKernelGGL(av_k_keep_scan, dim3(1), dim3(AV_BLOCK), 0, ctx->stream, (const u32 *)blk_cnt, nb, blk_off);
         hipLaunchKernelGGL(av_k_keep_list, dim3(nb), dim3(AV_BLOCK), 0, ctx->stream, d_status, (u32)n, (const u32 *)blk_off,
                            nb, d_kept);
     });
-    if (rc) return rc;
+}
+static int av_keep(ssa_ctx *ctx, const u8 *d_status, size_t n, u32 *d_kept, uint64_t *m_out) {
+    const u32 *d_m = nullptr;
+    if (int rc = av_keep_enqueue(ctx, d_status, n, d_kept, &d_m)) return rc;
     u32 m = 0;
-    HIP_TRY(hipMemcpyAsync(&m, blk_off + nb, sizeof m, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(&m, d_m, sizeof m, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     *m_out = m;
     return 0;
@@ -2823,6 +2828,117 @@ extern "C" int ssa_aggregator_finish(ssa_ctx *ctx, ssa_aggregator *ag, size_t n_
     HostCall hc(ctx);
     u8 *d_agg = hc.out(ctx->st_aux, agg_out, SSA_AGGREGATE_LENGTH(n), 16);
     return hc.finish([&] { return ssa_aggregator_finish_device(ctx, ag, n, d_agg); });
+}
+
+// ---- removing lanes in place (the move and its hazard: agx_k_move in ssa_aggregator.hpp)
+// (a first_changed of 0 is planned as the front drop of held - new_held lanes: see the header)
+extern "C" int ssa_debug_aggregator_remove_plan(uint64_t held, uint64_t first_changed, uint64_t new_held,
+                                                uint64_t block_lanes, uint64_t out[4]) {
+    const size_t B = agx_block(block_lanes);
+    if (!out || !B || held > SSA_MAX_BATCH || new_held > held || first_changed > new_held) return SSA_ERR_ARG;
+    const AgxRemovePlan p = agx_remove_plan(held, first_changed, new_held, B, first_changed == 0);
+    out[0] = p.unchanged;
+    out[1] = p.moved;
+    out[2] = p.first;
+    out[3] = p.count;
+    return 0;
+}
+
+// The m kept lanes of an object -- ascending: d_kept[c], or c + (held - m) for a front drop, which has no list
+// (d_kept == nullptr) -- take the places [0, m).  f: the first place whose content changes.  Only enqueues.  The move is
+// in place and cannot be undone: once its first launch is enqueued, an error leaves the object EMPTY, never half-moved.
+static int agx_remove_apply(ssa_aggregator *ag, const u32 *d_kept, size_t f, size_t m) {
+    ssa_ctx *ctx = ag->ctx;
+    const size_t held = ag->held, B = ag->block, shift = d_kept ? 0 : held - m;
+    if (m == held) return SSA_OK;
+    const AgxRemovePlan p = agx_remove_plan(held, f, m, B, !d_kept);
+    const size_t P = f < m ? std::min(ags_piece(ctx), m - f) : 0, top0 = shift / B;
+    const bool tops_overlap = p.moved && top0 < p.moved;
+    if ((P && ctx->agx_stage.reserve(113 * P + 16)) || (tops_overlap && ctx->ags_tops.reserve((size_t)p.moved * 32)))
+        return SSA_ERR_HIP;
+    // one piece of staging: P leaves, P scalars, 49 P bytes of R's (each part dword-aligned, and more)
+    u64 *st_leaves = (u64 *)ctx->agx_stage.p, *st_scal = st_leaves + 4 * P;
+    u8 *st_wire = (u8 *)(st_scal + 4 * P);
+    u64 *leaves = (u64 *)ag->leaves.p, *scal = (u64 *)ag->scal.p, *tops = (u64 *)ag->tops.p;
+    u8 *wire = (u8 *)ag->wire.p;
+    const int rc = [&]() -> int {
+        for (size_t c0 = f; c0 < m; c0 += P) {
+            const size_t cnt = std::min(P, m - c0);
+            const int r = timed_launch(ctx, "agx_k_move", [&] {
+                hipLaunchKernelGGL(agx_k_move, dim3(grid_for(cnt, 256)), dim3(256), 0, ctx->stream, d_kept, shift, c0, cnt,
+                                   (const u64 *)leaves, (const u64 *)scal, (const u8 *)wire, st_leaves, st_scal, st_wire);
+            });
+            if (r) return r;
+            // behind the gather on the stream, in front of the next piece's: places [c0, c0 + cnt) alone are written
+            HIP_TRY(hipMemcpyAsync(leaves + 4 * c0, st_leaves, 32 * cnt, hipMemcpyDeviceToDevice, ctx->stream));
+            HIP_TRY(hipMemcpyAsync(scal + 4 * c0, st_scal, 32 * cnt, hipMemcpyDeviceToDevice, ctx->stream));
+            HIP_TRY(hipMemcpyAsync(wire + 49 * c0, st_wire, 49 * cnt, hipMemcpyDeviceToDevice, ctx->stream));
+        }
+        if (p.moved) {       // new block b is old block b + top0; a copy onto its own source goes through a workspace
+            const size_t bytes = (size_t)p.moved * 32;
+            if (tops_overlap) {
+                HIP_TRY(hipMemcpyAsync(ctx->ags_tops.p, tops + 4 * top0, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+                HIP_TRY(hipMemcpyAsync(tops, ctx->ags_tops.p, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+            } else {
+                HIP_TRY(hipMemcpyAsync(tops, tops + 4 * top0, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+            }
+        }
+        return p.count ? agx_reduce_blocks(*ag, AgxPlan{p.first, p.count, 0, 0}) : 0;
+    }();
+    ag->held = rc ? 0 : m;
+    return rc;
+}
+
+// Only enqueues on the context's stream: every size it needs is on the host.
+extern "C" int ssa_aggregator_drop_front(ssa_ctx *ctx, ssa_aggregator *ag, size_t n) {
+    size_t k;
+    if (int rc = agx_take(ctx, ag, n, &k)) return rc;
+    if (k == 0) return SSA_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    return agx_remove_apply(ag, nullptr, 0, ag->held - k);
+}
+
+// what both forms of remove refuse before anything is enqueued
+static int agx_remove_args(const ssa_ctx *ctx, const ssa_aggregator *ag, const uint8_t *drop, size_t n_bytes,
+                           const uint64_t *n_kept_out) {
+    return !ctx || !ag || ag->ctx != ctx || !n_kept_out || n_bytes != ag->held || (n_bytes && !drop) ? SSA_ERR_ARG : 0;
+}
+
+// Synchronises the stream once, for the kept count and the first place that changes, which are read from the device
+// together; from then on every size is on the host.
+extern "C" int ssa_aggregator_remove_device(ssa_ctx *ctx, ssa_aggregator *ag, const uint8_t *d_drop, size_t n_bytes,
+                                            uint64_t *n_kept_out) {
+    if (int rc = agx_remove_args(ctx, ag, d_drop, n_bytes, n_kept_out)) return rc;
+    *n_kept_out = 0;
+    const size_t held = ag->held;
+    if (held == 0) return SSA_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (ctx->agx_kept.reserve(held * sizeof(u32)) || ctx->agx_first.reserve(sizeof(u32))) return SSA_ERR_HIP;
+    u32 *d_kept = (u32 *)ctx->agx_kept.p, *d_first = (u32 *)ctx->agx_first.p;
+    const u32 *d_m = nullptr;
+    // a lane is kept iff its byte is zero: the status-vector convention av_keep lists by
+    if (int rc = av_keep_enqueue(ctx, d_drop, held, d_kept, &d_m)) return rc;
+    const int rc = timed_launch(ctx, "agx_k_first_changed", [&] {
+        hipLaunchKernelGGL(agx_k_first_changed, dim3(grid_for(held + 1, 256)), dim3(256), 0, ctx->stream,
+                           (const u32 *)d_kept, d_m, held, d_first);
+    });
+    if (rc) return rc;
+    u32 m = 0, f = 0;
+    HIP_TRY(hipMemcpyAsync(&m, d_m, sizeof m, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(&f, d_first, sizeof f, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (m > held || f > m) return SSA_ERR_HIP;        // (cannot be: the list is of `held` bytes)
+    *n_kept_out = m;
+    return agx_remove_apply(ag, d_kept, f, m);
+}
+
+extern "C" int ssa_aggregator_remove(ssa_ctx *ctx, ssa_aggregator *ag, const uint8_t *drop, size_t n_bytes,
+                                     uint64_t *n_kept_out) {
+    if (int rc = agx_remove_args(ctx, ag, drop, n_bytes, n_kept_out)) return rc;
+    if (n_bytes == 0) return ssa_aggregator_remove_device(ctx, ag, nullptr, 0, n_kept_out);
+    HostCall hc(ctx);
+    const u8 *d_drop = hc.in(ctx->st_status, drop, n_bytes);
+    return hc.finish([&] { return ssa_aggregator_remove_device(ctx, ag, d_drop, n_bytes, n_kept_out); });
 }
 
 // ------------------------------------------------------------------ streaming aggregate verifier (ssa_aggverifier.hpp)

@@ -205,6 +205,9 @@ struct CtxKnobs {
     /* the streaming aggregator (ssa_aggregator.hpp): the kept lanes of one push.  What the object \
        holds between calls is its own and not listed here */ \
     X(agx_kept) \
+    /* removing lanes from a streaming aggregator: the staging of one piece of the move -- its \
+       leaves, its scalars, its R's -- and the first place a mask changes.  Nothing lives in them between calls */ \
+    X(agx_stage) X(agx_first) \
     /* the end game of ssa_k_verify, per tail group: finished pieces; parked accumulators + status (152 B per lane) */ \
     X(tail_done) X(tail_park)
 

@@ -922,6 +922,35 @@ class Aggregator {
         if (rc != 0) throw std::runtime_error(std::string("ssa_aggregator_finish: ") + ssa_strerror(rc));
         return a;
     }
+    // Removing triples in place: the object is then what it would be had it admitted the remaining
+    // triples alone, in their order; only `held` and `blocks` of the counters move.  drop_front: the first n (All: every
+    // one); more than are held throws and changes nothing.
+    void drop_front(size_t n = All) {
+        const int rc = ssa_aggregator_drop_front(cx_.get(), ag_, n);
+        if (rc != 0) throw std::runtime_error(std::string("ssa_aggregator_drop_front: ") + ssa_strerror(rc));
+    }
+    // drop: one byte per held triple; triple i is removed iff drop[i] != 0 (a status vector can be handed in as it is).
+    // -> the number of triples kept.  Another length throws and changes nothing.
+    uint64_t remove(const std::vector<uint8_t> &drop) {
+        uint64_t n_kept = 0;
+        const int rc = ssa_aggregator_remove(cx_.get(), ag_, drop.empty() ? nullptr : drop.data(), drop.size(), &n_kept);
+        if (rc != 0) throw std::runtime_error(std::string("ssa_aggregator_remove: ") + ssa_strerror(rc));
+        return n_kept;
+    }
+    // the same over a mask in device memory; synchronises the context's stream once, for the count
+    uint64_t remove_device(const uint8_t *d_drop, size_t n_bytes) {
+        uint64_t n_kept = 0;
+        const int rc = ssa_aggregator_remove_device(cx_.get(), ag_, d_drop, n_bytes, &n_kept);
+        if (rc != 0) throw std::runtime_error(std::string("ssa_aggregator_remove_device: ") + ssa_strerror(rc));
+        return n_kept;
+    }
+    // finish(n_take), then drop_front of the same triples: they leave the object, the rest stays for the next block
+    AggregateSignature take(size_t n_take = All) {
+        const size_t n = n_take == All ? (size_t)info().held : n_take;
+        AggregateSignature a = finish(n);
+        drop_front(n);
+        return a;
+    }
     void reset() {
         const int rc = ssa_aggregator_reset(ag_);
         if (rc != 0) throw std::runtime_error(std::string("ssa_aggregator_reset: ") + ssa_strerror(rc));

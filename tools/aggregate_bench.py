@@ -77,6 +77,10 @@ Every timed output is compared with the aggregates of the single call, batch by 
 pushes, then ssa_aggregator_finish_device against ssa_aggregate_many_sliced_device of --baseline-lib over the same
 signatures, legs alternating; the pushes' own times and ssa_aggregate_valid_many_device at --n are recorded beside it.
 
+--accumulator --remove measures removing lanes in place on an object of --n lanes: drop_front of
+half, of half plus one, and remove_device of a random half, against reset + unscreened pushes of the remaining half
+through the aggregator of --baseline-lib (accumulator_remove_main).
+
 --verifier measures the streaming aggregate verifier: the R's, keys and messages of --n honest
 signatures pushed in --pushes equal pushes, then ssa_aggverifier_finish_device against
 ssa_verify_aggregate_sliced_device of --baseline-lib over the same lanes, legs alternating; the pushes' own times, the
@@ -1153,6 +1157,167 @@ def accumulator_main(a):
     return 0 if res["mismatches"] == 0 else 1
 
 
+REMOVE_KERNELS = ("av_k_keep", "agx_k_first_changed", "agx_k_move", "ag_k_level", "ag_k_tree")
+
+
+class BaselineAggregator:
+    """the streaming aggregator of a build of the library given by its path, on a context of its own: reset, unscreened
+    ssa_aggregator_push_device, ssa_aggregator_finish_device"""
+
+    def __init__(self, path, capacity):
+        import ctypes as C
+        self.C, self.lib = C, C.CDLL(path)
+        vp, sz, i32, u32 = C.c_void_p, C.c_size_t, C.c_int, C.c_uint32
+        self.lib.ssa_ctx_create_ex.argtypes = [C.POINTER(vp), i32, vp, sz, u32, C.c_uint64]
+        self.lib.ssa_aggregator_create.argtypes = [vp, sz, sz, u32, C.POINTER(vp)]
+        self.lib.ssa_aggregator_reset.argtypes = [vp]
+        self.lib.ssa_aggregator_push_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, u32, vp,
+                                                        C.POINTER(C.c_uint64)]
+        self.lib.ssa_aggregator_finish_device.argtypes = [vp, vp, sz, vp]
+        self.lib.ssa_aggregator_destroy.argtypes = [vp]
+        self.lib.ssa_aggregator_destroy.restype = None
+        self.lib.ssa_ctx_sync.argtypes = [vp]
+        self.lib.ssa_ctx_destroy.argtypes = [vp]
+        self.lib.ssa_ctx_destroy.restype = None
+        self.ctx, self.ag = vp(), vp()
+        if self.lib.ssa_ctx_create_ex(C.byref(self.ctx), 0, None, 0, 0, 0) != 0:
+            raise RuntimeError("baseline library: ssa_ctx_create_ex failed")
+        if self.lib.ssa_aggregator_create(self.ctx, capacity, 0, 0, C.byref(self.ag)) != 0:
+            raise RuntimeError("baseline library: ssa_aggregator_create failed")
+
+    def repush(self, d_sigs, d_pks, d_msgs, per):
+        """reset, then the lanes of the three tensors in unscreened pushes of `per`"""
+        if self.lib.ssa_aggregator_reset(self.ag) != 0:
+            raise RuntimeError("baseline library: ssa_aggregator_reset failed")
+        kept, n = self.C.c_uint64(0), int(d_pks.shape[0])
+        for lo in range(0, n, per):
+            cnt = min(per, n - lo)
+            rc = self.lib.ssa_aggregator_push_device(self.ctx, self.ag, d_sigs[lo:].data_ptr(), d_pks[lo:].data_ptr(), None,
+                                                     d_msgs[lo:].data_ptr(), None, 80, 80, cnt, 1, None, self.C.byref(kept))
+            if rc != 0 or kept.value != cnt:
+                raise RuntimeError("baseline library: ssa_aggregator_push_device failed (%d)" % rc)
+
+    def finish(self, d_agg):
+        if self.lib.ssa_aggregator_finish_device(self.ctx, self.ag, (1 << 64) - 1, d_agg.data_ptr()) != 0:
+            raise RuntimeError("baseline library: ssa_aggregator_finish_device failed")
+
+    def sync(self):
+        self.lib.ssa_ctx_sync(self.ctx)
+
+    def close(self):
+        self.lib.ssa_aggregator_destroy(self.ag)
+        self.lib.ssa_ctx_destroy(self.ctx)
+
+
+def accumulator_remove_main(a):
+    """--accumulator --remove: removing lanes in place.  An object holds --n honest signatures
+    over 80-byte messages (device buffers); the legs alternate in one process, each timed call with a stream
+    synchronisation, an untimed call of the same kind in front of it, and the object reloaded before both:
+      drop_front_aligned   drop_front(n / 2): the tops are moved
+      drop_front_odd       drop_front(n / 2 + 1): every block is reduced again
+      remove_half          remove_device of a random half
+      baseline_repush      the cheapest route --baseline-lib (a build of the parent commit; without it, this tree's own
+                           library) has to the state of drop_front_aligned: reset, then unscreened push_device of the
+                           remaining n / 2 lanes in pushes of 2^16
+    After every timed call the object's finish is compared with the aggregate the baseline library's aggregator gives
+    the kept lanes.  The bar: each removal leg below baseline_repush by more than baseline_repush differs between two
+    processes."""
+    import torch
+    import schnorr_sig_amd as ssa
+    dev = torch.device("cuda", 0)
+    eng = ssa.Engine(0)
+    base_path = a.baseline_lib or ssa.LIB_PATH
+    n, per = a.n, 1 << 16
+    if n % (2 * per):
+        raise SystemExit("--accumulator --remove: --n must be a multiple of 2^17")
+    half = n // 2
+    base = BaselineAggregator(base_path, n)
+    rng = np.random.default_rng(a.seed)
+    msgs = rng.integers(0, 256, (n, 80), dtype=np.uint8)
+    pks, sigs = eng.keygen_sign_many(_scalars(rng, n), _scalars(rng, n), msgs)
+    t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)   # noqa: E731
+    d_sigs, d_pks, d_msgs = t(sigs), t(pks), t(msgs)
+    drop = np.zeros(n, np.uint8)
+    drop[rng.choice(n, half, replace=False)] = 1
+    d_drop, d_keep = t(drop), t(np.flatnonzero(drop == 0))
+    d_agg = torch.zeros(49 * n + 32, dtype=torch.uint8, device=dev)
+    sha = lambda path: hashlib.sha256(open(path, "rb").read()).hexdigest()[:16]   # noqa: E731
+    res = {"metric": "aggregator_remove", "n": n, "msg_len": 80, "rounds": a.rounds, "warmup": a.warmup,
+           "library_sha256": sha(ssa.LIB_PATH), "baseline_sha256": sha(base_path), "baseline_is_this_tree": not a.baseline_lib,
+           "device": torch.cuda.get_device_name(0), "date": time.strftime("%Y-%m-%d"), "mismatches": 0}
+    # the kept lanes of each leg, and the baseline library's aggregate of them handed to its aggregator alone
+    lanes = {"drop_front_aligned": (d_sigs[half:], d_pks[half:], d_msgs[half:]),
+             "drop_front_odd": (d_sigs[half + 1:], d_pks[half + 1:], d_msgs[half + 1:]),
+             "remove_half": (d_sigs[d_keep].contiguous(), d_pks[d_keep].contiguous(), d_msgs[d_keep].contiguous())}
+    want = {}
+    for leg, (s, p, m) in lanes.items():
+        base.repush(s, p, m, per)
+        want[leg] = torch.zeros(49 * int(p.shape[0]) + 32, dtype=torch.uint8, device=dev)
+        base.finish(want[leg])
+        base.sync()
+    want["baseline_repush"] = want["drop_front_aligned"]
+    ag = eng.aggregator(n)
+
+    def wall(fn, sync):
+        sync()
+        t0 = time.perf_counter()
+        fn()
+        sync()
+        return (time.perf_counter() - t0) * 1e3
+
+    def reload():
+        ag.reset()
+        for lo in range(0, n, per):
+            ag.push_device(d_sigs[lo:lo + per], d_pks[lo:lo + per], d_msgs[lo:lo + per], screen=False)
+        eng.sync()
+
+    calls = {"drop_front_aligned": lambda: ag.drop_front(half), "drop_front_odd": lambda: ag.drop_front(half + 1),
+             "remove_half": lambda: ag.remove_device(d_drop),
+             "baseline_repush": lambda: base.repush(*lanes["drop_front_aligned"], per)}
+    times = {leg: [] for leg in calls}
+    for rnd in range(a.warmup + a.rounds):
+        for leg, call in calls.items():
+            mine = leg != "baseline_repush"
+            sync = eng.sync if mine else base.sync
+            for timed_call in (False, True):
+                if mine:
+                    reload()
+                ms = wall(call, sync)
+            out = d_agg[:want[leg].numel()]
+            out.fill_(0xEE)
+            torch.cuda.synchronize()
+            if mine:
+                ag.finish_device(out, int((want[leg].numel() - 32) // 49))
+                eng.sync()
+            else:
+                base.finish(out)
+                base.sync()
+            res["mismatches"] += 0 if bool((out == want[leg]).all()) else 1
+            if rnd >= a.warmup:
+                times[leg].append(ms)
+    med = res["ms_median"] = {leg: round(float(np.median(v)), 3) for leg, v in times.items()}
+    res["ms_all"] = {leg: [round(x, 3) for x in v] for leg, v in times.items()}
+    res["ratio_to_baseline_repush"] = {leg: round(med[leg] / med["baseline_repush"], 4) for leg in calls}
+    kern = {}
+    for leg in ("drop_front_aligned", "drop_front_odd", "remove_half"):
+        reload()
+        eng.enable_timing(True)
+        calls[leg]()
+        eng.sync()
+        kern[leg] = {}
+        for kn in REMOVE_KERNELS:
+            avg, cnt = eng.read_timing(kn)
+            if cnt:
+                kern[leg][kn] = [round(avg, 4), int(cnt)]
+        eng.enable_timing(False)
+    res["kernel_ms_avg_launches"] = kern
+    print(json.dumps(res))
+    ag.close()
+    eng.close()
+    base.close()
+    return 0 if res["mismatches"] == 0 else 1
+
+
 VERIFIER_KERNELS = ("ag_k_expand", "ssa_k_hash", "agv_k_append", "ag_k_level", "ag_k_tree", "agv_k_scalars", "msm_sort",
                     "msm_k_buckets", "msm_reduce", "msm_k_sum_records", "ag_k_finish")
 
@@ -1628,11 +1793,14 @@ def main():
     ap.add_argument("--rotate-legs", action="store_true",
                     help="--verifier --cached: a diagnostic -- swap each leg with its counterpart every other round and "
                          "record the times by place as well")
+    ap.add_argument("--remove", action="store_true",
+                    help="--accumulator: drop_front and remove_device on an object of --n lanes (DESIGN.md section 30) "
+                         "against reset + unscreened pushes of the remaining half through --baseline-lib")
     a = ap.parse_args()
     if a.verifier:
         return verifier_cached_main(a) if a.cached else verifier_main(a)
     if a.accumulator:
-        return accumulator_main(a)
+        return accumulator_remove_main(a) if a.remove else accumulator_main(a)
     if a.produce_many:
         return produce_many_main(a)
     if a.sharded:
