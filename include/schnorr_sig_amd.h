@@ -1205,8 +1205,8 @@ int ssa_aggregate_valid_keyed_many_cached_device(ssa_ctx *ctx, ssa_keycache *kc,
  * that the challenge hash, the admission check, the leaves and most of the tree are paid on arrival, and block time pays
  * one permutation, one multiplication and a sum per lane.  It belongs to the context it was created on, like a key cache.
  *   create   capacity: 1 .. SSA_MAX_BATCH lanes; block_lanes: 0 (the default, 512) or a power of two from 2 to 512 (small
- *            values let tests reach every path of the tree at a few thousand lanes); flags: 0.  Anything else:
- *            SSA_ERR_ARG.  All device memory is allocated here -- 49 capacity + 32 bytes of R's, 32 bytes of scalar and 32
+ *            values let tests reach every path of the tree at a few thousand lanes); flags: 0 or
+ *            SSA_AGGR_HOLD_KEYS49 (below).  Anything else: SSA_ERR_ARG.  All device memory is allocated here -- 49 capacity + 32 bytes of R's, 32 bytes of scalar and 32
  *            bytes of leaf per lane, 32 bytes per block: about 113 bytes per lane -- and is the object's own: destroy
  *            releases it, or ssa_ctx_destroy (the handle then stays valid for destroy and is refused everywhere else).
  *   push     the arguments of ssa_aggregate_valid_many.  Let S be the status vector: with flags == 0 the one
@@ -1247,10 +1247,41 @@ int ssa_aggregate_valid_keyed_many_cached_device(ssa_ctx *ctx, ssa_keycache *kc,
  *            an orphaned object, a NULL mask with lanes held, a NULL n_kept_out, the length and range errors above.
  *            A move in place cannot be undone: a runtime error (SSA_ERR_HIP) once the move has begun leaves the object
  *            EMPTY (0 lanes held, counters as they were), never half-moved.
- * NOT here: reordering held lanes, finishing an arbitrary subset without removing it, admission through a key cache,
- * ssa_multi forms.  The validator's counterpart is ssa_aggverifier, below. */
+ *   push_cached, push_keyed_cached   admission through a key cache, under the verdict validators apply (DESIGN.md
+ *            section 31).  push_cached takes the lanes of push and an AFFINE cache, push_keyed_cached n 130-byte
+ *            KeyedSignature records (key 49 || signature 81) and a WIRE cache.  Two equalities, in every state of the
+ *            cache (cold, warm, partly warm, cleared or compacted between two slices of the push, bypassed):
+ *            the admission -- status_out (may be NULL), the 12 words of stats_out (HOST memory, may be NULL) and the state
+ *            of the cache afterwards are exactly those ssa_aggregate_valid_many_cached (for records:
+ *            ssa_aggregate_valid_keyed_many_cached) gives THIS batch alone on the same cache: SSA_FLAG_CHECK_TORSION |
+ *            SSA_FLAG_SIG_FLAG_BYTE, library-drawn coefficients, the cache used exactly where that call uses it (not for
+ *            a push, or a last slice, of at most the context's small-batch bound), and the key deciding over a bad
+ *            signature in the same lane;
+ *            the object -- the lanes of status 0 are appended in lane order, and every later finish(n_take) is byte for
+ *            byte ssa_aggregate_many (flags 0) on the first n_take admitted lanes handed in alone (records: split into
+ *            signatures and decompressed keys), whichever kind of push admitted each lane: plain, cached and keyed pushes
+ *            may be mixed in one object, the stored R, scalar and leaf do not depend on how a lane came in.
+ *            Everything else follows push: every message is hashed ONCE; a push is refused by n; n == 0 counts a push
+ *            and touches neither cache nor object; *n_kept_out is HOST memory in both forms; the return value reports
+ *            errors only.  SSA_ERR_ARG, with object and cache untouched: a NULL cache, a cache of the other mode, of
+ *            another context or orphaned, and everything push refuses.  The _device forms synchronise as
+ *            ssa_aggregate_valid_many_cached_device does.
+ *   SSA_AGGR_HOLD_KEYS49 (create flag)   the object also holds the 49 wire bytes of every admitted lane's key, in arrival
+ *            order: 49 more bytes per lane, about 162 in all.  Such an object takes push_keyed_cached ONLY -- the other
+ *            pushes carry no wire key: SSA_ERR_ARG, the object unchanged.  keys(n_take) writes the first n_take held
+ *            lanes' keys, 49 n_take bytes -- the first 49 bytes of each lane's record, verbatim -- by the conventions of
+ *            finish: SIZE_MAX = all lanes held, n_take > held is SSA_ERR_ARG, n_take == 0 writes nothing, the _device form
+ *            only enqueues, no state of the object changes.  On an object created without the flag: SSA_ERR_ARG.
+ *            drop_front, remove and reset treat the key column as they treat the R's: after a removal the object is
+ *            indistinguishable, keys included, from one that admitted the kept lanes alone.  The outputs of finish and
+ *            keys, unchanged, with the kept messages, k = 1 and counts = {n}, are what
+ *            ssa_verify_aggregates_many_cached_wire takes; on the same cache that call finds every key (stats[2] == 0)
+ *            unless the push bypassed the cache or did not use it.
+ * NOT here: reordering held lanes, finishing an arbitrary subset without removing it, a column of affine keys, the
+ * messages, ssa_multi forms.  The validator's counterpart is ssa_aggverifier, below. */
 typedef struct ssa_aggregator ssa_aggregator;
 #define SSA_AGGR_NO_SCREEN 1u      /* push flag */
+#define SSA_AGGR_HOLD_KEYS49 2u    /* create flag */
 int ssa_aggregator_create(ssa_ctx *ctx, size_t capacity, size_t block_lanes, uint32_t flags, ssa_aggregator **out);
 void ssa_aggregator_destroy(ssa_aggregator *ag);
 int ssa_aggregator_reset(ssa_aggregator *ag);
@@ -1261,8 +1292,28 @@ int ssa_aggregator_push(ssa_ctx *ctx, ssa_aggregator *ag, const uint8_t *sigs, c
 int ssa_aggregator_push_device(ssa_ctx *ctx, ssa_aggregator *ag, const uint8_t *d_sigs, const uint8_t *d_pks,
                                const uint8_t *d_pk_inf, const uint8_t *d_msgs, const uint64_t *d_msg_off, size_t msg_stride,
                                size_t msg_len, size_t n, uint32_t flags, uint8_t *d_status_out, uint64_t *n_kept_out);
+int ssa_aggregator_push_cached(ssa_ctx *ctx, ssa_aggregator *ag, ssa_keycache *kc, const uint8_t *sigs, const uint8_t *pks,
+                               const uint8_t *pk_inf, const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride,
+                               size_t msg_len, size_t n, uint8_t *status_out, uint64_t *n_kept_out, uint64_t stats_out[12]);
+int ssa_aggregator_push_cached_device(ssa_ctx *ctx, ssa_aggregator *ag, ssa_keycache *kc, const uint8_t *d_sigs,
+                                      const uint8_t *d_pks, const uint8_t *d_pk_inf, const uint8_t *d_msgs,
+                                      const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len, size_t n,
+                                      uint8_t *d_status_out, uint64_t *n_kept_out, uint64_t stats_out[12]);
+int ssa_aggregator_push_keyed_cached(ssa_ctx *ctx, ssa_aggregator *ag, ssa_keycache *kc, const uint8_t *keyed,
+                                     const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len,
+                                     size_t n, uint8_t *status_out, uint64_t *n_kept_out, uint64_t stats_out[12]);
+int ssa_aggregator_push_keyed_cached_device(ssa_ctx *ctx, ssa_aggregator *ag, ssa_keycache *kc, const uint8_t *d_keyed,
+                                            const uint8_t *d_msgs, const uint64_t *d_msg_off, size_t msg_stride,
+                                            size_t msg_len, size_t n, uint8_t *d_status_out, uint64_t *n_kept_out,
+                                            uint64_t stats_out[12]);
 int ssa_aggregator_finish(ssa_ctx *ctx, ssa_aggregator *ag, size_t n_take, uint8_t *agg_out);
 int ssa_aggregator_finish_device(ssa_ctx *ctx, ssa_aggregator *ag, size_t n_take, uint8_t *d_agg_out);
+int ssa_aggregator_keys(ssa_ctx *ctx, ssa_aggregator *ag, size_t n_take, uint8_t *keys49_out);
+int ssa_aggregator_keys_device(ssa_ctx *ctx, ssa_aggregator *ag, size_t n_take, uint8_t *d_keys49_out);
+/* tests: the bytes create allocates for an object of this capacity, block size and flags (host code, no device):
+ * out[0] the R's, [1] the scalars, [2] the leaves, [3] the tops, [4] the key column (0 without SSA_AGGR_HOLD_KEYS49).
+ * SSA_ERR_ARG for anything create would refuse. */
+int ssa_debug_aggregator_bytes(size_t capacity, size_t block_lanes, uint32_t flags, uint64_t out[5]);
 /* tests: what a push of m kept lanes onto `held` lanes completes with blocks of block_lanes (0: 512) lanes (host code, no
  * device): out[0] the first completed block, out[1] the number of completed blocks, out[2] the first lane of the ragged
  * tail, out[3] its length.  SSA_ERR_ARG for a block size create would refuse or held + m above SSA_MAX_BATCH. */

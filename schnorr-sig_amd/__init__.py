@@ -300,6 +300,13 @@ def _load():
         "ssa_aggregator_push_device": (i32, [vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, u32, vp, u64p]),
         "ssa_aggregator_finish": (i32, [vp, vp, sz, vp]),
         "ssa_aggregator_finish_device": (i32, [vp, vp, sz, vp]),
+        "ssa_aggregator_push_cached": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, vp, u64p, vp]),
+        "ssa_aggregator_push_cached_device": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, vp, u64p, vp]),
+        "ssa_aggregator_push_keyed_cached": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz, vp, u64p, vp]),
+        "ssa_aggregator_push_keyed_cached_device": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz, vp, u64p, vp]),
+        "ssa_aggregator_keys": (i32, [vp, vp, sz, vp]),
+        "ssa_aggregator_keys_device": (i32, [vp, vp, sz, vp]),
+        "ssa_debug_aggregator_bytes": (i32, [sz, sz, u32, u64p]),
         "ssa_debug_aggregator_plan": (i32, [C.c_uint64, C.c_uint64, C.c_uint64, u64p]),
         "ssa_aggregator_drop_front": (i32, [vp, vp, sz]),
         "ssa_aggregator_remove": (i32, [vp, vp, vp, sz, u64p]),
@@ -619,14 +626,16 @@ class Engine:
                 raise
         return cache
 
-    def aggregator(self, capacity, block_lanes=0):
+    def aggregator(self, capacity, block_lanes=0, hold_keys=False):
         """a streaming aggregator of `capacity` lanes on this engine's device: push signatures
         as they arrive, finish at block time.  All of its device memory, about 113 bytes per lane, is allocated here.
-        block_lanes: 0 (512) or a power of two from 2 to 512."""
+        block_lanes: 0 (512) or a power of two from 2 to 512.
+        hold_keys=True (SSA_AGGR_HOLD_KEYS49): the object also holds every admitted lane's 49-byte
+        wire key (49 more bytes per lane) for Aggregator.keys(); it then takes push_keyed alone."""
         h = C.c_void_p()
-        _check(_lib.ssa_aggregator_create(self._ctx, int(capacity), int(block_lanes), 0, C.byref(h)),
-               "ssa_aggregator_create")
-        return Aggregator(self, h)
+        _check(_lib.ssa_aggregator_create(self._ctx, int(capacity), int(block_lanes), AGGR_HOLD_KEYS49 if hold_keys else 0,
+                                          C.byref(h)), "ssa_aggregator_create")
+        return Aggregator(self, h, hold_keys=hold_keys)
 
     def aggregate_verifier(self, capacity, block_lanes=0):
         """a streaming aggregate verifier of `capacity` lanes on this engine's device: push the
@@ -1801,6 +1810,7 @@ class KeyCache(_Handle, _KeyTables):
 
 
 AGGR_NO_SCREEN = 1    # SSA_AGGR_NO_SCREEN
+AGGR_HOLD_KEYS49 = 2  # SSA_AGGR_HOLD_KEYS49
 AGGREGATOR_FIELDS = ("held", "capacity", "block_lanes", "pushes", "offered", "dropped", "blocks", "finishes")
 AGGVERIFIER_FIELDS = ("held", "capacity", "block_lanes", "pushes", "pushed", "reserved", "blocks", "finishes")
 #   ("reserved" is word [5] of ssa_aggverifier_info: since section 29 the lanes pushed through a key cache, 0 for an
@@ -1818,6 +1828,15 @@ def aggregator_plan(held, m, block_lanes=0):
     lanes onto `held` lanes (ssa_debug_aggregator_plan: host code, no device)"""
     out = (C.c_uint64 * 4)()
     _check(_lib.ssa_debug_aggregator_plan(int(held), int(m), int(block_lanes), out), "ssa_debug_aggregator_plan")
+    return tuple(int(v) for v in out)
+
+
+def aggregator_bytes(capacity, block_lanes=0, hold_keys=False):
+    """tests: the bytes Engine.aggregator allocates -- (R's, scalars, leaves, tops, key column), the last 0 without
+    hold_keys (ssa_debug_aggregator_bytes: host code, no device)"""
+    out = (C.c_uint64 * 5)()
+    _check(_lib.ssa_debug_aggregator_bytes(int(capacity), int(block_lanes), AGGR_HOLD_KEYS49 if hold_keys else 0, out),
+           "ssa_debug_aggregator_bytes")
     return tuple(int(v) for v in out)
 
 
@@ -1859,23 +1878,105 @@ class Aggregator(_LaneStore):
     """ssa_aggregator handle (Engine.aggregator): the lanes admitted so far, on the device, in
     arrival order.  push() admits a batch on arrival; finish() gives the AggregateSignature of the first n_take held
     lanes -- what Engine.aggregate gives those lanes handed in alone -- and changes nothing; drop_front(), remove() and
-    take() remove lanes in place and keep the rest of the pool.  Tied to its Engine like
-    KeyCache; destroyed exactly once (close(), the end of a `with` block, or when the object goes away)."""
+    take() remove lanes in place and keep the rest of the pool; push(cache=) and push_keyed()
+    admit through a key cache, and an object made with hold_keys=True keeps the admitted lanes' wire keys for keys() and
+    take_block().  Tied to its Engine like KeyCache; destroyed exactly once (close(), the end of
+    a `with` block, or when the object goes away)."""
     _prefix, _fields = "aggregator", AGGREGATOR_FIELDS
 
-    def push(self, sigs, pks, msgs, pk_inf=None, screen=True, offsets=None, engine=None):
+    def __init__(self, engine, handle, hold_keys=False):
+        super().__init__(engine, handle)
+        self.hold_keys = bool(hold_keys)
+
+    def push(self, sigs, pks, msgs, pk_inf=None, screen=True, offsets=None, engine=None, cache=None):
         """a batch of signatures, keys and messages as Engine.aggregate_valid takes them -> (status uint8[n], n_kept):
         the lanes whose status is zero are appended in lane order.  screen=True: the statuses of
         Engine.verify_batch_screened on this batch alone; screen=False (SSA_AGGR_NO_SCREEN): 0 or MALFORMED by the checks
         of Engine.aggregate(check=False), for a producer that made the signatures itself.  A batch that does not fit
-        what is left of the capacity raises and changes nothing.  engine: tests (a context other than the object's)."""
+        what is left of the capacity raises and changes nothing.  engine: tests (a context other than the object's).
+        cache: an AFFINE KeyCache -- the statuses, and the stats, of
+        Engine.aggregate_valid_cached on this batch alone and the same cache: a lane whose key lies outside the subgroup
+        is dropped with INVALID_PUBLIC_KEY.  Then returns (status, n_kept, stats uint64[12])."""
         eng = engine or self.engine
         n, batch, keep = eng._agg_batch(sigs, 81, pks, msgs, offsets, pk_inf)
         status = np.full(n, 255, dtype=np.uint8)
         n_kept = C.c_uint64(0)
+        if cache is not None:
+            if screen is not True:
+                raise ValueError("a cached push always screens")
+            stats = np.zeros(12, dtype=np.uint64)
+            _check(_lib.ssa_aggregator_push_cached(eng._ctx, self.handle, cache.handle, *batch, _ptr(status) if n else None,
+                                                   C.byref(n_kept), stats.ctypes.data), "ssa_aggregator_push_cached")
+            return status, int(n_kept.value), stats
         _check(_lib.ssa_aggregator_push(eng._ctx, self.handle, *batch, 0 if screen else AGGR_NO_SCREEN,
                                         _ptr(status) if n else None, C.byref(n_kept)), "ssa_aggregator_push")
         return status, int(n_kept.value)
+
+    def push_keyed(self, cache, keyed, msgs, offsets=None, engine=None):
+        """n 130-byte KeyedSignature records pk(49) || sig(81) through a key cache made with wire=True (DESIGN.md
+        section 31) -> (status uint8[n], n_kept, stats uint64[12]): status and stats are those of
+        Engine.aggregate_valid_keyed_cached on this batch alone and the same cache; the lanes of status zero are appended
+        in lane order, and an object made with hold_keys=True keeps their 49 key bytes.  cache=None raises as the
+        library refuses it.  engine: tests."""
+        eng = engine or self.engine
+        kd = _np_u8(keyed, 130)
+        n = kd.shape[0]
+        m_, off, stride, mlen = eng._msg_args(msgs, offsets, n) if n else (None, None, 0, 0)
+        status = np.full(n, 255, dtype=np.uint8)
+        stats = np.zeros(12, dtype=np.uint64)
+        n_kept = C.c_uint64(0)
+        _check(_lib.ssa_aggregator_push_keyed_cached(
+            eng._ctx, self.handle, None if cache is None else cache.handle, _ptr(kd) if n else None, _ptr(m_), _ptr(off),
+            stride, mlen, n, _ptr(status) if n else None, C.byref(n_kept), stats.ctypes.data),
+            "ssa_aggregator_push_keyed_cached")
+        return status, int(n_kept.value), stats
+
+    def push_cached_device(self, cache, d_sigs, d_pks, d_msgs, d_status=None, d_pk_inf=None, d_offsets=None, msg_len=None,
+                           msg_stride=None, want_stats=True):
+        """device form of push(cache=) over torch tensors on the engine's device, shaped as push_device takes them.
+        Synchronises the stream as Engine.aggregate_valid_cached_device does -> (n_kept, stats uint64[12] or None)."""
+        n = int(d_pks.shape[0])
+        stride, mlen = _dev_msg_shape(d_msgs, d_offsets, msg_len, msg_stride)
+        n_kept = C.c_uint64(0)
+        stats = np.zeros(12, dtype=np.uint64) if want_stats else None
+        _check(_lib.ssa_aggregator_push_cached_device(
+            self.engine._ctx, self.handle, cache.handle, _addr(d_sigs), _addr(d_pks), _addr(d_pk_inf), _addr(d_msgs),
+            _addr(d_offsets), stride, mlen, n, _addr(d_status), C.byref(n_kept), stats.ctypes.data if want_stats else None),
+            "ssa_aggregator_push_cached_device")
+        return int(n_kept.value), stats
+
+    def push_keyed_device(self, cache, d_keyed, d_msgs, d_status=None, d_offsets=None, msg_len=None, msg_stride=None,
+                          want_stats=True):
+        """device form of push_keyed: d_keyed an (n, 130) uint8 tensor on the engine's device -> (n_kept, stats uint64[12]
+        or None).  Synchronises as push_cached_device."""
+        n = int(d_keyed.shape[0])
+        stride, mlen = _dev_msg_shape(d_msgs, d_offsets, msg_len, msg_stride)
+        n_kept = C.c_uint64(0)
+        stats = np.zeros(12, dtype=np.uint64) if want_stats else None
+        _check(_lib.ssa_aggregator_push_keyed_cached_device(
+            self.engine._ctx, self.handle, cache.handle, _addr(d_keyed), _addr(d_msgs), _addr(d_offsets), stride, mlen, n,
+            _addr(d_status), C.byref(n_kept), stats.ctypes.data if want_stats else None),
+            "ssa_aggregator_push_keyed_cached_device")
+        return int(n_kept.value), stats
+
+    def keys(self, n_take=None):
+        """the 49-byte wire keys of the first n_take held lanes (None: all) as uint8[n, 49], in arrival order: the first
+        49 bytes of each admitted record, verbatim.  Changes no state.  An object made without hold_keys raises."""
+        held = self.info()["held"]
+        n = held if n_take is None else int(n_take)
+        out = np.full((max(min(n, held), 1), 49), 255, dtype=np.uint8)
+        _check(_lib.ssa_aggregator_keys(self.engine._ctx, self.handle, _n_take(n_take), _ptr(out)), "ssa_aggregator_keys")
+        return out[:min(n, held)].copy()
+
+    def keys_device(self, d_keys49, n_take=None):
+        """device form: only enqueues on the engine's stream; the 49 n bytes land in the uint8 tensor d_keys49 (any byte
+        alignment), n = n_take or all lanes held.  Returns n."""
+        n = self.info()["held"] if n_take is None else int(n_take)
+        if d_keys49.numel() < 49 * n:
+            raise ValueError("the keys of %d lanes are %d bytes" % (n, 49 * n))
+        _check(_lib.ssa_aggregator_keys_device(self.engine._ctx, self.handle, n, d_keys49.data_ptr()),
+               "ssa_aggregator_keys_device")
+        return n
 
     def push_device(self, d_sigs, d_pks, d_msgs, d_status=None, d_pk_inf=None, d_offsets=None, msg_len=None,
                     msg_stride=None, screen=True):
@@ -1947,6 +2048,14 @@ class Aggregator(_LaneStore):
         agg = self.finish(n)
         self.drop_front(n)
         return agg
+
+    def take_block(self, n_take=None):
+        """take() of an object made with hold_keys=True -> (AggregateSignature, keys uint8[n, 49]): the aggregate and the
+        key column of the block body; the lanes leave the object, the rest stays for the next block"""
+        n = self.info()["held"] if n_take is None else int(n_take)
+        agg, keys = self.finish(n), self.keys(n)
+        self.drop_front(n)
+        return agg, keys
 
 
 class AggregateVerifier(_LaneStore):

@@ -201,13 +201,13 @@ ag_k_pack(const u8 *__restrict__ sigs, size_t n, u8 *__restrict__ agg_out) {
     }
 }
 
-// leaf_i = H(d_i || flag byte of R_i || 0xA1): dig the raw digests (four words per lane), sigs the lanes at stride 81
-SSA_DEV void ag_leaf_hash(u64 *A, const DevParams *__restrict__ prm, const u64 *__restrict__ dig, const u8 *__restrict__ sigs,
-                          size_t i, u64 (&d)[4]) {
+// leaf_i = H(d_i || flag byte of R_i || 0xA1): dig the raw digests (four words per lane), flag the lane's byte 48
+SSA_DEV void ag_leaf_hash(u64 *A, const DevParams *__restrict__ prm, const u64 *__restrict__ dig, size_t i, u8 flag,
+                          u64 (&d)[4]) {
     u64 in[8];
 #pragma unroll
     for (int k = 0; k < 4; k++) in[k] = dig[4 * i + k];
-    in[4] = (u64)sigs[81 * i + 48];
+    in[4] = (u64)flag;
     in[5] = AG_TAG_LEAF;
     in[6] = in[7] = 0;
     ag_hash8(A, prm, in, 6u, d);
@@ -221,7 +221,7 @@ ag_k_leaf(const DevParams *__restrict__ prm, const u64 *__restrict__ dig, const 
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     u64 d[4];
-    ag_leaf_hash(A, prm, dig, sigs, i, d);
+    ag_leaf_hash(A, prm, dig, i, sigs[81 * i + 48], d);
 #pragma unroll
     for (int k = 0; k < 4; k++) nodes[4 * i + k] = d[k];
 }

@@ -8,8 +8,11 @@
 //   scal    four words per lane: e_i, canonical (every kept lane has e_i < q by either admission check)
 //   leaves  four words per lane: leaf_i
 //   tops    four words per COMPLETE block of B lanes: the top of its subtree
+//   keys    49 bytes per lane, only in an object created with SSA_AGGR_HOLD_KEYS49: the wire key of
+//           the lane's KeyedSignature record, verbatim -- the key column of the block body next to the aggregate
 //
-//   push    status vector (the screen of ssa_verify_batch_screened, or the checks of ag_k_fold) -> av_keep lists the kept
+//   push    status vector (the screen of ssa_verify_batch_screened, the checks of ag_k_fold, or -- the cached pushes,
+//           section 31 -- the statuses of ssa_verify_many_cached / ssa_verify_keyed_many_cached) -> av_keep lists the kept
 //           lanes -> agx_k_append stores leaf, scalar and R of each -> the blocks this push completed are reduced to
 //           their tops: ag_k_tree over that range of the leaves for B = 512, log2 B launches of ag_k_level for smaller B
 //   finish  for the first n held lanes: the stored tops of the n / B complete blocks are copied into a workspace of the
@@ -21,7 +24,7 @@
 //           workspaces of the context (agx_k_move, below), and agx_remove_plan says which tops stay, move or are reduced
 //           again.  No message, key or signature is touched.
 //
-// The object's four arrays are its own allocations (released by destroy, or by the context's clean-up): they are not in
+// The object's four (with the key column: five) arrays are its own allocations (released by destroy, or by the context's clean-up): they are not in
 // the context's list of workspaces, and nothing the object needs between two calls lives in one.
 #pragma once
 #include "ssa_aggregate.hpp"
@@ -32,6 +35,7 @@
 struct AgxStore {
     ssa_ctx *ctx = nullptr;   // nullptr: the context is gone, the device memory went with it
     size_t capacity = 0, block = 0, held = 0;     // block: B, a power of two from 2 to AG_TREE_SPAN
+    uint32_t flags = 0;                           // the create flags (each type says which it knows: kCreateFlags)
     uint64_t pushes = 0, finishes = 0;
     DevBuf leaves, tops;
     // a buffer of the object and the bytes it takes at the object's capacity and B
@@ -43,12 +47,18 @@ struct AgxStore {
 };
 
 struct ssa_aggregator : AgxStore {
+    static constexpr uint32_t kCreateFlags = SSA_AGGR_HOLD_KEYS49;
     uint64_t offered = 0, dropped = 0;
-    DevBuf wire, scal;
+    DevBuf wire, scal, keys;
+    bool hold_keys() const { return (flags & SSA_AGGR_HOLD_KEYS49) != 0; }
 };
-// everything the object will ever hold, in the order it is allocated and released
+// everything the object will ever hold, in the order it is allocated and released (the key column: only with the flag,
+// 49 bytes per lane and the rest of the last dword -- agx_k_move reads whole aligned dwords)
 static inline std::vector<AgxStore::Buf> agx_bufs(ssa_aggregator &a) {
-    return {{&a.wire, 49 * a.capacity + 32}, {&a.scal, 32 * a.capacity}, {&a.leaves, 32 * a.capacity}, {&a.tops, 32 * a.n_tops()}};
+    std::vector<AgxStore::Buf> bufs{
+        {&a.wire, 49 * a.capacity + 32}, {&a.scal, 32 * a.capacity}, {&a.leaves, 32 * a.capacity}, {&a.tops, 32 * a.n_tops()}};
+    if (a.hold_keys()) bufs.push_back({&a.keys, 49 * a.capacity + 3});
+    return bufs;
 }
 template <class T>
 static inline void agx_release_all(T &obj) {
@@ -97,77 +107,16 @@ agx_k_check(const u8 *__restrict__ sigs, const u8 *__restrict__ pks, const u8 *_
     status[i] = (u8)(ag_lane_ok(sigs, pks, pk_inf, i, true, e) ? ST_OK : ST_MALFORMED);
 }
 
-// One lane per kept lane: rank c, source lane kept[c] of the push, place held + c of the aggregate.
-//   leaves[held + c] = H(d || flag byte of R || 0xA1) from the lane's raw digest (the body of ag_k_leaf);
-//   scal[held + c]   = e as four words;
-//   wire[49 (held + c), + 49) = R.
-// The R's of a push land on bytes [D0, D1) = [49 held, 49 (held + m)) of `wire` (the object's own allocation: wire itself
-// is dword-aligned), which start and end anywhere mod 4.  A dword belongs to the lane its FIRST byte lies in, so lane c
-// writes the aligned dwords that start in [49 (held + c), 49 (held + c + 1)) -- the last of them may run into lane c + 1's
-// R and takes those bytes from kept[c + 1] -- as dwords while they end within D1.  The two edges are bytes: lane 0 writes
-// [D0, the first aligned address), the last lane what is left behind the last whole dword.  So no two threads write one
-// dword, and no byte in front of D0 -- the R's of earlier pushes -- is written.
-__global__ void __launch_bounds__(256, 4)
-agx_k_append(const DevParams *__restrict__ prm, const u8 *__restrict__ sigs, const u64 *__restrict__ dig,
-             const u32 *__restrict__ kept, size_t m, size_t held, u64 *__restrict__ leaves, u64 *__restrict__ scal,
-             u8 *__restrict__ wire) {
-    __shared__ u64 lds[RS_LDS_U64];
-    u64 *A = lds + threadIdx.x;
-    const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= m) return;
-    const size_t src = kept[c], dst = held + c;
-    const u8 *sig = sigs + 81 * src;
-    u64 d[4];
-    ag_leaf_hash(A, prm, dig, sigs, src, d);
-    const sc256 e = ld_sc(sig + 49);
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        leaves[4 * dst + k] = d[k];
-        scal[4 * dst + k] = e.w[k];
-    }
-    const size_t lo = 49 * dst, hi = lo + 49, end = 49 * (held + m);
-    size_t w = (lo + 3) & ~(size_t)3;
-    if (c == 0)
-        for (size_t b = lo; b < w && b < end; b++) wire[b] = sig[b - lo];
-    const u8 *next = c + 1 < m ? sigs + 81 * (size_t)kept[c + 1] : sig;     // (read only where c + 1 < m)
-    for (; w < hi; w += 4) {
-        if (w + 4 <= end) {
-            u32 v = 0;
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const size_t b = w + k;
-                v |= (u32)(b < hi ? sig[b - lo] : next[b - hi]) << (8 * k);
-            }
-            *reinterpret_cast<u32 *>(wire + w) = v;
-        } else {                                      // (the last lane alone: for every other one end >= hi + 49)
-            for (size_t b = w; b < end; b++) wire[b] = sig[b - lo];
-        }
-    }
-}
-
-// Removing lanes (ssa_aggregator_drop_front, _remove; DESIGN.md section 30).  The kept lanes, ascending, take the places
-// 0, 1, 2, ...: kept lane c comes from place src(c) = kept[c] (a mask; the list of av_keep) or c + shift (a front drop:
-// kept == nullptr, no list exists), and src(c) >= c, src ascending.  What a lane stores does not depend on its place, so
-// the lane is MOVED: four words of leaves, four of scal, 49 bytes of wire.
-//
-// The hazard.  The move is in place, and the threads of a launch run in no order: with one lane dropped at the front
-// every thread's source is its neighbour's destination.  So no launch writes the object.  The host walks the kept
-// lanes in ascending pieces [c0, c1) of at most the context's MSM slice, and for each piece
-//   1. agx_k_move gathers the piece -- reads the object at src(c), writes STAGING (workspaces of the context) at c - c0;
-//   2. three stream-ordered device-to-device copies put the staging back on places [c0, c1);
-//   3. only then is the next piece enqueued, on the same stream.
-// Why that is right: (a) a piece's own sources were all read by step 1 before step 2 began (stream order), so step 2
-// may overwrite them; (b) every later piece reads places src(c) >= c >= c1, and step 2 wrote [c0, c1) alone, so no
-// later source has been overwritten; (c) earlier pieces wrote places < c0 <= src(c) only.  Every lane is therefore read
-// as it was before the call.  The walk starts at the first place whose content changes: nothing in front of it is
-// written, not even with its own value.
-//
-// The 49-byte stride.  The staging of a piece starts dword-aligned, so lane t owns the aligned dwords that START in
-// [49 t, 49 (t + 1)) of it -- the rule of agx_k_append: the last of them may run into lane t + 1's R and takes those
-// bytes from src(c + 1) -- written as dwords while they end within the piece's 49 cnt bytes; the last lane writes what
-// is left behind the last whole dword as bytes.  No two threads write one dword.  The source 49 src(c) starts anywhere
-// mod 4: ld_u32_any reads the one or two aligned dwords a misaligned one lies in (never past the dword that holds its
-// last byte, so never outside `wire`).  The copy back lands at byte 49 c0 of wire, any alignment.
+// The 49-byte columns (the R's in `wire`, the wire keys in `keys`) and the one rule by which they are written, here and
+// in the staging of agx_k_move.  The lanes of a launch land on bytes [d0, d1) of `dst` -- a dword-aligned array; d0 and
+// d1 are multiples of 49 and start and end anywhere mod 4 -- the lane at place p on [49 p, 49 (p + 1)).  A dword belongs
+// to the lane its FIRST byte lies in, so a lane writes the aligned dwords that start in [49 p, 49 (p + 1)) -- the last of
+// them may run into the next lane's bytes and takes those from `next`, the NEXT lane's source (read only where there is
+// one: the dword ends within d1) -- as dwords while they end within d1.  The two edges are bytes: the first lane
+// (49 p == d0) writes [d0, the first aligned address), the last lane what is left behind the last whole dword.  So no
+// two threads write one dword, and no byte in front of d0 -- the lanes of earlier pushes -- or behind d1 is written.
+// ANY: src lies in device memory at any alignment and the dwords inside the lane are read with ld_u32_any (agx_k_move);
+// otherwise they are put together from bytes (agx_k_append, whose source is the caller's batch).
 static __device__ __forceinline__ u32 ld_u32_any(const u8 *p) {
     const uintptr_t a = (uintptr_t)p;
     const u32 *q = reinterpret_cast<const u32 *>(a & ~(uintptr_t)3);
@@ -176,10 +125,90 @@ static __device__ __forceinline__ u32 ld_u32_any(const u8 *p) {
     return sh ? (lo >> sh) | (q[1] << (32u - sh)) : lo;
 }
 
+template <bool ANY>
+static __device__ __forceinline__ void agx_put49(u8 *__restrict__ dst, size_t d0, size_t d1, size_t place,
+                                                 const u8 *__restrict__ src, const u8 *__restrict__ next) {
+    const size_t lo = 49 * place, hi = lo + 49;
+    size_t w = (lo + 3) & ~(size_t)3;
+    if (lo == d0)
+        for (size_t b = lo; b < w && b < d1; b++) dst[b] = src[b - lo];
+    for (; w < hi; w += 4) {
+        if (ANY && w + 4 <= hi) {
+            *reinterpret_cast<u32 *>(dst + w) = ld_u32_any(src + (w - lo));
+        } else if (w + 4 <= d1) {                     // (ANY: the dword shared with the next lane)
+            u32 v = 0;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const size_t b = w + k;
+                v |= (u32)(b < hi ? src[b - lo] : next[b - hi]) << (8 * k);
+            }
+            *reinterpret_cast<u32 *>(dst + w) = v;
+        } else {                                      // (the last lane alone: for every other one d1 >= hi + 49)
+            for (size_t b = w; b < d1; b++) dst[b] = src[b - lo];
+        }
+    }
+}
+
+// One lane per kept lane: rank c, source lane kept[c] of the push, place held + c of the aggregate.  The lanes are
+// records of `stride` bytes with the signature at `off`: 81 / 0 for signatures, 130 / 49 for KeyedSignature records (the
+// idiom of av_finish_kept).
+//   leaves[held + c] = H(d || flag byte of R || 0xA1) from the lane's raw digest (the body of ag_k_leaf);
+//   scal[held + c]   = e as four words;
+//   wire[49 (held + c), + 49) = R;
+//   keys[49 (held + c), + 49) = the first 49 bytes of the record, when the object has a key column (keys != nullptr;
+//                               then the lanes are records).
+// Both columns by agx_put49 on [49 held, 49 (held + m)).
+__global__ void __launch_bounds__(256, 4)
+agx_k_append(const DevParams *__restrict__ prm, const u8 *__restrict__ recs, u32 stride, u32 off,
+             const u64 *__restrict__ dig, const u32 *__restrict__ kept, size_t m, size_t held, u64 *__restrict__ leaves,
+             u64 *__restrict__ scal, u8 *__restrict__ wire, u8 *__restrict__ keys) {
+    __shared__ u64 lds[RS_LDS_U64];
+    u64 *A = lds + threadIdx.x;
+    const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= m) return;
+    const size_t src = kept[c], dst = held + c;
+    const u8 *rec = recs + (size_t)stride * src, *sig = rec + off;
+    u64 d[4];
+    ag_leaf_hash(A, prm, dig, src, sig[48], d);
+    const sc256 e = ld_sc(sig + 49);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        leaves[4 * dst + k] = d[k];
+        scal[4 * dst + k] = e.w[k];
+    }
+    const u8 *next = c + 1 < m ? recs + (size_t)stride * kept[c + 1] : rec;     // (read only where c + 1 < m)
+    agx_put49<false>(wire, 49 * held, 49 * (held + m), dst, sig, next + off);
+    if (keys) agx_put49<false>(keys, 49 * held, 49 * (held + m), dst, rec, next);
+}
+
+// Removing lanes (ssa_aggregator_drop_front, _remove; DESIGN.md section 30).  The kept lanes, ascending, take the places
+// 0, 1, 2, ...: kept lane c comes from place src(c) = kept[c] (a mask; the list of av_keep) or c + shift (a front drop:
+// kept == nullptr, no list exists), and src(c) >= c, src ascending.  What a lane stores does not depend on its place, so
+// the lane is MOVED: four words of leaves, four of scal, 49 bytes of wire and, with a key column, 49 bytes of keys.
+//
+// The hazard.  The move is in place, and the threads of a launch run in no order: with one lane dropped at the front
+// every thread's source is its neighbour's destination.  So no launch writes the object.  The host walks the kept
+// lanes in ascending pieces [c0, c1) of at most the context's MSM slice, and for each piece
+//   1. agx_k_move gathers the piece -- reads the object at src(c), writes STAGING (workspaces of the context) at c - c0;
+//   2. three (with a key column: four) stream-ordered device-to-device copies put the staging back on places [c0, c1);
+//   3. only then is the next piece enqueued, on the same stream.
+// Why that is right: (a) a piece's own sources were all read by step 1 before step 2 began (stream order), so step 2
+// may overwrite them; (b) every later piece reads places src(c) >= c >= c1, and step 2 wrote [c0, c1) alone, so no
+// later source has been overwritten; (c) earlier pieces wrote places < c0 <= src(c) only.  Every lane is therefore read
+// as it was before the call.  The walk starts at the first place whose content changes: nothing in front of it is
+// written, not even with its own value.  The argument speaks of PLACES, not of arrays: the key column is a fourth array
+// indexed by the same places, gathered by the same launch and copied back by a fourth copy behind the other three, so
+// (a), (b) and (c) cover it unchanged.
+//
+// The 49-byte stride.  The staging of a piece starts dword-aligned (each 49-byte part of it does), so the piece is a
+// column of agx_put49 with d0 = 0, d1 = 49 cnt and lane t at place t; the next lane's source is the column at
+// src(c + 1).  The source 49 src(c) starts anywhere mod 4: ld_u32_any reads the one or two aligned dwords a misaligned
+// one lies in (never past the dword that holds its last byte, so never outside the column).  The copy back lands at
+// byte 49 c0 of the column, any alignment.
 __global__ void __launch_bounds__(256)
 agx_k_move(const u32 *__restrict__ kept, size_t shift, size_t c0, size_t cnt, const u64 *__restrict__ leaves,
-           const u64 *__restrict__ scal, const u8 *__restrict__ wire, u64 *__restrict__ st_leaves,
-           u64 *__restrict__ st_scal, u8 *__restrict__ st_wire) {
+           const u64 *__restrict__ scal, const u8 *__restrict__ wire, const u8 *__restrict__ keys,
+           u64 *__restrict__ st_leaves, u64 *__restrict__ st_scal, u8 *__restrict__ st_wire, u8 *__restrict__ st_keys) {
     const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= cnt) return;
     const size_t src = kept ? (size_t)kept[c0 + t] : c0 + t + shift;
@@ -191,24 +220,10 @@ agx_k_move(const u32 *__restrict__ kept, size_t shift, size_t c0, size_t cnt, co
     dl[1] = l1;
     ds[0] = s0;
     ds[1] = s1;
-    const size_t lo = 49 * t, hi = lo + 49, end = 49 * cnt;
-    const u8 *r = wire + 49 * src;
-    for (size_t w = (lo + 3) & ~(size_t)3; w < hi; w += 4) {
-        if (w + 4 <= hi) {
-            *reinterpret_cast<u32 *>(st_wire + w) = ld_u32_any(r + (w - lo));
-        } else if (w + 4 <= end) {                    // the dword shared with lane t + 1 (then t + 1 < cnt)
-            const u8 *next = wire + 49 * (kept ? (size_t)kept[c0 + t + 1] : src + 1);
-            u32 v = 0;
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const size_t b = w + k;
-                v |= (u32)(b < hi ? r[b - lo] : next[b - hi]) << (8 * k);
-            }
-            *reinterpret_cast<u32 *>(st_wire + w) = v;
-        } else {                                      // (the last lane alone: for every other one end >= hi + 49)
-            for (size_t b = w; b < end; b++) st_wire[b] = r[b - lo];
-        }
-    }
+    // (the next lane's source is read only for the dword shared with it: then t + 1 < cnt)
+    const size_t nsrc = t + 1 < cnt ? (kept ? (size_t)kept[c0 + t + 1] : src + 1) : src;
+    agx_put49<true>(st_wire, 0, 49 * cnt, t, wire + 49 * src, wire + 49 * nsrc);
+    if (keys) agx_put49<true>(st_keys, 0, 49 * cnt, t, keys + 49 * src, keys + 49 * nsrc);
 }
 
 // out[0] = the first place whose content a removal changes: the first c with kept[c] != c, or m when the m kept lanes

@@ -38,6 +38,7 @@
 #include "ssa_aggregator.hpp"
 
 struct ssa_aggverifier : AgxStore {
+    static constexpr uint32_t kCreateFlags = 0;
     uint64_t pushed = 0, cached = 0;              // cached: lanes pushed through a key cache
     bool keyed = false;                           // kst[0, held) is valid and finish folds it (the rule above)
     DevBuf rpts, ppts, h, bad, kst;
@@ -74,7 +75,7 @@ agv_k_append(const DevParams *__restrict__ prm, const u8 *__restrict__ sigs, con
     if (i >= n) return;
     const size_t dst = held + i;
     u64 d[4];
-    ag_leaf_hash(A, prm, dig, sigs, i, d);
+    ag_leaf_hash(A, prm, dig, i, sigs[81 * i + 48], d);
 #pragma unroll
     for (int k = 0; k < 4; k++) {
         leaves[4 * dst + k] = d[k];

@@ -2577,10 +2577,11 @@ template <class T>
 static int agx_create(ssa_ctx *ctx, size_t capacity, size_t block_lanes, uint32_t flags, T **out) {
     if (out) *out = nullptr;
     const size_t B = agx_block(block_lanes);
-    if (!ctx || !out || flags != 0 || capacity == 0 || capacity > SSA_MAX_BATCH || !B) return SSA_ERR_ARG;
+    if (!ctx || !out || (flags & ~T::kCreateFlags) || capacity == 0 || capacity > SSA_MAX_BATCH || !B) return SSA_ERR_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
     T *obj = new T();
     obj->ctx = ctx;
+    obj->flags = flags;
     obj->capacity = capacity;
     obj->block = B;
     // everything the object will ever hold, now: no push or finish allocates for it
@@ -2618,6 +2619,19 @@ extern "C" int ssa_debug_aggregator_plan(uint64_t held, uint64_t m, uint64_t blo
     return 0;
 }
 
+extern "C" int ssa_debug_aggregator_bytes(size_t capacity, size_t block_lanes, uint32_t flags, uint64_t out[5]) {
+    const size_t B = agx_block(block_lanes);
+    if (!out || (flags & ~ssa_aggregator::kCreateFlags) || capacity == 0 || capacity > SSA_MAX_BATCH || !B) return SSA_ERR_ARG;
+    ssa_aggregator a;          // (never allocated: agx_bufs only says what create would reserve)
+    a.capacity = capacity;
+    a.block = B;
+    a.flags = flags;
+    std::fill(out, out + 5, (uint64_t)0);
+    size_t k = 0;
+    for (const AgxStore::Buf &b : agx_bufs(a)) out[k++] = b.bytes;
+    return 0;
+}
+
 extern "C" int ssa_aggregator_create(ssa_ctx *ctx, size_t capacity, size_t block_lanes, uint32_t flags, ssa_aggregator **out) {
     const int rc = agx_create(ctx, capacity, block_lanes, flags, out);
     if (rc == 0) ctx->aggregators.push_back(*out);
@@ -2647,10 +2661,13 @@ extern "C" int ssa_aggregator_info(ssa_aggregator *ag, uint64_t out[8]) {
     return 0;
 }
 
-// what both forms of push refuse before anything is enqueued or counted
+// what every form of push refuses before anything is enqueued or counted.  sigs, pks: the inputs that must not be null
+// when n != 0 (records: both the records).  keyed: the lanes are KeyedSignature records -- the only push that carries the
+// wire key an object with a key column holds.
 static int agx_push_args(const ssa_ctx *ctx, const ssa_aggregator *ag, const MsgView &mv, size_t n, uint32_t flags,
-                         const void *sigs, const void *pks, const uint64_t *n_kept_out) {
-    if (!ctx || !ag || ag->ctx != ctx || !n_kept_out || (flags & ~SSA_AGGR_NO_SCREEN) || (n && (!sigs || !pks)))
+                         const void *sigs, const void *pks, const uint64_t *n_kept_out, bool keyed = false) {
+    if (!ctx || !ag || ag->ctx != ctx || !n_kept_out || (flags & ~SSA_AGGR_NO_SCREEN) || (n && (!sigs || !pks)) ||
+        (ag->hold_keys() && !keyed))
         return SSA_ERR_ARG;
     if (int rc = agg_check_args(ctx, mv, n)) return rc;
     return n > ag->capacity - ag->held ? SSA_ERR_ARG : 0;      // by n, not by the kept count: never applied in part
@@ -2710,6 +2727,36 @@ static int agx_root(const AgxStore &s, size_t n) {
     return ags_root(ctx, d_tops, n_tops, n, (u64 *)ctx->agm_roots.p);
 }
 
+// The tail of every push, behind the n statuses of its admission (with the raw digests of all n lanes in ctx->ag_dig):
+// the kept lanes are listed (av_keep, one synchronisation for their number), appended -- the lanes are records of
+// `stride` bytes at d_recs with the signature at `off`, and an object with a key column keeps the records' first 49
+// bytes -- the blocks this push completed are reduced, and the object counts the push.
+static int agx_admit(ssa_ctx *ctx, ssa_aggregator *ag, const u8 *d_status, size_t n, const u8 *d_recs, u32 stride, u32 off,
+                     uint64_t *n_kept_out) {
+    if (ctx->agx_kept.reserve(n * sizeof(u32))) return SSA_ERR_HIP;
+    uint64_t m = 0;
+    if (int rc = av_keep(ctx, d_status, n, (u32 *)ctx->agx_kept.p, &m)) return rc;
+    if (m) {
+        int rc = timed_launch(ctx, "agx_k_append", [&] {
+            hipLaunchKernelGGL(agx_k_append, dim3(grid_for(m, 256)), dim3(256), 0, ctx->stream, ctx->d_params, d_recs, stride,
+                               off, (const u64 *)ctx->ag_dig.p, (const u32 *)ctx->agx_kept.p, (size_t)m, ag->held,
+                               (u64 *)ag->leaves.p, (u64 *)ag->scal.p, (u8 *)ag->wire.p,
+                               ag->hold_keys() ? (u8 *)ag->keys.p : (u8 *)nullptr);
+        });
+        if (rc) return rc;
+        const AgxPlan p = agx_plan(ag->held, m, ag->block);
+        if (p.count)
+            if ((rc = agx_reduce_blocks(*ag, p))) return rc;
+    }
+    // (only now: a launch that could not be enqueued leaves the object as it was -- what it wrote lies behind `held`)
+    ag->held += m;
+    ag->pushes++;
+    ag->offered += n;
+    ag->dropped += n - m;
+    *n_kept_out = m;
+    return SSA_OK;
+}
+
 // Synchronises the stream as ssa_aggregate_valid_many_device does: once inside the screen (not at all with
 // SSA_AGGR_NO_SCREEN or for at most msm_small_max lanes) and once for the kept count, which the object keeps on the host
 // from then on.
@@ -2726,7 +2773,7 @@ extern "C" int ssa_aggregator_push_device(ssa_ctx *ctx, ssa_aggregator *ag, cons
         return SSA_OK;
     }
     u8 *d_status = ag_status_buf(ctx, d_status_out, n);
-    if (!d_status || ctx->agx_kept.reserve(n * sizeof(u32))) return SSA_ERR_HIP;
+    if (!d_status) return SSA_ERR_HIP;
     // ONE challenge hash over the n lanes: the raw digests for the leaves and, screened, the scalars mod q for the screen
     const bool screen = !(flags & SSA_AGGR_NO_SCREEN);
     if (int rc = ag_transcript_front(ctx, nullptr, &d_sigs, d_pks, b.msgs, n, screen, nullptr, 1)) return rc;
@@ -2739,26 +2786,7 @@ extern "C" int ssa_aggregator_push_device(ssa_ctx *ctx, ssa_aggregator *ag, cons
         });
         if (rc) return rc;
     }
-    uint64_t m = 0;
-    if (int rc = av_keep(ctx, d_status, n, (u32 *)ctx->agx_kept.p, &m)) return rc;
-    if (m) {
-        int rc = timed_launch(ctx, "agx_k_append", [&] {
-            hipLaunchKernelGGL(agx_k_append, dim3(grid_for(m, 256)), dim3(256), 0, ctx->stream, ctx->d_params, d_sigs,
-                               (const u64 *)ctx->ag_dig.p, (const u32 *)ctx->agx_kept.p, (size_t)m, ag->held,
-                               (u64 *)ag->leaves.p, (u64 *)ag->scal.p, (u8 *)ag->wire.p);
-        });
-        if (rc) return rc;
-        const AgxPlan p = agx_plan(ag->held, m, ag->block);
-        if (p.count)
-            if ((rc = agx_reduce_blocks(*ag, p))) return rc;
-    }
-    // (only now: a launch that could not be enqueued leaves the object as it was -- what it wrote lies behind `held`)
-    ag->held += m;
-    ag->pushes++;
-    ag->offered += n;
-    ag->dropped += n - m;
-    *n_kept_out = m;
-    return SSA_OK;
+    return agx_admit(ctx, ag, d_status, n, d_sigs, 81, 0, n_kept_out);
 }
 
 extern "C" int ssa_aggregator_push(ssa_ctx *ctx, ssa_aggregator *ag, const uint8_t *sigs, const uint8_t *pks,
@@ -2830,6 +2858,28 @@ extern "C" int ssa_aggregator_finish(ssa_ctx *ctx, ssa_aggregator *ag, size_t n_
     return hc.finish([&] { return ssa_aggregator_finish_device(ctx, ag, n, d_agg); });
 }
 
+// ---- the key column (SSA_AGGR_HOLD_KEYS49)
+// Only enqueues: one device-to-device copy.  Changes no state of the object.
+extern "C" int ssa_aggregator_keys_device(ssa_ctx *ctx, ssa_aggregator *ag, size_t n_take, uint8_t *d_keys49_out) {
+    size_t n;
+    if (int rc = agx_take(ctx, ag, n_take, &n)) return rc;
+    if (!ag->hold_keys() || (n && !d_keys49_out)) return SSA_ERR_ARG;
+    if (n == 0) return SSA_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipMemcpyAsync(d_keys49_out, ag->keys.p, 49 * n, hipMemcpyDeviceToDevice, ctx->stream));
+    return SSA_OK;
+}
+
+extern "C" int ssa_aggregator_keys(ssa_ctx *ctx, ssa_aggregator *ag, size_t n_take, uint8_t *keys49_out) {
+    size_t n;
+    if (int rc = agx_take(ctx, ag, n_take, &n)) return rc;
+    if (!ag->hold_keys() || (n && !keys49_out)) return SSA_ERR_ARG;
+    if (n == 0) return SSA_OK;
+    HostCall hc(ctx);
+    u8 *d_keys = hc.out(ctx->st_aux, keys49_out, 49 * n, 16);
+    return hc.finish([&] { return ssa_aggregator_keys_device(ctx, ag, n, d_keys); });
+}
+
 // ---- removing lanes in place (the move and its hazard: agx_k_move in ssa_aggregator.hpp)
 // (a first_changed of 0 is planned as the front drop of held - new_held lanes: see the header)
 extern "C" int ssa_debug_aggregator_remove_plan(uint64_t held, uint64_t first_changed, uint64_t new_held,
@@ -2854,25 +2904,31 @@ static int agx_remove_apply(ssa_aggregator *ag, const u32 *d_kept, size_t f, siz
     const AgxRemovePlan p = agx_remove_plan(held, f, m, B, !d_kept);
     const size_t P = f < m ? std::min(ags_piece(ctx), m - f) : 0, top0 = shift / B;
     const bool tops_overlap = p.moved && top0 < p.moved;
-    if ((P && ctx->agx_stage.reserve(113 * P + 16)) || (tops_overlap && ctx->ags_tops.reserve((size_t)p.moved * 32)))
+    // one piece of staging: P leaves, P scalars, 49 P bytes of R's and -- an object with a key column -- 49 P bytes of
+    // keys behind the R's part rounded up to a dword (each part dword-aligned, and more)
+    const bool hold = ag->hold_keys();
+    const size_t wire_part = hold ? (49 * P + 3) & ~(size_t)3 : 49 * P;
+    if ((P && ctx->agx_stage.reserve(64 * P + wire_part + (hold ? 49 * P : 0) + 16)) ||
+        (tops_overlap && ctx->ags_tops.reserve((size_t)p.moved * 32)))
         return SSA_ERR_HIP;
-    // one piece of staging: P leaves, P scalars, 49 P bytes of R's (each part dword-aligned, and more)
     u64 *st_leaves = (u64 *)ctx->agx_stage.p, *st_scal = st_leaves + 4 * P;
-    u8 *st_wire = (u8 *)(st_scal + 4 * P);
+    u8 *st_wire = (u8 *)(st_scal + 4 * P), *st_keys = hold ? st_wire + wire_part : nullptr;
     u64 *leaves = (u64 *)ag->leaves.p, *scal = (u64 *)ag->scal.p, *tops = (u64 *)ag->tops.p;
-    u8 *wire = (u8 *)ag->wire.p;
+    u8 *wire = (u8 *)ag->wire.p, *keys = hold ? (u8 *)ag->keys.p : nullptr;
     const int rc = [&]() -> int {
         for (size_t c0 = f; c0 < m; c0 += P) {
             const size_t cnt = std::min(P, m - c0);
             const int r = timed_launch(ctx, "agx_k_move", [&] {
                 hipLaunchKernelGGL(agx_k_move, dim3(grid_for(cnt, 256)), dim3(256), 0, ctx->stream, d_kept, shift, c0, cnt,
-                                   (const u64 *)leaves, (const u64 *)scal, (const u8 *)wire, st_leaves, st_scal, st_wire);
+                                   (const u64 *)leaves, (const u64 *)scal, (const u8 *)wire, (const u8 *)keys, st_leaves,
+                                   st_scal, st_wire, st_keys);
             });
             if (r) return r;
             // behind the gather on the stream, in front of the next piece's: places [c0, c0 + cnt) alone are written
             HIP_TRY(hipMemcpyAsync(leaves + 4 * c0, st_leaves, 32 * cnt, hipMemcpyDeviceToDevice, ctx->stream));
             HIP_TRY(hipMemcpyAsync(scal + 4 * c0, st_scal, 32 * cnt, hipMemcpyDeviceToDevice, ctx->stream));
             HIP_TRY(hipMemcpyAsync(wire + 49 * c0, st_wire, 49 * cnt, hipMemcpyDeviceToDevice, ctx->stream));
+            if (hold) HIP_TRY(hipMemcpyAsync(keys + 49 * c0, st_keys, 49 * cnt, hipMemcpyDeviceToDevice, ctx->stream));
         }
         if (p.moved) {       // new block b is old block b + top0; a copy onto its own source goes through a workspace
             const size_t bytes = (size_t)p.moved * 32;
@@ -3770,23 +3826,28 @@ extern "C" int ssa_aggverifier_push_cached_wire(ssa_ctx *ctx, ssa_aggverifier *a
 // cache or ctx->ws_tab, and the re-check gather copies scalars into ctx->scr_in.  Both are reserved for n lanes before
 // the first slice, so no later reserve of a slice's size moves them.
 // The synchronisations of the slices (ssa_verify_many_cached_device has the count) and one for |K|.
-static int avc_run(ssa_ctx *ctx, ssa_keycache *kc, const DevBatch &b, const u8 *d_keyed, size_t n, u8 *d_agg_out,
-                   u32 *d_kept_out, uint64_t *n_kept_out, u8 *d_status_out, u8 *d_keys_out, u8 *d_inf_out,
-                   uint64_t *stats_out) {
+// The status half, which the cached pushes of the streaming aggregator share (section 31): the hash and the n statuses
+// at *d_status_io (nullptr: a buffer of the context, handed back there).
+static int avc_status(ssa_ctx *ctx, ssa_keycache *kc, const DevBatch &b, const u8 *d_keyed, size_t n, u8 **d_status_io,
+                      uint64_t *stats_out) {
     HIP_TRY(hipSetDevice(ctx->device));
-    u8 *d_status = ag_status_buf(ctx, d_status_out, n);
+    u8 *d_status = *d_status_io = ag_status_buf(ctx, *d_status_io, n);
     if (!d_status) return SSA_ERR_HIP;
     if (d_keyed) {
         if (ctx->ws_h.reserve(n * 32) || ctx->ag_dig.reserve(n * 32)) return SSA_ERR_HIP;
-        if (int rc = ssa_internal_screen_keyed_hashed(ctx, kc, d_keyed, b.msgs, n, (uint64_t *)ctx->ws_h.p,
-                                                      (uint8_t *)ctx->ag_dig.p, d_status, stats_out))
-            return rc;
-    } else {
-        const u8 *d_sigs = b.sigs;
-        if (int rc = ag_transcript_front(ctx, nullptr, &d_sigs, b.pks, b.msgs, n, true, nullptr, 1)) return rc;
-        if (int rc = ssa_internal_screen_many_hashed(ctx, kc, b, n, (const uint64_t *)ctx->ws_h.p, d_status, stats_out))
-            return rc;
+        return ssa_internal_screen_keyed_hashed(ctx, kc, d_keyed, b.msgs, n, (uint64_t *)ctx->ws_h.p, (uint8_t *)ctx->ag_dig.p,
+                                                d_status, stats_out);
     }
+    const u8 *d_sigs = b.sigs;
+    if (int rc = ag_transcript_front(ctx, nullptr, &d_sigs, b.pks, b.msgs, n, true, nullptr, 1)) return rc;
+    return ssa_internal_screen_many_hashed(ctx, kc, b, n, (const uint64_t *)ctx->ws_h.p, d_status, stats_out);
+}
+
+static int avc_run(ssa_ctx *ctx, ssa_keycache *kc, const DevBatch &b, const u8 *d_keyed, size_t n, u8 *d_agg_out,
+                   u32 *d_kept_out, uint64_t *n_kept_out, u8 *d_status_out, u8 *d_keys_out, u8 *d_inf_out,
+                   uint64_t *stats_out) {
+    u8 *d_status = d_status_out;
+    if (int rc = avc_status(ctx, kc, b, d_keyed, n, &d_status, stats_out)) return rc;
     // the kept lanes' keys as the caller gave them, and zeros up to the capacity of n lanes (the kernel writes both)
     const auto gather_keys = [&](size_t m) {
         if (!d_keys_out && !d_inf_out) return 0;
@@ -3897,6 +3958,95 @@ extern "C" int ssa_aggregate_valid_keyed_many_cached(ssa_ctx *ctx, ssa_keycache 
     return hc.finish([&] {
         return avc_run(ctx, kc, {nullptr, nullptr, nullptr, mv}, d_keyed, n, d_agg, d_kept, n_kept_out, d_status, d_keys_out,
                        nullptr, stats_out);
+    });
+}
+
+// ---- the streaming aggregator's admission through a key cache: the status half of avc_run, then
+// the tail of every push (agx_admit) in place of the kept lanes' transcript, fold and key gather.
+// arguments of all four forms, before anything is written, enqueued or counted
+static int agx_push_cached_args(const ssa_ctx *ctx, const ssa_aggregator *ag, const ssa_keycache *kc, bool keyed,
+                                const void *in0, const void *in1, const MsgView &mv, size_t n, uint64_t *n_kept_out,
+                                uint64_t *stats_out) {
+    if (int rc = agc_check_cache(ctx, kc, keyed)) return rc;
+    if (int rc = agx_push_args(ctx, ag, mv, n, 0, in0, in1, n_kept_out, keyed)) return rc;
+    *n_kept_out = 0;
+    if (stats_out) std::memset(stats_out, 0, 12 * sizeof(uint64_t));
+    return 0;
+}
+
+// d_keyed: the records (then b holds the messages alone), or nullptr and b the affine lanes.  n >= 1.
+static int agx_push_cached_run(ssa_ctx *ctx, ssa_aggregator *ag, ssa_keycache *kc, const DevBatch &b, const u8 *d_keyed,
+                               size_t n, u8 *d_status_out, uint64_t *n_kept_out, uint64_t *stats_out) {
+    u8 *d_status = d_status_out;
+    if (int rc = avc_status(ctx, kc, b, d_keyed, n, &d_status, stats_out)) return rc;
+    return d_keyed ? agx_admit(ctx, ag, d_status, n, d_keyed, 130, 49, n_kept_out)
+                   : agx_admit(ctx, ag, d_status, n, b.sigs, 81, 0, n_kept_out);
+}
+
+extern "C" int ssa_aggregator_push_cached_device(ssa_ctx *ctx, ssa_aggregator *ag, ssa_keycache *kc, const uint8_t *d_sigs,
+                                                 const uint8_t *d_pks, const uint8_t *d_pk_inf, const uint8_t *d_msgs,
+                                                 const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len, size_t n,
+                                                 uint8_t *d_status_out, uint64_t *n_kept_out, uint64_t stats_out[12]) {
+    const DevBatch b{d_sigs, d_pks, d_pk_inf, {d_msgs, d_msg_off, msg_stride, msg_len}};
+    if (int rc = agx_push_cached_args(ctx, ag, kc, false, d_sigs, d_pks, b.msgs, n, n_kept_out, stats_out)) return rc;
+    if (n == 0) {
+        ag->pushes++;
+        return SSA_OK;
+    }
+    return agx_push_cached_run(ctx, ag, kc, b, nullptr, n, d_status_out, n_kept_out, stats_out);
+}
+
+extern "C" int ssa_aggregator_push_keyed_cached_device(ssa_ctx *ctx, ssa_aggregator *ag, ssa_keycache *kc,
+                                                       const uint8_t *d_keyed, const uint8_t *d_msgs,
+                                                       const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len, size_t n,
+                                                       uint8_t *d_status_out, uint64_t *n_kept_out, uint64_t stats_out[12]) {
+    const DevBatch b{nullptr, nullptr, nullptr, {d_msgs, d_msg_off, msg_stride, msg_len}};
+    if (int rc = agx_push_cached_args(ctx, ag, kc, true, d_keyed, d_keyed, b.msgs, n, n_kept_out, stats_out)) return rc;
+    if (n == 0) {
+        ag->pushes++;
+        return SSA_OK;
+    }
+    return agx_push_cached_run(ctx, ag, kc, b, d_keyed, n, d_status_out, n_kept_out, stats_out);
+}
+
+extern "C" int ssa_aggregator_push_cached(ssa_ctx *ctx, ssa_aggregator *ag, ssa_keycache *kc, const uint8_t *sigs,
+                                          const uint8_t *pks, const uint8_t *pk_inf, const uint8_t *msgs,
+                                          const uint64_t *msg_off, size_t msg_stride, size_t msg_len, size_t n,
+                                          uint8_t *status_out, uint64_t *n_kept_out, uint64_t stats_out[12]) {
+    if (int rc = agx_push_cached_args(ctx, ag, kc, false, sigs, pks, {msgs, msg_off, msg_stride, msg_len}, n, n_kept_out,
+                                      nullptr))
+        return rc;
+    if (int rc = check_host_offsets(msg_off, n)) return rc;
+    if (stats_out) std::memset(stats_out, 0, 12 * sizeof(uint64_t));
+    if (n == 0) {
+        ag->pushes++;
+        return SSA_OK;
+    }
+    HostCall hc(ctx);
+    const DevBatch b = hc.lanes({sigs, pks, pk_inf, msgs, msg_off, msg_stride, msg_len}, n * 81, n);
+    u8 *d_status = hc.out(ctx->st_status, status_out, n, 16);
+    return hc.finish([&] { return agx_push_cached_run(ctx, ag, kc, b, nullptr, n, d_status, n_kept_out, stats_out); });
+}
+
+extern "C" int ssa_aggregator_push_keyed_cached(ssa_ctx *ctx, ssa_aggregator *ag, ssa_keycache *kc, const uint8_t *keyed,
+                                                const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride,
+                                                size_t msg_len, size_t n, uint8_t *status_out, uint64_t *n_kept_out,
+                                                uint64_t stats_out[12]) {
+    if (int rc = agx_push_cached_args(ctx, ag, kc, true, keyed, keyed, {msgs, msg_off, msg_stride, msg_len}, n, n_kept_out,
+                                      nullptr))
+        return rc;
+    if (int rc = check_host_offsets(msg_off, n)) return rc;
+    if (stats_out) std::memset(stats_out, 0, 12 * sizeof(uint64_t));
+    if (n == 0) {
+        ag->pushes++;
+        return SSA_OK;
+    }
+    HostCall hc(ctx);
+    const u8 *d_keyed = hc.in(ctx->st_keyed, keyed, n * 130);
+    const MsgView mv = hc.msgs(msgs, msg_off, msg_stride, msg_len, n);
+    u8 *d_status = hc.out(ctx->st_status, status_out, n, 16);
+    return hc.finish([&] {
+        return agx_push_cached_run(ctx, ag, kc, {nullptr, nullptr, nullptr, mv}, d_keyed, n, d_status, n_kept_out, stats_out);
     });
 }
 

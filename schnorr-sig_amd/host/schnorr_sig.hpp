@@ -880,16 +880,21 @@ class KeyCache {
 // finish at block time.  push admits a slice of triples and appends the ones that pass, in order; finish gives the
 // aggregate of the first n_take admitted triples -- byte for byte AggregateSignature::aggregate(check = false) of those
 // triples alone -- and changes nothing, so it may be repeated, called with another n_take, and followed by more pushes.
-// Belongs to the context it was made on.
+// The KeyCache overloads admit through a key cache, under the verdict validators apply, and an object made with HoldKeys
+// keeps the admitted lanes' wire keys.  Belongs to the context it was made on.
 class Aggregator {
   public:
     struct Info {
         uint64_t held, capacity, block_lanes, pushes, offered, dropped, blocks, finishes;
     };
     static constexpr size_t All = SIZE_MAX;       // finish: every triple held
-    // block_lanes: 0 (512) or a power of two from 2 to 512.  All device memory, about 113 bytes per lane, is allocated here.
-    Aggregator(Context &cx, size_t capacity, size_t block_lanes = 0) : cx_(cx) {
-        const int rc = ssa_aggregator_create(cx.get(), capacity, block_lanes, 0u, &ag_);
+    // HoldKeys (SSA_AGGR_HOLD_KEYS49): the object also holds the 49 wire bytes of every admitted lane's key, for keys();
+    // it then takes push_keyed alone
+    enum Options : uint32_t { None = 0u, HoldKeys = SSA_AGGR_HOLD_KEYS49 };
+    // block_lanes: 0 (512) or a power of two from 2 to 512.  All device memory, about 113 bytes per lane (162 with
+    // HoldKeys), is allocated here.
+    Aggregator(Context &cx, size_t capacity, size_t block_lanes = 0, Options options = None) : cx_(cx) {
+        const int rc = ssa_aggregator_create(cx.get(), capacity, block_lanes, (uint32_t)options, &ag_);
         if (rc != 0) throw std::runtime_error(std::string("ssa_aggregator_create: ") + ssa_strerror(rc));
     }
     ~Aggregator() { ssa_aggregator_destroy(ag_); }
@@ -913,6 +918,72 @@ class Aggregator {
         if (rc != 0) throw std::runtime_error(std::string("ssa_aggregator_push: ") + ssa_strerror(rc));
         if (n_kept_out) *n_kept_out = n_kept;
         return status;
+    }
+    // Through a key cache, subgroup check included: statuses and stats_out (12 words, or nullptr)
+    // are those of ssa_aggregate_valid_many_cached on this slice alone and the same cache -- a triple whose key lies
+    // outside the prime-order subgroup is dropped with SSA_INVALID_PUBLIC_KEY.  An Affine cache here, a Wire cache for
+    // push_keyed.  Lanes of every kind of push may be mixed in one object.
+    std::vector<uint8_t> push(KeyCache &cache, const std::vector<Signature> &signatures,
+                              const std::vector<PublicKey> &public_keys,
+                              const std::vector<std::pair<const uint8_t *, size_t>> &messages, uint64_t *n_kept_out = nullptr,
+                              uint64_t *stats_out = nullptr) {
+        if (cache.wire()) throw std::invalid_argument("a Wire key cache takes KeyedSignature records (push_keyed)");
+        const PackedTriples t = pack_triples(signatures, public_keys, messages);
+        const size_t n = signatures.size();
+        std::vector<uint8_t> status(n, 0);
+        uint64_t n_kept = 0;
+        const int rc = ssa_aggregator_push_cached(cx_.get(), ag_, cache.get(), t.sigs.data(), t.pks.data(), t.inf.data(),
+                                                  t.flat.data(), t.off.data(), 0, 0, n, n ? status.data() : nullptr, &n_kept,
+                                                  stats_out);
+        if (rc != 0) throw std::runtime_error(std::string("ssa_aggregator_push_cached: ") + ssa_strerror(rc));
+        if (n_kept_out) *n_kept_out = n_kept;
+        return status;
+    }
+    // keyed: messages.size() records side by side, 130 bytes each (key 49 || signature 81), as a mempool receives them;
+    // statuses and stats_out are those of ssa_aggregate_valid_keyed_many_cached on this slice alone and the same cache
+    std::vector<uint8_t> push_keyed(KeyCache &cache, const std::vector<uint8_t> &keyed,
+                                    const std::vector<std::pair<const uint8_t *, size_t>> &messages,
+                                    uint64_t *n_kept_out = nullptr, uint64_t *stats_out = nullptr) {
+        if (!cache.wire()) throw std::invalid_argument("an Affine key cache takes triples (push), not KeyedSignature records");
+        const size_t n = messages.size();
+        if (keyed.size() != n * KEYED_SIGNATURE_LENGTH)
+            throw std::invalid_argument("We should have the same number of messages than keyed signatures");
+        std::vector<uint8_t> flat;
+        std::vector<uint64_t> off(n + 1, 0);
+        for (size_t i = 0; i < n; i++) {
+            flat.insert(flat.end(), messages[i].first, messages[i].first + messages[i].second);
+            off[i + 1] = flat.size();
+        }
+        flat.push_back(0);
+        std::vector<uint8_t> status(n, 0);
+        uint64_t n_kept = 0;
+        const int rc = ssa_aggregator_push_keyed_cached(cx_.get(), ag_, cache.get(), n ? keyed.data() : nullptr, flat.data(),
+                                                        off.data(), 0, 0, n, n ? status.data() : nullptr, &n_kept, stats_out);
+        if (rc != 0) throw std::runtime_error(std::string("ssa_aggregator_push_keyed_cached: ") + ssa_strerror(rc));
+        if (n_kept_out) *n_kept_out = n_kept;
+        return status;
+    }
+    // the same over KeyedSignature objects: each is put on the wire (KeyedSignature::to_bytes) first
+    std::vector<uint8_t> push_keyed(KeyCache &cache, const std::vector<KeyedSignature> &records,
+                                    const std::vector<std::pair<const uint8_t *, size_t>> &messages,
+                                    uint64_t *n_kept_out = nullptr, uint64_t *stats_out = nullptr) {
+        std::vector<uint8_t> keyed;
+        keyed.reserve(records.size() * KEYED_SIGNATURE_LENGTH);
+        for (const KeyedSignature &r : records) {
+            const auto b = r.to_bytes(cx_);
+            keyed.insert(keyed.end(), b.begin(), b.end());
+        }
+        return push_keyed(cache, keyed, messages, n_kept_out, stats_out);
+    }
+    // the wire keys of the first n_take held triples, 49 bytes each, in arrival order (an object made with HoldKeys; any
+    // other throws): with finish(n_take) the block body AggregateSignature::verify_many's wire-key overload takes
+    std::vector<uint8_t> keys(size_t n_take = All) const {
+        const size_t n = n_take == All ? (size_t)info().held : n_take;
+        std::vector<uint8_t> out(n * PUBLIC_KEY_LENGTH + 1, 0);
+        const int rc = ssa_aggregator_keys(cx_.get(), ag_, n, out.data());
+        if (rc != 0) throw std::runtime_error(std::string("ssa_aggregator_keys: ") + ssa_strerror(rc));
+        out.resize(n * PUBLIC_KEY_LENGTH);
+        return out;
     }
     AggregateSignature finish(size_t n_take = All) const {
         const size_t n = n_take == All ? (size_t)info().held : n_take;
