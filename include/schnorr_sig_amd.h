@@ -1277,7 +1277,32 @@ int ssa_aggregate_valid_keyed_many_cached_device(ssa_ctx *ctx, ssa_keycache *kc,
  *            keys, unchanged, with the kept messages, k = 1 and counts = {n}, are what
  *            ssa_verify_aggregates_many_cached_wire takes; on the same cache that call finds every key (stats[2] == 0)
  *            unless the push bypassed the cache or did not use it.
- * NOT here: reordering held lanes, finishing an arbitrary subset without removing it, a column of affine keys, the
+ *   finish_select, remove_indices   CHOOSE among the held lanes: a producer fills its block with the
+ *            lanes it wants, in an order of its own, and keeps the rest.  Let L be the lanes held; order[0, m) names m
+ *            DISTINCT places < held.  finish_select writes SSA_AGGREGATE_LENGTH(m) bytes: byte for byte what
+ *            ssa_aggregate_many (flags 0) returns for L[order[0]], ..., L[order[m - 1]] handed in alone in that order.
+ *            Like finish it changes no state of the object but the `finishes` counter (every call that passes the
+ *            argument checks counts): it may be repeated, mixed with finish, and followed by pushes and removals.
+ *            keys49_out (may be NULL; otherwise the object must have SSA_AGGR_HOLD_KEYS49, else SSA_ERR_ARG) receives the
+ *            selected lanes' 49 key bytes in the same order, 49 m bytes; the two outputs, with the selected messages,
+ *            k = 1 and counts = {m}, are what ssa_verify_aggregates_many_cached_wire takes.  m == 0: 32 zero bytes.  No
+ *            message, key or signature is touched: the call gathers the stored leaves, scalars, R's and keys, runs the
+ *            tree over the gathered leaves and the coefficient fold of finish.
+ *            SSA_ERR_ARG before anything is launched: m > held, m above the context's MSM slice, a NULL order with
+ *            m > 0, a NULL agg_out, an object of another context or an orphaned one, a device list that is not 4-byte
+ *            aligned, a NULL d_result_out.
+ *            Whether the list is valid -- every index < held, no index twice -- is decided ON THE DEVICE.  An invalid list
+ *            zeroes the outputs (SSA_AGGREGATE_LENGTH(m) bytes, and 49 m bytes of keys), the way ssa_aggregates_many
+ *            refuses an aggregate, and no lane outside [0, held) is read.  The host form then returns SSA_ERR_ARG; the
+ *            _device form only enqueues and writes *d_result_out (DEVICE memory, required): 0 valid, 1 invalid.  Either
+ *            way the object is unchanged and a later finish gives the bytes it gave before.
+ *            remove_indices is remove with a list in place of a mask: the lanes named are removed, everything else stays
+ *            in arrival order, and the object then equals the one remove leaves for the equivalent mask.  The list obeys
+ *            the rules above (any m <= held: no slice limit); an invalid one is SSA_ERR_ARG with the object unchanged --
+ *            the device's verdict is read before the move begins.  *n_kept_out (HOST memory in both forms) = the lanes
+ *            kept (for a refused list: the lanes held).  m == 0: SSA_OK, nothing is launched.  The _device form
+ *            synchronises the context's stream once, as remove_device does.
+ * NOT here: selections above one MSM slice, reuse of the stored tops for a selection, a column of affine keys, the
  * messages, ssa_multi forms.  The validator's counterpart is ssa_aggverifier, below. */
 typedef struct ssa_aggregator ssa_aggregator;
 #define SSA_AGGR_NO_SCREEN 1u      /* push flag */
@@ -1322,6 +1347,13 @@ int ssa_aggregator_drop_front(ssa_ctx *ctx, ssa_aggregator *ag, size_t n);
 int ssa_aggregator_remove(ssa_ctx *ctx, ssa_aggregator *ag, const uint8_t *drop, size_t n_bytes, uint64_t *n_kept_out);
 int ssa_aggregator_remove_device(ssa_ctx *ctx, ssa_aggregator *ag, const uint8_t *d_drop, size_t n_bytes,
                                  uint64_t *n_kept_out);
+int ssa_aggregator_finish_select(ssa_ctx *ctx, ssa_aggregator *ag, const uint32_t *order, size_t m, uint8_t *agg_out,
+                                 uint8_t *keys49_out);
+int ssa_aggregator_finish_select_device(ssa_ctx *ctx, ssa_aggregator *ag, const uint32_t *d_order, size_t m,
+                                        uint8_t *d_agg_out, uint8_t *d_keys49_out, uint32_t *d_result_out);
+int ssa_aggregator_remove_indices(ssa_ctx *ctx, ssa_aggregator *ag, const uint32_t *order, size_t m, uint64_t *n_kept_out);
+int ssa_aggregator_remove_indices_device(ssa_ctx *ctx, ssa_aggregator *ag, const uint32_t *d_order, size_t m,
+                                         uint64_t *n_kept_out);
 /* tests: what a removal does to the stored tops (host code, no device).  held: the lanes held before; first_changed: the
  * first place whose content changes -- the first removed lane; new_held: the lanes kept; first_changed <= new_held <=
  * held.  first_changed == 0 stands for drop_front(held - new_held), the one removal the library plans with that value (a

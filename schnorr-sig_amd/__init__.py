@@ -312,6 +312,10 @@ def _load():
         "ssa_aggregator_remove": (i32, [vp, vp, vp, sz, u64p]),
         "ssa_aggregator_remove_device": (i32, [vp, vp, vp, sz, u64p]),
         "ssa_debug_aggregator_remove_plan": (i32, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, u64p]),
+        "ssa_aggregator_finish_select": (i32, [vp, vp, vp, sz, vp, vp]),
+        "ssa_aggregator_finish_select_device": (i32, [vp, vp, vp, sz, vp, vp, vp]),
+        "ssa_aggregator_remove_indices": (i32, [vp, vp, vp, sz, u64p]),
+        "ssa_aggregator_remove_indices_device": (i32, [vp, vp, vp, sz, u64p]),
         "ssa_aggverifier_create": (i32, [vp, sz, sz, u32, C.POINTER(vp)]),
         "ssa_aggverifier_destroy": (None, [vp]),
         "ssa_aggverifier_reset": (i32, [vp]),
@@ -1855,6 +1859,45 @@ def _n_take(n_take):
     return AGGREGATOR_ALL if n_take is None else int(n_take)
 
 
+def _order_u32(order):
+    """a list of held lanes' places (any integer sequence or array) as the contiguous uint32 array the ABI takes;
+    ValueError, before any call, for values that are no integers or do not fit 32 bits"""
+    if isinstance(order, np.ndarray) and order.dtype == np.uint32 and order.ndim == 1 and order.flags.c_contiguous:
+        return order
+    a = np.asarray(order if isinstance(order, np.ndarray) else list(order))
+    if a.size == 0:
+        return np.zeros(0, dtype=np.uint32)
+    if a.ndim != 1 or a.dtype.kind not in "iu":
+        raise ValueError("order is a one-dimensional sequence of integers")
+    if int(a.min()) < 0 or int(a.max()) > 0xFFFFFFFF:
+        raise ValueError("order holds places of held lanes: 0 .. 2^32 - 1")
+    return np.ascontiguousarray(a, dtype=np.uint32)
+
+
+def _on_device(t, engine):
+    """the tensor lies on the engine's GPU"""
+    dev = getattr(t, "device", None)
+    return dev is not None and dev.type == "cuda" and (dev.index or 0) == int(getattr(engine, "device", 0) or 0)
+
+
+def _dev_order(d_order, engine):
+    """a list of places in device memory as the _device forms take it: a contiguous one-dimensional int32 / uint32 tensor
+    on the engine's device (the address is handed to the kernel as it is) -> its length; ValueError otherwise"""
+    if str(getattr(d_order, "dtype", None)) not in ("torch.int32", "torch.uint32"):
+        raise ValueError("d_order holds 32-bit integer indices (torch.int32 or torch.uint32)")
+    if d_order.dim() != 1 or not d_order.is_contiguous():
+        raise ValueError("d_order is a contiguous one-dimensional tensor")
+    if not _on_device(d_order, engine):
+        raise ValueError("d_order lies on the engine's device")
+    return int(d_order.numel())
+
+
+def _dev_bytes(t, engine, name):
+    """an output of a _device form: a contiguous uint8 tensor on the engine's device; ValueError otherwise"""
+    if str(getattr(t, "dtype", None)) != "torch.uint8" or not t.is_contiguous() or not _on_device(t, engine):
+        raise ValueError("%s is a contiguous uint8 tensor on the engine's device" % name)
+
+
 class _LaneStore(_Handle):
     """what the two streaming objects share: the eight info words under the names of _fields, len() = the lanes held,
     reset()"""
@@ -1880,7 +1923,8 @@ class Aggregator(_LaneStore):
     lanes -- what Engine.aggregate gives those lanes handed in alone -- and changes nothing; drop_front(), remove() and
     take() remove lanes in place and keep the rest of the pool; push(cache=) and push_keyed()
     admit through a key cache, and an object made with hold_keys=True keeps the admitted lanes' wire keys for keys() and
-    take_block().  Tied to its Engine like KeyCache; destroyed exactly once (close(), the end of
+    take_block(); finish_select(), remove_indices() and take_select() do the same for lanes of
+    the caller's choosing, in the caller's order.  Tied to its Engine like KeyCache; destroyed exactly once (close(), the end of
     a `with` block, or when the object goes away)."""
     _prefix, _fields = "aggregator", AGGREGATOR_FIELDS
 
@@ -2040,6 +2084,74 @@ class Aggregator(_LaneStore):
         _check(_lib.ssa_aggregator_remove_device(self.engine._ctx, self.handle, _addr(d_drop), int(d_drop.numel()),
                                                  C.byref(n_kept)), "ssa_aggregator_remove_device")
         return int(n_kept.value)
+
+    def finish_select_bytes(self, order, keys=False):
+        """the aggregate of the held lanes at the places order[0], order[1], ... in that order, as uint8[49 m + 32]; with
+        keys=True (an object made with hold_keys=True) -> (that, their wire keys uint8[m, 49])"""
+        order = _order_u32(order)
+        m = int(order.size)
+        agg = np.full(49 * m + 32, 255, dtype=np.uint8)
+        k49 = np.full((max(m, 1), 49), 255, dtype=np.uint8) if keys else None
+        _check(_lib.ssa_aggregator_finish_select(self.engine._ctx, self.handle, _ptr(order) if m else None, m, _ptr(agg),
+                                                 _ptr(k49)), "ssa_aggregator_finish_select")
+        return (agg, k49[:m].copy()) if keys else agg
+
+    def finish_select(self, order, keys=False):
+        """-> the AggregateSignature of the held lanes order[0], order[1], ... (distinct places below the lanes held, any
+        integer sequence or array) in THAT order: what Engine.aggregate gives those lanes handed in alone (DESIGN.md
+        section 32).  Changes no state, like finish.  keys=True: -> (aggregate, keys uint8[m, 49]), the block body's key
+        column in the same order.  Indices that do not fit 32 bits raise ValueError here; an index out of range or named
+        twice is refused by the device and raises as every SSA_ERR_ARG does."""
+        out = self.finish_select_bytes(order, keys)
+        return (AggregateSignature(out[0].tobytes()), out[1]) if keys else AggregateSignature(out.tobytes())
+
+    def finish_select_device(self, d_order, d_agg, d_result, d_keys49=None):
+        """device form: only enqueues on the engine's stream.  d_order: an int32 / uint32-valued tensor of m indices on
+        the engine's device (4-byte aligned); the 49 m + 32 bytes land in the uint8 tensor d_agg, the 49 m key bytes in
+        d_keys49 when it is given (both at any byte alignment), and d_result (one int32 on the device) receives 0 for a
+        valid list, 1 for a refused one -- whose outputs are zeroed.  Returns m."""
+        m = _dev_order(d_order, self.engine)
+        _dev_bytes(d_agg, self.engine, "d_agg")
+        if d_keys49 is not None:
+            _dev_bytes(d_keys49, self.engine, "d_keys49")
+        if (str(d_result.dtype) not in ("torch.int32", "torch.uint32") or d_result.numel() < 1 or not d_result.is_contiguous()
+                or not _on_device(d_result, self.engine)):
+            raise ValueError("d_result is one 32-bit integer on the engine's device")
+        if d_agg.numel() < 49 * m + 32 or (d_keys49 is not None and d_keys49.numel() < 49 * m):
+            raise ValueError("a selection of %d lanes is %d bytes and %d bytes of keys" % (m, 49 * m + 32, 49 * m))
+        _check(_lib.ssa_aggregator_finish_select_device(
+            self.engine._ctx, self.handle, _addr(d_order), m, d_agg.data_ptr(),
+            None if d_keys49 is None else d_keys49.data_ptr(), d_result.data_ptr()), "ssa_aggregator_finish_select_device")
+        return m
+
+    def remove_indices(self, order, engine=None):
+        """remove() with a list in place of a mask: the held lanes at the places named in `order` (distinct, below the
+        lanes held, in any order) leave the object, the rest stays in arrival order -> the number of lanes kept.  An
+        invalid list raises and changes nothing.  engine: tests."""
+        order = _order_u32(order)
+        n_kept = C.c_uint64(0)
+        _check(_lib.ssa_aggregator_remove_indices((engine or self.engine)._ctx, self.handle,
+                                                  _ptr(order) if order.size else None, int(order.size), C.byref(n_kept)),
+               "ssa_aggregator_remove_indices")
+        return int(n_kept.value)
+
+    def remove_indices_device(self, d_order):
+        """device form of remove_indices over a 32-bit integer tensor on the engine's device.  Synchronises the stream
+        once, as remove_device does -> the number of lanes kept."""
+        m = _dev_order(d_order, self.engine)
+        n_kept = C.c_uint64(0)
+        _check(_lib.ssa_aggregator_remove_indices_device(self.engine._ctx, self.handle, _addr(d_order), m,
+                                                         C.byref(n_kept)), "ssa_aggregator_remove_indices_device")
+        return int(n_kept.value)
+
+    def take_select(self, order):
+        """finish_select(order) -- with the keys when the object holds them -- then remove_indices(order): the chosen
+        lanes leave as a block body, the rest stays, in arrival order, for the next slot.  -> AggregateSignature, or
+        (AggregateSignature, keys uint8[m, 49]) from an object made with hold_keys=True"""
+        order = _order_u32(order)
+        out = self.finish_select(order, keys=self.hold_keys)
+        self.remove_indices(order)
+        return out
 
     def take(self, n_take=None):
         """finish(n_take), then drop_front of the same lanes: the AggregateSignature of the first n_take held lanes

@@ -23,6 +23,10 @@
 //   remove  (drop_front, remove) the kept lanes move to the front piece by piece through staging
 //           workspaces of the context (agx_k_move, below), and agx_remove_plan says which tops stay, move or are reduced
 //           again.  No message, key or signature is touched.
+//   select  (finish_select, remove_indices) a list of distinct places, in the caller's order: the
+//           named lanes are gathered into staging workspaces of the context (agx_k_select, below, which also decides
+//           whether the list is valid), the tree runs over the gathered leaves from the bottom -- the stored tops say
+//           nothing about another order -- and the coefficient fold is finish's.  The object is read, never written.
 //
 // The object's four (with the key column: five) arrays are its own allocations (released by destroy, or by the context's clean-up): they are not in
 // the context's list of workspaces, and nothing the object needs between two calls lives in one.
@@ -236,6 +240,92 @@ agx_k_first_changed(const u32 *__restrict__ kept, const u32 *__restrict__ m_dev,
     if (c > n || c > m) return;
     const bool here = c == m || kept[c] != c, before = c > 0 && kept[c - 1] != c - 1;
     if (here && !before) out[0] = (u32)c;
+}
+
+// A selection (ssa_aggregator_finish_select, _remove_indices): order[0, m) names m DISTINCT places
+// below `held`.  Whether it does is decided here, on the device, by every thread for its own index:
+//   bits   one bit per held lane, cleared by the call in front of the launch; the thread of order[t] sets bit order[t]
+//          with an atomic OR, and the value the OR returns says whether somebody set it before;
+//   flag   one word, cleared with the bitmap, raised (atomic OR) for an index >= held or a bit that was already set.
+// Of two threads that name the same place exactly one finds the bit set, whichever comes second: the flag ends up
+// raised either way, and nothing else depends on which of them it was.
+// -> the index is in range (a duplicate is: its lane may be read, the flag refuses the list as a whole).
+static __device__ __forceinline__ bool agx_claim(u32 idx, size_t held, u32 *__restrict__ bits, u32 *__restrict__ flag) {
+    if ((size_t)idx >= held) {
+        atomicOr(flag, 1u);
+        return false;
+    }
+    const u32 bit = 1u << (idx & 31u);
+    if (atomicOr(bits + (idx >> 5), bit) & bit) atomicOr(flag, 1u);
+    return true;
+}
+
+// The gather of a selection: one lane per selected position t.  The lane at place order[t] of the object is copied to
+// place t of the STAGING (workspaces of the context: the selection reads the object and never writes it) -- leaf and
+// scalar as in agx_k_move, the 49-byte columns by agx_put49 with d0 = 0, d1 = 49 m and lane t at place t.  The next
+// lane's source is the column at order[t + 1]; the sources are in no order, which agx_put49 does not need: it reads
+// `next` for the bytes of one shared dword only.
+//
+// Why no thread reads outside [0, held).  Every address into the object is formed from `src` or `nsrc`, and both have
+// been compared with `held` first: a thread whose own index fails agx_claim returns before it forms any address (it
+// reads nothing and writes nothing: the flag it raised makes the call zero its outputs), and a next index that is not
+// below `held` is replaced by the thread's own, checked, index -- the bytes it then puts into the shared dword are wrong,
+// in a list that is refused anyway.  ld_u32_any stays inside the column of the lane it is given (see agx_k_move), and the
+// bitmap word idx >> 5 exists because idx < held.
+__global__ void __launch_bounds__(256)
+agx_k_select(const u32 *__restrict__ order, size_t m, size_t held, u32 *__restrict__ bits, u32 *__restrict__ flag,
+             const u64 *__restrict__ leaves, const u64 *__restrict__ scal, const u8 *__restrict__ wire,
+             const u8 *__restrict__ keys, u64 *__restrict__ st_leaves, u64 *__restrict__ st_scal, u8 *__restrict__ st_wire,
+             u8 *__restrict__ st_keys) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= m) return;
+    const u32 idx = order[t];
+    if (!agx_claim(idx, held, bits, flag)) return;
+    const size_t src = idx;
+    const ulonglong2 *l = reinterpret_cast<const ulonglong2 *>(leaves + 4 * src);
+    const ulonglong2 *s = reinterpret_cast<const ulonglong2 *>(scal + 4 * src);
+    const ulonglong2 l0 = l[0], l1 = l[1], s0 = s[0], s1 = s[1];
+    ulonglong2 *dl = reinterpret_cast<ulonglong2 *>(st_leaves + 4 * t), *ds = reinterpret_cast<ulonglong2 *>(st_scal + 4 * t);
+    dl[0] = l0;
+    dl[1] = l1;
+    ds[0] = s0;
+    ds[1] = s1;
+    size_t nsrc = src;
+    if (t + 1 < m) {
+        const u32 nidx = order[t + 1];
+        if ((size_t)nidx < held) nsrc = nidx;
+    }
+    agx_put49<true>(st_wire, 0, 49 * m, t, wire + 49 * src, wire + 49 * nsrc);
+    if (st_keys) agx_put49<true>(st_keys, 0, 49 * m, t, keys + 49 * src, keys + 49 * nsrc);
+}
+
+// The same decision without a gather (ssa_aggregator_remove_indices): one thread per listed index.
+__global__ void __launch_bounds__(256)
+agx_k_mark(const u32 *__restrict__ order, size_t m, size_t held, u32 *__restrict__ bits, u32 *__restrict__ flag) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < m) (void)agx_claim(order[t], held, bits, flag);
+}
+
+// The bitmap as the byte mask ssa_aggregator_remove_device takes: mask[i] = 1 iff bit i is set.  One thread per held lane.
+__global__ void __launch_bounds__(256)
+agx_k_bits_to_mask(const u32 *__restrict__ bits, size_t held, u8 *__restrict__ mask) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < held) mask[i] = (u8)((bits[i >> 5] >> (i & 31u)) & 1u);
+}
+
+// Behind a selection's copies: *result = 0 for a valid list, 1 for a refused one, and a refused list's outputs -- n_agg
+// bytes at agg, n_keys bytes at keys (nullptr: none), at any alignment -- are zeroed, the way ssa_aggregates_many refuses
+// an aggregate.  A valid list costs every thread one read of the flag.  Grid-stride over bytes.
+__global__ void __launch_bounds__(256)
+agx_k_select_verdict(const u32 *__restrict__ flag, u8 *__restrict__ agg, size_t n_agg, u8 *__restrict__ keys, size_t n_keys,
+                     u32 *__restrict__ result) {
+    const u32 bad = *flag ? 1u : 0u;
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x, step = (size_t)gridDim.x * blockDim.x;
+    if (g == 0) *result = bad;
+    if (!bad) return;
+    for (size_t b = g; b < n_agg; b += step) agg[b] = 0;
+    if (keys)
+        for (size_t b = g; b < n_keys; b += step) keys[b] = 0;
 }
 
 // The block-time hot path: one lane per held lane of a piece.  Lane i (place lane0 + i of the aggregate) derives its

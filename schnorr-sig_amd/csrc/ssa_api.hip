@@ -2805,30 +2805,21 @@ extern "C" int ssa_aggregator_push(ssa_ctx *ctx, ssa_aggregator *ag, const uint8
     });
 }
 
-// Only enqueues on the context's stream: every size it needs is on the host.  Reads the object, writes workspaces of the
-// context and the caller's buffer.
-extern "C" int ssa_aggregator_finish_device(ssa_ctx *ctx, ssa_aggregator *ag, size_t n_take, uint8_t *d_agg_out) {
-    size_t n;
-    if (int rc = agx_take(ctx, ag, n_take, &n)) return rc;
-    if (!d_agg_out) return SSA_ERR_ARG;
-    HIP_TRY(hipSetDevice(ctx->device));
-    ag->finishes++;
-    if (n == 0) {
-        HIP_TRY(hipMemsetAsync(d_agg_out, 0, 32, ctx->stream));
-        return SSA_OK;
-    }
+// e_agg of n (>= 1) lanes whose scalars stand at d_scal, four words per lane, lane i at place i of the aggregate, under
+// the root in ctx->agm_roots: agx_k_coeff_fold per piece of at most one MSM slice, ag_k_fold_finish per piece and over
+// the pieces, into ag_misc(ctx, AG_E).  What finish runs on the object's scalars and finish_select on the gathered ones.
+static int agx_fold(ssa_ctx *ctx, const u64 *d_scal, size_t n) {
     const size_t piece = ags_piece(ctx), k = (n + piece - 1) / piece;
     if (ctx->ag_misc.reserve(AG_MISC_BYTES) || ctx->ags_parts.reserve(k * 32) ||
         ctx->ag_partials.reserve((size_t)grid_for(std::min(piece, n), 256) * 32))
         return SSA_ERR_HIP;
-    if (int rc = agx_root(*ag, n)) return rc;
-    const u64 *d_root = (const u64 *)ctx->agm_roots.p;      // (only now: agx_root reserves it)
+    const u64 *d_root = (const u64 *)ctx->agm_roots.p;
     for (size_t lo = 0, j = 0; lo < n; lo += piece, j++) {
         const size_t cnt = std::min(piece, n - lo);
         const unsigned n_blocks = grid_for(cnt, 256);
         int rc = timed_launch(ctx, "agx_k_coeff_fold", [&] {
             hipLaunchKernelGGL(agx_k_coeff_fold, dim3(n_blocks), dim3(256), 0, ctx->stream, ctx->d_params, d_root,
-                               (const u64 *)ag->scal.p + 4 * lo, cnt, (u64)lo, (u64 *)ctx->ag_partials.p);
+                               d_scal + 4 * lo, cnt, (u64)lo, (u64 *)ctx->ag_partials.p);
         });
         if (rc) return rc;
         rc = timed_launch(ctx, "ag_k_fold_finish", [&] {
@@ -2844,6 +2835,23 @@ extern "C" int ssa_aggregator_finish_device(ssa_ctx *ctx, ssa_aggregator *ag, si
         });
         if (rc) return rc;
     }
+    return SSA_OK;
+}
+
+// Only enqueues on the context's stream: every size it needs is on the host.  Reads the object, writes workspaces of the
+// context and the caller's buffer.
+extern "C" int ssa_aggregator_finish_device(ssa_ctx *ctx, ssa_aggregator *ag, size_t n_take, uint8_t *d_agg_out) {
+    size_t n;
+    if (int rc = agx_take(ctx, ag, n_take, &n)) return rc;
+    if (!d_agg_out) return SSA_ERR_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    ag->finishes++;
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(d_agg_out, 0, 32, ctx->stream));
+        return SSA_OK;
+    }
+    if (int rc = agx_root(*ag, n)) return rc;
+    if (int rc = agx_fold(ctx, (const u64 *)ag->scal.p, n)) return rc;
     HIP_TRY(hipMemcpyAsync(d_agg_out, ag->wire.p, 49 * n, hipMemcpyDeviceToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(d_agg_out + 49 * n, ag_misc(ctx, AG_E), 32, hipMemcpyDeviceToDevice, ctx->stream));
     return SSA_OK;
@@ -2894,6 +2902,22 @@ extern "C" int ssa_debug_aggregator_remove_plan(uint64_t held, uint64_t first_ch
     return 0;
 }
 
+// The staging of P gathered lanes (a piece of the move, a selection) in `buf`: P leaves, P scalars, 49 P bytes of R's and
+// -- with_keys -- 49 P bytes of keys behind the R's part rounded up to a dword (each part dword-aligned, and more).
+struct AgxStage {
+    u64 *leaves, *scal;
+    u8 *wire, *keys;
+};
+static int agx_stage_layout(DevBuf &buf, size_t P, bool with_keys, AgxStage *st) {
+    const size_t wire_part = with_keys ? (49 * P + 3) & ~(size_t)3 : 49 * P;
+    if (buf.reserve(64 * P + wire_part + (with_keys ? 49 * P : 0) + 16)) return SSA_ERR_HIP;
+    st->leaves = (u64 *)buf.p;
+    st->scal = st->leaves + 4 * P;
+    st->wire = (u8 *)(st->scal + 4 * P);
+    st->keys = with_keys ? st->wire + wire_part : nullptr;
+    return 0;
+}
+
 // The m kept lanes of an object -- ascending: d_kept[c], or c + (held - m) for a front drop, which has no list
 // (d_kept == nullptr) -- take the places [0, m).  f: the first place whose content changes.  Only enqueues.  The move is
 // in place and cannot be undone: once its first launch is enqueued, an error leaves the object EMPTY, never half-moved.
@@ -2904,15 +2928,12 @@ static int agx_remove_apply(ssa_aggregator *ag, const u32 *d_kept, size_t f, siz
     const AgxRemovePlan p = agx_remove_plan(held, f, m, B, !d_kept);
     const size_t P = f < m ? std::min(ags_piece(ctx), m - f) : 0, top0 = shift / B;
     const bool tops_overlap = p.moved && top0 < p.moved;
-    // one piece of staging: P leaves, P scalars, 49 P bytes of R's and -- an object with a key column -- 49 P bytes of
-    // keys behind the R's part rounded up to a dword (each part dword-aligned, and more)
     const bool hold = ag->hold_keys();
-    const size_t wire_part = hold ? (49 * P + 3) & ~(size_t)3 : 49 * P;
-    if ((P && ctx->agx_stage.reserve(64 * P + wire_part + (hold ? 49 * P : 0) + 16)) ||
-        (tops_overlap && ctx->ags_tops.reserve((size_t)p.moved * 32)))
+    AgxStage st{};
+    if ((P && agx_stage_layout(ctx->agx_stage, P, hold, &st)) || (tops_overlap && ctx->ags_tops.reserve((size_t)p.moved * 32)))
         return SSA_ERR_HIP;
-    u64 *st_leaves = (u64 *)ctx->agx_stage.p, *st_scal = st_leaves + 4 * P;
-    u8 *st_wire = (u8 *)(st_scal + 4 * P), *st_keys = hold ? st_wire + wire_part : nullptr;
+    u64 *st_leaves = st.leaves, *st_scal = st.scal;
+    u8 *st_wire = st.wire, *st_keys = st.keys;
     u64 *leaves = (u64 *)ag->leaves.p, *scal = (u64 *)ag->scal.p, *tops = (u64 *)ag->tops.p;
     u8 *wire = (u8 *)ag->wire.p, *keys = hold ? (u8 *)ag->keys.p : nullptr;
     const int rc = [&]() -> int {
@@ -2960,15 +2981,13 @@ static int agx_remove_args(const ssa_ctx *ctx, const ssa_aggregator *ag, const u
     return !ctx || !ag || ag->ctx != ctx || !n_kept_out || n_bytes != ag->held || (n_bytes && !drop) ? SSA_ERR_ARG : 0;
 }
 
-// Synchronises the stream once, for the kept count and the first place that changes, which are read from the device
-// together; from then on every size is on the host.
-extern "C" int ssa_aggregator_remove_device(ssa_ctx *ctx, ssa_aggregator *ag, const uint8_t *d_drop, size_t n_bytes,
-                                            uint64_t *n_kept_out) {
-    if (int rc = agx_remove_args(ctx, ag, d_drop, n_bytes, n_kept_out)) return rc;
-    *n_kept_out = 0;
+// The removal by a byte mask on the device (the arguments checked, lanes held).  Synchronises the stream once, for the
+// kept count and the first place that changes, which are read from the device together; from then on every size is on
+// the host.  d_refuse (remove_indices; nullptr: none): a word read under the same synchronisation -- nonzero refuses the
+// call with SSA_ERR_ARG before the move begins, the object unchanged.
+static int agx_remove_masked(ssa_ctx *ctx, ssa_aggregator *ag, const uint8_t *d_drop, const u32 *d_refuse,
+                             uint64_t *n_kept_out) {
     const size_t held = ag->held;
-    if (held == 0) return SSA_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
     if (ctx->agx_kept.reserve(held * sizeof(u32)) || ctx->agx_first.reserve(sizeof(u32))) return SSA_ERR_HIP;
     u32 *d_kept = (u32 *)ctx->agx_kept.p, *d_first = (u32 *)ctx->agx_first.p;
     const u32 *d_m = nullptr;
@@ -2979,13 +2998,24 @@ extern "C" int ssa_aggregator_remove_device(ssa_ctx *ctx, ssa_aggregator *ag, co
                            (const u32 *)d_kept, d_m, held, d_first);
     });
     if (rc) return rc;
-    u32 m = 0, f = 0;
+    u32 m = 0, f = 0, refuse = 0;
     HIP_TRY(hipMemcpyAsync(&m, d_m, sizeof m, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipMemcpyAsync(&f, d_first, sizeof f, hipMemcpyDeviceToHost, ctx->stream));
+    if (d_refuse) HIP_TRY(hipMemcpyAsync(&refuse, d_refuse, sizeof refuse, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (refuse) return SSA_ERR_ARG;
     if (m > held || f > m) return SSA_ERR_HIP;        // (cannot be: the list is of `held` bytes)
     *n_kept_out = m;
     return agx_remove_apply(ag, d_kept, f, m);
+}
+
+extern "C" int ssa_aggregator_remove_device(ssa_ctx *ctx, ssa_aggregator *ag, const uint8_t *d_drop, size_t n_bytes,
+                                            uint64_t *n_kept_out) {
+    if (int rc = agx_remove_args(ctx, ag, d_drop, n_bytes, n_kept_out)) return rc;
+    *n_kept_out = 0;
+    if (ag->held == 0) return SSA_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    return agx_remove_masked(ctx, ag, d_drop, nullptr, n_kept_out);
 }
 
 extern "C" int ssa_aggregator_remove(ssa_ctx *ctx, ssa_aggregator *ag, const uint8_t *drop, size_t n_bytes,
@@ -2995,6 +3025,126 @@ extern "C" int ssa_aggregator_remove(ssa_ctx *ctx, ssa_aggregator *ag, const uin
     HostCall hc(ctx);
     const u8 *d_drop = hc.in(ctx->st_status, drop, n_bytes);
     return hc.finish([&] { return ssa_aggregator_remove_device(ctx, ag, d_drop, n_bytes, n_kept_out); });
+}
+
+// ---- a selection of held lanes in the caller's order (the gather and the validity decision:
+// agx_k_select in ssa_aggregator.hpp)
+// ctx->agx_sel_bits: the flag word, the result word of the host forms, and from byte 16 on one bit per held lane
+constexpr size_t AGX_SEL_FLAG = 0, AGX_SEL_RESULT = 4, AGX_SEL_BITS = 16;
+static size_t agx_sel_bytes(size_t held) { return AGX_SEL_BITS + 4 * ((held + 31) / 32); }
+static u32 *agx_sel_word(ssa_ctx *ctx, size_t off) { return (u32 *)((u8 *)ctx->agx_sel_bits.p + off); }
+
+// what every form of a selection refuses before anything is enqueued.  device: the list lies in device memory
+static int agx_select_args(const ssa_ctx *ctx, const ssa_aggregator *ag, const uint32_t *order, size_t m, bool device) {
+    if (!ctx || !ag || ag->ctx != ctx || m > ag->held || (m && !order)) return SSA_ERR_ARG;
+    return device && (reinterpret_cast<uintptr_t>(order) & 3u) ? SSA_ERR_ARG : 0;
+}
+static int agx_finish_select_args(const ssa_ctx *ctx, const ssa_aggregator *ag, const uint32_t *order, size_t m,
+                                  const uint8_t *agg_out, const uint8_t *keys49_out, bool device) {
+    if (int rc = agx_select_args(ctx, ag, order, m, device)) return rc;
+    return !agg_out || m > ctx->knobs.msm_slice || (keys49_out && !ag->hold_keys()) ? SSA_ERR_ARG : 0;
+}
+
+// flag, result word and the bitmap of `held` lanes, cleared on the stream: the call that uses them clears them
+static int agx_select_clear(ssa_ctx *ctx, size_t held) {
+    if (ctx->agx_sel_bits.reserve(agx_sel_bytes(held))) return SSA_ERR_HIP;
+    HIP_TRY(hipMemsetAsync(ctx->agx_sel_bits.p, 0, agx_sel_bytes(held), ctx->stream));
+    return 0;
+}
+
+// Only enqueues on the context's stream: every size it needs is on the host, and whether the list is valid is decided
+// and acted upon on the device (agx_k_select raises the flag, agx_k_select_verdict zeroes the outputs of a refused list
+// and writes *d_result_out).  Reads the object, writes workspaces of the context and the caller's buffers.  `finishes`
+// counts every call that passed the argument checks: what the device decides later is not known here.
+extern "C" int ssa_aggregator_finish_select_device(ssa_ctx *ctx, ssa_aggregator *ag, const uint32_t *d_order, size_t m,
+                                                   uint8_t *d_agg_out, uint8_t *d_keys49_out, uint32_t *d_result_out) {
+    if (int rc = agx_finish_select_args(ctx, ag, d_order, m, d_agg_out, d_keys49_out, true)) return rc;
+    if (!d_result_out) return SSA_ERR_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    ag->finishes++;
+    if (m == 0) {
+        HIP_TRY(hipMemsetAsync(d_agg_out, 0, 32, ctx->stream));
+        HIP_TRY(hipMemsetAsync(d_result_out, 0, sizeof(uint32_t), ctx->stream));
+        return SSA_OK;
+    }
+    const bool with_keys = d_keys49_out != nullptr;
+    AgxStage st{};
+    if (agx_stage_layout(ctx->agx_sel_stage, m, with_keys, &st) || ctx->agm_roots.reserve(32)) return SSA_ERR_HIP;
+    if (int rc = agx_select_clear(ctx, ag->held)) return rc;
+    u32 *d_flag = agx_sel_word(ctx, AGX_SEL_FLAG);
+    int rc = timed_launch(ctx, "agx_k_select", [&] {
+        hipLaunchKernelGGL(agx_k_select, dim3(grid_for(m, 256)), dim3(256), 0, ctx->stream, d_order, m, ag->held,
+                           agx_sel_word(ctx, AGX_SEL_BITS), d_flag, (const u64 *)ag->leaves.p, (const u64 *)ag->scal.p,
+                           (const u8 *)ag->wire.p, with_keys ? (const u8 *)ag->keys.p : (const u8 *)nullptr, st.leaves,
+                           st.scal, st.wire, st.keys);
+    });
+    if (rc) return rc;
+    // the tree over the m gathered leaves from the bottom (no stored top speaks of this order), then finish's fold
+    if ((rc = ags_root(ctx, st.leaves, m, m, (u64 *)ctx->agm_roots.p))) return rc;
+    if ((rc = agx_fold(ctx, st.scal, m))) return rc;
+    HIP_TRY(hipMemcpyAsync(d_agg_out, st.wire, 49 * m, hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(d_agg_out + 49 * m, ag_misc(ctx, AG_E), 32, hipMemcpyDeviceToDevice, ctx->stream));
+    if (with_keys) HIP_TRY(hipMemcpyAsync(d_keys49_out, st.keys, 49 * m, hipMemcpyDeviceToDevice, ctx->stream));
+    const size_t n_agg = SSA_AGGREGATE_LENGTH(m), n_keys = with_keys ? 49 * m : 0;
+    return timed_launch(ctx, "agx_k_select_verdict", [&] {
+        hipLaunchKernelGGL(agx_k_select_verdict, dim3(std::min(grid_for(n_agg, 256), 4096u)), dim3(256), 0, ctx->stream,
+                           (const u32 *)d_flag, d_agg_out, n_agg, d_keys49_out, n_keys, d_result_out);
+    });
+}
+
+// The flag comes back with the results, under the one synchronisation a host form needs anyway.
+extern "C" int ssa_aggregator_finish_select(ssa_ctx *ctx, ssa_aggregator *ag, const uint32_t *order, size_t m,
+                                            uint8_t *agg_out, uint8_t *keys49_out) {
+    if (int rc = agx_finish_select_args(ctx, ag, order, m, agg_out, keys49_out, false)) return rc;
+    HostCall hc(ctx);
+    const u32 *d_order = hc.in<u32>(ctx->agx_sel_order, order, m * sizeof(u32));
+    u8 *d_agg = hc.out(ctx->st_aux, agg_out, SSA_AGGREGATE_LENGTH(m), 16);
+    u8 *d_keys = keys49_out ? hc.out(ctx->st_aux2, keys49_out, 49 * m, 16) : nullptr;
+    // (reserved here at the size the device form asks for: the result word does not move under it)
+    if (hc.ok() && ctx->agx_sel_bits.reserve(agx_sel_bytes(ag->held))) hc.rc = SSA_ERR_HIP;
+    if (!hc.ok()) return hc.rc;
+    u32 refused = 0, *d_result = agx_sel_word(ctx, AGX_SEL_RESULT);
+    hc.copy_back(&refused, d_result, sizeof refused);
+    if (int rc = hc.finish([&] { return ssa_aggregator_finish_select_device(ctx, ag, d_order, m, d_agg, d_keys, d_result); }))
+        return rc;
+    return refused ? SSA_ERR_ARG : SSA_OK;
+}
+
+// remove with a list in place of a mask: the list is validated as a selection's (agx_k_mark), one small kernel turns the
+// bitmap into the byte mask, and from there on it is the path of remove_device -- which reads the flag under the one
+// synchronisation it makes for the kept count, before the move begins.  No slice limit: nothing here is per-slice.
+extern "C" int ssa_aggregator_remove_indices_device(ssa_ctx *ctx, ssa_aggregator *ag, const uint32_t *d_order, size_t m,
+                                                    uint64_t *n_kept_out) {
+    if (int rc = agx_select_args(ctx, ag, d_order, m, true)) return rc;
+    if (!n_kept_out) return SSA_ERR_ARG;
+    const size_t held = ag->held;
+    *n_kept_out = held;
+    if (m == 0) return SSA_OK;       // (then nothing is removed, and nothing is launched)
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (ctx->agx_sel_mask.reserve(held)) return SSA_ERR_HIP;
+    if (int rc = agx_select_clear(ctx, held)) return rc;
+    u32 *d_flag = agx_sel_word(ctx, AGX_SEL_FLAG), *d_bits = agx_sel_word(ctx, AGX_SEL_BITS);
+    u8 *d_mask = (u8 *)ctx->agx_sel_mask.p;
+    int rc = timed_launch(ctx, "agx_k_mark", [&] {
+        hipLaunchKernelGGL(agx_k_mark, dim3(grid_for(m, 256)), dim3(256), 0, ctx->stream, d_order, m, held, d_bits, d_flag);
+    });
+    if (rc) return rc;
+    rc = timed_launch(ctx, "agx_k_bits_to_mask", [&] {
+        hipLaunchKernelGGL(agx_k_bits_to_mask, dim3(grid_for(held, 256)), dim3(256), 0, ctx->stream, (const u32 *)d_bits,
+                           held, d_mask);
+    });
+    if (rc) return rc;
+    return agx_remove_masked(ctx, ag, d_mask, d_flag, n_kept_out);
+}
+
+extern "C" int ssa_aggregator_remove_indices(ssa_ctx *ctx, ssa_aggregator *ag, const uint32_t *order, size_t m,
+                                             uint64_t *n_kept_out) {
+    if (int rc = agx_select_args(ctx, ag, order, m, false)) return rc;
+    if (!n_kept_out) return SSA_ERR_ARG;
+    if (m == 0) return ssa_aggregator_remove_indices_device(ctx, ag, nullptr, 0, n_kept_out);
+    HostCall hc(ctx);
+    const u32 *d_order = hc.in<u32>(ctx->agx_sel_order, order, m * sizeof(u32));
+    return hc.finish([&] { return ssa_aggregator_remove_indices_device(ctx, ag, d_order, m, n_kept_out); });
 }
 
 // ------------------------------------------------------------------ streaming aggregate verifier (ssa_aggverifier.hpp)

@@ -208,6 +208,11 @@ struct CtxKnobs {
     /* removing lanes from a streaming aggregator: the staging of one piece of the move -- its \
        leaves, its scalars, its R's -- and the first place a mask changes.  Nothing lives in them between calls */ \
     X(agx_stage) X(agx_first) \
+    /* a selection of held lanes: the staging of the gathered lanes -- leaves, scalars, R's, \
+       keys, laid out as a piece of the move -- the flag word, the result word of the host forms and the bitmap of the \
+       lanes held (cleared by every call that uses them, never assumed clean), the list as the host forms upload it, \
+       and the byte mask remove_indices hands to the move */ \
+    X(agx_sel_stage) X(agx_sel_bits) X(agx_sel_order) X(agx_sel_mask) \
     /* the end game of ssa_k_verify, per tail group: finished pieces; parked accumulators + status (152 B per lane) */ \
     X(tail_done) X(tail_park)
 

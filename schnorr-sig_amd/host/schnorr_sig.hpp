@@ -1022,6 +1022,37 @@ class Aggregator {
         drop_front(n);
         return a;
     }
+    // A block of the producer's choosing: the aggregate of the held triples at the places
+    // order[0], order[1], ... -- distinct, below the triples held -- in THAT order: byte for byte
+    // AggregateSignature::aggregate(check = false) of those triples alone.  Changes nothing, like finish.  keys49_out (an
+    // object made with HoldKeys; any other throws): their wire keys in the same order, 49 bytes each.  A list the device
+    // refuses (an index out of range or named twice) throws, and the object is as it was.
+    AggregateSignature finish_select(const std::vector<uint32_t> &order, std::vector<uint8_t> *keys49_out = nullptr) const {
+        const size_t m = order.size();
+        AggregateSignature a;
+        a.bytes.assign(SSA_AGGREGATE_LENGTH(m), 0);
+        if (keys49_out) keys49_out->assign(m * PUBLIC_KEY_LENGTH + 1, 0);
+        const int rc = ssa_aggregator_finish_select(cx_.get(), ag_, m ? order.data() : nullptr, m, a.bytes.data(),
+                                                    keys49_out ? keys49_out->data() : nullptr);
+        if (rc != 0) throw std::runtime_error(std::string("ssa_aggregator_finish_select: ") + ssa_strerror(rc));
+        if (keys49_out) keys49_out->resize(m * PUBLIC_KEY_LENGTH);
+        return a;
+    }
+    // remove with a list in place of a mask: the named triples leave, the rest stays in arrival order -> the number kept.
+    // A list the device refuses throws and changes nothing.
+    uint64_t remove_indices(const std::vector<uint32_t> &order) {
+        uint64_t n_kept = 0;
+        const int rc = ssa_aggregator_remove_indices(cx_.get(), ag_, order.empty() ? nullptr : order.data(), order.size(), &n_kept);
+        if (rc != 0) throw std::runtime_error(std::string("ssa_aggregator_remove_indices: ") + ssa_strerror(rc));
+        return n_kept;
+    }
+    // finish_select(order), then remove_indices(order): the chosen triples leave as a block body, the rest stays for the
+    // next slot
+    AggregateSignature take_select(const std::vector<uint32_t> &order, std::vector<uint8_t> *keys49_out = nullptr) {
+        AggregateSignature a = finish_select(order, keys49_out);
+        remove_indices(order);
+        return a;
+    }
     void reset() {
         const int rc = ssa_aggregator_reset(ag_);
         if (rc != 0) throw std::runtime_error(std::string("ssa_aggregator_reset: ") + ssa_strerror(rc));
