@@ -175,7 +175,10 @@ int ssa_ctx_stream_acquire(ssa_ctx *ctx, void *producer_hip_stream);
  * stream; to select the legacy null stream pass HIP's own handle for it, hipStreamLegacy (or hipStreamPerThread). */
 int ssa_ctx_set_stream(ssa_ctx *ctx, void *hip_stream);
 /* average duration (ms) of the `ssa_k_verify` launches since the last call, measured with
- * hipEvents on the context's stream when profiling is on; resets the statistics. */
+ * hipEvents on the context's stream when profiling is on; resets the statistics.  A one-slice call that ran as two
+ * parts on two streams counts as ONE launch per key: its entry runs from the earlier start to
+ * the later end of the two launches of that kernel.  The ssa_k_hash and ssa_k_verify entries of such a call overlap
+ * by design, so they do not add up to the call's time and neither describes an exclusive launch. */
 int ssa_ctx_enable_timing(ssa_ctx *ctx, int on);
 int ssa_ctx_read_timing(ssa_ctx *ctx, const char *kernel, double *avg_ms, uint64_t *launches);
 
@@ -1519,6 +1522,20 @@ int ssa_debug_keytab_read(ssa_keyset *ks, ssa_keycache *kc, int what, uint64_t k
  * whole-pass descriptors ([q]P of the subgroup check, [h]P). */
 int ssa_debug_tail_plan(unsigned waves, unsigned pieces, unsigned gens, int uniform, unsigned min_main, size_t n,
                         uint32_t flags, uint32_t out[14]);
+/* One-slice calls of the lane kernels as two unequal parts on the context's two streams (SSA_SPLIT_FRAC, SSA_SPLIT_MIN;
+ * DESIGN.md section 33).  ssa_debug_split_plan is the host logic, no context and no device needed: for a call of n lanes
+ * with `flags`, the knobs as given (split_frac: the short part's share in 1/16ths, 0 = off; the two crossovers of the
+ * cooperative kernel; twin: a second stream exists), out[0] = nA lanes stay on the caller's stream and out[1] = nB run
+ * on the twin's: nA + nB = n, nA a multiple of 256, nB <= nA, nB = 0 when the call is not split.
+ * ssa_debug_split_config sets the knobs on this context (negative: leave that one as it is; tail_b: part B runs with an
+ * end game of its own; alone = 0: calls are split also while the process has other contexts on the device, which the
+ * tests' processes always have).  ssa_debug_split_timing reads, and leaves in place, the last entry of timing key `kernel` that a
+ * split call recorded: out[0] the span ssa_ctx_read_timing will count (earlier start to later end), out[1] and out[2]
+ * the launches of part A and part B alone, in ms; SSA_ERR_ARG when there is none. */
+int ssa_debug_split_plan(size_t n, uint32_t flags, size_t split_min, unsigned split_frac, size_t coop_max_n,
+                         size_t coop_max_n_torsion, int twin, uint64_t out[2]);
+int ssa_debug_split_config(ssa_ctx *ctx, int64_t split_min, int split_frac, int tail_b, int alone);
+int ssa_debug_split_timing(ssa_ctx *ctx, const char *kernel, double out[3]);
 /* host logic of the screened form, no context and no device needed: the plan for n signatures with coeff_bytes-wide
  * coefficients (0: library-drawn, 128-bit) at the default SSA_MSM_SLICE.  out: segments K of the first slice, lanes per
  * segment (a multiple of 256; only the last segment of a slice is ragged), window bits c, windows, windows that carry

@@ -200,6 +200,9 @@ def _load():
         "ssa_ctx_stream_acquire": (i32, [vp, vp]),
         "ssa_debug_fault_after_chunk": (i32, [vp, i32]),
         "ssa_debug_tail_plan": (i32, [u32, u32, u32, i32, u32, sz, u32, vp]),
+        "ssa_debug_split_plan": (i32, [sz, u32, sz, u32, sz, sz, i32, vp]),
+        "ssa_debug_split_config": (i32, [vp, C.c_int64, i32, i32, i32]),
+        "ssa_debug_split_timing": (i32, [vp, C.c_char_p, vp]),
         "ssa_verify_batch_screened": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz, vp, vp, u64p]),
         "ssa_verify_batch_screened_device": (i32, [vp, vp, vp, vp, vp, vp, sz, sz, sz, vp, u32, vp, vp]),
         "ssa_debug_screen_plan": (i32, [sz, u32, vp]),
@@ -1612,6 +1615,22 @@ class Engine:
                "ssa_ctx_read_timing")
         return avg.value, int(cnt.value)
 
+    def debug_split_config(self, split_min=-1, split_frac=-1, tail_b=-1, alone=-1):
+        """tests: the knobs of the one-slice split on this context (SSA_SPLIT_MIN, SSA_SPLIT_FRAC in 1/16ths with 0 = off,
+        SSA_SPLIT_TAIL_B, SSA_SPLIT_ALONE); a negative value leaves that knob as it is"""
+        _check(_lib.ssa_debug_split_config(self._ctx, int(split_min), int(split_frac), int(tail_b), int(alone)),
+               "ssa_debug_split_config")
+
+    def debug_split_timing(self, kernel):
+        """tests: (span, part A, part B) in ms of the last entry a split call recorded under `kernel`, left in place for
+        read_timing; None when there is none"""
+        out = np.zeros(3, dtype=np.float64)
+        rc = _lib.ssa_debug_split_timing(self._ctx, kernel.encode(), out.ctypes.data)
+        if rc == ERR_ARG:
+            return None
+        _check(rc, "ssa_debug_split_timing")
+        return tuple(float(v) for v in out)
+
     def host_path_probe(self, sigs_t, pks_t, msgs_t, n, reps=3):
         """PCIe-inclusive rate of the host-buffer entry point ssa_verify_many (what a Rust shim binds): the
         device tensors are copied to ordinary pageable host arrays first, then `reps` timed calls."""
@@ -2453,6 +2472,16 @@ def debug_tail_plan(waves, n, check_torsion=False, pieces=5, gens=1, uniform=Fal
         return (d & 1, bool(d & 2), bool(d & 4), (d >> 8) & 0xff, (d >> 16) & 0xff)
     return {"n_pieces": int(out[0]), "tail_groups": int(out[1]), "main_blocks": int(out[2]), "grid_blocks": int(out[3]),
             "pieces": [dec(out[4 + k]) for k in range(int(out[0]))], "whole": [dec(out[12]), dec(out[13])]}
+
+
+def debug_split_plan(n, split_frac, split_min=0, check_torsion=False, force_lane=False, coop_max_n=7680,
+                     coop_max_n_torsion=10496, twin=True):
+    """host logic of the one-slice split (no device needed): (nA, nB) for a call of n lanes; nB == 0: not split"""
+    out = np.zeros(2, dtype=np.uint64)
+    flags = (FLAG_CHECK_TORSION if check_torsion else 0) | (FLAG_FORCE_LANE if force_lane else 0)
+    _check(_lib.ssa_debug_split_plan(int(n), flags, int(split_min), int(split_frac), int(coop_max_n),
+                                     int(coop_max_n_torsion), int(bool(twin)), out.ctypes.data), "ssa_debug_split_plan")
+    return int(out[0]), int(out[1])
 
 
 def debug_screen_plan(n, coeff_bytes=0):

@@ -61,6 +61,20 @@ struct SharedGtab {
 static std::mutex g_gtab_mu;
 static std::vector<SharedGtab *> g_gtabs;
 
+// The live contexts of this process per device, twins not counted: a call is split over the two streams (DESIGN.md
+// section 33) only while its context is the one context of its device.  A process that keeps several there overlaps
+// its calls itself, and the parts of two split calls get in each other's way (profiles/r30/README.md).
+static std::mutex g_live_mu;
+static std::map<int, int> g_live_ctxs;
+static void live_ctxs_add(int device, int d) {
+    std::lock_guard<std::mutex> lock(g_live_mu);
+    g_live_ctxs[device] += d;
+}
+static int live_ctxs_on(int device) {
+    std::lock_guard<std::mutex> lock(g_live_mu);
+    return g_live_ctxs[device];
+}
+
 static inline size_t gtab_bytes(u32 bits) { return gtab_entries(bits) * 12 * sizeof(u64); }
 
 // ssa_debug_corrupt_table_builds: the next n comb builds of the process get one word flipped before their check
@@ -213,6 +227,10 @@ static void ctx_read_env(ssa_ctx *ctx, uint32_t *gtab_bits, uint64_t *hbm_budget
     env_flag("SSA_MSM_OVERLAP", k.msm_overlap);
     env_int("SSA_PIPELINE_CHUNKS", 1, 8, k.pipeline_chunks);
     env_flag("SSA_TWO_STREAMS", ctx->two_streams);
+    env_u64("SSA_SPLIT_MIN", 0, UINT64_MAX, k.split_min);            // one-slice calls below this many lanes are not split
+    env_int("SSA_SPLIT_FRAC", 0, 8, k.split_frac);                   // the short part's share in 1/16ths (0: no split)
+    env_flag("SSA_SPLIT_TAIL_B", k.split_tail_b);
+    env_flag("SSA_SPLIT_ALONE", k.split_alone);                      // 0: split also beside other contexts of the device
     uint64_t mb = 0;
     if (*hbm_budget_bytes == 0 && env_u64("SSA_HBM_BUDGET_MB", 0, UINT64_MAX, mb)) *hbm_budget_bytes = mb << 20;
     if (*gtab_bits == 0) env_one_of("SSA_GTAB_BITS", {16, 20, 22, 24}, *gtab_bits);
@@ -311,6 +329,10 @@ static int ctx_create(ssa_ctx **out, int device, const void *params, size_t para
     HIP_TRY(hipMemcpyAsync(&gen_ok, ctx->ws_fail.p, sizeof gen_ok, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     if (gen_ok != 1u) return SSA_ERR_PARAMS;
+    if (!inherit) {
+        live_ctxs_add(device, 1);
+        ctx->counted_live = true;
+    }
     *out = guard.release();
     return 0;
 }
@@ -362,6 +384,7 @@ extern "C" void ssa_ctx_destroy(ssa_ctx *ctx) {
         ssa_ctx_destroy(ctx->twin);
         ctx->twin = nullptr;
     }
+    if (ctx->counted_live) live_ctxs_add(ctx->device, -1);
     // a key set that outlives its context (garbage-collection order of a binding) must not touch the dead stream:
     // its tables are freed here, the handle stays valid for ssa_keyset_destroy and is refused everywhere else
     orphan_handles(ctx->keysets, [](ssa_keyset *ks) { ks->release_all(); });
@@ -370,10 +393,7 @@ extern "C" void ssa_ctx_destroy(ssa_ctx *ctx) {
     orphan_handles(ctx->aggregators, [](ssa_aggregator *ag) { agx_release_all(*ag); });
     orphan_handles(ctx->aggverifiers, [](ssa_aggverifier *av) { agx_release_all(*av); });
     for (auto &kv : ctx->timed)
-        for (auto &t : kv.second) {
-            (void)hipEventDestroy(t.start);
-            (void)hipEventDestroy(t.stop);
-        }
+        for (auto &t : kv.second) timed_destroy(t);
     for_each_devbuf(ctx, [](DevBuf &b) { b.release(); });
     for_each_hostbuf(ctx, [](HostBuf &b) { b.release(); });
     if (ctx->d_params) (void)hipFree(ctx->d_params);
@@ -493,7 +513,10 @@ extern "C" int ssa_ctx_read_timing(ssa_ctx *ctx, const char *kernel, double *avg
     double total = 0;
     uint64_t cnt = 0;
     // the context's own launches and, after calls of more than one slice, its twin's (whose launches overlap the
-    // context's: their event times are then not exclusive -- DESIGN.md section 5)
+    // context's: their event times are then not exclusive -- DESIGN.md section 5).  A one-slice call split over the two
+    // streams has ONE entry per key, kept by the context: the span from the earlier start to the
+    // later end of its two launches of that kernel.  The two keys of such a call overlap by design -- part B's
+    // ssa_k_verify runs under part A's ssa_k_hash -- so their times do not add up to the call's.
     for (ssa_ctx *c : {ctx, ctx->twin}) {
         if (!c) continue;
         if (c != ctx) HIP_TRY(hipStreamSynchronize(c->stream));
@@ -501,18 +524,39 @@ extern "C" int ssa_ctx_read_timing(ssa_ctx *ctx, const char *kernel, double *avg
         if (it == c->timed.end()) continue;
         for (auto &t : it->second) {
             float ms = 0;
-            if (hipEventElapsedTime(&ms, t.start, t.stop) == hipSuccess) {
+            if (timed_ms(t, &ms)) {
                 total += ms;
                 cnt++;
             }
-            (void)hipEventDestroy(t.start);
-            (void)hipEventDestroy(t.stop);
+            timed_destroy(t);
         }
         c->timed.erase(it);
     }
     if (avg_ms) *avg_ms = cnt ? total / (double)cnt : 0.0;
     if (launches) *launches = cnt;
     return 0;
+}
+
+// test hook: the last entry of `kernel` that a split call recorded, read and left in place:
+// out[0] the entry's span as ssa_ctx_read_timing will count it, out[1] part A's launch alone, out[2] part B's (ms).
+// SSA_ERR_ARG: no such entry.
+extern "C" int ssa_debug_split_timing(ssa_ctx *ctx, const char *kernel, double out[3]) {
+    if (!ctx || !kernel || !out) return SSA_ERR_ARG;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    const auto it = ctx->timed.find(kernel);
+    if (it == ctx->timed.end()) return SSA_ERR_ARG;
+    for (auto t = it->second.rbegin(); t != it->second.rend(); ++t) {
+        if (!t->start2) continue;
+        float span = 0, a = 0, b = 0;
+        if (!timed_ms(*t, &span)) return SSA_ERR_HIP;
+        HIP_TRY(hipEventElapsedTime(&a, t->start, t->stop));
+        HIP_TRY(hipEventElapsedTime(&b, t->start2, t->stop2));
+        out[0] = span;
+        out[1] = a;
+        out[2] = b;
+        return 0;
+    }
+    return SSA_ERR_ARG;
 }
 
 // ------------------------------------------------------------------ device entry points
@@ -655,25 +699,81 @@ extern "C" int ssa_debug_tail_plan(unsigned waves, unsigned pieces, unsigned gen
     return 0;
 }
 
+// A one-slice call of the lane kernels as two unequal parts on the context's two streams: part A,
+// lanes [0, nA), stays on the caller's stream and ends alone; part B, the nB lanes behind it, runs on the twin's.
+// nA + nB = n, nA is a multiple of 256 (a whole number of ssa_k_hash and ssa_k_verify workgroups: B's lanes start at a
+// workgroup of their own), nB <= nA; nB = 0: the call is not split -- the split is off (frac 0), the call is short
+// (n < min_n) or takes the cooperative kernel, or there is no second stream.
+struct SplitKnobs {
+    size_t min_n;
+    unsigned frac;       // the short part's share in 1/16ths: 1..8
+    bool coop, twin;     // the call takes the cooperative kernel; a twin is there to run part B
+};
+static void split_plan_of(const SplitKnobs &kn, size_t n, size_t *nA, size_t *nB) {
+    *nA = n;
+    *nB = 0;
+    if (kn.frac == 0 || kn.frac > 8 || kn.coop || !kn.twin || n < kn.min_n) return;
+    const size_t want_b = n / 16 * kn.frac + n % 16 * kn.frac / 16;       // n * frac / 16
+    const size_t a = (n - want_b + 255) / 256 * 256;
+    if (a >= n) return;                                                   // (nothing left behind a whole workgroup)
+    *nA = a;
+    *nB = n - a;
+}
+// the plan for explicit knobs, like ssa_debug_tail_plan (tests/test_split_plan.py): out[0] = nA, out[1] = nB
+extern "C" int ssa_debug_split_plan(size_t n, uint32_t flags, size_t split_min, unsigned split_frac, size_t coop_max_n,
+                                    size_t coop_max_n_torsion, int twin, uint64_t out[2]) {
+    if (!out) return SSA_ERR_ARG;
+    size_t nA, nB;
+    split_plan_of({split_min, split_frac, takes_coop_of(coop_max_n, coop_max_n_torsion, n, flags), twin != 0}, n, &nA, &nB);
+    out[0] = nA;
+    out[1] = nB;
+    return 0;
+}
+// test hook: the split's knobs on this context (its twin takes them at the next call); a negative value leaves a knob alone
+extern "C" int ssa_debug_split_config(ssa_ctx *ctx, int64_t split_min, int split_frac, int tail_b, int alone) {
+    if (!ctx || split_frac > 8) return SSA_ERR_ARG;
+    if (alone >= 0) ctx->knobs.split_alone = alone != 0;
+    if (split_min >= 0) ctx->knobs.split_min = (size_t)split_min;
+    if (split_frac >= 0) ctx->knobs.split_frac = (unsigned)split_frac;
+    if (tail_b >= 0) ctx->knobs.split_tail_b = tail_b != 0;
+    return 0;
+}
+
+// One ssa_k_verify launch over cnt lanes on c->stream, in two steps: verify_grid plans it (end_game: it may have one) and
+// zeroes c's end-game flags on the stream; verify_kernel is the launch itself -- the lanes' challenge scalars at d_h,
+// their tables at d_tab, the end-game buffers c's own -- for whoever times it.
+struct VerifyGrid {
+    TailPlan tp;
+    unsigned blocks;
+};
+static int verify_grid(ssa_ctx *c, size_t cnt, uint32_t flags, bool end_game, VerifyGrid *g) {
+    g->tp = end_game ? tail_plan(c, cnt, flags) : tail_plan_of({0u, 0u, 0u, c->knobs.verify_block, 0u, false, false}, cnt, flags);
+    g->blocks = grid_for(cnt, c->knobs.verify_block);
+    if (g->tp.n_pieces) {
+        if (c->tail_done.reserve(2 * (size_t)g->tp.tail_groups * sizeof(u32)) ||       // finished pieces, claimed pieces
+            c->tail_park.reserve((size_t)g->tp.tail_groups * PARK_WORDS * 64 * sizeof(u64)))
+            return SSA_ERR_HIP;
+        HIP_TRY(hipMemsetAsync(c->tail_done.p, 0, 2 * (size_t)g->tp.tail_groups * sizeof(u32), c->stream));
+        g->blocks = tail_grid_blocks(g->tp);
+    }
+    return 0;
+}
+static void verify_kernel(ssa_ctx *c, const VerifyGrid &g, const DevBatch &s, const u64 *d_h, u64 *d_tab, size_t cnt,
+                          uint32_t flags, uint8_t *d_status_out, unsigned long long *d_fail) {
+    hipLaunchKernelGGL(ssa_k_verify, dim3(g.blocks), dim3(c->knobs.verify_block), 0, c->stream, s.sigs, s.pks, s.pk_inf, d_h,
+                       (const u64 *)c->d_gtab, d_tab, cnt, flags, d_status_out, d_fail, g.tp, (u32 *)c->tail_done.p,
+                       (u64 *)c->tail_park.p);
+}
+
 // ssa_k_verify over n lanes whose challenge scalars are in d_h, in slices of at most ctx->knobs.lane_slice lanes: the 4 KB
 // per-lane table workspace never exceeds one slice (the caller has reserved it).  *d_fail is added to.
 static int verify_slices(ssa_ctx *ctx, const DevBatch &b, const u64 *d_h, size_t n, uint32_t flags, uint8_t *d_status_out,
                          unsigned long long *d_fail) {
     return for_dev_slices(b, n, ctx->knobs.lane_slice, [&](size_t lo, size_t cnt, const DevBatch &s) {
-        const TailPlan tp = tail_plan(ctx, cnt, flags);
-        unsigned blocks = grid_for(cnt, ctx->knobs.verify_block);
-        if (tp.n_pieces) {
-            if (ctx->tail_done.reserve(2 * (size_t)tp.tail_groups * sizeof(u32)) ||       // finished pieces, claimed pieces
-                ctx->tail_park.reserve((size_t)tp.tail_groups * PARK_WORDS * 64 * sizeof(u64)))
-                return SSA_ERR_HIP;
-            HIP_TRY(hipMemsetAsync(ctx->tail_done.p, 0, 2 * (size_t)tp.tail_groups * sizeof(u32), ctx->stream));
-            blocks = tail_grid_blocks(tp);
-        }
+        VerifyGrid g;
+        if (int rc = verify_grid(ctx, cnt, flags, true, &g)) return rc;
         return timed_launch(ctx, "ssa_k_verify", [&] {
-            hipLaunchKernelGGL(ssa_k_verify, dim3(blocks), dim3(ctx->knobs.verify_block), 0,
-                               ctx->stream, s.sigs, s.pks, s.pk_inf, d_h + 4 * lo, (const u64 *)ctx->d_gtab,
-                               (u64 *)ctx->ws_tab.p, cnt, flags, d_status_out + lo, d_fail, tp, (u32 *)ctx->tail_done.p,
-                               (u64 *)ctx->tail_park.p);
+            verify_kernel(ctx, g, s, d_h + 4 * lo, (u64 *)ctx->ws_tab.p, cnt, flags, d_status_out + lo, d_fail);
         });
     });
 }
@@ -698,9 +798,67 @@ static int verify_one_slice(ssa_ctx *c, const DevBatch &b, size_t cnt, uint32_t 
     return verify_slices(c, b, (const u64 *)c->ws_h.p, cnt, flags, d_status_out, d_fail);
 }
 
-// the kernels of one verification batch on ctx->stream; *d_fail is added to, not reset
+// ONE slice as two parts (split_plan_of): hash + verification of lanes [0, nA) on ctx->stream and of
+// the nB lanes behind them on tw->stream, into disjoint lane ranges of ctx's OWN ws_h and ws_tab (sized for the slice, as
+// for an unsplit call), of the one status array and into the one counter.  Of the twin only the stream and the end-game
+// buffers are used.  Stream events are the only ordering: tw->stream starts behind everything queued on ctx->stream
+// before the call, and ctx->stream continues behind both parts, on an error return too.  B's launches are queued in front
+// of A's verifier: B's short hash ends early, its verifier runs under the end of A's hash, and its ladder is resident when
+// every wave of A's first generation builds its table.  With timing on, each key gets ONE entry for its two launches.
+static int verify_split(ssa_ctx *ctx, ssa_ctx *tw, const DevBatch &b, size_t nA, size_t nB, uint32_t flags,
+                        uint8_t *d_status_out, unsigned long long *d_fail) {
+    constexpr size_t TAB_WORDS = (size_t)(PTAB_ENTRIES * PTAB_ENTRY_U64);
+    const size_t n = nA + nB;
+    if (ctx->ws_h.reserve(n * 4 * sizeof(u64)) || ctx->ws_tab.reserve(n * TAB_WORDS * sizeof(u64))) return SSA_ERR_HIP;
+    u64 *h = (u64 *)ctx->ws_h.p, *tab = (u64 *)ctx->ws_tab.p;
+    const DevBatch bB = b.slice(nA);
+    HIP_TRY(hipEventRecord(ctx->order_ev, ctx->stream));
+    HIP_TRY(hipStreamWaitEvent(tw->stream, ctx->order_ev, 0));
+    TimedLaunch th{}, tv{};
+    const bool timing = ctx->knobs.timing;
+    auto mark = [&](hipEvent_t *ev, hipStream_t st) {
+        if (!timing) return 0;
+        HIP_TRY(hipEventCreate(ev));
+        HIP_TRY(hipEventRecord(*ev, st));
+        return 0;
+    };
+    auto hash = [&](ssa_ctx *c, const DevBatch &s, size_t cnt, u64 *d_h, hipEvent_t *start, hipEvent_t *stop) {
+        if (int r = mark(start, c->stream)) return r;
+        hipLaunchKernelGGL(ssa_k_hash, dim3(grid_for(cnt, 256)), dim3(256), 0, c->stream, c->d_params, s.sigs, s.pks, s.msgs,
+                           cnt, d_h, (u8 *)nullptr, (const u32 *)nullptr, 0u);
+        HIP_TRY(hipGetLastError());
+        return mark(stop, c->stream);
+    };
+    auto verify = [&](ssa_ctx *c, const DevBatch &s, size_t lo, size_t cnt, bool end_game, hipEvent_t *start, hipEvent_t *stop) {
+        VerifyGrid g;
+        if (int r = verify_grid(c, cnt, flags, end_game, &g)) return r;
+        if (int r = mark(start, c->stream)) return r;
+        verify_kernel(c, g, s, h + 4 * lo, tab + lo * TAB_WORDS, cnt, flags, d_status_out + lo, d_fail);
+        HIP_TRY(hipGetLastError());
+        return mark(stop, c->stream);
+    };
+    int rc = hash(ctx, b, nA, h, &th.start, &th.stop);
+    if (rc == 0) rc = hash(tw, bB, nB, h + 4 * nA, &th.start2, &th.stop2);
+    if (rc == 0) rc = verify(tw, bB, nA, nB, ctx->knobs.split_tail_b, &tv.start2, &tv.stop2);
+    if (rc == 0) rc = verify(ctx, b, 0, nA, true, &tv.start, &tv.stop);
+    if (timing && rc == 0) {
+        ctx->timed["ssa_k_hash"].push_back(th);
+        ctx->timed["ssa_k_verify"].push_back(tv);
+    } else {
+        timed_destroy(th);
+        timed_destroy(tv);
+    }
+    if (hipEventRecord(tw->order_ev, tw->stream) != hipSuccess || hipStreamWaitEvent(ctx->stream, tw->order_ev, 0) != hipSuccess)
+        return rc ? rc : SSA_ERR_HIP;
+    return rc;
+}
+
+// the kernels of one verification batch on ctx->stream; *d_fail is added to, not reset.  may_split: a one-slice batch may
+// run as two parts on the two streams (verify_split) -- the EXPORTED ssa_verify_many_device alone says so, not the
+// library's own uses of it (ssa_internal_verify_many_device): the host forms drive the context and its twin from two
+// threads (run_host_slices), where nobody else may reach into the twin, and none of the other forms was measured.
 static int verify_launch(ssa_ctx *ctx, const DevBatch &b, size_t n, uint32_t flags, uint8_t *d_status_out,
-                         unsigned long long *d_fail) {
+                         unsigned long long *d_fail, bool may_split = false) {
     // small batches: one wave per signature (low latency); large ones: one lane per signature (throughput)
     if (takes_coop(ctx, n, flags)) {
         return timed_launch(ctx, "ssa_k_verify_coop", [&] {
@@ -713,7 +871,17 @@ static int verify_launch(ssa_ctx *ctx, const DevBatch &b, size_t n, uint32_t fla
     // length, src/batch.rs:31-50): a larger batch runs slice after slice, into the caller's one status array and the one
     // rejection counter.  At n <= lane_slice this is the single pair of launches it always was.
     const size_t slice = ctx->knobs.lane_slice < n ? ctx->knobs.lane_slice : n;
-    if (n <= slice) return verify_one_slice(ctx, b, n, flags, d_status_out, d_fail);
+    if (n <= slice) {
+        // one slice: two unequal parts on the two streams where the split is on, the call is long enough and the context
+        // has its device to itself (the twin is made only for such a call), otherwise the single pair of launches
+        if (may_split && ctx->knobs.split_frac && n >= ctx->knobs.split_min && (!ctx->knobs.split_alone || live_ctxs_on(ctx->device) == 1)) {
+            ssa_ctx *tw = ssa_internal_twin(ctx);
+            size_t nA, nB;
+            split_plan_of({ctx->knobs.split_min, ctx->knobs.split_frac, false, tw != nullptr}, n, &nA, &nB);
+            if (nB) return verify_split(ctx, tw, b, nA, nB, flags, d_status_out, d_fail);
+        }
+        return verify_one_slice(ctx, b, n, flags, d_status_out, d_fail);
+    }
     // More than one slice: the slices alternate between the context's stream and its twin's (a second set of
     // workspaces), so that one slice's kernels fill the tails of the other's -- ordered after everything queued on
     // ctx->stream before the call, and ctx->stream continues after both.
@@ -737,17 +905,33 @@ static int verify_launch(ssa_ctx *ctx, const DevBatch &b, size_t n, uint32_t fla
     return rc;
 }
 
+static int verify_many_device(ssa_ctx *ctx, const DevBatch &b, size_t n, uint32_t flags, uint8_t *d_status_out,
+                              uint64_t *d_n_fail_out, bool may_split) {
+    if (int rc = check_dev_batch(ctx, b, n, d_status_out)) return rc;
+    unsigned long long *d_fail;
+    if (int rc = reset_fail_counter(ctx, d_n_fail_out, &d_fail)) return rc;
+    if (n == 0) return 0;
+    return verify_launch(ctx, b, n, flags, d_status_out, d_fail, may_split);
+}
+
+// the exported call: the one place that lets a one-slice batch run as two parts (may_split)
 extern "C" int ssa_verify_many_device(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks,
                                       const uint8_t *d_pk_inf, const uint8_t *d_msgs,
                                       const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len,
                                       size_t n, uint32_t flags, uint8_t *d_status_out,
                                       uint64_t *d_n_fail_out) {
-    const DevBatch b{d_sigs, d_pks, d_pk_inf, {d_msgs, d_msg_off, msg_stride, msg_len}};
-    if (int rc = check_dev_batch(ctx, b, n, d_status_out)) return rc;
-    unsigned long long *d_fail;
-    if (int rc = reset_fail_counter(ctx, d_n_fail_out, &d_fail)) return rc;
-    if (n == 0) return 0;
-    return verify_launch(ctx, b, n, flags, d_status_out, d_fail);
+    return verify_many_device(ctx, {d_sigs, d_pks, d_pk_inf, {d_msgs, d_msg_off, msg_stride, msg_len}}, n, flags,
+                              d_status_out, d_n_fail_out, true);
+}
+
+// ssa_verify_many_device as the one-slice worker of the library's other forms (the keyed records, host and device; the
+// small batches of the screened forms): the same checks and launches, never split -- those forms were not measured, and
+// the host ones drive the context and its twin from two threads
+int ssa_internal_verify_many_device(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_pk_inf,
+                                    const uint8_t *d_msgs, const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len,
+                                    size_t n, uint32_t flags, uint8_t *d_status_out, uint64_t *d_n_fail_out) {
+    return verify_many_device(ctx, {d_sigs, d_pks, d_pk_inf, {d_msgs, d_msg_off, msg_stride, msg_len}}, n, flags,
+                              d_status_out, d_n_fail_out, false);
 }
 
 // the throughput (variable-time) signer's launch; arguments checked by the caller (ssa_sign.hip)
@@ -912,8 +1096,8 @@ static int verify_keyed_host_one(ssa_ctx *ctx, const uint8_t *keyed, const HostB
     unsigned long long nf = 0, *d_fail = (unsigned long long *)ctx->ws_fail.p;
     hc.copy_back(&nf, d_fail, sizeof nf);
     if (int rc = hc.finish([&] {
-            return ssa_verify_many_device(ctx, d_sigs, d_pks, d_inf, mv.msgs, mv.off, b.msg_stride, b.msg_len, n, flags,
-                                          d_status, (uint64_t *)d_fail);
+            return ssa_internal_verify_many_device(ctx, d_sigs, d_pks, d_inf, mv.msgs, mv.off, b.msg_stride, b.msg_len, n, flags,
+                                                   d_status, (uint64_t *)d_fail);
         }))
         return rc;
     if (n_fail_out) *n_fail_out = nf;

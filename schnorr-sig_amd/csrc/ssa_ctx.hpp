@@ -93,8 +93,11 @@ struct HostBuf {
     }
 };
 
+// one entry of a timing key.  A call split over the two streams records ONE entry for its two
+// launches of a kernel: start2 / stop2 are the second launch's, and the entry runs from the earlier start to the later stop
 struct TimedLaunch {
     hipEvent_t start, stop;
+    hipEvent_t start2 = nullptr, stop2 = nullptr;
 };
 
 // key dedup defaults: keyed route when u < ratio * lanes, without / with the subgroup check
@@ -132,6 +135,16 @@ struct CtxKnobs {
     unsigned tail_min_main = 0;   // SSA_TAIL_MIN_MAIN: generations of ordinary workgroups a launch must have beside its tail
     unsigned tail_waves_override = 0;   // SSA_TAIL_WAVES: the tests' small "generation" (the end game on batches of thousands)
     bool timing = false;          // ssa_ctx_enable_timing
+    // A one-slice call of the lane kernels as two UNEQUAL parts on the context's two streams: the
+    // short part B = split_frac sixteenths of the lanes runs on the twin's stream, its verifier under the end of the long
+    // part's hash and its ladder under the long part's first table builds; the long part ends alone, with the end game.
+    // Measured (profiles/r30/README.md): 2/16 gains 0.1-0.9 ms at every size tried from 2^19 to 2^20 lanes (-0.43 ms at
+    // 2^20) and loses at 2^18 and below; an end game of B's own costs what the split brings.
+    size_t split_min = (size_t)1 << 19;   // SSA_SPLIT_MIN: one-slice calls of fewer lanes are not split
+    unsigned split_frac = 2;      // SSA_SPLIT_FRAC: the short part's share in 1/16ths, 1..8 (0: no call is split)
+    bool split_tail_b = false;    // SSA_SPLIT_TAIL_B=1: the short part runs with an end game of its own when it is long enough
+    bool split_alone = true;      // SSA_SPLIT_ALONE=0: split also while the process has other contexts on the device (two
+                                  //   contexts that each split their half of a batch lose 1.0-1.5 ms per batch)
     unsigned screen_segs = 0;     // segments per slice of the screened forms forced by ssa_debug_screen_segments (0 = automatic)
     // a slice takes the keyed route when u < dedup_ratio[subgroup check on] * lanes: the measured thresholds of DESIGN.md
     // section 14 (without the check the keyed route never paid, with it always but for all-distinct keys);
@@ -243,6 +256,7 @@ struct ssa_ctx {
     ssa_ctx *twin = nullptr;                  // second set of streams and workspaces: calls of more than one slice
                                               //   alternate their slices between the two (created at the first such call)
     bool is_twin = false, two_streams = true; // SSA_TWO_STREAMS=0 turns the alternation off
+    bool counted_live = false;                // counted among the live contexts of its device (ssa_api.hip: live_ctxs_on)
 #define X(name) DevBuf name;
     SSA_CTX_DEVBUFS(X)
 #undef X
@@ -370,6 +384,24 @@ static inline int timed_launch(ssa_ctx *ctx, const char *name, F &&launch) {
     return 0;
 }
 
+// what an entry measured, in ms: stop - start, or for the two launches of a split call the span from the earlier start to
+// the later stop -- the largest of the four differences (events of two streams of one device compare); false: not measurable
+static inline bool timed_ms(const TimedLaunch &t, float *ms) {
+    if (hipEventElapsedTime(ms, t.start, t.stop) != hipSuccess) return false;
+    if (!t.start2) return true;
+    for (hipEvent_t s : {t.start, t.start2})
+        for (hipEvent_t e : {t.stop, t.stop2}) {
+            float d = 0;
+            if (hipEventElapsedTime(&d, s, e) != hipSuccess) return false;
+            if (d > *ms) *ms = d;
+        }
+    return true;
+}
+static inline void timed_destroy(TimedLaunch &t) {
+    for (hipEvent_t ev : {t.start, t.stop, t.start2, t.stop2})
+        if (ev) (void)hipEventDestroy(ev);
+}
+
 
 // ---- argument checks and host->device staging shared by the entry points ----
 static inline int check_msgs(const MsgView &mv, size_t n) {
@@ -462,9 +494,12 @@ static inline int check_dev_batch(const ssa_ctx *ctx, const DevBatch &b, size_t 
 
 // small batches take the cooperative kernel (one wave per signature: low latency), large ones the lane kernels (one lane
 // per signature: throughput).  The host forms stage their inputs by this answer and the device forms launch by it.
-static inline bool takes_coop(const ssa_ctx *ctx, size_t n, uint32_t flags) {
-    const size_t coop_lim = (flags & SSA_FLAG_CHECK_TORSION) ? ctx->knobs.coop_max_n_torsion : ctx->knobs.coop_max_n;
+static inline bool takes_coop_of(size_t coop_max_n, size_t coop_max_n_torsion, size_t n, uint32_t flags) {
+    const size_t coop_lim = (flags & SSA_FLAG_CHECK_TORSION) ? coop_max_n_torsion : coop_max_n;
     return (flags & SSA_FLAG_FORCE_COOP) || (!(flags & SSA_FLAG_FORCE_LANE) && n <= coop_lim);
+}
+static inline bool takes_coop(const ssa_ctx *ctx, size_t n, uint32_t flags) {
+    return takes_coop_of(ctx->knobs.coop_max_n, ctx->knobs.coop_max_n_torsion, n, flags);
 }
 
 // the statistics words an entry point reports (`width` of them: 4 for the dedup, 8 screened, 12 with a key cache), summed
@@ -875,6 +910,12 @@ int ssa_internal_screen_keyed_hashed(ssa_ctx *ctx, struct ssa_keycache *kc, cons
 // d_h (the per-lane workspace reserved for one slice of lanes); *d_fail is added to
 int ssa_internal_verify_hashed(ssa_ctx *ctx, const DevBatch &b, const uint64_t *d_h, size_t n, uint32_t flags,
                                uint8_t *d_status_out, unsigned long long *d_fail);
+
+// defined in ssa_api.hip: ssa_verify_many_device for the library's own use -- the same call, but a one-slice batch is
+// never split over the two streams (only the exported entry point may)
+int ssa_internal_verify_many_device(ssa_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_pk_inf,
+                                    const uint8_t *d_msgs, const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len,
+                                    size_t n, uint32_t flags, uint8_t *d_status_out, uint64_t *d_n_fail_out);
 
 // defined in ssa_api.hip, for ssa_verify_many_screened (ssa_msm.hip): the distinct keys of one slice of at most
 // ctx->knobs.lane_slice lanes checked once each (ctx->dd_idx, ctx->dd_kstatus, tables in ctx->ws_tab; one synchronisation, for

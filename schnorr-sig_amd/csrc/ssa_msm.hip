@@ -1697,8 +1697,8 @@ static int screen_slice(ssa_ctx *ctx, const DevBatch &b, size_t n, const uint8_t
     unsigned long long *scratch_fail = (unsigned long long *)ctx->scr_fail.p;    // (the caller counts the statuses)
     if (n <= ctx->knobs.msm_small_max) {      // the exact per-lane path
         if (d_h) return ssa_internal_verify_hashed(ctx, b, d_h, n, SSA_FLAG_SIG_FLAG_BYTE, d_status, scratch_fail);
-        return ssa_verify_many_device(ctx, b.sigs, b.pks, b.pk_inf, b.msgs.msgs, b.msgs.off, b.msgs.stride, b.msgs.len, n,
-                                      SSA_FLAG_SIG_FLAG_BYTE, d_status, (uint64_t *)scratch_fail);
+        return ssa_internal_verify_many_device(ctx, b.sigs, b.pks, b.pk_inf, b.msgs.msgs, b.msgs.off, b.msgs.stride, b.msgs.len, n,
+                                               SSA_FLAG_SIG_FLAG_BYTE, d_status, (uint64_t *)scratch_fail);
     }
     const ScreenPlan pl = screen_plan(n, ctx->knobs.screen_segs);
     if (ctx->scr_ok.reserve(SCREEN_MAX_SEGS)) return SSA_ERR_HIP;
@@ -1766,8 +1766,8 @@ extern "C" int ssa_verify_batch_screened_device(ssa_ctx *ctx, const uint8_t *d_s
     if (int rc = reset_fail_counter(ctx, d_n_fail_out, &d_fail)) return rc;
     if (n == 0) return 0;
     if (n <= ctx->knobs.msm_small_max)
-        return ssa_verify_many_device(ctx, d_sigs, d_pks, d_pk_inf, d_msgs, d_msg_off, msg_stride, msg_len, n,
-                                      SSA_FLAG_SIG_FLAG_BYTE, d_status_out, (uint64_t *)d_fail);
+        return ssa_internal_verify_many_device(ctx, d_sigs, d_pks, d_pk_inf, d_msgs, d_msg_off, msg_stride, msg_len, n,
+                                               SSA_FLAG_SIG_FLAG_BYTE, d_status_out, (uint64_t *)d_fail);
     // (segments never straddle two slices)
     if (int rc = for_dev_slices(b, n, ctx->knobs.msm_slice, [&](size_t lo, size_t cnt, const DevBatch &s) {
             return screen_slice(ctx, s, cnt, d_coeffs ? d_coeffs + (size_t)coeff_bytes * lo : nullptr, coeff_bytes, nullptr,
@@ -1832,8 +1832,8 @@ static int screen_many_slice(ssa_ctx *ctx, const DevBatch &b, size_t n, const ui
     if (n <= ctx->knobs.msm_small_max) {      // the exact per-lane path, the caller's flags
         sv[6] = 1;
         const int rc = d_h ? ssa_internal_verify_hashed(ctx, b, d_h, n, flags, d_status, scratch_fail)
-                           : ssa_verify_many_device(ctx, b.sigs, b.pks, b.pk_inf, b.msgs.msgs, b.msgs.off, b.msgs.stride,
-                                                    b.msgs.len, n, flags, d_status, (uint64_t *)scratch_fail);
+                           : ssa_internal_verify_many_device(ctx, b.sigs, b.pks, b.pk_inf, b.msgs.msgs, b.msgs.off, b.msgs.stride,
+                                                             b.msgs.len, n, flags, d_status, (uint64_t *)scratch_fail);
         if (rc == 0 && stats) stats->add(sv);
         return rc;
     }
@@ -1957,8 +1957,8 @@ static int many_screened_device(ssa_ctx *ctx, ssa_keycache *kc, const DevBatch &
     if (int rc = reset_fail_counter(ctx, d_n_fail_out, &d_fail)) return rc;
     if (n == 0) return 0;
     if (n <= ctx->knobs.msm_small_max) {
-        const int rc = ssa_verify_many_device(ctx, b.sigs, b.pks, b.pk_inf, b.msgs.msgs, b.msgs.off, b.msgs.stride,
-                                              b.msgs.len, n, flags, d_status_out, (uint64_t *)d_fail);
+        const int rc = ssa_internal_verify_many_device(ctx, b.sigs, b.pks, b.pk_inf, b.msgs.msgs, b.msgs.off, b.msgs.stride,
+                                                       b.msgs.len, n, flags, d_status_out, (uint64_t *)d_fail);
         if (rc == 0 && stats_out) stats_out[6] = 1;
         return rc;
     }
@@ -2105,8 +2105,8 @@ static int keyed_exact_slice(ssa_ctx *ctx, const uint8_t *d_keyed, const MsgView
         if (int rc = keyed_hash_slice(ctx, b, n, *sh)) return rc;
         return ssa_internal_verify_hashed(ctx, b, sh->h, n, flags, d_status, d_fail);
     }
-    return ssa_verify_many_device(ctx, b.sigs, b.pks, b.pk_inf, mv.msgs, mv.off, mv.stride, mv.len, n, flags, d_status,
-                                  (uint64_t *)d_fail);
+    return ssa_internal_verify_many_device(ctx, b.sigs, b.pks, b.pk_inf, mv.msgs, mv.off, mv.stride, mv.len, n, flags, d_status,
+                                           (uint64_t *)d_fail);
 }
 
 // check_dev_batch for records: the argument checks of the device forms, before anything is zeroed or enqueued
