@@ -1376,8 +1376,8 @@ int ssa_debug_aggregator_remove_plan(uint64_t held, uint64_t first_changed, uint
  * byte, and the top of every complete block of block_lanes leaves.  finish pays one permutation and one multiplication
  * per lane, the bucket MSM and the exact comparison.  It belongs to the context it was created on, like a key cache.
  *   create   capacity: 1 .. SSA_MAX_BATCH lanes; block_lanes: 0 (the default, 512) or a power of two from 2 to 512;
- *            flags: 0.  Anything else: SSA_ERR_ARG.  All device memory is allocated here -- 96 + 96 + 32 + 32 + 1 + 1
- *            bytes per lane and 32 bytes per block: about 258 bytes per lane -- and is the object's own: destroy releases it,
+ *            flags: 0.  Anything else: SSA_ERR_ARG.  All device memory is allocated here -- 96 + 96 + 32 + 32 + 1 + 1 + 1
+ *            bytes per lane and 32 bytes per block: about 259 bytes per lane -- and is the object's own: destroy releases it,
  *            or ssa_ctx_destroy (the handle then stays valid for destroy and is refused everywhere else).
  *   push     n R's at stride 49 (the aggregate's wire layout), their keys, pk_inf (may be NULL) and messages, as
  *            ssa_verify_aggregate takes them.  ALL n lanes are appended: a validator cannot drop a lane, its place is
@@ -1401,7 +1401,7 @@ int ssa_debug_aggregator_remove_plan(uint64_t held, uint64_t first_changed, uint
  * Through a key cache, subgroup check included.  The plain push verifies under verify_batch
  * semantics: a key P + T with T of small order can pass.  The cached pushes put the key cache of sections 16, 18, 19 and
  * 23 in front: every distinct key is checked (limbs, curve, [q]P) once and then found, a wire key is decompressed once,
- * and the object keeps ONE MORE byte per lane, the key's status (258 bytes per lane in all).
+ * and the object keeps ONE MORE byte per lane, the key's status.
  *   push_cached(_device)       n affine keys (96 bytes each, optional pk_inf), an affine cache;
  *   push_cached_wire(_device)  n dense 49-byte keys, a cache made with SSA_KEYCACHE_WIRE: the host form uploads 49
  *                              bytes per key instead of 97, and U (section 23) is what ssa_decompress_many gives.
@@ -1458,6 +1458,54 @@ int ssa_aggverifier_push_cached_wire_device(ssa_ctx *ctx, ssa_aggverifier *av, s
 /* tests: the lanes of key statuses one workgroup of finish's fold takes (AGV_KST_SPAN): its edges are where a fold of a
  * long prefix can lose a byte */
 size_t ssa_debug_aggverifier_key_span(void);
+
+/* ---- a block against the pool: known lanes by scalar, the rest by MSM ----
+ * A validator that follows a chain holds most lanes of an incoming block already: it received, screened and admitted
+ * them into an ssa_aggregator, which keeps each lane's leaf and scalar s_i.  For a lane with s_i G = R_i + h_i P_i
+ * established, the term a_i (R_i + h_i P_i) of the aggregate's equation is [a_i s_i]G, so
+ *     [e_agg - S]G = sum over the unknown lanes of a_i (R_i + h_i P_i),   S = sum over the known lanes of a_i s_i mod q.
+ * A known lane costs a gather of 64 bytes, its share of the tree and one coefficient permutation; only the unknown
+ * lanes pay the challenge hash, the decompression and the MSM.
+ *   push_mixed   appends n lanes.  places[i] is SSA_AGGV_UNKNOWN or a place < held of `ag`, a streaming aggregator of
+ *                the same context.  The u unknown lanes come with the call, side by side in block order -- R's at stride
+ *                49, keys, pk_inf (may be NULL), messages, exactly as ssa_aggverifier_push takes them -- and are
+ *                treated exactly as that call treats them.  A known lane takes the leaf and the scalar of the pool's
+ *                lane, COPIED: a later remove or drop_front on the pool does not reach the verifier.  It holds the
+ *                (0, 0) rows, no "failed a check" mark and key status "not checked" (the pool's cached push checked its
+ *                key on admission).  A place may be named more than once.  push_known is the case u == 0.
+ *   finish       unchanged in signature; for a prefix that holds a known lane it answers what ssa_verify_aggregate
+ *                answers for the block in which every known lane is replaced by the (R, key, message) the pool admitted
+ *                it with, PROVIDED every known lane's stored scalar satisfies its own verification equation.
+ * THE CONTRACT IS THE CALLER'S.  Lanes admitted by a screened or cached push of the aggregator meet it; a lane pushed
+ * with SSA_AGGR_NO_SCREEN is the caller's own word.  A wrong stored scalar makes honest blocks fail, and somebody who
+ * knows of such a lane in a validator's pool could craft a block that this path accepts and ssa_verify_aggregate
+ * refuses.  Do not name such lanes as known.
+ * Host forms: SSA_ERR_ARG, the object unchanged, for a place >= ag->held that is not the sentinel, u different from the
+ * number of sentinels, objects of different contexts or orphaned, n > capacity - held, n or u above the context's MSM
+ * slice, bad message arguments, NULL objects, a NULL list with n != 0.
+ * _device forms: only enqueue, never synchronise.  d_places (4-byte aligned) and *d_result_out (required) are DEVICE
+ * memory; u is the caller's (the size of its compact arrays).  The device decides whether the list is valid and fails
+ * closed: a place out of range holds a lane marked as failed, a sentinel count other than u marks every lane of the
+ * push so, *d_result_out becomes 1 (0 for a valid list), and every finish whose prefix reaches such a lane answers
+ * SSA_MALFORMED.  The lanes are appended either way: reset the object after a refused push.
+ * ssa_debug_aggverifier_record gives the record of the prefix's unknown lanes alone (SSA_ERR_ARG when it has none);
+ * ssa_debug_aggverifier_known_sum writes S of the first n_take lanes, 32 bytes little-endian, to DEVICE memory (zero
+ * without a known lane).  An object that never sees a mixed push enqueues exactly what it did before these entry points
+ * existed; it holds one more byte per lane (259 in all).
+ * NOT here: mixed pushes through a key cache, a per-lane "was screened" bit in the aggregator, ssa_multi forms, known
+ * lanes taken from another verifier. */
+#define SSA_AGGV_UNKNOWN 0xFFFFFFFFu
+int ssa_aggverifier_push_mixed(ssa_ctx *ctx, ssa_aggverifier *av, ssa_aggregator *ag, const uint32_t *places, size_t n,
+                               const uint8_t *rs49, const uint8_t *pks, const uint8_t *pk_inf, const uint8_t *msgs,
+                               const uint64_t *msg_off, size_t msg_stride, size_t msg_len, size_t u);
+int ssa_aggverifier_push_mixed_device(ssa_ctx *ctx, ssa_aggverifier *av, ssa_aggregator *ag, const uint32_t *d_places,
+                                      size_t n, const uint8_t *d_rs49, const uint8_t *d_pks, const uint8_t *d_pk_inf,
+                                      const uint8_t *d_msgs, const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len,
+                                      size_t u, uint32_t *d_result_out);
+int ssa_aggverifier_push_known(ssa_ctx *ctx, ssa_aggverifier *av, ssa_aggregator *ag, const uint32_t *places, size_t m);
+int ssa_aggverifier_push_known_device(ssa_ctx *ctx, ssa_aggverifier *av, ssa_aggregator *ag, const uint32_t *d_places,
+                                      size_t m, uint32_t *d_result_out);
+int ssa_debug_aggverifier_known_sum(ssa_ctx *ctx, ssa_aggverifier *av, size_t n_take, uint8_t *d_s32_out);
 
 /* ---- ABI version -------------------------------------------------------------------------------------------
  * Bumped whenever an exported signature changes (round 2 inserted pk_inf into the batch entry points under the same

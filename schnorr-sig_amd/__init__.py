@@ -333,6 +333,11 @@ def _load():
         "ssa_aggverifier_push_cached_wire": (i32, [vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, vp]),
         "ssa_aggverifier_push_cached_wire_device": (i32, [vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, vp]),
         "ssa_debug_aggverifier_key_span": (sz, []),
+        "ssa_aggverifier_push_mixed": (i32, [vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, sz, sz, sz]),
+        "ssa_aggverifier_push_mixed_device": (i32, [vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, sz, sz, sz, vp]),
+        "ssa_aggverifier_push_known": (i32, [vp, vp, vp, vp, sz]),
+        "ssa_aggverifier_push_known_device": (i32, [vp, vp, vp, vp, sz, vp]),
+        "ssa_debug_aggverifier_known_sum": (i32, [vp, vp, sz, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)      # AttributeError here == ABI symbol missing: fail loudly
@@ -646,7 +651,7 @@ class Engine:
 
     def aggregate_verifier(self, capacity, block_lanes=0):
         """a streaming aggregate verifier of `capacity` lanes on this engine's device: push the
-        R's, keys and messages of a block body as they arrive, finish with e_agg.  All of its device memory, about 258
+        R's, keys and messages of a block body as they arrive, finish with e_agg.  All of its device memory, about 259
         bytes per lane, is allocated here.  block_lanes: 0 (512) or a power of two from 2 to 512."""
         h = C.c_void_p()
         _check(_lib.ssa_aggverifier_create(self._ctx, int(capacity), int(block_lanes), 0, C.byref(h)),
@@ -1893,6 +1898,42 @@ def _order_u32(order):
     return np.ascontiguousarray(a, dtype=np.uint32)
 
 
+AGGV_UNKNOWN = 0xFFFFFFFF      # SSA_AGGV_UNKNOWN: the lane comes with the call, not from the pool
+
+
+def _places_u32(places):
+    """the places of a mixed push (any integer sequence or array; None or -1: an unknown lane) as the contiguous uint32
+    array the ABI takes, AGGV_UNKNOWN for the unknown ones; ValueError, before any call, for values that are no
+    integers or do not fit"""
+    if isinstance(places, np.ndarray) and places.dtype == np.uint32 and places.ndim == 1 and places.flags.c_contiguous:
+        return places
+    if isinstance(places, np.ndarray):
+        if places.ndim != 1 or places.dtype.kind not in "iu":
+            raise ValueError("places is a one-dimensional sequence of integers")
+        vals = places.astype(object).tolist() if places.size else []
+    else:
+        vals = list(places)
+    out = np.empty(len(vals), dtype=np.uint32)
+    for i, v in enumerate(vals):
+        if v is None:
+            v = AGGV_UNKNOWN
+        elif isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise ValueError("places holds integers, None or -1")
+        v = int(v)
+        if v == -1:
+            v = AGGV_UNKNOWN
+        if v < 0 or v > 0xFFFFFFFF:
+            raise ValueError("places holds places of a pool's lanes, 0 .. 2^32 - 2, and None or -1 for an unknown lane")
+        out[i] = v
+    return out
+
+
+def _dev_result(d_result, engine):
+    if (str(getattr(d_result, "dtype", None)) not in ("torch.int32", "torch.uint32") or d_result.numel() < 1
+            or not d_result.is_contiguous() or not _on_device(d_result, engine)):
+        raise ValueError("d_result is one 32-bit integer on the engine's device")
+
+
 def _on_device(t, engine):
     """the tensor lies on the engine's GPU"""
     dev = getattr(t, "device", None)
@@ -2317,6 +2358,68 @@ class AggregateVerifier(_LaneStore):
                "ssa_debug_aggverifier_record")
         self.engine.sync()
         return d_rec.cpu().numpy().view(np.uint64)
+
+    # ---- a block against the pool
+    def push_mixed(self, aggregator, places, rs49, pks, msgs, offsets=None, pk_inf=None, engine=None):
+        """n lanes of a block, most of them held by `aggregator` (an Aggregator of the same Engine) already: places[i]
+        is the pool's place of lane i, or None / -1 for a lane the pool does not hold.  The u unknown lanes come with
+        the call, side by side in block order (rs49, pks, msgs, pk_inf as push() takes them) and are treated as
+        push() treats them; a known lane takes leaf and scalar from the pool, copied.  finish() then answers as for
+        the block with every known lane replaced by what the pool admitted it with -- PROVIDED the pool's scalar of
+        every known lane satisfies its verification equation: name only lanes admitted by a screened or cached push.
+        An invalid list (a place not held, a count of unknown lanes other than u) raises and changes nothing.
+        engine: tests.  Returns n."""
+        places = _places_u32(places)
+        n = int(places.size)
+        eng = engine or self.engine
+        u, batch, keep = eng._agg_batch(rs49, 49, pks, msgs, offsets, pk_inf)
+        _check(_lib.ssa_aggverifier_push_mixed(eng._ctx, self.handle, aggregator.handle if aggregator is not None else None,
+                                               _ptr(places) if n else None, n, *batch), "ssa_aggverifier_push_mixed")
+        return n
+
+    def push_known(self, aggregator, places, engine=None):
+        """push_mixed without unknown lanes: every lane of the block is held by the pool.  Returns n."""
+        places = _places_u32(places)
+        n = int(places.size)
+        _check(_lib.ssa_aggverifier_push_known((engine or self.engine)._ctx, self.handle,
+                                               aggregator.handle if aggregator is not None else None,
+                                               _ptr(places) if n else None, n), "ssa_aggverifier_push_known")
+        return n
+
+    def push_mixed_device(self, aggregator, d_places, d_result, d_rs49, d_pks, d_msgs, d_pk_inf=None, d_offsets=None,
+                          msg_len=None, msg_stride=None):
+        """device form: only enqueues on the engine's stream.  d_places: an int32 / uint32-valued tensor of n places on
+        the engine's device (AGGV_UNKNOWN, or -1 as int32, for an unknown lane); the u unknown lanes as push_device
+        takes them (u = the rows of d_pks; None: no unknown lane).  d_result (one int32 on the device) receives 0 for a
+        valid list, 1 for a refused one, whose lanes are held as failed: every finish that reaches one answers MALFORMED.
+        Returns n."""
+        n = _dev_order(d_places, self.engine)
+        _dev_result(d_result, self.engine)
+        u = 0 if d_pks is None else int(d_pks.shape[0])
+        stride, mlen = _dev_msg_shape(d_msgs, d_offsets, msg_len, msg_stride, no_msgs_ok=True) if u else (0, 0)
+        _check(_lib.ssa_aggverifier_push_mixed_device(
+            self.engine._ctx, self.handle, aggregator.handle, _addr(d_places), n, _addr(d_rs49), _addr(d_pks), _addr(d_pk_inf),
+            _addr(d_msgs), _addr(d_offsets), stride, mlen, u, d_result.data_ptr()), "ssa_aggverifier_push_mixed_device")
+        return n
+
+    def push_known_device(self, aggregator, d_places, d_result):
+        """device form of push_known.  Returns n."""
+        n = _dev_order(d_places, self.engine)
+        _dev_result(d_result, self.engine)
+        _check(_lib.ssa_aggverifier_push_known_device(self.engine._ctx, self.handle, aggregator.handle, _addr(d_places), n,
+                                                      d_result.data_ptr()), "ssa_aggverifier_push_known_device")
+        return n
+
+    def known_sum(self, n_take=None):
+        """tests: S = sum a_i s_i mod q over the known lanes of the first n_take held lanes (None: all) as a Python
+        integer (ssa_debug_aggverifier_known_sum); 0 without a known lane"""
+        import torch
+        d_s = torch.zeros(32, dtype=torch.uint8, device="cuda:%d" % self.engine.device)
+        torch.cuda.synchronize(d_s.device)      # (the engine's stream is not torch's)
+        _check(_lib.ssa_debug_aggverifier_known_sum(self.engine._ctx, self.handle, _n_take(n_take), d_s.data_ptr()),
+               "ssa_debug_aggverifier_known_sum")
+        self.engine.sync()
+        return int.from_bytes(d_s.cpu().numpy().tobytes(), "little")
 
 
 class SignerSet:

@@ -333,6 +333,25 @@ agx_k_select_verdict(const u32 *__restrict__ flag, u8 *__restrict__ agg, size_t 
 // it and the workgroup sums: partials[b] = sum over workgroup b of a_i e_i mod q.  The coefficients never travel through
 // memory.
 // scal: the piece's scalars, four words per lane.
+// (the lane's term, a_place e mod q with e the four words at `scal4`, is agx_coeff_term: the known fold of the streaming
+// aggregate verifier, agv_k_known_fold in ssa_aggverifier.hpp, sums the same term over the lanes it took from a pool)
+SSA_DEV sc256 agx_coeff_term(u64 *A, const DevParams *__restrict__ prm, const u64 *__restrict__ root, u64 place,
+                             const u64 *__restrict__ scal4) {
+    u64 in[8], d[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) in[k] = root[k];
+    in[4] = place;
+    in[5] = AG_TAG_COEFF;
+    in[6] = in[7] = 0;
+    ag_hash8(A, prm, in, 6u, d);
+    sc256 a, e;
+    ag_coeff_of_digest(d, a.w[0], a.w[1]);
+    a.w[2] = a.w[3] = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) e.w[k] = scal4[k];
+    return sc_mul_mod(a, e);
+}
+
 __global__ void __launch_bounds__(256, 4)
 agx_k_coeff_fold(const DevParams *__restrict__ prm, const u64 *__restrict__ root, const u64 *__restrict__ scal, size_t n,
                  u64 lane0, u64 *__restrict__ partials) {
@@ -343,21 +362,7 @@ agx_k_coeff_fold(const DevParams *__restrict__ prm, const u64 *__restrict__ root
     sc256 ae;
 #pragma unroll
     for (int k = 0; k < 4; k++) ae.w[k] = 0;
-    if (i < n) {
-        u64 in[8], d[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) in[k] = root[k];
-        in[4] = lane0 + (u64)i;
-        in[5] = AG_TAG_COEFF;
-        in[6] = in[7] = 0;
-        ag_hash8(A, prm, in, 6u, d);
-        sc256 a, e;
-        ag_coeff_of_digest(d, a.w[0], a.w[1]);
-        a.w[2] = a.w[3] = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) e.w[k] = scal[4 * i + k];
-        ae = sc_mul_mod(a, e);
-    }
+    if (i < n) ae = agx_coeff_term(A, prm, root, lane0 + (u64)i, scal + 4 * i);
     ag_block_sum(red, ae);
     if (threadIdx.x == 0) {
 #pragma unroll

@@ -3346,7 +3346,8 @@ extern "C" int ssa_aggverifier_reset(ssa_aggverifier *av) {
     if (!av || !av->ctx) return SSA_ERR_ARG;
     av->held = 0;
     av->pushes = av->pushed = av->finishes = av->cached = 0;
-    av->keyed = false;
+    av->keyed = av->mixed = false;
+    av->mixed_pushes.clear();
     return 0;
 }
 
@@ -3395,6 +3396,8 @@ static int agv_push_body(ssa_ctx *ctx, ssa_aggverifier *av, const u8 *d_rs49, co
         if ((rc = agx_reduce_blocks(*av, p))) return rc;
     // a plain push into a keyed object: its lanes' keys are "not checked"
     if (av->keyed && !through_cache) HIP_TRY(hipMemsetAsync((u8 *)av->kst.p + av->held, 0, n, ctx->stream));
+    // a push that took no lane from a pool into an object that holds such lanes: none of its lanes is known
+    if (av->mixed) HIP_TRY(hipMemsetAsync((u8 *)av->known.p + av->held, 0, n, ctx->stream));
     // (only now: a launch that could not be enqueued leaves the object as it was -- what it wrote lies behind `held`)
     av->held += n;
     av->pushes++;
@@ -3457,6 +3460,102 @@ static int agv_record(ssa_ctx *ctx, const ssa_aggverifier *av, size_t n, u64 *d_
     return k == 1 ? 0 : ssa_internal_msm_sum_records(ctx, (const uint64_t *)ctx->ags_recs.p, k, false, (uint64_t *)d_rec_out);
 }
 
+// ---- a prefix that holds known lanes (the kernels: ssa_aggverifier.hpp)
+// ctx->agv_misc: the flag word of a push, the result word of the host forms, the flag word of a finish, S, e_agg - S
+constexpr size_t AGV_PUSH_FLAG = 0, AGV_RESULT = 4, AGV_FIN_FLAG = 8, AGV_S = 32, AGV_D = 64, AGV_MISC_BYTES = 96;
+static u8 *agv_misc(ssa_ctx *ctx, size_t off) { return (u8 *)ctx->agv_misc.p + off; }
+
+// The ascending list of the unknown places of the first n (>= 1) held lanes into ctx->agv_pos, its length at *d_m_out
+// (on the device): the compaction of av_keep over the known bytes -- a lane is listed iff its byte is zero.
+static int agv_list_unknown(ssa_ctx *ctx, const ssa_aggverifier *av, size_t n, const u32 **d_m_out) {
+    if (ctx->agv_pos.reserve(n * sizeof(u32))) return SSA_ERR_HIP;
+    return av_keep_enqueue(ctx, (const u8 *)av->known.p, n, (u32 *)ctx->agv_pos.p, d_m_out);
+}
+
+// S of the first n (>= 1) held lanes under the root in ctx->agm_roots, 32 bytes at d_s32_out: agx_fold with
+// agv_k_known_fold in place of agx_k_coeff_fold.  The finish's flag word is cleared in front and raised by a known lane
+// marked bad or a list of more than u_cap unknown places (*d_m: agv_list_unknown's count).
+static int agv_known_sum(ssa_ctx *ctx, const ssa_aggverifier *av, size_t n, const u32 *d_m, size_t u_cap, u8 *d_s32_out) {
+    const size_t piece = ags_piece(ctx), k = (n + piece - 1) / piece;
+    if (ctx->ags_parts.reserve(k * 32) || ctx->ag_partials.reserve((size_t)grid_for(std::min(piece, n), 256) * 32))
+        return SSA_ERR_HIP;
+    const u64 *d_root = (const u64 *)ctx->agm_roots.p;
+    u32 *d_flag = (u32 *)agv_misc(ctx, AGV_FIN_FLAG);
+    HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(u32), ctx->stream));
+    for (size_t lo = 0, j = 0; lo < n; lo += piece, j++) {
+        const size_t cnt = std::min(piece, n - lo);
+        const unsigned n_blocks = grid_for(cnt, 256);
+        int rc = timed_launch(ctx, "agv_k_known_fold", [&] {
+            hipLaunchKernelGGL(agv_k_known_fold, dim3(n_blocks), dim3(256), 0, ctx->stream, ctx->d_params, d_root,
+                               (const u64 *)av->h.p + 4 * lo, (const u8 *)av->known.p + lo, (const u8 *)av->bad.p + lo, cnt,
+                               (u64)lo, d_m, (u32)u_cap, (u64 *)ctx->ag_partials.p, d_flag);
+        });
+        if (rc) return rc;
+        rc = timed_launch(ctx, "ag_k_fold_finish", [&] {
+            hipLaunchKernelGGL(ag_k_fold_finish, dim3(1), dim3(256), 0, ctx->stream, (const u64 *)ctx->ag_partials.p, n_blocks,
+                               k == 1 ? d_s32_out : (u8 *)ctx->ags_parts.p + 32 * j);
+        });
+        if (rc) return rc;
+    }
+    if (k > 1) {
+        const int rc = timed_launch(ctx, "ag_k_fold_finish", [&] {
+            hipLaunchKernelGGL(ag_k_fold_finish, dim3(1), dim3(256), 0, ctx->stream, (const u64 *)ctx->ags_parts.p, (u32)k,
+                               d_s32_out);
+        });
+        if (rc) return rc;
+    }
+    return SSA_OK;
+}
+
+// The record of the MSM over the unknown lanes of the first n held lanes, at d_rec_out, under the root in
+// ctx->agm_roots: agv_record with agv_k_scalars_at over the u_cap (>= 1) rows of the list of unknown places
+// (agv_list_unknown: ctx->agv_pos, its length at *d_m), in pieces of at most one MSM slice.
+static int agv_record_listed(ssa_ctx *ctx, const ssa_aggverifier *av, const u32 *d_m, size_t u_cap, u64 *d_rec_out) {
+    const size_t piece = ags_piece(ctx), k = (u_cap + piece - 1) / piece;
+    if (k > 4096) return SSA_ERR_ARG;
+    if (ctx->ags_recs.reserve(k * 24 * sizeof(u64))) return SSA_ERR_HIP;
+    const u64 *d_root = (const u64 *)ctx->agm_roots.p;
+    const u32 *d_list = (const u32 *)ctx->agv_pos.p;
+    for (size_t lo = 0, j = 0; j < k; lo += piece, j++) {
+        const size_t cnt = std::min(piece, u_cap - lo);
+        const int rc = ssa_internal_msm_record_prepared(ctx, cnt, 16, [&](const MsmFill &f) {
+            return timed_launch(ctx, "agv_k_scalars_at", [&] {
+                (void)hipMemsetAsync(f.partials, 0, (size_t)f.n_blocks * 32, ctx->stream);
+                hipLaunchKernelGGL(agv_k_scalars_at, dim3(f.n_blocks), dim3(256), 0, ctx->stream, ctx->d_params, d_root,
+                                   (const u64 *)av->h.p, (const u64 *)av->rpts.p, (const u64 *)av->ppts.p,
+                                   (const u8 *)av->bad.p, d_list, d_m, lo, cnt, f.sh, f.wa, f.points, f.digits, f.flags);
+            });
+        }, k == 1 ? (uint64_t *)d_rec_out : (uint64_t *)ctx->ags_recs.p + 24 * j);
+        if (rc) return rc;
+    }
+    return k == 1 ? 0 : ssa_internal_msm_sum_records(ctx, (const uint64_t *)ctx->ags_recs.p, k, false, (uint64_t *)d_rec_out);
+}
+
+// finish for a prefix of n (>= 1) lanes that holds known lanes: the root; the unknown lanes' record (none: no MSM);
+// S over the known lanes; then [e_agg - S]G against the record by ag_k_finish_scalar -- agv_k_known_close forms the
+// difference, leaves a non-canonical e_agg as it is and carries the flag into the record's malformed word -- or, without
+// a record, the verdict of agv_k_known_close itself.  Only enqueues.
+static int agv_finish_mixed(ssa_ctx *ctx, const ssa_aggverifier *av, const u8 *d_e_agg, size_t n, u32 *d_verdict_out) {
+    const size_t u_cap = av->unknown_cap(n);
+    if (ctx->agv_misc.reserve(AGV_MISC_BYTES)) return SSA_ERR_HIP;
+    if (int rc = agx_root(*av, n)) return rc;
+    u64 *d_rec = u_cap ? (u64 *)ag_misc(ctx, AG_REC) : nullptr;
+    const u32 *d_m = nullptr;
+    if (int rc = agv_list_unknown(ctx, av, n, &d_m)) return rc;
+    if (u_cap)
+        if (int rc = agv_record_listed(ctx, av, d_m, u_cap, d_rec)) return rc;
+    if (int rc = agv_known_sum(ctx, av, n, d_m, u_cap, agv_misc(ctx, AGV_S))) return rc;
+    int rc = timed_launch(ctx, "agv_k_known_close", [&] {
+        hipLaunchKernelGGL(agv_k_known_close, dim3(1), dim3(64), 0, ctx->stream, d_e_agg, (const u8 *)agv_misc(ctx, AGV_S),
+                           (const u32 *)agv_misc(ctx, AGV_FIN_FLAG), d_rec, agv_misc(ctx, AGV_D), d_verdict_out);
+    });
+    if (rc || !u_cap) return rc;
+    return timed_launch(ctx, "ag_k_finish", [&] {
+        hipLaunchKernelGGL(ag_k_finish_scalar, dim3(1), dim3(64), 0, ctx->stream, (const u64 *)d_rec,
+                           (const u8 *)agv_misc(ctx, AGV_D), 0u, (const u64 *)ctx->d_gtab, d_verdict_out);
+    });
+}
+
 // Only enqueues on the context's stream: every size it needs is on the host.  Reads the object, writes workspaces of the
 // context and the caller's verdict word.
 extern "C" int ssa_aggverifier_finish_device(ssa_ctx *ctx, ssa_aggverifier *av, const uint8_t *d_e_agg, size_t n_take,
@@ -3467,10 +3566,11 @@ extern "C" int ssa_aggverifier_finish_device(ssa_ctx *ctx, ssa_aggverifier *av, 
     HIP_TRY(hipSetDevice(ctx->device));
     if (ctx->ag_misc.reserve(AG_MISC_BYTES)) return SSA_ERR_HIP;
     av->finishes++;
-    if (n)
+    const bool mixed = av->prefix_mixed(n);      // (then n >= 1) known lanes in the prefix: DESIGN.md section 34
+    if (n && !mixed)
         if (int rc = agv_record(ctx, av, n, (u64 *)ag_misc(ctx, AG_REC))) return rc;
     // the exact comparison of ssa_verify_aggregate_combine_device; the empty aggregate has no record: the kernel reads none
-    const int rc = timed_launch(ctx, "ag_k_finish", [&] {
+    const int rc = mixed ? agv_finish_mixed(ctx, av, d_e_agg, n, d_verdict_out) : timed_launch(ctx, "ag_k_finish", [&] {
         hipLaunchKernelGGL(ag_k_finish_scalar, dim3(1), dim3(64), 0, ctx->stream, (const u64 *)ag_misc(ctx, AG_REC), d_e_agg,
                            n == 0 ? 1u : 0u, (const u64 *)ctx->d_gtab, d_verdict_out);
     });
@@ -3502,7 +3602,153 @@ extern "C" int ssa_debug_aggverifier_record(ssa_ctx *ctx, ssa_aggverifier *av, s
     if (int rc = agx_take(ctx, av, n_take, &n)) return rc;
     if (n == 0 || !d_record24_out || !aligned8(d_record24_out)) return SSA_ERR_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
-    return agv_record(ctx, av, n, (u64 *)d_record24_out);
+    if (!av->prefix_mixed(n)) return agv_record(ctx, av, n, (u64 *)d_record24_out);
+    // known lanes in the prefix: the record of its unknown lanes alone (none of those either, no record)
+    const size_t u_cap = av->unknown_cap(n);
+    if (u_cap == 0) return SSA_ERR_ARG;
+    if (int rc = agx_root(*av, n)) return rc;
+    const u32 *d_m = nullptr;
+    if (int rc = agv_list_unknown(ctx, av, n, &d_m)) return rc;
+    return agv_record_listed(ctx, av, d_m, u_cap, (u64 *)d_record24_out);
+}
+
+// tests: S of the first n_take held lanes (32 bytes, little-endian, canonical; zero without a known lane).  Only enqueues.
+extern "C" int ssa_debug_aggverifier_known_sum(ssa_ctx *ctx, ssa_aggverifier *av, size_t n_take, uint8_t *d_s32_out) {
+    size_t n;
+    if (int rc = agx_take(ctx, av, n_take, &n)) return rc;
+    if (!d_s32_out) return SSA_ERR_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (!av->prefix_mixed(n)) {
+        HIP_TRY(hipMemsetAsync(d_s32_out, 0, 32, ctx->stream));
+        return SSA_OK;
+    }
+    if (ctx->agv_misc.reserve(AGV_MISC_BYTES)) return SSA_ERR_HIP;
+    if (int rc = agx_root(*av, n)) return rc;
+    const u32 *d_m = nullptr;
+    if (int rc = agv_list_unknown(ctx, av, n, &d_m)) return rc;
+    return agv_known_sum(ctx, av, n, d_m, av->unknown_cap(n), d_s32_out);
+}
+
+// ---- a block against the pool: known lanes from a streaming aggregator, the rest with the call
+// what every form of a mixed push refuses before anything is enqueued or counted.  n lanes, u of them unknown, the
+// places at `places` (device: in device memory).  The u compact lanes are checked as a plain push of u lanes is.
+static int agv_mixed_args(const ssa_ctx *ctx, const ssa_aggverifier *av, const ssa_aggregator *ag, const uint32_t *places,
+                          size_t n, size_t u, const MsgView &mv, const void *rs49, const void *pks, bool device) {
+    if (!ctx || !av || !ag || av->ctx != ctx || ag->ctx != ctx || (n && !places) || u > n || (u && (!rs49 || !pks)))
+        return SSA_ERR_ARG;
+    if (device && (reinterpret_cast<uintptr_t>(places) & 3u)) return SSA_ERR_ARG;
+    if (int rc = agg_check_args(ctx, mv, u)) return rc;
+    return n > ctx->knobs.msm_slice || n > av->capacity - av->held ? SSA_ERR_ARG : 0;
+}
+
+// The body of both forms behind the argument checks.  Only enqueues: whether the list is valid is decided on the device
+// (agv_k_classify, agv_k_mixed_close) and lands in *d_result_out.
+static int agv_push_mixed_body(ssa_ctx *ctx, ssa_aggverifier *av, const ssa_aggregator *ag, const u32 *d_places, size_t n,
+                               size_t u, const u8 *d_rs49, const u8 *d_pks, const u8 *d_pk_inf, const MsgView &mv,
+                               u32 *d_result_out) {
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(d_result_out, 0, sizeof(u32), ctx->stream));
+        av->pushes++;
+        return SSA_OK;
+    }
+    if (ctx->agv_keep.reserve(n + 16) || ctx->agv_pos.reserve(n * sizeof(u32)) || ctx->agv_misc.reserve(AGV_MISC_BYTES))
+        return SSA_ERR_HIP;
+    const size_t held = av->held;
+    // the first mixed push of the object: none of the lanes held so far is known (the rule in ssa_aggverifier.hpp)
+    if (!av->mixed && held) HIP_TRY(hipMemsetAsync(av->known.p, 0, held, ctx->stream));
+    u32 *d_flag = (u32 *)agv_misc(ctx, AGV_PUSH_FLAG);
+    HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(u32), ctx->stream));
+    u8 *d_keep = (u8 *)ctx->agv_keep.p;
+    u32 *d_pos = (u32 *)ctx->agv_pos.p;
+    int rc = timed_launch(ctx, "agv_k_classify", [&] {
+        hipLaunchKernelGGL(agv_k_classify, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, d_places, n, held, ag->held,
+                           (const u64 *)ag->leaves.p, (const u64 *)ag->scal.p, (u64 *)av->leaves.p, (u64 *)av->h.p,
+                           (u64 *)av->rpts.p, (u64 *)av->ppts.p, (u8 *)av->bad.p, av->keyed ? (u8 *)av->kst.p : (u8 *)nullptr,
+                           (u8 *)av->known.p, d_keep, d_flag);
+    });
+    if (rc) return rc;
+    // the unknown positions, ascending, and their number -- which stays on the device
+    const u32 *d_m = nullptr;
+    if ((rc = av_keep_enqueue(ctx, d_keep, n, d_pos, &d_m))) return rc;
+    if (u) {
+        // ONE challenge hash over the u lanes the call brought, as the plain push's over its n
+        const u8 *d_sigs = nullptr;
+        if ((rc = ag_transcript_front(ctx, d_rs49, &d_sigs, d_pks, mv, u, true, nullptr, 1))) return rc;
+        rc = timed_launch(ctx, "agv_k_append_at", [&] {
+            hipLaunchKernelGGL(agv_k_append_at, dim3(grid_for(u, 256)), dim3(256), 0, ctx->stream, ctx->d_params, d_sigs, d_pks,
+                               d_pk_inf, (const u64 *)ctx->ag_dig.p, (const u64 *)ctx->ws_h.p, u, (const u32 *)d_pos, d_m, held,
+                               (u64 *)av->leaves.p, (u64 *)av->h.p, (u64 *)av->rpts.p, (u64 *)av->ppts.p, (u8 *)av->bad.p);
+        });
+        if (rc) return rc;
+    }
+    rc = timed_launch(ctx, "agv_k_mixed_close", [&] {
+        hipLaunchKernelGGL(agv_k_mixed_close, dim3(std::min(grid_for(n, 256), 1024u)), dim3(256), 0, ctx->stream, d_m, (u32)u,
+                           (const u32 *)d_flag, n, (u8 *)av->bad.p + held, d_result_out);
+    });
+    if (rc) return rc;
+    const AgxPlan p = agx_plan(held, n, av->block);
+    if (p.count)
+        if ((rc = agx_reduce_blocks(*av, p))) return rc;
+    // (only now: a launch that could not be enqueued leaves the object as it was -- what it wrote lies behind `held`)
+    av->mixed = true;
+    if (n > u) av->mixed_pushes.push_back({held, n, u});
+    av->held += n;
+    av->pushes++;
+    av->pushed += n;
+    return SSA_OK;
+}
+
+extern "C" int ssa_aggverifier_push_mixed_device(ssa_ctx *ctx, ssa_aggverifier *av, ssa_aggregator *ag,
+                                                 const uint32_t *d_places, size_t n, const uint8_t *d_rs49,
+                                                 const uint8_t *d_pks, const uint8_t *d_pk_inf, const uint8_t *d_msgs,
+                                                 const uint64_t *d_msg_off, size_t msg_stride, size_t msg_len, size_t u,
+                                                 uint32_t *d_result_out) {
+    const MsgView mv{d_msgs, d_msg_off, msg_stride, msg_len};
+    if (int rc = agv_mixed_args(ctx, av, ag, d_places, n, u, mv, d_rs49, d_pks, true)) return rc;
+    if (!d_result_out) return SSA_ERR_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    return agv_push_mixed_body(ctx, av, ag, d_places, n, u, d_rs49, d_pks, d_pk_inf, mv, d_result_out);
+}
+
+// The list is on the host: everything a device would refuse is refused here, before a launch.
+extern "C" int ssa_aggverifier_push_mixed(ssa_ctx *ctx, ssa_aggverifier *av, ssa_aggregator *ag, const uint32_t *places,
+                                          size_t n, const uint8_t *rs49, const uint8_t *pks, const uint8_t *pk_inf,
+                                          const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len,
+                                          size_t u) {
+    if (int rc = agv_mixed_args(ctx, av, ag, places, n, u, {msgs, msg_off, msg_stride, msg_len}, rs49, pks, false)) return rc;
+    if (int rc = check_host_offsets(msg_off, u)) return rc;
+    size_t sentinels = 0;
+    for (size_t i = 0; i < n; i++) {
+        if (places[i] == SSA_AGGV_UNKNOWN) sentinels++;
+        else if (places[i] >= ag->held) return SSA_ERR_ARG;
+    }
+    if (sentinels != u) return SSA_ERR_ARG;
+    HostCall hc(ctx);
+    const u32 *d_places = hc.in<u32>(ctx->agv_places, places, n * sizeof(u32));
+    DevBatch b{};
+    if (u) b = hc.lanes({rs49, pks, pk_inf, msgs, msg_off, msg_stride, msg_len}, u * 49, u);
+    // (reserved here at the size the body asks for: the result word does not move under it)
+    if (hc.ok() && ctx->agv_misc.reserve(AGV_MISC_BYTES)) hc.rc = SSA_ERR_HIP;
+    if (!hc.ok()) return hc.rc;
+    u32 refused = 0, *d_result = (u32 *)agv_misc(ctx, AGV_RESULT);
+    hc.copy_back(&refused, d_result, sizeof refused);
+    const int rc = hc.finish([&] {
+        return agv_push_mixed_body(ctx, av, ag, d_places, n, u, b.sigs, b.pks, b.pk_inf, {b.msgs.msgs, b.msgs.off, msg_stride, msg_len},
+                                   d_result);
+    });
+    if (rc) return rc;
+    return refused ? SSA_ERR_HIP : SSA_OK;      // (cannot be: the list was checked above)
+}
+
+extern "C" int ssa_aggverifier_push_known_device(ssa_ctx *ctx, ssa_aggverifier *av, ssa_aggregator *ag,
+                                                 const uint32_t *d_places, size_t m, uint32_t *d_result_out) {
+    return ssa_aggverifier_push_mixed_device(ctx, av, ag, d_places, m, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0,
+                                             d_result_out);
+}
+
+extern "C" int ssa_aggverifier_push_known(ssa_ctx *ctx, ssa_aggverifier *av, ssa_aggregator *ag, const uint32_t *places,
+                                          size_t m) {
+    return ssa_aggverifier_push_mixed(ctx, av, ag, places, m, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0);
 }
 
 // ---- several devices in one process: every device takes a contiguous run of whole blocks, block counts differ by at

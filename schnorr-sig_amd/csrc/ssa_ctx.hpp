@@ -226,6 +226,11 @@ struct CtxKnobs {
        lanes held (cleared by every call that uses them, never assumed clean), the list as the host forms upload it, \
        and the byte mask remove_indices hands to the move */ \
     X(agx_sel_stage) X(agx_sel_bits) X(agx_sel_order) X(agx_sel_mask) \
+    /* known lanes in the streaming aggregate verifier: a keep byte per lane of a mixed push, the \
+       list of unknown positions (of a push) or places (of a finish), the place list as the host forms upload it, and \
+       one small block: the flag words, the result word of the host forms, S and e_agg - S.  Nothing lives in them \
+       between calls */ \
+    X(agv_keep) X(agv_pos) X(agv_places) X(agv_misc) \
     /* the end game of ssa_k_verify, per tail group: finished pieces; parked accumulators + status (152 B per lane) */ \
     X(tail_done) X(tail_park)
 

@@ -1080,7 +1080,7 @@ class AggregateVerifier {
         uint64_t held, capacity, block_lanes, pushes, pushed, reserved, blocks, finishes;     // reserved: lanes pushed
     };                                                                                        // through a key cache
     static constexpr size_t All = SIZE_MAX;       // finish: every lane held
-    // block_lanes: 0 (512) or a power of two from 2 to 512.  All device memory, about 258 bytes per lane, is allocated here.
+    // block_lanes: 0 (512) or a power of two from 2 to 512.  All device memory, about 259 bytes per lane, is allocated here.
     AggregateVerifier(Context &cx, size_t capacity, size_t block_lanes = 0) : cx_(cx) {
         const int rc = ssa_aggverifier_create(cx.get(), capacity, block_lanes, 0u, &av_);
         if (rc != 0) throw std::runtime_error(std::string("ssa_aggverifier_create: ") + ssa_strerror(rc));
@@ -1139,6 +1139,27 @@ class AggregateVerifier {
         const int rc = ssa_aggverifier_push_cached_wire(cx_.get(), av_, cache.get(), rs49, wire_keys.data(), flat.data(),
                                                         off.data(), 0, 0, n, stats_out);
         if (rc != 0) throw std::runtime_error(std::string("ssa_aggverifier_push_cached_wire: ") + ssa_strerror(rc));
+    }
+    // A block against the pool: places[i] is the place in `pool` of lane i of the block, or Unknown
+    // for a lane the pool does not hold.  The unknown lanes come with the call, side by side in block order -- rs49 their
+    // R's, 49 bytes each, then their keys and messages as push takes them --; a known lane takes leaf and scalar from the
+    // pool, copied.  finish then answers as for the block with every known lane replaced by what the pool admitted it
+    // with, PROVIDED the pool's scalar of every known lane satisfies its verification equation: name only lanes that a
+    // screened or cached push admitted.  An invalid list throws and changes nothing.
+    static constexpr uint32_t Unknown = SSA_AGGV_UNKNOWN;
+    void push_mixed(Aggregator &pool, const std::vector<uint32_t> &places, const uint8_t *rs49,
+                    const std::vector<PublicKey> &public_keys,
+                    const std::vector<std::pair<const uint8_t *, size_t>> &messages) {
+        const size_t u = public_keys.size();
+        const PackedTriples t = pack_triples(std::vector<Signature>(u), public_keys, messages);
+        const int rc = ssa_aggverifier_push_mixed(cx_.get(), av_, pool.get(), places.data(), places.size(), rs49, t.pks.data(),
+                                                  t.inf.data(), t.flat.data(), t.off.data(), 0, 0, u);
+        if (rc != 0) throw std::runtime_error(std::string("ssa_aggverifier_push_mixed: ") + ssa_strerror(rc));
+    }
+    // every lane of the block is held by the pool
+    void push_known(Aggregator &pool, const std::vector<uint32_t> &places) {
+        const int rc = ssa_aggverifier_push_known(cx_.get(), av_, pool.get(), places.data(), places.size());
+        if (rc != 0) throw std::runtime_error(std::string("ssa_aggverifier_push_known: ") + ssa_strerror(rc));
     }
     // the status word: SSA_OK, SSA_INVALID_SIGNATURE or SSA_MALFORMED; SSA_INVALID_PUBLIC_KEY after pushes through a cache
     int finish_status(const uint8_t e_agg[32], size_t n_take = All) const {
