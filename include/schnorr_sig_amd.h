@@ -1208,8 +1208,8 @@ int ssa_aggregate_valid_keyed_many_cached_device(ssa_ctx *ctx, ssa_keycache *kc,
  * that the challenge hash, the admission check, the leaves and most of the tree are paid on arrival, and block time pays
  * one permutation, one multiplication and a sum per lane.  It belongs to the context it was created on, like a key cache.
  *   create   capacity: 1 .. SSA_MAX_BATCH lanes; block_lanes: 0 (the default, 512) or a power of two from 2 to 512 (small
- *            values let tests reach every path of the tree at a few thousand lanes); flags: 0 or
- *            SSA_AGGR_HOLD_KEYS49 (below).  Anything else: SSA_ERR_ARG.  All device memory is allocated here -- 49 capacity + 32 bytes of R's, 32 bytes of scalar and 32
+ *            values let tests reach every path of the tree at a few thousand lanes); flags: 0 or any of
+ *            SSA_AGGR_HOLD_KEYS49 and SSA_AGGR_HOLD_ADMISSION (below).  Anything else: SSA_ERR_ARG.  All device memory is allocated here -- 49 capacity + 32 bytes of R's, 32 bytes of scalar and 32
  *            bytes of leaf per lane, 32 bytes per block: about 113 bytes per lane -- and is the object's own: destroy
  *            releases it, or ssa_ctx_destroy (the handle then stays valid for destroy and is refused everywhere else).
  *   push     the arguments of ssa_aggregate_valid_many.  Let S be the status vector: with flags == 0 the one
@@ -1280,6 +1280,21 @@ int ssa_aggregate_valid_keyed_many_cached_device(ssa_ctx *ctx, ssa_keycache *kc,
  *            keys, unchanged, with the kept messages, k = 1 and counts = {n}, are what
  *            ssa_verify_aggregates_many_cached_wire takes; on the same cache that call finds every key (stats[2] == 0)
  *            unless the push bypassed the cache or did not use it.
+ *   SSA_AGGR_HOLD_ADMISSION (create flag)   the object also records HOW each lane was admitted: one
+ *            more byte per lane, `adm`, written by the library behind every push and by nobody else:
+ *              SSA_ADM_UNSCREENED (0)    a push with SSA_AGGR_NO_SCREEN: the caller's own word;
+ *              SSA_ADM_SCREENED (1)      the plain screened push: the lane's equation is established, its key has had
+ *                                        no subgroup check;
+ *              SSA_ADM_KEY_CHECKED (2)   push_cached or push_keyed_cached, with or without the key column: the equation
+ *                                        and the subgroup check of the key.
+ *            The byte moves with its lane under drop_front, remove and remove_indices (after a removal the object is
+ *            indistinguishable, classes included, from one that admitted the kept lanes alone by the same kinds of
+ *            push); reset forgets it; finish, finish_select and keys neither read nor write it.  admission(n_take)
+ *            writes the first n_take held lanes' classes, n_take bytes, by the conventions of keys: SIZE_MAX = all lanes
+ *            held, n_take > held is SSA_ERR_ARG, n_take == 0 writes nothing, the _device form only enqueues, no state of
+ *            the object changes.  On an object created without the flag: SSA_ERR_ARG.  Such an object allocates what
+ *            it did before the flag existed and enqueues exactly the launches and copies it did.  The classes are what
+ *            ssa_aggverifier_push_mixed_cached requires of the lanes it takes from the pool.
  *   finish_select, remove_indices   CHOOSE among the held lanes: a producer fills its block with the
  *            lanes it wants, in an order of its own, and keeps the rest.  Let L be the lanes held; order[0, m) names m
  *            DISTINCT places < held.  finish_select writes SSA_AGGREGATE_LENGTH(m) bytes: byte for byte what
@@ -1310,6 +1325,10 @@ int ssa_aggregate_valid_keyed_many_cached_device(ssa_ctx *ctx, ssa_keycache *kc,
 typedef struct ssa_aggregator ssa_aggregator;
 #define SSA_AGGR_NO_SCREEN 1u      /* push flag */
 #define SSA_AGGR_HOLD_KEYS49 2u    /* create flag */
+#define SSA_AGGR_HOLD_ADMISSION 8u /* create flag */
+#define SSA_ADM_UNSCREENED 0u      /* the admission classes of SSA_AGGR_HOLD_ADMISSION */
+#define SSA_ADM_SCREENED 1u
+#define SSA_ADM_KEY_CHECKED 2u
 int ssa_aggregator_create(ssa_ctx *ctx, size_t capacity, size_t block_lanes, uint32_t flags, ssa_aggregator **out);
 void ssa_aggregator_destroy(ssa_aggregator *ag);
 int ssa_aggregator_reset(ssa_aggregator *ag);
@@ -1342,6 +1361,11 @@ int ssa_aggregator_keys_device(ssa_ctx *ctx, ssa_aggregator *ag, size_t n_take, 
  * out[0] the R's, [1] the scalars, [2] the leaves, [3] the tops, [4] the key column (0 without SSA_AGGR_HOLD_KEYS49).
  * SSA_ERR_ARG for anything create would refuse. */
 int ssa_debug_aggregator_bytes(size_t capacity, size_t block_lanes, uint32_t flags, uint64_t out[5]);
+/* tests: the same five words (SSA_AGGR_HOLD_ADMISSION is accepted by both and changes none of them), out[5] the
+ * admission column (0 without SSA_AGGR_HOLD_ADMISSION), out[6] = out[7] = 0. */
+int ssa_debug_aggregator_bytes_ex(size_t capacity, size_t block_lanes, uint32_t flags, uint64_t out[8]);
+int ssa_aggregator_admission(ssa_ctx *ctx, ssa_aggregator *ag, size_t n_take, uint8_t *adm_out);
+int ssa_aggregator_admission_device(ssa_ctx *ctx, ssa_aggregator *ag, size_t n_take, uint8_t *d_adm_out);
 /* tests: what a push of m kept lanes onto `held` lanes completes with blocks of block_lanes (0: 512) lanes (host code, no
  * device): out[0] the first completed block, out[1] the number of completed blocks, out[2] the first lane of the ragged
  * tail, out[3] its length.  SSA_ERR_ARG for a block size create would refuse or held + m above SSA_MAX_BATCH. */
@@ -1476,10 +1500,11 @@ size_t ssa_debug_aggverifier_key_span(void);
  *   finish       unchanged in signature; for a prefix that holds a known lane it answers what ssa_verify_aggregate
  *                answers for the block in which every known lane is replaced by the (R, key, message) the pool admitted
  *                it with, PROVIDED every known lane's stored scalar satisfies its own verification equation.
- * THE CONTRACT IS THE CALLER'S.  Lanes admitted by a screened or cached push of the aggregator meet it; a lane pushed
- * with SSA_AGGR_NO_SCREEN is the caller's own word.  A wrong stored scalar makes honest blocks fail, and somebody who
- * knows of such a lane in a validator's pool could craft a block that this path accepts and ssa_verify_aggregate
- * refuses.  Do not name such lanes as known.
+ * THE CONTRACT IS THE CALLER'S on these entry points, which have no `require` argument.  Lanes admitted by a screened or
+ * cached push of the aggregator meet it; a lane pushed with SSA_AGGR_NO_SCREEN is the caller's own word.  A wrong stored
+ * scalar makes honest blocks fail, and somebody who knows of such a lane in a validator's pool could craft a block that
+ * this path accepts and ssa_verify_aggregate refuses.  Do not name such lanes as known -- or let the library refuse
+ * them: ssa_aggverifier_push_mixed_cached (below) with require >= 1 on a pool that records its admissions.
  * Host forms: SSA_ERR_ARG, the object unchanged, for a place >= ag->held that is not the sentinel, u different from the
  * number of sentinels, objects of different contexts or orphaned, n > capacity - held, n or u above the context's MSM
  * slice, bad message arguments, NULL objects, a NULL list with n != 0.
@@ -1492,8 +1517,8 @@ size_t ssa_debug_aggverifier_key_span(void);
  * ssa_debug_aggverifier_known_sum writes S of the first n_take lanes, 32 bytes little-endian, to DEVICE memory (zero
  * without a known lane).  An object that never sees a mixed push enqueues exactly what it did before these entry points
  * existed; it holds one more byte per lane (259 in all).
- * NOT here: mixed pushes through a key cache, a per-lane "was screened" bit in the aggregator, ssa_multi forms, known
- * lanes taken from another verifier. */
+ * NOT here: ssa_multi forms, known lanes taken from another verifier.  (Mixed pushes through a key cache and the
+ * admission class of a pool's lane: the next block.) */
 #define SSA_AGGV_UNKNOWN 0xFFFFFFFFu
 int ssa_aggverifier_push_mixed(ssa_ctx *ctx, ssa_aggverifier *av, ssa_aggregator *ag, const uint32_t *places, size_t n,
                                const uint8_t *rs49, const uint8_t *pks, const uint8_t *pk_inf, const uint8_t *msgs,
@@ -1506,6 +1531,54 @@ int ssa_aggverifier_push_known(ssa_ctx *ctx, ssa_aggverifier *av, ssa_aggregator
 int ssa_aggverifier_push_known_device(ssa_ctx *ctx, ssa_aggverifier *av, ssa_aggregator *ag, const uint32_t *d_places,
                                       size_t m, uint32_t *d_result_out);
 int ssa_debug_aggverifier_known_sum(ssa_ctx *ctx, ssa_aggverifier *av, size_t n_take, uint8_t *d_s32_out);
+
+/* ---- a block against the pool through the key cache, with a required admission class ----
+ * push_mixed with the guarantee of ssa_verify_aggregates_many_cached(_wire), and with its soundness condition checked
+ * by the library.  The arguments of push_mixed, a key cache `kc`, and `require`:
+ *   unknown lanes   are treated exactly as ssa_aggverifier_push_cached (_wire: push_cached_wire) treats them: the u
+ *                compact keys -- affine with pk_inf and an AFFINE cache, or 49-byte wire keys and a WIRE cache -- go
+ *                through the cache in slices of the context's lane slice, each distinct key is checked (a wire key
+ *                decompressed) once, and each lane's key status is held at the lane's true place in the block.  The
+ *                first such push makes the object keyed, as a cached push does.  stats_out (HOST memory, may be NULL):
+ *                the eight words of push_cached over the u unknown lanes.
+ *   known lanes  require is 0, 1 or 2 (anything else: SSA_ERR_ARG), and a known lane whose admission class in the pool
+ *                (SSA_ADM_*, above) is BELOW require is refused exactly as a place out of range is.  require > 0 needs
+ *                a pool created with SSA_AGGR_HOLD_ADMISSION, else SSA_ERR_ARG.  require == 0 is push_mixed's contract
+ *                on any pool.  A known lane that passes is stored as push_mixed stores it, key status 0.
+ * THE CONTRACT.  Take a prefix of n lanes, all pushed through a cache or known lanes of class 2 pushed with
+ * require == 2.  finish(e_agg, n) equals ssa_verify_aggregates_many_cached (_wire) with k = 1, counts = {n} on the block
+ * in which every known lane is replaced by the (R, key, message) the pool admitted it with -- in every state of the
+ * cache, and with nothing owed by the caller beyond having looked up the right places.  What remains is the error
+ * probability of the screen that admitted the pool's lanes, stated once.  With require == 1 the
+ * equality is with ssa_verify_aggregate, as for push_mixed, now without its proviso; with require == 0 it is push_mixed's.
+ * The result word (*d_result_out; the host forms read it themselves): bit 0 = the list is invalid (a place out of range,
+ * a sentinel miscount), bit 1 = a known lane was below the required class.
+ * Host forms refuse before anything is applied: everything push_mixed and push_cached refuse on the host, and, with
+ * require > 0, a pre-check launch over the uploaded places whose word the host reads before the cache or the object is
+ * touched -- nonzero: SSA_ERR_ARG, with object, cache and info unchanged.  A push is never applied in part.
+ * _device forms fail closed as push_mixed_device does: a refused lane is held as failed, every finish that reaches it
+ * is SSA_MALFORMED; reset the object after a refusal.  They are NOT enqueue-only: they synchronise the context's stream
+ * once per cache slice, as push_cached_device does (and once more for stats_out, if given).
+ * The existing push_mixed / push_known entry points, and an object that never sees these calls, enqueue exactly what
+ * they did. */
+int ssa_aggverifier_push_mixed_cached(ssa_ctx *ctx, ssa_aggverifier *av, ssa_aggregator *ag, ssa_keycache *kc,
+                                      const uint32_t *places, size_t n, const uint8_t *rs49, const uint8_t *pks,
+                                      const uint8_t *pk_inf, const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride,
+                                      size_t msg_len, size_t u, uint32_t require, uint64_t stats_out[8]);
+int ssa_aggverifier_push_mixed_cached_device(ssa_ctx *ctx, ssa_aggverifier *av, ssa_aggregator *ag, ssa_keycache *kc,
+                                             const uint32_t *d_places, size_t n, const uint8_t *d_rs49, const uint8_t *d_pks,
+                                             const uint8_t *d_pk_inf, const uint8_t *d_msgs, const uint64_t *d_msg_off,
+                                             size_t msg_stride, size_t msg_len, size_t u, uint32_t require,
+                                             uint32_t *d_result_out, uint64_t stats_out[8]);
+int ssa_aggverifier_push_mixed_cached_wire(ssa_ctx *ctx, ssa_aggverifier *av, ssa_aggregator *ag, ssa_keycache *kc,
+                                           const uint32_t *places, size_t n, const uint8_t *rs49, const uint8_t *pks49,
+                                           const uint8_t *msgs, const uint64_t *msg_off, size_t msg_stride, size_t msg_len,
+                                           size_t u, uint32_t require, uint64_t stats_out[8]);
+int ssa_aggverifier_push_mixed_cached_wire_device(ssa_ctx *ctx, ssa_aggverifier *av, ssa_aggregator *ag, ssa_keycache *kc,
+                                                  const uint32_t *d_places, size_t n, const uint8_t *d_rs49,
+                                                  const uint8_t *d_pks49, const uint8_t *d_msgs, const uint64_t *d_msg_off,
+                                                  size_t msg_stride, size_t msg_len, size_t u, uint32_t require,
+                                                  uint32_t *d_result_out, uint64_t stats_out[8]);
 
 /* ---- ABI version -------------------------------------------------------------------------------------------
  * Bumped whenever an exported signature changes (round 2 inserted pk_inf into the batch entry points under the same

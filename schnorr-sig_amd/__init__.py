@@ -310,6 +310,9 @@ def _load():
         "ssa_aggregator_keys": (i32, [vp, vp, sz, vp]),
         "ssa_aggregator_keys_device": (i32, [vp, vp, sz, vp]),
         "ssa_debug_aggregator_bytes": (i32, [sz, sz, u32, u64p]),
+        "ssa_debug_aggregator_bytes_ex": (i32, [sz, sz, u32, u64p]),
+        "ssa_aggregator_admission": (i32, [vp, vp, sz, vp]),
+        "ssa_aggregator_admission_device": (i32, [vp, vp, sz, vp]),
         "ssa_debug_aggregator_plan": (i32, [C.c_uint64, C.c_uint64, C.c_uint64, u64p]),
         "ssa_aggregator_drop_front": (i32, [vp, vp, sz]),
         "ssa_aggregator_remove": (i32, [vp, vp, vp, sz, u64p]),
@@ -335,6 +338,12 @@ def _load():
         "ssa_debug_aggverifier_key_span": (sz, []),
         "ssa_aggverifier_push_mixed": (i32, [vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, sz, sz, sz]),
         "ssa_aggverifier_push_mixed_device": (i32, [vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, sz, sz, sz, vp]),
+        "ssa_aggverifier_push_mixed_cached": (i32, [vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, sz, sz, sz, u32, vp]),
+        "ssa_aggverifier_push_mixed_cached_device": (i32, [vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, sz, sz, sz, u32, vp,
+                                                           vp]),
+        "ssa_aggverifier_push_mixed_cached_wire": (i32, [vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, sz, sz, sz, u32, vp]),
+        "ssa_aggverifier_push_mixed_cached_wire_device": (i32, [vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, sz, sz, sz, u32, vp,
+                                                                vp]),
         "ssa_aggverifier_push_known": (i32, [vp, vp, vp, vp, sz]),
         "ssa_aggverifier_push_known_device": (i32, [vp, vp, vp, vp, sz, vp]),
         "ssa_debug_aggverifier_known_sum": (i32, [vp, vp, sz, vp]),
@@ -638,16 +647,19 @@ class Engine:
                 raise
         return cache
 
-    def aggregator(self, capacity, block_lanes=0, hold_keys=False):
+    def aggregator(self, capacity, block_lanes=0, hold_keys=False, hold_admission=False):
         """a streaming aggregator of `capacity` lanes on this engine's device: push signatures
         as they arrive, finish at block time.  All of its device memory, about 113 bytes per lane, is allocated here.
         block_lanes: 0 (512) or a power of two from 2 to 512.
         hold_keys=True (SSA_AGGR_HOLD_KEYS49): the object also holds every admitted lane's 49-byte
-        wire key (49 more bytes per lane) for Aggregator.keys(); it then takes push_keyed alone."""
+        wire key (49 more bytes per lane) for Aggregator.keys(); it then takes push_keyed alone.
+        hold_admission=True (SSA_AGGR_HOLD_ADMISSION): the object also records the class of the
+        push that admitted each lane (one more byte per lane) for Aggregator.admission() and for
+        AggregateVerifier.push_mixed(cache=, require=)."""
         h = C.c_void_p()
-        _check(_lib.ssa_aggregator_create(self._ctx, int(capacity), int(block_lanes), AGGR_HOLD_KEYS49 if hold_keys else 0,
+        _check(_lib.ssa_aggregator_create(self._ctx, int(capacity), int(block_lanes), _aggr_flags(hold_keys, hold_admission),
                                           C.byref(h)), "ssa_aggregator_create")
-        return Aggregator(self, h, hold_keys=hold_keys)
+        return Aggregator(self, h, hold_keys=hold_keys, hold_admission=hold_admission)
 
     def aggregate_verifier(self, capacity, block_lanes=0):
         """a streaming aggregate verifier of `capacity` lanes on this engine's device: push the
@@ -1839,6 +1851,11 @@ class KeyCache(_Handle, _KeyTables):
 
 AGGR_NO_SCREEN = 1    # SSA_AGGR_NO_SCREEN
 AGGR_HOLD_KEYS49 = 2  # SSA_AGGR_HOLD_KEYS49
+AGGR_HOLD_ADMISSION = 8  # SSA_AGGR_HOLD_ADMISSION
+# the admission classes an Aggregator made with hold_admission=True records
+ADM_UNSCREENED = 0    # SSA_ADM_UNSCREENED: push(screen=False)
+ADM_SCREENED = 1      # SSA_ADM_SCREENED: the plain screened push
+ADM_KEY_CHECKED = 2   # SSA_ADM_KEY_CHECKED: push(cache=), push_keyed
 AGGREGATOR_FIELDS = ("held", "capacity", "block_lanes", "pushes", "offered", "dropped", "blocks", "finishes")
 AGGVERIFIER_FIELDS = ("held", "capacity", "block_lanes", "pushes", "pushed", "reserved", "blocks", "finishes")
 #   ("reserved" is word [5] of ssa_aggverifier_info: since section 29 the lanes pushed through a key cache, 0 for an
@@ -1866,6 +1883,26 @@ def aggregator_bytes(capacity, block_lanes=0, hold_keys=False):
     _check(_lib.ssa_debug_aggregator_bytes(int(capacity), int(block_lanes), AGGR_HOLD_KEYS49 if hold_keys else 0, out),
            "ssa_debug_aggregator_bytes")
     return tuple(int(v) for v in out)
+
+
+def _aggr_flags(hold_keys, hold_admission):
+    return (AGGR_HOLD_KEYS49 if hold_keys else 0) | (AGGR_HOLD_ADMISSION if hold_admission else 0)
+
+
+def aggregator_bytes_ex(capacity, block_lanes=0, hold_keys=False, hold_admission=False):
+    """tests: the five words of aggregator_bytes, the admission column (0 without hold_admission) and two zeros
+    (ssa_debug_aggregator_bytes_ex: host code, no device)"""
+    out = (C.c_uint64 * 8)()
+    _check(_lib.ssa_debug_aggregator_bytes_ex(int(capacity), int(block_lanes), _aggr_flags(hold_keys, hold_admission), out),
+           "ssa_debug_aggregator_bytes_ex")
+    return tuple(int(v) for v in out)
+
+
+def _require_class(require):
+    """the `require` argument of a mixed push through a key cache: 0, 1 or 2 (ADM_*); ValueError before any call"""
+    if isinstance(require, (bool, np.bool_)) or not isinstance(require, (int, np.integer)) or not 0 <= int(require) <= 2:
+        raise ValueError("require is an admission class: 0, 1 or 2")
+    return int(require)
 
 
 def aggregator_remove_plan(held, first_changed, new_held, block_lanes=0):
@@ -1988,9 +2025,32 @@ class Aggregator(_LaneStore):
     a `with` block, or when the object goes away)."""
     _prefix, _fields = "aggregator", AGGREGATOR_FIELDS
 
-    def __init__(self, engine, handle, hold_keys=False):
+    def __init__(self, engine, handle, hold_keys=False, hold_admission=False):
         super().__init__(engine, handle)
         self.hold_keys = bool(hold_keys)
+        self.hold_admission = bool(hold_admission)
+
+    def admission(self, n=None):
+        """the admission classes (ADM_*) of the first n held lanes (None: all) as uint8[n], in arrival order: how the
+        push that admitted each lane screened it.  Changes no state.  An object made without
+        hold_admission raises."""
+        held = self.info()["held"]
+        k = held if n is None else int(n)
+        out = np.full(max(min(k, held), 1), 255, dtype=np.uint8)
+        _check(_lib.ssa_aggregator_admission(self.engine._ctx, self.handle, _n_take(n), _ptr(out)),
+               "ssa_aggregator_admission")
+        return out[:min(k, held)].copy()
+
+    def admission_device(self, d_adm, n=None):
+        """device form: only enqueues on the engine's stream; the n bytes land in the uint8 tensor d_adm, n as given or
+        all lanes held.  Returns n."""
+        k = self.info()["held"] if n is None else int(n)
+        _dev_bytes(d_adm, self.engine, "d_adm")
+        if d_adm.numel() < k:
+            raise ValueError("the classes of %d lanes are %d bytes" % (k, k))
+        _check(_lib.ssa_aggregator_admission_device(self.engine._ctx, self.handle, k, d_adm.data_ptr()),
+               "ssa_aggregator_admission_device")
+        return k
 
     def push(self, sigs, pks, msgs, pk_inf=None, screen=True, offsets=None, engine=None, cache=None):
         """a batch of signatures, keys and messages as Engine.aggregate_valid takes them -> (status uint8[n], n_kept):
@@ -2360,7 +2420,22 @@ class AggregateVerifier(_LaneStore):
         return d_rec.cpu().numpy().view(np.uint64)
 
     # ---- a block against the pool
-    def push_mixed(self, aggregator, places, rs49, pks, msgs, offsets=None, pk_inf=None, engine=None):
+    def _mixed_cached_check(self, aggregator, cache, require, wire):
+        """what the host can see of a mixed push through a key cache, before any call: ValueError"""
+        require = _require_class(require)
+        if cache is None:
+            if require:
+                raise ValueError("require > 0 goes with a key cache: the class is enforced by the cached mixed push")
+            return 0
+        if bool(cache.wire) != wire:
+            raise ValueError("push_mixed takes affine keys and an affine key cache, push_mixed_wire 49-byte keys and a "
+                             "cache made with wire=True")
+        if require and not getattr(aggregator, "hold_admission", False):
+            raise ValueError("require > 0 needs an Aggregator made with hold_admission=True")
+        return require
+
+    def push_mixed(self, aggregator, places, rs49, pks, msgs, offsets=None, pk_inf=None, engine=None, cache=None,
+                   require=0):
         """n lanes of a block, most of them held by `aggregator` (an Aggregator of the same Engine) already: places[i]
         is the pool's place of lane i, or None / -1 for a lane the pool does not hold.  The u unknown lanes come with
         the call, side by side in block order (rs49, pks, msgs, pk_inf as push() takes them) and are treated as
@@ -2368,17 +2443,64 @@ class AggregateVerifier(_LaneStore):
         the block with every known lane replaced by what the pool admitted it with -- PROVIDED the pool's scalar of
         every known lane satisfies its verification equation: name only lanes admitted by a screened or cached push.
         An invalid list (a place not held, a count of unknown lanes other than u) raises and changes nothing.
-        engine: tests.  Returns n."""
+        engine: tests.  Returns n.
+        cache: an AFFINE KeyCache -- the unknown lanes go through it as push(cache=) sends
+        them, and a known lane whose admission class in the pool (Aggregator.admission) is below `require` (0, 1 or 2;
+        above 0 the pool must be made with hold_admission=True) is refused: the call raises and changes nothing.  With
+        require=2 on lanes the pool admitted through a cache, finish() answers what Engine.verify_aggregates_cached
+        answers for the whole block, with nothing owed by the caller.  Then returns (n, stats uint64[8])."""
+        require = self._mixed_cached_check(aggregator, cache, require, False)
         places = _places_u32(places)
         n = int(places.size)
         eng = engine or self.engine
         u, batch, keep = eng._agg_batch(rs49, 49, pks, msgs, offsets, pk_inf)
-        _check(_lib.ssa_aggverifier_push_mixed(eng._ctx, self.handle, aggregator.handle if aggregator is not None else None,
-                                               _ptr(places) if n else None, n, *batch), "ssa_aggverifier_push_mixed")
+        ag = aggregator.handle if aggregator is not None else None
+        if cache is not None:
+            stats = np.zeros(8, dtype=np.uint64)
+            _check(_lib.ssa_aggverifier_push_mixed_cached(eng._ctx, self.handle, ag, cache.handle, _ptr(places) if n else None,
+                                                          n, *batch, require, stats.ctypes.data),
+                   "ssa_aggverifier_push_mixed_cached")
+            return n, stats
+        _check(_lib.ssa_aggverifier_push_mixed(eng._ctx, self.handle, ag, _ptr(places) if n else None, n, *batch),
+               "ssa_aggverifier_push_mixed")
         return n
 
-    def push_known(self, aggregator, places, engine=None):
-        """push_mixed without unknown lanes: every lane of the block is held by the pool.  Returns n."""
+    def push_mixed_wire(self, aggregator, places, rs49, pks49, msgs, offsets=None, cache=None, require=0, engine=None):
+        """push_mixed with the u unknown lanes' keys as dense 49-byte wire keys through a key cache made with wire=True
+        (required): what push_wire does for the unknown lanes, `require` as in push_mixed.  -> (n, stats uint64[8])."""
+        if cache is None:
+            raise ValueError("push_mixed_wire needs a key cache made with wire=True")
+        require = self._mixed_cached_check(aggregator, cache, require, True)
+        places = _places_u32(places)
+        n = int(places.size)
+        eng = engine or self.engine
+        keys = _np_u8(pks49, 49)
+        u = keys.shape[0]
+        lead = _np_u8(rs49).reshape(-1)
+        if lead.size != 49 * u:
+            raise MalformedInput("We should have the same number of signatures than public keys")
+        m, off, stride, mlen = eng._msg_args(msgs, offsets, u) if u else (None, None, 0, 0)
+        stats = np.zeros(8, dtype=np.uint64)
+        _check(_lib.ssa_aggverifier_push_mixed_cached_wire(
+            eng._ctx, self.handle, aggregator.handle if aggregator is not None else None, cache.handle,
+            _ptr(places) if n else None, n, _ptr(lead) if u else None, _ptr(keys) if u else None, _ptr(m), _ptr(off), stride,
+            mlen, u, require, stats.ctypes.data), "ssa_aggverifier_push_mixed_cached_wire")
+        return n, stats
+
+    def push_known(self, aggregator, places, engine=None, cache=None, require=0):
+        """push_mixed without unknown lanes: every lane of the block is held by the pool.  Returns n.
+        require > 0 (with the cache the object's other lanes go through, affine or wire: no key is sent to it) routes
+        through the cached mixed push with u = 0, which enforces the class and makes the object keyed; require == 0
+        is the plain call, whatever `cache` is."""
+        require = _require_class(require)
+        if require:
+            if cache is None:
+                raise ValueError("require > 0 goes with a key cache: the class is enforced by the cached mixed push")
+            if cache.wire:
+                return self.push_mixed_wire(aggregator, places, np.zeros(0, np.uint8), np.zeros((0, 49), np.uint8), None,
+                                            cache=cache, require=require, engine=engine)[0]
+            return self.push_mixed(aggregator, places, np.zeros(0, np.uint8), np.zeros((0, 96), np.uint8), None,
+                                   engine=engine, cache=cache, require=require)[0]
         places = _places_u32(places)
         n = int(places.size)
         _check(_lib.ssa_aggverifier_push_known((engine or self.engine)._ctx, self.handle,
@@ -2387,20 +2509,48 @@ class AggregateVerifier(_LaneStore):
         return n
 
     def push_mixed_device(self, aggregator, d_places, d_result, d_rs49, d_pks, d_msgs, d_pk_inf=None, d_offsets=None,
-                          msg_len=None, msg_stride=None):
+                          msg_len=None, msg_stride=None, cache=None, require=0, want_stats=True):
         """device form: only enqueues on the engine's stream.  d_places: an int32 / uint32-valued tensor of n places on
         the engine's device (AGGV_UNKNOWN, or -1 as int32, for an unknown lane); the u unknown lanes as push_device
         takes them (u = the rows of d_pks; None: no unknown lane).  d_result (one int32 on the device) receives 0 for a
         valid list, 1 for a refused one, whose lanes are held as failed: every finish that reaches one answers MALFORMED.
-        Returns n."""
+        Returns n.
+        cache, require: as push_mixed (an affine cache).  Then the call is NOT enqueue-only -- it synchronises the
+        stream once per slice of the unknown keys, as push_device(cache=) does -- d_result gets bit 0 for an invalid
+        list and bit 1 for a known lane below the required class, and the call returns (n, stats or None)."""
+        require = self._mixed_cached_check(aggregator, cache, require, False)
         n = _dev_order(d_places, self.engine)
         _dev_result(d_result, self.engine)
         u = 0 if d_pks is None else int(d_pks.shape[0])
         stride, mlen = _dev_msg_shape(d_msgs, d_offsets, msg_len, msg_stride, no_msgs_ok=True) if u else (0, 0)
+        if cache is not None:
+            stats = np.zeros(8, dtype=np.uint64) if want_stats else None
+            _check(_lib.ssa_aggverifier_push_mixed_cached_device(
+                self.engine._ctx, self.handle, aggregator.handle, cache.handle, _addr(d_places), n, _addr(d_rs49),
+                _addr(d_pks), _addr(d_pk_inf), _addr(d_msgs), _addr(d_offsets), stride, mlen, u, require,
+                d_result.data_ptr(), stats.ctypes.data if want_stats else None), "ssa_aggverifier_push_mixed_cached_device")
+            return n, stats
         _check(_lib.ssa_aggverifier_push_mixed_device(
             self.engine._ctx, self.handle, aggregator.handle, _addr(d_places), n, _addr(d_rs49), _addr(d_pks), _addr(d_pk_inf),
             _addr(d_msgs), _addr(d_offsets), stride, mlen, u, d_result.data_ptr()), "ssa_aggverifier_push_mixed_device")
         return n
+
+    def push_mixed_wire_device(self, aggregator, d_places, d_result, d_rs49, d_pks49, d_msgs, d_offsets=None, msg_len=None,
+                               msg_stride=None, cache=None, require=0, want_stats=True):
+        """device form of push_mixed_wire: d_pks49 holds u x 49 bytes (None: no unknown lane) -> (n, stats or None).
+        Synchronises and reports as push_mixed_device(cache=...)."""
+        if cache is None:
+            raise ValueError("push_mixed_wire_device needs a key cache made with wire=True")
+        require = self._mixed_cached_check(aggregator, cache, require, True)
+        n = _dev_order(d_places, self.engine)
+        _dev_result(d_result, self.engine)
+        u, stride, mlen = self._push_device_args(d_pks49, d_msgs, d_offsets, msg_len, msg_stride, 49)
+        stats = np.zeros(8, dtype=np.uint64) if want_stats else None
+        _check(_lib.ssa_aggverifier_push_mixed_cached_wire_device(
+            self.engine._ctx, self.handle, aggregator.handle, cache.handle, _addr(d_places), n, _addr(d_rs49), _addr(d_pks49),
+            _addr(d_msgs), _addr(d_offsets), stride, mlen, u, require, d_result.data_ptr(),
+            stats.ctypes.data if want_stats else None), "ssa_aggverifier_push_mixed_cached_wire_device")
+        return n, stats
 
     def push_known_device(self, aggregator, d_places, d_result):
         """device form of push_known.  Returns n."""

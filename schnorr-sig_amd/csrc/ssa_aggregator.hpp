@@ -10,6 +10,11 @@
 //   tops    four words per COMPLETE block of B lanes: the top of its subtree
 //   keys    49 bytes per lane, only in an object created with SSA_AGGR_HOLD_KEYS49: the wire key of
 //           the lane's KeyedSignature record, verbatim -- the key column of the block body next to the aggregate
+//   adm     one byte per lane, only in an object created with SSA_AGGR_HOLD_ADMISSION: the class of
+//           the push that admitted the lane (SSA_ADM_*).  Written by agx_admit alone -- one hipMemsetAsync of
+//           adm[held, held + m) behind agx_k_append, the kept count being on the host by then -- moved with its lane by
+//           agx_k_move, read by ssa_aggregator_admission and by the mixed pushes of the streaming aggregate verifier
+//           (agv_k_classify_adm, agv_k_require in ssa_aggverifier.hpp).  finish, finish_select and keys do not touch it.
 //
 //   push    status vector (the screen of ssa_verify_batch_screened, the checks of ag_k_fold, or -- the cached pushes,
 //           section 31 -- the statuses of ssa_verify_many_cached / ssa_verify_keyed_many_cached) -> av_keep lists the kept
@@ -28,7 +33,7 @@
 //           whether the list is valid), the tree runs over the gathered leaves from the bottom -- the stored tops say
 //           nothing about another order -- and the coefficient fold is finish's.  The object is read, never written.
 //
-// The object's four (with the key column: five) arrays are its own allocations (released by destroy, or by the context's clean-up): they are not in
+// The object's four (with the key column and the admission column: up to six) arrays are its own allocations (released by destroy, or by the context's clean-up): they are not in
 // the context's list of workspaces, and nothing the object needs between two calls lives in one.
 #pragma once
 #include "ssa_aggregate.hpp"
@@ -51,17 +56,20 @@ struct AgxStore {
 };
 
 struct ssa_aggregator : AgxStore {
-    static constexpr uint32_t kCreateFlags = SSA_AGGR_HOLD_KEYS49;
+    static constexpr uint32_t kCreateFlags = SSA_AGGR_HOLD_KEYS49 | SSA_AGGR_HOLD_ADMISSION;
     uint64_t offered = 0, dropped = 0;
-    DevBuf wire, scal, keys;
+    DevBuf wire, scal, keys, adm;
     bool hold_keys() const { return (flags & SSA_AGGR_HOLD_KEYS49) != 0; }
+    bool hold_adm() const { return (flags & SSA_AGGR_HOLD_ADMISSION) != 0; }
 };
 // everything the object will ever hold, in the order it is allocated and released (the key column: only with the flag,
-// 49 bytes per lane and the rest of the last dword -- agx_k_move reads whole aligned dwords)
+// 49 bytes per lane and the rest of the last dword -- agx_k_move reads whole aligned dwords; the admission column: only
+// with its flag, one byte per lane, read and written as bytes)
 static inline std::vector<AgxStore::Buf> agx_bufs(ssa_aggregator &a) {
     std::vector<AgxStore::Buf> bufs{
         {&a.wire, 49 * a.capacity + 32}, {&a.scal, 32 * a.capacity}, {&a.leaves, 32 * a.capacity}, {&a.tops, 32 * a.n_tops()}};
     if (a.hold_keys()) bufs.push_back({&a.keys, 49 * a.capacity + 3});
+    if (a.hold_adm()) bufs.push_back({&a.adm, a.capacity + 16});
     return bufs;
 }
 template <class T>
@@ -202,7 +210,9 @@ agx_k_append(const DevParams *__restrict__ prm, const u8 *__restrict__ recs, u32
 // as it was before the call.  The walk starts at the first place whose content changes: nothing in front of it is
 // written, not even with its own value.  The argument speaks of PLACES, not of arrays: the key column is a fourth array
 // indexed by the same places, gathered by the same launch and copied back by a fourth copy behind the other three, so
-// (a), (b) and (c) cover it unchanged.
+// (a), (b) and (c) cover it unchanged.  So they do the admission column (adm: one byte per place, nullptr without it),
+// gathered by the same launch -- thread t stores the one byte st_adm[t], so no two lanes write one staging byte and
+// nothing outside [0, cnt) is written -- and copied back by one more copy behind the others.
 //
 // The 49-byte stride.  The staging of a piece starts dword-aligned (each 49-byte part of it does), so the piece is a
 // column of agx_put49 with d0 = 0, d1 = 49 cnt and lane t at place t; the next lane's source is the column at
@@ -212,7 +222,8 @@ agx_k_append(const DevParams *__restrict__ prm, const u8 *__restrict__ recs, u32
 __global__ void __launch_bounds__(256)
 agx_k_move(const u32 *__restrict__ kept, size_t shift, size_t c0, size_t cnt, const u64 *__restrict__ leaves,
            const u64 *__restrict__ scal, const u8 *__restrict__ wire, const u8 *__restrict__ keys,
-           u64 *__restrict__ st_leaves, u64 *__restrict__ st_scal, u8 *__restrict__ st_wire, u8 *__restrict__ st_keys) {
+           const u8 *__restrict__ adm, u64 *__restrict__ st_leaves, u64 *__restrict__ st_scal, u8 *__restrict__ st_wire,
+           u8 *__restrict__ st_keys, u8 *__restrict__ st_adm) {
     const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= cnt) return;
     const size_t src = kept ? (size_t)kept[c0 + t] : c0 + t + shift;
@@ -228,6 +239,7 @@ agx_k_move(const u32 *__restrict__ kept, size_t shift, size_t c0, size_t cnt, co
     const size_t nsrc = t + 1 < cnt ? (kept ? (size_t)kept[c0 + t + 1] : src + 1) : src;
     agx_put49<true>(st_wire, 0, 49 * cnt, t, wire + 49 * src, wire + 49 * nsrc);
     if (keys) agx_put49<true>(st_keys, 0, 49 * cnt, t, keys + 49 * src, keys + 49 * nsrc);
+    if (adm) st_adm[t] = adm[src];
 }
 
 // out[0] = the first place whose content a removal changes: the first c with kept[c] != c, or m when the m kept lanes

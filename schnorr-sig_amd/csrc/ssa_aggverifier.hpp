@@ -16,7 +16,8 @@
 //           while the host flag `keyed` is on, and then every byte of kst[0, held) has been written by the push that
 //           brought its lane.  `keyed` turns on at the first push through a cache, which zeroes kst[0, held) on the
 //           context's stream first; from then on the cached pushes write their lanes' bytes through agc_k_expand and
-//           the plain push writes its n bytes with one hipMemsetAsync; reset turns it off.  So bytes that a failed push
+//           the plain push writes its n bytes with one hipMemsetAsync (a mixed push: zeros in its classification, and,
+//           through a cache, the unknown lanes' statuses by agv_k_kst_at behind them); reset turns it off.  So bytes that a failed push
 //           left behind `held`, or that an earlier life of the object left anywhere, are overwritten before they can be
 //           read as a status, and an object that never sees a cached push enqueues exactly what it did without kst.
 //
@@ -47,6 +48,15 @@
 //           behind the device's count are sentinels with zero digits); agv_k_known_fold sums S = sum a_i s_i over the
 //           known lanes (the term of agx_k_coeff_fold at the lane's true place); agv_k_known_close hands
 //           e_agg - S mod q to ag_k_finish_scalar, or, with no unknown lane at all, writes the verdict itself.
+//
+//   push_mixed_cached   the u compact keys through the key cache first, slice by slice as a cached
+//           push's (agc_begin, agc_slices: the dense statuses into ctx->agc_kst, wire keys expanded into the context's
+//           buffers), then push_mixed over the expanded keys with two differences: the classification also reads the
+//           pool's admission class of a known lane and refuses one below `require` as it refuses a place out of range
+//           (agv_k_classify_adm; bit 1 of the flag word), and behind agv_k_append_at agv_k_kst_at scatters the dense
+//           statuses to the lanes' true places, kst[held + pos[j]] = status[j] -- behind agv_k_classify_adm on the same
+//           stream, which wrote zeros there.  The first such push turns `keyed` on by kst's rule.  The host forms
+//           with require > 0 run agv_k_require over the uploaded places and read its word before anything is touched.
 //
 // The object's eight arrays are its own allocations (released by destroy, or by the context's clean-up): they are not in
 // the context's list of workspaces, and nothing the object needs between two calls lives in one.
@@ -179,18 +189,25 @@ agv_k_append_at(const DevParams *__restrict__ prm, const u8 *__restrict__ sigs, 
 // ag_held, and a thread whose place fails forms no address into the pool.  known[.] = 1 for every lane that is not
 // unknown; kst (nullptr: the object is not keyed) = 0, "not checked", for every lane.
 constexpr u32 AGV_UNKNOWN = 0xFFFFFFFFu;
-__global__ void __launch_bounds__(256)
-agv_k_classify(const u32 *__restrict__ places, size_t n, size_t held, size_t ag_held, const u64 *__restrict__ ag_leaves,
-               const u64 *__restrict__ ag_scal, u64 *__restrict__ leaves, u64 *__restrict__ h, u64 *__restrict__ rpts,
-               u64 *__restrict__ ppts, u8 *__restrict__ bad, u8 *__restrict__ kst, u8 *__restrict__ known,
-               u8 *__restrict__ keep, u32 *__restrict__ flag) {
+// (the body, written once.  ADM: the push requires an admission class -- adm is the pool's admission column, one byte
+// per place, and a known lane with adm[p] < require is refused as a place out of range is, raising bit 1 of *flag where
+// that raises bit 0.  adm[p] is read only for a place that compared below ag_held: the rule above covers it.)
+template <bool ADM>
+static __device__ __forceinline__ void
+agv_classify_lane(const u32 *__restrict__ places, size_t n, size_t held, size_t ag_held, const u64 *__restrict__ ag_leaves,
+                  const u64 *__restrict__ ag_scal, const u8 *__restrict__ adm, u32 require, u64 *__restrict__ leaves,
+                  u64 *__restrict__ h, u64 *__restrict__ rpts, u64 *__restrict__ ppts, u8 *__restrict__ bad,
+                  u8 *__restrict__ kst, u8 *__restrict__ known, u8 *__restrict__ keep, u32 *__restrict__ flag) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const u32 p = places[i];
     const bool unknown = p == AGV_UNKNOWN, in_range = !unknown && (size_t)p < ag_held;
+    bool below = false;
+    if (ADM && in_range) below = (u32)adm[p] < require;
+    const bool taken = in_range && !below;
     const ulonglong2 zero = make_ulonglong2(0, 0);
     ulonglong2 l0 = zero, l1 = zero, s0 = zero, s1 = zero;
-    if (in_range) {
+    if (taken) {
         const size_t src = p;
         const ulonglong2 *l = reinterpret_cast<const ulonglong2 *>(ag_leaves + 4 * src);
         const ulonglong2 *s = reinterpret_cast<const ulonglong2 *>(ag_scal + 4 * src);
@@ -211,16 +228,66 @@ agv_k_classify(const u32 *__restrict__ places, size_t n, size_t held, size_t ag_
         rd[k] = zero;
         pd[k] = zero;
     }
-    const bool refused = !unknown && !in_range;
+    const bool refused = !unknown && !taken;
     bad[dst] = (u8)(refused ? 1u : 0u);
     known[dst] = (u8)(unknown ? 0u : 1u);
     if (kst) kst[dst] = 0;
     keep[i] = (u8)(unknown ? 0u : 1u);
-    if (refused) atomicOr(flag, 1u);
+    if (refused) atomicOr(flag, below ? 2u : 1u);
 }
 
-// The last launch of a mixed push before the tree: *result = 0 for a valid list, 1 for a refused one -- a place out of
-// range raised *flag, or the list holds *m_dev sentinels where the caller announced u.  In the second case nobody knows
+__global__ void __launch_bounds__(256)
+agv_k_classify(const u32 *__restrict__ places, size_t n, size_t held, size_t ag_held, const u64 *__restrict__ ag_leaves,
+               const u64 *__restrict__ ag_scal, u64 *__restrict__ leaves, u64 *__restrict__ h, u64 *__restrict__ rpts,
+               u64 *__restrict__ ppts, u8 *__restrict__ bad, u8 *__restrict__ kst, u8 *__restrict__ known,
+               u8 *__restrict__ keep, u32 *__restrict__ flag) {
+    agv_classify_lane<false>(places, n, held, ag_held, ag_leaves, ag_scal, nullptr, 0u, leaves, h, rpts, ppts, bad, kst, known,
+                             keep, flag);
+}
+
+// The same launch for a push that requires an admission class (require is 1 or 2, adm the
+// admission column of a pool created with SSA_AGGR_HOLD_ADMISSION, ag_held bytes of it written).
+__global__ void __launch_bounds__(256)
+agv_k_classify_adm(const u32 *__restrict__ places, size_t n, size_t held, size_t ag_held, const u64 *__restrict__ ag_leaves,
+                   const u64 *__restrict__ ag_scal, const u8 *__restrict__ adm, u32 require, u64 *__restrict__ leaves,
+                   u64 *__restrict__ h, u64 *__restrict__ rpts, u64 *__restrict__ ppts, u8 *__restrict__ bad,
+                   u8 *__restrict__ kst, u8 *__restrict__ known, u8 *__restrict__ keep, u32 *__restrict__ flag) {
+    agv_classify_lane<true>(places, n, held, ag_held, ag_leaves, ag_scal, adm, require, leaves, h, rpts, ppts, bad, kst, known,
+                            keep, flag);
+}
+
+// The pre-check of the host forms with require > 0: one thread per position of the uploaded list, nothing but the word
+// is written.  *flag (cleared in front) gets bit 1 for a known place whose class is below `require` and bit 0 for a
+// place out of range (the host checked the range itself: cannot be).  adm[p] is read only for p < ag_held.
+__global__ void __launch_bounds__(256)
+agv_k_require(const u32 *__restrict__ places, size_t n, size_t ag_held, const u8 *__restrict__ adm, u32 require,
+              u32 *__restrict__ flag) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const u32 p = places[i];
+    if (p == AGV_UNKNOWN) return;
+    if ((size_t)p >= ag_held) {
+        atomicOr(flag, 1u);
+        return;
+    }
+    if ((u32)adm[p] < require) atomicOr(flag, 2u);
+}
+
+// Behind agv_k_append_at in a mixed push through a key cache: the key status of compact lane j, status[j] as
+// agc_k_expand wrote it, goes to the lane's true place, kst[pos[j]] (kst: the object's array from lane `held` on; pos
+// and *m_dev as in agv_k_append_at: every entry below the n of the push).  j >= *m_dev: no place, nothing is written --
+// the push is refused as a whole.  Distinct j have distinct pos[j]: no two threads write one byte.
+__global__ void __launch_bounds__(256)
+agv_k_kst_at(const u8 *__restrict__ status, size_t u, const u32 *__restrict__ pos, const u32 *__restrict__ m_dev,
+             u8 *__restrict__ kst) {
+    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= u || j >= (size_t)*m_dev) return;
+    kst[pos[j]] = status[j];
+}
+
+// The last launch of a mixed push before the tree: *result = 0 for a valid list; bit 0 for a refused one -- a place out
+// of range raised bit 0 of *flag, or the list holds *m_dev sentinels where the caller announced u -- and bit 1 where a
+// known lane was below the required class (bit 1 of *flag: agv_k_classify_adm alone raises it).  In the second case nobody knows
 // which compact lane belongs where, so EVERY lane of the push is marked bad (behind agv_k_append_at on the stream, which
 // writes the byte of the lanes it fills).  A valid list costs every thread two reads.  Grid-stride over the n lanes.
 __global__ void __launch_bounds__(256)
@@ -228,7 +295,10 @@ agv_k_mixed_close(const u32 *__restrict__ m_dev, u32 u, const u32 *__restrict__ 
                   u32 *__restrict__ result) {
     const bool miscount = *m_dev != u;
     const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x, step = (size_t)gridDim.x * blockDim.x;
-    if (g == 0) *result = miscount || *flag ? 1u : 0u;
+    if (g == 0) {
+        const u32 f = *flag;
+        *result = (miscount || (f & 1u) ? 1u : 0u) | (f & 2u);
+    }
     if (!miscount) return;
     for (size_t i = g; i < n; i += step) bad[i] = 1;
 }

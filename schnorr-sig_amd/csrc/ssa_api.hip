@@ -2803,17 +2803,35 @@ extern "C" int ssa_debug_aggregator_plan(uint64_t held, uint64_t m, uint64_t blo
     return 0;
 }
 
-extern "C" int ssa_debug_aggregator_bytes(size_t capacity, size_t block_lanes, uint32_t flags, uint64_t out[5]) {
+// the eight words of ssa_debug_aggregator_bytes_ex: each optional column has its own word, whichever flags are set
+static int agx_bytes_words(size_t capacity, size_t block_lanes, uint32_t flags, uint64_t w[8]) {
     const size_t B = agx_block(block_lanes);
-    if (!out || (flags & ~ssa_aggregator::kCreateFlags) || capacity == 0 || capacity > SSA_MAX_BATCH || !B) return SSA_ERR_ARG;
+    if ((flags & ~ssa_aggregator::kCreateFlags) || capacity == 0 || capacity > SSA_MAX_BATCH || !B) return SSA_ERR_ARG;
     ssa_aggregator a;          // (never allocated: agx_bufs only says what create would reserve)
     a.capacity = capacity;
     a.block = B;
     a.flags = flags;
-    std::fill(out, out + 5, (uint64_t)0);
+    std::fill(w, w + 8, (uint64_t)0);
     size_t k = 0;
-    for (const AgxStore::Buf &b : agx_bufs(a)) out[k++] = b.bytes;
+    for (const AgxStore::Buf &b : agx_bufs(a)) {
+        if (b.buf == &a.keys) k = 4;
+        if (b.buf == &a.adm) k = 5;
+        w[k++] = b.bytes;
+    }
     return 0;
+}
+
+// (five words, as before the admission column existed: the flag is accepted, the column is not reported here)
+extern "C" int ssa_debug_aggregator_bytes(size_t capacity, size_t block_lanes, uint32_t flags, uint64_t out[5]) {
+    uint64_t w[8];
+    if (!out) return SSA_ERR_ARG;
+    if (int rc = agx_bytes_words(capacity, block_lanes, flags, w)) return rc;
+    std::copy(w, w + 5, out);
+    return 0;
+}
+
+extern "C" int ssa_debug_aggregator_bytes_ex(size_t capacity, size_t block_lanes, uint32_t flags, uint64_t out[8]) {
+    return out ? agx_bytes_words(capacity, block_lanes, flags, out) : SSA_ERR_ARG;
 }
 
 extern "C" int ssa_aggregator_create(ssa_ctx *ctx, size_t capacity, size_t block_lanes, uint32_t flags, ssa_aggregator **out) {
@@ -2824,7 +2842,8 @@ extern "C" int ssa_aggregator_create(ssa_ctx *ctx, size_t capacity, size_t block
 
 extern "C" void ssa_aggregator_destroy(ssa_aggregator *ag) { agx_destroy(ag, &ssa_ctx::aggregators); }
 
-// Nothing on the device needs clearing: every array is written before it is read, up to `held`.
+// Nothing on the device needs clearing: every array is written before it is read, up to `held` (the admission column
+// too: it is forgotten with the lanes).
 extern "C" int ssa_aggregator_reset(ssa_aggregator *ag) {
     if (!ag || !ag->ctx) return SSA_ERR_ARG;
     ag->held = 0;
@@ -2914,9 +2933,11 @@ static int agx_root(const AgxStore &s, size_t n) {
 // The tail of every push, behind the n statuses of its admission (with the raw digests of all n lanes in ctx->ag_dig):
 // the kept lanes are listed (av_keep, one synchronisation for their number), appended -- the lanes are records of
 // `stride` bytes at d_recs with the signature at `off`, and an object with a key column keeps the records' first 49
-// bytes -- the blocks this push completed are reduced, and the object counts the push.
+// bytes -- the blocks this push completed are reduced, and the object counts the push.  adm_class (SSA_ADM_*): what this
+// kind of push establishes of a lane it keeps; an object with an admission column records it for the m kept lanes, one
+// memset behind the append (the count is on the host by then).
 static int agx_admit(ssa_ctx *ctx, ssa_aggregator *ag, const u8 *d_status, size_t n, const u8 *d_recs, u32 stride, u32 off,
-                     uint64_t *n_kept_out) {
+                     u32 adm_class, uint64_t *n_kept_out) {
     if (ctx->agx_kept.reserve(n * sizeof(u32))) return SSA_ERR_HIP;
     uint64_t m = 0;
     if (int rc = av_keep(ctx, d_status, n, (u32 *)ctx->agx_kept.p, &m)) return rc;
@@ -2928,6 +2949,7 @@ static int agx_admit(ssa_ctx *ctx, ssa_aggregator *ag, const u8 *d_status, size_
                                ag->hold_keys() ? (u8 *)ag->keys.p : (u8 *)nullptr);
         });
         if (rc) return rc;
+        if (ag->hold_adm()) HIP_TRY(hipMemsetAsync((u8 *)ag->adm.p + ag->held, (int)adm_class, m, ctx->stream));
         const AgxPlan p = agx_plan(ag->held, m, ag->block);
         if (p.count)
             if ((rc = agx_reduce_blocks(*ag, p))) return rc;
@@ -2970,7 +2992,7 @@ extern "C" int ssa_aggregator_push_device(ssa_ctx *ctx, ssa_aggregator *ag, cons
         });
         if (rc) return rc;
     }
-    return agx_admit(ctx, ag, d_status, n, d_sigs, 81, 0, n_kept_out);
+    return agx_admit(ctx, ag, d_status, n, d_sigs, 81, 0, screen ? SSA_ADM_SCREENED : SSA_ADM_UNSCREENED, n_kept_out);
 }
 
 extern "C" int ssa_aggregator_push(ssa_ctx *ctx, ssa_aggregator *ag, const uint8_t *sigs, const uint8_t *pks,
@@ -3072,6 +3094,28 @@ extern "C" int ssa_aggregator_keys(ssa_ctx *ctx, ssa_aggregator *ag, size_t n_ta
     return hc.finish([&] { return ssa_aggregator_keys_device(ctx, ag, n, d_keys); });
 }
 
+// ---- the admission column (SSA_AGGR_HOLD_ADMISSION)
+// Only enqueues: one device-to-device copy.  Changes no state of the object.
+extern "C" int ssa_aggregator_admission_device(ssa_ctx *ctx, ssa_aggregator *ag, size_t n_take, uint8_t *d_adm_out) {
+    size_t n;
+    if (int rc = agx_take(ctx, ag, n_take, &n)) return rc;
+    if (!ag->hold_adm() || (n && !d_adm_out)) return SSA_ERR_ARG;
+    if (n == 0) return SSA_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipMemcpyAsync(d_adm_out, ag->adm.p, n, hipMemcpyDeviceToDevice, ctx->stream));
+    return SSA_OK;
+}
+
+extern "C" int ssa_aggregator_admission(ssa_ctx *ctx, ssa_aggregator *ag, size_t n_take, uint8_t *adm_out) {
+    size_t n;
+    if (int rc = agx_take(ctx, ag, n_take, &n)) return rc;
+    if (!ag->hold_adm() || (n && !adm_out)) return SSA_ERR_ARG;
+    if (n == 0) return SSA_OK;
+    HostCall hc(ctx);
+    u8 *d_adm = hc.out(ctx->st_aux, adm_out, n, 16);
+    return hc.finish([&] { return ssa_aggregator_admission_device(ctx, ag, n, d_adm); });
+}
+
 // ---- removing lanes in place (the move and its hazard: agx_k_move in ssa_aggregator.hpp)
 // (a first_changed of 0 is planned as the front drop of held - new_held lanes: see the header)
 extern "C" int ssa_debug_aggregator_remove_plan(uint64_t held, uint64_t first_changed, uint64_t new_held,
@@ -3087,18 +3131,21 @@ extern "C" int ssa_debug_aggregator_remove_plan(uint64_t held, uint64_t first_ch
 }
 
 // The staging of P gathered lanes (a piece of the move, a selection) in `buf`: P leaves, P scalars, 49 P bytes of R's and
-// -- with_keys -- 49 P bytes of keys behind the R's part rounded up to a dword (each part dword-aligned, and more).
+// -- with_keys -- 49 P bytes of keys behind the R's part rounded up to a dword (each part dword-aligned, and more);
+// -- with_adm -- P bytes of admission classes behind everything else (bytes: any alignment does).
 struct AgxStage {
     u64 *leaves, *scal;
-    u8 *wire, *keys;
+    u8 *wire, *keys, *adm;
 };
-static int agx_stage_layout(DevBuf &buf, size_t P, bool with_keys, AgxStage *st) {
+static int agx_stage_layout(DevBuf &buf, size_t P, bool with_keys, AgxStage *st, bool with_adm = false) {
     const size_t wire_part = with_keys ? (49 * P + 3) & ~(size_t)3 : 49 * P;
-    if (buf.reserve(64 * P + wire_part + (with_keys ? 49 * P : 0) + 16)) return SSA_ERR_HIP;
+    const size_t front = 64 * P + wire_part + (with_keys ? 49 * P : 0);
+    if (buf.reserve(front + 16 + (with_adm ? P + 16 : 0))) return SSA_ERR_HIP;
     st->leaves = (u64 *)buf.p;
     st->scal = st->leaves + 4 * P;
     st->wire = (u8 *)(st->scal + 4 * P);
     st->keys = with_keys ? st->wire + wire_part : nullptr;
+    st->adm = with_adm ? (u8 *)buf.p + front + 16 : nullptr;
     return 0;
 }
 
@@ -3112,21 +3159,21 @@ static int agx_remove_apply(ssa_aggregator *ag, const u32 *d_kept, size_t f, siz
     const AgxRemovePlan p = agx_remove_plan(held, f, m, B, !d_kept);
     const size_t P = f < m ? std::min(ags_piece(ctx), m - f) : 0, top0 = shift / B;
     const bool tops_overlap = p.moved && top0 < p.moved;
-    const bool hold = ag->hold_keys();
+    const bool hold = ag->hold_keys(), hold_adm = ag->hold_adm();
     AgxStage st{};
-    if ((P && agx_stage_layout(ctx->agx_stage, P, hold, &st)) || (tops_overlap && ctx->ags_tops.reserve((size_t)p.moved * 32)))
+    if ((P && agx_stage_layout(ctx->agx_stage, P, hold, &st, hold_adm)) || (tops_overlap && ctx->ags_tops.reserve((size_t)p.moved * 32)))
         return SSA_ERR_HIP;
     u64 *st_leaves = st.leaves, *st_scal = st.scal;
-    u8 *st_wire = st.wire, *st_keys = st.keys;
+    u8 *st_wire = st.wire, *st_keys = st.keys, *st_adm = st.adm;
     u64 *leaves = (u64 *)ag->leaves.p, *scal = (u64 *)ag->scal.p, *tops = (u64 *)ag->tops.p;
-    u8 *wire = (u8 *)ag->wire.p, *keys = hold ? (u8 *)ag->keys.p : nullptr;
+    u8 *wire = (u8 *)ag->wire.p, *keys = hold ? (u8 *)ag->keys.p : nullptr, *adm = hold_adm ? (u8 *)ag->adm.p : nullptr;
     const int rc = [&]() -> int {
         for (size_t c0 = f; c0 < m; c0 += P) {
             const size_t cnt = std::min(P, m - c0);
             const int r = timed_launch(ctx, "agx_k_move", [&] {
                 hipLaunchKernelGGL(agx_k_move, dim3(grid_for(cnt, 256)), dim3(256), 0, ctx->stream, d_kept, shift, c0, cnt,
-                                   (const u64 *)leaves, (const u64 *)scal, (const u8 *)wire, (const u8 *)keys, st_leaves,
-                                   st_scal, st_wire, st_keys);
+                                   (const u64 *)leaves, (const u64 *)scal, (const u8 *)wire, (const u8 *)keys, (const u8 *)adm,
+                                   st_leaves, st_scal, st_wire, st_keys, st_adm);
             });
             if (r) return r;
             // behind the gather on the stream, in front of the next piece's: places [c0, c0 + cnt) alone are written
@@ -3134,6 +3181,7 @@ static int agx_remove_apply(ssa_aggregator *ag, const u32 *d_kept, size_t f, siz
             HIP_TRY(hipMemcpyAsync(scal + 4 * c0, st_scal, 32 * cnt, hipMemcpyDeviceToDevice, ctx->stream));
             HIP_TRY(hipMemcpyAsync(wire + 49 * c0, st_wire, 49 * cnt, hipMemcpyDeviceToDevice, ctx->stream));
             if (hold) HIP_TRY(hipMemcpyAsync(keys + 49 * c0, st_keys, 49 * cnt, hipMemcpyDeviceToDevice, ctx->stream));
+            if (hold_adm) HIP_TRY(hipMemcpyAsync(adm + c0, st_adm, cnt, hipMemcpyDeviceToDevice, ctx->stream));
         }
         if (p.moved) {       // new block b is old block b + top0; a copy onto its own source goes through a workspace
             const size_t bytes = (size_t)p.moved * 32;
@@ -3641,11 +3689,20 @@ static int agv_mixed_args(const ssa_ctx *ctx, const ssa_aggverifier *av, const s
     return n > ctx->knobs.msm_slice || n > av->capacity - av->held ? SSA_ERR_ARG : 0;
 }
 
+// What a mixed push through a key cache adds to the body (all zero: the push of section 34, which
+// then enqueues exactly what it did): require > 0 -- the pool's admission column is read and a known lane below the
+// class is refused (agv_k_classify_adm in place of agv_k_classify); d_kst -- the dense key statuses of the u compact
+// lanes, scattered to their places behind agv_k_append_at (agv_k_kst_at); the object is keyed by then.
+struct AgvMixedCached {
+    u32 require = 0;
+    const u8 *d_kst = nullptr;
+};
+
 // The body of both forms behind the argument checks.  Only enqueues: whether the list is valid is decided on the device
 // (agv_k_classify, agv_k_mixed_close) and lands in *d_result_out.
 static int agv_push_mixed_body(ssa_ctx *ctx, ssa_aggverifier *av, const ssa_aggregator *ag, const u32 *d_places, size_t n,
                                size_t u, const u8 *d_rs49, const u8 *d_pks, const u8 *d_pk_inf, const MsgView &mv,
-                               u32 *d_result_out) {
+                               u32 *d_result_out, const AgvMixedCached &mc = {}) {
     if (n == 0) {
         HIP_TRY(hipMemsetAsync(d_result_out, 0, sizeof(u32), ctx->stream));
         av->pushes++;
@@ -3660,7 +3717,12 @@ static int agv_push_mixed_body(ssa_ctx *ctx, ssa_aggverifier *av, const ssa_aggr
     HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(u32), ctx->stream));
     u8 *d_keep = (u8 *)ctx->agv_keep.p;
     u32 *d_pos = (u32 *)ctx->agv_pos.p;
-    int rc = timed_launch(ctx, "agv_k_classify", [&] {
+    int rc = mc.require ? timed_launch(ctx, "agv_k_classify_adm", [&] {
+        hipLaunchKernelGGL(agv_k_classify_adm, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, d_places, n, held, ag->held,
+                           (const u64 *)ag->leaves.p, (const u64 *)ag->scal.p, (const u8 *)ag->adm.p, mc.require,
+                           (u64 *)av->leaves.p, (u64 *)av->h.p, (u64 *)av->rpts.p, (u64 *)av->ppts.p, (u8 *)av->bad.p,
+                           av->keyed ? (u8 *)av->kst.p : (u8 *)nullptr, (u8 *)av->known.p, d_keep, d_flag);
+    }) : timed_launch(ctx, "agv_k_classify", [&] {
         hipLaunchKernelGGL(agv_k_classify, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, d_places, n, held, ag->held,
                            (const u64 *)ag->leaves.p, (const u64 *)ag->scal.p, (u64 *)av->leaves.p, (u64 *)av->h.p,
                            (u64 *)av->rpts.p, (u64 *)av->ppts.p, (u8 *)av->bad.p, av->keyed ? (u8 *)av->kst.p : (u8 *)nullptr,
@@ -3680,6 +3742,14 @@ static int agv_push_mixed_body(ssa_ctx *ctx, ssa_aggverifier *av, const ssa_aggr
                                (u64 *)av->leaves.p, (u64 *)av->h.p, (u64 *)av->rpts.p, (u64 *)av->ppts.p, (u8 *)av->bad.p);
         });
         if (rc) return rc;
+        // the unknown lanes' key statuses to their true places: behind the classification, which wrote zeros there
+        if (mc.d_kst) {
+            rc = timed_launch(ctx, "agv_k_kst_at", [&] {
+                hipLaunchKernelGGL(agv_k_kst_at, dim3(grid_for(u, 256)), dim3(256), 0, ctx->stream, mc.d_kst, u,
+                                   (const u32 *)d_pos, d_m, (u8 *)av->kst.p + held);
+            });
+            if (rc) return rc;
+        }
     }
     rc = timed_launch(ctx, "agv_k_mixed_close", [&] {
         hipLaunchKernelGGL(agv_k_mixed_close, dim3(std::min(grid_for(n, 256), 1024u)), dim3(256), 0, ctx->stream, d_m, (u32)u,
@@ -3695,6 +3765,7 @@ static int agv_push_mixed_body(ssa_ctx *ctx, ssa_aggverifier *av, const ssa_aggr
     av->held += n;
     av->pushes++;
     av->pushed += n;
+    if (mc.d_kst) av->cached += u;
     return SSA_OK;
 }
 
@@ -4396,6 +4467,157 @@ extern "C" int ssa_aggverifier_push_cached_wire(ssa_ctx *ctx, ssa_aggverifier *a
     return agv_push_cached_host(ctx, av, kc, rs49, pks49, nullptr, true, msgs, msg_off, msg_stride, msg_len, n, stats_out);
 }
 
+// ------------------------------------------------------------------ a block against the pool through the key cache
+// The cache in front of the mixed push of section 34, as agv_push_cached_run puts it in front of the plain push: the u
+// compact keys go through the cache in slices of at most lane_slice lanes; agc_k_expand leaves their statuses DENSE in
+// ctx->agc_kst (a compact lane's place in the object is known only on the device) and, for wire keys, the keys and
+// flags in the context's u-lane buffers; the body then scatters the statuses behind its append (agv_k_kst_at).  The
+// first such push turns `keyed` on behind a zeroing of kst[0, held).  require > 0: the classification reads the pool's
+// admission column.  One synchronisation per slice, the dedup's; none without an unknown lane.
+// what all four forms refuse before anything is enqueued, counted or written
+static int agv_mixed_cached_args(const ssa_ctx *ctx, const ssa_aggverifier *av, const ssa_aggregator *ag,
+                                 const ssa_keycache *kc, bool wire, const uint32_t *places, size_t n, size_t u,
+                                 const MsgView &mv, const void *rs49, const void *keys, uint32_t require, bool device) {
+    if (int rc = agc_check_cache(ctx, kc, wire)) return rc;
+    if (int rc = agv_mixed_args(ctx, av, ag, places, n, u, mv, rs49, keys, device)) return rc;
+    return require > SSA_ADM_KEY_CHECKED || (require && !ag->hold_adm()) ? SSA_ERR_ARG : 0;
+}
+
+// n >= 1, the context's device selected
+static int agv_push_mixed_cached_run(ssa_ctx *ctx, ssa_aggverifier *av, const ssa_aggregator *ag, ssa_keycache *kc,
+                                     const u32 *d_places, size_t n, size_t u, const u8 *d_rs49, const u8 *d_keys,
+                                     const u8 *d_pk_inf, bool wire, const MsgView &mv, u32 require, u32 *d_result_out,
+                                     uint64_t *sv) {
+    AgvMixedCached mc;
+    mc.require = require;
+    if (u)
+        if (int rc = agc_begin(ctx, wire, u, true)) return rc;
+    if (!av->keyed) {
+        if (av->held) HIP_TRY(hipMemsetAsync(av->kst.p, 0, av->held, ctx->stream));
+        av->keyed = true;
+    }
+    DevBatch U{};
+    if (u) {
+        if (int rc = agc_slices(ctx, kc, d_keys, d_pk_inf, wire, u, (u8 *)ctx->agc_kst.p, sv, &U)) return rc;
+        mc.d_kst = (const u8 *)ctx->agc_kst.p;
+    }
+    return agv_push_mixed_body(ctx, av, ag, d_places, n, u, d_rs49, U.pks, U.pk_inf, mv, d_result_out, mc);
+}
+
+static int agv_push_mixed_cached_dev(ssa_ctx *ctx, ssa_aggverifier *av, ssa_aggregator *ag, ssa_keycache *kc,
+                                     const uint32_t *d_places, size_t n, const u8 *d_rs49, const u8 *d_keys,
+                                     const u8 *d_pk_inf, bool wire, const MsgView &mv, size_t u, uint32_t require,
+                                     uint32_t *d_result_out, uint64_t stats_out[8]) {
+    if (int rc = agv_mixed_cached_args(ctx, av, ag, kc, wire, d_places, n, u, mv, d_rs49, d_keys, require, true)) return rc;
+    if (!d_result_out) return SSA_ERR_ARG;
+    uint64_t sv[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    const unsigned long long none[AGC_CNT_WORDS] = {0, 0};
+    agc_stats_out(stats_out, sv, none, false);
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (n == 0) return agv_push_mixed_body(ctx, av, ag, d_places, 0, 0, nullptr, nullptr, nullptr, mv, d_result_out);
+    if (int rc = agv_push_mixed_cached_run(ctx, av, ag, kc, d_places, n, u, d_rs49, d_keys, d_pk_inf, wire, mv, require,
+                                           d_result_out, sv))
+        return rc;
+    return u ? agc_stats_dev(ctx, stats_out, sv, false) : 0;      // (no unknown lane: the cache was not asked)
+}
+
+// The list is on the host, the classes are on the device: the host refuses what push_mixed refuses, and with
+// require > 0 agv_k_require reads the classes of the uploaded places -- its word is read before the cache or the object
+// is touched.
+static int agv_push_mixed_cached_host(ssa_ctx *ctx, ssa_aggverifier *av, ssa_aggregator *ag, ssa_keycache *kc,
+                                      const uint32_t *places, size_t n, const uint8_t *rs49, const uint8_t *keys,
+                                      const uint8_t *pk_inf, bool wire, const uint8_t *msgs, const uint64_t *msg_off,
+                                      size_t msg_stride, size_t msg_len, size_t u, uint32_t require, uint64_t stats_out[8]) {
+    if (int rc = agv_mixed_cached_args(ctx, av, ag, kc, wire, places, n, u, {msgs, msg_off, msg_stride, msg_len}, rs49, keys,
+                                       require, false))
+        return rc;
+    if (int rc = check_host_offsets(msg_off, u)) return rc;
+    size_t sentinels = 0;
+    for (size_t i = 0; i < n; i++) {
+        if (places[i] == SSA_AGGV_UNKNOWN) sentinels++;
+        else if (places[i] >= ag->held) return SSA_ERR_ARG;
+    }
+    if (sentinels != u) return SSA_ERR_ARG;
+    uint64_t sv[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned long long cnt[AGC_CNT_WORDS] = {0, 0};
+    agc_stats_out(stats_out, sv, cnt, false);
+    if (n == 0) {
+        av->pushes++;
+        return SSA_OK;
+    }
+    HostCall hc(ctx);
+    const u32 *d_places = hc.in<u32>(ctx->agv_places, places, n * sizeof(u32));
+    // (reserved here at the size the body asks for: the words do not move under it)
+    if (hc.ok() && ctx->agv_misc.reserve(AGV_MISC_BYTES)) hc.rc = SSA_ERR_HIP;
+    if (!hc.ok()) return hc.rc;
+    if (require) {
+        u32 below = 0, *d_flag = (u32 *)agv_misc(ctx, AGV_PUSH_FLAG);
+        hc.step([&]() -> int {
+            HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(u32), ctx->stream));
+            if (int rc = timed_launch(ctx, "agv_k_require", [&] {
+                    hipLaunchKernelGGL(agv_k_require, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, d_places, n, ag->held,
+                                       (const u8 *)ag->adm.p, require, d_flag);
+                }))
+                return rc;
+            HIP_TRY(hipMemcpyAsync(&below, d_flag, sizeof below, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(hipStreamSynchronize(ctx->stream));
+            return 0;
+        });
+        if (!hc.ok()) return hc.rc;
+        if (below) return SSA_ERR_ARG;       // object, cache and info untouched
+    }
+    DevBatch b{};
+    if (u) b = hc.lanes({rs49, keys, pk_inf, msgs, msg_off, msg_stride, msg_len}, u * 49, u, wire);
+    u32 refused = 0, *d_result = (u32 *)agv_misc(ctx, AGV_RESULT);
+    hc.copy_back(&refused, d_result, sizeof refused);
+    if (u) (void)hc.out(ctx->agc_cnt, cnt, sizeof cnt, 48);      // (copied back behind the push, as a cached push's)
+    const int rc = hc.finish([&] {
+        return agv_push_mixed_cached_run(ctx, av, ag, kc, d_places, n, u, b.sigs, b.pks, b.pk_inf, wire,
+                                         {b.msgs.msgs, b.msgs.off, msg_stride, msg_len}, require, d_result, sv);
+    });
+    if (rc) return rc;
+    agc_stats_out(stats_out, sv, cnt, false);
+    return refused ? SSA_ERR_HIP : SSA_OK;      // (cannot be: the list and the classes were checked above)
+}
+
+extern "C" int ssa_aggverifier_push_mixed_cached_device(ssa_ctx *ctx, ssa_aggverifier *av, ssa_aggregator *ag,
+                                                        ssa_keycache *kc, const uint32_t *d_places, size_t n,
+                                                        const uint8_t *d_rs49, const uint8_t *d_pks, const uint8_t *d_pk_inf,
+                                                        const uint8_t *d_msgs, const uint64_t *d_msg_off, size_t msg_stride,
+                                                        size_t msg_len, size_t u, uint32_t require, uint32_t *d_result_out,
+                                                        uint64_t stats_out[8]) {
+    return agv_push_mixed_cached_dev(ctx, av, ag, kc, d_places, n, d_rs49, d_pks, d_pk_inf, false,
+                                     {d_msgs, d_msg_off, msg_stride, msg_len}, u, require, d_result_out, stats_out);
+}
+
+extern "C" int ssa_aggverifier_push_mixed_cached(ssa_ctx *ctx, ssa_aggverifier *av, ssa_aggregator *ag, ssa_keycache *kc,
+                                                 const uint32_t *places, size_t n, const uint8_t *rs49, const uint8_t *pks,
+                                                 const uint8_t *pk_inf, const uint8_t *msgs, const uint64_t *msg_off,
+                                                 size_t msg_stride, size_t msg_len, size_t u, uint32_t require,
+                                                 uint64_t stats_out[8]) {
+    return agv_push_mixed_cached_host(ctx, av, ag, kc, places, n, rs49, pks, pk_inf, false, msgs, msg_off, msg_stride, msg_len,
+                                      u, require, stats_out);
+}
+
+extern "C" int ssa_aggverifier_push_mixed_cached_wire_device(ssa_ctx *ctx, ssa_aggverifier *av, ssa_aggregator *ag,
+                                                             ssa_keycache *kc, const uint32_t *d_places, size_t n,
+                                                             const uint8_t *d_rs49, const uint8_t *d_pks49,
+                                                             const uint8_t *d_msgs, const uint64_t *d_msg_off,
+                                                             size_t msg_stride, size_t msg_len, size_t u, uint32_t require,
+                                                             uint32_t *d_result_out, uint64_t stats_out[8]) {
+    return agv_push_mixed_cached_dev(ctx, av, ag, kc, d_places, n, d_rs49, d_pks49, nullptr, true,
+                                     {d_msgs, d_msg_off, msg_stride, msg_len}, u, require, d_result_out, stats_out);
+}
+
+extern "C" int ssa_aggverifier_push_mixed_cached_wire(ssa_ctx *ctx, ssa_aggverifier *av, ssa_aggregator *ag,
+                                                      ssa_keycache *kc, const uint32_t *places, size_t n,
+                                                      const uint8_t *rs49, const uint8_t *pks49, const uint8_t *msgs,
+                                                      const uint64_t *msg_off, size_t msg_stride, size_t msg_len, size_t u,
+                                                      uint32_t require, uint64_t stats_out[8]) {
+    return agv_push_mixed_cached_host(ctx, av, ag, kc, places, n, rs49, pks49, nullptr, true, msgs, msg_off, msg_stride,
+                                      msg_len, u, require, stats_out);
+}
+
 // ------------------------------------------------------------------ filtering half-aggregation through a key cache
 // ssa_aggregate_valid_many with the statuses of ssa_verify_many_cached (affine keys) or ssa_verify_keyed_many_cached
 // (130-byte records: d_keyed, and b holds the messages alone) in place of the screen's, and the kept lanes' keys handed
@@ -4559,8 +4781,8 @@ static int agx_push_cached_run(ssa_ctx *ctx, ssa_aggregator *ag, ssa_keycache *k
                                size_t n, u8 *d_status_out, uint64_t *n_kept_out, uint64_t *stats_out) {
     u8 *d_status = d_status_out;
     if (int rc = avc_status(ctx, kc, b, d_keyed, n, &d_status, stats_out)) return rc;
-    return d_keyed ? agx_admit(ctx, ag, d_status, n, d_keyed, 130, 49, n_kept_out)
-                   : agx_admit(ctx, ag, d_status, n, b.sigs, 81, 0, n_kept_out);
+    return d_keyed ? agx_admit(ctx, ag, d_status, n, d_keyed, 130, 49, SSA_ADM_KEY_CHECKED, n_kept_out)
+                   : agx_admit(ctx, ag, d_status, n, b.sigs, 81, 0, SSA_ADM_KEY_CHECKED, n_kept_out);
 }
 
 extern "C" int ssa_aggregator_push_cached_device(ssa_ctx *ctx, ssa_aggregator *ag, ssa_keycache *kc, const uint8_t *d_sigs,

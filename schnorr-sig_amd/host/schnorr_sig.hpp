@@ -889,8 +889,21 @@ class Aggregator {
     };
     static constexpr size_t All = SIZE_MAX;       // finish: every triple held
     // HoldKeys (SSA_AGGR_HOLD_KEYS49): the object also holds the 49 wire bytes of every admitted lane's key, for keys();
-    // it then takes push_keyed alone
-    enum Options : uint32_t { None = 0u, HoldKeys = SSA_AGGR_HOLD_KEYS49 };
+    // it then takes push_keyed alone.  HoldAdmission (SSA_AGGR_HOLD_ADMISSION): the object also
+    // records the class of the push that admitted each lane, for admission() and for the KeyCache overloads of
+    // AggregateVerifier::push_mixed.
+    enum Options : uint32_t {
+        None = 0u,
+        HoldKeys = SSA_AGGR_HOLD_KEYS49,
+        HoldAdmission = SSA_AGGR_HOLD_ADMISSION,
+        HoldKeysAndAdmission = SSA_AGGR_HOLD_KEYS49 | SSA_AGGR_HOLD_ADMISSION
+    };
+    // how a lane was admitted: by push(screen = false), by the plain screened push, or through a key cache
+    enum class Admission : uint8_t {
+        Unscreened = SSA_ADM_UNSCREENED,
+        Screened = SSA_ADM_SCREENED,
+        KeyChecked = SSA_ADM_KEY_CHECKED
+    };
     // block_lanes: 0 (512) or a power of two from 2 to 512.  All device memory, about 113 bytes per lane (162 with
     // HoldKeys), is allocated here.
     Aggregator(Context &cx, size_t capacity, size_t block_lanes = 0, Options options = None) : cx_(cx) {
@@ -983,6 +996,16 @@ class Aggregator {
         const int rc = ssa_aggregator_keys(cx_.get(), ag_, n, out.data());
         if (rc != 0) throw std::runtime_error(std::string("ssa_aggregator_keys: ") + ssa_strerror(rc));
         out.resize(n * PUBLIC_KEY_LENGTH);
+        return out;
+    }
+    // the admission classes (Admission, as bytes) of the first n_take held triples, in arrival order (an object made with
+    // HoldAdmission; any other throws).  Changes nothing.
+    std::vector<uint8_t> admission(size_t n_take = All) const {
+        const size_t n = n_take == All ? (size_t)info().held : n_take;
+        std::vector<uint8_t> out(n + 1, 0);
+        const int rc = ssa_aggregator_admission(cx_.get(), ag_, n, out.data());
+        if (rc != 0) throw std::runtime_error(std::string("ssa_aggregator_admission: ") + ssa_strerror(rc));
+        out.resize(n);
         return out;
     }
     AggregateSignature finish(size_t n_take = All) const {
@@ -1155,6 +1178,49 @@ class AggregateVerifier {
         const int rc = ssa_aggverifier_push_mixed(cx_.get(), av_, pool.get(), places.data(), places.size(), rs49, t.pks.data(),
                                                   t.inf.data(), t.flat.data(), t.off.data(), 0, 0, u);
         if (rc != 0) throw std::runtime_error(std::string("ssa_aggverifier_push_mixed: ") + ssa_strerror(rc));
+    }
+    // The same through a key cache, with a required admission class: the unknown lanes are treated
+    // as push(cache, ...) / push_wire treat them, and a known lane whose class in the pool is below `require` is refused
+    // -- the call throws and changes nothing.  Above Require::None the pool must be made with HoldAdmission.  With
+    // Require::KeyChecked on lanes the pool admitted through a cache, finish answers what
+    // AggregateSignature::verify_many's cached form answers for the whole block: the caller owes nothing but the places.
+    // An Affine cache here, a Wire cache for push_mixed_wire.  stats_out: 8 words over the unknown lanes, or nullptr.
+    enum class Require : uint32_t {
+        None = SSA_ADM_UNSCREENED,
+        Screened = SSA_ADM_SCREENED,
+        KeyChecked = SSA_ADM_KEY_CHECKED
+    };
+    void push_mixed(Aggregator &pool, KeyCache &cache, const std::vector<uint32_t> &places, const uint8_t *rs49,
+                    const std::vector<PublicKey> &public_keys,
+                    const std::vector<std::pair<const uint8_t *, size_t>> &messages, Require require = Require::None,
+                    uint64_t *stats_out = nullptr) {
+        if (cache.wire()) throw std::invalid_argument("a Wire key cache takes 49-byte keys (push_mixed_wire)");
+        const size_t u = public_keys.size();
+        const PackedTriples t = pack_triples(std::vector<Signature>(u), public_keys, messages);
+        const int rc = ssa_aggverifier_push_mixed_cached(cx_.get(), av_, pool.get(), cache.get(), places.data(), places.size(),
+                                                         rs49, t.pks.data(), t.inf.data(), t.flat.data(), t.off.data(), 0, 0, u,
+                                                         (uint32_t)require, stats_out);
+        if (rc != 0) throw std::runtime_error(std::string("ssa_aggverifier_push_mixed_cached: ") + ssa_strerror(rc));
+    }
+    // wire_keys: the unknown lanes' keys side by side, 49 bytes each (messages.size() of them)
+    void push_mixed_wire(Aggregator &pool, KeyCache &cache, const std::vector<uint32_t> &places, const uint8_t *rs49,
+                         const std::vector<uint8_t> &wire_keys,
+                         const std::vector<std::pair<const uint8_t *, size_t>> &messages, Require require = Require::None,
+                         uint64_t *stats_out = nullptr) {
+        if (!cache.wire()) throw std::invalid_argument("an Affine key cache takes PublicKey objects (push_mixed)");
+        const size_t u = messages.size();
+        if (wire_keys.size() != u * PUBLIC_KEY_LENGTH) throw Panic("We should have the same number of messages than public keys");
+        std::vector<uint8_t> flat;
+        std::vector<uint64_t> off(u + 1, 0);
+        for (size_t i = 0; i < u; i++) {
+            flat.insert(flat.end(), messages[i].first, messages[i].first + messages[i].second);
+            off[i + 1] = flat.size();
+        }
+        flat.push_back(0);
+        const int rc = ssa_aggverifier_push_mixed_cached_wire(cx_.get(), av_, pool.get(), cache.get(), places.data(),
+                                                              places.size(), u ? rs49 : nullptr, u ? wire_keys.data() : nullptr,
+                                                              flat.data(), off.data(), 0, 0, u, (uint32_t)require, stats_out);
+        if (rc != 0) throw std::runtime_error(std::string("ssa_aggverifier_push_mixed_cached_wire: ") + ssa_strerror(rc));
     }
     // every lane of the block is held by the pool
     void push_known(Aggregator &pool, const std::vector<uint32_t> &places) {
