@@ -1209,7 +1209,7 @@ int ssa_aggregate_valid_keyed_many_cached_device(ssa_ctx *ctx, ssa_keycache *kc,
  * one permutation, one multiplication and a sum per lane.  It belongs to the context it was created on, like a key cache.
  *   create   capacity: 1 .. SSA_MAX_BATCH lanes; block_lanes: 0 (the default, 512) or a power of two from 2 to 512 (small
  *            values let tests reach every path of the tree at a few thousand lanes); flags: 0 or any of
- *            SSA_AGGR_HOLD_KEYS49 and SSA_AGGR_HOLD_ADMISSION (below).  Anything else: SSA_ERR_ARG.  All device memory is allocated here -- 49 capacity + 32 bytes of R's, 32 bytes of scalar and 32
+ *            SSA_AGGR_HOLD_KEYS49, SSA_AGGR_HOLD_ADMISSION and SSA_AGGR_HOLD_INDEX (below).  Anything else: SSA_ERR_ARG.  All device memory is allocated here -- 49 capacity + 32 bytes of R's, 32 bytes of scalar and 32
  *            bytes of leaf per lane, 32 bytes per block: about 113 bytes per lane -- and is the object's own: destroy
  *            releases it, or ssa_ctx_destroy (the handle then stays valid for destroy and is refused everywhere else).
  *   push     the arguments of ssa_aggregate_valid_many.  Let S be the status vector: with flags == 0 the one
@@ -1320,12 +1320,59 @@ int ssa_aggregate_valid_keyed_many_cached_device(ssa_ctx *ctx, ssa_keycache *kc,
  *            the device's verdict is read before the move begins.  *n_kept_out (HOST memory in both forms) = the lanes
  *            kept (for a refused list: the lanes held).  m == 0: SSA_OK, nothing is launched.  The _device form
  *            synchronises the context's stream once, as remove_device does.
+ *   leaves, leaves_select   the LEAF column.  Every held lane has a 32-byte leaf,
+ *            H(d || flag byte of R || 0xA1) of its challenge digest: the one value that binds (R, key, message) and that
+ *            the aggregator and the aggregate verifier compute identically.  It is the lane's ID.  Both calls work on
+ *            every aggregator, whatever its flags, and change no state.  leaves(n_take) writes the first n_take held
+ *            lanes' leaves, 32 n_take bytes, by the conventions of keys: SIZE_MAX = all lanes held, n_take > held is
+ *            SSA_ERR_ARG, n_take == 0 writes nothing, the _device form is one device-to-device copy.  leaves_select
+ *            writes the leaves at the places order[0], ..., order[m - 1] in that order, 32 m bytes: the id column that
+ *            goes beside finish_select on the same list.  An index >= held is refused and no lane outside [0, held) is
+ *            read: the host form zeroes the 32 m bytes and returns SSA_ERR_ARG; the _device form only enqueues, zeroes
+ *            them and writes *d_result_out (DEVICE memory, 4-byte aligned, required) = 1, else 0.  A place named twice
+ *            is written twice: whether a list may repeat a place is finish_select's decision.  m == 0: SSA_OK, nothing
+ *            is launched or written.  SSA_ERR_ARG before anything is launched: NULL arguments with m > 0,
+ *            m > SSA_MAX_BATCH, an object of another context or an orphaned one, a device list that is not 4-byte aligned.
+ *   SSA_AGGR_HOLD_INDEX (create flag)   the object also holds a LEAF INDEX: a table on the device,
+ *            8 bytes per slot with at least four slots per lane of the capacity (a power of two, at least 1024) and one
+ *            8-byte counter, that answers "which of my places holds this leaf?".  It is what a validator needs to
+ *            receive a compact block -- ids plus the few lanes it lacks -- since the pool's places move under every
+ *            removal, some of them by masks that exist on the device only.  Combinable with the other create flags.
+ *            lookup(ids32, n): places_out[i] = the LOWEST place p < held whose leaf equals the 32 bytes
+ *            ids32[32 i, 32 i + 32), or SSA_AGGV_UNKNOWN; an id that occurs several times gets the same answer each
+ *            time.  *n_unknown_out = the number of SSA_AGGV_UNKNOWN answers: with places_out, exactly what
+ *            ssa_aggverifier_push_mixed* takes as places and as the count of lanes that come with the call.  The
+ *            _device form only enqueues on the context's stream; d_ids32 may lie at any byte alignment (read by 64-bit
+ *            words when 8-aligned, byte by byte otherwise), d_places_out and d_n_unknown_out (ONE uint32, device memory)
+ *            are 4-byte aligned, else SSA_ERR_ARG.  The host form stages and copies back like every host form;
+ *            *n_unknown_out is then a uint64 in host memory.  n == 0: SSA_OK, count 0, nothing is launched;
+ *            n > SSA_MAX_BATCH, NULL arguments, an object created without the flag, of another context or orphaned:
+ *            SSA_ERR_ARG with nothing written.
+ *            THE INDEX IS LAZY.  push*, finish*, keys, admission, drop_front, remove*, and reset enqueue on an object
+ *            with the flag exactly what they enqueue on one without.  The object keeps on the host how many lanes the
+ *            table covers (`indexed`) and whether it is `stale`: a removal that changed the object, a reset, and a
+ *            removal that failed with SSA_ERR_HIP after its move began make it stale.  All index work is enqueued by
+ *            index_sync and, identically, in front of every lookup: for a stale table one clear (slots to all-ones,
+ *            the counter to zero), then ONE insert launch over the lanes [indexed, held).  So after pushes the insert
+ *            is incremental, after a removal it is a rebuild, and a caller takes the rebuild off its critical path by
+ *            calling index_sync right behind the removal.  index_sync only enqueues.
+ *            FAIL-OPEN.  A returned place is always right: all 32 bytes of the stored leaf were compared, the table's
+ *            fingerprint (SipHash-2-4 under the context's random key) only picks slots.  SSA_AGGV_UNKNOWN for an id
+ *            the pool DOES hold can happen only for a lane whose insert ran into the probe bound (128 slots by
+ *            default, at a load of at most 1/4; index_info word [4] counts such lanes).  The mixed push then treats
+ *            that lane as unknown and verifies it from the block body: that costs time and never changes a verdict.
+ *            index_info: out[0] slots, [1] lanes indexed, [2] stale (0 / 1), [3] clears of the table so far (rebuilds,
+ *            the first build included), [4] lanes that hit the probe bound since the last clear, [5] lookup calls that
+ *            launched, [6] ids looked up, [7] 0.  Word [4] is a counter on the device: the call SYNCHRONISES the
+ *            context's stream once (not when the table is stale: then it reports 0).
  * NOT here: selections above one MSM slice, reuse of the stored tops for a selection, a column of affine keys, the
- * messages, ssa_multi forms.  The validator's counterpart is ssa_aggverifier, below. */
+ * messages, ssa_multi forms, dropping duplicate leaves on push, short ids, an index on the verifier object.  The
+ * validator's counterpart is ssa_aggverifier, below. */
 typedef struct ssa_aggregator ssa_aggregator;
 #define SSA_AGGR_NO_SCREEN 1u      /* push flag */
 #define SSA_AGGR_HOLD_KEYS49 2u    /* create flag */
 #define SSA_AGGR_HOLD_ADMISSION 8u /* create flag */
+#define SSA_AGGR_HOLD_INDEX 32u    /* create flag */
 #define SSA_ADM_UNSCREENED 0u      /* the admission classes of SSA_AGGR_HOLD_ADMISSION */
 #define SSA_ADM_SCREENED 1u
 #define SSA_ADM_KEY_CHECKED 2u
@@ -1361,11 +1408,23 @@ int ssa_aggregator_keys_device(ssa_ctx *ctx, ssa_aggregator *ag, size_t n_take, 
  * out[0] the R's, [1] the scalars, [2] the leaves, [3] the tops, [4] the key column (0 without SSA_AGGR_HOLD_KEYS49).
  * SSA_ERR_ARG for anything create would refuse. */
 int ssa_debug_aggregator_bytes(size_t capacity, size_t block_lanes, uint32_t flags, uint64_t out[5]);
-/* tests: the same five words (SSA_AGGR_HOLD_ADMISSION is accepted by both and changes none of them), out[5] the
- * admission column (0 without SSA_AGGR_HOLD_ADMISSION), out[6] = out[7] = 0. */
+/* tests: the same five words (SSA_AGGR_HOLD_ADMISSION and SSA_AGGR_HOLD_INDEX are accepted by both and change none of
+ * them), out[5] the admission column (0 without SSA_AGGR_HOLD_ADMISSION), out[6] the leaf index, 8 bytes per slot and
+ * the 8-byte counter (0 without SSA_AGGR_HOLD_INDEX), out[7] = 0. */
 int ssa_debug_aggregator_bytes_ex(size_t capacity, size_t block_lanes, uint32_t flags, uint64_t out[8]);
 int ssa_aggregator_admission(ssa_ctx *ctx, ssa_aggregator *ag, size_t n_take, uint8_t *adm_out);
 int ssa_aggregator_admission_device(ssa_ctx *ctx, ssa_aggregator *ag, size_t n_take, uint8_t *d_adm_out);
+int ssa_aggregator_leaves(ssa_ctx *ctx, ssa_aggregator *ag, size_t n_take, uint8_t *ids32_out);
+int ssa_aggregator_leaves_device(ssa_ctx *ctx, ssa_aggregator *ag, size_t n_take, uint8_t *d_ids32_out);
+int ssa_aggregator_leaves_select(ssa_ctx *ctx, ssa_aggregator *ag, const uint32_t *order, size_t m, uint8_t *ids32_out);
+int ssa_aggregator_leaves_select_device(ssa_ctx *ctx, ssa_aggregator *ag, const uint32_t *d_order, size_t m,
+                                        uint8_t *d_ids32_out, uint32_t *d_result_out);
+int ssa_aggregator_index_sync(ssa_ctx *ctx, ssa_aggregator *ag);
+int ssa_aggregator_lookup(ssa_ctx *ctx, ssa_aggregator *ag, const uint8_t *ids32, size_t n, uint32_t *places_out,
+                          uint64_t *n_unknown_out);
+int ssa_aggregator_lookup_device(ssa_ctx *ctx, ssa_aggregator *ag, const uint8_t *d_ids32, size_t n, uint32_t *d_places_out,
+                                 uint32_t *d_n_unknown_out);
+int ssa_aggregator_index_info(ssa_ctx *ctx, ssa_aggregator *ag, uint64_t out[8]);
 /* tests: what a push of m kept lanes onto `held` lanes completes with blocks of block_lanes (0: 512) lanes (host code, no
  * device): out[0] the first completed block, out[1] the number of completed blocks, out[2] the first lane of the ragged
  * tail, out[3] its length.  SSA_ERR_ARG for a block size create would refuse or held + m above SSA_MAX_BATCH. */

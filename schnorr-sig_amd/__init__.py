@@ -313,6 +313,14 @@ def _load():
         "ssa_debug_aggregator_bytes_ex": (i32, [sz, sz, u32, u64p]),
         "ssa_aggregator_admission": (i32, [vp, vp, sz, vp]),
         "ssa_aggregator_admission_device": (i32, [vp, vp, sz, vp]),
+        "ssa_aggregator_leaves": (i32, [vp, vp, sz, vp]),
+        "ssa_aggregator_leaves_device": (i32, [vp, vp, sz, vp]),
+        "ssa_aggregator_leaves_select": (i32, [vp, vp, vp, sz, vp]),
+        "ssa_aggregator_leaves_select_device": (i32, [vp, vp, vp, sz, vp, vp]),
+        "ssa_aggregator_index_sync": (i32, [vp, vp]),
+        "ssa_aggregator_lookup": (i32, [vp, vp, vp, sz, vp, u64p]),
+        "ssa_aggregator_lookup_device": (i32, [vp, vp, vp, sz, vp, vp]),
+        "ssa_aggregator_index_info": (i32, [vp, vp, u64p]),
         "ssa_debug_aggregator_plan": (i32, [C.c_uint64, C.c_uint64, C.c_uint64, u64p]),
         "ssa_aggregator_drop_front": (i32, [vp, vp, sz]),
         "ssa_aggregator_remove": (i32, [vp, vp, vp, sz, u64p]),
@@ -647,7 +655,7 @@ class Engine:
                 raise
         return cache
 
-    def aggregator(self, capacity, block_lanes=0, hold_keys=False, hold_admission=False):
+    def aggregator(self, capacity, block_lanes=0, hold_keys=False, hold_admission=False, index=False):
         """a streaming aggregator of `capacity` lanes on this engine's device: push signatures
         as they arrive, finish at block time.  All of its device memory, about 113 bytes per lane, is allocated here.
         block_lanes: 0 (512) or a power of two from 2 to 512.
@@ -655,11 +663,14 @@ class Engine:
         wire key (49 more bytes per lane) for Aggregator.keys(); it then takes push_keyed alone.
         hold_admission=True (SSA_AGGR_HOLD_ADMISSION): the object also records the class of the
         push that admitted each lane (one more byte per lane) for Aggregator.admission() and for
-        AggregateVerifier.push_mixed(cache=, require=)."""
+        AggregateVerifier.push_mixed(cache=, require=).
+        index=True (SSA_AGGR_HOLD_INDEX): the object also holds a leaf index (32 bytes per lane
+        of the capacity and more: 8 bytes per slot, at least four slots per lane) for Aggregator.lookup(): which place
+        holds this id?"""
         h = C.c_void_p()
-        _check(_lib.ssa_aggregator_create(self._ctx, int(capacity), int(block_lanes), _aggr_flags(hold_keys, hold_admission),
-                                          C.byref(h)), "ssa_aggregator_create")
-        return Aggregator(self, h, hold_keys=hold_keys, hold_admission=hold_admission)
+        _check(_lib.ssa_aggregator_create(self._ctx, int(capacity), int(block_lanes),
+                                          _aggr_flags(hold_keys, hold_admission, index), C.byref(h)), "ssa_aggregator_create")
+        return Aggregator(self, h, hold_keys=hold_keys, hold_admission=hold_admission, index=index)
 
     def aggregate_verifier(self, capacity, block_lanes=0):
         """a streaming aggregate verifier of `capacity` lanes on this engine's device: push the
@@ -1852,6 +1863,9 @@ class KeyCache(_Handle, _KeyTables):
 AGGR_NO_SCREEN = 1    # SSA_AGGR_NO_SCREEN
 AGGR_HOLD_KEYS49 = 2  # SSA_AGGR_HOLD_KEYS49
 AGGR_HOLD_ADMISSION = 8  # SSA_AGGR_HOLD_ADMISSION
+AGGR_HOLD_INDEX = 32  # SSA_AGGR_HOLD_INDEX
+# the eight words of Aggregator.index_info
+AGGREGATOR_INDEX_FIELDS = ("slots", "indexed", "stale", "rebuilds", "overflowed", "lookups", "ids", "reserved")
 # the admission classes an Aggregator made with hold_admission=True records
 ADM_UNSCREENED = 0    # SSA_ADM_UNSCREENED: push(screen=False)
 ADM_SCREENED = 1      # SSA_ADM_SCREENED: the plain screened push
@@ -1885,15 +1899,17 @@ def aggregator_bytes(capacity, block_lanes=0, hold_keys=False):
     return tuple(int(v) for v in out)
 
 
-def _aggr_flags(hold_keys, hold_admission):
-    return (AGGR_HOLD_KEYS49 if hold_keys else 0) | (AGGR_HOLD_ADMISSION if hold_admission else 0)
+def _aggr_flags(hold_keys, hold_admission, index=False):
+    return ((AGGR_HOLD_KEYS49 if hold_keys else 0) | (AGGR_HOLD_ADMISSION if hold_admission else 0)
+            | (AGGR_HOLD_INDEX if index else 0))
 
 
-def aggregator_bytes_ex(capacity, block_lanes=0, hold_keys=False, hold_admission=False):
-    """tests: the five words of aggregator_bytes, the admission column (0 without hold_admission) and two zeros
-    (ssa_debug_aggregator_bytes_ex: host code, no device)"""
+def aggregator_bytes_ex(capacity, block_lanes=0, hold_keys=False, hold_admission=False, index=False):
+    """tests: the five words of aggregator_bytes, the admission column (0 without hold_admission), the leaf index (0
+    without index) and a zero (ssa_debug_aggregator_bytes_ex: host code, no device)"""
     out = (C.c_uint64 * 8)()
-    _check(_lib.ssa_debug_aggregator_bytes_ex(int(capacity), int(block_lanes), _aggr_flags(hold_keys, hold_admission), out),
+    _check(_lib.ssa_debug_aggregator_bytes_ex(int(capacity), int(block_lanes),
+                                              _aggr_flags(hold_keys, hold_admission, index), out),
            "ssa_debug_aggregator_bytes_ex")
     return tuple(int(v) for v in out)
 
@@ -2025,10 +2041,110 @@ class Aggregator(_LaneStore):
     a `with` block, or when the object goes away)."""
     _prefix, _fields = "aggregator", AGGREGATOR_FIELDS
 
-    def __init__(self, engine, handle, hold_keys=False, hold_admission=False):
+    def __init__(self, engine, handle, hold_keys=False, hold_admission=False, index=False):
         super().__init__(engine, handle)
         self.hold_keys = bool(hold_keys)
         self.hold_admission = bool(hold_admission)
+        self.index = bool(index)
+
+    # ---- the leaf column and the leaf index (DESIGN.md section 36)
+    def leaves(self, n=None):
+        """the 32-byte leaves -- the ids -- of the first n held lanes (None: all) as uint8[n, 32], in arrival order.
+        Changes no state; every aggregator has them."""
+        held = self.info()["held"]
+        k = held if n is None else int(n)
+        out = np.full((max(min(k, held), 1), 32), 255, dtype=np.uint8)
+        _check(_lib.ssa_aggregator_leaves(self.engine._ctx, self.handle, _n_take(n), _ptr(out)), "ssa_aggregator_leaves")
+        return out[:min(k, held)].copy()
+
+    def leaves_device(self, d_ids32, n=None):
+        """device form: only enqueues; the 32 n bytes land in the uint8 tensor d_ids32 (any byte alignment), n as given
+        or all lanes held.  Returns n."""
+        k = self.info()["held"] if n is None else int(n)
+        _dev_bytes(d_ids32, self.engine, "d_ids32")
+        if d_ids32.numel() < 32 * k:
+            raise ValueError("the leaves of %d lanes are %d bytes" % (k, 32 * k))
+        _check(_lib.ssa_aggregator_leaves_device(self.engine._ctx, self.handle, k, d_ids32.data_ptr()),
+               "ssa_aggregator_leaves_device")
+        return k
+
+    def leaves_select(self, order):
+        """the leaves of the held lanes at the places order[0], order[1], ... in THAT order as uint8[m, 32]: the id
+        column that goes beside finish_select(order).  A place may be named twice; an index that is not below the lanes
+        held is refused by the device and raises as every SSA_ERR_ARG does."""
+        order = _order_u32(order)
+        m = int(order.size)
+        out = np.full((max(m, 1), 32), 255, dtype=np.uint8)
+        _check(_lib.ssa_aggregator_leaves_select(self.engine._ctx, self.handle, _ptr(order) if m else None, m, _ptr(out)),
+               "ssa_aggregator_leaves_select")
+        return out[:m].copy()
+
+    def leaves_select_device(self, d_order, d_ids32, d_result):
+        """device form: only enqueues.  d_order: m 32-bit indices on the engine's device; the 32 m bytes land in the
+        uint8 tensor d_ids32 (any byte alignment); d_result (one int32 on the device) receives 0, or 1 for a list with
+        an index out of range, whose output is zeroed.  Returns m."""
+        m = _dev_order(d_order, self.engine)
+        _dev_bytes(d_ids32, self.engine, "d_ids32")
+        _dev_result(d_result, self.engine)
+        if d_ids32.numel() < 32 * m:
+            raise ValueError("the leaves of %d lanes are %d bytes" % (m, 32 * m))
+        _check(_lib.ssa_aggregator_leaves_select_device(self.engine._ctx, self.handle, _addr(d_order), m,
+                                                        d_ids32.data_ptr(), d_result.data_ptr()),
+               "ssa_aggregator_leaves_select_device")
+        return m
+
+    def _need_index(self):
+        if not self.index:
+            raise ValueError("this aggregator was made without index=True (SSA_AGGR_HOLD_INDEX)")
+
+    def index_sync(self):
+        """brings the leaf index up to date with the lanes held; only enqueues.  A lookup does the same in front of its
+        query: calling this right after a removal takes the rebuild off the block's critical path."""
+        self._need_index()
+        _check(_lib.ssa_aggregator_index_sync(self.engine._ctx, self.handle), "ssa_aggregator_index_sync")
+
+    def lookup(self, ids):
+        """ids: n 32-byte leaves (uint8[n, 32], or any buffer of 32 n bytes) -> (places uint32[n], n_unknown):
+        places[i] is the LOWEST place of the pool whose leaf is ids[i], or AGGV_UNKNOWN; n_unknown counts the latter.
+        The pair is what AggregateVerifier.push_mixed* takes.  ValueError, before any call, on a pool made without
+        index=True or for ids whose size is no multiple of 32."""
+        self._need_index()
+        a = np.ascontiguousarray(np.frombuffer(ids, dtype=np.uint8) if isinstance(ids, (bytes, bytearray, memoryview))
+                                 else np.asarray(ids, dtype=np.uint8)).reshape(-1)
+        if a.size % 32:
+            raise ValueError("ids are 32 bytes each")
+        n = a.size // 32
+        places = np.full(max(n, 1), AGGV_UNKNOWN, dtype=np.uint32)
+        unknown = C.c_uint64(0)
+        _check(_lib.ssa_aggregator_lookup(self.engine._ctx, self.handle, _ptr(a) if n else None, n, _ptr(places),
+                                          C.byref(unknown)), "ssa_aggregator_lookup")
+        return places[:n].copy(), int(unknown.value)
+
+    def lookup_device(self, d_ids, d_places, d_count):
+        """device form: only enqueues (the index is brought up to date in front of the query).  d_ids: a contiguous
+        uint8 tensor of 32 n bytes on the engine's device, any byte alignment; d_places: a 32-bit integer tensor of at
+        least n words; d_count: one 32-bit integer, the number of AGGV_UNKNOWN answers.  Both outputs stay on the
+        device: d_places goes unread into AggregateVerifier.push_mixed*_device.  Returns n."""
+        self._need_index()
+        _dev_bytes(d_ids, self.engine, "d_ids")
+        if d_ids.numel() % 32:
+            raise ValueError("ids are 32 bytes each")
+        n = int(d_ids.numel()) // 32
+        if _dev_order(d_places, self.engine) < n:
+            raise ValueError("the places of %d ids are %d words" % (n, n))
+        _dev_result(d_count, self.engine)
+        _check(_lib.ssa_aggregator_lookup_device(self.engine._ctx, self.handle, d_ids.data_ptr() if n else None, n,
+                                                 d_places.data_ptr() if n else None, d_count.data_ptr()),
+               "ssa_aggregator_lookup_device")
+        return n
+
+    def index_info(self):
+        """the eight words of ssa_aggregator_index_info by the names of AGGREGATOR_INDEX_FIELDS.  Synchronises the
+        engine's stream once: `overflowed` is a counter on the device."""
+        self._need_index()
+        out = (C.c_uint64 * 8)()
+        _check(_lib.ssa_aggregator_index_info(self.engine._ctx, self.handle, out), "ssa_aggregator_index_info")
+        return dict(zip(AGGREGATOR_INDEX_FIELDS, (int(v) for v in out)))
 
     def admission(self, n=None):
         """the admission classes (ADM_*) of the first n held lanes (None: all) as uint8[n], in arrival order: how the

@@ -15,6 +15,11 @@
 //           adm[held, held + m) behind agx_k_append, the kept count being on the host by then -- moved with its lane by
 //           agx_k_move, read by ssa_aggregator_admission and by the mixed pushes of the streaming aggregate verifier
 //           (agv_k_classify_adm, agv_k_require in ssa_aggverifier.hpp).  finish, finish_select and keys do not touch it.
+//   index   8 bytes per slot, dd_slots_for(capacity) slots, and one counter, only in an object created with
+//           SSA_AGGR_HOLD_INDEX: the open-addressing table of ssa_dedup.hpp over the leaf column,
+//           which answers "which place holds this leaf?" (agi_k_insert, agi_k_lookup below).  LAZY: no push, finish or
+//           removal touches it -- they keep `indexed` and `stale` on the host -- and all of its work is enqueued by
+//           ssa_aggregator_index_sync and in front of a look-up.
 //
 //   push    status vector (the screen of ssa_verify_batch_screened, the checks of ag_k_fold, or -- the cached pushes,
 //           section 31 -- the statuses of ssa_verify_many_cached / ssa_verify_keyed_many_cached) -> av_keep lists the kept
@@ -33,11 +38,12 @@
 //           whether the list is valid), the tree runs over the gathered leaves from the bottom -- the stored tops say
 //           nothing about another order -- and the coefficient fold is finish's.  The object is read, never written.
 //
-// The object's four (with the key column and the admission column: up to six) arrays are its own allocations (released by destroy, or by the context's clean-up): they are not in
+// The object's four (with the key column, the admission column and the leaf index: up to seven) arrays are its own allocations (released by destroy, or by the context's clean-up): they are not in
 // the context's list of workspaces, and nothing the object needs between two calls lives in one.
 #pragma once
 #include "ssa_aggregate.hpp"
 #include "ssa_ctx.hpp"
+#include "ssa_dedup.hpp"
 
 // What the streaming aggregator and the streaming aggregate verifier (ssa_aggverifier.hpp) both are: lanes in arrival
 // order, their leaves, and the tops of the complete blocks of B.
@@ -56,11 +62,25 @@ struct AgxStore {
 };
 
 struct ssa_aggregator : AgxStore {
-    static constexpr uint32_t kCreateFlags = SSA_AGGR_HOLD_KEYS49 | SSA_AGGR_HOLD_ADMISSION;
+    static constexpr uint32_t kCreateFlags = SSA_AGGR_HOLD_KEYS49 | SSA_AGGR_HOLD_ADMISSION | SSA_AGGR_HOLD_INDEX;
     uint64_t offered = 0, dropped = 0;
-    DevBuf wire, scal, keys, adm;
+    DevBuf wire, scal, keys, adm, index;
+    // the leaf index (SSA_AGGR_HOLD_INDEX), host side: lanes [0, indexed) are in the table; stale:
+    // the table says nothing (never cleared yet, or lanes moved since) and is cleared before the next insert
+    size_t indexed = 0;
+    bool stale = true;
+    uint64_t rebuilds = 0, lookups = 0, looked_up = 0;
     bool hold_keys() const { return (flags & SSA_AGGR_HOLD_KEYS49) != 0; }
     bool hold_adm() const { return (flags & SSA_AGGR_HOLD_ADMISSION) != 0; }
+    bool hold_index() const { return (flags & SSA_AGGR_HOLD_INDEX) != 0; }
+    size_t index_slots() const { return ssa::dd_slots_for(capacity); }
+    u64 *index_table() const { return (u64 *)index.p; }
+    unsigned long long *index_over() const { return (unsigned long long *)index.p + index_slots(); }   // behind the slots
+    // the lanes moved, or left: what the table says is void (every removal that changed the object, reset, a failed move)
+    void index_void() {
+        indexed = 0;
+        stale = true;
+    }
 };
 // everything the object will ever hold, in the order it is allocated and released (the key column: only with the flag,
 // 49 bytes per lane and the rest of the last dword -- agx_k_move reads whole aligned dwords; the admission column: only
@@ -70,6 +90,7 @@ static inline std::vector<AgxStore::Buf> agx_bufs(ssa_aggregator &a) {
         {&a.wire, 49 * a.capacity + 32}, {&a.scal, 32 * a.capacity}, {&a.leaves, 32 * a.capacity}, {&a.tops, 32 * a.n_tops()}};
     if (a.hold_keys()) bufs.push_back({&a.keys, 49 * a.capacity + 3});
     if (a.hold_adm()) bufs.push_back({&a.adm, a.capacity + 16});
+    if (a.hold_index()) bufs.push_back({&a.index, 8 * a.index_slots() + 8});
     return bufs;
 }
 template <class T>
@@ -338,6 +359,151 @@ agx_k_select_verdict(const u32 *__restrict__ flag, u8 *__restrict__ agg, size_t 
     for (size_t b = g; b < n_agg; b += step) agg[b] = 0;
     if (keys)
         for (size_t b = g; b < n_keys; b += step) keys[b] = 0;
+}
+
+// The leaf column in the caller's order (ssa_aggregator_leaves_select): out[t] = the leaf at place
+// order[t], four words into a dword-aligned workspace of the context.  The range check dominates the read: a thread
+// whose index is not below `held` raises the flag (atomic OR, as agx_claim does) and returns before it forms an address;
+// agx_k_select_verdict then zeroes the output.  A place named twice is copied twice: whether a list may repeat a place
+// is finish_select's business.
+__global__ void __launch_bounds__(256)
+agx_k_leaves_select(const u32 *__restrict__ order, size_t m, size_t held, u32 *__restrict__ flag,
+                    const u64 *__restrict__ leaves, u64 *__restrict__ out) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= m) return;
+    const u32 idx = order[t];
+    if ((size_t)idx >= held) {
+        atomicOr(flag, 1u);
+        return;
+    }
+    const ulonglong2 *l = reinterpret_cast<const ulonglong2 *>(leaves + 4 * (size_t)idx);
+    const ulonglong2 l0 = l[0], l1 = l[1];
+    ulonglong2 *d = reinterpret_cast<ulonglong2 *>(out + 4 * t);
+    d[0] = l0;
+    d[1] = l1;
+}
+
+// ---- the leaf index (SSA_AGGR_HOLD_INDEX): which place holds this leaf?
+// The table of ssa_dedup.hpp over the leaf column: `slots` 64-bit words, a power of two and at least four per lane of
+// the capacity, all ones = empty, otherwise (fingerprint's upper half << 32) | place.  The fingerprint is dd_fingerprint
+// under the context's random key over the leaf's four words and one constant word (33 bytes: dd_fingerprint wants a
+// partly filled last word); it only picks slots.  Whether a place holds an id is decided on the 32 bytes, always.
+//
+// A source of ssa_dedup.hpp over the leaf column (the rows of the index) and over the caller's ids (the lanes of a
+// look-up: any byte alignment, read by u64 when the base is 8-aligned -- then every id is, at 32 bytes apart -- and byte
+// by byte otherwise, as dd_key_word reads a key).
+constexpr u64 AGI_TAG = 0xA4;
+struct AgiLeafRows {
+    static constexpr int WORDS = 5, BYTES = 33;
+    const u64 *leaves;
+    SSA_DEV u64 word(size_t p, int k) const { return k < 4 ? leaves[4 * p + k] : AGI_TAG; }
+};
+struct AgiIdLanes {
+    static constexpr int WORDS = 5, BYTES = 33;
+    const u8 *ids;
+    bool aligned;
+    SSA_DEV u64 word(size_t i, int k) const {
+        const u8 *p = ids + 32 * i + 8 * k;
+        return k < 4 ? (aligned ? *reinterpret_cast<const u64 *>(p) : ld_u64_le(p)) : AGI_TAG;
+    }
+};
+
+// The insert: one thread per place p in [lo, hi).  The walk starts at fp & mask and takes at most `bound` slots:
+//   an empty slot       is claimed by compare-and-swap with tag << 32 | p;
+//   a slot of my tag whose owner o < hi holds my four words   is my leaf's slot: atomicMin of the 64-bit word with mine
+//                       -- the upper halves are equal, so the lower PLACE wins -- and the walk ends;
+//   anything else       moves on to the next slot.
+// A lane that finds neither within the bound is counted in *over (one atomicAdd of the ballot's popcount per wave) and
+// is in no slot: a look-up answers "unknown" for its leaf unless a lower place holds the same leaf.
+//
+// Memory model (the argument of ssa_dedup.hpp, with one more transition).  Between the workgroups of a launch nothing
+// is exchanged but the slot words, through agent-scope atomics only.  The leaves read behind a slot word -- places below
+// hi -- were written by an earlier launch on the same stream (agx_k_append, or the copies of a removal).  A slot word
+// goes from empty to owned, and from there only to a LOWER owner of the SAME leaf (atomicMin between lanes that have
+// compared all four words): whatever value a thread reads, now or stale, is the place of a lane that holds the leaf the
+// slot stands for, so a comparison against it decides rightly, and a stale "empty" costs one failed swap.
+//
+// Why the result does not depend on the order in which the waves arrive.  Lanes with equal leaves have equal
+// fingerprints and walk the same chain of slots from the same start under the same bound.  A slot never becomes empty
+// again and never changes the leaf it stands for, so a chain only grows at its end: every slot a lane passed stays a
+// slot another lane of the same leaf passes too.  Of the lanes of one leaf, whichever reaches the first slot that is
+// empty or already theirs claims it, and every other one finds it there; atomicMin then leaves the lowest place among
+// them, in any order.  Lanes [0, lo) were inserted by earlier launches and are below every p of this one, so an
+// incremental insert never lowers an owner and leaves what a rebuild over [0, hi) would.  (WHICH leaves run into the
+// probe bound may depend on the order -- it decides who stands where in a shared chain; with the default bound at load
+// <= 1/4 none does.  Such a leaf is answered "unknown", never with a wrong place.)
+__global__ void __launch_bounds__(256)
+agi_k_insert(const u64 *__restrict__ leaves, u32 lo, u32 hi, u64 k0, u64 k1, u64 *__restrict__ slots, u32 mask, u32 bound,
+             unsigned long long *__restrict__ over) {
+    const u32 p = lo + blockIdx.x * DD_BLOCK + threadIdx.x;
+    const AgiLeafRows rows{leaves};
+    bool lost = false;
+    if (p < hi) {
+        const ulonglong2 *l = reinterpret_cast<const ulonglong2 *>(leaves + 4 * (size_t)p);
+        const ulonglong2 l0 = l[0], l1 = l[1];
+        const u64 w[AgiLeafRows::WORDS] = {l0.x, l0.y, l1.x, l1.y, AGI_TAG};
+        const u64 fp = dd_fingerprint_of<AgiLeafRows>(w, k0, k1);
+        const u64 tag = fp >> 32, mine = (tag << 32) | (u64)p;
+        u32 s = (u32)fp & mask;
+        lost = true;
+#pragma unroll 1
+        for (u32 t = 0; t < bound; t++) {
+            u64 cur = __hip_atomic_load(slots + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (cur == DD_EMPTY) {
+                cur = atomicCAS((unsigned long long *)(slots + s), (unsigned long long)DD_EMPTY, (unsigned long long)mine);
+                if (cur == DD_EMPTY) {
+                    lost = false;
+                    break;
+                }
+            }
+            const u32 o = (u32)cur;
+            if ((cur >> 32) == tag && o < hi && dd_same_key(rows, o, w)) {       // my leaf's slot: the bytes decided
+                atomicMin((unsigned long long *)(slots + s), (unsigned long long)mine);
+                lost = false;
+                break;
+            }
+            s = (s + 1u) & mask;
+        }
+    }
+    const unsigned long long losts = __ballot(lost);
+    if ((threadIdx.x & 63u) == 0 && losts) atomicAdd(over, (unsigned long long)__popcll(losts));
+}
+
+// The look-up: one thread per id, the same walk, read-only.  places[i] = the owner of the first slot of the id's tag
+// whose owner holds the id's four words, or SSA_AGGV_UNKNOWN at an empty slot or at the bound.  An owner is used as an
+// index only after it compared below `indexed` -- the lanes the table was built over, all written by earlier launches --
+// so no thread reads outside the leaf column whatever a slot word holds.  No slot is written: the launch exchanges
+// nothing between its threads but the count, *n_unknown += the ballot's popcount, once per wave (cleared by the call in
+// front of the launch).  places and n_unknown are 4-byte aligned (the call checks).
+__global__ void __launch_bounds__(256)
+agi_k_lookup(const u8 *__restrict__ ids, u32 n, const u64 *__restrict__ leaves, u32 indexed, u64 k0, u64 k1,
+             const u64 *__restrict__ slots, u32 mask, u32 bound, u32 *__restrict__ places, u32 *__restrict__ n_unknown) {
+    const u32 i = blockIdx.x * DD_BLOCK + threadIdx.x;
+    const AgiIdLanes lanes{ids, ((size_t)ids & 7u) == 0};
+    const AgiLeafRows rows{leaves};
+    bool unknown = false;
+    if (i < n) {
+        u64 w[AgiIdLanes::WORDS];
+        dd_load(lanes, i, w);
+        const u64 fp = dd_fingerprint_of<AgiIdLanes>(w, k0, k1);
+        const u64 tag = fp >> 32;
+        u32 s = (u32)fp & mask, place = SSA_AGGV_UNKNOWN;
+#pragma unroll 1
+        for (u32 t = 0; t < bound; t++) {
+            const u64 cur = __hip_atomic_load(slots + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (cur == DD_EMPTY) break;
+            const u32 o = (u32)cur;
+            if ((cur >> 32) == tag && o < indexed && dd_same_key(rows, o, w)) {      // the bytes decide
+                place = o;
+                break;
+            }
+            s = (s + 1u) & mask;
+        }
+        places[i] = place;
+        unknown = place == SSA_AGGV_UNKNOWN;
+    }
+    const unsigned long long unknowns = __ballot(unknown);
+    if ((threadIdx.x & 63u) == 0 && unknowns) atomicAdd(n_unknown, (u32)__popcll(unknowns));
 }
 
 // The block-time hot path: one lane per held lane of a piece.  Lane i (place lane0 + i of the aggregate) derives its

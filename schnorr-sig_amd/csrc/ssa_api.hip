@@ -2816,12 +2816,14 @@ static int agx_bytes_words(size_t capacity, size_t block_lanes, uint32_t flags, 
     for (const AgxStore::Buf &b : agx_bufs(a)) {
         if (b.buf == &a.keys) k = 4;
         if (b.buf == &a.adm) k = 5;
+        if (b.buf == &a.index) k = 6;
         w[k++] = b.bytes;
     }
     return 0;
 }
 
-// (five words, as before the admission column existed: the flag is accepted, the column is not reported here)
+// (five words, as before the admission column and the leaf index existed: their flags are accepted, neither is reported
+// here)
 extern "C" int ssa_debug_aggregator_bytes(size_t capacity, size_t block_lanes, uint32_t flags, uint64_t out[5]) {
     uint64_t w[8];
     if (!out) return SSA_ERR_ARG;
@@ -2848,6 +2850,7 @@ extern "C" int ssa_aggregator_reset(ssa_aggregator *ag) {
     if (!ag || !ag->ctx) return SSA_ERR_ARG;
     ag->held = 0;
     ag->pushes = ag->offered = ag->dropped = ag->finishes = 0;
+    ag->index_void();        // (the leaf index: cleared by the next index_sync or look-up, not here)
     return 0;
 }
 
@@ -3195,6 +3198,7 @@ static int agx_remove_apply(ssa_aggregator *ag, const u32 *d_kept, size_t f, siz
         return p.count ? agx_reduce_blocks(*ag, AgxPlan{p.first, p.count, 0, 0}) : 0;
     }();
     ag->held = rc ? 0 : m;
+    ag->index_void();        // the lanes moved (or, after an error, left): the leaf index is rebuilt when it is next asked
     return rc;
 }
 
@@ -3377,6 +3381,183 @@ extern "C" int ssa_aggregator_remove_indices(ssa_ctx *ctx, ssa_aggregator *ag, c
     HostCall hc(ctx);
     const u32 *d_order = hc.in<u32>(ctx->agx_sel_order, order, m * sizeof(u32));
     return hc.finish([&] { return ssa_aggregator_remove_indices_device(ctx, ag, d_order, m, n_kept_out); });
+}
+
+// ---- the leaf column and the leaf index (the kernels and their arguments: agi_k_insert,
+// agi_k_lookup in ssa_aggregator.hpp)
+// Only enqueues: one device-to-device copy.  Changes no state of the object.  Every aggregator has the column.
+extern "C" int ssa_aggregator_leaves_device(ssa_ctx *ctx, ssa_aggregator *ag, size_t n_take, uint8_t *d_ids32_out) {
+    size_t n;
+    if (int rc = agx_take(ctx, ag, n_take, &n)) return rc;
+    if (n && !d_ids32_out) return SSA_ERR_ARG;
+    if (n == 0) return SSA_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipMemcpyAsync(d_ids32_out, ag->leaves.p, 32 * n, hipMemcpyDeviceToDevice, ctx->stream));
+    return SSA_OK;
+}
+
+extern "C" int ssa_aggregator_leaves(ssa_ctx *ctx, ssa_aggregator *ag, size_t n_take, uint8_t *ids32_out) {
+    size_t n;
+    if (int rc = agx_take(ctx, ag, n_take, &n)) return rc;
+    if (n && !ids32_out) return SSA_ERR_ARG;
+    if (n == 0) return SSA_OK;
+    HostCall hc(ctx);
+    u8 *d_ids = hc.out(ctx->st_aux, ids32_out, 32 * n, 16);
+    return hc.finish([&] { return ssa_aggregator_leaves_device(ctx, ag, n, d_ids); });
+}
+
+// what both forms of leaves_select refuse before anything is enqueued (a list may name a place twice, so m is bounded by
+// the batch limit, not by the lanes held)
+static int agx_leaves_select_args(const ssa_ctx *ctx, const ssa_aggregator *ag, const uint32_t *order, size_t m,
+                                  const uint8_t *ids32_out, bool device) {
+    if (!ctx || !ag || ag->ctx != ctx || m > SSA_MAX_BATCH || (m && (!order || !ids32_out))) return SSA_ERR_ARG;
+    return device && (reinterpret_cast<uintptr_t>(order) & 3u) ? SSA_ERR_ARG : 0;
+}
+
+// Only enqueues.  The gather goes into a workspace of the context (the caller's buffer may lie at any alignment), one
+// copy puts it out, and agx_k_select_verdict -- the verdict of finish_select -- zeroes the output of a list with an index
+// out of range and writes *d_result_out.
+extern "C" int ssa_aggregator_leaves_select_device(ssa_ctx *ctx, ssa_aggregator *ag, const uint32_t *d_order, size_t m,
+                                                   uint8_t *d_ids32_out, uint32_t *d_result_out) {
+    if (int rc = agx_leaves_select_args(ctx, ag, d_order, m, d_ids32_out, true)) return rc;
+    if (m && (!d_result_out || (reinterpret_cast<uintptr_t>(d_result_out) & 3u))) return SSA_ERR_ARG;
+    if (m == 0) return SSA_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (ctx->agx_sel_stage.reserve(32 * m) || ctx->agx_sel_bits.reserve(agx_sel_bytes(ag->held))) return SSA_ERR_HIP;
+    u32 *d_flag = agx_sel_word(ctx, AGX_SEL_FLAG);
+    u64 *d_stage = (u64 *)ctx->agx_sel_stage.p;
+    HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(u32), ctx->stream));
+    const int rc = timed_launch(ctx, "agx_k_leaves_select", [&] {
+        hipLaunchKernelGGL(agx_k_leaves_select, dim3(grid_for(m, 256)), dim3(256), 0, ctx->stream, d_order, m, ag->held, d_flag,
+                           (const u64 *)ag->leaves.p, d_stage);
+    });
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(d_ids32_out, d_stage, 32 * m, hipMemcpyDeviceToDevice, ctx->stream));
+    return timed_launch(ctx, "agx_k_select_verdict", [&] {
+        hipLaunchKernelGGL(agx_k_select_verdict, dim3(std::min(grid_for(32 * m, 256), 4096u)), dim3(256), 0, ctx->stream,
+                           (const u32 *)d_flag, d_ids32_out, 32 * m, (u8 *)nullptr, (size_t)0, d_result_out);
+    });
+}
+
+extern "C" int ssa_aggregator_leaves_select(ssa_ctx *ctx, ssa_aggregator *ag, const uint32_t *order, size_t m,
+                                            uint8_t *ids32_out) {
+    if (int rc = agx_leaves_select_args(ctx, ag, order, m, ids32_out, false)) return rc;
+    if (m == 0) return SSA_OK;
+    HostCall hc(ctx);
+    const u32 *d_order = hc.in<u32>(ctx->agx_sel_order, order, m * sizeof(u32));
+    u8 *d_ids = hc.out(ctx->st_aux, ids32_out, 32 * m, 16);
+    // (reserved here at the size the device form asks for: the result word does not move under it)
+    if (hc.ok() && ctx->agx_sel_bits.reserve(agx_sel_bytes(ag->held))) hc.rc = SSA_ERR_HIP;
+    if (!hc.ok()) return hc.rc;
+    u32 refused = 0, *d_result = agx_sel_word(ctx, AGX_SEL_RESULT);
+    hc.copy_back(&refused, d_result, sizeof refused);
+    if (int rc = hc.finish([&] { return ssa_aggregator_leaves_select_device(ctx, ag, d_order, m, d_ids, d_result); })) return rc;
+    return refused ? SSA_ERR_ARG : SSA_OK;
+}
+
+// what every call of the index refuses: an object without SSA_AGGR_HOLD_INDEX above all
+static int agi_args(const ssa_ctx *ctx, const ssa_aggregator *ag) {
+    return !ctx || !ag || ag->ctx != ctx || !ag->hold_index() ? SSA_ERR_ARG : 0;
+}
+
+// The index brought up to date with the lanes held (the arguments checked).  Only enqueues: a stale table is cleared --
+// the slots to all-ones, the counter behind them to zero: two memsets of one allocation -- and lanes [indexed, held) are
+// inserted by one launch.  The host state moves only when everything was enqueued.
+static int agi_sync(ssa_ctx *ctx, ssa_aggregator *ag) {
+    const size_t slots = ag->index_slots();
+    if (int rc = dedup_fingerprint_key(ctx)) return rc;      // (drawn at the first use by anyone: before any slot is picked)
+    if (ag->stale) {
+        HIP_TRY(hipMemsetAsync(ag->index_table(), 0xFF, 8 * slots, ctx->stream));
+        HIP_TRY(hipMemsetAsync(ag->index_over(), 0, 8, ctx->stream));
+        ag->stale = false;
+        ag->indexed = 0;
+        ag->rebuilds++;
+    }
+    if (ag->indexed < ag->held) {
+        const u32 lo = (u32)ag->indexed, hi = (u32)ag->held;
+        const int rc = timed_launch(ctx, "agi_k_insert", [&] {
+            hipLaunchKernelGGL(agi_k_insert, dim3(grid_for(hi - lo, DD_BLOCK)), dim3(DD_BLOCK), 0, ctx->stream,
+                               (const u64 *)ag->leaves.p, lo, hi, ctx->dedup_key[0], ctx->dedup_key[1], ag->index_table(),
+                               (u32)(slots - 1), (u32)ctx->knobs.dedup_probe_bound, ag->index_over());
+        });
+        if (rc) {
+            ag->index_void();
+            return rc;
+        }
+        ag->indexed = ag->held;
+    }
+    return SSA_OK;
+}
+
+extern "C" int ssa_aggregator_index_sync(ssa_ctx *ctx, ssa_aggregator *ag) {
+    if (int rc = agi_args(ctx, ag)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    return agi_sync(ctx, ag);
+}
+
+static int agi_lookup_args(const ssa_ctx *ctx, const ssa_aggregator *ag, const uint8_t *ids32, size_t n,
+                           const uint32_t *places_out, const void *n_unknown_out, bool device) {
+    if (int rc = agi_args(ctx, ag)) return rc;
+    if (!n_unknown_out || n > SSA_MAX_BATCH || (n && (!ids32 || !places_out))) return SSA_ERR_ARG;
+    return device && ((reinterpret_cast<uintptr_t>(places_out) | reinterpret_cast<uintptr_t>(n_unknown_out)) & 3u) ? SSA_ERR_ARG
+                                                                                                                    : 0;
+}
+
+// Only enqueues on the context's stream: the index is brought up to date (agi_sync), the count word is cleared, and one
+// launch answers the n ids.  n == 0 launches nothing and leaves the index as it is.
+extern "C" int ssa_aggregator_lookup_device(ssa_ctx *ctx, ssa_aggregator *ag, const uint8_t *d_ids32, size_t n,
+                                            uint32_t *d_places_out, uint32_t *d_n_unknown_out) {
+    if (int rc = agi_lookup_args(ctx, ag, d_ids32, n, d_places_out, d_n_unknown_out, true)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipMemsetAsync(d_n_unknown_out, 0, sizeof(uint32_t), ctx->stream));
+    if (n == 0) return SSA_OK;
+    if (int rc = agi_sync(ctx, ag)) return rc;
+    ag->lookups++;
+    ag->looked_up += n;
+    return timed_launch(ctx, "agi_k_lookup", [&] {
+        hipLaunchKernelGGL(agi_k_lookup, dim3(grid_for(n, DD_BLOCK)), dim3(DD_BLOCK), 0, ctx->stream, d_ids32, (u32)n,
+                           (const u64 *)ag->leaves.p, (u32)ag->indexed, ctx->dedup_key[0], ctx->dedup_key[1],
+                           (const u64 *)ag->index_table(), (u32)(ag->index_slots() - 1), (u32)ctx->knobs.dedup_probe_bound,
+                           d_places_out, d_n_unknown_out);
+    });
+}
+
+// The count word travels behind the places in one workspace and comes back with them under the one synchronisation.
+extern "C" int ssa_aggregator_lookup(ssa_ctx *ctx, ssa_aggregator *ag, const uint8_t *ids32, size_t n, uint32_t *places_out,
+                                     uint64_t *n_unknown_out) {
+    if (int rc = agi_lookup_args(ctx, ag, ids32, n, places_out, n_unknown_out, false)) return rc;
+    *n_unknown_out = 0;
+    if (n == 0) return SSA_OK;
+    HostCall hc(ctx);
+    const u8 *d_ids = hc.in(ctx->st_sigs, ids32, 32 * n);
+    u8 *d_places = hc.out(ctx->st_aux, places_out, 4 * n, 16);
+    if (!hc.ok()) return hc.rc;
+    u32 unknown = 0, *d_unknown = (u32 *)(d_places + 4 * n);
+    hc.copy_back(&unknown, d_unknown, sizeof unknown);
+    if (int rc = hc.finish([&] { return ssa_aggregator_lookup_device(ctx, ag, d_ids, n, (u32 *)d_places, d_unknown); })) return rc;
+    *n_unknown_out = unknown;
+    return SSA_OK;
+}
+
+// Synchronises the context's stream once: word [4] is a counter on the device.
+extern "C" int ssa_aggregator_index_info(ssa_ctx *ctx, ssa_aggregator *ag, uint64_t out[8]) {
+    if (int rc = agi_args(ctx, ag)) return rc;
+    if (!out) return SSA_ERR_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    unsigned long long over = 0;
+    if (!ag->stale) {        // (a stale table's counter is cleared with it, before anything counts again)
+        HIP_TRY(hipMemcpyAsync(&over, ag->index_over(), sizeof over, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    out[0] = ag->index_slots();
+    out[1] = ag->indexed;
+    out[2] = ag->stale ? 1 : 0;
+    out[3] = ag->rebuilds;
+    out[4] = over;
+    out[5] = ag->lookups;
+    out[6] = ag->looked_up;
+    out[7] = 0;
+    return SSA_OK;
 }
 
 // ------------------------------------------------------------------ streaming aggregate verifier (ssa_aggverifier.hpp)

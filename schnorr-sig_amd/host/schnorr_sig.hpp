@@ -891,12 +891,23 @@ class Aggregator {
     // HoldKeys (SSA_AGGR_HOLD_KEYS49): the object also holds the 49 wire bytes of every admitted lane's key, for keys();
     // it then takes push_keyed alone.  HoldAdmission (SSA_AGGR_HOLD_ADMISSION): the object also
     // records the class of the push that admitted each lane, for admission() and for the KeyCache overloads of
-    // AggregateVerifier::push_mixed.
+    // AggregateVerifier::push_mixed.  HoldIndex (SSA_AGGR_HOLD_INDEX): the object also holds a leaf
+    // index, for lookup().  The options combine with | (below).
     enum Options : uint32_t {
         None = 0u,
         HoldKeys = SSA_AGGR_HOLD_KEYS49,
         HoldAdmission = SSA_AGGR_HOLD_ADMISSION,
-        HoldKeysAndAdmission = SSA_AGGR_HOLD_KEYS49 | SSA_AGGR_HOLD_ADMISSION
+        HoldKeysAndAdmission = SSA_AGGR_HOLD_KEYS49 | SSA_AGGR_HOLD_ADMISSION,
+        HoldIndex = SSA_AGGR_HOLD_INDEX
+    };
+    friend constexpr Options operator|(Options a, Options b) { return (Options)((uint32_t)a | (uint32_t)b); }
+    // the words of index_info(), and what lookup() returns
+    struct IndexInfo {
+        uint64_t slots, indexed, stale, rebuilds, overflowed, lookups, ids, reserved;
+    };
+    struct Lookup {
+        std::vector<uint32_t> places;      // the lowest place that holds the id, or SSA_AGGV_UNKNOWN
+        uint64_t n_unknown;
     };
     // how a lane was admitted: by push(screen = false), by the plain screened push, or through a key cache
     enum class Admission : uint8_t {
@@ -1007,6 +1018,49 @@ class Aggregator {
         if (rc != 0) throw std::runtime_error(std::string("ssa_aggregator_admission: ") + ssa_strerror(rc));
         out.resize(n);
         return out;
+    }
+    // ---- the leaf column and the leaf index.  A lane's 32-byte leaf is its id.
+    // the leaves of the first n_take held triples, 32 bytes each, in arrival order (every object has them)
+    std::vector<uint8_t> leaves(size_t n_take = All) const {
+        const size_t n = n_take == All ? (size_t)info().held : n_take;
+        std::vector<uint8_t> out(32 * n + 1, 0);
+        const int rc = ssa_aggregator_leaves(cx_.get(), ag_, n, out.data());
+        if (rc != 0) throw std::runtime_error(std::string("ssa_aggregator_leaves: ") + ssa_strerror(rc));
+        out.resize(32 * n);
+        return out;
+    }
+    // the leaves at the places order[0], order[1], ... in that order: the id column beside finish_select(order).  An index
+    // that is not below the triples held throws.
+    std::vector<uint8_t> leaves_select(const std::vector<uint32_t> &order) const {
+        const size_t m = order.size();
+        std::vector<uint8_t> out(32 * m + 1, 0);
+        const int rc = ssa_aggregator_leaves_select(cx_.get(), ag_, m ? order.data() : nullptr, m, out.data());
+        if (rc != 0) throw std::runtime_error(std::string("ssa_aggregator_leaves_select: ") + ssa_strerror(rc));
+        out.resize(32 * m);
+        return out;
+    }
+    // brings the index up to date with the triples held (only enqueues; a lookup does the same in front of its query)
+    void index_sync() {
+        const int rc = ssa_aggregator_index_sync(cx_.get(), ag_);
+        if (rc != 0) throw std::runtime_error(std::string("ssa_aggregator_index_sync: ") + ssa_strerror(rc));
+    }
+    // ids32: n ids side by side, 32 bytes each -> for each the lowest place that holds it, or SSA_AGGV_UNKNOWN, and the
+    // number of the latter: what AggregateVerifier::push_mixed takes.  An object made without HoldIndex throws.
+    Lookup lookup(const std::vector<uint8_t> &ids32) {
+        if (ids32.size() % 32) throw std::invalid_argument("ids are 32 bytes each");
+        const size_t n = ids32.size() / 32;
+        Lookup r{std::vector<uint32_t>(n + 1, SSA_AGGV_UNKNOWN), 0};
+        const int rc = ssa_aggregator_lookup(cx_.get(), ag_, n ? ids32.data() : nullptr, n, r.places.data(), &r.n_unknown);
+        if (rc != 0) throw std::runtime_error(std::string("ssa_aggregator_lookup: ") + ssa_strerror(rc));
+        r.places.resize(n);
+        return r;
+    }
+    // synchronises the context's stream once (the overflow counter lives on the device)
+    IndexInfo index_info() const {
+        uint64_t w[8] = {0};
+        const int rc = ssa_aggregator_index_info(cx_.get(), ag_, w);
+        if (rc != 0) throw std::runtime_error(std::string("ssa_aggregator_index_info: ") + ssa_strerror(rc));
+        return IndexInfo{w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7]};
     }
     AggregateSignature finish(size_t n_take = All) const {
         const size_t n = n_take == All ? (size_t)info().held : n_take;
