@@ -26,32 +26,44 @@ def _step(family, variant, n, seed_shift=0):
 
 
 def _plans():
-    """per thread, three rounds of steps; every round of every thread mixes families"""
+    """per thread, three rounds of steps; every round of every thread mixes families, the aggregate side among them"""
     sl = cs.SLICED
+    new = [s for s in sl[14:] if cs.slicing(s) is True]
+    lanes = [s for s in sl[14:] if cs.slicing(s) == "lanes"]
+    assert len(new) == 5 and len(lanes) == 3
+    alt = cs.N_OF
     return [
-        # 0: a 16-bit comb for G; a cold cache insert, the constant-time table build, a key-set build, self-checks
+        # 0: a 16-bit comb for G; a cold cache insert, the constant-time table build, a key-set build, self-checks; the
+        #    aggregate validator and the streaming aggregator walk that comb
         [[_step("verify_many_cached", "T.c32.host", 3073), _step("verify_many", "auto.T.host", 10496),
-          _step("selfcheck", "ctx", 0)],
+          _step("selfcheck", "ctx", 0), _step("verify_aggregate", "honest.host", 3073), _step("aggregator", "screened", 257)],
          [_step("verify_many_indexed", "ladder.T.host", 63), _step("keygen_sign_many", "ct", 63),
-          _step("verify_batch_screened", "c32.host", 20000)],
+          _step("verify_batch_screened", "c32.host", 20000), _step("verify_aggregate", "mid.dev", 257),
+          _step("aggregator", "index.admission", 1500)],
          [_step("selfcheck", "keyset", 0), _step("verify_batch_msm", "c32.host.bad", 3073),
-          _step("verify_many_screened", "T.c32.host", 20000)]],
-        # 1: 5000-lane slices: every call runs over three of them, on the context and its twin
-        [sl[0:5], sl[5:10], sl[10:14]],
+          _step("verify_many_screened", "T.c32.host", 20000), _step("verify_aggregate", "last.dev", 20000),
+          _step("aggregator", "cached", 1500)]],
+        # 1: 5000-lane slices: every call runs over three of them, on the context and its twin (the new sliced steps but
+        #    those of callscript.LANE_SLICED, which this engine refuses: thread 3 has them)
+        [sl[0:5] + new[0:2], sl[5:10] + new[2:4], sl[10:14] + new[4:5]],
         # 2: another parameter blob (its own sponge layout): nothing of it may leak into the other contexts
         [[_step("verify_many", "auto.N.host", 7680, ALT_SEED), _step("hash_message_many", "len7", 257, ALT_SEED),
-          _step("keygen_sign_many", "ct.keyed", 1000, ALT_SEED)],
+          _step("keygen_sign_many", "ct.keyed", 1000, ALT_SEED), _step("aggregate", "check.host.honest", 513, ALT_SEED),
+          _step("aggregate", "check.dev.bad", 257, ALT_SEED)],
          [_step("verify_many_dedup", "T.host", 257, ALT_SEED), _step("verify_keyed_many", "T.host", 10497, ALT_SEED),
-          _step("selfcheck", "ctx", 0, ALT_SEED)],
+          _step("selfcheck", "ctx", 0, ALT_SEED), _step("verify_aggregates", "edges.host", alt["edges"], ALT_SEED),
+          _step("verify_aggregates", "many.dev", alt["many"], ALT_SEED)],
          [_step("verify_many_cached", "T.c32.host", 3073, ALT_SEED), _step("rescue_hash_many", "w8", 257, ALT_SEED),
-          _step("sign_many_indexed", "ct.keyed", 257, ALT_SEED)]],
-        # 3: its engine, key cache and signer set are closed and made again between the rounds
+          _step("sign_many_indexed", "ct.keyed", 257, ALT_SEED), _step("aggverifier", "wire", 1500, ALT_SEED)]],
+        # 3: its engine, key cache and signer set are closed and made again between the rounds; the first engine has
+        #    5000-lane lane slices, and the first round holds the sliced steps that need them
         [[_step("verify_keyed_many_cached", "T.c32.host", 3073), _step("sign_many_indexed", "tp", 63),
-          _step("xprv_derive_many", "priv", 257)],
+          _step("xprv_derive_many", "priv", 257), _step("aggregate_valid_keyed_cached", "host", 257)] + lanes,
          [_step("verify_many_cached", "N.c32.host", 257), _step("rng_signers", "indexed.ct", 257),
-          _step("verify_many", "coop.TF.host", 1000), _step("selfcheck", "cache", 0)],
+          _step("verify_many", "coop.TF.host", 1000), _step("selfcheck", "cache", 0),
+          _step("aggregator", "index.admission", 1500)],
          [_step("verify_many", "auto.T.dev", 10497), _step("msm_partial", "c32.host", 4095),
-          _step("verify_many_indexed", "ladder.N.dev", 257)]],
+          _step("verify_many_indexed", "ladder.N.dev", 257), _step("aggverifier", "mixed.wire.require2", 257)]],
     ]
 
 
@@ -67,20 +79,22 @@ def _engines(blob):
     """the four engines of one phase, made by the main thread: the environment is changed and restored here, before any
     thread runs (the library reads it with getenv when a context is created)"""
     import schnorr_sig_amd as ssa
-    engs = [ssa.Engine(0, gtab_bits=16)]
-    old = {k: os.environ.get(k) for k in ("SSA_LANE_SLICE", "SSA_MSM_SLICE")}
-    os.environ.update({k: str(cs.SLICE) for k in old})
-    try:
-        engs.append(ssa.Engine(0))
-    finally:
-        for k, v in old.items():
-            if v is None:
-                del os.environ[k]
-            else:
-                os.environ[k] = v
-    engs.append(ssa.Engine(0, params=blob))
-    engs.append(ssa.Engine(0))
-    return engs
+
+    def cut(*names):
+        old = {k: os.environ.get(k) for k in names}
+        os.environ.update({k: str(cs.SLICE) for k in old})
+        try:
+            return ssa.Engine(0)
+        finally:
+            for k, v in old.items():
+                if v is None:
+                    del os.environ[k]
+                else:
+                    os.environ[k] = v
+    # (3: the engine of its first round has 5000-lane LANE slices, for the steps of callscript.LANE_SLICED; the engines
+    #  the thread makes for its later rounds are plain ones)
+    return [ssa.Engine(0, gtab_bits=16), cut("SSA_LANE_SLICE", "SSA_MSM_SLICE"), ssa.Engine(0, params=blob),
+            cut("SSA_LANE_SLICE")]
 
 
 def _orphans_are_refused():
